@@ -16,8 +16,13 @@ With `--gpus N > 1` the ONE launch (one process group) answers both multi-GPU qu
 `extra.sharded_c5` = the strong-scaling form run right behind it by the same ranks (per-rank codec ms, spread, gather ms and
 bytes); `rccl` names the backend, world size and devices the collectives ran on.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.  The line is kept short
-enough for the driver's log tail (numbers rounded to 5 significant digits, `extra` entries under short keys: `extra_legend`);
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 (value, ms_per_step, kernel_ms and the
+`roofline` derived from the timed steps).  `--full` adds what takes runs or checks of its own: the per-list round-trip check
+(`verified_roundtrip`), the secondary workloads and codecs under `extra` (with N > 1 GPUs: `extra.sharded_c5*`), the chain floor
+and issue bound under `roofline`, and the CPU codec timed on this host (`cpu_baseline`); the `--no-*` switches skip parts of it.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs) for output-by-output comparison of two builds.
+The line is kept short enough for the driver's log tail (numbers rounded to 5 significant digits, `extra` entries under
+short keys: `extra_legend`);
 the unabridged measurements go to gpurun_out/bench_detail.json.
 
 `--dry-run` (tests/test_bench_cpu.py, no GPU): the same control flow, process group (gloo) and line assembly with a
@@ -192,6 +197,41 @@ def committed_issue(tag, kernel_ms):
         return out
     except Exception:
         return None
+
+
+DUMP_CAP = 1_000_000  # elements per dumped array: 8 MB as float64, four arrays at most -> 32 MB in all
+
+
+def dump_outputs(path, r, out, ntotal, want_perm):
+    """`--dump-outputs`: what the last timed step handed its caller, as float64 .npy files under `path`.  Every codec:
+    `decoded_ids` (ROC: each list in its sampling order) and `compressed_bytes`; ROC adds the streams (`words`, all lists back to
+    back), the sampling permutation (`perm`, when encoded) and `lists` = one row per list [head >> 32, head & 0xffffffff,
+    nwords, precision, mt_draws].  float64 holds every value exactly (ids < 2^53, the 64-bit heads split in halves).  An
+    array longer than DUMP_CAP (rows for `lists`) is replaced by a fixed sample: the same seeded positions for the same length."""
+    import torch
+
+    def sample(a, cap):
+        n = a.shape[0]
+        if n <= cap:
+            return a
+        idx = np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))
+        return a[torch.from_numpy(idx).to(a.device)] if torch.is_tensor(a) else a[idx]
+
+    arrays = {"decoded_ids": sample(out[:ntotal], DUMP_CAP), "compressed_bytes": np.array([r.compressed_bytes])}
+    if hasattr(r, "all_words"):  # ROC
+        info = r.info()
+        heads = info["heads"].astype(np.uint64)
+        arrays["lists"] = sample(np.stack([heads >> np.uint64(32), heads & np.uint64(0xFFFFFFFF), info["nwords"],
+                                           info["precision"], info["mt_draws"]], axis=1).astype(np.uint64), DUMP_CAP // 5)
+        arrays["words"] = sample(r.all_words(), DUMP_CAP)
+        if want_perm:
+            arrays["perm"] = sample(r.perm(), DUMP_CAP)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.size and int(a.max()) >= 1 << 53:
+            raise ValueError(f"--dump-outputs: {name} holds values float64 cannot represent exactly")
+        np.save(os.path.join(path, f"{name}.npy"), a.astype(np.float64))
 
 
 def per_list_multisets_equal(offsets, got, want, chunk=1 << 27):
@@ -403,7 +443,16 @@ def main():
     ap.add_argument("--sharded-workload", default="c5", help="the ONE index of extra.sharded_c5 (a synth.workload name)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU (tests): gloo, cpu tensors, a pass-through stand-in for the codec; prints value null")
+    ap.add_argument("--full", action="store_true",
+                    help="also the round-trip check, the secondary measurements (`extra`, chain floor, issue bound) and the CPU "
+                         "baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.sharded:
+        ap.error("--dump-outputs writes the outputs of the weak-scaling steps; --sharded has none")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, RCCL), exactly the
@@ -485,7 +534,7 @@ def main():
         r, _, _ = step()
     # correctness gate inside the bench: every list must come back as the same set of ids
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verified = per_list_multisets_equal(offsets, out, d_ids)
 
     if dist is not None:
@@ -508,6 +557,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, out, ntotal, want_perm and args.codec == "roc")
     if verified is not None:  # the output of the LAST timed step too (outside the timed region)
         verified = verified and (per_list_multisets_equal(offsets, out, d_ids) if args.codec == "roc" else bool(torch.equal(out, d_ids)))
 
@@ -745,7 +796,7 @@ def main():
 
     # one launch answers both multi-GPU questions: behind the weak steps the SAME ranks shard ONE index (strong form)
     sharded = sharded_ef = None
-    if world > 1 and not args.no_sharded_extra and args.codec == "roc":
+    if world > 1 and args.full and not args.no_sharded_extra and args.codec == "roc":
         try:
             sharded = sharded_measure(args, ctx, dist, rank, world, steps=min(args.steps, 5), warmup=1,
                                       workload=args.sharded_workload, device=device)
@@ -800,7 +851,7 @@ def main():
         full = None  # the unabridged secondary measurements (detail file)
         if dominant is not None:
             res["roofline"]["dominant_kernel"] = dominant
-        if world == 1 and not args.no_extra and args.codec == "roc" and args.workload == "s1" and not dry:
+        if world == 1 and args.full and not args.no_extra and args.codec == "roc" and args.workload == "s1" and not dry:
             # other regimes of the same kernels, for context only (never part of `value`): many equal lists
             # (no long serial chain) and the two bandwidth-bound codecs of the same plugin surface
             full = {}
@@ -845,7 +896,7 @@ def main():
                     "steps": shd["steps"], "per_rank": shd["per_rank"], "gather_bytes": shd["gather_bytes"],
                     "gather_lists": shd["gather_lists"], "gather_verified": shd["gather_verified"], "scaling": "strong",
                     "strong_bound": shd["strong_bound"]})
-        if world == 1 and args.codec == "roc" and not args.no_extra and not dry:
+        if world == 1 and args.full and args.codec == "roc" and not args.no_extra and not dry:
             try:
                 cf = chain_floor(wl, d_ids)
                 cf["chain_floor_ms"] = cf["encode_ms"] + cf["decode_ms"]
@@ -856,7 +907,7 @@ def main():
                 res["roofline"]["note"] = "latency bound: the batch cannot finish before its longest list's chain of dependent codec steps (chain_floor)"
             except Exception as e:
                 res["roofline"]["chain_floor"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline and args.codec == "roc" and ids_host is not None and not dry:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.codec == "roc" and ids_host is not None and not dry:
             try:
                 res["cpu_baseline"] = cpu_baseline(offsets, ids_host)
             except Exception as e:  # the checker libraries are optional at bench time

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/roc_golden.json from the REFERENCE codec (oracle/_ref).
+"""Generate tests/golden/roc_golden.json and tests/golden/roc_ref_random.json from the REFERENCE codec (oracle/_ref).
 
 Run in the build container (needs /root/reference to build oracle/_ref/libvidc_ref.so):
     python tests/golden/make_golden.py
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from golden_cases import CASES, fnv_stream, fnv_u64, make_ids  # noqa: E402
+from golden_cases import CASES, fnv_stream, fnv_u64, make_ids, ref_random_inputs  # noqa: E402
 from oracle.pyoracle import Oracle, Ref  # noqa: E402
 
 FULL_LIMIT = 96  # store complete vectors up to this n
@@ -56,6 +56,25 @@ def main():
         print(f"{case['name']:40s} n={n:6d} P={prec:2d} head={rec['head']} words={rec['nwords']} "
               f"set_ok={rec['roundtrip_set_ok']}")
     path = os.path.join(ROOT, "tests", "golden", "roc_golden.json")
+    with open(path, "w") as f:
+        json.dump(dict(source="reference codec.cpp via oracle/_ref (oracle/ref_driver.cpp)", cases=out), f, indent=0)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    main_random(ref, orc)
+
+
+def main_random(ref, orc):
+    """roc_ref_random.json: the reference's container encode (stream, order, permutation) and its decode of that stream, for
+    the inputs of golden_cases.ref_random_inputs (precision by the container rule, as in main())."""
+    out = []
+    for t, ids in ref_random_inputs():
+        n, prec = int(ids.size), orc.list_precision(ids)
+        c = ref.container_encode(ids, prec, shuffle_seed=t)
+        dec, end_head, end_words = ref.decompress(c["head"], c["words"], n, prec)
+        out.append(dict(t=t, n=n, precision=int(prec), ids_fnv=fnv_u64(ids), head=int(c["head"]), nwords=int(c["words"].size),
+                        stream_fnv=fnv_stream(c["head"], c["words"]), order_fnv=fnv_u64(c["order"]),
+                        perm_fnv=fnv_u64(c["perm"].astype(np.uint64)), decoded_fnv=fnv_u64(dec), end_head=int(end_head),
+                        end_stream_fnv=fnv_stream(end_head, end_words)))
+    path = os.path.join(ROOT, "tests", "golden", "roc_ref_random.json")
     with open(path, "w") as f:
         json.dump(dict(source="reference codec.cpp via oracle/_ref (oracle/ref_driver.cpp)", cases=out), f, indent=0)
     print("wrote", path, os.path.getsize(path), "bytes")

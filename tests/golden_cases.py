@@ -121,6 +121,19 @@ def make_ids(case):
     raise ValueError(kind)
 
 
+def ref_random_inputs(count=120, seed=123):
+    """Inputs of the random oracle-vs-reference cases (expected outputs: tests/golden/roc_ref_random.json): case t holds up
+    to 1500 distinct ids of a random P-bit universe in random order; the reference's container encode of case t uses shuffle
+    seed t."""
+    rng = np.random.default_rng(seed)
+    for t in range(count):
+        P = int(rng.integers(1, 32))
+        n = int(rng.integers(1, min(1500, 2**P) + 1))
+        ids = np.unique(rng.integers(0, 2**P, size=n, dtype=np.uint64))
+        rng.shuffle(ids)
+        yield t, ids
+
+
 def _c(name, gen, **kw):
     d = dict(name=name, gen=gen)
     d.update(kw)

@@ -723,8 +723,8 @@ def test_bench_gpus_flag_launches_the_ranks_itself(tmp_path):
                            capture_output=True, text=True, timeout=600, env=env, cwd=root)
         assert r.returncode != 0 and "only 1 GPU" in (r.stdout + r.stderr)
         return
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extra",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["verified_roundtrip"] is True

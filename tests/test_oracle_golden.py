@@ -1,9 +1,12 @@
 """CPU: the clean-room oracle (oracle/vidc_oracle.c) against the reference-generated golden vectors,
 and against the compiled reference itself when oracle/_ref is available."""
+import json
+import os
+
 import numpy as np
 import pytest
 
-from golden_cases import CASES, fnv_stream, fnv_u64, make_ids
+from golden_cases import CASES, fnv_stream, fnv_u64, make_ids, ref_random_inputs
 
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 
@@ -76,20 +79,27 @@ def test_oracle_matches_golden(oracle, golden, name):
 
 
 def test_oracle_vs_compiled_reference_random():
+    """120 random lists: the oracle's stream, order, permutation and decode against the reference's, as recorded in
+    tests/golden/roc_ref_random.json (make_golden.py), and against the compiled reference itself when oracle/_ref is built."""
     from oracle.pyoracle import Oracle, Ref
 
-    if not Ref.available():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    o, r = Oracle(), Ref()
-    rng = np.random.default_rng(123)
-    for t in range(120):
-        P = int(rng.integers(1, 32))
-        n = int(rng.integers(1, min(1500, 2**P) + 1))
-        ids = np.unique(rng.integers(0, 2**P, size=n, dtype=np.uint64))
-        rng.shuffle(ids)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "roc_ref_random.json")) as f:
+        recorded = json.load(f)["cases"]
+    o = Oracle()
+    r = Ref() if Ref.available() else None
+    assert len(recorded) == 120
+    for (t, ids), g in zip(ref_random_inputs(), recorded):
         n = ids.size
+        assert g["t"] == t and g["n"] == n and fnv_u64(ids) == g["ids_fnv"]  # the inputs the fixture was recorded for
         prec = o.list_precision(ids)
+        assert prec == g["precision"]
         a = o.roc_encode(ids, prec)
+        assert a["head"] == g["head"] and a["words"].size == g["nwords"] and fnv_stream(a["head"], a["words"]) == g["stream_fnv"]
+        assert fnv_u64(a["order"]) == g["order_fnv"] and fnv_u64(a["perm"].astype(np.uint64)) == g["perm_fnv"]
+        d = o.roc_decode(a["head"], a["words"], n, prec, a["mt_draws"])
+        assert fnv_u64(d[0]) == g["decoded_fnv"] and d[1] == g["end_head"] and fnv_stream(d[1], d[2]) == g["end_stream_fnv"]
+        if r is None:
+            continue
         c = r.container_encode(ids, prec, shuffle_seed=t)
         assert a["head"] == c["head"] and np.array_equal(a["words"], c["words"])
         assert np.array_equal(a["order"], c["order"]) and np.array_equal(a["perm"], c["perm"])

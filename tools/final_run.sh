@@ -3,6 +3,7 @@ set -x
 cd $GRAFT_REPO_ROOT
 R=${1:-r01e}
 mkdir -p gpurun_out/$R
+S=$_  # the directory just made: the bench lines below write there
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -5 > gpurun_out/$R/pytest_gpu.txt
 VIDC_FORCE_GENERAL=1 timeout 900 python -m pytest tests/test_gpu_roc.py tests/test_gpu_containers.py -m gpu -q 2>&1 | tail -3 > gpurun_out/$R/pytest_force_general.txt
 VIDC_NO_LANE=1 timeout 900 python -m pytest tests/test_gpu_roc.py tests/test_gpu_containers.py -m gpu -q 2>&1 | tail -3 > gpurun_out/$R/pytest_no_lane.txt
@@ -35,12 +36,12 @@ timeout 300 python tools/fuzz_graph_roc.py 31 40 2>&1 | tail -1 > gpurun_out/$R/
 timeout 300 python tools/fuzz_wt.py 31 30 2>&1 | tail -1 > gpurun_out/$R/fuzz_wt.txt
 timeout 300 python tools/bench_wt.py 2>&1 | tail -4 > gpurun_out/$R/bench_wt.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/$R/smoke.txt 2>&1
-timeout 600 python bench.py > gpurun_out/$R/bench.json 2> gpurun_out/$R/bench.err
+timeout 600 python bench.py --full > "$S/bench.json" 2> "$S/bench.err"
 for w in s1_uniform uniform_16m uniform_64m_1k c5 s2_64m; do
-  timeout 900 python bench.py --workload $w --no-cpu-baseline --no-extra --steps 5 --warmup 2 2>/dev/null >> gpurun_out/$R/bench_other.jsonl
+  timeout 900 python bench.py --workload $w --full --no-cpu-baseline --no-extra --steps 5 --warmup 2 2>/dev/null >> "$S/bench_other.jsonl"
 done
 for c in packed ef; do for w in s1 uniform_16m uniform_64m_1k; do
-  timeout 600 python bench.py --workload $w --codec $c --no-cpu-baseline --no-extra --steps 10 --warmup 3 2>/dev/null >> gpurun_out/$R/bench_other.jsonl
+  timeout 600 python bench.py --workload $w --codec $c --full --no-cpu-baseline --no-extra --steps 10 --warmup 3 2>/dev/null >> "$S/bench_other.jsonl"
 done; done
 # round 6: BASELINE configs[3] evidence (line, rocprofv3 kernel stats, FETCH_SIZE / WRITE_SIZE per kernel) + issue / wait counters per kernel
 bash tools/prof_graph.sh $R > gpurun_out/$R/prof_graph.log 2>&1
