@@ -6,7 +6,8 @@
  * torch or C++ types cross this boundary.  Every entry point names the reference
  * interface it replaces (file:line under /root/reference).
  *
- * Data model: a set of lists is a CSR pair  offsets[nlist+1] (host, uint64) + ids[ntotal].
+ * Data model: a set of lists is a CSR pair  offsets[nlist+1] (host, uint64) + ids[ntotal].  The *_encode_dev /
+ * vidc_wt_build_dev entry points take the offsets as a DEVICE array instead (lists built on the GPU).
  * IDs are faiss::idx_t viewed as uint64 (custom_invlists_impl.cpp:79,159,217,248) or int32
  * graph rows (altid_impl.cpp:26-37).  "dev" pointers are HIP device pointers valid on the
  * context's device; everything else is host memory.  Out-buffers are caller-allocated.
@@ -107,6 +108,10 @@ typedef struct vidc_roc vidc_roc;
 #define VIDC_ROC_MAX_LIST 262144u
 int vidc_roc_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids,
                     int precision_mode, uint32_t flags, vidc_roc **out);
+/* device offsets: see vidc_packed_encode_dev.  The call copies d_offsets to the host once and runs vidc_roc_encode's planner
+ * on that copy: an O(nlist) D2H copy and host pass (ROC is bound by its ANS chains, not by this copy). */
+int vidc_roc_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal,
+                        const uint64_t *d_ids, int precision_mode, uint32_t flags, vidc_roc **out);
 /* Graph rows: d_rows device int32[N*K], -1 terminated rows (altid_impl.cpp:110-117). */
 int vidc_roc_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, int precision_mode,
                          uint32_t flags, vidc_roc **out);
@@ -164,6 +169,18 @@ typedef struct vidc_packed vidc_packed;
 int vidc_packed_bits_for(uint64_t ntotal); /* :68-70 */
 int vidc_packed_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, int bits,
                        vidc_packed **out);
+/* Device offsets: d_offsets is a DEVICE uint64[nlist+1] on the context's device, read in order on the context's stream (the
+ * caller orders its producer before the call, e.g. by running the context on torch's stream).  ntotal: the caller's id count
+ * (= d_offsets[nlist], checked on the device, as are d_offsets[0] == 0 and monotone offsets: VIDC_ERR_INVALID naming the first
+ * bad list).  The object keeps its own copy, so d_offsets may be freed or reused after the call returns.  Objects are the same
+ * as the host-offsets calls produce, word for word.  Packed and wavelet tree: no O(nlist) host work or PCIe transfer, and no wait
+ * beyond those of the host-offsets call.
+ * Elias-Fano: the same; its chunk kernels read their count and form on the device (a list that is not ascending copies the
+ * offsets to the host once, as the retry of the host path re-walks them; ids >= 2^32 take the host path's extra wait).  ROC: the length classes are planned on the host, so the offsets cross PCIe once (D2H). */
+int vidc_packed_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal,
+                           const uint64_t *d_ids, int bits, vidc_packed **out);
+/* host copy of the object's offsets[nlist+1] (objects from device offsets copy them from the device on first use) */
+int vidc_packed_offsets(vidc_ctx *ctx, const vidc_packed *p, uint64_t *offsets);
 void vidc_packed_destroy(vidc_packed *p);
 uint64_t vidc_packed_compressed_bytes(const vidc_packed *p); /* sum ceil(ls*bits/8), :80,85 */
 int vidc_packed_bits(const vidc_packed *p);
@@ -209,6 +226,9 @@ typedef struct vidc_ef vidc_ef;
 #define VIDC_EF_WANT_PERM 1u
 int vidc_ef_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, uint32_t flags,
                    vidc_ef **out);
+/* device offsets: see vidc_packed_encode_dev */
+int vidc_ef_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal,
+                       const uint64_t *d_ids, uint32_t flags, vidc_ef **out);
 void vidc_ef_destroy(vidc_ef *e);
 /* (sum low bits + sum high bits) / 8, custom_invlists_impl.cpp:272-282 */
 uint64_t vidc_ef_compressed_bytes(const vidc_ef *e);
@@ -249,6 +269,10 @@ int vidc_ef_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
 typedef struct vidc_wt vidc_wt;
 int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, int wt_type,
                   vidc_wt **out);
+/* device offsets: see vidc_packed_encode_dev */
+int vidc_wt_build_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal,
+                      const uint64_t *d_ids, int wt_type, vidc_wt **out);
+int vidc_wt_offsets(vidc_ctx *ctx, const vidc_wt *w, uint64_t *offsets); /* see vidc_packed_offsets */
 void vidc_wt_destroy(vidc_wt *w);
 uint64_t vidc_wt_size_in_bytes(const vidc_wt *w);
 uint32_t vidc_wt_levels(const vidc_wt *w);

@@ -57,6 +57,7 @@ def _declare(lib):
     f("vidc_ctx_chain_info", C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp)
     # ROC
     f("vidc_roc_encode", C.c_int, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp))
+    f("vidc_roc_encode_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, C.c_int, _u32, _P(_vp))
     f("vidc_roc_encode_rows", C.c_int, _vp, _u64, _u32, _vp, C.c_int, _u32, _P(_vp))
     f("vidc_roc_destroy", None, _vp)
     f("vidc_roc_nlist", _u64, _vp)
@@ -77,6 +78,8 @@ def _declare(lib):
     # packed bits
     f("vidc_packed_bits_for", C.c_int, _u64)
     f("vidc_packed_encode", C.c_int, _vp, _u64, _vp, _vp, C.c_int, _P(_vp))
+    f("vidc_packed_encode_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, C.c_int, _P(_vp))
+    f("vidc_packed_offsets", C.c_int, _vp, _vp, _vp)
     f("vidc_packed_destroy", None, _vp)
     f("vidc_packed_compressed_bytes", _u64, _vp)
     f("vidc_packed_bits", C.c_int, _vp)
@@ -90,6 +93,7 @@ def _declare(lib):
     f("vidc_packed_import", C.c_int, _vp, _u64, _vp, C.c_int, _vp, _u64, _P(_vp))
     # Elias-Fano
     f("vidc_ef_encode", C.c_int, _vp, _u64, _vp, _vp, _u32, _P(_vp))
+    f("vidc_ef_encode_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, _u32, _P(_vp))
     f("vidc_ef_destroy", None, _vp)
     f("vidc_ef_compressed_bytes", _u64, _vp)
     f("vidc_ef_list_info", C.c_int, _vp, _vp, _vp, _vp)
@@ -114,6 +118,8 @@ def _declare(lib):
     f("vidc_compact_export_row", C.c_int, _vp, _vp, _u64, _vp, C.c_size_t)
     # wavelet tree
     f("vidc_wt_build", C.c_int, _vp, _u64, _vp, _vp, C.c_int, _P(_vp))
+    f("vidc_wt_build_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, C.c_int, _P(_vp))
+    f("vidc_wt_offsets", C.c_int, _vp, _vp, _vp)
     f("vidc_wt_destroy", None, _vp)
     f("vidc_wt_size_in_bytes", _u64, _vp)
     f("vidc_wt_levels", _u32, _vp)
@@ -131,16 +137,17 @@ EXPORTED_SYMBOLS = [
     "vidc_roc_encode", "vidc_roc_encode_rows", "vidc_roc_destroy", "vidc_roc_nlist", "vidc_roc_ntotal",
     "vidc_roc_compressed_bytes", "vidc_roc_total_words", "vidc_roc_list_info", "vidc_roc_export_words", "vidc_roc_export_all_words",
     "vidc_roc_perm", "vidc_roc_perm_dev", "vidc_roc_import", "vidc_roc_decode_all", "vidc_roc_decode_lists", "vidc_roc_decode_gather",
-    "vidc_roc_decode_rows", "vidc_roc_last_decode_nonclean",
+    "vidc_roc_decode_rows", "vidc_roc_last_decode_nonclean", "vidc_roc_encode_dev",
     "vidc_packed_bits_for", "vidc_packed_encode", "vidc_packed_destroy", "vidc_packed_compressed_bytes",
     "vidc_packed_bits", "vidc_packed_decode_all", "vidc_packed_decode_lists", "vidc_packed_decode_gather", "vidc_packed_get", "vidc_packed_export", "vidc_packed_total_words", "vidc_packed_export_all", "vidc_packed_import",
+    "vidc_packed_encode_dev", "vidc_packed_offsets",
     "vidc_ef_encode", "vidc_ef_destroy", "vidc_ef_compressed_bytes", "vidc_ef_list_info", "vidc_ef_decode_all",
     "vidc_ef_get", "vidc_ef_perm", "vidc_ef_export", "vidc_ef_stream_words", "vidc_ef_export_all", "vidc_ef_import",
-    "vidc_ef_encode_rows", "vidc_ef_decode_rows", "vidc_ef_decode_lists", "vidc_ef_decode_gather",
+    "vidc_ef_encode_rows", "vidc_ef_decode_rows", "vidc_ef_decode_lists", "vidc_ef_decode_gather", "vidc_ef_encode_dev",
     "vidc_compact_rows_encode", "vidc_compact_destroy", "vidc_compact_bits", "vidc_compact_stride",
     "vidc_compact_size_in_bytes", "vidc_compact_rows_decode", "vidc_compact_export_row",
     "vidc_wt_build", "vidc_wt_destroy", "vidc_wt_size_in_bytes", "vidc_wt_levels", "vidc_wt_select",
-    "vidc_wt_decode_all", "vidc_wt_decode_lists", "vidc_wt_decode_gather",
+    "vidc_wt_decode_all", "vidc_wt_decode_lists", "vidc_wt_decode_gather", "vidc_wt_build_dev", "vidc_wt_offsets",
 ]
 
 
@@ -184,6 +191,7 @@ class Context:
         h = _vp()
         check(lib().vidc_ctx_create(device, C.byref(h)))
         self.h = h
+        self.device = device  # (< 0: the HIP device current when it was created)
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,7 +1,8 @@
 """Device-resident codec objects over the C-ABI (one object = every list of one index / graph).
 
-IDs live in HBM as torch int64 tensors (faiss::idx_t); list boundaries are a host CSR
-`offsets[nlist+1]`.  All heavy work happens in the HIP kernels behind libvidc.so.
+IDs live in HBM as torch int64 tensors (faiss::idx_t); list boundaries are a CSR `offsets[nlist+1]`, on the host
+(numpy / list) or on the GPU (an int64 / uint64 CUDA tensor, routed to the vidc_*_encode_dev entry points).  All heavy work
+happens in the HIP kernels behind libvidc.so.
 """
 import ctypes as C
 
@@ -21,6 +22,44 @@ def _as_offsets(offsets):
     off = np.ascontiguousarray(offsets, dtype=np.uint64)
     assert off.ndim == 1 and off.size >= 1
     return off
+
+
+def _cuda_offsets(offsets, ctx):
+    """The offsets as a contiguous int64 / uint64 CUDA tensor on the context's device, or None for host offsets (numpy, lists).
+    (Real exceptions, not asserts: the C call reads 8 * numel bytes of device memory.)"""
+    if type(offsets).__module__.split(".")[0] != "torch":
+        return None
+    torch = _torch()
+    if not offsets.is_cuda:
+        return None
+    if offsets.dtype not in (torch.int64, torch.uint64):
+        raise TypeError(f"device offsets must be int64 or uint64, not {offsets.dtype}")
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("device offsets must be a 1-D tensor of nlist + 1 entries")
+    want = getattr(ctx, "device", -1)
+    want = torch.cuda.current_device() if want is None or want < 0 else want
+    if offsets.device.index != want:
+        raise ValueError(f"device offsets live on cuda:{offsets.device.index}, the context on cuda:{want}")
+    return offsets.contiguous()
+
+
+def _dev_ids_dev(ids, d_off):
+    """ids of a device-offsets call: a 64-bit CUDA tensor on the offsets' device (checked with exceptions: the kernels read 8 bytes
+    per id)."""
+    torch = _torch()
+    if isinstance(ids, np.ndarray):
+        ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.uint64).view(np.int64)).cuda()
+    if not ids.is_cuda or ids.dtype not in (torch.int64, torch.uint64):
+        raise TypeError("ids must be an int64 / uint64 CUDA tensor")
+    ids = _dev_ids(ids, _count(ids))
+    if ids.device != d_off.device:
+        raise ValueError("ids and offsets must live on the same device")
+    return ids
+
+
+def _count(ids):
+    """number of ids in a tensor or an array"""
+    return int(ids.numel()) if hasattr(ids, "numel") else int(np.asarray(ids).size)
 
 
 def _dev_ids(ids, ntotal):
@@ -77,6 +116,13 @@ class RocLists:
     @classmethod
     def encode(cls, offsets, ids, precision_mode=VIDC_PREC_REFERENCE, want_perm=False, ctx=None):
         ctx = _lib.default_context() if ctx is None else ctx
+        d_off = _cuda_offsets(offsets, ctx)
+        if d_off is not None:  # device offsets: ntotal = ids.numel(), checked against offsets[-1] on the device
+            d_ids = _dev_ids_dev(ids, d_off)
+            h = C.c_void_p()
+            check(lib().vidc_roc_encode_dev(ctx.h, d_off.numel() - 1, ptr(d_off), d_ids.numel(), ptr(d_ids) if d_ids.numel() else None,
+                                            int(precision_mode), _lib.VIDC_ROC_WANT_PERM if want_perm else 0, C.byref(h)))
+            return cls(h, ctx, None)
         off = _as_offsets(offsets)
         nlist = off.size - 1
         d_ids = _dev_ids(ids, int(off[-1] - off[0])) if off[-1] > off[0] else None
@@ -223,10 +269,21 @@ class RocLists:
 class PackedLists:
     """Fixed-width packed ids (vidc_packed): ceil(log2(ntotal+1)) bits per id, LSB-first."""
 
-    def __init__(self, handle, ctx, offsets):
+    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
         self.h = handle
         self.ctx = ctx
-        self.offsets = offsets
+        self._offsets = offsets
+        self._nlist = nlist
+        self._ntotal = ntotal
+
+    @property
+    def offsets(self):
+        """CSR offsets (host).  Objects built from device offsets copy the object's own device array on first use."""
+        if self._offsets is None:
+            off = np.zeros(self._nlist + 1, np.uint64)
+            check(lib().vidc_packed_offsets(self.ctx.h, self.h, ptr(off)))
+            self._offsets = off
+        return self._offsets
 
     def __del__(self):
         try:  # may run during interpreter shutdown, after module globals are gone
@@ -243,6 +300,16 @@ class PackedLists:
     @classmethod
     def encode(cls, offsets, ids, bits=None, ctx=None):
         ctx = _lib.default_context() if ctx is None else ctx
+        d_off = _cuda_offsets(offsets, ctx)
+        if d_off is not None:  # device offsets: ntotal = ids.numel(), checked against offsets[-1] on the device
+            d_ids = _dev_ids_dev(ids, d_off)
+            ntotal, nlist = d_ids.numel(), d_off.numel() - 1
+            if bits is None:
+                bits = cls.bits_for(ntotal)
+            h = C.c_void_p()
+            check(lib().vidc_packed_encode_dev(ctx.h, nlist, ptr(d_off), ntotal, ptr(d_ids) if ntotal else None, int(bits),
+                                               C.byref(h)))
+            return cls(h, ctx, None, nlist, ntotal)
         off = _as_offsets(offsets)
         ntotal = int(off[-1])
         if bits is None:
@@ -254,7 +321,7 @@ class PackedLists:
 
     @property
     def ntotal(self):
-        return int(self.offsets[-1])
+        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
 
     @property
     def bits(self):
@@ -323,11 +390,12 @@ class PackedLists:
 class EfLists:
     """Elias-Fano coded lists (vidc_ef), succinct::elias_fano geometry."""
 
-    def __init__(self, handle, ctx, offsets):
+    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
         self.h = handle
         self.ctx = ctx
         self._offsets = offsets
-        self._nlist = None
+        self._nlist = nlist
+        self._ntotal = ntotal
 
     @property
     def offsets(self):
@@ -348,6 +416,14 @@ class EfLists:
     @classmethod
     def encode(cls, offsets, ids, want_perm=False, ctx=None):
         ctx = _lib.default_context() if ctx is None else ctx
+        d_off = _cuda_offsets(offsets, ctx)
+        if d_off is not None:  # device offsets: ntotal = ids.numel(), checked against offsets[-1] on the device
+            d_ids = _dev_ids_dev(ids, d_off)
+            ntotal, nlist = d_ids.numel(), d_off.numel() - 1
+            h = C.c_void_p()
+            check(lib().vidc_ef_encode_dev(ctx.h, nlist, ptr(d_off), ntotal, ptr(d_ids) if ntotal else None,
+                                           _lib.VIDC_EF_WANT_PERM if want_perm else 0, C.byref(h)))
+            return cls(h, ctx, None, nlist, ntotal)
         off = _as_offsets(offsets)
         ntotal = int(off[-1])
         d_ids = _dev_ids(ids, ntotal) if ntotal else None
@@ -358,7 +434,7 @@ class EfLists:
 
     @property
     def ntotal(self):
-        return int(self.offsets[-1])
+        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
 
     @property
     def compressed_bytes(self):
@@ -537,10 +613,21 @@ class CompactRows:
 class WaveletTreeLists:
     """Wavelet tree over list_nos[id] (vidc_wt): id = select(offset + 1, list_no)."""
 
-    def __init__(self, handle, ctx, offsets):
+    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
         self.h = handle
         self.ctx = ctx
-        self.offsets = offsets
+        self._offsets = offsets
+        self._nlist = nlist
+        self._ntotal = ntotal
+
+    @property
+    def offsets(self):
+        """CSR offsets (host).  Objects built from device offsets copy the object's own device array on first use."""
+        if self._offsets is None:
+            off = np.zeros(self._nlist + 1, np.uint64)
+            check(lib().vidc_wt_offsets(self.ctx.h, self.h, ptr(off)))
+            self._offsets = off
+        return self._offsets
 
     def __del__(self):
         try:  # may run during interpreter shutdown, after module globals are gone
@@ -553,6 +640,14 @@ class WaveletTreeLists:
     @classmethod
     def build(cls, offsets, ids, wt_type=0, ctx=None):
         ctx = _lib.default_context() if ctx is None else ctx
+        d_off = _cuda_offsets(offsets, ctx)
+        if d_off is not None:  # device offsets: ntotal = ids.numel(), checked against offsets[-1] on the device
+            d_ids = _dev_ids_dev(ids, d_off)
+            ntotal, nlist = d_ids.numel(), d_off.numel() - 1
+            h = C.c_void_p()
+            check(lib().vidc_wt_build_dev(ctx.h, nlist, ptr(d_off), ntotal, ptr(d_ids) if ntotal else None, int(wt_type),
+                                          C.byref(h)))
+            return cls(h, ctx, None, nlist, ntotal)
         off = _as_offsets(offsets)
         ntotal = int(off[-1])
         d_ids = _dev_ids(ids, ntotal) if ntotal else None
@@ -562,7 +657,7 @@ class WaveletTreeLists:
 
     @property
     def ntotal(self):
-        return int(self.offsets[-1])
+        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
 
     @property
     def size_in_bytes(self):

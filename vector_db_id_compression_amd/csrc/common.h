@@ -247,6 +247,8 @@ struct vidc_ctx {
     uint32_t *d_mt = nullptr;  // VIDC_MT_TABLE words
     void *d_u2tab = nullptr;   // per-divisor constants of the hand-scheduled chain kernels (roc_u2.h), VIDC_ROC_MAX_LIST + 1 entries
     void *d_ltab = nullptr;    // divisor table of the lane-per-list kernels (roc_lane.h), VIDC_LANE_TAB + 1 entries
+    // accumulators (zero between calls: the kernel that uses them clears them) + results of k_offsets_ingest (dev_offsets.h), 16 words
+    unsigned long long *d_doff = nullptr;
     int num_cu = 256;
     double last_kernel_ms = 0.0;
     double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // see VIDC_PHASE_* in vidc.h

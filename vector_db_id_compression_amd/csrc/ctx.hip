@@ -257,6 +257,7 @@ void vidc_ctx_destroy(vidc_ctx *c) {
         if (b.p) (void)hipHostFree(b.p);
     if (c->d_mt) (void)hipFree(c->d_mt);
     if (c->d_ltab) (void)hipFree(c->d_ltab);
+    if (c->d_doff) (void)hipFree(c->d_doff);
     if (c->d_u2tab) (void)hipFree(c->d_u2tab);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

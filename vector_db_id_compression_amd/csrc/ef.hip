@@ -15,6 +15,7 @@
 #include "bits.h"
 #include "chunks.h"
 #include "common.h"
+#include "dev_offsets.h"
 #include "scan.h"
 #include "rows_csr.h"
 #include "rows_tile.h"
@@ -880,6 +881,38 @@ __global__ void __launch_bounds__(64) k_ef_lowhigh32(const uint64_t *__restrict_
             ef_lowhigh32_chunk<4, false, V2>(rc, sorted_ids, low, high, hrank, batches, unsorted, drecs, win32, img32);
         else
             ef_lowhigh32_chunk<1, false, V2>(rc, sorted_ids, low, high, hrank, batches, unsorted, drecs, win32, img32);
+        wave_lds_sync();
+    }
+}
+
+// The chunk kernel of an object built from device offsets (vidc_ef_encode_dev): the record count comes from the ingest's results
+// (dev_offsets.h) instead of the host, and so does the choice of form: the three forms the host path picks from (max_list <= 256
+// -> <4, true>; chunks half full on average -> <EF_CHUNK / 64, true>; otherwise <EF_CHUNK / 64, false>) are queued back to back and
+// each one returns at once unless it is the form the results name.  Bad offsets: nothing runs.
+template <int RMAX, bool SMALL, uint32_t FORM>
+__global__ void __launch_bounds__(64) k_ef_lowhigh32_dev(const uint64_t *__restrict__ sorted_ids, const EfChunkRec *__restrict__ recs,
+                                                         const unsigned long long *__restrict__ res, uint64_t ntotal,
+                                                         uint64_t *__restrict__ low, uint64_t *__restrict__ high,
+                                                         uint32_t *__restrict__ hrank, Chunk *__restrict__ batches,
+                                                         uint32_t *__restrict__ unsorted, EfRec *__restrict__ drecs,
+                                                         const uint32_t *__restrict__ abort) {
+    __shared__ uint32_t win32[EF_WIN_WORDS * 2];
+    __shared__ uint32_t img32[(64 * RMAX + 8) * 2];
+    if (*abort || res[DOFF_BAD]) return;
+    const uint64_t nchunks = res[DOFF_CHUNKS];
+    const uint32_t form = res[DOFF_MAX] <= 256u ? 0u : (ntotal < 256u * nchunks ? 1u : 2u);
+    if (form != FORM) return;
+    for (uint64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const EfChunkRec rc = recs[c];
+        const uint32_t nc = rc.n - rc.start < EF_CHUNK ? rc.n - rc.start : EF_CHUNK;
+        if (!SMALL || (RMAX > 4 && nc > 256u))
+            ef_lowhigh32_chunk<RMAX, false, true>(rc, sorted_ids, low, high, hrank, batches, unsorted, drecs, win32, img32);
+        else if (nc == 256u)
+            ef_lowhigh32_chunk<4, true, true>(rc, sorted_ids, low, high, hrank, batches, unsorted, drecs, win32, img32);
+        else if (nc > 64u)
+            ef_lowhigh32_chunk<4, false, true>(rc, sorted_ids, low, high, hrank, batches, unsorted, drecs, win32, img32);
+        else
+            ef_lowhigh32_chunk<1, false, true>(rc, sorted_ids, low, high, hrank, batches, unsorted, drecs, win32, img32);
         wave_lds_sync();
     }
 }
@@ -1829,8 +1862,16 @@ int ef_encode_general(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t
 // do not fit (a universe beyond the guess, ids >= 2^32) it raises *abort, the chunk kernels return at once, *respec is set and the
 // caller runs the call again the old way.  Cost of the bound: the buffers are up to ~15 % larger than the streams (n_low / n_high
 // hold the exact word counts).
+// dv (device offsets, vidc_ef_encode_dev): the caller's array, copied into e->d_offsets and validated by k_offsets_ingest inside the
+// timed region; nchunks / max_list are then bounds (floor(ntotal / EF_CHUNK) + nlist, ntotal) and the exact values come from the
+// ingest's results (device) and summary (host, after the wait).
+struct EfDevIn {
+    const uint64_t *src;
+    unsigned long long *acc;  // doff_block: accumulators, then results
+    DevOffSummary *sum;       // pinned
+};
 int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
-                   bool *retry, bool spec, bool *respec) {
+                   bool *retry, bool spec, bool *respec, const EfDevIn *dv) {
     const uint64_t nlist = e->nlist;
     const uint32_t nl32 = (uint32_t)nlist;
     // (one tile only for objects whose chunk records one workgroup can write: 1024 lists of a million ids each are two million records,
@@ -1870,6 +1911,11 @@ int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t fl
     VIDC_TRY(e->d_chunks.alloc(1, ctx->dpool));  // (the chunk table of the three-pass encoder: not needed here)
     tr.mark("scratch + geometry arrays");
     pt.begin();
+    if (dv) {
+        dv->sum->done = 0;
+        hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, dv->src, e->d_offsets.p, nlist, e->ntotal,
+                           (uint32_t)__builtin_ctz(EF_CHUNK), 0u, 0xfffffff0ull, dv->acc, dv->acc + DOFF_NACC, dv->sum);
+    }
     if (single) {
         hipLaunchKernelGGL((k_ef_offsets<true, 2, 512>), dim3(1), dim3(512), 0, ctx->stream, d_ids, e->d_offsets.p, nl32,
                            e->d_lbits.p, e->d_universe.p, (const EfRaw *)nullptr, (const EfTile *)nullptr, 1u,
@@ -1904,6 +1950,12 @@ int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t fl
     e->nbatches = lim.nbatches;  // (spec: an upper bound until the call's only wait)
     if (!spec) {
         VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        if (dv) {  // (this path waits here anyway: the exact figures take the host path's decisions from now on)
+            VIDC_TRY(doff_status(*dv->sum, "elias-fano", VIDC_ERR_INVALID));
+            nchunks = dv->sum->chunks;
+            max_list = dv->sum->max_n;
+            e->nchunks = nchunks;
+        }
         if (hs->nchunks != nchunks) {
             set_error("elias-fano encoder: chunk count mismatch (%llu vs %llu)", (unsigned long long)hs->nchunks,
                       (unsigned long long)nchunks);
@@ -1952,7 +2004,20 @@ int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t fl
         hs[1].unsorted = 0u;
         uint32_t *d_flag = &hs[1].unsorted;
         if (clear_high) VIDC_HIP(hipMemsetAsync(e->d_high.p, 0, high_words * 8, ctx->stream));
-        if (wide_ids)
+        if (dv && spec) {  // (spec: the ids are below 2^32, wide_ids is false)
+            const unsigned long long *res = dv->acc + DOFF_NACC;
+            // (grid: 32 wavefronts per CU, looping over the chunks -- the two forms that return at once then cost two small dispatches,
+            // not two of up to 256 wavefronts per CU)
+            const uint32_t cgrid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)ctx->num_cu * 32);
+            hipLaunchKernelGGL((k_ef_lowhigh32_dev<4, true, 0u>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids, s_recs.as<EfChunkRec>(), res,
+                               e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
+            hipLaunchKernelGGL((k_ef_lowhigh32_dev<EF_CHUNK / 64, true, 1u>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids,
+                               s_recs.as<EfChunkRec>(), res, e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag,
+                               d_drecs, d_abort);
+            hipLaunchKernelGGL((k_ef_lowhigh32_dev<EF_CHUNK / 64, false, 2u>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids,
+                               s_recs.as<EfChunkRec>(), res, e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag,
+                               d_drecs, d_abort);
+        } else if (wide_ids)
             hipLaunchKernelGGL(k_ef_lowhigh, dim3(cgrid), dim3(64), 0, ctx->stream, d_ids, s_recs.as<EfChunkRec>(), nchunks,
                                e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
         else if (max_list <= 256)
@@ -1972,6 +2037,14 @@ int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t fl
     tr.mark("wait");
     ctx->last_kernel_ms = pt.collect();
     tr.mark("event times");
+    if (dv && spec) {  // bad offsets first (the kernels above ran on the valid split that replaced them); then the exact figures
+        if (!dv->sum->done) { set_error("elias-fano: the offsets summary was not written"); return VIDC_ERR_HIP; }
+        VIDC_TRY(doff_status(*dv->sum, "elias-fano", VIDC_ERR_INVALID));
+        nchunks = dv->sum->chunks;
+        max_list = dv->sum->max_n;
+        e->nchunks = nchunks;
+        e->max_list = max_list;
+    }
     if (spec) {
         if (hs->nchunks != nchunks) {
             set_error("elias-fano encoder: chunk count mismatch (%llu vs %llu)", (unsigned long long)hs->nchunks,
@@ -1995,6 +2068,10 @@ int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t fl
     }
     return VIDC_OK;
 }
+
+struct EfDevIn;
+int ef_encode_lists(vidc_ctx *ctx, vidc_ef *ep, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
+                    const uint64_t *host_offsets, const EfDevIn *dv = nullptr);
 
 }  // namespace
 
@@ -2041,30 +2118,52 @@ int vidc_ef_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
     }
     if (e->ntotal && !d_ids) return VIDC_ERR_INVALID;
     tr.mark("host offsets pass");
+    VIDC_TRY(ef_encode_lists(ctx, e.get(), d_ids, flags, nchunks, max_list, offsets));
+    guard.armed = false;
+    *out = e.release();
+    return VIDC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the encode once the chunk count and the longest list are known (host or device offsets); host_offsets: the caller's host array,
+// NULL for an object built from device offsets (the retry mirrors the object's device copy)
+int ef_encode_lists(vidc_ctx *ctx, vidc_ef *ep, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
+                    const uint64_t *host_offsets, const EfDevIn *dv) {
+    HostTrace tr("ef encode (lists)");
+    const uint64_t nlist = ep->nlist;
+    struct NoDelete { void operator()(vidc_ef *) const {} };
+    std::unique_ptr<vidc_ef, NoDelete> e(ep);
+    const uint64_t *offsets = host_offsets;
     bool retry = false;
     e->max_list = max_list;
     tr.mark("offsets staged");
     static const bool no_spec = std::getenv("VIDC_EF_NO_SPEC") != nullptr;  // (measurement switch: always size the streams after the geometry kernels)
     bool respec = false;
     const bool spec = !no_spec && e->ntotal && e->ntotal <= 0xffffffffull;
-    VIDC_TRY(ef_encode_fast(ctx, e.get(), d_ids, flags, nchunks, max_list, &retry, spec, &respec));
+    VIDC_TRY(ef_encode_fast(ctx, e.get(), d_ids, flags, nchunks, max_list, &retry, spec, &respec, dv));
     if (respec) {  // the guess of the universe was too small: size the streams from the ids, and remember how large they are
         e->d_recs.release();
         e->recs_ready = false;
         e->has_perm = false;
         e->n_low = e->n_high = ~0ull;
-        VIDC_TRY(ef_encode_fast(ctx, e.get(), d_ids, flags, nchunks, max_list, &retry, false, &respec));
+        VIDC_TRY(ef_encode_fast(ctx, e.get(), d_ids, flags, nchunks, max_list, &retry, false, &respec, dv));
         std::vector<uint64_t> uni(nlist);
         VIDC_HIP(hipMemcpy(uni.data(), e->d_universe.p, nlist * 8, hipMemcpyDeviceToHost));
         for (uint64_t u : uni) ctx->ef_universe_hint = std::max(ctx->ef_universe_hint, u);
     }
-    guard.armed = false;  // (ef_encode_fast has waited)
     tr.mark("encode_fast (launches + wait)");
     if (retry) {  // some list is not ascending: general three-pass encoder with the sort
-        e->offsets = vec_pool<uint64_t>().take(nlist + 1);
-        if (nlist) e->offsets.assign(offsets, offsets + nlist + 1);
-        else e->offsets.assign(1, 0);
-        e->offsets_host = true;
+        if (offsets) {
+            e->offsets = vec_pool<uint64_t>().take(nlist + 1);
+            if (nlist) e->offsets.assign(offsets, offsets + nlist + 1);
+            else e->offsets.assign(1, 0);
+            e->offsets_host = true;
+        } else {
+            VIDC_TRY(ef_ensure_offsets(e.get()));  // (device offsets: the one copy of them to the host, on this slow path only)
+        }
         e->n_low = e->n_high = ~0ull;
         e->total_bits = 0;
         e->has_perm = false;
@@ -2072,6 +2171,43 @@ int vidc_ef_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
         e->d_recs.release();
         VIDC_TRY(ef_encode_general(ctx, e.get(), d_ids, flags));
     }
+    return VIDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Device offsets (include/vidc.h): k_offsets_ingest copies them into the object, validates them and sums the chunk count and the
+// longest list, as the first kernel of ef_encode_fast; every buffer is sized from the bounds floor(ntotal / EF_CHUNK) + nlist chunks
+// and ntotal ids per list, and the chunk kernels take their count and form from the ingest's results on the device: one wait.
+int vidc_ef_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids,
+                       uint32_t flags, vidc_ef **out) {
+    if (!ctx || !out || !d_offsets) return VIDC_ERR_INVALID;
+    *out = nullptr;
+    if (nlist >= 0xffffffffull) return VIDC_ERR_INVALID;
+    if (ntotal && !d_ids) return VIDC_ERR_INVALID;
+    if (!nlist && ntotal) { set_error("elias-fano: ntotal > 0 with no lists"); return VIDC_ERR_INVALID; }
+    // (every split of ntotal ids into nlist lists has one over the limit: the valid split bad offsets are replaced by would too)
+    if (nlist && (ntotal + nlist - 1) / nlist > 0xfffffff0ull) { set_error("elias-fano: bad offsets (a list of 2^32 ids or more)"); return VIDC_ERR_INVALID; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<vidc_ef> e(new vidc_ef());
+    e->device = ctx->device;
+    e->nlist = nlist;
+    e->ntotal = ntotal;
+    VIDC_TRY(e->d_offsets.alloc(nlist + 1, ctx->dpool));
+    unsigned long long *acc = nullptr;
+    VIDC_TRY(doff_block(ctx, &acc));
+    Pinned h_sum;
+    VIDC_TRY(h_sum.get(ctx, sizeof(DevOffSummary)));
+    const EfDevIn dv{d_offsets, acc, h_sum.as<DevOffSummary>()};
+    struct SyncOnExit {  // (an early return must not release blocks that kernels in flight still use)
+        vidc_ctx *c;
+        bool armed = true;
+        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
+    } guard{ctx};
+    VIDC_TRY(ef_encode_lists(ctx, e.get(), d_ids, flags, ntotal / EF_CHUNK + nlist, ntotal, nullptr, &dv));
+    guard.armed = false;
     *out = e.release();
     return VIDC_OK;
 }

@@ -8,10 +8,12 @@
 // HBM-bound: 8 B read + bits/8 B written per id (encode), the mirror for decode.
 #include <algorithm>
 #include <memory>
+#include <mutex>
 
 #include "bits.h"
 #include "chunks.h"
 #include "common.h"
+#include "dev_offsets.h"
 #include "rows_tile.h"
 #include "scan.h"
 
@@ -23,7 +25,11 @@ struct vidc_packed {
     uint64_t nlist = 0, ntotal = 0;
     int bits = 0;
     uint64_t compressed_bytes = 0, total_words = 0;
-    std::vector<uint64_t> offsets;
+    // host mirror of d_offsets: filled at encode from host offsets, on first use (packed_ensure_offsets, under mu) for objects built
+    // from device offsets
+    mutable std::vector<uint64_t> offsets;
+    mutable bool offsets_host = true;
+    mutable std::mutex mu;
     DevBuf<uint64_t> d_offsets, d_word_off, d_words;
     DevBuf<Chunk> d_chunks;
     uint64_t nchunks = 0;
@@ -42,10 +48,9 @@ namespace {
 // unrolled code of every register, used or not; these kernels are not bound by their instructions, though: 16 M ids in
 // lists of 256 encode 55 -> 53 us, decode 36 -> 35 us, against 83 -> 70 us for the Elias-Fano encoder's same change)
 template <int R>
-__global__ void __launch_bounds__(64) k_packed_encode(const uint64_t *ids, const uint64_t *offsets,
-                                                      const uint64_t *word_off, const Chunk *chunks, uint64_t nchunks,
-                                                      uint32_t bits, uint64_t id_limit, uint64_t *words, uint32_t *err) {
-    __shared__ unsigned long long img[64 * R + 8];  // <= 64 R * 64 / 64 words
+__device__ __forceinline__ void packed_encode_chunks(const uint64_t *ids, const uint64_t *offsets, const uint64_t *word_off,
+                                                     const Chunk *chunks, uint64_t nchunks, uint32_t bits, uint64_t id_limit,
+                                                     uint64_t *words, uint32_t *err, unsigned long long *img) {
     const uint32_t lane = threadIdx.x;
     const uint64_t keep = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
     for (uint64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
@@ -82,6 +87,28 @@ __global__ void __launch_bounds__(64) k_packed_encode(const uint64_t *ids, const
         for (uint32_t w = lane; w < nw; w += 64) dst[w] = img[w];
         wave_lds_sync();
     }
+}
+template <int R>
+__global__ void __launch_bounds__(64) k_packed_encode(const uint64_t *ids, const uint64_t *offsets,
+                                                      const uint64_t *word_off, const Chunk *chunks, uint64_t nchunks,
+                                                      uint32_t bits, uint64_t id_limit, uint64_t *words, uint32_t *err) {
+    __shared__ unsigned long long img[64 * R + 8];  // <= 64 R * 64 / 64 words
+    packed_encode_chunks<R>(ids, offsets, word_off, chunks, nchunks, bits, id_limit, words, err, img);
+}
+// The same for an object built from device offsets (vidc_packed_encode_dev): the chunk count and the longest list come from the
+// ingest's results (dev_offsets.h), the grid from the bound floor(ntotal / 512) + nlist.  The choice between the four- and
+// eight-register forms is made here, by the wavefront, from the longest list: one launch serves both (the unused form costs
+// registers only, and these kernels are not bound by their registers or instructions).  Bad offsets: nothing runs.
+__global__ void __launch_bounds__(64) k_packed_encode_dev(const uint64_t *ids, const uint64_t *offsets, const uint64_t *word_off,
+                                                          const Chunk *chunks, const unsigned long long *acc, uint32_t bits,
+                                                          uint64_t *words, uint32_t *err) {
+    __shared__ unsigned long long img[64 * (CHUNK_IDS / 64) + 8];
+    if (acc[DOFF_BAD]) return;
+    const uint64_t nchunks = acc[DOFF_CHUNKS];
+    if (acc[DOFF_MAX] <= 256u)
+        packed_encode_chunks<4>(ids, offsets, word_off, chunks, nchunks, bits, ~0ull, words, err, img);
+    else
+        packed_encode_chunks<CHUNK_IDS / 64>(ids, offsets, word_off, chunks, nchunks, bits, ~0ull, words, err, img);
 }
 
 // The geometry of an object in ONE launch: chunk table, word offsets and the zeroed padding word of every list.  (Chunk counts -> scan
@@ -721,6 +748,26 @@ int vidc_compact_export_row(vidc_ctx *ctx, const vidc_compact *c, uint64_t node,
     return vidc_copy_d2h(ctx, bytes, c->d_data.p + node * c->stride, c->stride);
 }
 
+// the host mirror of an object built from device offsets, on first use (one copy of nlist + 1 words)
+static int packed_ensure_offsets(const vidc_packed *p) {
+    std::lock_guard<std::mutex> g(p->mu);
+    if (p->offsets_host) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(p->device));
+    std::vector<uint64_t> h = vec_pool<uint64_t>().take(p->nlist + 1);
+    h.resize(p->nlist + 1);
+    VIDC_HIP(hipMemcpy(h.data(), p->d_offsets.p, (p->nlist + 1) * 8, hipMemcpyDeviceToHost));
+    p->offsets = std::move(h);
+    p->offsets_host = true;
+    return VIDC_OK;
+}
+
+int vidc_packed_offsets(vidc_ctx *ctx, const vidc_packed *p, uint64_t *offsets) {
+    if (!ctx || !p || !offsets) return VIDC_ERR_INVALID;
+    VIDC_TRY(packed_ensure_offsets(p));
+    std::memcpy(offsets, p->offsets.data(), (p->nlist + 1) * 8);
+    return VIDC_OK;
+}
+
 int vidc_packed_bits_for(uint64_t ntotal) {  // custom_invlists_impl.cpp:68-70
     int bits = 0;
     while (bits < 64 && (1ull << bits) < ntotal + 1) bits++;
@@ -832,6 +879,89 @@ int vidc_packed_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, c
     return VIDC_OK;
 }
 
+// Device offsets (include/vidc.h): the offsets never visit the host.  One kernel copies them into the object, validates them and
+// sums the geometry (k_offsets_ingest); the buffers are sized from the bounds that every valid CSR of (nlist, ntotal) meets --
+// words <= ceil(ntotal bits / 64) + 2 nlist, chunks <= floor(ntotal / 512) + nlist -- and the exact figures come from the
+// ingest's summary (pinned memory) after the call's only wait.
+int vidc_packed_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids, int bits,
+                           vidc_packed **out) {
+    if (!ctx || !out || !d_offsets || bits < 0 || bits > 64) return VIDC_ERR_INVALID;
+    *out = nullptr;
+    if (nlist >= 0xffffffffull) return VIDC_ERR_INVALID;
+    if (ntotal && !d_ids) return VIDC_ERR_INVALID;
+    if (!nlist && ntotal) { set_error("packed bits: ntotal > 0 with no lists"); return VIDC_ERR_INVALID; }
+    if (ntotal >> 57) { set_error("packed bits: ntotal too large"); return VIDC_ERR_INVALID; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<vidc_packed> p(new vidc_packed());
+    p->device = ctx->device;
+    p->nlist = nlist;
+    p->bits = bits;
+    p->ntotal = ntotal;
+    p->offsets_host = false;
+    const uint64_t words_b = (ntotal * (uint64_t)bits + 63) / 64 + 2 * nlist, chunks_b = ntotal / CHUNK_IDS + nlist;
+    VIDC_TRY(p->d_offsets.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(p->d_word_off.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(p->d_words.alloc(words_b ? words_b : 1, ctx->dpool));
+    VIDC_TRY(p->d_chunks.alloc(chunks_b ? chunks_b : 1, ctx->dpool));
+    // k_packed_table's tiling, as packed_setup
+    const uint32_t per = nlist + 1 <= 4096u ? (uint32_t)((nlist + 1 + 255u) / 256u)
+                                            : (uint32_t)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (nlist + 1 + 262143u) / 262144u));
+    const uint32_t ntiles = (uint32_t)((nlist + 1 + 256u * per - 1u) / (256u * per));
+    // the ingest's accumulators / results (context block, no per-call memset); k_packed_table's scan state, cleared only when the object
+    // has more than one tile (as packed_setup)
+    unsigned long long *acc = nullptr;
+    VIDC_TRY(doff_block(ctx, &acc));
+    unsigned long long *res = acc + DOFF_NACC;
+    Scratch s_state;
+    VIDC_TRY(s_state.get(ctx, ((size_t)2 * ntiles + 1) * 8));
+    // the ingest's summary (64 bytes) and the "an id does not fit" flag, both written by kernels into pinned memory
+    Pinned h_tail;
+    VIDC_TRY(h_tail.get(ctx, 128));
+    DevOffSummary *hs = h_tail.as<DevOffSummary>();
+    volatile uint32_t *err_flag = (volatile uint32_t *)(h_tail.as<char>() + 64);
+    hs->done = 0;
+    *err_flag = 0u;
+    struct SyncOnExit {  // (an early return must not release blocks that kernels in flight still use)
+        vidc_ctx *c;
+        bool armed = true;
+        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
+    } guard{ctx};
+    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    if (ntiles > 1u) VIDC_HIP(hipMemsetAsync(s_state.p, 0, ((size_t)2 * ntiles + 1) * 8, ctx->stream));
+    hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, d_offsets, p->d_offsets.p, nlist, ntotal,
+                       9u, (uint32_t)bits, ~0ull, acc, res, hs);
+    static_assert(CHUNK_IDS == 512, "the ingest counts chunks of 2^9 ids");
+    hipLaunchKernelGGL(k_packed_table, dim3(ntiles), dim3(256), 0, ctx->stream, p->d_offsets.p, (uint32_t)nlist, (uint32_t)bits,
+                       s_state.as<unsigned long long>(), p->d_chunks.p, p->d_word_off.p, p->d_words.p, per);
+    if (chunks_b)
+        hipLaunchKernelGGL(k_packed_encode_dev, dim3((uint32_t)std::min<uint64_t>(chunks_b, (uint64_t)ctx->num_cu * 256)), dim3(64), 0,
+                           ctx->stream, d_ids, p->d_offsets.p, p->d_word_off.p, p->d_chunks.p, res, (uint32_t)bits, p->d_words.p,
+                           (uint32_t *)err_flag);
+    VIDC_HIP(hipGetLastError());
+    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    guard.armed = false;
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+        ctx->last_kernel_ms = ms;
+    }
+    const DevOffSummary sum = *hs;  // (after the wait)
+    if (!sum.done) { set_error("packed bits: the offsets summary was not written"); return VIDC_ERR_HIP; }
+    VIDC_TRY(doff_status(sum, "packed bits", VIDC_ERR_INVALID));
+    if (*err_flag) {
+        set_error("packed bits: an id does not fit %d bits (reference: FAISS_THROW_IF_NOT(ids_in[i] >= 0 && "
+                  "ids_in[i] < ntotal), custom_invlists_impl.cpp:87)", bits);
+        return VIDC_ERR_DOMAIN;
+    }
+    p->compressed_bytes = sum.bytes;
+    p->total_words = sum.words;
+    p->nchunks = sum.chunks;
+    p->max_list = sum.max_n;
+    *out = p.release();
+    return VIDC_OK;
+}
+
 // ---- flat image of the object (the reference keeps compressed lists in memory only): {offsets, bits, words}, words =
 // the device layout (every list starts on a 64-bit word, one padding word follows it)
 uint64_t vidc_packed_total_words(const vidc_packed *p) { return p ? p->total_words : 0; }
@@ -891,6 +1021,7 @@ int vidc_packed_decode_all(vidc_ctx *ctx, const vidc_packed *p, uint64_t *d_out)
 int vidc_packed_decode_lists(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,
                              uint64_t *out_offsets) {
     if (!ctx || !p || (m && !list_nos) || !out_offsets) return VIDC_ERR_INVALID;
+    VIDC_TRY(packed_ensure_offsets(p));
     out_offsets[0] = 0;
     std::vector<PackedItem> items;
     for (uint64_t i = 0; i < m; i++) {
@@ -925,6 +1056,7 @@ int vidc_packed_decode_lists(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, co
 int vidc_packed_decode_gather(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
                               const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out) {
     if (!ctx || !p) return VIDC_ERR_INVALID;
+    VIDC_TRY(packed_ensure_offsets(p));
     return vidc_decode_gather_impl(ctx, p->nlist, m, list_nos, n_items, item_slot, item_off, ids_out,
                                    [&](uint64_t l) { return p->offsets[l + 1] - p->offsets[l]; },
                                    [&](uint64_t *d, uint64_t *lo) { return vidc_packed_decode_lists(ctx, p, m, list_nos, d, lo); });
@@ -934,6 +1066,7 @@ int vidc_packed_get(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, const uint6
                     int64_t *ids_out) {
     if (!ctx || !p || (m && (!list_nos || !offs || !ids_out))) return VIDC_ERR_INVALID;
     if (!m) return VIDC_OK;
+    VIDC_TRY(packed_ensure_offsets(p));
     for (uint64_t i = 0; i < m; i++) {
         if (list_nos[i] >= p->nlist || offs[i] >= p->offsets[list_nos[i] + 1] - p->offsets[list_nos[i]]) {
             set_error("packed get: (list %llu, offset %llu) out of range", (unsigned long long)list_nos[i],
@@ -958,6 +1091,7 @@ int vidc_packed_get(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, const uint6
 
 int vidc_packed_export(vidc_ctx *ctx, const vidc_packed *p, uint64_t list_no, uint8_t *bytes, size_t cap) {
     if (!ctx || !p || list_no >= p->nlist) return VIDC_ERR_INVALID;
+    VIDC_TRY(packed_ensure_offsets(p));
     uint64_t n = p->offsets[list_no + 1] - p->offsets[list_no];
     uint64_t nb = (n * p->bits + 7) / 8;
     if (nb > cap) { set_error("export buffer too small"); return VIDC_ERR_INVALID; }

@@ -2214,6 +2214,28 @@ int vidc_roc_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, cons
     return encode_impl(ctx, nlist, offsets, d_ids, false, 0, 0, nullptr, precision_mode, flags, out);
 }
 
+// Device offsets (include/vidc.h): the host planner classifies the lists by length, so the offsets come to the host once (one D2H
+// copy into a pinned block, in stream order) and the host path runs on that copy.
+int vidc_roc_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids,
+                        int precision_mode, uint32_t flags, vidc_roc **out) {
+    if (!ctx || !out || !d_offsets) return VIDC_ERR_INVALID;
+    *out = nullptr;
+    if (nlist >= 0xffffffffull) return VIDC_ERR_INVALID;
+    if (ntotal && !d_ids) return VIDC_ERR_INVALID;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    Pinned h_off;
+    VIDC_TRY(h_off.get(ctx, (nlist + 1) * 8));
+    uint64_t *h = h_off.as<uint64_t>();
+    VIDC_HIP(hipMemcpyAsync(h, d_offsets, (nlist + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    if (h[0] != 0 || h[nlist] != ntotal) {
+        set_error("roc: bad device offsets at list %llu (offsets[0] must be 0, offsets[nlist] == ntotal)",
+                  (unsigned long long)(h[0] != 0 || !nlist ? 0 : nlist - 1));
+        return VIDC_ERR_INVALID;
+    }
+    return encode_impl(ctx, nlist, h, d_ids, false, 0, 0, nullptr, precision_mode, flags, out);
+}
+
 int vidc_roc_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, int precision_mode,
                          uint32_t flags, vidc_roc **out) {
     if (N && !d_rows) return VIDC_ERR_INVALID;

@@ -20,9 +20,11 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <mutex>
 
 #include "bits.h"
 #include "common.h"
+#include "dev_offsets.h"
 #include "scan.h"
 
 using namespace vidc;
@@ -35,7 +37,9 @@ struct vidc_wt {
     int wt_type = 0;
     uint64_t words_per_level = 0, blocks_per_level = 0;
     uint64_t size_bytes = 0;
-    std::vector<uint64_t> offsets;      // host copy of the symbol start positions C[s]
+    mutable std::vector<uint64_t> offsets;  // host copy of the symbol start positions C[s]: for objects built from device offsets
+    mutable bool offsets_host = true;       // filled on first use (wt_ensure_offsets, under mu)
+    mutable std::mutex mu;
     DevBuf<uint64_t> d_bits;            // L * words_per_level                      (wt_type 0)
     DevBuf<uint32_t> d_rank;            // L * (blocks_per_level + 1): ones before each 512-bit block
     DevBuf<uint64_t> d_C;               // nlist + 1
@@ -1045,11 +1049,11 @@ WtRrrView rrr_view(const vidc_wt *w) {
 
 }  // namespace
 
-extern "C" {
-
-int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, int wt_type,
-                  vidc_wt **out) {
-    if (!ctx || !out || (nlist && !offsets) || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
+// offsets: host array (vidc_wt_build), or NULL and d_offsets + ntotal (vidc_wt_build_dev: copied into d_C and validated by
+// k_offsets_ingest, whose summary is read at the build's wait for the verdict on the ids, before any level is built)
+static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_offsets, uint64_t ntotal,
+                         const uint64_t *d_ids, int wt_type, vidc_wt **out) {
+    if (!ctx || !out || (nlist && !offsets && !d_offsets) || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
     *out = nullptr;
     if (nlist == 0 || nlist >= 0xffffffffull) { set_error("wavelet tree needs 1 <= nlist < 2^32"); return VIDC_ERR_INVALID; }
     VIDC_HIP(hipSetDevice(ctx->device));
@@ -1057,8 +1061,14 @@ int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const 
     w->device = ctx->device;
     w->nlist = nlist;
     w->wt_type = wt_type;
-    w->offsets.assign(offsets, offsets + nlist + 1);
-    w->ntotal = offsets[nlist];
+    if (offsets) {
+        w->offsets.assign(offsets, offsets + nlist + 1);
+        w->ntotal = offsets[nlist];
+    } else {
+        w->offsets_host = false;
+        w->ntotal = ntotal;
+    }
+    if (w->ntotal && !d_ids && !offsets) return VIDC_ERR_INVALID;
     if (w->ntotal >= 0xffffffffull) { set_error("wavelet tree: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED; }
     uint32_t L = 1;
     while ((1ull << L) < nlist) L++;
@@ -1067,7 +1077,18 @@ int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const 
     w->words_per_level = (nt + 63) / 64 + 1;
     w->blocks_per_level = (w->words_per_level + BLK_WORDS - 1) / BLK_WORDS;
     VIDC_TRY(w->d_C.alloc(nlist + 1));
-    VIDC_HIP(hipMemcpyAsync(w->d_C.p, w->offsets.data(), (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    Pinned h_dsum;
+    if (offsets) {
+        VIDC_HIP(hipMemcpyAsync(w->d_C.p, w->offsets.data(), (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        unsigned long long *acc = nullptr;
+        VIDC_TRY(doff_block(ctx, &acc));
+        VIDC_TRY(h_dsum.get(ctx, sizeof(DevOffSummary)));
+        h_dsum.as<DevOffSummary>()->done = 0;
+        hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, d_offsets, w->d_C.p, nlist, w->ntotal, 0u,
+                           0u, ~0ull, acc, acc + DOFF_NACC, h_dsum.as<DevOffSummary>());
+        VIDC_HIP(hipGetLastError());
+    }
     // wt_type 1 keeps one level of plain bits at a time (scratch) and the RRR coding of every level
     const bool rrr = wt_type == 1;
     if (rrr && L > 32) { set_error("wavelet tree: more than 32 levels"); return VIDC_ERR_UNSUPPORTED; }
@@ -1148,6 +1169,11 @@ int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const 
     uint32_t err = 0;
     VIDC_HIP(hipMemcpyAsync(&err, s_err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    if (!offsets) {  // (bad offsets were replaced by a valid split on the device: nothing above wrote outside its buffers)
+        const DevOffSummary sum = *h_dsum.as<DevOffSummary>();  // (after the wait)
+        if (!sum.done) { set_error("wavelet tree: the offsets summary was not written"); return VIDC_ERR_HIP; }
+        VIDC_TRY(doff_status(sum, "wavelet tree", VIDC_ERR_INVALID));
+    }
     if (err) {
         set_error("wavelet tree: ids must be a permutation of 0..ntotal-1, ascending inside every list "
                   "(asserts at custom_invlists_impl.cpp:359-360)");
@@ -1207,6 +1233,40 @@ int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const 
     return VIDC_OK;
 }
 
+static int wt_ensure_offsets(const vidc_wt *w) {
+    std::lock_guard<std::mutex> g(w->mu);
+    if (w->offsets_host) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(w->device));
+    std::vector<uint64_t> h(w->nlist + 1);
+    VIDC_HIP(hipMemcpy(h.data(), w->d_C.p, (w->nlist + 1) * 8, hipMemcpyDeviceToHost));
+    w->offsets = std::move(h);
+    w->offsets_host = true;
+    return VIDC_OK;
+}
+
+extern "C" {
+
+int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, int wt_type,
+                  vidc_wt **out) {
+    if (!ctx || !out || (nlist && !offsets) || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
+    return wt_build_impl(ctx, nlist, offsets, nullptr, 0, d_ids, wt_type, out);
+}
+
+int vidc_wt_build_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids, int wt_type,
+                      vidc_wt **out) {
+    if (!ctx || !out || !d_offsets || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
+    *out = nullptr;
+    if (ntotal >= 0xffffffffull) { set_error("wavelet tree: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED; }
+    return wt_build_impl(ctx, nlist, nullptr, d_offsets, ntotal, d_ids, wt_type, out);
+}
+
+int vidc_wt_offsets(vidc_ctx *ctx, const vidc_wt *w, uint64_t *offsets) {
+    if (!ctx || !w || !offsets) return VIDC_ERR_INVALID;
+    VIDC_TRY(wt_ensure_offsets(w));
+    std::memcpy(offsets, w->offsets.data(), (w->nlist + 1) * 8);
+    return VIDC_OK;
+}
+
 void vidc_wt_destroy(vidc_wt *w) { delete w; }
 uint64_t vidc_wt_size_in_bytes(const vidc_wt *w) { return w ? w->size_bytes : 0; }
 uint32_t vidc_wt_levels(const vidc_wt *w) { return w ? w->L : 0; }
@@ -1215,6 +1275,7 @@ int vidc_wt_select(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *
                    int64_t *ids_out) {
     if (!ctx || !w || (m && (!list_nos || !offs || !ids_out))) return VIDC_ERR_INVALID;
     if (!m) return VIDC_OK;
+    VIDC_TRY(wt_ensure_offsets(w));
     for (uint64_t i = 0; i < m; i++)
         if (list_nos[i] >= w->nlist || offs[i] >= w->offsets[list_nos[i] + 1] - w->offsets[list_nos[i]]) {
             set_error("wt select: (list %llu, offset %llu) out of range", (unsigned long long)list_nos[i],
@@ -1243,6 +1304,7 @@ int vidc_wt_select(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *
 int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,
                          uint64_t *out_offsets) {
     if (!ctx || !w || (m && !list_nos) || !out_offsets) return VIDC_ERR_INVALID;
+    VIDC_TRY(wt_ensure_offsets(w));
     out_offsets[0] = 0;
     for (uint64_t i = 0; i < m; i++) {
         if (list_nos[i] >= w->nlist) { set_error("list number out of range"); return VIDC_ERR_INVALID; }
@@ -1277,6 +1339,7 @@ int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint
 int vidc_wt_decode_gather(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
                           const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out) {
     if (!ctx || !w) return VIDC_ERR_INVALID;
+    VIDC_TRY(wt_ensure_offsets(w));
     return vidc_decode_gather_impl(ctx, w->nlist, m, list_nos, n_items, item_slot, item_off, ids_out,
                                    [&](uint64_t l) { return w->offsets[l + 1] - w->offsets[l]; },
                                    [&](uint64_t *d, uint64_t *lo) { return vidc_wt_decode_lists(ctx, w, m, list_nos, d, lo); });
