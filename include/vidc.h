@@ -286,6 +286,51 @@ int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint
 int vidc_wt_decode_gather(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
                           const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out);
 
+/* ------------------------------------------- device-resident requests (labels, graph nodes) */
+/* The decode section of a search that runs on the GPU: its labels (from a top-k) and its frontier (from an argmin) are device arrays
+ * already, and these calls take them as such (custom_invlists_impl.cpp:508-525 as one call; get_neighbors, altid_impl.cpp).
+ *
+ * Labels.  A label is Faiss's lo_build(list_no, offset) = list_no << 32 | offset.  d_ids[i] = get_ids(list_no)[offset]: the id that
+ *   vidc_*_decode_lists / vidc_*_decode_gather return for that pair, in the list's own order (sampling order for ROC, ascending for
+ *   Elias-Fano and the wavelet tree, input order for packed bits).  A negative label (Faiss's "no result") gives -1 and is not counted.
+ *   A label whose list is >= nlist, or whose offset is >= that list's size, is INVALID: it gives -1, and the call adds the number of
+ *   such labels to *d_invalid (a device uint64 the caller zeroes; NULL: not counted).  d_ids == d_labels is allowed (in place).
+ * Nodes.  A negative node gives a row of K times -1 and count 0, uncounted; a node >= N gives the same row and is counted in
+ *   *d_invalid.  Rows and counts of the other nodes are those of the host-node calls (vidc_*_decode_rows, vidc_compact_rows_decode),
+ *   which also fix which (object, K) pairs are accepted: K == 0 is rejected as there, a row with more than K edges fails as there.
+ * Device pointers live on the context's device and are read and written in order on the context's stream.  d_counts (device uint32[m])
+ *   and d_invalid may be NULL.  n == 0 / m == 0 returns VIDC_OK and launches nothing.  A NULL context or object, or a NULL array with
+ *   n > 0 / m > 0, returns VIDC_ERR_INVALID before any device work.
+ * Residency.  Packed bits, Elias-Fano and the wavelet tree (labels), compact rows and the rows of Elias-Fano graph objects with K >= the
+ *   object's K (nodes): the call only ENQUEUES work -- no host work proportional to n / m, no PCIe transfer, no wait -- and does not
+ *   update vidc_ctx_last_kernel_ms.  The first call on an object may build its lazy device tables as the host-array calls do (an
+ *   Elias-Fano graph object gets its per-list streams, ef_ensure_csr, when it is translated); the first call with a larger request than
+ *   the context has served before grows the context's request block in stream order (hipFreeAsync + hipMallocAsync on the
+ *   context's stream: no host wait).
+ *   ROC labels: the touched lists are marked and compacted on the device; their numbers (4 bytes per touched list, metadata: not
+ *   counted in vidc_ctx_d2h_bytes) are read back once, the host plans their decode as vidc_roc_decode_lists does, the ids are picked
+ *   on the device.  The call synchronises.
+ *   ROC rows: on the lean lane path (graph object, K >= its K, a request of thousands of nodes, lane kernels not switched off) the nodes
+ *   stay on the device (work list, counts and fix-up are kernels; the decode synchronises as vidc_roc_decode_rows does).  Other ROC
+ *   requests, and Elias-Fano rows of list objects or of K < the object's K, copy the nodes to the host once (D2H) and run the host-node
+ *   path (negative and invalid nodes ask it for the request's first valid node, whose row is then replaced by -1s), and wait.
+ * The objects are read-only: concurrent calls on one object from different contexts behave as the host-array calls do. */
+int vidc_packed_translate_labels_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                     uint64_t *d_invalid);
+int vidc_ef_translate_labels_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                 uint64_t *d_invalid);
+int vidc_wt_translate_labels_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                 uint64_t *d_invalid);
+int vidc_roc_translate_labels_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                  uint64_t *d_invalid);
+/* get_neighbors for a device-resident node array: d_nodes device int64[m], d_out device int32[m*K] (-1 padded). */
+int vidc_compact_rows_decode_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const int64_t *d_nodes, int32_t *d_out,
+                                 uint32_t *d_counts, uint64_t *d_invalid);
+int vidc_ef_decode_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,
+                            uint32_t *d_counts, uint64_t *d_invalid);
+int vidc_roc_decode_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,
+                             uint32_t *d_counts, uint64_t *d_invalid);
+
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,
  * measured with hipEvents on the context's stream (used by bench.py for the roofline figure). */

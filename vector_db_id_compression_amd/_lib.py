@@ -127,6 +127,12 @@ def _declare(lib):
     f("vidc_wt_decode_all", C.c_int, _vp, _vp, _vp)
     f("vidc_wt_decode_lists", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
     f("vidc_wt_decode_gather", C.c_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp)
+    # device-resident requests (labels, graph nodes)
+    for codec in ("packed", "ef", "wt", "roc"):
+        f(f"vidc_{codec}_translate_labels_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_compact_rows_decode_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
+    f("vidc_ef_decode_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp)
+    f("vidc_roc_decode_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp)
 
 
 #: every symbol include/vidc.h declares (checked by the CPU test-suite against the built library)
@@ -148,6 +154,8 @@ EXPORTED_SYMBOLS = [
     "vidc_compact_size_in_bytes", "vidc_compact_rows_decode", "vidc_compact_export_row",
     "vidc_wt_build", "vidc_wt_destroy", "vidc_wt_size_in_bytes", "vidc_wt_levels", "vidc_wt_select",
     "vidc_wt_decode_all", "vidc_wt_decode_lists", "vidc_wt_decode_gather", "vidc_wt_build_dev", "vidc_wt_offsets",
+    "vidc_packed_translate_labels_dev", "vidc_ef_translate_labels_dev", "vidc_wt_translate_labels_dev", "vidc_roc_translate_labels_dev",
+    "vidc_compact_rows_decode_dev", "vidc_ef_decode_rows_dev", "vidc_roc_decode_rows_dev",
 ]
 
 

@@ -35,7 +35,10 @@ class _GraphBase:
         return out.cpu().numpy(), cnt
 
     def get_neighbors_device(self, nodes):
-        """The same with the rows left in HBM: int32 [m, K] CUDA tensor, -1 padded (no edge counts cross PCIe)."""
+        """The same with the rows left in HBM: int32 [m, K] CUDA tensor, -1 padded (no edge counts cross PCIe).  `nodes` may be a CUDA
+        tensor (a frontier from a GPU argmin): it stays on the device, and a negative node gives a row of -1."""
+        if type(nodes).__module__.split(".")[0] == "torch" and nodes.is_cuda:
+            return self._c.decode_rows(nodes, self.K, want_counts=False)[0]
         return self._c.decode_rows(np.asarray(nodes, dtype=np.uint64), self.K, want_counts=False)[0]
 
 

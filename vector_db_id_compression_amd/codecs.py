@@ -75,6 +75,68 @@ def _dev_ids(ids, ntotal):
 
 
 
+def _is_cuda(x):
+    """a CUDA tensor (a device-resident request)"""
+    return type(x).__module__.split(".")[0] == "torch" and x.is_cuda
+
+
+def _on_torch_stream(ctx):
+    """The producer of a device-resident request is torch's current stream: the default context follows it, as
+    _lib.default_context does when it hands the context out."""
+    torch = _torch()
+    if _lib._default_ctx.get(torch.cuda.current_device()) is ctx:
+        ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+
+
+def _dev_array(x, ctx, what):
+    """x as a contiguous CUDA tensor on the context's device (real exceptions: the C call reads 8 bytes per entry)."""
+    want = getattr(ctx, "device", -1)
+    want = _torch().cuda.current_device() if want is None or want < 0 else want
+    if x.device.index != want:
+        raise ValueError(f"{what} live on cuda:{x.device.index}, the context on cuda:{want}")
+    return x.contiguous()
+
+
+def _translate_labels(fn, obj, labels, out, invalid):
+    """vidc_*_translate_labels_dev: Faiss labels (list_no << 32 | offset, -1 = no result) -> ids, on the device.  labels: int64 CUDA
+    tensor of any shape; out (optional, may be labels itself): int64 CUDA tensor of the same size; invalid (optional): 1-element int64
+    CUDA tensor the number of invalid labels is added to.  Nothing is synchronised (ROC plans on the host: it waits)."""
+    torch = _torch()
+    if not _is_cuda(labels) or labels.dtype != torch.int64:
+        raise TypeError("labels must be an int64 CUDA tensor")
+    if out is not None and out is labels and not labels.is_contiguous():
+        raise ValueError("in-place translation needs contiguous labels")
+    lab = _dev_array(labels, obj.ctx, "labels")
+    if out is None:
+        out = torch.empty_like(lab)
+    elif not _is_cuda(out) or out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != lab.numel():
+        raise ValueError("out must be a contiguous int64 CUDA tensor with one entry per label")
+    elif out.device != lab.device:
+        raise ValueError("out and labels must live on the same device")
+    if invalid is not None and (not _is_cuda(invalid) or invalid.dtype != torch.int64 or invalid.numel() != 1
+                                or not invalid.is_contiguous() or invalid.device != lab.device):
+        raise ValueError("invalid must be a 1-element int64 CUDA tensor on the labels' device")
+    _on_torch_stream(obj.ctx)
+    check(fn(obj.ctx.h, obj.h, lab.numel(), ptr(lab) if lab.numel() else None, ptr(out) if lab.numel() else None, ptr(invalid)))
+    return out
+
+
+def _decode_rows_dev(fn, obj, nodes, K, want_counts, pass_K=True):
+    """vidc_*_decode_rows_dev / vidc_compact_rows_decode_dev: rows of a CUDA tensor of nodes (-1 rows for negative nodes and nodes
+    >= N) -> (int32 [m, K] CUDA tensor, int32 CUDA counts or None)."""
+    torch = _torch()
+    if nodes.dtype.is_floating_point or nodes.dtype == torch.bool:
+        raise TypeError("nodes must be an integer CUDA tensor")
+    nd = _dev_array(nodes.reshape(-1).long(), obj.ctx, "nodes")
+    m = nd.numel()
+    out = torch.empty((max(m, 1), K), dtype=torch.int32, device=nd.device)
+    counts = torch.empty(max(m, 1), dtype=torch.int32, device=nd.device) if want_counts else None
+    _on_torch_stream(obj.ctx)
+    args = (obj.ctx.h, obj.h, m, ptr(nd) if m else None) + ((K,) if pass_K else ()) + (ptr(out), ptr(counts), None)
+    check(fn(*args))
+    return out[:m], (counts[:m] if want_counts else None)
+
+
 def _decode_gather(fn, obj, list_nos, item_slot, item_off):
     """vidc_*_decode_gather: decode the touched lists on the device, pick the requested ids there, copy 8 bytes per item
     (the decode section of the deferred search, custom_invlists_impl.cpp:508-525) -> numpy int64[n_items]."""
@@ -246,11 +308,19 @@ class RocLists:
         8 bytes per result copied to the host (vidc_roc_decode_gather)."""
         return _decode_gather(lib().vidc_roc_decode_gather, self, list_nos, item_slot, item_off)
 
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels (int64 CUDA tensor, list_no << 32 | offset) -> ids (int64 CUDA tensor), on the device: the decode section of
+        a search whose labels come from a GPU top-k (vidc_roc_translate_labels_dev).  Negative labels and labels outside the
+        object give -1; the latter are added to `invalid` (optional 1-element int64 CUDA tensor).  `out` may be `labels`."""
+        return _translate_labels(lib().vidc_roc_translate_labels_dev, self, labels, out, invalid)
+
     def decode_rows(self, nodes, K=None, want_counts=True):
         """-> (int32 [m, K] CUDA tensor, -1 padded; edge counts or None).  `want_counts=False` keeps the per-node
         edge counts on the device (no metadata crosses PCIe)."""
         torch = _torch()
         K = K or self.K
+        if nodes is not None and _is_cuda(nodes):  # device nodes (vidc_roc_decode_rows_dev): counts stay on the device too
+            return _decode_rows_dev(lib().vidc_roc_decode_rows_dev, self, nodes, K, want_counts)
         if nodes is None:  # every node, in order: no index array at all
             nd, m = None, self.nlist
         else:
@@ -353,6 +423,12 @@ class PackedLists:
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
         8 bytes per result copied to the host (vidc_packed_decode_gather)."""
         return _decode_gather(lib().vidc_packed_decode_gather, self, list_nos, item_slot, item_off)
+
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels (int64 CUDA tensor, list_no << 32 | offset) -> ids (int64 CUDA tensor), on the device: the decode section of
+        a search whose labels come from a GPU top-k (vidc_packed_translate_labels_dev).  Negative labels and labels outside the
+        object give -1; the latter are added to `invalid` (optional 1-element int64 CUDA tensor).  `out` may be `labels`."""
+        return _translate_labels(lib().vidc_packed_translate_labels_dev, self, labels, out, invalid)
 
     def get(self, list_nos, offs):
         ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
@@ -489,6 +565,8 @@ class EfLists:
         edge counts on the device."""
         torch = _torch()
         K = K or self.K
+        if nodes is not None and _is_cuda(nodes):  # device nodes (vidc_ef_decode_rows_dev): counts stay on the device too
+            return _decode_rows_dev(lib().vidc_ef_decode_rows_dev, self, nodes, K, want_counts)
         if nodes is None:  # every node, in order
             nd, m = None, self._nlist if self._offsets is None else self._offsets.size - 1
         else:
@@ -513,6 +591,12 @@ class EfLists:
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
         8 bytes per result copied to the host (vidc_ef_decode_gather)."""
         return _decode_gather(lib().vidc_ef_decode_gather, self, list_nos, item_slot, item_off)
+
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels (int64 CUDA tensor, list_no << 32 | offset) -> ids (int64 CUDA tensor), on the device: the decode section of
+        a search whose labels come from a GPU top-k (vidc_ef_translate_labels_dev).  Negative labels and labels outside the
+        object give -1; the latter are added to `invalid` (optional 1-element int64 CUDA tensor).  `out` may be `labels`."""
+        return _translate_labels(lib().vidc_ef_translate_labels_dev, self, labels, out, invalid)
 
     # -- flat on-disk / wire image (the reference keeps compressed lists in memory only, SURVEY 5)
     def save(self, path):
@@ -592,8 +676,11 @@ class CompactRows:
         return int(lib().vidc_compact_size_in_bytes(self.h))
 
     def decode_rows(self, nodes, K=None, want_counts=True):
-        """nodes=None: every node in order (no index array)."""
+        """nodes=None: every node in order (no index array).  A CUDA tensor of nodes takes vidc_compact_rows_decode_dev: the counts
+        then come back as an int32 CUDA tensor (or None)."""
         torch = _torch()
+        if nodes is not None and _is_cuda(nodes):
+            return _decode_rows_dev(lib().vidc_compact_rows_decode_dev, self, nodes, self.K, want_counts, pass_K=False)
         if nodes is None:
             nd, m = None, self.N
         else:
@@ -682,6 +769,12 @@ class WaveletTreeLists:
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
         8 bytes per result copied to the host (vidc_wt_decode_gather)."""
         return _decode_gather(lib().vidc_wt_decode_gather, self, list_nos, item_slot, item_off)
+
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels (int64 CUDA tensor, list_no << 32 | offset) -> ids (int64 CUDA tensor), on the device: the decode section of
+        a search whose labels come from a GPU top-k (vidc_wt_translate_labels_dev).  Negative labels and labels outside the
+        object give -1; the latter are added to `invalid` (optional 1-element int64 CUDA tensor).  `out` may be `labels`."""
+        return _translate_labels(lib().vidc_wt_translate_labels_dev, self, labels, out, invalid)
 
     def select(self, list_nos, offs):
         ln = np.ascontiguousarray(list_nos, dtype=np.uint64)

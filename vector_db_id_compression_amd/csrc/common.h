@@ -200,6 +200,14 @@ struct Pinned {
 int gather_to_host(::vidc_ctx *c, const uint64_t *d_ids, const uint64_t *list_off, uint64_t m, uint64_t n_items,
                    const uint64_t *item_slot, const uint64_t *item_off, int64_t *host_out);
 
+// Device scratch of the calls that only enqueue work (the *_dev request calls of requests.h): one block owned by the context and
+// reused in stream order.  req_scratch makes the context's stream wait (hipStreamWaitEvent, no host wait) for the previous user of
+// the block, so a context moved to another stream in between does not overwrite a block that is still being read; req_done
+// records that use.  A call that needs more than the block holds grows it in stream order (hipFreeAsync + hipMallocAsync on the
+// context's stream): no host wait either.
+int req_scratch(::vidc_ctx *c, size_t bytes, void **p);
+int req_done(::vidc_ctx *c);
+
 }  // namespace vidc
 
 // mt19937(1234) words available to the kernels for ANS stack underflow (codec.h:16-18,32-40).
@@ -259,6 +267,11 @@ struct vidc_ctx {
     // largest list universe (last id) the Elias-Fano encoder has met on this context: sizes the streams of the next object before
     // its ids have been looked at (ef_encode_fast)
     uint64_t ef_universe_hint = 0;
+    // scratch of the enqueue-only request calls (req_scratch): the block, its size, the event behind its last use
+    void *d_req = nullptr;
+    size_t req_bytes = 0;
+    hipEvent_t ev_req = nullptr;
+    bool req_pending = false;
 };
 
 // vidc_*_decode_gather (include/vidc.h): decode the m touched lists into staging from the context's block cache, pick the

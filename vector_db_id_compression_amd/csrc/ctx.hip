@@ -136,6 +136,37 @@ __global__ void k_gather_ids(const uint64_t *__restrict__ ids, const uint64_t *_
     if (i < n) out[i] = (int64_t)ids[pos[i]];
 }
 
+int req_scratch(::vidc_ctx *c, size_t bytes, void **p) {
+    // (the previous user of the block, on whichever stream the context had then, comes first on this call's stream)
+    if (c->req_pending) VIDC_HIP(hipStreamWaitEvent(c->stream, c->ev_req, 0));
+    if (bytes > c->req_bytes) {
+        // grown in stream order: hipFree would wait for the whole device, the stream-ordered pair waits for nothing on the host
+        if (c->d_req) VIDC_HIP(hipFreeAsync(c->d_req, c->stream));
+        c->d_req = nullptr;
+        c->req_bytes = 0;
+        const size_t want = std::max<size_t>(bytes + bytes / 4, (size_t)1 << 16);  // (request sizes drift between calls)
+        VIDC_HIP(hipMallocAsync(&c->d_req, want, c->stream));
+        c->req_bytes = want;
+    }
+    *p = c->d_req;
+    return VIDC_OK;
+}
+// the block back to the device's pool, behind its last use (vidc_ctx_trim, vidc_ctx_destroy): on stream s, which the caller then waits for
+static int req_release(::vidc_ctx *c, hipStream_t s) {
+    if (!c->d_req) return VIDC_OK;
+    if (c->req_pending) VIDC_HIP(hipStreamWaitEvent(s, c->ev_req, 0));
+    VIDC_HIP(hipFreeAsync(c->d_req, s));
+    c->d_req = nullptr;
+    c->req_bytes = 0;
+    c->req_pending = false;
+    return VIDC_OK;
+}
+int req_done(::vidc_ctx *c) {
+    VIDC_HIP(hipEventRecord(c->ev_req, c->stream));
+    c->req_pending = true;
+    return VIDC_OK;
+}
+
 int gather_to_host(::vidc_ctx *c, const uint64_t *d_ids, const uint64_t *list_off, uint64_t m, uint64_t n_items,
                    const uint64_t *item_slot, const uint64_t *item_off, int64_t *host_out) {
     if (!n_items) return VIDC_OK;
@@ -207,6 +238,7 @@ int vidc_ctx_create(int device, vidc_ctx **out) {
         [&] { for (auto &ev : c->tev) if (hipEventCreate(&ev) != hipSuccess) return true; return false; }() ||
         [&] { for (auto &ev : c->ev_pre) if (hipEventCreate(&ev) != hipSuccess) return true; return false; }() ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_req, hipEventDisableTiming) != hipSuccess ||
         [&] { for (auto &ev : c->ev_join) if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return true; return false; }() ||
         hipMalloc((void **)&c->d_mt, VIDC_MT_TABLE * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc(&c->d_ltab, (VIDC_LANE_TAB + 1) * 16) != hipSuccess) {
@@ -265,6 +297,8 @@ void vidc_ctx_destroy(vidc_ctx *c) {
     for (auto &ev : c->tev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_pre) if (ev) (void)hipEventDestroy(ev);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->d_req && c->own_stream && vidc::req_release(c, c->own_stream) == VIDC_OK) (void)vidc::vidc_stream_wait(c->own_stream);
+    if (c->ev_req) (void)hipEventDestroy(c->ev_req);
     for (int i = 0; i < VIDC_NAUX; i++) {
         if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
         if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]);
@@ -310,6 +344,11 @@ int vidc_ctx_trim(vidc_ctx *c, uint64_t *freed_bytes) {
                 b.p = nullptr;
                 b.bytes = 0;
             }
+    }
+    if (c->d_req) {
+        freed += c->req_bytes;
+        VIDC_TRY(vidc::req_release(c, c->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(c->stream));
     }
     for (auto &b : c->ppool)
         if (!b.in_use && b.p) {

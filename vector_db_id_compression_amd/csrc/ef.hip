@@ -18,6 +18,7 @@
 #include "dev_offsets.h"
 #include "scan.h"
 #include "rows_csr.h"
+#include "requests.h"
 #include "rows_tile.h"
 #include "wave.h"
 
@@ -1541,6 +1542,130 @@ __global__ void __launch_bounds__(64) k_ef_get(const uint64_t *low, const uint64
     }
 }
 
+#ifndef VIDC_EF_TRANSLATE_WAVE
+#define VIDC_EF_TRANSLATE_WAVE 0  // 1: vidc_ef_translate_labels_dev runs the wave form (A/B builds only)
+#endif
+// Faiss labels -> ids (vidc_ef_translate_labels_dev): ef->select(offset) of k_ef_get with the label decode and the checks in front of
+// its loads.  labels and ids may be the same array (a label is read before its id is written, by the same wavefront).
+// Wave form: one wavefront per label, k_ef_get's 64-lane popcount scan over one batch of 64 high words.
+__global__ void __launch_bounds__(64) k_ef_translate_wave(const uint64_t *__restrict__ low, const uint64_t *__restrict__ high,
+                                                          const uint64_t *__restrict__ low_off, const uint64_t *__restrict__ high_off,
+                                                          const uint32_t *__restrict__ lbits, const uint64_t *__restrict__ batch_off,
+                                                          const uint32_t *__restrict__ hrank, const uint64_t *__restrict__ offsets,
+                                                          uint64_t nlist, uint64_t n, const int64_t *labels, int64_t *ids,
+                                                          unsigned long long *invalid) {
+    const uint32_t lane = lane_id();
+    for (uint64_t q = blockIdx.x; q < n; q += gridDim.x) {
+        uint64_t l = 0, i = 0;
+        const bool pos = req_label(labels[q], l, i);
+        const bool ok = pos && l < nlist && i < offsets[l + 1] - offsets[l];
+        req_count_invalid(lane == 0 && pos && !ok, invalid);
+        int64_t res = -1;
+        if (ok) {
+            const uint32_t b = lbits[l];
+            const uint64_t *hw = high + high_off[l];
+            const uint64_t nhw = high_off[l + 1] - high_off[l];
+            const uint32_t *hr = hrank + batch_off[l];
+            const uint64_t nb = batch_off[l + 1] - batch_off[l];
+            uint64_t lo = 0, hi = nb;  // largest batch with hrank <= i
+            while (hi - lo > 1) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (hr[mid] <= i) lo = mid; else hi = mid;
+            }
+            const uint64_t w0 = lo * 64;
+            const uint64_t wi = w0 + lane;
+            const uint64_t word = wi < nhw ? hw[wi] : 0ull;
+            const uint32_t c = popc64(word);
+            uint32_t incl = c;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                uint32_t v = (uint32_t)__shfl_up((int)incl, o, 64);
+                if (lane >= (uint32_t)o) incl += v;
+            }
+            const uint64_t need = i - hr[lo];
+            const uint64_t hit = ballot((uint64_t)incl > need);
+            if (hit) {
+                const uint32_t wl_ = ff1(hit);
+                uint32_t k = (uint32_t)need - (rl(incl, wl_) - rl(c, wl_));
+                uint64_t ww = rl64((uint32_t)word, (uint32_t)(word >> 32), wl_);
+                for (; k; k--) ww &= ww - 1;
+                const uint64_t p = (w0 + wl_) * 64 + (uint32_t)__builtin_ctzll(ww);
+                res = (int64_t)(((p - i) << b) | read_bits(low + low_off[l], i * b, b));
+            }
+        }
+        if (lane == 0) ids[q] = res;
+    }
+}
+
+// Group form: 16 lanes per label, four labels per wavefront.  An IVF list of ~10^3 ids has ONE batch of 64 high words; lane j of a
+// group holds words 4j .. 4j + 3 of the label's batch, the group scans its 16 popcount sums, and the lane whose four words hold the
+// wanted one bit finds it among them.
+__global__ void __launch_bounds__(256) k_ef_translate_g16(const uint64_t *__restrict__ low, const uint64_t *__restrict__ high,
+                                                          const uint64_t *__restrict__ low_off, const uint64_t *__restrict__ high_off,
+                                                          const uint32_t *__restrict__ lbits, const uint64_t *__restrict__ batch_off,
+                                                          const uint32_t *__restrict__ hrank, const uint64_t *__restrict__ offsets,
+                                                          uint64_t nlist, uint64_t n, const int64_t *labels, int64_t *ids,
+                                                          unsigned long long *invalid) {
+    const uint32_t lane = lane_id(), g = lane >> 4, j = lane & 15u;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t q0 = wave * 4u; q0 < n; q0 += nwaves * 4u) {  // (q0: wavefront-uniform)
+        const uint64_t q = q0 + g;
+        uint64_t l = 0, i = 0;
+        const bool pos = req_label(q < n ? labels[q] : -1, l, i);
+        const bool ok = pos && l < nlist && i < offsets[l + 1] - offsets[l];
+        req_count_invalid(j == 0 && pos && !ok, invalid);
+        uint64_t w[4] = {0ull, 0ull, 0ull, 0ull};
+        uint64_t w0 = 0, need = 0;
+        uint32_t b = 0, c = 0;
+        if (ok) {
+            b = lbits[l];
+            const uint64_t *hw = high + high_off[l];
+            const uint64_t nhw = high_off[l + 1] - high_off[l];
+            const uint32_t *hr = hrank + batch_off[l];
+            const uint64_t nb = batch_off[l + 1] - batch_off[l];
+            uint64_t lo = 0, hi = nb;  // largest batch with hrank <= i
+            while (hi - lo > 1) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (hr[mid] <= i) lo = mid; else hi = mid;
+            }
+            w0 = lo * 64 + 4u * j;
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = w0 + k < nhw ? hw[w0 + k] : 0ull;
+            c = popc64(w[0]) + popc64(w[1]) + popc64(w[2]) + popc64(w[3]);
+            need = i - hr[lo];
+        }
+        uint32_t incl = c;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)incl, o, 16);
+            if (j >= (uint32_t)o) incl += v;
+        }
+        const uint32_t hit = (uint32_t)(ballot(ok && (uint64_t)incl > need) >> (16u * g)) & 0xffffu;
+        if (hit && j == ff1(hit)) {
+            uint32_t k = (uint32_t)need - (incl - c);
+            // (no dynamic index into w[]: it would live in scratch)
+            uint64_t ww = w[0];
+            uint32_t ws = 0;
+            const uint32_t p0 = popc64(w[0]);
+            if (k >= p0) {
+                k -= p0; ww = w[1]; ws = 1;
+                const uint32_t p1 = popc64(w[1]);
+                if (k >= p1) {
+                    k -= p1; ww = w[2]; ws = 2;
+                    const uint32_t p2 = popc64(w[2]);
+                    if (k >= p2) { k -= p2; ww = w[3]; ws = 3; }
+                }
+            }
+            for (; k; k--) ww &= ww - 1;
+            const uint64_t p = (w0 + ws) * 64 + (uint32_t)__builtin_ctzll(ww);
+            ids[q] = (int64_t)(((p - i) << b) | read_bits(low + low_off[l], i * b, b));
+        } else if (!hit && j == 0 && q < n) {
+            ids[q] = -1;
+        }
+    }
+}
+
 
 // ---- per-list geometry and work-item tables, built on the device
 // elias_fano.hpp:28-29 per list; word counts of the two streams and of the select directory
@@ -2392,26 +2517,12 @@ static void ef_rows_geometry(uint32_t K, uint32_t ubound, uint32_t *LW, uint32_t
     *HW = (3u * K + 1u + 63u) / 64u;
 }
 
-// graph object, every requested row at most K wide: one row per lane from the arena
-static int ef_decode_rows_arena(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *nodes, uint32_t K, int32_t *d_out,
-                                uint32_t *counts) {
-    VIDC_HIP(hipSetDevice(ctx->device));
-    Scratch s_n, s_c;
-    Pinned h_io;
-    const uint64_t *d_nodes = nullptr;  // nodes == NULL: rows 0..m-1, no index array
-    if (nodes || counts) VIDC_TRY(h_io.get(ctx, m * 8));
-    if (nodes) {
-        VIDC_TRY(s_n.get(ctx, m * 8));
-        std::memcpy(h_io.p, nodes, m * 8);
-        VIDC_HIP(hipMemcpyAsync(s_n.p, h_io.p, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_nodes = s_n.as<uint64_t>();
-    }
-    if (counts) VIDC_TRY(s_c.get(ctx, m * 4));
+// the arena row decoder of a graph object for m rows (d_nodes == NULL: rows 0..m-1; d_cnt may be NULL)
+static int ef_rows_arena_launch(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *d_nodes, uint32_t K, int32_t *d_out,
+                                uint32_t *d_cnt) {
     const uint32_t S = e->a_lw + e->a_hw;
     const size_t dyn = ((size_t)64 * (S | 1u) + 1) * 8;
     const dim3 grid(tile_grid(ctx->num_cu, (m + 63) / 64, (uint32_t)std::min<size_t>(16, (150u << 10) / (dyn + 4608 + 256))));
-    uint32_t *d_cnt = counts ? s_c.as<uint32_t>() : nullptr;
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     const bool quad = (K & 3u) == 0u && ((uintptr_t)d_out & 15u) == 0;
 #define VIDC_EF_ROWS_DEC2(KP, HWC, Q)                                                                                                  \
     hipLaunchKernelGGL((k_ef_rows_decode_tile<KP, HWC, Q>), grid, dim3(64), dyn, ctx->stream, e->d_arena.p, e->d_rmeta.p, m, d_nodes, K, \
@@ -2432,6 +2543,26 @@ static int ef_decode_rows_arena(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, con
 #undef VIDC_EF_ROWS_DEC
 #undef VIDC_EF_ROWS_DEC2
     VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
+// graph object, every requested row at most K wide: one row per lane from the arena
+static int ef_decode_rows_arena(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *nodes, uint32_t K, int32_t *d_out,
+                                uint32_t *counts) {
+    VIDC_HIP(hipSetDevice(ctx->device));
+    Scratch s_n, s_c;
+    Pinned h_io;
+    const uint64_t *d_nodes = nullptr;  // nodes == NULL: rows 0..m-1, no index array
+    if (nodes || counts) VIDC_TRY(h_io.get(ctx, m * 8));
+    if (nodes) {
+        VIDC_TRY(s_n.get(ctx, m * 8));
+        std::memcpy(h_io.p, nodes, m * 8);
+        VIDC_HIP(hipMemcpyAsync(s_n.p, h_io.p, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_nodes = s_n.as<uint64_t>();
+    }
+    if (counts) VIDC_TRY(s_c.get(ctx, m * 4));
+    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    VIDC_TRY(ef_rows_arena_launch(ctx, e, m, d_nodes, K, d_out, counts ? s_c.as<uint32_t>() : nullptr));
     VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     if (counts) VIDC_HIP(hipMemcpyAsync(h_io.p, s_c.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
@@ -2540,6 +2671,38 @@ int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_
     ctx->last_kernel_ms = ms;
     *out = e.release();
     return VIDC_OK;
+}
+
+int vidc_ef_translate_labels_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                 uint64_t *d_invalid) {
+    VIDC_TRY(req_check_labels(ctx, e, n, d_labels, d_ids));
+    if (!n) return VIDC_OK;
+    VIDC_TRY(ef_ensure_csr(ctx, e));  // (graph objects: the per-list streams, on the first call that needs them)
+    VIDC_HIP(hipSetDevice(ctx->device));
+#if VIDC_EF_TRANSLATE_WAVE  // (the wave-per-label form, kept for the A/B of tools/bench_device_requests.py)
+    hipLaunchKernelGGL(k_ef_translate_wave, dim3((uint32_t)std::min<uint64_t>(n, 1u << 20)), dim3(64), 0, ctx->stream, e->d_low.p,
+                       e->d_high.p, e->d_low_off.p, e->d_high_off.p, e->d_lbits.p, e->d_batch_off.p, e->d_hrank.p, e->d_offsets.p,
+                       e->nlist, n, d_labels, d_ids, (unsigned long long *)d_invalid);
+#else
+    hipLaunchKernelGGL(k_ef_translate_g16, req_grid(ctx, n, 16), dim3(256), 0, ctx->stream, e->d_low.p, e->d_high.p, e->d_low_off.p,
+                       e->d_high_off.p, e->d_lbits.p, e->d_batch_off.p, e->d_hrank.p, e->d_offsets.p, e->nlist, n, d_labels, d_ids,
+                       (unsigned long long *)d_invalid);
+#endif
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
+int vidc_ef_decode_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,
+                            uint32_t *d_counts, uint64_t *d_invalid) {
+    VIDC_TRY(req_check_rows(ctx, e, m, d_nodes, d_out));
+    if (K == 0) { set_error("K=0 unsupported"); return VIDC_ERR_INVALID; }  // (as vidc_ef_decode_rows)
+    if (!m) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    if (e->arena && K >= e->K)  // rows of a graph object never exceed its K: the arena decoder, on the device
+        return req_rows_on_device<uint64_t>(ctx, e->nlist, m, d_nodes, K, d_out, d_counts, d_invalid, false,
+                                            [&](const uint64_t *nd, uint32_t *cnt) { return ef_rows_arena_launch(ctx, e, m, nd, K, d_out, cnt); });
+    return req_rows_via_host(ctx, e->nlist, m, d_nodes, K, d_out, d_counts, d_invalid,
+                             [&](const uint64_t *hn, uint32_t *hc) { return vidc_ef_decode_rows(ctx, e, m, hn, K, d_out, hc); });
 }
 
 int vidc_ef_get(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *list_nos, const uint64_t *offs,

@@ -14,6 +14,7 @@
 #include "chunks.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "requests.h"
 #include "rows_tile.h"
 #include "scan.h"
 
@@ -309,6 +310,23 @@ __global__ void k_packed_get(const uint64_t *words, const uint64_t *word_off, ui
                              const uint64_t *list_nos, const uint64_t *offs, int64_t *out) {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q < m) out[q] = (int64_t)read_bits(words + word_off[list_nos[q]], offs[q] * bits, bits);
+}
+
+// Faiss labels -> ids (vidc_packed_translate_labels_dev): k_packed_get with the label decode and the checks in front of its loads, one
+// thread per label.  labels and ids may be the same array (each thread reads its label before it writes its id).
+__global__ void __launch_bounds__(256) k_packed_translate(const uint64_t *__restrict__ words, const uint64_t *__restrict__ word_off,
+                                                          const uint64_t *__restrict__ offsets, uint64_t nlist, uint32_t bits, uint64_t n,
+                                                          const int64_t *labels, int64_t *ids, unsigned long long *invalid) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
+        const uint64_t i = i0 + lane_id();
+        uint64_t l = 0, off = 0;
+        const bool pos = req_label(i < n ? labels[i] : -1, l, off);
+        const bool ok = pos && l < nlist && off < offsets[l + 1] - offsets[l];
+        const int64_t v = ok ? (int64_t)read_bits(words + word_off[l], off * bits, bits) : -1;
+        if (i < n) ids[i] = v;
+        req_count_invalid(pos && !ok, invalid);
+    }
 }
 
 // ---- CompactBitNSGGraph (altid_impl.cpp:20-51): row i occupies bytes [i*stride, (i+1)*stride); neighbours are
@@ -694,6 +712,29 @@ uint32_t vidc_compact_bits(const vidc_compact *c) { return c ? c->bits : 0; }
 uint32_t vidc_compact_stride(const vidc_compact *c) { return c ? c->stride : 0; }
 uint64_t vidc_compact_size_in_bytes(const vidc_compact *c) { return c ? c->N * c->stride : 0; }
 
+// the row decoder of a compact object for m rows (d_nodes == NULL: rows 0..m-1); d_cnt may be NULL only for the tile decoder
+static int compact_rows_launch(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const uint64_t *d_nodes, int32_t *d_out, uint32_t *d_cnt) {
+    const bool tile = c->K <= 64 && (c->stride & 3u) == 0u;
+    if (tile) {
+        const uint32_t SD = c->stride / 4u;
+        const size_t dyn = ((size_t)64 * (SD | 1u) + 1u) * 4u;
+        const dim3 tgrid(dev::tile_grid(ctx->num_cu, (m + 63) / 64, (uint32_t)std::min<size_t>(16, (150u << 10) / dyn)));
+        if ((c->K & 3u) == 0u && ((uintptr_t)d_out & 15u) == 0)
+            hipLaunchKernelGGL(k_compact_rows_decode_tile<true>, tgrid, dim3(64), dyn, ctx->stream, (const uint32_t *)c->d_data.p, c->N, c->K,
+                               c->bits, SD, dev::tile_magic(SD), m, d_nodes, d_out, d_cnt);
+        else
+            hipLaunchKernelGGL(k_compact_rows_decode_tile<false>, tgrid, dim3(64), dyn, ctx->stream, (const uint32_t *)c->d_data.p, c->N, c->K,
+                               c->bits, SD, dev::tile_magic(SD), m, d_nodes, d_out, d_cnt);
+    } else if (c->K <= 64)
+        hipLaunchKernelGGL(k_compact_rows_decode, dim3((uint32_t)std::min<uint64_t>((m + 3) / 4, (uint64_t)ctx->num_cu * 256)), dim3(64), 0, ctx->stream,
+                           c->d_data.p, c->N, c->K, c->bits, c->stride, m, d_nodes, d_out, d_cnt);
+    else
+        hipLaunchKernelGGL(k_compact_rows_decode_wide, dim3((uint32_t)std::min<uint64_t>(m, (uint64_t)ctx->num_cu * 256)), dim3(64), 0,
+                           ctx->stream, c->d_data.p, c->N, c->K, c->bits, c->stride, m, d_nodes, d_out, d_cnt);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
 int vidc_compact_rows_decode(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const uint64_t *nodes, int32_t *d_out,
                              uint32_t *counts) {
     if (!ctx || !c || (m && !d_out)) return VIDC_ERR_INVALID;
@@ -715,24 +756,7 @@ int vidc_compact_rows_decode(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, c
         d_nodes = s_n.as<uint64_t>();
     }
     VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    if (tile) {
-        const uint32_t SD = c->stride / 4u;
-        const size_t dyn = ((size_t)64 * (SD | 1u) + 1u) * 4u;
-        const dim3 tgrid(dev::tile_grid(ctx->num_cu, (m + 63) / 64, (uint32_t)std::min<size_t>(16, (150u << 10) / dyn)));
-        uint32_t *d_cnt = counts ? s_c.as<uint32_t>() : nullptr;
-        if ((c->K & 3u) == 0u && ((uintptr_t)d_out & 15u) == 0)
-            hipLaunchKernelGGL(k_compact_rows_decode_tile<true>, tgrid, dim3(64), dyn, ctx->stream, (const uint32_t *)c->d_data.p, c->N, c->K,
-                               c->bits, SD, dev::tile_magic(SD), m, d_nodes, d_out, d_cnt);
-        else
-            hipLaunchKernelGGL(k_compact_rows_decode_tile<false>, tgrid, dim3(64), dyn, ctx->stream, (const uint32_t *)c->d_data.p, c->N, c->K,
-                               c->bits, SD, dev::tile_magic(SD), m, d_nodes, d_out, d_cnt);
-    } else if (c->K <= 64)
-        hipLaunchKernelGGL(k_compact_rows_decode, dim3((uint32_t)std::min<uint64_t>((m + 3) / 4, (uint64_t)ctx->num_cu * 256)), dim3(64), 0, ctx->stream,
-                           c->d_data.p, c->N, c->K, c->bits, c->stride, m, d_nodes, d_out, s_c.as<uint32_t>());
-    else
-        hipLaunchKernelGGL(k_compact_rows_decode_wide, dim3((uint32_t)std::min<uint64_t>(m, (uint64_t)ctx->num_cu * 256)), dim3(64), 0,
-                           ctx->stream, c->d_data.p, c->N, c->K, c->bits, c->stride, m, d_nodes, d_out, s_c.as<uint32_t>());
-    VIDC_HIP(hipGetLastError());
+    VIDC_TRY(compact_rows_launch(ctx, c, m, d_nodes, d_out, (counts || !tile) ? s_c.as<uint32_t>() : nullptr));
     VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     if (counts) VIDC_HIP(hipMemcpyAsync(h_io.p, s_c.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
@@ -741,6 +765,16 @@ int vidc_compact_rows_decode(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, c
     (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     ctx->last_kernel_ms = ms;
     return VIDC_OK;
+}
+
+int vidc_compact_rows_decode_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const int64_t *d_nodes, int32_t *d_out,
+                                 uint32_t *d_counts, uint64_t *d_invalid) {
+    VIDC_TRY(req_check_rows(ctx, c, m, d_nodes, d_out));
+    if (!m) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const bool tile = c->K <= 64 && (c->stride & 3u) == 0u;  // (the other two decoders always write counts)
+    return req_rows_on_device<uint64_t>(ctx, c->N, m, d_nodes, c->K, d_out, d_counts, d_invalid, !tile,
+                                        [&](const uint64_t *nd, uint32_t *cnt) { return compact_rows_launch(ctx, c, m, nd, d_out, cnt); });
 }
 
 int vidc_compact_export_row(vidc_ctx *ctx, const vidc_compact *c, uint64_t node, uint8_t *bytes, size_t cap) {
@@ -1086,6 +1120,17 @@ int vidc_packed_get(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, const uint6
     VIDC_HIP(hipMemcpyAsync(ids_out, s_r.p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
     ctx->d2h_bytes += m * 8;
+    return VIDC_OK;
+}
+
+int vidc_packed_translate_labels_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                     uint64_t *d_invalid) {
+    VIDC_TRY(req_check_labels(ctx, p, n, d_labels, d_ids));
+    if (!n) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_packed_translate, req_grid(ctx, n), dim3(256), 0, ctx->stream, p->d_words.p, p->d_word_off.p, p->d_offsets.p,
+                       p->nlist, (uint32_t)p->bits, n, d_labels, d_ids, (unsigned long long *)d_invalid);
+    VIDC_HIP(hipGetLastError());
     return VIDC_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "rows_csr.h"
 #include "roc_lane.h"
 #include "roc_grp.h"
+#include "requests.h"
 #include "scan.h"
 
 using namespace vidc;
@@ -471,6 +472,7 @@ struct DecPlan {
     uint64_t implicit = 0;           // lean plan without a work list: items are rows 0..implicit-1
     const uint32_t *order_dev = nullptr;  // ... or every row of the object in this device-resident order, each to its OWN output row
     bool order_build = false;        // ... which this call builds first (k_rows_order_*, inside the call's timed region)
+    bool order_req = false;          // ... or order_dev is a work list in request order: item k -> output row k (device node requests)
     DecPlan() = default;
     DecPlan(const DecPlan &) = default;
     DecPlan(DecPlan &&) = default;
@@ -1840,7 +1842,7 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
     a.heads = r->d_heads.p; a.prec = r->d_prec.p; a.nwords = r->d_nwords.p; a.draws = r->d_draws.p;
     a.words = r->d_words.p; a.word_off = r->d_word_off.p;
     a.out = d_out; a.out_rows = d_out_rows; a.K = K;
-    a.out_by_list = (p.implicit && p.order_dev) ? 1u : 0u;
+    a.out_by_list = (p.implicit && p.order_dev && !p.order_req) ? 1u : 0u;
     a.scratch_words = s_scr.as<uint32_t>();
     a.slots = s_slots.as<uint32_t>();
     a.end_state = s_end.as<uint32_t>(); a.status = d_status;
@@ -2204,6 +2206,41 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
     return VIDC_OK;
 }
 
+// ---- device-resident label requests (vidc_roc_translate_labels_dev): ROC has no random access, so the touched lists are decoded.
+// mark[l] = size of list l and flag[l] = 1 for every list a valid label names (plain stores of the same value: idempotent, no atomics);
+// both arrays are cleared by the call.
+__global__ void __launch_bounds__(256) k_req_roc_mark(const int64_t *__restrict__ labels, uint64_t n, const uint64_t *__restrict__ offsets,
+                                                      uint64_t nlist, uint32_t *__restrict__ mark, uint32_t *__restrict__ flag,
+                                                      unsigned long long *invalid) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
+        const uint64_t i = i0 + lane_id();
+        uint64_t l = 0, off = 0;
+        const bool pos = req_label(i < n ? labels[i] : -1, l, off);
+        uint32_t sz = 0;
+        if (pos && l < nlist) sz = (uint32_t)(offsets[l + 1] - offsets[l]);
+        const bool ok = pos && l < nlist && off < sz;
+        if (ok) { mark[l] = sz; flag[l] = 1u; }
+        req_count_invalid(pos && !ok, invalid);
+    }
+}
+// touched[tpos[l]] = l for every flagged list: the touched list numbers in ascending order (tpos = exclusive scan of flag)
+__global__ void __launch_bounds__(256) k_req_roc_touched(const uint32_t *__restrict__ flag, const uint64_t *__restrict__ tpos, uint64_t nlist,
+                                                         uint32_t *__restrict__ touched) {
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x)
+        if (flag[l]) touched[tpos[l]] = (uint32_t)l;
+}
+// ids[i] = staging[stage_off[list] + offset] (stage_off = exclusive scan of mark: where each touched list was decoded to)
+__global__ void __launch_bounds__(256) k_req_roc_pick(const int64_t *labels, uint64_t n, const uint64_t *__restrict__ offsets, uint64_t nlist,
+                                                      const uint64_t *__restrict__ stage_off, const uint64_t *__restrict__ staging, int64_t *ids) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t l = 0, off = 0;
+        const bool pos = req_label(labels[i], l, off);
+        const bool ok = pos && l < nlist && off < offsets[l + 1] - offsets[l];
+        ids[i] = ok ? (int64_t)staging[stage_off[l] + off] : -1;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2522,6 +2559,96 @@ int vidc_roc_decode_rows(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const uin
     std::vector<uint64_t> out_off(m);
     for (size_t k = 0; k < m; k++) out_off[k] = (uint64_t)p.item[k] * K;
     return decode_impl(ctx, r, p, out_off.data(), nullptr, d_out, K);
+}
+
+int vidc_roc_translate_labels_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                  uint64_t *d_invalid) {
+    VIDC_TRY(req_check_labels(ctx, r, n, d_labels, d_ids));
+    if (!n) return VIDC_OK;
+    VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const uint64_t nlist = r->nlist;
+    Scratch s_mark, s_off, s_touched, s_t0, s_stage;
+    Pinned h_back;
+    VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));   // mark | flag
+    VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));    // stage_off | tpos
+    VIDC_TRY(s_touched.get(ctx, (nlist + 1) * 4));
+    uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
+    uint64_t *stage_off = s_off.as<uint64_t>(), *tpos = stage_off + nlist + 1;
+    VIDC_HIP(hipMemsetAsync(s_mark.p, 0, 2 * (nlist + 1) * 4, ctx->stream));  // (cached blocks hold stale marks, or poison)
+    hipLaunchKernelGGL(k_req_roc_mark, req_grid(ctx, n), dim3(256), 0, ctx->stream, d_labels, n, r->d_offsets.p, nlist, mark, flag,
+                       (unsigned long long *)d_invalid);
+    VIDC_HIP(hipGetLastError());
+    if (nlist) {
+        Scan4 sc{};
+        sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = tpos;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
+        hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, tpos, nlist, s_touched.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+    }
+    // the touched list numbers come back once (count, then the numbers: 4 bytes per touched list, metadata)
+    VIDC_TRY(h_back.get(ctx, 8 + (nlist + 1) * 4));
+    uint64_t *h_cnt = h_back.as<uint64_t>();
+    uint32_t *h_touched = (uint32_t *)(h_cnt + 1);
+    *h_cnt = 0;
+    if (nlist) VIDC_HIP(hipMemcpyAsync(h_cnt, tpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    const uint64_t cnt = *h_cnt;
+    std::vector<uint32_t> lists(cnt);
+    uint64_t total = 0;
+    std::vector<uint64_t> req_off(cnt + 1, 0);
+    if (cnt) {
+        VIDC_HIP(hipMemcpyAsync(h_touched, s_touched.p, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        for (uint64_t k = 0; k < cnt; k++) {  // (the same offsets k_req_roc_mark + the scan put into stage_off)
+            lists[k] = h_touched[k];
+            req_off[k + 1] = req_off[k] + (r->offsets[lists[k] + 1] - r->offsets[lists[k]]);
+        }
+        total = req_off[cnt];
+    }
+    VIDC_TRY(s_stage.get(ctx, (total ? total : 1) * 8));
+    if (cnt) {
+        DecPlan p;
+        plan_decode(r, lists, false, p, ctx->wide);
+        std::vector<uint64_t> out_off(cnt);
+        for (size_t k = 0; k < cnt; k++) out_off[k] = req_off[p.item[k]];  // work item k -> its place in the staging
+        VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+    }
+    hipLaunchKernelGGL(k_req_roc_pick, req_grid(ctx, n), dim3(256), 0, ctx->stream, d_labels, n, r->d_offsets.p, nlist, stage_off,
+                       s_stage.as<uint64_t>(), d_ids);
+    VIDC_HIP(hipGetLastError());
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    return VIDC_OK;
+}
+
+int vidc_roc_decode_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,
+                             uint32_t *d_counts, uint64_t *d_invalid) {
+    VIDC_TRY(req_check_rows(ctx, r, m, d_nodes, d_out));
+    if (K == 0) { set_error("K=0 unsupported"); return VIDC_ERR_UNSUPPORTED; }  // (as vidc_roc_decode_rows)
+    if (!m) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const bool lean = K <= TINY_MAX && r->rows && K >= r->K && r->nlist && !force_general() && lane_wanted(lane_policy(), m, LANE_MIN_TINY);
+    if (!lean)  // the plan of these shapes is built from the node numbers on the host
+        return req_rows_via_host(ctx, r->nlist, m, d_nodes, K, d_out, d_counts, d_invalid,
+                                 [&](const uint64_t *hn, uint32_t *hc) { return vidc_roc_decode_rows(ctx, r, m, hn, K, d_out, hc); });
+    // lean lane path: the sanitized nodes are the decoder's work list, in request order; counts from the offsets, on the device
+    Scratch s_wl;
+    VIDC_TRY(s_wl.get(ctx, m * 4));
+    hipLaunchKernelGGL(k_req_nodes_sanitize<uint32_t>, req_grid(ctx, m), dim3(256), 0, ctx->stream, d_nodes, m, r->nlist,
+                       s_wl.as<uint32_t>(), (unsigned long long *)d_invalid);
+    if (d_counts)
+        hipLaunchKernelGGL(k_gather_sizes<uint32_t>, dim3((uint32_t)std::min<uint64_t>((m + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                           r->d_offsets.p, s_wl.as<uint32_t>(), m, d_counts);
+    VIDC_HIP(hipGetLastError());
+    DecPlan p;
+    p.lean = true; p.tiny_lane = true; p.implicit = m;
+    p.count[DC_TINY] = m;
+    p.order_dev = s_wl.as<uint32_t>();
+    p.order_req = true;
+    VIDC_TRY(decode_impl(ctx, r, p, nullptr, nullptr, d_out, K));  // (ends with a synchronisation of the stream)
+    hipLaunchKernelGGL(k_req_rows_fixup, req_grid(ctx, m), dim3(256), 0, ctx->stream, d_nodes, m, r->nlist, K, d_out, d_counts);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
 }
 
 }  // extern "C"

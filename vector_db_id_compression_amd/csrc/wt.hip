@@ -25,6 +25,7 @@
 #include "bits.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "requests.h"
 #include "scan.h"
 
 using namespace vidc;
@@ -844,32 +845,50 @@ __device__ __forceinline__ void wt_use_tables(Bv &bv, const uint64_t *s_binom, c
     if constexpr (Bv::kRrr) { bv.binom = s_binom; bv.ow = s_ow; }
 }
 
-// one thread per query: id of the (k+1)-th element of list c
+// the walk of one select: position of the (pos+1)-th element of list c, from the root level down
 template <class View>
+__device__ __forceinline__ uint64_t wt_select_walk(const View &vw, const uint64_t *C, const uint32_t *__restrict__ nrank, uint32_t nlist,
+                                                   uint32_t L, uint32_t c, uint64_t pos, const uint64_t *s_binom, const uint8_t *s_ow) {
+    for (int level = (int)L - 1; level >= 0; level--) {
+        const uint32_t sh = L - (uint32_t)level;
+        const uint64_t p = sh >= 32 ? 0 : (uint64_t)(c >> sh);
+        const uint64_t s_lo = sh >= 32 ? 0 : (p << sh);
+        uint64_t s_hi = sh >= 32 ? nlist : ((p + 1) << sh);
+        if (s_hi > nlist) s_hi = nlist;
+        const uint64_t ns = C[s_lo], ne = C[s_hi];
+        const bool bit = (c >> (L - 1u - (uint32_t)level)) & 1u;
+        auto bv = vw.level((uint32_t)level);
+        wt_use_tables(bv, s_binom, s_ow);
+        const uint64_t r_ns = nrank[wt_nrank_base((uint32_t)level) + p];  // (== bv.rank_1(ns), from the build)
+        const uint64_t before = bit ? r_ns : ns - r_ns;
+        pos = bv.select_in(before + pos, bit, ns, ne) - ns;
+    }
+    return pos;
+}
+
+// one thread per query: id of the (k+1)-th element of list c.  LABELS (vidc_wt_translate_labels_dev): list_nos holds Faiss labels
+// (int64 list << 32 | offset; offs unused), checked against C before the walk starts; -1 for a negative or invalid label, the invalid
+// ones counted.  out may then be the labels array itself.
+template <class View, bool LABELS = false>
 __global__ void k_wt_select(View vw, const uint64_t *C, const uint32_t *__restrict__ nrank, uint32_t nlist, uint32_t L, uint64_t m,
-                            const uint64_t *list_nos, const uint64_t *offs, int64_t *out) {
+                            const uint64_t *list_nos, const uint64_t *offs, int64_t *out, unsigned long long *invalid = nullptr) {
     __shared__ uint64_t s_binom[View::kRrrView ? 64 * 64 : 1];
     __shared__ uint8_t s_ow[64];
     wt_stage_tables(vw, s_binom, s_ow);
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride) {
-        const uint32_t c = (uint32_t)list_nos[q];
-        uint64_t pos = offs[q];
-        for (int level = (int)L - 1; level >= 0; level--) {
-            const uint32_t sh = L - (uint32_t)level;
-            const uint64_t p = sh >= 32 ? 0 : (uint64_t)(c >> sh);
-            const uint64_t s_lo = sh >= 32 ? 0 : (p << sh);
-            uint64_t s_hi = sh >= 32 ? nlist : ((p + 1) << sh);
-            if (s_hi > nlist) s_hi = nlist;
-            const uint64_t ns = C[s_lo], ne = C[s_hi];
-            const bool bit = (c >> (L - 1u - (uint32_t)level)) & 1u;
-            auto bv = vw.level((uint32_t)level);
-            wt_use_tables(bv, s_binom, s_ow);
-            const uint64_t r_ns = nrank[wt_nrank_base((uint32_t)level) + p];  // (== bv.rank_1(ns), from the build)
-            const uint64_t before = bit ? r_ns : ns - r_ns;
-            pos = bv.select_in(before + pos, bit, ns, ne) - ns;
+    if constexpr (LABELS) {
+        for (uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); q0 < m; q0 += stride) {  // (q0: wavefront-uniform)
+            const uint64_t q = q0 + (threadIdx.x & 63u);
+            uint64_t l = 0, o = 0;
+            const bool nonneg = req_label(q < m ? (int64_t)list_nos[q] : -1, l, o);
+            const bool ok = nonneg && l < nlist && o < C[l + 1] - C[l];
+            req_count_invalid(nonneg && !ok, invalid);
+            if (ok) out[q] = (int64_t)wt_select_walk(vw, C, nrank, nlist, L, (uint32_t)l, o, s_binom, s_ow);
+            else if (q < m) out[q] = -1;
         }
-        out[q] = (int64_t)pos;
+    } else {
+        for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride)
+            out[q] = (int64_t)wt_select_walk(vw, C, nrank, nlist, L, (uint32_t)list_nos[q], offs[q], s_binom, s_ow);
     }
 }
 
@@ -1298,6 +1317,24 @@ int vidc_wt_select(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *
     VIDC_HIP(hipMemcpyAsync(ids_out, s_r.p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
     ctx->d2h_bytes += m * 8;
+    return VIDC_OK;
+}
+
+int vidc_wt_translate_labels_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                 uint64_t *d_invalid) {
+    VIDC_TRY(req_check_labels(ctx, w, n, d_labels, d_ids));
+    if (!n) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const dim3 sgrid((uint32_t)std::min<uint64_t>((n + 127) / 128, 1u << 16));
+    const uint64_t *lab = (const uint64_t *)d_labels;
+    unsigned long long *inv = (unsigned long long *)d_invalid;
+    if (w->wt_type == 1)
+        hipLaunchKernelGGL((k_wt_select<WtRrrView, true>), sgrid, dim3(128), 0, ctx->stream, rrr_view(w), w->d_C.p, w->d_nrank.p,
+                           (uint32_t)w->nlist, w->L, n, lab, (const uint64_t *)nullptr, d_ids, inv);
+    else
+        hipLaunchKernelGGL((k_wt_select<WtPlainView, true>), sgrid, dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p,
+                           (uint32_t)w->nlist, w->L, n, lab, (const uint64_t *)nullptr, d_ids, inv);
+    VIDC_HIP(hipGetLastError());
     return VIDC_OK;
 }
 

@@ -89,6 +89,11 @@ class InvertedListsArrayCodes:
         (slot in list_nos, offset) items, picked on the device; numpy int64."""
         return self._c.decode_gather(np.asarray(list_nos, dtype=np.uint64), item_slot, item_off)
 
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels of a search (int64 CUDA tensor, list_no << 32 | offset) -> ids, on the device, in place when out is labels:
+        the loop of custom_invlists_impl.cpp:508-525 for a caller whose labels come from a GPU top-k (codec translate_labels)."""
+        return self._c.translate_labels(labels, out=out, invalid=invalid)
+
 
 class CompressedIDInvertedListsPackedBits(InvertedListsArrayCodes):
     """custom_invlists_impl.cpp:64-118."""

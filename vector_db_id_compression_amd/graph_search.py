@@ -16,10 +16,19 @@ class RawGraph:
         return out, (out >= 0).sum(1).astype(np.uint32)
 
     def get_neighbors_device(self, nodes):
+        """rows of `nodes` as an int32 CUDA tensor; a CUDA tensor of nodes stays on the device, and its nodes outside [0, N) give a row
+        of -1 (as the compressed graphs do)"""
         import torch
 
         if getattr(self, "_dev", None) is None:
             self._dev = torch.from_numpy(self.rows).cuda()
+        if isinstance(nodes, torch.Tensor) and nodes.is_cuda:
+            nd = nodes.long()
+            if self.N == 0:
+                return torch.full((nd.numel(), self.K), -1, dtype=torch.int32, device=nd.device)
+            ok = (nd >= 0) & (nd < self.N)
+            out = self._dev[torch.where(ok, nd, torch.zeros_like(nd))]
+            return torch.where(ok[:, None], out, torch.full_like(out, -1))
         return self._dev[torch.as_tensor(np.asarray(nodes, dtype=np.int64), device="cuda")]
 
 
@@ -76,7 +85,7 @@ def search(graph, x, xq, k, L=32, entry=0):
 def search_batched(graph, x, xq, k, L=64, entry=0, max_rounds=None):
     """The same best-first search for a whole batch of queries in lock step on the GPU: every round expands the best
     unexpanded candidate of every query with ONE `get_neighbors_device` call (one decode launch for the whole
-    frontier) -- the shape in which a compressed graph pays off on a GPU.  Pools are ordered by (distance, node id), so
+    frontier, handed over as a CUDA tensor: -1 for a query that is done) -- the shape in which a compressed graph pays off on a GPU.  Pools are ordered by (distance, node id), so
     the result does not depend on the order in which a container returns the neighbours of a node.
     -> (D float32 [nq, k], I int64 [nq, k])"""
     import torch
@@ -102,9 +111,9 @@ def search_batched(graph, x, xq, k, L=64, entry=0, max_rounds=None):
         if not bool(active.any()) or (max_rounds is not None and rounds >= max_rounds):
             break
         rounds += 1
-        nodes = torch.where(active, pool_n[rows, best], torch.zeros_like(best))
+        nodes = torch.where(active, pool_n[rows, best], torch.full_like(best, -1))  # (a finished query asks for no row)
         pool_e[rows, best] = True
-        nb = graph.get_neighbors_device(nodes.cpu().numpy()).long()  # [nq, K], -1 padded
+        nb = graph.get_neighbors_device(nodes).long()  # [nq, K], -1 padded; the frontier stays on the device
         ok = (nb >= 0) & active[:, None]
         nbv = torch.where(nb >= 0, nb, torch.full_like(nb, N))
         nbc = nb.clamp(min=0)
