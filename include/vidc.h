@@ -240,7 +240,11 @@ int vidc_ef_perm(vidc_ctx *ctx, const vidc_ef *e, uint32_t *perm_host); /* sort 
 /* EliasFanoNSGGraph (altid_impl.cpp:53-101): rows are counted (-1 terminated), sorted and coded per node. */
 int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, vidc_ef **out);
 /* get_neighbors for m nodes: d_out device int32[m*K] ascending, -1 padded; counts host uint32[m] (may be NULL);
- * nodes == NULL selects nodes 0..m-1 */
+ * nodes == NULL selects nodes 0..m-1.
+ * Output contract, the same for host nodes, nodes == NULL and device nodes (vidc_ef_decode_rows_dev): any K >= the widest requested
+ * row is served, also K above the K the object was built with and K > 64; after the call EVERY one of the m * K elements is defined
+ * -- a row's ids, then -1 up to column K - 1 -- whatever d_out held before, and no byte outside d_out[0 .. m*K) is written.  d_out
+ * needs 4-byte alignment only. */
 int vidc_ef_decode_rows(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *nodes, uint32_t K, int32_t *d_out,
                         uint32_t *counts);
 /* decode m selected lists back to back (get_ids per touched list, custom_invlists_impl.cpp:508-525) */
@@ -323,7 +327,8 @@ int vidc_wt_translate_labels_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, co
                                  uint64_t *d_invalid);
 int vidc_roc_translate_labels_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
                                   uint64_t *d_invalid);
-/* get_neighbors for a device-resident node array: d_nodes device int64[m], d_out device int32[m*K] (-1 padded). */
+/* get_neighbors for a device-resident node array: d_nodes device int64[m], d_out device int32[m*K] (-1 padded: every column up to
+ * K - 1 of every row is written at any accepted K, nothing outside d_out is; the output contract stated at vidc_ef_decode_rows). */
 int vidc_compact_rows_decode_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const int64_t *d_nodes, int32_t *d_out,
                                  uint32_t *d_counts, uint64_t *d_invalid);
 int vidc_ef_decode_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,

@@ -2517,9 +2517,13 @@ static void ef_rows_geometry(uint32_t K, uint32_t ubound, uint32_t *LW, uint32_t
     *HW = (3u * K + 1u + 63u) / 64u;
 }
 
-// the arena row decoder of a graph object for m rows (d_nodes == NULL: rows 0..m-1; d_cnt may be NULL)
+// the arena row decoder of a graph object for m rows (d_nodes == NULL: rows 0..m-1; d_cnt may be NULL).  The tile kernel writes the
+// first min(K, 64) columns of a row (an arena row has at most 64 edges); a wider output gets its -1s from a fill in front of it, in
+// stream order and without a host wait (as the wide ROC rows, vidc_roc_decode_rows).  K <= 64 launches exactly what it did before.
+// (In ef_decode_rows_arena the fill lies between the two timing events: at K > 64 last_kernel_ms includes it.)
 static int ef_rows_arena_launch(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *d_nodes, uint32_t K, int32_t *d_out,
                                 uint32_t *d_cnt) {
+    if (K > 64) VIDC_HIP(hipMemsetAsync(d_out, 0xff, m * (uint64_t)K * 4, ctx->stream));
     const uint32_t S = e->a_lw + e->a_hw;
     const size_t dyn = ((size_t)64 * (S | 1u) + 1) * 8;
     const dim3 grid(tile_grid(ctx->num_cu, (m + 63) / 64, (uint32_t)std::min<size_t>(16, (150u << 10) / (dyn + 4608 + 256))));
