@@ -336,6 +336,50 @@ int vidc_ef_decode_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const i
 int vidc_roc_decode_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,
                              uint32_t *d_counts, uint64_t *d_invalid);
 
+/* ---------------------------------------------------- append (batches of ids, device-resident) */
+/* Objects stay immutable: an append returns a NEW object in *out, the old one stays valid and unchanged, and either may be destroyed
+ * first (the new object owns all of its memory).
+ *
+ * The batch.  Pair i is (d_list_nos[i], d_ids[i]): what a coarse quantizer on the GPU hands to `add`.  With old_l = list l of the old
+ *   object in the object's own order (what vidc_*_decode_lists returns), the merged input of list l is
+ *       M_l = old_l ++ [d_ids[i] for every i with d_list_nos[i] == l, in ascending i]
+ *   -- the placement is stable: batch order inside a list is part of the contract.  A negative list number is skipped and not counted
+ *   (Faiss's "not assigned"); a list number >= nlist is skipped and counted in *d_invalid (a device uint64 the caller zeroes; may be NULL).
+ * The result is the object the existing encoder builds from the CSR form of M, word for word (streams, per-list metadata, sizes,
+ *   compressed_bytes, and the permutation when the flag asks for it): vidc_packed_encode with `bits` (0 keeps the object's width; a
+ *   larger width re-packs every list; an id that does not fit gives VIDC_ERR_DOMAIN), vidc_ef_encode with `flags`, vidc_wt_build with
+ *   the object's wt_type (M must be what vidc_wt_build demands -- a permutation of 0 .. ntotal_new - 1, ascending inside each list --
+ *   otherwise its status is returned), vidc_roc_encode with `precision_mode` and `flags` (the caller passes the mode the object was built
+ *   with; the call cannot check it).  A permutation is over positions in M_l: j < |old_l| is the old entry at offset j, j >= |old_l| the
+ *   (j - |old_l|)-th batch entry of that list.
+ * ROC and duplicates.  The ROC stream of a list depends only on the multiset of its ids, and a decoded list of distinct ids re-encodes
+ *   to the identity permutation; with duplicate ids inside one list the reference codec is lossy.  The result is defined through M as
+ *   above whatever old_l decodes to; ids should be distinct inside every merged list (the IVF case).  A list the batch does not touch
+ *   keeps its stream and gets the identity permutation: that is the from-scratch result whenever the list decodes to its own distinct
+ *   ids (not for the reference's lossy cases -- duplicates, a power-of-two maximum under VIDC_PREC_REFERENCE, more than 65 536 ids).
+ * Labels.  d_labels[i] (device int64[n_add], may be NULL) = list_no << 32 | offset at which batch entry i sits in the new object:
+ *   vidc_*_translate_labels_dev on the new object gives back d_ids[i].  Skipped entries get -1.  The offset is |old_l| + the entry's
+ *   rank in the batch (packed bits, wavelet tree), its position in the stable ascending order of M_l (Elias-Fano), its position in
+ *   sampling order (ROC).
+ * Arrays are device arrays on the context's device, read and written in order on the context's stream; n_add < 2^32 - 1.
+ * Status.  NULL context, object or out, or a NULL array with n_add > 0: VIDC_ERR_INVALID before any device work.  A graph object (rows,
+ *   Elias-Fano arena): VIDC_ERR_UNSUPPORTED.  A merged ROC list above VIDC_ROC_MAX_LIST, or an id >= 2^31: VIDC_ERR_DOMAIN.  On any
+ *   error *out == NULL, the old object is untouched and the context stays usable.  n_add == 0, or a batch without a valid pair, returns
+ *   an object equal to the old one.
+ * Residency.  No id payload crosses PCIe (vidc_ctx_d2h_bytes does not move).  Packed bits, Elias-Fano and the wavelet tree are REBUILT:
+ *   decode_all into scratch, the merge, the device-offsets encoder -- memory-rate kernels, one 8-byte read-back (the valid pair count),
+ *   no O(nlist) array on the host.  ROC is SPLICED: only the lists the batch touches are decoded and re-encoded (their numbers and add
+ *   counts are read back once, 8 bytes per touched list, and the host plans their classes as vidc_roc_translate_labels_dev does);
+ *   every other list's stream is copied.  The calls synchronise. */
+int vidc_packed_append_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
+                           int bits, vidc_packed **out, int64_t *d_labels, uint64_t *d_invalid);
+int vidc_ef_append_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
+                       uint32_t flags, vidc_ef **out, int64_t *d_labels, uint64_t *d_invalid);
+int vidc_wt_append_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
+                       vidc_wt **out, int64_t *d_labels, uint64_t *d_invalid);
+int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
+                        int precision_mode, uint32_t flags, vidc_roc **out, int64_t *d_labels, uint64_t *d_invalid);
+
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,
  * measured with hipEvents on the context's stream (used by bench.py for the roofline figure). */

@@ -133,6 +133,11 @@ def _declare(lib):
     f("vidc_compact_rows_decode_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp, _vp)
     f("vidc_ef_decode_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp)
     f("vidc_roc_decode_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp)
+    # append (batches of ids, device-resident)
+    f("vidc_packed_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _P(_vp), _vp, _vp)
+    f("vidc_ef_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp)
+    f("vidc_wt_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp)
+    f("vidc_roc_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp)
 
 
 #: every symbol include/vidc.h declares (checked by the CPU test-suite against the built library)
@@ -156,6 +161,7 @@ EXPORTED_SYMBOLS = [
     "vidc_wt_decode_all", "vidc_wt_decode_lists", "vidc_wt_decode_gather", "vidc_wt_build_dev", "vidc_wt_offsets",
     "vidc_packed_translate_labels_dev", "vidc_ef_translate_labels_dev", "vidc_wt_translate_labels_dev", "vidc_roc_translate_labels_dev",
     "vidc_compact_rows_decode_dev", "vidc_ef_decode_rows_dev", "vidc_roc_decode_rows_dev",
+    "vidc_packed_append_dev", "vidc_ef_append_dev", "vidc_wt_append_dev", "vidc_roc_append_dev",
 ]
 
 

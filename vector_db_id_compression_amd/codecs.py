@@ -121,6 +121,45 @@ def _translate_labels(fn, obj, labels, out, invalid):
     return out
 
 
+def _append(fn, obj, list_nos, ids, extra, labels, invalid):
+    """vidc_*_append_dev: a batch of (list number, id) pairs placed behind the lists of `obj`, in batch order inside every list -> (handle
+    of the NEW object, labels).  list_nos: int64 CUDA tensor (negative = not assigned, skipped), ids: int64 / uint64 CUDA tensor of the
+    same size; numpy arrays are uploaded.  labels: True (a new int64 CUDA tensor), False / None (none) or an int64 CUDA tensor to fill:
+    list_no << 32 | offset of every batch entry in the new object, -1 for a skipped one.  invalid (optional): 1-element int64 CUDA tensor
+    the number of list numbers >= nlist is added to.  Runs on torch's current stream; the call synchronises."""
+    torch = _torch()
+    if not torch.cuda.is_available():
+        raise _lib.VidcError("no HIP device: append needs an MI355X (there is no CPU fallback)")
+    if isinstance(list_nos, np.ndarray):
+        list_nos = torch.from_numpy(np.ascontiguousarray(list_nos, dtype=np.int64)).cuda()
+    if isinstance(ids, np.ndarray):
+        ids = torch.from_numpy(np.ascontiguousarray(ids).view(np.int64)).cuda()
+    if not _is_cuda(list_nos) or list_nos.dtype != torch.int64:
+        raise TypeError("list_nos must be an int64 CUDA tensor")
+    if not _is_cuda(ids) or ids.dtype not in (torch.int64, torch.uint64):
+        raise TypeError("ids must be an int64 / uint64 CUDA tensor")
+    if list_nos.numel() != ids.numel():
+        raise ValueError("list_nos and ids must have one entry per pair")
+    ln = _dev_array(list_nos.reshape(-1), obj.ctx, "list_nos")
+    di = _dev_array(ids.reshape(-1), obj.ctx, "ids")
+    n = ln.numel()
+    lab = None
+    if labels is True:
+        lab = torch.empty(max(n, 1), dtype=torch.int64, device=ln.device)
+    elif labels is not None and labels is not False:
+        if not _is_cuda(labels) or labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() != n or labels.device != ln.device:
+            raise ValueError("labels must be a contiguous int64 CUDA tensor with one entry per pair, on the batch's device")
+        lab = labels
+    if invalid is not None and (not _is_cuda(invalid) or invalid.dtype != torch.int64 or invalid.numel() != 1
+                                or not invalid.is_contiguous() or invalid.device != ln.device):
+        raise ValueError("invalid must be a 1-element int64 CUDA tensor on the batch's device")
+    _on_torch_stream(obj.ctx)
+    h = C.c_void_p()
+    check(fn(obj.ctx.h, obj.h, n, ptr(ln) if n else None, ptr(di) if n else None, *extra, C.byref(h),
+             ptr(lab) if lab is not None and n else None, ptr(invalid)))
+    return h, (None if lab is None else lab[:n])
+
+
 def _decode_rows_dev(fn, obj, nodes, K, want_counts, pass_K=True):
     """vidc_*_decode_rows_dev / vidc_compact_rows_decode_dev: rows of a CUDA tensor of nodes (-1 rows for negative nodes and nodes
     >= N) -> (int32 [m, K] CUDA tensor, int32 CUDA counts or None)."""
@@ -224,6 +263,14 @@ class RocLists:
         check(lib().vidc_roc_import(ctx.h, nlist, ptr(off), ptr(prec), ptr(hd), ptr(nw), ptr(dr),
                                     ptr(wc) if wc.size else None, C.byref(h)))
         return cls(h, ctx, off)
+
+    def append(self, list_nos, ids, precision_mode=VIDC_PREC_REFERENCE, want_perm=False, labels=True, invalid=None):
+        """A batch of (list number, id) pairs behind the lists of this object -> (NEW RocLists, labels); this object stays valid and
+        unchanged (vidc_roc_append_dev).  Only the lists the batch touches are decoded and re-encoded; the streams of the others are
+        copied on the device.  precision_mode: the mode this object was built with.  See _append for the arguments."""
+        h, lab = _append(lib().vidc_roc_append_dev, self, list_nos, ids,
+                         (int(precision_mode), _lib.VIDC_ROC_WANT_PERM if want_perm else 0), labels, invalid)
+        return type(self)(h, self.ctx, None), lab
 
     # -- flat on-disk / wire image (the reference keeps compressed lists in memory only, SURVEY 5)
     def save(self, path):
@@ -389,6 +436,12 @@ class PackedLists:
         check(lib().vidc_packed_encode(ctx.h, off.size - 1, ptr(off), ptr(d_ids), int(bits), C.byref(h)))
         return cls(h, ctx, off)
 
+    def append(self, list_nos, ids, bits=None, labels=True, invalid=None):
+        """A batch of (list number, id) pairs behind the lists of this object -> (NEW PackedLists, labels); this object stays valid and
+        unchanged (vidc_packed_append_dev).  bits=None keeps this object's width; a larger one re-packs every list.  See _append."""
+        h, lab = _append(lib().vidc_packed_append_dev, self, list_nos, ids, (0 if bits is None else int(bits),), labels, invalid)
+        return type(self)(h, self.ctx, None, self._nlist if self._offsets is None else self._offsets.size - 1, None), lab
+
     @property
     def ntotal(self):
         return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
@@ -507,6 +560,12 @@ class EfLists:
         check(lib().vidc_ef_encode(ctx.h, off.size - 1, ptr(off), ptr(d_ids),
                                    _lib.VIDC_EF_WANT_PERM if want_perm else 0, C.byref(h)))
         return cls(h, ctx, off)
+
+    def append(self, list_nos, ids, want_perm=False, labels=True, invalid=None):
+        """A batch of (list number, id) pairs merged into the lists of this object -> (NEW EfLists, labels); this object stays valid
+        and unchanged (vidc_ef_append_dev).  A label's offset is the entry's place in the ascending merged list.  See _append."""
+        h, lab = _append(lib().vidc_ef_append_dev, self, list_nos, ids, (_lib.VIDC_EF_WANT_PERM if want_perm else 0,), labels, invalid)
+        return type(self)(h, self.ctx, None, self._nlist if self._offsets is None else self._offsets.size - 1, None), lab
 
     @property
     def ntotal(self):
@@ -741,6 +800,13 @@ class WaveletTreeLists:
         h = C.c_void_p()
         check(lib().vidc_wt_build(ctx.h, off.size - 1, ptr(off), ptr(d_ids), int(wt_type), C.byref(h)))
         return cls(h, ctx, off)
+
+    def append(self, list_nos, ids, labels=True, invalid=None):
+        """A batch of (list number, id) pairs behind the lists of this object -> (NEW WaveletTreeLists, labels); this object stays
+        valid and unchanged (vidc_wt_append_dev).  The merged lists must be what `build` demands: a permutation of 0 .. ntotal - 1,
+        ascending inside every list (a batch of ids ntotal .. ntotal + n - 1 in add order is).  See _append."""
+        h, lab = _append(lib().vidc_wt_append_dev, self, list_nos, ids, (), labels, invalid)
+        return type(self)(h, self.ctx, None, self._nlist if self._offsets is None else self._offsets.size - 1, None), lab
 
     @property
     def ntotal(self):

@@ -14,6 +14,7 @@
 
 #include "bits.h"
 #include "chunks.h"
+#include "append.h"
 #include "common.h"
 #include "dev_offsets.h"
 #include "scan.h"
@@ -2707,6 +2708,31 @@ int vidc_ef_decode_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const i
                                             [&](const uint64_t *nd, uint32_t *cnt) { return ef_rows_arena_launch(ctx, e, m, nd, K, d_out, cnt); });
     return req_rows_via_host(ctx, e->nlist, m, d_nodes, K, d_out, d_counts, d_invalid,
                              [&](const uint64_t *hn, uint32_t *hc) { return vidc_ef_decode_rows(ctx, e, m, hn, K, d_out, hc); });
+}
+
+// Append (include/vidc.h): decode_all into scratch, the shared merge (append.h), the device-offsets encoder on the merged CSR.  A
+// batch entry's offset is its place in the stable ascending order of the merged list: the labels are read off the new object's sort
+// permutation (kept only when the caller asked for it).
+int vidc_ef_append_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags,
+                       vidc_ef **out, int64_t *d_labels, uint64_t *d_invalid) {
+    VIDC_TRY(append_check(ctx, e, out, n_add, d_list_nos, d_ids));
+    if (e->rows || e->arena) { set_error("elias-fano append: graph objects are not appendable"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    AppendMerged m;
+    VIDC_TRY(append_merge(ctx, e->nlist, e->ntotal, e->d_offsets.p, n_add, d_list_nos, d_ids, d_labels, d_invalid, false, m,
+                          [&](uint64_t *d) { return vidc_ef_decode_all(ctx, e, d); }));
+    const bool need_perm = d_labels && m.batch.n_valid;
+    vidc_ef *ne = nullptr;
+    VIDC_TRY(vidc_ef_encode_dev(ctx, e->nlist, m.batch.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(),
+                                need_perm ? flags | VIDC_EF_WANT_PERM : flags, &ne));
+    if (need_perm) {
+        if (!ne->has_perm) { delete ne; set_error("elias-fano append: the encoder kept no permutation"); return VIDC_ERR_INVALID; }
+        const int st = append_labels_from_perm(ctx, m.batch, ne->d_perm.p, ne->d_offsets.p, nullptr, e->nlist, m.ntotal_new, e->d_offsets.p, d_labels);
+        if (st != VIDC_OK) { delete ne; return st; }
+        if (!(flags & VIDC_EF_WANT_PERM)) { ne->d_perm.release(); ne->has_perm = false; }
+    }
+    *out = ne;
+    return VIDC_OK;
 }
 
 int vidc_ef_get(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *list_nos, const uint64_t *offs,

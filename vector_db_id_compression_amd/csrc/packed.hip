@@ -12,6 +12,7 @@
 
 #include "bits.h"
 #include "chunks.h"
+#include "append.h"
 #include "common.h"
 #include "dev_offsets.h"
 #include "requests.h"
@@ -1132,6 +1133,19 @@ int vidc_packed_translate_labels_dev(vidc_ctx *ctx, const vidc_packed *p, uint64
                        p->nlist, (uint32_t)p->bits, n, d_labels, d_ids, (unsigned long long *)d_invalid);
     VIDC_HIP(hipGetLastError());
     return VIDC_OK;
+}
+
+// Append (include/vidc.h): decode_all into scratch, the shared merge (append.h), the device-offsets encoder on the merged CSR.  The
+// labels of this input-order container are written by the merge.
+int vidc_packed_append_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, int bits,
+                           vidc_packed **out, int64_t *d_labels, uint64_t *d_invalid) {
+    VIDC_TRY(append_check(ctx, p, out, n_add, d_list_nos, d_ids));
+    if (bits < 0 || bits > 64) { set_error("packed append: bits must be 0 (keep) .. 64"); return VIDC_ERR_INVALID; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    AppendMerged m;
+    VIDC_TRY(append_merge(ctx, p->nlist, p->ntotal, p->d_offsets.p, n_add, d_list_nos, d_ids, d_labels, d_invalid, true, m,
+                          [&](uint64_t *d) { return vidc_packed_decode_all(ctx, p, d); }));
+    return vidc_packed_encode_dev(ctx, p->nlist, m.batch.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), bits ? bits : p->bits, out);
 }
 
 int vidc_packed_export(vidc_ctx *ctx, const vidc_packed *p, uint64_t list_no, uint8_t *bytes, size_t cap) {

@@ -9,6 +9,7 @@
 #include <numeric>
 #include <thread>
 
+#include "append.h"
 #include "common.h"
 #include "roc_kernels.h"
 #include "roc_u.h"
@@ -2241,6 +2242,65 @@ __global__ void __launch_bounds__(256) k_req_roc_pick(const int64_t *labels, uin
     }
 }
 
+// ---- append (vidc_roc_append_dev): only the lists the batch touches are decoded and re-encoded; the rest of the object is spliced.
+// flag[l] = the batch adds to list l, mark[l] = ids of its merged list (0 for an untouched list): their exclusive scans are the
+// touched list's number among the touched ones (tpos) and its place in the staging CSR (stage_off).
+__global__ void __launch_bounds__(256) k_app_roc_mark(const uint64_t *__restrict__ old_off, const uint64_t *__restrict__ add_off, uint64_t nlist,
+                                                      uint32_t *__restrict__ mark, uint32_t *__restrict__ flag) {
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t add = add_off[l + 1] - add_off[l];
+        flag[l] = add ? 1u : 0u;
+        const uint64_t n = old_off[l + 1] - old_off[l] + add;
+        mark[l] = add ? (uint32_t)(n < 0xffffffffull ? n : 0xffffffffull) : 0u;
+    }
+}
+// touched[tpos[l]] = l, added[tpos[l]] = batch entries of l, for every flagged list, ascending
+__global__ void __launch_bounds__(256) k_app_roc_touched(const uint32_t *__restrict__ flag, const uint64_t *__restrict__ tpos,
+                                                         const uint64_t *__restrict__ add_off, uint64_t nlist, uint32_t *__restrict__ touched,
+                                                         uint32_t *__restrict__ added) {
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x)
+        if (flag[l]) {
+            touched[tpos[l]] = (uint32_t)l;
+            added[tpos[l]] = (uint32_t)(add_off[l + 1] - add_off[l]);
+        }
+}
+// per-list metadata of the spliced object: from the small object (list tpos[l] of it) for a touched list, from the old one otherwise;
+// slot[l] = tpos[l] + 1 or 0, what the word and permutation copies select their source by
+struct RocMeta {
+    const uint64_t *heads;
+    const uint32_t *prec, *nwords, *draws;
+};
+__global__ void __launch_bounds__(256) k_app_roc_meta(const uint32_t *__restrict__ flag, const uint64_t *__restrict__ tpos, uint64_t nlist, RocMeta old,
+                                                      RocMeta small, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
+                                                      uint32_t *__restrict__ nwords, uint32_t *__restrict__ draws, uint32_t *__restrict__ slot) {
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x) {
+        const bool t = flag[l] != 0u;
+        const uint64_t k = t ? tpos[l] : l;
+        const RocMeta &m = t ? small : old;
+        heads[l] = m.heads[k];
+        prec[l] = m.prec[k];
+        nwords[l] = m.nwords[k];
+        draws[l] = m.draws[k];
+        slot[l] = t ? (uint32_t)k + 1u : 0u;
+    }
+}
+// sampling permutation of the spliced object: the small object's for a touched list, the identity otherwise (a decoded list of
+// distinct ids re-encodes to the identity).  A wavefront per chunk of the new lists.
+__global__ void __launch_bounds__(256) k_app_roc_perm(const uint64_t *__restrict__ new_off, const uint32_t *__restrict__ slot,
+                                                      const uint32_t *__restrict__ sperm, const uint64_t *__restrict__ soff,
+                                                      const Chunk *__restrict__ items, const uint64_t *__restrict__ n_items, uint32_t *__restrict__ perm) {
+    const uint64_t total = *n_items;
+    const uint32_t lane = lane_id();
+    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < total; c += (uint64_t)gridDim.x * 4u) {
+        const Chunk ch = items[c];
+        const uint64_t base = new_off[ch.list], n = new_off[ch.list + 1] - base;
+        const uint32_t nc = (uint32_t)(n - ch.start < APP_COPY_UNIT ? n - ch.start : APP_COPY_UNIT);
+        const uint32_t sl = slot[ch.list];
+        const uint32_t *src = sl ? sperm + soff[sl - 1u] + ch.start : nullptr;
+        for (uint32_t j = lane; j < nc; j += 64u) perm[base + ch.start + j] = sl ? src[j] : ch.start + j;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2618,6 +2678,173 @@ int vidc_roc_translate_labels_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, 
                        s_stage.as<uint64_t>(), d_ids);
     VIDC_HIP(hipGetLastError());
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    return VIDC_OK;
+}
+
+// Append (include/vidc.h).  The batch is sorted by list on the device (append.h); the touched lists are marked and compacted there, and
+// their numbers and add counts come back once (8 bytes per touched list, metadata).  The host sizes a staging CSR of the merged touched
+// lists, the old ids are decoded into it (plan_decode / decode_impl on the subset), the batch ids are placed behind them, and
+// encode_impl runs on the staging CSR alone: a small object of the touched lists.  The new object is spliced on the device -- metadata
+// from the small object or the old one, the scan of the word counts, a segmented copy of every list's words from whichever object
+// holds them -- so an untouched list costs a copy of its words, not an ANS chain.  Like an imported object it carries no planner
+// hints (prec / umax / order_desc are empty: the planners mirror the metadata on first use).
+int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
+                        uint32_t flags, vidc_roc **out, int64_t *d_labels, uint64_t *d_invalid) {
+    VIDC_TRY(append_check(ctx, r, out, n_add, d_list_nos, d_ids));
+    if (r->rows) { set_error("roc append: graph objects are not appendable"); return VIDC_ERR_UNSUPPORTED; }
+    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
+        set_error("precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
+        return VIDC_ERR_INVALID;
+    }
+    VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc append");
+    const uint64_t nlist = r->nlist;
+    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
+    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    double kernel_ms = 0;
+    AppendBatch b;
+    VIDC_TRY(append_sort_batch(ctx, nlist, r->d_offsets.p, n_add, d_list_nos, d_invalid, b));
+    tr.mark("batch sorted by list");
+    // the touched lists
+    Scratch s_mark, s_off, s_touched, s_t0, s_stage, s_slot;
+    Pinned h_back;
+    VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));   // mark | flag
+    VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));    // stage_off | tpos
+    VIDC_TRY(s_touched.get(ctx, 2 * (nlist + 1) * 4));  // touched | added
+    VIDC_TRY(s_slot.get(ctx, (nlist + 1) * 4));
+    uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
+    uint64_t *stage_off = s_off.as<uint64_t>(), *tpos = stage_off + nlist + 1;
+    VIDC_TRY(h_back.get(ctx, 16 + (nlist + 1) * 8));
+    uint64_t *h_cnt = h_back.as<uint64_t>();
+    uint32_t *h_touched = (uint32_t *)(h_cnt + 2), *h_added = h_touched + nlist + 1;
+    uint32_t *d_touched = s_touched.as<uint32_t>(), *d_added = d_touched + nlist + 1;
+    h_cnt[0] = 0;
+    if (nlist) {
+        hipLaunchKernelGGL(k_app_roc_mark, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, r->d_offsets.p, (const uint64_t *)b.add_off, nlist, mark, flag);
+        Scan4 sc{};
+        sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = tpos;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
+        hipLaunchKernelGGL(k_app_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, tpos, (const uint64_t *)b.add_off, nlist,
+                           d_touched, d_added);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemcpyAsync(h_cnt, tpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    const uint64_t cnt = h_cnt[0];
+    if (cnt) {
+        VIDC_HIP(hipMemcpyAsync(h_touched, d_touched, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_added, d_added, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    }
+    // staging CSR of the merged touched lists; host offsets of the new object
+    std::vector<uint64_t> st_off(cnt + 1, 0);
+    std::vector<uint32_t> dec_lists, dec_slot;  // touched lists that hold old ids, and their number among the touched ones
+    for (uint64_t k = 0; k < cnt; k++) {
+        const uint64_t l = h_touched[k], old_n = r->offsets[l + 1] - r->offsets[l], n = old_n + h_added[k];
+        if (n > VIDC_ROC_MAX_LIST) {
+            set_error("roc append: list %llu would hold %llu ids (limit %u)", (unsigned long long)l, (unsigned long long)n, VIDC_ROC_MAX_LIST);
+            return VIDC_ERR_DOMAIN;
+        }
+        st_off[k + 1] = st_off[k] + n;
+        if (old_n) { dec_lists.push_back((uint32_t)l); dec_slot.push_back((uint32_t)k); }
+    }
+    const uint64_t total = st_off[cnt];
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = ctx->device;
+    nr->nlist = nlist;
+    nr->ntotal = r->ntotal + b.n_valid;
+    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
+    nr->offsets.resize(nlist + 1);
+    uint64_t nonempty = 0;
+    {
+        uint64_t shift = 0, k = 0;
+        for (uint64_t l = 0; l < nlist; l++) {
+            nr->offsets[l] = r->offsets[l] + shift;
+            if (k < cnt && h_touched[k] == l) shift += h_added[k++];
+            nonempty += r->offsets[l + 1] + shift != nr->offsets[l];
+        }
+        nr->offsets[nlist] = r->offsets[nlist] + shift;
+    }
+    nr->offsets_host = true;
+    tr.mark("touched lists read back, staging sized");
+    VIDC_TRY(s_stage.get(ctx, (total ? total : 1) * 8));
+    if (!dec_lists.empty()) {
+        DecPlan p;
+        plan_decode(r, dec_lists, false, p, ctx->wide);
+        std::vector<uint64_t> out_off(dec_lists.size());
+        for (size_t k = 0; k < dec_lists.size(); k++) out_off[k] = st_off[dec_slot[p.item[k]]];  // work item k -> its place in the staging
+        VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+        kernel_ms += ctx->last_kernel_ms;
+    }
+    tr.mark("touched lists decoded");
+    if (n_add) {
+        hipLaunchKernelGGL(k_app_place, req_grid(ctx, n_add), dim3(256), 0, ctx->stream, b.keys, b.vals, (uint32_t)n_add, nlist, r->d_offsets.p,
+                           (const uint64_t *)b.add_off, (const uint64_t *)stage_off, d_ids, s_stage.as<uint64_t>(), d_labels, false);
+        VIDC_HIP(hipGetLastError());
+    }
+    std::unique_ptr<vidc_roc> small;
+    if (cnt) {
+        vidc_roc *sp = nullptr;
+        VIDC_TRY(encode_impl(ctx, cnt, st_off.data(), s_stage.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
+                             want_perm || d_labels ? VIDC_ROC_WANT_PERM : 0u, &sp));
+        small.reset(sp);
+        kernel_ms += ctx->last_kernel_ms;
+    }
+    tr.mark("touched lists encoded");
+    // splice
+    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
+    VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, b.new_off, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    EventTimer tm(ctx);
+    Scratch s_t1;
+    if (nlist) {
+        const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};
+        const RocMeta m_small = small ? RocMeta{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p} : m_old;
+        hipLaunchKernelGGL(k_app_roc_meta, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, tpos, nlist, m_old, m_small, nr->d_heads.p,
+                           nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_slot.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+        VIDC_TRY(device_exscan(ctx, nr->d_nwords.p, (uint32_t)nlist, nr->d_word_off.p, s_t1));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+        h_cnt[1] = 0;
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_cnt[1];
+    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
+    AppChunks ch_w, ch_p, ch_l;
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, ch_w));
+        hipLaunchKernelGGL((k_app_copy<uint32_t, true>), app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, (const uint32_t *)r->d_words.p,
+                           (const uint64_t *)r->d_word_off.p, small ? (const uint32_t *)small->d_words.p : nullptr,
+                           small ? (const uint64_t *)small->d_word_off.p : nullptr, (const uint32_t *)s_slot.as<uint32_t>(),
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
+        VIDC_HIP(hipGetLastError());
+    }
+    if (want_perm && nr->ntotal) {
+        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, ch_p));
+        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
+                           (const uint32_t *)s_slot.as<uint32_t>(), small ? (const uint32_t *)small->d_perm.p : nullptr,
+                           small ? (const uint64_t *)small->d_offsets.p : nullptr, ch_p.items, ch_p.n_items, nr->d_perm.p);
+        VIDC_HIP(hipGetLastError());
+    }
+    if (d_labels && small) {  // a batch entry's offset: where the small object's permutation names it (sampling order)
+        VIDC_TRY(app_chunks(ctx, small->d_offsets.p, cnt, total, ch_l));
+        hipLaunchKernelGGL(k_app_labels_perm, app_chunk_grid(ctx, ch_l.bound), dim3(256), 0, ctx->stream, (const uint32_t *)small->d_perm.p,
+                           (const uint64_t *)small->d_offsets.p, (const uint32_t *)d_touched, (const uint64_t *)r->d_offsets.p,
+                           (const uint64_t *)b.add_off, b.vals, ch_l.items, ch_l.n_items, d_labels);
+        VIDC_HIP(hipGetLastError());
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    ctx->last_kernel_ms = kernel_ms;
+    tr.mark("spliced");
+    *out = nr.release();
     return VIDC_OK;
 }
 

@@ -22,6 +22,7 @@
 #include <memory>
 #include <mutex>
 
+#include "append.h"
 #include "bits.h"
 #include "common.h"
 #include "dev_offsets.h"
@@ -1336,6 +1337,18 @@ int vidc_wt_translate_labels_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, co
                            (uint32_t)w->nlist, w->L, n, lab, (const uint64_t *)nullptr, d_ids, inv);
     VIDC_HIP(hipGetLastError());
     return VIDC_OK;
+}
+
+// Append (include/vidc.h): decode_all into scratch, the shared merge (append.h), vidc_wt_build_dev on the merged CSR -- which checks
+// what the reference asserts of it (a permutation of 0 .. ntotal - 1, ascending inside every list).
+int vidc_wt_append_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, vidc_wt **out,
+                       int64_t *d_labels, uint64_t *d_invalid) {
+    VIDC_TRY(append_check(ctx, w, out, n_add, d_list_nos, d_ids));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    AppendMerged m;
+    VIDC_TRY(append_merge(ctx, w->nlist, w->ntotal, w->d_C.p, n_add, d_list_nos, d_ids, d_labels, d_invalid, true, m,
+                          [&](uint64_t *d) { return vidc_wt_decode_all(ctx, w, d); }));
+    return vidc_wt_build_dev(ctx, w->nlist, m.batch.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), w->wt_type, out);
 }
 
 int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,

@@ -69,6 +69,63 @@ class InvertedListsArrayCodes:
 
     update_entries = resize = add_entries
 
+    # -- growth: the one mutator these containers have.  add_entries / update_entries / resize above keep mirroring the reference's
+    # read-only virtuals; a batch of (list number, id, code) triples from a coarse quantizer on the GPU goes through the codec's append.
+    def _append_ids(self, list_nos, ids, invalid):
+        """-> (new codec object, labels, permutation over the merged lists as a host array or None)"""
+        raise NotImplementedError
+
+    def _refresh_sizes(self):
+        """the public size attributes, as a fresh container over the same lists reports them"""
+        raise NotImplementedError
+
+    def add_batch(self, list_nos, ids, codes=None):
+        """Append a batch: list_nos int64 [n] (negative = not assigned, skipped), ids int64 [n], codes uint8 [n, code_size]; CUDA
+        tensors (numpy arrays are uploaded).  Entry i goes behind the entries of list list_nos[i], in batch order (what add_entries per
+        list does to an ArrayInvertedLists).  The compressed ids are appended by the codec (vidc_*_append_dev: a new object replaces
+        `self._c`), codes_all is rebuilt on the device in the new object's order, and the size attributes become what a fresh
+        container over the same lists reports.  Returns the labels (list_no << 32 | offset, int64 CUDA tensor) of the batch."""
+        torch = _torch()
+        as_dev = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)).cuda() if isinstance(x, np.ndarray) else x).to(dt).reshape(-1)
+        ln, di = as_dev(list_nos, torch.int64).contiguous(), as_dev(ids, torch.int64).contiguous()
+        n = ln.numel()
+        if di.numel() != n:
+            raise ValueError("list_nos and ids must have one entry per vector")
+        cs = self.code_size
+        if cs:
+            if codes is None:
+                raise ValueError("this container keeps codes: add_batch needs them")
+            codes = as_dev(codes, torch.uint8).reshape(n, cs)
+        invalid = torch.zeros(1, dtype=torch.int64, device=ln.device)
+        new_c, labels, perm = self._append_ids(ln, di, invalid)
+        if int(invalid.item()):
+            raise _lib.VidcError(f"add_batch: {int(invalid.item())} list numbers are >= nlist = {self.nlist}")
+        valid = ln >= 0
+        lv = ln[valid]
+        add_cnt = torch.bincount(lv, minlength=self.nlist)
+        old_off = torch.from_numpy(self._offsets.astype(np.int64)).to(ln.device)
+        new_off = old_off + torch.cat([add_cnt.new_zeros(1), torch.cumsum(add_cnt, 0)])
+        ntotal_new = int(new_off[-1].item())
+        if cs:
+            lists = torch.arange(self.nlist, device=ln.device)
+            new_codes = torch.empty((ntotal_new, cs), dtype=torch.uint8, device=ln.device)
+            old_n = old_off[1:] - old_off[:-1]
+            if perm is None:  # input-order containers: the old codes keep their offsets, the batch codes go behind them
+                l_old = torch.repeat_interleave(lists, old_n)
+                new_codes[torch.arange(self.ntotal, device=ln.device) + (new_off - old_off)[l_old]] = self.codes_all
+            else:  # re-ordering containers: position q of list l holds entry perm[q] of the merged input; entries < |old_l| are old ones
+                l_new = torch.repeat_interleave(lists, new_off[1:] - new_off[:-1])
+                j = torch.from_numpy(perm.astype(np.int64)).to(ln.device)
+                is_old = j < old_n[l_new]
+                new_codes[is_old] = self.codes_all[(old_off[l_new] + j)[is_old]]
+            new_codes[new_off[lv] + (labels[valid] & 0xFFFFFFFF)] = codes[valid]
+            self.codes_all = new_codes
+        self._c = new_c
+        self._offsets = new_off.cpu().numpy().astype(np.uint64)
+        self.ntotal = ntotal_new
+        self._refresh_sizes()
+        return labels
+
     # -- batched helpers shared by the subclasses
     def get_single_id(self, list_no, offset):
         return int(self.get_single_ids([list_no], [offset])[0])
@@ -104,10 +161,19 @@ class CompressedIDInvertedListsPackedBits(InvertedListsArrayCodes):
         if ids.size and int(ids.max()) >= self.ntotal:  # FAISS_THROW_IF_NOT(ids_in[i] >= 0 && ids_in[i] < ntotal), :87
             raise _lib.VidcError("Error: 'ids_in[i] >= 0 && ids_in[i] < ntotal' failed")
         self._c = PackedLists.encode(self._offsets, ids, bits=PackedLists.bits_for(self.ntotal))
-        self.bits = self._c.bits
-        self.compressed_ids_size_in_bytes = self._c.compressed_bytes
+        self._refresh_sizes()
         self._store_codes()
         self._ids_host = None
+
+    def _refresh_sizes(self):
+        self.bits = self._c.bits
+        self.compressed_ids_size_in_bytes = self._c.compressed_bytes
+
+    def _append_ids(self, list_nos, ids, invalid):
+        # the width a fresh container takes for the grown index (:68-70); an id that does not fit it fails as the constructor does (:87)
+        ntotal_new = self.ntotal + int((list_nos >= 0).sum().item())
+        new_c, labels = self._c.append(list_nos, ids, bits=PackedLists.bits_for(ntotal_new), invalid=invalid)
+        return new_c, labels, None
 
     def get_ids_all(self):
         return self._c.decode_all()
@@ -125,16 +191,24 @@ class CompressedIDInvertedListsFenwickTree(InvertedListsArrayCodes):
     def __init__(self, il):
         super().__init__(il)
         self._c = RocLists.encode(self._offsets, self._ids_host, want_perm=self.code_size > 0)
-        info = self._c.info()
-        self.id_symbol_precision = info["precision"].astype(np.uint64)
-        self.compressed_ids_size_in_bytes = self._c.compressed_bytes  # :196-206
         self.overhead_in_bytes = 0                                   # declared, never written (:62)
         # codes are re-ordered into sampling order (:188-193)
         self._store_codes(self._c.perm() if self.code_size else None)
+        self._refresh_sizes()
+        self._ids_host = None
+
+    def _refresh_sizes(self):
+        info = self._c.info()
+        self.id_symbol_precision = info["precision"].astype(np.uint64)
+        self.compressed_ids_size_in_bytes = self._c.compressed_bytes  # :196-206
         # the reference adds the size of ALL code arrays once per non-empty list (:203-205, accidental O(nlist^2))
         nonempty = int(np.count_nonzero(self._offsets[1:] > self._offsets[:-1]))
         self.codes_size_in_bytes = nonempty * self.ntotal * self.code_size
-        self._ids_host = None
+
+    def _append_ids(self, list_nos, ids, invalid):
+        want = self.code_size > 0
+        new_c, labels = self._c.append(list_nos, ids, want_perm=want, invalid=invalid)  # (the constructor's precision mode)
+        return new_c, labels, (new_c.perm() if want else None)
 
     def get_ids_all(self):
         return self._c.decode_all()
@@ -156,12 +230,20 @@ class CompressedIDInvertedListsEliasFano(InvertedListsArrayCodes):
     def __init__(self, il):
         super().__init__(il)
         self._c = EfLists.encode(self._offsets, self._ids_host, want_perm=self.code_size > 0)
-        self.compressed_ids_size_in_bytes = self._c.compressed_bytes  # :272-282
         self.overhead_in_bytes = 0
         self._store_codes(self._c.perm() if self.code_size else None)  # canonicalize_order_inplace, :324-339
+        self._refresh_sizes()
+        self._ids_host = None
+
+    def _refresh_sizes(self):
+        self.compressed_ids_size_in_bytes = self._c.compressed_bytes  # :272-282
         nonempty = int(np.count_nonzero(self._offsets[1:] > self._offsets[:-1]))
         self.codes_size_in_bytes = nonempty * self.ntotal * self.code_size
-        self._ids_host = None
+
+    def _append_ids(self, list_nos, ids, invalid):
+        want = self.code_size > 0
+        new_c, labels = self._c.append(list_nos, ids, want_perm=want, invalid=invalid)
+        return new_c, labels, (new_c.perm() if want else None)
 
     def get_ids_all(self):
         return self._c.decode_all()
@@ -181,9 +263,16 @@ class CompressedIDInvertedListsWaveletTree(InvertedListsArrayCodes):
         assert wt_type in (0, 1)
         self.wt_type = wt_type
         self._c = WaveletTreeLists.build(self._offsets, self._ids_host, wt_type)
-        self.compressed_ids_size_in_bytes = self._c.size_in_bytes
+        self._refresh_sizes()
         self._store_codes()
         self._ids_host = None
+
+    def _refresh_sizes(self):
+        self.compressed_ids_size_in_bytes = self._c.size_in_bytes
+
+    def _append_ids(self, list_nos, ids, invalid):
+        new_c, labels = self._c.append(list_nos, ids, invalid=invalid)
+        return new_c, labels, None
 
     def get_ids_all(self):
         return self._c.decode_all()

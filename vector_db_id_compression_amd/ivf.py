@@ -75,17 +75,28 @@ class IVFIndex:
             assert dsub * self.M == self.d
             self.pq = torch.stack([_kmeans(xt[:, m * dsub:(m + 1) * dsub], 256, seed=7 + m) for m in range(self.M)])
 
-    def _encode(self, x):
+    def _encode_dev(self, x):
+        """codes of x as a uint8 CUDA tensor [n, code_size]"""
         torch = _torch()
         if not self.M:
-            return x.contiguous().cpu().numpy().view(np.uint8).reshape(x.shape[0], 4 * self.d)
+            return x.contiguous().view(torch.uint8).reshape(x.shape[0], 4 * self.d)
         dsub = self.d // self.M
         codes = torch.stack([_assign(x[:, m * dsub:(m + 1) * dsub].contiguous(), self.pq[m]) for m in range(self.M)], 1)
-        return codes.to(torch.uint8).cpu().numpy()
+        return codes.to(torch.uint8)
+
+    def _encode(self, x):
+        return self._encode_dev(x).cpu().numpy()
 
     def add(self, xb):
         torch = _torch()
         xb = torch.as_tensor(np.asarray(xb, dtype=np.float32)).cuda()
+        if hasattr(self.invlists, "add_batch"):  # a compressed container: assignments, ids and codes stay on the device
+            n = xb.shape[0]
+            ids = torch.arange(self.ntotal, self.ntotal + n, dtype=torch.int64, device=xb.device)
+            self.invlists.add_batch(_assign(xb, self.centroids), ids, self._encode_dev(xb))
+            self.ntotal += n
+            self._dev = None
+            return
         assign = _assign(xb, self.centroids).cpu().numpy()
         codes = self._encode(xb)
         ids = np.arange(self.ntotal, self.ntotal + xb.shape[0], dtype=np.int64)
