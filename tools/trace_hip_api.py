@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Dev tool: N encode + decode_all pairs of one codec on one workload, nothing else -- run under
 `rocprofv3 --hip-trace --stats` to see which HIP calls the host side of a call is made of, or alone for the wall / kernel split.
-usage: trace_hip_api.py <workload> <ef|packed|roc> [reps]"""
+usage: trace_hip_api.py <workload> <ef|packed|roc> [reps] [host|device]   (device: CUDA offsets, the vidc_*_encode_dev path)"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +13,7 @@ cls = {"ef": EfLists, "packed": PackedLists, "roc": RocLists}[sys.argv[2] if len
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 ids, off = w["ids"], w["offsets"]
 if isinstance(ids, np.ndarray): ids = torch.from_numpy(ids.view(np.int64)).cuda()
+if len(sys.argv) > 4 and sys.argv[4] == "device": off = torch.from_numpy(off.view(np.int64)).cuda()
 out = torch.empty(w["ntotal"], dtype=torch.int64, device="cuda")
 te = td = ke = kd = 0.0
 for it in range(reps + 3):

@@ -188,30 +188,86 @@ def _decode_gather(fn, obj, list_nos, item_slot, item_off):
     return out[: sl.size]
 
 
-class RocLists:
-    """ROC-compressed lists (vidc_roc): bit-identical streams to codec.cpp."""
+class _ListCodec:
+    """What the four list codecs share: the handle and its release, the lazily fetched host offsets, ntotal, and the calls that differ
+    only in the C symbol (`_prefix` + "_decode_all", ...).  Each class picks how its offsets are fetched in its own `offsets`."""
 
-    def __init__(self, handle, ctx, offsets):
+    _prefix = None  # "vidc_packed", ...
+
+    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
         self.h = handle
         self.ctx = ctx
         self._offsets = offsets
+        self._nlist = nlist
+        self._ntotal = ntotal
 
-    @property
-    def offsets(self):
-        """CSR offsets of the decoded output.  Graph objects fetch the edge counts from the device on first use
-        (the per-node metadata stays on the GPU otherwise)."""
+    def _fn(self, name):
+        return getattr(lib(), f"{self._prefix}_{name}")
+
+    def __del__(self):
+        try:  # may run during interpreter shutdown, after module globals are gone
+            if getattr(self, "h", None):
+                self._fn("destroy")(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _offsets_from_symbol(self):
+        """the object's own offsets array (vidc_*_offsets), fetched once"""
+        if self._offsets is None:
+            off = np.zeros(self._nlist + 1, np.uint64)
+            check(self._fn("offsets")(self.ctx.h, self.h, ptr(off)))
+            self._offsets = off
+        return self._offsets
+
+    def _offsets_from_info(self):
+        """the prefix sum of info()["sizes"], computed once"""
         if self._offsets is None:
             sizes = self.info()["sizes"]
             self._offsets = np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]).astype(np.uint64)
         return self._offsets
 
-    def __del__(self):
-        try:  # may run during interpreter shutdown, after module globals are gone
-            if getattr(self, "h", None):
-                lib().vidc_roc_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+    @property
+    def ntotal(self):
+        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
+
+    def decode_all(self, out=None):
+        torch = _torch()
+        if out is None:
+            out = torch.empty(max(self.ntotal, 1), dtype=torch.int64, device="cuda")
+        check(self._fn("decode_all")(self.ctx.h, self.h, ptr(out)))
+        return out[: self.ntotal]
+
+    def decode_lists(self, list_nos):
+        """Decode the requested lists back to back (work proportional to their sizes) -> (int64 CUDA tensor, offsets)."""
+        torch = _torch()
+        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
+        sizes = (self.offsets[1:] - self.offsets[:-1])[ln.astype(np.int64)] if ln.size else np.zeros(0, np.uint64)
+        total = int(sizes.sum())
+        out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
+        out_off = np.zeros(ln.size + 1, np.uint64)
+        check(self._fn("decode_lists")(self.ctx.h, self.h, ln.size, ptr(ln), ptr(out), ptr(out_off)))
+        return out[:total], out_off
+
+    def _get(self, name, list_nos, offs):
+        """ids[i] = list_nos[i][offs[i]] (vidc_*_get / vidc_wt_select) -> numpy int64"""
+        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
+        of = np.ascontiguousarray(offs, dtype=np.uint64)
+        out = np.zeros(max(ln.size, 1), np.int64)
+        check(self._fn(name)(self.ctx.h, self.h, ln.size, ptr(ln), ptr(of), ptr(out)))
+        return out[: ln.size]
+
+
+class RocLists(_ListCodec):
+    """ROC-compressed lists (vidc_roc): bit-identical streams to codec.cpp."""
+
+    _prefix = "vidc_roc"
+
+    @property
+    def offsets(self):
+        """CSR offsets of the decoded output.  Graph objects fetch the edge counts from the device on first use
+        (the per-node metadata stays on the GPU otherwise)."""
+        return self._offsets_from_info()
 
     # -- construction
     @classmethod
@@ -332,24 +388,7 @@ class RocLists:
         check(lib().vidc_roc_perm(self.ctx.h, self.h, ptr(p)))
         return p[: self.ntotal]
 
-    # -- decode
-    def decode_all(self, out=None):
-        torch = _torch()
-        if out is None:
-            out = torch.empty(max(self.ntotal, 1), dtype=torch.int64, device="cuda")
-        check(lib().vidc_roc_decode_all(self.ctx.h, self.h, ptr(out)))
-        return out[: self.ntotal]
-
-    def decode_lists(self, list_nos):
-        torch = _torch()
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        sizes = (self.offsets[1:] - self.offsets[:-1])[ln.astype(np.int64)] if ln.size else np.zeros(0, np.uint64)
-        total = int(sizes.sum())
-        out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
-        out_off = np.zeros(ln.size + 1, np.uint64)
-        check(lib().vidc_roc_decode_lists(self.ctx.h, self.h, ln.size, ptr(ln), ptr(out), ptr(out_off)))
-        return out[:total], out_off
-
+    # -- decode (decode_all, decode_lists: _ListCodec)
     def decode_gather(self, list_nos, item_slot, item_off):
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
         8 bytes per result copied to the host (vidc_roc_decode_gather)."""
@@ -383,32 +422,15 @@ class RocLists:
         return int(lib().vidc_roc_last_decode_nonclean(self.h))
 
 
-class PackedLists:
+class PackedLists(_ListCodec):
     """Fixed-width packed ids (vidc_packed): ceil(log2(ntotal+1)) bits per id, LSB-first."""
 
-    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
-        self.h = handle
-        self.ctx = ctx
-        self._offsets = offsets
-        self._nlist = nlist
-        self._ntotal = ntotal
+    _prefix = "vidc_packed"
 
     @property
     def offsets(self):
         """CSR offsets (host).  Objects built from device offsets copy the object's own device array on first use."""
-        if self._offsets is None:
-            off = np.zeros(self._nlist + 1, np.uint64)
-            check(lib().vidc_packed_offsets(self.ctx.h, self.h, ptr(off)))
-            self._offsets = off
-        return self._offsets
-
-    def __del__(self):
-        try:  # may run during interpreter shutdown, after module globals are gone
-            if getattr(self, "h", None):
-                lib().vidc_packed_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        return self._offsets_from_symbol()
 
     @staticmethod
     def bits_for(ntotal):
@@ -443,34 +465,12 @@ class PackedLists:
         return type(self)(h, self.ctx, None, self._nlist if self._offsets is None else self._offsets.size - 1, None), lab
 
     @property
-    def ntotal(self):
-        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
-
-    @property
     def bits(self):
         return int(lib().vidc_packed_bits(self.h))
 
     @property
     def compressed_bytes(self):
         return int(lib().vidc_packed_compressed_bytes(self.h))
-
-    def decode_all(self, out=None):
-        torch = _torch()
-        if out is None:
-            out = torch.empty(max(self.ntotal, 1), dtype=torch.int64, device="cuda")
-        check(lib().vidc_packed_decode_all(self.ctx.h, self.h, ptr(out)))
-        return out[: self.ntotal]
-
-    def decode_lists(self, list_nos):
-        """Decode the requested lists back to back (work proportional to their sizes) -> (int64 CUDA tensor, offsets)."""
-        torch = _torch()
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        sizes = (self.offsets[1:] - self.offsets[:-1])[ln.astype(np.int64)] if ln.size else np.zeros(0, np.uint64)
-        total = int(sizes.sum())
-        out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
-        out_off = np.zeros(ln.size + 1, np.uint64)
-        check(lib().vidc_packed_decode_lists(self.ctx.h, self.h, ln.size, ptr(ln), ptr(out), ptr(out_off)))
-        return out[:total], out_off
 
     def decode_gather(self, list_nos, item_slot, item_off):
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
@@ -484,11 +484,7 @@ class PackedLists:
         return _translate_labels(lib().vidc_packed_translate_labels_dev, self, labels, out, invalid)
 
     def get(self, list_nos, offs):
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        of = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = np.zeros(max(ln.size, 1), np.int64)
-        check(lib().vidc_packed_get(self.ctx.h, self.h, ln.size, ptr(ln), ptr(of), ptr(out)))
-        return out[: ln.size]
+        return self._get("get", list_nos, offs)
 
     # -- flat on-disk / wire image (the reference keeps compressed lists in memory only)
     def save(self, path):
@@ -516,31 +512,15 @@ class PackedLists:
         return buf[:nb]
 
 
-class EfLists:
+class EfLists(_ListCodec):
     """Elias-Fano coded lists (vidc_ef), succinct::elias_fano geometry."""
 
-    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
-        self.h = handle
-        self.ctx = ctx
-        self._offsets = offsets
-        self._nlist = nlist
-        self._ntotal = ntotal
+    _prefix = "vidc_ef"
 
     @property
     def offsets(self):
         """CSR offsets of the decoded output (graph objects fetch the edge counts from the device on first use)."""
-        if self._offsets is None:
-            sizes = self.info()["sizes"]
-            self._offsets = np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]).astype(np.uint64)
-        return self._offsets
-
-    def __del__(self):
-        try:  # may run during interpreter shutdown, after module globals are gone
-            if getattr(self, "h", None):
-                lib().vidc_ef_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        return self._offsets_from_info()
 
     @classmethod
     def encode(cls, offsets, ids, want_perm=False, ctx=None):
@@ -568,10 +548,6 @@ class EfLists:
         return type(self)(h, self.ctx, None, self._nlist if self._offsets is None else self._offsets.size - 1, None), lab
 
     @property
-    def ntotal(self):
-        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
-
-    @property
     def compressed_bytes(self):
         return int(lib().vidc_ef_compressed_bytes(self.h))
 
@@ -583,19 +559,8 @@ class EfLists:
         check(lib().vidc_ef_list_info(self.h, ptr(sizes), ptr(lb), ptr(uni)))
         return dict(sizes=sizes[:n], low_bits=lb[:n], universe=uni[:n])
 
-    def decode_all(self, out=None):
-        torch = _torch()
-        if out is None:
-            out = torch.empty(max(self.ntotal, 1), dtype=torch.int64, device="cuda")
-        check(lib().vidc_ef_decode_all(self.ctx.h, self.h, ptr(out)))
-        return out[: self.ntotal]
-
     def get(self, list_nos, offs):
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        of = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = np.zeros(max(ln.size, 1), np.int64)
-        check(lib().vidc_ef_get(self.ctx.h, self.h, ln.size, ptr(ln), ptr(of), ptr(out)))
-        return out[: ln.size]
+        return self._get("get", list_nos, offs)
 
     def perm(self):
         p = np.zeros(max(self.ntotal, 1), np.uint32)
@@ -635,16 +600,6 @@ class EfLists:
         counts = np.zeros(max(m, 1), np.uint32) if want_counts else None
         check(lib().vidc_ef_decode_rows(self.ctx.h, self.h, m, ptr(nd), K, ptr(out), ptr(counts)))
         return out[:m], (counts[:m] if want_counts else None)
-
-    def decode_lists(self, list_nos):
-        torch = _torch()
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        sizes = (self.offsets[1:] - self.offsets[:-1])[ln.astype(np.int64)] if ln.size else np.zeros(0, np.uint64)
-        total = int(sizes.sum())
-        out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
-        out_off = np.zeros(ln.size + 1, np.uint64)
-        check(lib().vidc_ef_decode_lists(self.ctx.h, self.h, ln.size, ptr(ln), ptr(out), ptr(out_off)))
-        return out[:total], out_off
 
     def decode_gather(self, list_nos, item_slot, item_off):
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
@@ -756,32 +711,15 @@ class CompactRows:
         return buf
 
 
-class WaveletTreeLists:
+class WaveletTreeLists(_ListCodec):
     """Wavelet tree over list_nos[id] (vidc_wt): id = select(offset + 1, list_no)."""
 
-    def __init__(self, handle, ctx, offsets, nlist=None, ntotal=None):
-        self.h = handle
-        self.ctx = ctx
-        self._offsets = offsets
-        self._nlist = nlist
-        self._ntotal = ntotal
+    _prefix = "vidc_wt"
 
     @property
     def offsets(self):
         """CSR offsets (host).  Objects built from device offsets copy the object's own device array on first use."""
-        if self._offsets is None:
-            off = np.zeros(self._nlist + 1, np.uint64)
-            check(lib().vidc_wt_offsets(self.ctx.h, self.h, ptr(off)))
-            self._offsets = off
-        return self._offsets
-
-    def __del__(self):
-        try:  # may run during interpreter shutdown, after module globals are gone
-            if getattr(self, "h", None):
-                lib().vidc_wt_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
+        return self._offsets_from_symbol()
 
     @classmethod
     def build(cls, offsets, ids, wt_type=0, ctx=None):
@@ -809,27 +747,12 @@ class WaveletTreeLists:
         return type(self)(h, self.ctx, None, self._nlist if self._offsets is None else self._offsets.size - 1, None), lab
 
     @property
-    def ntotal(self):
-        return self._ntotal if self._ntotal is not None else int(self.offsets[-1])
-
-    @property
     def size_in_bytes(self):
         return int(lib().vidc_wt_size_in_bytes(self.h))
 
     @property
     def levels(self):
         return int(lib().vidc_wt_levels(self.h))
-
-    def decode_lists(self, list_nos):
-        """Decode the requested lists back to back (work proportional to their sizes) -> (int64 CUDA tensor, offsets)."""
-        torch = _torch()
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        sizes = (self.offsets[1:] - self.offsets[:-1])[ln.astype(np.int64)] if ln.size else np.zeros(0, np.uint64)
-        total = int(sizes.sum())
-        out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
-        out_off = np.zeros(ln.size + 1, np.uint64)
-        check(lib().vidc_wt_decode_lists(self.ctx.h, self.h, ln.size, ptr(ln), ptr(out), ptr(out_off)))
-        return out[:total], out_off
 
     def decode_gather(self, list_nos, item_slot, item_off):
         """ids[i] = list_nos[item_slot[i]][item_off[i]]: the touched lists decoded and the results picked on the device,
@@ -843,15 +766,4 @@ class WaveletTreeLists:
         return _translate_labels(lib().vidc_wt_translate_labels_dev, self, labels, out, invalid)
 
     def select(self, list_nos, offs):
-        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
-        of = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = np.zeros(max(ln.size, 1), np.int64)
-        check(lib().vidc_wt_select(self.ctx.h, self.h, ln.size, ptr(ln), ptr(of), ptr(out)))
-        return out[: ln.size]
-
-    def decode_all(self, out=None):
-        torch = _torch()
-        if out is None:
-            out = torch.empty(max(self.ntotal, 1), dtype=torch.int64, device="cuda")
-        check(lib().vidc_wt_decode_all(self.ctx.h, self.h, ptr(out)))
-        return out[: self.ntotal]
+        return self._get("select", list_nos, offs)

@@ -17,6 +17,7 @@
 #include "append.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "host_call.h"
 #include "scan.h"
 #include "rows_csr.h"
 #include "requests.h"
@@ -1708,12 +1709,6 @@ __global__ void k_ef_geom(const uint64_t *offsets, const PrepOut *prep, uint32_t
 
 namespace {
 
-template <typename T>
-int ef_mirror(std::vector<T> &dst, const T *d_src, size_t count) {
-    dst.resize(count);
-    if (count) VIDC_HIP(hipMemcpy(dst.data(), d_src, count * sizeof(T), hipMemcpyDeviceToHost));
-    return VIDC_OK;
-}
 // words of the two streams (a buffer allocated by a bound is longer than its stream; an empty stream is kept as one word)
 inline uint64_t ef_low_count(const vidc_ef *e) { return e->n_low != ~0ull ? std::max<uint64_t>(e->n_low, 1) : e->d_low.n; }
 inline uint64_t ef_high_count(const vidc_ef *e) { return e->n_high != ~0ull ? std::max<uint64_t>(e->n_high, 1) : e->d_high.n; }
@@ -1744,12 +1739,7 @@ int ef_arena_mirror_locked(const vidc_ef *e) {
     return VIDC_OK;
 }
 int ef_ensure_offsets_locked(const vidc_ef *e) {
-    if (e->arena) return ef_arena_mirror_locked(e);
-    if (e->offsets_host) return VIDC_OK;
-    VIDC_HIP(hipSetDevice(e->device));
-    VIDC_TRY(ef_mirror(e->offsets, (const uint64_t *)e->d_offsets.p, e->nlist + 1));
-    e->offsets_host = true;
-    return VIDC_OK;
+    return e->arena ? ef_arena_mirror_locked(e) : ensure_offsets_host_locked(e, e->d_offsets.p);
 }
 int ef_ensure_offsets(const vidc_ef *e) {
     std::lock_guard<std::mutex> g(e->mu);
@@ -1760,10 +1750,10 @@ int ef_ensure_meta(const vidc_ef *e) {
     VIDC_TRY(ef_ensure_offsets_locked(e));
     if (e->meta_host) return VIDC_OK;
     VIDC_HIP(hipSetDevice(e->device));
-    VIDC_TRY(ef_mirror(e->low_off, (const uint64_t *)e->d_low_off.p, e->nlist + 1));
-    VIDC_TRY(ef_mirror(e->high_off, (const uint64_t *)e->d_high_off.p, e->nlist + 1));
-    VIDC_TRY(ef_mirror(e->universe, (const uint64_t *)e->d_universe.p, e->nlist));
-    VIDC_TRY(ef_mirror(e->lbits, (const uint32_t *)e->d_lbits.p, e->nlist));
+    VIDC_TRY(mirror_to_host(e->low_off, (const uint64_t *)e->d_low_off.p, e->nlist + 1));
+    VIDC_TRY(mirror_to_host(e->high_off, (const uint64_t *)e->d_high_off.p, e->nlist + 1));
+    VIDC_TRY(mirror_to_host(e->universe, (const uint64_t *)e->d_universe.p, e->nlist));
+    VIDC_TRY(mirror_to_host(e->lbits, (const uint32_t *)e->d_lbits.p, e->nlist));
     e->high_nbits.assign(e->nlist, 0);
     for (uint64_t l = 0; l < e->nlist; l++) {
         const uint64_t m = e->offsets[l + 1] - e->offsets[l];
@@ -2220,11 +2210,7 @@ int vidc_ef_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
     VIDC_TRY(e->d_offsets.alloc(nlist + 1, ctx->dpool));
     Pinned h_off;
     VIDC_TRY(h_off.get(ctx, (nlist + 1) * 8));
-    struct SyncOnExit {  // (an early return must not release the staging block of a copy in flight)
-        vidc_ctx *c;
-        bool armed = true;
-        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
-    } guard{ctx};
+    StreamGuard guard(ctx);  // (an early return must not release the staging block of a copy in flight)
     if (nlist) std::memcpy(h_off.p, offsets, (nlist + 1) * 8);
     else *h_off.as<uint64_t>() = 0;
     VIDC_HIP(hipMemcpyAsync(e->d_offsets.p, h_off.p, (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -2245,7 +2231,7 @@ int vidc_ef_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
     if (e->ntotal && !d_ids) return VIDC_ERR_INVALID;
     tr.mark("host offsets pass");
     VIDC_TRY(ef_encode_lists(ctx, e.get(), d_ids, flags, nchunks, max_list, offsets));
-    guard.armed = false;
+    guard.disarm();
     *out = e.release();
     return VIDC_OK;
 }
@@ -2327,13 +2313,9 @@ int vidc_ef_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets,
     Pinned h_sum;
     VIDC_TRY(h_sum.get(ctx, sizeof(DevOffSummary)));
     const EfDevIn dv{d_offsets, acc, h_sum.as<DevOffSummary>()};
-    struct SyncOnExit {  // (an early return must not release blocks that kernels in flight still use)
-        vidc_ctx *c;
-        bool armed = true;
-        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
-    } guard{ctx};
+    StreamGuard guard(ctx);  // (an early return must not release blocks that kernels in flight still use)
     VIDC_TRY(ef_encode_lists(ctx, e.get(), d_ids, flags, ntotal / EF_CHUNK + nlist, ntotal, nullptr, &dv));
-    guard.armed = false;
+    guard.disarm();
     *out = e.release();
     return VIDC_OK;
 }
@@ -2404,7 +2386,8 @@ int vidc_ef_decode_all(vidc_ctx *ctx, const vidc_ef *e, uint64_t *d_out) {
         }
         if (!publish_after_sync) g.unlock();
     }
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     if (e->nbatches) {
         const dim3 grid((uint32_t)std::min<uint64_t>(e->nbatches, (uint64_t)ctx->num_cu * 256));
         const uint32_t max_cnt = publish_after_sync ? pending_max_cnt : e->recs_max_cnt;
@@ -2424,16 +2407,14 @@ int vidc_ef_decode_all(vidc_ctx *ctx, const vidc_ef *e, uint64_t *d_out) {
                                e->d_recs.p, (uint32_t)e->nbatches, d_out);
     }
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    VIDC_HIP(t.mark());
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     if (publish_after_sync) { e->recs_max_cnt = pending_max_cnt; e->recs_ready = true; g.unlock(); }
     if (recs_timed) {
         float rms = 0;
         if (hipEventElapsedTime(&rms, ctx->ev_chain[0], ctx->ev_chain[1]) == hipSuccess) recs_ms = rms;
     }
-    ctx->last_kernel_ms = ms + recs_ms;
+    ctx->last_kernel_ms = t.elapsed() + recs_ms;  // (+ the records' own interval, ev_chain)
     return VIDC_OK;
 }
 
@@ -2456,7 +2437,8 @@ static int ef_decode_some(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uin
         std::memcpy(h_up.as<uint64_t>() + m, out_off_host, m * 8);
         VIDC_HIP(hipMemcpyAsync(s_o.p, h_up.as<uint64_t>() + m, m * 8, hipMemcpyHostToDevice, ctx->stream));
     }
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     {
         // few lists: several workgroups per list (by the longest requested list, ~2048 ids per workgroup; the host knows the sizes
         // whenever it knows the output offsets)
@@ -2475,11 +2457,7 @@ static int ef_decode_some(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uin
                            d_l, out_off_host ? s_o.as<uint64_t>() : nullptr, d_out, d_rows, K, nsplit);
     }
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    VIDC_TRY(t.finish());
     if (counts_host) VIDC_TRY(fetch_sizes<uint64_t>(ctx, e->d_offsets.p, d_l, m, counts_host));
     return VIDC_OK;
 }
@@ -2489,11 +2467,7 @@ int vidc_ef_decode_lists(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint
     if (!ctx || !e || (m && !list_nos) || !out_offsets) return VIDC_ERR_INVALID;
     VIDC_TRY(ef_ensure_csr(ctx, e));
     VIDC_TRY(ef_ensure_offsets(e));
-    out_offsets[0] = 0;
-    for (uint64_t i = 0; i < m; i++) {
-        if (list_nos[i] >= e->nlist) { set_error("list number out of range"); return VIDC_ERR_INVALID; }
-        out_offsets[i + 1] = out_offsets[i] + (e->offsets[list_nos[i] + 1] - e->offsets[list_nos[i]]);
-    }
+    VIDC_TRY(lists_request_offsets(e->nlist, e->offsets, m, list_nos, out_offsets));
     if (!m) return VIDC_OK;
     return ef_decode_some(ctx, e, m, list_nos, out_offsets, d_out, nullptr, 0);
 }
@@ -2566,15 +2540,14 @@ static int ef_decode_rows_arena(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, con
         d_nodes = s_n.as<uint64_t>();
     }
     if (counts) VIDC_TRY(s_c.get(ctx, m * 4));
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     VIDC_TRY(ef_rows_arena_launch(ctx, e, m, d_nodes, K, d_out, counts ? s_c.as<uint32_t>() : nullptr));
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    VIDC_HIP(t.mark());  // (in front of the counts copy: the copy is not kernel time)
     if (counts) VIDC_HIP(hipMemcpyAsync(h_io.p, s_c.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
     if (counts) std::memcpy(counts, h_io.p, m * 4);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    ctx->last_kernel_ms = t.elapsed();
     return VIDC_OK;
 }
 
@@ -2636,13 +2609,14 @@ int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_
     // ids) is seen by the kernel, which reports the largest id, and the call is repeated with records sized for it.
     uint32_t ubound = N ? (uint32_t)std::min<uint64_t>(N - 1, 0x7fffffffull) : 0u;
     const bool vec = ((uintptr_t)d_rows & 15u) == 0;
+    EventTimer tm(ctx);
     for (int attempt = 0;; attempt++) {
         ef_rows_geometry(K, ubound, &e->a_lw, &e->a_hw);
         const uint32_t S = e->a_lw + e->a_hw;
         if (2u * S + 1u > (K <= 32 ? 33u : 65u)) { set_error("EF rows: record of %u words does not fit the tile", S); return VIDC_ERR_UNSUPPORTED; }
         VIDC_TRY(e->d_arena.alloc(N * S + 2, ctx->dpool));  // (+2: the decoder reads 16-byte pieces)
         VIDC_HIP(hipMemsetAsync(s_tot.p, 0, tot_bytes, ctx->stream));
-        VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        VIDC_HIP(tm.start());
         if (N) {
             const dim3 grid((uint32_t)((N + 63) / 64));
             EfRowsTot *d_tot = s_tot.as<EfRowsTot>();
@@ -2659,7 +2633,7 @@ int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_
 #undef VIDC_EF_ROWS_ENC
             VIDC_HIP(hipGetLastError());
         }
-        VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        VIDC_HIP(tm.mark());
         VIDC_HIP(hipMemcpyAsync(tail.p, s_tot.p, tot_bytes, hipMemcpyDeviceToHost, ctx->stream));
         VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
         const EfRowsTot *t = tail.as<EfRowsTot>();
@@ -2671,9 +2645,7 @@ int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_
         for (int i = 0; i < 64; i++) { e->ntotal += t[i].edges; e->total_bits += t[i].bits; }
         break;
     }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    ctx->last_kernel_ms = tm.elapsed();
     *out = e.release();
     return VIDC_OK;
 }
@@ -2741,26 +2713,10 @@ int vidc_ef_get(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *lis
     if (!m) return VIDC_OK;
     VIDC_TRY(ef_ensure_csr(ctx, e));
     VIDC_TRY(ef_ensure_offsets(e));
-    for (uint64_t i = 0; i < m; i++) {
-        if (list_nos[i] >= e->nlist || offs[i] >= e->offsets[list_nos[i] + 1] - e->offsets[list_nos[i]]) {
-            set_error("ef get: (list %llu, offset %llu) out of range", (unsigned long long)list_nos[i],
-                      (unsigned long long)offs[i]);
-            return VIDC_ERR_INVALID;
-        }
-    }
-    VIDC_HIP(hipSetDevice(ctx->device));
-    Scratch s_l, s_o, s_r;
-    VIDC_TRY(s_l.get(ctx, m * 8)); VIDC_TRY(s_o.get(ctx, m * 8)); VIDC_TRY(s_r.get(ctx, m * 8));
-    VIDC_HIP(hipMemcpyAsync(s_l.p, list_nos, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    VIDC_HIP(hipMemcpyAsync(s_o.p, offs, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_ef_get, dim3((uint32_t)std::min<uint64_t>(m, 1u << 20)), dim3(64), 0, ctx->stream, e->d_low.p,
-                       e->d_high.p, e->d_low_off.p, e->d_high_off.p, e->d_lbits.p, e->d_batch_off.p, e->d_hrank.p, m,
-                       s_l.as<uint64_t>(), s_o.as<uint64_t>(), s_r.as<int64_t>());
-    VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipMemcpyAsync(ids_out, s_r.p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    ctx->d2h_bytes += m * 8;
-    return VIDC_OK;
+    return get_request(ctx, "ef get", e->nlist, e->offsets, m, list_nos, offs, ids_out, [&](const uint64_t *d_l, const uint64_t *d_o, int64_t *d_r) {
+        hipLaunchKernelGGL(k_ef_get, dim3((uint32_t)std::min<uint64_t>(m, 1u << 20)), dim3(64), 0, ctx->stream, e->d_low.p, e->d_high.p,
+                           e->d_low_off.p, e->d_high_off.p, e->d_lbits.p, e->d_batch_off.p, e->d_hrank.p, m, d_l, d_o, d_r);
+    });
 }
 
 int vidc_ef_perm(vidc_ctx *ctx, const vidc_ef *e, uint32_t *perm_host) {

@@ -15,6 +15,7 @@
 #include "append.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "host_call.h"
 #include "requests.h"
 #include "rows_tile.h"
 #include "scan.h"
@@ -651,6 +652,9 @@ struct vidc_compact {
     DevBuf<uint8_t> d_data;
 };
 
+// the rows_tile.h kernels serve the object (they write every byte of every row, and need no counts array to decode)
+static bool compact_tile(const vidc_compact *c) { return c->K <= 64 && (c->stride & 3u) == 0u; }
+
 extern "C" {
 
 int vidc_compact_rows_encode(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, vidc_compact **out) {
@@ -668,11 +672,12 @@ int vidc_compact_rows_encode(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_
     Scratch s_err;
     VIDC_TRY(s_err.get(ctx, 4));
     VIDC_HIP(hipMemsetAsync(s_err.p, 0, 4, ctx->stream));
-    const bool tile = K <= 64 && (c->stride & 3u) == 0u;  // (rows_tile.h kernels: they write every byte of every row)
+    const bool tile = compact_tile(c.get());
     if (tile) VIDC_HIP(hipMemsetAsync(c->d_data.p + N * c->stride, 0, 8, ctx->stream));
     else VIDC_HIP(hipMemsetAsync(c->d_data.p, 0, N * c->stride + 8, ctx->stream));
+    EventTimer t(ctx);
     if (N) {
-        VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        VIDC_HIP(t.start());
         uint32_t grid = (uint32_t)std::min<uint64_t>(N, (uint64_t)ctx->num_cu * 64);
         if (tile) {
             const uint32_t SD = c->stride / 4u, vec = ((uintptr_t)d_rows & 15u) == 0 ? 1u : 0u;
@@ -694,16 +699,12 @@ int vidc_compact_rows_encode(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_
             hipLaunchKernelGGL(k_compact_rows_encode_wide, dim3(grid), dim3(64), (c->stride / 4u + 2u) * 4u, ctx->stream, d_rows,
                                N, K, c->bits, c->stride, c->d_data.p, s_err.as<uint32_t>());
         VIDC_HIP(hipGetLastError());
-        VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        VIDC_HIP(t.mark());
     }
     uint32_t err = 0;
     VIDC_HIP(hipMemcpyAsync(&err, s_err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    if (N) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-        ctx->last_kernel_ms = ms;
-    }
+    if (N) ctx->last_kernel_ms = t.elapsed();
     if (err) { set_error("compact rows: neighbour id outside [0, N)"); return VIDC_ERR_DOMAIN; }
     *out = c.release();
     return VIDC_OK;
@@ -715,8 +716,7 @@ uint64_t vidc_compact_size_in_bytes(const vidc_compact *c) { return c ? c->N * c
 
 // the row decoder of a compact object for m rows (d_nodes == NULL: rows 0..m-1); d_cnt may be NULL only for the tile decoder
 static int compact_rows_launch(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const uint64_t *d_nodes, int32_t *d_out, uint32_t *d_cnt) {
-    const bool tile = c->K <= 64 && (c->stride & 3u) == 0u;
-    if (tile) {
+    if (compact_tile(c)) {
         const uint32_t SD = c->stride / 4u;
         const size_t dyn = ((size_t)64 * (SD | 1u) + 1u) * 4u;
         const dim3 tgrid(dev::tile_grid(ctx->num_cu, (m + 63) / 64, (uint32_t)std::min<size_t>(16, (150u << 10) / dyn)));
@@ -746,7 +746,7 @@ int vidc_compact_rows_decode(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, c
     VIDC_HIP(hipSetDevice(ctx->device));
     Scratch s_n, s_c;
     Pinned h_io;
-    const bool tile = c->K <= 64 && (c->stride & 3u) == 0u;
+    const bool tile = compact_tile(c);
     if (counts || !tile) VIDC_TRY(s_c.get(ctx, m * 4));
     if (counts || nodes) VIDC_TRY(h_io.get(ctx, m * 8));
     const uint64_t *d_nodes = nullptr;  // nodes == NULL: rows 0..m-1, no index array
@@ -756,15 +756,14 @@ int vidc_compact_rows_decode(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, c
         VIDC_HIP(hipMemcpyAsync(s_n.p, h_io.p, m * 8, hipMemcpyHostToDevice, ctx->stream));
         d_nodes = s_n.as<uint64_t>();
     }
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     VIDC_TRY(compact_rows_launch(ctx, c, m, d_nodes, d_out, (counts || !tile) ? s_c.as<uint32_t>() : nullptr));
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    VIDC_HIP(t.mark());  // (in front of the counts copy: the copy is not kernel time)
     if (counts) VIDC_HIP(hipMemcpyAsync(h_io.p, s_c.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
     if (counts) std::memcpy(counts, h_io.p, m * 4);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    ctx->last_kernel_ms = t.elapsed();
     return VIDC_OK;
 }
 
@@ -773,7 +772,7 @@ int vidc_compact_rows_decode_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t 
     VIDC_TRY(req_check_rows(ctx, c, m, d_nodes, d_out));
     if (!m) return VIDC_OK;
     VIDC_HIP(hipSetDevice(ctx->device));
-    const bool tile = c->K <= 64 && (c->stride & 3u) == 0u;  // (the other two decoders always write counts)
+    const bool tile = compact_tile(c);  // (the other two decoders always write counts)
     return req_rows_on_device<uint64_t>(ctx, c->N, m, d_nodes, c->K, d_out, d_counts, d_invalid, !tile,
                                         [&](const uint64_t *nd, uint32_t *cnt) { return compact_rows_launch(ctx, c, m, nd, d_out, cnt); });
 }
@@ -783,18 +782,7 @@ int vidc_compact_export_row(vidc_ctx *ctx, const vidc_compact *c, uint64_t node,
     return vidc_copy_d2h(ctx, bytes, c->d_data.p + node * c->stride, c->stride);
 }
 
-// the host mirror of an object built from device offsets, on first use (one copy of nlist + 1 words)
-static int packed_ensure_offsets(const vidc_packed *p) {
-    std::lock_guard<std::mutex> g(p->mu);
-    if (p->offsets_host) return VIDC_OK;
-    VIDC_HIP(hipSetDevice(p->device));
-    std::vector<uint64_t> h = vec_pool<uint64_t>().take(p->nlist + 1);
-    h.resize(p->nlist + 1);
-    VIDC_HIP(hipMemcpy(h.data(), p->d_offsets.p, (p->nlist + 1) * 8, hipMemcpyDeviceToHost));
-    p->offsets = std::move(h);
-    p->offsets_host = true;
-    return VIDC_OK;
-}
+static int packed_ensure_offsets(const vidc_packed *p) { return ensure_offsets_host(p, p->d_offsets.p); }
 
 int vidc_packed_offsets(vidc_ctx *ctx, const vidc_packed *p, uint64_t *offsets) {
     if (!ctx || !p || !offsets) return VIDC_ERR_INVALID;
@@ -809,13 +797,29 @@ int vidc_packed_bits_for(uint64_t ntotal) {  // custom_invlists_impl.cpp:68-70
     return bits;
 }
 
+// lists per thread of k_packed_table (256 threads per tile) and its tiles: an object of up to 4095 lists is ONE tile (no chained scan,
+// no cleared state), larger ones aim at ~1024 tiles -- 65 536 lists ran as 17 tiles of 4096 on 17 of the 256 CUs (16.3 us of a 102 us
+// encode + decode of 16 M ids), 2^20 lists as 257
+struct PackedTiling { uint32_t per, ntiles; };
+static PackedTiling packed_table_tiling(uint64_t nlist) {
+    const uint32_t per = nlist + 1 <= 4096u ? (uint32_t)((nlist + 1 + 255u) / 256u)
+                                            : (uint32_t)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (nlist + 1 + 262143u) / 262144u));
+    return {per, (uint32_t)((nlist + 1 + 256u * per - 1u) / (256u * per))};
+}
+static int packed_id_does_not_fit(int bits) {
+    set_error("packed bits: an id does not fit %d bits (reference: FAISS_THROW_IF_NOT(ids_in[i] >= 0 && "
+              "ids_in[i] < ntotal), custom_invlists_impl.cpp:87)", bits);
+    return VIDC_ERR_DOMAIN;
+}
+
 // geometry, offsets / word offsets on the device, chunk table (shared by encode and import).  Nothing is waited for here: the staging
 // block and the scan state live in `keep` until the caller has synchronised.
 struct PackedSetupKeep {
     Pinned h_up;
     Scratch s_state;
 };
-static int packed_setup(vidc_ctx *ctx, vidc_packed *p, uint64_t nlist, const uint64_t *offsets, int bits, PackedSetupKeep &keep) {
+static int packed_setup(vidc_ctx *ctx, vidc_packed *p, uint64_t nlist, const uint64_t *offsets, int bits, PackedSetupKeep &keep,
+                        EventTimer &t) {
     p->device = ctx->device;
     p->nlist = nlist;
     p->bits = bits;
@@ -846,15 +850,10 @@ static int packed_setup(vidc_ctx *ctx, vidc_packed *p, uint64_t nlist, const uin
     VIDC_TRY(p->d_word_off.alloc(nlist + 1, ctx->dpool));
     VIDC_TRY(p->d_words.alloc(p->total_words ? p->total_words : 1, ctx->dpool));
     VIDC_TRY(p->d_chunks.alloc(p->nchunks ? p->nchunks : 1, ctx->dpool));
-    // lists per thread of k_packed_table (256 threads per tile): an object of up to 4095 lists is ONE tile (no chained scan, no cleared
-    // state), larger ones aim at ~1024 tiles -- 65 536 lists ran as 17 tiles of 4096 on 17 of the 256 CUs (16.3 us of a 102 us
-    // encode + decode of 16 M ids), 2^20 lists as 257
-    const uint32_t per = nlist + 1 <= 4096u ? (uint32_t)((nlist + 1 + 255u) / 256u)
-                                            : (uint32_t)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (nlist + 1 + 262143u) / 262144u));
-    const uint32_t ntiles = (uint32_t)((nlist + 1 + 256u * per - 1u) / (256u * per));
+    const auto [per, ntiles] = packed_table_tiling(nlist);
     VIDC_TRY(keep.s_state.get(ctx, ((size_t)2 * ntiles + 1) * 8));
-    // (the device work of the set-up is part of the encode's kernel time: the caller reads ev0 .. ev1)
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    // (the device work of the set-up is part of the encode's kernel time: the caller marks and reads its timer)
+    VIDC_HIP(t.start());
     if (ntiles > 1u) VIDC_HIP(hipMemsetAsync(keep.s_state.p, 0, ((size_t)2 * ntiles + 1) * 8, ctx->stream));
     hipLaunchKernelGGL(k_packed_table, dim3(ntiles), dim3(256), 0, ctx->stream, p->d_offsets.p, (uint32_t)nlist, (uint32_t)bits,
                        keep.s_state.as<unsigned long long>(), p->d_chunks.p, p->d_word_off.p, p->d_words.p, per);
@@ -870,12 +869,9 @@ int vidc_packed_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, c
     VIDC_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<vidc_packed> p(new vidc_packed());
     PackedSetupKeep keep;
-    struct SyncOnExit {  // (an early return must not release the staging block of copies still in flight)
-        vidc_ctx *c;
-        bool armed = true;
-        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
-    } guard{ctx};
-    VIDC_TRY(packed_setup(ctx, p.get(), nlist, offsets, bits, keep));
+    StreamGuard guard(ctx);  // (an early return must not release the staging block of copies still in flight)
+    EventTimer t(ctx);  // (started by packed_setup)
+    VIDC_TRY(packed_setup(ctx, p.get(), nlist, offsets, bits, keep, t));
     if (p->ntotal && !d_ids) return VIDC_ERR_INVALID;
     // the "an id does not fit" flag is stored by the kernels into pinned memory (no copy engine behind the last kernel)
     Pinned h_err;
@@ -896,20 +892,11 @@ int vidc_packed_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, c
                                h_err.as<uint32_t>());
         VIDC_HIP(hipGetLastError());
     }
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    guard.armed = false;
+    VIDC_HIP(t.mark());
+    guard.disarm();
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-        ctx->last_kernel_ms = ms;
-    }
-    const uint32_t err = *err_flag;
-    if (err) {
-        set_error("packed bits: an id does not fit %d bits (reference: FAISS_THROW_IF_NOT(ids_in[i] >= 0 && "
-                  "ids_in[i] < ntotal), custom_invlists_impl.cpp:87)", bits);
-        return VIDC_ERR_DOMAIN;
-    }
+    ctx->last_kernel_ms = t.elapsed();
+    if (*err_flag) return packed_id_does_not_fit(bits);
     *out = p.release();
     return VIDC_OK;
 }
@@ -938,10 +925,7 @@ int vidc_packed_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offs
     VIDC_TRY(p->d_word_off.alloc(nlist + 1, ctx->dpool));
     VIDC_TRY(p->d_words.alloc(words_b ? words_b : 1, ctx->dpool));
     VIDC_TRY(p->d_chunks.alloc(chunks_b ? chunks_b : 1, ctx->dpool));
-    // k_packed_table's tiling, as packed_setup
-    const uint32_t per = nlist + 1 <= 4096u ? (uint32_t)((nlist + 1 + 255u) / 256u)
-                                            : (uint32_t)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (nlist + 1 + 262143u) / 262144u));
-    const uint32_t ntiles = (uint32_t)((nlist + 1 + 256u * per - 1u) / (256u * per));
+    const auto [per, ntiles] = packed_table_tiling(nlist);
     // the ingest's accumulators / results (context block, no per-call memset); k_packed_table's scan state, cleared only when the object
     // has more than one tile (as packed_setup)
     unsigned long long *acc = nullptr;
@@ -956,12 +940,9 @@ int vidc_packed_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offs
     volatile uint32_t *err_flag = (volatile uint32_t *)(h_tail.as<char>() + 64);
     hs->done = 0;
     *err_flag = 0u;
-    struct SyncOnExit {  // (an early return must not release blocks that kernels in flight still use)
-        vidc_ctx *c;
-        bool armed = true;
-        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
-    } guard{ctx};
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    StreamGuard guard(ctx);  // (an early return must not release blocks that kernels in flight still use)
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     if (ntiles > 1u) VIDC_HIP(hipMemsetAsync(s_state.p, 0, ((size_t)2 * ntiles + 1) * 8, ctx->stream));
     hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, d_offsets, p->d_offsets.p, nlist, ntotal,
                        9u, (uint32_t)bits, ~0ull, acc, res, hs);
@@ -973,22 +954,14 @@ int vidc_packed_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offs
                            ctx->stream, d_ids, p->d_offsets.p, p->d_word_off.p, p->d_chunks.p, res, (uint32_t)bits, p->d_words.p,
                            (uint32_t *)err_flag);
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    guard.armed = false;
+    VIDC_HIP(t.mark());
+    guard.disarm();
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-        ctx->last_kernel_ms = ms;
-    }
+    ctx->last_kernel_ms = t.elapsed();
     const DevOffSummary sum = *hs;  // (after the wait)
     if (!sum.done) { set_error("packed bits: the offsets summary was not written"); return VIDC_ERR_HIP; }
     VIDC_TRY(doff_status(sum, "packed bits", VIDC_ERR_INVALID));
-    if (*err_flag) {
-        set_error("packed bits: an id does not fit %d bits (reference: FAISS_THROW_IF_NOT(ids_in[i] >= 0 && "
-                  "ids_in[i] < ntotal), custom_invlists_impl.cpp:87)", bits);
-        return VIDC_ERR_DOMAIN;
-    }
+    if (*err_flag) return packed_id_does_not_fit(bits);
     p->compressed_bytes = sum.bytes;
     p->total_words = sum.words;
     p->nchunks = sum.chunks;
@@ -1014,7 +987,8 @@ int vidc_packed_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, i
     std::unique_ptr<vidc_packed> p(new vidc_packed());
     PackedSetupKeep keep;
     {
-        const int st = packed_setup(ctx, p.get(), nlist, offsets, bits, keep);
+        EventTimer t(ctx);  // (started by the set-up; an import reports no kernel time)
+        const int st = packed_setup(ctx, p.get(), nlist, offsets, bits, keep, t);
         VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the staging block / scan state of the set-up)
         VIDC_TRY(st);
     }
@@ -1036,7 +1010,8 @@ int vidc_packed_decode_all(vidc_ctx *ctx, const vidc_packed *p, uint64_t *d_out)
     if (!ctx || !p || (p->ntotal && !d_out)) return VIDC_ERR_INVALID;
     if (!p->ntotal) return VIDC_OK;
     VIDC_HIP(hipSetDevice(ctx->device));
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     uint32_t grid = (uint32_t)std::min<uint64_t>(p->nchunks, (uint64_t)ctx->num_cu * 256);
     if (p->max_list <= 256)
         hipLaunchKernelGGL(k_packed_decode<4>, dim3(grid), dim3(64), 0, ctx->stream, p->d_words.p, p->d_offsets.p,
@@ -1045,11 +1020,7 @@ int vidc_packed_decode_all(vidc_ctx *ctx, const vidc_packed *p, uint64_t *d_out)
         hipLaunchKernelGGL(k_packed_decode<CHUNK_IDS / 64>, dim3(grid), dim3(64), 0, ctx->stream, p->d_words.p,
                            p->d_offsets.p, p->d_word_off.p, p->d_chunks.p, p->nchunks, (uint32_t)p->bits, d_out);
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    VIDC_TRY(t.finish());
     return VIDC_OK;
 }
 
@@ -1057,14 +1028,10 @@ int vidc_packed_decode_lists(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, co
                              uint64_t *out_offsets) {
     if (!ctx || !p || (m && !list_nos) || !out_offsets) return VIDC_ERR_INVALID;
     VIDC_TRY(packed_ensure_offsets(p));
-    out_offsets[0] = 0;
+    VIDC_TRY(lists_request_offsets(p->nlist, p->offsets, m, list_nos, out_offsets));
     std::vector<PackedItem> items;
-    for (uint64_t i = 0; i < m; i++) {
-        if (list_nos[i] >= p->nlist) { set_error("list number out of range"); return VIDC_ERR_INVALID; }
-        const uint64_t n = p->offsets[list_nos[i] + 1] - p->offsets[list_nos[i]];
-        out_offsets[i + 1] = out_offsets[i] + n;
-        for (uint64_t s = 0; s < n; s += CHUNK_IDS) items.push_back(PackedItem{(uint32_t)i, (uint32_t)s});
-    }
+    for (uint64_t i = 0; i < m; i++)
+        for (uint64_t s = 0, n = out_offsets[i + 1] - out_offsets[i]; s < n; s += CHUNK_IDS) items.push_back(PackedItem{(uint32_t)i, (uint32_t)s});
     ctx->last_kernel_ms = 0;
     if (items.empty()) return VIDC_OK;
     if (!d_out) return VIDC_ERR_INVALID;
@@ -1074,17 +1041,14 @@ int vidc_packed_decode_lists(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, co
     VIDC_HIP(hipMemcpyAsync(s_l.p, list_nos, m * 8, hipMemcpyHostToDevice, ctx->stream));
     VIDC_HIP(hipMemcpyAsync(s_o.p, out_offsets, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     VIDC_HIP(hipMemcpyAsync(s_i.p, items.data(), items.size() * sizeof(PackedItem), hipMemcpyHostToDevice, ctx->stream));
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     const uint32_t grid = (uint32_t)std::min<uint64_t>(items.size(), (uint64_t)ctx->num_cu * 256);
     hipLaunchKernelGGL(k_packed_decode_lists, dim3(grid), dim3(64), 0, ctx->stream, p->d_words.p, p->d_offsets.p,
                        p->d_word_off.p, s_l.as<uint64_t>(), s_o.as<uint64_t>(), s_i.as<PackedItem>(), (uint64_t)items.size(),
                        (uint32_t)p->bits, d_out);
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // the staging vectors above are pageable host memory
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    VIDC_TRY(t.finish());  // (waits: the staging vectors above are pageable host memory)
     return VIDC_OK;
 }
 
@@ -1102,26 +1066,10 @@ int vidc_packed_get(vidc_ctx *ctx, const vidc_packed *p, uint64_t m, const uint6
     if (!ctx || !p || (m && (!list_nos || !offs || !ids_out))) return VIDC_ERR_INVALID;
     if (!m) return VIDC_OK;
     VIDC_TRY(packed_ensure_offsets(p));
-    for (uint64_t i = 0; i < m; i++) {
-        if (list_nos[i] >= p->nlist || offs[i] >= p->offsets[list_nos[i] + 1] - p->offsets[list_nos[i]]) {
-            set_error("packed get: (list %llu, offset %llu) out of range", (unsigned long long)list_nos[i],
-                      (unsigned long long)offs[i]);
-            return VIDC_ERR_INVALID;
-        }
-    }
-    VIDC_HIP(hipSetDevice(ctx->device));
-    Scratch s_l, s_o, s_r;
-    VIDC_TRY(s_l.get(ctx, m * 8)); VIDC_TRY(s_o.get(ctx, m * 8)); VIDC_TRY(s_r.get(ctx, m * 8));
-    VIDC_HIP(hipMemcpyAsync(s_l.p, list_nos, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    VIDC_HIP(hipMemcpyAsync(s_o.p, offs, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_packed_get, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, ctx->stream, p->d_words.p,
-                       p->d_word_off.p, (uint32_t)p->bits, m, s_l.as<uint64_t>(), s_o.as<uint64_t>(),
-                       s_r.as<int64_t>());
-    VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipMemcpyAsync(ids_out, s_r.p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    ctx->d2h_bytes += m * 8;
-    return VIDC_OK;
+    return get_request(ctx, "packed get", p->nlist, p->offsets, m, list_nos, offs, ids_out, [&](const uint64_t *d_l, const uint64_t *d_o, int64_t *d_r) {
+        hipLaunchKernelGGL(k_packed_get, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, ctx->stream, p->d_words.p, p->d_word_off.p,
+                           (uint32_t)p->bits, m, d_l, d_o, d_r);
+    });
 }
 
 int vidc_packed_translate_labels_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n, const int64_t *d_labels, int64_t *d_ids,

@@ -11,6 +11,7 @@
 
 #include "append.h"
 #include "common.h"
+#include "host_call.h"
 #include "roc_kernels.h"
 #include "roc_u.h"
 #include "roc_u2.h"
@@ -174,57 +175,21 @@ int download(vidc_ctx *ctx, std::vector<T> &dst, const T *d_src, size_t count) {
     return VIDC_OK;
 }
 
-// lazy host mirrors of the device-resident metadata (blocking copies; everything was synchronised when the
-// object was built)
-template <typename T>
-int mirror(std::vector<T> &dst, const T *d_src, size_t count) {
-    dst.resize(count);
-    if (count) VIDC_HIP(hipMemcpy(dst.data(), d_src, count * sizeof(T), hipMemcpyDeviceToHost));
-    return VIDC_OK;
-}
-int ensure_offsets_locked(const vidc_roc *r) {
-    if (r->offsets_host) return VIDC_OK;
-    VIDC_HIP(hipSetDevice(r->device));
-    VIDC_TRY(mirror(r->offsets, (const uint64_t *)r->d_offsets.p, r->nlist + 1));
-    r->offsets_host = true;
-    return VIDC_OK;
-}
-int ensure_offsets(const vidc_roc *r) {
-    std::lock_guard<std::mutex> g(r->mu);
-    return ensure_offsets_locked(r);
-}
+int ensure_offsets_locked(const vidc_roc *r) { return ensure_offsets_host_locked(r, r->d_offsets.p); }
+int ensure_offsets(const vidc_roc *r) { return ensure_offsets_host(r, r->d_offsets.p); }
 int ensure_meta(const vidc_roc *r) {
     std::lock_guard<std::mutex> g(r->mu);
     VIDC_TRY(ensure_offsets_locked(r));
     if (r->meta_host) return VIDC_OK;
     VIDC_HIP(hipSetDevice(r->device));
-    VIDC_TRY(mirror(r->prec, (const uint32_t *)r->d_prec.p, r->nlist));
-    VIDC_TRY(mirror(r->nwords, (const uint32_t *)r->d_nwords.p, r->nlist));
-    VIDC_TRY(mirror(r->draws, (const uint32_t *)r->d_draws.p, r->nlist));
-    VIDC_TRY(mirror(r->heads, (const uint64_t *)r->d_heads.p, r->nlist));
-    VIDC_TRY(mirror(r->word_off, (const uint64_t *)r->d_word_off.p, r->nlist + 1));
+    VIDC_TRY(mirror_to_host(r->prec, (const uint32_t *)r->d_prec.p, r->nlist));
+    VIDC_TRY(mirror_to_host(r->nwords, (const uint32_t *)r->d_nwords.p, r->nlist));
+    VIDC_TRY(mirror_to_host(r->draws, (const uint32_t *)r->d_draws.p, r->nlist));
+    VIDC_TRY(mirror_to_host(r->heads, (const uint64_t *)r->d_heads.p, r->nlist));
+    VIDC_TRY(mirror_to_host(r->word_off, (const uint64_t *)r->d_word_off.p, r->nlist + 1));
     r->meta_host = true;
     return VIDC_OK;
 }
-
-struct EventTimer {
-    vidc_ctx *c;
-    explicit EventTimer(vidc_ctx *ctx) : c(ctx) { (void)hipEventRecord(c->ev0, c->stream); }
-    double stop() {
-        (void)hipEventRecord(c->ev1, c->stream);
-        (void)vidc::vidc_event_wait(c->ev1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        return ms;
-    }
-    // the same in two halves, for a caller that synchronises the stream anyway (one host wait instead of two)
-    void mark() { (void)hipEventRecord(c->ev1, c->stream); }
-    double elapsed() {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-        return ms;
-    }
-};
 
 int check_status(const std::vector<uint32_t> &status, const char *what) {
     for (size_t l = 0; l < status.size(); l++) {
@@ -405,7 +370,7 @@ int finish_complete(vidc_ctx *ctx, vidc_roc *r, EncodeTail &e, const uint32_t *d
     r->compressed_bytes = 8ull * nonempty_lists + 4ull * r->total_words;
     VIDC_TRY(r->d_words.alloc(r->total_words + 16, ctx->dpool));  // + padding: the look-ahead of the lane / row decoders reads up to 15 words past the last stream
     if (nlist) {
-        EventTimer tm(ctx);
+        EventTimer tm = EventTimer::started(ctx);
         const uint64_t *d_off = r->rows ? (const uint64_t *)nullptr : (const uint64_t *)r->d_offsets.p;
         if (r->rows) {  // 64 rows per wavefront; word offsets and CSR offsets are scanned on the way
             const uint32_t nt = rows_tiles(nlist);
@@ -540,12 +505,9 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
     bool wl_sorted[10] = {};  // work-list classes found longest-first while they were filled
     Pinned h_wl, h_pre, h_off, h_plan;
     bool plan_on_device = false;
-    struct SyncOnExit {  // an early return while the offsets upload / the deferred prepass copy is in flight must not release their staging blocks
-                        // (declared behind them: destroyed first)
-        vidc_ctx *c;
-        bool armed = false;
-        ~SyncOnExit() { if (armed) (void)vidc::vidc_stream_wait(c->stream); }
-    } pre_guard{ctx};
+    // an early return while the offsets upload / the deferred prepass copy is in flight must not release their staging blocks
+    // (declared behind them: destroyed first; armed where such a copy is enqueued)
+    StreamGuard pre_guard(ctx, false);
     // (graph rows: slots of whole 64-byte sectors -- a row's ~100 bytes of stream then lie in two sectors, not in two and a half)
     const uint32_t arena_stride = rows ? (uint32_t)((arena_words_for(K) + 15u) & ~15ull) : 0u;
     uint64_t arena_words = 0, nonempty = 0, ntiny = 0;
@@ -679,7 +641,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
         if (offsets_copy.joinable()) offsets_copy.join();
         tr.mark("offsets: blocks");
         VIDC_HIP(hipMemcpyAsync(r->d_offsets.p, h_off.p, (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        pre_guard.armed = true;
+        pre_guard.arm();
         tr.mark("offsets: upload call");
         // The bitmap kernels own a whole CU's LDS (2^20-bit universe): latency-optimal for long lists, but only
         // num_cu lists in flight.  With many lists, short ones go to the high-occupancy kernels.
@@ -695,7 +657,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
             VIDC_TRY(s_maxid.get(ctx, nlist * 4));
             VIDC_TRY(s_flags.get(ctx, nlist * 4));
             VIDC_TRY(h_pre.get(ctx, nlist * 8));
-            EventTimer t(ctx);
+            EventTimer t = EventTimer::started(ctx);
             // Every kernel that takes a list streams it anyway and checks what the full prepass would (ids inside
             // [0, 2^31), ascending order where it matters, ids that fit the precision; the lane-per-list encoders since
             // round 3: each sampled id against its left neighbour): the prepass only looks at the LAST id of each list -- the maximum of an ascending
@@ -716,7 +678,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
                 VIDC_HIP(hipEventRecord(ctx->ev_pre[1], ctx->stream));
                 VIDC_HIP(hipMemcpyAsync(h_pre.p, s_maxid.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
                 VIDC_HIP(hipEventRecord(ctx->ev_pre[2], ctx->stream));
-                pre_guard.armed = true;
+                pre_guard.arm();
                 r->prec = vec_pool<uint32_t>().take(nlist);
                 r->prec.resize(nlist);
                 tr.mark("prepass kernel (read back later)");
@@ -730,11 +692,11 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
                                        dim3(256), 0, ctx->stream, d_ids, r->d_offsets.p, (uint32_t)nlist, precision_mode,
                                        s_maxid.as<uint32_t>(), s_flags.as<uint32_t>(), r->d_prec.p);
                 VIDC_HIP(hipGetLastError());
-                t.mark();
+                (void)t.mark();
                 VIDC_HIP(hipMemcpyAsync(h_pre.p, s_maxid.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
                 VIDC_HIP(hipMemcpyAsync(h_pre.as<uint32_t>() + nlist, s_flags.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
                 VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-                pre_guard.armed = false;
+                pre_guard.disarm();
                 kernel_ms += t.elapsed();
                 maxid = h_pre.as<uint32_t>();
                 pflags = maxid + nlist;
@@ -1000,7 +962,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
         return launch_gen_on(ctx->stream, wl, nwork, rl_max);
     };
     {
-        EventTimer t(ctx);
+        EventTimer t = EventTimer::started(ctx);
         VIDC_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
         // an auxiliary stream joins the call at its first launch (and only those are joined at the end: a small call that uses
         // one of them does not pay event traffic for seven)
@@ -1311,7 +1273,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
         // the kernels are in flight and the host has nothing to do until they finish: plan the decode of the whole
         // object now (7 ms per million lists that decode_all would otherwise spend on its critical path)
         // (the end event is recorded first: the planning is host time, not part of the kernels' duration)
-        t.mark();
+        (void)t.mark();
         VIDC_TRY(finish_enqueue(ctx, r.get(), tail, s_status, s_sizes.as<uint32_t>()));
         if (pre_deferred) {  // the maxima of the lists: precisions and bucket geometry for the decode planner
             VIDC_HIP(vidc::vidc_event_wait(ctx->ev_pre[2]));
@@ -1356,7 +1318,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
         }
         // ONE wait for the kernels, the status summary and the sizes (queued behind the kernels above)
         VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        pre_guard.armed = false;
+        pre_guard.disarm();
         kernel_ms += t.elapsed();
         if (ctx->chain_info[0][3]) {  // (the main stream joined the auxiliary ones)
             float cms = 0;
@@ -1399,7 +1361,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
             a.sid = s_sid.as<uint32_t>();
             a.skey = s_skey.as<uint64_t>(); a.skey_off = s_skey_off.as<uint64_t>(); a.spos = s_spos.as<uint32_t>();
             uint32_t rl_max = maxn <= 4096 ? 1 : (maxn <= 32768 ? 8 : (maxn <= 65536 ? 16 : 64));
-            EventTimer t2(ctx);
+            EventTimer t2 = EventTimer::started(ctx);
             VIDC_TRY(launch_gen(s_pend.as<uint32_t>(), (uint32_t)pend.size(), rl_max));
             kernel_ms += t2.stop();
             VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // scratch of this scope is released below
@@ -1448,7 +1410,7 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
             Scratch s_ul;
             VIDC_TRY(upload_scratch(ctx, s_ul, items));
             const uint32_t nitems = (uint32_t)(depth * 8);
-            EventTimer t(ctx);
+            EventTimer t = EventTimer::started(ctx);
             hipLaunchKernelGGL(k_perm_from_order, dim3(nitems), dim3(256), 0, ctx->stream, d_ids, r->d_offsets.p, s_ul.as<uint2>(),
                                nitems, r->d_perm.p);
             VIDC_HIP(hipGetLastError());
@@ -1854,7 +1816,7 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
         size_t acc = 0;
         for (int c = 0; c < DC_COUNT; c++) { base[c] = acc; acc += p.count[c]; }
     }
-    EventTimer t(ctx);
+    EventTimer t = EventTimer::started(ctx);
     if (p.order_build) {  // rows by edge count, most edges first: histogram per workgroup, segment starts, scatter
         uint32_t *part = const_cast<uint32_t *>(p.order_dev) + nwork;
         hipLaunchKernelGGL(k_rows_order_hist, dim3(VIDC_ORDER_BLOCKS), dim3(256), 0, ctx->stream, r->d_offsets.p, (uint32_t)nwork, part);
@@ -2142,7 +2104,7 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
     }
     // the end event of the kernels, then the 32-byte status summary (instead of copying two nlist-sized arrays back) behind them:
     // ONE wait for both
-    t.mark();
+    (void)t.mark();
     Pinned h_sum;
     constexpr uint32_t RETRY_SLOTS = 504;  // list numbers of handed-back lists behind the eight summary words
     VIDC_TRY(h_sum.get(ctx, (8 + RETRY_SLOTS) * 8));
@@ -2798,7 +2760,7 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
     VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
     VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
     VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, b.new_off, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    EventTimer tm(ctx);
+    EventTimer tm = EventTimer::started(ctx);
     Scratch s_t1;
     if (nlist) {
         const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};

@@ -26,6 +26,7 @@
 #include "bits.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "host_call.h"
 #include "requests.h"
 #include "scan.h"
 
@@ -1156,7 +1157,8 @@ static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets,
     if (!part2) VIDC_HIP(hipMemsetAsync(s_a.p, 0xff, (nt ? nt : 1) * 4, ctx->stream));
     const uint32_t grid = (uint32_t)std::min<uint64_t>((nt + 255) / 256 + 1, (uint64_t)ctx->num_cu * 32);
     if (part2) VIDC_TRY(s_part.get(ctx, ((size_t)VIDC_WTP_NBLK * VIDC_WTP_MAXB + 2 * VIDC_WTP_MAXB + 8) * 4));
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     if (part2) {
         uint32_t *part = s_part.as<uint32_t>(), *tot = part + (size_t)VIDC_WTP_NBLK * VIDC_WTP_MAXB, *bstart = tot + VIDC_WTP_MAXB;
         uint32_t *pairs = s_b.as<uint32_t>();  // (the second symbol array is free until the first level has run)
@@ -1244,25 +1246,12 @@ static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets,
         for (uint32_t level = 0; level < L; level++) off_bits += lvl_bits[level];
         w->size_bytes = (off_bits + 7) / 8 + (uint64_t)L * ((6 * nblk + 7) / 8) + (uint64_t)L * (nsamp + 1) * 8 + (nlist + 1) * 8;
     }
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    VIDC_TRY(t.finish());
     *out = w.release();
     return VIDC_OK;
 }
 
-static int wt_ensure_offsets(const vidc_wt *w) {
-    std::lock_guard<std::mutex> g(w->mu);
-    if (w->offsets_host) return VIDC_OK;
-    VIDC_HIP(hipSetDevice(w->device));
-    std::vector<uint64_t> h(w->nlist + 1);
-    VIDC_HIP(hipMemcpy(h.data(), w->d_C.p, (w->nlist + 1) * 8, hipMemcpyDeviceToHost));
-    w->offsets = std::move(h);
-    w->offsets_host = true;
-    return VIDC_OK;
-}
+static int wt_ensure_offsets(const vidc_wt *w) { return ensure_offsets_host(w, w->d_C.p); }
 
 extern "C" {
 
@@ -1296,29 +1285,15 @@ int vidc_wt_select(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *
     if (!ctx || !w || (m && (!list_nos || !offs || !ids_out))) return VIDC_ERR_INVALID;
     if (!m) return VIDC_OK;
     VIDC_TRY(wt_ensure_offsets(w));
-    for (uint64_t i = 0; i < m; i++)
-        if (list_nos[i] >= w->nlist || offs[i] >= w->offsets[list_nos[i] + 1] - w->offsets[list_nos[i]]) {
-            set_error("wt select: (list %llu, offset %llu) out of range", (unsigned long long)list_nos[i],
-                      (unsigned long long)offs[i]);
-            return VIDC_ERR_INVALID;
-        }
-    VIDC_HIP(hipSetDevice(ctx->device));
-    Scratch s_l, s_o, s_r;
-    VIDC_TRY(s_l.get(ctx, m * 8)); VIDC_TRY(s_o.get(ctx, m * 8)); VIDC_TRY(s_r.get(ctx, m * 8));
-    VIDC_HIP(hipMemcpyAsync(s_l.p, list_nos, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    VIDC_HIP(hipMemcpyAsync(s_o.p, offs, m * 8, hipMemcpyHostToDevice, ctx->stream));
-    const dim3 sgrid((uint32_t)std::min<uint64_t>((m + 127) / 128, 1u << 16));
-    if (w->wt_type == 1)
-        hipLaunchKernelGGL(k_wt_select<WtRrrView>, sgrid, dim3(128), 0, ctx->stream, rrr_view(w), w->d_C.p, w->d_nrank.p, (uint32_t)w->nlist,
-                           w->L, m, s_l.as<uint64_t>(), s_o.as<uint64_t>(), s_r.as<int64_t>());
-    else
-        hipLaunchKernelGGL(k_wt_select<WtPlainView>, sgrid, dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p,
-                           (uint32_t)w->nlist, w->L, m, s_l.as<uint64_t>(), s_o.as<uint64_t>(), s_r.as<int64_t>());
-    VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipMemcpyAsync(ids_out, s_r.p, m * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    ctx->d2h_bytes += m * 8;
-    return VIDC_OK;
+    return get_request(ctx, "wt select", w->nlist, w->offsets, m, list_nos, offs, ids_out, [&](const uint64_t *d_l, const uint64_t *d_o, int64_t *d_r) {
+        const dim3 sgrid((uint32_t)std::min<uint64_t>((m + 127) / 128, 1u << 16));
+        if (w->wt_type == 1)
+            hipLaunchKernelGGL(k_wt_select<WtRrrView>, sgrid, dim3(128), 0, ctx->stream, rrr_view(w), w->d_C.p, w->d_nrank.p, (uint32_t)w->nlist,
+                               w->L, m, d_l, d_o, d_r);
+        else
+            hipLaunchKernelGGL(k_wt_select<WtPlainView>, sgrid, dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p,
+                               (uint32_t)w->nlist, w->L, m, d_l, d_o, d_r);
+    });
 }
 
 int vidc_wt_translate_labels_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
@@ -1355,11 +1330,7 @@ int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint
                          uint64_t *out_offsets) {
     if (!ctx || !w || (m && !list_nos) || !out_offsets) return VIDC_ERR_INVALID;
     VIDC_TRY(wt_ensure_offsets(w));
-    out_offsets[0] = 0;
-    for (uint64_t i = 0; i < m; i++) {
-        if (list_nos[i] >= w->nlist) { set_error("list number out of range"); return VIDC_ERR_INVALID; }
-        out_offsets[i + 1] = out_offsets[i] + (w->offsets[list_nos[i] + 1] - w->offsets[list_nos[i]]);
-    }
+    VIDC_TRY(lists_request_offsets(w->nlist, w->offsets, m, list_nos, out_offsets));
     const uint64_t total = out_offsets[m];
     ctx->last_kernel_ms = 0;
     if (!total) return VIDC_OK;
@@ -1369,7 +1340,8 @@ int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint
     VIDC_TRY(s_l.get(ctx, m * 8)); VIDC_TRY(s_o.get(ctx, (m + 1) * 8));
     VIDC_HIP(hipMemcpyAsync(s_l.p, list_nos, m * 8, hipMemcpyHostToDevice, ctx->stream));
     VIDC_HIP(hipMemcpyAsync(s_o.p, out_offsets, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     const dim3 dgrid((uint32_t)std::min<uint64_t>((total + 127) / 128, 1u << 16));
     if (w->wt_type == 1)
         hipLaunchKernelGGL(k_wt_decode_lists<WtRrrView>, dgrid, dim3(128), 0, ctx->stream, rrr_view(w), w->d_C.p, w->d_nrank.p, (uint32_t)w->nlist, w->L, m,
@@ -1378,11 +1350,7 @@ int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint
         hipLaunchKernelGGL(k_wt_decode_lists<WtPlainView>, dgrid, dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p, (uint32_t)w->nlist, w->L, m,
                            s_l.as<uint64_t>(), s_o.as<uint64_t>(), total, d_out);
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    VIDC_TRY(t.finish());
     return VIDC_OK;
 }
 
@@ -1399,7 +1367,10 @@ int vidc_wt_decode_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *d_out) {
     if (!ctx || !w || (w->ntotal && !d_out)) return VIDC_ERR_INVALID;
     if (!w->ntotal) return VIDC_OK;
     VIDC_HIP(hipSetDevice(ctx->device));
-    VIDC_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    Scratch s_a, s_b;        // ping-pong (id, symbol prefix) arrays
+    Scratch s_bits, s_rank;  // wt_type 1: one level as plain bits + rank directory
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
     const uint32_t grid = (uint32_t)std::min<uint64_t>((w->ntotal + 255) / 256, (uint64_t)ctx->num_cu * 32);
     if (w->L == 0) {  // one list: ids 0..ntotal-1 in order (the per-id kernel handles it)
         if (w->wt_type == 1)
@@ -1409,8 +1380,6 @@ int vidc_wt_decode_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *d_out) {
             hipLaunchKernelGGL(k_wt_decode_all<WtPlainView>, dim3(grid), dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p,
                                (uint32_t)w->nlist, w->L, w->ntotal, d_out);
     } else {
-        Scratch s_a, s_b;  // ping-pong (id, symbol prefix) arrays
-        Scratch s_bits, s_rank;  // wt_type 1: one level as plain bits + rank directory
         if (w->wt_type == 1) {
             VIDC_TRY(s_bits.get(ctx, w->words_per_level * 8));
             VIDC_TRY(s_rank.get(ctx, (w->blocks_per_level + 1) * 4));
@@ -1445,20 +1414,9 @@ int vidc_wt_decode_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *d_out) {
             (void)nr;
             in = out;
         }
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // the scratch of this scope goes back to the pool below
-        float ms2 = 0;
-        (void)hipEventElapsedTime(&ms2, ctx->ev0, ctx->ev1);
-        ctx->last_kernel_ms = ms2;
-        return VIDC_OK;
     }
     VIDC_HIP(hipGetLastError());
-    VIDC_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->last_kernel_ms = ms;
+    VIDC_TRY(t.finish());  // (waits: the scratch of the levels goes back to the pool when the call returns)
     return VIDC_OK;
 }
 
