@@ -8,6 +8,8 @@ not installed.
 import numpy as np
 import pytest
 
+from wt_ref import rrr_size as _rrr_wt_size
+
 pytestmark = pytest.mark.gpu
 
 
@@ -209,31 +211,6 @@ def test_wavelet_tree_built_through_the_partitioned_scatter(nlist, ntotal, monke
             bad[a], bad[a + 1] = ids[a + 1], ids[a]
         with pytest.raises(VidcError):
             WaveletTreeLists.build(off, bad)
-
-
-def _rrr_wt_size(list_nos, nlist):
-    """Bytes of a levelwise wavelet tree whose levels are RRR coded with 63-bit blocks and one sample per 32 blocks:
-    6-bit class + ceil(log2 C(63, class)) offset bits per block, (32-bit stream pointer + 32-bit rank) per sample
-    (+ the final one), plus the table of symbol start positions (csrc/wt.hip)."""
-    import math
-
-    nt = list_nos.size
-    L = max(1, int(nlist - 1).bit_length())
-    ow = [0 if c in (0, 63) else math.ceil(math.log2(math.comb(63, c))) for c in range(64)]
-    nblk = (nt + 62) // 63
-    nsamp = (nblk + 31) // 32
-    order = np.arange(nt)
-    off_bits = 0
-    syms = list_nos.astype(np.int64)
-    for level in range(L):
-        bits = (syms[order] >> (L - 1 - level)) & 1
-        padded = np.zeros(nblk * 63, dtype=np.int64)
-        padded[:nt] = bits
-        cls = padded.reshape(nblk, 63).sum(1)
-        off_bits += int(sum(ow[int(c)] for c in cls))
-        # next level: stable sort by the top (level + 1) bits of the symbol
-        order = order[np.argsort(syms[order] >> (L - 1 - level), kind="stable")]
-    return (off_bits + 7) // 8 + L * ((6 * nblk + 7) // 8) + L * (nsamp + 1) * 8 + (nlist + 1) * 8
 
 
 def _random_graph(rng, N, K):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Differential fuzz of the wavelet-tree build (dev tool, run through gpurun): random list counts (1 .. 2^17), id counts on both sides of
+"""Differential fuzz of the wavelet-tree build (dev tool): random list counts (1 .. 2^17), id counts on both sides of
 the 2^18 from which list_nos[id] is built by the partitioned scatter, list-length distributions (equal, geometric, one huge list, thousands
-of empty lists), both level codings.  The tree built through the partitioned scatter and the one built through the direct scatter
+of empty lists) and id layouts (random positions; runs = ids laid out list after list; everything in one list), both level codings.
+The tree built through the partitioned scatter and the one built through the direct scatter
 (VIDC_WT_SCATTER=1) must decode to the same ids, answer the same selects and have the same size; decode_all must give back the input;
 a sample of selects is checked against the definition (the id at that offset of that list).
 usage: fuzz_wt.py seed seconds"""
@@ -25,13 +26,17 @@ def main():
     while time.time() - t0 < budget:
         ntotal = int(rng.choice([int(rng.integers(1, 5000)), int(rng.integers(200_000, 300_000)), int(rng.integers(1 << 18, 1 << 21))]))
         nlist = int(rng.choice([1, 2, int(rng.integers(1, 300)), int(rng.integers(300, 5000)), int(rng.integers(5000, 1 << 17))]))
-        shape = rng.choice(["uniform", "geometric", "huge", "empties"])
+        shape = rng.choice(["uniform", "geometric", "huge", "empties", "runs", "one_list"])
         if shape == "uniform":
             assign = rng.integers(0, nlist, ntotal)
         elif shape == "geometric":
             assign = np.minimum(rng.geometric(min(0.5, 8.0 / nlist), ntotal) - 1, nlist - 1)
         elif shape == "huge":
             assign = np.where(rng.random(ntotal) < 0.7, int(rng.integers(0, nlist)), rng.integers(0, nlist, ntotal))
+        elif shape == "runs":  # ids laid out list after list: long constant stretches on every level (RRR classes 0 / 63, equal samples)
+            assign = np.sort(np.where(rng.random(ntotal) < 0.5, rng.integers(0, nlist, ntotal), int(rng.integers(0, nlist))))
+        elif shape == "one_list":  # every level constant
+            assign = np.full(ntotal, int(rng.integers(0, nlist)))
         else:  # most lists empty
             used = rng.choice(nlist, size=max(1, nlist // 50), replace=False)
             assign = used[rng.integers(0, used.size, ntotal)]
