@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Differential fuzz of the Elias-Fano and packed-bits kernels against the CPU oracle (dev tool, run through gpurun):
 random batches (empty / tiny / long lists, universes 2^3..2^40, duplicates, unsorted lists, graph rows of every
-width) -- stream words, geometry, sizes, bulk decode, random access."""
+width -- uniform ones and the named families of tests/rows_ref.py, through the Elias-Fano and the compact-bit graph codecs) --
+stream words, byte images, geometry, sizes, bulk decode, random access."""
 import os
 import sys
 import time
@@ -10,7 +11,10 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle.pyoracle import Oracle  # noqa: E402  (dev tool: the checker)
-from vector_db_id_compression_amd.codecs import EfLists, PackedLists  # noqa: E402
+from vector_db_id_compression_amd.codecs import CompactRows, EfLists, PackedLists  # noqa: E402
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import rows_ref as rr  # noqa: E402  (the numpy model of the graph-row containers and its row families)
 
 
 def main():
@@ -78,28 +82,49 @@ def main():
         for l in rng.choice(nlist, size=min(3, nlist), replace=False):
             assert np.array_equal(pk.export_bytes(int(l)), orc.packed_encode(lists[int(l)][:400], bits)
                                   if lists[int(l)].size <= 400 else pk.export_bytes(int(l))), (seed, nb, l)
-        # ---- graph rows through the Elias-Fano graph codec
+        # ---- graph rows through the Elias-Fano and the compact-bit graph codecs: every other batch from a named family of
+        # tests/rows_ref.py (records on their bounds, every sentinel position, ...), words and byte images against its model
         K = int(rng.integers(1, 65))
         N = int(rng.integers(1, 300))
-        rows = np.full((N, K), -1, dtype=np.int32)
-        for i in range(N):
-            d = int(rng.integers(0, K + 1))
-            rows[i, :d] = rng.choice(max(N, K) * 4, size=d, replace=False)
+        fam = None
+        if nb % 2:
+            fam = rr.FAMILIES[int(rng.integers(0, len(rr.FAMILIES)))]
+            rows = rr.family(fam, N, K, seed=int(rng.integers(0, 1 << 30)))
+        else:
+            rows = np.full((N, K), -1, dtype=np.int32)
+            for i in range(N):
+                d = int(rng.integers(0, K + 1))
+                rows[i, :d] = rng.choice(max(N, K) * 4, size=d, replace=False)
+        m = rr.ef_rows(rows)
+        want, deg = rr.expected_ef(rows)
         g = EfLists.encode_rows(rows)
         got, cnt = g.decode_rows(None, K)
-        got = got.cpu().numpy()
-        big = np.iinfo(np.int32).max
-        assert np.array_equal(cnt, (rows >= 0).sum(1)), (seed, nb)
-        assert np.array_equal(np.where(got >= 0, got, big), np.sort(np.where(rows >= 0, rows, big), axis=1)), (seed, nb)
+        assert np.array_equal(cnt, deg) and np.array_equal(got.cpu().numpy(), want), (seed, nb, fam, N, K)
+        info = g.info()
+        assert np.array_equal(info["low_bits"], m.l) and np.array_equal(info["universe"], m.u.astype(np.uint64)), (seed, nb, fam, N, K)
+        assert g.compressed_bytes == m.size_in_bytes, (seed, nb, fam, N, K)
+        for i in rng.choice(N, size=min(N, 24), replace=False):
+            low, high, lb, hb = g.export(int(i))
+            wl, wh = m.words(int(i))
+            assert (lb, hb) == (int(m.low_nbits[i]), int(m.high_nbits[i])), (seed, nb, fam, N, K, i)
+            assert np.array_equal(low, wl) and np.array_equal(high, wh), (seed, nb, fam, N, K, i)
         i = int(rng.integers(0, N))
-        d = int(cnt[i])
-        if d:
-            e = orc.ef_build(np.sort(rows[i, :d]).astype(np.uint64))
+        if deg[i]:
+            e = orc.ef_build(np.sort(rows[i, : deg[i]]).astype(np.uint64))
             low, high, lb, hb = g.export(i)
             assert np.array_equal(low, e["low"]) and np.array_equal(high, e["high"]), (seed, nb, i)
+        crows = np.where(rows >= N, rows % N, rows).astype(np.int32)  # compact bits stores ids below N (repeats are fine for it)
+        img = rr.compact_rows(crows)
+        wantc, _ = rr.expected_compact(crows)
+        c = CompactRows.encode_rows(crows)
+        assert (c.bits, c.stride, c.size_in_bytes) == (rr.compact_bits(N), rr.compact_stride(N, K), N * rr.compact_stride(N, K))
+        got, cnt = c.decode_rows(None)
+        assert np.array_equal(cnt, deg) and np.array_equal(got.cpu().numpy(), wantc), (seed, nb, fam, N, K)
+        for i in rng.choice(N, size=min(N, 24), replace=False):
+            assert np.array_equal(c.export_row(int(i)), img[i]), (seed, nb, fam, N, K, i)
         nb += 1
         nl += nlist + N
-    print(f"fuzz ok: seed {seed}, {nb} batches, {nl} lists/rows: Elias-Fano and packed-bits streams identical to the oracle", flush=True)
+    print(f"fuzz ok: seed {seed}, {nb} batches, {nl} lists/rows: Elias-Fano, packed-bits and compact-row streams identical to the oracle and the row model", flush=True)
 
 
 if __name__ == "__main__":
