@@ -217,6 +217,15 @@ uint64_t vidc_compact_size_in_bytes(const vidc_compact *c);
 int vidc_compact_rows_decode(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const uint64_t *nodes, int32_t *d_out,
                              uint32_t *counts);
 int vidc_compact_export_row(vidc_ctx *ctx, const vidc_compact *c, uint64_t node, uint8_t *bytes, size_t cap);
+/* Flat image: the N * stride row bytes (row i at byte i * stride; field j of a row at bit j * bits, LSB first; the first -1 of a row
+ * is the sentinel N, fields behind it are zero as the encoder writes them and are never decoded).  bits and stride follow from
+ * (N, K) as in vidc_compact_rows_encode, with the same limits on K (VIDC_ERR_UNSUPPORTED); the import also returns
+ * VIDC_ERR_UNSUPPORTED for an N that needs more than 32 bits per field (N >= 2^32: rows are int32, and the check and the decoders
+ * read a field from two dwords); nbytes must equal N * stride.  The image is
+ * untrusted input: a kernel checks that in every row each field up to and including the first sentinel is <= N (a decoded id >= N
+ * would index past the caller's vectors), VIDC_ERR_INVALID otherwise, naming the first bad row.  All arrays are host memory. */
+int vidc_compact_export_all(vidc_ctx *ctx, const vidc_compact *c, uint8_t *bytes, size_t cap); /* N * stride bytes */
+int vidc_compact_import(vidc_ctx *ctx, uint64_t N, uint32_t K, const uint8_t *bytes, uint64_t nbytes, vidc_compact **out);
 
 /* -------------------------------------------------------------- Elias-Fano */
 /* Replaces CompressedIDInvertedListsEliasFano (custom_invlists_impl.cpp:229-339),
@@ -289,6 +298,35 @@ int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint
 /* decode of the touched lists + device-side pick of the n_items requested ids (see vidc_roc_decode_gather) */
 int vidc_wt_decode_gather(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
                           const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out);
+/* Flat image for saving / shipping a tree without rebuilding it.  All arrays are host memory.
+ * With L = vidc_wt_levels, nt = ntotal, W = ceil(nt / 64), nblk = ceil(nt / 63), nsamp = ceil(nblk / 32):
+ *   offsets[nlist + 1]: the object's own offsets (vidc_wt_offsets).
+ *   wt_type 0: bits = L * W words, level after level, without the object's internal pad word.  Bit i of level l is bit i & 63 of
+ *     word l * W + (i >> 6); bits at positions >= nt are zero; n_cls = n_offs = 0.
+ *   wt_type 1: n_bits = 0.  cls = L * 6 * nsamp 32-bit words, each level in whole samples: the class of block b of a level is the 6
+ *     bits at bit 6 b of that level's words, LSB first -- the popcount of bits [63 b, 63 b + 63) of the level; class fields of blocks
+ *     >= nblk are zero.  off_bits[l] = the sum over the level's blocks of ceil(log2 C(63, class)).  offs = the levels' offset streams
+ *     back to back, ceil(off_bits[l] / 64) words each, unused top bits zero, without the object's pad words; a block's offset is its
+ *     index among the 63-bit words with `class` ones in the combinatorial number system (the sum, over its ones in ascending order,
+ *     i = 1 .. class, of C(position_i, i)).
+ * The image does not carry the derived tables (they are not part of vidc_wt_size_in_bytes either): the 512-bit-block rank directory
+ * (type 0), the (pointer, rank) samples (type 1) and the per-node rank tables (both) are rebuilt on the device by vidc_wt_import.
+ * An image is untrusted input.  vidc_wt_import checks on the host: arguments and wt_type, 1 <= nlist < 2^32, offsets[0] == 0 and
+ * monotone offsets, ntotal < 2^32 (VIDC_ERR_UNSUPPORTED, as vidc_wt_build), n_bits / n_cls / n_offs against what the geometry and
+ * off_bits demand, zero pad bits / class fields / top bits; then on the device, before any position derived from the image is
+ * followed: the per-level totals of the offset widths against off_bits, every RRR block (offset < C(63, class), class <= the bits the
+ * block has, no one behind the level's end), and for every level l and node boundary p = 0 .. 2^l that the ones before position
+ * offsets[min(p << (L - l), nlist)] equal what the offsets alone demand -- equal boundary counts mean every select and decode walk
+ * finds the bit it looks for inside its node.  Any failure: VIDC_ERR_INVALID with a message naming the argument, or the first bad
+ * (level, node); *out == NULL and the context stays usable.  An imported object is a built one to every other entry point. */
+int vidc_wt_type(const vidc_wt *w); /* 0 / 1; -1 for NULL */
+/* words of the three image arrays (any pointer may be NULL) */
+int vidc_wt_image_words(const vidc_wt *w, uint64_t *n_bits, uint64_t *n_cls, uint64_t *n_offs);
+int vidc_wt_export_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *bits, size_t bits_cap, uint32_t *cls, size_t cls_cap,
+                       uint64_t *offs, size_t offs_cap, uint64_t *off_bits /* [levels], may be NULL for wt_type 0 */);
+int vidc_wt_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, int wt_type, const uint64_t *bits, uint64_t n_bits,
+                   const uint32_t *cls, uint64_t n_cls, const uint64_t *offs, uint64_t n_offs, const uint64_t *off_bits,
+                   vidc_wt **out);
 
 /* ------------------------------------------- device-resident requests (labels, graph nodes) */
 /* The decode section of a search that runs on the GPU: its labels (from a top-k) and its frontier (from an argmin) are device arrays
@@ -390,6 +428,9 @@ double vidc_ctx_last_kernel_ms(const vidc_ctx *ctx);
 #define VIDC_PHASE_ROC_DECODE 2  /* k_roc_decode_gen + k_roc_decode_tiny launches */
 #define VIDC_PHASE_ROC_ENCODE_CHAIN 3 /* the ONE launch holding the call's longest chains (k_roc_encode_u2<20/18>): its duration */
 #define VIDC_PHASE_ROC_DECODE_CHAIN 4 /* k_roc_decode_u2<20/18>, same */
+#define VIDC_PHASE_IMPORT_H2D 5 /* vidc_wt_import / vidc_compact_import: the host -> device copies of the image.  The kernels that rebuild
+                                 * and check are vidc_ctx_last_kernel_ms: for wt_type 1 the sum of the intervals in front of and behind the
+                                 * read-back of the levels' width totals, without the wait between them */
 #define VIDC_PHASE_COUNT 8
 double vidc_ctx_phase_ms(const vidc_ctx *ctx, int phase);
 /* What the chain launch of the last ROC encode (which = 0) / decode (1) on this context processed: ids, lists, longest list and

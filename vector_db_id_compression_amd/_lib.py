@@ -116,6 +116,8 @@ def _declare(lib):
     f("vidc_compact_size_in_bytes", _u64, _vp)
     f("vidc_compact_rows_decode", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
     f("vidc_compact_export_row", C.c_int, _vp, _vp, _u64, _vp, C.c_size_t)
+    f("vidc_compact_export_all", C.c_int, _vp, _vp, _vp, C.c_size_t)
+    f("vidc_compact_import", C.c_int, _vp, _u64, _u32, _vp, _u64, _P(_vp))
     # wavelet tree
     f("vidc_wt_build", C.c_int, _vp, _u64, _vp, _vp, C.c_int, _P(_vp))
     f("vidc_wt_build_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, C.c_int, _P(_vp))
@@ -127,6 +129,10 @@ def _declare(lib):
     f("vidc_wt_decode_all", C.c_int, _vp, _vp, _vp)
     f("vidc_wt_decode_lists", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
     f("vidc_wt_decode_gather", C.c_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_wt_type", C.c_int, _vp)
+    f("vidc_wt_image_words", C.c_int, _vp, _vp, _vp, _vp)
+    f("vidc_wt_export_all", C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp)
+    f("vidc_wt_import", C.c_int, _vp, _u64, _vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _P(_vp))
     # device-resident requests (labels, graph nodes)
     for codec in ("packed", "ef", "wt", "roc"):
         f(f"vidc_{codec}_translate_labels_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
@@ -162,6 +168,7 @@ EXPORTED_SYMBOLS = [
     "vidc_packed_translate_labels_dev", "vidc_ef_translate_labels_dev", "vidc_wt_translate_labels_dev", "vidc_roc_translate_labels_dev",
     "vidc_compact_rows_decode_dev", "vidc_ef_decode_rows_dev", "vidc_roc_decode_rows_dev",
     "vidc_packed_append_dev", "vidc_ef_append_dev", "vidc_wt_append_dev", "vidc_roc_append_dev",
+    "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
 ]
 
 

@@ -643,6 +643,35 @@ __global__ void __launch_bounds__(64) k_compact_rows_decode_wide(const uint8_t *
     }
 }
 
+// vidc_compact_import: in every row each field up to and including the first sentinel N must be <= N (fields behind the sentinel are
+// never decoded).  A wavefront per row, lane j reads fields j, j + 64, ...; a field (<= 32 bits) lies inside the two aligned dwords
+// around its first byte (the buffer ends with 8 padding bytes).  err: the smallest bad row (~0: none).
+__global__ void __launch_bounds__(256) k_compact_check_rows(const uint8_t *__restrict__ data, uint64_t N, uint32_t K, uint32_t bits, uint32_t stride,
+                                                            unsigned long long *err) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t mask = (1ull << bits) - 1ull;
+    const uint64_t waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t row = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); row < N; row += waves) {
+        bool bad = false;
+        for (uint32_t j0 = 0; j0 < K; j0 += 64u) {
+            const uint32_t j = j0 + lane;
+            uint64_t v = 0;
+            if (j < K) {
+                const uint64_t pos = (uint64_t)j * bits;
+                const uintptr_t a = (uintptr_t)(data + row * stride + (pos >> 3));
+                const uint32_t *w = (const uint32_t *)(a & ~(uintptr_t)3);
+                const uint32_t sh = (uint32_t)(a & 3u) * 8u + (uint32_t)(pos & 7u);
+                v = ((((uint64_t)w[1] << 32) | w[0]) >> sh) & mask;
+            }
+            const uint64_t sent = __ballot(j < K && v == N), big = __ballot(j < K && v > N);
+            const uint64_t upto = sent ? (sent & (0 - sent)) - 1ull : ~0ull;  // the lanes in front of the first sentinel
+            bad |= (big & upto) != 0;
+            if (sent) break;
+        }
+        if (bad && lane == 0) atomicMin(err, (unsigned long long)row);
+    }
+}
+
 }  // namespace
 
 struct vidc_compact {
@@ -780,6 +809,71 @@ int vidc_compact_rows_decode_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t 
 int vidc_compact_export_row(vidc_ctx *ctx, const vidc_compact *c, uint64_t node, uint8_t *bytes, size_t cap) {
     if (!ctx || !c || node >= c->N || cap < c->stride) return VIDC_ERR_INVALID;
     return vidc_copy_d2h(ctx, bytes, c->d_data.p + node * c->stride, c->stride);
+}
+
+// Flat image (include/vidc.h): the N * stride row bytes.
+int vidc_compact_export_all(vidc_ctx *ctx, const vidc_compact *c, uint8_t *bytes, size_t cap) {
+    if (!ctx || !c) { set_error("compact export_all: NULL context or object"); return VIDC_ERR_INVALID; }
+    const uint64_t nb = c->N * c->stride;
+    if (nb > cap) { set_error("compact export_all: export buffer too small"); return VIDC_ERR_INVALID; }
+    if (nb && !bytes) { set_error("compact export_all: NULL array"); return VIDC_ERR_INVALID; }
+    if (!nb) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(c->device));
+    VIDC_HIP(hipMemcpyAsync(bytes, c->d_data.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    return VIDC_OK;
+}
+
+int vidc_compact_import(vidc_ctx *ctx, uint64_t N, uint32_t K, const uint8_t *bytes, uint64_t nbytes, vidc_compact **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) { set_error("compact import: NULL context or out"); return VIDC_ERR_INVALID; }
+    if (K == 0 || K > 4096) { set_error("compact import: K=%u unsupported (1..4096)", K); return VIDC_ERR_UNSUPPORTED; }
+    const uint32_t bits = (uint32_t)vidc_packed_bits_for(N);
+    if (bits > 32) { set_error("compact import: N needs %u bits per field (rows are int32)", bits); return VIDC_ERR_UNSUPPORTED; }
+    const uint32_t stride = (K * bits + 7) / 8;
+    if (nbytes != N * stride || (nbytes && !bytes)) {
+        set_error("compact import: nbytes = %llu, (N, K) needs %llu", (unsigned long long)nbytes, (unsigned long long)(N * stride));
+        return VIDC_ERR_INVALID;
+    }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<vidc_compact> c(new vidc_compact());
+    c->device = ctx->device;
+    c->N = N;
+    c->K = K;
+    c->bits = bits;
+    c->stride = stride;
+    VIDC_TRY(c->d_data.alloc(nbytes + 8, ctx->dpool));
+    Scratch s_err;
+    VIDC_TRY(s_err.get(ctx, 8));
+    StreamGuard guard(ctx);
+    VIDC_HIP(hipEventRecord(ctx->tev[0], ctx->stream));
+    if (nbytes) VIDC_HIP(hipMemcpyAsync(c->d_data.p, bytes, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    VIDC_HIP(hipMemsetAsync(c->d_data.p + nbytes, 0, 8, ctx->stream));  // (the pad the encoder leaves: the decoders read two dwords per field)
+    VIDC_HIP(hipEventRecord(ctx->tev[1], ctx->stream));
+    VIDC_HIP(hipMemsetAsync(s_err.p, 0xff, 8, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
+    if (N) {
+        hipLaunchKernelGGL(k_compact_check_rows, dim3((uint32_t)std::min<uint64_t>((N + 3) / 4, (uint64_t)ctx->num_cu * 64)), dim3(256), 0, ctx->stream,
+                           c->d_data.p, N, K, bits, stride, s_err.as<unsigned long long>());
+        VIDC_HIP(hipGetLastError());
+    }
+    VIDC_HIP(t.mark());
+    unsigned long long err = 0;
+    VIDC_HIP(hipMemcpyAsync(&err, s_err.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    guard.disarm();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    ctx->last_kernel_ms = t.elapsed();
+    {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ctx->tev[0], ctx->tev[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_IMPORT_H2D] = ms;
+    }
+    if (err != ~0ull) {
+        set_error("compact import: bytes: row %llu holds a field above N in front of its sentinel", err);
+        return VIDC_ERR_INVALID;
+    }
+    *out = c.release();
+    return VIDC_OK;
 }
 
 static int packed_ensure_offsets(const vidc_packed *p) { return ensure_offsets_host(p, p->d_offsets.p); }

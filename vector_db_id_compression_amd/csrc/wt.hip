@@ -49,6 +49,7 @@ struct vidc_wt {
     // wt_type 1: RRR-63 levels
     uint64_t rrr_nblk = 0, rrr_nsamp = 0, rrr_cls_wpl = 0;
     std::vector<uint64_t> rrr_off_base;  // [L + 1] first word of every level's offset stream
+    std::vector<uint64_t> rrr_off_bits;  // [L] bits of every level's offset stream (host only: the image's off_bits)
     DevBuf<uint32_t> d_cls;             // L * rrr_cls_wpl: packed 6-bit classes
     DevBuf<uint64_t> d_offs;            // offset streams, level after level
     DevBuf<uint32_t> d_ptr, d_rs;       // L * (rrr_nsamp + 1): bit position in the offset stream / ones before block 32 s
@@ -1045,6 +1046,100 @@ __global__ void __launch_bounds__(256) k_wt_decode_tile(const WtItem *__restrict
     }
 }
 
+// ---- import (vidc_wt_import): the derived tables rebuilt from an image, and the checks that make an untrusted image one the query
+// kernels walk in bounds.  Streaming passes over the level bits / the packed classes, one scan over the concatenated levels each
+// (scan.h), and two checks that report through one error word (the smallest key wins: block checks in front of node checks, then
+// level << 56 | index << 8 | kind).
+#define VIDC_WT_IMP_OFFSET 1u   // an RRR block's offset is >= C(63, class)
+#define VIDC_WT_IMP_CLASS 2u    // an RRR block's class exceeds the bits the block has
+#define VIDC_WT_IMP_STRAY 3u    // an RRR block has a one behind the end of the level
+#define VIDC_WT_IMP_NODE 4u     // ones before a node boundary differ from what the offsets demand
+__device__ __forceinline__ unsigned long long wt_imp_key(uint32_t level, uint64_t index, uint32_t kind) {
+    return ((unsigned long long)(kind == VIDC_WT_IMP_NODE) << 63) | ((unsigned long long)level << 56) | ((unsigned long long)index << 8) | kind;
+}
+// ones of every 512-bit block of every level (blockIdx.y): a thread per word -- coalesced --, eight neighbouring lanes add up.
+// wpl: words of a level as stored (with its pad word), bpl = ceil(wpl / 8)
+__global__ void __launch_bounds__(256) k_wt_imp_block_ones(const uint64_t *__restrict__ bits, uint64_t wpl, uint64_t bpl, uint32_t *__restrict__ ones) {
+    const uint64_t level = blockIdx.y, w = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint32_t c = w < wpl ? (uint32_t)__builtin_popcountll(bits[level * wpl + w]) : 0u;
+    c += (uint32_t)__shfl_xor((int)c, 1, 64);
+    c += (uint32_t)__shfl_xor((int)c, 2, 64);
+    c += (uint32_t)__shfl_xor((int)c, 4, 64);
+    if ((threadIdx.x & 7u) == 0u && (w >> 3) < bpl) ones[level * bpl + (w >> 3)] = c;
+}
+// sums of the classes and of their offset widths over every sample (32 blocks = six class words) of every level (blockIdx.y)
+__global__ void __launch_bounds__(256) k_wt_imp_sample_sums(const uint32_t *__restrict__ cls, uint64_t cls_wpl, uint64_t nsamp, const uint8_t *__restrict__ ow,
+                                                            uint32_t *__restrict__ csum, uint32_t *__restrict__ wsum) {
+    __shared__ uint8_t s_ow[64];
+    if (threadIdx.x < 64u) s_ow[threadIdx.x] = ow[threadIdx.x];
+    __syncthreads();
+    const uint64_t level = blockIdx.y, s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (s >= nsamp) return;
+    const uint2 *cw = (const uint2 *)(cls + level * cls_wpl + 6 * s);  // (cls_wpl is even and a sample is 24 bytes: 8-byte aligned)
+    const uint2 q0 = cw[0], q1 = cw[1], q2 = cw[2];
+    const uint32_t w[7] = {q0.x, q0.y, q1.x, q1.y, q2.x, q2.y, 0u};
+    uint32_t cs = 0, ws = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < RRR_K; k++) {
+        const uint32_t bit0 = 6u * k, wi = bit0 >> 5, sh = bit0 & 31u;
+        uint32_t c = w[wi] >> sh;
+        if (sh > 26u) c |= w[wi + 1] << (32u - sh);
+        c &= 63u;
+        cs += c;
+        ws += s_ow[c];
+    }
+    csum[level * nsamp + s] = cs;
+    wsum[level * nsamp + s] = ws;
+}
+// per-level exclusive prefixes out of ONE scan over the concatenated levels: out[level][j] = scan[level * per + j] - scan[level * per]
+// for j = 0 .. per; totals (may be NULL): the levels' sums
+__global__ void __launch_bounds__(256) k_wt_imp_level_prefix(const uint64_t *__restrict__ scan, uint64_t per, uint32_t *__restrict__ out,
+                                                             uint64_t *__restrict__ totals) {
+    const uint64_t level = blockIdx.y, base = scan[level * per];
+    for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j <= per; j += (uint64_t)gridDim.x * 256u) {
+        const uint64_t v = scan[level * per + j] - base;
+        out[level * (per + 1) + j] = (uint32_t)v;
+        if (totals && j == per) totals[level] = v;
+    }
+}
+// every RRR block of every level (blockIdx.y): offset < C(63, class), class <= the bits the block has, no one behind the level's end.
+// The samples and the per-level totals of the widths were checked against off_bits before: every offset field lies inside its stream.
+__global__ void __launch_bounds__(256) k_wt_imp_check_blocks(WtRrrView vw, unsigned long long *err) {
+    const uint32_t level = blockIdx.y;
+    const BvRrr bv = vw.level(level);
+    for (uint64_t b = (uint64_t)blockIdx.x * 256u + threadIdx.x; b < bv.nblk; b += (uint64_t)gridDim.x * 256u) {
+        const uint64_t s = b / RRR_K;
+        uint64_t bp = bv.ptr[s];
+        for (uint64_t k = s * RRR_K; k < b; k++) bp += bv.ow[bv.cls_at(k)];
+        const uint32_t c = bv.cls_at(b);
+        const uint64_t left = bv.nbits - b * RRR_B;
+        const uint32_t len = left < RRR_B ? (uint32_t)left : RRR_B;
+        uint32_t kind = 0;
+        if (c > len) kind = VIDC_WT_IMP_CLASS;
+        else {
+            const uint64_t o = bv.offset_at(bp, c);
+            if (o >= bv.binom[RRR_B * 64u + c]) kind = VIDC_WT_IMP_OFFSET;
+            else if (len < RRR_B && (rrr_unrank_word(c, o, bv.binom) >> len)) kind = VIDC_WT_IMP_STRAY;
+        }
+        if (kind) atomicMin(err, wt_imp_key(level, b, kind));
+    }
+}
+// every node boundary p = 0 .. 2^level of every level (blockIdx.y): the ones in front of position C[min(p << (L - level), nlist)], asked of
+// the imported structure, against the nrank entry computed from the offsets alone
+template <class View>
+__global__ void __launch_bounds__(256) k_wt_imp_check_nodes(View vw, const uint64_t *__restrict__ C, const uint32_t *__restrict__ nrank, uint32_t nlist,
+                                                            uint32_t L, unsigned long long *err) {
+    const uint32_t level = blockIdx.y, shn = L - level;
+    const uint64_t nodes = 1ull << level;
+    const auto bv = vw.level(level);
+    const uint32_t *want = nrank + wt_nrank_base(level);
+    for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p <= nodes; p += (uint64_t)gridDim.x * 256u) {
+        uint64_t sym = p << shn;
+        if (sym > nlist) sym = nlist;
+        if ((uint32_t)bv.rank_1(C[sym]) != want[p]) atomicMin(err, wt_imp_key(level, p, VIDC_WT_IMP_NODE));
+    }
+}
+
 WtPlainView plain_view(const vidc_wt *w) { return WtPlainView{w->d_bits.p, w->d_rank.p, w->words_per_level, w->blocks_per_level}; }
 RrrTab rrr_tab() {
     RrrTab t;
@@ -1069,6 +1164,20 @@ WtRrrView rrr_view(const vidc_wt *w) {
 }
 
 }  // namespace
+
+// the tables of an RRR-coded object (build and import): C(n, k) for n, k < 64 and, behind them, the 64 offset widths as bytes
+static int wt_rrr_tables(vidc_ctx *ctx, vidc_wt *w, const RrrTab &tab) {
+    std::vector<uint64_t> bn(64 * 64, 0);
+    for (int n = 0; n < 64; n++) {
+        bn[n * 64] = 1;
+        for (int k = 1; k <= n; k++) bn[n * 64 + k] = (n ? bn[(n - 1) * 64 + k - 1] : 0) + (k <= n - 1 ? bn[(n - 1) * 64 + k] : 0);
+    }
+    VIDC_TRY(w->d_binom.alloc(64 * 64 + 8));
+    VIDC_HIP(hipMemcpyAsync(w->d_binom.p, bn.data(), 64 * 64 * 8, hipMemcpyHostToDevice, ctx->stream));
+    VIDC_HIP(hipMemcpyAsync(w->d_binom.p + 64 * 64, tab.ow, 64, hipMemcpyHostToDevice, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (bn leaves scope)
+    return VIDC_OK;
+}
 
 // offsets: host array (vidc_wt_build), or NULL and d_offsets + ntotal (vidc_wt_build_dev: copied into d_C and validated by
 // k_offsets_ingest, whose summary is read at the build's wait for the verdict on the ids, before any level is built)
@@ -1134,15 +1243,7 @@ static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets,
         // worst case of a level's offset stream: 61 bits per block (transient; the object keeps the exact size)
         VIDC_TRY(s_offs_tmp.get(ctx, (size_t)L * (w->words_per_level + 1) * 8));
         VIDC_HIP(hipMemsetAsync(s_offs_tmp.p, 0, (size_t)L * (w->words_per_level + 1) * 8, ctx->stream));
-        std::vector<uint64_t> bn(64 * 64, 0);
-        for (int n = 0; n < 64; n++) {
-            bn[n * 64] = 1;
-            for (int k = 1; k <= n; k++) bn[n * 64 + k] = (n ? bn[(n - 1) * 64 + k - 1] : 0) + (k <= n - 1 ? bn[(n - 1) * 64 + k] : 0);
-        }
-        VIDC_TRY(w->d_binom.alloc(64 * 64 + 8));
-        VIDC_HIP(hipMemcpyAsync(w->d_binom.p, bn.data(), 64 * 64 * 8, hipMemcpyHostToDevice, ctx->stream));
-        VIDC_HIP(hipMemcpyAsync(w->d_binom.p + 64 * 64, tab.ow, 64, hipMemcpyHostToDevice, ctx->stream));
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (bn leaves scope)
+        VIDC_TRY(wt_rrr_tables(ctx, w.get(), tab));
         w->rrr_off_base.assign(L + 1, 0);
     }
     VIDC_TRY(w->d_nrank.alloc(wt_nrank_base(L) + 1));
@@ -1232,6 +1333,7 @@ static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets,
     }
     if (rrr) {  // the exact-size offset streams, level after level (+ one pad word each: two-word reads)
         for (uint32_t level = 0; level < L; level++) w->rrr_off_base[level + 1] = w->rrr_off_base[level] + (lvl_bits[level] + 63) / 64 + 1;
+        w->rrr_off_bits = lvl_bits;
         VIDC_TRY(w->d_offs.alloc(w->rrr_off_base[L] ? w->rrr_off_base[L] : 1));
         for (uint32_t level = 0; level < L && nt; level++)
             VIDC_HIP(hipMemcpyAsync(w->d_offs.p + w->rrr_off_base[level], s_offs_tmp.as<uint64_t>() + (size_t)level * (w->words_per_level + 1),
@@ -1417,6 +1519,277 @@ int vidc_wt_decode_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *d_out) {
     }
     VIDC_HIP(hipGetLastError());
     VIDC_TRY(t.finish());  // (waits: the scratch of the levels goes back to the pool when the call returns)
+    return VIDC_OK;
+}
+
+// ---- flat images (include/vidc.h): what is stored is the level bits, or the RRR classes and offset streams; the rank directory, the
+// samples and the node tables are rebuilt on import
+int vidc_wt_type(const vidc_wt *w) { return w ? w->wt_type : -1; }
+
+int vidc_wt_image_words(const vidc_wt *w, uint64_t *n_bits, uint64_t *n_cls, uint64_t *n_offs) {
+    if (!w) { set_error("wt image_words: NULL object"); return VIDC_ERR_INVALID; }
+    uint64_t nb = 0, nc = 0, no = 0;
+    if (w->wt_type == 0) nb = (uint64_t)w->L * ((w->ntotal + 63) / 64);
+    else {
+        nc = (uint64_t)w->L * 6 * w->rrr_nsamp;
+        for (uint32_t l = 0; l < w->L; l++) no += (w->rrr_off_bits[l] + 63) / 64;
+    }
+    if (n_bits) *n_bits = nb;
+    if (n_cls) *n_cls = nc;
+    if (n_offs) *n_offs = no;
+    return VIDC_OK;
+}
+
+int vidc_wt_export_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *bits, size_t bits_cap, uint32_t *cls, size_t cls_cap, uint64_t *offs,
+                       size_t offs_cap, uint64_t *off_bits) {
+    if (!ctx || !w) { set_error("wt export_all: NULL context or object"); return VIDC_ERR_INVALID; }
+    uint64_t nb = 0, nc = 0, no = 0;
+    VIDC_TRY(vidc_wt_image_words(w, &nb, &nc, &no));
+    if (nb > bits_cap || nc > cls_cap || no > offs_cap) { set_error("wt export_all: export buffer too small"); return VIDC_ERR_INVALID; }
+    if ((nb && !bits) || (nc && !cls) || (no && !offs) || (w->wt_type == 1 && !off_bits)) {
+        set_error("wt export_all: NULL array");
+        return VIDC_ERR_INVALID;
+    }
+    VIDC_HIP(hipSetDevice(w->device));
+    StreamGuard guard(ctx);
+    if (w->wt_type == 0) {
+        const uint64_t W = (w->ntotal + 63) / 64;
+        for (uint32_t l = 0; l < w->L && W; l++)  // (without the level's pad word)
+            VIDC_HIP(hipMemcpyAsync(bits + (uint64_t)l * W, w->d_bits.p + (uint64_t)l * w->words_per_level, W * 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        const uint64_t cw = 6 * w->rrr_nsamp;
+        uint64_t at = 0;
+        for (uint32_t l = 0; l < w->L; l++) {
+            off_bits[l] = w->rrr_off_bits[l];
+            if (cw) VIDC_HIP(hipMemcpyAsync(cls + (uint64_t)l * cw, w->d_cls.p + (uint64_t)l * w->rrr_cls_wpl, cw * 4, hipMemcpyDeviceToHost, ctx->stream));
+            const uint64_t ow = (w->rrr_off_bits[l] + 63) / 64;
+            if (ow) VIDC_HIP(hipMemcpyAsync(offs + at, w->d_offs.p + w->rrr_off_base[l], ow * 8, hipMemcpyDeviceToHost, ctx->stream));
+            at += ow;
+        }
+    }
+    guard.disarm();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    return VIDC_OK;
+}
+
+int vidc_wt_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, int wt_type, const uint64_t *bits, uint64_t n_bits,
+                   const uint32_t *cls, uint64_t n_cls, const uint64_t *offs, uint64_t n_offs, const uint64_t *off_bits, vidc_wt **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) { set_error("wt import: NULL context or out"); return VIDC_ERR_INVALID; }
+    // 1. host checks: the geometry, and the sizes it demands of the arrays
+    if (!offsets) { set_error("wt import: offsets is NULL"); return VIDC_ERR_INVALID; }
+    if (wt_type != 0 && wt_type != 1) { set_error("wt import: wt_type must be 0 or 1, not %d", wt_type); return VIDC_ERR_INVALID; }
+    if (nlist == 0 || nlist >= 0xffffffffull) { set_error("wt import: nlist must be 1 <= nlist < 2^32"); return VIDC_ERR_INVALID; }
+    if (offsets[0] != 0) { set_error("wt import: offsets[0] must be 0"); return VIDC_ERR_INVALID; }
+    for (uint64_t l = 0; l < nlist; l++)
+        if (offsets[l + 1] < offsets[l]) {
+            set_error("wt import: offsets decrease at list %llu", (unsigned long long)l);
+            return VIDC_ERR_INVALID;
+        }
+    const uint64_t nt = offsets[nlist];
+    if (nt >= 0xffffffffull) { set_error("wt import: offsets: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED; }
+    uint32_t L = 1;
+    while ((1ull << L) < nlist) L++;
+    const bool rrr = wt_type == 1;
+    if (rrr && L > 32) { set_error("wt import: more than 32 levels"); return VIDC_ERR_UNSUPPORTED; }
+    const uint64_t W = (nt + 63) / 64, nblk = (nt + RRR_B - 1) / RRR_B, nsamp = (nblk + RRR_K - 1) / RRR_K;
+    const RrrTab tab = rrr_tab();
+    if (!rrr) {
+        if (n_bits != (uint64_t)L * W || (n_bits && !bits)) {
+            set_error("wt import: n_bits = %llu, the offsets need %llu words", (unsigned long long)n_bits, (unsigned long long)((uint64_t)L * W));
+            return VIDC_ERR_INVALID;
+        }
+        if (n_cls || n_offs) { set_error("wt import: n_cls and n_offs must be 0 for wt_type 0"); return VIDC_ERR_INVALID; }
+        if (nt & 63u)
+            for (uint32_t l = 0; l < L; l++)
+                if (bits[(uint64_t)l * W + W - 1] >> (nt & 63u)) {
+                    set_error("wt import: bits: level %u has a bit set behind position ntotal", l);
+                    return VIDC_ERR_INVALID;
+                }
+    } else {
+        if (n_bits) { set_error("wt import: n_bits must be 0 for wt_type 1"); return VIDC_ERR_INVALID; }
+        if (n_cls != (uint64_t)L * 6 * nsamp || (n_cls && !cls)) {
+            set_error("wt import: n_cls = %llu, the offsets need %llu words", (unsigned long long)n_cls, (unsigned long long)((uint64_t)L * 6 * nsamp));
+            return VIDC_ERR_INVALID;
+        }
+        if (!off_bits) { set_error("wt import: off_bits is NULL"); return VIDC_ERR_INVALID; }
+        uint64_t need = 0;
+        for (uint32_t l = 0; l < L; l++) {
+            if (off_bits[l] > 61 * nblk) {  // (the widest offset has 61 bits)
+                set_error("wt import: off_bits[%u] = %llu exceeds 61 bits per block", l, (unsigned long long)off_bits[l]);
+                return VIDC_ERR_INVALID;
+            }
+            need += (off_bits[l] + 63) / 64;
+        }
+        if (n_offs != need || (n_offs && !offs)) {
+            set_error("wt import: n_offs = %llu, off_bits needs %llu words", (unsigned long long)n_offs, (unsigned long long)need);
+            return VIDC_ERR_INVALID;
+        }
+        uint64_t at = 0;
+        for (uint32_t l = 0; l < L; l++) {
+            for (uint64_t b = nblk; b < nsamp * RRR_K; b++) {  // class fields behind the last block (fewer than 32)
+                const uint64_t bp = 6 * b;
+                uint64_t f = (uint64_t)cls[(uint64_t)l * 6 * nsamp + (bp >> 5)] >> (bp & 31);
+                if ((bp & 31) > 26) f |= (uint64_t)cls[(uint64_t)l * 6 * nsamp + (bp >> 5) + 1] << (32 - (bp & 31));
+                if (f & 63u) { set_error("wt import: cls: level %u has a class field behind its last block", l); return VIDC_ERR_INVALID; }
+            }
+            const uint64_t ow = (off_bits[l] + 63) / 64;
+            if ((off_bits[l] & 63u) && (offs[at + ow - 1] >> (off_bits[l] & 63u))) {
+                set_error("wt import: offs: level %u has a bit set behind off_bits", l);
+                return VIDC_ERR_INVALID;
+            }
+            at += ow;
+        }
+    }
+    // 2. the object as wt_build_impl lays it out; arrays copied in, every pad word zero
+    VIDC_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<vidc_wt> w(new vidc_wt());
+    w->device = ctx->device;
+    w->nlist = nlist;
+    w->wt_type = wt_type;
+    w->offsets.assign(offsets, offsets + nlist + 1);
+    w->ntotal = nt;
+    w->L = L;
+    w->words_per_level = W + 1;
+    w->blocks_per_level = (w->words_per_level + BLK_WORDS - 1) / BLK_WORDS;
+    const uint64_t wpl = w->words_per_level, bpl = w->blocks_per_level;
+    Scratch s_sum, s_sum2, s_scan, s_scan2, s_tmp, s_tmp2, s_err;
+    StreamGuard guard(ctx);  // (behind the blocks: an early return waits before they go back to the pool)
+    VIDC_TRY(w->d_C.alloc(nlist + 1));
+    VIDC_TRY(w->d_nrank.alloc(wt_nrank_base(L) + 1));
+    VIDC_TRY(w->d_dstab.alloc(2 * (wt_nrank_base(L) + 1)));
+    VIDC_TRY(s_err.get(ctx, 8 + (size_t)L * 8));  // the error word, the levels' width totals
+    if (!rrr) {
+        VIDC_TRY(w->d_bits.alloc(L * wpl));
+        VIDC_TRY(w->d_rank.alloc(L * (bpl + 1)));
+    } else {
+        w->rrr_nblk = nblk; w->rrr_nsamp = nsamp;
+        w->rrr_cls_wpl = 6 * nsamp + 2;
+        w->rrr_off_bits.assign(off_bits, off_bits + L);
+        w->rrr_off_base.assign(L + 1, 0);
+        for (uint32_t l = 0; l < L; l++) w->rrr_off_base[l + 1] = w->rrr_off_base[l] + (off_bits[l] + 63) / 64 + 1;
+        VIDC_TRY(w->d_cls.alloc(L * w->rrr_cls_wpl));
+        VIDC_TRY(w->d_ptr.alloc(L * (nsamp + 1)));
+        VIDC_TRY(w->d_rs.alloc(L * (nsamp + 1)));
+        VIDC_TRY(w->d_offs.alloc(w->rrr_off_base[L]));
+        VIDC_TRY(wt_rrr_tables(ctx, w.get(), tab));
+    }
+    // the pad words (one behind every level's bits; two class words and one offset word behind every level's RRR coding): everything
+    // else is overwritten by the copies
+    for (uint32_t l = 0; l < L; l++) {
+        if (!rrr) VIDC_HIP(hipMemsetAsync(w->d_bits.p + (uint64_t)l * wpl + W, 0, 8, ctx->stream));
+        else {
+            VIDC_HIP(hipMemsetAsync(w->d_cls.p + (uint64_t)l * w->rrr_cls_wpl + 6 * nsamp, 0, 8, ctx->stream));
+            VIDC_HIP(hipMemsetAsync(w->d_offs.p + w->rrr_off_base[l + 1] - 1, 0, 8, ctx->stream));
+        }
+    }
+    VIDC_HIP(hipEventRecord(ctx->tev[0], ctx->stream));
+    VIDC_HIP(hipMemcpyAsync(w->d_C.p, offsets, (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!rrr) {
+        for (uint32_t l = 0; l < L && W; l++)
+            VIDC_HIP(hipMemcpyAsync(w->d_bits.p + (uint64_t)l * wpl, bits + (uint64_t)l * W, W * 8, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        uint64_t at = 0;
+        for (uint32_t l = 0; l < L; l++) {
+            if (nsamp) VIDC_HIP(hipMemcpyAsync(w->d_cls.p + (uint64_t)l * w->rrr_cls_wpl, cls + (uint64_t)l * 6 * nsamp, 6 * nsamp * 4, hipMemcpyHostToDevice, ctx->stream));
+            const uint64_t ow = (off_bits[l] + 63) / 64;
+            if (ow) VIDC_HIP(hipMemcpyAsync(w->d_offs.p + w->rrr_off_base[l], offs + at, ow * 8, hipMemcpyHostToDevice, ctx->stream));
+            at += ow;
+        }
+    }
+    VIDC_HIP(hipEventRecord(ctx->tev[1], ctx->stream));
+    EventTimer t(ctx);
+    double kernel_ms_before = 0;
+    VIDC_HIP(t.start());
+    unsigned long long *d_err = s_err.as<unsigned long long>();
+    uint64_t *d_tot = s_err.as<uint64_t>() + 1;
+    VIDC_HIP(hipMemsetAsync(d_err, 0xff, 8, ctx->stream));
+    // 3. the node tables, from the offsets alone
+    VIDC_HIP(hipMemsetAsync(w->d_nrank.p, 0, (wt_nrank_base(L) + 1) * 4, ctx->stream));
+    hipLaunchKernelGGL(k_wt_node_ranks_from_C, dim3(L * VIDC_WT_NR_G), dim3(256), 0, ctx->stream, w->d_C.p, (uint32_t)nlist, L, w->d_nrank.p,
+                       w->d_dstab.p);
+    VIDC_HIP(hipGetLastError());
+    const dim3 ngrid((uint32_t)std::min<uint64_t>(((1ull << (L - 1)) + 1 + 255) / 256, 4096), L);
+    if (!rrr) {
+        // 4. the rank directory: ones of every 512-bit block, one scan over the levels back to back, per-level prefixes
+        const uint64_t n = (uint64_t)L * bpl;
+        VIDC_TRY(s_sum.get(ctx, n * 4));
+        VIDC_TRY(s_scan.get(ctx, (n + 1) * 8));
+        hipLaunchKernelGGL(k_wt_imp_block_ones, dim3((uint32_t)((bpl * 8 + 255) / 256), L), dim3(256), 0, ctx->stream, w->d_bits.p, wpl, bpl,
+                           s_sum.as<uint32_t>());
+        VIDC_TRY(device_exscan(ctx, s_sum.as<uint32_t>(), (uint32_t)n, s_scan.as<uint64_t>(), s_tmp));
+        hipLaunchKernelGGL(k_wt_imp_level_prefix, dim3((uint32_t)std::min<uint64_t>((bpl + 256) / 256, 1024), L), dim3(256), 0, ctx->stream,
+                           s_scan.as<uint64_t>(), bpl, w->d_rank.p, (uint64_t *)nullptr);
+        // 6. the node check
+        hipLaunchKernelGGL(k_wt_imp_check_nodes<WtPlainView>, ngrid, dim3(256), 0, ctx->stream, plain_view(w.get()), w->d_C.p, w->d_nrank.p,
+                           (uint32_t)nlist, L, d_err);
+        VIDC_HIP(hipGetLastError());
+    } else {
+        // 5. the samples: sums of the classes and of their widths per sample, two scans, per-level prefixes; the levels' width totals
+        // are compared with off_bits before anything reads an offset stream
+        const uint64_t n = (uint64_t)L * nsamp;
+        VIDC_TRY(s_sum.get(ctx, (n ? n : 1) * 4));
+        VIDC_TRY(s_sum2.get(ctx, (n ? n : 1) * 4));
+        VIDC_TRY(s_scan.get(ctx, (n + 1) * 8));
+        VIDC_TRY(s_scan2.get(ctx, (n + 1) * 8));
+        if (nsamp)
+            hipLaunchKernelGGL(k_wt_imp_sample_sums, dim3((uint32_t)((nsamp + 255) / 256), L), dim3(256), 0, ctx->stream, w->d_cls.p, w->rrr_cls_wpl,
+                               nsamp, (const uint8_t *)(w->d_binom.p + 64 * 64), s_sum.as<uint32_t>(), s_sum2.as<uint32_t>());
+        VIDC_TRY(device_exscan(ctx, s_sum.as<uint32_t>(), (uint32_t)n, s_scan.as<uint64_t>(), s_tmp));
+        VIDC_TRY(device_exscan(ctx, s_sum2.as<uint32_t>(), (uint32_t)n, s_scan2.as<uint64_t>(), s_tmp2));
+        const dim3 pgrid((uint32_t)std::min<uint64_t>((nsamp + 256) / 256, 1024), L);
+        hipLaunchKernelGGL(k_wt_imp_level_prefix, pgrid, dim3(256), 0, ctx->stream, s_scan.as<uint64_t>(), nsamp, w->d_rs.p, (uint64_t *)nullptr);
+        hipLaunchKernelGGL(k_wt_imp_level_prefix, pgrid, dim3(256), 0, ctx->stream, s_scan2.as<uint64_t>(), nsamp, w->d_ptr.p, d_tot);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(t.mark());  // (the kernel time of the call is the two intervals around this read-back, not the wait between them)
+        std::vector<uint64_t> tot(L, 0);
+        VIDC_HIP(hipMemcpyAsync(tot.data(), d_tot, (size_t)L * 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        kernel_ms_before = t.elapsed();
+        for (uint32_t l = 0; l < L; l++)
+            if (tot[l] != off_bits[l]) {
+                set_error("wt import: off_bits[%u] = %llu, the classes of the level need %llu bits", l, (unsigned long long)off_bits[l],
+                          (unsigned long long)tot[l]);
+                return VIDC_ERR_INVALID;
+            }
+        VIDC_HIP(t.start());
+        if (nblk)
+            hipLaunchKernelGGL(k_wt_imp_check_blocks, dim3((uint32_t)std::min<uint64_t>((nblk + 255) / 256, (uint64_t)ctx->num_cu * 8), L), dim3(256), 0,
+                               ctx->stream, rrr_view(w.get()), d_err);
+        // 6. the node check
+        hipLaunchKernelGGL(k_wt_imp_check_nodes<WtRrrView>, ngrid, dim3(256), 0, ctx->stream, rrr_view(w.get()), w->d_C.p, w->d_nrank.p,
+                           (uint32_t)nlist, L, d_err);
+        VIDC_HIP(hipGetLastError());
+    }
+    unsigned long long err = 0;
+    VIDC_HIP(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, ctx->stream));
+    guard.disarm();
+    VIDC_TRY(t.finish());
+    ctx->last_kernel_ms += kernel_ms_before;
+    {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ctx->tev[0], ctx->tev[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_IMPORT_H2D] = ms;
+    }
+    if (err != ~0ull) {
+        const uint32_t level = (uint32_t)(err >> 56) & 0x7fu, kind = (uint32_t)(err & 0xffu);
+        const unsigned long long idx = (err >> 8) & 0xffffffffffffull;
+        if (kind == VIDC_WT_IMP_NODE)
+            set_error("wt import: the image does not match the offsets: ones before node %llu of level %u differ", idx, level);
+        else
+            set_error("wt import: %s: block %llu of level %u %s", kind == VIDC_WT_IMP_OFFSET ? "offs" : "cls", idx, level,
+                      kind == VIDC_WT_IMP_OFFSET ? "has an offset >= C(63, class)"
+                      : kind == VIDC_WT_IMP_CLASS ? "has a class above the number of its bits" : "has a one behind the end of the level");
+        return VIDC_ERR_INVALID;
+    }
+    // 7. size accounting, as wt_build_impl
+    if (!rrr) {
+        w->size_bytes = (uint64_t)L * (W * 8 + (bpl + 1) * 4) + (nlist + 1) * 8;
+    } else {
+        uint64_t ob = 0;
+        for (uint32_t l = 0; l < L; l++) ob += off_bits[l];
+        w->size_bytes = (ob + 7) / 8 + (uint64_t)L * ((6 * nblk + 7) / 8) + (uint64_t)L * (nsamp + 1) * 8 + (nlist + 1) * 8;
+    }
+    *out = w.release();
     return VIDC_OK;
 }
 
