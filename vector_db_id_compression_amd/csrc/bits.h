@@ -27,10 +27,10 @@ __device__ __forceinline__ uint64_t read_bits(const uint64_t *words, uint64_t po
 }
 
 // the 64-bit word `w_in_list` of a stream that packs src[i] (i < n) at bit i*bits: gathered by ONE owner
-// thread, so no atomics are needed.  flags bit 0 is raised when a value does not fit / exceeds id_limit.
+// thread, so no atomics are needed.  flags bit 0 is raised when a value does not fit.
 template <bool CHECK>
 __device__ __forceinline__ uint64_t gather_word(const uint64_t *src, uint64_t n, uint64_t w_in_list, uint32_t bits,
-                                                uint64_t keep_mask, uint64_t id_limit, uint32_t *err) {
+                                                uint64_t keep_mask, uint32_t *err) {
     uint64_t out = 0;
     if (!bits) return 0;
     const uint64_t bit0 = w_in_list * 64;
@@ -39,7 +39,7 @@ __device__ __forceinline__ uint64_t gather_word(const uint64_t *src, uint64_t n,
         if (pos >= bit0 + 64) break;
         uint64_t v = src[i];
         if (CHECK) {
-            if (v >= id_limit || (bits < 64 && (v >> bits))) atomicOr(err, 1u);
+            if (bits < 64 && (v >> bits)) atomicOr(err, 1u);
         }
         v &= keep_mask;
         if (pos >= bit0) out |= v << (pos - bit0);

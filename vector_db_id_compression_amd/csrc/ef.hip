@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(64) k_ef_low(const uint64_t *sorted_ids, const
         const uint64_t w0 = (uint64_t)ch.start * b / 64, w1 = ((uint64_t)(ch.start + nc) * b + 63) / 64;
         uint64_t *dst = low + low_off[ch.list];
         for (uint64_t w = w0 + lane; w < w1; w += 64)
-            dst[w] = gather_word<false>(sorted_ids + off, n, w, b, keep, ~0ull, nullptr);
+            dst[w] = gather_word<false>(sorted_ids + off, n, w, b, keep, nullptr);
     }
 }
 

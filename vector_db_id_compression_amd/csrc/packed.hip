@@ -52,7 +52,7 @@ namespace {
 // lists of 256 encode 55 -> 53 us, decode 36 -> 35 us, against 83 -> 70 us for the Elias-Fano encoder's same change)
 template <int R>
 __device__ __forceinline__ void packed_encode_chunks(const uint64_t *ids, const uint64_t *offsets, const uint64_t *word_off,
-                                                     const Chunk *chunks, uint64_t nchunks, uint32_t bits, uint64_t id_limit,
+                                                     const Chunk *chunks, uint64_t nchunks, uint32_t bits,
                                                      uint64_t *words, uint32_t *err, unsigned long long *img) {
     const uint32_t lane = threadIdx.x;
     const uint64_t keep = bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
@@ -77,7 +77,7 @@ __device__ __forceinline__ void packed_encode_chunks(const uint64_t *ids, const 
         for (uint32_t r = 0; r < R; r++) {
             const uint32_t i = lane + 64 * r;
             if (i < nc) {
-                bad |= v[r] >= id_limit || (bits < 64 && (v[r] >> bits));
+                bad |= bits < 64 && (v[r] >> bits);  // (every id fits 64 bits, 2^64 - 1 included)
                 const uint64_t x = v[r] & keep;
                 const uint32_t pos = i * bits, sh = pos & 63u;
                 atomicOr(&img[pos >> 6], x << sh);
@@ -94,9 +94,9 @@ __device__ __forceinline__ void packed_encode_chunks(const uint64_t *ids, const 
 template <int R>
 __global__ void __launch_bounds__(64) k_packed_encode(const uint64_t *ids, const uint64_t *offsets,
                                                       const uint64_t *word_off, const Chunk *chunks, uint64_t nchunks,
-                                                      uint32_t bits, uint64_t id_limit, uint64_t *words, uint32_t *err) {
+                                                      uint32_t bits, uint64_t *words, uint32_t *err) {
     __shared__ unsigned long long img[64 * R + 8];  // <= 64 R * 64 / 64 words
-    packed_encode_chunks<R>(ids, offsets, word_off, chunks, nchunks, bits, id_limit, words, err, img);
+    packed_encode_chunks<R>(ids, offsets, word_off, chunks, nchunks, bits, words, err, img);
 }
 // The same for an object built from device offsets (vidc_packed_encode_dev): the chunk count and the longest list come from the
 // ingest's results (dev_offsets.h), the grid from the bound floor(ntotal / 512) + nlist.  The choice between the four- and
@@ -109,9 +109,9 @@ __global__ void __launch_bounds__(64) k_packed_encode_dev(const uint64_t *ids, c
     if (acc[DOFF_BAD]) return;
     const uint64_t nchunks = acc[DOFF_CHUNKS];
     if (acc[DOFF_MAX] <= 256u)
-        packed_encode_chunks<4>(ids, offsets, word_off, chunks, nchunks, bits, ~0ull, words, err, img);
+        packed_encode_chunks<4>(ids, offsets, word_off, chunks, nchunks, bits, words, err, img);
     else
-        packed_encode_chunks<CHUNK_IDS / 64>(ids, offsets, word_off, chunks, nchunks, bits, ~0ull, words, err, img);
+        packed_encode_chunks<CHUNK_IDS / 64>(ids, offsets, word_off, chunks, nchunks, bits, words, err, img);
 }
 
 // The geometry of an object in ONE launch: chunk table, word offsets and the zeroed padding word of every list.  (Chunk counts -> scan
@@ -901,8 +901,8 @@ static PackedTiling packed_table_tiling(uint64_t nlist) {
     return {per, (uint32_t)((nlist + 1 + 256u * per - 1u) / (256u * per))};
 }
 static int packed_id_does_not_fit(int bits) {
-    set_error("packed bits: an id does not fit %d bits (reference: FAISS_THROW_IF_NOT(ids_in[i] >= 0 && "
-              "ids_in[i] < ntotal), custom_invlists_impl.cpp:87)", bits);
+    set_error("packed bits: an id does not fit %d bits (the reference throws on an id outside [0, ntotal), "
+              "custom_invlists_impl.cpp:87; this library takes every id that fits the field)", bits);
     return VIDC_ERR_DOMAIN;
 }
 
@@ -974,15 +974,14 @@ int vidc_packed_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, c
     *err_flag = 0u;
     if (p->total_words) {
         uint32_t grid = (uint32_t)std::min<uint64_t>(p->nchunks, (uint64_t)ctx->num_cu * 256);
-        // ids must fit the field (FAISS_THROW_IF_NOT(ids_in[i] >= 0 && ids_in[i] < ntotal), :87)
-        uint64_t limit = ~0ull;
+        // ids must fit the field; the reference's narrower bound, ids_in[i] < ntotal (:87), is not enforced: the width may be given
         if (p->nchunks && p->max_list <= 256)
             hipLaunchKernelGGL(k_packed_encode<4>, dim3(grid), dim3(64), 0, ctx->stream, d_ids, p->d_offsets.p,
-                               p->d_word_off.p, p->d_chunks.p, p->nchunks, (uint32_t)bits, limit, p->d_words.p,
+                               p->d_word_off.p, p->d_chunks.p, p->nchunks, (uint32_t)bits, p->d_words.p,
                                h_err.as<uint32_t>());
         else if (p->nchunks)
             hipLaunchKernelGGL(k_packed_encode<CHUNK_IDS / 64>, dim3(grid), dim3(64), 0, ctx->stream, d_ids, p->d_offsets.p,
-                               p->d_word_off.p, p->d_chunks.p, p->nchunks, (uint32_t)bits, limit, p->d_words.p,
+                               p->d_word_off.p, p->d_chunks.p, p->nchunks, (uint32_t)bits, p->d_words.p,
                                h_err.as<uint32_t>());
         VIDC_HIP(hipGetLastError());
     }
