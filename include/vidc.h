@@ -418,6 +418,83 @@ int vidc_wt_append_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n_add, const in
 int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int precision_mode, uint32_t flags, vidc_roc **out, int64_t *d_labels, uint64_t *d_invalid);
 
+/* ---------------------------------------------- sharded lists (several contexts, one process) */
+/* One CSR set of lists cut into shards, one codec object per shard, each built and served through its own context: the container of a
+ * process that drives all of its GPUs itself (a Faiss process and its OpenMP loops, custom_invlists_impl.cpp:147,508-525), where
+ * sharding.py's ShardedInvLists needs one process per GPU.  Contexts of one object may sit on the same device: a supported mode (the host
+ * plans several ROC shards at once), and the only one exercised so far -- NOTHING HERE HAS BEEN RUN ON MORE THAN ONE GPU.
+ *
+ * Ownership.  Shards are balanced by the longest-processing-time rule on the list lengths: lists in descending size, ties by ascending
+ *   list number; each to the shard with the least load so far, ties to the lowest shard number (sharding.lpt_partition, bit for bit).
+ *   The local number of a list is its rank among its owner's lists in ascending global number.  The map is replicated on the home device
+ *   (one uint64 per list: shard << 32 | local_no); nlist < 2^32.
+ * Contract.  Shard s holds exactly the object that vidc_{packed,ef,roc}_encode builds from its cut CSR with the same param and flags,
+ *   word for word.  kind = VIDC_KIND_PACKED: param = the packed width, 0 = vidc_packed_bits_for(ntotal) of the GLOBAL id count (every shard
+ *   uses the same width); VIDC_KIND_ROC: param = precision_mode; VIDC_KIND_EF: param is ignored.  flags are the codec's own
+ *   (VIDC_ROC_WANT_PERM, VIDC_EF_WANT_PERM).  A shard that owns no list holds no object and is skipped everywhere; a shard whose lists are
+ *   all empty holds an ordinary object.  VIDC_KIND_WT is VIDC_ERR_UNSUPPORTED: a shard's ids are not a permutation of 0 .. n - 1.
+ * Contexts.  shard_ctxs: nshards distinct contexts on any devices, repeated devices included; `home` may be one of them.  The caller owns
+ *   them and keeps them alive as long as the object.  Device inputs and outputs of every call live on the home device and are read and
+ *   written on the home context's stream.  A call drives the home context and every shard context: no other call may use any of them
+ *   meanwhile.
+ * What runs where.  The cut (global ids -> each shard's contiguous ids), its inverse (decode_all) and the placement of decode_lists
+ *   results are one segmented-copy kernel on the home stream (a wavefront per 1024-element chunk of a segment; 16-byte accesses where a
+ *   segment's source and destination share their alignment mod 16).  A shard on the home device is read and written in place (blocks of
+ *   its context's cache); a shard on another device goes through hipMemcpyAsync(hipMemcpyDefault) between staging blocks of the two
+ *   contexts' caches.  Per-shard calls that wait (encode, decode_*, perm, ROC's translate) are issued from one host thread per involved
+ *   shard, at most VIDC_SHARDS_MAX; each sets its device itself.  The enqueue-only per-shard calls (packed, Elias-Fano translate) are
+ *   issued from the calling thread and ordered against the home stream with events the object owns (timing disabled; no spinning kernels,
+ *   no cross-context atomics).
+ * Errors.  NULL arguments, nshards outside 1 .. VIDC_SHARDS_MAX, a repeated context, an unknown kind: VIDC_ERR_INVALID before any device
+ *   work.  A status from a shard is returned; vidc_last_error names the lowest-numbered failing shard and carries its message.  On any
+ *   error of an encode *out == NULL, every shard object already built is destroyed, and every context stays usable. */
+typedef struct vidc_shards vidc_shards;
+#define VIDC_KIND_PACKED 0
+#define VIDC_KIND_EF 1
+#define VIDC_KIND_ROC 2
+#define VIDC_KIND_WT 3 /* known, and refused: VIDC_ERR_UNSUPPORTED */
+#define VIDC_SHARDS_MAX 8
+int vidc_shards_encode(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, int param, uint32_t flags, uint64_t nlist,
+                       const uint64_t *offsets /* host */, const uint64_t *d_ids /* home device */, vidc_shards **out);
+/* d_offsets: device uint64[nlist + 1] on the home device; the plan is made on the host, so the offsets cross PCIe once (D2H, as
+ * vidc_roc_encode_dev); ntotal must equal d_offsets[nlist]. */
+int vidc_shards_encode_dev(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, int param, uint32_t flags, uint64_t nlist,
+                           const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids, vidc_shards **out);
+void vidc_shards_destroy(vidc_shards *s);
+/* host-side accessors: no device work */
+int vidc_shards_count(const vidc_shards *s);
+int vidc_shards_kind(const vidc_shards *s); /* -1 for NULL */
+uint64_t vidc_shards_nlist(const vidc_shards *s);
+uint64_t vidc_shards_ntotal(const vidc_shards *s);
+/* the sum of the shards' own = the unsharded object's (Elias-Fano: the shards' stream bits are summed before the division by 8) */
+uint64_t vidc_shards_compressed_bytes(const vidc_shards *s);
+int vidc_shards_map(const vidc_shards *s, int32_t *owner, uint32_t *local_no); /* nlist entries each; either may be NULL */
+int vidc_shards_offsets(const vidc_shards *s, uint64_t *offsets);             /* the caller's offsets[nlist + 1] */
+/* borrowed: shard i's vidc_packed / vidc_ef / vidc_roc object, for parity tests and for saving shards one by one with the export calls
+ * (NULL for a shard without lists); and the context it was built through */
+const void *vidc_shards_shard(const vidc_shards *s, int i);
+vidc_ctx *vidc_shards_shard_ctx(const vidc_shards *s, int i);
+/* Requests: called on the home context the object was built with.  With U = the object vidc_*_encode builds from the same arguments:
+ * decode_all = U's decode_all, element for element (the shards decode concurrently, then the inverse cut runs).
+ * decode_lists = U's (request order and repeats kept, empty lists allowed; m == 0: VIDC_OK; a list >= nlist: VIDC_ERR_INVALID before any
+ *   device work); routed on the host, every involved shard decodes into staging, the copy kernel puts the lists in request order.
+ * translate_labels_dev = U's outputs and invalid count (negative labels, lists >= nlist, offsets >= the list's size as there; d_ids ==
+ *   d_labels allowed; n == 0 launches nothing; n < 2^32).  A route kernel writes for EVERY shard a full-length local label array
+ *   (local_no << 32 | offset where the shard owns the list, -1 elsewhere: nshards * n label slots, no count read-back), each shard's
+ *   own translate runs on it, a join kernel picks the owner's answer and adds up the invalid counts.  Unlike the single-object calls this
+ *   one WAITS for its join, for every kind; an enqueue-only form is out of scope.
+ * decode_gather = U's, signature and checks of vidc_*_decode_gather; items are routed on the host, each involved shard runs its own
+ *   decode_gather, a host scatter fills ids_out.  The contexts' vidc_ctx_d2h_bytes grow by 8 * n_items in total.
+ * perm = U's permutation in global CSR order (ROC / Elias-Fano built with the perm flag; VIDC_ERR_INVALID otherwise). */
+int vidc_shards_decode_all(vidc_ctx *home, const vidc_shards *s, uint64_t *d_out);
+int vidc_shards_decode_lists(vidc_ctx *home, const vidc_shards *s, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,
+                             uint64_t *out_offsets);
+int vidc_shards_translate_labels_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                     uint64_t *d_invalid);
+int vidc_shards_decode_gather(vidc_ctx *home, const vidc_shards *s, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
+                              const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out);
+int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host);
+
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,
  * measured with hipEvents on the context's stream (used by bench.py for the roofline figure). */

@@ -18,6 +18,8 @@ VIDC_PREC_EXACT = -2
 VIDC_ROC_WANT_PERM = 1
 VIDC_EF_WANT_PERM = 1
 VIDC_ROC_MAX_LIST = 262144
+VIDC_KIND_PACKED, VIDC_KIND_EF, VIDC_KIND_ROC, VIDC_KIND_WT = 0, 1, 2, 3
+VIDC_SHARDS_MAX = 8
 
 _lib = None
 
@@ -144,6 +146,24 @@ def _declare(lib):
     f("vidc_ef_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp)
     f("vidc_wt_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp)
     f("vidc_roc_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp)
+    # sharded lists (several contexts, one process)
+    f("vidc_shards_encode", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _u32, _u64, _vp, _vp, _P(_vp))
+    f("vidc_shards_encode_dev", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _u32, _u64, _vp, _u64, _vp, _P(_vp))
+    f("vidc_shards_destroy", None, _vp)
+    f("vidc_shards_count", C.c_int, _vp)
+    f("vidc_shards_kind", C.c_int, _vp)
+    f("vidc_shards_nlist", _u64, _vp)
+    f("vidc_shards_ntotal", _u64, _vp)
+    f("vidc_shards_compressed_bytes", _u64, _vp)
+    f("vidc_shards_map", C.c_int, _vp, _vp, _vp)
+    f("vidc_shards_offsets", C.c_int, _vp, _vp)
+    f("vidc_shards_shard", _vp, _vp, C.c_int)
+    f("vidc_shards_shard_ctx", _vp, _vp, C.c_int)
+    f("vidc_shards_decode_all", C.c_int, _vp, _vp, _vp)
+    f("vidc_shards_decode_lists", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_shards_translate_labels_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_shards_decode_gather", C.c_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_shards_perm", C.c_int, _vp, _vp, _vp)
 
 
 #: every symbol include/vidc.h declares (checked by the CPU test-suite against the built library)
@@ -169,6 +189,10 @@ EXPORTED_SYMBOLS = [
     "vidc_compact_rows_decode_dev", "vidc_ef_decode_rows_dev", "vidc_roc_decode_rows_dev",
     "vidc_packed_append_dev", "vidc_ef_append_dev", "vidc_wt_append_dev", "vidc_roc_append_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
+    "vidc_shards_encode", "vidc_shards_encode_dev", "vidc_shards_destroy", "vidc_shards_count", "vidc_shards_kind", "vidc_shards_nlist",
+    "vidc_shards_ntotal", "vidc_shards_compressed_bytes", "vidc_shards_map", "vidc_shards_offsets", "vidc_shards_shard",
+    "vidc_shards_shard_ctx", "vidc_shards_decode_all", "vidc_shards_decode_lists", "vidc_shards_translate_labels_dev",
+    "vidc_shards_decode_gather", "vidc_shards_perm",
 ]
 
 

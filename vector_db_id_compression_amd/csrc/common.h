@@ -208,6 +208,9 @@ int gather_to_host(::vidc_ctx *c, const uint64_t *d_ids, const uint64_t *list_of
 int req_scratch(::vidc_ctx *c, size_t bytes, void **p);
 int req_done(::vidc_ctx *c);
 
+// low + high stream bits of an Elias-Fano object (ef.hip): vidc_ef_compressed_bytes before its division by 8
+uint64_t ef_stream_bits(const ::vidc_ef *e);
+
 }  // namespace vidc
 
 // mt19937(1234) words available to the kernels for ANS stack underflow (codec.h:16-18,32-40).

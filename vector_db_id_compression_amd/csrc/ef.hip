@@ -2324,6 +2324,12 @@ void vidc_ef_destroy(vidc_ef *e) { delete e; }
 
 // compressed_ids_size_in_bytes = (sum of low.size() + high.size() in bits) / 8, custom_invlists_impl.cpp:272-282
 uint64_t vidc_ef_compressed_bytes(const vidc_ef *e) { return e ? e->total_bits / 8 : 0; }
+// (not part of the C-ABI: the undivided figure, for vidc_shards_compressed_bytes -- the sum of the shards' floors is not the floor of the sum)
+extern "C++" {
+namespace vidc {
+uint64_t ef_stream_bits(const vidc_ef *e) { return e ? e->total_bits : 0; }
+}  // namespace vidc
+}
 
 int vidc_ef_list_info(const vidc_ef *e, uint32_t *sizes, uint32_t *low_bits, uint64_t *universes) {
     if (!e) return VIDC_ERR_INVALID;

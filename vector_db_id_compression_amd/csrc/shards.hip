@@ -1,0 +1,687 @@
+// shards.hip -- vidc_shards (include/vidc.h): one CSR set of lists cut over several contexts of one process.  The plan is host code
+// (shard_plan.h); the shards are ordinary vidc_packed / vidc_ef / vidc_roc objects built and served through the public entry points, so a
+// shard IS what the single-object encoder builds from its cut CSR.  What is new on the device: the segmented copy (cut, inverse cut,
+// placement of decode_lists results) and the route / join pair of translate_labels.
+#include <thread>
+
+#include "common.h"
+#include "host_call.h"
+#include "requests.h"
+#include "shard_plan.h"
+#include "wave.h"
+
+using namespace vidc;
+using namespace vidc::shardplan;
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------------------------ kernels
+// Segmented copy, a wavefront per chunk of SHARD_COPY_UNIT elements: dst[seg.dst_start ..] = src[seg.src_start ..] (INV: the segment
+// table read the other way round -- the inverse of the cut).  16-byte accesses where the two runs share their alignment mod 16 (after
+// at most one leading element), 8-byte accesses otherwise.  chunks / segs come from the host plan: chunk.seg < the table's length and
+// chunk.start < seg.count by construction (shardplan::build_copy_chunks).
+template <bool INV>
+__global__ void __launch_bounds__(256) k_shard_copy(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, const Segment *__restrict__ segs,
+                                                    const CopyChunk *__restrict__ chunks, uint64_t nchunks) {
+    const uint32_t lane = dev::lane_id();
+    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < nchunks; c += (uint64_t)gridDim.x * 4u) {
+        const CopyChunk ch = chunks[c];
+        const Segment sg = segs[ch.seg];
+        const uint64_t left = sg.count - ch.start;
+        const uint32_t nc = (uint32_t)(left < SHARD_COPY_UNIT ? left : SHARD_COPY_UNIT);
+        const uint64_t *s = src + (INV ? sg.dst_start : sg.src_start) + ch.start;
+        uint64_t *d = dst + (INV ? sg.src_start : sg.dst_start) + ch.start;
+        if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0u) {
+            uint32_t head = (uint32_t)(((uintptr_t)d & 15u) ? 1u : 0u);
+            head = head < nc ? head : nc;
+            if (lane < head) d[lane] = s[lane];
+            const uint32_t nv = (nc - head) / 2u;
+            const uint4 *sv = (const uint4 *)(s + head);
+            uint4 *dv = (uint4 *)(d + head);
+            for (uint32_t j = lane; j < nv; j += 64u) dv[j] = sv[j];
+            for (uint32_t j = head + nv * 2u + lane; j < nc; j += 64u) d[j] = s[j];
+        } else {
+            for (uint32_t j = lane; j < nc; j += 64u) d[j] = s[j];
+        }
+    }
+}
+
+constexpr uint32_t NO_OWNER = 0xffu;
+
+// Label route: local[s * n + i] = local_no << 32 | offset if shard s owns label i's list, else -1 (the shards' own translate gives -1 for
+// a negative label and does not count it); owner[i] = the owning shard, NO_OWNER for a negative label or a list >= nlist (the latter
+// counted in *invalid).  The offset is checked by the owner.
+__global__ void __launch_bounds__(256) k_shard_route(const int64_t *__restrict__ labels, uint64_t n, const uint64_t *__restrict__ map, uint64_t nlist,
+                                                     uint32_t nshards, int64_t *__restrict__ local, uint8_t *__restrict__ owner,
+                                                     unsigned long long *invalid) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
+        const uint64_t i = i0 + dev::lane_id();
+        const int64_t lab = i < n ? labels[i] : -1;
+        uint64_t list, off;
+        const bool pos = req_label(lab, list, off);
+        const bool ok = pos && list < nlist;
+        const uint64_t e = ok ? map[list] : 0;
+        const uint32_t own = ok ? (uint32_t)(e >> 32) : NO_OWNER;
+        if (i < n) {
+            const int64_t mine = (int64_t)((e & 0xffffffffull) << 32 | off);
+            for (uint32_t s = 0; s < nshards; s++) local[(uint64_t)s * n + i] = s == own ? mine : -1;
+            owner[i] = (uint8_t)own;
+        }
+        req_count_invalid(pos && !ok, invalid);
+    }
+}
+
+// Label join: ids[i] = the owner's answer, or -1; *invalid += the shards' own counts (offsets >= the list's size)
+__global__ void __launch_bounds__(256) k_shard_join(const int64_t *__restrict__ answers, const uint8_t *__restrict__ owner, uint64_t n,
+                                                    uint32_t nshards, int64_t *__restrict__ ids, const unsigned long long *__restrict__ shard_invalid,
+                                                    unsigned long long *invalid) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t o = owner[i];
+        ids[i] = o < nshards ? answers[(uint64_t)o * n + i] : -1;
+    }
+    if (invalid && blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned long long sum = 0;
+        for (uint32_t s = 0; s < nshards; s++) sum += shard_invalid[s];
+        if (sum) atomicAdd(invalid, sum);
+    }
+}
+
+inline dim3 copy_grid(const vidc_ctx *c, uint64_t nchunks) {
+    return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nchunks + 3) / 4, (uint64_t)c->num_cu * 16)));
+}
+
+// ------------------------------------------------------------------------------------------- the codecs behind one switch
+int codec_encode(int kind, vidc_ctx *c, uint64_t nlist, const uint64_t *off, const uint64_t *d_ids, int param, uint32_t flags, void **out) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_encode(c, nlist, off, d_ids, param, (vidc_packed **)out);
+    case VIDC_KIND_EF: return vidc_ef_encode(c, nlist, off, d_ids, flags, (vidc_ef **)out);
+    default: return vidc_roc_encode(c, nlist, off, d_ids, param, flags, (vidc_roc **)out);
+    }
+}
+void codec_destroy(int kind, void *o) {
+    if (!o) return;
+    switch (kind) {
+    case VIDC_KIND_PACKED: vidc_packed_destroy((vidc_packed *)o); break;
+    case VIDC_KIND_EF: vidc_ef_destroy((vidc_ef *)o); break;
+    default: vidc_roc_destroy((vidc_roc *)o); break;
+    }
+}
+uint64_t codec_bytes(int kind, const void *o) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_compressed_bytes((const vidc_packed *)o);
+    case VIDC_KIND_EF: return vidc_ef_compressed_bytes((const vidc_ef *)o);
+    default: return vidc_roc_compressed_bytes((const vidc_roc *)o);
+    }
+}
+int codec_decode_all(int kind, vidc_ctx *c, const void *o, uint64_t *d_out) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_decode_all(c, (const vidc_packed *)o, d_out);
+    case VIDC_KIND_EF: return vidc_ef_decode_all(c, (const vidc_ef *)o, d_out);
+    default: return vidc_roc_decode_all(c, (const vidc_roc *)o, d_out);
+    }
+}
+int codec_decode_lists(int kind, vidc_ctx *c, const void *o, uint64_t m, const uint64_t *lists, uint64_t *d_out, uint64_t *out_off) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_decode_lists(c, (const vidc_packed *)o, m, lists, d_out, out_off);
+    case VIDC_KIND_EF: return vidc_ef_decode_lists(c, (const vidc_ef *)o, m, lists, d_out, out_off);
+    default: return vidc_roc_decode_lists(c, (const vidc_roc *)o, m, lists, d_out, out_off);
+    }
+}
+int codec_decode_gather(int kind, vidc_ctx *c, const void *o, uint64_t m, const uint64_t *lists, uint64_t n, const uint64_t *slot,
+                        const uint64_t *off, int64_t *out) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_decode_gather(c, (const vidc_packed *)o, m, lists, n, slot, off, out);
+    case VIDC_KIND_EF: return vidc_ef_decode_gather(c, (const vidc_ef *)o, m, lists, n, slot, off, out);
+    default: return vidc_roc_decode_gather(c, (const vidc_roc *)o, m, lists, n, slot, off, out);
+    }
+}
+int codec_translate(int kind, vidc_ctx *c, const void *o, uint64_t n, const int64_t *d_labels, int64_t *d_ids, uint64_t *d_invalid) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_translate_labels_dev(c, (const vidc_packed *)o, n, d_labels, d_ids, d_invalid);
+    case VIDC_KIND_EF: return vidc_ef_translate_labels_dev(c, (const vidc_ef *)o, n, d_labels, d_ids, d_invalid);
+    default: return vidc_roc_translate_labels_dev(c, (const vidc_roc *)o, n, d_labels, d_ids, d_invalid);
+    }
+}
+
+}  // namespace
+
+struct vidc_shards {
+    int kind = 0, param = 0;
+    uint32_t flags = 0;
+    vidc_ctx *home = nullptr;
+    std::vector<vidc_ctx *> ctxs;
+    std::vector<void *> objs;  // NULL: the shard owns no list
+    ShardPlan plan;
+    // on the home device: the map, and per shard the cut's segment and chunk tables
+    DevBuf<uint64_t> d_map;
+    std::vector<DevBuf<Segment>> d_cut;
+    std::vector<DevBuf<CopyChunk>> d_cut_chunks;
+    std::vector<uint64_t> n_cut_chunks;
+    // ordering between the home stream and the shard streams: ev_home is recorded on the home stream (home device), ev_shard[s] on
+    // shard s's stream (its device); timing disabled
+    hipEvent_t ev_home = nullptr;
+    std::vector<hipEvent_t> ev_shard;
+    bool same_device(int s) const { return ctxs[(size_t)s]->device == home->device; }
+    ~vidc_shards() {
+        for (size_t i = 0; i < objs.size(); i++) codec_destroy(kind, objs[i]);
+        if (ev_home) (void)hipEventDestroy(ev_home);
+        for (hipEvent_t e : ev_shard)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+// One host thread per involved shard (the per-shard calls wait): f(shard) -> status.  The status of the lowest-numbered failing shard is
+// returned and vidc_last_error carries "shard i: " + that shard's message (the message is thread-local: it is fetched in the worker).
+template <typename F>
+int fan_out(const std::vector<int> &shards, F &&f) {
+    const size_t k = shards.size();
+    std::vector<int> st(k, VIDC_OK);
+    std::vector<std::string> msg(k);
+    auto run = [&](size_t i) {
+        st[i] = f(shards[i]);
+        if (st[i] != VIDC_OK) msg[i] = vidc_last_error();
+    };
+    if (k == 1) {
+        run(0);
+    } else {
+        std::vector<std::thread> th;
+        th.reserve(k);
+        for (size_t i = 0; i < k; i++) th.emplace_back(run, i);
+        for (auto &t : th) t.join();
+    }
+    for (size_t i = 0; i < k; i++)
+        if (st[i] != VIDC_OK) {
+            set_error("shard %d: %s", shards[i], msg[i].c_str());
+            return st[i];
+        }
+    return VIDC_OK;
+}
+
+// waits for the streams of the shards a call touched when the scope is left (an early return must not hand staging back while work on
+// it is in flight); the home stream has its own StreamGuard
+struct ShardStreamsGuard {
+    const vidc_shards *s;
+    std::vector<int> which;
+    explicit ShardStreamsGuard(const vidc_shards *s_) : s(s_) {}
+    ~ShardStreamsGuard() {
+        for (int i : which) {
+            vidc_ctx *c = s->ctxs[(size_t)i];
+            if (hipSetDevice(c->device) == hipSuccess) (void)vidc_stream_wait(c->stream);
+        }
+        (void)hipSetDevice(s->home->device);
+    }
+};
+
+// segments (+ their chunk table) uploaded into scratch of the home context and copied on the home stream.  The host vectors must live
+// until the home stream has been waited for.
+struct StagedCopy {
+    Scratch s_seg, s_chunk;
+    std::vector<CopyChunk> chunks;
+};
+template <bool INV>
+int launch_copy(vidc_ctx *home, const uint64_t *src, uint64_t *dst, const Segment *d_segs, const CopyChunk *d_chunks, uint64_t nchunks) {
+    if (!nchunks) return VIDC_OK;
+    hipLaunchKernelGGL((k_shard_copy<INV>), copy_grid(home, nchunks), dim3(256), 0, home->stream, src, dst, d_segs, d_chunks, nchunks);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+int staged_copy(vidc_ctx *home, const uint64_t *src, uint64_t *dst, const std::vector<Segment> &segs, StagedCopy &sc) {
+    if (segs.empty()) return VIDC_OK;
+    sc.chunks = build_copy_chunks(segs);
+    VIDC_TRY(sc.s_seg.get(home, segs.size() * sizeof(Segment)));
+    VIDC_TRY(sc.s_chunk.get(home, sc.chunks.size() * sizeof(CopyChunk)));
+    VIDC_HIP(hipMemcpyAsync(sc.s_seg.p, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice, home->stream));
+    VIDC_HIP(hipMemcpyAsync(sc.s_chunk.p, sc.chunks.data(), sc.chunks.size() * sizeof(CopyChunk), hipMemcpyHostToDevice, home->stream));
+    return launch_copy<false>(home, src, dst, sc.s_seg.as<Segment>(), sc.s_chunk.as<CopyChunk>(), sc.chunks.size());
+}
+
+int check_request(const vidc_ctx *home, const vidc_shards *s, const char *what) {
+    if (!home || !s) {
+        set_error("%s: NULL context or object", what);
+        return VIDC_ERR_INVALID;
+    }
+    if (home != s->home) {
+        set_error("%s: not the home context the object was built with", what);
+        return VIDC_ERR_INVALID;
+    }
+    return VIDC_OK;
+}
+
+// the argument checks of the two encode calls: before any device work
+int check_encode(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, const uint64_t *offsets, const uint64_t *d_ids, uint64_t nlist,
+                 vidc_shards **out, bool ids_needed) {
+    if (out) *out = nullptr;
+    if (!home || !shard_ctxs || !offsets || !out || (ids_needed && !d_ids)) {
+        set_error("shards encode: NULL argument");
+        return VIDC_ERR_INVALID;
+    }
+    if (nshards < 1 || nshards > VIDC_SHARDS_MAX) {
+        set_error("shards encode: nshards %d outside 1 .. %d", nshards, VIDC_SHARDS_MAX);
+        return VIDC_ERR_INVALID;
+    }
+    for (int i = 0; i < nshards; i++) {
+        if (!shard_ctxs[i]) {
+            set_error("shards encode: shard context %d is NULL", i);
+            return VIDC_ERR_INVALID;
+        }
+        for (int j = 0; j < i; j++)
+            if (shard_ctxs[j] == shard_ctxs[i]) {
+                set_error("shards encode: shard contexts %d and %d are the same context", j, i);
+                return VIDC_ERR_INVALID;
+            }
+    }
+    if (kind < VIDC_KIND_PACKED || kind > VIDC_KIND_WT) {
+        set_error("shards encode: unknown kind %d", kind);
+        return VIDC_ERR_INVALID;
+    }
+    if (kind == VIDC_KIND_WT) {
+        set_error("shards encode: the wavelet tree cannot be sharded (a shard's ids are not a permutation of 0 .. n - 1)");
+        return VIDC_ERR_UNSUPPORTED;
+    }
+    if (nlist >= (1ull << 32)) {
+        set_error("shards encode: nlist must be below 2^32");
+        return VIDC_ERR_INVALID;
+    }
+    return VIDC_OK;
+}
+
+// host offsets (checked: start at 0, monotone) -> the object
+int encode_impl(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, int param, uint32_t flags, uint64_t nlist,
+                const uint64_t *offsets, const uint64_t *d_ids, vidc_shards **out) {
+    if (offsets[0] != 0) {
+        set_error("shards encode: offsets[0] must be 0");
+        return VIDC_ERR_INVALID;
+    }
+    for (uint64_t l = 0; l < nlist; l++)
+        if (offsets[l + 1] < offsets[l]) {
+            set_error("shards encode: offsets decrease at list %llu", (unsigned long long)l);
+            return VIDC_ERR_INVALID;
+        }
+    if (offsets[nlist] && !d_ids) {
+        set_error("shards encode: NULL argument");
+        return VIDC_ERR_INVALID;
+    }
+    std::unique_ptr<vidc_shards> S(new vidc_shards());
+    S->kind = kind;
+    S->flags = flags;
+    S->home = home;
+    S->ctxs.assign(shard_ctxs, shard_ctxs + nshards);
+    S->objs.assign((size_t)nshards, nullptr);
+    S->plan = make_plan(offsets, nlist, nshards);
+    const ShardPlan &P = S->plan;
+    S->param = kind == VIDC_KIND_PACKED && param == 0 ? vidc_packed_bits_for(P.ntotal) : param;  // (one width for every shard)
+    S->ev_shard.assign((size_t)nshards, nullptr);
+    for (int s = 0; s < nshards; s++) {
+        VIDC_HIP(hipSetDevice(S->ctxs[(size_t)s]->device));
+        VIDC_HIP(hipEventCreateWithFlags(&S->ev_shard[(size_t)s], hipEventDisableTiming));
+    }
+    VIDC_HIP(hipSetDevice(home->device));
+    VIDC_HIP(hipEventCreateWithFlags(&S->ev_home, hipEventDisableTiming));
+
+    // the map and the cut tables, on the home device (the host vectors outlive the wait below)
+    std::vector<uint64_t> map(nlist);
+    for (uint64_t l = 0; l < nlist; l++) map[l] = P.packed(l);
+    std::vector<std::vector<CopyChunk>> chunks((size_t)nshards);
+    std::vector<Scratch> cut_home((size_t)nshards), cut_shard((size_t)nshards);  // the shards' contiguous ids
+    std::vector<int> involved;
+    ShardStreamsGuard sguard(S.get());
+    StreamGuard hguard(home);
+    VIDC_TRY(S->d_map.alloc(nlist, home->dpool));
+    if (nlist) VIDC_HIP(hipMemcpyAsync(S->d_map.p, map.data(), nlist * 8, hipMemcpyHostToDevice, home->stream));
+    S->d_cut.resize((size_t)nshards);
+    S->d_cut_chunks.resize((size_t)nshards);
+    S->n_cut_chunks.assign((size_t)nshards, 0);
+    for (int s = 0; s < nshards; s++) {
+        const size_t i = (size_t)s;
+        if (P.lists[i].empty()) continue;
+        involved.push_back(s);
+        chunks[i] = build_copy_chunks(P.cut[i]);
+        S->n_cut_chunks[i] = chunks[i].size();
+        VIDC_TRY(S->d_cut[i].alloc(P.cut[i].size(), home->dpool));
+        VIDC_TRY(S->d_cut_chunks[i].alloc(chunks[i].size(), home->dpool));
+        if (!P.cut[i].empty()) {
+            VIDC_HIP(hipMemcpyAsync(S->d_cut[i].p, P.cut[i].data(), P.cut[i].size() * sizeof(Segment), hipMemcpyHostToDevice, home->stream));
+            VIDC_HIP(hipMemcpyAsync(S->d_cut_chunks[i].p, chunks[i].data(), chunks[i].size() * sizeof(CopyChunk), hipMemcpyHostToDevice, home->stream));
+        }
+        // a shard on the home device: the cut writes the block its encoder reads
+        VIDC_TRY((S->same_device(s) ? cut_shard[i] : cut_home[i]).get(S->same_device(s) ? S->ctxs[i] : home, (P.load[i] ? P.load[i] : 2) * 8));
+    }
+    // the cut: one launch per shard on the home stream; its kernel time is the home context's last_kernel_ms (unless a shard's encode
+    // runs on the home context as well and overwrites it)
+    EventTimer cut_timer(home);
+    VIDC_HIP(cut_timer.start());
+    for (int s : involved) {
+        const size_t i = (size_t)s;
+        uint64_t *dst = (S->same_device(s) ? cut_shard[i] : cut_home[i]).as<uint64_t>();
+        VIDC_TRY(launch_copy<false>(home, d_ids, dst, S->d_cut[i].p, S->d_cut_chunks[i].p, S->n_cut_chunks[i]));
+    }
+    VIDC_HIP(cut_timer.mark());
+    // every shard's encode waits anyway: the cut is waited for here, once, before the shard threads start
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    home->last_kernel_ms = cut_timer.elapsed();
+    hguard.disarm();
+    sguard.which = involved;
+    vidc_shards *Sp = S.get();
+    int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int s) -> int {
+        const size_t i = (size_t)s;
+        vidc_ctx *c = Sp->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        if (!Sp->same_device(s)) {
+            VIDC_TRY(cut_shard[i].get(c, (P.load[i] ? P.load[i] : 2) * 8));
+            if (P.load[i]) VIDC_HIP(hipMemcpyAsync(cut_shard[i].p, cut_home[i].p, P.load[i] * 8, hipMemcpyDefault, c->stream));
+        }
+        VIDC_TRY(codec_encode(kind, c, P.lists[i].size(), P.local_offsets[i].data(), cut_shard[i].as<uint64_t>(), Sp->param, flags, &Sp->objs[i]));
+        VIDC_HIP(vidc_stream_wait(c->stream));
+        return VIDC_OK;
+    });
+    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
+    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
+    *out = S.release();
+    return VIDC_OK;
+}
+
+std::vector<int> shards_with_ids(const vidc_shards *s) {
+    std::vector<int> v;
+    for (int i = 0; i < s->plan.nshards; i++)
+        if (s->objs[(size_t)i] && s->plan.load[(size_t)i]) v.push_back(i);
+    return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vidc_shards_encode(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, int param, uint32_t flags, uint64_t nlist,
+                       const uint64_t *offsets, const uint64_t *d_ids, vidc_shards **out) {
+    VIDC_TRY(check_encode(home, nshards, shard_ctxs, kind, offsets, d_ids, nlist, out, false));
+    return encode_impl(home, nshards, shard_ctxs, kind, param, flags, nlist, offsets, d_ids, out);
+}
+
+int vidc_shards_encode_dev(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, int param, uint32_t flags, uint64_t nlist,
+                           const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids, vidc_shards **out) {
+    VIDC_TRY(check_encode(home, nshards, shard_ctxs, kind, d_offsets, d_ids, nlist, out, ntotal != 0));
+    VIDC_HIP(hipSetDevice(home->device));
+    std::vector<uint64_t> off(nlist + 1);
+    VIDC_HIP(hipMemcpyAsync(off.data(), d_offsets, (nlist + 1) * 8, hipMemcpyDeviceToHost, home->stream));
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    if (off[nlist] != ntotal) {
+        set_error("shards encode: d_offsets[nlist] = %llu, ntotal = %llu", (unsigned long long)off[nlist], (unsigned long long)ntotal);
+        return VIDC_ERR_INVALID;
+    }
+    return encode_impl(home, nshards, shard_ctxs, kind, param, flags, nlist, off.data(), d_ids, out);
+}
+
+void vidc_shards_destroy(vidc_shards *s) { delete s; }
+
+int vidc_shards_count(const vidc_shards *s) { return s ? s->plan.nshards : 0; }
+int vidc_shards_kind(const vidc_shards *s) { return s ? s->kind : -1; }
+uint64_t vidc_shards_nlist(const vidc_shards *s) { return s ? s->plan.nlist : 0; }
+uint64_t vidc_shards_ntotal(const vidc_shards *s) { return s ? s->plan.ntotal : 0; }
+uint64_t vidc_shards_compressed_bytes(const vidc_shards *s) {
+    uint64_t b = 0;
+    if (!s) return 0;
+    // (Elias-Fano reports stream BITS / 8: the shards' bits are summed before the division, so that the figure is the unsharded object's)
+    for (void *o : s->objs)
+        if (o) b += s->kind == VIDC_KIND_EF ? ef_stream_bits((const vidc_ef *)o) : codec_bytes(s->kind, o);
+    return s->kind == VIDC_KIND_EF ? b / 8 : b;
+}
+int vidc_shards_map(const vidc_shards *s, int32_t *owner, uint32_t *local_no) {
+    if (!s) return VIDC_ERR_INVALID;
+    if (owner) std::copy(s->plan.owner.begin(), s->plan.owner.end(), owner);
+    if (local_no) std::copy(s->plan.local_no.begin(), s->plan.local_no.end(), local_no);
+    return VIDC_OK;
+}
+int vidc_shards_offsets(const vidc_shards *s, uint64_t *offsets) {
+    if (!s || !offsets) return VIDC_ERR_INVALID;
+    std::copy(s->plan.offsets.begin(), s->plan.offsets.end(), offsets);
+    return VIDC_OK;
+}
+const void *vidc_shards_shard(const vidc_shards *s, int i) { return s && i >= 0 && i < s->plan.nshards ? s->objs[(size_t)i] : nullptr; }
+vidc_ctx *vidc_shards_shard_ctx(const vidc_shards *s, int i) { return s && i >= 0 && i < s->plan.nshards ? s->ctxs[(size_t)i] : nullptr; }
+
+int vidc_shards_decode_all(vidc_ctx *home, const vidc_shards *s, uint64_t *d_out) {
+    VIDC_TRY(check_request(home, s, "shards decode_all"));
+    const ShardPlan &P = s->plan;
+    if (!P.ntotal) return VIDC_OK;
+    if (!d_out) { set_error("shards decode_all: NULL output"); return VIDC_ERR_INVALID; }
+    const std::vector<int> involved = shards_with_ids(s);
+    std::vector<Scratch> st_shard((size_t)P.nshards), st_home((size_t)P.nshards);
+    ShardStreamsGuard sguard(s);
+    StreamGuard hguard(home, false);
+    sguard.which = involved;
+    // the shards decode concurrently, each into a block of its context's cache (and, from another device, into home staging)
+    VIDC_TRY(fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        VIDC_TRY(st_shard[i].get(c, P.load[i] * 8));
+        VIDC_TRY(codec_decode_all(s->kind, c, s->objs[i], st_shard[i].as<uint64_t>()));
+        if (!s->same_device(sh)) {
+            VIDC_HIP(hipSetDevice(home->device));
+            VIDC_TRY(st_home[i].get(home, P.load[i] * 8));
+            VIDC_HIP(hipSetDevice(c->device));
+            VIDC_HIP(hipMemcpyAsync(st_home[i].p, st_shard[i].p, P.load[i] * 8, hipMemcpyDefault, c->stream));
+        }
+        VIDC_HIP(vidc_stream_wait(c->stream));
+        return VIDC_OK;
+    }));
+    VIDC_HIP(hipSetDevice(home->device));
+    hguard.arm();
+    EventTimer uncut_timer(home);
+    VIDC_HIP(uncut_timer.start());
+    for (int sh : involved) {
+        const size_t i = (size_t)sh;
+        const uint64_t *src = (s->same_device(sh) ? st_shard[i] : st_home[i]).as<uint64_t>();
+        VIDC_TRY(launch_copy<true>(home, src, d_out, s->d_cut[i].p, s->d_cut_chunks[i].p, s->n_cut_chunks[i]));
+    }
+    VIDC_TRY(uncut_timer.finish());  // (the call's wait; last_kernel_ms = the inverse cut)
+    hguard.disarm();
+    return VIDC_OK;
+}
+
+int vidc_shards_decode_lists(vidc_ctx *home, const vidc_shards *s, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,
+                             uint64_t *out_offsets) {
+    VIDC_TRY(check_request(home, s, "shards decode_lists"));
+    if (!m) {
+        if (out_offsets) out_offsets[0] = 0;
+        return VIDC_OK;
+    }
+    if (!list_nos || !out_offsets) { set_error("shards decode_lists: NULL array"); return VIDC_ERR_INVALID; }
+    const ShardPlan &P = s->plan;
+    ListsRoute R;
+    uint64_t bad = 0;
+    if (!route_lists(P, m, list_nos, R, &bad)) {
+        set_error("shards decode_lists: list number %llu (request entry %llu) out of range", (unsigned long long)list_nos[bad], (unsigned long long)bad);
+        return VIDC_ERR_INVALID;
+    }
+    std::copy(R.out_offsets.begin(), R.out_offsets.end(), out_offsets);
+    if (!R.out_offsets[m]) return VIDC_OK;
+    if (!d_out) { set_error("shards decode_lists: NULL output"); return VIDC_ERR_INVALID; }
+    std::vector<int> involved;
+    for (int sh = 0; sh < P.nshards; sh++)
+        if (R.staged[(size_t)sh]) involved.push_back(sh);
+    std::vector<Scratch> st_shard((size_t)P.nshards), st_home((size_t)P.nshards);
+    std::vector<StagedCopy> copies((size_t)P.nshards);
+    ShardStreamsGuard sguard(s);
+    StreamGuard hguard(home, false);
+    sguard.which = involved;
+    VIDC_TRY(fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        VIDC_TRY(st_shard[i].get(c, R.staged[i] * 8));
+        std::vector<uint64_t> off(R.local_lists[i].size() + 1);
+        VIDC_TRY(codec_decode_lists(s->kind, c, s->objs[i], R.local_lists[i].size(), R.local_lists[i].data(), st_shard[i].as<uint64_t>(), off.data()));
+        if (!s->same_device(sh)) {
+            VIDC_HIP(hipSetDevice(home->device));
+            VIDC_TRY(st_home[i].get(home, R.staged[i] * 8));
+            VIDC_HIP(hipSetDevice(c->device));
+            VIDC_HIP(hipMemcpyAsync(st_home[i].p, st_shard[i].p, R.staged[i] * 8, hipMemcpyDefault, c->stream));
+        }
+        VIDC_HIP(vidc_stream_wait(c->stream));
+        return VIDC_OK;
+    }));
+    VIDC_HIP(hipSetDevice(home->device));
+    hguard.arm();
+    for (int sh : involved) {
+        const size_t i = (size_t)sh;
+        const uint64_t *src = (s->same_device(sh) ? st_shard[i] : st_home[i]).as<uint64_t>();
+        VIDC_TRY(staged_copy(home, src, d_out, R.place[i], copies[i]));
+    }
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    hguard.disarm();
+    return VIDC_OK;
+}
+
+int vidc_shards_translate_labels_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                     uint64_t *d_invalid) {
+    VIDC_TRY(check_request(home, s, "shards translate_labels"));
+    if (n && (!d_labels || !d_ids)) { set_error("shards translate_labels: NULL array"); return VIDC_ERR_INVALID; }
+    if (!n) return VIDC_OK;
+    if (n >= (1ull << 32)) { set_error("shards translate_labels: n must be below 2^32"); return VIDC_ERR_INVALID; }
+    const ShardPlan &P = s->plan;
+    const uint32_t ns = (uint32_t)P.nshards;
+    std::vector<int> involved;
+    for (int sh = 0; sh < P.nshards; sh++)
+        if (s->objs[(size_t)sh]) involved.push_back(sh);
+    VIDC_HIP(hipSetDevice(home->device));
+    // home block: shard_invalid[ns] | local[ns * n] | answers[ns * n] | owner[n]
+    Scratch blk;
+    std::vector<Scratch> far((size_t)P.nshards);  // a shard on another device: invalid | labels[n] | answers[n] in its own cache
+    ShardStreamsGuard sguard(s);
+    StreamGuard hguard(home, false);
+    VIDC_TRY(blk.get(home, (size_t)ns * 8 + 2 * (size_t)ns * n * 8 + n));
+    unsigned long long *sh_inv = blk.as<unsigned long long>();
+    int64_t *local = (int64_t *)(sh_inv + ns), *answers = local + (uint64_t)ns * n;
+    uint8_t *owner = (uint8_t *)(answers + (uint64_t)ns * n);
+    hguard.arm();
+    VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
+    hipLaunchKernelGGL(k_shard_route, req_grid(home, n), dim3(256), 0, home->stream, d_labels, n, (const uint64_t *)s->d_map.p, P.nlist, ns, local,
+                       owner, (unsigned long long *)d_invalid);
+    VIDC_HIP(hipGetLastError());
+    sguard.which = involved;
+    auto shard_call = [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        const int64_t *lab = local + (uint64_t)i * n;
+        int64_t *ans = answers + (uint64_t)i * n;
+        uint64_t *inv = (uint64_t *)(sh_inv + i);
+        if (!s->same_device(sh)) {
+            VIDC_TRY(far[i].get(c, 16 + 2 * n * 8));
+            inv = far[i].as<uint64_t>();
+            int64_t *f_lab = (int64_t *)(inv + 2);
+            VIDC_HIP(hipMemsetAsync(inv, 0, 8, c->stream));
+            VIDC_HIP(hipMemcpyAsync(f_lab, lab, n * 8, hipMemcpyDefault, c->stream));
+            lab = f_lab;
+            ans = f_lab + n;
+        }
+        VIDC_TRY(codec_translate(s->kind, c, s->objs[i], n, lab, ans, inv));
+        if (!s->same_device(sh)) {
+            VIDC_HIP(hipMemcpyAsync(answers + (uint64_t)i * n, ans, n * 8, hipMemcpyDefault, c->stream));
+            VIDC_HIP(hipMemcpyAsync(sh_inv + i, inv, 8, hipMemcpyDefault, c->stream));
+        }
+        return VIDC_OK;
+    };
+    if (s->kind == VIDC_KIND_ROC) {
+        // ROC's translate plans on the host and waits: one thread per shard, behind a host wait for the route
+        VIDC_HIP(vidc_stream_wait(home->stream));
+        VIDC_TRY(fan_out(involved, [&](int sh) -> int {
+            VIDC_TRY(shard_call(sh));
+            VIDC_HIP(vidc_stream_wait(s->ctxs[(size_t)sh]->stream));
+            return VIDC_OK;
+        }));
+        VIDC_HIP(hipSetDevice(home->device));
+    } else {
+        // enqueue-only per-shard calls, from this thread: route -> ev_home -> every shard stream -> ev_shard -> the home stream
+        VIDC_HIP(hipEventRecord(s->ev_home, home->stream));
+        for (int sh : involved) {
+            vidc_ctx *c = s->ctxs[(size_t)sh];
+            VIDC_HIP(hipSetDevice(c->device));
+            VIDC_HIP(hipStreamWaitEvent(c->stream, s->ev_home, 0));
+            const int st = shard_call(sh);
+            if (st != VIDC_OK) {
+                const std::string msg = vidc_last_error();
+                set_error("shard %d: %s", sh, msg.c_str());
+                return st;
+            }
+            VIDC_HIP(hipEventRecord(s->ev_shard[(size_t)sh], c->stream));
+        }
+        VIDC_HIP(hipSetDevice(home->device));
+        for (int sh : involved) VIDC_HIP(hipStreamWaitEvent(home->stream, s->ev_shard[(size_t)sh], 0));
+    }
+    hipLaunchKernelGGL(k_shard_join, req_grid(home, n), dim3(256), 0, home->stream, (const int64_t *)answers, (const uint8_t *)owner, n, ns, d_ids,
+                       (const unsigned long long *)sh_inv, (unsigned long long *)d_invalid);
+    VIDC_HIP(hipGetLastError());
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    hguard.disarm();
+    sguard.which.clear();  // (the join waited for every shard stream's event)
+    return VIDC_OK;
+}
+
+int vidc_shards_decode_gather(vidc_ctx *home, const vidc_shards *s, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
+                              const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out) {
+    VIDC_TRY(check_request(home, s, "shards decode_gather"));
+    if (!n_items) return VIDC_OK;
+    if (!m || !list_nos || !item_slot || !item_off || !ids_out) { set_error("shards decode_gather: NULL array or no list"); return VIDC_ERR_INVALID; }
+    const ShardPlan &P = s->plan;
+    GatherRoute R;
+    uint64_t bad = 0;
+    const int rc = route_gather(P, m, list_nos, n_items, item_slot, item_off, R, &bad);
+    if (rc == 1) {
+        set_error("decode_gather: list number %llu out of range", (unsigned long long)list_nos[bad]);
+        return VIDC_ERR_INVALID;
+    }
+    if (rc == 2) {
+        set_error("decode_gather: item %llu = (slot %llu, offset %llu) is outside its list", (unsigned long long)bad,
+                  (unsigned long long)item_slot[bad], (unsigned long long)item_off[bad]);
+        return VIDC_ERR_INVALID;
+    }
+    std::vector<int> involved;
+    for (int sh = 0; sh < P.nshards; sh++)
+        if (!R.item_index[(size_t)sh].empty()) involved.push_back(sh);
+    std::vector<std::vector<int64_t>> got((size_t)P.nshards);
+    ShardStreamsGuard sguard(s);
+    sguard.which = involved;
+    VIDC_TRY(fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        got[i].resize(R.item_index[i].size());
+        return codec_decode_gather(s->kind, c, s->objs[i], R.local_lists[i].size(), R.local_lists[i].data(), R.item_index[i].size(),
+                                   R.item_slot[i].data(), R.item_off[i].data(), got[i].data());
+    }));
+    for (int sh : involved) {
+        const size_t i = (size_t)sh;
+        for (size_t k = 0; k < got[i].size(); k++) ids_out[R.item_index[i][k]] = got[i][k];
+    }
+    return VIDC_OK;
+}
+
+int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host) {
+    VIDC_TRY(check_request(home, s, "shards perm"));
+    const bool has = (s->kind == VIDC_KIND_ROC && (s->flags & VIDC_ROC_WANT_PERM)) || (s->kind == VIDC_KIND_EF && (s->flags & VIDC_EF_WANT_PERM));
+    if (!has) { set_error("shards perm: the object was built without a permutation"); return VIDC_ERR_INVALID; }
+    const ShardPlan &P = s->plan;
+    if (!P.ntotal) return VIDC_OK;
+    if (!perm_host) { set_error("shards perm: NULL output"); return VIDC_ERR_INVALID; }
+    const std::vector<int> involved = shards_with_ids(s);
+    ShardStreamsGuard sguard(s);
+    sguard.which = involved;
+    // a list's entries are positions inside the list: the shards' permutations go to their lists' places unchanged
+    return fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        std::vector<uint32_t> p(P.load[i]);
+        VIDC_TRY(s->kind == VIDC_KIND_ROC ? vidc_roc_perm(c, (const vidc_roc *)s->objs[i], p.data()) : vidc_ef_perm(c, (const vidc_ef *)s->objs[i], p.data()));
+        for (const Segment &sg : P.cut[i]) std::copy(p.begin() + (ptrdiff_t)sg.dst_start, p.begin() + (ptrdiff_t)(sg.dst_start + sg.count), perm_host + sg.src_start);
+        return VIDC_OK;
+    });
+}
+
+}  // extern "C"

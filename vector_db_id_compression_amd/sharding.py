@@ -9,6 +9,10 @@ list -> (rank, local number) map is replicated (nlist * 12 bytes), so message si
 
 Nothing here loops over lists in Python except the LPT assignment (a heap pop per list): shards are cut with index
 arithmetic and the gathered lists land in request order with one indexed copy per owning rank.
+
+`ShardedInvLists` is the multi-process form (one process per GPU, torch.distributed).  `DeviceShards` is the single-process form
+over the C-ABI's vidc_shards: one process drives every context, the cut / placement / label routing are HIP kernels, and no index
+arithmetic happens in Python.  It has been exercised with several contexts on one device; never run on more than one GPU.
 """
 import heapq
 
@@ -147,3 +151,192 @@ class ShardedInvLists:
             sz = torch.from_numpy(sizes[items]).to(self.device)
             out[_segment_index(st, sz, torch)] = buf
         return out, req_off
+
+
+_KINDS = {"packed": 0, "ef": 1, "roc": 2, "wt": 3}
+
+
+class DeviceShards:
+    """vidc_shards: one CSR set of lists cut over several contexts of ONE process (include/vidc.h), with the method names and return
+    shapes of the single-object containers (PackedLists / EfLists / RocLists), so IVFIndex.search_defer_id_decoding takes it as it is.
+
+    Exercised with several contexts on one device; never run on more than one GPU."""
+
+    def __init__(self, handle, home, ctxs, kind):
+        self.h, self.ctx, self.ctxs, self.kind = handle, home, list(ctxs), kind
+        self._offsets = self._owner = self._local_no = None
+
+    def __del__(self):
+        try:  # may run during interpreter shutdown, after module globals are gone
+            if getattr(self, "h", None):
+                from ._lib import lib
+
+                lib().vidc_shards_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @classmethod
+    def encode(cls, kind, offsets, ids, devices=None, ctxs=None, nshards=None, home=None, **codec_args):
+        """kind: "packed" / "ef" / "roc".  Contexts: `ctxs` (a list of _lib.Context, kept alive by the object), or one new context per
+        entry of `devices` (device numbers, repeats allowed), or `nshards` new contexts on the current device.  home: the context whose
+        device holds `ids` and every request's arrays (default: the current device's default context).  codec_args: bits (packed),
+        want_perm (ef, roc), precision_mode (roc).  offsets: host array, or an int64 / uint64 CUDA tensor on the home device."""
+        import ctypes as C
+
+        from . import _lib, codecs
+
+        k = _KINDS[kind] if isinstance(kind, str) else int(kind)
+        home = _lib.default_context() if home is None else home
+        if ctxs is None:
+            if devices is None:
+                import torch
+
+                devices = [torch.cuda.current_device()] * int(1 if nshards is None else nshards)
+            ctxs = [_lib.Context(int(d)) for d in devices]
+        ctxs = list(ctxs)
+        param, flags = 0, 0
+        if k == 0:
+            param = int(codec_args.pop("bits", None) or 0)
+        elif k == 1:
+            flags = _lib.VIDC_EF_WANT_PERM if codec_args.pop("want_perm", False) else 0
+        elif k == 2:
+            param = int(codec_args.pop("precision_mode", _lib.VIDC_PREC_REFERENCE))
+            flags = _lib.VIDC_ROC_WANT_PERM if codec_args.pop("want_perm", False) else 0
+        if codec_args:
+            raise TypeError(f"unknown codec arguments for {kind}: {sorted(codec_args)}")
+        arr = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
+        h = C.c_void_p()
+        d_off = codecs._cuda_offsets(offsets, home)
+        if d_off is not None:
+            d_ids = codecs._dev_ids_dev(ids, d_off)
+            _lib.check(_lib.lib().vidc_shards_encode_dev(home.h, len(ctxs), arr, k, param, flags, d_off.numel() - 1, _lib.ptr(d_off),
+                                                         d_ids.numel(), _lib.ptr(d_ids) if d_ids.numel() else None, C.byref(h)))
+            obj = cls(h, home, ctxs, k)
+        else:
+            off = codecs._as_offsets(offsets)
+            d_ids = codecs._dev_ids(ids, int(off[-1])) if off[-1] else None
+            _lib.check(_lib.lib().vidc_shards_encode(home.h, len(ctxs), arr, k, param, flags, off.size - 1, _lib.ptr(off), _lib.ptr(d_ids),
+                                                     C.byref(h)))
+            obj = cls(h, home, ctxs, k)
+            obj._offsets = off
+        return obj
+
+    # -- host-side accessors
+    @property
+    def nshards(self):
+        from ._lib import lib
+
+        return int(lib().vidc_shards_count(self.h))
+
+    @property
+    def nlist(self):
+        from ._lib import lib
+
+        return int(lib().vidc_shards_nlist(self.h))
+
+    @property
+    def ntotal(self):
+        from ._lib import lib
+
+        return int(lib().vidc_shards_ntotal(self.h))
+
+    @property
+    def compressed_bytes(self):
+        from ._lib import lib
+
+        return int(lib().vidc_shards_compressed_bytes(self.h))
+
+    @property
+    def offsets(self):
+        if self._offsets is None:
+            from ._lib import check, lib, ptr
+
+            off = np.zeros(self.nlist + 1, np.uint64)
+            check(lib().vidc_shards_offsets(self.h, ptr(off)))
+            self._offsets = off
+        return self._offsets
+
+    def _map(self):
+        if self._owner is None:
+            from ._lib import check, lib, ptr
+
+            owner, local = np.zeros(max(self.nlist, 1), np.int32), np.zeros(max(self.nlist, 1), np.uint32)
+            check(lib().vidc_shards_map(self.h, ptr(owner), ptr(local)))
+            self._owner, self._local_no = owner[: self.nlist], local[: self.nlist]
+        return self._owner, self._local_no
+
+    @property
+    def owner(self):
+        """int32[nlist]: the shard of every list (== lpt_partition(sizes, nshards))"""
+        return self._map()[0]
+
+    @property
+    def local_no(self):
+        """uint32[nlist]: a list's number inside its shard"""
+        return self._map()[1]
+
+    def shard(self, i):
+        """Shard i as a borrowed PackedLists / EfLists / RocLists view (None for a shard without lists): the view never destroys the
+        handle and keeps this object alive."""
+        from . import _lib, codecs
+
+        h = _lib.lib().vidc_shards_shard(self.h, int(i))
+        if not h:
+            return None
+        base = (codecs.PackedLists, codecs.EfLists, codecs.RocLists)[self.kind]
+        view_cls = type("Borrowed" + base.__name__, (base,), {"__del__": lambda self: None})
+        mine = self.owner == int(i)
+        sizes = (self.offsets[1:] - self.offsets[:-1])[mine]
+        view = view_cls(_lib._vp(h), self.ctxs[int(i)], np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]).astype(np.uint64))
+        view._shards = self
+        return view
+
+    # -- requests (home context; arrays on the home device)
+    def decode_all(self, out=None):
+        import torch
+
+        from . import codecs
+        from ._lib import check, lib, ptr
+
+        if out is None:
+            out = torch.empty(max(self.ntotal, 1), dtype=torch.int64, device="cuda")
+        codecs._on_torch_stream(self.ctx)
+        check(lib().vidc_shards_decode_all(self.ctx.h, self.h, ptr(out)))
+        return out[: self.ntotal]
+
+    def decode_lists(self, list_nos):
+        """-> (int64 CUDA tensor: the requested lists back to back, request order and repeats kept; offsets uint64[m + 1])"""
+        import torch
+
+        from . import codecs
+        from ._lib import check, lib, ptr
+
+        ln = np.ascontiguousarray(list_nos, dtype=np.uint64)
+        ok = ln[ln < self.nlist].astype(np.int64)
+        total = int((self.offsets[1:] - self.offsets[:-1])[ok].sum()) if ok.size else 0
+        out = torch.empty(max(total, 1), dtype=torch.int64, device="cuda")
+        out_off = np.zeros(ln.size + 1, np.uint64)
+        codecs._on_torch_stream(self.ctx)
+        check(lib().vidc_shards_decode_lists(self.ctx.h, self.h, ln.size, ptr(ln), ptr(out), ptr(out_off)))
+        return out[:total], out_off
+
+    def decode_gather(self, list_nos, item_slot, item_off):
+        from . import codecs
+        from ._lib import lib
+
+        return codecs._decode_gather(lib().vidc_shards_decode_gather, self, list_nos, item_slot, item_off)
+
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels (int64 CUDA tensor, list_no << 32 | offset) -> ids, on the device; `out` may be `labels`.  Waits for its join."""
+        from . import codecs
+        from ._lib import lib
+
+        return codecs._translate_labels(lib().vidc_shards_translate_labels_dev, self, labels, out, invalid)
+
+    def perm(self):
+        from ._lib import check, lib, ptr
+
+        p = np.zeros(max(self.ntotal, 1), np.uint32)
+        check(lib().vidc_shards_perm(self.ctx.h, self.h, ptr(p)))
+        return p[: self.ntotal]
