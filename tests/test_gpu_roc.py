@@ -873,3 +873,33 @@ def test_lane_quad_decoder_matches_bucket_decoder(roc, oracle, force_lane, monke
         got = got.cpu().numpy().view(np.uint64)
         for k, l in enumerate(sub):
             assert np.array_equal(got[int(goff[k]):int(goff[k + 1])], dec[int(off[l]):int(off[l + 1])])
+
+
+def test_by_length_and_per_list_classification_agree(roc, oracle, monkeypatch):
+    """A call without a list long enough for the bitmap kernels classifies by length alone; VIDC_NO_LENGTH_CLASSES=1 sends it
+    through the per-list loop.  Lengths on both sides of every class boundary up to 4096 ids, in shuffled order: both routes give
+    the oracle's streams under the automatic policy, the lane-per-list kernels and the row-per-list kernels."""
+    rng = np.random.default_rng(160)
+    sizes = np.repeat([0, 1, 64, 65, 256, 257, 1024, 1025, 2048, 2049, 4096], [64, 64, 72, 64, 10, 10, 2, 2, 1, 1, 1])
+    rng.shuffle(sizes)  # 291 lists, 26 253 ids
+    off, ids, lists = _random_lists(rng, sizes, nbits=22)
+    want = [oracle.roc_encode(li, oracle.list_precision(li)) if li.size else None for li in lists]
+    for hook in (None, "VIDC_FORCE_LANE", "VIDC_FORCE_GRP"):
+        got = {}
+        for per_list in ("0", "1"):
+            with monkeypatch.context() as m:
+                if hook:
+                    m.setenv(hook, "1")
+                m.setenv("VIDC_NO_LENGTH_CLASSES", per_list)
+                r = roc.encode(off, ids)
+            info = r.info()
+            got[per_list] = (info["heads"].copy(), info["nwords"].copy(), r.all_words().copy())
+            for l, e in enumerate(want):
+                if e is None:
+                    assert info["nwords"][l] == 0, (hook, per_list, l)
+                    continue
+                assert int(info["heads"][l]) == e["head"], (hook, per_list, l)
+                assert int(info["nwords"][l]) == len(e["words"]), (hook, per_list, l)
+                assert np.array_equal(r.words(l, int(info["nwords"][l])), e["words"]), (hook, per_list, l)
+        for a, b in zip(got["0"], got["1"]):
+            assert np.array_equal(a, b), hook

@@ -12,6 +12,7 @@
 #include "append.h"
 #include "common.h"
 #include "host_call.h"
+#include "roc_enc_plan.h"
 #include "roc_kernels.h"
 #include "roc_u.h"
 #include "roc_u2.h"
@@ -85,17 +86,11 @@ static_assert(VIDC_LANE_MAX64 == VIDC_LANE_TAB, "divisor table size");
 // VIDC_FORCE_LANE=1 (always); both families produce the same bits.
 constexpr uint64_t R2_MIN_LIST = 256;   // shorter lists: the general kernel (the chain kernel's set-up -- 32 KiB bitmap, counters -- is ~10 us)
 constexpr uint64_t LANE_MIN_LISTS = 8192, LANE_MIN_LISTS64 = 8192, LANE_MIN_TINY = 2048;  // 64: lists of 1025..4096 ids
-enum LanePolicy { LANE_NEVER = 0, LANE_AUTO = 1, LANE_ALWAYS = 2 };
-inline LanePolicy lane_policy() {
-    const char *e = getenv("VIDC_NO_LANE");
-    if (e && e[0] == '1') return LANE_NEVER;
-    e = getenv("VIDC_FORCE_LANE");
-    if (e && e[0] == '1') return LANE_ALWAYS;
-    return LANE_AUTO;
+inline bool env_1(const char *name) {  // starts with '1'
+    const char *e = getenv(name);
+    return e && e[0] == '1';
 }
-inline bool lane_wanted(LanePolicy p, uint64_t nlists, uint64_t min_lists) {
-    return p == LANE_ALWAYS || (p == LANE_AUTO && nlists >= min_lists);
-}
+inline LanePolicy lane_policy() { return env_1("VIDC_NO_LANE") ? LANE_NEVER : env_1("VIDC_FORCE_LANE") ? LANE_ALWAYS : LANE_AUTO; }
 
 inline bool env_on(const char *name) {  // set, not empty, not "0"
     const char *e = std::getenv(name);
@@ -107,7 +102,6 @@ inline bool env_on(const char *name) {  // set, not empty, not "0"
 // lists than the wave-per-list kernels keep resident.  Test hooks: VIDC_NO_GRP=1 (never), VIDC_FORCE_GRP=1 (every list
 // of 65 .. 131 072 ids).
 constexpr uint64_t GRP_MIN_LISTS = 8192;
-struct GrpPolicy { uint64_t min_lists, min_n, max_n, dec_max_n, dec_min_n; };
 inline GrpPolicy grp_policy() {
     // (lists beyond 32 768 ids are chains of >= 40 ms at this family's 1.2 us per step: they keep the lower-latency
     // wave-per-list kernels unless VIDC_FORCE_GRP says otherwise)
@@ -130,16 +124,10 @@ inline uint32_t lane_lists_per_wave(const vidc_ctx *, uint32_t, uint32_t) {
     static const int forced = [] { const char *e = std::getenv("VIDC_LPW"); return e ? std::atoi(e) : 0; }();
     return (forced == 8 || forced == 16 || forced == 32) ? (uint32_t)forced : 64u;
 }
-inline bool old_u_kernels() {
-    const char *e = getenv("VIDC_OLD_U");
-    return e && e[0] == '1';
-}
+inline bool old_u_kernels() { return env_1("VIDC_OLD_U"); }
 
 // test hook: VIDC_FORCE_GENERAL=1 routes every list through the general (sorted-position / bucket) kernels
-inline bool force_general() {
-    const char *e = getenv("VIDC_FORCE_GENERAL");
-    return e && e[0] == '1';
-}
+inline bool force_general() { return env_1("VIDC_FORCE_GENERAL"); }
 
 // kernels that ask for more than 64 KiB of dynamic LDS must opt in
 inline int set_big_lds(const void *fn, size_t bytes) {
@@ -466,6 +454,627 @@ namespace {
 std::shared_ptr<DecPlanCache> plan_ahead_build(const vidc_roc *r, bool wide);
 constexpr uint64_t PLAN_AHEAD_MIN_LISTS = 4096;
 
+static_assert(VIDC_PF_UNSORTED == ENC_PF_UNSORTED && VIDC_PF_DOMAIN == ENC_PF_DOMAIN && VIDC_OK == 0, "roc_enc_plan.h mirrors these");
+constexpr EncLimits ENC_LIMITS{TINY_MAX, VIDC_LANE_MAX, VIDC_LANE_MAX64, VIDC_GRP_LEV2_MAX, U_MIN_LIST, R2_MIN_LIST, VIDC_ROC_MAX_LIST,
+                               LANE_MIN_LISTS, LANE_MIN_LISTS64, LANE_MIN_TINY};
+// Every kernel class of a call is one entry of its launch list: its name, its default stream (0 = the caller's, i = auxiliary i - 1)
+// and its launch.  Default streams / order = the schedule measured best (comments at the entries); VIDC_ENC_SCHED (measurements)
+// replaces it (grammar: roc_enc_plan.h); names: U20 R2 C3 G3.<k> G2.<k> (octaves of the row-per-list classes, longest first) C2 U18
+// C1 L64 L32 L16 L4 TINY.  Launches the string does not name keep their default stream and go out last.
+struct EncLaunch { std::string name; int def_stream; std::function<int(hipStream_t)> fn; };
+// One encode call: the object under construction, the call's scratch and staging blocks, its work lists, and what one stage of
+// encode_impl leaves for the next.  (destroyed last member first: the guard ahead of the blocks it protects, the object last)
+struct EncodeCall {
+    vidc_ctx *ctx;
+    uint64_t nlist; const uint64_t *offsets, *d_ids; bool rows; uint32_t K; const int32_t *d_rows; int precision_mode;  // the call's arguments
+    std::unique_ptr<vidc_roc> r{new vidc_roc()};
+    double kernel_ms = 0;
+    HostTrace tr{"roc encode"};
+    EncPolicy pol; EncUse use; EncWorkLists w;
+    uint64_t ntotal_in = 0, max_n = 0, n_tiny_lists = 0, n_mid_lists = 0, arena_words = 0, nonempty = 0, ntiny = 0;
+    bool any_big = false, all_desc = false, light_prepass = false, pre_deferred = false, plan_on_device = false;
+    const uint32_t *maxid = nullptr, *pflags = nullptr;  // prepass results on the host (null: none, or read back later)
+    uint32_t arena_stride = 0;
+    Scratch s_arena, s_status, s_sizes, s_sid, s_wl, s_maxid, s_flags;
+    EncodeTail tail;  // status summary + sizes of the call, queued behind the encode kernels
+    Pinned h_wl, h_pre, h_off, h_plan;
+    // an early return while the offsets upload / the deferred prepass copy is in flight must not release their staging blocks
+    // (declared behind them: destroyed first; armed where such a copy is enqueued)
+    StreamGuard pre_guard{ctx, false};
+    const uint32_t *d_wl = nullptr;
+    RocEncArgs a{};
+    int enc_prio = 0;
+    std::vector<EncLaunch> L;
+    uint32_t aux_used = 0;  // auxiliary streams that have joined the call
+    std::vector<uint32_t> pend;  // lists the first pass handed back for the sorting pass
+    const std::vector<uint32_t> &wl(int cls) const { return w.wl[cls]; }
+    uint64_t len(uint32_t l) const { return r->offsets[l + 1] - r->offsets[l]; }
+};
+
+// policies of the call, persistent outputs; graph rows: everything the offsets stages would find out
+int enc_begin(EncodeCall &c, uint64_t N, uint32_t flags) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    r->device = ctx->device; r->rows = c.rows; r->K = c.K; r->nlist = c.nlist;
+    c.pol.want_perm = (flags & VIDC_ROC_WANT_PERM) && !c.rows;
+    c.ntotal_in = c.rows ? N * c.K : (c.nlist ? c.offsets[c.nlist] : 0);
+    c.pol.f_general = force_general();  // getenv once, not per list
+    c.pol.lpol = c.pol.f_general ? LANE_NEVER : lane_policy();
+    c.pol.gpol = grp_policy(); c.pol.wide = ctx->wide; c.pol.num_cu = ctx->num_cu;
+    VIDC_TRY(r->d_heads.alloc(c.nlist, ctx->dpool)); VIDC_TRY(r->d_prec.alloc(c.nlist, ctx->dpool));
+    VIDC_TRY(r->d_nwords.alloc(c.nlist, ctx->dpool)); VIDC_TRY(r->d_draws.alloc(c.nlist, ctx->dpool));
+    if (c.pol.want_perm) VIDC_TRY(r->d_perm.alloc(c.ntotal_in ? c.ntotal_in : 1, ctx->dpool));
+    c.tr.mark("persistent allocs");
+    // (graph rows: slots of whole 64-byte sectors -- a row's ~100 bytes of stream then lie in two sectors, not in two and a half)
+    c.arena_stride = c.rows ? (uint32_t)((arena_words_for(c.K) + 15u) & ~15ull) : 0u;
+    if (!c.rows) return VIDC_OK;
+    // graph rows: every row is a tiny list, in order -- no offsets, no prepass, no work list array (kernels take l = work item)
+    if (c.K == 0 || c.K > TINY_MAX) { set_error("graph rows: K=%u unsupported (1..64)", c.K); return VIDC_ERR_UNSUPPORTED; }
+    c.arena_words = roc_arena_at(nullptr, c.arena_stride, c.nlist);
+    c.ntiny = c.nlist;
+    c.use.lane_tiny = lane_wanted(c.pol.lpol, c.nlist, LANE_MIN_TINY);
+    return c.s_sizes.get(c.ctx, c.nlist * 4);
+}
+
+// the offsets: the object's host copy, validation, longest list, non-empty lists, the class sizes the policies look at, staging, upload
+int enc_scan_offsets(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    const uint64_t nlist = c.nlist, *offsets = c.offsets;
+    if (!offsets) return VIDC_ERR_INVALID;
+    // the object's host copy of the offsets: on a helper thread for calls of 10^5 lists and more (8 MB at 10^6 lists: 0.6 ms
+    // of the 1.3 ms this phase took on S2), next to the validation pass and the staging copy below; joined before the
+    // classification, the first reader
+    std::thread offsets_copy;
+    struct JoinOnExit { std::thread &t; ~JoinOnExit() { if (t.joinable()) t.join(); } } offsets_copy_guard{offsets_copy};
+    r->offsets = vec_pool<uint64_t>().take(nlist + 1);
+    if (par_parts(nlist) > 1) offsets_copy = std::thread([&] { r->offsets.assign(offsets, offsets + nlist + 1); });
+    else r->offsets.assign(offsets, offsets + nlist + 1);
+    r->offsets_host = true;
+    c.tr.mark("offsets: object's copy");
+    // (no synchronisation of its own for the upload below: the staging block lives until the call returns; an early error return
+    // before the call's first wait synchronises through the guard)
+    VIDC_TRY(c.h_off.get(ctx, (nlist + 1) * 8));
+    const unsigned parts = par_parts(nlist);
+    const GrpPolicy &gpol = c.pol.gpol;
+    // (first the cheap facts -- extremes, order, validity as ONE flag --; the class sizes only need their own pass when the
+    // lengths straddle a class boundary: an index of equal-sized lists, or a graph, is classified by its extremes)
+    std::vector<EncCounts> acc(parts);
+    par_ranges(nlist, parts, [&](uint64_t la, uint64_t lb, unsigned t) {
+        // (threaded calls count the classes in the same pass: every pass costs a round of thread starts)
+        if (parts > 1) { acc[t] = count_classes(offsets, la, lb, gpol, ENC_LIMITS); return; }
+        // (one thread: the staging copy for the upload rides along; four lists per instruction where the host can)
+        OffsetsPass op;
+        offsets_pass(offsets + la, lb - la, c.h_off.as<uint64_t>() + la, op);
+        acc[t].bad = op.bad; acc[t].nonempty = op.nonempty; acc[t].max_n = op.max_n; acc[t].min_n = op.min_n; c.all_desc = op.desc;
+    });
+    EncCounts all;
+    for (unsigned t = 0; t < parts; t++) all.add(acc[t]);
+    if (all.bad)  // the first offending list, as a single pass would report it
+        for (uint64_t l = 0; l < nlist; l++) {
+            if (offsets[l + 1] < offsets[l]) { set_error("offsets not monotone at list %llu", (unsigned long long)l); return VIDC_ERR_INVALID; }
+            if (offsets[l + 1] - offsets[l] > VIDC_ROC_MAX_LIST) {
+                set_error("list %llu has %llu ids; ROC lists are limited to %u (the reference codec is only lossless up to 65536, SURVEY 8a-Q2)",
+                          (unsigned long long)l, (unsigned long long)(offsets[l + 1] - offsets[l]), VIDC_ROC_MAX_LIST);
+                return VIDC_ERR_DOMAIN;
+            }
+        }
+    const uint64_t max_n = c.max_n = all.max_n, min_n = all.min_n;
+    c.nonempty = all.nonempty;
+    uint64_t n_mid64_lists = 0, n_grp_lists = 0;
+    auto in_one = [&](uint64_t lo, uint64_t hi) { return nlist && min_n >= lo && max_n <= hi; };
+    if (parts > 1) {
+        c.n_tiny_lists = all.c0; c.n_mid_lists = all.c1; n_mid64_lists = all.c2; n_grp_lists = all.cg;
+    } else {
+        const bool one_class = in_one(0, TINY_MAX) || in_one(TINY_MAX + 1, VIDC_LANE_MAX) || in_one(VIDC_LANE_MAX + 1, VIDC_LANE_MAX64) || (nlist && min_n > VIDC_LANE_MAX64);
+        const bool grp_reach = max_n >= gpol.min_n && min_n <= gpol.max_n;  // (lists in reach of the row-per-list kernels)
+        const EncCounts x = (!one_class || grp_reach) ? count_classes(offsets, 0, nlist, gpol, ENC_LIMITS) : EncCounts();
+        if (one_class) {
+            c.n_tiny_lists = max_n <= TINY_MAX ? nlist : 0;
+            c.n_mid_lists = in_one(TINY_MAX + 1, VIDC_LANE_MAX) ? nlist : 0;
+            n_mid64_lists = in_one(VIDC_LANE_MAX + 1, VIDC_LANE_MAX64) ? nlist : 0;
+        } else {
+            c.n_tiny_lists = x.c0; c.n_mid_lists = x.c1; n_mid64_lists = x.c2;
+        }
+        if (grp_reach) n_grp_lists = x.cg;
+    }
+    c.any_big = max_n > TINY_MAX;
+    c.tr.mark("offsets: pass + staging");
+    c.arena_words = roc_arena_at(offsets, 0, nlist);
+    r->ntotal = offsets[nlist];
+    VIDC_TRY(r->d_offsets.alloc(nlist + 1, ctx->dpool));
+    if (parts > 1 || nlist == 0)  // (a single-threaded pass above has copied them already)
+        par_ranges(nlist + 1, parts, [&](uint64_t a0, uint64_t b0, unsigned) {
+            std::memcpy(c.h_off.as<uint64_t>() + a0, offsets + a0, (b0 - a0) * 8);
+        });
+    if (offsets_copy.joinable()) offsets_copy.join();
+    c.tr.mark("offsets: blocks");
+    VIDC_HIP(hipMemcpyAsync(r->d_offsets.p, c.h_off.p, (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    c.pre_guard.arm();
+    c.tr.mark("offsets: upload call");
+    c.use = enc_families(c.n_tiny_lists, c.n_mid_lists, n_mid64_lists, n_grp_lists, c.pol, ENC_LIMITS);
+    return VIDC_OK;
+}
+
+// classification prepass (one workgroup per list): max id -> precision, sortedness, domain
+int enc_prepass(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    const uint64_t nlist = c.nlist;
+    if (!c.any_big) { r->prec.assign(nlist, 0); return VIDC_OK; }  // tiny lists only: the planner does not look at their precision
+    VIDC_TRY(c.s_maxid.get(ctx, nlist * 4)); VIDC_TRY(c.s_flags.get(ctx, nlist * 4)); VIDC_TRY(c.h_pre.get(ctx, nlist * 8));
+    EventTimer t = EventTimer::started(ctx);
+    // Every kernel that takes a list streams it anyway and checks what the full prepass would (ids inside
+    // [0, 2^31), ascending order where it matters, ids that fit the precision; the lane-per-list encoders since
+    // round 3: each sampled id against its left neighbour): the prepass only looks at the LAST id of each list -- the maximum of an ascending
+    // list -- instead of re-reading all of them (8 bytes per id).  A list that turns out not to be ascending
+    // comes back with VIDC_ST_PENDING_SORT and takes the sorting second pass like a multiset does.
+    c.light_prepass = !old_u_kernels() && !std::getenv("VIDC_FULL_PREPASS");
+    // No list long enough for the bitmap kernels (the only classes chosen by the width of a list's ids): the host
+    // classifies by length alone and reads the maxima back when it needs them -- for the decode plan, while the
+    // encode kernels run -- instead of waiting for the prepass here (0.1 ms per call at 65 536 lists).  A last id
+    // outside the domain is then reported by the kernel that takes the list, like one in the middle of a list.
+    c.pre_deferred = c.light_prepass && c.max_n < U_MIN_LIST;
+    auto prepass_last = [&] {
+        hipLaunchKernelGGL(k_roc_prepass_last, dim3((uint32_t)((nlist + 255) / 256)), dim3(256), 0, ctx->stream, c.d_ids,
+                           r->d_offsets.p, (uint32_t)nlist, c.precision_mode, c.s_maxid.as<uint32_t>(), c.s_flags.as<uint32_t>(), r->d_prec.p);
+    };
+    r->prec = vec_pool<uint32_t>().take(nlist); r->prec.resize(nlist);
+    if (c.pre_deferred) {
+        VIDC_HIP(hipEventRecord(ctx->ev_pre[0], ctx->stream));
+        prepass_last();
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipEventRecord(ctx->ev_pre[1], ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(c.h_pre.p, c.s_maxid.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipEventRecord(ctx->ev_pre[2], ctx->stream));
+        c.pre_guard.arm();
+        c.tr.mark("prepass kernel (read back later)");
+        return VIDC_OK;
+    }
+    if (c.light_prepass) prepass_last();
+    else
+        hipLaunchKernelGGL(k_roc_prepass, dim3((uint32_t)std::min<uint64_t>(nlist, (uint64_t)ctx->num_cu * 32)), dim3(256), 0, ctx->stream, c.d_ids,
+                           r->d_offsets.p, (uint32_t)nlist, c.precision_mode, c.s_maxid.as<uint32_t>(), c.s_flags.as<uint32_t>(), r->d_prec.p);
+    VIDC_HIP(hipGetLastError());
+    (void)t.mark();
+    VIDC_HIP(hipMemcpyAsync(c.h_pre.p, c.s_maxid.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(hipMemcpyAsync(c.h_pre.as<uint32_t>() + nlist, c.s_flags.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    c.pre_guard.disarm();
+    c.kernel_ms += t.elapsed();
+    c.maxid = c.h_pre.as<uint32_t>();
+    c.pflags = c.maxid + nlist;
+    c.tr.mark("prepass kernel + d2h");
+    // what the decode planner needs later (kernel class, bucket geometry) is known right here
+    // (the precisions are filled in by the classification: one pass over the lists instead of two)
+    r->umax = vec_pool<uint32_t>().take(nlist); r->umax.assign(c.maxid, c.maxid + nlist);
+    return VIDC_OK;
+}
+
+// every list into the work list of its kernel class, every class longest first, the longest chains to the position-bitmap kernel
+int enc_classify(EncodeCall &c) {
+    vidc_roc *r = c.r.get();
+    const uint64_t nlist = c.nlist; const unsigned parts = par_parts(nlist);
+    // (the switch is read where it always was: only by a call that could take the by-length route)
+    if (!c.maxid && !c.pflags && parts == 1 && !c.pol.f_general && !(c.pol.no_length_classes = env_on("VIDC_NO_LENGTH_CLASSES"))) {
+        // (the precisions are filled in when the prepass has been read back; tiny-only calls have set them)
+        std::vector<uint32_t> order = vec_pool<uint32_t>().take(nlist);
+        classify_by_length(c.offsets, nlist, c.max_n, c.all_desc, c.use, c.pol, ENC_LIMITS, c.w, order);
+        r->order_desc.swap(order);
+        r->order_max_n = c.max_n;
+    } else {
+        auto par = [](uint64_t n, unsigned np, auto &&f) { par_ranges(n, np, f); };
+        const int64_t bad = classify_per_list(c.offsets, nlist, c.maxid, c.pflags, c.precision_mode, c.use, c.pol, ENC_LIMITS, c.n_tiny_lists,
+                                              c.use.lane ? c.n_mid_lists : 0, parts, par, r->prec.data(), c.w);
+        if (bad >= 0) {
+            set_error("roc encode: list %llu holds an id outside [0, 2^31) (reference: int max_id, custom_invlists_impl.cpp:163)", (unsigned long long)bad);
+            return VIDC_ERR_DOMAIN;
+        }
+    }
+    c.ntiny = c.w.wl[W_TINY].size();
+    c.tr.mark("classify");
+    if (parts > 1) {  // one thread per class (independent vectors, read-only offsets)
+        std::vector<std::thread> th;
+        for (int k = W_U20; k < W_COUNT; k++)
+            if (c.w.wl[k].size() > 1) th.emplace_back([&c, r, k] { sort_desc(c.w.wl[k], r->offsets); });
+        sort_desc(c.w.wl[W_U18], r->offsets);
+        for (auto &x : th) x.join();
+    } else {
+        for (int k = W_U18; k < W_COUNT; k++)
+            if (!c.w.sorted[k]) sort_desc(c.w.wl[k], r->offsets);
+    }
+    c.pol.old_u = !c.pol.f_general && old_u_kernels(); c.pol.no_r2 = !c.pol.f_general && !c.pol.old_u && env_on("VIDC_NO_R2");  // (short-circuit, as ever)
+    promote_r2(c.w, r->offsets.data(), c.pol, ENC_LIMITS);
+    c.tr.mark("sort work lists");
+    return VIDC_OK;
+}
+
+// arena, status array, tail state; the work lists in one block, class after class (EncClass order); the kernels' arguments
+int enc_upload_worklists(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    VIDC_TRY(c.s_arena.get(ctx, c.arena_words * 4));
+    VIDC_TRY(c.s_status.get(ctx, c.nlist * 4));
+    if (c.nlist) VIDC_HIP(hipMemsetAsync(c.s_status.p, 0xff, c.nlist * 4, ctx->stream));
+    VIDC_TRY(finish_prepare(ctx, r, c.tail));
+    if (!c.rows) {
+        const size_t total = c.w.total();
+        VIDC_TRY(c.h_wl.get(ctx, total * 4));
+        size_t k = 0;
+        for (const std::vector<uint32_t> &v : c.w.wl) {
+            if (!v.empty()) std::memcpy(c.h_wl.as<uint32_t>() + k, v.data(), v.size() * 4);
+            k += v.size();
+        }
+        VIDC_TRY(c.s_wl.get(ctx, total * 4));
+        if (total) VIDC_HIP(hipMemcpyAsync(c.s_wl.p, c.h_wl.p, total * 4, hipMemcpyHostToDevice, ctx->stream));
+        c.d_wl = c.s_wl.as<uint32_t>();
+    }
+    RocEncArgs &a = c.a;
+    a.ids = c.d_ids; a.rows = c.d_rows; a.K = c.K;
+    a.offsets = c.rows ? nullptr : r->d_offsets.p; a.precision_mode = c.precision_mode;
+    a.heads = r->d_heads.p; a.prec = r->d_prec.p; a.nwords = r->d_nwords.p; a.draws = r->d_draws.p;
+    a.sizes = c.s_sizes.as<uint32_t>(); a.status = c.s_status.as<uint32_t>();
+    a.arena = c.s_arena.as<uint32_t>(); a.arena_stride = c.arena_stride;
+    a.perm = c.pol.want_perm ? r->d_perm.p : nullptr;
+    a.sid = c.s_sid.as<uint32_t>(); a.spos = nullptr; a.skey = nullptr; a.skey_off = nullptr; a.mt = ctx->d_mt;
+    // VIDC_ENC_PRIO=<mask>: s_setprio 3 for the general wave-per-list class (1), the 64- / 32-word lane classes (2), the
+    // position-bitmap chains (4).  Default 2: the few wavefronts of the 2049..4096-id lane classes run 4096 steps ahead of the other
+    // lane launches of their stream, and a step of theirs takes 9.5 us next to the chain classes (2.3 alone); first in their SIMD's
+    // arbitration the S2 encode is 53.5-53.9 instead of 54.7-55.6 ms (interleaved, profiles/r05v_s2_ab_enc_prio.txt; the other
+    // classes: no effect)
+    c.enc_prio = [] { const char *e = std::getenv("VIDC_ENC_PRIO"); return e ? std::atoi(e) : 2; }();
+    c.tr.mark("alloc + upload");
+    return VIDC_OK;
+}
+
+// ---- the launches, one small function per kernel family (in this order: the code object holds the kernels in the order of their first use)
+// (a kernel that can report input positions comes as a <.., true> / <.., false> pair: the call's want_perm picks)
+template <class Kernel, class... Args>
+int enc_launch(EncodeCall &c, Kernel with_perm, Kernel without, dim3 grid, size_t lds, hipStream_t st_, const Args &...args) {
+    hipLaunchKernelGGL(c.pol.want_perm ? with_perm : without, grid, dim3(64), lds, st_, args...);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+int enc_launch_gen(EncodeCall &c, hipStream_t st_, const uint32_t *wl, uint32_t nwork, uint32_t rl_max) {
+    if (!nwork) return VIDC_OK;
+    RocEncArgs b = c.a;
+    b.worklist = wl; b.nwork = nwork;
+    if (c.enc_prio & 1) b.lpw = 0x80000000u;
+    hipLaunchKernelGGL(k_roc_encode_gen, dim3(nwork), dim3(64), (size_t)64 * rl_max * 12, st_, b, rl_max);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+void enc_note_chain(EncodeCall &c, const std::vector<uint32_t> &w, uint32_t ub) {
+    uint64_t tot = 0;
+    for (uint32_t l : w) tot += c.len(l);
+    c.ctx->chain_info[0][0] = tot; c.ctx->chain_info[0][1] = w.size(); c.ctx->chain_info[0][2] = c.len(w[0]); c.ctx->chain_info[0][3] = ub;
+}
+// universe-bitmap lists; the 20-bit launch (or, without one, the 18-bit launch) is the call's chain launch
+template <int BITS>
+int enc_launch_u(EncodeCall &c, hipStream_t st_) {
+    vidc_ctx *ctx = c.ctx; constexpr int cls = BITS == 20 ? W_U20 : W_U18;
+    const bool is_chain = BITS == 20 || c.wl(W_U20).empty();
+    if (is_chain) { enc_note_chain(c, c.wl(cls), BITS); VIDC_HIP(hipEventRecord(ctx->ev_chain[0], st_)); }
+    RocEncArgs b = c.a;
+    b.worklist = c.d_wl + c.w.base(cls); b.nwork = (uint32_t)c.wl(cls).size();
+    const U2Div *dt = (const U2Div *)ctx->d_u2tab;
+    if (old_u_kernels()) {
+        if constexpr (BITS == 20) {
+            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u<BITS, false>, UGeom<BITS>::LDS_BYTES));
+            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u<BITS, true>, UGeom<BITS>::LDS_BYTES));
+        }
+        VIDC_TRY(enc_launch(c, k_roc_encode_u<BITS, true>, k_roc_encode_u<BITS, false>, dim3(b.nwork), UGeom<BITS>::LDS_BYTES, st_, b));
+    } else {
+        if constexpr (BITS == 20) {
+            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<BITS, false>, U2Geom<BITS>::LDS_BYTES));
+            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<BITS, true>, U2Geom<BITS>::LDS_BYTES));
+        }
+        VIDC_TRY(enc_launch(c, k_roc_encode_u2<BITS, true>, k_roc_encode_u2<BITS, false>, dim3(b.nwork), U2Geom<BITS>::LDS_BYTES, st_, b, dt));
+    }
+    if (is_chain) VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st_));
+    return VIDC_OK;
+}
+int enc_launch_r2(EncodeCall &c, hipStream_t st_r2);
+// main stream: bitmap-20 lists and the deepest general class (the critical paths), position-bitmap chains
+void enc_add_chains(EncodeCall &c) {
+    const bool u20 = !c.wl(W_U20).empty(), r2 = !c.wl(W_R2).empty();
+    // (bitmap-20 lists: the critical path of the 1 M-vector configurations)
+    if (u20) c.L.push_back({"U20", 0, [&c](hipStream_t st_) { return enc_launch_u<20>(c, st_); }});
+    // (behind a 20-bit bitmap launch on the main stream these chains would only start when that one has finished:
+    // S1 encode 12.5 -> 13.5 ms; they go to the first auxiliary stream then)
+    if (r2) c.L.push_back({"R2", u20 ? 1 : 0, [&c](hipStream_t st_) { return enc_launch_r2(c, st_); }});
+    // the deepest class: prefix rows sized for its longest list (first of the work list).  With the fixed
+    // 48 KiB layout a CU held 3 of these chains; lists up to 65 536 ids need 12 KiB (S2 encode 152 -> see DESIGN)
+    // (behind a chain launch on the main stream it would only start when that one has finished)
+    if (!c.wl(W_C3).empty())
+        c.L.push_back({"C3", (r2 && !u20) ? 1 : 0, [&c](hipStream_t st_c3) -> int {
+            const uint64_t nmax3 = c.len(c.wl(W_C3)[0]);
+            uint32_t rl3 = 16;
+            while ((uint64_t)64 * 64 * rl3 < nmax3) rl3 <<= 1;
+            return enc_launch_gen(c, st_c3, c.d_wl + c.w.base(W_C3), (uint32_t)c.wl(W_C3).size(), rl3);
+        }});
+}
+int enc_launch_r2(EncodeCall &c, hipStream_t st_r2) {
+    RocEncArgs b = c.a;
+    b.worklist = c.d_wl + c.w.base(W_R2); b.nwork = (uint32_t)c.wl(W_R2).size();
+    if (c.enc_prio & 4) b.lpw = 0x80000000u;
+    const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
+    // (the bitmap of a launch whose longest list -- the first of the work list -- has at most 65 536 positions: 8 KiB)
+    if (c.len(c.wl(W_R2)[0]) <= 65536) return enc_launch(c, k_roc_encode_r2<true, 10>, k_roc_encode_r2<false, 10>, dim3(b.nwork), VIDC_R2_LDS_BYTES(10), st_r2, b, dt);
+    return enc_launch(c, k_roc_encode_r2<true, 12>, k_roc_encode_r2<false, 12>, dim3(b.nwork), VIDC_R2_LDS_BYTES(12), st_r2, b, dt);
+}
+// row-per-list kernels: one launch per octave of list length (grp_segments)
+void enc_add_grp(EncodeCall &c, int cls, size_t &seg_no) {
+    // Every launch is latency-bound (its duration is its longest list's chain) and light on issue slots, so the octaves
+    // must overlap: they alternate between the first and the third auxiliary stream (the lane classes own the second).
+    // stream digit per segment (0 = main, 1.. = auxiliary; wide: the last auxiliary stream is the plan upload's: ADVICE round 4)
+    const char *gmap = c.ctx->wide ? "456" : "13";
+    const size_t gmap_n = std::strlen(gmap), wbase = c.w.base(cls);
+    const bool lev3 = cls == W_G3;
+    int seg_of_class = 0;
+    for (const GrpSegment &s : grp_segments(c.wl(cls), c.r->offsets.data())) {
+        const int sd = gmap[seg_no++ % gmap_n] - '0';
+        c.L.push_back({std::string(lev3 ? "G3." : "G2.") + std::to_string(seg_of_class++), (sd >= 1 && sd <= c.ctx->naux()) ? sd : 0,
+                       [&c, n0 = s.longest, nwork = (uint32_t)s.count, woff = wbase + s.first, lev3](hipStream_t st_g) -> int {
+            const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
+            RocEncArgs b = c.a;
+            b.worklist = c.d_wl + woff; b.nwork = nwork;
+            const uint32_t nblk = (uint32_t)((n0 + 511) >> 9);
+            const size_t lds = (size_t)4 * 4 * (lev3 ? roc_grp_enc_lds_words<3>(nblk) : roc_grp_enc_lds_words<2>(nblk));
+            const dim3 grid((b.nwork + 3u) / 4u);
+            if (lev3 && lds > 65536) {
+                VIDC_TRY(set_big_lds((const void *)k_roc_encode_grp<3, true>, lds));
+                VIDC_TRY(set_big_lds((const void *)k_roc_encode_grp<3, false>, lds));
+            }
+            if (lev3) return enc_launch(c, k_roc_encode_grp<3, true>, k_roc_encode_grp<3, false>, grid, lds, st_g, b, dt, nblk);
+            return enc_launch(c, k_roc_encode_grp<2, true>, k_roc_encode_grp<2, false>, grid, lds, st_g, b, dt, nblk);
+        }});
+    }
+}
+void enc_add_gen(EncodeCall &c, int cls, int sdef) {  // C2 / C1: mid-size and short general lists
+    if (c.wl(cls).empty()) return;
+    c.L.push_back({cls == W_C2 ? "C2" : "C1", sdef, [&c, cls](hipStream_t st_) {
+        return enc_launch_gen(c, st_, c.d_wl + c.w.base(cls), (uint32_t)c.wl(cls).size(), cls == W_C2 ? 8 : 1);
+    }});
+}
+template <int NW>
+int enc_launch_lane(EncodeCall &c, hipStream_t st_, const RocEncArgs &b) {
+    const dim3 grid((b.nwork + (b.lpw & 0xffffu) - 1u) / (b.lpw & 0xffffu));
+    return enc_launch(c, k_roc_encode_lane<NW, true>, k_roc_encode_lane<NW, false>, grid, 0, st_, b, (const LaneDiv *)c.ctx->d_ltab);
+}
+// aux 0: mid-size general lists (calls without lane classes) and bitmap-18 lists; aux 1: the lane-per-list kernels, then the general classes
+void enc_add_short_classes(EncodeCall &c) {
+    const bool lanes_present = !c.wl(W_L4).empty() || !c.wl(W_L16).empty() || !c.wl(W_L64).empty();
+    if (!lanes_present) enc_add_gen(c, W_C2, 1);
+    if (!c.wl(W_U18).empty()) c.L.push_back({"U18", 1, [&c](hipStream_t st_) { return enc_launch_u<18>(c, st_); }});
+    if (!lanes_present) enc_add_gen(c, W_C1, 2);
+    for (int cls = W_L64; cls >= W_L4; cls--) {  // longest chains first
+        const std::vector<uint32_t> &w = c.wl(cls);
+        if (w.empty()) continue;
+        RocEncArgs b = c.a;
+        b.worklist = c.d_wl + c.w.base(cls); b.nwork = (uint32_t)w.size();
+        // (LDS per wavefront: 4-word strips 14.3 KiB, 16-word 21.5 KiB, 32-word 31.5 KiB, 64-word 50.5 KiB)
+        b.lpw = lane_lists_per_wave(c.ctx, b.nwork, cls == W_L4 ? 15 : cls == W_L16 ? 11 : 4);
+        if (cls == W_L64) {
+            // lists are sorted longest first: the leading wavefronts need the 64-word strips (50.5 KiB of LDS,
+            // 3 per CU), everything from the first wavefront whose longest list has <= 2048 ids the 32-word
+            // ones (31.5 KiB, 5 per CU)
+            uint32_t n_big = 0;
+            while (n_big < b.nwork && c.len(w[n_big]) > 2048) n_big++;
+            n_big = std::min<uint32_t>(b.nwork, (n_big + b.lpw - 1u) / b.lpw * b.lpw);
+            if (c.enc_prio & 2) b.lpw |= 0x80000000u;
+            RocEncArgs b2 = b;
+            b2.worklist = b.worklist + n_big; b2.nwork = b.nwork - n_big;
+            b.nwork = n_big;
+            if (b.nwork) c.L.push_back({"L64", 2, [&c, b](hipStream_t st_) { return enc_launch_lane<64>(c, st_, b); }});
+            if (b2.nwork) c.L.push_back({"L32", 2, [&c, b2](hipStream_t st_) { return enc_launch_lane<32>(c, st_, b2); }});
+        } else if (cls == W_L4) c.L.push_back({"L4", 2, [&c, b](hipStream_t st_) { return enc_launch_lane<4>(c, st_, b); }});
+        else c.L.push_back({"L16", 2, [&c, b](hipStream_t st_) { return enc_launch_lane<16>(c, st_, b); }});
+    }
+    if (lanes_present) { enc_add_gen(c, W_C2, 2); enc_add_gen(c, W_C1, 2); }
+}
+int enc_launch_tiny(EncodeCall &c, hipStream_t st_) {
+    const bool rows = c.rows; const uint32_t K = c.K;
+    RocEncArgs b = c.a;
+    b.worklist = rows ? nullptr : c.d_wl; b.nwork = (uint32_t)c.ntiny;
+    if (c.use.lane_tiny) {  // one list per lane (roc_lane.h)
+        const dim3 grid((b.nwork + 63u) / 64u);
+        const LaneDiv *dt = (const LaneDiv *)c.ctx->d_ltab;
+        if (rows && K == 32) hipLaunchKernelGGL((k_roc_encode_tiny_lane<32, true, true>), grid, dim3(64), 0, st_, b, dt);
+        else if (rows && K == 64) hipLaunchKernelGGL((k_roc_encode_tiny_lane<64, true, true>), grid, dim3(64), 0, st_, b, dt);
+        else if (rows && K < 32) hipLaunchKernelGGL((k_roc_encode_tiny_lane<32, true>), grid, dim3(64), 0, st_, b, dt);
+        else if (rows) hipLaunchKernelGGL((k_roc_encode_tiny_lane<64, true>), grid, dim3(64), 0, st_, b, dt);
+        else hipLaunchKernelGGL((k_roc_encode_tiny_lane<64, false>), grid, dim3(64), 0, st_, b, dt);
+    } else if (rows) hipLaunchKernelGGL(k_roc_encode_tiny<true>, dim3(b.nwork), dim3(64), 0, st_, b);
+    else hipLaunchKernelGGL(k_roc_encode_tiny<false>, dim3(b.nwork), dim3(64), 0, st_, b);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+// Kernel classes run concurrently (one stream each): the longest chains on the caller's stream, shorter
+// classes on the auxiliary streams so that they fill the wave slots the long chains leave idle.
+void enc_build_launches(EncodeCall &c) {
+    enc_add_chains(c);
+    // The lane-per-list kernels and the throughput-bound general classes must not share the machine: on S2 the
+    // 64-word lane class took 69 ms next to the 26 316-list general class (49 ms) -- 9 ms and ~35 ms when each
+    // has the CUs to itself (the lane strips take 141 KiB of a CU's LDS, the general waves the issue slots).
+    // With lane classes in the call they go first on aux 1 and the general classes queue behind them; the long
+    // chains on the main stream overlap with all of it.
+    size_t seg_no = 0;
+    enc_add_grp(c, W_G3, seg_no);
+    enc_add_grp(c, W_G2, seg_no);
+    enc_add_short_classes(c);
+    if (c.ntiny) c.L.push_back({"TINY", 3, [&c](hipStream_t st_) { return enc_launch_tiny(c, st_); }});  // aux 2
+}
+
+// an auxiliary stream joins the call at its first launch (and only those are joined at the end: a small call that uses
+// one of them does not pay event traffic for seven)
+inline hipStream_t enc_fork(EncodeCall &c, int i) {
+    if (!(c.aux_used >> i & 1u)) { (void)hipStreamWaitEvent(c.ctx->aux[i], c.ctx->ev_fork, 0); c.aux_used |= 1u << i; }
+    return c.ctx->aux[i];
+}
+// fork, the launches in the default or the VIDC_ENC_SCHED order, join
+int enc_run_launches(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; std::vector<EncLaunch> &L = c.L;
+    VIDC_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+    // A call without a class for the caller's stream (no bitmap-20, deepest-general or position-bitmap lists: e.g. an index
+    // of equal-sized short lists, graph rows) gives that stream to the first auxiliary class it launches: the class then
+    // starts without the fork event and the call ends without its join (65 536 lists of 256 ids: ~0.1 ms of idle GPU
+    // between the event records of the encode).
+    const bool main_idle = c.wl(W_U20).empty() && c.wl(W_C3).empty() && c.wl(W_R2).empty();
+    int promoted = -1;
+    const bool serial = env_on("VIDC_SERIAL");  // measurements: every class on the caller's stream, one after the other
+    auto stream_no = [&](int sno) -> hipStream_t {  // a launch's default stream
+        if (serial || sno == 0) return ctx->stream;
+        if (main_idle && (promoted < 0 || promoted == sno - 1)) { promoted = sno - 1; return ctx->stream; }
+        return enc_fork(c, sno - 1);
+    };
+    ctx->chain_info[0][0] = ctx->chain_info[0][1] = ctx->chain_info[0][2] = ctx->chain_info[0][3] = 0;
+    ctx->phase_ms[VIDC_PHASE_ROC_ENCODE_CHAIN] = 0;
+    enc_build_launches(c);
+    // The schedule.  This site's rules (the decoder's differ, see decode_impl): a name's second entry is ignored; a round without
+    // progress (a cycle) drops ALL dependencies and goes on; the 24 PhaseTimer events of the context double as "launch i has been
+    // queued" markers, so only the first 24 launches can be waited for (other dependencies are dropped, not aliased), and an event
+    // is only recorded for a launch that something waits for (no VIDC_ENC_SCHED: none at all).
+    std::vector<SchedEntry> sched;
+    if (const char *e = std::getenv("VIDC_ENC_SCHED")) {
+        auto find = [&](const std::string &t) { for (size_t i = 0; i < L.size(); i++) if (L[i].name == t) return (int)i; return -1; };
+        sched = parse_schedule(e, find, ctx->naux(), true);
+        std::stable_sort(sched.begin(), sched.end(), [](const SchedEntry &x, const SchedEntry &y) { return x.pos < y.pos; });
+    }
+    std::vector<char> named(L.size(), 0), waited_on(L.size(), 0), done(L.size(), 0);
+    for (const SchedEntry &it : sched) named[it.item] = 1;
+    for (size_t i = 0; i < L.size(); i++) if (!named[i]) sched.push_back({(int)i, -1, 0, {}});
+    for (SchedEntry &it : sched) {
+        it.deps.erase(std::remove_if(it.deps.begin(), it.deps.end(), [](int d) { return d >= 24; }), it.deps.end());
+        for (int d : it.deps) waited_on[d] = 1;
+    }
+    VIDC_TRY(run_schedule(sched, done, true, [&](const SchedEntry &it) -> int {
+        hipStream_t st_ = serial || it.group == 0 ? ctx->stream : it.group > 0 ? enc_fork(c, it.group - 1) : stream_no(L[it.item].def_stream);
+        for (int d : it.deps) VIDC_HIP(hipStreamWaitEvent(st_, ctx->tev[d], 0));
+        VIDC_TRY(L[it.item].fn(st_));
+        if (waited_on[it.item]) VIDC_HIP(hipEventRecord(ctx->tev[it.item], st_));
+        return VIDC_OK;
+    }));
+    for (int i = 0; i < ctx->naux(); i++) {
+        if (!(c.aux_used >> i & 1u)) continue;
+        VIDC_HIP(hipEventRecord(ctx->ev_join[i], ctx->aux[i]));
+        VIDC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
+    }
+    return VIDC_OK;
+}
+
+// the kernels are in flight and the host has nothing to do until they finish: plan the decode of the whole
+// object now (7 ms per million lists that decode_all would otherwise spend on its critical path)
+int enc_plan_ahead(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    const uint64_t nlist = c.nlist;
+    if (c.pre_deferred) {  // the maxima of the lists: precisions and bucket geometry for the decode planner
+        VIDC_HIP(vidc::vidc_event_wait(ctx->ev_pre[2]));
+        const uint32_t *mx = c.h_pre.as<uint32_t>();
+        r->umax.assign(mx, mx + nlist);
+        for (uint64_t l = 0; l < nlist; l++) r->prec[l] = prec_from_max(c.offsets[l + 1] - c.offsets[l], mx[l], c.precision_mode);
+        float pms = 0;
+        if (hipEventElapsedTime(&pms, ctx->ev_pre[0], ctx->ev_pre[1]) == hipSuccess) c.kernel_ms += pms;
+    }
+    if (c.rows || nlist < PLAN_AHEAD_MIN_LISTS || r->prec.size() != nlist) return VIDC_OK;
+    r->plan_ahead = plan_ahead_build(r, ctx->wide);
+    // ... and send its work list and scratch offsets to the device behind the kernels (decode_all then finds the
+    // plan complete: 0.04 ms of its critical path at 65 536 lists)
+    DecPlanCache &pc = *r->plan_ahead;
+    const size_t ni = pc.plan.wl.size();
+    if (!ni || pc.plan.lean) return VIDC_OK;
+    VIDC_TRY(c.h_plan.get(ctx, ni * 20));
+    uint64_t *h64 = c.h_plan.as<uint64_t>();
+    uint32_t *h32 = (uint32_t *)(h64 + 2 * ni);
+    std::memcpy(h64, pc.plan.scratch_off.data(), ni * 8);
+    std::memcpy(h64 + ni, pc.plan.slots_off.data(), ni * 8);
+    std::memcpy(h32, pc.plan.wl.data(), ni * 4);
+    VIDC_TRY(pc.d_scratch_off.alloc(ni, ctx->dpool)); VIDC_TRY(pc.d_slots_off.alloc(ni, ctx->dpool)); VIDC_TRY(pc.d_wl.alloc(ni, ctx->dpool));
+    // (on a stream of their own -- the last auxiliary one, which no kernel class of this call uses --: behind the
+    // kernels on the caller's stream the 1.3 MB of a 65 536-list plan were 0.06 ms more before the call's wait)
+    hipStream_t cs = ctx->aux[VIDC_NAUX - 1];
+    VIDC_HIP(hipMemcpyAsync(pc.d_scratch_off.p, h64, ni * 8, hipMemcpyHostToDevice, cs));
+    VIDC_HIP(hipMemcpyAsync(pc.d_slots_off.p, h64 + ni, ni * 8, hipMemcpyHostToDevice, cs));
+    VIDC_HIP(hipMemcpyAsync(pc.d_wl.p, h32, ni * 4, hipMemcpyHostToDevice, cs));
+    VIDC_HIP(hipEventRecord(ctx->ev_join[VIDC_NAUX - 1], cs));
+    VIDC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[VIDC_NAUX - 1], 0));
+    c.plan_on_device = true;
+    return VIDC_OK;
+}
+
+// second pass for lists the first pass handed back: unsorted input of the general kernels (Faiss
+// lists are in add order, i.e. normally sorted) and multiset input of the bitmap kernels
+int enc_second_pass(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    const uint64_t nlist = c.nlist;
+    std::vector<uint32_t> &pend = c.pend;
+    if (c.rows || !nlist) return VIDC_OK;
+    // how many lists are pending: the summary came back with the sizes, the status array only if there are any
+    if (c.tail.t[3]) {
+        std::vector<uint32_t> status;
+        VIDC_TRY(download(ctx, status, c.s_status.as<uint32_t>(), nlist));
+        for (uint64_t l = 0; l < nlist; l++)
+            if (status[l] == VIDC_ST_PENDING_SORT) pend.push_back((uint32_t)l);
+    }
+    if (pend.empty()) return VIDC_OK;
+    sort_desc(pend, r->offsets);
+    std::vector<uint64_t> skey_off(nlist + 1, 0);
+    uint32_t maxn = 0;
+    {
+        std::vector<uint8_t> is_p(nlist, 0);
+        for (uint32_t l : pend) is_p[l] = 1;
+        for (uint64_t l = 0; l < nlist; l++) {
+            uint64_t n = r->offsets[l + 1] - r->offsets[l], p2 = 0;
+            if (is_p[l]) { p2 = 1; while (p2 < n) p2 <<= 1; maxn = std::max<uint32_t>(maxn, (uint32_t)n); }
+            skey_off[l + 1] = skey_off[l] + p2;
+        }
+    }
+    Scratch s_skey, s_skey_off, s_spos, s_pend;
+    VIDC_TRY(s_skey.get(ctx, skey_off[nlist] * 8));
+    VIDC_TRY(upload_scratch(ctx, s_skey_off, skey_off));
+    VIDC_TRY(s_spos.get(ctx, c.ntotal_in * 4));
+    if (!c.s_sid.p) VIDC_TRY(c.s_sid.get(ctx, c.ntotal_in * 4));
+    VIDC_TRY(upload_scratch(ctx, s_pend, pend));
+    c.a.sid = c.s_sid.as<uint32_t>();
+    c.a.skey = s_skey.as<uint64_t>(); c.a.skey_off = s_skey_off.as<uint64_t>(); c.a.spos = s_spos.as<uint32_t>();
+    uint32_t rl_max = maxn <= 4096 ? 1 : (maxn <= 32768 ? 8 : (maxn <= 65536 ? 16 : 64));
+    EventTimer t2 = EventTimer::started(ctx);
+    VIDC_TRY(enc_launch_gen(c, ctx->stream, s_pend.as<uint32_t>(), (uint32_t)pend.size(), rl_max));
+    c.kernel_ms += t2.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // scratch of this scope is released below
+    if (c.light_prepass) {
+        // the precision of these lists came from their last id, which was not their maximum if they were not
+        // ascending: the general kernel stored the real one
+        std::vector<uint32_t> dp;
+        VIDC_TRY(download(ctx, dp, r->d_prec.p, nlist));
+        for (uint32_t l : pend) { r->prec[l] = dp[l]; r->umax[l] = 0; }
+        r->plan_ahead.reset();
+    }
+    // statuses and word counts of the redone lists: summary and offsets again
+    VIDC_TRY(finish_enqueue(ctx, r, c.tail, c.s_status, c.s_sizes.as<uint32_t>()));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    return VIDC_OK;
+}
+
+// bitmap-kernel lists wrote sampled ids into the perm buffer: turn them into input positions
+int enc_perm_from_order(EncodeCall &c) {
+    vidc_ctx *ctx = c.ctx; vidc_roc *r = c.r.get();
+    if (!c.pol.want_perm || (c.wl(W_U18).empty() && c.wl(W_U20).empty())) return VIDC_OK;
+    std::vector<uint8_t> is_p(c.nlist, 0);
+    for (uint32_t l : c.pend) is_p[l] = 1;
+    std::vector<uint32_t> ul;
+    for (uint32_t l : c.wl(W_U18)) if (!is_p[l]) ul.push_back(l);
+    for (uint32_t l : c.wl(W_U20)) if (!is_p[l]) ul.push_back(l);
+    if (ul.empty()) return VIDC_OK;
+    const std::vector<uint32_t> items = perm_items(ul, r->offsets.data(), VIDC_PERM_CHUNK);
+    Scratch s_ul;
+    VIDC_TRY(upload_scratch(ctx, s_ul, items));
+    const uint32_t nitems = (uint32_t)(items.size() / 2);
+    EventTimer t = EventTimer::started(ctx);
+    hipLaunchKernelGGL(k_perm_from_order, dim3(nitems), dim3(256), 0, ctx->stream, c.d_ids, r->d_offsets.p, s_ul.as<uint2>(), nitems, r->d_perm.p);
+    VIDC_HIP(hipGetLastError());
+    c.kernel_ms += t.stop();
+    return VIDC_OK;
+}
+
+// The host call of every ROC encode (IVF lists; graph rows: rows == true, a short path through the same stages).  The planning
+// -- which kernel class takes which list, in which order -- is roc_enc_plan.h; the stages above queue what it decided.
 int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, bool rows, uint64_t N,
                 uint32_t K, const int32_t *d_rows, int precision_mode, uint32_t flags, vidc_roc **out) {
     if (!ctx || !out) return VIDC_ERR_INVALID;
@@ -476,954 +1085,38 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
     }
     if (nlist >= 0xffffffffull || N >= 0xffffffffull) { set_error("too many lists"); return VIDC_ERR_INVALID; }
     VIDC_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<vidc_roc> r(new vidc_roc());
-    r->device = ctx->device;
-    r->rows = rows;
-    r->K = K;
-    r->nlist = rows ? N : nlist;
-    nlist = r->nlist;
-    double kernel_ms = 0;
-
-    HostTrace tr("roc encode");
-    // work lists: tiny (n <= 64), universe-bitmap kernels (ids < 2^18 / 2^20), general kernels by bitmap depth,
-    // lane-per-list kernels
-    std::vector<uint32_t> wl_tiny, wl_u18, wl_u20, wl_c1, wl_c2, wl_c3, wl_l4, wl_l16, wl_l64, wl_r2, wl_g2, wl_g3;
-    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) && !rows;
-    const uint64_t ntotal_in = rows ? N * K : (nlist ? offsets[nlist] : 0);
-    const bool f_general = force_general();  // getenv once, not per list
-    const LanePolicy lpol = f_general ? LANE_NEVER : lane_policy();
-    bool use_lane = false, use_lane64 = false, use_lane_tiny = false, use_grp = false;
-    const GrpPolicy gpol = grp_policy();
-    // persistent outputs
-    VIDC_TRY(r->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(r->d_prec.alloc(nlist, ctx->dpool));
-    VIDC_TRY(r->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(r->d_draws.alloc(nlist, ctx->dpool));
-    if (want_perm) VIDC_TRY(r->d_perm.alloc(ntotal_in ? ntotal_in : 1, ctx->dpool));
-    tr.mark("persistent allocs");
-    Scratch s_arena, s_status, s_sizes, s_sid, s_wl, s_maxid, s_flags, s_sum;
-    EncodeTail tail;  // status summary + sizes of the call, queued behind the encode kernels
-    bool light_prepass = false, pre_deferred = false;
-    bool wl_sorted[10] = {};  // work-list classes found longest-first while they were filled
-    Pinned h_wl, h_pre, h_off, h_plan;
-    bool plan_on_device = false;
-    // an early return while the offsets upload / the deferred prepass copy is in flight must not release their staging blocks
-    // (declared behind them: destroyed first; armed where such a copy is enqueued)
-    StreamGuard pre_guard(ctx, false);
-    // (graph rows: slots of whole 64-byte sectors -- a row's ~100 bytes of stream then lie in two sectors, not in two and a half)
-    const uint32_t arena_stride = rows ? (uint32_t)((arena_words_for(K) + 15u) & ~15ull) : 0u;
-    uint64_t arena_words = 0, nonempty = 0, ntiny = 0;
-    if (rows) {
-        if (K == 0 || K > TINY_MAX) {
-            set_error("graph rows: K=%u unsupported (1..64)", K);
-            return VIDC_ERR_UNSUPPORTED;
-        }
-        arena_words = roc_arena_at(nullptr, arena_stride, nlist);
-        ntiny = nlist;  // every row, in order: no work list array (kernels take l = work item)
-        use_lane_tiny = lane_wanted(lpol, nlist, LANE_MIN_TINY);
-        VIDC_TRY(s_sizes.get(ctx, nlist * 4));
-    } else {
-        if (!offsets) return VIDC_ERR_INVALID;
-        // the object's host copy of the offsets: on a helper thread for calls of 10^5 lists and more (8 MB at 10^6 lists: 0.6 ms
-        // of the 1.3 ms this phase took on S2), next to the validation pass and the staging copy below; joined before the
-        // classification, the first reader
-        std::thread offsets_copy;
-        struct JoinOnExit { std::thread &t; ~JoinOnExit() { if (t.joinable()) t.join(); } } offsets_copy_guard{offsets_copy};
-        r->offsets = vec_pool<uint64_t>().take(nlist + 1);
-        if (par_parts(nlist) > 1) offsets_copy = std::thread([&] { r->offsets.assign(offsets, offsets + nlist + 1); });
-        else r->offsets.assign(offsets, offsets + nlist + 1);
-        r->offsets_host = true;
-        tr.mark("offsets: object's copy");
-        // the offsets: validation, longest list, non-empty lists and the class sizes the kernel-family policies look at
-        bool any_big = false, all_desc = false;
-        uint64_t max_n = 0;
-        uint64_t n_tiny_lists = 0, n_mid_lists = 0, n_mid64_lists = 0, n_grp_lists = 0;
-        // (no synchronisation of its own for the upload below: the staging block lives until the call returns; an early error return
-        // before the call's first wait synchronises through the guard)
-        VIDC_TRY(h_off.get(ctx, (nlist + 1) * 8));
-        {
-            const unsigned parts = par_parts(nlist);
-            // (first the cheap facts -- extremes, order, validity as ONE flag --; the class sizes only need their own pass when the
-            // lengths straddle a class boundary: an index of equal-sized lists, or a graph, is classified by its extremes)
-            struct Acc { uint64_t nonempty = 0, max_n = 0, min_n = ~0ull, prev = ~0ull, c0 = 0, c1 = 0, c2 = 0, cg = 0; bool desc = true, bad = false; };
-            std::vector<Acc> acc(parts);
-            par_ranges(nlist, parts, [&](uint64_t la, uint64_t lb, unsigned t) {
-                Acc x;
-                if (parts > 1) {  // (threaded calls count the classes in the same pass: every pass costs a round of thread starts)
-                    for (uint64_t l = la; l < lb; l++) {
-                        const uint64_t n = offsets[l + 1] - offsets[l];
-                        x.bad |= n > VIDC_ROC_MAX_LIST;
-                        x.nonempty += n != 0;
-                        x.max_n = std::max(x.max_n, n);
-                        x.min_n = std::min(x.min_n, n);
-                        x.c0 += n <= TINY_MAX;
-                        x.c1 += n > TINY_MAX && n <= VIDC_LANE_MAX;
-                        x.c2 += n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX64;
-                        x.cg += n >= gpol.min_n && n <= gpol.max_n;
-                    }
-                    x.desc = false;
-                } else {
-                    // (one thread: the staging copy for the upload rides along; four lists per instruction where the host can)
-                    OffsetsPass op;
-                    offsets_pass(offsets + la, lb - la, h_off.as<uint64_t>() + la, op);
-                    x.bad = op.bad; x.nonempty = op.nonempty; x.max_n = op.max_n; x.min_n = op.min_n; x.desc = op.desc; x.prev = op.prev;
-                }
-                acc[t] = x;
-            });
-            uint64_t min_n = ~0ull;
-            bool bad = false;
-            for (unsigned t = 0; t < parts; t++) {
-                bad |= acc[t].bad;
-                nonempty += acc[t].nonempty;
-                max_n = std::max(max_n, acc[t].max_n);
-                min_n = std::min(min_n, acc[t].min_n);
-            }
-            if (bad)  // the first offending list, as a single pass would report it
-                for (uint64_t l = 0; l < nlist; l++) {
-                    if (offsets[l + 1] < offsets[l]) {
-                        set_error("offsets not monotone at list %llu", (unsigned long long)l);
-                        return VIDC_ERR_INVALID;
-                    }
-                    if (offsets[l + 1] - offsets[l] > VIDC_ROC_MAX_LIST) {
-                        set_error("list %llu has %llu ids; ROC lists are limited to %u (the reference codec is only "
-                                  "lossless up to 65536, SURVEY 8a-Q2)", (unsigned long long)l,
-                                  (unsigned long long)(offsets[l + 1] - offsets[l]), VIDC_ROC_MAX_LIST);
-                        return VIDC_ERR_DOMAIN;
-                    }
-                }
-            auto in_one = [&](uint64_t lo, uint64_t hi) { return nlist && min_n >= lo && max_n <= hi; };
-            if (parts > 1) {
-                for (unsigned t = 0; t < parts; t++) { n_tiny_lists += acc[t].c0; n_mid_lists += acc[t].c1; n_mid64_lists += acc[t].c2; n_grp_lists += acc[t].cg; }
-            } else
-            if (in_one(0, TINY_MAX) || in_one(TINY_MAX + 1, VIDC_LANE_MAX) || in_one(VIDC_LANE_MAX + 1, VIDC_LANE_MAX64) ||
-                (nlist && min_n > VIDC_LANE_MAX64)) {
-                n_tiny_lists = max_n <= TINY_MAX ? nlist : 0;
-                n_mid_lists = in_one(TINY_MAX + 1, VIDC_LANE_MAX) ? nlist : 0;
-                n_mid64_lists = in_one(VIDC_LANE_MAX + 1, VIDC_LANE_MAX64) ? nlist : 0;
-            } else {
-                std::vector<uint64_t> cnt(3 * (size_t)parts, 0);
-                par_ranges(nlist, parts, [&](uint64_t la, uint64_t lb, unsigned t) {
-                    uint64_t c0 = 0, c1 = 0, c2 = 0;
-                    for (uint64_t l = la; l < lb; l++) {
-                        const uint64_t n = offsets[l + 1] - offsets[l];
-                        c0 += n <= TINY_MAX;
-                        c1 += n > TINY_MAX && n <= VIDC_LANE_MAX;
-                        c2 += n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX64;
-                    }
-                    cnt[3 * t] = c0; cnt[3 * t + 1] = c1; cnt[3 * t + 2] = c2;
-                });
-                for (unsigned t = 0; t < parts; t++) { n_tiny_lists += cnt[3 * t]; n_mid_lists += cnt[3 * t + 1]; n_mid64_lists += cnt[3 * t + 2]; }
-            }
-            if (parts == 1 && max_n >= gpol.min_n && min_n <= gpol.max_n) {  // (lists in reach of the row-per-list kernels)
-                std::vector<uint64_t> cnt(parts, 0);
-                par_ranges(nlist, parts, [&](uint64_t la, uint64_t lb, unsigned t) {
-                    uint64_t c = 0;
-                    for (uint64_t l = la; l < lb; l++) {
-                        const uint64_t n = offsets[l + 1] - offsets[l];
-                        c += n >= gpol.min_n && n <= gpol.max_n;
-                    }
-                    cnt[t] = c;
-                });
-                for (unsigned t = 0; t < parts; t++) n_grp_lists += cnt[t];
-            }
-            any_big = max_n > TINY_MAX;
-            all_desc = parts == 1 && acc[0].desc;
-        }
-        tr.mark("offsets: pass + staging");
-        arena_words = roc_arena_at(offsets, 0, nlist);
-        r->ntotal = offsets[nlist];
-        VIDC_TRY(r->d_offsets.alloc(nlist + 1, ctx->dpool));
-        {
-            const unsigned cparts = par_parts(nlist);
-            if (cparts > 1 || nlist == 0)  // (a single-threaded pass above has copied them already)
-                par_ranges(nlist + 1, cparts, [&](uint64_t a0, uint64_t b0, unsigned) {
-                    std::memcpy(h_off.as<uint64_t>() + a0, offsets + a0, (b0 - a0) * 8);
-                });
-        }
-        if (offsets_copy.joinable()) offsets_copy.join();
-        tr.mark("offsets: blocks");
-        VIDC_HIP(hipMemcpyAsync(r->d_offsets.p, h_off.p, (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        pre_guard.arm();
-        tr.mark("offsets: upload call");
-        // The bitmap kernels own a whole CU's LDS (2^20-bit universe): latency-optimal for long lists, but only
-        // num_cu lists in flight.  With many lists, short ones go to the high-occupancy kernels.
-        const uint64_t u_min = U_MIN_LIST;
-        use_lane = lane_wanted(lpol, n_mid_lists, LANE_MIN_LISTS);
-        use_lane64 = lane_wanted(lpol, n_mid64_lists, LANE_MIN_LISTS64);
-        use_lane_tiny = lane_wanted(lpol, n_tiny_lists, LANE_MIN_TINY);
-        // (the octaves of a call must overlap: without spare hardware queues they would run one after the other)
-        use_grp = n_grp_lists && n_grp_lists >= gpol.min_lists && (ctx->wide || gpol.min_lists == 0);
-        // classification prepass (one workgroup per list): max id -> precision, sortedness, domain
-        const uint32_t *maxid = nullptr, *pflags = nullptr;
-        if (any_big) {
-            VIDC_TRY(s_maxid.get(ctx, nlist * 4));
-            VIDC_TRY(s_flags.get(ctx, nlist * 4));
-            VIDC_TRY(h_pre.get(ctx, nlist * 8));
-            EventTimer t = EventTimer::started(ctx);
-            // Every kernel that takes a list streams it anyway and checks what the full prepass would (ids inside
-            // [0, 2^31), ascending order where it matters, ids that fit the precision; the lane-per-list encoders since
-            // round 3: each sampled id against its left neighbour): the prepass only looks at the LAST id of each list -- the maximum of an ascending
-            // list -- instead of re-reading all of them (8 bytes per id).  A list that turns out not to be ascending
-            // comes back with VIDC_ST_PENDING_SORT and takes the sorting second pass like a multiset does.
-            light_prepass = !old_u_kernels() && !std::getenv("VIDC_FULL_PREPASS");
-            // No list long enough for the bitmap kernels (the only classes chosen by the width of a list's ids): the host
-            // classifies by length alone and reads the maxima back when it needs them -- for the decode plan, while the
-            // encode kernels run -- instead of waiting for the prepass here (0.1 ms per call at 65 536 lists).  A last id
-            // outside the domain is then reported by the kernel that takes the list, like one in the middle of a list.
-            pre_deferred = light_prepass && max_n < u_min;
-            if (pre_deferred) {
-                VIDC_HIP(hipEventRecord(ctx->ev_pre[0], ctx->stream));
-                hipLaunchKernelGGL(k_roc_prepass_last, dim3((uint32_t)((nlist + 255) / 256)), dim3(256), 0, ctx->stream, d_ids,
-                                   r->d_offsets.p, (uint32_t)nlist, precision_mode, s_maxid.as<uint32_t>(),
-                                   s_flags.as<uint32_t>(), r->d_prec.p);
-                VIDC_HIP(hipGetLastError());
-                VIDC_HIP(hipEventRecord(ctx->ev_pre[1], ctx->stream));
-                VIDC_HIP(hipMemcpyAsync(h_pre.p, s_maxid.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
-                VIDC_HIP(hipEventRecord(ctx->ev_pre[2], ctx->stream));
-                pre_guard.arm();
-                r->prec = vec_pool<uint32_t>().take(nlist);
-                r->prec.resize(nlist);
-                tr.mark("prepass kernel (read back later)");
-            } else {
-                if (light_prepass)
-                    hipLaunchKernelGGL(k_roc_prepass_last, dim3((uint32_t)((nlist + 255) / 256)), dim3(256), 0, ctx->stream, d_ids,
-                                       r->d_offsets.p, (uint32_t)nlist, precision_mode, s_maxid.as<uint32_t>(),
-                                       s_flags.as<uint32_t>(), r->d_prec.p);
-                else
-                    hipLaunchKernelGGL(k_roc_prepass, dim3((uint32_t)std::min<uint64_t>(nlist, (uint64_t)ctx->num_cu * 32)),
-                                       dim3(256), 0, ctx->stream, d_ids, r->d_offsets.p, (uint32_t)nlist, precision_mode,
-                                       s_maxid.as<uint32_t>(), s_flags.as<uint32_t>(), r->d_prec.p);
-                VIDC_HIP(hipGetLastError());
-                (void)t.mark();
-                VIDC_HIP(hipMemcpyAsync(h_pre.p, s_maxid.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
-                VIDC_HIP(hipMemcpyAsync(h_pre.as<uint32_t>() + nlist, s_flags.p, nlist * 4, hipMemcpyDeviceToHost, ctx->stream));
-                VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-                pre_guard.disarm();
-                kernel_ms += t.elapsed();
-                maxid = h_pre.as<uint32_t>();
-                pflags = maxid + nlist;
-                tr.mark("prepass kernel + d2h");
-                // what the decode planner needs later (kernel class, bucket geometry) is known right here
-                // (the precisions are filled in by the classification loop below: one pass over the lists instead of two)
-                r->prec = vec_pool<uint32_t>().take(nlist);
-                r->prec.resize(nlist);
-                r->umax = vec_pool<uint32_t>().take(nlist);
-                r->umax.assign(maxid, maxid + nlist);
-            }
-        } else {
-            r->prec.assign(nlist, 0);  // tiny lists only: the planner does not look at their precision
-        }
-        {
-            // per-thread work lists (contiguous list ranges), concatenated in range order: the same lists in the
-            // same order as a single pass
-            enum { W_TINY = 0, W_U18, W_U20, W_C1, W_C2, W_C3, W_L4, W_L16, W_L64, W_G2, W_G3, W_COUNT };
-            const unsigned parts = par_parts(nlist);
-            std::vector<uint32_t> *dst[W_COUNT] = {&wl_tiny, &wl_u18, &wl_u20, &wl_c1, &wl_c2, &wl_c3, &wl_l4, &wl_l16, &wl_l64, &wl_g2, &wl_g3};
-            // Without per-list maxima (the prepass is read back later: no list is long enough for the bitmap kernels, the only
-            // classes chosen by the width of the ids) the class of a list is a function of its LENGTH: the lists are ordered by
-            // length once -- longest first, a stable counting sort, or nothing at all for an index of equal-sized lists -- and
-            // every class is a run of that order, copied out between two binary searches.  The per-list loop below with its
-            // dozen push_back targets and the per-class sorts behind it were 0.13 + 0.02 ms of a 65 536-list call.
-            const bool by_length = !maxid && !pflags && parts == 1 && !f_general && !env_on("VIDC_NO_LENGTH_CLASSES");
-            if (by_length) {
-                std::vector<uint32_t> order = vec_pool<uint32_t>().take(nlist);
-                order.resize(nlist);
-                if (all_desc) {
-                    std::iota(order.begin(), order.end(), 0u);
-                } else {
-                    std::vector<uint32_t> start(max_n + 2, 0);
-                    for (uint64_t l = 0; l < nlist; l++) start[max_n - (offsets[l + 1] - offsets[l]) + 1]++;  // bucket 0 = longest
-                    for (size_t i = 1; i < start.size(); i++) start[i] += start[i - 1];
-                    for (uint64_t l = 0; l < nlist; l++) order[start[max_n - (offsets[l + 1] - offsets[l])]++] = (uint32_t)l;
-                }
-                auto len_at = [&](size_t i) { return offsets[order[i] + 1] - offsets[order[i]]; };
-                auto first_le = [&](uint64_t bound) {  // first position of the order whose list has at most `bound` ids
-                    size_t lo = 0, hi = nlist;
-                    while (lo < hi) { const size_t mid = (lo + hi) / 2; if (len_at(mid) > bound) lo = mid + 1; else hi = mid; }
-                    return lo;
-                };
-                auto class_of = [&](uint64_t n) -> int {  // the decisions of the per-list loop below for a sorted list of n ids
-                    if (n <= TINY_MAX) return W_TINY;
-                    const bool lane_ok = (use_lane && n <= VIDC_LANE_MAX) || (use_lane64 && n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX64);
-                    const bool grp_ok = use_grp && n >= gpol.min_n && n <= gpol.max_n;
-                    return grp_ok ? (n <= VIDC_GRP_LEV2_MAX ? W_G2 : W_G3)
-                           : (lane_ok && n <= 256) ? W_L4
-                           : (lane_ok && n <= VIDC_LANE_MAX) ? W_L16
-                           : lane_ok ? W_L64
-                           : n <= 4096 ? W_C1
-                           : n <= 32768 ? W_C2 : W_C3;
-                };
-                // upper ends of the length intervals on which class_of is constant, longest first
-                uint64_t cuts[] = {VIDC_ROC_MAX_LIST, gpol.max_n, 32768, VIDC_GRP_LEV2_MAX, 4096, VIDC_LANE_MAX64, gpol.min_n - 1, VIDC_LANE_MAX, 256, TINY_MAX};
-                std::sort(std::begin(cuts), std::end(cuts), std::greater<uint64_t>());
-                size_t pos = 0;
-                for (size_t c = 0; c < sizeof(cuts) / sizeof(cuts[0]) && pos < nlist; c++) {
-                    const uint64_t hi = cuts[c], lo = c + 1 < sizeof(cuts) / sizeof(cuts[0]) ? cuts[c + 1] : 0;  // interval (lo, hi]
-                    if (hi == lo) continue;
-                    const size_t end = lo ? first_le(lo) : nlist;  // (the last interval also takes the empty lists)
-                    if (end > pos) {
-                        std::vector<uint32_t> &w = *dst[class_of(hi)];
-                        w.insert(w.end(), order.begin() + (ptrdiff_t)pos, order.begin() + (ptrdiff_t)end);
-                        pos = end;
-                    }
-                }
-                // (the precisions are filled in when the prepass has been read back; tiny-only calls set them above)
-                for (int c = 1; c < W_COUNT; c++) wl_sorted[c - 1] = true;
-                r->order_desc.swap(order);  // the decode planner cuts its classes out of the same order
-                r->order_max_n = max_n;
-            } else {
-            std::vector<std::vector<uint32_t>> part_wl((size_t)parts * W_COUNT);
-            std::vector<int64_t> bad_list(parts, -1);
-            bool cls_desc[W_COUNT];
-            uint64_t cls_last[W_COUNT];
-            for (int c = 0; c < W_COUNT; c++) { cls_desc[c] = parts == 1; cls_last[c] = ~0ull; }
-            par_ranges(nlist, parts, [&](uint64_t la, uint64_t lb, unsigned tpart) {
-                std::vector<uint32_t> *w = &part_wl[(size_t)tpart * W_COUNT];
-                if (parts == 1) {  // (upper bounds from the counting pass: no regrowth while 65 536 lists are appended)
-                    w[W_TINY].reserve(n_tiny_lists);
-                    w[W_L4].reserve(use_lane ? n_mid_lists : 0);
-                }
-                for (uint64_t l = la; l < lb; l++) {
-                    const uint64_t n = offsets[l + 1] - offsets[l];
-                    if (maxid) {
-                        const uint32_t m = maxid[l];
-                        r->prec[l] = n == 0 ? 0u
-                                     : precision_mode >= 0    ? (uint32_t)precision_mode
-                                     : precision_mode == VIDC_PREC_EXACT ? (m ? 32u - (uint32_t)__builtin_clz(m) : 0u)
-                                                                         : (m > 1u ? 32u - (uint32_t)__builtin_clz(m - 1u) : 0u);
-                    }
-                    if (n <= TINY_MAX) { w[W_TINY].push_back((uint32_t)l); continue; }
-                    const uint32_t pf = pflags ? pflags[l] : 0u;  // (deferred prepass: no list of the call depends on them)
-                    if (pf & VIDC_PF_DOMAIN) {
-                        if (bad_list[tpart] < 0) bad_list[tpart] = (int64_t)l;
-                        continue;
-                    }
-                    const uint32_t width = (maxid && maxid[l]) ? 32u - (uint32_t)__builtin_clz(maxid[l]) : 0u;  // ids < 2^width
-                    // the bitmap kernels need no sort; they cannot report input positions of an unsorted list
-                    const bool u_ok = maxid && !f_general && !((pf & VIDC_PF_UNSORTED) && want_perm) &&
-                                      (n >= u_min || (pf & VIDC_PF_UNSORTED));
-                    const bool lane_ok = !(pf & VIDC_PF_UNSORTED) &&
-                                         ((use_lane && n <= VIDC_LANE_MAX) ||
-                                          (use_lane64 && n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX64));
-                    // (the row-per-list kernel samples positions: ascending input; it checks that itself under the light prepass)
-                    const bool grp_ok = use_grp && n >= gpol.min_n && n <= gpol.max_n && !(pf & VIDC_PF_UNSORTED);
-                    const bool grp_first = grp_ok && gpol.min_lists == 0;  // VIDC_FORCE_GRP: ahead of every other family
-                    const int cls = grp_first ? (n <= VIDC_GRP_LEV2_MAX ? W_G2 : W_G3)
-                                    : (u_ok && width <= 18) ? W_U18
-                                    : (u_ok && width <= 20) ? W_U20
-                                    : grp_ok ? (n <= VIDC_GRP_LEV2_MAX ? W_G2 : W_G3)
-                                    : (lane_ok && n <= 256) ? W_L4
-                                    : (lane_ok && n <= VIDC_LANE_MAX) ? W_L16
-                                    : lane_ok ? W_L64
-                                    : n <= 4096 ? W_C1
-                                    : n <= 32768 ? W_C2 : W_C3;
-                    w[cls].push_back((uint32_t)l);
-                    if (parts == 1) {  // (is the class already longest-first?  equal-sized lists: saves sort_desc's own pass)
-                        cls_desc[cls] &= n <= cls_last[cls];
-                        cls_last[cls] = n;
-                    }
-                }
-            });
-            for (unsigned t = 0; t < parts; t++)
-                if (bad_list[t] >= 0) {  // the first offending list, as a single pass would report it
-                    set_error("roc encode: list %llu holds an id outside [0, 2^31) (reference: int max_id, "
-                              "custom_invlists_impl.cpp:163)", (unsigned long long)bad_list[t]);
-                    return VIDC_ERR_DOMAIN;
-                }
-            for (int c = 1; c < W_COUNT; c++) wl_sorted[c - 1] = cls_desc[c];  // (ws[] below: the classes without the tiny one)
-            for (int c = 0; c < W_COUNT; c++) {
-                if (parts == 1) { dst[c]->swap(part_wl[c]); continue; }
-                size_t tot = 0;
-                for (unsigned t = 0; t < parts; t++) tot += part_wl[(size_t)t * W_COUNT + c].size();
-                dst[c]->reserve(tot);
-                for (unsigned t = 0; t < parts; t++) {
-                    const auto &v = part_wl[(size_t)t * W_COUNT + c];
-                    dst[c]->insert(dst[c]->end(), v.begin(), v.end());
-                }
-            }
-            }  // per-list classification
-        }
-        ntiny = wl_tiny.size();
-        tr.mark("classify");
-        {
-            std::vector<uint32_t> *ws[10] = {&wl_u18, &wl_u20, &wl_c1, &wl_c2, &wl_c3, &wl_l4, &wl_l16, &wl_l64, &wl_g2, &wl_g3};
-            if (par_parts(nlist) > 1) {  // one thread per class (independent vectors, read-only offsets)
-                std::vector<std::thread> th;
-                for (int c = 1; c < 10; c++)
-                    if (ws[c]->size() > 1) th.emplace_back([&, c] { sort_desc(*ws[c], r->offsets); });
-                sort_desc(*ws[0], r->offsets);
-                for (auto &x : th) x.join();
-            } else {
-                for (int c = 0; c < 10; c++)
-                    if (!wl_sorted[c]) sort_desc(*ws[c], r->offsets);
-            }
-        }
-        // The longest general lists (any precision, more than 256 ids) take the position-bitmap chain kernel
-        // (k_roc_encode_r2: 0.26 instead of 0.48 us per step alone) -- when ALL the chains that decide the call's duration
-        // fit on the machine at once: at most four per CU (32 KiB of LDS and 233 VGPRs each), and only if no more than that
-        // many lists are at least half as long as the longest one.  1024 lists of 977 ids: encode 0.51 -> 0.35 ms; 256 x
-        // 3900: 1.75 -> 1.07; 1024 x 6000: 3.9 -> 2.5.  On S2 (1754 lists of 32 769..65 536 ids) 1024 of these chains took
-        // the LDS the lane-per-list classes need and the call went from 78 to 117 ms: there the general kernel, which packs
-        // six times as many chains per CU, keeps all of them.
-        if (!f_general && !old_u_kernels() && !env_on("VIDC_NO_R2")) {
-            const size_t cap = (size_t)ctx->num_cu * 4;
-            const std::vector<uint32_t> &top = !wl_c3.empty() ? wl_c3 : (!wl_c2.empty() ? wl_c2 : wl_c1);
-            if (!top.empty()) {
-                const uint64_t n_top = r->offsets[top[0] + 1] - r->offsets[top[0]];
-                size_t n_long = 0;
-                for (const std::vector<uint32_t> *w : {&wl_c3, &wl_c2, &wl_c1})
-                    for (uint32_t l : *w) {
-                        if (2 * (r->offsets[l + 1] - r->offsets[l]) < n_top || n_long > cap) break;
-                        n_long++;
-                    }
-                size_t take_cap = cap;
-                auto take = [&](std::vector<uint32_t> &w) {
-                    size_t k = 0;
-                    while (k < w.size() && wl_r2.size() < take_cap && r->offsets[w[k] + 1] - r->offsets[w[k]] > R2_MIN_LIST) {
-                        wl_r2.push_back(w[k]);
-                        k++;
-                    }
-                    w.erase(w.begin(), w.begin() + (ptrdiff_t)k);
-                };
-                if (n_long <= cap) {
-                    take(wl_c3);
-                    if (wl_c3.empty()) take(wl_c2);
-                    if (wl_c3.empty() && wl_c2.empty()) take(wl_c1);
-                } else if (n_top <= 65536 && !wl_c3.empty()) {
-                    // More long chains than that (S2: 1754 lists of 32 769..65 536 ids): the `cap` longest ones -- one per SIMD --
-                    // still decide the call (65 536 steps at 0.9 us on the general kernel under load against ~0.7 here) and, with
-                    // the bitmap sized for 65 536 positions (8 KiB instead of 32), no longer take the LDS the other classes need;
-                    // the rest of the class (<= ~45 000 ids on S2) finishes earlier on the general kernel anyway.
-                    // Half as many again queue behind the resident ones in the same launch: each starts when one of the longest
-                    // chains has finished, still ends before the launch's longest chain would have on the general kernel, and
-                    // leaves that kernel ~500 fewer chains (S2 encode 59-62 -> 55-57 ms; all 1754: 59).
-                    take_cap = cap + cap / 2;
-                    take(wl_c3);
-                }
-            }
-        }
-        tr.mark("sort work lists");
-    }
-    VIDC_TRY(s_arena.get(ctx, arena_words * 4));
-    VIDC_TRY(s_status.get(ctx, nlist * 4));
-    if (nlist) VIDC_HIP(hipMemsetAsync(s_status.p, 0xff, nlist * 4, ctx->stream));
-    VIDC_TRY(finish_prepare(ctx, r.get(), tail));
-    std::vector<size_t> base;
-    const uint32_t *d_wl = nullptr;
+    EncodeCall c{ctx, rows ? N : nlist, offsets, d_ids, rows, K, d_rows, precision_mode};
+    VIDC_TRY(enc_begin(c, N, flags));
     if (!rows) {
-        size_t total = 0;
-        for (auto *w : {&wl_tiny, &wl_u18, &wl_u20, &wl_c1, &wl_c2, &wl_c3, &wl_l4, &wl_l16, &wl_l64, &wl_r2, &wl_g2, &wl_g3}) {
-            base.push_back(total);
-            total += w->size();
-        }
-        VIDC_TRY(h_wl.get(ctx, total * 4));
-        size_t k = 0;
-        for (auto *w : {&wl_tiny, &wl_u18, &wl_u20, &wl_c1, &wl_c2, &wl_c3, &wl_l4, &wl_l16, &wl_l64, &wl_r2, &wl_g2, &wl_g3}) {
-            if (!w->empty()) std::memcpy(h_wl.as<uint32_t>() + k, w->data(), w->size() * 4);
-            k += w->size();
-        }
-        VIDC_TRY(s_wl.get(ctx, total * 4));
-        if (total) VIDC_HIP(hipMemcpyAsync(s_wl.p, h_wl.p, total * 4, hipMemcpyHostToDevice, ctx->stream));
-        d_wl = s_wl.as<uint32_t>();
-    } else {
-        base.assign(12, 0);
+        VIDC_TRY(enc_scan_offsets(c));
+        VIDC_TRY(enc_prepass(c));
+        VIDC_TRY(enc_classify(c));
     }
-
-    RocEncArgs a{};
-    a.ids = d_ids; a.rows = d_rows; a.K = K;
-    a.offsets = rows ? nullptr : r->d_offsets.p;
-    a.precision_mode = precision_mode;
-    a.heads = r->d_heads.p; a.prec = r->d_prec.p; a.nwords = r->d_nwords.p; a.draws = r->d_draws.p;
-    a.sizes = s_sizes.as<uint32_t>();
-    a.status = s_status.as<uint32_t>();
-    a.arena = s_arena.as<uint32_t>(); a.arena_stride = arena_stride;
-    a.perm = want_perm ? r->d_perm.p : nullptr;
-    a.sid = s_sid.as<uint32_t>(); a.spos = nullptr; a.skey = nullptr; a.skey_off = nullptr;
-    a.mt = ctx->d_mt;
-
-    // VIDC_ENC_PRIO=<mask>: s_setprio 3 for the general wave-per-list class (1), the 64- / 32-word lane classes (2), the
-    // position-bitmap chains (4).  Default 2: the few wavefronts of the 2049..4096-id lane classes run 4096 steps ahead of the other
-    // lane launches of their stream, and a step of theirs takes 9.5 us next to the chain classes (2.3 alone); first in their SIMD's
-    // arbitration the S2 encode is 53.5-53.9 instead of 54.7-55.6 ms (interleaved, profiles/r05v_s2_ab_enc_prio.txt; the other
-    // classes: no effect)
-    const int enc_prio = [] { const char *e = std::getenv("VIDC_ENC_PRIO"); return e ? std::atoi(e) : 2; }();
-    tr.mark("alloc + upload");
-    // Kernel classes run concurrently (one stream each): the longest chains on the caller's stream, shorter
-    // classes on the auxiliary streams so that they fill the wave slots the long chains leave idle.
-    auto launch_gen_on = [&](hipStream_t st_, const uint32_t *wl, uint32_t nwork, uint32_t rl_max) -> int {
-        if (!nwork) return VIDC_OK;
-        RocEncArgs b = a;
-        b.worklist = wl; b.nwork = nwork;
-        if (enc_prio & 1) b.lpw = 0x80000000u;
-        size_t lds = (size_t)64 * rl_max * 12;
-        hipLaunchKernelGGL(k_roc_encode_gen, dim3(nwork), dim3(64), lds, st_, b, rl_max);
-        VIDC_HIP(hipGetLastError());
-        return VIDC_OK;
-    };
-    auto launch_gen = [&](const uint32_t *wl, uint32_t nwork, uint32_t rl_max) -> int {
-        return launch_gen_on(ctx->stream, wl, nwork, rl_max);
-    };
-    {
-        EventTimer t = EventTimer::started(ctx);
-        VIDC_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-        // an auxiliary stream joins the call at its first launch (and only those are joined at the end: a small call that uses
-        // one of them does not pay event traffic for seven)
-        // A call without a class for the caller's stream (no bitmap-20, deepest-general or position-bitmap lists: e.g. an index
-        // of equal-sized short lists, graph rows) gives that stream to the first auxiliary class it launches: the class then
-        // starts without the fork event and the call ends without its join (65 536 lists of 256 ids: ~0.1 ms of idle GPU
-        // between the event records of the encode).
-        const bool main_idle = wl_u20.empty() && wl_c3.empty() && wl_r2.empty();
-        int promoted = -1;
-        uint32_t aux_used = 0;
-        const bool serial = env_on("VIDC_SERIAL");  // measurements: every class on the caller's stream, one after the other
-        auto AUX = [&](int i) -> hipStream_t {
-            if (serial) return ctx->stream;
-            if (main_idle && (promoted < 0 || promoted == i)) { promoted = i; return ctx->stream; }
-            if (!(aux_used >> i & 1u)) { (void)hipStreamWaitEvent(ctx->aux[i], ctx->ev_fork, 0); aux_used |= 1u << i; }
-            return ctx->aux[i];
-        };
-        // main stream: bitmap-20 lists and the deepest general class (the critical paths)
-        ctx->chain_info[0][0] = ctx->chain_info[0][1] = ctx->chain_info[0][2] = ctx->chain_info[0][3] = 0;
-        ctx->phase_ms[VIDC_PHASE_ROC_ENCODE_CHAIN] = 0;
-        auto note_chain = [&](const std::vector<uint32_t> &w, uint32_t ub) {
-            uint64_t tot = 0;
-            for (uint32_t l : w) tot += r->offsets[l + 1] - r->offsets[l];
-            ctx->chain_info[0][0] = tot; ctx->chain_info[0][1] = w.size();
-            ctx->chain_info[0][2] = r->offsets[w[0] + 1] - r->offsets[w[0]]; ctx->chain_info[0][3] = ub;
-        };
-        // Every kernel class of the call is one entry here: its name, its default stream (0 = the caller's, i = auxiliary i - 1)
-        // and its launch.  Default streams / order = the schedule measured best (comments at the entries); VIDC_ENC_SCHED
-        // (measurements) replaces it: streams separated by ';' (first = the caller's stream), the launches of a stream by ','
-        // in FIFO order, "NAME^DEP" also waits for launch DEP; host launch order: first entries of every stream, then the
-        // second ones, ...; names: U20 R2 C3 G3.<k> G2.<k> (octaves of the row-per-list classes, longest first) C2 U18 C1 L64 L32 L16
-        // L4 TINY.  Launches the string does not name keep their default stream and go out last.
-        struct EncLaunch { std::string name; int def_stream; std::function<int(hipStream_t)> fn; };
-        std::vector<EncLaunch> L;
-        if (!wl_u20.empty()) {  // main stream: bitmap-20 lists (the critical path of the 1 M-vector configurations)
-            L.push_back({"U20", 0, [&](hipStream_t st_) -> int {
-                note_chain(wl_u20, 20);
-                VIDC_HIP(hipEventRecord(ctx->ev_chain[0], st_));
-                RocEncArgs b = a;
-                b.worklist = d_wl + base[2]; b.nwork = (uint32_t)wl_u20.size();
-                const U2Div *dt = (const U2Div *)ctx->d_u2tab;
-                if (old_u_kernels()) {
-                    VIDC_TRY(set_big_lds((const void *)k_roc_encode_u<20, false>, UGeom<20>::LDS_BYTES));
-                    VIDC_TRY(set_big_lds((const void *)k_roc_encode_u<20, true>, UGeom<20>::LDS_BYTES));
-                    if (want_perm) hipLaunchKernelGGL((k_roc_encode_u<20, true>), dim3(b.nwork), dim3(64), UGeom<20>::LDS_BYTES, st_, b);
-                    else hipLaunchKernelGGL((k_roc_encode_u<20, false>), dim3(b.nwork), dim3(64), UGeom<20>::LDS_BYTES, st_, b);
-                } else {
-                    VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<20, false>, U2Geom<20>::LDS_BYTES));
-                    VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<20, true>, U2Geom<20>::LDS_BYTES));
-                    if (want_perm) hipLaunchKernelGGL((k_roc_encode_u2<20, true>), dim3(b.nwork), dim3(64), U2Geom<20>::LDS_BYTES, st_, b, dt);
-                    else hipLaunchKernelGGL((k_roc_encode_u2<20, false>), dim3(b.nwork), dim3(64), U2Geom<20>::LDS_BYTES, st_, b, dt);
-                }
-                VIDC_HIP(hipGetLastError());
-                VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st_));
-                return VIDC_OK;
-            }});
-        }
-        if (!wl_r2.empty()) {
-            // (behind a 20-bit bitmap launch on the main stream these chains would only start when that one has finished:
-            // S1 encode 12.5 -> 13.5 ms; they go to the first auxiliary stream then)
-            L.push_back({"R2", wl_u20.empty() ? 0 : 1, [&](hipStream_t st_r2) -> int {
-                RocEncArgs b = a;
-                b.worklist = d_wl + base[9]; b.nwork = (uint32_t)wl_r2.size();
-                if (enc_prio & 4) b.lpw = 0x80000000u;
-                const U2Div *dt = (const U2Div *)ctx->d_u2tab;
-                // (the bitmap of a launch whose longest list -- the first of the work list -- has at most 65 536 positions: 8 KiB)
-                const bool small = r->offsets[wl_r2[0] + 1] - r->offsets[wl_r2[0]] <= 65536;
-                if (small && want_perm) hipLaunchKernelGGL((k_roc_encode_r2<true, 10>), dim3(b.nwork), dim3(64), VIDC_R2_LDS_BYTES(10), st_r2, b, dt);
-                else if (small) hipLaunchKernelGGL((k_roc_encode_r2<false, 10>), dim3(b.nwork), dim3(64), VIDC_R2_LDS_BYTES(10), st_r2, b, dt);
-                else if (want_perm) hipLaunchKernelGGL((k_roc_encode_r2<true, 12>), dim3(b.nwork), dim3(64), VIDC_R2_LDS_BYTES(12), st_r2, b, dt);
-                else hipLaunchKernelGGL((k_roc_encode_r2<false, 12>), dim3(b.nwork), dim3(64), VIDC_R2_LDS_BYTES(12), st_r2, b, dt);
-                VIDC_HIP(hipGetLastError());
-                return VIDC_OK;
-            }});
-        }
-        // the deepest class: prefix rows sized for its longest list (first of the work list).  With the fixed
-        // 48 KiB layout a CU held 3 of these chains; lists up to 65 536 ids need 12 KiB (S2 encode 152 -> see DESIGN)
-        if (!wl_c3.empty()) {
-            // (behind a chain launch on the main stream it would only start when that one has finished)
-            L.push_back({"C3", (!wl_r2.empty() && wl_u20.empty()) ? 1 : 0, [&](hipStream_t st_c3) -> int {
-                const uint64_t nmax3 = r->offsets[wl_c3[0] + 1] - r->offsets[wl_c3[0]];
-                uint32_t rl3 = 16;
-                while ((uint64_t)64 * 64 * rl3 < nmax3) rl3 <<= 1;
-                return launch_gen_on(st_c3, d_wl + base[5], (uint32_t)wl_c3.size(), rl3);
-            }});
-        }
-        // The lane-per-list kernels and the throughput-bound general classes must not share the machine: on S2 the
-        // 64-word lane class took 69 ms next to the 26 316-list general class (49 ms) -- 9 ms and ~35 ms when each
-        // has the CUs to itself (the lane strips take 141 KiB of a CU's LDS, the general waves the issue slots).
-        // With lane classes in the call they go first on aux 1 and the general classes queue behind them; the long
-        // chains on the main stream overlap with all of it.
-        // row-per-list kernels: one launch per octave of list length (the LDS of a launch is sized by its longest list)
-        {
-            // Every launch is latency-bound (its duration is its longest list's chain) and light on issue slots, so the octaves
-            // must overlap: they alternate between the first and the third auxiliary stream (the lane classes own the second).
-            // stream digit per segment (0 = main, 1.. = auxiliary; wide: the last auxiliary stream is the plan upload's: ADVICE round 4)
-            const char *gmap = ctx->wide ? "456" : "13";
-            const size_t gmap_n = std::strlen(gmap);
-            size_t seg_no = 0;
-            auto add_grp = [&](const std::vector<uint32_t> &w, size_t wbase, bool lev3) {
-                size_t k0 = 0;
-                int seg_of_class = 0;
-                while (k0 < w.size()) {
-                    const uint64_t n0 = r->offsets[w[k0] + 1] - r->offsets[w[k0]];  // longest of the segment
-                    uint64_t lo = 1;                                                 // segment: lengths in (lo, 2 lo]
-                    while (lo * 2 < n0) lo *= 2;
-                    size_t k1 = k0;
-                    while (k1 < w.size() && r->offsets[w[k1] + 1] - r->offsets[w[k1]] > lo) k1++;
-                    const int sd = gmap[seg_no++ % gmap_n] - '0';
-                    const uint32_t nwork = (uint32_t)(k1 - k0);
-                    const size_t woff = wbase + k0;
-                    L.push_back({std::string(lev3 ? "G3." : "G2.") + std::to_string(seg_of_class++), (sd >= 1 && sd <= ctx->naux()) ? sd : 0,
-                                 [&, n0, nwork, woff, lev3](hipStream_t st_g) -> int {
-                        const U2Div *dt = (const U2Div *)ctx->d_u2tab;
-                        RocEncArgs b = a;
-                        b.worklist = d_wl + woff; b.nwork = nwork;
-                        const uint32_t nblk = (uint32_t)((n0 + 511) >> 9);
-                        const size_t lds = (size_t)4 * 4 * (lev3 ? roc_grp_enc_lds_words<3>(nblk) : roc_grp_enc_lds_words<2>(nblk));
-                        const dim3 grid((b.nwork + 3u) / 4u);
-                        if (lev3) {
-                            if (lds > 65536) {
-                                VIDC_TRY(set_big_lds((const void *)k_roc_encode_grp<3, true>, lds));
-                                VIDC_TRY(set_big_lds((const void *)k_roc_encode_grp<3, false>, lds));
-                            }
-                            if (want_perm) hipLaunchKernelGGL((k_roc_encode_grp<3, true>), grid, dim3(64), lds, st_g, b, dt, nblk);
-                            else hipLaunchKernelGGL((k_roc_encode_grp<3, false>), grid, dim3(64), lds, st_g, b, dt, nblk);
-                        } else if (want_perm) hipLaunchKernelGGL((k_roc_encode_grp<2, true>), grid, dim3(64), lds, st_g, b, dt, nblk);
-                        else hipLaunchKernelGGL((k_roc_encode_grp<2, false>), grid, dim3(64), lds, st_g, b, dt, nblk);
-                        VIDC_HIP(hipGetLastError());
-                        return VIDC_OK;
-                    }});
-                    k0 = k1;
-                }
-            };
-            add_grp(wl_g3, base[11], true);
-            add_grp(wl_g2, base[10], false);
-        }
-        const bool lanes_present = !wl_l4.empty() || !wl_l16.empty() || !wl_l64.empty();
-        // aux 0: mid-size general lists (calls without lane classes) and bitmap-18 lists
-        auto add_c2 = [&](int sdef) {
-            L.push_back({"C2", sdef, [&](hipStream_t st_) -> int { return launch_gen_on(st_, d_wl + base[4], (uint32_t)wl_c2.size(), 8); }});
-        };
-        auto add_c1 = [&](int sdef) {
-            L.push_back({"C1", sdef, [&](hipStream_t st_) -> int { return launch_gen_on(st_, d_wl + base[3], (uint32_t)wl_c1.size(), 1); }});
-        };
-        if (!lanes_present && !wl_c2.empty()) add_c2(1);
-        if (!wl_u18.empty()) {
-            L.push_back({"U18", 1, [&](hipStream_t st_) -> int {
-                const bool is_chain = wl_u20.empty();
-                if (is_chain) { note_chain(wl_u18, 18); VIDC_HIP(hipEventRecord(ctx->ev_chain[0], st_)); }
-                RocEncArgs b = a;
-                b.worklist = d_wl + base[1]; b.nwork = (uint32_t)wl_u18.size();
-                const U2Div *dt = (const U2Div *)ctx->d_u2tab;
-                if (old_u_kernels()) {
-                    if (want_perm) hipLaunchKernelGGL((k_roc_encode_u<18, true>), dim3(b.nwork), dim3(64), UGeom<18>::LDS_BYTES, st_, b);
-                    else hipLaunchKernelGGL((k_roc_encode_u<18, false>), dim3(b.nwork), dim3(64), UGeom<18>::LDS_BYTES, st_, b);
-                } else if (want_perm) hipLaunchKernelGGL((k_roc_encode_u2<18, true>), dim3(b.nwork), dim3(64), U2Geom<18>::LDS_BYTES, st_, b, dt);
-                else hipLaunchKernelGGL((k_roc_encode_u2<18, false>), dim3(b.nwork), dim3(64), U2Geom<18>::LDS_BYTES, st_, b, dt);
-                VIDC_HIP(hipGetLastError());
-                if (is_chain) VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st_));
-                return VIDC_OK;
-            }});
-        }
-        // aux 1: the lane-per-list kernels, then the general classes; aux 2: tiny lists
-        if (!lanes_present && !wl_c1.empty()) add_c1(2);
-        for (int cls = 2; cls >= 0; cls--) {  // longest chains first
-            const std::vector<uint32_t> &w = cls == 2 ? wl_l64 : (cls ? wl_l16 : wl_l4);
-            if (w.empty()) continue;
-            RocEncArgs b = a;
-            b.worklist = d_wl + base[6 + cls]; b.nwork = (uint32_t)w.size();
-            // (LDS per wavefront: 4-word strips 14.3 KiB, 16-word 21.5 KiB, 32-word 31.5 KiB, 64-word 50.5 KiB)
-            b.lpw = lane_lists_per_wave(ctx, b.nwork, cls == 0 ? 15 : cls == 1 ? 11 : 4);
-            if (cls == 2) {
-                // lists are sorted longest first: the leading wavefronts need the 64-word strips (50.5 KiB of LDS,
-                // 3 per CU), everything from the first wavefront whose longest list has <= 2048 ids the 32-word
-                // ones (31.5 KiB, 5 per CU)
-                uint32_t n_big = 0;
-                while (n_big < b.nwork && r->offsets[w[n_big] + 1] - r->offsets[w[n_big]] > 2048) n_big++;
-                n_big = std::min<uint32_t>(b.nwork, (n_big + b.lpw - 1u) / b.lpw * b.lpw);
-                if (enc_prio & 2) b.lpw |= 0x80000000u;
-                RocEncArgs b2 = b;
-                b2.worklist = b.worklist + n_big; b2.nwork = b.nwork - n_big;
-                b.nwork = n_big;
-                if (b.nwork)
-                    L.push_back({"L64", 2, [&, b](hipStream_t st_) -> int {
-                        const LaneDiv *dt = (const LaneDiv *)ctx->d_ltab;
-                        const dim3 g1((b.nwork + (b.lpw & 0xffffu) - 1u) / (b.lpw & 0xffffu));
-                        if (want_perm) hipLaunchKernelGGL((k_roc_encode_lane<64, true>), g1, dim3(64), 0, st_, b, dt);
-                        else hipLaunchKernelGGL((k_roc_encode_lane<64, false>), g1, dim3(64), 0, st_, b, dt);
-                        VIDC_HIP(hipGetLastError());
-                        return VIDC_OK;
-                    }});
-                if (b2.nwork)
-                    L.push_back({"L32", 2, [&, b2](hipStream_t st_) -> int {
-                        const LaneDiv *dt = (const LaneDiv *)ctx->d_ltab;
-                        const dim3 g2((b2.nwork + (b2.lpw & 0xffffu) - 1u) / (b2.lpw & 0xffffu));
-                        if (want_perm) hipLaunchKernelGGL((k_roc_encode_lane<32, true>), g2, dim3(64), 0, st_, b2, dt);
-                        else hipLaunchKernelGGL((k_roc_encode_lane<32, false>), g2, dim3(64), 0, st_, b2, dt);
-                        VIDC_HIP(hipGetLastError());
-                        return VIDC_OK;
-                    }});
-            } else {
-                L.push_back({cls == 0 ? "L4" : "L16", 2, [&, b, cls](hipStream_t st_) -> int {
-                    const LaneDiv *dt = (const LaneDiv *)ctx->d_ltab;
-                    const dim3 grid((b.nwork + b.lpw - 1u) / b.lpw);
-                    if (cls == 0 && want_perm) hipLaunchKernelGGL((k_roc_encode_lane<4, true>), grid, dim3(64), 0, st_, b, dt);
-                    else if (cls == 0) hipLaunchKernelGGL((k_roc_encode_lane<4, false>), grid, dim3(64), 0, st_, b, dt);
-                    else if (want_perm) hipLaunchKernelGGL((k_roc_encode_lane<16, true>), grid, dim3(64), 0, st_, b, dt);
-                    else hipLaunchKernelGGL((k_roc_encode_lane<16, false>), grid, dim3(64), 0, st_, b, dt);
-                    VIDC_HIP(hipGetLastError());
-                    return VIDC_OK;
-                }});
-            }
-        }
-        if (lanes_present) {
-            if (!wl_c2.empty()) add_c2(2);
-            if (!wl_c1.empty()) add_c1(2);
-        }
-        if (ntiny) {
-            L.push_back({"TINY", 3, [&](hipStream_t st_) -> int {
-                RocEncArgs b = a;
-                b.worklist = rows ? nullptr : d_wl; b.nwork = (uint32_t)ntiny;
-                if (use_lane_tiny) {  // one list per lane (roc_lane.h)
-                    const dim3 grid((b.nwork + 63u) / 64u);
-                    const LaneDiv *dt = (const LaneDiv *)ctx->d_ltab;
-                    if (rows && K == 32) hipLaunchKernelGGL((k_roc_encode_tiny_lane<32, true, true>), grid, dim3(64), 0, st_, b, dt);
-                    else if (rows && K == 64) hipLaunchKernelGGL((k_roc_encode_tiny_lane<64, true, true>), grid, dim3(64), 0, st_, b, dt);
-                    else if (rows && K < 32) hipLaunchKernelGGL((k_roc_encode_tiny_lane<32, true>), grid, dim3(64), 0, st_, b, dt);
-                    else if (rows) hipLaunchKernelGGL((k_roc_encode_tiny_lane<64, true>), grid, dim3(64), 0, st_, b, dt);
-                    else hipLaunchKernelGGL((k_roc_encode_tiny_lane<64, false>), grid, dim3(64), 0, st_, b, dt);
-                } else if (rows) hipLaunchKernelGGL(k_roc_encode_tiny<true>, dim3(b.nwork), dim3(64), 0, st_, b);
-                else hipLaunchKernelGGL(k_roc_encode_tiny<false>, dim3(b.nwork), dim3(64), 0, st_, b);
-                VIDC_HIP(hipGetLastError());
-                return VIDC_OK;
-            }});
-        }
-        {
-            auto stream_no = [&](int sno) -> hipStream_t { return sno == 0 ? ctx->stream : AUX(sno - 1); };
-            std::vector<int> sch_stream(L.size(), -1), sch_pos(L.size(), 0);
-            std::vector<std::vector<int>> deps(L.size());
-            auto find = [&](const std::string &t) { for (size_t i = 0; i < L.size(); i++) if (L[i].name == t) return (int)i; return -1; };
-            std::vector<int> order_l;
-            if (const char *e = std::getenv("VIDC_ENC_SCHED")) {
-                std::string str(e);
-                int grp = 0, pos = 0;
-                size_t i0 = 0;
-                for (size_t i = 0; i <= str.size(); i++) {
-                    if (i < str.size() && str[i] != ',' && str[i] != ';') continue;
-                    std::string tok = str.substr(i0, i - i0);
-                    i0 = i + 1;
-                    if (!tok.empty()) {
-                        int me = -1;
-                        size_t j0 = 0;
-                        bool first = true;
-                        for (size_t j = 0; j <= tok.size(); j++) {
-                            if (j < tok.size() && tok[j] != '^') continue;
-                            const int c = find(tok.substr(j0, j - j0));
-                            j0 = j + 1;
-                            if (first) me = c; else if (c >= 0 && me >= 0) deps[me].push_back(c);
-                            first = false;
-                        }
-                        if (me >= 0 && sch_stream[me] < 0 && grp <= ctx->naux()) { sch_stream[me] = grp; sch_pos[me] = pos++; order_l.push_back(me); }
-                    }
-                    if (i < str.size() && str[i] == ';') { grp++; pos = 0; }
-                }
-                std::stable_sort(order_l.begin(), order_l.end(), [&](int x, int y) { return sch_pos[x] < sch_pos[y]; });
-            }
-            for (size_t i = 0; i < L.size(); i++)
-                if (sch_stream[i] < 0) order_l.push_back((int)i);
-            // dependency events: the 24 PhaseTimer events of the context double as "launch i has been queued" markers, so a schedule
-            // can only name the first 24 launches as something to wait for (others are dropped, not aliased), and an event is only
-            // recorded for a launch that something waits for (no VIDC_ENC_SCHED: none at all)
-            std::vector<char> waited_on(L.size(), 0);
-            for (auto &dv : deps) {
-                dv.erase(std::remove_if(dv.begin(), dv.end(), [](int d) { return d >= 24; }), dv.end());
-                for (int d : dv) waited_on[d] = 1;
-            }
-            std::vector<char> done(L.size(), 0);
-            size_t left = L.size();
-            while (left) {
-                const size_t before = left;
-                for (int i : order_l) {
-                    if (done[i]) continue;
-                    bool ready = true;
-                    for (int d : deps[i]) ready &= done[d] != 0;
-                    if (!ready) continue;
-                    hipStream_t st_ = serial ? ctx->stream : (sch_stream[i] >= 0 ? (sch_stream[i] == 0 ? ctx->stream : [&] {
-                        const int x = sch_stream[i] - 1;
-                        if (!(aux_used >> x & 1u)) { (void)hipStreamWaitEvent(ctx->aux[x], ctx->ev_fork, 0); aux_used |= 1u << x; }
-                        return ctx->aux[x];
-                    }()) : stream_no(L[i].def_stream));
-                    for (int d : deps[i]) VIDC_HIP(hipStreamWaitEvent(st_, ctx->tev[d], 0));
-                    VIDC_TRY(L[i].fn(st_));
-                    if (waited_on[i]) VIDC_HIP(hipEventRecord(ctx->tev[i], st_));
-                    done[i] = 1;
-                    left--;
-                }
-                if (left == before) {  // circular / unknown dependencies: drop them
-                    for (auto &d : deps) d.clear();
-                }
-            }
-        }
-        for (int i = 0; i < ctx->naux(); i++) {
-            if (!(aux_used >> i & 1u)) continue;
-            VIDC_HIP(hipEventRecord(ctx->ev_join[i], ctx->aux[i]));
-            VIDC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
-        }
-        // the kernels are in flight and the host has nothing to do until they finish: plan the decode of the whole
-        // object now (7 ms per million lists that decode_all would otherwise spend on its critical path)
-        // (the end event is recorded first: the planning is host time, not part of the kernels' duration)
-        (void)t.mark();
-        VIDC_TRY(finish_enqueue(ctx, r.get(), tail, s_status, s_sizes.as<uint32_t>()));
-        if (pre_deferred) {  // the maxima of the lists: precisions and bucket geometry for the decode planner
-            VIDC_HIP(vidc::vidc_event_wait(ctx->ev_pre[2]));
-            const uint32_t *mx = h_pre.as<uint32_t>();
-            r->umax.assign(mx, mx + nlist);
-            for (uint64_t l = 0; l < nlist; l++) {
-                const uint32_t m = mx[l];
-                r->prec[l] = offsets[l + 1] == offsets[l] ? 0u
-                             : precision_mode >= 0    ? (uint32_t)precision_mode
-                             : precision_mode == VIDC_PREC_EXACT ? (m ? 32u - (uint32_t)__builtin_clz(m) : 0u)
-                                                                 : (m > 1u ? 32u - (uint32_t)__builtin_clz(m - 1u) : 0u);
-            }
-            float pms = 0;
-            if (hipEventElapsedTime(&pms, ctx->ev_pre[0], ctx->ev_pre[1]) == hipSuccess) kernel_ms += pms;
-        }
-        if (!rows && nlist >= PLAN_AHEAD_MIN_LISTS && r->prec.size() == nlist) {
-            r->plan_ahead = plan_ahead_build(r.get(), ctx->wide);
-            // ... and send its work list and scratch offsets to the device behind the kernels (decode_all then finds the
-            // plan complete: 0.04 ms of its critical path at 65 536 lists)
-            DecPlanCache &pc = *r->plan_ahead;
-            const size_t ni = pc.plan.wl.size();
-            if (ni && !pc.plan.lean) {
-                VIDC_TRY(h_plan.get(ctx, ni * 20));
-                uint64_t *h64 = h_plan.as<uint64_t>();
-                uint32_t *h32 = (uint32_t *)(h64 + 2 * ni);
-                std::memcpy(h64, pc.plan.scratch_off.data(), ni * 8);
-                std::memcpy(h64 + ni, pc.plan.slots_off.data(), ni * 8);
-                std::memcpy(h32, pc.plan.wl.data(), ni * 4);
-                VIDC_TRY(pc.d_scratch_off.alloc(ni, ctx->dpool));
-                VIDC_TRY(pc.d_slots_off.alloc(ni, ctx->dpool));
-                VIDC_TRY(pc.d_wl.alloc(ni, ctx->dpool));
-                // (on a stream of their own -- the last auxiliary one, which no kernel class of this call uses --: behind the
-                // kernels on the caller's stream the 1.3 MB of a 65 536-list plan were 0.06 ms more before the call's wait)
-                hipStream_t cs = ctx->aux[VIDC_NAUX - 1];
-                VIDC_HIP(hipMemcpyAsync(pc.d_scratch_off.p, h64, ni * 8, hipMemcpyHostToDevice, cs));
-                VIDC_HIP(hipMemcpyAsync(pc.d_slots_off.p, h64 + ni, ni * 8, hipMemcpyHostToDevice, cs));
-                VIDC_HIP(hipMemcpyAsync(pc.d_wl.p, h32, ni * 4, hipMemcpyHostToDevice, cs));
-                VIDC_HIP(hipEventRecord(ctx->ev_join[VIDC_NAUX - 1], cs));
-                VIDC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[VIDC_NAUX - 1], 0));
-                plan_on_device = true;
-            }
-        }
-        // ONE wait for the kernels, the status summary and the sizes (queued behind the kernels above)
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        pre_guard.disarm();
-        kernel_ms += t.elapsed();
-        if (ctx->chain_info[0][3]) {  // (the main stream joined the auxiliary ones)
-            float cms = 0;
-            if (hipEventElapsedTime(&cms, ctx->ev_chain[0], ctx->ev_chain[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_ROC_ENCODE_CHAIN] = cms;
-        }
+    VIDC_TRY(enc_upload_worklists(c));
+    EventTimer t = EventTimer::started(ctx);
+    VIDC_TRY(enc_run_launches(c));
+    // (the end event is recorded first: the planning is host time, not part of the kernels' duration)
+    (void)t.mark();
+    VIDC_TRY(finish_enqueue(ctx, c.r.get(), c.tail, c.s_status, c.s_sizes.as<uint32_t>()));
+    VIDC_TRY(enc_plan_ahead(c));
+    // ONE wait for the kernels, the status summary and the sizes (queued behind the kernels above)
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    c.pre_guard.disarm();
+    c.kernel_ms += t.elapsed();
+    if (ctx->chain_info[0][3]) {  // (the main stream joined the auxiliary ones)
+        float cms = 0;
+        if (hipEventElapsedTime(&cms, ctx->ev_chain[0], ctx->ev_chain[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_ROC_ENCODE_CHAIN] = cms;
     }
-
-    tr.mark("encode kernels (sync)");
-    // second pass for lists the first pass handed back: unsorted input of the general kernels (Faiss
-    // lists are in add order, i.e. normally sorted) and multiset input of the bitmap kernels
-    std::vector<uint32_t> pend;
-    if (!rows && nlist) {
-        // how many lists are pending: the summary came back with the sizes, the status array only if there are any
-        const unsigned long long *t = tail.t;
-        if (t[3]) {
-            std::vector<uint32_t> status;
-            VIDC_TRY(download(ctx, status, s_status.as<uint32_t>(), nlist));
-            for (uint64_t l = 0; l < nlist; l++)
-                if (status[l] == VIDC_ST_PENDING_SORT) pend.push_back((uint32_t)l);
-        }
-        if (!pend.empty()) {
-            sort_desc(pend, r->offsets);
-            std::vector<uint64_t> skey_off(nlist + 1, 0);
-            uint32_t maxn = 0;
-            {
-                std::vector<uint8_t> is_p(nlist, 0);
-                for (uint32_t l : pend) is_p[l] = 1;
-                for (uint64_t l = 0; l < nlist; l++) {
-                    uint64_t n = r->offsets[l + 1] - r->offsets[l], p2 = 0;
-                    if (is_p[l]) { p2 = 1; while (p2 < n) p2 <<= 1; maxn = std::max<uint32_t>(maxn, (uint32_t)n); }
-                    skey_off[l + 1] = skey_off[l] + p2;
-                }
-            }
-            Scratch s_skey, s_skey_off, s_spos, s_pend;
-            VIDC_TRY(s_skey.get(ctx, skey_off[nlist] * 8));
-            VIDC_TRY(upload_scratch(ctx, s_skey_off, skey_off));
-            VIDC_TRY(s_spos.get(ctx, ntotal_in * 4));
-            if (!s_sid.p) VIDC_TRY(s_sid.get(ctx, ntotal_in * 4));
-            VIDC_TRY(upload_scratch(ctx, s_pend, pend));
-            a.sid = s_sid.as<uint32_t>();
-            a.skey = s_skey.as<uint64_t>(); a.skey_off = s_skey_off.as<uint64_t>(); a.spos = s_spos.as<uint32_t>();
-            uint32_t rl_max = maxn <= 4096 ? 1 : (maxn <= 32768 ? 8 : (maxn <= 65536 ? 16 : 64));
-            EventTimer t2 = EventTimer::started(ctx);
-            VIDC_TRY(launch_gen(s_pend.as<uint32_t>(), (uint32_t)pend.size(), rl_max));
-            kernel_ms += t2.stop();
-            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // scratch of this scope is released below
-            if (light_prepass) {
-                // the precision of these lists came from their last id, which was not their maximum if they were not
-                // ascending: the general kernel stored the real one
-                std::vector<uint32_t> dp;
-                VIDC_TRY(download(ctx, dp, r->d_prec.p, nlist));
-                for (uint32_t l : pend) { r->prec[l] = dp[l]; r->umax[l] = 0; }
-                r->plan_ahead.reset();
-            }
-            // statuses and word counts of the redone lists: summary and offsets again
-            VIDC_TRY(finish_enqueue(ctx, r.get(), tail, s_status, s_sizes.as<uint32_t>()));
-            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        }
-    }
-    // bitmap-kernel lists wrote sampled ids into the perm buffer: turn them into input positions
-    if (want_perm && (!wl_u18.empty() || !wl_u20.empty())) {
-        std::vector<uint8_t> is_p(nlist, 0);
-        for (uint32_t l : pend) is_p[l] = 1;
-        std::vector<uint32_t> ul;
-        for (uint32_t l : wl_u18) if (!is_p[l]) ul.push_back(l);
-        for (uint32_t l : wl_u20) if (!is_p[l]) ul.push_back(l);
-        if (!ul.empty()) {
-            // lists -> 8 lanes (longest first to the lane with the fewest chunks), lane x's k-th chunk at item 8 k + x
-            std::vector<uint32_t> byl(ul);
-            std::stable_sort(byl.begin(), byl.end(), [&](uint32_t x, uint32_t y) {
-                return r->offsets[x + 1] - r->offsets[x] > r->offsets[y + 1] - r->offsets[y];
-            });
-            std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lanes(8);
-            for (uint32_t l : byl) {
-                size_t best = 0;
-                for (size_t x = 1; x < 8; x++)
-                    if (lanes[x].size() < lanes[best].size()) best = x;
-                for (uint64_t st0 = 0, n = r->offsets[l + 1] - r->offsets[l]; st0 < n; st0 += VIDC_PERM_CHUNK)
-                    lanes[best].push_back({l, (uint32_t)st0});
-            }
-            size_t depth = 0;
-            for (auto &ln : lanes) depth = std::max(depth, ln.size());
-            std::vector<uint32_t> items(depth * 8 * 2, 0xffffffffu);
-            for (size_t x = 0; x < 8; x++)
-                for (size_t k = 0; k < lanes[x].size(); k++) {
-                    items[(k * 8 + x) * 2] = lanes[x][k].first;
-                    items[(k * 8 + x) * 2 + 1] = lanes[x][k].second;
-                }
-            Scratch s_ul;
-            VIDC_TRY(upload_scratch(ctx, s_ul, items));
-            const uint32_t nitems = (uint32_t)(depth * 8);
-            EventTimer t = EventTimer::started(ctx);
-            hipLaunchKernelGGL(k_perm_from_order, dim3(nitems), dim3(256), 0, ctx->stream, d_ids, r->d_offsets.p, s_ul.as<uint2>(),
-                               nitems, r->d_perm.p);
-            VIDC_HIP(hipGetLastError());
-            kernel_ms += t.stop();
-        }
-    }
-    tr.mark("second pass / perm");
-    ctx->phase_ms[VIDC_PHASE_ROC_ENCODE] = kernel_ms;
-    VIDC_TRY(finish_complete(ctx, r.get(), tail, s_arena.as<uint32_t>(), arena_stride, s_status, nonempty, kernel_ms));
-    tr.mark("metadata + compaction");
-    ctx->last_kernel_ms = kernel_ms;
-    if (plan_on_device && r->plan_ahead) r->plan_all = std::move(r->plan_ahead);  // (a sorting second pass drops the plan)
-    *out = r.release();
+    c.tr.mark("encode kernels (sync)");
+    VIDC_TRY(enc_second_pass(c));
+    VIDC_TRY(enc_perm_from_order(c));
+    c.tr.mark("second pass / perm");
+    ctx->phase_ms[VIDC_PHASE_ROC_ENCODE] = c.kernel_ms;
+    VIDC_TRY(finish_complete(ctx, c.r.get(), c.tail, c.s_arena.as<uint32_t>(), c.arena_stride, c.s_status, c.nonempty, c.kernel_ms));
+    c.tr.mark("metadata + compaction");
+    ctx->last_kernel_ms = c.kernel_ms;
+    if (c.plan_on_device && c.r->plan_ahead) c.r->plan_all = std::move(c.r->plan_ahead);  // (a sorting second pass drops the plan)
+    *out = c.r.release();
     return VIDC_OK;
 }
 
@@ -2029,39 +1722,18 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
         if (c == chain_class) VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st_));
         return VIDC_OK;
     };
-    // VIDC_DEC_SCHED (measurements): explicit schedule.  Streams separated by ';' (first = the caller's stream, then the
-    // auxiliary ones), the classes of a stream separated by ',' run in that order; "CLS^DEP" additionally waits for class DEP
-    // (on another stream) to finish.  Launch order on the host: first entries of every stream, then the second ones, ...
-    // Classes of the call the string does not name keep the automatic assignment.  E.g. "B2;GHUGE;LANEP,LANE,LANE64;GMID^LANEP".
-    struct SchedItem { int cls, grp, pos; std::vector<int> deps; };
-    std::vector<SchedItem> sched;
+    // VIDC_DEC_SCHED (measurements): explicit schedule (grammar: roc_enc_plan.h), e.g. "B2;GHUGE;LANEP,LANE,LANE64;GMID^LANEP"; "CLS^DEP"
+    // waits for class DEP (on another stream) to finish.  Classes of the call the string does not name keep the automatic assignment.
+    // This site's rules (the encoder's differ, see enc_run_launches): a class without lists in this call counts as unknown; a name's
+    // second entry is kept and skipped by the loop; an event is recorded for every scheduled class; a round without progress (a
+    // cycle) ends the loop and the rest is launched in order[].
+    std::vector<SchedEntry> sched;
     if (const char *e = std::getenv("VIDC_DEC_SCHED")) {
         static const char *names[DC_COUNT] = {"TINY", "U18", "U20", "GSMALL", "G8K", "G16K", "GMID", "GHUGE", "LANE", "LANE64", "LANE128", "B2", "B2T", "B2S",
                                               "B2L", "B2M", "GRP0", "GRP2", "GRP3", "GRP4", "LANEP", "LANEQ"};
-        auto cls_of = [&](const std::string &t) { for (int c = 0; c < DC_COUNT; c++) if (t == names[c]) return c; return -1; };
-        std::string str(e);
-        int grp = 0, pos = 0;
-        size_t i0 = 0;
-        for (size_t i = 0; i <= str.size(); i++) {
-            if (i < str.size() && str[i] != ',' && str[i] != ';') continue;
-            std::string tok = str.substr(i0, i - i0);
-            i0 = i + 1;
-            if (!tok.empty()) {
-                SchedItem it{-1, grp, pos, {}};
-                size_t j0 = 0;
-                bool first = true;
-                for (size_t j = 0; j <= tok.size(); j++) {
-                    if (j < tok.size() && tok[j] != '^') continue;
-                    const int c = cls_of(tok.substr(j0, j - j0));
-                    j0 = j + 1;
-                    if (first) it.cls = c; else if (c >= 0) it.deps.push_back(c);
-                    first = false;
-                }
-                if (it.cls >= 0 && p.count[it.cls] && grp <= ctx->naux()) { sched.push_back(it); pos++; }
-            }
-            if (i < str.size() && str[i] == ';') { grp++; pos = 0; }
-        }
-        for (const SchedItem &it : sched) stream_of[it.cls] = it.grp == 0 ? ctx->stream : ctx->aux[it.grp - 1];
+        auto cls_of = [&](const std::string &t) { for (int c = 0; c < DC_COUNT; c++) if (t == names[c]) return p.count[c] ? c : -1; return -1; };
+        sched = parse_schedule(e, cls_of, ctx->naux(), false);
+        for (const SchedEntry &it : sched) stream_of[it.item] = it.group == 0 ? ctx->stream : ctx->aux[it.group - 1];
     }
     if (pair_first) VIDC_TRY(launch(DC_LANEP));
     VIDC_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
@@ -2073,25 +1745,14 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
                 aux_used |= 1u << i;
             }
     if (!sched.empty()) {
-        bool done[DC_COUNT] = {};
-        std::stable_sort(sched.begin(), sched.end(), [](const SchedItem &x, const SchedItem &y) { return x.pos < y.pos; });
-        size_t left = sched.size();
-        while (left) {  // (an entry whose dependency is launched later in the list waits for the next round)
-            size_t before = left;
-            for (SchedItem &it : sched) {
-                if (it.cls < 0 || done[it.cls]) continue;
-                bool ready = true;
-                for (int d : it.deps) ready &= !p.count[d] || done[d];
-                if (!ready) continue;
-                for (int d : it.deps)
-                    if (p.count[d]) VIDC_HIP(hipStreamWaitEvent(stream_of[it.cls], ctx->tev[d], 0));
-                VIDC_TRY(launch(it.cls));
-                VIDC_HIP(hipEventRecord(ctx->tev[it.cls], stream_of[it.cls]));
-                done[it.cls] = true;
-                left--;
-            }
-            if (left == before) break;  // circular dependencies: the rest goes out below, unordered
-        }
+        std::vector<char> done(DC_COUNT, 0);
+        std::stable_sort(sched.begin(), sched.end(), [](const SchedEntry &x, const SchedEntry &y) { return x.pos < y.pos; });
+        VIDC_TRY(run_schedule(sched, done, false, [&](const SchedEntry &it) -> int {
+            for (int d : it.deps) VIDC_HIP(hipStreamWaitEvent(stream_of[it.item], ctx->tev[d], 0));
+            VIDC_TRY(launch(it.item));
+            VIDC_HIP(hipEventRecord(ctx->tev[it.item], stream_of[it.item]));
+            return VIDC_OK;
+        }));
         for (int k = 0; k < DC_COUNT; k++)
             if (!done[order[k]] && !(pair_first && order[k] == DC_LANEP)) VIDC_TRY(launch(order[k]));
     } else
