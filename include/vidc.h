@@ -441,7 +441,7 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
  *   results are one segmented-copy kernel on the home stream (a wavefront per 1024-element chunk of a segment; 16-byte accesses where a
  *   segment's source and destination share their alignment mod 16).  A shard on the home device is read and written in place (blocks of
  *   its context's cache); a shard on another device goes through hipMemcpyAsync(hipMemcpyDefault) between staging blocks of the two
- *   contexts' caches.  Per-shard calls that wait (encode, decode_*, perm, ROC's translate) are issued from one host thread per involved
+ *   contexts' caches.  Per-shard calls that wait (encode, append, decode_*, perm, ROC's translate) are issued from one host thread per involved
  *   shard, at most VIDC_SHARDS_MAX; each sets its device itself.  The enqueue-only per-shard calls (packed, Elias-Fano translate) are
  *   issued from the calling thread and ordered against the home stream with events the object owns (timing disabled; no spinning kernels,
  *   no cross-context atomics).
@@ -494,6 +494,43 @@ int vidc_shards_translate_labels_dev(vidc_ctx *home, const vidc_shards *s, uint6
 int vidc_shards_decode_gather(vidc_ctx *home, const vidc_shards *s, uint64_t m, const uint64_t *list_nos, uint64_t n_items,
                               const uint64_t *item_slot, const uint64_t *item_off, int64_t *ids_out);
 int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host);
+/* Append to a sharded object: the "append" section's contract, carried over the shards.  Called on the home context; d_list_nos, d_ids,
+ * d_labels (may be NULL) and d_invalid (may be NULL; the caller zeroes it) live on the home device; n_add < 2^32 - 1.
+ * Immutable.  *out is a NEW sharded object over the same shard contexts and the same home; `s` stays valid and unchanged, and either may be
+ *   destroyed first.
+ * The map does not change.  Owner and local number of every list in *out are those of `s`: an append never re-balances, so the balance
+ *   drifts with the batches.  vidc_sharded_loads (ids per shard = the sum of the owned lists' sizes; a host accessor, no device work) lets a
+ *   caller watch the drift and decide when a full re-encode (decode_all + vidc_shards_encode_dev) is worth it.
+ * The batch is that of the "append" section: pair i = (d_list_nos[i], d_ids[i]) with GLOBAL list numbers, M_l stable in i, a negative list
+ *   number skipped and not counted, one >= nlist skipped and counted in *d_invalid.
+ * The result.  Shard k of *out is what vidc_*_append_dev returns for shard k of `s` and the pairs routed to it -- word for word what
+ *   vidc_{packed,ef,roc}_encode builds from the cut of M's CSR by the map of `s`; vidc_shards_offsets of *out is M's offsets.  With U' = the
+ *   single-object append of the same batch to the unsharded U: every request on *out (decode_all, decode_lists, translate_labels_dev,
+ *   decode_gather, perm) returns what U' returns, and d_labels (global list number << 32 | offset, -1 for a skipped pair) and the invalid
+ *   count equal U''s.
+ * Parameters.  Packed: param = bits, 0 keeps the object's one width, a larger width re-packs every shard, an id that does not fit gives
+ *   VIDC_ERR_DOMAIN.  ROC: param = precision_mode (the mode the object was built with).  Elias-Fano: param is ignored.  flags are the
+ *   codec's own perm flags and become those of *out.
+ * Shards without pairs.  A shard that owns no list holds no object afterwards either.  A shard that holds an object but receives no pair
+ *   gets an object equal to its old one (the single-object "batch without a valid pair" case); n_add == 0 returns an equal object.
+ * What runs where.  A route kernel on the home stream takes every pair's owner from the device map and writes for EVERY shard a
+ *   full-length local list-number array (local_no where the shard owns the list, -1 elsewhere, which the shard's own append skips
+ *   uncounted: nshards * n_add slots, batch order and with it the stability contract kept, no count read-back) and an owner byte per pair.
+ *   The host waits for the route; then one host thread per shard that holds an object runs the shard's own vidc_*_append_dev, for every
+ *   kind.  A shard on the home device reads the caller's d_ids and its slice of the route block in place and writes its labels into the
+ *   home block; a shard on another device gets list numbers and ids through hipMemcpyAsync(hipMemcpyDefault) into a staging block of its
+ *   own cache, and its labels back -- a path that CANNOT RUN ON A ONE-GPU MACHINE AND HAS NOT BEEN RUN.  A join kernel writes d_labels[i] =
+ *   d_list_nos[i] << 32 | the offset of the owner's label.  The new object's offsets are the new shard objects' own list sizes (their
+ *   host-side metadata accessors) scattered through the map: O(nlist) host work, as in vidc_shards_encode_dev, and no batch histogram on
+ *   the host.  The call WAITS.  vidc_ctx_last_kernel_ms of the home context = route + join.
+ * Status.  NULL home / s / out, a NULL array with n_add > 0, n_add >= 2^32 - 1, or a home that is not the object's: VIDC_ERR_INVALID
+ *   before any device work.  A status from a shard is returned, "shard i: " in front of its message.  A shard's own invalid count stays 0
+ *   (every local number it sees is valid or negative); a non-zero one is an internal error, VIDC_ERR_INVALID.  On any error *out == NULL,
+ *   every new shard object already built is destroyed, `s` is untouched and every context stays usable (*d_invalid may have been added to).
+ * Residency.  No id payload crosses PCIe: vidc_ctx_d2h_bytes of the home context and of every shard context does not move. */
+int vidc_sharded_append_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
+                            int param, uint32_t flags, vidc_shards **out, int64_t *d_labels, uint64_t *d_invalid);
+int vidc_sharded_loads(const vidc_shards *s, uint64_t *loads /* nshards entries: ids per shard */);
 
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <numeric>
+#include <utility>
 #include <vector>
 
 namespace vidc {
@@ -56,16 +57,16 @@ inline std::vector<int32_t> lpt_partition(const std::vector<uint64_t> &sizes, in
     return owner;
 }
 
+// The plan of a GIVEN ownership (owner[l] in 0 .. nshards - 1; the caller checked): local numbers, local offsets, loads and cut segments.
+// An append keeps the owner of every list and re-plans with the new offsets: the local numbers depend on the owner alone, so they stay.
 // offsets: nlist + 1 entries, offsets[0] == 0, monotone (the caller checked)
-inline ShardPlan make_plan(const uint64_t *offsets, uint64_t nlist, int nshards) {
+inline ShardPlan make_plan_for_owner(const uint64_t *offsets, uint64_t nlist, int nshards, std::vector<int32_t> owner) {
     ShardPlan p;
     p.nshards = nshards;
     p.nlist = nlist;
     p.offsets.assign(offsets, offsets + nlist + 1);
     p.ntotal = offsets[nlist];
-    std::vector<uint64_t> sizes(nlist);
-    for (uint64_t l = 0; l < nlist; l++) sizes[l] = offsets[l + 1] - offsets[l];
-    p.owner = lpt_partition(sizes, nshards);
+    p.owner = std::move(owner);
     p.local_no.assign(nlist, 0);
     p.load.assign((size_t)nshards, 0);
     p.lists.assign((size_t)nshards, {});
@@ -75,11 +76,19 @@ inline ShardPlan make_plan(const uint64_t *offsets, uint64_t nlist, int nshards)
         const size_t s = (size_t)p.owner[l];
         p.local_no[l] = (uint32_t)p.lists[s].size();
         p.lists[s].push_back(l);
-        if (sizes[l]) p.cut[s].push_back(Segment{offsets[l], p.local_offsets[s].back(), sizes[l]});
-        p.local_offsets[s].push_back(p.local_offsets[s].back() + sizes[l]);
-        p.load[s] += sizes[l];
+        const uint64_t n = offsets[l + 1] - offsets[l];
+        if (n) p.cut[s].push_back(Segment{offsets[l], p.local_offsets[s].back(), n});
+        p.local_offsets[s].push_back(p.local_offsets[s].back() + n);
+        p.load[s] += n;
     }
     return p;
+}
+
+// the plan of vidc_shards_encode: ownership by the LPT rule, the rest from it
+inline ShardPlan make_plan(const uint64_t *offsets, uint64_t nlist, int nshards) {
+    std::vector<uint64_t> sizes(nlist);
+    for (uint64_t l = 0; l < nlist; l++) sizes[l] = offsets[l + 1] - offsets[l];
+    return make_plan_for_owner(offsets, nlist, nshards, lpt_partition(sizes, nshards));
 }
 
 // the chunk table of a segment table: every segment cut into pieces of SHARD_COPY_UNIT elements (lists are Zipf: one wavefront per

@@ -1,7 +1,7 @@
 // shards.hip -- vidc_shards (include/vidc.h): one CSR set of lists cut over several contexts of one process.  The plan is host code
 // (shard_plan.h); the shards are ordinary vidc_packed / vidc_ef / vidc_roc objects built and served through the public entry points, so a
 // shard IS what the single-object encoder builds from its cut CSR.  What is new on the device: the segmented copy (cut, inverse cut,
-// placement of decode_lists results) and the route / join pair of translate_labels.
+// placement of decode_lists results), the route / join pair of translate_labels and the route / join pair of the append.
 #include <thread>
 
 #include "common.h"
@@ -88,6 +88,41 @@ __global__ void __launch_bounds__(256) k_shard_join(const int64_t *__restrict__ 
     }
 }
 
+// Pair route of an append: local[s * n + i] = the local number of pair i's list if shard s owns it, else -1 (the shards' own appends skip
+// a negative list number and do not count it); owner[i] = the owning shard, NO_OWNER for a negative list number or one >= nlist (the
+// latter counted in *invalid).
+__global__ void __launch_bounds__(256) k_shard_route_pairs(const int64_t *__restrict__ list_nos, uint64_t n, const uint64_t *__restrict__ map,
+                                                           uint64_t nlist, uint32_t nshards, int64_t *__restrict__ local, uint8_t *__restrict__ owner,
+                                                           unsigned long long *invalid) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
+        const uint64_t i = i0 + dev::lane_id();
+        const int64_t l = i < n ? list_nos[i] : -1;
+        const bool pos = l >= 0;
+        const bool ok = pos && (uint64_t)l < nlist;
+        const uint64_t e = ok ? map[l] : 0;
+        const uint32_t own = ok ? (uint32_t)(e >> 32) : NO_OWNER;
+        if (i < n) {
+            const int64_t mine = (int64_t)(e & 0xffffffffull);
+            for (uint32_t s = 0; s < nshards; s++) local[(uint64_t)s * n + i] = s == own ? mine : -1;
+            owner[i] = (uint8_t)own;
+        }
+        req_count_invalid(pos && !ok, invalid);
+    }
+}
+
+// Label join of an append: labels[i] = GLOBAL list number << 32 | the offset of the owner's label, or -1 for a skipped pair
+__global__ void __launch_bounds__(256) k_shard_join_labels(const int64_t *__restrict__ list_nos, const int64_t *__restrict__ shard_labels,
+                                                           const uint8_t *__restrict__ owner, uint64_t n, uint32_t nshards,
+                                                           int64_t *__restrict__ labels) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t o = owner[i];
+        const int64_t lab = o < nshards ? shard_labels[(uint64_t)o * n + i] : -1;
+        labels[i] = lab >= 0 ? (int64_t)((uint64_t)list_nos[i] << 32 | ((uint64_t)lab & 0xffffffffull)) : -1;
+    }
+}
+
 inline dim3 copy_grid(const vidc_ctx *c, uint64_t nchunks) {
     return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nchunks + 3) / 4, (uint64_t)c->num_cu * 16)));
 }
@@ -143,6 +178,29 @@ int codec_translate(int kind, vidc_ctx *c, const void *o, uint64_t n, const int6
     case VIDC_KIND_EF: return vidc_ef_translate_labels_dev(c, (const vidc_ef *)o, n, d_labels, d_ids, d_invalid);
     default: return vidc_roc_translate_labels_dev(c, (const vidc_roc *)o, n, d_labels, d_ids, d_invalid);
     }
+}
+int codec_append(int kind, vidc_ctx *c, const void *o, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int param, uint32_t flags,
+                 void **out, int64_t *d_labels, uint64_t *d_invalid) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return vidc_packed_append_dev(c, (const vidc_packed *)o, n, d_list_nos, d_ids, param, (vidc_packed **)out, d_labels, d_invalid);
+    case VIDC_KIND_EF: return vidc_ef_append_dev(c, (const vidc_ef *)o, n, d_list_nos, d_ids, flags, (vidc_ef **)out, d_labels, d_invalid);
+    default: return vidc_roc_append_dev(c, (const vidc_roc *)o, n, d_list_nos, d_ids, param, flags, (vidc_roc **)out, d_labels, d_invalid);
+    }
+}
+// the sizes of an object's nl lists, through the codecs' host-side accessors (metadata mirrored on first use)
+int codec_list_sizes(int kind, vidc_ctx *c, const void *o, uint64_t nl, std::vector<uint64_t> &sizes) {
+    sizes.assign(nl, 0);
+    if (kind == VIDC_KIND_PACKED) {
+        std::vector<uint64_t> off(nl + 1);
+        VIDC_TRY(vidc_packed_offsets(c, (const vidc_packed *)o, off.data()));
+        for (uint64_t l = 0; l < nl; l++) sizes[l] = off[l + 1] - off[l];
+        return VIDC_OK;
+    }
+    std::vector<uint32_t> n32(nl ? nl : 1);
+    VIDC_TRY(kind == VIDC_KIND_EF ? vidc_ef_list_info((const vidc_ef *)o, n32.data(), nullptr, nullptr)
+                                  : vidc_roc_list_info((const vidc_roc *)o, n32.data(), nullptr, nullptr, nullptr, nullptr));
+    for (uint64_t l = 0; l < nl; l++) sizes[l] = n32[l];
+    return VIDC_OK;
 }
 
 }  // namespace
@@ -289,6 +347,50 @@ int check_encode(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int k
     return VIDC_OK;
 }
 
+// What every new object sets up, from encode and from append alike.  The events: one on the home device, one per shard on its device.
+int create_events(vidc_shards *S) {
+    const int nshards = (int)S->ctxs.size();
+    S->ev_shard.assign((size_t)nshards, nullptr);
+    for (int s = 0; s < nshards; s++) {
+        VIDC_HIP(hipSetDevice(S->ctxs[(size_t)s]->device));
+        VIDC_HIP(hipEventCreateWithFlags(&S->ev_shard[(size_t)s], hipEventDisableTiming));
+    }
+    VIDC_HIP(hipSetDevice(S->home->device));
+    VIDC_HIP(hipEventCreateWithFlags(&S->ev_home, hipEventDisableTiming));
+    return VIDC_OK;
+}
+// The map and, per shard that owns a list, the cut's segment and chunk tables of S->plan: allocated from the home context's cache and
+// uploaded on the home stream (current device: home).  The host vectors in `t` must live until the home stream has been waited for.
+struct PlanTables {
+    std::vector<uint64_t> map;
+    std::vector<std::vector<CopyChunk>> chunks;
+};
+int upload_plan(vidc_shards *S, PlanTables &t) {
+    const ShardPlan &P = S->plan;
+    vidc_ctx *home = S->home;
+    const size_t ns = (size_t)P.nshards;
+    t.map.resize(P.nlist);
+    for (uint64_t l = 0; l < P.nlist; l++) t.map[l] = P.packed(l);
+    t.chunks.assign(ns, {});
+    VIDC_TRY(S->d_map.alloc(P.nlist, home->dpool));
+    if (P.nlist) VIDC_HIP(hipMemcpyAsync(S->d_map.p, t.map.data(), P.nlist * 8, hipMemcpyHostToDevice, home->stream));
+    S->d_cut.resize(ns);
+    S->d_cut_chunks.resize(ns);
+    S->n_cut_chunks.assign(ns, 0);
+    for (size_t i = 0; i < ns; i++) {
+        if (P.lists[i].empty()) continue;
+        t.chunks[i] = build_copy_chunks(P.cut[i]);
+        S->n_cut_chunks[i] = t.chunks[i].size();
+        VIDC_TRY(S->d_cut[i].alloc(P.cut[i].size(), home->dpool));
+        VIDC_TRY(S->d_cut_chunks[i].alloc(t.chunks[i].size(), home->dpool));
+        if (!P.cut[i].empty()) {
+            VIDC_HIP(hipMemcpyAsync(S->d_cut[i].p, P.cut[i].data(), P.cut[i].size() * sizeof(Segment), hipMemcpyHostToDevice, home->stream));
+            VIDC_HIP(hipMemcpyAsync(S->d_cut_chunks[i].p, t.chunks[i].data(), t.chunks[i].size() * sizeof(CopyChunk), hipMemcpyHostToDevice, home->stream));
+        }
+    }
+    return VIDC_OK;
+}
+
 // host offsets (checked: start at 0, monotone) -> the object
 int encode_impl(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int kind, int param, uint32_t flags, uint64_t nlist,
                 const uint64_t *offsets, const uint64_t *d_ids, vidc_shards **out) {
@@ -314,39 +416,18 @@ int encode_impl(vidc_ctx *home, int nshards, vidc_ctx *const *shard_ctxs, int ki
     S->plan = make_plan(offsets, nlist, nshards);
     const ShardPlan &P = S->plan;
     S->param = kind == VIDC_KIND_PACKED && param == 0 ? vidc_packed_bits_for(P.ntotal) : param;  // (one width for every shard)
-    S->ev_shard.assign((size_t)nshards, nullptr);
-    for (int s = 0; s < nshards; s++) {
-        VIDC_HIP(hipSetDevice(S->ctxs[(size_t)s]->device));
-        VIDC_HIP(hipEventCreateWithFlags(&S->ev_shard[(size_t)s], hipEventDisableTiming));
-    }
-    VIDC_HIP(hipSetDevice(home->device));
-    VIDC_HIP(hipEventCreateWithFlags(&S->ev_home, hipEventDisableTiming));
+    VIDC_TRY(create_events(S.get()));
 
-    // the map and the cut tables, on the home device (the host vectors outlive the wait below)
-    std::vector<uint64_t> map(nlist);
-    for (uint64_t l = 0; l < nlist; l++) map[l] = P.packed(l);
-    std::vector<std::vector<CopyChunk>> chunks((size_t)nshards);
+    PlanTables tables;
     std::vector<Scratch> cut_home((size_t)nshards), cut_shard((size_t)nshards);  // the shards' contiguous ids
     std::vector<int> involved;
     ShardStreamsGuard sguard(S.get());
     StreamGuard hguard(home);
-    VIDC_TRY(S->d_map.alloc(nlist, home->dpool));
-    if (nlist) VIDC_HIP(hipMemcpyAsync(S->d_map.p, map.data(), nlist * 8, hipMemcpyHostToDevice, home->stream));
-    S->d_cut.resize((size_t)nshards);
-    S->d_cut_chunks.resize((size_t)nshards);
-    S->n_cut_chunks.assign((size_t)nshards, 0);
+    VIDC_TRY(upload_plan(S.get(), tables));
     for (int s = 0; s < nshards; s++) {
         const size_t i = (size_t)s;
         if (P.lists[i].empty()) continue;
         involved.push_back(s);
-        chunks[i] = build_copy_chunks(P.cut[i]);
-        S->n_cut_chunks[i] = chunks[i].size();
-        VIDC_TRY(S->d_cut[i].alloc(P.cut[i].size(), home->dpool));
-        VIDC_TRY(S->d_cut_chunks[i].alloc(chunks[i].size(), home->dpool));
-        if (!P.cut[i].empty()) {
-            VIDC_HIP(hipMemcpyAsync(S->d_cut[i].p, P.cut[i].data(), P.cut[i].size() * sizeof(Segment), hipMemcpyHostToDevice, home->stream));
-            VIDC_HIP(hipMemcpyAsync(S->d_cut_chunks[i].p, chunks[i].data(), chunks[i].size() * sizeof(CopyChunk), hipMemcpyHostToDevice, home->stream));
-        }
         // a shard on the home device: the cut writes the block its encoder reads
         VIDC_TRY((S->same_device(s) ? cut_shard[i] : cut_home[i]).get(S->same_device(s) ? S->ctxs[i] : home, (P.load[i] ? P.load[i] : 2) * 8));
     }
@@ -659,6 +740,142 @@ int vidc_shards_decode_gather(vidc_ctx *home, const vidc_shards *s, uint64_t m, 
         const size_t i = (size_t)sh;
         for (size_t k = 0; k < got[i].size(); k++) ids_out[R.item_index[i][k]] = got[i][k];
     }
+    return VIDC_OK;
+}
+
+int vidc_sharded_loads(const vidc_shards *s, uint64_t *loads) {
+    if (!s || !loads) {
+        set_error("sharded loads: NULL object or array");
+        return VIDC_ERR_INVALID;
+    }
+    std::copy(s->plan.load.begin(), s->plan.load.end(), loads);
+    return VIDC_OK;
+}
+
+// Append (include/vidc.h): the route kernel writes every shard's full-length local list numbers, every shard that holds an object runs
+// its own append on them (one host thread each, behind a host wait for the route), the join kernel turns the owners' labels into global
+// ones.  The new plan keeps the owner of every list; its offsets are the new shard objects' own list sizes scattered through the map.
+int vidc_sharded_append_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, int param,
+                            uint32_t flags, vidc_shards **out, int64_t *d_labels, uint64_t *d_invalid) {
+    if (out) *out = nullptr;
+    if (!home || !s || !out || (n_add && (!d_list_nos || !d_ids))) {
+        set_error("sharded append: NULL context, object, out or array");
+        return VIDC_ERR_INVALID;
+    }
+    if (n_add >= 0xffffffffull) { set_error("sharded append: a batch holds fewer than 2^32 - 1 pairs"); return VIDC_ERR_INVALID; }
+    VIDC_TRY(check_request(home, s, "sharded append"));
+    HostTrace tr("sharded append");
+    const ShardPlan &P = s->plan;
+    const uint32_t ns = (uint32_t)P.nshards;
+    const uint64_t n = n_add;
+    std::vector<int> involved;
+    for (int sh = 0; sh < P.nshards; sh++)
+        if (s->objs[(size_t)sh]) involved.push_back(sh);
+    std::unique_ptr<vidc_shards> N(new vidc_shards());
+    N->kind = s->kind;
+    N->flags = flags;
+    N->home = home;
+    N->ctxs = s->ctxs;
+    N->objs.assign((size_t)ns, nullptr);
+    N->param = s->kind == VIDC_KIND_EF || (s->kind == VIDC_KIND_PACKED && param == 0) ? s->param : param;
+    VIDC_HIP(hipSetDevice(home->device));
+    // home block: shard_invalid[ns] | local[ns * n] | shard labels[ns * n] | owner[n]
+    PlanTables tables;
+    Scratch blk;
+    Pinned h_inv;
+    std::vector<Scratch> far((size_t)ns);  // a shard on another device: invalid | list numbers[n] | ids[n] | labels[n] in its own cache
+    std::vector<std::vector<uint64_t>> sizes((size_t)ns);
+    ShardStreamsGuard sguard(s);
+    StreamGuard hguard(home, false);
+    VIDC_TRY(blk.get(home, (size_t)ns * 8 + 2 * (size_t)ns * n * 8 + n + 8));
+    VIDC_TRY(h_inv.get(home, (size_t)ns * 8));
+    unsigned long long *sh_inv = blk.as<unsigned long long>();
+    int64_t *local = (int64_t *)(sh_inv + ns), *sh_lab = local + (uint64_t)ns * n;
+    uint8_t *owner = (uint8_t *)(sh_lab + (uint64_t)ns * n);
+    hguard.arm();
+    EventTimer timer(home);
+    VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
+    double kernel_ms = 0;
+    if (n) {
+        VIDC_HIP(timer.start());
+        hipLaunchKernelGGL(k_shard_route_pairs, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, n, (const uint64_t *)s->d_map.p, P.nlist, ns,
+                           local, owner, (unsigned long long *)d_invalid);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(timer.mark());
+    }
+    // every shard's append waits anyway: the route (and the caller's batch) is waited for here, once, before the shard threads start
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    if (n) kernel_ms = timer.elapsed();
+    hguard.disarm();
+    tr.mark("routed, waited");
+    sguard.which = involved;
+    vidc_shards *Np = N.get();
+    const int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        const int64_t *ln = n ? local + (uint64_t)i * n : nullptr;
+        const uint64_t *ids = n ? d_ids : nullptr;
+        int64_t *lab = n && d_labels ? sh_lab + (uint64_t)i * n : nullptr;
+        uint64_t *inv = (uint64_t *)(sh_inv + i);
+        const bool far_shard = !s->same_device(sh);
+        if (far_shard) {
+            VIDC_TRY(far[i].get(c, 16 + 3 * n * 8));
+            inv = far[i].as<uint64_t>();
+            VIDC_HIP(hipMemsetAsync(inv, 0, 8, c->stream));
+            if (n) {
+                int64_t *f_ln = (int64_t *)(inv + 2);
+                uint64_t *f_ids = (uint64_t *)(f_ln + n);
+                VIDC_HIP(hipMemcpyAsync(f_ln, ln, n * 8, hipMemcpyDefault, c->stream));
+                VIDC_HIP(hipMemcpyAsync(f_ids, d_ids, n * 8, hipMemcpyDefault, c->stream));
+                ln = f_ln;
+                ids = f_ids;
+                if (lab) lab = (int64_t *)(f_ids + n);
+            }
+        }
+        VIDC_TRY(codec_append(s->kind, c, s->objs[i], n, ln, ids, param, flags, &Np->objs[i], lab, inv));
+        if (far_shard) {
+            if (lab) VIDC_HIP(hipMemcpyAsync(sh_lab + (uint64_t)i * n, lab, n * 8, hipMemcpyDefault, c->stream));
+            VIDC_HIP(hipMemcpyAsync(sh_inv + i, inv, 8, hipMemcpyDefault, c->stream));
+        }
+        VIDC_HIP(vidc_stream_wait(c->stream));
+        HostTrace ts("sharded append, a shard");
+        const int rc = codec_list_sizes(s->kind, c, Np->objs[i], P.lists[i].size(), sizes[i]);
+        ts.mark("list sizes to the host");
+        return rc;
+    });
+    tr.mark("shards appended, sizes read");
+    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
+    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
+    VIDC_HIP(hipSetDevice(home->device));
+    std::vector<uint64_t> off(P.nlist + 1, 0);
+    for (uint64_t l = 0; l < P.nlist; l++) off[l + 1] = off[l] + sizes[(size_t)P.owner[l]][P.local_no[l]];
+    N->plan = make_plan_for_owner(off.data(), P.nlist, P.nshards, P.owner);
+    tr.mark("plan");
+    VIDC_TRY(create_events(N.get()));
+    hguard.arm();
+    if (n && d_labels) {
+        VIDC_HIP(timer.start());
+        hipLaunchKernelGGL(k_shard_join_labels, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, (const int64_t *)sh_lab,
+                           (const uint8_t *)owner, n, ns, d_labels);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(timer.mark());
+    }
+    unsigned long long *h = h_inv.as<unsigned long long>();
+    VIDC_HIP(hipMemcpyAsync(h, sh_inv, (size_t)ns * 8, hipMemcpyDeviceToHost, home->stream));
+    VIDC_TRY(upload_plan(N.get(), tables));
+    tr.mark("join, tables enqueued");
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    hguard.disarm();
+    tr.mark("waited");
+    if (n && d_labels) kernel_ms += timer.elapsed();
+    home->last_kernel_ms = kernel_ms;  // (route + join)
+    for (uint32_t i = 0; i < ns; i++)
+        if (h[i]) {  // every local number a shard sees is valid or negative
+            set_error("sharded append: internal error, shard %u counted %llu list numbers outside its lists", i, h[i]);
+            return VIDC_ERR_INVALID;
+        }
+    *out = N.release();
     return VIDC_OK;
 }
 

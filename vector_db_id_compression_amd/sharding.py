@@ -12,7 +12,9 @@ arithmetic and the gathered lists land in request order with one indexed copy pe
 
 `ShardedInvLists` is the multi-process form (one process per GPU, torch.distributed).  `DeviceShards` is the single-process form
 over the C-ABI's vidc_shards: one process drives every context, the cut / placement / label routing are HIP kernels, and no index
-arithmetic happens in Python.  It has been exercised with several contexts on one device; never run on more than one GPU.
+arithmetic happens in Python.  `DeviceShards.append` adds a batch of (list number, id) pairs without re-encoding the index: the map
+stays, `DeviceShards.loads` shows how the balance drifts.  It has been exercised with several contexts on one device; never run on
+more than one GPU.
 """
 import heapq
 
@@ -333,6 +335,37 @@ class DeviceShards:
         from ._lib import lib
 
         return codecs._translate_labels(lib().vidc_shards_translate_labels_dev, self, labels, out, invalid)
+
+    @property
+    def loads(self):
+        """uint64[nshards]: ids per shard (the sum of its lists' sizes).  Appends keep the map, so the balance drifts: compare with
+        ntotal / nshards to decide when a full re-encode is worth it."""
+        from ._lib import check, lib, ptr
+
+        loads = np.zeros(self.nshards, np.uint64)
+        check(lib().vidc_sharded_loads(self.h, ptr(loads)))
+        return loads
+
+    def append(self, list_nos, ids, labels=True, invalid=None, **codec_args):
+        """A batch of (GLOBAL list number, id) pairs behind the lists of this object -> (NEW DeviceShards over the same contexts and the
+        same map, labels); this object stays valid and unchanged (vidc_sharded_append_dev).  Every shard runs its own append on the pairs
+        routed to it.  codec_args as in the single-object appends: bits (packed; None / 0 keeps the width), want_perm (ef, roc),
+        precision_mode (roc: the mode this object was built with).  See codecs._append for list_nos / ids / labels / invalid: the arrays
+        live on the home device, the labels carry global list numbers.  The call waits."""
+        from . import _lib, codecs
+
+        param, flags = 0, 0
+        if self.kind == 0:
+            param = int(codec_args.pop("bits", None) or 0)
+        elif self.kind == 1:
+            flags = _lib.VIDC_EF_WANT_PERM if codec_args.pop("want_perm", False) else 0
+        elif self.kind == 2:
+            param = int(codec_args.pop("precision_mode", _lib.VIDC_PREC_REFERENCE))
+            flags = _lib.VIDC_ROC_WANT_PERM if codec_args.pop("want_perm", False) else 0
+        if codec_args:
+            raise TypeError(f"unknown codec arguments: {sorted(codec_args)}")
+        h, lab = codecs._append(_lib.lib().vidc_sharded_append_dev, self, list_nos, ids, (param, flags), labels, invalid)
+        return type(self)(h, self.ctx, self.ctxs, self.kind), lab  # (the offsets are fetched from the new object on first use)
 
     def perm(self):
         from ._lib import check, lib, ptr
