@@ -856,7 +856,7 @@ def test_lane_quad_decoder_matches_bucket_decoder(roc, oracle, force_lane, monke
         sizes = np.minimum(sizes, (1 << nbits) - 1)
         off, ids, lists = _random_lists(rng, sizes, nbits=nbits)
         r = roc.encode(off, ids)
-        monkeypatch.setenv("VIDC_LANE_QUAD", "1")  # (opt-in: measured slower than the bucket rows, see roc.hip DecEnv)
+        monkeypatch.setenv("VIDC_LANE_QUAD", "1")  # (opt-in: measured slower than the bucket rows, see roc_dec_plan.h DecPolicy)
         dec = r.decode_all().cpu().numpy().view(np.uint64)
         assert r.last_decode_nonclean == 0
         monkeypatch.delenv("VIDC_LANE_QUAD")
@@ -903,3 +903,40 @@ def test_by_length_and_per_list_classification_agree(roc, oracle, monkeypatch):
                 assert np.array_equal(r.words(l, int(info["nwords"][l])), e["words"]), (hook, per_list, l)
         for a, b in zip(got["0"], got["1"]):
             assert np.array_equal(a, b), hook
+
+
+def test_by_length_and_per_list_decode_plans_agree(roc, oracle, monkeypatch):
+    """The decode planner of a whole object whose lists the encoder left ordered by length cuts its classes out of that order;
+    VIDC_NO_LENGTH_CLASSES=1 sends it through the per-list loop.  The lists of the test above: decode_all of a freshly encoded
+    object (the plan is cached with the object) under both settings gives the oracle's decode and the same ids, and decode_lists
+    of a shuffled subset -- always the per-list route -- agrees with it.  At this size only VIDC_FORCE_LANE reaches the by-length
+    route: the automatic policy has too few lists for the lane kernels, and VIDC_FORCE_GRP puts every list of 65 ids or more
+    in reach of the row-per-list kernels, which the by-length route does not plan."""
+    rng = np.random.default_rng(160)
+    sizes = np.repeat([0, 1, 64, 65, 256, 257, 1024, 1025, 2048, 2049, 4096], [64, 64, 72, 64, 10, 10, 2, 2, 1, 1, 1])
+    rng.shuffle(sizes)  # 291 lists, 26 253 ids
+    off, ids, lists = _random_lists(rng, sizes, nbits=22)
+    want = np.zeros(ids.size, dtype=np.uint64)
+    for l, li in enumerate(lists):
+        if li.size:
+            e = oracle.roc_encode(li, oracle.list_precision(li))
+            want[int(off[l]):int(off[l + 1])] = oracle.roc_decode(e["head"], e["words"], li.size, oracle.list_precision(li), e["mt_draws"])[0]
+    sub = rng.permutation(len(lists))[:50]
+    for hook in (None, "VIDC_FORCE_LANE", "VIDC_FORCE_GRP"):
+        got = {}
+        for per_list in ("0", "1"):
+            with monkeypatch.context() as m:
+                if hook:
+                    m.setenv(hook, "1")
+                m.setenv("VIDC_NO_LENGTH_CLASSES", "0")
+                r = roc.encode(off, ids)
+                m.setenv("VIDC_NO_LENGTH_CLASSES", per_list)
+                dec = r.decode_all().cpu().numpy().view(np.uint64)
+                assert r.last_decode_nonclean == 0, (hook, per_list)
+                part, poff = r.decode_lists(sub.astype(np.uint64))
+            assert np.array_equal(dec, want), (hook, per_list)
+            part = part.cpu().numpy().view(np.uint64)
+            for k, l in enumerate(sub):
+                assert np.array_equal(part[int(poff[k]):int(poff[k + 1])], want[int(off[l]):int(off[l + 1])]), (hook, per_list, l)
+            got[per_list] = dec
+        assert np.array_equal(got["0"], got["1"]), hook

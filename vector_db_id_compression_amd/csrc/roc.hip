@@ -12,6 +12,7 @@
 #include "append.h"
 #include "common.h"
 #include "host_call.h"
+#include "roc_dec_plan.h"
 #include "roc_enc_plan.h"
 #include "roc_kernels.h"
 #include "roc_u.h"
@@ -112,9 +113,6 @@ inline GrpPolicy grp_policy() {
     if (env_on("VIDC_FORCE_GRP")) { g.min_lists = 0; g.min_n = g.dec_min_n = VIDC_GRP_MIN_LIST; g.max_n = g.dec_max_n = VIDC_GRP_MAX_LIST; }
     return g;
 }
-
-// wavefronts of a bucket-row lane decoder launch: one per group of lists
-inline uint32_t lane_grid(uint32_t groups) { return groups; }
 
 // test hook: VIDC_OLD_U=1 keeps the round-1 bitmap kernels (roc_u.h) instead of the hand-scheduled ones (roc_u2.h)
 // Lists per wavefront of a lane-per-list launch (VIDC_LPW=8|16|32, measurements only; default 64).  Every list of a
@@ -399,40 +397,15 @@ int finish_complete(vidc_ctx *ctx, vidc_roc *r, EncodeTail &e, const uint32_t *d
     return VIDC_OK;
 }
 
-// ---- decode planning: work items grouped by kernel class, each with private scratch
-// general decoder classes by LDS footprint of the fine prefix rows (2^fb u32, fb = lg(n) - 3): occupancy, not
-// arithmetic, bounds the general decoder when a batch has many mid-size lists
-// (DC_LANE .. the last class: kernels that may hand a list back with VIDC_ST_RETRY)
-enum DecClass { DC_TINY = 0, DC_U18, DC_U20, DC_GSMALL, DC_G8K, DC_G16K, DC_GMID, DC_GHUGE, DC_LANE, DC_LANE64, DC_LANE128, DC_B2, DC_B2T, DC_B2S, DC_B2L, DC_B2M,
-                DC_GRP0, DC_GRP2, DC_GRP3, DC_GRP4,   // row-per-list decoder by bucket bits 8 + F (roc_grp.h)
-                DC_LANEP, DC_LANEQ, DC_COUNT };        // 257..512 / 513..1024 ids on a pair / quad of lanes, ids in registers (k_roc_decode_lane_reg<.., 2 / 4>)
-constexpr uint64_t B2_MIN_LIST = 4096;
+// ---- decode planning (roc_dec_plan.h): work items grouped by kernel class, each with private scratch
 #define VIDC_LANE_ALIGN_DEFAULT 16u        // bucket rows of the lane decoders on 64-byte boundaries (S2 decode 70.9 -> 69.8 ms: DESIGN section 13)
 constexpr uint32_t B2_MASK_MIN_CHAINS = 512;  // k_roc_decode_b2 launches of this many chains size their row loads by the member count
-constexpr size_t B2_CAP = 1024;      // chains of k_roc_decode_b2 per call (four per CU of an MI355X: 1 MiB of member rows each)
-constexpr size_t B2_TOP_CAP = 5120;  // ... of a call with more long chains than that: every list beyond 16 384 ids (comment at the planner)
-
-struct DecPlan {
-    std::vector<uint32_t> wl;        // list numbers, grouped by class, longest first inside a class
-    std::vector<uint32_t> item;      // index of each work item in the caller's request
-    size_t count[DC_COUNT] = {};
-    uint64_t sum_n[DC_COUNT] = {}, max_n[DC_COUNT] = {};
-    std::vector<uint64_t> scratch_off, slots_off;
-    uint64_t scratch_words = 0, slots_words = 0;
-    bool lean = false;               // graph rows, lane decoder: item k == request k, no scratch / offset arrays
-    bool tiny_lane = false;          // DC_TINY items run on the lane-per-list kernel
-    bool gsmall_lrows = false;       // DC_GSMALL items keep their member rows in LDS (33 KiB each: only for few lists)
-    uint32_t lane_align = 4;         // slots a bucket row of the lane decoders is aligned / padded to (roc_lane_cap_nb)
-    uint64_t implicit = 0;           // lean plan without a work list: items are rows 0..implicit-1
-    const uint32_t *order_dev = nullptr;  // ... or every row of the object in this device-resident order, each to its OWN output row
-    bool order_build = false;        // ... which this call builds first (k_rows_order_*, inside the call's timed region)
-    bool order_req = false;          // ... or order_dev is a work list in request order: item k -> output row k (device node requests)
-    DecPlan() = default;
-    DecPlan(const DecPlan &) = default;
-    DecPlan(DecPlan &&) = default;
-    DecPlan &operator=(const DecPlan &) = default;
-    DecPlan &operator=(DecPlan &&) = default;
-    ~DecPlan() {
+constexpr DecLimits DEC_LIMITS{TINY_MAX, GEN_SMALL_MAX, U_MIN_LIST, R2_MIN_LIST, VIDC_LANE_REG_MAX, VIDC_LANE_PAIR_MAX, VIDC_LANE_QUAD_MAX, VIDC_LANE_MAX,
+                               VIDC_LANE_MAX128, VIDC_LANE_MAX64, VIDC_B2L_MAX_LIST, VIDC_B2L_MID_LIST, VIDC_B2L_LOAD, LANE_MIN_LISTS, LANE_MIN_LISTS64,
+                               LANE_MIN_TINY};
+// a plan whose arrays come from and go back to the process-wide vector cache (common.h)
+struct PooledDecPlan : DecPlan {
+    ~PooledDecPlan() {
         vec_pool<uint32_t>().give(std::move(wl)); vec_pool<uint32_t>().give(std::move(item));
         vec_pool<uint64_t>().give(std::move(scratch_off)); vec_pool<uint64_t>().give(std::move(slots_off));
     }
@@ -442,7 +415,7 @@ struct DecPlan {
 
 // device copy of a plan, kept with the compressed object for repeated decode_all calls
 struct DecPlanCache {
-    DecPlan plan;
+    PooledDecPlan plan;
     bool wide = false;  // the stream mode the plan was built for (a context of the other mode builds its own: ADVICE round 4)
     DevBuf<uint32_t> d_wl;
     DevBuf<uint64_t> d_scratch_off, d_slots_off;
@@ -1120,680 +1093,395 @@ int encode_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const ui
     return VIDC_OK;
 }
 
-inline DecClass grp_dec_class(uint64_t n) {
-    const uint32_t f = roc_grp_dec_fbits((uint32_t)n);
-    return f == 0 ? DC_GRP0 : (f == 2 ? DC_GRP2 : (f == 3 ? DC_GRP3 : DC_GRP4));
+// ---- decode.  The planning -- which kernel class takes which work item, where its scratch and slots lie, which queue runs which
+// class -- is roc_dec_plan.h; plan_decode fills its policy from the environment and the context, the dec_* stages below queue what
+// it decided.
+inline DecView dec_view(const vidc_roc *r) {
+    DecView v;
+    v.offsets = r->offsets.data(); v.prec = r->prec.data();
+    v.umax = r->umax.data(); v.n_umax = r->umax.size();
+    v.nwords = r->meta_host ? r->nwords.data() : nullptr;
+    v.order_desc = r->order_desc.data(); v.n_order = r->order_desc.size(); v.order_max_n = r->order_max_n;
+    return v;
 }
-// (the environment is read once per plan, not once per list: three getenv per list were 1 ms of a 65 536-list plan)
-struct DecEnv {
-    bool nb256, pair, quad;
-    bool nb128, mid128;
-    uint64_t pair_min = VIDC_LANE_REG_MAX;  // lists of more than this many ids (up to 512) decode on a PAIR of lanes
-    DecEnv() : nb256(false),  // (256 buckets for the 257..1024-id lists too: measured no better, HISTORY.md)
-               pair(!env_on("VIDC_NO_LANE_PAIR") && !env_on("VIDC_NO_LANE_REG")),
-               // (quads of lanes for 513..1024 ids: opt-in.  Measured slower than the bucket rows: 65 536 x 1024 ids decode in 5.6
-               // instead of 4.1 ms -- 16 lists per 256-VGPR wavefront means two rounds of wavefronts per SIMD --, S2 84 instead of 78 ms)
-               quad(env_on("VIDC_LANE_QUAD") && !env_on("VIDC_NO_LANE_PAIR") && !env_on("VIDC_NO_LANE_REG")) {
-        nb128 = !env_on("VIDC_NO_LANE128");  // lists of 1025..2048 ids on 128 buckets (VIDC_NO_LANE128=1: 256, as before round 4)
-        mid128 = false;  // (the bucket-row lists of up to 1024 ids on 128 buckets: measured no better, HISTORY.md)
-        // VIDC_PAIR_MIN=n (64 .. 256): lists of n+1 .. 256 ids on lane pairs too -- 32 lists per wavefront, i.e. two wavefronts
-        // per SIMD where a call of 65 536 lists has one (measurements: DESIGN section 12)
-        if (const char *e = std::getenv("VIDC_PAIR_MIN")) pair_min = std::min<uint64_t>(VIDC_LANE_REG_MAX, std::max<uint64_t>(TINY_MAX, (uint64_t)std::atoll(e)));
-    }
-};
-inline DecClass dec_class(uint64_t n, uint32_t P, uint64_t u_min, bool f_general, bool allow_lane, bool allow_lane64,
-                          const GrpPolicy *grp, const DecEnv &env) {  // (allow_lane*: mid-size policies; grp: row-per-list kernels wanted)
-    if (n <= TINY_MAX) return DC_TINY;
-    const bool grp_ok = grp && n >= grp->dec_min_n && n <= grp->dec_max_n && P <= 32;
-    if (grp_ok && grp->min_lists == 0) return grp_dec_class(n);  // VIDC_FORCE_GRP: ahead of every other family
-    if (!f_general && n >= u_min) {
-        if (P <= 18) return DC_U18;
-        if (P <= 20) return DC_U20;
-    }
-    if (grp_ok) return grp_dec_class(n);
-    // lists of 257..512 ids: the register decoder on lane pairs (VIDC_NO_LANE_PAIR=1: the bucket-row decoder)
-    if (allow_lane && env.pair && n > env.pair_min && n <= VIDC_LANE_PAIR_MAX) return DC_LANEP;
-    if (allow_lane && env.quad && n > VIDC_LANE_PAIR_MAX && n <= VIDC_LANE_QUAD_MAX) return DC_LANEQ;
-    if (allow_lane && env.nb256 && n > VIDC_LANE_REG_MAX && n <= VIDC_LANE_MAX) return DC_LANE64;
-    if (allow_lane && env.mid128 && n > VIDC_LANE_REG_MAX && n <= VIDC_LANE_MAX) return DC_LANE128;
-    if (allow_lane && n <= VIDC_LANE_MAX) return DC_LANE;
-    if (allow_lane64 && env.nb128 && n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX128) return DC_LANE128;
-    if (allow_lane64 && n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX64) return DC_LANE64;
-    if (n <= GEN_SMALL_MAX) return DC_GSMALL;
-    if (n <= 8192) return DC_G8K;
-    if (n <= 16384) return DC_G16K;
-    if (n <= 32768) return DC_GMID;
-    return DC_GHUGE;
-}
-
 // lists[i] = list number of request item i (a list may appear more than once)
 // only_general: the caller decodes into int32 rows (wide graph rows): only the kernels that honour out_rows -- the tiny
-// and the general wave-per-list decoders -- may be planned
-// whole_sorted: `lists` is 0 .. nlist-1 and r->order_desc holds the same lists longest first
-// wide: the context that will run the plan has a stream per kernel class (8 hardware queues): the row-per-list kernels are
-// only planned then, like the encoder only takes them then (their octaves must overlap)
+// and the general wave-per-list decoders -- may be planned.  whole_sorted, allow_b2, wide: roc_dec_plan.h
 void plan_decode(const vidc_roc *r, const std::vector<uint32_t> &lists, bool rows_flavour, DecPlan &p, bool wide,
                  bool allow_lane = true, bool allow_b2 = true, bool only_general = false, bool whole_sorted = false) {
-    const bool f_general = force_general() || only_general;
+    DecPolicy pol;
+    pol.f_general = force_general() || only_general;
     if (only_general) { allow_lane = false; allow_b2 = false; }
-    const LanePolicy lpol = (allow_lane && !f_general) ? lane_policy() : LANE_NEVER;
-    p.wl.clear(); p.item.clear(); p.scratch_off.clear(); p.slots_off.clear();
-    p.scratch_words = 0; p.slots_words = 0;
-    for (int c = 0; c < DC_COUNT; c++) { p.count[c] = 0; p.sum_n[c] = 0; p.max_n[c] = 0; }
-    p.tiny_lane = false;
-    if (rows_flavour && lane_wanted(lpol, lists.size(), LANE_MIN_TINY)) {
-        // graph rows with the lane-per-row decoder: request order, no scratch, implicit output offsets
-        p.wl = lists;
-        p.count[DC_TINY] = lists.size();
-        p.lean = true;
-        p.tiny_lane = true;
-        return;
-    }
-    p.lean = false;
-    std::vector<uint32_t> cls[DC_COUNT];
-    const uint64_t u_min = U_MIN_LIST;
-    bool allow_lane64 = false;
-    const GrpPolicy gpol = grp_policy();
-    const DecEnv denv;
-    bool use_grp = false;
-    auto len = [&](uint32_t i) { return r->offsets[lists[i] + 1] - r->offsets[lists[i]]; };
-    bool by_length = false;
-    if (whole_sorted && !rows_flavour && !f_general && r->order_desc.size() == lists.size() && r->order_max_n <= VIDC_LANE_MAX64 &&
-        !env_on("VIDC_NO_LENGTH_CLASSES")) {
-        // The whole object, no list beyond the lane classes, and the encoder left its lists ordered by length: the class of a list
-        // is a function of its length (dec_class below looks at the precision only for lists of more than 4096 ids), so every class
-        // is one or two runs of that order.  Replaces three passes over the lists (counts, classification with a push_back per
-        // list, sortedness) of a 65 536-list plan.
-        const std::vector<uint32_t> &order = r->order_desc;
-        const uint64_t *offs = r->offsets.data();
-        const size_t nl = order.size();
-        auto first_le = [&](uint64_t bound) {
-            size_t lo = 0, hi = nl;
-            while (lo < hi) { const size_t mid = (lo + hi) / 2; if (offs[order[mid] + 1] - offs[order[mid]] > bound) lo = mid + 1; else hi = mid; }
-            return lo;
-        };
-        const size_t e4096 = 0, e2048 = first_le(VIDC_LANE_MAX128), e1024 = first_le(VIDC_LANE_MAX), e512 = first_le(VIDC_LANE_PAIR_MAX),
-                     e256 = first_le(denv.pair ? denv.pair_min : VIDC_LANE_REG_MAX), e64 = first_le(TINY_MAX);
-        const uint64_t n_mid64 = e1024 - e4096, n_mid = e64 - e1024, n_tiny = nl - e64;
-        allow_lane = lane_wanted(lpol, n_mid, LANE_MIN_LISTS);
-        allow_lane64 = lane_wanted(lpol, n_mid64, LANE_MIN_LISTS64);
-        p.tiny_lane = lane_wanted(lpol, n_tiny, LANE_MIN_TINY);
-        const bool grp_in_reach = allow_b2 && gpol.dec_min_n <= r->order_max_n && gpol.min_lists != ~0ull;  // (VIDC_FORCE_GRP / VIDC_GRP_DEC_MINN)
-        if ((allow_lane || !n_mid) && (allow_lane64 || !n_mid64) && !grp_in_reach) {
-            by_length = true;
-            auto take = [&](int c, size_t a, size_t b) { if (b > a) cls[c].insert(cls[c].end(), order.begin() + (ptrdiff_t)a, order.begin() + (ptrdiff_t)b); };
-            take(DC_LANE64, e4096, e2048);
-            take(denv.nb128 ? DC_LANE128 : DC_LANE64, e2048, e1024);
-            // 513..1024 | 257..512 | 65..256 (dec_class: pair, quad, 256 buckets, 64 buckets -- in that order)
-            const int mid = denv.nb256 ? DC_LANE64 : (denv.mid128 ? DC_LANE128 : DC_LANE);
-            take(denv.quad ? DC_LANEQ : mid, e1024, e512);
-            take(denv.pair ? DC_LANEP : mid, e512, e256);
-            take(DC_LANE, e256, e64);
-            // (tiny lists in request order, like the per-list loop)
-            if (n_tiny) {
-                if (n_tiny == nl) { cls[DC_TINY].resize(nl); std::iota(cls[DC_TINY].begin(), cls[DC_TINY].end(), 0u); }
-                else {
-                    cls[DC_TINY].assign(order.begin() + (ptrdiff_t)e64, order.end());
-                    std::sort(cls[DC_TINY].begin(), cls[DC_TINY].end());
-                }
-            }
-        }
-    }
-    if (!by_length) {
-    {
-        uint64_t n_mid = 0, n_mid64 = 0, n_tiny = 0, n_grp = 0;
-        for (uint32_t l : lists) {
-            const uint64_t n = r->offsets[l + 1] - r->offsets[l];
-            n_tiny += n <= TINY_MAX;
-            n_mid += n > TINY_MAX && n <= VIDC_LANE_MAX;
-            n_mid64 += n > VIDC_LANE_MAX && n <= VIDC_LANE_MAX64;
-            n_grp += n >= gpol.dec_min_n && n <= gpol.dec_max_n;
-        }
-        use_grp = allow_b2 && !f_general && !rows_flavour && n_grp && n_grp >= gpol.min_lists &&
-                  (wide || gpol.min_lists == 0);
-        allow_lane = lane_wanted(lpol, n_mid, LANE_MIN_LISTS);
-        allow_lane64 = lane_wanted(lpol, n_mid64, LANE_MIN_LISTS64);
-        p.tiny_lane = lane_wanted(lpol, rows_flavour ? lists.size() : n_tiny, LANE_MIN_TINY);
-    }
-    {
-        // (the classes that can hold most lists of a big call grow once, not by doubling)
-        const uint64_t nl = lists.size();
-        if (nl >= 4096) for (int c : {(int)DC_TINY, (int)DC_LANE, (int)DC_GSMALL}) cls[c].reserve(nl);
-    }
-    for (uint32_t i = 0; i < lists.size(); i++) {
-        uint32_t l = lists[i];
-        uint64_t n = r->offsets[l + 1] - r->offsets[l];
-        cls[rows_flavour ? DC_TINY : dec_class(n, r->prec[l], u_min, f_general, allow_lane, allow_lane64, use_grp ? &gpol : nullptr, denv)].push_back(i);
-    }
-    for (int c = 0; c < DC_COUNT; c++) {
-        if (c != DC_TINY && cls[c].size() > 1) {  // counting sort by length, longest first (stable)
-            uint64_t maxlen = 0, prev = ~0ull;
-            bool sorted_already = true;  // equal-sized lists, or an index whose lists come longest first: nothing to do
-            for (uint32_t i : cls[c]) {
-                const uint64_t n = len(i);
-                maxlen = std::max<uint64_t>(maxlen, n);
-                sorted_already &= n <= prev;
-                prev = n;
-            }
-            if (sorted_already) continue;
-            std::vector<uint32_t> start(maxlen + 2, 0), sorted(cls[c].size());
-            for (uint32_t i : cls[c]) start[maxlen - len(i) + 1]++;
-            for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
-            for (uint32_t i : cls[c]) sorted[start[maxlen - len(i)]++] = i;
-            cls[c].swap(sorted);
-        }
-    }
-    }  // per-list classification
-    // The longest general chains (precision above 20 bits) take k_roc_decode_b2 under the rule of the encoder's
-    // k_roc_encode_r2: only when every chain at least half as long as the longest one gets it (<= B2_CAP of them).
-    if (allow_b2 && !f_general && !rows_flavour && !old_u_kernels() && !env_on("VIDC_NO_R2")) {
-        const int order_[4] = {DC_GHUGE, DC_GMID, DC_G16K, DC_G8K};
-        uint64_t n_top = 0;
-        for (int c : order_)
-            if (!cls[c].empty()) { n_top = len(cls[c][0]); break; }
-        size_t n_long = 0;
-        bool stop = false;
-        for (int c : order_) {
-            for (uint32_t i : cls[c]) {
-                if (2 * len(i) < n_top || n_long > B2_CAP) { stop = true; break; }
-                n_long++;
-            }
-            if (stop) break;
-        }
-        size_t b2_cap = B2_CAP;
-        // More long chains than the cap (S2: 1754 lists of 32 769..65 536 ids and 2666 of 16 385..32 768): round 3 gave the `cap`
-        // longest ones to this kernel and left the rest on the general decoder, whose step under load is ~1.1 us against ~0.65
-        // here.  Measured in round 4 (S2 decode, kernels): 1024 chains 77-79 ms, all 1754 lists beyond 32 768 ids 74, these and
-        // the 2666 lists of 16 385..32 768 ids 71-73; the lists of 8193..16 384 ids too (instead of the row-per-list kernel): 80-90.
-        // So every list beyond 16 384 ids takes it, up to B2_TOP_CAP chains (20 per CU of an MI355X: 8 KiB of LDS each).
-        const bool top_only = n_top && n_long > b2_cap;
-        if (top_only) b2_cap = B2_TOP_CAP;
-        if (n_top && (n_long <= b2_cap || top_only))
-            for (int c : order_) {  // longest first; a list that does not qualify stays where it is
-                if (top_only && c != DC_GHUGE && c != DC_GMID) break;
-                std::vector<uint32_t> keep;
-                for (uint32_t i : cls[c]) {
-                    const uint32_t P = r->prec[lists[i]];
-                    // (beyond ~100 000 ids a 64-member row overflows too often: average bucket load n / 4096)
-                    // (shorter than B2_MIN_LIST: the general decoder keeps the member rows of such a list in LDS, while 1 MiB of
-                    // sparse rows per list -- 1 GiB for a thousand lists -- makes every step of this kernel an HBM miss:
-                    // 1024 x 977 ids decoded in 0.53 instead of 0.50 ms)
-                    if (cls[DC_B2].size() < b2_cap && len(i) <= 98304 && len(i) > B2_MIN_LIST && P >= 12 && P <= 31) cls[DC_B2].push_back(i);
-                    else keep.push_back(i);
-                }
-                cls[c].swap(keep);
-            }
-        // short lists (257..4096 ids) of a call with few lists: the same loop with 32 .. 256 buckets and their 64-member rows in
-        // LDS (8.3 / 16.5 / 33 / 66 KiB per chain) -- if the chains taken so far and all of these fit at 150 KiB of LDS and 16
-        // wavefronts (128 VGPRs each) per CU: 1024 chains of 33 KiB, 4096 of 8.3 KiB on 256 CUs.  The bucket count
-        // follows the expected load: ids are spread over (max id >> shift) + 1 buckets, half of them in the worst case when the
-        // maximum is unknown (imported streams); at <= 30 ids per bucket a 64-member row practically never overflows.
-        {
-            auto buckets_for = [&](uint32_t i) -> uint32_t {
-                const uint64_t n = len(i);
-                const uint32_t l = lists[i], P = r->prec[l];
-                if (n <= R2_MIN_LIST || n > VIDC_B2L_MAX_LIST || P > 31) return 0u;
-                for (uint32_t bk : {32u, 64u, 128u, 256u}) {
-                    const uint32_t bbits = bk == 32u ? 5u : (bk == 64u ? 6u : (bk == 128u ? 7u : 8u)), bsh = P > bbits ? P - bbits : 0u;
-                    const uint32_t mx = (l < r->umax.size() && r->umax[l]) ? r->umax[l] : ((P ? (1u << (P - 1u)) : 1u));
-                    const uint64_t eff = std::min<uint64_t>(bk, (uint64_t)(mx >> bsh) + 1u);
-                    if (n <= VIDC_B2L_LOAD * eff) return bk;
-                }
-                return 0u;
-            };
-            size_t units = 0, n_el = 0;  // (units of 8.25 KiB of LDS: 18 per CU; a chain with its rows in memory takes one)
-            bool longer_left = false;   // a longer chain that stays on the general kernel decides the call anyway
-            for (int c : order_) longer_left |= !cls[c].empty();
-            for (uint32_t i : cls[DC_GSMALL]) {
-                const uint32_t bk = buckets_for(i);
-                units += bk / 32u;
-                n_el += bk != 0;
-                longer_left |= !bk && len(i) > VIDC_B2L_MID_LIST;
-            }
-            if (n_el && !longer_left && cls[DC_B2].size() + units <= b2_cap * 9 / 2 && cls[DC_B2].size() + n_el <= b2_cap * 4) {
-                std::vector<uint32_t> keep;
-                for (uint32_t i : cls[DC_GSMALL]) {
-                    const uint32_t bk = buckets_for(i);
-                    if (bk == 32u) cls[DC_B2T].push_back(i);
-                    else if (bk == 64u) cls[DC_B2S].push_back(i);
-                    else if (bk == 128u) cls[DC_B2L].push_back(i);
-                    else if (bk == 256u) cls[DC_B2M].push_back(i);
-                    else keep.push_back(i);
-                }
-                cls[DC_GSMALL].swap(keep);
-            }
-        }
-    }
-    // LDS member rows for the short general lists only while all of them are resident at four per CU: beyond that the 33 KiB
-    // per wavefront cost more in occupancy than the global rows cost in traffic (6000 x 300 ids: 0.86 vs 0.3 ms)
-    p.gsmall_lrows = cls[DC_GSMALL].size() <= B2_CAP;
-    // one pass per class over its work items: work list, per-class totals, scratch / slot offsets (65 536 lists: the two
-    // passes with push_back this replaces were half of the planner's time)
-    size_t total_items = 0;
-    for (int c = 0; c < DC_COUNT; c++) total_items += cls[c].size();
-    p.item = vec_pool<uint32_t>().take(total_items); p.item.resize(total_items);
-    p.wl = vec_pool<uint32_t>().take(total_items); p.wl.resize(total_items);
-    p.scratch_off = vec_pool<uint64_t>().take(total_items); p.scratch_off.resize(total_items);
-    p.slots_off = vec_pool<uint64_t>().take(total_items); p.slots_off.resize(total_items);
-    uint64_t so = 0, sl = 0;
-    size_t k = 0;
-    {   // VIDC_LANE_ALIGN=4 / 16 (measurement switch): bucket rows of the lane decoders on 16- / 64-byte boundaries
-        const char *ae = std::getenv("VIDC_LANE_ALIGN");
-        p.lane_align = ae ? (std::atoi(ae) >= 16 ? 16u : 4u) : VIDC_LANE_ALIGN_DEFAULT;
-    }
-    const uint64_t la = p.lane_align;
-    const uint64_t *offs = r->offsets.data();
-    const bool have_nwords = r->meta_host;
-    for (int c = 0; c < DC_COUNT; c++) {
-        p.count[c] = cls[c].size();
-        uint64_t sum_n = 0, max_n = 0;
-        // re-spill scratch of the decoder stack (== roc_dec_stack_cap in the kernels); the lane-per-list decoders
-        // keep what they push in LDS
-        const bool stack_scratch = c != DC_LANE && c != DC_LANE64 && c != DC_LANE128 && c < DC_GRP0;
-        for (const uint32_t i : cls[c]) {
-            const uint32_t l = lists[i];
-            const uint64_t n = offs[l + 1] - offs[l];
-            p.item[k] = i;
-            p.wl[k] = l;
-            sum_n += n;
-            max_n = std::max(max_n, n);
-            p.scratch_off[k] = so;
-            if (stack_scratch) so += roc_dec_stack_cap((uint32_t)n, have_nwords ? r->nwords[l] : 0u);
-            uint64_t slot = sl;
-            if (c == DC_LANEP || c == DC_LANEQ) {
-                slot = 0;  // no scratch of any kind
-            } else if (c == DC_LANE) {
-                sl = (sl + la - 1) & ~(la - 1);  // rows are read as uint4
-                slot = sl;
-                sl += 64ull * roc_lane_cap_nb<64>((uint32_t)n, p.lane_align);
-            } else if (c == DC_LANE64) {
-                sl = (sl + la - 1) & ~(la - 1);
-                slot = sl;
-                sl += 256ull * roc_lane_cap_nb<256>((uint32_t)n, p.lane_align);
-            } else if (c == DC_LANE128) {
-                sl = (sl + la - 1) & ~(la - 1);
-                slot = sl;
-                sl += 128ull * roc_lane_cap_nb<128>((uint32_t)n, p.lane_align);
-            } else if (c >= DC_GRP0) {
-                sl = (sl + 15) & ~(uint64_t)15;  // member rows of 32 .. 96 u32: 64-byte aligned
-                slot = sl;
-                sl += roc_grp_dec_slots((uint32_t)n);
-            } else if (c == DC_U18 || c == DC_U20) {
-                sl += n;  // duplicate side list
-            } else if (c == DC_B2) {
-                sl = (sl + 63) & ~(uint64_t)63;  // 4096 rows of 64 members
-                slot = sl;
-                sl += 4096ull * 64ull;
-            } else if (c == DC_GSMALL && p.gsmall_lrows) {
-                sl += n;  // overflow list only: the member rows are in LDS
-            } else if (c >= DC_GSMALL && c <= DC_GHUGE) {
-                const uint32_t fb = roc_dec_fine_bits((uint32_t)n, r->prec[l] > 32 ? 32 : r->prec[l]);
-                sl += ((uint64_t)1 << fb) * roc_dec_cap((uint32_t)n) + n;
-            }
-            p.slots_off[k] = slot;
-            k++;
-        }
-        p.sum_n[c] += sum_n;
-        p.max_n[c] = std::max<uint64_t>(p.max_n[c], max_n);
-    }
-    p.scratch_words = so;
-    p.slots_words = sl;
+    pol.lpol = (allow_lane && !pol.f_general) ? lane_policy() : LANE_NEVER;
+    if (plan_decode_lean(lists, rows_flavour, pol, DEC_LIMITS, p)) return;
+    pol.wide = wide;
+    pol.gpol = grp_policy();
+    pol.pair = !env_on("VIDC_NO_LANE_PAIR") && !env_on("VIDC_NO_LANE_REG");
+    pol.quad = env_on("VIDC_LANE_QUAD") && pol.pair;
+    pol.nb128 = !env_on("VIDC_NO_LANE128");
+    pol.pair_min = VIDC_LANE_REG_MAX;
+    if (const char *e = std::getenv("VIDC_PAIR_MIN")) pol.pair_min = std::min<uint64_t>(VIDC_LANE_REG_MAX, std::max<uint64_t>(TINY_MAX, (uint64_t)std::atoll(e)));
+    pol.no_length_classes = whole_sorted && env_on("VIDC_NO_LENGTH_CLASSES");
+    pol.old_u = old_u_kernels();
+    pol.no_r2 = env_on("VIDC_NO_R2");
+    const char *ae = std::getenv("VIDC_LANE_ALIGN");
+    pol.lane_align = ae ? (std::atoi(ae) >= 16 ? 16u : 4u) : VIDC_LANE_ALIGN_DEFAULT;
+    const size_t ni = lists.size();
+    p.item = vec_pool<uint32_t>().take(ni); p.wl = vec_pool<uint32_t>().take(ni);
+    p.scratch_off = vec_pool<uint64_t>().take(ni); p.slots_off = vec_pool<uint64_t>().take(ni);
+    plan_decode_classes(dec_view(r), lists, rows_flavour, allow_b2, whole_sorted, pol, DEC_LIMITS, p);
 }
 
-
-
-int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64_t *out_off_host, uint64_t *d_out,
-                int32_t *d_out_rows, uint32_t K, const struct DecPlanCache *cache = nullptr) {
-    VIDC_HIP(hipSetDevice(ctx->device));
-    const size_t nwork = p.implicit ? (size_t)p.implicit : p.wl.size();
-    if (nwork == 0) { ctx->last_kernel_ms = 0; return VIDC_OK; }
-    HostTrace tr("roc decode");
-    Scratch s_wl, s_scr_off, s_slots_off, s_scr, s_slots, s_out_off, s_end, s_sum;
-    Pinned h_up;
-    const uint32_t *d_wl;
+// One decode call: its arguments, its scratch and staging blocks, the kernels' common arguments, and what one stage leaves for the
+// next.  The stages (dec_*) run in the order decode_impl lists them.
+struct DecodeCall {
+    vidc_ctx *ctx; const vidc_roc *r; const DecPlan &p;
+    const uint64_t *out_off_host; uint64_t *d_out; int32_t *d_out_rows; uint32_t K;
+    const DecPlanCache *cache;
+    size_t nwork;
+    HostTrace tr{"roc decode"};
+    Scratch s_wl, s_scr_off, s_slots_off, s_scr, s_slots, s_out_off, s_end;
+    Pinned h_up, h_sum;
+    const uint32_t *d_wl = nullptr;
     const uint64_t *d_scr_off = nullptr, *d_slots_off = nullptr;
-    if (cache) {
-        d_wl = cache->d_wl.p; d_scr_off = cache->d_scratch_off.p; d_slots_off = cache->d_slots_off.p;
+    uint32_t *d_status = nullptr;
+    RocDecArgs a{};                   // what every launch of the call shares
+    size_t base[DC_COUNT] = {};       // first work item of every class
+    int order[DC_COUNT] = {};         // the classes, longest estimated duration first
+    hipStream_t stream_of[DC_COUNT] = {};
+    std::vector<SchedEntry> sched;    // VIDC_DEC_SCHED
+    int chain_class = -1;
+    uint32_t aux_used = 0;            // only the auxiliary streams that carry a class of this call are forked and joined
+    EventTimer t;
+    unsigned long long *sum = nullptr;  // the status summary, in pinned memory
+    DecodeCall(vidc_ctx *ctx_, const vidc_roc *r_, const DecPlan &p_, const uint64_t *out_off_host_, uint64_t *d_out_, int32_t *d_out_rows_,
+               uint32_t K_, const DecPlanCache *cache_, size_t nwork_)
+        : ctx(ctx_), r(r_), p(p_), out_off_host(out_off_host_), d_out(d_out_), d_out_rows(d_out_rows_), K(K_), cache(cache_), nwork(nwork_), t(ctx_) {}
+};
+constexpr uint32_t DEC_RETRY_SLOTS = 504;  // list numbers of handed-back lists behind the eight summary words
+
+// work list, scratch / slot offsets and output offsets to the device (a cached plan's are there already), the call's scratch,
+// and the kernels' common arguments
+int dec_upload(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx; const vidc_roc *r = c.r; const DecPlan &p = c.p;
+    const size_t nwork = c.nwork;
+    if (c.cache) {  // (decode_all: the object's own offsets place the output)
+        c.d_wl = c.cache->d_wl.p; c.d_scr_off = c.cache->d_scratch_off.p; c.d_slots_off = c.cache->d_slots_off.p;
     } else if (p.implicit) {
-        d_wl = p.order_dev;
+        c.d_wl = p.order_dev;
     } else {
         // one pinned staging block for everything that goes up: work list | scratch offsets | slot offsets | out offsets
         const size_t n8 = p.lean ? 0 : nwork;
-        VIDC_TRY(h_up.get(ctx, nwork * 4 + 8 + n8 * 24));
-        uint32_t *h_wl = h_up.as<uint32_t>();
-        uint64_t *h_64 = (uint64_t *)((char *)h_up.p + ((nwork * 4 + 7) & ~(size_t)7));
+        VIDC_TRY(c.h_up.get(ctx, nwork * 4 + 8 + n8 * 24));
+        uint32_t *h_wl = c.h_up.as<uint32_t>();
+        uint64_t *h_64 = (uint64_t *)((char *)c.h_up.p + ((nwork * 4 + 7) & ~(size_t)7));
         std::memcpy(h_wl, p.wl.data(), nwork * 4);
-        VIDC_TRY(s_wl.get(ctx, nwork * 4));
-        VIDC_HIP(hipMemcpyAsync(s_wl.p, h_wl, nwork * 4, hipMemcpyHostToDevice, ctx->stream));
-        d_wl = s_wl.as<uint32_t>();
+        VIDC_TRY(c.s_wl.get(ctx, nwork * 4));
+        VIDC_HIP(hipMemcpyAsync(c.s_wl.p, h_wl, nwork * 4, hipMemcpyHostToDevice, ctx->stream));
+        c.d_wl = c.s_wl.as<uint32_t>();
         if (!p.lean) {
             std::memcpy(h_64, p.scratch_off.data(), nwork * 8);
             std::memcpy(h_64 + nwork, p.slots_off.data(), nwork * 8);
-            VIDC_TRY(s_scr_off.get(ctx, nwork * 8));
-            VIDC_TRY(s_slots_off.get(ctx, nwork * 8));
-            VIDC_HIP(hipMemcpyAsync(s_scr_off.p, h_64, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
-            VIDC_HIP(hipMemcpyAsync(s_slots_off.p, h_64 + nwork, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
-            d_scr_off = s_scr_off.as<uint64_t>(); d_slots_off = s_slots_off.as<uint64_t>();
-            if (out_off_host) {
-                std::memcpy(h_64 + 2 * nwork, out_off_host, nwork * 8);
-                VIDC_TRY(s_out_off.get(ctx, nwork * 8));
-                VIDC_HIP(hipMemcpyAsync(s_out_off.p, h_64 + 2 * nwork, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
+            VIDC_TRY(c.s_scr_off.get(ctx, nwork * 8));
+            VIDC_TRY(c.s_slots_off.get(ctx, nwork * 8));
+            VIDC_HIP(hipMemcpyAsync(c.s_scr_off.p, h_64, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
+            VIDC_HIP(hipMemcpyAsync(c.s_slots_off.p, h_64 + nwork, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
+            c.d_scr_off = c.s_scr_off.as<uint64_t>(); c.d_slots_off = c.s_slots_off.as<uint64_t>();
+            if (c.out_off_host) {
+                std::memcpy(h_64 + 2 * nwork, c.out_off_host, nwork * 8);
+                VIDC_TRY(c.s_out_off.get(ctx, nwork * 8));
+                VIDC_HIP(hipMemcpyAsync(c.s_out_off.p, h_64 + 2 * nwork, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
             }
         }
     }
-    if (cache && out_off_host) {
-        VIDC_TRY(h_up.get(ctx, nwork * 8));
-        std::memcpy(h_up.p, out_off_host, nwork * 8);
-        VIDC_TRY(s_out_off.get(ctx, nwork * 8));
-        VIDC_HIP(hipMemcpyAsync(s_out_off.p, h_up.p, nwork * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    VIDC_TRY(s_scr.get(ctx, p.scratch_words * 4));
-    VIDC_TRY(s_slots.get(ctx, p.slots_words * 4));
-    VIDC_TRY(s_end.get(ctx, r->nlist * 8 + 64));  // end states | statuses | summary accumulators: one block, one memset
-    VIDC_HIP(hipMemsetAsync(s_end.p, 0, r->nlist * 8 + 64, ctx->stream));
-    uint32_t *const d_status = s_end.as<uint32_t>() + r->nlist;
-    tr.mark("scratch + uploads");
-    RocDecArgs a{};
+    VIDC_TRY(c.s_scr.get(ctx, p.scratch_words * 4));
+    VIDC_TRY(c.s_slots.get(ctx, p.slots_words * 4));
+    VIDC_TRY(c.s_end.get(ctx, r->nlist * 8 + 64));  // end states | statuses | summary accumulators: one block, one memset
+    VIDC_HIP(hipMemsetAsync(c.s_end.p, 0, r->nlist * 8 + 64, ctx->stream));
+    c.d_status = c.s_end.as<uint32_t>() + r->nlist;
+    c.tr.mark("scratch + uploads");
+    RocDecArgs &a = c.a;
     a.offsets = r->d_offsets.p;
     a.heads = r->d_heads.p; a.prec = r->d_prec.p; a.nwords = r->d_nwords.p; a.draws = r->d_draws.p;
     a.words = r->d_words.p; a.word_off = r->d_word_off.p;
-    a.out = d_out; a.out_rows = d_out_rows; a.K = K;
+    a.out = c.d_out; a.out_rows = c.d_out_rows; a.K = c.K;
     a.out_by_list = (p.implicit && p.order_dev && !p.order_req) ? 1u : 0u;
-    a.scratch_words = s_scr.as<uint32_t>();
-    a.slots = s_slots.as<uint32_t>();
-    a.end_state = s_end.as<uint32_t>(); a.status = d_status;
+    a.scratch_words = c.s_scr.as<uint32_t>();
+    a.slots = c.s_slots.as<uint32_t>();
+    a.end_state = c.s_end.as<uint32_t>(); a.status = c.d_status;
     a.mt = ctx->d_mt;
-
-    size_t base[DC_COUNT];
-    {
-        size_t acc = 0;
-        for (int c = 0; c < DC_COUNT; c++) { base[c] = acc; acc += p.count[c]; }
-    }
-    EventTimer t = EventTimer::started(ctx);
-    if (p.order_build) {  // rows by edge count, most edges first: histogram per workgroup, segment starts, scatter
-        uint32_t *part = const_cast<uint32_t *>(p.order_dev) + nwork;
-        hipLaunchKernelGGL(k_rows_order_hist, dim3(VIDC_ORDER_BLOCKS), dim3(256), 0, ctx->stream, r->d_offsets.p, (uint32_t)nwork, part);
-        hipLaunchKernelGGL(k_rows_order_starts, dim3(1), dim3(128), 0, ctx->stream, part);
-        hipLaunchKernelGGL(k_rows_order_scatter, dim3(VIDC_ORDER_BLOCKS), dim3(256), 0, ctx->stream, r->d_offsets.p, (uint32_t)nwork, part,
-                           const_cast<uint32_t *>(p.order_dev));
-        VIDC_HIP(hipGetLastError());
-    }
-    // classes run concurrently: the longest chains on the caller's stream, the rest on the auxiliary streams (fork below)
-    // The lane-pair register decoder goes FIRST and alone when the call has other work for the whole machine: its wavefronts
-    // need 256 VGPRs, and next to memory-bound classes that fill the SIMDs with small wavefronts they wait for register
-    // space -- 6 ms alone on S2's 217 M ids, 73 ms as the tail of the call when everything starts at once.
-    // (measured on S2: 92-95 ms of decode against 86-87 with everything started at once -- the other classes take their ~85 ms
-    // whether or not these lists are among them; opt-in for measurements)
-    const bool pair_first = p.count[DC_LANEP] && false;  // (the pair class first: measured no better, HISTORY.md)
-    // Stream assignment: a class's kernel lasts about max(its longest chain, its share of the machine); classes are
-    // taken longest first and each goes to the stream that frees up first (LPT over 3 streams).  A fixed
-    // assignment left three general classes back to back on one stream on S2 (70 + 45 + 18 ms) while the
-    // others had drained.
-    int order[DC_COUNT];
-    hipStream_t stream_of[DC_COUNT];
-    {
-        double est[DC_COUNT];
-        for (int c = 0; c < DC_COUNT; c++) {
-            order[c] = c;
-            const bool u = c == DC_U18 || c == DC_U20 || c == DC_B2 || c == DC_B2T || c == DC_B2S || c == DC_B2L || c == DC_B2M, lane = c == DC_LANE || c == DC_LANE64 || c == DC_LANE128 || c == DC_LANEP || c == DC_LANEQ;
-            const bool grpc = c >= DC_GRP0 && c <= DC_GRP4;
-            // (constants fitted to the S2 timeline: general kernels ~2.5 G steps/s while they share the machine)
-            const double step_us = u ? 0.4 : (lane ? 2.5 : (c == DC_TINY ? 0.5 : (grpc ? 1.5 : 1.2)));       // one chain step
-            const double rate = u ? 0.6e3 : (lane ? 16e3 : (c == DC_TINY ? 30e3 : (grpc ? 12e3 : 2.5e3)));     // steps / us, all CUs
-            est[c] = std::max((double)p.max_n[c] * step_us, (double)p.sum_n[c] / rate);
-        }
-        std::sort(order, order + DC_COUNT, [&](int x, int y) { return est[x] > est[y]; });
-        // three streams: a 4th one did not run concurrently (HIP maps streams onto 4 hardware queues and the
-        // process has other streams; the kernels of aux[2] started when the main stream's had finished)
-        double load[VIDC_NAUX + 1] = {};
-        // (wide: a stream per class.  S2 decode by stream count, final kernel set (row decoder up to 16 384 ids, lane-pair register
-        // decoder): 78-79 ms with 8, 84-85 with 6 -- a class queued behind the lane-pair launch, whose 256-VGPR wavefronts are slow
-        // to find room, becomes the tail; without that decoder 81-82 / 83-84)
-        int nq = ctx->wide ? VIDC_NAUX + 1 : 3;
-        if (const char *e = std::getenv("VIDC_DEC_NQ")) nq = std::max(1, std::min(ctx->naux() + 1, std::atoi(e)));
-        if (env_on("VIDC_SERIAL")) nq = 1;  // measurements: one class after the other
-        for (int k = 0; k < DC_COUNT; k++) {
-            const int c = order[k];
-            if (!p.count[c]) continue;
-            if (pair_first && c == DC_LANEP) { stream_of[c] = ctx->stream; continue; }
-            int best = 0;
-            for (int q = 1; q < nq; q++)
-                if (load[q] < load[best]) best = q;
-            stream_of[c] = best == 0 ? ctx->stream : ctx->aux[best - 1];
-            load[best] += est[c] + 1.0;
-        }
-    }
+    size_t acc = 0;
+    for (int k = 0; k < DC_COUNT; k++) { c.base[k] = acc; acc += p.count[k]; }
+    return VIDC_OK;
+}
+// rows by edge count, most edges first: histogram per workgroup, segment starts, scatter
+int dec_build_row_order(DecodeCall &c) {
+    const DecPlan &p = c.p;
+    if (!p.order_build) return VIDC_OK;
+    hipStream_t st = c.ctx->stream;
+    const uint32_t nwork = (uint32_t)c.nwork;
+    uint32_t *part = const_cast<uint32_t *>(p.order_dev) + c.nwork;
+    hipLaunchKernelGGL(k_rows_order_hist, dim3(VIDC_ORDER_BLOCKS), dim3(256), 0, st, c.r->d_offsets.p, nwork, part);
+    hipLaunchKernelGGL(k_rows_order_starts, dim3(1), dim3(128), 0, st, part);
+    hipLaunchKernelGGL(k_rows_order_scatter, dim3(VIDC_ORDER_BLOCKS), dim3(256), 0, st, c.r->d_offsets.p, nwork, part, const_cast<uint32_t *>(p.order_dev));
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+// classes run concurrently: the longest chains on the caller's stream, the rest on the auxiliary streams (dec_assign_queues:
+// queue 0 = the caller's stream, i = auxiliary stream i - 1)
+int dec_assign_streams(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx; const DecPlan &p = c.p;
+    // three streams: a 4th one did not run concurrently (HIP maps streams onto 4 hardware queues and the
+    // process has other streams; the kernels of aux[2] started when the main stream's had finished)
+    // (wide: a stream per class.  S2 decode by stream count, final kernel set (row decoder up to 16 384 ids, lane-pair register
+    // decoder): 78-79 ms with 8, 84-85 with 6 -- a class queued behind the lane-pair launch, whose 256-VGPR wavefronts are slow
+    // to find room, becomes the tail; without that decoder 81-82 / 83-84)
+    int nq = ctx->wide ? VIDC_NAUX + 1 : 3;
+    if (const char *e = std::getenv("VIDC_DEC_NQ")) nq = std::max(1, std::min(ctx->naux() + 1, std::atoi(e)));
+    if (env_on("VIDC_SERIAL")) nq = 1;  // measurements: one class after the other
+    int queue_of[DC_COUNT];
+    dec_assign_queues(p.count, p.sum_n, p.max_n, nq, c.order, queue_of);
+    for (int k = 0; k < DC_COUNT; k++) c.stream_of[k] = queue_of[k] > 0 ? ctx->aux[queue_of[k] - 1] : ctx->stream;
     ctx->chain_info[1][0] = ctx->chain_info[1][1] = ctx->chain_info[1][2] = ctx->chain_info[1][3] = 0;
     ctx->phase_ms[VIDC_PHASE_ROC_DECODE_CHAIN] = 0;
-    const int chain_class = p.count[DC_U20] ? DC_U20 : (p.count[DC_U18] ? DC_U18 : -1);
-    auto launch = [&](int c) -> int {
-        if (!p.count[c]) return VIDC_OK;
-        hipStream_t st_ = stream_of[c];
-        if (c == chain_class) {
-            ctx->chain_info[1][0] = p.sum_n[c]; ctx->chain_info[1][1] = p.count[c]; ctx->chain_info[1][2] = p.max_n[c];
-            ctx->chain_info[1][3] = c == DC_U20 ? 20 : 18;
-            VIDC_HIP(hipEventRecord(ctx->ev_chain[0], st_));
-        }
-        RocDecArgs b = a;
-        b.worklist = d_wl ? d_wl + base[c] : nullptr;
-        b.nwork = (uint32_t)p.count[c];
-        b.out_off = (out_off_host && !p.lean) ? s_out_off.as<uint64_t>() + base[c] : nullptr;
-        b.scratch_off = d_scr_off ? d_scr_off + base[c] : nullptr;
-        b.slots_off = d_slots_off ? d_slots_off + base[c] : nullptr;
-        b.row_align = p.lane_align;
-        switch (c) {
-            case DC_TINY:
-                if (p.tiny_lane) {  // one list per lane (roc_lane.h)
-                    const dim3 grid((b.nwork + 63u) / 64u);
-                    const LaneDiv *dt = (const LaneDiv *)ctx->d_ltab;
-                    if (d_out_rows) hipLaunchKernelGGL(k_roc_decode_tiny_lane<true>, grid, dim3(64), 0, st_, b, dt);
-                    else hipLaunchKernelGGL(k_roc_decode_tiny_lane<false>, grid, dim3(64), 0, st_, b, dt);
-                } else if (d_out_rows) hipLaunchKernelGGL(k_roc_decode_tiny<true>, dim3(b.nwork), dim3(64), 0, st_, b);
-                else hipLaunchKernelGGL(k_roc_decode_tiny<false>, dim3(b.nwork), dim3(64), 0, st_, b);
-                break;
-            case DC_U18:
-                if (old_u_kernels()) hipLaunchKernelGGL(k_roc_decode_u<18>, dim3(b.nwork), dim3(64), UGeom<18>::LDS_BYTES, st_, b);
-                else hipLaunchKernelGGL(k_roc_decode_u2<18>, dim3(b.nwork), dim3(64), U2Geom<18>::LDS_BYTES, st_, b,
-                                        (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_U20:
-                if (old_u_kernels()) {
-                    VIDC_TRY(set_big_lds((const void *)k_roc_decode_u<20>, UGeom<20>::LDS_BYTES));
-                    hipLaunchKernelGGL(k_roc_decode_u<20>, dim3(b.nwork), dim3(64), UGeom<20>::LDS_BYTES, st_, b);
-                } else {
-                    VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20>, U2Geom<20>::LDS_BYTES));
-                    hipLaunchKernelGGL(k_roc_decode_u2<20>, dim3(b.nwork), dim3(64), U2Geom<20>::LDS_BYTES, st_, b,
-                                       (const U2Div *)ctx->d_u2tab);
-                }
-                break;
-            case DC_GSMALL:
-                if (p.gsmall_lrows)  // member rows in LDS: 1 + 32 KiB
-                    hipLaunchKernelGGL((k_roc_decode_gen<uint16_t, true>), dim3(b.nwork), dim3(64), 512 * 2 + 512 * VIDC_DEC_CAP * 4, st_,
-                                       b, 512u, VIDC_DEC_CAP);
-                else
-                    hipLaunchKernelGGL(k_roc_decode_gen<uint16_t>, dim3(b.nwork), dim3(64), 512 * 2, st_, b, 512u, VIDC_DEC_CAP);
-                break;
-            case DC_LANE: {  // 12.5 KiB of LDS per wavefront
-                b.lpw = lane_lists_per_wave(ctx, b.nwork, 24);
-                // lists are sorted longest first: those of <= 256 ids (the tail of the work list, from a wavefront
-                // boundary on) take the decoder that keeps the decoded ids in registers
-                uint32_t n_big = b.nwork;
-                if (!std::getenv("VIDC_NO_LANE_REG") && !p.wl.empty()) {
-                    const uint32_t *wl0 = p.wl.data() + base[c];
-                    n_big = (uint32_t)(std::partition_point(wl0, wl0 + b.nwork, [&](uint32_t l) {
-                                           return r->offsets[l + 1] - r->offsets[l] > VIDC_LANE_REG_MAX;
-                                       }) - wl0);
-                    n_big = std::min<uint32_t>(b.nwork, (n_big + b.lpw - 1u) / b.lpw * b.lpw);
-                }
-                RocDecArgs b2 = b;
-                b2.worklist = b.worklist + n_big; b2.nwork = b.nwork - n_big;
-                if (b2.out_off) b2.out_off += n_big;
-                b.nwork = n_big;
-                if (b.nwork && env_on("VIDC_LANE_LOOP"))
-                    hipLaunchKernelGGL((k_roc_decode_lane<64, false>), dim3(lane_grid((b.nwork + b.lpw - 1u) / b.lpw)), dim3(64), 0, st_, b,
-                                       (const LaneDiv *)ctx->d_ltab);
-                else if (b.nwork)
-                    hipLaunchKernelGGL((k_roc_decode_lane<64, true>), dim3(lane_grid((b.nwork + b.lpw - 1u) / b.lpw)), dim3(64), 0, st_, b,
-                                       (const LaneDiv *)ctx->d_ltab);
-                if (b2.nwork)
-                    hipLaunchKernelGGL(k_roc_decode_lane_reg<VIDC_LANE_REG_EL>, dim3((b2.nwork + b2.lpw - 1u) / b2.lpw), dim3(64), 0, st_,
-                                       b2, (const LaneDiv *)ctx->d_ltab);
-                break;
-            }
-            case DC_LANE64:  // 26.5 KiB of LDS per wavefront
-                b.lpw = lane_lists_per_wave(ctx, b.nwork, 7);
-                if (env_on("VIDC_LANE_LOOP"))
-                    hipLaunchKernelGGL((k_roc_decode_lane<256, false>), dim3(lane_grid((b.nwork + b.lpw - 1u) / b.lpw)), dim3(64), 0, st_, b,
-                                       (const LaneDiv *)ctx->d_ltab);
-                else
-                    hipLaunchKernelGGL((k_roc_decode_lane<256, true>), dim3(lane_grid((b.nwork + b.lpw - 1u) / b.lpw)), dim3(64), 0, st_, b,
-                                       (const LaneDiv *)ctx->d_ltab);
-                break;
-            case DC_LANE128:  // 18.5 KiB of LDS per wavefront
-                b.lpw = lane_lists_per_wave(ctx, b.nwork, 7);
-                hipLaunchKernelGGL((k_roc_decode_lane<128, true>), dim3(lane_grid((b.nwork + b.lpw - 1u) / b.lpw)), dim3(64), 0, st_, b,
-                                   (const LaneDiv *)ctx->d_ltab);
-                break;
-            case DC_B2: {
-                // (round 5 measured and dropped: the next step's candidate rows requested one step ahead -- 45.7 against 47.5 ms with
-                // the class alone, 72.9 against 72.2 ms for the whole S2 decode: HISTORY.md)
-                // VIDC_B2_MASK=1 / 0: the row load under exec = lanes below the bucket's member count (roc_u2.h, U2B_DEC_IDX_MC: a third
-                // of the sectors, a later load) / the whole row at once.  Default: calls of many chains, whose rows come from HBM.
-                const char *mke = std::getenv("VIDC_B2_MASK");
-                const bool mk = mke ? mke[0] == '1' : b.nwork >= B2_MASK_MIN_CHAINS;
-                if (mk) hipLaunchKernelGGL((k_roc_decode_b2<0, 2>), dim3(b.nwork), dim3(64), VIDC_B2_LDS_BYTES, st_, b, (const U2Div *)ctx->d_u2tab);
-                else hipLaunchKernelGGL(k_roc_decode_b2<0>, dim3(b.nwork), dim3(64), VIDC_B2_LDS_BYTES, st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            }
-            case DC_B2T:  // 32 buckets, 8.3 KiB of LDS
-                hipLaunchKernelGGL(k_roc_decode_b2<32>, dim3(b.nwork), dim3(64), VIDC_B2L_LDS_BYTES(32u), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_B2S:  // 64 buckets, 16.5 KiB of LDS
-                hipLaunchKernelGGL(k_roc_decode_b2<64>, dim3(b.nwork), dim3(64), VIDC_B2L_LDS_BYTES(64u), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_B2L:  // 128 buckets, 33 KiB of LDS
-                hipLaunchKernelGGL(k_roc_decode_b2<128>, dim3(b.nwork), dim3(64), VIDC_B2L_LDS_BYTES(128u), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_B2M:  // 256 buckets, 66 KiB
-                VIDC_TRY(set_big_lds((const void *)k_roc_decode_b2<256>, VIDC_B2L_LDS_BYTES(256u)));
-                hipLaunchKernelGGL(k_roc_decode_b2<256>, dim3(b.nwork), dim3(64), VIDC_B2L_LDS_BYTES(256u), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_LANEQ:
-                b.lpw = 16u;
-                hipLaunchKernelGGL((k_roc_decode_lane_reg<VIDC_LANE_REG_EL, 4>), dim3((b.nwork + 15u) / 16u), dim3(64), 0, st_, b,
-                                   (const LaneDiv *)ctx->d_ltab);
-                break;
-            case DC_LANEP:
-                b.lpw = 32u;
-                hipLaunchKernelGGL((k_roc_decode_lane_reg<VIDC_LANE_REG_EL, 2>), dim3((b.nwork + 31u) / 32u), dim3(64), 0, st_, b,
-                                   (const LaneDiv *)ctx->d_ltab);
-                break;
-            case DC_GRP0:
-                hipLaunchKernelGGL(k_roc_decode_grp<0>, dim3((b.nwork + 3u) / 4u), dim3(64), 16u * roc_grp_dec_lds_words(0), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_GRP2:
-                hipLaunchKernelGGL(k_roc_decode_grp<2>, dim3((b.nwork + 3u) / 4u), dim3(64), 16u * roc_grp_dec_lds_words(2), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_GRP3:
-                hipLaunchKernelGGL(k_roc_decode_grp<3>, dim3((b.nwork + 3u) / 4u), dim3(64), 16u * roc_grp_dec_lds_words(3), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_GRP4:
-                hipLaunchKernelGGL(k_roc_decode_grp<4>, dim3((b.nwork + 3u) / 4u), dim3(64), 16u * roc_grp_dec_lds_words(4), st_, b, (const U2Div *)ctx->d_u2tab);
-                break;
-            case DC_G8K:
-                hipLaunchKernelGGL(k_roc_decode_gen<uint16_t>, dim3(b.nwork), dim3(64), 1024 * 2, st_, b, 1024u, VIDC_DEC_CAP);
-                break;
-            case DC_G16K:
-                hipLaunchKernelGGL(k_roc_decode_gen<uint16_t>, dim3(b.nwork), dim3(64), 2048 * 2, st_, b, 2048u, VIDC_DEC_CAP);
-                break;
-            case DC_GMID:
-                hipLaunchKernelGGL(k_roc_decode_gen<uint16_t>, dim3(b.nwork), dim3(64), (1u << VIDC_DEC_MAX_FB) * 2, st_, b,
-                                   1u << VIDC_DEC_MAX_FB, VIDC_DEC_CAP);
-                break;
-            default:  // DC_GHUGE: 16-bit row counters unless the class holds a list beyond 65 536 ids
-                if (p.max_n[DC_GHUGE] <= 65536)
-                    hipLaunchKernelGGL(k_roc_decode_gen<uint16_t>, dim3(b.nwork), dim3(64), (1u << VIDC_DEC_MAX_FB) * 2, st_,
-                                       b, 1u << VIDC_DEC_MAX_FB, VIDC_DEC_CAP_BIG);
-                else
-                    hipLaunchKernelGGL(k_roc_decode_gen<uint32_t>, dim3(b.nwork), dim3(64), (1u << VIDC_DEC_MAX_FB) * 4, st_,
-                                       b, 1u << VIDC_DEC_MAX_FB, VIDC_DEC_CAP_BIG);
-        }
-        VIDC_HIP(hipGetLastError());
-        if (c == chain_class) VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st_));
-        return VIDC_OK;
-    };
+    c.chain_class = p.count[DC_U20] ? DC_U20 : (p.count[DC_U18] ? DC_U18 : -1);
     // VIDC_DEC_SCHED (measurements): explicit schedule (grammar: roc_enc_plan.h), e.g. "B2;GHUGE;LANEP,LANE,LANE64;GMID^LANEP"; "CLS^DEP"
     // waits for class DEP (on another stream) to finish.  Classes of the call the string does not name keep the automatic assignment.
     // This site's rules (the encoder's differ, see enc_run_launches): a class without lists in this call counts as unknown; a name's
     // second entry is kept and skipped by the loop; an event is recorded for every scheduled class; a round without progress (a
     // cycle) ends the loop and the rest is launched in order[].
-    std::vector<SchedEntry> sched;
     if (const char *e = std::getenv("VIDC_DEC_SCHED")) {
-        static const char *names[DC_COUNT] = {"TINY", "U18", "U20", "GSMALL", "G8K", "G16K", "GMID", "GHUGE", "LANE", "LANE64", "LANE128", "B2", "B2T", "B2S",
-                                              "B2L", "B2M", "GRP0", "GRP2", "GRP3", "GRP4", "LANEP", "LANEQ"};
-        auto cls_of = [&](const std::string &t) { for (int c = 0; c < DC_COUNT; c++) if (t == names[c]) return p.count[c] ? c : -1; return -1; };
-        sched = parse_schedule(e, cls_of, ctx->naux(), false);
-        for (const SchedEntry &it : sched) stream_of[it.item] = it.group == 0 ? ctx->stream : ctx->aux[it.group - 1];
+        auto cls_of = [&](const std::string &t) { const int k = dec_class_by_name(t); return k >= 0 && p.count[k] ? k : -1; };
+        c.sched = parse_schedule(e, cls_of, ctx->naux(), false);
+        for (const SchedEntry &it : c.sched) c.stream_of[it.item] = it.group == 0 ? ctx->stream : ctx->aux[it.group - 1];
     }
-    if (pair_first) VIDC_TRY(launch(DC_LANEP));
+    return VIDC_OK;
+}
+int dec_fork(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
     VIDC_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-    uint32_t aux_used = 0;  // only the auxiliary streams that carry a class of this call are forked and joined
-    for (int c = 0; c < DC_COUNT; c++)
+    for (int k = 0; k < DC_COUNT; k++)
         for (int i = 0; i < ctx->naux(); i++)
-            if (p.count[c] && stream_of[c] == ctx->aux[i] && !(aux_used >> i & 1u)) {
+            if (c.p.count[k] && c.stream_of[k] == ctx->aux[i] && !(c.aux_used >> i & 1u)) {
                 VIDC_HIP(hipStreamWaitEvent(ctx->aux[i], ctx->ev_fork, 0));
-                aux_used |= 1u << i;
+                c.aux_used |= 1u << i;
             }
-    if (!sched.empty()) {
-        std::vector<char> done(DC_COUNT, 0);
-        std::stable_sort(sched.begin(), sched.end(), [](const SchedEntry &x, const SchedEntry &y) { return x.pos < y.pos; });
-        VIDC_TRY(run_schedule(sched, done, false, [&](const SchedEntry &it) -> int {
-            for (int d : it.deps) VIDC_HIP(hipStreamWaitEvent(stream_of[it.item], ctx->tev[d], 0));
-            VIDC_TRY(launch(it.item));
-            VIDC_HIP(hipEventRecord(ctx->tev[it.item], stream_of[it.item]));
-            return VIDC_OK;
-        }));
-        for (int k = 0; k < DC_COUNT; k++)
-            if (!done[order[k]] && !(pair_first && order[k] == DC_LANEP)) VIDC_TRY(launch(order[k]));
-    } else
-    for (int k = 0; k < DC_COUNT; k++)  // longest first
-        if (!(pair_first && order[k] == DC_LANEP)) VIDC_TRY(launch(order[k]));
+    return VIDC_OK;
+}
+
+// ---- one launch function per kernel family: b = the class's arguments (its part of the work list and of the offset arrays)
+using DecLaunchFn = int (*)(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st);
+int dec_launch_tiny(DecodeCall &c, int, RocDecArgs &b, hipStream_t st) {
+    if (c.p.tiny_lane) {  // one list per lane (roc_lane.h)
+        const dim3 grid((b.nwork + 63u) / 64u);
+        const LaneDiv *dt = (const LaneDiv *)c.ctx->d_ltab;
+        if (c.d_out_rows) hipLaunchKernelGGL(k_roc_decode_tiny_lane<true>, grid, dim3(64), 0, st, b, dt);
+        else hipLaunchKernelGGL(k_roc_decode_tiny_lane<false>, grid, dim3(64), 0, st, b, dt);
+    } else if (c.d_out_rows) hipLaunchKernelGGL(k_roc_decode_tiny<true>, dim3(b.nwork), dim3(64), 0, st, b);
+    else hipLaunchKernelGGL(k_roc_decode_tiny<false>, dim3(b.nwork), dim3(64), 0, st, b);
+    return VIDC_OK;
+}
+int dec_launch_u(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // universe-bitmap kernels: ids < 2^18 / 2^20
+    const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
+    if (cls == DC_U18) {
+        if (old_u_kernels()) hipLaunchKernelGGL(k_roc_decode_u<18>, dim3(b.nwork), dim3(64), UGeom<18>::LDS_BYTES, st, b);
+        else hipLaunchKernelGGL(k_roc_decode_u2<18>, dim3(b.nwork), dim3(64), U2Geom<18>::LDS_BYTES, st, b, dt);
+    } else if (old_u_kernels()) {
+        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u<20>, UGeom<20>::LDS_BYTES));
+        hipLaunchKernelGGL(k_roc_decode_u<20>, dim3(b.nwork), dim3(64), UGeom<20>::LDS_BYTES, st, b);
+    } else {
+        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20>, U2Geom<20>::LDS_BYTES));
+        hipLaunchKernelGGL(k_roc_decode_u2<20>, dim3(b.nwork), dim3(64), U2Geom<20>::LDS_BYTES, st, b, dt);
+    }
+    return VIDC_OK;
+}
+// general wave-per-list decoder: nf fine prefix counters of 16 bits in LDS
+int dec_launch_gen(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {
+    const uint32_t nf = cls == DC_GSMALL ? 512u : (cls == DC_G8K ? 1024u : (cls == DC_G16K ? 2048u : 1u << VIDC_DEC_MAX_FB));
+    const uint32_t cap = cls == DC_GHUGE ? VIDC_DEC_CAP_BIG : VIDC_DEC_CAP;
+    if (cls == DC_GSMALL && c.p.gsmall_lrows)  // member rows in LDS: 1 + 32 KiB
+        hipLaunchKernelGGL((k_roc_decode_gen<uint16_t, true>), dim3(b.nwork), dim3(64), nf * 2 + nf * cap * 4, st, b, nf, cap);
+    else
+        hipLaunchKernelGGL(k_roc_decode_gen<uint16_t>, dim3(b.nwork), dim3(64), nf * 2, st, b, nf, cap);
+    return VIDC_OK;
+}
+int dec_launch_lane(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // 12.5 KiB of LDS per wavefront
+    vidc_ctx *ctx = c.ctx; const DecPlan &p = c.p;
+    b.lpw = lane_lists_per_wave(ctx, b.nwork, 24);
+    // lists are sorted longest first: those of <= 256 ids (the tail of the work list, from a wavefront
+    // boundary on) take the decoder that keeps the decoded ids in registers
+    uint32_t n_big = b.nwork;
+    if (!std::getenv("VIDC_NO_LANE_REG") && !p.wl.empty()) {
+        const uint32_t *wl0 = p.wl.data() + c.base[cls];
+        n_big = (uint32_t)(std::partition_point(wl0, wl0 + b.nwork, [&](uint32_t l) {
+                               return c.r->offsets[l + 1] - c.r->offsets[l] > VIDC_LANE_REG_MAX;
+                           }) - wl0);
+        n_big = std::min<uint32_t>(b.nwork, (n_big + b.lpw - 1u) / b.lpw * b.lpw);
+    }
+    RocDecArgs b2 = b;
+    b2.worklist = b.worklist + n_big; b2.nwork = b.nwork - n_big;
+    if (b2.out_off) b2.out_off += n_big;
+    b.nwork = n_big;
+    if (b.nwork && env_on("VIDC_LANE_LOOP"))
+        hipLaunchKernelGGL((k_roc_decode_lane<64, false>), dim3((b.nwork + b.lpw - 1u) / b.lpw), dim3(64), 0, st, b,
+                           (const LaneDiv *)ctx->d_ltab);
+    else if (b.nwork)
+        hipLaunchKernelGGL((k_roc_decode_lane<64, true>), dim3((b.nwork + b.lpw - 1u) / b.lpw), dim3(64), 0, st, b,
+                           (const LaneDiv *)ctx->d_ltab);
+    if (b2.nwork)
+        hipLaunchKernelGGL(k_roc_decode_lane_reg<VIDC_LANE_REG_EL>, dim3((b2.nwork + b2.lpw - 1u) / b2.lpw), dim3(64), 0, st,
+                           b2, (const LaneDiv *)ctx->d_ltab);
+    return VIDC_OK;
+}
+int dec_launch_lane_nb(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // 256 buckets: 26.5 KiB of LDS per wavefront, 128: 18.5
+    b.lpw = lane_lists_per_wave(c.ctx, b.nwork, 7);
+    const dim3 grid((b.nwork + b.lpw - 1u) / b.lpw);
+    const LaneDiv *dt = (const LaneDiv *)c.ctx->d_ltab;
+    if (cls == DC_LANE64 && env_on("VIDC_LANE_LOOP")) hipLaunchKernelGGL((k_roc_decode_lane<256, false>), grid, dim3(64), 0, st, b, dt);
+    else if (cls == DC_LANE64) hipLaunchKernelGGL((k_roc_decode_lane<256, true>), grid, dim3(64), 0, st, b, dt);
+    else hipLaunchKernelGGL((k_roc_decode_lane<128, true>), grid, dim3(64), 0, st, b, dt);
+    return VIDC_OK;
+}
+int dec_launch_b2(DecodeCall &c, int, RocDecArgs &b, hipStream_t st) {
+    // (round 5 measured and dropped: the next step's candidate rows requested one step ahead -- 45.7 against 47.5 ms with
+    // the class alone, 72.9 against 72.2 ms for the whole S2 decode: HISTORY.md)
+    // VIDC_B2_MASK=1 / 0: the row load under exec = lanes below the bucket's member count (roc_u2.h, U2B_DEC_IDX_MC: a third
+    // of the sectors, a later load) / the whole row at once.  Default: calls of many chains, whose rows come from HBM.
+    const char *mke = std::getenv("VIDC_B2_MASK");
+    const bool mk = mke ? mke[0] == '1' : b.nwork >= B2_MASK_MIN_CHAINS;
+    if (mk) hipLaunchKernelGGL((k_roc_decode_b2<0, 2>), dim3(b.nwork), dim3(64), VIDC_B2_LDS_BYTES, st, b, (const U2Div *)c.ctx->d_u2tab);
+    else hipLaunchKernelGGL(k_roc_decode_b2<0>, dim3(b.nwork), dim3(64), VIDC_B2_LDS_BYTES, st, b, (const U2Div *)c.ctx->d_u2tab);
+    return VIDC_OK;
+}
+int dec_launch_b2l(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // 32 / 64 / 128 / 256 buckets, member rows in LDS: 8.3 / 16.5 / 33 / 66 KiB
+    const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
+    const dim3 grid(b.nwork);
+    if (cls == DC_B2T) hipLaunchKernelGGL(k_roc_decode_b2<32>, grid, dim3(64), VIDC_B2L_LDS_BYTES(32u), st, b, dt);
+    else if (cls == DC_B2S) hipLaunchKernelGGL(k_roc_decode_b2<64>, grid, dim3(64), VIDC_B2L_LDS_BYTES(64u), st, b, dt);
+    else if (cls == DC_B2L) hipLaunchKernelGGL(k_roc_decode_b2<128>, grid, dim3(64), VIDC_B2L_LDS_BYTES(128u), st, b, dt);
+    else {
+        VIDC_TRY(set_big_lds((const void *)k_roc_decode_b2<256>, VIDC_B2L_LDS_BYTES(256u)));
+        hipLaunchKernelGGL(k_roc_decode_b2<256>, grid, dim3(64), VIDC_B2L_LDS_BYTES(256u), st, b, dt);
+    }
+    return VIDC_OK;
+}
+int dec_launch_lane_reg(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // the register decoder on quads / pairs of lanes
+    const LaneDiv *dt = (const LaneDiv *)c.ctx->d_ltab;
+    b.lpw = cls == DC_LANEQ ? 16u : 32u;
+    const dim3 grid((b.nwork + b.lpw - 1u) / b.lpw);
+    if (cls == DC_LANEQ) hipLaunchKernelGGL((k_roc_decode_lane_reg<VIDC_LANE_REG_EL, 4>), grid, dim3(64), 0, st, b, dt);
+    else hipLaunchKernelGGL((k_roc_decode_lane_reg<VIDC_LANE_REG_EL, 2>), grid, dim3(64), 0, st, b, dt);
+    return VIDC_OK;
+}
+int dec_launch_grp(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // row-per-list decoder, four lists per wavefront
+    const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
+    const dim3 grid((b.nwork + 3u) / 4u);
+    if (cls == DC_GRP0) hipLaunchKernelGGL(k_roc_decode_grp<0>, grid, dim3(64), 16u * roc_grp_dec_lds_words(0), st, b, dt);
+    else if (cls == DC_GRP2) hipLaunchKernelGGL(k_roc_decode_grp<2>, grid, dim3(64), 16u * roc_grp_dec_lds_words(2), st, b, dt);
+    else if (cls == DC_GRP3) hipLaunchKernelGGL(k_roc_decode_grp<3>, grid, dim3(64), 16u * roc_grp_dec_lds_words(3), st, b, dt);
+    else hipLaunchKernelGGL(k_roc_decode_grp<4>, grid, dim3(64), 16u * roc_grp_dec_lds_words(4), st, b, dt);
+    return VIDC_OK;
+}
+int dec_launch_ghuge(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // 16-bit row counters unless the class holds a list beyond 65 536 ids
+    if (c.p.max_n[DC_GHUGE] <= 65536) return dec_launch_gen(c, cls, b, st);
+    hipLaunchKernelGGL(k_roc_decode_gen<uint32_t>, dim3(b.nwork), dim3(64), (1u << VIDC_DEC_MAX_FB) * 4, st, b, 1u << VIDC_DEC_MAX_FB, VIDC_DEC_CAP_BIG);
+    return VIDC_OK;
+}
+// (in the order of DecClass)
+const DecLaunchFn DEC_LAUNCH[DC_COUNT] = {
+    dec_launch_tiny, dec_launch_u, dec_launch_u, dec_launch_gen, dec_launch_gen, dec_launch_gen, dec_launch_gen, dec_launch_ghuge,
+    dec_launch_lane, dec_launch_lane_nb, dec_launch_lane_nb, dec_launch_b2, dec_launch_b2l, dec_launch_b2l, dec_launch_b2l, dec_launch_b2l,
+    dec_launch_grp, dec_launch_grp, dec_launch_grp, dec_launch_grp, dec_launch_lane_reg, dec_launch_lane_reg};
+
+// the launch of one class on its stream, between the chain events where it is the call's chain class
+int dec_launch_class(DecodeCall &c, int cls) {
+    vidc_ctx *ctx = c.ctx; const DecPlan &p = c.p;
+    if (!p.count[cls]) return VIDC_OK;
+    hipStream_t st = c.stream_of[cls];
+    if (cls == c.chain_class) {
+        ctx->chain_info[1][0] = p.sum_n[cls]; ctx->chain_info[1][1] = p.count[cls]; ctx->chain_info[1][2] = p.max_n[cls];
+        ctx->chain_info[1][3] = cls == DC_U20 ? 20 : 18;
+        VIDC_HIP(hipEventRecord(ctx->ev_chain[0], st));
+    }
+    RocDecArgs b = c.a;
+    b.worklist = c.d_wl ? c.d_wl + c.base[cls] : nullptr;
+    b.nwork = (uint32_t)p.count[cls];
+    b.out_off = (c.out_off_host && !p.lean) ? c.s_out_off.as<uint64_t>() + c.base[cls] : nullptr;
+    b.scratch_off = c.d_scr_off ? c.d_scr_off + c.base[cls] : nullptr;
+    b.slots_off = c.d_slots_off ? c.d_slots_off + c.base[cls] : nullptr;
+    b.row_align = p.lane_align;
+    VIDC_TRY(DEC_LAUNCH[cls](c, cls, b, st));
+    VIDC_HIP(hipGetLastError());
+    if (cls == c.chain_class) VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st));
+    return VIDC_OK;
+}
+// every class of the call: longest first, or as VIDC_DEC_SCHED says (its rules: dec_assign_streams)
+int dec_run_launches(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    if (c.sched.empty()) {
+        for (int k = 0; k < DC_COUNT; k++) VIDC_TRY(dec_launch_class(c, c.order[k]));
+        return VIDC_OK;
+    }
+    std::vector<char> done(DC_COUNT, 0);
+    std::stable_sort(c.sched.begin(), c.sched.end(), [](const SchedEntry &x, const SchedEntry &y) { return x.pos < y.pos; });
+    VIDC_TRY(run_schedule(c.sched, done, false, [&](const SchedEntry &it) -> int {
+        for (int d : it.deps) VIDC_HIP(hipStreamWaitEvent(c.stream_of[it.item], ctx->tev[d], 0));
+        VIDC_TRY(dec_launch_class(c, it.item));
+        VIDC_HIP(hipEventRecord(ctx->tev[it.item], c.stream_of[it.item]));
+        return VIDC_OK;
+    }));
+    for (int k = 0; k < DC_COUNT; k++)
+        if (!done[c.order[k]]) VIDC_TRY(dec_launch_class(c, c.order[k]));
+    return VIDC_OK;
+}
+int dec_join(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
     for (int i = 0; i < ctx->naux(); i++) {
-        if (!(aux_used >> i & 1u)) continue;
+        if (!(c.aux_used >> i & 1u)) continue;
         VIDC_HIP(hipEventRecord(ctx->ev_join[i], ctx->aux[i]));
         VIDC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
     }
-    // the end event of the kernels, then the 32-byte status summary (instead of copying two nlist-sized arrays back) behind them:
-    // ONE wait for both
-    (void)t.mark();
-    Pinned h_sum;
-    constexpr uint32_t RETRY_SLOTS = 504;  // list numbers of handed-back lists behind the eight summary words
-    VIDC_TRY(h_sum.get(ctx, (8 + RETRY_SLOTS) * 8));
-    unsigned long long *sum = h_sum.as<unsigned long long>();
+    return VIDC_OK;
+}
+// the end event of the kernels, then the 32-byte status summary (instead of copying two nlist-sized arrays back) behind them:
+// ONE wait for both
+int dec_summary_wait(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx; const vidc_roc *r = c.r;
+    (void)c.t.mark();
+    VIDC_TRY(c.h_sum.get(ctx, (8 + DEC_RETRY_SLOTS) * 8));
+    unsigned long long *sum = c.sum = c.h_sum.as<unsigned long long>();
     sum[0] = ~0ull; sum[1] = 0; sum[2] = 0; sum[3] = 0;
     // (the kernel's last workgroup stores the summary into the pinned block itself: no copy up, no copy down)
     hipLaunchKernelGGL(k_roc_status_summary_host, dim3((uint32_t)std::min<uint64_t>((r->nlist + 1023) / 1024, 256)), dim3(256),
-                       0, ctx->stream, d_status, s_end.as<uint32_t>(), (uint32_t)r->nlist,
-                       (unsigned long long *)(s_end.as<uint32_t>() + 2 * r->nlist), sum, (out_off_host || r->rows) ? 0u : RETRY_SLOTS);
+                       0, ctx->stream, c.d_status, c.s_end.as<uint32_t>(), (uint32_t)r->nlist,
+                       (unsigned long long *)(c.s_end.as<uint32_t>() + 2 * r->nlist), sum, (c.out_off_host || r->rows) ? 0u : DEC_RETRY_SLOTS);
     VIDC_HIP(hipGetLastError());
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    ctx->last_kernel_ms = t.elapsed();
+    ctx->last_kernel_ms = c.t.elapsed();
     ctx->phase_ms[VIDC_PHASE_ROC_DECODE] = ctx->last_kernel_ms;
-    if (chain_class >= 0) {
+    if (c.chain_class >= 0) {
         float cms = 0;
         if (hipEventElapsedTime(&cms, ctx->ev_chain[0], ctx->ev_chain[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_ROC_DECODE_CHAIN] = cms;
     }
-    tr.mark("decode kernels + status summary (sync)");
+    c.tr.mark("decode kernels + status summary (sync)");
+    return VIDC_OK;
+}
+int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64_t *out_off_host, uint64_t *d_out,
+                int32_t *d_out_rows, uint32_t K, const struct DecPlanCache *cache = nullptr);
+// errors, and the lists the lane-per-list decoders handed back (a full bucket row on skewed ids): these are redone with the
+// wave-per-list kernels, into the same output slots
+int dec_check_and_retry(DecodeCall &c) {
+    vidc_ctx *ctx = c.ctx; const vidc_roc *r = c.r; const DecPlan &p = c.p;
+    const unsigned long long *sum = c.sum;
+    const uint64_t *out_off_host = c.out_off_host;
     const double first_ms = ctx->last_kernel_ms;
     uint64_t nonclean = sum[1];
     if (sum[0] != ~0ull || sum[2]) {
         // (a few handed-back lists and nothing else to report: their numbers came with the summary; otherwise the statuses are fetched)
-        const bool listed = sum[0] == ~0ull && !out_off_host && !r->rows && sum[2] <= RETRY_SLOTS;
+        const bool listed = sum[0] == ~0ull && !out_off_host && !r->rows && sum[2] <= DEC_RETRY_SLOTS;
         std::vector<uint32_t> status(listed ? 0 : r->nlist);
-        if (!listed) VIDC_HIP(hipMemcpy(status.data(), d_status, r->nlist * 4, hipMemcpyDeviceToHost));
+        if (!listed) VIDC_HIP(hipMemcpy(status.data(), c.d_status, r->nlist * 4, hipMemcpyDeviceToHost));
         if (sum[2]) {
-            // lists the lane-per-list decoder handed back (a full bucket row on skewed ids): redo them with the
-            // wave-per-list kernels, into the same output slots
             std::vector<uint32_t> lists2;
             std::vector<uint64_t> off2;
             if (listed) {
@@ -1801,24 +1489,24 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
                 std::sort(lists2.begin(), lists2.end());
                 for (uint32_t l : lists2) off2.push_back(r->offsets[l]);
             } else
-            for (size_t k = base[DC_LANE]; k < p.wl.size(); k++) {  // lane classes, B2, row-per-list classes
+            for (size_t k = c.base[DC_LANE]; k < p.wl.size(); k++) {  // lane classes, B2, row-per-list classes
                 if (status[p.wl[k]] != VIDC_ST_RETRY) continue;
                 lists2.push_back(p.wl[k]);
                 off2.push_back(out_off_host ? out_off_host[k] : r->offsets[p.wl[k]]);
             }
             if (!listed) for (uint32_t l : lists2) status[l] = VIDC_ST_OK;
-            if (tr.on) {
+            if (c.tr.on) {
                 uint64_t mx = 0, mn = ~0ull;
                 for (uint32_t l : lists2) { const uint64_t n = r->offsets[l + 1] - r->offsets[l]; mx = std::max(mx, n); mn = std::min(mn, n); }
                 fprintf(stderr, "[vidc] roc decode: %zu lists handed back by the lane decoders (%llu .. %llu ids)\n", lists2.size(),
                         (unsigned long long)mn, (unsigned long long)mx);
             }
             if (!listed) VIDC_TRY(check_status(status, "roc decode"));
-            DecPlan p2;
+            PooledDecPlan p2;
             plan_decode(r, lists2, false, p2, ctx->wide, false, false);
             std::vector<uint64_t> out_off2(lists2.size());
             for (size_t k = 0; k < lists2.size(); k++) out_off2[k] = off2[p2.item[k]];
-            VIDC_TRY(decode_impl(ctx, r, p2, out_off2.data(), d_out, nullptr, 0));
+            VIDC_TRY(decode_impl(ctx, r, p2, out_off2.data(), c.d_out, nullptr, 0));
             nonclean += r->last_nonclean;
             ctx->last_kernel_ms += first_ms;
             ctx->phase_ms[VIDC_PHASE_ROC_DECODE] = ctx->last_kernel_ms;
@@ -1828,6 +1516,25 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
     }
     r->last_nonclean = nonclean;
     return VIDC_OK;
+}
+
+// The host call of every ROC decode: a plan (plan_decode, a cached one with its device arrays, or a lean / implicit one of graph
+// rows) and where the ids go (out_off_host: an output offset per work item; d_out_rows / K: int32 rows instead of u64 ids).
+int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64_t *out_off_host, uint64_t *d_out,
+                int32_t *d_out_rows, uint32_t K, const struct DecPlanCache *cache) {
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const size_t nwork = p.implicit ? (size_t)p.implicit : p.wl.size();
+    if (nwork == 0) { ctx->last_kernel_ms = 0; return VIDC_OK; }
+    DecodeCall c(ctx, r, p, out_off_host, d_out, d_out_rows, K, cache, nwork);
+    VIDC_TRY(dec_upload(c));
+    (void)c.t.start();
+    VIDC_TRY(dec_build_row_order(c));
+    VIDC_TRY(dec_assign_streams(c));
+    VIDC_TRY(dec_fork(c));
+    VIDC_TRY(dec_run_launches(c));
+    VIDC_TRY(dec_join(c));
+    VIDC_TRY(dec_summary_wait(c));
+    return dec_check_and_retry(c);
 }
 
 // ---- device-resident label requests (vidc_roc_translate_labels_dev): ROC has no random access, so the touched lists are decoded.
@@ -2086,6 +1793,13 @@ std::shared_ptr<DecPlanCache> plan_ahead_build(const vidc_roc *r, bool wide) {
     plan_decode(r, all, false, c->plan, wide, true, true, false, /*whole_sorted=*/true);
     return c;
 }
+// the arrays of a plan that the kernels read, to the device, on the context's stream
+int upload_plan(vidc_ctx *ctx, DecPlanCache &c) {
+    VIDC_TRY(upload(ctx, c.d_wl, c.plan.wl));
+    VIDC_TRY(upload(ctx, c.d_scratch_off, c.plan.scratch_off));
+    VIDC_TRY(upload(ctx, c.d_slots_off, c.plan.slots_off));
+    return VIDC_OK;
+}
 }  // namespace
 
 int vidc_roc_decode_all(vidc_ctx *ctx, const vidc_roc *r, uint64_t *d_out) {
@@ -2102,9 +1816,7 @@ int vidc_roc_decode_all(vidc_ctx *ctx, const vidc_roc *r, uint64_t *d_out) {
         HostTrace tr("roc decode_all (plan of the other stream mode)");
         auto c = plan_ahead_build(r, ctx->wide);
         VIDC_HIP(hipSetDevice(ctx->device));
-        VIDC_TRY(upload(ctx, c->d_wl, c->plan.wl));
-        VIDC_TRY(upload(ctx, c->d_scratch_off, c->plan.scratch_off));
-        VIDC_TRY(upload(ctx, c->d_slots_off, c->plan.slots_off));
+        VIDC_TRY(upload_plan(ctx, *c));
         const int st = decode_impl(ctx, r, c->plan, nullptr, d_out, nullptr, 0, c.get());
         if (st == VIDC_OK) {
             std::lock_guard<std::mutex> g(r->mu);
@@ -2123,9 +1835,7 @@ int vidc_roc_decode_all(vidc_ctx *ctx, const vidc_roc *r, uint64_t *d_out) {
         if (!c) c = plan_ahead_build(r, ctx->wide);
         tr.mark("plan");
         VIDC_HIP(hipSetDevice(ctx->device));
-        VIDC_TRY(upload(ctx, c->d_wl, c->plan.wl));
-        VIDC_TRY(upload(ctx, c->d_scratch_off, c->plan.scratch_off));
-        VIDC_TRY(upload(ctx, c->d_slots_off, c->plan.slots_off));
+        VIDC_TRY(upload_plan(ctx, *c));
         tr.mark("plan upload");
         VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // another context may use the cached plan next
         std::lock_guard<std::mutex> g(r->mu);
@@ -2147,7 +1857,7 @@ int vidc_roc_decode_lists(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const ui
         req_off[i + 1] = req_off[i] + (r->offsets[lists[i] + 1] - r->offsets[lists[i]]);
     }
     std::memcpy(out_offsets, req_off.data(), (m + 1) * 8);
-    DecPlan p;
+    PooledDecPlan p;
     plan_decode(r, lists, false, p, ctx->wide);
     std::vector<uint64_t> out_off(m);
     for (size_t k = 0; k < m; k++) out_off[k] = req_off[p.item[k]];  // work item k -> its slot in the request
@@ -2182,7 +1892,7 @@ int vidc_roc_decode_rows(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const uin
         if (!m) return VIDC_OK;
         VIDC_HIP(hipSetDevice(ctx->device));
         VIDC_HIP(hipMemsetAsync(d_out, 0xff, m * (uint64_t)K * 4, ctx->stream));
-        DecPlan p;
+        PooledDecPlan p;
         plan_decode(r, lists, false, p, ctx->wide, false, false, true);  // only the kernels that write int32 rows
         std::vector<uint64_t> out_off(m);
         for (size_t k = 0; k < m; k++) out_off[k] = (uint64_t)p.item[k] * K;
@@ -2190,7 +1900,7 @@ int vidc_roc_decode_rows(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const uin
     }
     const bool lean = r->rows && K >= r->K && !force_general() && lane_wanted(lane_policy(), m, LANE_MIN_TINY);
     if (lean && !nodes) {  // rows 0..m-1 of a graph object: nothing proportional to m is built on or leaves the host
-        DecPlan p;
+        PooledDecPlan p;
         p.lean = true; p.tiny_lane = true; p.implicit = m;
         p.count[DC_TINY] = m;
         std::unique_lock<std::mutex> g(r->mu, std::defer_lock);
@@ -2224,7 +1934,7 @@ int vidc_roc_decode_rows(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const uin
             if (counts) counts[i] = (uint32_t)n;
         }
     }
-    DecPlan p;
+    PooledDecPlan p;
     plan_decode(r, lists, true, p, ctx->wide, lean);
     if (p.lean) {
         VIDC_TRY(decode_impl(ctx, r, p, nullptr, nullptr, d_out, K));
@@ -2291,7 +2001,7 @@ int vidc_roc_translate_labels_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, 
     }
     VIDC_TRY(s_stage.get(ctx, (total ? total : 1) * 8));
     if (cnt) {
-        DecPlan p;
+        PooledDecPlan p;
         plan_decode(r, lists, false, p, ctx->wide);
         std::vector<uint64_t> out_off(cnt);
         for (size_t k = 0; k < cnt; k++) out_off[k] = req_off[p.item[k]];  // work item k -> its place in the staging
@@ -2393,7 +2103,7 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
     tr.mark("touched lists read back, staging sized");
     VIDC_TRY(s_stage.get(ctx, (total ? total : 1) * 8));
     if (!dec_lists.empty()) {
-        DecPlan p;
+        PooledDecPlan p;
         plan_decode(r, dec_lists, false, p, ctx->wide);
         std::vector<uint64_t> out_off(dec_lists.size());
         for (size_t k = 0; k < dec_lists.size(); k++) out_off[k] = st_off[dec_slot[p.item[k]]];  // work item k -> its place in the staging
@@ -2490,7 +2200,7 @@ int vidc_roc_decode_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const
         hipLaunchKernelGGL(k_gather_sizes<uint32_t>, dim3((uint32_t)std::min<uint64_t>((m + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
                            r->d_offsets.p, s_wl.as<uint32_t>(), m, d_counts);
     VIDC_HIP(hipGetLastError());
-    DecPlan p;
+    PooledDecPlan p;
     p.lean = true; p.tiny_lane = true; p.implicit = m;
     p.count[DC_TINY] = m;
     p.order_dev = s_wl.as<uint32_t>();

@@ -317,17 +317,9 @@ __device__ __forceinline__ void gw_land(GWStack &s, bool go, uint32_t sub, uint3
     }
 }
 
-// bucket geometry of the decoder: 2^B value buckets, B = 8 + F (top 4 bits: registers, next 4: `mid`, last F: `leaf`)
-__host__ __device__ inline uint32_t roc_grp_dec_fbits(uint32_t n) {  // <= 8 members per bucket on average up to 32 768 ids
-    return n <= 2048u ? 0u : (n <= 8192u ? 2u : (n <= 16384u ? 3u : 4u));
-}
-__host__ __device__ inline uint32_t roc_grp_dec_cap(uint32_t n) { return n <= 32768u ? 32u : (n <= 65536u ? 64u : 96u); }
+// (bucket geometry of the decoder -- roc_grp_dec_fbits, roc_grp_dec_cap, roc_grp_dec_slots: roc_sizing.h)
 __host__ __device__ inline uint32_t roc_grp_dec_lds_words(uint32_t F) {
     return 128u + (F ? (128u << F) : 0u) + VIDC_GRP_DWIN + VIDC_GRP_DPST;  // mid 256 u16 | leaf 256 << F u16 | window | pst
-}
-// member rows of one list: 2^(8 + F) rows of `cap` u32
-__host__ __device__ inline uint64_t roc_grp_dec_slots(uint32_t n) {
-    return ((uint64_t)256u << roc_grp_dec_fbits(n)) * roc_grp_dec_cap(n);
 }
 
 template <int F>

@@ -18,6 +18,7 @@
 // The order-statistic structures replace the reference's pointer BST (fenwick_tree.h:20-167);
 // the bitstream only depends on rank/select over the set.
 #pragma once
+#include "roc_sizing.h"
 #include "wave.h"
 
 namespace vidc {
@@ -62,13 +63,7 @@ struct RocEncArgs {
 __host__ __device__ inline uint64_t roc_arena_at(const uint64_t *offsets, uint32_t stride, uint64_t l) {
     return offsets ? ((offsets[l] * 37ull) >> 5) + 9ull * l : l * (uint64_t)stride;
 }
-// capacity of a decoder's private stack scratch (plan_decode allots exactly this): the decoder pushes at most
-// ~log2(n) bits per step, so streams of the encoder never outgrow the encoder's own arena bound; a stream whose
-// precision is far below log2(n) (reference quirk domain) GROWS while it is decoded and needs that room
-__host__ __device__ inline uint32_t roc_dec_stack_cap(uint32_t n, uint32_t W) {
-    const uint32_t a = (uint32_t)(((uint64_t)n * 37ull) >> 5) + 8u;
-    return (a > W ? a : W) + 64u;
-}
+// (roc_dec_stack_cap, the capacity of a decoder's private stack scratch: roc_sizing.h)
 __device__ __forceinline__ uint64_t arena_at(const RocEncArgs &a, uint64_t l) {
     return roc_arena_at(a.rows ? nullptr : a.offsets, a.arena_stride, l);
 }
@@ -99,20 +94,7 @@ struct RocDecArgs {
     uint32_t out_by_list;       // graph flavour: the work list is an ORDER of the rows (k_rows_order_*): row l goes to output row l, not to its item number
 };
 
-#define VIDC_DEC_CAP 16u       // members per fine bucket before spilling to the overflow list (lists <= 32768)
-#define VIDC_DEC_CAP_BIG 64u   // same for longer lists (average bucket load up to 64)
-__host__ __device__ inline uint32_t roc_dec_cap(uint32_t n) { return n > 32768u ? VIDC_DEC_CAP_BIG : VIDC_DEC_CAP; }
-#define VIDC_DEC_MAX_FB 12u    // <= 64 coarse x 64 fine buckets
-
-// fine-bucket bits used by the decoder for a list of n elements with precision P (host + device)
-__host__ __device__ inline uint32_t roc_dec_fine_bits(uint32_t n, uint32_t P) {
-    uint32_t lg = 0;
-    while ((1u << lg) < n) lg++;
-    uint32_t fb = lg > 3u ? lg - 3u : 0u;
-    if (fb > VIDC_DEC_MAX_FB) fb = VIDC_DEC_MAX_FB;
-    if (fb > P) fb = P;
-    return fb;
-}
+// (VIDC_DEC_CAP, VIDC_DEC_CAP_BIG, VIDC_DEC_MAX_FB, roc_dec_cap, roc_dec_fine_bits: roc_sizing.h)
 
 // ---------------------------------------------------------------------------------------------
 // Per-64-step reciprocals: lane t prepares the divisor d = dmax - t.

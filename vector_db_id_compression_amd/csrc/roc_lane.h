@@ -418,19 +418,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_lane(RocEncArgs a, const Lane
 // the top 6 / 8 bits of the P-bit universe; LDS per lane: NB byte counters (groups of 16) + u16 group counters (4 per
 // u64) + for NB = 256 4 u16 super-group counters; bucket members (u32, unsorted) in a row of `cap` slots in global
 // memory, written in chunks of 4 so that every chunk below ceil(count/4) is fully defined.
-template <int NB>
-__host__ __device__ inline uint32_t roc_lane_cap_nb(uint32_t n) {
-    // twice the mean + 16 (round 4; + 12 before: four of S2's 900 000 bucket-row lists -- 1089 .. 3291 ids -- overflowed a bucket,
-    // and the pass that redoes them on the wave-per-list kernels waited for the whole decode first: 2.5 ms behind a 71 ms call)
-    return (((n / (uint32_t)NB) * 2u + 16u) + 3u) & ~3u;
-}
-// align = 16 (round 5, RocDecArgs::row_align): rows start on 64-byte boundaries and are a multiple of 64 bytes long, so the four
-// 16-byte chunks a step requests together lie in ONE 64-byte sector -- at align = 4 a row starts anywhere and they straddle two
-// sectors three times out of four (S2: 1.45 sectors fetched per decoded id of the lane classes)
-template <int NB>
-__host__ __device__ inline uint32_t roc_lane_cap_nb(uint32_t n, uint32_t align) {
-    return align > 4u ? (roc_lane_cap_nb<NB>(n) + align - 1u) & ~(align - 1u) : roc_lane_cap_nb<NB>(n);
-}
+// (the row length `cap`, roc_lane_cap_nb<NB>(n [, align]): roc_sizing.h)
 __host__ __device__ inline uint32_t roc_lane_cap(uint32_t n) { return roc_lane_cap_nb<64>(n); }
 
 // sum of the bytes j < t (t <= 8) of the 8-byte value v
