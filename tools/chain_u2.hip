@@ -1,5 +1,6 @@
-// chain_u2.hip -- dev tool: one long list through k_roc_encode_u (round 1) and k_roc_encode_u2 (round 2): identical
-// head / words / order, ns per step of each (hipEvents).   usage: chain_u2 [n] [seed] [ub]
+// chain_u2.hip -- dev tool: one long list through k_roc_encode_u (round 1), k_roc_encode_u2 (round 2, bitmap body) and, for ub 20,
+// k_roc_encode_u2 with dense 16-id blocks: identical head / words / order, ns per step of each (hipEvents, five repeats: min and
+// max).   usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: the section table is that of the LAST arm run)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I vector_db_id_compression_amd/csrc tools/chain_u2.hip -o /tmp/chain_u2
 #include <cstdio>
 #include <cstdlib>
@@ -44,18 +45,22 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
     uint32_t *d_prof; CK(hipMalloc(&d_prof, 256)); CK(hipMemset(d_prof, 0, 256));
     a.draws = d_dr; a.status = d_st; a.arena = d_arena; a.arena_stride = 0; a.sid = d_prof; a.mt = d_mt; a.perm = d_perm;
     CK(hipFuncSetAttribute((const void *)k_roc_encode_u<UB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, UGeom<UB>::LDS_BYTES));
-    CK(hipFuncSetAttribute((const void *)k_roc_encode_u2<UB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, U2Geom<UB>::LDS_BYTES));
+    const uint32_t lds2 = u2_enc_lds_bytes<UB>(true);
+    CK(hipFuncSetAttribute((const void *)k_roc_encode_u2<UB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
+    const int narm = UB == 20 && n > U2Dense::MIN_N && n <= U2Dense::MAX_N ? 3 : 2;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    struct Res { uint64_t head; uint32_t nw, st; std::vector<uint32_t> words, order; float ms; } r[2];
-    for (int which = 0; which < 2; which++) {
-        for (int rep = 0; rep < 2; rep++) {
+    struct Res { uint64_t head; uint32_t nw, st; std::vector<uint32_t> words, order; float ms, ms_max; } r[3];
+    for (int which = 0; which < narm; which++) {
+        r[which].ms = 1e30f; r[which].ms_max = 0.f;
+        for (int rep = 0; rep < 6; rep++) {  // the first one warms up
             CK(hipMemset(d_arena, 0, aw * 4)); CK(hipMemset(d_st, 0xff, 4)); CK(hipMemset(d_perm, 0, n * 4));
             CK(hipEventRecord(e0, 0));
             if (which == 0) hipLaunchKernelGGL((k_roc_encode_u<UB, true>), dim3(1), dim3(64), UGeom<UB>::LDS_BYTES, 0, a);
-            else hipLaunchKernelGGL((k_roc_encode_u2<UB, true>), dim3(1), dim3(64), U2Geom<UB>::LDS_BYTES, 0, a, (const U2Div *)d_tab);
+            else { a.dense = which == 2; hipLaunchKernelGGL((k_roc_encode_u2<UB, true>), dim3(1), dim3(64), lds2, 0, a, (const U2Div *)d_tab); }
             CK(hipEventRecord(e1, 0));
             CK(hipDeviceSynchronize());
-            CK(hipEventElapsedTime(&r[which].ms, e0, e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            if (rep) { r[which].ms = std::min(r[which].ms, ms); r[which].ms_max = std::max(r[which].ms_max, ms); }
         }
         CK(hipMemcpy(&r[which].head, d_heads, 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(&r[which].nw, d_nw, 4, hipMemcpyDeviceToHost));
         CK(hipMemcpy(&r[which].st, d_st, 4, hipMemcpyDeviceToHost));
@@ -68,6 +73,14 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
     printf("UB=%d n=%u P=%u seed=%u: ENCODE old %.1f ns/step, new %.1f ns/step; status %u/%u head %llx/%llx words %u/%u first order diff at %zu -> %s\n",
            UB, n, P, seed, r[0].ms * 1e6 / n, r[1].ms * 1e6 / n, r[0].st, r[1].st, (unsigned long long)r[0].head,
            (unsigned long long)r[1].head, r[0].nw, r[1].nw, fd, same ? "IDENTICAL" : "MISMATCH");
+    printf("    five repeats, ns/step min..max: old %.1f..%.1f, bitmap %.1f..%.1f\n", r[0].ms * 1e6 / n, r[0].ms_max * 1e6 / n, r[1].ms * 1e6 / n, r[1].ms_max * 1e6 / n);
+    if (narm == 3) {
+        const bool dsame = r[2].head == r[1].head && r[2].nw == r[1].nw && r[2].words == r[1].words && r[2].order == r[1].order && r[2].st == 0;
+        size_t dd = 0; while (dd < n && r[2].order[dd] == r[1].order[dd]) dd++;
+        printf("    DENSE %.1f..%.1f ns/step against bitmap %.1f..%.1f; status %u head %llx words %u first order diff at %zu -> %s\n", r[2].ms * 1e6 / n,
+               r[2].ms_max * 1e6 / n, r[1].ms * 1e6 / n, r[1].ms_max * 1e6 / n, r[2].st, (unsigned long long)r[2].head, r[2].nw, dd, dsame ? "IDENTICAL" : "MISMATCH");
+        same = same && dsame;
+    }
     // ---- decode the (old-kernel) stream with both decoders
     bool dsame = true;
     {
@@ -120,6 +133,10 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
     const char *names[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "fix-up chain .. v_mov k (12)", "add64, L1 cmp, 3 readlanes (5)", "bitmap valu, ff1, row read (8)",
         "ds_write, slice 0 (8)", "L1 readlane.. L2 cmp, E1, ff1, entry (9)", "ds_read, slice 1, L2 readlane, division .. waitcnt (24)", "L3a valu: bcnt, dpp, cmp (10)",
         "L3a ff1, salu, 3 readlanes, sub (10)", "L3b: mbcnt, cmp, and, ff1, x (6)", "push 2 + order (7)", "row write-back (3)", "exit tests (7)"};
+    const char *dnames[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "fix-up chain .. k readlane (11)", "L1 cmp, add64, 2 readlanes (5)", "ff1, row read (4)",
+        "slice 0, slice 1 (14)", "L1 readlane, mul_hi, k sub, L2 cmp, mad, E1, ff1, entry (12)", "2 ds_read, mad, L2 readlane, row update (9)", "k sub, shift mask (4)",
+        "add64, mad, waitcnt (4)", "slot / base read-out, mul, x, shift (8)", "push 2 + order (7)", "row write-back (3)", "exit tests (7)"};
+    if (narm == 3) for (int q = 0; q < 14; q++) names[q] = dnames[q];
     double tot = 0, pc = (double)prof[1] / n;
     for (int q = 0; q < 14; q++) { printf("  %-58s %8.1f  net %7.1f cycles/step\n", names[q], (double)prof[q] / n, (double)prof[q] / n - pc); tot += prof[q]; }
     printf("  total %.1f, net of probes %.1f cycles/step\n", tot / n, tot / n - 14 * pc);

@@ -123,6 +123,12 @@ inline uint32_t lane_lists_per_wave(const vidc_ctx *, uint32_t, uint32_t) {
     return (forced == 8 || forced == 16 || forced == 32) ? (uint32_t)forced : 64u;
 }
 inline bool old_u_kernels() { return env_1("VIDC_OLD_U"); }
+// VIDC_U2_DENSE=0 keeps every list of the 20-bit chain launch on the bitmap body; default: lists of 4097 .. 65 536 ids select from
+// dense 16-id blocks (roc_u2.h, U2Dense)
+inline bool u2_dense() {
+    const char *e = std::getenv("VIDC_U2_DENSE");
+    return !(e && e[0] == '0' && !e[1]);
+}
 
 // test hook: VIDC_FORCE_GENERAL=1 routes every list through the general (sorted-position / bucket) kernels
 inline bool force_general() { return env_1("VIDC_FORCE_GENERAL"); }
@@ -692,6 +698,7 @@ int enc_upload_worklists(EncodeCall &c) {
     // arbitration the S2 encode is 53.5-53.9 instead of 54.7-55.6 ms (interleaved, profiles/r05v_s2_ab_enc_prio.txt; the other
     // classes: no effect)
     c.enc_prio = [] { const char *e = std::getenv("VIDC_ENC_PRIO"); return e ? std::atoi(e) : 2; }();
+    a.dense = u2_dense() ? 1u : 0u;
     c.tr.mark("alloc + upload");
     return VIDC_OK;
 }
@@ -734,11 +741,12 @@ int enc_launch_u(EncodeCall &c, hipStream_t st_) {
         }
         VIDC_TRY(enc_launch(c, k_roc_encode_u<BITS, true>, k_roc_encode_u<BITS, false>, dim3(b.nwork), UGeom<BITS>::LDS_BYTES, st_, b));
     } else {
+        const uint32_t lds = u2_enc_lds_bytes<BITS>(b.dense != 0u);  // (one workgroup per CU with either body)
         if constexpr (BITS == 20) {
-            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<BITS, false>, U2Geom<BITS>::LDS_BYTES));
-            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<BITS, true>, U2Geom<BITS>::LDS_BYTES));
+            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<BITS, false>, lds));
+            VIDC_TRY(set_big_lds((const void *)k_roc_encode_u2<BITS, true>, lds));
         }
-        VIDC_TRY(enc_launch(c, k_roc_encode_u2<BITS, true>, k_roc_encode_u2<BITS, false>, dim3(b.nwork), U2Geom<BITS>::LDS_BYTES, st_, b, dt));
+        VIDC_TRY(enc_launch(c, k_roc_encode_u2<BITS, true>, k_roc_encode_u2<BITS, false>, dim3(b.nwork), lds, st_, b, dt));
     }
     if (is_chain) VIDC_HIP(hipEventRecord(ctx->ev_chain[1], st_));
     return VIDC_OK;

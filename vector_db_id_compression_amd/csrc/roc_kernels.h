@@ -54,6 +54,7 @@ struct RocEncArgs {
     const uint64_t *skey_off;  // [nlist+1] or nullptr
     const uint32_t *mt;
     uint32_t lpw;              // lane-per-list kernels: lists per wavefront (0 = 64); the remaining lanes idle
+    uint32_t dense;            // k_roc_encode_u2<20>: lists of 4097 .. 65 536 ids select from dense 16-id blocks (VIDC_U2_DENSE)
 };
 
 // Worst-case arena layout in closed form (no per-list offset array to build, upload or read): a list of n ids

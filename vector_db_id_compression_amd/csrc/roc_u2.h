@@ -18,6 +18,10 @@
 //    the body is ordered so that those windows and the LDS round trip hold independent vector work (the division of
 //    B, counter updates, the removal of the previous id from the bitmap).
 //  * renormalisation is branch-free (s_cselect + unconditional ring write + stack-pointer add of the condition).
+//  * k_roc_encode_u2<20> keeps a list of 4097 .. 65 536 ids as dense blocks of 16 ids in POSITION space instead of the bitmap
+//    (U2Dense, U2_ENC_*_D below): the third search level, the bit select and the rewrite of the bitmap word become one LDS read
+//    by all lanes, one v_readlane and a masked 16-bit store (87 instructions per step against 106).  The kernel decides per list;
+//    RocEncArgs::dense = 0 (VIDC_U2_DENSE=0) keeps every list on the bitmap body.
 //
 // Anything rare (index-pop renormalisation, stack underflow, nmax <= 2, ring spills) leaves the asm loop at a step
 // boundary and runs one generic C++ step (u2_slow_step) on the same data structures.
@@ -39,6 +43,24 @@ struct U2Geom {
     static constexpr uint32_t BITMAP_BYTES = NE * G * 8u;
     static constexpr uint32_t LDS_BYTES = BITMAP_BYTES + 16u;  // + a dummy word: target of the "no pending removal" store
 };
+
+// Dense 16-id blocks in POSITION space (k_roc_encode_u2<20> only, lists of 4097 .. 65 536 ids): block b holds the ids at positions
+// 16 b .. 16 b + 15 of the ascending input as 16 u16 slots (id - first id of the block) and the first id in a u32 table.  Blocks are
+// stored in REVERSED order like the bitmap entries (storage index e = 4095 - b = L1 * 64 + L2 of the reversed counters).  The base
+// table sits in FRONT of the slots so that its read takes the 16-bit offset field (one address instruction instead of two); a step
+// reads 64 u16 from the block's first slot on, i.e. up to 96 bytes past the block: the pad behind the last block.
+struct U2Dense {
+    static constexpr uint32_t MIN_N = 4096u;              // shorter lists stay with the lane / general kernels anyway
+    static constexpr uint32_t MAX_N = 65536u;             // 4096 blocks
+    static constexpr uint32_t BASE_OFF = 16u;             // u32 base[4096]
+    static constexpr uint32_t SLOT_OFF = BASE_OFF + 4096u * 4u;  // u16 slot[4096][16]
+    static constexpr uint32_t LDS_BYTES = SLOT_OFF + 4096u * 32u + 128u;
+};
+// LDS bytes of a k_roc_encode_u2<UB, *> launch
+template <int UB>
+constexpr uint32_t u2_enc_lds_bytes(bool dense) {
+    return UB == 20 && dense && U2Dense::LDS_BYTES > U2Geom<UB>::LDS_BYTES ? U2Dense::LDS_BYTES : U2Geom<UB>::LDS_BYTES;
+}
 
 // LDS word index of id x: entries are stored in REVERSED order (entry e' = e ^ 4095), words inside an entry ascending
 template <int UB>
@@ -119,6 +141,84 @@ __device__ __forceinline__ uint32_t u2_slow_step(uint64_t &head, WStack &st, uin
     row -= lane < L2 ? 1u : 0u;
     u2_row_set(ra, rb, L1, row);
     bm[e * U::G + g] = W & ~(1ull << b);
+    wave_sync();
+    ans_id_push(head, st, x, p0, p1);
+    return x;
+}
+
+// ---- dense blocks: staging, counters, generic step
+// One coalesced pass over the list: slots and bases into LDS, and every check the dense body relies on -- ids strictly ascending
+// and below 2^31, the precision the prepass wrote at most 20 bits and wide enough for the largest id, every block's span below 2^16.
+// false: the caller runs the bitmap body on this list from scratch (which also reports what has to be reported).
+__device__ __forceinline__ bool u2d_stage(const RocEncArgs &a, uint64_t off, uint32_t n, uint32_t l, unsigned char *smem) {
+    uint16_t *slots = (uint16_t *)(smem + U2Dense::SLOT_OFF);
+    uint32_t *base = (uint32_t *)(smem + U2Dense::BASE_OFF);
+    const uint32_t lane = lane_id();
+    bool fail = false;
+    uint32_t mx = 0;
+    uint64_t prev_last = 0;  // id at j0 - 1
+    for (uint32_t j0 = 0; j0 < n; j0 += 512u) {  // 8 loads per lane in flight
+        uint64_t v[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; u++) {
+            const uint32_t j = j0 + u * 64u + lane;
+            v[u] = j < n ? __builtin_nontemporal_load(&a.ids[off + j]) : ~0ull;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; u++) {
+            const uint32_t j = j0 + u * 64u + lane;
+            uint64_t below = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v[u] >> 32), 1, 64) << 32) |
+                             (uint32_t)__shfl_up((int)(uint32_t)v[u], 1, 64);
+            if (lane == 0) below = prev_last;
+            prev_last = rfl64(((uint64_t)rl((uint32_t)(v[u] >> 32), 63) << 32) | rl((uint32_t)v[u], 63));
+            const uint32_t first = (uint32_t)__shfl((int)(uint32_t)v[u], (int)(lane & ~15u), 64);  // id at position j & ~15
+            if (j >= n) continue;
+            const uint32_t x = (uint32_t)v[u];
+            fail |= (v[u] >> 31) != 0 || (j != 0u && below >= v[u]) || x - first > 0xffffu;
+            mx = x > mx ? x : mx;
+            const uint32_t e = 4095u - (j >> 4);  // j < n <= 65 536
+            slots[e * 16u + (j & 15u)] = (uint16_t)(x - first);
+            if ((j & 15u) == 0u) base[e] = x;
+        }
+    }
+    wave_sync();
+    const uint32_t P = rfl(a.prec[l]);  // written by the prepass
+    const uint32_t maxid = rfl(wave_max_u32(mx));  // (wave-uniform for the compiler too: the caller branches on the result)
+    return !(ballot(fail) || P > 20u || (maxid >> P) != 0u);
+}
+// counters of a full list in closed form: every block holds 16 ids, the last one n - 16 (nblocks - 1)
+__device__ __forceinline__ void u2d_init_counts(uint32_t n, uint32_t &E1, v32u &ra, v32u &rb) {
+    const uint32_t lane = lane_id();
+    E1 = min(n, 1024u * (63u - lane));
+#pragma unroll
+    for (int L1 = 63; L1 >= 0; L1--) {
+        const uint32_t lo = 1024u * (63u - (uint32_t)L1), hi = lo + 16u * (63u - lane);  // positions of block (L1, lane): from hi on
+        const uint32_t row = min(max(n, lo), hi) - lo;
+        if (L1 < 32) ra[L1] = row; else rb[L1 - 32] = row;
+    }
+}
+// one generic encode step on the dense blocks (rare path): codec.cpp:131-137
+__device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, uint32_t nmax, uint32_t &E1, v32u &ra, v32u &rb,
+                                               unsigned char *smem, uint32_t p0, uint32_t p1) {
+    uint16_t *slots = (uint16_t *)(smem + U2Dense::SLOT_OFF);
+    const uint32_t *base = (const uint32_t *)(smem + U2Dense::BASE_OFF);
+    const uint32_t lane = lane_id();
+    ws_prepare(st);
+    const uint32_t lq = 0x80000000u / nmax;
+    uint32_t k = ans_idx_pop(head, st, nmax, lq * nmax, ~0ull / (uint64_t)nmax);
+    const uint32_t L1 = ff1(ballot(E1 <= k));
+    k -= rl(E1, L1);
+    uint32_t row = u2_row_get(ra, rb, L1);
+    const uint32_t L2 = ff1(ballot(row <= k));
+    k -= rl(row, L2);
+    const uint32_t e = L1 * 64u + L2;
+    const uint32_t sv = slots[e * 16u + (lane & 15u)];
+    const uint32_t x = rfl(base[e]) + rl(sv, k);
+    wave_sync();
+    if (lane > k && lane < 16u) slots[e * 16u + lane - 1u] = (uint16_t)sv;  // the alive slots behind k move down by one
+    E1 -= lane < L1 ? 1u : 0u;
+    row -= lane < L2 ? 1u : 0u;
+    u2_row_set(ra, rb, L1, row);
     wave_sync();
     ans_id_push(head, st, x, p0, p1);
     return x;
@@ -336,6 +436,112 @@ __device__ __forceinline__ uint32_t u2_slow_step(uint64_t &head, WStack &st, uin
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* (first instruction of the exit test, SCC = B >= 2^31: m0 settles meanwhile) */ \
     "v_writelane_b32 v6, s40, m0\n"
 
+// ---- the step on dense blocks (U2Dense): identical to the bitmap step up to level 2, with the rank k kept in s42 (v_cmp takes the
+// SGPR operand; the two subtractions sit behind the counter updates that fill their v_readlane windows).  Behind level 2 all 64
+// lanes read u16 slots from the block's first slot on (lane j holds slot j; lanes >= 16 read the following blocks or the pad), one
+// v_readlane at the remaining rank gives the slot, base + slot is x in s40 where the bitmap step leaves it.  The removal is a shift
+// inside the block: lanes k_rem < L <= 15 store their own value one slot down (v28 is the lane's slot address MINUS 2, the read adds
+// it back as an offset) while the v_readlane window of x runs.  LDS operations of one wavefront execute in order, so the next read
+// of the block sees the shift; slots behind a block's alive count hold stale values and are never selected.  Nothing is pending at
+// a step boundary (the bitmap step clears the previous id's bit at the top of the next one).
+// A scalar instruction issued within ~16 cycles of a v_readlane / v_cmp waits the window out, and the removed instructions were the
+// bitmap step's filler: both slices are therefore renormalised BEFORE level 2 (they depend on q alone), which frees the division of
+// B to start early, and its 16-cycle multiplies (v_mul_hi, v_mul_lo) and the counter updates sit behind the read-outs.
+//   v3 = 2 * lane - 2 + SLOT_OFF   v26 base address   v28 slot address - 2   v30 slots   v31 base   s46 base   s48 slot
+//   s42 k, then the rank inside the block   s[82:83] lanes of the shift
+#define U2_ENC_TOP_D \
+    U2P(130) U2P(131) \
+    "v_lshrrev_b32_e64 v14, 16, s40\n"                 /* x_hi */ \
+    "v_bfe_u32 v15, s40, 0, 16\n"                      /* x_lo */ \
+    "v_add_u32 v16, v48, v14\n"                        /* s = r_B + x_hi */ \
+    "v_mad_u32_u24 v16, v15, s41, v16\n"               /*   + x_lo * mul */ \
+    "v_mul_hi_u32 v17, v16, v10\n"                     /* q^ = mulhi(s, 2^32 / d) */ \
+    "v_mad_i32_i24 v18, v17, v29, v16\n"               /* r = s - q^ d in [0, 2d) */ \
+    "v_sub_u32 v19, v18, v9\n" \
+    "v_min_u32 v52, v18, v19\n"                        /* k (of this lane's divisor) */ \
+    "v_ashrrev_i32 v27, 31, v19\n"                     /* -1 if r < d */ \
+    "v_add3_u32 v20, v17, v27, 1\n"                    /* qf = q^ + (r >= d) */ \
+    "v_readlane_b32 s42, v52, s69\n"                   /* k of the step */ U2P(132) \
+    "v_cmp_ge_u32 vcc, s42, v4\n"                      /* level 1 */ \
+    "v_add_co_u32_e64 v50, s[78:79], v46, v20\n"       /* q = head div d (per lane) */ \
+    "v_addc_co_u32_e64 v51, s[78:79], 0, v47, s[78:79]\n" \
+    "v_readlane_b32 s50, v50, s69\n" \
+    "v_readlane_b32 s51, v51, s69\n" \
+    U2P(133) \
+    "s_ff1_i32_b64 s43, vcc\n" \
+    "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
+    "v_mov_b32 v13, v64\n"                             /* row L1 */ \
+    "s_set_gpr_idx_off\n" U2P(134) \
+    "s_and_b32 m0, s60, 63\n"                          /* slice 0 (codec.cpp:65-76), branch-free */ \
+    "s_cmp_ge_u32 s51, s73\n" \
+    "v_writelane_b32 v5, s50, m0\n" \
+    "s_cselect_b32 s52, s51, s50\n" \
+    "s_cselect_b32 s53, 0, s51\n" \
+    "s_addc_u32 s60, s60, 0\n" \
+    "s_lshl_b64 s[54:55], s[52:53], s76\n" \
+    "s_and_b32 s62, s60, 63\n"                         /* slice 1: B is known before the select has started */ \
+    "s_cmp_ge_u32 s55, s74\n" \
+    "s_cselect_b32 s41, 0, s75\n" \
+    "s_cselect_b32 s56, s55, s54\n" \
+    "s_cselect_b32 s57, 0, s55\n" \
+    "s_addc_u32 s60, s60, 0\n" \
+    "s_lshl_b64 s[58:59], s[56:57], s77\n"             /* B */ U2P(135) \
+    "v_readlane_b32 s49, v4, s43\n" \
+    "v_mul_hi_u32 v36, s58, v7\n"                      /* B div d (all lanes): mulhi64(B, m); 16 cycles, the readlane's window */ \
+    "s_sub_u32 s42, s42, s49\n" \
+    "v_cmp_ge_u32 vcc, s42, v13\n"                     /* level 2 */ \
+    "v_mad_u64_u32 v[38:39], s[78:79], s58, v8, v[36:37]\n" \
+    "v_subrev_u32 v27, s43, v2\n"                      /* lane - L1 */ \
+    "v_ashrrev_i32 v27, 31, v27\n" \
+    "v_add_u32 v4, v4, v27\n"                          /* E1 -= 1 in lanes below L1 */ \
+    "v_mov_b32 v40, v38\n" \
+    "s_ff1_i32_b64 s44, vcc\n" \
+    "s_lshl_b32 s45, s43, 6\n" \
+    "s_or_b32 s45, s45, s44\n" U2P(136)
+#define U2_ENC_MID_D \
+    "v_lshl_add_u32 v28, s45, 5, v3\n" \
+    "v_lshlrev_b32_e64 v26, 2, s45\n" \
+    "ds_read_u16 v30, v28 offset:2\n" \
+    "ds_read_b32 v31, v26 offset:16\n"                 /* (U2Dense::BASE_OFF) */ \
+    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[40:41]\n" \
+    "v_readlane_b32 s63, v13, s44\n" \
+    "v_subrev_u32 v59, s44, v2\n"                      /* lane - L2 */ \
+    "v_ashrrev_i32 v59, 31, v59\n" \
+    "v_add_u32 v13, v13, v59\n"                        /* row -= 1 in lanes below L2 */ U2P(137) \
+    "s_sub_u32 s42, s42, s63\n"                        /* rank inside the block */ \
+    "s_sub_u32 s68, 15, s42\n"                         /* removal mask: lanes k_rem < L <= 15 */ \
+    "s_add_u32 s72, s42, 1\n" \
+    "s_bfm_b64 s[82:83], s68, s72\n" U2P(138) \
+    "v_add_co_u32_e64 v44, s[78:79], v39, v43\n" \
+    "v_addc_co_u32_e64 v45, s[80:81], 0, 0, s[78:79]\n" \
+    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[44:45]\n" \
+    "s_waitcnt lgkmcnt(0)\n" U2P(139)
+#define U2_ENC_BOT_D(ORDER, LSHR, RING, TAIL) \
+    "v_readlane_b32 s48, v30, s42\n"                   /* the slot */ \
+    "v_readfirstlane_b32 s46, v31\n"                   /* the block's first id */ \
+    "v_mul_lo_u32 v48, v46, v9\n"                      /* (16 cycles: the window of the two read-outs) */ \
+    "v_sub_u32 v48, s58, v48\n"                        /* r_B in [0, 2d) */ \
+    "s_add_u32 s40, s46, s48\n"                        /* x */ \
+    "s_mov_b64 exec, s[82:83]\n"                       /* removal: the alive slots behind k_rem move one slot down */ \
+    "ds_write_b16 v28, v30\n" \
+    "s_mov_b64 exec, -1\n" U2P(140) \
+    "s_mov_b32 m0, s62\n" \
+    "s_and_b32 s68, s40, 0xffff\n" \
+    "s_or_b32 s68, s68, s54\n" \
+    "v_writelane_b32 v5, s68, m0\n"                    /* word of the second slice (kept only if it renormalised) */ \
+    ORDER U2P(141) \
+    "s_set_gpr_idx_on s43, gpr_idx(DST)\n" \
+    "v_mov_b32 v64, v13\n" \
+    "s_set_gpr_idx_off\n" U2P(142) \
+    LSHR                                               /* next index pop must not renormalise (u2_needs_generic): SCC = B >= 2^31 */ \
+    "s_cselect_b32 s71, s70, 0\n" \
+    "s_cmp_ge_u32 s59, 0x7ff80000\n" \
+    "s_cselect_b32 s71, 0, s71\n" \
+    RING \
+    "s_add_u32 s69, s69, 1\n" U2P(143) \
+    "s_cmp_lt_u32 s69, s71\n" \
+    TAIL
+
 // store order-ring lanes [0, s72) at order[s87 ...]; s87 += s72
 #define U2_ORDER_FLUSH \
     "v_cmp_gt_u32 vcc, s72, v2\n" \
@@ -421,61 +627,72 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
     const uint32_t l = rfl(a.worklist[wi]);
     const uint64_t off = rfl64(a.offsets[l]);
     const uint32_t n = rfl((uint32_t)(a.offsets[l + 1] - off));
-    {
-        uint4 *z = (uint4 *)smem;
-        for (uint32_t w = lane; w < U::LDS_BYTES / 16u; w += 64) z[w] = make_uint4(0, 0, 0, 0);
-    }
-    wave_sync();
-    // The host classified this list by its LAST id (light prepass): the loop checks the rest -- every id inside
-    // [0, 2^31) and, because the sampled ids only turn into input positions for an ascending list, the order when the
-    // permutation is wanted.  An id beyond the bitmap is only counted in the maximum (the precision test below sends
-    // the list to the general kernels).
-    bool dup = false, bad = false;
-    uint32_t mx = 0;
-    uint64_t prev_last = 0;  // id at j0 - 1
-    for (uint32_t j0 = 0; j0 < n; j0 += 512u) {  // 8 loads per lane in flight (one per iteration made this loop 1.2 ms of S1)
-        uint64_t v[8];
-#pragma unroll
-        for (uint32_t u = 0; u < 8u; u++) {
-            const uint32_t j = j0 + u * 64u + lane;
-            v[u] = j < n ? __builtin_nontemporal_load(&a.ids[off + j]) : ~0ull;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 8u; u++) {
-            if (WANT_ORDER) {
-                uint64_t below = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v[u] >> 32), 1, 64) << 32) |
-                                 (uint32_t)__shfl_up((int)(uint32_t)v[u], 1, 64);
-                if (lane == 0) below = prev_last;
-                prev_last = rfl64(((uint64_t)rl((uint32_t)(v[u] >> 32), 63) << 32) | rl((uint32_t)v[u], 63));
-                if (v[u] != ~0ull && (j0 + u * 64u + lane) != 0u && below >= v[u]) dup = true;
-            }
-            if (v[u] == ~0ull) continue;
-            bad |= (v[u] >> 31) != 0;
-            const uint32_t x = (uint32_t)v[u];
-            mx = x > mx ? x : mx;
-            if (x >> UB) continue;
-            const uint32_t bit = 1u << (x & 31u);
-            const uint32_t old = atomicOr(&bm32[u2_word_of<UB>(x) * 2u + ((x >> 5) & 1u)], bit);
-            dup |= (old & bit) != 0;
-        }
-    }
-    wave_sync();
-    if (ballot(bad)) {
-        if (lane == 0) a.status[l] = VIDC_ST_DOMAIN;
-        return;
-    }
-    const uint32_t P = rfl(a.prec[l]);  // written by the prepass
-    const uint32_t maxid = wave_max_u32(mx);
-    // multisets, precisions above 20 bits and ids that do not fit the precision (reference carry quirk) take the
-    // general kernels
-    if (ballot(dup) || P > 20u || (maxid >> P) != 0u || (maxid >> UB) != 0u) {
-        if (lane == 0) a.status[l] = VIDC_ST_PENDING_SORT;
-        return;
-    }
     uint32_t E1;
     v32u ra, rb;
-    u2_build_counts<UB>(bm, E1, ra, rb);
+    // dense blocks (20-bit launches, 4097 .. 65 536 ids); a list that fails one of their checks runs the bitmap body below from
+    // scratch, which hands back what has to be handed back
+    bool dense = false;
+    if constexpr (UB == 20) {
+        if (a.dense && n > U2Dense::MIN_N && n <= U2Dense::MAX_N) dense = rfl((uint32_t)u2d_stage(a, off, n, l, smem)) != 0u;
+    }
+    if (dense) {
+        u2d_init_counts(n, E1, ra, rb);
+    } else {
+        {
+            uint4 *z = (uint4 *)smem;
+            for (uint32_t w = lane; w < U::LDS_BYTES / 16u; w += 64) z[w] = make_uint4(0, 0, 0, 0);
+        }
+        wave_sync();
+        // The host classified this list by its LAST id (light prepass): the loop checks the rest -- every id inside
+        // [0, 2^31) and, because the sampled ids only turn into input positions for an ascending list, the order when the
+        // permutation is wanted.  An id beyond the bitmap is only counted in the maximum (the precision test below sends
+        // the list to the general kernels).
+        bool dup = false, bad = false;
+        uint32_t mx = 0;
+        uint64_t prev_last = 0;  // id at j0 - 1
+        for (uint32_t j0 = 0; j0 < n; j0 += 512u) {  // 8 loads per lane in flight (one per iteration made this loop 1.2 ms of S1)
+            uint64_t v[8];
+#pragma unroll
+            for (uint32_t u = 0; u < 8u; u++) {
+                const uint32_t j = j0 + u * 64u + lane;
+                v[u] = j < n ? __builtin_nontemporal_load(&a.ids[off + j]) : ~0ull;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 8u; u++) {
+                if (WANT_ORDER) {
+                    uint64_t below = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v[u] >> 32), 1, 64) << 32) |
+                                     (uint32_t)__shfl_up((int)(uint32_t)v[u], 1, 64);
+                    if (lane == 0) below = prev_last;
+                    prev_last = rfl64(((uint64_t)rl((uint32_t)(v[u] >> 32), 63) << 32) | rl((uint32_t)v[u], 63));
+                    if (v[u] != ~0ull && (j0 + u * 64u + lane) != 0u && below >= v[u]) dup = true;
+                }
+                if (v[u] == ~0ull) continue;
+                bad |= (v[u] >> 31) != 0;
+                const uint32_t x = (uint32_t)v[u];
+                mx = x > mx ? x : mx;
+                if (x >> UB) continue;
+                const uint32_t bit = 1u << (x & 31u);
+                const uint32_t old = atomicOr(&bm32[u2_word_of<UB>(x) * 2u + ((x >> 5) & 1u)], bit);
+                dup |= (old & bit) != 0;
+            }
+        }
+        wave_sync();
+        if (ballot(bad)) {
+            if (lane == 0) a.status[l] = VIDC_ST_DOMAIN;
+            return;
+        }
+        const uint32_t Pb = rfl(a.prec[l]);  // written by the prepass
+        const uint32_t maxid = wave_max_u32(mx);
+        // multisets, precisions above 20 bits and ids that do not fit the precision (reference carry quirk) take the
+        // general kernels
+        if (ballot(dup) || Pb > 20u || (maxid >> Pb) != 0u || (maxid >> UB) != 0u) {
+            if (lane == 0) a.status[l] = VIDC_ST_PENDING_SORT;
+            return;
+        }
+        u2_build_counts<UB>(bm, E1, ra, rb);
+    }
 
+    const uint32_t P = rfl(a.prec[l]);  // written by the prepass
     const uint32_t p0 = P < 16u ? P : 16u, p1 = P > 16u ? P - 16u : 0u;
     WStack st;
     {
@@ -486,7 +703,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
     uint32_t obuf = 0, obase = 0;
     uint32_t *order = WANT_ORDER ? a.perm + off : nullptr;  // sampled ids; k_perm_from_order turns them into positions
     const uint32_t T0 = 0x80000000u >> p0, T1 = 0x80000000u >> p1, MULN = 1u << p1;
-    const uint32_t l3off = U::G == 4u ? (lane & 3u) * 8u : 0u;
+    const uint32_t l3off = dense ? 2u * lane + (U2Dense::SLOT_OFF - 2u) : U::G == 4u ? (lane & 3u) * 8u : 0u;
 
 #ifdef U2_PROF
     uint32_t prof[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -500,7 +717,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
         if (st.sp - st.lo >= U2_RING_ROOM) ws_spill32(st);
         // generic step: the last two (the fix-up reciprocal needs nmax' >= 2) and index pops that renormalise
         if (nmax < 3u || u2_needs_generic(head)) {
-            const uint32_t x = u2_slow_step<UB>(head, st, nmax, E1, ra, rb, bm, p0, p1);
+            const uint32_t x = dense ? u2d_slow_step(head, st, nmax, E1, ra, rb, smem, p0, p1)
+                                     : u2_slow_step<UB>(head, st, nmax, E1, ra, rb, bm, p0, p1);
             if (WANT_ORDER) {
                 if (lane == 0) order[obase] = x;
                 obase++;
@@ -535,7 +753,17 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
               "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57",\
               "s62", "s63", "s64", "s68", "s70", "s71", "s72", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s96",       \
               "s97", "s98", "s99")
-        if (U::G == 4u) {
+        if (dense) {
+            // (eight / four copies and the ring test in the last one, like the bitmap bodies)
+#define U2_STEP_D(ORDER, LSHR) U2_ENC_TOP_D U2_ENC_MID_D U2_ENC_BOT_D(ORDER, LSHR, "", "s_cbranch_scc0 7f\n")
+#define U2_LAST_D(ORDER, LSHR) U2_ENC_TOP_D U2_ENC_MID_D U2_ENC_BOT_D(ORDER, LSHR, U2_RING_CHECK, "s_cbranch_scc1 1b\n")
+            if (WANT_ORDER) U2_ENC_ASM(U2_ENC_ENTRY "1:\n" U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "")
+                                       U2_LAST_D(U2_ENC_ORDER, "") "7:\n" U2_ENC_OUTER(U2_ORDER_FLUSH));
+            else U2_ENC_ASM(U2_ENC_ENTRY "1:\n" U2_STEP_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") U2_STEP_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") U2_STEP_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n")
+                            U2_LAST_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") "7:\n" U2_ENC_OUTER(""));
+#undef U2_STEP_D
+#undef U2_LAST_D
+        } else if (U::G == 4u) {
             // four steps per loop iteration: the taken branch at the end of a step costs ~6 cycles of instruction-buffer refill
 #define U2_STEP_X(ORDER, LSHR) U2_ENC_TOP_NL U2_ENC_MID_G4 U2_ENC_SLICE1_G4 U2_ENC_L3_G4 U2_ENC_BOT_T(ORDER, LSHR, "", "s_cbranch_scc0 7f\n")
             if (WANT_ORDER) U2_ENC_ASM(U2_ENC_ENTRY "1:\n" U2_STEP_X(U2_ENC_ORDER, "") U2_STEP_X(U2_ENC_ORDER, "") U2_STEP_X(U2_ENC_ORDER, "") U2_STEP_X(U2_ENC_ORDER, "") U2_STEP_X(U2_ENC_ORDER, "") U2_STEP_X(U2_ENC_ORDER, "") U2_STEP_X(U2_ENC_ORDER, "")
@@ -565,7 +793,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
         // ---- back to the plain state.  head = B + c(x); x's bit leaves the bitmap; slices 2 and 3 of ID_push
         // (precision 0: "if head >= 2^63 push", codec.cpp:92-105) can only fire on the way out
         head = s_B + (uint64_t)((s_x & 0xffffu) * s_mul + (s_x >> 16));
-        bm[s_waddr >> 3] = s_w & ~(1ull << (s_x & 63u));
+        if (!dense) bm[s_waddr >> 3] = s_w & ~(1ull << (s_x & 63u));  // (a dense step leaves nothing pending)
         ws_window(st);
         if (__builtin_expect((head >> 63) != 0ull, 0)) {
             ws_prepare(st);

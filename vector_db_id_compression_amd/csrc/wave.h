@@ -235,7 +235,8 @@ __device__ __forceinline__ void ans_id_push(uint64_t &head, WStack &s, uint32_t 
     // slices 2 and 3 (precision 0, symbol 0): "if (head >= 2^63) push", twice; after one push head < 2^31, so the
     // second test can only fire when the first did not.  Only reachable through the carry quirk (x >= 2^P).
     uint32_t top;
-    asm volatile("s_lshr_b32 %0, %1, 31" : "=s"(top) : "s"((uint32_t)(head >> 32)));
+    // (rfl: the head is wave-uniform, but where the compiler chose to keep it in VGPRs an "s" operand is not legalised for it)
+    asm volatile("s_lshr_b32 %0, %1, 31" : "=s"(top) : "s"(rfl((uint32_t)(head >> 32))));
     if (__builtin_expect(top != 0u, 0)) {
         ans_u_push(head, s, 0u, 0u);
         ans_u_push(head, s, 0u, 0u);
