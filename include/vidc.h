@@ -161,6 +161,10 @@ int vidc_roc_decode_rows(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const uin
 /* End-state self check of the last decode_all: number of lists whose final ANS state is not the
  * initial one (head 2^31; SURVEY appendix A invariant).  Lossy reference cases (Q2/Q3) count here. */
 uint64_t vidc_roc_last_decode_nonclean(const vidc_roc *r);
+/* Work items of the object's last decode call that a bucket-row decoder handed back (a bucket of the list would have taken one
+ * member more than its row holds) and that the call then decoded again, one after the other, on the general kernel: the output is
+ * the same, the call pays a serial chain.  A list that the request names twice counts twice.  0 after a call without hand-backs. */
+uint64_t vidc_roc_last_decode_handed_back(const vidc_roc *r);
 
 /* -------------------------------------------------------------- packed bits */
 /* Replaces CompressedIDInvertedListsPackedBits (custom_invlists_impl.cpp:64-118) and

@@ -46,6 +46,7 @@ int main(void) {
     CHECK(vidc_copy_d2h(ctx, decoded, d_out, sizeof decoded));
     REQUIRE(memcmp(decoded, want_order, sizeof want_order) == 0);
     REQUIRE(vidc_roc_last_decode_nonclean(roc) == 0);
+    REQUIRE(vidc_roc_last_decode_handed_back(roc) == 0);
     CHECK(vidc_roc_decode_lists(ctx, roc, 1, &one, (uint64_t *)d_out, out_off));
     REQUIRE(out_off[0] == 0 && out_off[1] == 4);
     /* error convention: a negative status + a message, nothing thrown */

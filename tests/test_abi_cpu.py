@@ -22,6 +22,7 @@ def test_header_symbols_are_exported(libpath):
     from vector_db_id_compression_amd import _lib
 
     assert declared == set(_lib.EXPORTED_SYMBOLS), declared ^ set(_lib.EXPORTED_SYMBOLS)
+    assert {"vidc_roc_last_decode_nonclean", "vidc_roc_last_decode_handed_back"} <= declared
     dll = ctypes.CDLL(libpath)
     for sym in sorted(declared):
         assert hasattr(dll, sym), sym
@@ -35,6 +36,10 @@ def test_pure_host_entry_points(libpath):
     assert L.vidc_packed_bits_for(0) == 0 and L.vidc_packed_bits_for(1) == 1
     assert L.vidc_packed_bits_for(1_000_000) == 20 and L.vidc_packed_bits_for(1023) == 10
     assert L.vidc_packed_bits_for(1024) == 11
+    # the decode self-checks of a ROC object: u64 accessors, 0 without an object
+    for name in ("vidc_roc_last_decode_nonclean", "vidc_roc_last_decode_handed_back"):
+        fn = getattr(L, name)
+        assert fn.restype is ctypes.c_uint64 and fn(None) == 0, name
 
 
 def test_no_gpu_fails_loudly(libpath):

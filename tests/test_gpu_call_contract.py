@@ -335,6 +335,7 @@ SURFACE = {
         "encode_rows": "(rows, precision_mode=-1, ctx=None)",
         "from_streams": "(offsets, precisions, heads, nwords, words_concat, mt_draws=None, ctx=None)",
         "info": "(self)",
+        "last_decode_handed_back": "property",
         "last_decode_nonclean": "property",
         "load": "(path, ctx=None)",
         "nlist": "property",

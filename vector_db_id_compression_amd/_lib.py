@@ -77,6 +77,7 @@ def _declare(lib):
     f("vidc_roc_decode_gather", C.c_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp)
     f("vidc_roc_decode_rows", C.c_int, _vp, _vp, _u64, _vp, _u32, _vp, _vp)
     f("vidc_roc_last_decode_nonclean", _u64, _vp)
+    f("vidc_roc_last_decode_handed_back", _u64, _vp)
     # packed bits
     f("vidc_packed_bits_for", C.c_int, _u64)
     f("vidc_packed_encode", C.c_int, _vp, _u64, _vp, _vp, C.c_int, _P(_vp))
@@ -176,7 +177,7 @@ EXPORTED_SYMBOLS = [
     "vidc_roc_encode", "vidc_roc_encode_rows", "vidc_roc_destroy", "vidc_roc_nlist", "vidc_roc_ntotal",
     "vidc_roc_compressed_bytes", "vidc_roc_total_words", "vidc_roc_list_info", "vidc_roc_export_words", "vidc_roc_export_all_words",
     "vidc_roc_perm", "vidc_roc_perm_dev", "vidc_roc_import", "vidc_roc_decode_all", "vidc_roc_decode_lists", "vidc_roc_decode_gather",
-    "vidc_roc_decode_rows", "vidc_roc_last_decode_nonclean", "vidc_roc_encode_dev",
+    "vidc_roc_decode_rows", "vidc_roc_last_decode_nonclean", "vidc_roc_last_decode_handed_back", "vidc_roc_encode_dev",
     "vidc_packed_bits_for", "vidc_packed_encode", "vidc_packed_destroy", "vidc_packed_compressed_bytes",
     "vidc_packed_bits", "vidc_packed_decode_all", "vidc_packed_decode_lists", "vidc_packed_decode_gather", "vidc_packed_get", "vidc_packed_export", "vidc_packed_total_words", "vidc_packed_export_all", "vidc_packed_import",
     "vidc_packed_encode_dev", "vidc_packed_offsets",

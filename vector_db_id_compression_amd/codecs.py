@@ -421,6 +421,12 @@ class RocLists(_ListCodec):
     def last_decode_nonclean(self):
         return int(lib().vidc_roc_last_decode_nonclean(self.h))
 
+    @property
+    def last_decode_handed_back(self):
+        """Work items of the last decode call that a bucket-row decoder handed back (a full member row) and that the call decoded
+        again on the general kernel: same output, a serial chain more (vidc_roc_last_decode_handed_back)."""
+        return int(lib().vidc_roc_last_decode_handed_back(self.h))
+
 
 class PackedLists(_ListCodec):
     """Fixed-width packed ids (vidc_packed): ceil(log2(ntotal+1)) bits per id, LSB-first."""

@@ -55,6 +55,7 @@ struct vidc_roc {
     DevBuf<uint64_t> d_offsets, d_heads, d_word_off;
     DevBuf<uint32_t> d_prec, d_nwords, d_draws, d_words, d_perm;
     mutable uint64_t last_nonclean = 0;
+    mutable uint64_t last_handed_back = 0;  // work items of the last decode call that came back with VIDC_ST_RETRY
     // graph objects: the rows ordered by edge count (k_rows_order_*), built by the first whole-graph decode_rows (guarded by mu)
     mutable DevBuf<uint32_t> d_row_order;
     mutable bool row_order_ready = false;
@@ -1483,7 +1484,7 @@ int dec_check_and_retry(DecodeCall &c) {
     const unsigned long long *sum = c.sum;
     const uint64_t *out_off_host = c.out_off_host;
     const double first_ms = ctx->last_kernel_ms;
-    uint64_t nonclean = sum[1];
+    uint64_t nonclean = sum[1], handed_back = 0;
     if (sum[0] != ~0ull || sum[2]) {
         // (a few handed-back lists and nothing else to report: their numbers came with the summary; otherwise the statuses are fetched)
         const bool listed = sum[0] == ~0ull && !out_off_host && !r->rows && sum[2] <= DEC_RETRY_SLOTS;
@@ -1514,6 +1515,7 @@ int dec_check_and_retry(DecodeCall &c) {
             plan_decode(r, lists2, false, p2, ctx->wide, false, false);
             std::vector<uint64_t> out_off2(lists2.size());
             for (size_t k = 0; k < lists2.size(); k++) out_off2[k] = off2[p2.item[k]];
+            handed_back = lists2.size();  // (sum[2] counts lists; an item per mention of a list that a request names twice)
             VIDC_TRY(decode_impl(ctx, r, p2, out_off2.data(), c.d_out, nullptr, 0));
             nonclean += r->last_nonclean;
             ctx->last_kernel_ms += first_ms;
@@ -1523,6 +1525,7 @@ int dec_check_and_retry(DecodeCall &c) {
         }
     }
     r->last_nonclean = nonclean;
+    r->last_handed_back = handed_back;  // (behind the nested decode of the handed-back lists, which stored its own 0)
     return VIDC_OK;
 }
 
@@ -1532,7 +1535,7 @@ int decode_impl(vidc_ctx *ctx, const vidc_roc *r, const DecPlan &p, const uint64
                 int32_t *d_out_rows, uint32_t K, const struct DecPlanCache *cache) {
     VIDC_HIP(hipSetDevice(ctx->device));
     const size_t nwork = p.implicit ? (size_t)p.implicit : p.wl.size();
-    if (nwork == 0) { ctx->last_kernel_ms = 0; return VIDC_OK; }
+    if (nwork == 0) { ctx->last_kernel_ms = 0; r->last_handed_back = 0; return VIDC_OK; }
     DecodeCall c(ctx, r, p, out_off_host, d_out, d_out_rows, K, cache, nwork);
     VIDC_TRY(dec_upload(c));
     (void)c.t.start();
@@ -1697,6 +1700,7 @@ uint64_t vidc_roc_ntotal(const vidc_roc *r) { return r ? r->ntotal : 0; }
 uint64_t vidc_roc_compressed_bytes(const vidc_roc *r) { return r ? r->compressed_bytes : 0; }
 uint64_t vidc_roc_total_words(const vidc_roc *r) { return r ? r->total_words : 0; }
 uint64_t vidc_roc_last_decode_nonclean(const vidc_roc *r) { return r ? r->last_nonclean : 0; }
+uint64_t vidc_roc_last_decode_handed_back(const vidc_roc *r) { return r ? r->last_handed_back : 0; }
 
 int vidc_roc_list_info(const vidc_roc *r, uint32_t *sizes, uint32_t *precisions, uint64_t *heads,
                        uint32_t *nwords, uint32_t *mt_draws) {
