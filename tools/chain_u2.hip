@@ -1,6 +1,8 @@
 // chain_u2.hip -- dev tool: one long list through k_roc_encode_u (round 1), k_roc_encode_u2 (round 2, bitmap body) and, for ub 20,
 // k_roc_encode_u2 with dense 16-id blocks: identical head / words / order, ns per step of each (hipEvents, five repeats: min and
-// max).   usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: the section table is that of the LAST arm run)
+// max); then the stream through k_roc_decode_u (round 1) and k_roc_decode_u2, five repeats each as well.
+// usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: section tables of the LAST encode arm run and of the k_roc_decode_u2 step;
+// -DU2_DEC_SHARED_STEP: k_roc_decode_u2 runs the step it shared with the bucket kernels, the 'before' of profiles/r21_roc_decode_step.txt)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I vector_db_id_compression_amd/csrc tools/chain_u2.hip -o /tmp/chain_u2
 #include <cstdio>
 #include <cstdlib>
@@ -97,20 +99,22 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
         b.words = d_arena; b.word_off = d_woff; b.out = d_out; b.out_rows = nullptr; b.K = 0; b.scratch_words = d_scr; b.scratch_off = d_z;
         b.slots = d_slots; b.slots_off = d_z; b.end_state = d_end; b.status = d_st; b.mt = d_mt;
         CK(hipFuncSetAttribute((const void *)k_roc_decode_u<UB>, hipFuncAttributeMaxDynamicSharedMemorySize, UGeom<UB>::LDS_BYTES));
-        CK(hipFuncSetAttribute((const void *)k_roc_decode_u2<UB>, hipFuncAttributeMaxDynamicSharedMemorySize, U2Geom<UB>::LDS_BYTES));
-        std::vector<uint64_t> outv[2]; float dms[2]; uint32_t dst[2], dend[2];
+        CK(hipFuncSetAttribute((const void *)k_roc_decode_u2<UB>, hipFuncAttributeMaxDynamicSharedMemorySize, U2Geom<UB>::DEC_LDS_BYTES));
+        std::vector<uint64_t> outv[2]; float dms[2], dms_max[2]; uint32_t dst[2], dend[2];
         for (int which = 0; which < 2; which++) {
-            for (int rep = 0; rep < 2; rep++) {
+            dms[which] = 1e30f; dms_max[which] = 0.f;
+            for (int rep = 0; rep < 6; rep++) {  // the first one warms up
                 CK(hipMemset(d_out, 0xee, (size_t)n * 8)); CK(hipMemset(d_st, 0xff, 4)); CK(hipMemset(d_end, 0xff, 4));
                 CK(hipEventRecord(e0, 0));
                 if (which == 0) hipLaunchKernelGGL((k_roc_decode_u<UB>), dim3(1), dim3(64), UGeom<UB>::LDS_BYTES, 0, b);
-                else hipLaunchKernelGGL((k_roc_decode_u2<UB>), dim3(1), dim3(64), U2Geom<UB>::LDS_BYTES, 0, b, (const U2Div *)d_tab);
+                else hipLaunchKernelGGL((k_roc_decode_u2<UB>), dim3(1), dim3(64), U2Geom<UB>::DEC_LDS_BYTES, 0, b, (const U2Div *)d_tab);
                 CK(hipEventRecord(e1, 0));
                 CK(hipDeviceSynchronize());
-                CK(hipEventElapsedTime(&dms[which], e0, e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+                if (rep) { dms[which] = std::min(dms[which], ms); dms_max[which] = std::max(dms_max[which], ms); }
             }
 #ifdef U2_PROF2
-            if (which == 1) { uint32_t dbg[4]; CK(hipMemcpy(dbg, d_slots, 16, hipMemcpyDeviceToHost)); printf("   decode dbg: slow steps %u, asm entries %u, bits %u, n %u\n", dbg[0], dbg[1], dbg[2], dbg[3]); }
+            if (which == 1) { uint32_t dbg[4]; CK(hipMemcpy(dbg, d_slots, 16, hipMemcpyDeviceToHost)); printf("   decode dbg: slow steps %u, asm entries %u, bits %u, n %u -> decoded again by the round-1 body: %s\n", dbg[0], dbg[1], dbg[2], dbg[3], dbg[2] == dbg[3] ? "no" : "YES"); }
 #endif
             outv[which].resize(n);
             CK(hipMemcpy(outv[which].data(), d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -121,6 +125,31 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
         dsame = dd == n && dst[0] == 0 && dst[1] == 0 && dend[0] == dend[1];
         printf("                         DECODE old %.1f ns/step, new %.1f ns/step; status %u/%u end state %u/%u first diff old/new at %zu, new/encoder order at %zu -> %s\n",
                dms[0] * 1e6 / n, dms[1] * 1e6 / n, dst[0], dst[1], dend[0], dend[1], dd, od, dsame ? "IDENTICAL" : "MISMATCH");
+        printf("    five repeats, ns/step min..max: old %.1f..%.1f, u2 %.1f..%.1f\n", dms[0] * 1e6 / n, dms_max[0] * 1e6 / n, dms[1] * 1e6 / n, dms_max[1] * 1e6 / n);
+#ifdef U2_PROF
+        {   // the decode step's sections (the last launch of k_roc_decode_u2 left them in the slots array)
+            uint32_t dp[14]; CK(hipMemcpy(dp, d_slots, 56, hipMemcpyDeviceToHost));
+#ifdef U2_DEC_SHARED_STEP
+            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, address, ds_read, g, dword (7)",
+                "MID: L1, L2, row read bracket (5)", "MID: bfm, address, bit, exec, ds_or, exec (6)", "MID: 3 readlanes, 4 valu of the counters (7)", "MID: m0, renormalise H, ring write (6)",
+                "MID: H * nmax, E1 + row (5)", "MID: row write-back bracket, m0 (4)", "RANK: waitcnt, 10 valu / 4 valu (11 / 5)", "RANK: s_nop, readlane (2)", "AFTER_RANK: ring write, E1 update (3)",
+                "BOT: counters, head', refill test (7) [+ cmp, branch]"};
+#else
+            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, address, ds_read, g, dword (7)",
+                "MID: L1, L2, row read bracket, bfm, m0 (7)", "MID: 3 readlanes, row update, ring write (7)", "MID: renormalise H (4)", "MID: H * nmax (4)",
+                "MID: row write-back bracket, m0 (4)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: address, bit, ring write, ds_or (4)", "(unused)",
+                "BOT: counters, head', refill test (6) [+ cmp, branch]"};
+#endif
+            double tot = 0, pc = (double)dp[1] / n;
+            int np = 0;  // probes the step has (a slot the step does not use stays 0)
+            printf("  k_roc_decode_u2 step, cycles per step (s_memtime; 'net' subtracts one probe):\n");
+            for (int q = 0; q < 14; q++) {
+                if (dp[q] == 0) continue;
+                printf("  %-62s %8.1f  net %7.1f\n", sn[q], (double)dp[q] / n, (double)dp[q] / n - pc); tot += dp[q]; np++;
+            }
+            printf("  total %.1f, net of %d probes %.1f cycles/step\n", tot / n, np, tot / n - np * pc);
+        }
+#endif
     }
     same = same && dsame;
 #ifdef U2_PROF2

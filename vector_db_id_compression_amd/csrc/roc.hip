@@ -1294,13 +1294,13 @@ int dec_launch_u(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // un
     const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
     if (cls == DC_U18) {
         if (old_u_kernels()) hipLaunchKernelGGL(k_roc_decode_u<18>, dim3(b.nwork), dim3(64), UGeom<18>::LDS_BYTES, st, b);
-        else hipLaunchKernelGGL(k_roc_decode_u2<18>, dim3(b.nwork), dim3(64), U2Geom<18>::LDS_BYTES, st, b, dt);
+        else hipLaunchKernelGGL(k_roc_decode_u2<18>, dim3(b.nwork), dim3(64), U2Geom<18>::DEC_LDS_BYTES, st, b, dt);
     } else if (old_u_kernels()) {
         VIDC_TRY(set_big_lds((const void *)k_roc_decode_u<20>, UGeom<20>::LDS_BYTES));
         hipLaunchKernelGGL(k_roc_decode_u<20>, dim3(b.nwork), dim3(64), UGeom<20>::LDS_BYTES, st, b);
     } else {
-        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20>, U2Geom<20>::LDS_BYTES));
-        hipLaunchKernelGGL(k_roc_decode_u2<20>, dim3(b.nwork), dim3(64), U2Geom<20>::LDS_BYTES, st, b, dt);
+        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20>, U2Geom<20>::DEC_LDS_BYTES));
+        hipLaunchKernelGGL(k_roc_decode_u2<20>, dim3(b.nwork), dim3(64), U2Geom<20>::DEC_LDS_BYTES, st, b, dt);
     }
     return VIDC_OK;
 }

@@ -42,6 +42,9 @@ struct U2Geom {
     static constexpr uint32_t NE = 4096u;                 // 64 blocks x 64 entries
     static constexpr uint32_t BITMAP_BYTES = NE * G * 8u;
     static constexpr uint32_t LDS_BYTES = BITMAP_BYTES + 16u;  // + a dummy word: target of the "no pending removal" store
+    // k_roc_decode_u2: + a strip of one dword per lane behind the bitmap.  The insertion is a ds_or by ALL lanes: lane 0 hits the
+    // bitmap, lane j > 0 its own dword of the strip (no exec write in the step, no two lanes on one address)
+    static constexpr uint32_t DEC_LDS_BYTES = BITMAP_BYTES + 256u;
 };
 
 // Dense 16-id blocks in POSITION space (k_roc_encode_u2<20> only, lists of 4097 .. 65 536 ids): block b holds the ids at positions
@@ -1113,12 +1116,23 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //
 // Register map (decode):
 //   v2 lane  v3 (lane & 3) * 8  v4 E1  v5 stack ring  v6:7 {output ring, 0}  v10 lq = floor(2^31 / nmax) per lane (nmax = N0 + lane)
+//   v8 v9 multiplier / addend of the insertion address (k_roc_decode_u2: lane 0 -> bitmap dword, lane j -> strip dword j)
 //   v13 row  v26 address / v27 bit of the insertion  v28 LDS address  v30:31 word(s)  v32..v37 popcount temporaries
 //   v54:57 table entry of the next block  v58 v59 tmp  v64..v127 level-2 rows
 //   s40 x  s43 L1  s44 L2  s45 entry  s46 x_hi  s47 g  s48 b  s49 E1[L1]  s50:51 H  s52:53 H * nmax  s58:59 head  s60 sp
 //   s61 lo  s62 lq  s63 row[L2]  s64 below  s65 tmp  s66:67 mask below b  s68 tmp  s69 t  s70 t_end  s71 limit  s72 tmp
 //   s73 2^p1 - 1  s74 2^p0 - 1  s75 nmax  s76 p0  s77 p1  s85 N0  s86 steps left at lane 0  s87 output index of lane 0
 //   s88:89 output pointer  s94:95 divisor table  s96:97 saved exec  s98 s99 tmp
+#ifdef U2_PROF  // the decode arm's probes (the encoder's U2P with registers the loop of k_roc_decode_u2 leaves alone: s78..s81; the
+                // bucket kernels, which share some of the probed macros, use those registers: k_roc_decode_b2 refuses a probed build)
+#define U2PD(i) "s_memtime s[78:79]\n s_waitcnt lgkmcnt(0)\n s_sub_u32 s81, s78, s80\n s_mov_b32 s80, s78\n v_add_u32 v" #i ", s81, v" #i "\n"
+#define U2PD_INIT "s_memtime s[78:79]\n s_waitcnt lgkmcnt(0)\n s_mov_b32 s80, s78\n"
+#define U2PD_CLOBBERS , "s78", "s79", "s80", "s81"
+#else
+#define U2PD(i) ""
+#define U2PD_INIT ""
+#define U2PD_CLOBBERS
+#endif
 #define U2_DEC_INSTALL \
     "v_mov_b32 v10, v57\n" \
     "s_add_u32 s68, s85, 64\n" \
@@ -1135,10 +1149,11 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     U2_DEC_INSTALL \
     "s_mov_b32 s69, 0\n" \
     "s_mov_b32 s75, s85\n" \
-    "s_min_u32 s70, s86, 64\n"
+    "s_min_u32 s70, s86, 64\n" U2PD_INIT
 
 #define U2_DEC_TOP "1:\n" U2_DEC_TOP_L("20", "21", "22", "23")
 #define U2_DEC_TOP_L(LA, LB, LC, LD)                   /* (labels of the two refill side paths and their returns) */ \
+    U2PD(130) U2PD(131) \
     "s_and_b32 s46, s58, s73\n"                        /* slice 1: x_hi (codec.cpp:78-90) */ \
     "s_lshr_b64 s[58:59], s[58:59], s77\n" \
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* (SCC = head >= 2^31: one instruction instead of shift + or, round 5) */ \
@@ -1149,7 +1164,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_lshr_b64 s[98:99], s[58:59], 31\n" \
     "s_cbranch_scc0 " LC "f\n" \
     LD ":\n" \
-    "s_pack_ll_b32_b16 s40, s40, s46\n"                /* x = x_hi : x_lo (one instruction, round 5) */
+    "s_pack_ll_b32_b16 s40, s40, s46\n"                /* x = x_hi : x_lo (one instruction, round 5) */ U2PD(132)
 #define U2_DEC_IDX_G4 \
     "s_lshr_b32 s45, s40, 8\n" \
     "s_xor_b32 s45, s45, 0xfff\n"                      /* entry (reversed) */ \
@@ -1157,53 +1172,53 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "ds_read_b64 v[30:31], v28\n" \
     "s_bfe_u32 s47, s40, 0x20006\n"                    /* g */ \
     "s_bfe_u32 s65, s40, 0x30005\n"                    /* 32-bit half of the entry holding x */ \
-    "s_lshl3_add_u32 s65, s45, s65\n"                  /* (dword of the bitmap; U2_DEC_MID shifts it to a byte address) */
+    "s_lshl3_add_u32 s65, s45, s65\n"                  /* (dword of the bitmap; U2_DEC_MID shifts it to a byte address) */ U2PD(133)
 #define U2_DEC_IDX_G1 \
     "s_lshr_b32 s45, s40, 6\n" \
     "s_xor_b32 s45, s45, 0xfff\n" \
     "v_lshlrev_b32_e64 v28, 3, s45\n" \
     "ds_read_b64 v[30:31], v28\n" \
     "s_bfe_u32 s65, s40, 0x10005\n" \
-    "s_lshl1_add_u32 s65, s45, s65\n"
+    "s_lshl1_add_u32 s65, s45, s65\n" U2PD(133)
 #define U2_DEC_MID \
     "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
     "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
     "v_mov_b32 v13, v64\n" \
-    "s_set_gpr_idx_off\n" \
+    "s_set_gpr_idx_off\n" U2PD(134) \
     "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */ \
     "v_lshlrev_b32_e64 v26, 2, s65\n"                  /* insertion of x: after the read in LDS order */ \
     "v_lshlrev_b32_e64 v27, s40, 1\n" \
     "s_mov_b64 exec, 1\n" \
     "ds_or_b32 v26, v27\n" \
-    "s_mov_b64 exec, -1\n" \
+    "s_mov_b64 exec, -1\n" U2PD(135) \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
     "v_readlane_b32 s63, v13, s44\n"                   /* row[L2] */ \
     "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
     "v_subrev_u32 v58, s43, v2\n" \
     "v_subrev_u32 v59, s44, v2\n" \
     "v_ashrrev_i32 v59, 31, v59\n" \
-    "v_sub_u32 v13, v13, v59\n"                        /* row += 1 in lanes below L2 */ \
+    "v_sub_u32 v13, v13, v59\n"                        /* row += 1 in lanes below L2 */ U2PD(136) \
     "s_and_b32 m0, s60, 63\n"                          /* index push, first half (codec.cpp:44-63): renormalise H */ \
     "s_cmp_ge_u32 s59, s62\n" \
     "v_writelane_b32 v5, s58, m0\n" \
     "s_cselect_b32 s50, s59, s58\n" \
     "s_cselect_b32 s51, 0, s59\n" \
-    "s_addc_u32 s60, s60, 0\n" \
+    "s_addc_u32 s60, s60, 0\n" U2PD(137) \
     "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
     "s_mul_hi_u32 s53, s50, s75\n" \
     "s_mul_i32 s68, s51, s75\n" \
     "s_add_u32 s53, s53, s68\n" \
-    "s_add_u32 s72, s49, s63\n" \
+    "s_add_u32 s72, s49, s63\n" U2PD(138) \
     "s_set_gpr_idx_on s43, gpr_idx(DST)\n" \
     "v_mov_b32 v64, v13\n" \
     "s_set_gpr_idx_off\n" \
-    "s_mov_b32 m0, s69\n"
+    "s_mov_b32 m0, s69\n" U2PD(139)
 // (the three vector instructions that follow the last readlane of the rank keep the scalar tail off its SGPR write)
 #define U2_DEC_AFTER_RANK \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
     "v_ashrrev_i32 v58, 31, v58\n" \
-    "v_sub_u32 v4, v4, v58\n"                          /* E1 += 1 in lanes below L1 */
+    "v_sub_u32 v4, v4, v58\n"                          /* E1 += 1 in lanes below L1 */ U2PD(142)
 #define U2_DEC_RANK_G4 \
     "s_waitcnt lgkmcnt(1)\n" \
     "v_bcnt_u32_b32 v32, v30, 0\n" \
@@ -1215,19 +1230,125 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_bcnt_u32_b32 v33, v34, v33\n"                   /* ... below b */ \
     "v_add_u32_dpp v36, v35, v35 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
     "v_sub_u32 v33, v33, v32\n" \
-    "v_add_u32 v37, v36, v33\n"                        /* lane g: bits of the entry below x */ \
+    "v_add_u32 v37, v36, v33\n"                        /* lane g: bits of the entry below x */ U2PD(140) \
     "s_nop 0\n" \
-    "v_readlane_b32 s64, v37, s47\n" \
+    "v_readlane_b32 s64, v37, s47\n" U2PD(141) \
     U2_DEC_AFTER_RANK
 #define U2_DEC_RANK_G1 \
     "s_waitcnt lgkmcnt(1)\n" \
     "v_and_b32 v33, s66, v30\n" \
     "v_and_b32 v34, s67, v31\n" \
     "v_bcnt_u32_b32 v33, v33, 0\n" \
-    "v_bcnt_u32_b32 v37, v34, v33\n" \
+    "v_bcnt_u32_b32 v37, v34, v33\n" U2PD(140) \
     "s_nop 0\n" \
-    "v_readfirstlane_b32 s64, v37\n" \
+    "v_readfirstlane_b32 s64, v37\n" U2PD(141) \
     U2_DEC_AFTER_RANK
+// ---- the step of k_roc_decode_u2 (the bucket kernels keep U2_DEC_MID / U2_DEC_RANK_* / U2_DEC_BOT_CORE* above; U2_DEC_TOP_L, the
+// index macros, U2_DEC_SIDE and U2_DEC_OUTER are shared).  Same data flow, 68 instructions instead of 74 with four words per entry
+// (62 instead of 67 with one), and ordered by the rule the encoder's dense step was built on: a scalar instruction issued within
+// ~16 cycles of a vector instruction that wrote an SGPR or VCC (v_readlane, v_cmp, v_addc) waits the window out, so each of the
+// two read-outs whose results the scalar unit needs is followed by four vector / LDS instructions (profiles/r21_roc_decode_step.txt
+// has the section tables and what each change bought).
+//  * insertion: a ds_or by all 64 lanes, exec untouched (the two exec writes cost 8 cycles more than their issue slots).  v8 / v9
+//    are per-lane constants (lane 0: v8 = 4, v9 = 0; lane j: v8 = 0, v9 = BITMAP_BYTES + 4 j): one v_mad_u32_u24 sends lane 0 to the
+//    bitmap dword and every other lane to its own dword of the strip behind the bitmap (U2Geom::DEC_LDS_BYTES).  Address, bit and the
+//    ds_or sit BEHIND the rank's read-out, so the wait in front of the rank is lgkmcnt(0): the read of this step and the insertion of
+//    the previous one (LDS operations of a wavefront complete in order, the next read sees the bit).
+//  * rank: E1[L1] rides in on the addend of a v_bcnt and row[L2] on a v_add3, so the read-out is the whole rank and head' is one
+//    64-bit add (the two scalar adds are gone).
+//  * counters: the E1 update is v_cmp_gt (L1 > lane) + v_addc_co (+ 0 + carry) inside the rank's vector block, where vector work
+//    follows both; the v_addc takes the wait state in front of the read-out (s_nop 0 before).  The row keeps the three-instruction
+//    form: it writes no SGPR and fills the window of the three read-outs of U2_DEC_MID_U (as v_cmp + v_addc there the step was
+//    0.6 ns longer with four words per entry and 4.3 ns longer with one).
+#define U2_DEC_MID_U \
+    "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
+    "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
+    "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
+    "v_mov_b32 v13, v64\n" \
+    "s_set_gpr_idx_off\n" \
+    "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */ \
+    "s_and_b32 m0, s60, 63\n" U2PD(134) \
+    "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
+    "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
+    "v_readlane_b32 s63, v13, s44\n"                   /* row[L2] */ \
+    "v_subrev_u32 v59, s44, v2\n" \
+    "v_ashrrev_i32 v59, 31, v59\n" \
+    "v_sub_u32 v13, v13, v59\n"                        /* row += 1 in lanes below L2 */ \
+    "v_writelane_b32 v5, s58, m0\n"                    /* index push, first half (codec.cpp:44-63): the word, kept if H renormalises */ U2PD(135) \
+    "s_cmp_ge_u32 s59, s62\n" \
+    "s_cselect_b32 s50, s59, s58\n" \
+    "s_cselect_b32 s51, 0, s59\n" \
+    "s_addc_u32 s60, s60, 0\n" U2PD(136) \
+    "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
+    "s_mul_hi_u32 s53, s50, s75\n" \
+    "s_mul_i32 s68, s51, s75\n" \
+    "s_add_u32 s53, s53, s68\n" U2PD(137) \
+    "s_set_gpr_idx_on s43, gpr_idx(DST)\n" \
+    "v_mov_b32 v64, v13\n" \
+    "s_set_gpr_idx_off\n" \
+    "s_mov_b32 m0, s69\n" U2PD(138)
+#define U2_DEC_RANK_TAIL_U \
+    "v_mad_u32_u24 v26, s65, v8, v9\n"                 /* insertion address: lane 0 the bitmap dword, lane j its strip dword */ \
+    "v_lshlrev_b32_e64 v27, s40, 1\n" \
+    "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
+    "ds_or_b32 v26, v27\n"                             /* insertion of x */ U2PD(141)
+#define U2_DEC_RANK_U_G4 \
+    "s_waitcnt lgkmcnt(0)\n" \
+    "v_bcnt_u32_b32 v32, v30, 0\n" \
+    "v_bcnt_u32_b32 v32, v31, v32\n"                   /* set bits of the lane's word */ \
+    "v_and_b32 v33, s66, v30\n" \
+    "v_and_b32 v34, s67, v31\n" \
+    "v_add_u32_dpp v35, v32, v32 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
+    "v_bcnt_u32_b32 v33, v33, s49\n"                   /* E1[L1] + ... */ \
+    "v_bcnt_u32_b32 v33, v34, v33\n"                   /* ... the bits below b */ \
+    "v_add_u32_dpp v36, v35, v35 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
+    "v_sub_u32 v33, v33, v32\n" \
+    "v_cmp_gt_u32 vcc, s43, v2\n" \
+    "v_add3_u32 v37, v36, v33, s63\n"                  /* lane g: the rank of x */ U2PD(139) \
+    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes below L1 */ \
+    "v_readlane_b32 s64, v37, s47\n" U2PD(140) \
+    U2_DEC_RANK_TAIL_U
+#define U2_DEC_RANK_U_G1 \
+    "s_waitcnt lgkmcnt(0)\n" \
+    "v_and_b32 v33, s66, v30\n" \
+    "v_and_b32 v34, s67, v31\n" \
+    "v_bcnt_u32_b32 v33, v33, s49\n" \
+    "v_bcnt_u32_b32 v33, v34, v33\n" \
+    "v_cmp_gt_u32 vcc, s43, v2\n" \
+    "v_add_u32 v37, s63, v33\n" U2PD(139) \
+    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n" \
+    "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
+    U2_DEC_RANK_TAIL_U
+#define U2_DEC_BOT_T_U(RLO, RSPAN)                     /* (U2_DEC_BOT_CORE_T with the rank in one register) */ \
+    "s_sub_u32 s68, s60, s61\n"                        /* ring: two pops and one push must fit the next step */ \
+    "s_add_u32 s68, s68, " RLO "\n" \
+    "s_add_u32 s69, s69, 1\n" \
+    "s_add_u32 s75, s75, 1\n" \
+    "s_add_u32 s58, s52, s64\n"                        /* head' = H * nmax + rank */ \
+    "s_addc_u32 s59, s53, 0\n" \
+    "s_cmp_gt_u32 s68, " RSPAN "\n" \
+    "s_cselect_b32 s71, 0, s70\n" \
+    "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
+    "s_cselect_b32 s71, s71, 0\n" U2PD(143) \
+    "s_cmp_lt_u32 s69, s71\n"
+#define U2_DEC_BOT_NR_U \
+    "s_add_u32 s69, s69, 1\n" \
+    "s_add_u32 s75, s75, 1\n" \
+    "s_add_u32 s58, s52, s64\n"                        /* head' = H * nmax + rank */ \
+    "s_addc_u32 s59, s53, 0\n" \
+    "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
+    "s_cselect_b32 s71, s70, 0\n" U2PD(143) \
+    "s_cmp_lt_u32 s69, s71\n"
+#define U2_DEC_STEP_U(IDX, RANK, LA, LB, LC, LD) U2_DEC_TOP_L(LA, LB, LC, LD) IDX U2_DEC_MID_U RANK U2_DEC_BOT_NR_U "s_cbranch_scc0 2f\n"
+#define U2_DEC_LOOP8_U(IDX, RANK) \
+    "1:\n" U2_DEC_STEP_U(IDX, RANK, "20", "21", "22", "23") U2_DEC_STEP_U(IDX, RANK, "30", "31", "32", "33") \
+    U2_DEC_STEP_U(IDX, RANK, "40", "41", "42", "43") U2_DEC_STEP_U(IDX, RANK, "50", "51", "52", "53") \
+    U2_DEC_STEP_U(IDX, RANK, "60", "61", "62", "63") U2_DEC_STEP_U(IDX, RANK, "70", "71", "72", "73") \
+    U2_DEC_STEP_U(IDX, RANK, "80", "81", "82", "83") \
+    U2_DEC_TOP_L("90", "91", "92", "93") IDX U2_DEC_MID_U RANK U2_DEC_BOT_T_U("-18", "35") "s_cbranch_scc1 1b\n s_branch 2f\n" \
+    U2_DEC_SIDE("20", "21", "22", "23") U2_DEC_SIDE("30", "31", "32", "33") U2_DEC_SIDE("40", "41", "42", "43") \
+    U2_DEC_SIDE("50", "51", "52", "53") U2_DEC_SIDE("60", "61", "62", "63") U2_DEC_SIDE("70", "71", "72", "73") \
+    U2_DEC_SIDE("80", "81", "82", "83") U2_DEC_SIDE("90", "91", "92", "93") "2:\n"
 #define U2_DEC_BOT U2_DEC_BOT_CORE "s_cbranch_scc1 1b\n s_branch 2f\n" U2_DEC_SIDE("20", "21", "22", "23") "2:\n"
 #define U2_DEC_BOT_CORE U2_DEC_BOT_CORE_T("-2", "59")
 #define U2_DEC_BOT_CORE_T(RLO, RSPAN)                  /* the next step may run while RLO <= words in the ring <= RLO + RSPAN */ \
@@ -1241,7 +1362,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_cmp_gt_u32 s68, " RSPAN "\n" \
     "s_cselect_b32 s71, 0, s70\n" \
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
-    "s_cselect_b32 s71, s71, 0\n" \
+    "s_cselect_b32 s71, s71, 0\n" U2PD(143) \
     "s_cmp_lt_u32 s69, s71\n"
 // the same without the ring test: copies of the loop body whose ring state the last copy (or the entry) has vouched for
 #define U2_DEC_BOT_CORE_NR \
@@ -1251,7 +1372,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_add_u32 s58, s52, s72\n"                        /* head' = H * nmax + rank */ \
     "s_addc_u32 s59, s53, 0\n" \
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
-    "s_cselect_b32 s71, s70, 0\n" \
+    "s_cselect_b32 s71, s70, 0\n" U2PD(143) \
     "s_cmp_lt_u32 s69, s71\n"
 // Ring of the eight-copy loop: a step pops at most two words and pushes at most one, so eight steps are safe while the ring
 // holds U2_DEC_RING_LO .. U2_DEC_RING_HI words when the first copy starts (18 - 16 = 2 words left for the last pops, 53 + 8 = 61
@@ -1373,7 +1494,7 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
     const uint64_t ooff = rfl64(a.out_off ? a.out_off[wi] : a.offsets[l]);
     {
         uint4 *z = (uint4 *)smem;
-        for (uint32_t w = lane; w < U::LDS_BYTES / 16u; w += 64) z[w] = make_uint4(0, 0, 0, 0);
+        for (uint32_t w = lane; w < U::DEC_LDS_BYTES / 16u; w += 64) z[w] = make_uint4(0, 0, 0, 0);
     }
     const uint32_t P = rfl(a.prec[l]);
     const uint32_t p0 = P < 16u ? P : 16u, p1 = P > 16u ? (P - 16u > 16u ? 16u : P - 16u) : 0u;
@@ -1388,9 +1509,13 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
 #pragma unroll
     for (int c = 0; c < 32; c++) { ra[c] = 0u; rb[c] = 0u; }
     const uint32_t l3off = U::G == 4u ? (lane & 3u) * 8u : 0u;
+    const uint32_t ins_mul = lane == 0u ? 4u : 0u, ins_add = lane == 0u ? 0u : U::BITMAP_BYTES + 4u * lane;  // U2_DEC_MID_U
     const uint32_t M1 = (1u << p1) - 1u, M0 = (1u << p0) - 1u;
     uint64_t *out = a.out + ooff;
     wave_sync();
+#ifdef U2_PROF
+    uint32_t prof[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
 
 #ifdef U2_PROF2
     uint32_t dbg[4] = {0, 0, 0, 0};
@@ -1423,14 +1548,20 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
         asm volatile(BODY                                                                                                 \
             : "+{v4}"(E1), "+{v5}"(st.win), "+{v[6:7]}"(oring), "+{v[64:95]}"(ra), "+{v[96:127]}"(rb),                     \
               "+{s[58:59]}"(s_h), "+{s60}"(st.sp), "+{s69}"(s_t), "+{s85}"(s_N0), "+{s86}"(s_left), "+{s87}"(s_oidx)        \
-            : "{v2}"(lane), "{v3}"(l3off), "{s61}"(st.lo), "{s73}"(M1), "{s74}"(M0), "{s76}"(p0), "{s77}"(p1),               \
-              "{s[88:89]}"(out), "{s[94:95]}"(dtab)                                                                        \
+              U2P_OPERANDS                                                                                                 \
+            : "{v2}"(lane), "{v3}"(l3off), "{v8}"(ins_mul), "{v9}"(ins_add), "{s61}"(st.lo), "{s73}"(M1), "{s74}"(M0),      \
+              "{s76}"(p0), "{s77}"(p1), "{s[88:89]}"(out), "{s[94:95]}"(dtab)                                              \
             : "memory", "vcc", "scc", "v10", "v13", "v26", "v27", "v28", "v30", "v31", "v32", "v33", "v34", "v35", "v36",     \
               "v37", "v54", "v55", "v56", "v57", "v58", "v59", "s40", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",\
               "s51", "s52", "s53", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", "s97",\
-              "s98", "s99")
+              "s98", "s99" U2PD_CLOBBERS)
+#if defined(U2_DEC_SHARED_STEP)  // dev (tools/chain_u2.hip): the step the bucket kernels run, for the 'before' rows of a section table
         if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8(U2_DEC_IDX_G4, U2_DEC_MID, U2_DEC_RANK_G4) U2_DEC_OUTER_T("-18", "35"));
         else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8(U2_DEC_IDX_G1, U2_DEC_MID, U2_DEC_RANK_G1) U2_DEC_OUTER_T("-18", "35"));
+#else
+        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
+        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
+#endif
 #undef U2_DEC_ASM
         // clang-format on
         head = s_h;
@@ -1448,6 +1579,10 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
     for (int o = 32; o > 0; o >>= 1) bits += (uint32_t)__shfl_xor((int)bits, o, 64);
 #ifdef U2_PROF2
     if (lane == 0) { a.slots[0] = dbg[0]; a.slots[1] = dbg[1]; a.slots[2] = rfl(bits); a.slots[3] = n; }
+#endif
+#ifdef U2_PROF
+    if (lane == 0)
+        for (int q = 0; q < 14; q++) a.slots[q] = prof[q];
 #endif
     if (rfl(bits) != n) {
         wave_sync();
@@ -1822,6 +1957,9 @@ __device__ __forceinline__ void roc_decode_b2_body(RocDecArgs a, const U2Div *__
 }
 template <int BK, int MODE = 0>
 __global__ void __launch_bounds__(64) k_roc_decode_b2(RocDecArgs a, const U2Div *__restrict__ dtab) {
+#ifdef U2_PROF  // the U2PD probes inside the shared macros are wired into k_roc_decode_u2 alone (its clobbers and operands)
+    static_assert(BK != BK, "-DU2_PROF: the probes use s78..s81 and v130..v143, which the bucket kernels use themselves");
+#endif
     roc_decode_b2_body<BK, MODE>(a, dtab);
 }
 
