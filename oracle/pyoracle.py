@@ -39,6 +39,14 @@ class _AnsState(C.Structure):
     ]
 
 
+class _StackStats(C.Structure):
+    _fields_ = [(name, C.c_size_t) for name in ("peak", "min_sp", "max_above_min", "max_pop_run", "pop_run", "pushes", "pops")]
+
+    def as_dict(self):
+        return dict(peak=int(self.peak), min_sp=int(self.min_sp), depth=int(self.max_above_min), pop_run=int(self.max_pop_run),
+                    pushes=int(self.pushes), pops=int(self.pops))
+
+
 class _Ef(C.Structure):
     _fields_ = [
         ("universe", C.c_uint64),
@@ -64,6 +72,8 @@ class Oracle:
         L.vo_ans_free.argtypes = [C.POINTER(_AnsState)]
         L.vo_roc_encode.argtypes = [C.c_size_t, _u64p, C.c_int, C.POINTER(_AnsState), _u64p, _u32p]
         L.vo_roc_decode.argtypes = [C.POINTER(_AnsState), C.c_size_t, C.c_int, _u64p]
+        L.vo_roc_encode_stats.argtypes = L.vo_roc_encode.argtypes + [C.POINTER(_StackStats)]
+        L.vo_roc_decode_stats.argtypes = L.vo_roc_decode.argtypes + [C.POINTER(_StackStats)]
         L.vo_packed_bits_for.argtypes = [C.c_uint64]
         L.vo_packed_bits_for.restype = C.c_int
         L.vo_packed_write.argtypes = [_u8p, C.c_size_t, C.c_uint64, C.c_int]
@@ -100,22 +110,35 @@ class Oracle:
         return self.precision(int(ids.max()))
 
     # -- ROC
-    def roc_encode(self, ids, precision):
-        """-> dict(head, words, order, perm, mt_draws)."""
+    def roc_encode(self, ids, precision, stats=False):
+        """-> dict(head, words, order, perm, mt_draws); stats=True adds `stack`: dict(peak, min_sp, depth, pop_run, pushes, pops),
+        the shape of the word stack during the encode (vo_stack_stats)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint64)
         n = ids.size
         st = _AnsState()
         self.lib.vo_ans_init(C.byref(st))
         order = np.zeros(max(n, 1), dtype=np.uint64)
         perm = np.zeros(max(n, 1), dtype=np.uint32)
-        self.lib.vo_roc_encode(n, ids if n else np.zeros(1, np.uint64), precision, C.byref(st), order, perm)
+        ss = _StackStats()
+        if stats:
+            self.lib.vo_roc_encode_stats(n, ids if n else np.zeros(1, np.uint64), precision, C.byref(st), order, perm, C.byref(ss))
+        else:
+            self.lib.vo_roc_encode(n, ids if n else np.zeros(1, np.uint64), precision, C.byref(st), order, perm)
         words = np.ctypeslib.as_array(st.stack, shape=(st.nstack,)).copy() if st.nstack else np.zeros(0, np.uint32)
         res = dict(head=int(st.head), words=words.astype(np.uint32), order=order[:n], perm=perm[:n],
                    mt_draws=int(st.mt_draws))
+        if stats:
+            res["stack"] = ss.as_dict()
         self.lib.vo_ans_free(C.byref(st))
         return res
 
-    def roc_decode(self, head, words, n, precision, mt_draws=0):
+    def roc_decode_stats(self, head, words, n, precision, mt_draws=0):
+        """roc_decode plus the shape of the word stack during the decode -> (..., dict(peak, min_sp, depth, pop_run, pushes, pops)):
+        peak = the largest stack in words, depth = the most words that ever stood above the running minimum of the stack size (the
+        decoder's own pushes that it holds at once)."""
+        return self.roc_decode(head, words, n, precision, mt_draws, stats=True)
+
+    def roc_decode(self, head, words, n, precision, mt_draws=0, stats=False):
         """-> (decoded ids in sampling order, end_head, end_words, end_mt_draws)."""
         words = np.ascontiguousarray(words, dtype=np.uint32)
         st = _AnsState()
@@ -133,9 +156,15 @@ class Oracle:
         st.cap = cap
         st.mt_draws = mt_draws
         out = np.zeros(max(n, 1), dtype=np.uint64)
-        self.lib.vo_roc_decode(C.byref(st), n, precision, out)
+        ss = _StackStats()
+        if stats:
+            self.lib.vo_roc_decode_stats(C.byref(st), n, precision, out, C.byref(ss))
+        else:
+            self.lib.vo_roc_decode(C.byref(st), n, precision, out)
         end_words = np.ctypeslib.as_array(st.stack, shape=(st.nstack,)).copy() if st.nstack else np.zeros(0, np.uint32)
         res = (out[:n], int(st.head), end_words.astype(np.uint32), int(st.mt_draws))
+        if stats:
+            res += (ss.as_dict(),)
         self.lib.vo_ans_free(C.byref(st))
         del buf
         return res

@@ -81,15 +81,33 @@ void vo_ans_copy(vo_ans_state *dst, const vo_ans_state *src) {
     dst->stack = (uint32_t *)malloc(dst->cap * sizeof(uint32_t));
     if (src->nstack) memcpy(dst->stack, src->stack, src->nstack * sizeof(uint32_t));
 }
+/* the shape of the stack during one vo_roc_encode_stats / vo_roc_decode_stats call (NULL: not recorded) */
+static _Thread_local vo_stack_stats *vo_stats;
 static void pushw(vo_ans_state *st, uint64_t w) { /* codec.h:20-22 */
     if (st->nstack == st->cap) {
         st->cap = st->cap ? st->cap * 2 : 64;
         st->stack = (uint32_t *)realloc(st->stack, st->cap * sizeof(uint32_t));
     }
     st->stack[st->nstack++] = (uint32_t)(w & 0xffffffffu);
+    if (vo_stats) {
+        vo_stack_stats *s = vo_stats;
+        s->pushes++;
+        s->pop_run = 0;
+        if (st->nstack > s->peak) s->peak = st->nstack;
+        if (st->nstack - s->min_sp > s->max_above_min) s->max_above_min = st->nstack - s->min_sp;
+    }
 }
 static uint64_t popw(vo_ans_state *st) { /* codec.h:32-40 */
-    if (st->nstack) return st->stack[--st->nstack];
+    if (st->nstack) {
+        --st->nstack;
+        if (vo_stats) {
+            vo_stack_stats *s = vo_stats;
+            s->pops++;
+            if (st->nstack < s->min_sp) s->min_sp = st->nstack;
+            if (++s->pop_run > s->max_pop_run) s->max_pop_run = s->pop_run;
+        }
+        return st->stack[st->nstack];
+    }
     uint32_t tab[64];
     /* draws are rare (0 or 1 per list): regenerate the prefix of the sequence */
     size_t need = (size_t)st->mt_draws + 1;
@@ -273,6 +291,24 @@ void vo_roc_decode(vo_ans_state *st, size_t n, int precision, uint64_t *out) {
         out[n - 1 - i] = x;
     }
     free(t);
+}
+
+/* The same calls with the shape of the word stack recorded (vidc_oracle.h: vo_stack_stats). */
+static void stats_begin(vo_stack_stats *s, const vo_ans_state *st) {
+    memset(s, 0, sizeof(*s));
+    s->peak = s->min_sp = st->nstack;
+    vo_stats = s;
+}
+void vo_roc_encode_stats(size_t n, const uint64_t *ids, int precision, vo_ans_state *st,
+                         uint64_t *order_out, uint32_t *perm_out, vo_stack_stats *stats) {
+    stats_begin(stats, st);
+    vo_roc_encode(n, ids, precision, st, order_out, perm_out);
+    vo_stats = NULL;
+}
+void vo_roc_decode_stats(vo_ans_state *st, size_t n, int precision, uint64_t *out, vo_stack_stats *stats) {
+    stats_begin(stats, st);
+    vo_roc_decode(st, n, precision, out);
+    vo_stats = NULL;
 }
 
 /* ------------------------------------------------------------ packed bits */

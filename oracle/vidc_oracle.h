@@ -59,6 +59,22 @@ void vo_roc_encode(size_t n, const uint64_t *ids, int precision, vo_ans_state *s
 /* ROC decode (codec.cpp:140-152); st is consumed (copy first if needed). */
 void vo_roc_decode(vo_ans_state *st, size_t n, int precision, uint64_t *out);
 
+/* The shape of the word stack during one encode or decode (test planning: which lists reach a kernel's cold stack paths).
+ * A pop from the empty stack (an mt19937 draw, counted in vo_ans_state.mt_draws) moves nothing and ends no run. */
+typedef struct {
+    size_t peak;          /* largest stack size in words, the size at the start included */
+    size_t min_sp;        /* smallest stack size */
+    size_t max_above_min; /* most words that ever stood above the running minimum of the stack size: the words a decoder holds that
+                             are its own pushes, not the stored stream */
+    size_t max_pop_run;   /* longest run of pops from a non-empty stack with no push in between: pops past the freshest pushes,
+                             served from the words stored earlier */
+    size_t pop_run;       /* (the run in progress) */
+    size_t pushes, pops;  /* words pushed / popped from a non-empty stack */
+} vo_stack_stats;
+void vo_roc_encode_stats(size_t n, const uint64_t *ids, int precision, vo_ans_state *st,
+                         uint64_t *order_out, uint32_t *perm_out, vo_stack_stats *stats);
+void vo_roc_decode_stats(vo_ans_state *st, size_t n, int precision, uint64_t *out, vo_stack_stats *stats);
+
 /* ---- packed bits (custom_invlists_impl.cpp:35-58,64-113; altid_impl.cpp:20-51) ---- */
 int vo_packed_bits_for(uint64_t ntotal);                              /* :68-70 */
 void vo_packed_write(uint8_t *code, size_t bit_offset, uint64_t x, int nbit);
