@@ -327,7 +327,7 @@ def family(name, seed=0):
 
 
 # --------------------------------------------------------------------------------------------------------------------- objects
-# The encoder picks its kernel per OBJECT (csrc/ef.hip, ef_encode_fast), so the families are dealt into objects by list length:
+# The encoder picks its kernel per OBJECT (csrc/ef_plan.h, ef_chunk_form), so the families are dealt into objects by list length:
 OBJECTS = ("short", "half", "full_q", "full_runs", "full_seams", "full_big")
 ROUTES = ("host", "dev", "wide", "unsorted")
 NARROW = 1 << 32
@@ -399,8 +399,9 @@ def object_lists(name, route, seed=0):
 
 
 def encoder_form(lists):
-    """which chunk kernel the single-pass encoder runs for an object of these lists (ef_encode_fast; the device-offset route takes
-    the k_ef_lowhigh32_dev form of the same name): 'general' (some list not ascending: the three-pass path for the whole object),
+    """which chunk kernel the single-pass encoder runs for an object of these lists (csrc/ef_plan.h: ef_chunk_form, and
+    tests/test_ef_plan_cpu.py holds this restatement against it; the device-offset route takes the k_ef_lowhigh32_dev form of
+    the same name): 'general' (some list not ascending: the three-pass path for the whole object),
     'wide' (some id of 2^32 or more: k_ef_lowhigh), 'short' (no list above 256 ids: k_ef_lowhigh32<4, SMALL>), 'half' (ntotal <
     256 * nchunks: <8, SMALL>), 'full' (<8>)"""
     ne = [u64(li) for li in lists if len(li)]

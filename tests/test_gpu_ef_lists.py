@@ -12,8 +12,8 @@ the boundary it is named after; the case distinctions of csrc/ef.hip map to fami
   four lanes x four words of k_ef_translate_g16               batch_seams, chunk_seams, runs      translate_labels at every position
 
 The encoder picks its chunk kernel per OBJECT, so the families are dealt into objects by list length (lists_ref.base_lists), and every
-object is encoded along four routes (lists_ref.object_lists); lists_ref.encoder_form restates the host's choice and the CPU file
-asserts this table from it:
+object is encoded along four routes (lists_ref.object_lists); lists_ref.encoder_form restates the host's choice (csrc/ef_plan.h: ef_chunk_form;
+tests/test_ef_plan_cpu.py asserts that the two agree on every object) and the CPU file asserts this table from it:
 
   object      route      encoder                                              bulk decoder (decode_all)
   short       host       k_ef_lowhigh32<4, SMALL>   (no list above 256 ids)   k_ef_decode_rec<uint32_t, 4>

@@ -421,3 +421,81 @@ def test_elias_fano_decode_lists_shares_long_lists_between_workgroups():
         assert int(goff[-1]) == int(sizes[req].sum())
         for k, l in enumerate(req):
             assert np.array_equal(got[int(goff[k]):int(goff[k + 1])], ids[int(off[l]):int(off[l + 1])]), (req, k)
+
+
+# ---- the encoder's driver (csrc/ef.hip, ef_encode_lists): attempt, re-run without speculation, three-pass fallback -- and the one
+# function that puts the object back between them (ef_enc_put_back).  Five lists of 0, 1, 3, 257 and 600 ids on a context of their
+# own (its universe hint starts at 0: the first attempt sizes the streams for ids up to ntotal - 1 = 860).
+_DRIVER_SIZES = (0, 1, 3, 257, 600)
+
+
+def _driver_lists(case):
+    """a  ids up to 2^31, ascending: the speculative streams are too small, the re-run finishes the object
+       b  as a, the 257-id list not ascending: re-run, then the three-pass encoder, in one call
+       c  ids below 2^20, one id of 2^32 or more, the 257-id list not ascending: the wide verdict, re-run, three-pass encoder
+       d  as b under VIDC_EF_LAZY_RECS=1"""
+    rng = np.random.default_rng(2323)
+    top = (1 << 20) if case == "c" else (1 << 31)
+    lists = []
+    for n in _DRIVER_SIZES:
+        li = np.cumsum(rng.integers(1, top // (n + 1), size=n)).astype(np.uint64)  # strictly ascending, below top
+        if n:
+            li[-1] = top
+        lists.append(li)
+    if case == "c":
+        lists[4][-1] = (1 << 32) + 5
+    if case != "a":
+        lists[3] = rng.permutation(lists[3])
+        assert np.any(lists[3][1:] < lists[3][:-1])
+    return lists
+
+
+def _check_driver_object(ef, lists, off):
+    """every word of every list against the numpy model, decode_all twice, perm -> the exported words"""
+    import lists_ref as lr
+
+    want = [np.sort(li) for li in lists]
+    info = ef.info()
+    assert np.array_equal(info["sizes"], [li.size for li in lists])
+    assert ef.compressed_bytes == lr.ef_sizes(want)["compressed_bytes"]
+    words = []
+    for l, li in enumerate(want):
+        low, high, lb, hb = ef.export(l)
+        words.append((low, high))
+        if li.size == 0:
+            assert (lb, hb, low.size, high.size) == (0, 0, 0, 0)
+            continue
+        m = lr.ef_list(li)
+        assert (int(info["low_bits"][l]), int(info["universe"][l]), lb, hb) == (m.l, m.u, m.low_nbits, m.high_nbits), l
+        assert np.array_equal(low, m.low) and np.array_equal(high, m.high), l
+    flat = np.concatenate(want)
+    for _ in range(2):  # (the second call finds the records of the first)
+        assert np.array_equal(ef.decode_all().cpu().numpy().view(np.uint64), flat)
+    perm = ef.perm()
+    for l, li in enumerate(lists):
+        a, b = int(off[l]), int(off[l + 1])
+        assert np.array_equal(li[perm[a:b]], want[l]), l
+    return words
+
+
+@pytest.mark.parametrize("offsets", ["host", "dev"])
+@pytest.mark.parametrize("case", ["a", "b", "c", "d"])
+def test_elias_fano_encoder_reruns_and_falls_back_in_one_call(monkeypatch, case, offsets):
+    import torch
+    from vector_db_id_compression_amd import _lib
+    from vector_db_id_compression_amd.codecs import EfLists
+
+    if case == "d":
+        monkeypatch.setenv("VIDC_EF_LAZY_RECS", "1")
+    else:
+        monkeypatch.delenv("VIDC_EF_LAZY_RECS", raising=False)
+    lists = _driver_lists(case)
+    off = np.concatenate([[0], np.cumsum([li.size for li in lists])]).astype(np.uint64)
+    ids = torch.from_numpy(np.concatenate(lists).view(np.int64)).cuda()
+    d_off = torch.from_numpy(off.view(np.int64)).cuda() if offsets == "dev" else off
+    ctx = _lib.Context(torch.cuda.current_device())
+    first = _check_driver_object(EfLists.encode(d_off, ids, want_perm=True, ctx=ctx), lists, off)
+    # the same encode on the same context: its universe hint has grown, so (a) now fits at the first attempt.  The same words.
+    again = _check_driver_object(EfLists.encode(d_off, ids, want_perm=True, ctx=ctx), lists, off)
+    for l, ((lo0, hi0), (lo1, hi1)) in enumerate(zip(first, again)):
+        assert np.array_equal(lo0, lo1) and np.array_equal(hi0, hi1), l

@@ -268,7 +268,7 @@ struct vidc_ctx {
     // id payload copied device -> host through this context (vidc_copy_d2h, *_get, *_decode_gather): see vidc_ctx_d2h_bytes
     uint64_t d2h_bytes = 0;
     // largest list universe (last id) the Elias-Fano encoder has met on this context: sizes the streams of the next object before
-    // its ids have been looked at (ef_encode_fast)
+    // its ids have been looked at (ef_plan.h: ef_spec_limits)
     uint64_t ef_universe_hint = 0;
     // scratch of the enqueue-only request calls (req_scratch): the block, its size, the event behind its last use
     void *d_req = nullptr;

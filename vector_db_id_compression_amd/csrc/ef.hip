@@ -17,6 +17,7 @@
 #include "append.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "ef_plan.h"
 #include "host_call.h"
 #include "scan.h"
 #include "rows_csr.h"
@@ -87,9 +88,7 @@ struct EfRec {
     uint32_t nb;        // batches of the list
 };
 // (the record array ends with one unused record: a wavefront loads its record and the next one together)
-#define EF_CLEAR_HIGH_BYTES (64ull << 20)  // high streams beyond this are cleared ahead of the chunk kernels (comment at the memset)
-#define EF_SINGLE_MAX_CHUNKS 16384u  // chunk records the single-tile geometry kernel writes itself (S1: 2.4 k)
-#define EF_ENC_RECS_MAX (1u << 18)  // objects of fewer batches: records written by the encoder, LDS table sized by the longest list
+// (the thresholds of the host calls -- EF_CHUNK, EF_BATCH_BITS, EF_ENC_RECS_MAX, ... -- and every decision taken from them: ef_plan.h)
 
 namespace {
 
@@ -98,7 +97,6 @@ struct PrepOut {
     uint32_t unsorted;
     uint32_t pad;
 };
-__host__ __device__ inline int msb64(uint64_t x) { return 63 - __builtin_clzll(x); }
 struct EfTotals {
     unsigned long long total_bits;
     unsigned int n_unsorted;
@@ -268,27 +266,13 @@ __global__ void __launch_bounds__(64) k_ef_high(const uint64_t *sorted_ids, cons
 // Any order violation raises `unsorted` and the caller redoes the object with the three-pass path further down.
 // (a tile = the lists of one workgroup: 512 threads with two lists each when that is the whole object, else 256 threads
 // with one list each, or four each from 2^18 lists on -- every workgroup of k_ef_offsets sums the totals of the tiles before it)
-// ids per chunk record of the single-pass encoder (VIDC_EF_CHUNK: build-time experiment hook)
-#ifndef VIDC_EF_CHUNK
-#define VIDC_EF_CHUNK 512
-#endif
-constexpr uint32_t EF_CHUNK = VIDC_EF_CHUNK;
-#define EF_SINGLE_LISTS 1024u
-#define EF_E1_MAX_LISTS 262144u
 struct EfRaw {     // the four per-list counts (k_ef_meta) whose prefix sums are the offsets of a list
     uint64_t lw, hw, nb, cnt;  // low words (incl. the padding word), high words, batches of 64 high words, chunks
 };
 struct EfTile {    // totals of one tile
     uint64_t lw, hw, nb, cnt, bits, wide;
 };
-struct EfLimits {  // sizes the host allocated ahead of the geometry kernels (all ~0 / wide_ok: it allocates after them)
-    uint64_t low_words, high_words, nbatches;
-    uint32_t wide_ok, pad;
-};
-struct EfSummary {  // what the host needs before it can allocate the streams
-    uint64_t low_words, high_words, nbatches, nchunks, total_bits;
-    uint32_t wide, unsorted;
-};
+// (EfLimits, EfSummary: ef_plan.h)
 // Everything a wavefront needs to encode one chunk, in one 64-byte record (one scalar load): with the CSR arrays a
 // wavefront walks chunk item -> six per-list arrays -> ids, three dependent round trips for 4 KiB of payload.
 struct EfChunkRec {
@@ -307,7 +291,6 @@ struct EfChunkRec {
 // A list of more than EF_BIG_CHUNKS chunks leaves the records behind its first one to k_ef_big_recs: the tile holding the
 // longest lists of a Zipf-sized index (S2: 1024 lists of 65 536 ids = 130 000 records) kept its 256 threads busy for 0.4 ms
 // while the median tile wrote 1 500 records.
-#define EF_BIG_CHUNKS 8u
 struct EfBigList {
     uint64_t o0, u, lw, hw, nb, rec0;  // first id, universe, offsets of the low / high words and directory entries, first record
     uint32_t l, m, lb, pad;
@@ -378,6 +361,7 @@ __device__ inline void block_exscan(uint64_t (&v)[N], uint64_t (&tot)[N], uint64
 }
 // geometry of this thread's lists (elias_fano.hpp:28-29 per list) -> lbits, universe, raw and the registers o / u / lb / r;
 // returns the tile totals.  All loads of a step are issued together: the kernel is two memory round trips long.
+// (the formulas are ef_plan.h's ef_low_bits / ef_list_geom, written out: this body keeps the schedule of k_ef_meta and k_ef_offsets)
 template <int E, int NT>
 __device__ inline EfTile ef_meta_tile(const uint64_t *ids, const uint64_t *offsets, uint32_t nlist, uint32_t tile,
                                       uint32_t *lbits, uint64_t *universe, EfRaw *raw, uint64_t *sh,
@@ -431,7 +415,7 @@ __global__ void __launch_bounds__(256) k_ef_meta(const uint64_t *ids, const uint
 }
 __device__ inline EfChunkRec ef_make_rec(uint32_t l, uint64_t c, uint64_t o0, uint32_t m, uint64_t u, uint32_t lb,
                                          uint64_t lw, uint64_t hw, uint64_t nb0) {
-    const uint64_t nhw = ((uint64_t)m + 1 + (u >> lb) + 1 + 63) / 64;
+    const uint64_t nhw = ef_high_words(m, u, lb);
     EfChunkRec rc;
     rc.src = o0 + c * EF_CHUNK;
     rc.low_word = lw; rc.high_word = hw; rc.batch0 = nb0; rc.u = u;
@@ -439,7 +423,7 @@ __device__ inline EfChunkRec ef_make_rec(uint32_t l, uint64_t c, uint64_t o0, ui
     rc.n = m;
     rc.list = l;
     rc.b = lb;
-    rc.nb = (uint32_t)((nhw + 63) / 64);
+    rc.nb = (uint32_t)ef_batches_of(nhw);  // (ef_list_geom's batches, in its two parts: see ef_plan.h)
     rc.pad = 0;
     return rc;
 }
@@ -519,7 +503,7 @@ __global__ void __launch_bounds__(NT) k_ef_offsets(const uint64_t *ids, const ui
             out.low_words = a[0]; out.high_words = a[1]; out.nbatches = a[2]; out.nchunks = P[3] + a[3];
             out.total_bits = P[4]; out.wide = P[5] ? 1u : 0u; out.unsorted = 0u;
             *sum = out;
-            // streams allocated before this kernel ran (ef_encode_fast): the chunk kernels behind it do nothing if they do not fit
+            // streams allocated before this kernel ran (ef_enc_plan: spec): the chunk kernels behind it do nothing if they do not fit
             *abort = (a[0] > lim.low_words || a[1] > lim.high_words || a[2] > lim.nbatches || (P[5] && !lim.wide_ok)) ? 1u : 0u;
         }
     }
@@ -974,7 +958,6 @@ __global__ void k_ef_hrank(const uint64_t *sorted_ids, const uint64_t *offsets, 
 // TRANSPOSED through LDS (pos[rank]) and the values are then produced rank-major: lane r reads pos[r], the low bits
 // of element r (both words unconditionally, eight elements per lane in flight) and stores out[r] -- every global
 // access is coalesced and independent of the others.
-#define EF_BATCH_BITS 4096u
 __global__ void __launch_bounds__(64) k_ef_decode(const uint64_t *low, const uint64_t *high, const uint64_t *offsets,
                                                   const uint64_t *low_off, const uint64_t *high_off,
                                                   const uint32_t *lbits, const uint64_t *batch_off,
@@ -1482,8 +1465,9 @@ __global__ void k_ef_arena_geom(const uint2 *meta, uint64_t N, uint32_t *sizes, 
         const uint32_t n = mt.y & 0xffu, l = (mt.y >> 8) & 0x1fu;
         uint32_t lw = 0, hw = 0;
         if (n) {
-            lw = (n * l + 63u) / 64u + 1u;  // +1 padding word for read_bits
-            hw = ((n + 1u) + (mt.x >> l) + 1u + 63u) / 64u;
+            const EfGeom g = ef_list_geom(n, mt.x, l);
+            lw = (uint32_t)g.low_words;
+            hw = (uint32_t)g.high_words;
         }
         sizes[i] = n; lbits[i] = l; universe[i] = mt.x; low_words[i] = lw; high_words[i] = hw; nbatch[i] = (hw + 63u) / 64u;
     }
@@ -1684,11 +1668,11 @@ __global__ void k_ef_geom(const uint64_t *offsets, const PrepOut *prep, uint32_t
         if (m) {  // empty lists have no bitstream object (ef_bitstreams[list_no] stays null, :239-241)
             u = prep[l].max_id;
             wide |= (u >> 32) != 0 || m >= (1ull << 30);
-            lb = (u / m) ? (uint32_t)msb64(u / m) : 0u;
-            const uint64_t hb = (m + 1) + (u >> lb) + 1;
-            bits += m * lb + hb;
-            lw = (uint32_t)((m * lb + 63) / 64 + 1);  // +1 padding word for read_bits
-            hw = (uint32_t)((hb + 63) / 64);
+            lb = ef_low_bits(m, u);
+            const EfGeom g = ef_list_geom(m, u, lb);
+            bits += m * lb + g.high_bits;
+            lw = (uint32_t)g.low_words;
+            hw = (uint32_t)g.high_words;
             uns += prep[l].unsorted ? 1u : 0u;
         }
         lbits[l] = lb; universe[l] = u; low_words[l] = lw; high_words[l] = hw; nbatch[l] = (hw + 63u) / 64u;
@@ -1726,9 +1710,10 @@ int ef_arena_mirror_locked(const vidc_ef *e) {
         const uint32_t n = mt[i].y & 0xffu, l = (mt[i].y >> 8) & 0x1fu;
         uint64_t lw = 0, hw = 0;
         if (n) {
-            e->high_nbits[i] = (uint64_t)(n + 1u) + (mt[i].x >> l) + 1u;
-            lw = ((uint64_t)n * l + 63) / 64 + 1;  // (the CSR form keeps one padding word per list for read_bits)
-            hw = (e->high_nbits[i] + 63) / 64;
+            const EfGeom g = ef_list_geom(n, mt[i].x, l);  // (the CSR form keeps one padding word per list for read_bits)
+            e->high_nbits[i] = g.high_bits;
+            lw = g.low_words;
+            hw = g.high_words;
         }
         e->lbits[i] = l; e->universe[i] = mt[i].x;
         e->offsets[i + 1] = e->offsets[i] + n;
@@ -1757,7 +1742,7 @@ int ef_ensure_meta(const vidc_ef *e) {
     e->high_nbits.assign(e->nlist, 0);
     for (uint64_t l = 0; l < e->nlist; l++) {
         const uint64_t m = e->offsets[l + 1] - e->offsets[l];
-        if (m) e->high_nbits[l] = (m + 1) + (e->universe[l] >> e->lbits[l]) + 1;
+        if (m) e->high_nbits[l] = ef_list_geom(m, e->universe[l], e->lbits[l]).high_bits;
     }
     e->meta_host = true;
     return VIDC_OK;
@@ -1819,6 +1804,15 @@ int ef_ensure_csr(vidc_ctx *ctx, const vidc_ef *ce) {
     return VIDC_OK;
 }
 
+// the per-list geometry arrays of an object under construction (both encoders)
+int ef_alloc_geometry(vidc_ctx *ctx, vidc_ef *e) {
+    const uint64_t nlist = e->nlist;
+    VIDC_TRY(e->d_low_off.alloc(nlist + 1, ctx->dpool)); VIDC_TRY(e->d_high_off.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(e->d_batch_off.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(e->d_lbits.alloc(nlist ? nlist : 1, ctx->dpool)); VIDC_TRY(e->d_universe.alloc(nlist ? nlist : 1, ctx->dpool));
+    return VIDC_OK;
+}
+
 // the three-pass encoder for objects with lists that are not ascending (max + order check, sort, streams):
 // e->d_offsets, nlist, ntotal are set
 int ef_encode_general(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t flags) {
@@ -1857,9 +1851,7 @@ int ef_encode_general(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t
     VIDC_TRY(s_prep.get(ctx, (nlist + 1) * sizeof(PrepOut)));
     VIDC_TRY(s_lw.get(ctx, (nlist + 1) * 4)); VIDC_TRY(s_hw.get(ctx, (nlist + 1) * 4)); VIDC_TRY(s_nb.get(ctx, (nlist + 1) * 4));
     VIDC_TRY(s_tot.get(ctx, sizeof(EfTotals)));
-    VIDC_TRY(e->d_low_off.alloc(nlist + 1, ctx->dpool)); VIDC_TRY(e->d_high_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(e->d_batch_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(e->d_lbits.alloc(nlist ? nlist : 1, ctx->dpool)); VIDC_TRY(e->d_universe.alloc(nlist ? nlist : 1, ctx->dpool));
+    VIDC_TRY(ef_alloc_geometry(ctx, e));
     VIDC_HIP(hipMemsetAsync(s_prep.p, 0, (nlist + 1) * sizeof(PrepOut), ctx->stream));
     VIDC_HIP(hipMemsetAsync(s_tot.p, 0, sizeof(EfTotals), ctx->stream));
     if (e->nchunks)
@@ -1911,18 +1903,9 @@ int ef_encode_general(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t
         VIDC_TRY(ef_ensure_offsets(e));
         std::vector<PrepOut> prep(nlist);
         VIDC_HIP(hipMemcpy(prep.data(), s_prep.p, nlist * sizeof(PrepOut), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> unsorted;
-        for (uint64_t l = 0; l < nlist; l++)
-            if (e->offsets[l + 1] > e->offsets[l] && prep[l].unsorted) unsorted.push_back((uint32_t)l);
-        std::stable_sort(unsorted.begin(), unsorted.end(), [&](uint32_t a, uint32_t b) {
-            return e->offsets[a + 1] - e->offsets[a] > e->offsets[b + 1] - e->offsets[b];
-        });
-        std::vector<uint64_t> key_off(unsorted.size() + 1, 0);
-        for (size_t i = 0; i < unsorted.size(); i++) {
-            uint64_t n = e->offsets[unsorted[i] + 1] - e->offsets[unsorted[i]], p2 = 1;
-            while (p2 < n) p2 <<= 1;
-            key_off[i + 1] = key_off[i] + p2;
-        }
+        const EfSortPlan sp = ef_sort_plan(e->offsets.data(), nlist, [&](uint64_t l) { return prep[l].unsorted != 0; });
+        const std::vector<uint32_t> &unsorted = sp.lists;
+        const std::vector<uint64_t> &key_off = sp.key_off;
         VIDC_TRY(s_sorted.get(ctx, e->ntotal * 8));
         VIDC_HIP(hipMemcpyAsync(s_sorted.p, d_ids, e->ntotal * 8, hipMemcpyDeviceToDevice, ctx->stream));
         VIDC_TRY(s_keys.get(ctx, key_off.back() * 8));
@@ -1967,17 +1950,11 @@ int ef_encode_general(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t
     return VIDC_OK;
 }
 
-// the single-pass encoder (kernels above); *retry is raised when some list turned out not to be ascending.
+// ---- the single-pass encoder (kernels above): one attempt = the stages ef_enc_begin .. ef_enc_finish over an EfEncodeCall; what
+// they decide is ef_plan.h's.
 // nchunks: number of EF_CHUNK-sized pieces of all lists (the caller walks the host offsets anyway)
-// spec: the streams are allocated BEFORE the geometry kernels run, by bounds that need only the list lengths and a guess of the
-// largest universe U (ids of an index are 0 .. ntotal-1 unless the caller numbers them himself; the context remembers a larger
-// one it has met):   low  <= sum n_i msb(U / n_i) <= ntotal log2(U nlist / ntotal) bits (n log(U / n) is concave) + 2 words per list,
-//                    high  = (n + 1) + (u >> l) + 1 <= 3 n + 1 bits per list (u >> l < 2 n) whatever U is.
-// Geometry and chunk kernels are then queued back to back and the call waits ONCE, at its end (before: a wait between them for the
-// sizes, 20-25 us of an S1-sized call's 60).  k_ef_offsets checks the exact sizes against the allocation on the device; if they
-// do not fit (a universe beyond the guess, ids >= 2^32) it raises *abort, the chunk kernels return at once, *respec is set and the
-// caller runs the call again the old way.  Cost of the bound: the buffers are up to ~15 % larger than the streams (n_low / n_high
-// hold the exact word counts).
+// spec (ef_want_spec): streams allocated ahead of the geometry kernels, one wait; an attempt whose streams were too small ends as
+// EF_ENC_RESPEC (the chunk kernels saw *abort and wrote nothing) and the driver runs it again the old way.
 // dv (device offsets, vidc_ef_encode_dev): the caller's array, copied into e->d_offsets and validated by k_offsets_ingest inside the
 // timed region; nchunks / max_list are then bounds (floor(ntotal / EF_CHUNK) + nlist, ntotal) and the exact values come from the
 // ingest's results (device) and summary (host, after the wait).
@@ -1986,208 +1963,279 @@ struct EfDevIn {
     unsigned long long *acc;  // doff_block: accumulators, then results
     DevOffSummary *sum;       // pinned
 };
-int ef_encode_fast(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
-                   bool *retry, bool spec, bool *respec, const EfDevIn *dv) {
-    const uint64_t nlist = e->nlist;
-    const uint32_t nl32 = (uint32_t)nlist;
-    // (one tile only for objects whose chunk records one workgroup can write: 1024 lists of a million ids each are two million records,
-    // and spreading those over the GPU is what k_ef_big_recs is for)
-    const bool single = nl32 <= EF_SINGLE_LISTS && nchunks <= EF_SINGLE_MAX_CHUNKS;  // (one tile, the geometry kernel alone)
-    const uint32_t tile_lists = single ? EF_SINGLE_LISTS : (nl32 <= EF_E1_MAX_LISTS ? 256u : 1024u);
-    const uint32_t ntiles = nl32 ? (nl32 + tile_lists - 1u) / tile_lists : 1u;
-    VidcPhaseTimer pt(ctx);
-    HostTrace tr("ef encode_fast");
+enum EfEncOutcome { EF_ENC_DONE, EF_ENC_RESPEC /* the speculative streams were too small */, EF_ENC_UNSORTED /* some list is not ascending */ };
+struct EfEncIn {  // what every attempt of a call starts from
+    vidc_ctx *ctx;
+    vidc_ef *e;  // the object under construction: d_offsets, nlist, ntotal are set
+    const uint64_t *d_ids;
+    uint32_t flags;
+    uint64_t nchunks, max_list;
+    const EfDevIn *dv;
+    EfEncPolicy pol;
+};
+struct EfEncodeCall : EfEncIn {
+    explicit EfEncodeCall(const EfEncIn &in) : EfEncIn(in), pt(in.ctx), tr("ef encode_fast") {}
+    EfEncPlan plan;
+    VidcPhaseTimer pt;
+    HostTrace tr;
     Scratch s_raw, s_tiles, s_recs, s_big;
     Pinned tail;
-    VIDC_TRY(tail.get(ctx, 2 * sizeof(EfSummary)));
-    EfSummary *hs = tail.as<EfSummary>();
-    VIDC_TRY(s_raw.get(ctx, (nlist + 1) * sizeof(EfRaw)));
-    VIDC_TRY(s_tiles.get(ctx, (size_t)ntiles * sizeof(EfTile)));
-    VIDC_TRY(s_recs.get(ctx, (nchunks ? nchunks : 1) * sizeof(EfChunkRec)));
-    // long lists (more than EF_BIG_CHUNKS chunks: at most nchunks / (EF_BIG_CHUNKS + 1) of them) + their count
-    const uint64_t big_cap = nchunks / (EF_BIG_CHUNKS + 1u) + 1u;
-    VIDC_TRY(s_big.get(ctx, big_cap * sizeof(EfBigList) + 16));
-    EfBigList *d_big = (EfBigList *)((char *)s_big.p + 16);
-    uint32_t *d_nbig = s_big.as<uint32_t>();
-    uint32_t *d_abort = d_nbig + 1;  // (written by k_ef_offsets whenever there are lists)
-    if (!single || !nlist) VIDC_HIP(hipMemsetAsync(d_nbig, 0, 16, ctx->stream));  // (a single tile writes every record itself)
-    EfLimits lim{~0ull, ~0ull, ~0ull, 1u, 0u};
-    if (spec) {
-        const uint64_t U = std::max<uint64_t>(e->ntotal ? e->ntotal - 1 : 0, ctx->ef_universe_hint);
-        const double ratio = e->ntotal ? (double)U * (double)nlist / (double)e->ntotal : 0.0;
-        const double low_bits = ratio > 1.0 ? (double)e->ntotal * std::log2(ratio) * 1.0001 : 0.0;
-        lim.low_words = (uint64_t)(low_bits / 64.0) + 2 * nlist + 4;
-        lim.high_words = (3 * e->ntotal + nlist) / 64 + nlist + 2;
-        lim.nbatches = lim.high_words / 64 + nlist + 2;
-        lim.wide_ok = 0u;
-    }
-    VIDC_TRY(e->d_low_off.alloc(nlist + 1, ctx->dpool)); VIDC_TRY(e->d_high_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(e->d_batch_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(e->d_lbits.alloc(nlist ? nlist : 1, ctx->dpool)); VIDC_TRY(e->d_universe.alloc(nlist ? nlist : 1, ctx->dpool));
+    EfSummary *hs = nullptr;  // pinned: [0] the geometry kernel's summary, [1].unsorted the chunk kernels' "not ascending" flag
+    EfBigList *d_big = nullptr;
+    uint32_t *d_nbig = nullptr, *d_abort = nullptr;  // (d_abort: written by k_ef_offsets whenever there are lists)
+    EfRec *d_drecs = nullptr;                         // the object's bulk-decode records when the encoder writes them
+    uint64_t low_words = 0, high_words = 0;           // words to allocate
+    bool wide_ids = false, clear_high = false, enc_recs = false;
+    EfEncOutcome outcome = EF_ENC_DONE;
+};
+
+int ef_enc_begin(EfEncodeCall &c, bool spec) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_ef *e = c.e;
+    const uint64_t nlist = e->nlist;
+    c.pol.universe_hint = ctx->ef_universe_hint;
+    c.plan = ef_enc_plan(nlist, e->ntotal, c.nchunks, c.max_list, c.dv != nullptr, spec, c.pol);
+    VIDC_TRY(c.tail.get(ctx, 2 * sizeof(EfSummary)));
+    c.hs = c.tail.as<EfSummary>();
+    VIDC_TRY(c.s_raw.get(ctx, c.plan.raw_n * sizeof(EfRaw)));
+    VIDC_TRY(c.s_tiles.get(ctx, (size_t)c.plan.tiles_n * sizeof(EfTile)));
+    VIDC_TRY(c.s_recs.get(ctx, c.plan.recs_n * sizeof(EfChunkRec)));
+    VIDC_TRY(c.s_big.get(ctx, c.plan.big_cap * sizeof(EfBigList) + 16));  // the long lists + their count
+    c.d_big = (EfBigList *)((char *)c.s_big.p + 16);
+    c.d_nbig = c.s_big.as<uint32_t>();
+    c.d_abort = c.d_nbig + 1;
+    if (!c.plan.single || !nlist) VIDC_HIP(hipMemsetAsync(c.d_nbig, 0, 16, ctx->stream));  // (a single tile writes every record itself)
+    VIDC_TRY(ef_alloc_geometry(ctx, e));
     VIDC_TRY(e->d_chunks.alloc(1, ctx->dpool));  // (the chunk table of the three-pass encoder: not needed here)
-    tr.mark("scratch + geometry arrays");
-    pt.begin();
-    if (dv) {
-        dv->sum->done = 0;
-        hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, dv->src, e->d_offsets.p, nlist, e->ntotal,
-                           (uint32_t)__builtin_ctz(EF_CHUNK), 0u, 0xfffffff0ull, dv->acc, dv->acc + DOFF_NACC, dv->sum);
+    c.tr.mark("scratch + geometry arrays");
+    return VIDC_OK;
+}
+
+// ingest of device offsets and the geometry kernels, queued
+int ef_enc_geometry(EfEncodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_ef *e = c.e;
+    const EfEncPlan &pl = c.plan;
+    const uint64_t nlist = e->nlist;
+    const uint32_t nl32 = (uint32_t)nlist;
+    c.pt.begin();
+    if (c.dv) {
+        c.dv->sum->done = 0;
+        hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, c.dv->src, e->d_offsets.p, nlist, e->ntotal,
+                           (uint32_t)__builtin_ctz(EF_CHUNK), 0u, 0xfffffff0ull, c.dv->acc, c.dv->acc + DOFF_NACC, c.dv->sum);
     }
-    if (single) {
-        hipLaunchKernelGGL((k_ef_offsets<true, 2, 512>), dim3(1), dim3(512), 0, ctx->stream, d_ids, e->d_offsets.p, nl32,
-                           e->d_lbits.p, e->d_universe.p, (const EfRaw *)nullptr, (const EfTile *)nullptr, 1u,
-                           e->d_low_off.p, e->d_high_off.p, e->d_batch_off.p, s_recs.as<EfChunkRec>(),
-                           hs, d_big, d_nbig, lim, d_abort);
-    } else if (tile_lists == 256u) {
-        hipLaunchKernelGGL(k_ef_meta<1>, dim3(ntiles), dim3(256), 0, ctx->stream, d_ids, e->d_offsets.p, nl32,
-                           e->d_lbits.p, e->d_universe.p, s_raw.as<EfRaw>(), s_tiles.as<EfTile>());
-        hipLaunchKernelGGL((k_ef_offsets<false, 1, 256>), dim3(ntiles), dim3(256), 0, ctx->stream, d_ids, e->d_offsets.p,
-                           nl32, e->d_lbits.p, e->d_universe.p, s_raw.as<EfRaw>(), s_tiles.as<EfTile>(), ntiles,
-                           e->d_low_off.p, e->d_high_off.p, e->d_batch_off.p, s_recs.as<EfChunkRec>(),
-                           hs, d_big, d_nbig, lim, d_abort);
+    auto offsets_kernel = [&](auto kernel, uint32_t threads, const EfRaw *raw, const EfTile *tiles) {
+        hipLaunchKernelGGL(kernel, dim3(pl.ntiles), dim3(threads), 0, ctx->stream, c.d_ids, e->d_offsets.p, nl32, e->d_lbits.p,
+                           e->d_universe.p, raw, tiles, pl.ntiles, e->d_low_off.p, e->d_high_off.p, e->d_batch_off.p,
+                           c.s_recs.as<EfChunkRec>(), c.hs, c.d_big, c.d_nbig, pl.lim, c.d_abort);
+    };
+    auto meta_kernel = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(pl.ntiles), dim3(256), 0, ctx->stream, c.d_ids, e->d_offsets.p, nl32, e->d_lbits.p,
+                           e->d_universe.p, c.s_raw.as<EfRaw>(), c.s_tiles.as<EfTile>());
+    };
+    if (pl.single) {
+        offsets_kernel(k_ef_offsets<true, 2, 512>, 512u, (const EfRaw *)nullptr, (const EfTile *)nullptr);
+    } else if (pl.lists_per_thread == 1u) {
+        meta_kernel(k_ef_meta<1>);
+        offsets_kernel(k_ef_offsets<false, 1, 256>, 256u, c.s_raw.as<EfRaw>(), c.s_tiles.as<EfTile>());
     } else {
-        hipLaunchKernelGGL(k_ef_meta<4>, dim3(ntiles), dim3(256), 0, ctx->stream, d_ids, e->d_offsets.p, nl32,
-                           e->d_lbits.p, e->d_universe.p, s_raw.as<EfRaw>(), s_tiles.as<EfTile>());
-        hipLaunchKernelGGL((k_ef_offsets<false, 4, 256>), dim3(ntiles), dim3(256), 0, ctx->stream, d_ids, e->d_offsets.p,
-                           nl32, e->d_lbits.p, e->d_universe.p, s_raw.as<EfRaw>(), s_tiles.as<EfTile>(), ntiles,
-                           e->d_low_off.p, e->d_high_off.p, e->d_batch_off.p, s_recs.as<EfChunkRec>(),
-                           hs, d_big, d_nbig, lim, d_abort);
+        meta_kernel(k_ef_meta<4>);
+        offsets_kernel(k_ef_offsets<false, 4, 256>, 256u, c.s_raw.as<EfRaw>(), c.s_tiles.as<EfTile>());
     }
-    if (!single && max_list > (uint64_t)EF_CHUNK * EF_BIG_CHUNKS)  // (some list is that long)
-        hipLaunchKernelGGL(k_ef_big_recs, dim3((uint32_t)std::min<uint64_t>(big_cap, (uint64_t)ctx->num_cu * 32)), dim3(64), 0, ctx->stream,
-                           d_big, d_nbig, s_recs.as<EfChunkRec>());
+    if (pl.big_recs)
+        hipLaunchKernelGGL(k_ef_big_recs, dim3((uint32_t)std::min<uint64_t>(pl.big_cap, (uint64_t)ctx->num_cu * 32)), dim3(64), 0, ctx->stream,
+                           c.d_big, c.d_nbig, c.s_recs.as<EfChunkRec>());
     VIDC_HIP(hipGetLastError());
     // (ONE pair of timing events around the call's kernels: every record is a packet the queue processes between two kernels)
     // (the geometry kernel stores its summary into the pinned block itself, and the chunk kernels their "not ascending" flag: a copy
     // engine between a kernel and the host's wake-up costs more than these kernels)
-    tr.mark("geometry kernels queued");
-    uint64_t low_words = lim.low_words, high_words = lim.high_words;  // words to allocate
-    bool wide_ids = false;
-    e->nchunks = nchunks;
-    e->nbatches = lim.nbatches;  // (spec: an upper bound until the call's only wait)
-    if (!spec) {
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        if (dv) {  // (this path waits here anyway: the exact figures take the host path's decisions from now on)
-            VIDC_TRY(doff_status(*dv->sum, "elias-fano", VIDC_ERR_INVALID));
-            nchunks = dv->sum->chunks;
-            max_list = dv->sum->max_n;
-            e->nchunks = nchunks;
-        }
-        if (hs->nchunks != nchunks) {
-            set_error("elias-fano encoder: chunk count mismatch (%llu vs %llu)", (unsigned long long)hs->nchunks,
-                      (unsigned long long)nchunks);
-            return VIDC_ERR_OVERFLOW;
-        }
-        low_words = hs->low_words; high_words = hs->high_words;
-        e->nbatches = hs->nbatches;
-        e->total_bits = hs->total_bits;
-        wide_ids = hs->wide != 0;
-        e->narrow = !wide_ids;
+    c.tr.mark("geometry kernels queued");
+    return VIDC_OK;
+}
+
+// behind a wait: the status of device offsets and their exact figures, then the geometry kernel's chunk count against the call's
+int ef_enc_exact_figures(EfEncodeCall &c) {
+    if (c.dv) {
+        VIDC_TRY(doff_status(*c.dv->sum, "elias-fano", VIDC_ERR_INVALID));
+        c.nchunks = c.e->nchunks = c.dv->sum->chunks;
+        c.max_list = c.dv->sum->max_n;
     }
-    VIDC_TRY(e->d_low.alloc(low_words ? low_words : 1, ctx->dpool));
-    VIDC_TRY(e->d_high.alloc(high_words ? high_words : 1, ctx->dpool));
+    if (c.hs->nchunks == c.nchunks) return VIDC_OK;
+    set_error("elias-fano encoder: chunk count mismatch (%llu vs %llu)", (unsigned long long)c.hs->nchunks, (unsigned long long)c.nchunks);
+    return VIDC_ERR_OVERFLOW;
+}
+
+// the sizes of the streams (without speculation: from the geometry kernel's summary, after a wait), the stream and directory
+// allocations, the clearing and record decisions
+int ef_enc_size_streams(EfEncodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_ef *e = c.e;
+    c.low_words = c.plan.lim.low_words; c.high_words = c.plan.lim.high_words;
+    e->nchunks = c.nchunks;
+    e->nbatches = c.plan.lim.nbatches;  // (spec: an upper bound until the call's only wait)
+    if (!c.plan.spec) {
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        VIDC_TRY(ef_enc_exact_figures(c));  // (device offsets: this path waits here anyway, and takes the host path's decisions from now on)
+        c.low_words = c.hs->low_words; c.high_words = c.hs->high_words;
+        e->nbatches = c.hs->nbatches;
+        e->total_bits = c.hs->total_bits;
+        c.wide_ids = c.hs->wide != 0;
+        e->narrow = !c.wide_ids;
+    }
+    VIDC_TRY(e->d_low.alloc(c.low_words ? c.low_words : 1, ctx->dpool));
+    VIDC_TRY(e->d_high.alloc(c.high_words ? c.high_words : 1, ctx->dpool));
     VIDC_TRY(e->d_batches.alloc(e->nbatches ? e->nbatches : 1, ctx->dpool));
     VIDC_TRY(e->d_hrank.alloc(e->nbatches ? e->nbatches : 1, ctx->dpool));
-    // The chunk kernels write every word of the high stream (k_ef_lowhigh), so nothing has to zero it.  A stream that does not
-    // fit the caches is cleared all the same, inside the timed region: the kernels store a chunk's 100-200 bytes at a time, lines shared
-    // between wavefronts reach HBM as partial writes, and the same kernel runs 8 % faster on lines a fill has just left in the
-    // memory-side cache (S2, 250 MB of high words: 2.95 + 0.08 ms instead of 3.19; 16 M ids, 4 MB: 68.7 instead of 65.8 + 4.5 us).
-    // VIDC_EF_MEMSET=1 / 0 (measurements): always / never.
-    const char *ms_env = std::getenv("VIDC_EF_MEMSET");
-    const bool clear_high = ms_env ? ms_env[0] == '1' : high_words * 8 > EF_CLEAR_HIGH_BYTES;
-    // Objects of up to 2^18 batches get their bulk-decode records (EfRec) from the encoder: the wavefront that writes a batch's
-    // directory entry holds everything the record needs, and the first decode_all of a fresh object is one launch instead of
-    // k_ef_build_recs + decode (16 M ids in lists of 256: 53 -> ~47 us; S1-sized: 20 -> ~15 us).  Larger objects keep the lazy
-    // build: it also finds the exact size of the largest batch, which sets the occupancy of their millisecond-long decode.
-    EfRec *d_drecs = nullptr;
-    const bool enc_recs = nchunks && max_list && e->nbatches && e->nbatches < EF_ENC_RECS_MAX && !std::getenv("VIDC_EF_LAZY_RECS");
-    if (enc_recs) {
+    const char *ms_env = std::getenv("VIDC_EF_MEMSET");  // (measurements: 1 / 0 = always / never)
+    c.pol.memset = ms_env ? (ms_env[0] == '1' ? 1 : 0) : -1;
+    c.pol.lazy_recs = std::getenv("VIDC_EF_LAZY_RECS") != nullptr;
+    c.clear_high = ef_clear_high(c.high_words, c.pol);  // (cleared inside the timed region)
+    c.enc_recs = ef_enc_recs(c.nchunks, c.max_list, e->nbatches, c.pol);
+    if (c.enc_recs) {
         std::lock_guard<std::mutex> g(e->mu);
         e->recs_ready = false;
         VIDC_TRY(e->d_recs.alloc(e->nbatches + 1, ctx->dpool));
-        d_drecs = e->d_recs.p;
+        c.d_drecs = e->d_recs.p;
     }
-    if ((flags & VIDC_EF_WANT_PERM) != 0) {
+    return VIDC_OK;
+}
+
+// the identity permutation (an ascending list keeps its order), the clearing, the chunk kernel(s)
+int ef_enc_chunks(EfEncodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_ef *e = c.e;
+    if ((c.flags & VIDC_EF_WANT_PERM) != 0) {
         VIDC_TRY(e->d_perm.alloc(e->ntotal ? e->ntotal : 1, ctx->dpool));
         e->has_perm = true;
         if (e->ntotal) {
             const uint32_t grid = (uint32_t)std::min<uint64_t>((e->ntotal + 255) / 256, (uint64_t)ctx->num_cu * 32);
-            hipLaunchKernelGGL(k_iota_perm, dim3(grid), dim3(256), 0, ctx->stream, e->d_offsets.p, nl32, e->ntotal,
+            hipLaunchKernelGGL(k_iota_perm, dim3(grid), dim3(256), 0, ctx->stream, e->d_offsets.p, (uint32_t)e->nlist, e->ntotal,
                                e->d_perm.p);
         }
     }
-    if (nchunks) {
-        const uint32_t cgrid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)ctx->num_cu * 256);
-        hs[1].unsorted = 0u;
-        uint32_t *d_flag = &hs[1].unsorted;
-        if (clear_high) VIDC_HIP(hipMemsetAsync(e->d_high.p, 0, high_words * 8, ctx->stream));
-        if (dv && spec) {  // (spec: the ids are below 2^32, wide_ids is false)
-            const unsigned long long *res = dv->acc + DOFF_NACC;
-            // (grid: 32 wavefronts per CU, looping over the chunks -- the two forms that return at once then cost two small dispatches,
-            // not two of up to 256 wavefronts per CU)
-            const uint32_t cgrid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)ctx->num_cu * 32);
-            hipLaunchKernelGGL((k_ef_lowhigh32_dev<4, true, 0u>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids, s_recs.as<EfChunkRec>(), res,
-                               e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
-            hipLaunchKernelGGL((k_ef_lowhigh32_dev<EF_CHUNK / 64, true, 1u>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids,
-                               s_recs.as<EfChunkRec>(), res, e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag,
-                               d_drecs, d_abort);
-            hipLaunchKernelGGL((k_ef_lowhigh32_dev<EF_CHUNK / 64, false, 2u>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids,
-                               s_recs.as<EfChunkRec>(), res, e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag,
-                               d_drecs, d_abort);
-        } else if (wide_ids)
-            hipLaunchKernelGGL(k_ef_lowhigh, dim3(cgrid), dim3(64), 0, ctx->stream, d_ids, s_recs.as<EfChunkRec>(), nchunks,
-                               e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
-        else if (max_list <= 256)
-            hipLaunchKernelGGL((k_ef_lowhigh32<4, true, true, true>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids, s_recs.as<EfChunkRec>(),
-                               nchunks, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
-        else if (e->ntotal < 256 * nchunks)  // (chunks half full on average)
-            hipLaunchKernelGGL((k_ef_lowhigh32<EF_CHUNK / 64, true, true, true>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids,
-                               s_recs.as<EfChunkRec>(), nchunks, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
-        else
-            hipLaunchKernelGGL((k_ef_lowhigh32<EF_CHUNK / 64, false, true, true>), dim3(cgrid), dim3(64), 0, ctx->stream, d_ids,
-                               s_recs.as<EfChunkRec>(), nchunks, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, d_drecs, d_abort);
+    const EfChunkLaunch cl = ef_chunk_form(c.nchunks, e->ntotal, c.max_list, c.wide_ids, c.plan.dev_forms, ctx->num_cu);
+    if (cl.form != EF_FORM_NONE) {
+        c.hs[1].unsorted = 0u;
+        uint32_t *d_flag = &c.hs[1].unsorted;
+        if (c.clear_high) VIDC_HIP(hipMemsetAsync(e->d_high.p, 0, c.high_words * 8, ctx->stream));
+        auto host_form = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(cl.grid), dim3(64), 0, ctx->stream, c.d_ids, c.s_recs.as<EfChunkRec>(), c.nchunks, e->d_low.p,
+                               e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, c.d_drecs, c.d_abort);
+        };
+        auto dev_form = [&](auto kernel) {  // (the form and the chunk count are the ingest's results, on the device)
+            hipLaunchKernelGGL(kernel, dim3(cl.grid), dim3(64), 0, ctx->stream, c.d_ids, c.s_recs.as<EfChunkRec>(), c.dv->acc + DOFF_NACC,
+                               e->ntotal, e->d_low.p, e->d_high.p, e->d_hrank.p, e->d_batches.p, d_flag, c.d_drecs, c.d_abort);
+        };
+        switch (cl.form) {
+        case EF_FORM_DEV:
+            dev_form(k_ef_lowhigh32_dev<4, true, 0u>);
+            dev_form(k_ef_lowhigh32_dev<EF_CHUNK / 64, true, 1u>);
+            dev_form(k_ef_lowhigh32_dev<EF_CHUNK / 64, false, 2u>);
+            break;
+        case EF_FORM_WIDE: host_form(k_ef_lowhigh); break;
+        case EF_FORM_SHORT: host_form(k_ef_lowhigh32<4, true, true, true>); break;
+        case EF_FORM_HALF: host_form(k_ef_lowhigh32<EF_CHUNK / 64, true, true, true>); break;
+        default: host_form(k_ef_lowhigh32<EF_CHUNK / 64, false, true, true>); break;
+        }
         VIDC_HIP(hipGetLastError());
     }
-    pt.end();
-    tr.mark("streams allocated, chunk kernels queued");
+    c.pt.end();
+    c.tr.mark("streams allocated, chunk kernels queued");
+    return VIDC_OK;
+}
+
+// the wait, the status of device offsets, the verdict on the speculative sizes, publication of the records
+int ef_enc_finish(EfEncodeCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_ef *e = c.e;
+    const bool spec = c.plan.spec;
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    tr.mark("wait");
-    ctx->last_kernel_ms = pt.collect();
-    tr.mark("event times");
-    if (dv && spec) {  // bad offsets first (the kernels above ran on the valid split that replaced them); then the exact figures
-        if (!dv->sum->done) { set_error("elias-fano: the offsets summary was not written"); return VIDC_ERR_HIP; }
-        VIDC_TRY(doff_status(*dv->sum, "elias-fano", VIDC_ERR_INVALID));
-        nchunks = dv->sum->chunks;
-        max_list = dv->sum->max_n;
-        e->nchunks = nchunks;
-        e->max_list = max_list;
-    }
-    if (spec) {
-        if (hs->nchunks != nchunks) {
-            set_error("elias-fano encoder: chunk count mismatch (%llu vs %llu)", (unsigned long long)hs->nchunks,
-                      (unsigned long long)nchunks);
-            return VIDC_ERR_OVERFLOW;
-        }
-        if (hs->low_words > lim.low_words || hs->high_words > lim.high_words || hs->nbatches > lim.nbatches || hs->wide) {
-            *respec = true;  // (the chunk kernels saw the same verdict in *abort and wrote nothing)
+    c.tr.mark("wait");
+    ctx->last_kernel_ms = c.pt.collect();
+    c.tr.mark("event times");
+    if (spec) {  // bad offsets first (the kernels above ran on the valid split that replaced them); then the exact figures
+        if (c.dv && !c.dv->sum->done) { set_error("elias-fano: the offsets summary was not written"); return VIDC_ERR_HIP; }
+        VIDC_TRY(ef_enc_exact_figures(c));
+        if (c.dv) e->max_list = c.max_list;
+        if (!ef_spec_fits(*c.hs, c.plan.lim)) {  // (the chunk kernels saw the same verdict in *abort and wrote nothing)
+            c.outcome = EF_ENC_RESPEC;
             return VIDC_OK;
         }
-        e->nbatches = hs->nbatches;
-        e->total_bits = hs->total_bits;
+        e->nbatches = c.hs->nbatches;
+        e->total_bits = c.hs->total_bits;
         e->narrow = true;
-        e->n_low = hs->low_words; e->n_high = hs->high_words;
+        e->n_low = c.hs->low_words; e->n_high = c.hs->high_words;
     }
-    if (nchunks && hs[1].unsorted) *retry = true;
-    if (enc_recs && !*retry) {
+    if (c.nchunks && c.hs[1].unsorted) c.outcome = EF_ENC_UNSORTED;
+    if (c.enc_recs && c.outcome != EF_ENC_UNSORTED) {
         std::lock_guard<std::mutex> g(e->mu);
-        e->recs_max_cnt = (uint32_t)std::min<uint64_t>(max_list, EF_BATCH_BITS);
+        e->recs_max_cnt = ef_recs_max_cnt(c.max_list);
         e->recs_ready = true;
     }
     return VIDC_OK;
 }
 
-struct EfDevIn;
-int ef_encode_lists(vidc_ctx *ctx, vidc_ef *ep, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
-                    const uint64_t *host_offsets, const EfDevIn *dv = nullptr);
+// one attempt; its scratch and pinned blocks go back to the context before the next one starts
+int ef_enc_attempt(const EfEncIn &in, bool spec, EfEncOutcome *outcome) {
+    EfEncodeCall c(in);
+    VIDC_TRY(ef_enc_begin(c, spec));
+    VIDC_TRY(ef_enc_geometry(c));
+    VIDC_TRY(ef_enc_size_streams(c));
+    VIDC_TRY(ef_enc_chunks(c));
+    VIDC_TRY(ef_enc_finish(c));
+    *outcome = c.outcome;
+    return VIDC_OK;
+}
+
+// The one place that puts an object back for another attempt: what an attempt leaves behind that the next encoder does not
+// overwrite by itself -- the exact stream sizes, the size, the permutation flag, the bulk-decode records.  (The two hand-written
+// lists this replaces differed in total_bits alone: the re-run without speculation did not clear it.  A speculative attempt that
+// does not fit ends before it writes total_bits, so the object still holds 0 there and clearing it changes nothing.)
+void ef_enc_put_back(vidc_ef *e) {
+    e->n_low = e->n_high = ~0ull;
+    e->total_bits = 0;
+    e->has_perm = false;
+    e->recs_ready = false;  // (the general encoder's objects build their records on the first bulk decode)
+    e->d_recs.release();
+}
+
+// the encode once the chunk count and the longest list are known (host or device offsets): attempt, re-run without speculation,
+// three-pass fallback.  host_offsets: the caller's host array, NULL for an object built from device offsets (the fallback mirrors
+// the object's device copy)
+int ef_encode_lists(vidc_ctx *ctx, vidc_ef *e, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
+                    const uint64_t *host_offsets, const EfDevIn *dv = nullptr) {
+    HostTrace tr("ef encode (lists)");
+    const uint64_t nlist = e->nlist;
+    e->max_list = max_list;
+    tr.mark("offsets staged");
+    static const bool no_spec = std::getenv("VIDC_EF_NO_SPEC") != nullptr;  // (measurement switch: always size the streams after the geometry kernels)
+    EfEncIn in{ctx, e, d_ids, flags, nchunks, max_list, dv, EfEncPolicy{}};
+    in.pol.no_spec = no_spec;
+    in.pol.num_cu = ctx->num_cu;
+    EfEncOutcome outcome = EF_ENC_DONE;
+    VIDC_TRY(ef_enc_attempt(in, ef_want_spec(e->ntotal, in.pol), &outcome));
+    if (outcome == EF_ENC_RESPEC) {  // the guess of the universe was too small: size the streams from the ids, and remember how large they are
+        ef_enc_put_back(e);
+        VIDC_TRY(ef_enc_attempt(in, false, &outcome));
+        std::vector<uint64_t> uni(nlist);
+        VIDC_HIP(hipMemcpy(uni.data(), e->d_universe.p, nlist * 8, hipMemcpyDeviceToHost));
+        for (uint64_t u : uni) ctx->ef_universe_hint = std::max(ctx->ef_universe_hint, u);
+    }
+    tr.mark("encode_fast (launches + wait)");
+    if (outcome == EF_ENC_UNSORTED) {  // some list is not ascending: general three-pass encoder with the sort
+        if (host_offsets) {
+            e->offsets = vec_pool<uint64_t>().take(nlist + 1);
+            if (nlist) e->offsets.assign(host_offsets, host_offsets + nlist + 1);
+            else e->offsets.assign(1, 0);
+            e->offsets_host = true;
+        } else {
+            VIDC_TRY(ef_ensure_offsets(e));  // (device offsets: the one copy of them to the host, on this slow path only)
+        }
+        ef_enc_put_back(e);
+        VIDC_TRY(ef_encode_general(ctx, e, d_ids, flags));
+    }
+    return VIDC_OK;
+}
 
 }  // namespace
 
@@ -2236,62 +2284,8 @@ int vidc_ef_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
     return VIDC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// the encode once the chunk count and the longest list are known (host or device offsets); host_offsets: the caller's host array,
-// NULL for an object built from device offsets (the retry mirrors the object's device copy)
-int ef_encode_lists(vidc_ctx *ctx, vidc_ef *ep, const uint64_t *d_ids, uint32_t flags, uint64_t nchunks, uint64_t max_list,
-                    const uint64_t *host_offsets, const EfDevIn *dv) {
-    HostTrace tr("ef encode (lists)");
-    const uint64_t nlist = ep->nlist;
-    struct NoDelete { void operator()(vidc_ef *) const {} };
-    std::unique_ptr<vidc_ef, NoDelete> e(ep);
-    const uint64_t *offsets = host_offsets;
-    bool retry = false;
-    e->max_list = max_list;
-    tr.mark("offsets staged");
-    static const bool no_spec = std::getenv("VIDC_EF_NO_SPEC") != nullptr;  // (measurement switch: always size the streams after the geometry kernels)
-    bool respec = false;
-    const bool spec = !no_spec && e->ntotal && e->ntotal <= 0xffffffffull;
-    VIDC_TRY(ef_encode_fast(ctx, e.get(), d_ids, flags, nchunks, max_list, &retry, spec, &respec, dv));
-    if (respec) {  // the guess of the universe was too small: size the streams from the ids, and remember how large they are
-        e->d_recs.release();
-        e->recs_ready = false;
-        e->has_perm = false;
-        e->n_low = e->n_high = ~0ull;
-        VIDC_TRY(ef_encode_fast(ctx, e.get(), d_ids, flags, nchunks, max_list, &retry, false, &respec, dv));
-        std::vector<uint64_t> uni(nlist);
-        VIDC_HIP(hipMemcpy(uni.data(), e->d_universe.p, nlist * 8, hipMemcpyDeviceToHost));
-        for (uint64_t u : uni) ctx->ef_universe_hint = std::max(ctx->ef_universe_hint, u);
-    }
-    tr.mark("encode_fast (launches + wait)");
-    if (retry) {  // some list is not ascending: general three-pass encoder with the sort
-        if (offsets) {
-            e->offsets = vec_pool<uint64_t>().take(nlist + 1);
-            if (nlist) e->offsets.assign(offsets, offsets + nlist + 1);
-            else e->offsets.assign(1, 0);
-            e->offsets_host = true;
-        } else {
-            VIDC_TRY(ef_ensure_offsets(e.get()));  // (device offsets: the one copy of them to the host, on this slow path only)
-        }
-        e->n_low = e->n_high = ~0ull;
-        e->total_bits = 0;
-        e->has_perm = false;
-        e->recs_ready = false;  // (the general encoder's objects build their records on the first bulk decode)
-        e->d_recs.release();
-        VIDC_TRY(ef_encode_general(ctx, e.get(), d_ids, flags));
-    }
-    return VIDC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 // Device offsets (include/vidc.h): k_offsets_ingest copies them into the object, validates them and sums the chunk count and the
-// longest list, as the first kernel of ef_encode_fast; every buffer is sized from the bounds floor(ntotal / EF_CHUNK) + nlist chunks
+// longest list, as the first kernel of ef_enc_geometry; every buffer is sized from the bounds floor(ntotal / EF_CHUNK) + nlist chunks
 // and ntotal ids per list, and the chunk kernels take their count and form from the ingest's results on the device: one wait.
 int vidc_ef_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids,
                        uint32_t flags, vidc_ef **out) {
@@ -2359,7 +2353,7 @@ int vidc_ef_decode_all(vidc_ctx *ctx, const vidc_ef *e, uint64_t *d_out) {
             // (no batch holds more elements than its list) takes that bound: the records are built and used back to back,
             // without the read-back of the exact maximum and its synchronisation (S1-sized calls: two launches of ~5 + ~12 us
             // instead of fill + build + copy + wait + decode).  Large objects keep the exact value (occupancy of a 2 ms kernel).
-            const bool bounded = e->max_list && e->nbatches < EF_ENC_RECS_MAX;
+            const bool bounded = ef_recs_bounded(e->max_list, e->nbatches);
             VIDC_HIP(hipEventRecord(ctx->ev_chain[0], ctx->stream));
             Scratch s_mx;
             Pinned h_mx;
@@ -2380,7 +2374,7 @@ int vidc_ef_decode_all(vidc_ctx *ctx, const vidc_ef *e, uint64_t *d_out) {
                 // (the bound is written to the object only when the records are published, so a call that fails
                 // between here and its wait leaves the object as it found it; the lock is held for the ~20 us of a small object's
                 // first decode -- only objects below EF_ENC_RECS_MAX batches come this way)
-                pending_max_cnt = (uint32_t)std::min<uint64_t>(e->max_list, EF_BATCH_BITS);
+                pending_max_cnt = ef_recs_max_cnt(e->max_list);
                 publish_after_sync = true;
             } else {
                 VIDC_HIP(hipMemcpyAsync(h_mx.p, s_mx.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2396,21 +2390,11 @@ int vidc_ef_decode_all(vidc_ctx *ctx, const vidc_ef *e, uint64_t *d_out) {
     VIDC_HIP(t.start());
     if (e->nbatches) {
         const dim3 grid((uint32_t)std::min<uint64_t>(e->nbatches, (uint64_t)ctx->num_cu * 256));
-        const uint32_t max_cnt = publish_after_sync ? pending_max_cnt : e->recs_max_cnt;
-        const uint32_t lds = std::min<uint32_t>(EF_BATCH_BITS, (max_cnt + 63u) & ~63u) * 2;
-        const bool small = max_cnt <= 256;
-        if (e->narrow && small)
-            hipLaunchKernelGGL((k_ef_decode_rec<uint32_t, 4>), grid, dim3(64), lds, ctx->stream, e->d_low.p, e->d_high.p,
-                               e->d_recs.p, (uint32_t)e->nbatches, d_out);
-        else if (e->narrow)
-            hipLaunchKernelGGL((k_ef_decode_rec<uint32_t, 8>), grid, dim3(64), lds, ctx->stream, e->d_low.p, e->d_high.p,
-                               e->d_recs.p, (uint32_t)e->nbatches, d_out);
-        else if (small)
-            hipLaunchKernelGGL((k_ef_decode_rec<uint64_t, 4>), grid, dim3(64), lds, ctx->stream, e->d_low.p, e->d_high.p,
-                               e->d_recs.p, (uint32_t)e->nbatches, d_out);
-        else
-            hipLaunchKernelGGL((k_ef_decode_rec<uint64_t, 8>), grid, dim3(64), lds, ctx->stream, e->d_low.p, e->d_high.p,
-                               e->d_recs.p, (uint32_t)e->nbatches, d_out);
+        const EfDecodeForm f = ef_decode_form(e->narrow, publish_after_sync ? pending_max_cnt : e->recs_max_cnt);
+        auto kernel = f.elem_bytes == 4u ? (f.per_lane == 4u ? k_ef_decode_rec<uint32_t, 4> : k_ef_decode_rec<uint32_t, 8>)
+                                         : (f.per_lane == 4u ? k_ef_decode_rec<uint64_t, 4> : k_ef_decode_rec<uint64_t, 8>);
+        hipLaunchKernelGGL(kernel, grid, dim3(64), f.lds_bytes, ctx->stream, e->d_low.p, e->d_high.p, e->d_recs.p, (uint32_t)e->nbatches,
+                           d_out);
     }
     VIDC_HIP(hipGetLastError());
     VIDC_HIP(t.mark());
@@ -2798,11 +2782,11 @@ int vidc_ef_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const
         const uint64_t m = e->offsets[l + 1] - e->offsets[l];
         uint64_t lw = 0, hw = 0;
         if (m) {
-            const uint64_t hb = (m + 1) + (universe[l] >> lbits[l]) + 1;
-            e->high_nbits[l] = hb;
-            e->total_bits += m * lbits[l] + hb;
-            lw = (m * lbits[l] + 63) / 64 + 1;
-            hw = (hb + 63) / 64;
+            const EfGeom g = ef_list_geom(m, universe[l], lbits[l]);
+            e->high_nbits[l] = g.high_bits;
+            e->total_bits += m * lbits[l] + g.high_bits;
+            lw = g.low_words;
+            hw = g.high_words;
         }
         e->low_off[l + 1] = e->low_off[l] + lw;
         e->high_off[l + 1] = e->high_off[l] + hw;
