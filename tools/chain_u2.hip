@@ -160,11 +160,11 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
 #ifdef U2_PROF
     uint32_t prof[14]; CK(hipMemcpy(prof, d_prof, 56, hipMemcpyDeviceToHost));
     const char *names[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "fix-up chain .. v_mov k (12)", "add64, L1 cmp, 3 readlanes (5)", "bitmap valu, ff1, row read (8)",
-        "ds_write, slice 0 (8)", "L1 readlane.. L2 cmp, E1, ff1, entry (9)", "ds_read, slice 1, L2 readlane, division .. waitcnt (24)", "L3a valu: bcnt, dpp, cmp (10)",
+        "ds_write, slice 0 (8)", "L1 readlane.. L2 cmp, E1, ff1, entry (8)", "ds_read, slice 1, L2 readlane, division .. waitcnt (23)", "L3a valu: bcnt, dpp, cmp (8)",
         "L3a ff1, salu, 3 readlanes, sub (10)", "L3b: mbcnt, cmp, and, ff1, x (6)", "push 2 + order (7)", "row write-back (3)", "exit tests (7)"};
     const char *dnames[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "fix-up chain .. k readlane (11)", "L1 cmp, add64, 2 readlanes (5)", "ff1, row read (4)",
-        "slice 0, slice 1 (14)", "L1 readlane, mul_hi, k sub, L2 cmp, mad, E1, ff1, entry (12)", "2 ds_read, mad, L2 readlane, row update (9)", "k sub, shift mask (4)",
-        "add64, mad, waitcnt (4)", "slot / base read-out, mul, x, shift (8)", "push 2 + order (7)", "row write-back (3)", "exit tests (7)"};
+        "slice 0, slice 1 (14)", "L1 readlane, add, L2 cmp, mul_hi, ff1, entry (7)", "2 addresses, 2 ds_read, L2 readlane, counter updates (9)", "k sub, shift compare (2)",
+        "3 mad, mov, waitcnt (5)", "base + slot, address, x read-out, store, mul, sub (6)", "push 2 + order (7)", "row write-back (3)", "exit tests (6)"};
     if (narm == 3) for (int q = 0; q < 14; q++) names[q] = dnames[q];
     double tot = 0, pc = (double)prof[1] / n;
     for (int q = 0; q < 14; q++) { printf("  %-58s %8.1f  net %7.1f cycles/step\n", names[q], (double)prof[q] / n, (double)prof[q] / n - pc); tot += prof[q]; }

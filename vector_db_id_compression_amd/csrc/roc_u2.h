@@ -20,7 +20,7 @@
 //  * renormalisation is branch-free (s_cselect + unconditional ring write + stack-pointer add of the condition).
 //  * k_roc_encode_u2<20> keeps a list of 4097 .. 65 536 ids as dense blocks of 16 ids in POSITION space instead of the bitmap
 //    (U2Dense, U2_ENC_*_D below): the third search level, the bit select and the rewrite of the bitmap word become one LDS read
-//    by all lanes, one v_readlane and a masked 16-bit store (87 instructions per step against 106).  The kernel decides per list;
+//    by all lanes, one v_readlane and a 16-bit store by all lanes (79 instructions per step against 102).  The kernel decides per list;
 //    RocEncArgs::dense = 0 (VIDC_U2_DENSE=0) keeps every list on the bitmap body.
 //
 // Anything rare (index-pop renormalisation, stack underflow, nmax <= 2, ring spills) leaves the asm loop at a step
@@ -57,7 +57,10 @@ struct U2Dense {
     static constexpr uint32_t MAX_N = 65536u;             // 4096 blocks
     static constexpr uint32_t BASE_OFF = 16u;             // u32 base[4096]
     static constexpr uint32_t SLOT_OFF = BASE_OFF + 4096u * 4u;  // u16 slot[4096][16]
-    static constexpr uint32_t LDS_BYTES = SLOT_OFF + 4096u * 32u + 128u;
+    // behind the pad: a strip of one dword per lane.  The removal's ds_write_b16 runs in ALL lanes: a lane that shifts hits the slot
+    // below its own, every other lane its own dword of the strip (no exec write in the step, no two lanes on one address)
+    static constexpr uint32_t STRIP_OFF = SLOT_OFF + 4096u * 32u + 128u;
+    static constexpr uint32_t LDS_BYTES = STRIP_OFF + 256u;
 };
 // LDS bytes of a k_roc_encode_u2<UB, *> launch
 template <int UB>
@@ -235,8 +238,8 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
 //   v12 k     v13 row   v14 x_hi  v15 x_lo  v16 s  v17 q^  v18 r  v19 r - d  v20:21 {qf, 0}  v52 k per lane
 //   v22:23 bit mask  v24:25 new word  v26 its address  v27 tmp  v28 LDS address  v30:31 loaded word(s)  v58 tmp
 //   v32 popcount  v33 v34 prefix  v35 exclusive prefix  v49 mbcnt
-//   v36:37 {ph, 0}  v38:39 U  v40:41 {U.lo, 0}  v42:43 W  v44:45 Z  v46:47 q^ of B (per lane)  v48 r of B (per lane)
-//   v50:51 q = q^ + qf (per lane)           v64..v127 level-2 rows
+//   v36:37 {t, 0}  v38:39 P1  v40:41 {hi32(S), 0}  v42:43 S  v46:47 q^ of B (per lane)  v48 r of B (per lane)   (U2_DIV)
+//   v50:51 q = q^ + qf (per lane)           v64..v127 level-2 rows         v60 v61 v62 dense removal (see U2_ENC_TOP_D)
 //   s40 x      s41 mul    s42 k      s43 L1    s44 L2    s45 entry   s46 x base  s47 g     s48 b     s49 E1[L1]
 //   s50:51 q   s52:53 a   s54:55 A   s56:57 b  s58:59 B  s60 sp      s61 lo      s62 slot of the second push
 //   s63 row[L2]  s64 excl[g]  s65 word address  s66:67 word  s68 tmp  s69 t (lane of the current divisor)
@@ -259,14 +262,20 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
 #define U2P(i) ""
 #define U2P_OPERANDS
 #endif
+// q^ = hi64(B m) in five instructions; every encoder body carries the same five, spread over its windows.  P1 = b0 m1 + hi32(b0 m0)
+// goes into the second multiply-add WHOLE (S = b1 m0 + P1) and q^ = b1 m1 + hi32(S): the carry of S out of 64 bits is dropped.
+// It cannot occur in a lane that a step reads: the exit test keeps B < U2_SAFE_HI * 2^32 < 2^63 (b1 < 2^31), and lane t is read
+// only while s69 < s71 <= s70 = min(s86, 63) with s86 = D0 - 2, i.e. for a divisor d = D0 - t >= 3 (the lane moved at a block change
+// has d >= 2), so m < 2^63 (m1 < 2^31), b1 m0 < 2^63, P1 < 2^63 and S < 2^64.  Lanes past the list's end (divisor clamped to 1 in
+// U2_INSTALL, m = 2^64 - 1 or the table's zero entry) may wrap; their (v46:47, v48) are never read and never moved.
+// hi32(S) sits in an odd register and a 64-bit operand has to start at an even one, hence the v_mov (v41 stays 0 like v37).
+// The same data flow in plain C++: csrc/u2_div_ref.h (tests/u2_div_test.cpp checks it against unsigned __int128).
 #define U2_DIV \
     "v_mul_hi_u32 v36, s58, v7\n"                      /* B div d (all lanes): mulhi64(B, m) */ \
     "v_mad_u64_u32 v[38:39], s[78:79], s58, v8, v[36:37]\n" \
-    "v_mov_b32 v40, v38\n" \
-    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[40:41]\n" \
-    "v_add_co_u32_e64 v44, s[78:79], v39, v43\n" \
-    "v_addc_co_u32_e64 v45, s[80:81], 0, 0, s[78:79]\n" \
-    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[44:45]\n"
+    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[38:39]\n" \
+    "v_mov_b32 v40, v43\n" \
+    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[40:41]\n"
 #define U2_DIV_REM \
     "v_mul_lo_u32 v48, v46, v9\n" \
     "v_sub_u32 v48, s58, v48\n"                        /* r_B in [0, 2d) */
@@ -329,10 +338,9 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_addc_u32 s60, s60, 0\n" \
     "s_lshl_b64 s[54:55], s[52:53], s76\n" U2P(135) \
     "v_readlane_b32 s49, v4, s43\n" \
-    "v_subrev_u32 v27, s43, v2\n"                      /* lane - L1 */ \
+    "v_cndmask_b32_e64 v27, -1, 0, vcc\n"              /* -1 in the lanes below L1: the ones the level-1 compare left 0 */ \
     "v_subrev_u32 v12, s49, v12\n" \
     "v_cmp_le_u32 vcc, v13, v12\n"                     /* level 2 */ \
-    "v_ashrrev_i32 v27, 31, v27\n" \
     "v_add_u32 v4, v4, v27\n"                          /* E1 -= 1 in lanes below L1 */ \
     "s_ff1_i32_b64 s44, vcc\n" \
     "s_lshl_b32 s45, s43, 6\n" \
@@ -360,22 +368,19 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_xor_b32 s46, s45, " XORC "\n" \
     SHIFT                                              /* id bits of the entry */ \
     "v_readlane_b32 s63, v13, s44\n" \
-    "v_subrev_u32 v59, s44, v2\n"                      /* lane - L2 */ \
+    "v_cndmask_b32_e64 v59, -1, 0, vcc\n"              /* -1 in the lanes below L2: the ones the level-2 compare left 0 */ \
     "v_subrev_u32 v12, s63, v12\n" \
-    "v_mul_hi_u32 v36, s58, v7\n"                      /* B div d (all lanes): mulhi64(B, m) */ \
+    "v_mul_hi_u32 v36, s58, v7\n"                      /* B div d (all lanes): mulhi64(B, m), see U2_DIV */ \
     "v_mad_u64_u32 v[38:39], s[78:79], s58, v8, v[36:37]\n" \
-    "v_mov_b32 v40, v38\n" \
-    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[40:41]\n"
+    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[38:39]\n"
 
 #define U2_ENC_L3_G4 \
     "s_waitcnt lgkmcnt(0)\n" U2P(137) \
     "v_bcnt_u32_b32 v32, v30, 0\n" \
     "v_bcnt_u32_b32 v32, v31, v32\n" \
-    "v_add_co_u32_e64 v44, s[78:79], v39, v43\n" \
-    "v_addc_co_u32_e64 v45, s[80:81], 0, 0, s[78:79]\n" \
+    "v_mov_b32 v40, v43\n" \
     "v_add_u32_dpp v33, v32, v32 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
-    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[44:45]\n" \
-    "v_ashrrev_i32 v59, 31, v59\n" \
+    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[40:41]\n" \
     "v_add_u32_dpp v34, v33, v33 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
     "v_cmp_gt_u32 vcc, v34, v12\n"                     /* word of the entry */ \
     "v_sub_u32 v35, v34, v32\n" U2P(138) \
@@ -392,10 +397,8 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "v_subrev_u32 v12, s64, v12\n" U2P(139)
 #define U2_ENC_L3_G1 \
     "s_lshl_b32 s65, s45, 3\n" \
-    "v_add_co_u32_e64 v44, s[78:79], v39, v43\n" \
-    "v_addc_co_u32_e64 v45, s[80:81], 0, 0, s[78:79]\n" \
-    "v_ashrrev_i32 v59, 31, v59\n" \
-    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[44:45]\n" \
+    "v_mov_b32 v40, v43\n" \
+    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[40:41]\n" \
     "v_add_u32 v13, v13, v59\n" \
     "s_waitcnt lgkmcnt(0)\n" \
     "v_readfirstlane_b32 s66, v30\n" \
@@ -439,19 +442,29 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* (first instruction of the exit test, SCC = B >= 2^31: m0 settles meanwhile) */ \
     "v_writelane_b32 v6, s40, m0\n"
 
-// ---- the step on dense blocks (U2Dense): identical to the bitmap step up to level 2, with the rank k kept in s42 (v_cmp takes the
-// SGPR operand; the two subtractions sit behind the counter updates that fill their v_readlane windows).  Behind level 2 all 64
-// lanes read u16 slots from the block's first slot on (lane j holds slot j; lanes >= 16 read the following blocks or the pad), one
-// v_readlane at the remaining rank gives the slot, base + slot is x in s40 where the bitmap step leaves it.  The removal is a shift
-// inside the block: lanes k_rem < L <= 15 store their own value one slot down (v28 is the lane's slot address MINUS 2, the read adds
-// it back as an offset) while the v_readlane window of x runs.  LDS operations of one wavefront execute in order, so the next read
-// of the block sees the shift; slots behind a block's alive count hold stale values and are never selected.  Nothing is pending at
-// a step boundary (the bitmap step clears the previous id's bit at the top of the next one).
-// A scalar instruction issued within ~16 cycles of a v_readlane / v_cmp waits the window out, and the removed instructions were the
-// bitmap step's filler: both slices are therefore renormalised BEFORE level 2 (they depend on q alone), which frees the division of
-// B to start early, and its 16-cycle multiplies (v_mul_hi, v_mul_lo) and the counter updates sit behind the read-outs.
-//   v3 = 2 * lane - 2 + SLOT_OFF   v26 base address   v28 slot address - 2   v30 slots   v31 base   s46 base   s48 slot
-//   s42 k, then the rank inside the block   s[82:83] lanes of the shift
+// ---- the step on dense blocks (U2Dense), 79 instructions: the bitmap step's fix-up and level 1, with k kept in s42 (v_cmp takes
+// the SGPR operand) and the level-1 mask in s[82:83].  Level 2 compares k itself with E1[L1] + row (one v_add in all lanes instead
+// of a scalar subtraction between two read-outs); the v_readlane of that sum at L2 gives E1[L1] + row[L2], one s_sub the rank inside
+// the block.  Behind level 2 all 64 lanes read u16 slots from the block's first slot on (lane j holds slot j; lanes >= 16 read the
+// following blocks or the pad) and the block's first id (one dword, the same address in every lane); base + slot is added in every
+// lane and ONE v_readlane at the rank puts x into s40, where the bitmap step leaves it.
+// Counters: they are exclusive and stored in reversed lane order, so a level's compare is true exactly from the wanted lane upwards
+// and the lanes that lose 1 are the lanes its mask left 0: v_cndmask -1 / 0 from the mask and one v_add per level (the wanted lane
+// keeps its value, so the read-outs of E1[L1] and row[L2] may come before or after).
+// The removal is a shift inside the block: lanes k_rem < L <= 15 store their own value one slot down (v28 is the lane's slot
+// address MINUS 2, the read adds it back as an offset).  exec is not written: one v_cmp of the rank against v60 (the lane number in
+// lanes 1..15, 0 elsewhere) selects those lanes, a v_cndmask gives them the slot address and every other lane its own dword of the
+// strip behind the pad (v62), and the ds_write_b16 runs in all lanes.  Every address it can form is a slot of the block that was
+// read (bytes 2 (L - 1) of it, L <= 15) or lies in the strip: inside U2Dense::LDS_BYTES.  LDS operations of one wavefront execute
+// in order, so the next read of the block sees the shift; slots behind a block's alive count hold stale values and are never
+// selected.  Nothing is pending at a step boundary (the bitmap step clears the previous id's bit at the top of the next one).
+// A scalar instruction issued within ~16 cycles of a v_readlane / v_cmp / carry-writing instruction waits the window out: both
+// slices are renormalised BEFORE level 2 (they depend on q alone); v_mul_hi fills the window of the level-2 compare, the four counter
+// instructions the window of the level-2 read-out, the three v_mad_u64_u32 of the division (U2_DIV) run behind the removal's compare
+// in the shadow of the LDS reads, and v_mul_lo fills the window of x.  (profiles/r24_roc_encode_step.txt: what each change bought.)
+//   v3 = 2 * lane - 2 + SLOT_OFF   v26 base address   v27 E1[L1] + row   v28 slot address - 2   v30 slots   v31 base   v32 base + slots
+//   v59 -1 / 0 of a counter update   v60 lane number in lanes 1..15, else 0   v61 address of the removal's store   v62 STRIP_OFF + 4 * lane
+//   s42 k, then the rank inside the block   s63 E1[L1] + row[L2]   s[82:83] level-1 mask, then the lanes of the shift
 #define U2_ENC_TOP_D \
     U2P(130) U2P(131) \
     "v_lshrrev_b32_e64 v14, 16, s40\n"                 /* x_hi */ \
@@ -465,13 +478,13 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "v_ashrrev_i32 v27, 31, v19\n"                     /* -1 if r < d */ \
     "v_add3_u32 v20, v17, v27, 1\n"                    /* qf = q^ + (r >= d) */ \
     "v_readlane_b32 s42, v52, s69\n"                   /* k of the step */ U2P(132) \
-    "v_cmp_ge_u32 vcc, s42, v4\n"                      /* level 1 */ \
+    "v_cmp_ge_u32_e64 s[82:83], s42, v4\n"             /* level 1; the mask stays in s[82:83] for the update of E1 */ \
     "v_add_co_u32_e64 v50, s[78:79], v46, v20\n"       /* q = head div d (per lane) */ \
     "v_addc_co_u32_e64 v51, s[78:79], 0, v47, s[78:79]\n" \
     "v_readlane_b32 s50, v50, s69\n" \
     "v_readlane_b32 s51, v51, s69\n" \
     U2P(133) \
-    "s_ff1_i32_b64 s43, vcc\n" \
+    "s_ff1_i32_b64 s43, s[82:83]\n" \
     "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
     "v_mov_b32 v13, v64\n"                             /* row L1 */ \
     "s_set_gpr_idx_off\n" U2P(134) \
@@ -490,14 +503,9 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_addc_u32 s60, s60, 0\n" \
     "s_lshl_b64 s[58:59], s[56:57], s77\n"             /* B */ U2P(135) \
     "v_readlane_b32 s49, v4, s43\n" \
-    "v_mul_hi_u32 v36, s58, v7\n"                      /* B div d (all lanes): mulhi64(B, m); 16 cycles, the readlane's window */ \
-    "s_sub_u32 s42, s42, s49\n" \
-    "v_cmp_ge_u32 vcc, s42, v13\n"                     /* level 2 */ \
-    "v_mad_u64_u32 v[38:39], s[78:79], s58, v8, v[36:37]\n" \
-    "v_subrev_u32 v27, s43, v2\n"                      /* lane - L1 */ \
-    "v_ashrrev_i32 v27, 31, v27\n" \
-    "v_add_u32 v4, v4, v27\n"                          /* E1 -= 1 in lanes below L1 */ \
-    "v_mov_b32 v40, v38\n" \
+    "v_add_u32 v27, s49, v13\n"                        /* E1[L1] + row: level 2 compares k itself, no scalar subtraction in between */ \
+    "v_cmp_ge_u32 vcc, s42, v27\n"                     /* level 2 */ \
+    "v_mul_hi_u32 v36, s58, v7\n"                      /* B div d (all lanes): mulhi64(B, m), see U2_DIV; 16 cycles, the compare's window */ \
     "s_ff1_i32_b64 s44, vcc\n" \
     "s_lshl_b32 s45, s43, 6\n" \
     "s_or_b32 s45, s45, s44\n" U2P(136)
@@ -506,28 +514,25 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "v_lshlrev_b32_e64 v26, 2, s45\n" \
     "ds_read_u16 v30, v28 offset:2\n" \
     "ds_read_b32 v31, v26 offset:16\n"                 /* (U2Dense::BASE_OFF) */ \
-    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[40:41]\n" \
-    "v_readlane_b32 s63, v13, s44\n" \
-    "v_subrev_u32 v59, s44, v2\n"                      /* lane - L2 */ \
-    "v_ashrrev_i32 v59, 31, v59\n" \
-    "v_add_u32 v13, v13, v59\n"                        /* row -= 1 in lanes below L2 */ U2P(137) \
+    "v_readlane_b32 s63, v27, s44\n"                   /* E1[L1] + row[L2] */ \
+    "v_cndmask_b32_e64 v59, -1, 0, vcc\n"              /* the lanes below L2 are the lanes the level-2 compare left 0 */ \
+    "v_add_u32 v13, v13, v59\n"                        /* row -= 1 there */ \
+    "v_cndmask_b32_e64 v59, -1, 0, s[82:83]\n"         /* likewise level 1 */ \
+    "v_add_u32 v4, v4, v59\n"                          /* E1 -= 1 in lanes below L1 */ U2P(137) \
     "s_sub_u32 s42, s42, s63\n"                        /* rank inside the block */ \
-    "s_sub_u32 s68, 15, s42\n"                         /* removal mask: lanes k_rem < L <= 15 */ \
-    "s_add_u32 s72, s42, 1\n" \
-    "s_bfm_b64 s[82:83], s68, s72\n" U2P(138) \
-    "v_add_co_u32_e64 v44, s[78:79], v39, v43\n" \
-    "v_addc_co_u32_e64 v45, s[80:81], 0, 0, s[78:79]\n" \
-    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[44:45]\n" \
+    "v_cmp_lt_u32_e64 s[82:83], s42, v60\n"            /* removal: lanes k_rem < L <= 15 (v60 = L in lanes 1..15, 0 elsewhere) */ U2P(138) \
+    "v_mad_u64_u32 v[38:39], s[78:79], s58, v8, v[36:37]\n" \
+    "v_mad_u64_u32 v[42:43], s[78:79], s59, v7, v[38:39]\n" \
+    "v_mov_b32 v40, v43\n" \
+    "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[40:41]\n" \
     "s_waitcnt lgkmcnt(0)\n" U2P(139)
 #define U2_ENC_BOT_D(ORDER, LSHR, RING, TAIL) \
-    "v_readlane_b32 s48, v30, s42\n"                   /* the slot */ \
-    "v_readfirstlane_b32 s46, v31\n"                   /* the block's first id */ \
-    "v_mul_lo_u32 v48, v46, v9\n"                      /* (16 cycles: the window of the two read-outs) */ \
-    "v_sub_u32 v48, s58, v48\n"                        /* r_B in [0, 2d) */ \
-    "s_add_u32 s40, s46, s48\n"                        /* x */ \
-    "s_mov_b64 exec, s[82:83]\n"                       /* removal: the alive slots behind k_rem move one slot down */ \
-    "ds_write_b16 v28, v30\n" \
-    "s_mov_b64 exec, -1\n" U2P(140) \
+    "v_add_u32 v32, v30, v31\n"                        /* every lane: the block's first id + its slot */ \
+    "v_cndmask_b32_e64 v61, v62, v28, s[82:83]\n"      /* the slot below, or the lane's own dword of the strip */ \
+    "v_readlane_b32 s40, v32, s42\n"                   /* x */ \
+    "ds_write_b16 v61, v30\n"                          /* removal: the alive slots behind k_rem move one slot down (all lanes store) */ \
+    "v_mul_lo_u32 v48, v46, v9\n"                      /* (16 cycles: the window of the read-out) */ \
+    "v_sub_u32 v48, s58, v48\n"                        /* r_B in [0, 2d) */ U2P(140) \
     "s_mov_b32 m0, s62\n" \
     "s_and_b32 s68, s40, 0xffff\n" \
     "s_or_b32 s68, s68, s54\n" \
@@ -707,6 +712,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
     uint32_t *order = WANT_ORDER ? a.perm + off : nullptr;  // sampled ids; k_perm_from_order turns them into positions
     const uint32_t T0 = 0x80000000u >> p0, T1 = 0x80000000u >> p1, MULN = 1u << p1;
     const uint32_t l3off = dense ? 2u * lane + (U2Dense::SLOT_OFF - 2u) : U::G == 4u ? (lane & 3u) * 8u : 0u;
+    // dense removal: the lanes that can shift (1 .. 15) compare the rank with their own number, and every lane owns a dword of the strip
+    const uint32_t rmlane = lane - 1u < 15u ? lane : 0u, strip = U2Dense::STRIP_OFF + 4u * lane;
 
 #ifdef U2_PROF
     uint32_t prof[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -749,10 +756,10 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
               "+{s61}"(st.lo), "+{s65}"(s_waddr), "+{s[66:67]}"(s_w), "+{s69}"(s_t), "+{s85}"(s_D0), "+{s86}"(s_left),       \
               "+{s87}"(obase), "+{s93}"(st.err), "+{v[20:21]}"(z0), "+{v[36:37]}"(z1), "+{v[40:41]}"(z2) U2P_OPERANDS       \
             : "{v2}"(lane), "{v3}"(l3off), "{s73}"(T0), "{s74}"(T1), "{s75}"(MULN), "{s76}"(p0), "{s77}"(p1),                \
-              "{s[88:89]}"(order), "{s[90:91]}"(st.mem), "{s92}"(st.cap), "{s[94:95]}"(dtab)                                \
+              "{s[88:89]}"(order), "{s[90:91]}"(st.mem), "{s92}"(st.cap), "{s[94:95]}"(dtab), "{v60}"(rmlane), "{v62}"(strip) \
             : "memory", "vcc", "scc", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",  \
               "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v38", "v39",\
-              "v42", "v43", "v44", "v45", "v49", "v50", "v51", "v52", "v54", "v55", "v56", "v57", "v58", "v59",                     \
+              "v42", "v43", "v44", "v45", "v49", "v50", "v51", "v52", "v54", "v55", "v56", "v57", "v58", "v59", "v61",              \
               "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57",\
               "s62", "s63", "s64", "s68", "s70", "s71", "s72", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s96",       \
               "s97", "s98", "s99")
@@ -874,10 +881,9 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
     "s_addc_u32 s60, s60, 0\n" \
     "s_lshl_b64 s[54:55], s[52:53], s76\n" \
     "v_readlane_b32 s49, v4, s43\n" \
-    "v_subrev_u32 v27, s43, v2\n"                      /* lane - L1 */ \
+    "v_cndmask_b32_e64 v27, -1, 0, vcc\n"              /* -1 in the lanes below L1: the ones the level-1 compare left 0 */ \
     "v_subrev_u32 v12, s49, v12\n" \
     "v_cmp_le_u32 vcc, v13, v12\n"                     /* level 2 */ \
-    "v_ashrrev_i32 v27, 31, v27\n" \
     "v_add_u32 v4, v4, v27\n"                          /* E1 -= 1 in lanes below L1 */ \
     "s_ff1_i32_b64 s44, vcc\n" \
     "s_lshl_b32 s45, s43, 6\n" \
