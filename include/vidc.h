@@ -422,6 +422,49 @@ int vidc_wt_append_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n_add, const in
 int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int precision_mode, uint32_t flags, vidc_roc **out, int64_t *d_labels, uint64_t *d_invalid);
 
+/* ---------------------------------------------------- remove (batches of pairs, device-resident) */
+/* Objects stay immutable: a remove returns a NEW object in *out, the old one stays valid and unchanged, and either may be destroyed
+ * first (the new object owns all of its memory).
+ *
+ * The batch.  Pair i is (d_list_nos[i], d_ids[i]); n_rm < 2^32 - 1.  d_list_nos chooses the mode:
+ *   Pairs mode (d_list_nos != NULL): an entry of list l is removed iff some pair has that list number and an id equal to the entry's
+ *     id.  A negative list number is skipped and not counted; a list number >= nlist is skipped and counted in *d_invalid.
+ *   Any-list mode (d_list_nos == NULL): an entry of ANY list is removed iff its id equals some d_ids[i] -- Faiss's remove_ids over an
+ *     IDSelectorBatch.
+ *   Equality is over all 64 bits of what the old object decodes to.  Every copy of a matching id inside a list goes; repeated pairs are
+ *   harmless.  A valid pair that matches no entry adds one to *d_missing -- in pairs mode that includes an id that sits in another
+ *   list, and everywhere an id wider than the object can hold (>= 2^32 for ROC, >= 2^bits for packed bits); a repeated pair is judged
+ *   like its first copy.  d_missing and d_invalid are device uint64 the caller zeroes; either may be NULL.
+ * The result.  With old_l = list l of the old object in the object's own order (what vidc_*_decode_lists returns) and S_l = old_l
+ *   without the removed entries, order kept, the new object is the one the existing encoder builds from the CSR form of S, word for
+ *   word (streams, per-list metadata, sizes, compressed_bytes, and the permutation when the flag asks for it, which is over positions
+ *   in S_l): vidc_packed_encode with the object's own width, vidc_ef_encode with `flags`, vidc_roc_encode with `precision_mode` and
+ *   `flags` (the caller passes the mode the object was built with; the call cannot check it).  A ROC list that loses no entry keeps
+ *   its stream and gets the identity permutation: that is the from-scratch result whenever the list decodes to its own distinct ids
+ *   (not for the reference's lossy cases -- duplicates, a power-of-two maximum under VIDC_PREC_REFERENCE, more than 65 536 ids).
+ *   Lists may become empty, and so may the object.  n_rm == 0, or a batch that matches nothing, returns an object equal to the old one.
+ * d_removed (device uint8[ntotal_old], may be NULL): every byte is written -- 1 where the entry at that position of the old object's
+ *   decode_all order was removed, 0 elsewhere.  A caller that keeps per-entry payload (the vector codes) drops the same rows.
+ * Arrays are device arrays on the context's device, read and written in order on the context's stream.
+ * Status.  NULL context, object or out, NULL d_ids with n_rm > 0, n_rm >= 2^32 - 1, a bad precision_mode: VIDC_ERR_INVALID before any
+ *   device work.  A graph object (rows, Elias-Fano arena): VIDC_ERR_UNSUPPORTED.  On any error *out == NULL, the old object is
+ *   untouched and the context stays usable.
+ * Residency.  No id payload crosses PCIe (vidc_ctx_d2h_bytes does not move).  The batch is sorted by (list, id) on the device; every
+ *   decoded entry binary-searches its list's run, and the survivors are placed by a scan of per-chunk kill counts: no atomic decides
+ *   a position, the result is the same on every run.  Packed bits and Elias-Fano are REBUILT: decode_all into scratch, the mark, the
+ *   compaction, the device-offsets encoder; one 8-byte read-back (the survivor count).  ROC is SPLICED: the candidates -- the
+ *   non-empty lists a valid pair names; in any-list mode EVERY non-empty list, which decodes the whole object -- are decoded and
+ *   marked (their numbers are read back once, 4 bytes each); only the lists that lose an entry are re-encoded (their numbers and
+ *   survivor counts are read back, 8 bytes per touched list); every other list's stream is copied.  The calls synchronise;
+ *   vidc_ctx_last_kernel_ms is the sum over the call's kernels.
+ * There is no wavelet-tree form (a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks) and no sharded one. */
+int vidc_packed_remove_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
+                           vidc_packed **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
+int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
+                       uint32_t flags, vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
+int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
+                        int precision_mode, uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
+
 /* ---------------------------------------------- sharded lists (several contexts, one process) */
 /* One CSR set of lists cut into shards, one codec object per shard, each built and served through its own context: the container of a
  * process that drives all of its GPUs itself (a Faiss process and its OpenMP loops, custom_invlists_impl.cpp:147,508-525), where

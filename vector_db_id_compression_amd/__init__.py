@@ -7,5 +7,6 @@ C-ABI (include/vidc.h); this package is the thin Python host side mirroring the 
 from . import _lib  # noqa: F401
 from ._lib import VIDC_PREC_EXACT, VIDC_PREC_REFERENCE, VidcError  # noqa: F401
 from . import persist  # noqa: F401,E402  (save / load of every container: flat .npz images)
+from . import removal  # noqa: F401,E402  (removal of (list, id) batches from the list containers)
 
-__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist"]
+__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal"]

@@ -243,42 +243,68 @@ inline int append_check(const ::vidc_ctx *ctx, const Obj *obj, Obj **out, uint64
     return VIDC_OK;
 }
 
+// The stable LSD sort of n pairs (n > 0): two key and two value buffers of n words each, and where the sort stands -- kin / vin are the
+// keys and the pair numbers in the current order (vin == NULL: the identity, nothing sorted yet).
+struct AppSort {
+    uint32_t n = 0;
+    uint32_t *kb[2] = {nullptr, nullptr}, *vb[2] = {nullptr, nullptr};
+    const uint32_t *kin = nullptr, *vin = nullptr;
+};
+inline int app_sort_scratch(::vidc_ctx *ctx, const AppSort &s, Scratch &s_hist, Scratch &s_scan) {
+    const uint32_t ntiles = (s.n + APP_TILE - 1u) / APP_TILE;
+    VIDC_TRY(s_hist.get(ctx, (size_t)ntiles * 256 * 4));
+    VIDC_TRY(s_scan.get(ctx, ((size_t)ntiles * 256 + 1) * 8));
+    return VIDC_OK;
+}
+// One phase: gather(kdst, vin) enqueues the kernel that writes the phase's 32-bit keys in the current order (position p holds the key of
+// pair vin[p]), then `bits` key bits are sorted, 8 per pass, at least one pass.  The order of earlier phases survives inside equal keys:
+// phases run from the least significant key to the most significant one.
+template <typename Gather>
+inline int app_sort_phase(::vidc_ctx *ctx, AppSort &s, uint32_t bits, Scratch &s_hist, Scratch &s_scan, Scratch &s_tmp, Gather &&gather) {
+    const uint32_t n = s.n, ntiles = (n + APP_TILE - 1u) / APP_TILE;
+    gather(s.kb[0], s.vin);
+    VIDC_HIP(hipGetLastError());
+    s.kin = s.kb[0];
+    uint32_t *kout = s.kb[1], *vout = s.vin == s.vb[0] ? s.vb[1] : s.vb[0];
+    const dim3 grid(std::min<uint32_t>(ntiles, (uint32_t)ctx->num_cu * 32u));
+    for (uint32_t shift = 0; shift == 0 || shift < bits; shift += 8u) {
+        hipLaunchKernelGGL(k_app_hist, grid, dim3(64), 0, ctx->stream, s.kin, n, shift, ntiles, s_hist.as<uint32_t>());
+        VIDC_TRY(device_exscan(ctx, s_hist.as<uint32_t>(), ntiles * 256u, s_scan.as<uint64_t>(), s_tmp));
+        hipLaunchKernelGGL(k_app_scatter, grid, dim3(64), 0, ctx->stream, s.kin, s.vin, n, shift, ntiles, s_scan.as<uint64_t>(), kout, vout);
+        VIDC_HIP(hipGetLastError());
+        s.kin = kout;
+        s.vin = vout;
+        kout = kout == s.kb[1] ? s.kb[0] : s.kb[1];
+        vout = vout == s.vb[0] ? s.vb[1] : s.vb[0];
+    }
+    return VIDC_OK;
+}
+
 // steps 1-3 (header).  Ends with the call's read-back of the valid pair count: synchronises.
 inline int append_sort_batch(::vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_old_off, uint64_t n_add, const int64_t *d_list_nos,
                              uint64_t *d_invalid, AppendBatch &b) {
     b.n_add = n_add;
     b.nlist = nlist;
     const uint32_t n = (uint32_t)n_add;
-    const uint32_t ntiles = (n + APP_TILE - 1u) / APP_TILE;
     VIDC_TRY(b.s_sort.get(ctx, ((size_t)n * 4 + 4) * 4));
     VIDC_TRY(b.s_off.get(ctx, 2 * (nlist + 1) * 8));
     VIDC_TRY(b.h_back.get(ctx, 64));
-    uint32_t *k0 = b.s_sort.as<uint32_t>(), *k1 = k0 + n, *v0 = k1 + n, *v1 = v0 + n;
+    AppSort s;
+    s.n = n;
+    s.kb[0] = b.s_sort.as<uint32_t>(); s.kb[1] = s.kb[0] + n; s.vb[0] = s.kb[1] + n; s.vb[1] = s.vb[0] + n;
+    s.kin = s.kb[0];
     b.add_off = b.s_off.as<uint64_t>();
     b.new_off = b.add_off + nlist + 1;
-    const uint32_t *kin = k0, *vin = nullptr;
     if (n) {
-        VIDC_TRY(b.s_hist.get(ctx, (size_t)ntiles * 256 * 4));
-        VIDC_TRY(b.s_scan.get(ctx, ((size_t)ntiles * 256 + 1) * 8));
-        hipLaunchKernelGGL(k_app_keys, req_grid(ctx, n), dim3(256), 0, ctx->stream, d_list_nos, n_add, nlist, k0, (unsigned long long *)d_invalid);
-        VIDC_HIP(hipGetLastError());
+        VIDC_TRY(app_sort_scratch(ctx, s, b.s_hist, b.s_scan));
         uint32_t bits = 0;
         while (bits < 32u && (nlist >> bits)) bits++;  // keys are 0 .. nlist
-        uint32_t *kout = k1, *vout = v0;
-        const dim3 grid(std::min<uint32_t>(ntiles, (uint32_t)ctx->num_cu * 32u));
-        for (uint32_t shift = 0; shift == 0 || shift < bits; shift += 8u) {
-            hipLaunchKernelGGL(k_app_hist, grid, dim3(64), 0, ctx->stream, kin, n, shift, ntiles, b.s_hist.as<uint32_t>());
-            VIDC_TRY(device_exscan(ctx, b.s_hist.as<uint32_t>(), ntiles * 256u, b.s_scan.as<uint64_t>(), b.s_tmp));
-            hipLaunchKernelGGL(k_app_scatter, grid, dim3(64), 0, ctx->stream, kin, vin, n, shift, ntiles, b.s_scan.as<uint64_t>(), kout, vout);
-            VIDC_HIP(hipGetLastError());
-            kin = kout;
-            vin = vout;
-            kout = kout == k1 ? k0 : k1;
-            vout = vout == v0 ? v1 : v0;
-        }
+        VIDC_TRY(app_sort_phase(ctx, s, bits, b.s_hist, b.s_scan, b.s_tmp, [&](uint32_t *kdst, const uint32_t *) {
+            hipLaunchKernelGGL(k_app_keys, req_grid(ctx, n), dim3(256), 0, ctx->stream, d_list_nos, n_add, nlist, kdst, (unsigned long long *)d_invalid);
+        }));
     }
-    b.keys = kin;
-    b.vals = vin;
+    b.keys = s.kin;
+    b.vals = s.vin;
     hipLaunchKernelGGL(k_app_bounds, req_grid(ctx, nlist + 1), dim3(256), 0, ctx->stream, b.keys, n, d_old_off, nlist, b.add_off, b.new_off);
     VIDC_HIP(hipGetLastError());
     uint64_t *h = b.h_back.as<uint64_t>();

@@ -15,6 +15,7 @@
 #include "bits.h"
 #include "chunks.h"
 #include "append.h"
+#include "remove.h"
 #include "common.h"
 #include "dev_offsets.h"
 #include "ef_plan.h"
@@ -2694,6 +2695,21 @@ int vidc_ef_append_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_add, const in
         if (!(flags & VIDC_EF_WANT_PERM)) { ne->d_perm.release(); ne->has_perm = false; }
     }
     *out = ne;
+    return VIDC_OK;
+}
+
+// Remove (include/vidc.h): decode_all into scratch, the shared mark and compaction (remove.h), the device-offsets encoder on the
+// surviving CSR.  The survivors of an ascending list are ascending: the encoder stays on its sorted path.
+int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags,
+                       vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+    VIDC_TRY(remove_check(ctx, e, out, n_rm, d_ids));
+    if (e->rows || e->arena) { set_error("elias-fano remove: graph objects hold no removable lists"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    RemoveRebuilt m;
+    VIDC_TRY(remove_rebuild(ctx, e->nlist, e->ntotal, e->d_offsets.p, n_rm, d_list_nos, d_ids, 64u, d_removed, d_missing, d_invalid, m,
+                            [&](uint64_t *d) { return vidc_ef_decode_all(ctx, e, d); }));
+    VIDC_TRY(vidc_ef_encode_dev(ctx, e->nlist, m.new_off, m.ntotal_new, m.s_out.as<uint64_t>(), flags, out));
+    ctx->last_kernel_ms += m.kernel_ms;
     return VIDC_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "append.h"
+#include "remove.h"
 #include "common.h"
 #include "host_call.h"
 #include "roc_dec_plan.h"
@@ -1642,6 +1643,49 @@ __global__ void __launch_bounds__(256) k_app_roc_perm(const uint64_t *__restrict
     }
 }
 
+// ---- remove (vidc_roc_remove_dev): the candidates are decoded and marked, the lists that lose an entry are re-encoded, the rest is
+// spliced.  flag[l] = list l is a candidate -- non-empty and (run_off != NULL) named by a pair of the batch; mark[l] = its ids.
+__global__ void __launch_bounds__(256) k_rm_roc_cand(const uint64_t *__restrict__ old_off, const uint64_t *__restrict__ run_off, uint64_t nlist,
+                                                     uint32_t *__restrict__ mark, uint32_t *__restrict__ flag) {
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t n = old_off[l + 1] - old_off[l];
+        const bool c = n != 0 && (!run_off || run_off[l + 1] != run_off[l]);
+        flag[l] = c ? 1u : 0u;
+        mark[l] = c ? (uint32_t)n : 0u;
+    }
+}
+// candidate k (seg_off: where it was decoded to, new_off: the offsets of its survivors) is touched when it lost an entry:
+// tflag[k], tmark[k] = its survivor count (0 for an untouched candidate)
+__global__ void __launch_bounds__(256) k_rm_roc_kills(const uint64_t *__restrict__ seg_off, const uint64_t *__restrict__ new_off, uint64_t cnt,
+                                                      uint32_t *__restrict__ tflag, uint32_t *__restrict__ tmark) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < cnt; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t n = seg_off[k + 1] - seg_off[k], left = new_off[k + 1] - new_off[k];
+        tflag[k] = left != n ? 1u : 0u;
+        tmark[k] = left != n ? (uint32_t)left : 0u;
+    }
+}
+// t_cand[tpos[k]] = k, t_left[tpos[k]] = survivors, for every touched candidate, ascending; and for the splice lflag[l] = 1,
+// ltpos[l] = tpos[k] of its list l = cand[k] (lflag zeroed by the caller)
+__global__ void __launch_bounds__(256) k_rm_roc_touched(const uint32_t *__restrict__ tflag, const uint32_t *__restrict__ tmark,
+                                                        const uint64_t *__restrict__ tpos, const uint32_t *__restrict__ cand, uint64_t cnt,
+                                                        uint32_t *__restrict__ t_cand, uint32_t *__restrict__ t_left, uint32_t *__restrict__ lflag,
+                                                        uint64_t *__restrict__ ltpos) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < cnt; k += (uint64_t)gridDim.x * blockDim.x)
+        if (tflag[k]) {
+            t_cand[tpos[k]] = (uint32_t)k;
+            t_left[tpos[k]] = tmark[k];
+            lflag[cand[k]] = 1u;
+            ltpos[cand[k]] = tpos[k];
+        }
+}
+// sizes of the spliced object's lists: the small object's for a touched list, the old one's otherwise
+__global__ void __launch_bounds__(256) k_rm_roc_sizes(const uint32_t *__restrict__ lflag, const uint64_t *__restrict__ ltpos,
+                                                      const uint64_t *__restrict__ old_off, const uint64_t *__restrict__ small_off, uint64_t nlist,
+                                                      uint32_t *__restrict__ sizes) {
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x)
+        sizes[l] = (uint32_t)(lflag[l] ? small_off[ltpos[l] + 1] - small_off[ltpos[l]] : old_off[l + 1] - old_off[l]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2187,6 +2231,224 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
     }
     kernel_ms += tm.stop();
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    ctx->last_kernel_ms = kernel_ms;
+    tr.mark("spliced");
+    *out = nr.release();
+    return VIDC_OK;
+}
+
+// Remove (include/vidc.h).  The batch is sorted by (list, id) on the device (remove.h).  The candidates -- the non-empty lists a valid
+// pair names, or every non-empty list in any-list mode -- are compacted there and their numbers come back once (4 bytes per
+// candidate, metadata); the host sizes a staging CSR, the candidates are decoded into it (plan_decode / decode_impl on the subset)
+// and marked.  The candidates that lost an entry are the touched lists: their staging numbers and survivor counts come back (8 bytes
+// per touched list), their survivors are compacted into a second staging CSR and encode_impl runs on that alone.  The splice is the
+// append's: metadata from the small object or the old one, the scan of the word counts, a segmented copy of every list's words.
+int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
+                        uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+    VIDC_TRY(remove_check(ctx, r, out, n_rm, d_ids));
+    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
+        set_error("roc remove: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
+        return VIDC_ERR_INVALID;
+    }
+    if (r->rows) { set_error("roc remove: graph objects hold no removable lists"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc remove");
+    const uint64_t nlist = r->nlist;
+    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
+    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    double kernel_ms = 0;
+    RemoveBatch b;
+    RemoveMarked mk;
+    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_t2, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids, s_slot, s_sizes;
+    Pinned h_back, h_seg;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
+    EventTimer tm = EventTimer::started(ctx);
+    VIDC_TRY(remove_sort_batch(ctx, nlist, n_rm, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
+    if (d_removed && r->ntotal) VIDC_HIP(hipMemsetAsync(d_removed, 0, r->ntotal, ctx->stream));
+    // the candidates
+    VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
+    VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
+    VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
+    uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
+    uint64_t *stage_off = s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
+    uint32_t *d_cand = s_cand.as<uint32_t>();
+    VIDC_TRY(h_back.get(ctx, 32 + (nlist + 1) * 8));
+    uint64_t *h_cnt = h_back.as<uint64_t>();
+    uint32_t *h_a = (uint32_t *)(h_cnt + 4), *h_b = h_a + nlist + 1;
+    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
+    if (nlist && n_rm) {  // (an empty batch has no candidate, in either mode)
+        hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p,
+                           b.any ? (const uint64_t *)nullptr : b.run_off, nlist, mark, flag);
+        Scan4 sc{};
+        sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
+        hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    const uint64_t cnt = h_cnt[0];
+    std::vector<uint32_t> cand(cnt);
+    VIDC_TRY(h_seg.get(ctx, (cnt + 1) * 8));
+    uint64_t *seg_off = h_seg.as<uint64_t>();
+    seg_off[0] = 0;
+    if (cnt) {
+        VIDC_HIP(hipMemcpyAsync(h_a, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        for (uint64_t k = 0; k < cnt; k++) {
+            cand[k] = h_a[k];
+            seg_off[k + 1] = seg_off[k] + (r->offsets[cand[k] + 1] - r->offsets[cand[k]]);
+        }
+    }
+    const uint64_t total = seg_off[cnt];
+    tr.mark("batch sorted, candidates read back");
+    // decode and mark the candidates; the touched ones
+    uint64_t T = 0, ttotal = 0, killed = 0;
+    std::vector<uint64_t> ts_off(1, 0);
+    std::vector<uint32_t> t_list;  // list numbers of the touched lists, ascending
+    VIDC_TRY(s_lf.get(ctx, (nlist + 1) * 4));
+    VIDC_TRY(s_lt.get(ctx, (nlist + 1) * 8));
+    uint32_t *lflag = s_lf.as<uint32_t>();
+    uint64_t *ltpos = s_lt.as<uint64_t>();
+    VIDC_HIP(hipMemsetAsync(lflag, 0, (nlist + 1) * 4, ctx->stream));
+    if (cnt) {
+        VIDC_TRY(s_stage.get(ctx, total * 8));
+        VIDC_TRY(s_rm.get(ctx, total));
+        VIDC_TRY(s_seg.get(ctx, (cnt + 1) * 8));
+        VIDC_HIP(hipMemcpyAsync(s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        {
+            PooledDecPlan p;
+            plan_decode(r, cand, false, p, ctx->wide);
+            std::vector<uint64_t> out_off(cnt);
+            for (size_t k = 0; k < cnt; k++) out_off[k] = seg_off[p.item[k]];  // work item k -> its place in the staging
+            VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+            kernel_ms += ctx->last_kernel_ms;
+        }
+        tr.mark("candidates decoded");
+        (void)tm.start();
+        VIDC_TRY(remove_mark(ctx, b, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), d_cand, cnt, total, s_rm.as<uint8_t>(), d_removed,
+                             (const uint64_t *)r->d_offsets.p, d_missing, mk));
+        VIDC_TRY(s_tf.get(ctx, 2 * (cnt + 1) * 4));  // tflag | tmark
+        VIDC_TRY(s_tp.get(ctx, 2 * (cnt + 1) * 8));  // tpos | tdst
+        VIDC_TRY(s_tl.get(ctx, 2 * (cnt + 1) * 4));  // t_cand | t_left
+        uint32_t *tflag = s_tf.as<uint32_t>(), *tmark = tflag + cnt + 1;
+        uint64_t *tpos = s_tp.as<uint64_t>(), *tdst = tpos + cnt + 1;
+        uint32_t *t_cand = s_tl.as<uint32_t>(), *t_left = t_cand + cnt + 1;
+        hipLaunchKernelGGL(k_rm_roc_kills, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint64_t *)s_seg.as<uint64_t>(),
+                           (const uint64_t *)mk.new_off, cnt, tflag, tmark);
+        Scan4 sc{};
+        sc.in[0] = tflag; sc.in[1] = tmark; sc.out[0] = tpos; sc.out[1] = tdst;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)cnt, s_t1));
+        hipLaunchKernelGGL(k_rm_roc_touched, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint32_t *)tflag, (const uint32_t *)tmark,
+                           (const uint64_t *)tpos, (const uint32_t *)d_cand, cnt, t_cand, t_left, lflag, ltpos);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, tpos + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, mk.new_off + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        kernel_ms += tm.stop();
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        T = h_cnt[1];
+        killed = total - h_cnt[2];
+        if (T) {
+            VIDC_HIP(hipMemcpyAsync(h_a, t_cand, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+            VIDC_HIP(hipMemcpyAsync(h_b, t_left, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+            ts_off.resize(T + 1);
+            t_list.resize(T);
+            for (uint64_t t = 0; t < T; t++) {
+                t_list[t] = cand[h_a[t]];
+                ts_off[t + 1] = ts_off[t] + h_b[t];
+            }
+            ttotal = ts_off[T];
+            VIDC_TRY(s_small_ids.get(ctx, (ttotal ? ttotal : 1) * 8));
+            (void)tm.start();
+            VIDC_TRY(remove_compact(ctx, mk, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), s_rm.as<uint8_t>(), tdst, tflag, s_small_ids.as<uint64_t>()));
+            kernel_ms += tm.stop();
+        }
+    }
+    (void)tm.start();
+    VIDC_TRY(remove_count_missing(ctx, b, d_missing));
+    kernel_ms += tm.stop();
+    tr.mark("candidates marked, touched lists read back");
+    std::unique_ptr<vidc_roc> small;
+    if (T) {
+        vidc_roc *sp = nullptr;
+        VIDC_TRY(encode_impl(ctx, T, ts_off.data(), s_small_ids.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
+                             want_perm ? VIDC_ROC_WANT_PERM : 0u, &sp));
+        small.reset(sp);
+        kernel_ms += ctx->last_kernel_ms;
+    }
+    tr.mark("touched lists encoded");
+    // the new object: host offsets, then the append's splice
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = ctx->device;
+    nr->nlist = nlist;
+    nr->ntotal = r->ntotal - killed;
+    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
+    nr->offsets.resize(nlist + 1);
+    uint64_t nonempty = 0;
+    {
+        uint64_t gone = 0, t = 0;
+        for (uint64_t l = 0; l < nlist; l++) {
+            nr->offsets[l] = r->offsets[l] - gone;
+            if (t < T && t_list[t] == l) { gone += (r->offsets[l + 1] - r->offsets[l]) - (ts_off[t + 1] - ts_off[t]); t++; }
+            nonempty += r->offsets[l + 1] - gone != nr->offsets[l];
+        }
+        nr->offsets[nlist] = r->offsets[nlist] - gone;
+    }
+    nr->offsets_host = true;
+    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(s_slot.get(ctx, (nlist + 1) * 4));
+    VIDC_TRY(s_sizes.get(ctx, (nlist + 1) * 4));
+    (void)tm.start();
+    if (nlist) {
+        if (small) {
+            hipLaunchKernelGGL(k_rm_roc_sizes, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos,
+                               (const uint64_t *)r->d_offsets.p, (const uint64_t *)small->d_offsets.p, nlist, s_sizes.as<uint32_t>());
+            VIDC_TRY(device_exscan(ctx, s_sizes.as<uint32_t>(), (uint32_t)nlist, nr->d_offsets.p, s_t2));
+        } else {
+            VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, r->d_offsets.p, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};
+        const RocMeta m_small = small ? RocMeta{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p} : m_old;
+        hipLaunchKernelGGL(k_app_roc_meta, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos, nlist,
+                           m_old, m_small, nr->d_heads.p, nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_slot.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+        VIDC_TRY(device_exscan(ctx, nr->d_nwords.p, (uint32_t)nlist, nr->d_word_off.p, s_t1));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 3, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+        h_cnt[3] = 0;
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_cnt[3];
+    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
+    AppChunks ch_w, ch_p;
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, ch_w));
+        hipLaunchKernelGGL((k_app_copy<uint32_t, true>), app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, (const uint32_t *)r->d_words.p,
+                           (const uint64_t *)r->d_word_off.p, small ? (const uint32_t *)small->d_words.p : nullptr,
+                           small ? (const uint64_t *)small->d_word_off.p : nullptr, (const uint32_t *)s_slot.as<uint32_t>(),
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
+        VIDC_HIP(hipGetLastError());
+    }
+    if (want_perm && nr->ntotal) {
+        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, ch_p));
+        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
+                           (const uint32_t *)s_slot.as<uint32_t>(), small ? (const uint32_t *)small->d_perm.p : nullptr,
+                           small ? (const uint64_t *)small->d_offsets.p : nullptr, ch_p.items, ch_p.n_items, nr->d_perm.p);
+        VIDC_HIP(hipGetLastError());
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
     tr.mark("spliced");
     *out = nr.release();

@@ -126,6 +126,52 @@ class InvertedListsArrayCodes:
         self._refresh_sizes()
         return labels
 
+    # -- shrinkage: the counterpart of add_batch.  The compressed ids go through the codec's remove (vidc_*_remove_dev).
+    _reorders = False  # the container keeps its codes in the order of the codec's permutation (ROC: sampling order)
+
+    def remove_batch(self, list_nos, ids):
+        """Remove a batch: entry of list l leaves iff (l, id) is a pair of the batch; list_nos=None removes the ids from every list
+        (Faiss's remove_ids over an IDSelectorBatch).  list_nos int64 [n] (negative = skipped), ids int64 [n]; CUDA tensors (numpy
+        arrays are uploaded).  A new codec object replaces `self._c`, codes_all loses the same rows on the device (and follows the
+        new permutation of the lists the codec re-ordered), and the size attributes become what a fresh container over the
+        surviving lists reports -- packed bits keeps its width: the surviving ids still need it.  Returns the number removed."""
+        from . import removal
+
+        torch = _torch()
+        as_dev = lambda x, dt: (torch.from_numpy(np.ascontiguousarray(x)).cuda() if isinstance(x, np.ndarray) else x).to(dt).reshape(-1)
+        di = as_dev(ids, torch.int64).contiguous()
+        ln = None if list_nos is None else as_dev(list_nos, torch.int64).contiguous()
+        if ln is not None and ln.numel() != di.numel():
+            raise ValueError("list_nos and ids must have one entry per pair")
+        invalid = torch.zeros(1, dtype=torch.int64, device=di.device)
+        want = self._reorders and self.code_size > 0
+        new_c, mask = removal.remove(self._c, ln, di, want_perm=want or self._keeps_perm(), invalid=invalid)
+        if int(invalid.item()):
+            raise _lib.VidcError(f"remove_batch: {int(invalid.item())} list numbers are >= nlist = {self.nlist}")
+        gone = torch.cat([mask.new_zeros(1, dtype=torch.int64), torch.cumsum(mask.to(torch.int64), 0)])
+        n_removed = int(gone[-1].item())
+        if not n_removed:
+            return 0
+        old_off = torch.from_numpy(self._offsets.astype(np.int64)).to(di.device)
+        new_off = old_off - gone[old_off]
+        if self.code_size:
+            codes = self.codes_all[mask == 0]
+            if want:  # position q of list l holds survivor perm[q] of that list
+                sizes = new_off[1:] - new_off[:-1]
+                base = torch.repeat_interleave(new_off[:-1], sizes)
+                codes = codes[base + torch.from_numpy(new_c.perm().astype(np.int64)).to(di.device)]
+            self.codes_all = codes
+        self._c = new_c
+        self._offsets = new_off.cpu().numpy().astype(np.uint64)
+        self.ntotal -= n_removed
+        self._n_removed = getattr(self, "_n_removed", 0) + n_removed
+        self._refresh_sizes()
+        return n_removed
+
+    def _keeps_perm(self):
+        """whether a fresh constructor keeps the codec's permutation (the new object then does as well)"""
+        return False
+
     # -- batched helpers shared by the subclasses
     def get_single_id(self, list_no, offset):
         return int(self.get_single_ids([list_no], [offset])[0])
@@ -171,7 +217,8 @@ class CompressedIDInvertedListsPackedBits(InvertedListsArrayCodes):
 
     def _append_ids(self, list_nos, ids, invalid):
         # the width a fresh container takes for the grown index (:68-70); an id that does not fit it fails as the constructor does (:87)
-        ntotal_new = self.ntotal + int((list_nos >= 0).sum().item())
+        # (ids handed out after a removal continue from the number of vectors ever added: the width covers those)
+        ntotal_new = self.ntotal + getattr(self, "_n_removed", 0) + int((list_nos >= 0).sum().item())
         new_c, labels = self._c.append(list_nos, ids, bits=PackedLists.bits_for(ntotal_new), invalid=invalid)
         return new_c, labels, None
 
@@ -204,6 +251,8 @@ class CompressedIDInvertedListsFenwickTree(InvertedListsArrayCodes):
         # the reference adds the size of ALL code arrays once per non-empty list (:203-205, accidental O(nlist^2))
         nonempty = int(np.count_nonzero(self._offsets[1:] > self._offsets[:-1]))
         self.codes_size_in_bytes = nonempty * self.ntotal * self.code_size
+
+    _reorders = True
 
     def _append_ids(self, list_nos, ids, invalid):
         want = self.code_size > 0
@@ -240,6 +289,9 @@ class CompressedIDInvertedListsEliasFano(InvertedListsArrayCodes):
         nonempty = int(np.count_nonzero(self._offsets[1:] > self._offsets[:-1]))
         self.codes_size_in_bytes = nonempty * self.ntotal * self.code_size
 
+    def _keeps_perm(self):
+        return self.code_size > 0  # (the survivors of an ascending list are ascending: the permutation is the identity)
+
     def _append_ids(self, list_nos, ids, invalid):
         want = self.code_size > 0
         new_c, labels = self._c.append(list_nos, ids, want_perm=want, invalid=invalid)
@@ -273,6 +325,9 @@ class CompressedIDInvertedListsWaveletTree(InvertedListsArrayCodes):
     def _append_ids(self, list_nos, ids, invalid):
         new_c, labels = self._c.append(list_nos, ids, invalid=invalid)
         return new_c, labels, None
+
+    def remove_batch(self, list_nos, ids):
+        raise RuntimeError("not implemented: a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks")
 
     def get_ids_all(self):
         return self._c.decode_all()

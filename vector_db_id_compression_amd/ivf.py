@@ -59,6 +59,7 @@ class IVFIndex:
         self.code_size = 4 * self.d if code == "Flat" else self.M
         self.invlists = ArrayInvertedLists(self.nlist, self.code_size)
         self.ntotal = 0
+        self._next_id = 0  # vectors ever added: ids handed out by add never repeat, also after remove_ids
         self._dev = None
 
     # -- build
@@ -92,14 +93,15 @@ class IVFIndex:
         xb = torch.as_tensor(np.asarray(xb, dtype=np.float32)).cuda()
         if hasattr(self.invlists, "add_batch"):  # a compressed container: assignments, ids and codes stay on the device
             n = xb.shape[0]
-            ids = torch.arange(self.ntotal, self.ntotal + n, dtype=torch.int64, device=xb.device)
+            ids = torch.arange(self._next_id, self._next_id + n, dtype=torch.int64, device=xb.device)
             self.invlists.add_batch(_assign(xb, self.centroids), ids, self._encode_dev(xb))
             self.ntotal += n
+            self._next_id += n
             self._dev = None
             return
         assign = _assign(xb, self.centroids).cpu().numpy()
         codes = self._encode(xb)
-        ids = np.arange(self.ntotal, self.ntotal + xb.shape[0], dtype=np.int64)
+        ids = np.arange(self._next_id, self._next_id + xb.shape[0], dtype=np.int64)
         order = np.argsort(assign, kind="stable")
         bounds = np.searchsorted(assign[order], np.arange(self.nlist + 1))
         for l in range(self.nlist):
@@ -107,7 +109,27 @@ class IVFIndex:
             if sel.size:
                 self.invlists.add_entries(l, ids[sel], codes[sel])
         self.ntotal += xb.shape[0]
+        self._next_id += xb.shape[0]
         self._dev = None
+
+    def remove_ids(self, ids):
+        """IndexIVF::remove_ids over an IDSelectorBatch: every entry whose id is in `ids` leaves its list -> the number removed.
+        A compressed container removes on the device (remove_batch, any-list mode); ArrayInvertedLists is filtered on the host."""
+        il = self.invlists
+        if hasattr(il, "remove_batch"):
+            n = il.remove_batch(None, ids)
+        elif isinstance(il, ArrayInvertedLists):
+            sel = np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids, dtype=np.int64).reshape(-1)
+            n = 0
+            for l in range(il.nlist):
+                keep = ~np.isin(il._ids[l], sel)
+                n += int(keep.size - keep.sum())
+                il._ids[l], il._codes[l] = il._ids[l][keep], il._codes[l][keep]
+        else:
+            raise RuntimeError("remove_ids: the inverted lists are read-only")
+        self.ntotal -= n
+        self._dev = None
+        return n
 
     def replace_invlists(self, il, own=False):
         self.invlists = il
