@@ -3,7 +3,7 @@
 //
 // The reference delegates to sdsl::wt_int (not in the reference tree, "parity unpinned" for its size and
 // internal layout); what is reproduced here is the data structure itself and the select semantics:
-//   L = bit_width(nlist - 1) levels; level l holds one bit per id (bit L-1-l of the symbol) in the order
+//   L = max(1, bit_width(nlist - 1)) levels; level l holds one bit per id (bit L-1-l of the symbol) in the order
 //   obtained by stable-sorting the ids by the top l bits of their symbol (pointerless / levelwise layout);
 //   every level has a rank directory (ones before each 512-bit block).
 // select walks the levels bottom-up with one rank and one select per level.  Everything is built and
@@ -29,6 +29,7 @@
 #include "host_call.h"
 #include "requests.h"
 #include "scan.h"
+#include "wt_plan.h"
 
 using namespace vidc;
 using namespace vidc::dev;
@@ -63,9 +64,6 @@ struct vidc_wt {
 };
 
 namespace {
-
-constexpr uint32_t BLK_WORDS = 8;  // 512-bit rank blocks
-__host__ __device__ inline uint64_t wt_nrank_base(uint32_t level) { return ((uint64_t)1 << level) - 1u + level; }  // sum of (2^j + 1), j < level
 
 // list_nos[id] = list number; validates the reference's asserts (ids ascending inside a list, < ntotal).
 // A workgroup takes 4096 consecutive positions: two searches of the whole offset table find the lists of its first and last position,
@@ -112,13 +110,7 @@ __global__ void k_wt_check_syms(const uint32_t *syms, uint64_t ntotal, uint32_t 
 // not from a search per position), then one workgroup
 // per bucket places its pairs in a 64 KiB LDS image of the bucket's 16 384 ids and writes the image out with 16-byte stores; a slot nobody
 // wrote is found on the way (k_wt_check_syms and the 0xff fill of the array are not needed).
-#define VIDC_WTP_BSH 14u
-#define VIDC_WTP_BUCKET (1u << VIDC_WTP_BSH)
-#define VIDC_WTP_MAXB 1024u  // buckets
-#define VIDC_WTP_NBLK 1024u  // workgroups of the two passes over the positions (16 384 positions each at 16.8 M ids)
-__host__ __device__ inline uint64_t wtp_chunk(uint64_t ntotal) {  // positions per workgroup: whole 4096-position tiles
-    return ((ntotal + VIDC_WTP_NBLK - 1u) / VIDC_WTP_NBLK + 4095u) & ~4095ull;
-}
+// (VIDC_WTP_*, wtp_chunk: wt_plan.h)
 __global__ void __launch_bounds__(256) k_wt_part_hist(const uint64_t *__restrict__ ids, uint64_t ntotal, uint32_t *__restrict__ part) {
     __shared__ uint32_t h[VIDC_WTP_MAXB];
     for (uint32_t k = threadIdx.x; k < VIDC_WTP_MAXB; k += 256u) h[k] = 0u;
@@ -307,8 +299,7 @@ __global__ void __launch_bounds__(256) k_wt_part_place(const uint32_t *__restric
 // its inclusive prefix; a successor adds counts until it meets a prefix; tiles take their numbers from a counter in start order, so every
 // wait ends), and an element's slot in the next level follows from its rank and from tables that need only the symbol start table C: the
 // ones before every node start (k_wt_node_ranks_from_C, all levels in one launch before the first pass).
-#define VIDC_WT_EPT 64u                    // elements per thread
-#define VIDC_WT_TILE (256u * VIDC_WT_EPT)  // 16 384 positions = 256 bit-vector words = 32 rank blocks per workgroup
+// (VIDC_WT_EPT elements per thread, tiles of VIDC_WT_TILE positions: wt_plan.h)
 struct WtScanState {  // per tile: bit 63 = inclusive prefix, bit 62 = the tile's own count; 0 = nothing yet.  [ntiles] | ticket
     unsigned long long v;
 };
@@ -321,7 +312,6 @@ struct WtScanState {  // per tile: bit 63 = inclusive prefix, bit 62 = the tile'
 // (coalesced, independent loads: redundant work, 128 loads per thread at most for a 65 536-list tree) and then scans its run 256 nodes
 // per trip.  One workgroup per level -- 64 trips for the last level, or a run of 128 nodes per thread with every access 2 KiB from its
 // neighbour's -- kept the whole last level on ONE CU's address unit: 92-98 us whatever the loop looked like.
-#define VIDC_WT_NR_G 16u
 __global__ void __launch_bounds__(256) k_wt_node_ranks_from_C(const uint64_t *__restrict__ C, uint32_t nlist, uint32_t L, uint32_t *__restrict__ nrank,
                                                               uint32_t *__restrict__ dstab) {
     __shared__ uint64_t wsum[4];
@@ -598,7 +588,6 @@ struct WtPlainView {
     }
 };
 
-constexpr uint32_t RRR_B = 63, RRR_K = 32;
 struct RrrTab { uint8_t ow[64]; };  // offset width of class c: ceil(log2 C(63, c))
 
 // index of the 63-bit word v (c ones) among the words with c ones: sum over its ones (ascending, i = 1..c) of C(p_i, i)
@@ -929,35 +918,6 @@ __global__ void k_wt_decode_lists(View vw, const uint64_t *C, const uint32_t *__
     }
 }
 
-// get_ids for every list (custom_invlists_impl.cpp:381-392 loops get_single_id)
-template <class View>
-__global__ void k_wt_decode_all(View vw, const uint64_t *C, const uint32_t *__restrict__ nrank, uint32_t nlist, uint32_t L, uint64_t ntotal,
-                                uint64_t *out) {
-    __shared__ uint64_t s_binom[View::kRrrView ? 64 * 64 : 1];
-    __shared__ uint8_t s_ow[64];
-    wt_stage_tables(vw, s_binom, s_ow);
-    const uint32_t nlist_ = nlist;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ntotal; g += stride) {
-        const uint32_t c = find_list(C, nlist, g);
-        uint64_t pos = g - C[c];
-        for (int level = (int)L - 1; level >= 0; level--) {
-            const uint32_t sh = L - (uint32_t)level;
-            const uint64_t p = sh >= 32 ? 0 : (uint64_t)(c >> sh);
-            const uint64_t ns = C[sh >= 32 ? 0 : (p << sh)];
-            uint64_t s_hi = sh >= 32 ? nlist_ : ((p + 1) << sh);
-            if (s_hi > nlist_) s_hi = nlist_;
-            const uint64_t ne = C[s_hi];
-            const bool bit = (c >> (L - 1u - (uint32_t)level)) & 1u;
-            auto bv = vw.level((uint32_t)level);
-            wt_use_tables(bv, s_binom, s_ow);
-            const uint64_t r_ns = nrank[wt_nrank_base((uint32_t)level) + p];
-            pos = bv.select_in((bit ? r_ns : ns - r_ns) + pos, bit, ns, ne) - ns;
-        }
-        out[g] = pos;
-    }
-}
-
 // get_ids for every list as L stable partitions of the id sequence (the build's own passes, run on ids instead of
 // symbols): at level l the element at position i of node p goes to the zeros / ones part of its node, one rank per
 // element instead of the select (binary search over the rank directory + word scan) the per-id walk needs per level.
@@ -965,33 +925,11 @@ __global__ void k_wt_decode_all(View vw, const uint64_t *C, const uint32_t *__re
 struct WtItem {
     uint32_t id, pref;
 };
-template <bool LAST, class Bv>
-__global__ void k_wt_decode_level(const WtItem *in, WtItem *out, uint64_t *out_ids, Bv bv, const uint64_t *C,
-                                  const uint32_t *__restrict__ nrank_level, uint64_t ntotal, uint32_t nlist, uint32_t L, uint32_t level) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint32_t sh = L - level;  // symbols of one node share their top `level` bits
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ntotal; i += stride) {
-        const WtItem it = in ? in[i] : WtItem{(uint32_t)i, 0u};
-        const uint64_t p = it.pref;
-        uint64_t s_lo = sh >= 32 ? 0 : (p << sh), s_hi = sh >= 32 ? nlist : ((p + 1) << sh);
-        if (s_lo > nlist) s_lo = nlist;
-        if (s_hi > nlist) s_hi = nlist;
-        const uint64_t ns = C[s_lo], ne = C[s_hi];
-        bool bit;
-        // (ones before the node and before the next one: from the build's table -- one rank per element instead of three)
-        const uint64_t r_ns = nrank_level[p], r_ne = nrank_level[p + 1], r_i = bv.rank_1_bit(i, bit);
-        const uint64_t zeros_in_node = (ne - ns) - (r_ne - r_ns);
-        const uint64_t dst = bit ? ns + zeros_in_node + (r_i - r_ns) : ns + ((i - ns) - (r_i - r_ns));
-        if (LAST) out_ids[dst] = it.id;
-        else out[dst] = WtItem{it.id, (uint32_t)((p << 1) | (bit ? 1u : 0u))};
-    }
-}
 
-// The same pass over tiles of 8192 consecutive positions (round 6): the tile's 128 bit-vector words and 16 rank-directory entries give
-// every position its bit and rank (v_mbcnt inside the word) -- the per-element form above asked the rank directory and up to eight words
+// The pass over tiles of 8192 consecutive positions (round 6): the tile's 128 bit-vector words and 16 rank-directory entries give
+// every position its bit and rank (v_mbcnt inside the word) -- a per-element form asked the rank directory and up to eight words
 // per element --, the destination is one table entry (d_dstab) plus that rank, and all of a thread's 32 items are requested before any
 // of them is used.
-#define VIDC_WTD_EPT 32u
 template <bool LAST>
 __global__ void __launch_bounds__(256) k_wt_decode_tile(const WtItem *__restrict__ in, WtItem *__restrict__ out, uint64_t *__restrict__ out_ids,
                                                         const uint64_t *__restrict__ bits, uint64_t nwords, const uint32_t *__restrict__ rank,
@@ -1172,128 +1110,191 @@ static int wt_rrr_tables(vidc_ctx *ctx, vidc_wt *w, const RrrTab &tab) {
         bn[n * 64] = 1;
         for (int k = 1; k <= n; k++) bn[n * 64 + k] = (n ? bn[(n - 1) * 64 + k - 1] : 0) + (k <= n - 1 ? bn[(n - 1) * 64 + k] : 0);
     }
-    VIDC_TRY(w->d_binom.alloc(64 * 64 + 8));
     VIDC_HIP(hipMemcpyAsync(w->d_binom.p, bn.data(), 64 * 64 * 8, hipMemcpyHostToDevice, ctx->stream));
     VIDC_HIP(hipMemcpyAsync(w->d_binom.p + 64 * 64, tab.ow, 64, hipMemcpyHostToDevice, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (bn leaves scope)
     return VIDC_OK;
 }
 
+// ---- shared by build and import.  What they decide is wt_plan.h's; the stages below only queue it.
+// the object of a geometry: its fields and every device array the geometry sizes (the offset streams follow their bit counts:
+// wt_set_offset_streams)
+static int wt_object_alloc(vidc_ctx *ctx, vidc_wt *w, uint64_t nlist, const WtGeom &g) {
+    w->device = ctx->device;
+    w->nlist = nlist; w->ntotal = g.ntotal;
+    w->wt_type = g.wt_type; w->L = g.L;
+    w->words_per_level = g.words_per_level; w->blocks_per_level = g.blocks_per_level;
+    if (g.wt_type == 1) {
+        w->rrr_nblk = g.nblk; w->rrr_nsamp = g.nsamp; w->rrr_cls_wpl = g.cls_wpl;
+        w->rrr_off_base.assign(g.L + 1, 0);
+    }
+    VIDC_TRY(w->d_C.alloc(g.C_n));
+    VIDC_TRY(w->d_nrank.alloc(g.nrank_n));
+    VIDC_TRY(w->d_dstab.alloc(g.dstab_n));
+    VIDC_TRY(w->d_bits.alloc(g.bits_n));
+    VIDC_TRY(w->d_rank.alloc(g.rank_n));
+    VIDC_TRY(w->d_cls.alloc(g.cls_n));
+    VIDC_TRY(w->d_ptr.alloc(g.samp_n));
+    VIDC_TRY(w->d_rs.alloc(g.samp_n));
+    VIDC_TRY(w->d_binom.alloc(g.binom_n));
+    return VIDC_OK;
+}
+static WtGeom wt_geom_of(const vidc_wt *w) { return wt_geom(w->nlist, w->ntotal, w->wt_type); }
+// wt_type 1: the exact-size offset streams, level after level
+static int wt_set_offset_streams(vidc_wt *w, const WtGeom &g, const uint64_t *off_bits) {
+    w->rrr_off_bits.assign(off_bits, off_bits + g.L);
+    w->rrr_off_base = wt_off_base(g, off_bits);
+    return w->d_offs.alloc(w->rrr_off_base[g.L]);
+}
+// the ones before every node start of every level and the partition tables, from the symbol start table alone (d_nrank is cleared
+// by the caller, where each call always queued that: the build in front of its timed region, the import inside)
+static int wt_queue_node_tables(vidc_ctx *ctx, vidc_wt *w, const WtGeom &g) {
+    hipLaunchKernelGGL(k_wt_node_ranks_from_C, dim3(wt_nr_grid(g)), dim3(256), 0, ctx->stream, w->d_C.p, (uint32_t)w->nlist, g.L, w->d_nrank.p,
+                       w->d_dstab.p);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
+// ---- build: the stages wt_build_begin .. wt_build_finish over one WtBuildCall
 // offsets: host array (vidc_wt_build), or NULL and d_offsets + ntotal (vidc_wt_build_dev: copied into d_C and validated by
 // k_offsets_ingest, whose summary is read at the build's wait for the verdict on the ids, before any level is built)
-static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_offsets, uint64_t ntotal,
-                         const uint64_t *d_ids, int wt_type, vidc_wt **out) {
-    if (!ctx || !out || (nlist && !offsets && !d_offsets) || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
-    *out = nullptr;
-    if (nlist == 0 || nlist >= 0xffffffffull) { set_error("wavelet tree needs 1 <= nlist < 2^32"); return VIDC_ERR_INVALID; }
-    VIDC_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<vidc_wt> w(new vidc_wt());
-    w->device = ctx->device;
-    w->nlist = nlist;
-    w->wt_type = wt_type;
-    if (offsets) {
-        w->offsets.assign(offsets, offsets + nlist + 1);
-        w->ntotal = offsets[nlist];
-    } else {
-        w->offsets_host = false;
-        w->ntotal = ntotal;
+struct WtBuildIn {
+    vidc_ctx *ctx;
+    uint64_t nlist;
+    const uint64_t *offsets, *d_offsets;
+    uint64_t ntotal;  // (device offsets)
+    const uint64_t *d_ids;
+    int wt_type;
+    WtBuildPolicy pol;
+};
+struct WtBuildCall : WtBuildIn {
+    explicit WtBuildCall(const WtBuildIn &in) : WtBuildIn(in), t(in.ctx) {}
+    std::unique_ptr<vidc_wt> w;  // the object under construction
+    WtGeom g{};
+    WtBuildPlan plan;
+    RrrTab tab;
+    Pinned h_dsum;  // device offsets: the ingest's summary
+    Scratch s_a, s_b, s_err, s_lvl_bits, s_lvl_rank, s_width, s_bitpos, s_scan, s_offs_tmp, s_part, s_state;
+    EventTimer t;
+    uint32_t *cur = nullptr, *nxt = nullptr;  // the level's order and the next one's
+    std::vector<uint64_t> lvl_bits;           // wt_type 1: bits of every level's offset stream
+    bool rrr() const { return g.wt_type == 1; }  // (keeps one level of plain bits at a time, scratch, and the RRR coding of every level)
+};
+
+static int wt_build_shape(uint64_t nlist, uint64_t ntotal, int wt_type) {
+    switch (wt_shape_check(nlist, ntotal, wt_type)) {
+    case WT_SHAPE_OK: return VIDC_OK;
+    case WT_SHAPE_TYPE: return VIDC_ERR_INVALID;
+    case WT_SHAPE_NLIST: set_error("wavelet tree needs 1 <= nlist < 2^32"); return VIDC_ERR_INVALID;
+    default: set_error("wavelet tree: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED;
     }
-    if (w->ntotal && !d_ids && !offsets) return VIDC_ERR_INVALID;
-    if (w->ntotal >= 0xffffffffull) { set_error("wavelet tree: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED; }
-    uint32_t L = 1;
-    while ((1ull << L) < nlist) L++;
-    w->L = L;
-    const uint64_t nt = w->ntotal;
-    w->words_per_level = (nt + 63) / 64 + 1;
-    w->blocks_per_level = (w->words_per_level + BLK_WORDS - 1) / BLK_WORDS;
-    VIDC_TRY(w->d_C.alloc(nlist + 1));
-    Pinned h_dsum;
-    if (offsets) {
-        VIDC_HIP(hipMemcpyAsync(w->d_C.p, w->offsets.data(), (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        unsigned long long *acc = nullptr;
-        VIDC_TRY(doff_block(ctx, &acc));
-        VIDC_TRY(h_dsum.get(ctx, sizeof(DevOffSummary)));
-        h_dsum.as<DevOffSummary>()->done = 0;
-        hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(nlist)), dim3(256), 0, ctx->stream, d_offsets, w->d_C.p, nlist, w->ntotal, 0u,
-                           0u, ~0ull, acc, acc + DOFF_NACC, h_dsum.as<DevOffSummary>());
-        VIDC_HIP(hipGetLastError());
+}
+
+// checks, geometry and plan, the object and its arrays
+static int wt_build_begin(WtBuildCall &c) {
+    VIDC_TRY(wt_build_shape(c.nlist, 0, c.wt_type));  // (nlist first: ntotal is read behind nlist offsets)
+    VIDC_HIP(hipSetDevice(c.ctx->device));
+    const uint64_t nt = c.offsets ? c.offsets[c.nlist] : c.ntotal;
+    if (nt && !c.d_ids && !c.offsets) return VIDC_ERR_INVALID;
+    VIDC_TRY(wt_build_shape(c.nlist, nt, c.wt_type));
+    c.g = wt_geom(c.nlist, nt, c.wt_type);
+    c.plan = wt_build_plan(c.g, c.nlist, c.pol);
+    c.w.reset(new vidc_wt());
+    if (c.offsets) c.w->offsets.assign(c.offsets, c.offsets + c.nlist + 1);
+    else c.w->offsets_host = false;
+    if (c.rrr()) c.tab = rrr_tab();
+    c.lvl_bits.assign(c.g.L, 0);
+    return wt_object_alloc(c.ctx, c.w.get(), c.nlist, c.g);
+}
+
+// the symbol start table: copied from the host, or ingested from the device
+static int wt_build_ingest_offsets(WtBuildCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    if (c.offsets) {
+        VIDC_HIP(hipMemcpyAsync(w->d_C.p, w->offsets.data(), c.g.C_n * 8, hipMemcpyHostToDevice, ctx->stream));
+        return VIDC_OK;
     }
-    // wt_type 1 keeps one level of plain bits at a time (scratch) and the RRR coding of every level
-    const bool rrr = wt_type == 1;
-    if (rrr && L > 32) { set_error("wavelet tree: more than 32 levels"); return VIDC_ERR_UNSUPPORTED; }
-    Scratch s_a, s_b, s_err, s_lvl_bits, s_lvl_rank, s_width, s_bitpos, s_scan, s_offs_tmp;
-    const uint64_t nblk = (nt + RRR_B - 1) / RRR_B, nsamp = (nblk + RRR_K - 1) / RRR_K;
-    const RrrTab tab = rrr_tab();
-    if (!rrr) {
-        VIDC_TRY(w->d_bits.alloc(L * w->words_per_level));
-        VIDC_TRY(w->d_rank.alloc(L * (w->blocks_per_level + 1)));
-        VIDC_HIP(hipMemsetAsync(w->d_bits.p, 0, L * w->words_per_level * 8, ctx->stream));
+    unsigned long long *acc = nullptr;
+    VIDC_TRY(doff_block(ctx, &acc));
+    VIDC_TRY(c.h_dsum.get(ctx, sizeof(DevOffSummary)));
+    c.h_dsum.as<DevOffSummary>()->done = 0;
+    hipLaunchKernelGGL(k_offsets_ingest, dim3(doff_grid(c.nlist)), dim3(256), 0, ctx->stream, c.d_offsets, w->d_C.p, c.nlist, w->ntotal, 0u,
+                       0u, ~0ull, acc, acc + DOFF_NACC, c.h_dsum.as<DevOffSummary>());
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
+// the scratch of the call; what has to be zero is cleared, the RRR tables go up
+static int wt_build_alloc(WtBuildCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    const WtBuildPlan &pl = c.plan;
+    if (!c.rrr()) {
+        VIDC_HIP(hipMemsetAsync(w->d_bits.p, 0, c.g.bits_n * 8, ctx->stream));
     } else {
-        w->rrr_nblk = nblk; w->rrr_nsamp = nsamp;
-        w->rrr_cls_wpl = 6 * nsamp + 2;  // 192 bits per sample of 32 blocks (whole samples: select_in reads a sample's six words), even: 8-byte loads
-        VIDC_TRY(w->d_cls.alloc(L * w->rrr_cls_wpl));
-        VIDC_TRY(w->d_ptr.alloc(L * (nsamp + 1)));
-        VIDC_TRY(w->d_rs.alloc(L * (nsamp + 1)));
-        VIDC_HIP(hipMemsetAsync(w->d_cls.p, 0, L * w->rrr_cls_wpl * 4, ctx->stream));
-        VIDC_TRY(s_lvl_bits.get(ctx, w->words_per_level * 8));
-        VIDC_TRY(s_lvl_rank.get(ctx, (w->blocks_per_level + 1) * 4));
-        VIDC_TRY(s_width.get(ctx, (nblk + 1) * 4));
-        VIDC_TRY(s_bitpos.get(ctx, (nblk + 1) * 8));
-        // worst case of a level's offset stream: 61 bits per block (transient; the object keeps the exact size)
-        VIDC_TRY(s_offs_tmp.get(ctx, (size_t)L * (w->words_per_level + 1) * 8));
-        VIDC_HIP(hipMemsetAsync(s_offs_tmp.p, 0, (size_t)L * (w->words_per_level + 1) * 8, ctx->stream));
-        VIDC_TRY(wt_rrr_tables(ctx, w.get(), tab));
-        w->rrr_off_base.assign(L + 1, 0);
+        VIDC_HIP(hipMemsetAsync(w->d_cls.p, 0, c.g.cls_n * 4, ctx->stream));
+        VIDC_TRY(c.s_lvl_bits.get(ctx, pl.lvl_bits_n * 8));
+        VIDC_TRY(c.s_lvl_rank.get(ctx, pl.lvl_rank_n * 4));
+        VIDC_TRY(c.s_width.get(ctx, pl.width_n * 4));
+        VIDC_TRY(c.s_bitpos.get(ctx, pl.bitpos_n * 8));
+        VIDC_TRY(c.s_offs_tmp.get(ctx, (size_t)pl.offs_tmp_n * 8));
+        VIDC_HIP(hipMemsetAsync(c.s_offs_tmp.p, 0, (size_t)pl.offs_tmp_n * 8, ctx->stream));
+        VIDC_TRY(wt_rrr_tables(ctx, w, c.tab));
     }
-    VIDC_TRY(w->d_nrank.alloc(wt_nrank_base(L) + 1));
-    VIDC_HIP(hipMemsetAsync(w->d_nrank.p, 0, (wt_nrank_base(L) + 1) * 4, ctx->stream));
-    VIDC_TRY(s_a.get(ctx, (nt ? nt : 1) * 4));
-    VIDC_TRY(s_b.get(ctx, (nt ? nt : 1) * 4));
-    VIDC_TRY(s_err.get(ctx, 4));
-    VIDC_HIP(hipMemsetAsync(s_err.p, 0, 4, ctx->stream));
-    // list_nos[id]: partition + place (two streaming passes) for the sizes it is built for, the direct scatter otherwise
-    const bool part2 = nt >= (1ull << 18) && nt <= (1ull << 24) && nlist <= (1ull << 18) && !std::getenv("VIDC_WT_SCATTER");
-    Scratch s_part;
-    if (!part2) VIDC_HIP(hipMemsetAsync(s_a.p, 0xff, (nt ? nt : 1) * 4, ctx->stream));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((nt + 255) / 256 + 1, (uint64_t)ctx->num_cu * 32);
-    if (part2) VIDC_TRY(s_part.get(ctx, ((size_t)VIDC_WTP_NBLK * VIDC_WTP_MAXB + 2 * VIDC_WTP_MAXB + 8) * 4));
-    EventTimer t(ctx);
-    VIDC_HIP(t.start());
-    if (part2) {
-        uint32_t *part = s_part.as<uint32_t>(), *tot = part + (size_t)VIDC_WTP_NBLK * VIDC_WTP_MAXB, *bstart = tot + VIDC_WTP_MAXB;
-        uint32_t *pairs = s_b.as<uint32_t>();  // (the second symbol array is free until the first level has run)
-        const uint32_t nbuckets = (uint32_t)((nt + VIDC_WTP_BUCKET - 1) >> VIDC_WTP_BSH);
-        hipLaunchKernelGGL(k_wt_part_hist, dim3(VIDC_WTP_NBLK), dim3(256), 0, ctx->stream, d_ids, nt, part);
+    VIDC_HIP(hipMemsetAsync(w->d_nrank.p, 0, c.g.nrank_n * 4, ctx->stream));
+    VIDC_TRY(c.s_a.get(ctx, pl.syms_n * 4));
+    VIDC_TRY(c.s_b.get(ctx, pl.syms_n * 4));
+    VIDC_TRY(c.s_err.get(ctx, 4));
+    VIDC_HIP(hipMemsetAsync(c.s_err.p, 0, 4, ctx->stream));
+    if (!pl.part2) VIDC_HIP(hipMemsetAsync(c.s_a.p, 0xff, pl.syms_n * 4, ctx->stream));  // (k_wt_check_syms looks for slots nobody wrote)
+    else VIDC_TRY(c.s_part.get(ctx, (size_t)pl.part_n * 4));
+    VIDC_TRY(c.s_state.get(ctx, (size_t)pl.state_n * 8));
+    c.cur = c.s_a.as<uint32_t>();
+    c.nxt = c.s_b.as<uint32_t>();
+    return VIDC_OK;
+}
+
+// list_nos[id] into s_a: partition + place, or the direct scatter and its check
+static int wt_build_symbols(WtBuildCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    const WtBuildPlan &pl = c.plan;
+    const uint64_t nt = c.g.ntotal;
+    const uint64_t *C = c.w->d_C.p;
+    uint32_t *syms = c.s_a.as<uint32_t>(), *err = c.s_err.as<uint32_t>();
+    VIDC_HIP(c.t.start());
+    if (pl.part2) {
+        uint32_t *part = c.s_part.as<uint32_t>(), *tot = part + (size_t)VIDC_WTP_NBLK * VIDC_WTP_MAXB, *bstart = tot + VIDC_WTP_MAXB;
+        uint32_t *pairs = c.s_b.as<uint32_t>();  // (the second symbol array is free until the first level has run)
+        hipLaunchKernelGGL(k_wt_part_hist, dim3(VIDC_WTP_NBLK), dim3(256), 0, ctx->stream, c.d_ids, nt, part);
         hipLaunchKernelGGL(k_wt_part_scan, dim3(VIDC_WTP_MAXB / 64), dim3(64), 0, ctx->stream, part, tot);
-        hipLaunchKernelGGL(k_wt_part_scatter, dim3(VIDC_WTP_NBLK), dim3(256), 0, ctx->stream, d_ids, w->d_C.p, (uint32_t)nlist, nt, part, tot,
-                           bstart, pairs, s_err.as<uint32_t>());
-        hipLaunchKernelGGL(k_wt_part_place, dim3(nbuckets), dim3(256), VIDC_WTP_BUCKET * 4, ctx->stream, pairs, bstart, nt, s_a.as<uint32_t>(),
-                           s_err.as<uint32_t>());
+        hipLaunchKernelGGL(k_wt_part_scatter, dim3(VIDC_WTP_NBLK), dim3(256), 0, ctx->stream, c.d_ids, C, (uint32_t)c.nlist, nt, part, tot,
+                           bstart, pairs, err);
+        hipLaunchKernelGGL(k_wt_part_place, dim3(pl.nbuckets), dim3(256), VIDC_WTP_BUCKET * 4, ctx->stream, pairs, bstart, nt, syms, err);
         VIDC_HIP(hipGetLastError());
     } else if (nt) {
-        hipLaunchKernelGGL(k_wt_scatter_syms, dim3((uint32_t)std::min<uint64_t>((nt + 4095) / 4096, (uint64_t)ctx->num_cu * 32)), dim3(256), 0,
-                           ctx->stream, d_ids, w->d_C.p, (uint32_t)nlist, nt, s_a.as<uint32_t>(), s_err.as<uint32_t>());
-        hipLaunchKernelGGL(k_wt_check_syms, dim3(grid), dim3(256), 0, ctx->stream, s_a.as<uint32_t>(), nt, s_err.as<uint32_t>());
+        hipLaunchKernelGGL(k_wt_scatter_syms, dim3(pl.scatter_grid), dim3(256), 0, ctx->stream, c.d_ids, C, (uint32_t)c.nlist, nt, syms, err);
+        hipLaunchKernelGGL(k_wt_check_syms, dim3(pl.check_grid), dim3(256), 0, ctx->stream, syms, nt, err);
         VIDC_HIP(hipGetLastError());
     }
-    // scan states of every level's pass (zeroed once) and the ones before every node start of every level (from C alone): queued in front
-    // of the wait for the verdict on the ids, which they do not depend on
-    Scratch s_state;
-    {
-        VIDC_TRY(w->d_dstab.alloc(2 * (wt_nrank_base(L) + 1)));
-        const size_t per_level = (size_t)((w->words_per_level + VIDC_WT_EPT * 4 - 1) / (VIDC_WT_EPT * 4)) + 1;
-        VIDC_TRY(s_state.get(ctx, (size_t)L * per_level * 8));
-        VIDC_HIP(hipMemsetAsync(s_state.p, 0, (size_t)L * per_level * 8, ctx->stream));
-        hipLaunchKernelGGL(k_wt_node_ranks_from_C, dim3(L * VIDC_WT_NR_G), dim3(256), 0, ctx->stream, w->d_C.p, (uint32_t)nlist, L, w->d_nrank.p,
-                           w->d_dstab.p);
-        VIDC_HIP(hipGetLastError());
-    }
+    return VIDC_OK;
+}
+
+// scan states of every level's pass (zeroed once) and the node tables: queued in front of the wait for the verdict on the ids, which
+// they do not depend on
+static int wt_build_node_tables(WtBuildCall &c) {
+    VIDC_HIP(hipMemsetAsync(c.s_state.p, 0, (size_t)c.plan.state_n * 8, c.ctx->stream));
+    return wt_queue_node_tables(c.ctx, c.w.get(), c.g);
+}
+
+// the one wait in front of the levels, and what it brings back: the status of device offsets, the verdict on the ids
+static int wt_build_verdict(WtBuildCall &c) {
+    vidc_ctx *ctx = c.ctx;
     uint32_t err = 0;
-    VIDC_HIP(hipMemcpyAsync(&err, s_err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(hipMemcpyAsync(&err, c.s_err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    if (!offsets) {  // (bad offsets were replaced by a valid split on the device: nothing above wrote outside its buffers)
-        const DevOffSummary sum = *h_dsum.as<DevOffSummary>();  // (after the wait)
+    if (!c.offsets) {  // (bad offsets were replaced by a valid split on the device: nothing above wrote outside its buffers)
+        const DevOffSummary sum = *c.h_dsum.as<DevOffSummary>();  // (after the wait)
         if (!sum.done) { set_error("wavelet tree: the offsets summary was not written"); return VIDC_ERR_HIP; }
         VIDC_TRY(doff_status(sum, "wavelet tree", VIDC_ERR_INVALID));
     }
@@ -1302,54 +1303,274 @@ static int wt_build_impl(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets,
                   "(asserts at custom_invlists_impl.cpp:359-360)");
         return VIDC_ERR_DOMAIN;
     }
-    uint32_t *cur = s_a.as<uint32_t>(), *nxt = s_b.as<uint32_t>();
-    std::vector<uint64_t> lvl_bits(L, 0);  // wt_type 1: bits of every level's offset stream
-    for (uint32_t level = 0; level < L && nt; level++) {
-        uint64_t *bits = rrr ? s_lvl_bits.as<uint64_t>() : w->d_bits.p + (uint64_t)level * w->words_per_level;
-        uint32_t *rank = rrr ? s_lvl_rank.as<uint32_t>() : w->d_rank.p + (uint64_t)level * (w->blocks_per_level + 1);
-        if (rrr) VIDC_HIP(hipMemsetAsync(bits, 0, w->words_per_level * 8, ctx->stream));
-        const uint32_t ntiles = (uint32_t)((w->words_per_level + VIDC_WT_EPT * 4 - 1) / (VIDC_WT_EPT * 4));
-        unsigned long long *st = s_state.as<unsigned long long>() + (size_t)level * (ntiles + 1);
-        hipLaunchKernelGGL(k_wt_level, dim3(ntiles), dim3(256), 0, ctx->stream, cur, level + 1 < L ? nxt : (uint32_t *)nullptr, nt,
-                           (uint32_t)nlist, L, level, w->d_dstab.p + 2 * wt_nrank_base(level), bits, w->words_per_level, rank,
-                           w->blocks_per_level, st, ntiles);
-        if (level + 1 < L) std::swap(cur, nxt);
-        VIDC_HIP(hipGetLastError());
-        if (rrr) {  // code this level: classes -> offset widths -> bit positions (scan) -> offsets, samples
-            const uint32_t bgrid = (uint32_t)std::min<uint64_t>((nblk + 255) / 256 + 1, (uint64_t)ctx->num_cu * 32);
-            uint64_t *otmp = s_offs_tmp.as<uint64_t>() + (size_t)level * (w->words_per_level + 1);
-            hipLaunchKernelGGL(k_rrr_classes, dim3(bgrid), dim3(256), 0, ctx->stream, bits, nblk, tab,
-                               w->d_cls.p + (uint64_t)level * w->rrr_cls_wpl, s_width.as<uint32_t>());
-            VIDC_TRY(device_exscan(ctx, s_width.as<uint32_t>(), (uint32_t)nblk, s_bitpos.as<uint64_t>(), s_scan));
-            hipLaunchKernelGGL(k_rrr_offsets, dim3(bgrid), dim3(256), 0, ctx->stream, bits, nblk, tab, w->d_binom.p,
-                               s_bitpos.as<uint64_t>(), (unsigned long long *)otmp);
-            hipLaunchKernelGGL(k_rrr_samples, dim3((uint32_t)std::min<uint64_t>(nsamp / 256 + 1, 4096)), dim3(256), 0, ctx->stream,
-                               bits, rank, nt, nblk, nsamp, s_bitpos.as<uint64_t>(), w->d_ptr.p + (uint64_t)level * (nsamp + 1),
-                               w->d_rs.p + (uint64_t)level * (nsamp + 1));
-            VIDC_HIP(hipGetLastError());
-            VIDC_HIP(hipMemcpyAsync(&lvl_bits[level], s_bitpos.as<uint64_t>() + nblk, 8, hipMemcpyDeviceToHost, ctx->stream));
-            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch of the level is reused by the next one)
-        }
-    }
-    if (rrr) {  // the exact-size offset streams, level after level (+ one pad word each: two-word reads)
-        for (uint32_t level = 0; level < L; level++) w->rrr_off_base[level + 1] = w->rrr_off_base[level] + (lvl_bits[level] + 63) / 64 + 1;
-        w->rrr_off_bits = lvl_bits;
-        VIDC_TRY(w->d_offs.alloc(w->rrr_off_base[L] ? w->rrr_off_base[L] : 1));
-        for (uint32_t level = 0; level < L && nt; level++)
-            VIDC_HIP(hipMemcpyAsync(w->d_offs.p + w->rrr_off_base[level], s_offs_tmp.as<uint64_t>() + (size_t)level * (w->words_per_level + 1),
+    return VIDC_OK;
+}
+
+// wt_type 1, one level: classes -> offset widths -> bit positions (scan) -> offsets, samples; the bits of its offset stream come back
+static int wt_build_rrr_level(WtBuildCall &c, uint32_t level, const uint64_t *bits, const uint32_t *rank) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    const WtGeom &g = c.g;
+    const WtBuildPlan &pl = c.plan;
+    uint32_t *width = c.s_width.as<uint32_t>();
+    uint64_t *bitpos = c.s_bitpos.as<uint64_t>();
+    uint64_t *otmp = c.s_offs_tmp.as<uint64_t>() + (size_t)level * pl.offs_tmp_per_level;
+    hipLaunchKernelGGL(k_rrr_classes, dim3(pl.rrr_block_grid), dim3(256), 0, ctx->stream, bits, g.nblk, c.tab,
+                       w->d_cls.p + (uint64_t)level * g.cls_wpl, width);
+    VIDC_TRY(device_exscan(ctx, width, (uint32_t)g.nblk, bitpos, c.s_scan));
+    hipLaunchKernelGGL(k_rrr_offsets, dim3(pl.rrr_block_grid), dim3(256), 0, ctx->stream, bits, g.nblk, c.tab, w->d_binom.p, bitpos,
+                       (unsigned long long *)otmp);
+    hipLaunchKernelGGL(k_rrr_samples, dim3(pl.rrr_sample_grid), dim3(256), 0, ctx->stream, bits, rank, g.ntotal, g.nblk, g.nsamp, bitpos,
+                       w->d_ptr.p + (uint64_t)level * (g.nsamp + 1), w->d_rs.p + (uint64_t)level * (g.nsamp + 1));
+    VIDC_HIP(hipGetLastError());
+    VIDC_HIP(hipMemcpyAsync(&c.lvl_bits[level], bitpos + g.nblk, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch of the level is reused by the next one)
+    return VIDC_OK;
+}
+
+// one level: its bits, rank directory and the next level's order in one pass; then its RRR coding
+static int wt_build_level(WtBuildCall &c, uint32_t level) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    const WtGeom &g = c.g;
+    const bool rrr = c.rrr(), last = level + 1 == g.L;
+    uint64_t *bits = rrr ? c.s_lvl_bits.as<uint64_t>() : w->d_bits.p + (uint64_t)level * g.words_per_level;
+    uint32_t *rank = rrr ? c.s_lvl_rank.as<uint32_t>() : w->d_rank.p + (uint64_t)level * (g.blocks_per_level + 1);
+    if (rrr) VIDC_HIP(hipMemsetAsync(bits, 0, g.words_per_level * 8, ctx->stream));
+    unsigned long long *st = c.s_state.as<unsigned long long>() + (size_t)level * g.state_per_level;
+    hipLaunchKernelGGL(k_wt_level, dim3(g.level_tiles), dim3(256), 0, ctx->stream, c.cur, last ? (uint32_t *)nullptr : c.nxt, g.ntotal,
+                       (uint32_t)c.nlist, g.L, level, w->d_dstab.p + 2 * wt_nrank_base(level), bits, g.words_per_level, rank,
+                       g.blocks_per_level, st, g.level_tiles);
+    if (!last) std::swap(c.cur, c.nxt);
+    VIDC_HIP(hipGetLastError());
+    return rrr ? wt_build_rrr_level(c, level, bits, rank) : VIDC_OK;
+}
+
+// wt_type 1: the offset streams at their exact size; the size; the call's last wait
+static int wt_build_finish(WtBuildCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    if (c.rrr()) {
+        VIDC_TRY(wt_set_offset_streams(w, c.g, c.lvl_bits.data()));
+        for (uint32_t level = 0; level < c.g.L && c.g.ntotal; level++)
+            VIDC_HIP(hipMemcpyAsync(w->d_offs.p + w->rrr_off_base[level], c.s_offs_tmp.as<uint64_t>() + (size_t)level * c.plan.offs_tmp_per_level,
                                     (w->rrr_off_base[level + 1] - w->rrr_off_base[level]) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    // size accounting = what the object holds: plain bits + rank directory, or the RRR arrays (packed classes,
-    // offset streams, samples); + the symbol start table
-    if (!rrr) {
-        w->size_bytes = (uint64_t)L * (((nt + 63) / 64) * 8 + (w->blocks_per_level + 1) * 4) + (nlist + 1) * 8;
-    } else {
-        uint64_t off_bits = 0;
-        for (uint32_t level = 0; level < L; level++) off_bits += lvl_bits[level];
-        w->size_bytes = (off_bits + 7) / 8 + (uint64_t)L * ((6 * nblk + 7) / 8) + (uint64_t)L * (nsamp + 1) * 8 + (nlist + 1) * 8;
+    w->size_bytes = wt_size_bytes(c.g, c.nlist, c.lvl_bits.data());
+    return c.t.finish();
+}
+
+static int wt_build_impl(const WtBuildIn &in, vidc_wt **out) {
+    WtBuildCall c(in);
+    c.pol.direct_scatter = std::getenv("VIDC_WT_SCATTER") != nullptr;
+    c.pol.num_cu = in.ctx->num_cu;
+    VIDC_TRY(wt_build_begin(c));
+    VIDC_TRY(wt_build_ingest_offsets(c));
+    VIDC_TRY(wt_build_alloc(c));
+    VIDC_TRY(wt_build_symbols(c));
+    VIDC_TRY(wt_build_node_tables(c));
+    VIDC_TRY(wt_build_verdict(c));
+    for (uint32_t level = 0; level < c.g.L && c.g.ntotal; level++) VIDC_TRY(wt_build_level(c, level));
+    VIDC_TRY(wt_build_finish(c));
+    *out = c.w.release();
+    return VIDC_OK;
+}
+
+// ---- bulk decode: one level of a compressed tree back as plain bits + rank directory (scratch), each block unranked once
+static int wt_decode_expand_level(vidc_ctx *ctx, const vidc_wt *w, const WtDecodePlan &pl, uint32_t level, uint64_t *bits, uint32_t *rank) {
+    const BvRrr rv = rrr_view_level(w, level);
+    VIDC_HIP(hipMemsetAsync(bits, 0, pl.lvl_bits_n * 8, ctx->stream));
+    hipLaunchKernelGGL(k_rrr_expand, dim3(pl.expand_grid), dim3(256), 0, ctx->stream, rv, (unsigned long long *)bits);
+    hipLaunchKernelGGL(k_rrr_rankdir, dim3(pl.rankdir_grid), dim3(256), 0, ctx->stream, rv, w->blocks_per_level, rank);
+    return VIDC_OK;
+}
+
+// ---- import: the stages over one WtImportCall, behind the host verdict (wt_import_host_verdict)
+struct WtImportIn {  // (the arrays' word counts are checked by the host verdict and not needed behind it)
+    vidc_ctx *ctx;
+    uint64_t nlist;
+    const uint64_t *offsets;
+    int wt_type;
+    const uint64_t *bits;
+    const uint32_t *cls;
+    const uint64_t *offs, *off_bits;
+};
+struct WtImportCall : WtImportIn {
+    explicit WtImportCall(const WtImportIn &in) : WtImportIn(in), guard(in.ctx), t(in.ctx) {}
+    std::unique_ptr<vidc_wt> w;
+    WtGeom g{};
+    WtImportPlan plan;
+    Scratch s_sum, s_sum2, s_scan, s_scan2, s_tmp, s_tmp2, s_err;
+    StreamGuard guard;  // (behind the blocks: an early return waits before they go back to the pool)
+    EventTimer t;
+    double kernel_ms_before = 0;
+    unsigned long long *d_err = nullptr;  // the error word of the device checks
+    uint64_t *d_tot = nullptr;            // the levels' width totals
+    bool rrr() const { return g.wt_type == 1; }
+};
+
+// the verdict of wt_image_check as the call's message and status
+static int wt_import_host_verdict(const WtImportIn &in, uint64_t n_bits, uint64_t n_cls, uint64_t n_offs) {
+    const WtImageVerdict v = wt_image_check(in.nlist, in.offsets, in.wt_type, in.bits, n_bits, in.cls, n_cls, in.offs, n_offs, in.off_bits);
+    const unsigned long long a = v.a, b = v.b;
+    switch (v.kind) {
+    case WT_IMG_OK: return VIDC_OK;
+    case WT_IMG_TYPE: set_error("wt import: wt_type must be 0 or 1, not %d", in.wt_type); break;
+    case WT_IMG_NLIST: set_error("wt import: nlist must be 1 <= nlist < 2^32"); break;
+    case WT_IMG_OFFSETS_START: set_error("wt import: offsets[0] must be 0"); break;
+    case WT_IMG_OFFSETS_ORDER: set_error("wt import: offsets decrease at list %llu", a); break;
+    case WT_IMG_NTOTAL: set_error("wt import: offsets: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED;
+    case WT_IMG_N_BITS: set_error("wt import: n_bits = %llu, the offsets need %llu words", a, b); break;
+    case WT_IMG_PLAIN_EXTRA: set_error("wt import: n_cls and n_offs must be 0 for wt_type 0"); break;
+    case WT_IMG_BITS_STRAY: set_error("wt import: bits: level %u has a bit set behind position ntotal", v.level); break;
+    case WT_IMG_RRR_EXTRA: set_error("wt import: n_bits must be 0 for wt_type 1"); break;
+    case WT_IMG_N_CLS: set_error("wt import: n_cls = %llu, the offsets need %llu words", a, b); break;
+    case WT_IMG_OFF_BITS_NULL: set_error("wt import: off_bits is NULL"); break;
+    case WT_IMG_OFF_BITS_MAX: set_error("wt import: off_bits[%u] = %llu exceeds 61 bits per block", v.level, a); break;
+    case WT_IMG_N_OFFS: set_error("wt import: n_offs = %llu, off_bits needs %llu words", a, b); break;
+    case WT_IMG_CLS_STRAY: set_error("wt import: cls: level %u has a class field behind its last block", v.level); break;
+    case WT_IMG_OFFS_STRAY: set_error("wt import: offs: level %u has a bit set behind off_bits", v.level); break;
     }
-    VIDC_TRY(t.finish());
-    *out = w.release();
+    return VIDC_ERR_INVALID;
+}
+
+// the object and its arrays; the image copied in, every pad word zero
+static int wt_import_object(WtImportCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    const WtGeom &g = c.g = wt_geom(c.nlist, c.offsets[c.nlist], c.wt_type);
+    c.plan = wt_import_plan(g, ctx->num_cu);
+    c.w.reset(new vidc_wt());
+    vidc_wt *w = c.w.get();
+    w->offsets.assign(c.offsets, c.offsets + c.nlist + 1);
+    VIDC_TRY(wt_object_alloc(ctx, w, c.nlist, g));
+    VIDC_TRY(c.s_err.get(ctx, (size_t)c.plan.err_n * 8));
+    c.d_err = c.s_err.as<unsigned long long>();
+    c.d_tot = c.s_err.as<uint64_t>() + 1;
+    if (c.rrr()) {
+        VIDC_TRY(wt_set_offset_streams(w, g, c.off_bits));
+        VIDC_TRY(wt_rrr_tables(ctx, w, rrr_tab()));
+    }
+    // the pad words (one behind every level's bits; two class words and one offset word behind every level's RRR coding): everything
+    // else is overwritten by the copies
+    for (uint32_t l = 0; l < g.L; l++) {
+        if (!c.rrr()) VIDC_HIP(hipMemsetAsync(w->d_bits.p + (uint64_t)l * g.words_per_level + g.W, 0, 8, ctx->stream));
+        else {
+            VIDC_HIP(hipMemsetAsync(w->d_cls.p + (uint64_t)l * g.cls_wpl + g.cls_img_wpl, 0, 8, ctx->stream));
+            VIDC_HIP(hipMemsetAsync(w->d_offs.p + w->rrr_off_base[l + 1] - 1, 0, 8, ctx->stream));
+        }
+    }
+    VIDC_HIP(hipEventRecord(ctx->tev[0], ctx->stream));
+    VIDC_HIP(hipMemcpyAsync(w->d_C.p, c.offsets, g.C_n * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint64_t at = 0;
+    for (uint32_t l = 0; l < g.L; l++) {
+        if (!c.rrr()) {
+            if (g.W) VIDC_HIP(hipMemcpyAsync(w->d_bits.p + (uint64_t)l * g.words_per_level, c.bits + (uint64_t)l * g.W, g.W * 8, hipMemcpyHostToDevice, ctx->stream));
+            continue;
+        }
+        if (g.nsamp) VIDC_HIP(hipMemcpyAsync(w->d_cls.p + (uint64_t)l * g.cls_wpl, c.cls + (uint64_t)l * g.cls_img_wpl, g.cls_img_wpl * 4, hipMemcpyHostToDevice, ctx->stream));
+        const uint64_t ow = wt_words(c.off_bits[l]);
+        if (ow) VIDC_HIP(hipMemcpyAsync(w->d_offs.p + w->rrr_off_base[l], c.offs + at, ow * 8, hipMemcpyHostToDevice, ctx->stream));
+        at += ow;
+    }
+    VIDC_HIP(hipEventRecord(ctx->tev[1], ctx->stream));
+    return VIDC_OK;
+}
+
+// the error word, and the node tables from the offsets alone
+static int wt_import_node_tables(WtImportCall &c) {
+    VIDC_HIP(c.t.start());
+    VIDC_HIP(hipMemsetAsync(c.d_err, 0xff, 8, c.ctx->stream));
+    VIDC_HIP(hipMemsetAsync(c.w->d_nrank.p, 0, c.g.nrank_n * 4, c.ctx->stream));
+    return wt_queue_node_tables(c.ctx, c.w.get(), c.g);
+}
+
+template <class View>
+static int wt_import_check_nodes(WtImportCall &c, const View &vw) {
+    const vidc_wt *w = c.w.get();
+    hipLaunchKernelGGL(k_wt_imp_check_nodes<View>, dim3(c.plan.node_grid, c.g.L), dim3(256), 0, c.ctx->stream, vw, w->d_C.p, w->d_nrank.p,
+                       (uint32_t)c.nlist, c.g.L, c.d_err);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
+// wt_type 0, the rank directory: ones of every 512-bit block, one scan over the levels back to back, per-level prefixes; the node check
+static int wt_import_rank_dir(WtImportCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    const WtGeom &g = c.g;
+    const WtImportPlan &pl = c.plan;
+    VIDC_TRY(c.s_sum.get(ctx, pl.sum_n * 4));
+    VIDC_TRY(c.s_scan.get(ctx, pl.scan_n * 8));
+    hipLaunchKernelGGL(k_wt_imp_block_ones, dim3(pl.ones_grid, g.L), dim3(256), 0, ctx->stream, w->d_bits.p, g.words_per_level, g.blocks_per_level,
+                       c.s_sum.as<uint32_t>());
+    VIDC_TRY(device_exscan(ctx, c.s_sum.as<uint32_t>(), (uint32_t)(g.L * pl.per_level), c.s_scan.as<uint64_t>(), c.s_tmp));
+    hipLaunchKernelGGL(k_wt_imp_level_prefix, dim3(pl.prefix_grid, g.L), dim3(256), 0, ctx->stream, c.s_scan.as<uint64_t>(), pl.per_level, w->d_rank.p,
+                       (uint64_t *)nullptr);
+    return wt_import_check_nodes(c, plain_view(w));
+}
+
+// wt_type 1, the samples: sums of the classes and of their widths per sample, two scans, per-level prefixes; the levels' width totals
+// are compared with off_bits before anything reads an offset stream; then the block check and the node check
+static int wt_import_samples(WtImportCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    vidc_wt *w = c.w.get();
+    const WtGeom &g = c.g;
+    const WtImportPlan &pl = c.plan;
+    const uint32_t n = (uint32_t)(g.L * pl.per_level);
+    VIDC_TRY(c.s_sum.get(ctx, pl.sum_n * 4));
+    VIDC_TRY(c.s_sum2.get(ctx, pl.sum_n * 4));
+    VIDC_TRY(c.s_scan.get(ctx, pl.scan_n * 8));
+    VIDC_TRY(c.s_scan2.get(ctx, pl.scan_n * 8));
+    if (g.nsamp)
+        hipLaunchKernelGGL(k_wt_imp_sample_sums, dim3(pl.sums_grid, g.L), dim3(256), 0, ctx->stream, w->d_cls.p, g.cls_wpl, g.nsamp,
+                           (const uint8_t *)(w->d_binom.p + 64 * 64), c.s_sum.as<uint32_t>(), c.s_sum2.as<uint32_t>());
+    VIDC_TRY(device_exscan(ctx, c.s_sum.as<uint32_t>(), n, c.s_scan.as<uint64_t>(), c.s_tmp));
+    VIDC_TRY(device_exscan(ctx, c.s_sum2.as<uint32_t>(), n, c.s_scan2.as<uint64_t>(), c.s_tmp2));
+    const dim3 pgrid(pl.prefix_grid, g.L);
+    hipLaunchKernelGGL(k_wt_imp_level_prefix, pgrid, dim3(256), 0, ctx->stream, c.s_scan.as<uint64_t>(), g.nsamp, w->d_rs.p, (uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_wt_imp_level_prefix, pgrid, dim3(256), 0, ctx->stream, c.s_scan2.as<uint64_t>(), g.nsamp, w->d_ptr.p, c.d_tot);
+    VIDC_HIP(hipGetLastError());
+    VIDC_HIP(c.t.mark());  // (the kernel time of the call is the two intervals around this read-back, not the wait between them)
+    std::vector<uint64_t> tot(g.L, 0);
+    VIDC_HIP(hipMemcpyAsync(tot.data(), c.d_tot, (size_t)g.L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    c.kernel_ms_before = c.t.elapsed();
+    for (uint32_t l = 0; l < g.L; l++)
+        if (tot[l] != c.off_bits[l]) {
+            set_error("wt import: off_bits[%u] = %llu, the classes of the level need %llu bits", l, (unsigned long long)c.off_bits[l],
+                      (unsigned long long)tot[l]);
+            return VIDC_ERR_INVALID;
+        }
+    VIDC_HIP(c.t.start());
+    if (g.nblk)
+        hipLaunchKernelGGL(k_wt_imp_check_blocks, dim3(pl.blocks_grid, g.L), dim3(256), 0, ctx->stream, rrr_view(w), c.d_err);
+    return wt_import_check_nodes(c, rrr_view(w));
+}
+
+// the call's last wait, the times, the verdict of the device checks, the size
+static int wt_import_device_verdict(WtImportCall &c) {
+    vidc_ctx *ctx = c.ctx;
+    unsigned long long err = 0;
+    VIDC_HIP(hipMemcpyAsync(&err, c.d_err, 8, hipMemcpyDeviceToHost, ctx->stream));
+    c.guard.disarm();
+    VIDC_TRY(c.t.finish());
+    ctx->last_kernel_ms += c.kernel_ms_before;
+    {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ctx->tev[0], ctx->tev[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_IMPORT_H2D] = ms;
+    }
+    if (err != ~0ull) {
+        const uint32_t level = (uint32_t)(err >> 56) & 0x7fu, kind = (uint32_t)(err & 0xffu);
+        const unsigned long long idx = (err >> 8) & 0xffffffffffffull;
+        if (kind == VIDC_WT_IMP_NODE)
+            set_error("wt import: the image does not match the offsets: ones before node %llu of level %u differ", idx, level);
+        else
+            set_error("wt import: %s: block %llu of level %u %s", kind == VIDC_WT_IMP_OFFSET ? "offs" : "cls", idx, level,
+                      kind == VIDC_WT_IMP_OFFSET ? "has an offset >= C(63, class)"
+                      : kind == VIDC_WT_IMP_CLASS ? "has a class above the number of its bits" : "has a one behind the end of the level");
+        return VIDC_ERR_INVALID;
+    }
+    c.w->size_bytes = wt_size_bytes(c.g, c.nlist, c.off_bits);
     return VIDC_OK;
 }
 
@@ -1360,15 +1581,16 @@ extern "C" {
 int vidc_wt_build(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint64_t *d_ids, int wt_type,
                   vidc_wt **out) {
     if (!ctx || !out || (nlist && !offsets) || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
-    return wt_build_impl(ctx, nlist, offsets, nullptr, 0, d_ids, wt_type, out);
+    *out = nullptr;
+    return wt_build_impl(WtBuildIn{ctx, nlist, offsets, nullptr, 0, d_ids, wt_type, WtBuildPolicy{}}, out);
 }
 
 int vidc_wt_build_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids, int wt_type,
                       vidc_wt **out) {
     if (!ctx || !out || !d_offsets || (wt_type != 0 && wt_type != 1)) return VIDC_ERR_INVALID;
     *out = nullptr;
-    if (ntotal >= 0xffffffffull) { set_error("wavelet tree: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED; }
-    return wt_build_impl(ctx, nlist, nullptr, d_offsets, ntotal, d_ids, wt_type, out);
+    if (!wt_ntotal_ok(ntotal)) return wt_build_shape(1, ntotal, wt_type);  // (in front of the refusal of nlist)
+    return wt_build_impl(WtBuildIn{ctx, nlist, nullptr, d_offsets, ntotal, d_ids, wt_type, WtBuildPolicy{}}, out);
 }
 
 int vidc_wt_offsets(vidc_ctx *ctx, const vidc_wt *w, uint64_t *offsets) {
@@ -1469,53 +1691,36 @@ int vidc_wt_decode_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *d_out) {
     if (!ctx || !w || (w->ntotal && !d_out)) return VIDC_ERR_INVALID;
     if (!w->ntotal) return VIDC_OK;
     VIDC_HIP(hipSetDevice(ctx->device));
+    const WtDecodePlan pl = wt_decode_plan(wt_geom_of(w), ctx->num_cu);
     Scratch s_a, s_b;        // ping-pong (id, symbol prefix) arrays
     Scratch s_bits, s_rank;  // wt_type 1: one level as plain bits + rank directory
     EventTimer t(ctx);
     VIDC_HIP(t.start());
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((w->ntotal + 255) / 256, (uint64_t)ctx->num_cu * 32);
-    if (w->L == 0) {  // one list: ids 0..ntotal-1 in order (the per-id kernel handles it)
-        if (w->wt_type == 1)
-            hipLaunchKernelGGL(k_wt_decode_all<WtRrrView>, dim3(grid), dim3(128), 0, ctx->stream, rrr_view(w), w->d_C.p, w->d_nrank.p,
-                               (uint32_t)w->nlist, w->L, w->ntotal, d_out);
-        else
-            hipLaunchKernelGGL(k_wt_decode_all<WtPlainView>, dim3(grid), dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p,
-                               (uint32_t)w->nlist, w->L, w->ntotal, d_out);
-    } else {
+    if (w->wt_type == 1) {
+        VIDC_TRY(s_bits.get(ctx, pl.lvl_bits_n * 8));
+        VIDC_TRY(s_rank.get(ctx, pl.lvl_rank_n * 4));
+    }
+    if (pl.item_arrays > 0) VIDC_TRY(s_a.get(ctx, pl.items_n * sizeof(WtItem)));
+    if (pl.item_arrays > 1) VIDC_TRY(s_b.get(ctx, pl.items_n * sizeof(WtItem)));
+    const WtItem *in = nullptr;
+    for (uint32_t level = 0; level < w->L; level++) {
+        const bool last = level + 1 == w->L;
+        WtItem *out = last ? nullptr : ((level & 1u) ? s_b.as<WtItem>() : s_a.as<WtItem>());
+        uint64_t *oid = last ? d_out : nullptr;
+        const uint64_t *bits = s_bits.as<uint64_t>();
+        const uint32_t *rank = s_rank.as<uint32_t>();
         if (w->wt_type == 1) {
-            VIDC_TRY(s_bits.get(ctx, w->words_per_level * 8));
-            VIDC_TRY(s_rank.get(ctx, (w->blocks_per_level + 1) * 4));
+            VIDC_TRY(wt_decode_expand_level(ctx, w, pl, level, s_bits.as<uint64_t>(), s_rank.as<uint32_t>()));
+        } else {
+            bits = w->d_bits.p + (uint64_t)level * w->words_per_level;
+            rank = w->d_rank.p + (uint64_t)level * (w->blocks_per_level + 1);
         }
-        if (w->L > 1) {
-            VIDC_TRY(s_a.get(ctx, w->ntotal * sizeof(WtItem)));
-            if (w->L > 2) VIDC_TRY(s_b.get(ctx, w->ntotal * sizeof(WtItem)));
-        }
-        const WtItem *in = nullptr;
-        for (uint32_t level = 0; level < w->L; level++) {
-            const bool last = level + 1 == w->L;
-            WtItem *out = last ? nullptr : ((level & 1u) ? s_b.as<WtItem>() : s_a.as<WtItem>());
-            uint64_t *oid = last ? d_out : nullptr;
-            const uint32_t *nr = w->d_nrank.p + wt_nrank_base(level);
-            BvPlain bv{w->d_bits.p + (uint64_t)level * w->words_per_level,
-                       w->d_rank.p + (uint64_t)level * (w->blocks_per_level + 1), w->blocks_per_level, w->words_per_level};
-            if (w->wt_type == 1) {  // the level back as plain bits + rank directory (scratch), each block unranked once
-                const BvRrr rv = rrr_view_level(w, level);
-                VIDC_HIP(hipMemsetAsync(s_bits.p, 0, w->words_per_level * 8, ctx->stream));
-                hipLaunchKernelGGL(k_rrr_expand, dim3((uint32_t)std::min<uint64_t>((w->rrr_nblk + 255) / 256, (uint64_t)ctx->num_cu * 32)),
-                                   dim3(256), 0, ctx->stream, rv, (unsigned long long *)s_bits.p);
-                hipLaunchKernelGGL(k_rrr_rankdir, dim3((uint32_t)std::min<uint64_t>((w->blocks_per_level + 256) / 256, 1024)), dim3(256),
-                                   0, ctx->stream, rv, w->blocks_per_level, s_rank.as<uint32_t>());
-                bv = BvPlain{s_bits.as<uint64_t>(), s_rank.as<uint32_t>(), w->blocks_per_level, w->words_per_level};
-            }
-            const dim3 tgrid((uint32_t)((w->ntotal + 256u * VIDC_WTD_EPT - 1) / (256u * VIDC_WTD_EPT)));
-            const uint32_t *dt = w->d_dstab.p + 2 * wt_nrank_base(level);
-            if (last) hipLaunchKernelGGL(k_wt_decode_tile<true>, tgrid, dim3(256), 0, ctx->stream, in, out, oid, bv.bits, w->words_per_level, bv.rank,
-                                         dt, w->ntotal);
-            else hipLaunchKernelGGL(k_wt_decode_tile<false>, tgrid, dim3(256), 0, ctx->stream, in, out, oid, bv.bits, w->words_per_level, bv.rank,
-                                    dt, w->ntotal);
-            (void)nr;
-            in = out;
-        }
+        const uint32_t *dt = w->d_dstab.p + 2 * wt_nrank_base(level);
+        if (last) hipLaunchKernelGGL(k_wt_decode_tile<true>, dim3(pl.tile_grid), dim3(256), 0, ctx->stream, in, out, oid, bits, w->words_per_level, rank,
+                                     dt, w->ntotal);
+        else hipLaunchKernelGGL(k_wt_decode_tile<false>, dim3(pl.tile_grid), dim3(256), 0, ctx->stream, in, out, oid, bits, w->words_per_level, rank,
+                                dt, w->ntotal);
+        in = out;
     }
     VIDC_HIP(hipGetLastError());
     VIDC_TRY(t.finish());  // (waits: the scratch of the levels goes back to the pool when the call returns)
@@ -1528,41 +1733,35 @@ int vidc_wt_type(const vidc_wt *w) { return w ? w->wt_type : -1; }
 
 int vidc_wt_image_words(const vidc_wt *w, uint64_t *n_bits, uint64_t *n_cls, uint64_t *n_offs) {
     if (!w) { set_error("wt image_words: NULL object"); return VIDC_ERR_INVALID; }
-    uint64_t nb = 0, nc = 0, no = 0;
-    if (w->wt_type == 0) nb = (uint64_t)w->L * ((w->ntotal + 63) / 64);
-    else {
-        nc = (uint64_t)w->L * 6 * w->rrr_nsamp;
-        for (uint32_t l = 0; l < w->L; l++) no += (w->rrr_off_bits[l] + 63) / 64;
-    }
-    if (n_bits) *n_bits = nb;
-    if (n_cls) *n_cls = nc;
-    if (n_offs) *n_offs = no;
+    const WtImageWords iw = wt_image_words(wt_geom_of(w), w->rrr_off_bits.data());
+    if (n_bits) *n_bits = iw.n_bits;
+    if (n_cls) *n_cls = iw.n_cls;
+    if (n_offs) *n_offs = iw.n_offs;
     return VIDC_OK;
 }
 
 int vidc_wt_export_all(vidc_ctx *ctx, const vidc_wt *w, uint64_t *bits, size_t bits_cap, uint32_t *cls, size_t cls_cap, uint64_t *offs,
                        size_t offs_cap, uint64_t *off_bits) {
     if (!ctx || !w) { set_error("wt export_all: NULL context or object"); return VIDC_ERR_INVALID; }
-    uint64_t nb = 0, nc = 0, no = 0;
-    VIDC_TRY(vidc_wt_image_words(w, &nb, &nc, &no));
-    if (nb > bits_cap || nc > cls_cap || no > offs_cap) { set_error("wt export_all: export buffer too small"); return VIDC_ERR_INVALID; }
-    if ((nb && !bits) || (nc && !cls) || (no && !offs) || (w->wt_type == 1 && !off_bits)) {
+    const WtGeom g = wt_geom_of(w);
+    const WtImageWords iw = wt_image_words(g, w->rrr_off_bits.data());
+    if (iw.n_bits > bits_cap || iw.n_cls > cls_cap || iw.n_offs > offs_cap) { set_error("wt export_all: export buffer too small"); return VIDC_ERR_INVALID; }
+    if ((iw.n_bits && !bits) || (iw.n_cls && !cls) || (iw.n_offs && !offs) || (w->wt_type == 1 && !off_bits)) {
         set_error("wt export_all: NULL array");
         return VIDC_ERR_INVALID;
     }
     VIDC_HIP(hipSetDevice(w->device));
     StreamGuard guard(ctx);
     if (w->wt_type == 0) {
-        const uint64_t W = (w->ntotal + 63) / 64;
-        for (uint32_t l = 0; l < w->L && W; l++)  // (without the level's pad word)
-            VIDC_HIP(hipMemcpyAsync(bits + (uint64_t)l * W, w->d_bits.p + (uint64_t)l * w->words_per_level, W * 8, hipMemcpyDeviceToHost, ctx->stream));
+        for (uint32_t l = 0; l < g.L && g.W; l++)  // (without the level's pad word)
+            VIDC_HIP(hipMemcpyAsync(bits + (uint64_t)l * g.W, w->d_bits.p + (uint64_t)l * g.words_per_level, g.W * 8, hipMemcpyDeviceToHost, ctx->stream));
     } else {
-        const uint64_t cw = 6 * w->rrr_nsamp;
+        const uint64_t cw = g.cls_img_wpl;
         uint64_t at = 0;
-        for (uint32_t l = 0; l < w->L; l++) {
+        for (uint32_t l = 0; l < g.L; l++) {
             off_bits[l] = w->rrr_off_bits[l];
-            if (cw) VIDC_HIP(hipMemcpyAsync(cls + (uint64_t)l * cw, w->d_cls.p + (uint64_t)l * w->rrr_cls_wpl, cw * 4, hipMemcpyDeviceToHost, ctx->stream));
-            const uint64_t ow = (w->rrr_off_bits[l] + 63) / 64;
+            if (cw) VIDC_HIP(hipMemcpyAsync(cls + (uint64_t)l * cw, w->d_cls.p + (uint64_t)l * g.cls_wpl, cw * 4, hipMemcpyDeviceToHost, ctx->stream));
+            const uint64_t ow = wt_words(w->rrr_off_bits[l]);
             if (ow) VIDC_HIP(hipMemcpyAsync(offs + at, w->d_offs.p + w->rrr_off_base[l], ow * 8, hipMemcpyDeviceToHost, ctx->stream));
             at += ow;
         }
@@ -1576,220 +1775,16 @@ int vidc_wt_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, int w
                    const uint32_t *cls, uint64_t n_cls, const uint64_t *offs, uint64_t n_offs, const uint64_t *off_bits, vidc_wt **out) {
     if (out) *out = nullptr;
     if (!ctx || !out) { set_error("wt import: NULL context or out"); return VIDC_ERR_INVALID; }
-    // 1. host checks: the geometry, and the sizes it demands of the arrays
     if (!offsets) { set_error("wt import: offsets is NULL"); return VIDC_ERR_INVALID; }
-    if (wt_type != 0 && wt_type != 1) { set_error("wt import: wt_type must be 0 or 1, not %d", wt_type); return VIDC_ERR_INVALID; }
-    if (nlist == 0 || nlist >= 0xffffffffull) { set_error("wt import: nlist must be 1 <= nlist < 2^32"); return VIDC_ERR_INVALID; }
-    if (offsets[0] != 0) { set_error("wt import: offsets[0] must be 0"); return VIDC_ERR_INVALID; }
-    for (uint64_t l = 0; l < nlist; l++)
-        if (offsets[l + 1] < offsets[l]) {
-            set_error("wt import: offsets decrease at list %llu", (unsigned long long)l);
-            return VIDC_ERR_INVALID;
-        }
-    const uint64_t nt = offsets[nlist];
-    if (nt >= 0xffffffffull) { set_error("wt import: offsets: ntotal must be < 2^32"); return VIDC_ERR_UNSUPPORTED; }
-    uint32_t L = 1;
-    while ((1ull << L) < nlist) L++;
-    const bool rrr = wt_type == 1;
-    if (rrr && L > 32) { set_error("wt import: more than 32 levels"); return VIDC_ERR_UNSUPPORTED; }
-    const uint64_t W = (nt + 63) / 64, nblk = (nt + RRR_B - 1) / RRR_B, nsamp = (nblk + RRR_K - 1) / RRR_K;
-    const RrrTab tab = rrr_tab();
-    if (!rrr) {
-        if (n_bits != (uint64_t)L * W || (n_bits && !bits)) {
-            set_error("wt import: n_bits = %llu, the offsets need %llu words", (unsigned long long)n_bits, (unsigned long long)((uint64_t)L * W));
-            return VIDC_ERR_INVALID;
-        }
-        if (n_cls || n_offs) { set_error("wt import: n_cls and n_offs must be 0 for wt_type 0"); return VIDC_ERR_INVALID; }
-        if (nt & 63u)
-            for (uint32_t l = 0; l < L; l++)
-                if (bits[(uint64_t)l * W + W - 1] >> (nt & 63u)) {
-                    set_error("wt import: bits: level %u has a bit set behind position ntotal", l);
-                    return VIDC_ERR_INVALID;
-                }
-    } else {
-        if (n_bits) { set_error("wt import: n_bits must be 0 for wt_type 1"); return VIDC_ERR_INVALID; }
-        if (n_cls != (uint64_t)L * 6 * nsamp || (n_cls && !cls)) {
-            set_error("wt import: n_cls = %llu, the offsets need %llu words", (unsigned long long)n_cls, (unsigned long long)((uint64_t)L * 6 * nsamp));
-            return VIDC_ERR_INVALID;
-        }
-        if (!off_bits) { set_error("wt import: off_bits is NULL"); return VIDC_ERR_INVALID; }
-        uint64_t need = 0;
-        for (uint32_t l = 0; l < L; l++) {
-            if (off_bits[l] > 61 * nblk) {  // (the widest offset has 61 bits)
-                set_error("wt import: off_bits[%u] = %llu exceeds 61 bits per block", l, (unsigned long long)off_bits[l]);
-                return VIDC_ERR_INVALID;
-            }
-            need += (off_bits[l] + 63) / 64;
-        }
-        if (n_offs != need || (n_offs && !offs)) {
-            set_error("wt import: n_offs = %llu, off_bits needs %llu words", (unsigned long long)n_offs, (unsigned long long)need);
-            return VIDC_ERR_INVALID;
-        }
-        uint64_t at = 0;
-        for (uint32_t l = 0; l < L; l++) {
-            for (uint64_t b = nblk; b < nsamp * RRR_K; b++) {  // class fields behind the last block (fewer than 32)
-                const uint64_t bp = 6 * b;
-                uint64_t f = (uint64_t)cls[(uint64_t)l * 6 * nsamp + (bp >> 5)] >> (bp & 31);
-                if ((bp & 31) > 26) f |= (uint64_t)cls[(uint64_t)l * 6 * nsamp + (bp >> 5) + 1] << (32 - (bp & 31));
-                if (f & 63u) { set_error("wt import: cls: level %u has a class field behind its last block", l); return VIDC_ERR_INVALID; }
-            }
-            const uint64_t ow = (off_bits[l] + 63) / 64;
-            if ((off_bits[l] & 63u) && (offs[at + ow - 1] >> (off_bits[l] & 63u))) {
-                set_error("wt import: offs: level %u has a bit set behind off_bits", l);
-                return VIDC_ERR_INVALID;
-            }
-            at += ow;
-        }
-    }
-    // 2. the object as wt_build_impl lays it out; arrays copied in, every pad word zero
+    const WtImportIn in{ctx, nlist, offsets, wt_type, bits, cls, offs, off_bits};
+    VIDC_TRY(wt_import_host_verdict(in, n_bits, n_cls, n_offs));
     VIDC_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<vidc_wt> w(new vidc_wt());
-    w->device = ctx->device;
-    w->nlist = nlist;
-    w->wt_type = wt_type;
-    w->offsets.assign(offsets, offsets + nlist + 1);
-    w->ntotal = nt;
-    w->L = L;
-    w->words_per_level = W + 1;
-    w->blocks_per_level = (w->words_per_level + BLK_WORDS - 1) / BLK_WORDS;
-    const uint64_t wpl = w->words_per_level, bpl = w->blocks_per_level;
-    Scratch s_sum, s_sum2, s_scan, s_scan2, s_tmp, s_tmp2, s_err;
-    StreamGuard guard(ctx);  // (behind the blocks: an early return waits before they go back to the pool)
-    VIDC_TRY(w->d_C.alloc(nlist + 1));
-    VIDC_TRY(w->d_nrank.alloc(wt_nrank_base(L) + 1));
-    VIDC_TRY(w->d_dstab.alloc(2 * (wt_nrank_base(L) + 1)));
-    VIDC_TRY(s_err.get(ctx, 8 + (size_t)L * 8));  // the error word, the levels' width totals
-    if (!rrr) {
-        VIDC_TRY(w->d_bits.alloc(L * wpl));
-        VIDC_TRY(w->d_rank.alloc(L * (bpl + 1)));
-    } else {
-        w->rrr_nblk = nblk; w->rrr_nsamp = nsamp;
-        w->rrr_cls_wpl = 6 * nsamp + 2;
-        w->rrr_off_bits.assign(off_bits, off_bits + L);
-        w->rrr_off_base.assign(L + 1, 0);
-        for (uint32_t l = 0; l < L; l++) w->rrr_off_base[l + 1] = w->rrr_off_base[l] + (off_bits[l] + 63) / 64 + 1;
-        VIDC_TRY(w->d_cls.alloc(L * w->rrr_cls_wpl));
-        VIDC_TRY(w->d_ptr.alloc(L * (nsamp + 1)));
-        VIDC_TRY(w->d_rs.alloc(L * (nsamp + 1)));
-        VIDC_TRY(w->d_offs.alloc(w->rrr_off_base[L]));
-        VIDC_TRY(wt_rrr_tables(ctx, w.get(), tab));
-    }
-    // the pad words (one behind every level's bits; two class words and one offset word behind every level's RRR coding): everything
-    // else is overwritten by the copies
-    for (uint32_t l = 0; l < L; l++) {
-        if (!rrr) VIDC_HIP(hipMemsetAsync(w->d_bits.p + (uint64_t)l * wpl + W, 0, 8, ctx->stream));
-        else {
-            VIDC_HIP(hipMemsetAsync(w->d_cls.p + (uint64_t)l * w->rrr_cls_wpl + 6 * nsamp, 0, 8, ctx->stream));
-            VIDC_HIP(hipMemsetAsync(w->d_offs.p + w->rrr_off_base[l + 1] - 1, 0, 8, ctx->stream));
-        }
-    }
-    VIDC_HIP(hipEventRecord(ctx->tev[0], ctx->stream));
-    VIDC_HIP(hipMemcpyAsync(w->d_C.p, offsets, (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (!rrr) {
-        for (uint32_t l = 0; l < L && W; l++)
-            VIDC_HIP(hipMemcpyAsync(w->d_bits.p + (uint64_t)l * wpl, bits + (uint64_t)l * W, W * 8, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        uint64_t at = 0;
-        for (uint32_t l = 0; l < L; l++) {
-            if (nsamp) VIDC_HIP(hipMemcpyAsync(w->d_cls.p + (uint64_t)l * w->rrr_cls_wpl, cls + (uint64_t)l * 6 * nsamp, 6 * nsamp * 4, hipMemcpyHostToDevice, ctx->stream));
-            const uint64_t ow = (off_bits[l] + 63) / 64;
-            if (ow) VIDC_HIP(hipMemcpyAsync(w->d_offs.p + w->rrr_off_base[l], offs + at, ow * 8, hipMemcpyHostToDevice, ctx->stream));
-            at += ow;
-        }
-    }
-    VIDC_HIP(hipEventRecord(ctx->tev[1], ctx->stream));
-    EventTimer t(ctx);
-    double kernel_ms_before = 0;
-    VIDC_HIP(t.start());
-    unsigned long long *d_err = s_err.as<unsigned long long>();
-    uint64_t *d_tot = s_err.as<uint64_t>() + 1;
-    VIDC_HIP(hipMemsetAsync(d_err, 0xff, 8, ctx->stream));
-    // 3. the node tables, from the offsets alone
-    VIDC_HIP(hipMemsetAsync(w->d_nrank.p, 0, (wt_nrank_base(L) + 1) * 4, ctx->stream));
-    hipLaunchKernelGGL(k_wt_node_ranks_from_C, dim3(L * VIDC_WT_NR_G), dim3(256), 0, ctx->stream, w->d_C.p, (uint32_t)nlist, L, w->d_nrank.p,
-                       w->d_dstab.p);
-    VIDC_HIP(hipGetLastError());
-    const dim3 ngrid((uint32_t)std::min<uint64_t>(((1ull << (L - 1)) + 1 + 255) / 256, 4096), L);
-    if (!rrr) {
-        // 4. the rank directory: ones of every 512-bit block, one scan over the levels back to back, per-level prefixes
-        const uint64_t n = (uint64_t)L * bpl;
-        VIDC_TRY(s_sum.get(ctx, n * 4));
-        VIDC_TRY(s_scan.get(ctx, (n + 1) * 8));
-        hipLaunchKernelGGL(k_wt_imp_block_ones, dim3((uint32_t)((bpl * 8 + 255) / 256), L), dim3(256), 0, ctx->stream, w->d_bits.p, wpl, bpl,
-                           s_sum.as<uint32_t>());
-        VIDC_TRY(device_exscan(ctx, s_sum.as<uint32_t>(), (uint32_t)n, s_scan.as<uint64_t>(), s_tmp));
-        hipLaunchKernelGGL(k_wt_imp_level_prefix, dim3((uint32_t)std::min<uint64_t>((bpl + 256) / 256, 1024), L), dim3(256), 0, ctx->stream,
-                           s_scan.as<uint64_t>(), bpl, w->d_rank.p, (uint64_t *)nullptr);
-        // 6. the node check
-        hipLaunchKernelGGL(k_wt_imp_check_nodes<WtPlainView>, ngrid, dim3(256), 0, ctx->stream, plain_view(w.get()), w->d_C.p, w->d_nrank.p,
-                           (uint32_t)nlist, L, d_err);
-        VIDC_HIP(hipGetLastError());
-    } else {
-        // 5. the samples: sums of the classes and of their widths per sample, two scans, per-level prefixes; the levels' width totals
-        // are compared with off_bits before anything reads an offset stream
-        const uint64_t n = (uint64_t)L * nsamp;
-        VIDC_TRY(s_sum.get(ctx, (n ? n : 1) * 4));
-        VIDC_TRY(s_sum2.get(ctx, (n ? n : 1) * 4));
-        VIDC_TRY(s_scan.get(ctx, (n + 1) * 8));
-        VIDC_TRY(s_scan2.get(ctx, (n + 1) * 8));
-        if (nsamp)
-            hipLaunchKernelGGL(k_wt_imp_sample_sums, dim3((uint32_t)((nsamp + 255) / 256), L), dim3(256), 0, ctx->stream, w->d_cls.p, w->rrr_cls_wpl,
-                               nsamp, (const uint8_t *)(w->d_binom.p + 64 * 64), s_sum.as<uint32_t>(), s_sum2.as<uint32_t>());
-        VIDC_TRY(device_exscan(ctx, s_sum.as<uint32_t>(), (uint32_t)n, s_scan.as<uint64_t>(), s_tmp));
-        VIDC_TRY(device_exscan(ctx, s_sum2.as<uint32_t>(), (uint32_t)n, s_scan2.as<uint64_t>(), s_tmp2));
-        const dim3 pgrid((uint32_t)std::min<uint64_t>((nsamp + 256) / 256, 1024), L);
-        hipLaunchKernelGGL(k_wt_imp_level_prefix, pgrid, dim3(256), 0, ctx->stream, s_scan.as<uint64_t>(), nsamp, w->d_rs.p, (uint64_t *)nullptr);
-        hipLaunchKernelGGL(k_wt_imp_level_prefix, pgrid, dim3(256), 0, ctx->stream, s_scan2.as<uint64_t>(), nsamp, w->d_ptr.p, d_tot);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(t.mark());  // (the kernel time of the call is the two intervals around this read-back, not the wait between them)
-        std::vector<uint64_t> tot(L, 0);
-        VIDC_HIP(hipMemcpyAsync(tot.data(), d_tot, (size_t)L * 8, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        kernel_ms_before = t.elapsed();
-        for (uint32_t l = 0; l < L; l++)
-            if (tot[l] != off_bits[l]) {
-                set_error("wt import: off_bits[%u] = %llu, the classes of the level need %llu bits", l, (unsigned long long)off_bits[l],
-                          (unsigned long long)tot[l]);
-                return VIDC_ERR_INVALID;
-            }
-        VIDC_HIP(t.start());
-        if (nblk)
-            hipLaunchKernelGGL(k_wt_imp_check_blocks, dim3((uint32_t)std::min<uint64_t>((nblk + 255) / 256, (uint64_t)ctx->num_cu * 8), L), dim3(256), 0,
-                               ctx->stream, rrr_view(w.get()), d_err);
-        // 6. the node check
-        hipLaunchKernelGGL(k_wt_imp_check_nodes<WtRrrView>, ngrid, dim3(256), 0, ctx->stream, rrr_view(w.get()), w->d_C.p, w->d_nrank.p,
-                           (uint32_t)nlist, L, d_err);
-        VIDC_HIP(hipGetLastError());
-    }
-    unsigned long long err = 0;
-    VIDC_HIP(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, ctx->stream));
-    guard.disarm();
-    VIDC_TRY(t.finish());
-    ctx->last_kernel_ms += kernel_ms_before;
-    {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ctx->tev[0], ctx->tev[1]) == hipSuccess) ctx->phase_ms[VIDC_PHASE_IMPORT_H2D] = ms;
-    }
-    if (err != ~0ull) {
-        const uint32_t level = (uint32_t)(err >> 56) & 0x7fu, kind = (uint32_t)(err & 0xffu);
-        const unsigned long long idx = (err >> 8) & 0xffffffffffffull;
-        if (kind == VIDC_WT_IMP_NODE)
-            set_error("wt import: the image does not match the offsets: ones before node %llu of level %u differ", idx, level);
-        else
-            set_error("wt import: %s: block %llu of level %u %s", kind == VIDC_WT_IMP_OFFSET ? "offs" : "cls", idx, level,
-                      kind == VIDC_WT_IMP_OFFSET ? "has an offset >= C(63, class)"
-                      : kind == VIDC_WT_IMP_CLASS ? "has a class above the number of its bits" : "has a one behind the end of the level");
-        return VIDC_ERR_INVALID;
-    }
-    // 7. size accounting, as wt_build_impl
-    if (!rrr) {
-        w->size_bytes = (uint64_t)L * (W * 8 + (bpl + 1) * 4) + (nlist + 1) * 8;
-    } else {
-        uint64_t ob = 0;
-        for (uint32_t l = 0; l < L; l++) ob += off_bits[l];
-        w->size_bytes = (ob + 7) / 8 + (uint64_t)L * ((6 * nblk + 7) / 8) + (uint64_t)L * (nsamp + 1) * 8 + (nlist + 1) * 8;
-    }
-    *out = w.release();
+    WtImportCall c(in);
+    VIDC_TRY(wt_import_object(c));
+    VIDC_TRY(wt_import_node_tables(c));
+    VIDC_TRY(c.rrr() ? wt_import_samples(c) : wt_import_rank_dir(c));
+    VIDC_TRY(wt_import_device_verdict(c));
+    *out = c.w.release();
     return VIDC_OK;
 }
 
