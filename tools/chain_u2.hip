@@ -2,7 +2,7 @@
 // k_roc_encode_u2 with dense 16-id blocks: identical head / words / order, ns per step of each (hipEvents, five repeats: min and
 // max); then the stream through k_roc_decode_u (round 1) and k_roc_decode_u2, five repeats each as well.
 // usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: section tables of the LAST encode arm run and of the k_roc_decode_u2 step;
-// -DU2_DEC_SHARED_STEP: k_roc_decode_u2 runs the step it shared with the bucket kernels, the 'before' of profiles/r21_roc_decode_step.txt)
+// -DU2_PROF2: generic steps, entries into the asm loop and bits in the bitmap of the last k_roc_decode_u2 launch)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I vector_db_id_compression_amd/csrc tools/chain_u2.hip -o /tmp/chain_u2
 #include <cstdio>
 #include <cstdlib>
@@ -129,17 +129,10 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
 #ifdef U2_PROF
         {   // the decode step's sections (the last launch of k_roc_decode_u2 left them in the slots array)
             uint32_t dp[14]; CK(hipMemcpy(dp, d_slots, 56, hipMemcpyDeviceToHost));
-#ifdef U2_DEC_SHARED_STEP
-            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, address, ds_read, g, dword (7)",
-                "MID: L1, L2, row read bracket (5)", "MID: bfm, address, bit, exec, ds_or, exec (6)", "MID: 3 readlanes, 4 valu of the counters (7)", "MID: m0, renormalise H, ring write (6)",
-                "MID: H * nmax, E1 + row (5)", "MID: row write-back bracket, m0 (4)", "RANK: waitcnt, 10 valu / 4 valu (11 / 5)", "RANK: s_nop, readlane (2)", "AFTER_RANK: ring write, E1 update (3)",
-                "BOT: counters, head', refill test (7) [+ cmp, branch]"};
-#else
-            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, address, ds_read, g, dword (7)",
-                "MID: L1, L2, row read bracket, bfm, m0 (7)", "MID: 3 readlanes, row update, ring write (7)", "MID: renormalise H (4)", "MID: H * nmax (4)",
-                "MID: row write-back bracket, m0 (4)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: address, bit, ring write, ds_or (4)", "(unused)",
+            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, 2 addresses, 2 ds_read, g, dword (9)",
+                "MID: L1, L2, bfm, [bfm,] m0 (5 / 4)", "MID: 2 readlanes, row address, data, [address,] ring write (6)", "MID: renormalise H (4)", "MID: H * nmax, m0 (5)",
+                "(unused)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: [address,] bit, ring write, ds_or, ds_add (4 / 5)", "(unused)",
                 "BOT: counters, head', refill test (6) [+ cmp, branch]"};
-#endif
             double tot = 0, pc = (double)dp[1] / n;
             int np = 0;  // probes the step has (a slot the step does not use stays 0)
             printf("  k_roc_decode_u2 step, cycles per step (s_memtime; 'net' subtracts one probe):\n");

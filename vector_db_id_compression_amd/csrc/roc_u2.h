@@ -42,9 +42,14 @@ struct U2Geom {
     static constexpr uint32_t NE = 4096u;                 // 64 blocks x 64 entries
     static constexpr uint32_t BITMAP_BYTES = NE * G * 8u;
     static constexpr uint32_t LDS_BYTES = BITMAP_BYTES + 16u;  // + a dummy word: target of the "no pending removal" store
-    // k_roc_decode_u2: + a strip of one dword per lane behind the bitmap.  The insertion is a ds_or by ALL lanes: lane 0 hits the
-    // bitmap, lane j > 0 its own dword of the strip (no exec write in the step, no two lanes on one address)
-    static constexpr uint32_t DEC_LDS_BYTES = BITMAP_BYTES + 256u;
+    // k_roc_decode_u2: the level-2 counters u32 row[64][64] in FRONT of the bitmap (row[L1][L2] is dword `entry`; a DS offset field
+    // has 16 bits, so nothing that wants one can sit behind a 128 KiB bitmap), and a strip of one dword per lane behind the bitmap.
+    // The insertion is a ds_or by ALL lanes: lane 0 hits the bitmap, lane j > 0 its own dword of the strip (no exec write in the step,
+    // no two lanes on one address).  147 712 bytes with 20 universe bits, 49 408 with 18 (no set_big_lds).
+    static constexpr uint32_t DEC_ROWS_BYTES = 64u * 64u * 4u;
+    static constexpr uint32_t DEC_BITMAP_OFF = DEC_ROWS_BYTES;
+    static constexpr uint32_t DEC_STRIP_OFF = DEC_BITMAP_OFF + BITMAP_BYTES;
+    static constexpr uint32_t DEC_LDS_BYTES = DEC_STRIP_OFF + 256u;
 };
 
 // Dense 16-id blocks in POSITION space (k_roc_encode_u2<20> only, lists of 4097 .. 65 536 ids): block b holds the ids at positions
@@ -1121,12 +1126,15 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 // n at the end and such a list is decoded again by the round-1 kernel body, which keeps a side list of duplicates.
 //
 // Register map (decode):
-//   v2 lane  v3 (lane & 3) * 8  v4 E1  v5 stack ring  v6:7 {output ring, 0}  v10 lq = floor(2^31 / nmax) per lane (nmax = N0 + lane)
-//   v8 v9 multiplier / addend of the insertion address (k_roc_decode_u2: lane 0 -> bitmap dword, lane j -> strip dword j)
-//   v13 row  v26 address / v27 bit of the insertion  v28 LDS address  v30:31 word(s)  v32..v37 popcount temporaries
-//   v54:57 table entry of the next block  v58 v59 tmp  v64..v127 level-2 rows
-//   s40 x  s43 L1  s44 L2  s45 entry  s46 x_hi  s47 g  s48 b  s49 E1[L1]  s50:51 H  s52:53 H * nmax  s58:59 head  s60 sp
-//   s61 lo  s62 lq  s63 row[L2]  s64 below  s65 tmp  s66:67 mask below b  s68 tmp  s69 t  s70 t_end  s71 limit  s72 tmp
+//   v2 lane  v3 DEC_BITMAP_OFF + (lane & 3) * 8  v4 E1  v5 stack ring  v6:7 {output ring, 0}
+//   v8 v9 multiplier / addend of the insertion address (lane 0 -> bitmap dword, lane j -> strip dword j)
+//   v10 lq = floor(2^31 / nmax) per lane (nmax = N0 + lane)  v11 4 * lane  v26 address / v27 bit of the insertion
+//   v28 address of the bitmap read  v29 address, then value of row[L1][L2]  v30:31 word(s)  v32..v37 popcount temporaries
+//   v38 address / v39 data of the row update  v54:57 table entry of the next block  v58 tmp
+//   (the bucket kernels, which keep their level-2 rows in registers: v3 4 * lane (+ the rows' start), v13 row, v58 v59 tmp,
+//   v64..v127 level-2 rows, s63 row[L2])
+//   s40 x  s43 L1  s44 L2  s45 entry  s46 x_hi  s47 g  s49 E1[L1]  s50:51 H  s52:53 H * nmax  s58:59 head  s60 sp
+//   s61 lo  s62 lq  s64 rank (bucket kernels: below)  s65 tmp  s66:67 mask below b  s68 tmp  s69 t  s70 t_end  s71 limit  s72 tmp
 //   s73 2^p1 - 1  s74 2^p0 - 1  s75 nmax  s76 p0  s77 p1  s85 N0  s86 steps left at lane 0  s87 output index of lane 0
 //   s88:89 output pointer  s94:95 divisor table  s96:97 saved exec  s98 s99 tmp
 #ifdef U2_PROF  // the decode arm's probes (the encoder's U2P with registers the loop of k_roc_decode_u2 leaves alone: s78..s81; the
@@ -1175,111 +1183,62 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_lshr_b32 s45, s40, 8\n" \
     "s_xor_b32 s45, s45, 0xfff\n"                      /* entry (reversed) */ \
     "v_lshl_add_u32 v28, s45, 5, v3\n" \
+    "v_lshlrev_b32_e64 v29, 2, s45\n"                  /* row[L1][L2] is dword `entry` of the LDS */ \
     "ds_read_b64 v[30:31], v28\n" \
+    "ds_read_b32 v29, v29\n"                           /* (one address in every lane: a broadcast) */ \
     "s_bfe_u32 s47, s40, 0x20006\n"                    /* g */ \
     "s_bfe_u32 s65, s40, 0x30005\n"                    /* 32-bit half of the entry holding x */ \
-    "s_lshl3_add_u32 s65, s45, s65\n"                  /* (dword of the bitmap; U2_DEC_MID shifts it to a byte address) */ U2PD(133)
+    "s_lshl3_add_u32 s65, s45, s65\n"                  /* (dword of the bitmap; the insertion's v_mad makes it a byte address) */ U2PD(133)
 #define U2_DEC_IDX_G1 \
     "s_lshr_b32 s45, s40, 6\n" \
     "s_xor_b32 s45, s45, 0xfff\n" \
-    "v_lshlrev_b32_e64 v28, 3, s45\n" \
+    "v_lshl_add_u32 v28, s45, 3, v3\n" \
+    "v_lshlrev_b32_e64 v29, 2, s45\n" \
     "ds_read_b64 v[30:31], v28\n" \
+    "ds_read_b32 v29, v29\n" \
     "s_bfe_u32 s65, s40, 0x10005\n" \
     "s_lshl1_add_u32 s65, s45, s65\n" U2PD(133)
-#define U2_DEC_MID \
-    "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
-    "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
-    "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
-    "v_mov_b32 v13, v64\n" \
-    "s_set_gpr_idx_off\n" U2PD(134) \
-    "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */ \
-    "v_lshlrev_b32_e64 v26, 2, s65\n"                  /* insertion of x: after the read in LDS order */ \
-    "v_lshlrev_b32_e64 v27, s40, 1\n" \
-    "s_mov_b64 exec, 1\n" \
-    "ds_or_b32 v26, v27\n" \
-    "s_mov_b64 exec, -1\n" U2PD(135) \
-    "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
-    "v_readlane_b32 s63, v13, s44\n"                   /* row[L2] */ \
-    "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
-    "v_subrev_u32 v58, s43, v2\n" \
-    "v_subrev_u32 v59, s44, v2\n" \
-    "v_ashrrev_i32 v59, 31, v59\n" \
-    "v_sub_u32 v13, v13, v59\n"                        /* row += 1 in lanes below L2 */ U2PD(136) \
-    "s_and_b32 m0, s60, 63\n"                          /* index push, first half (codec.cpp:44-63): renormalise H */ \
-    "s_cmp_ge_u32 s59, s62\n" \
-    "v_writelane_b32 v5, s58, m0\n" \
-    "s_cselect_b32 s50, s59, s58\n" \
-    "s_cselect_b32 s51, 0, s59\n" \
-    "s_addc_u32 s60, s60, 0\n" U2PD(137) \
-    "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
-    "s_mul_hi_u32 s53, s50, s75\n" \
-    "s_mul_i32 s68, s51, s75\n" \
-    "s_add_u32 s53, s53, s68\n" \
-    "s_add_u32 s72, s49, s63\n" U2PD(138) \
-    "s_set_gpr_idx_on s43, gpr_idx(DST)\n" \
-    "v_mov_b32 v64, v13\n" \
-    "s_set_gpr_idx_off\n" \
-    "s_mov_b32 m0, s69\n" U2PD(139)
 // (the three vector instructions that follow the last readlane of the rank keep the scalar tail off its SGPR write)
 #define U2_DEC_AFTER_RANK \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
     "v_ashrrev_i32 v58, 31, v58\n" \
     "v_sub_u32 v4, v4, v58\n"                          /* E1 += 1 in lanes below L1 */ U2PD(142)
-#define U2_DEC_RANK_G4 \
-    "s_waitcnt lgkmcnt(1)\n" \
-    "v_bcnt_u32_b32 v32, v30, 0\n" \
-    "v_bcnt_u32_b32 v32, v31, v32\n"                   /* set bits of the lane's word */ \
-    "v_and_b32 v33, s66, v30\n" \
-    "v_and_b32 v34, s67, v31\n" \
-    "v_add_u32_dpp v35, v32, v32 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
-    "v_bcnt_u32_b32 v33, v33, 0\n" \
-    "v_bcnt_u32_b32 v33, v34, v33\n"                   /* ... below b */ \
-    "v_add_u32_dpp v36, v35, v35 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
-    "v_sub_u32 v33, v33, v32\n" \
-    "v_add_u32 v37, v36, v33\n"                        /* lane g: bits of the entry below x */ U2PD(140) \
-    "s_nop 0\n" \
-    "v_readlane_b32 s64, v37, s47\n" U2PD(141) \
-    U2_DEC_AFTER_RANK
-#define U2_DEC_RANK_G1 \
-    "s_waitcnt lgkmcnt(1)\n" \
-    "v_and_b32 v33, s66, v30\n" \
-    "v_and_b32 v34, s67, v31\n" \
-    "v_bcnt_u32_b32 v33, v33, 0\n" \
-    "v_bcnt_u32_b32 v37, v34, v33\n" U2PD(140) \
-    "s_nop 0\n" \
-    "v_readfirstlane_b32 s64, v37\n" U2PD(141) \
-    U2_DEC_AFTER_RANK
-// ---- the step of k_roc_decode_u2 (the bucket kernels keep U2_DEC_MID / U2_DEC_RANK_* / U2_DEC_BOT_CORE* above; U2_DEC_TOP_L, the
-// index macros, U2_DEC_SIDE and U2_DEC_OUTER are shared).  Same data flow, 68 instructions instead of 74 with four words per entry
-// (62 instead of 67 with one), and ordered by the rule the encoder's dense step was built on: a scalar instruction issued within
-// ~16 cycles of a vector instruction that wrote an SGPR or VCC (v_readlane, v_cmp, v_addc) waits the window out, so each of the
-// two read-outs whose results the scalar unit needs is followed by four vector / LDS instructions (profiles/r21_roc_decode_step.txt
-// has the section tables and what each change bought).
+// ---- the step of k_roc_decode_u2 (the bucket kernels have their own index / middle / rank macros further down and share
+// U2_DEC_TOP_L, U2_DEC_AFTER_RANK, U2_DEC_BOT_CORE*, U2_DEC_SIDE and U2_DEC_OUTER).  Ordered by the rule the encoder's dense step was
+// built on: a scalar instruction issued within ~16 cycles of a vector instruction that wrote an SGPR or VCC (v_readlane, v_cmp,
+// v_addc) waits the window out, so each read-out whose result the scalar unit needs is followed by four vector / LDS instructions
+// (profiles/r21_roc_decode_step.txt and profiles/r27_roc_decode_rows_lds.txt have the section tables and what each change bought).
 //  * insertion: a ds_or by all 64 lanes, exec untouched (the two exec writes cost 8 cycles more than their issue slots).  v8 / v9
-//    are per-lane constants (lane 0: v8 = 4, v9 = 0; lane j: v8 = 0, v9 = BITMAP_BYTES + 4 j): one v_mad_u32_u24 sends lane 0 to the
-//    bitmap dword and every other lane to its own dword of the strip behind the bitmap (U2Geom::DEC_LDS_BYTES).  Address, bit and the
-//    ds_or sit BEHIND the rank's read-out, so the wait in front of the rank is lgkmcnt(0): the read of this step and the insertion of
-//    the previous one (LDS operations of a wavefront complete in order, the next read sees the bit).
-//  * rank: E1[L1] rides in on the addend of a v_bcnt and row[L2] on a v_add3, so the read-out is the whole rank and head' is one
-//    64-bit add (the two scalar adds are gone).
+//    are per-lane constants (lane 0: v8 = 4, v9 = DEC_BITMAP_OFF; lane j: v8 = 0, v9 = DEC_STRIP_OFF + 4 j): one v_mad_u32_u24 sends
+//    lane 0 to the bitmap dword and every other lane to its own dword of the strip behind the bitmap.  Address, bit and the ds_or sit
+//    BEHIND the rank's read-out, so the wait in front of the rank is lgkmcnt(0): the reads of this step and the insertion of the
+//    previous one (LDS operations of a wavefront complete in order, the next read sees the bit).
+//  * level-2 counters: u32 row[64][64] at the front of the LDS, not in registers (the encoders search a row across lanes, the
+//    decoder reads ONE element and increments a lane prefix).  The element is a ds_read_b32 of dword `entry` by all lanes (a
+//    broadcast) issued next to the bitmap read; the update is a ds_add_u32 by all lanes (lane j: dword j of row L1, data 1 below L2
+//    and 0 elsewhere: no exec write, no VCC, no write-back) behind the ds_or, and the next step's read sees it by the same in-order
+//    argument.  No s_set_gpr_idx bracket and no v_readlane of the row is left in the step.
+//  * rank: E1[L1] rides in on the addend of a v_bcnt and the row element on a v_add3 (a VGPR operand now), so the read-out is the
+//    whole rank and head' is one 64-bit add.
 //  * counters: the E1 update is v_cmp_gt (L1 > lane) + v_addc_co (+ 0 + carry) inside the rank's vector block, where vector work
-//    follows both; the v_addc takes the wait state in front of the read-out (s_nop 0 before).  The row keeps the three-instruction
-//    form: it writes no SGPR and fills the window of the three read-outs of U2_DEC_MID_U (as v_cmp + v_addc there the step was
-//    0.6 ns longer with four words per entry and 4.3 ns longer with one).
-#define U2_DEC_MID_U \
+//    follows both; the v_addc takes the wait state in front of the read-out.  Row address and the 0 / 1 data of the ds_add write no
+//    SGPR and fill the window of the two read-outs of U2_DEC_MID_U together with the ring write.
+//    The data is (lane - L2) >> 31 in two vector instructions with one word per entry; with four words it is s_bfm (lanes below L2,
+//    ahead of the read-outs) + v_cndmask on that mask, and the insertion's address takes the freed slot of the window: 0.4 .. 0.8 ns
+//    shorter there, 2.9 ns longer with one word (profiles/r27_roc_decode_rows_lds.txt, candidates c0 / c2).
+#define U2_DEC_INS_ADDR "v_mad_u32_u24 v26, s65, v8, v9\n" /* insertion address: lane 0 the bitmap dword, lane j its strip dword */
+#define U2_DEC_MID_U_G4 U2_DEC_MID_U("s_bfm_b64 s[98:99], s44, 0\n", "v_cndmask_b32_e64 v39, 0, 1, s[98:99]\n" U2_DEC_INS_ADDR)
+#define U2_DEC_MID_U_G1 U2_DEC_MID_U("", "v_subrev_u32 v39, s44, v2\n" "v_lshrrev_b32 v39, 31, v39\n")
+#define U2_DEC_MID_U(ROW_S, ROW_V)                     /* ROW_V: v39 = 1 in lanes below L2, 0 elsewhere; two instructions */ \
     "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
-    "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
-    "v_mov_b32 v13, v64\n" \
-    "s_set_gpr_idx_off\n" \
     "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */ \
+    ROW_S \
     "s_and_b32 m0, s60, 63\n" U2PD(134) \
     "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
-    "v_readlane_b32 s63, v13, s44\n"                   /* row[L2] */ \
-    "v_subrev_u32 v59, s44, v2\n" \
-    "v_ashrrev_i32 v59, 31, v59\n" \
-    "v_sub_u32 v13, v13, v59\n"                        /* row += 1 in lanes below L2 */ \
+    "v_lshl_add_u32 v38, s43, 8, v11\n"                /* lane j: dword j of row L1 */ \
+    ROW_V \
     "v_writelane_b32 v5, s58, m0\n"                    /* index push, first half (codec.cpp:44-63): the word, kept if H renormalises */ U2PD(135) \
     "s_cmp_ge_u32 s59, s62\n" \
     "s_cselect_b32 s50, s59, s58\n" \
@@ -1288,16 +1247,14 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
     "s_mul_hi_u32 s53, s50, s75\n" \
     "s_mul_i32 s68, s51, s75\n" \
-    "s_add_u32 s53, s53, s68\n" U2PD(137) \
-    "s_set_gpr_idx_on s43, gpr_idx(DST)\n" \
-    "v_mov_b32 v64, v13\n" \
-    "s_set_gpr_idx_off\n" \
-    "s_mov_b32 m0, s69\n" U2PD(138)
-#define U2_DEC_RANK_TAIL_U \
-    "v_mad_u32_u24 v26, s65, v8, v9\n"                 /* insertion address: lane 0 the bitmap dword, lane j its strip dword */ \
+    "s_add_u32 s53, s53, s68\n" \
+    "s_mov_b32 m0, s69\n" U2PD(137)
+#define U2_DEC_RANK_TAIL_U(INS_ADDR) \
+    INS_ADDR \
     "v_lshlrev_b32_e64 v27, s40, 1\n" \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
-    "ds_or_b32 v26, v27\n"                             /* insertion of x */ U2PD(141)
+    "ds_or_b32 v26, v27\n"                             /* insertion of x */ \
+    "ds_add_u32 v38, v39\n"                            /* row += 1 in lanes below L2 */ U2PD(141)
 #define U2_DEC_RANK_U_G4 \
     "s_waitcnt lgkmcnt(0)\n" \
     "v_bcnt_u32_b32 v32, v30, 0\n" \
@@ -1310,10 +1267,10 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_add_u32_dpp v36, v35, v35 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
     "v_sub_u32 v33, v33, v32\n" \
     "v_cmp_gt_u32 vcc, s43, v2\n" \
-    "v_add3_u32 v37, v36, v33, s63\n"                  /* lane g: the rank of x */ U2PD(139) \
+    "v_add3_u32 v37, v36, v33, v29\n"                  /* + row[L1][L2]; lane g: the rank of x */ U2PD(139) \
     "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes below L1 */ \
     "v_readlane_b32 s64, v37, s47\n" U2PD(140) \
-    U2_DEC_RANK_TAIL_U
+    U2_DEC_RANK_TAIL_U("")
 #define U2_DEC_RANK_U_G1 \
     "s_waitcnt lgkmcnt(0)\n" \
     "v_and_b32 v33, s66, v30\n" \
@@ -1321,10 +1278,10 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_bcnt_u32_b32 v33, v33, s49\n" \
     "v_bcnt_u32_b32 v33, v34, v33\n" \
     "v_cmp_gt_u32 vcc, s43, v2\n" \
-    "v_add_u32 v37, s63, v33\n" U2PD(139) \
+    "v_add_u32 v37, v29, v33\n" U2PD(139) \
     "v_addc_co_u32 v4, vcc, 0, v4, vcc\n" \
     "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
-    U2_DEC_RANK_TAIL_U
+    U2_DEC_RANK_TAIL_U(U2_DEC_INS_ADDR)
 #define U2_DEC_BOT_T_U(RLO, RSPAN)                     /* (U2_DEC_BOT_CORE_T with the rank in one register) */ \
     "s_sub_u32 s68, s60, s61\n"                        /* ring: two pops and one push must fit the next step */ \
     "s_add_u32 s68, s68, " RLO "\n" \
@@ -1345,13 +1302,13 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
     "s_cselect_b32 s71, s70, 0\n" U2PD(143) \
     "s_cmp_lt_u32 s69, s71\n"
-#define U2_DEC_STEP_U(IDX, RANK, LA, LB, LC, LD) U2_DEC_TOP_L(LA, LB, LC, LD) IDX U2_DEC_MID_U RANK U2_DEC_BOT_NR_U "s_cbranch_scc0 2f\n"
-#define U2_DEC_LOOP8_U(IDX, RANK) \
-    "1:\n" U2_DEC_STEP_U(IDX, RANK, "20", "21", "22", "23") U2_DEC_STEP_U(IDX, RANK, "30", "31", "32", "33") \
-    U2_DEC_STEP_U(IDX, RANK, "40", "41", "42", "43") U2_DEC_STEP_U(IDX, RANK, "50", "51", "52", "53") \
-    U2_DEC_STEP_U(IDX, RANK, "60", "61", "62", "63") U2_DEC_STEP_U(IDX, RANK, "70", "71", "72", "73") \
-    U2_DEC_STEP_U(IDX, RANK, "80", "81", "82", "83") \
-    U2_DEC_TOP_L("90", "91", "92", "93") IDX U2_DEC_MID_U RANK U2_DEC_BOT_T_U("-18", "35") "s_cbranch_scc1 1b\n s_branch 2f\n" \
+#define U2_DEC_STEP_U(IDX, MID, RANK, LA, LB, LC, LD) U2_DEC_TOP_L(LA, LB, LC, LD) IDX MID RANK U2_DEC_BOT_NR_U "s_cbranch_scc0 2f\n"
+#define U2_DEC_LOOP8_U(IDX, MID, RANK) \
+    "1:\n" U2_DEC_STEP_U(IDX, MID, RANK, "20", "21", "22", "23") U2_DEC_STEP_U(IDX, MID, RANK, "30", "31", "32", "33") \
+    U2_DEC_STEP_U(IDX, MID, RANK, "40", "41", "42", "43") U2_DEC_STEP_U(IDX, MID, RANK, "50", "51", "52", "53") \
+    U2_DEC_STEP_U(IDX, MID, RANK, "60", "61", "62", "63") U2_DEC_STEP_U(IDX, MID, RANK, "70", "71", "72", "73") \
+    U2_DEC_STEP_U(IDX, MID, RANK, "80", "81", "82", "83") \
+    U2_DEC_TOP_L("90", "91", "92", "93") IDX MID RANK U2_DEC_BOT_T_U("-18", "35") "s_cbranch_scc1 1b\n s_branch 2f\n" \
     U2_DEC_SIDE("20", "21", "22", "23") U2_DEC_SIDE("30", "31", "32", "33") U2_DEC_SIDE("40", "41", "42", "43") \
     U2_DEC_SIDE("50", "51", "52", "53") U2_DEC_SIDE("60", "61", "62", "63") U2_DEC_SIDE("70", "71", "72", "73") \
     U2_DEC_SIDE("80", "81", "82", "83") U2_DEC_SIDE("90", "91", "92", "93") "2:\n"
@@ -1465,7 +1422,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 
 // one generic decode step on the reversed structures (rare path): codec.cpp:144-150
 template <int UB>
-__device__ __forceinline__ uint32_t u2_slow_dec_step(uint64_t &head, WStack &st, uint32_t nmax, uint32_t &E1, v32u &ra, v32u &rb,
+__device__ __forceinline__ uint32_t u2_slow_dec_step(uint64_t &head, WStack &st, uint32_t nmax, uint32_t &E1, uint32_t *rows,
                                                      uint64_t *bm, uint32_t p0, uint32_t p1) {
     using U = U2Geom<UB>;
     const uint32_t lane = lane_id();
@@ -1473,15 +1430,13 @@ __device__ __forceinline__ uint32_t u2_slow_dec_step(uint64_t &head, WStack &st,
     const uint32_t x = ans_id_pop(head, st, p0, p1);
     const uint32_t e = (x >> U::ESH) ^ (U::NE - 1u);
     const uint32_t L1 = e >> 6, L2 = e & 63u, g = (x >> 6) & (U::G - 1u), b = x & 63u;
-    uint32_t row = u2_row_get(ra, rb, L1);
-    uint32_t r = rl(E1, L1) + rl(row, L2);
+    uint32_t r = rl(E1, L1) + rfl(rows[e]);  // row[L1][L2]
     for (uint32_t j = 0; j < g; j++) r += popc64(rfl64(bm[e * U::G + j]));
     const uint64_t W = rfl64(bm[e * U::G + g]);
     r += popc64(W & ((1ull << b) - 1ull));
     ans_idx_push(head, st, r, nmax, 0x80000000u / nmax);
     E1 += lane < L1 ? 1u : 0u;
-    row += lane < L2 ? 1u : 0u;
-    u2_row_set(ra, rb, L1, row);
+    rows[L1 * 64u + lane] += lane < L2 ? 1u : 0u;
     bm[e * U::G + g] = W | (1ull << b);
     wave_sync();
     return x;
@@ -1491,7 +1446,8 @@ template <int UB>
 __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div *__restrict__ dtab) {
     using U = U2Geom<UB>;
     extern __shared__ __align__(16) unsigned char smem[];
-    uint64_t *bm = (uint64_t *)smem;
+    uint32_t *rows = (uint32_t *)smem;  // row[64][64], then the bitmap, then the insertion strip (U2Geom)
+    uint64_t *bm = (uint64_t *)(smem + U::DEC_BITMAP_OFF);
     const uint32_t lane = lane_id();
     const uint32_t wi = blockIdx.x;
     if (wi >= a.nwork) return;
@@ -1511,11 +1467,9 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
     const uint32_t draws0 = st.draws;
     uint64_t head = rfl64(a.heads[l]);
     uint32_t E1 = 0;
-    v32u ra, rb;
-#pragma unroll
-    for (int c = 0; c < 32; c++) { ra[c] = 0u; rb[c] = 0u; }
-    const uint32_t l3off = U::G == 4u ? (lane & 3u) * 8u : 0u;
-    const uint32_t ins_mul = lane == 0u ? 4u : 0u, ins_add = lane == 0u ? 0u : U::BITMAP_BYTES + 4u * lane;  // U2_DEC_MID_U
+    const uint32_t l3off = U::DEC_BITMAP_OFF + (U::G == 4u ? (lane & 3u) * 8u : 0u);  // U2_DEC_IDX_*
+    const uint32_t ins_mul = lane == 0u ? 4u : 0u, ins_add = lane == 0u ? U::DEC_BITMAP_OFF : U::DEC_STRIP_OFF + 4u * lane;  // U2_DEC_RANK_TAIL_U
+    const uint32_t row_lane = 4u * lane;  // U2_DEC_MID_U
     const uint32_t M1 = (1u << p1) - 1u, M0 = (1u << p0) - 1u;
     uint64_t *out = a.out + ooff;
     wave_sync();
@@ -1539,7 +1493,7 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
         }
         if (lt_2p31(head) || st.sp - st.lo < RING_LO || st.sp - st.lo > RING_HI) {  // generic step
             U2_DBG(0);
-            const uint32_t x = u2_slow_dec_step<UB>(head, st, i + 1u, E1, ra, rb, bm, p0, p1);
+            const uint32_t x = u2_slow_dec_step<UB>(head, st, i + 1u, E1, rows, bm, p0, p1);
             if (lane == 0) out[n - 1u - i] = (uint64_t)x;
             i++;
             continue;
@@ -1552,22 +1506,17 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
         // clang-format off
 #define U2_DEC_ASM(BODY)                                                                                                  \
         asm volatile(BODY                                                                                                 \
-            : "+{v4}"(E1), "+{v5}"(st.win), "+{v[6:7]}"(oring), "+{v[64:95]}"(ra), "+{v[96:127]}"(rb),                     \
+            : "+{v4}"(E1), "+{v5}"(st.win), "+{v[6:7]}"(oring),                                                           \
               "+{s[58:59]}"(s_h), "+{s60}"(st.sp), "+{s69}"(s_t), "+{s85}"(s_N0), "+{s86}"(s_left), "+{s87}"(s_oidx)        \
               U2P_OPERANDS                                                                                                 \
-            : "{v2}"(lane), "{v3}"(l3off), "{v8}"(ins_mul), "{v9}"(ins_add), "{s61}"(st.lo), "{s73}"(M1), "{s74}"(M0),      \
-              "{s76}"(p0), "{s77}"(p1), "{s[88:89]}"(out), "{s[94:95]}"(dtab)                                              \
-            : "memory", "vcc", "scc", "v10", "v13", "v26", "v27", "v28", "v30", "v31", "v32", "v33", "v34", "v35", "v36",     \
-              "v37", "v54", "v55", "v56", "v57", "v58", "v59", "s40", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50",\
-              "s51", "s52", "s53", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", "s97",\
+            : "{v2}"(lane), "{v3}"(l3off), "{v8}"(ins_mul), "{v9}"(ins_add), "{v11}"(row_lane), "{s61}"(st.lo),            \
+              "{s73}"(M1), "{s74}"(M0), "{s76}"(p0), "{s77}"(p1), "{s[88:89]}"(out), "{s[94:95]}"(dtab)                     \
+            : "memory", "vcc", "scc", "v10", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36",     \
+              "v37", "v38", "v39", "v54", "v55", "v56", "v57", "v58", "s40", "s43", "s44", "s45", "s46", "s47", "s49", "s50", \
+              "s51", "s52", "s53", "s62", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", "s97",       \
               "s98", "s99" U2PD_CLOBBERS)
-#if defined(U2_DEC_SHARED_STEP)  // dev (tools/chain_u2.hip): the step the bucket kernels run, for the 'before' rows of a section table
-        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8(U2_DEC_IDX_G4, U2_DEC_MID, U2_DEC_RANK_G4) U2_DEC_OUTER_T("-18", "35"));
-        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8(U2_DEC_IDX_G1, U2_DEC_MID, U2_DEC_RANK_G1) U2_DEC_OUTER_T("-18", "35"));
-#else
-        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
-        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
-#endif
+        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U_G4, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
+        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_MID_U_G1, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
 #undef U2_DEC_ASM
         // clang-format on
         head = s_h;
