@@ -129,9 +129,9 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
 #ifdef U2_PROF
         {   // the decode step's sections (the last launch of k_roc_decode_u2 left them in the slots array)
             uint32_t dp[14]; CK(hipMemcpy(dp, d_slots, 56, hipMemcpyDeviceToHost));
-            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, 2 addresses, 2 ds_read, g, dword (9)",
-                "MID: L1, L2, bfm, [bfm,] m0 (5 / 4)", "MID: 2 readlanes, row address, data, [address,] ring write (6)", "MID: renormalise H (4)", "MID: H * nmax, m0 (5)",
-                "(unused)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: [address,] bit, ring write, ds_or, ds_add (4 / 5)", "(unused)",
+            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, 2 addresses, 2 ds_read, [g,] dword (7 / 6)",
+                "MID: L1, L2, bfm, m0 (4)", "MID: 2 readlanes, row address, data (2), ring write (6)", "MID: renormalise H (4)", "MID: H * nmax, m0 (5)",
+                "(unused)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: address, bit, ring write, ds_or, ds_add (5)", "(unused)",
                 "BOT: counters, head', refill test (6) [+ cmp, branch]"};
             double tot = 0, pc = (double)dp[1] / n;
             int np = 0;  // probes the step has (a slot the step does not use stays 0)

@@ -22,6 +22,10 @@
 //    (U2Dense, U2_ENC_*_D below): the third search level, the bit select and the rewrite of the bitmap word become one LDS read
 //    by all lanes, one v_readlane and a 16-bit store by all lanes (79 instructions per step against 102).  The kernel decides per list;
 //    RocEncArgs::dense = 0 (VIDC_U2_DENSE=0) keeps every list on the bitmap body.
+//    Its level-2 rows stay in v64..v127.  u16 rows in LDS behind the strip (one ds_read_u16 of row L1 behind s_ff1, one
+//    ds_write_b16 in place of the register write-back: 77 instructions) were measured and left out: 179.0 ns per step with the
+//    store where the write-back was and 184.0 ns with it in the window of the level-2 read-out, against 174.4 ns; an LDS
+//    instruction costs a lone wavefront more than the index bracket it replaces (profiles/r28_roc_chain_rows_order.txt).
 //
 // Anything rare (index-pop renormalisation, stack underflow, nmax <= 2, ring spills) leaves the asm loop at a step
 // boundary and runs one generic C++ step (u2_slow_step) on the same data structures.
@@ -29,49 +33,10 @@
 // general kernels through VIDC_ST_PENDING_SORT like roc_u.h does for multisets.
 #pragma once
 #include "roc_u.h"
+#include "roc_u2_geom.h"  // U2Geom, U2Dense, u2_enc_lds_bytes
 
 namespace vidc {
 namespace dev {
-
-template <int UB>
-struct U2Geom {
-    static_assert(UB == 18 || UB == 20, "universe bits");
-    static constexpr uint32_t GSH = UB == 20 ? 2u : 0u;   // log2(bitmap words per level-2 entry)
-    static constexpr uint32_t G = 1u << GSH;
-    static constexpr uint32_t ESH = 6u + GSH;             // id bits below the entry index
-    static constexpr uint32_t NE = 4096u;                 // 64 blocks x 64 entries
-    static constexpr uint32_t BITMAP_BYTES = NE * G * 8u;
-    static constexpr uint32_t LDS_BYTES = BITMAP_BYTES + 16u;  // + a dummy word: target of the "no pending removal" store
-    // k_roc_decode_u2: the level-2 counters u32 row[64][64] in FRONT of the bitmap (row[L1][L2] is dword `entry`; a DS offset field
-    // has 16 bits, so nothing that wants one can sit behind a 128 KiB bitmap), and a strip of one dword per lane behind the bitmap.
-    // The insertion is a ds_or by ALL lanes: lane 0 hits the bitmap, lane j > 0 its own dword of the strip (no exec write in the step,
-    // no two lanes on one address).  147 712 bytes with 20 universe bits, 49 408 with 18 (no set_big_lds).
-    static constexpr uint32_t DEC_ROWS_BYTES = 64u * 64u * 4u;
-    static constexpr uint32_t DEC_BITMAP_OFF = DEC_ROWS_BYTES;
-    static constexpr uint32_t DEC_STRIP_OFF = DEC_BITMAP_OFF + BITMAP_BYTES;
-    static constexpr uint32_t DEC_LDS_BYTES = DEC_STRIP_OFF + 256u;
-};
-
-// Dense 16-id blocks in POSITION space (k_roc_encode_u2<20> only, lists of 4097 .. 65 536 ids): block b holds the ids at positions
-// 16 b .. 16 b + 15 of the ascending input as 16 u16 slots (id - first id of the block) and the first id in a u32 table.  Blocks are
-// stored in REVERSED order like the bitmap entries (storage index e = 4095 - b = L1 * 64 + L2 of the reversed counters).  The base
-// table sits in FRONT of the slots so that its read takes the 16-bit offset field (one address instruction instead of two); a step
-// reads 64 u16 from the block's first slot on, i.e. up to 96 bytes past the block: the pad behind the last block.
-struct U2Dense {
-    static constexpr uint32_t MIN_N = 4096u;              // shorter lists stay with the lane / general kernels anyway
-    static constexpr uint32_t MAX_N = 65536u;             // 4096 blocks
-    static constexpr uint32_t BASE_OFF = 16u;             // u32 base[4096]
-    static constexpr uint32_t SLOT_OFF = BASE_OFF + 4096u * 4u;  // u16 slot[4096][16]
-    // behind the pad: a strip of one dword per lane.  The removal's ds_write_b16 runs in ALL lanes: a lane that shifts hits the slot
-    // below its own, every other lane its own dword of the strip (no exec write in the step, no two lanes on one address)
-    static constexpr uint32_t STRIP_OFF = SLOT_OFF + 4096u * 32u + 128u;
-    static constexpr uint32_t LDS_BYTES = STRIP_OFF + 256u;
-};
-// LDS bytes of a k_roc_encode_u2<UB, *> launch
-template <int UB>
-constexpr uint32_t u2_enc_lds_bytes(bool dense) {
-    return UB == 20 && dense && U2Dense::LDS_BYTES > U2Geom<UB>::LDS_BYTES ? U2Dense::LDS_BYTES : U2Geom<UB>::LDS_BYTES;
-}
 
 // LDS word index of id x: entries are stored in REVERSED order (entry e' = e ^ 4095), words inside an entry ascending
 template <int UB>
@@ -79,6 +44,10 @@ __device__ __forceinline__ uint32_t u2_word_of(uint32_t x) {
     using U = U2Geom<UB>;
     return (((x >> U::ESH) ^ (U::NE - 1u)) << U::GSH) | ((x >> 6) & (U::G - 1u));
 }
+
+// k_roc_decode_u2 keeps its entries in NATURAL order (it never searches, see the decode section): an entry's words are
+// x >> 6 for its ids x, the insertion's dword is x >> 5.  The encoder's bitmap bodies stay with u2_word_of.
+__device__ __forceinline__ uint32_t u2_dec_word_of(uint32_t x) { return x >> 6; }
 
 // Per-divisor constants (16 bytes, table built once per context, vidc_ctx::d_u2tab, VIDC_ROC_MAX_LIST + 1 entries):
 //   x = floor((2^64 - 1) / d) low, y = high, z = floor(2^32 / d) (d >= 2), w = floor(2^31 / d).  Entry 0 is all zero.
@@ -1120,8 +1089,13 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //
 // head' = H * nmax + r with H (the head after the two slice pops, renormalised for the index push) independent of the
 // rank r: the push renormalisation, the 64 x 32 multiply and all insertions run in the shadow of the LDS read; r joins with
-// one 64-bit add, and the next id is a bit field of that sum.  The set is a bitmap over the id universe with the same
-// reversed exclusive counters as the encoder (rank = E1[L1] + row[L1][L2] + set bits below x inside its entry).
+// one 64-bit add, and the next id is a bit field of that sum.  The set is a bitmap over the id universe with two levels of
+// exclusive counters (rank = E1[L1] + row[L1][L2] + set bits below x inside its entry).  k_roc_decode_u2 keeps entries, rows and
+// E1 in NATURAL order: entry = x >> ESH, E1[L] = ids in blocks below L, row[L1][L] = ids of block L1 in entries below L.  The
+// encoders reverse the order because their search wants "counter <= k" to be true from the wanted lane upwards; the decoder never
+// searches, it computes a rank and inserts into structures it builds itself from empty LDS and that nothing else reads, so the
+// reversal only cost it an s_xor and a two-instruction insertion dword per step (the dword is x >> 5 now).  The bucket kernels
+// (k_roc_decode_b2) keep the reversed counters in registers that they share with the encoders' helpers.
 // Multiset streams (reference quirk regimes) cannot be represented by a bitmap: the number of set bits is compared with
 // n at the end and such a list is decoded again by the round-1 kernel body, which keeps a side list of duplicates.
 //
@@ -1180,24 +1154,20 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     LD ":\n" \
     "s_pack_ll_b32_b16 s40, s40, s46\n"                /* x = x_hi : x_lo (one instruction, round 5) */ U2PD(132)
 #define U2_DEC_IDX_G4 \
-    "s_lshr_b32 s45, s40, 8\n" \
-    "s_xor_b32 s45, s45, 0xfff\n"                      /* entry (reversed) */ \
+    "s_lshr_b32 s45, s40, 8\n"                         /* entry (natural order: the decoder never searches) */ \
     "v_lshl_add_u32 v28, s45, 5, v3\n" \
     "v_lshlrev_b32_e64 v29, 2, s45\n"                  /* row[L1][L2] is dword `entry` of the LDS */ \
     "ds_read_b64 v[30:31], v28\n" \
     "ds_read_b32 v29, v29\n"                           /* (one address in every lane: a broadcast) */ \
     "s_bfe_u32 s47, s40, 0x20006\n"                    /* g */ \
-    "s_bfe_u32 s65, s40, 0x30005\n"                    /* 32-bit half of the entry holding x */ \
-    "s_lshl3_add_u32 s65, s45, s65\n"                  /* (dword of the bitmap; the insertion's v_mad makes it a byte address) */ U2PD(133)
+    "s_lshr_b32 s65, s40, 5\n"                         /* dword of the bitmap holding x (the insertion's v_mad makes it a byte address) */ U2PD(133)
 #define U2_DEC_IDX_G1 \
     "s_lshr_b32 s45, s40, 6\n" \
-    "s_xor_b32 s45, s45, 0xfff\n" \
     "v_lshl_add_u32 v28, s45, 3, v3\n" \
     "v_lshlrev_b32_e64 v29, 2, s45\n" \
     "ds_read_b64 v[30:31], v28\n" \
     "ds_read_b32 v29, v29\n" \
-    "s_bfe_u32 s65, s40, 0x10005\n" \
-    "s_lshl1_add_u32 s65, s45, s65\n" U2PD(133)
+    "s_lshr_b32 s65, s40, 5\n" U2PD(133)
 // (the three vector instructions that follow the last readlane of the rank keep the scalar tail off its SGPR write)
 #define U2_DEC_AFTER_RANK \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
@@ -1214,31 +1184,31 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //    BEHIND the rank's read-out, so the wait in front of the rank is lgkmcnt(0): the reads of this step and the insertion of the
 //    previous one (LDS operations of a wavefront complete in order, the next read sees the bit).
 //  * level-2 counters: u32 row[64][64] at the front of the LDS, not in registers (the encoders search a row across lanes, the
-//    decoder reads ONE element and increments a lane prefix).  The element is a ds_read_b32 of dword `entry` by all lanes (a
-//    broadcast) issued next to the bitmap read; the update is a ds_add_u32 by all lanes (lane j: dword j of row L1, data 1 below L2
+//    decoder reads ONE element and increments the lanes above it).  The element is a ds_read_b32 of dword `entry` by all lanes (a
+//    broadcast) issued next to the bitmap read; the update is a ds_add_u32 by all lanes (lane j: dword j of row L1, data 1 above L2
 //    and 0 elsewhere: no exec write, no VCC, no write-back) behind the ds_or, and the next step's read sees it by the same in-order
 //    argument.  No s_set_gpr_idx bracket and no v_readlane of the row is left in the step.
 //  * rank: E1[L1] rides in on the addend of a v_bcnt and the row element on a v_add3 (a VGPR operand now), so the read-out is the
 //    whole rank and head' is one 64-bit add.
-//  * counters: the E1 update is v_cmp_gt (L1 > lane) + v_addc_co (+ 0 + carry) inside the rank's vector block, where vector work
+//  * counters: the E1 update is v_cmp_lt (L1 < lane) + v_addc_co (+ 0 + carry) inside the rank's vector block, where vector work
 //    follows both; the v_addc takes the wait state in front of the read-out.  Row address and the 0 / 1 data of the ds_add write no
 //    SGPR and fill the window of the two read-outs of U2_DEC_MID_U together with the ring write.
-//    The data is (lane - L2) >> 31 in two vector instructions with one word per entry; with four words it is s_bfm (lanes below L2,
-//    ahead of the read-outs) + v_cndmask on that mask, and the insertion's address takes the freed slot of the window: 0.4 .. 0.8 ns
-//    shorter there, 2.9 ns longer with one word (profiles/r27_roc_decode_rows_lds.txt, candidates c0 / c2).
+//    The data is (L2 - lane) >> 31 in two vector instructions in both geometries.  The other form, a scalar mask of the lanes above
+//    L2 (s_lshl_b64 -2, L2) + v_cndmask with the insertion's address in the freed slot of the window, is 1.2 ns longer with four
+//    words per entry and 2 ns longer with one (profiles/r28_roc_chain_rows_order.txt; with reversed entries the four-word body had
+//    preferred it by 0.4 .. 0.8 ns, profiles/r27_roc_decode_rows_lds.txt).
+//  * 62 instructions per step with four words per entry, 56 with one.
 #define U2_DEC_INS_ADDR "v_mad_u32_u24 v26, s65, v8, v9\n" /* insertion address: lane 0 the bitmap dword, lane j its strip dword */
-#define U2_DEC_MID_U_G4 U2_DEC_MID_U("s_bfm_b64 s[98:99], s44, 0\n", "v_cndmask_b32_e64 v39, 0, 1, s[98:99]\n" U2_DEC_INS_ADDR)
-#define U2_DEC_MID_U_G1 U2_DEC_MID_U("", "v_subrev_u32 v39, s44, v2\n" "v_lshrrev_b32 v39, 31, v39\n")
-#define U2_DEC_MID_U(ROW_S, ROW_V)                     /* ROW_V: v39 = 1 in lanes below L2, 0 elsewhere; two instructions */ \
+#define U2_DEC_MID_U \
     "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
     "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */ \
-    ROW_S \
     "s_and_b32 m0, s60, 63\n" U2PD(134) \
     "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
     "v_lshl_add_u32 v38, s43, 8, v11\n"                /* lane j: dword j of row L1 */ \
-    ROW_V \
+    "v_sub_u32 v39, s44, v2\n" \
+    "v_lshrrev_b32 v39, 31, v39\n"                     /* 1 in lanes above L2, 0 elsewhere */ \
     "v_writelane_b32 v5, s58, m0\n"                    /* index push, first half (codec.cpp:44-63): the word, kept if H renormalises */ U2PD(135) \
     "s_cmp_ge_u32 s59, s62\n" \
     "s_cselect_b32 s50, s59, s58\n" \
@@ -1249,12 +1219,12 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_mul_i32 s68, s51, s75\n" \
     "s_add_u32 s53, s53, s68\n" \
     "s_mov_b32 m0, s69\n" U2PD(137)
-#define U2_DEC_RANK_TAIL_U(INS_ADDR) \
-    INS_ADDR \
+#define U2_DEC_RANK_TAIL_U \
+    U2_DEC_INS_ADDR \
     "v_lshlrev_b32_e64 v27, s40, 1\n" \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
     "ds_or_b32 v26, v27\n"                             /* insertion of x */ \
-    "ds_add_u32 v38, v39\n"                            /* row += 1 in lanes below L2 */ U2PD(141)
+    "ds_add_u32 v38, v39\n"                            /* row += 1 in lanes above L2 */ U2PD(141)
 #define U2_DEC_RANK_U_G4 \
     "s_waitcnt lgkmcnt(0)\n" \
     "v_bcnt_u32_b32 v32, v30, 0\n" \
@@ -1266,22 +1236,22 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_bcnt_u32_b32 v33, v34, v33\n"                   /* ... the bits below b */ \
     "v_add_u32_dpp v36, v35, v35 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n" \
     "v_sub_u32 v33, v33, v32\n" \
-    "v_cmp_gt_u32 vcc, s43, v2\n" \
+    "v_cmp_lt_u32 vcc, s43, v2\n" \
     "v_add3_u32 v37, v36, v33, v29\n"                  /* + row[L1][L2]; lane g: the rank of x */ U2PD(139) \
-    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes below L1 */ \
+    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes above L1 */ \
     "v_readlane_b32 s64, v37, s47\n" U2PD(140) \
-    U2_DEC_RANK_TAIL_U("")
+    U2_DEC_RANK_TAIL_U
 #define U2_DEC_RANK_U_G1 \
     "s_waitcnt lgkmcnt(0)\n" \
     "v_and_b32 v33, s66, v30\n" \
     "v_and_b32 v34, s67, v31\n" \
     "v_bcnt_u32_b32 v33, v33, s49\n" \
     "v_bcnt_u32_b32 v33, v34, v33\n" \
-    "v_cmp_gt_u32 vcc, s43, v2\n" \
+    "v_cmp_lt_u32 vcc, s43, v2\n" \
     "v_add_u32 v37, v29, v33\n" U2PD(139) \
     "v_addc_co_u32 v4, vcc, 0, v4, vcc\n" \
     "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
-    U2_DEC_RANK_TAIL_U(U2_DEC_INS_ADDR)
+    U2_DEC_RANK_TAIL_U
 #define U2_DEC_BOT_T_U(RLO, RSPAN)                     /* (U2_DEC_BOT_CORE_T with the rank in one register) */ \
     "s_sub_u32 s68, s60, s61\n"                        /* ring: two pops and one push must fit the next step */ \
     "s_add_u32 s68, s68, " RLO "\n" \
@@ -1420,7 +1390,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     U2_DEC_FLUSH \
     "s_waitcnt vmcnt(0)\n"
 
-// one generic decode step on the reversed structures (rare path): codec.cpp:144-150
+// one generic decode step on the decoder's structures (natural entry order; rare path): codec.cpp:144-150
 template <int UB>
 __device__ __forceinline__ uint32_t u2_slow_dec_step(uint64_t &head, WStack &st, uint32_t nmax, uint32_t &E1, uint32_t *rows,
                                                      uint64_t *bm, uint32_t p0, uint32_t p1) {
@@ -1428,16 +1398,16 @@ __device__ __forceinline__ uint32_t u2_slow_dec_step(uint64_t &head, WStack &st,
     const uint32_t lane = lane_id();
     ws_prepare(st);
     const uint32_t x = ans_id_pop(head, st, p0, p1);
-    const uint32_t e = (x >> U::ESH) ^ (U::NE - 1u);
-    const uint32_t L1 = e >> 6, L2 = e & 63u, g = (x >> 6) & (U::G - 1u), b = x & 63u;
+    const uint32_t e = x >> U::ESH, w = u2_dec_word_of(x);
+    const uint32_t L1 = e >> 6, L2 = e & 63u, g = w & (U::G - 1u), b = x & 63u;
     uint32_t r = rl(E1, L1) + rfl(rows[e]);  // row[L1][L2]
-    for (uint32_t j = 0; j < g; j++) r += popc64(rfl64(bm[e * U::G + j]));
-    const uint64_t W = rfl64(bm[e * U::G + g]);
+    for (uint32_t j = 0; j < g; j++) r += popc64(rfl64(bm[w - g + j]));
+    const uint64_t W = rfl64(bm[w]);
     r += popc64(W & ((1ull << b) - 1ull));
     ans_idx_push(head, st, r, nmax, 0x80000000u / nmax);
-    E1 += lane < L1 ? 1u : 0u;
-    rows[L1 * 64u + lane] += lane < L2 ? 1u : 0u;
-    bm[e * U::G + g] = W | (1ull << b);
+    E1 += lane > L1 ? 1u : 0u;
+    rows[L1 * 64u + lane] += lane > L2 ? 1u : 0u;
+    bm[w] = W | (1ull << b);
     wave_sync();
     return x;
 }
@@ -1515,8 +1485,8 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
               "v37", "v38", "v39", "v54", "v55", "v56", "v57", "v58", "s40", "s43", "s44", "s45", "s46", "s47", "s49", "s50", \
               "s51", "s52", "s53", "s62", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", "s97",       \
               "s98", "s99" U2PD_CLOBBERS)
-        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U_G4, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
-        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_MID_U_G1, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
+        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
+        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_MID_U, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
 #undef U2_DEC_ASM
         // clang-format on
         head = s_h;
@@ -1553,7 +1523,7 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
 
 // ===============================================================================================================
 // The decode loop for ids of any precision 12 <= P <= 31: k_roc_decode_b2.  The bitmap over the id universe of
-// k_roc_decode_u2 becomes 4096 value buckets over the top 12 bits: the same reversed exclusive counters give the number
+// k_roc_decode_u2 becomes 4096 value buckets over the top 12 bits: the encoders' reversed exclusive counters give the number
 // of decoded ids in smaller buckets, the members of x's bucket (<= 64, unsorted u32) sit in a row of global memory that
 // the wavefront reads with one load (lane j: member j) and compares with one v_cmp; the bucket sizes are u16 in LDS.
 // Members stored during the current 64-step block may not have reached memory yet: they are taken from the output
