@@ -1,6 +1,7 @@
 // chain_u2.hip -- dev tool: one long list through k_roc_encode_u (round 1), k_roc_encode_u2 (round 2, bitmap body) and, for ub 20,
 // k_roc_encode_u2 with dense 16-id blocks: identical head / words / order, ns per step of each (hipEvents, five repeats: min and
-// max); then the stream through k_roc_decode_u (round 1) and k_roc_decode_u2, five repeats each as well.
+// max); then the stream through k_roc_decode_u (round 1), k_roc_decode_u2 and, for ub 20, k_roc_decode_u2 on word-granular rows
+// (U2DecWord), five repeats each as well.  With -DU2_PROF the decode section table is the LAST decode arm's.
 // usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: section tables of the LAST encode arm run and of the k_roc_decode_u2 step;
 // -DU2_PROF2: generic steps, entries into the asm loop and bits in the bitmap of the last k_roc_decode_u2 launch)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I vector_db_id_compression_amd/csrc tools/chain_u2.hip -o /tmp/chain_u2
@@ -99,22 +100,25 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
         b.words = d_arena; b.word_off = d_woff; b.out = d_out; b.out_rows = nullptr; b.K = 0; b.scratch_words = d_scr; b.scratch_off = d_z;
         b.slots = d_slots; b.slots_off = d_z; b.end_state = d_end; b.status = d_st; b.mt = d_mt;
         CK(hipFuncSetAttribute((const void *)k_roc_decode_u<UB>, hipFuncAttributeMaxDynamicSharedMemorySize, UGeom<UB>::LDS_BYTES));
-        CK(hipFuncSetAttribute((const void *)k_roc_decode_u2<UB>, hipFuncAttributeMaxDynamicSharedMemorySize, U2Geom<UB>::DEC_LDS_BYTES));
-        std::vector<uint64_t> outv[2]; float dms[2], dms_max[2]; uint32_t dst[2], dend[2];
-        for (int which = 0; which < 2; which++) {
+        CK(hipFuncSetAttribute((const void *)k_roc_decode_u2<UB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, U2Geom<UB>::DEC_LDS_BYTES));
+        if (UB == 20) CK(hipFuncSetAttribute((const void *)k_roc_decode_u2<20, true>, hipFuncAttributeMaxDynamicSharedMemorySize, U2DecWord::LDS_BYTES));
+        const int ndarm = UB == 20 ? 3 : 2;  // arm 2: word-granular rows (U2DecWord), 20 universe bits only
+        std::vector<uint64_t> outv[3]; float dms[3], dms_max[3]; uint32_t dst[3], dend[3];
+        for (int which = 0; which < ndarm; which++) {
             dms[which] = 1e30f; dms_max[which] = 0.f;
             for (int rep = 0; rep < 6; rep++) {  // the first one warms up
                 CK(hipMemset(d_out, 0xee, (size_t)n * 8)); CK(hipMemset(d_st, 0xff, 4)); CK(hipMemset(d_end, 0xff, 4));
                 CK(hipEventRecord(e0, 0));
                 if (which == 0) hipLaunchKernelGGL((k_roc_decode_u<UB>), dim3(1), dim3(64), UGeom<UB>::LDS_BYTES, 0, b);
-                else hipLaunchKernelGGL((k_roc_decode_u2<UB>), dim3(1), dim3(64), U2Geom<UB>::DEC_LDS_BYTES, 0, b, (const U2Div *)d_tab);
+                else if (which == 1) hipLaunchKernelGGL((k_roc_decode_u2<UB, false>), dim3(1), dim3(64), U2Geom<UB>::DEC_LDS_BYTES, 0, b, (const U2Div *)d_tab);
+                else hipLaunchKernelGGL((k_roc_decode_u2<20, true>), dim3(1), dim3(64), U2DecWord::LDS_BYTES, 0, b, (const U2Div *)d_tab);
                 CK(hipEventRecord(e1, 0));
                 CK(hipDeviceSynchronize());
                 float ms; CK(hipEventElapsedTime(&ms, e0, e1));
                 if (rep) { dms[which] = std::min(dms[which], ms); dms_max[which] = std::max(dms_max[which], ms); }
             }
 #ifdef U2_PROF2
-            if (which == 1) { uint32_t dbg[4]; CK(hipMemcpy(dbg, d_slots, 16, hipMemcpyDeviceToHost)); printf("   decode dbg: slow steps %u, asm entries %u, bits %u, n %u -> decoded again by the round-1 body: %s\n", dbg[0], dbg[1], dbg[2], dbg[3], dbg[2] == dbg[3] ? "no" : "YES"); }
+            if (which >= 1) { uint32_t dbg[4]; CK(hipMemcpy(dbg, d_slots, 16, hipMemcpyDeviceToHost)); printf("   decode dbg: slow steps %u, asm entries %u, bits %u, n %u -> decoded again by the round-1 body: %s\n", dbg[0], dbg[1], dbg[2], dbg[3], dbg[2] == dbg[3] ? "no" : "YES"); }
 #endif
             outv[which].resize(n);
             CK(hipMemcpy(outv[which].data(), d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -126,11 +130,19 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
         printf("                         DECODE old %.1f ns/step, new %.1f ns/step; status %u/%u end state %u/%u first diff old/new at %zu, new/encoder order at %zu -> %s\n",
                dms[0] * 1e6 / n, dms[1] * 1e6 / n, dst[0], dst[1], dend[0], dend[1], dd, od, dsame ? "IDENTICAL" : "MISMATCH");
         printf("    five repeats, ns/step min..max: old %.1f..%.1f, u2 %.1f..%.1f\n", dms[0] * 1e6 / n, dms_max[0] * 1e6 / n, dms[1] * 1e6 / n, dms_max[1] * 1e6 / n);
+        if (ndarm == 3) {
+            size_t wd = 0; while (wd < n && outv[0][wd] == outv[2][wd]) wd++;
+            const bool wsame = wd == n && dst[2] == 0 && dend[2] == dend[0];
+            printf("    WORD ROWS %.1f..%.1f ns/step against u2 %.1f..%.1f (keep: max below min: %s); status %u end state %u first diff old/word at %zu -> %s\n",
+                   dms[2] * 1e6 / n, dms_max[2] * 1e6 / n, dms[1] * 1e6 / n, dms_max[1] * 1e6 / n, dms_max[2] < dms[1] ? "yes" : "NO", dst[2], dend[2], wd,
+                   wsame ? "IDENTICAL" : "MISMATCH");
+            dsame = dsame && wsame;
+        }
 #ifdef U2_PROF
         {   // the decode step's sections (the last launch of k_roc_decode_u2 left them in the slots array)
             uint32_t dp[14]; CK(hipMemcpy(dp, d_slots, 56, hipMemcpyDeviceToHost));
             const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, 2 addresses, 2 ds_read, [g,] dword (7 / 6)",
-                "MID: L1, L2, bfm, m0 (4)", "MID: 2 readlanes, row address, data (2), ring write (6)", "MID: renormalise H (4)", "MID: H * nmax, m0 (5)",
+                "MID: L1, L2, bfm, m0 (4)", "MID: 2 readlanes, row address, data (2 / 4), ring write (6 / 8)", "MID: renormalise H (4)", "MID: H * nmax, m0 (5)",
                 "(unused)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: address, bit, ring write, ds_or, ds_add (5)", "(unused)",
                 "BOT: counters, head', refill test (6) [+ cmp, branch]"};
             double tot = 0, pc = (double)dp[1] / n;

@@ -3,7 +3,8 @@
 (4 097 .. 70 000 ids, now and then up to 150 000: the reference's lossy regime) over universes 2^13 .. 2^20, dense lists,
 duplicates, unsorted input, explicit precisions below / above what the ids need.  Encoded and decoded by the new kernels,
 the round-1 bitmap kernels (VIDC_OLD_U=1) and the general kernels (VIDC_FORCE_GENERAL=1): streams, permutations and decoded
-arrays must be identical (and so must the chain kernels with VIDC_U2_DENSE=0: dense-block lists on the bitmap body); every list is
+arrays must be identical (and so must the chain kernels with VIDC_U2_DENSE=0 and VIDC_U2_DEC_WORD=0: dense-block lists on the bitmap
+body, 20-bit lists decoded by the four-word step); every list is
 also checked against the CPU oracle (stream + the reference's decode of it)."""
 import os
 import sys
@@ -15,10 +16,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle.pyoracle import Oracle  # noqa: E402  (dev tool: the checker)
 from vector_db_id_compression_amd.codecs import RocLists  # noqa: E402
 
-MODES = {"u2": {"VIDC_OLD_U": "0", "VIDC_FORCE_GENERAL": "0", "VIDC_U2_DENSE": "1"},
-         "bitmap": {"VIDC_OLD_U": "0", "VIDC_FORCE_GENERAL": "0", "VIDC_U2_DENSE": "0"},  # the bitmap body for every 20-bit list
-         "u1": {"VIDC_OLD_U": "1", "VIDC_FORCE_GENERAL": "0", "VIDC_U2_DENSE": "1"},
-         "general": {"VIDC_OLD_U": "0", "VIDC_FORCE_GENERAL": "1", "VIDC_U2_DENSE": "1"}}
+MODES = {"u2": {"VIDC_OLD_U": "0", "VIDC_FORCE_GENERAL": "0", "VIDC_U2_DENSE": "1", "VIDC_U2_DEC_WORD": "1"},
+         # the bitmap body for every 20-bit list on the encode side, the four-word step on u32 rows on the decode side
+         "bitmap": {"VIDC_OLD_U": "0", "VIDC_FORCE_GENERAL": "0", "VIDC_U2_DENSE": "0", "VIDC_U2_DEC_WORD": "0"},
+         "u1": {"VIDC_OLD_U": "1", "VIDC_FORCE_GENERAL": "0", "VIDC_U2_DENSE": "1", "VIDC_U2_DEC_WORD": "1"},
+         "general": {"VIDC_OLD_U": "0", "VIDC_FORCE_GENERAL": "1", "VIDC_U2_DENSE": "1", "VIDC_U2_DEC_WORD": "1"}}
 # third argument "wide": universes 2^21 .. 2^31 -- the position-bitmap chain kernel (k_roc_encode_r2) against the general
 # kernels (VIDC_NO_R2=1: through the normal classes, VIDC_FORCE_GENERAL=1: everything) and the oracle
 WIDE = len(sys.argv) > 3 and sys.argv[3] == "wide"

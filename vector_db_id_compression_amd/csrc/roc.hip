@@ -131,6 +131,12 @@ inline bool u2_dense() {
     const char *e = std::getenv("VIDC_U2_DENSE");
     return !(e && e[0] == '0' && !e[1]);
 }
+// VIDC_U2_DEC_WORD=0 decodes the 20-bit chain launch with the four-word step on U2Geom<20>::DEC_* (A/B runs and tests); default: the
+// one-word step on word-granular rows (roc_u2.h, U2DecWord).  Same output either way.
+inline bool u2_dec_word() {
+    const char *e = std::getenv("VIDC_U2_DEC_WORD");
+    return !(e && e[0] == '0' && !e[1]);
+}
 
 // test hook: VIDC_FORCE_GENERAL=1 routes every list through the general (sorted-position / bucket) kernels
 inline bool force_general() { return env_1("VIDC_FORCE_GENERAL"); }
@@ -1295,13 +1301,16 @@ int dec_launch_u(DecodeCall &c, int cls, RocDecArgs &b, hipStream_t st) {  // un
     const U2Div *dt = (const U2Div *)c.ctx->d_u2tab;
     if (cls == DC_U18) {
         if (old_u_kernels()) hipLaunchKernelGGL(k_roc_decode_u<18>, dim3(b.nwork), dim3(64), UGeom<18>::LDS_BYTES, st, b);
-        else hipLaunchKernelGGL(k_roc_decode_u2<18>, dim3(b.nwork), dim3(64), U2Geom<18>::DEC_LDS_BYTES, st, b, dt);
+        else hipLaunchKernelGGL((k_roc_decode_u2<18, false>), dim3(b.nwork), dim3(64), U2Geom<18>::DEC_LDS_BYTES, st, b, dt);
     } else if (old_u_kernels()) {
         VIDC_TRY(set_big_lds((const void *)k_roc_decode_u<20>, UGeom<20>::LDS_BYTES));
         hipLaunchKernelGGL(k_roc_decode_u<20>, dim3(b.nwork), dim3(64), UGeom<20>::LDS_BYTES, st, b);
+    } else if (u2_dec_word()) {
+        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20, true>, U2DecWord::LDS_BYTES));
+        hipLaunchKernelGGL((k_roc_decode_u2<20, true>), dim3(b.nwork), dim3(64), U2DecWord::LDS_BYTES, st, b, dt);
     } else {
-        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20>, U2Geom<20>::DEC_LDS_BYTES));
-        hipLaunchKernelGGL(k_roc_decode_u2<20>, dim3(b.nwork), dim3(64), U2Geom<20>::DEC_LDS_BYTES, st, b, dt);
+        VIDC_TRY(set_big_lds((const void *)k_roc_decode_u2<20, false>, U2Geom<20>::DEC_LDS_BYTES));
+        hipLaunchKernelGGL((k_roc_decode_u2<20, false>), dim3(b.nwork), dim3(64), U2Geom<20>::DEC_LDS_BYTES, st, b, dt);
     }
     return VIDC_OK;
 }

@@ -1108,6 +1108,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //   (the bucket kernels, which keep their level-2 rows in registers: v3 4 * lane (+ the rows' start), v13 row, v58 v59 tmp,
 //   v64..v127 level-2 rows, s63 row[L2])
 //   s40 x  s43 L1  s44 L2  s45 entry  s46 x_hi  s47 g  s49 E1[L1]  s50:51 H  s52:53 H * nmax  s58:59 head  s60 sp
+//   (word-granular rows, U2_DEC_*_W: v3 16 - 64 * lane, v11 8 * lane, v12 lane == 0, v[34:35] row data, s44 w & 255, s[54:55] field ones)
 //   s61 lo  s62 lq  s64 rank (bucket kernels: below)  s65 tmp  s66:67 mask below b  s68 tmp  s69 t  s70 t_end  s71 limit  s72 tmp
 //   s73 2^p1 - 1  s74 2^p0 - 1  s75 nmax  s76 p0  s77 p1  s85 N0  s86 steps left at lane 0  s87 output index of lane 0
 //   s88:89 output pointer  s94:95 divisor table  s96:97 saved exec  s98 s99 tmp
@@ -1197,7 +1198,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //    L2 (s_lshl_b64 -2, L2) + v_cndmask with the insertion's address in the freed slot of the window, is 1.2 ns longer with four
 //    words per entry and 2 ns longer with one (profiles/r28_roc_chain_rows_order.txt; with reversed entries the four-word body had
 //    preferred it by 0.4 .. 0.8 ns, profiles/r27_roc_decode_rows_lds.txt).
-//  * 62 instructions per step with four words per entry, 56 with one.
+//  * 62 instructions per step with four words per entry, 56 with one.  The 20-bit launch runs the one-word step on word-granular
+//    rows by default (U2_DEC_*_W below, 58 instructions); the four-word step stays as k_roc_decode_u2<20, false>.
 #define U2_DEC_INS_ADDR "v_mad_u32_u24 v26, s65, v8, v9\n" /* insertion address: lane 0 the bitmap dword, lane j its strip dword */
 #define U2_DEC_MID_U \
     "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
@@ -1252,6 +1254,70 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_addc_co_u32 v4, vcc, 0, v4, vcc\n" \
     "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
     U2_DEC_RANK_TAIL_U
+// ---- the 20-bit step on word-granular rows (U2DecWord, k_roc_decode_u2<20, true>): the one-word step above with w = x >> 6 in the
+// place of the entry.  u16 row[64][256] sits at LDS byte 0 and the bitmap at byte 32 768, which the bitmap read takes as its offset
+// field; the row element is a broadcast ds_read_u16 of byte 2 w.  L1 = w >> 8, and the rank is E1[L1] + row[w] + the masked popcount
+// of the one word, read out with v_readfirstlane: no g, no whole-word popcounts, no prefix over four lanes.
+//  * row update: ONE ds_add_u64 by all lanes.  Lane j owns u64 j of row L1 (the fields of words 4 j .. 4 j + 3) and adds 1 to the
+//    fields above w & 255: FIELD_ONES << 16 z with z = the lane's fields at or below w & 255.  16 z = 16 (w & 255) + 16 - 64 j clamped
+//    to 0 .. 64 (v3 = 16 - 64 j: one v_lshl_add, one v_med3).  A 64-bit shift takes six bits of its count, so the clamp stops at 63:
+//    a lane with no field to count shifts the lowest one to bit 63 and the v_and of the high half removes it; a lane with all four
+//    shifts by 0.  No exec, no VCC.  A field of a set stays below 2^14, so no carry crosses a field; on a multiset stream a field
+//    may wrap into its neighbour, which only changes ranks of a list that the recount sends to the round-1 body anyway.
+//  * insertion: the ds_or by all lanes with v9 = 4 j in lanes j > 0 (dword j of the rows) and the bit operand v12 = 1 in lane 0 and 0
+//    elsewhere: the other lanes OR nothing into the rows.  Lane 0's dword lies in the bitmap, so no two lanes meet.
+//  * every address is formed from x < 2^20 alone: row element below 32 768, word and dword inside the bitmap, u64 (x >> 14, lane) inside
+//    the rows (U2DecWord's functions are these formulas; tests/roc_u2_decword_geom_test.cpp walks all of them).
+//  * 58 instructions per step (the four-word step: 62).
+//   v3 16 - 64 * lane   v11 8 * lane   v12 lane == 0   v29 address, then value of row[w]   v32 v33 masked word, popcounts
+//   v[34:35] data of the row update   v38 its address   v39 shift count   s43 L1   s44 w & 255   s45 w   s[54:55] FIELD_ONES
+// The other four-instruction form of the data was measured 0.6 ns per step longer: both halves by v_med3_i32 (y, 0, 0x10001) with
+// y = (4 j + 1 - (w & 255)) << 16 (one v_mad_i32_i24) for the low half and y + 0x20000 for the high one, no 64-bit shift
+// (profiles/r29_roc_decode_word_rows.txt).
+#define U2_DEC_IDX_W \
+    "s_lshr_b32 s45, s40, 6\n"                         /* w */ \
+    "v_lshlrev_b32_e64 v28, 3, s45\n" \
+    "v_lshlrev_b32_e64 v29, 1, s45\n" \
+    "ds_read_b64 v[30:31], v28 offset:32768\n"         /* (U2DecWord::BITMAP_OFF; one address in every lane) */ \
+    "ds_read_u16 v29, v29\n"                           /* row[w] */ \
+    "s_lshr_b32 s65, s40, 5\n"                         /* dword of the bitmap holding x */ U2PD(133)
+#define U2_DEC_MID_W \
+    "s_lshr_b32 s43, s45, 8\n"                         /* L1 */ \
+    "s_and_b32 s44, s45, 255\n"                        /* word inside the block */ \
+    "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 */ \
+    "s_and_b32 m0, s60, 63\n" U2PD(134) \
+    "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
+    "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
+    "v_lshl_add_u32 v38, s43, 9, v11\n"                /* lane j: u64 j of row L1 */ \
+    "v_lshl_add_u32 v39, s44, 4, v3\n"                 /* 16 * (fields of the lane at or below the word), unclamped */ \
+    "v_med3_i32 v39, v39, 0, 63\n" \
+    "v_writelane_b32 v5, s58, m0\n"                    /* index push, first half */ \
+    "v_lshlrev_b64 v[34:35], v39, s[54:55]\n"          /* 1 in the fields above the word */ \
+    "v_and_b32 v35, 0x7fffffff, v35\n"                 /* (the shift by 63 of a lane with no such field) */ U2PD(135) \
+    "s_cmp_ge_u32 s59, s62\n" \
+    "s_cselect_b32 s50, s59, s58\n" \
+    "s_cselect_b32 s51, 0, s59\n" \
+    "s_addc_u32 s60, s60, 0\n" U2PD(136) \
+    "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
+    "s_mul_hi_u32 s53, s50, s75\n" \
+    "s_mul_i32 s68, s51, s75\n" \
+    "s_add_u32 s53, s53, s68\n" \
+    "s_mov_b32 m0, s69\n" U2PD(137)
+#define U2_DEC_RANK_W \
+    "s_waitcnt lgkmcnt(0)\n" \
+    "v_and_b32 v32, s66, v30\n" \
+    "v_and_b32 v33, s67, v31\n" \
+    "v_bcnt_u32_b32 v32, v32, s49\n"                   /* E1[L1] + ... */ \
+    "v_bcnt_u32_b32 v32, v33, v32\n"                   /* ... the bits below b */ \
+    "v_cmp_lt_u32 vcc, s43, v2\n" \
+    "v_add_u32 v37, v29, v32\n"                        /* + row[w]: the rank of x, in every lane */ U2PD(139) \
+    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes above L1 */ \
+    "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
+    U2_DEC_INS_ADDR \
+    "v_lshlrev_b32 v27, s40, v12\n"                    /* the bit in lane 0, 0 elsewhere */ \
+    "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
+    "ds_or_b32 v26, v27\n"                             /* insertion of x */ \
+    "ds_add_u64 v38, v[34:35]\n"                       /* row += 1 in the words above w */ U2PD(141)
 #define U2_DEC_BOT_T_U(RLO, RSPAN)                     /* (U2_DEC_BOT_CORE_T with the rank in one register) */ \
     "s_sub_u32 s68, s60, s61\n"                        /* ring: two pops and one push must fit the next step */ \
     "s_add_u32 s68, s68, " RLO "\n" \
@@ -1411,13 +1477,35 @@ __device__ __forceinline__ uint32_t u2_slow_dec_step(uint64_t &head, WStack &st,
     wave_sync();
     return x;
 }
+// the same on word-granular rows (U2DecWord): the row update is the fast step's packed add, lane by lane
+__device__ __forceinline__ uint32_t u2w_slow_dec_step(uint64_t &head, WStack &st, uint32_t nmax, uint32_t &E1, unsigned char *smem,
+                                                      uint32_t p0, uint32_t p1) {
+    using D = U2DecWord;
+    const uint32_t lane = lane_id();
+    ws_prepare(st);
+    const uint32_t x = ans_id_pop(head, st, p0, p1);  // below 2^(p0 + p1) <= 2^20
+    const uint32_t L1 = x >> 14, b = x & 63u;
+    uint64_t *word = (uint64_t *)(smem + D::word_addr(x));
+    const uint64_t W = rfl64(*word);
+    const uint32_t r = rl(E1, L1) + rfl((uint32_t) * (const uint16_t *)(smem + D::row_addr(x))) + popc64(W & ((1ull << b) - 1ull));
+    ans_idx_push(head, st, r, nmax, 0x80000000u / nmax);
+    E1 += lane > L1 ? 1u : 0u;
+    *(uint64_t *)(smem + D::add_addr(x, lane)) += D::add_data(x, lane);
+    *word = W | (1ull << b);
+    wave_sync();
+    return x;
+}
 
-template <int UB>
+// WORD (20 universe bits only): word-granular u16 rows and the one-word step (U2DecWord, U2_DEC_*_W); the host picks the
+// instantiation (VIDC_U2_DEC_WORD=0: the four-word step on U2Geom<20>::DEC_*).
+template <int UB, bool WORD>
 __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div *__restrict__ dtab) {
+    static_assert(!WORD || UB == 20, "word-granular rows are the 20-bit geometry");
     using U = U2Geom<UB>;
     extern __shared__ __align__(16) unsigned char smem[];
-    uint32_t *rows = (uint32_t *)smem;  // row[64][64], then the bitmap, then the insertion strip (U2Geom)
-    uint64_t *bm = (uint64_t *)(smem + U::DEC_BITMAP_OFF);
+    uint32_t *rows = (uint32_t *)smem;  // row[64][64], then the bitmap, then the insertion strip (U2Geom); WORD: U2DecWord
+    uint64_t *bm = (uint64_t *)(smem + (WORD ? U2DecWord::BITMAP_OFF : U::DEC_BITMAP_OFF));
+    constexpr uint32_t LDS_CLEAR = WORD ? U2DecWord::LDS_BYTES : U::DEC_LDS_BYTES;
     const uint32_t lane = lane_id();
     const uint32_t wi = blockIdx.x;
     if (wi >= a.nwork) return;
@@ -1426,7 +1514,7 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
     const uint64_t ooff = rfl64(a.out_off ? a.out_off[wi] : a.offsets[l]);
     {
         uint4 *z = (uint4 *)smem;
-        for (uint32_t w = lane; w < U::DEC_LDS_BYTES / 16u; w += 64) z[w] = make_uint4(0, 0, 0, 0);
+        for (uint32_t w = lane; w < LDS_CLEAR / 16u; w += 64) z[w] = make_uint4(0, 0, 0, 0);
     }
     const uint32_t P = rfl(a.prec[l]);
     const uint32_t p0 = P < 16u ? P : 16u, p1 = P > 16u ? (P - 16u > 16u ? 16u : P - 16u) : 0u;
@@ -1437,9 +1525,14 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
     const uint32_t draws0 = st.draws;
     uint64_t head = rfl64(a.heads[l]);
     uint32_t E1 = 0;
-    const uint32_t l3off = U::DEC_BITMAP_OFF + (U::G == 4u ? (lane & 3u) * 8u : 0u);  // U2_DEC_IDX_*
-    const uint32_t ins_mul = lane == 0u ? 4u : 0u, ins_add = lane == 0u ? U::DEC_BITMAP_OFF : U::DEC_STRIP_OFF + 4u * lane;  // U2_DEC_RANK_TAIL_U
-    const uint32_t row_lane = 4u * lane;  // U2_DEC_MID_U
+    // v3: U2_DEC_IDX_* / the shift count of U2_DEC_MID_W;  v8 v9: U2_DEC_INS_ADDR;  v11: the lane's part of the row update's address;
+    // v12, s[54:55]: U2_DEC_RANK_W / U2_DEC_MID_W only
+    const uint32_t l3off = WORD ? 16u - 64u * lane : U::DEC_BITMAP_OFF + (U::G == 4u ? (lane & 3u) * 8u : 0u);
+    const uint32_t ins_mul = WORD ? U2DecWord::ins_mul(lane) : (lane == 0u ? 4u : 0u);
+    const uint32_t ins_add = WORD ? U2DecWord::ins_add(lane) : (lane == 0u ? U::DEC_BITMAP_OFF : U::DEC_STRIP_OFF + 4u * lane);
+    const uint32_t row_lane = WORD ? 8u * lane : 4u * lane;
+    const uint32_t ins_bit = lane == 0u ? 1u : 0u;
+    const uint64_t field_ones = rfl64(U2DecWord::FIELD_ONES);
     const uint32_t M1 = (1u << p1) - 1u, M0 = (1u << p0) - 1u;
     uint64_t *out = a.out + ooff;
     wave_sync();
@@ -1463,7 +1556,9 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
         }
         if (lt_2p31(head) || st.sp - st.lo < RING_LO || st.sp - st.lo > RING_HI) {  // generic step
             U2_DBG(0);
-            const uint32_t x = u2_slow_dec_step<UB>(head, st, i + 1u, E1, rows, bm, p0, p1);
+            uint32_t x;
+            if constexpr (WORD) x = u2w_slow_dec_step(head, st, i + 1u, E1, smem, p0, p1);
+            else x = u2_slow_dec_step<UB>(head, st, i + 1u, E1, rows, bm, p0, p1);
             if (lane == 0) out[n - 1u - i] = (uint64_t)x;
             i++;
             continue;
@@ -1474,20 +1569,23 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
         st.sp = rfl(st.sp);
         st.lo = rfl(st.lo);
         // clang-format off
-#define U2_DEC_ASM(BODY)                                                                                                  \
+#define U2_DEC_IN_W "{v12}"(ins_bit), "{s[54:55]}"(field_ones),  /* (the word-row body's own inputs) */
+#define U2_DEC_ASM(BODY, ...)                                                                                             \
         asm volatile(BODY                                                                                                 \
             : "+{v4}"(E1), "+{v5}"(st.win), "+{v[6:7]}"(oring),                                                           \
               "+{s[58:59]}"(s_h), "+{s60}"(st.sp), "+{s69}"(s_t), "+{s85}"(s_N0), "+{s86}"(s_left), "+{s87}"(s_oidx)        \
               U2P_OPERANDS                                                                                                 \
-            : "{v2}"(lane), "{v3}"(l3off), "{v8}"(ins_mul), "{v9}"(ins_add), "{v11}"(row_lane), "{s61}"(st.lo),            \
+            : __VA_ARGS__ "{v2}"(lane), "{v3}"(l3off), "{v8}"(ins_mul), "{v9}"(ins_add), "{v11}"(row_lane), "{s61}"(st.lo), \
               "{s73}"(M1), "{s74}"(M0), "{s76}"(p0), "{s77}"(p1), "{s[88:89]}"(out), "{s[94:95]}"(dtab)                     \
             : "memory", "vcc", "scc", "v10", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36",     \
               "v37", "v38", "v39", "v54", "v55", "v56", "v57", "v58", "s40", "s43", "s44", "s45", "s46", "s47", "s49", "s50", \
               "s51", "s52", "s53", "s62", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", "s97",       \
               "s98", "s99" U2PD_CLOBBERS)
-        if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
+        if constexpr (WORD) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_W, U2_DEC_MID_W, U2_DEC_RANK_W) U2_DEC_OUTER_T("-18", "35"), U2_DEC_IN_W);
+        else if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
         else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_MID_U, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
 #undef U2_DEC_ASM
+#undef U2_DEC_IN_W
         // clang-format on
         head = s_h;
         ws_window(st);

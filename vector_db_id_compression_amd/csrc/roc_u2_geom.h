@@ -25,6 +25,37 @@ struct U2Geom {
     static constexpr uint32_t DEC_LDS_BYTES = DEC_STRIP_OFF + 256u;
 };
 
+// k_roc_decode_u2<20, true>: one level-2 counter per bitmap WORD, so that the rank inside an entry is the masked popcount of one word
+// (the one-word step of the 18-bit launch).  u16 row[64][256] at the front -- element w = x >> 6 counts the inserted ids of level-1
+// block w >> 8 in words below w (at most 255 * 64 = 16 320 for a set) -- and the bitmap of 2^20 bits behind it, word w at
+// BITMAP_OFF + 8 w: exactly the 160 KiB a workgroup can have, no strip.  The insertion is a ds_or by all lanes: lane 0 ORs the bit
+// into the bitmap dword x >> 5, lane j > 0 ORs 0 into dword j of the rows (an OR of 0 changes nothing).  The row update is a
+// ds_add_u64 by all lanes: lane j owns the four fields of words 4 j .. 4 j + 3 of row L1 and adds 1 to those above w & 255.
+// A decoded id is below 2^20 whatever the stream holds, so every address below lies inside LDS_BYTES.
+// The functions are the step's address and data formation, instruction by instruction (tests/roc_u2_decword_geom_test.cpp).
+struct U2DecWord {
+    static constexpr uint32_t UB = 20u;
+    static constexpr uint32_t ROWS_BYTES = 64u * 256u * 2u;
+    static constexpr uint32_t BITMAP_OFF = ROWS_BYTES;
+    static constexpr uint32_t BITMAP_BYTES = (1u << UB) / 8u;
+    static constexpr uint32_t LDS_BYTES = BITMAP_OFF + BITMAP_BYTES;
+    static constexpr uint64_t FIELD_ONES = 0x0001000100010001ull;
+    static constexpr uint32_t row_addr(uint32_t x) { return 2u * (x >> 6); }                  // ds_read_u16
+    static constexpr uint32_t word_addr(uint32_t x) { return BITMAP_OFF + 8u * (x >> 6); }    // ds_read_b64
+    static constexpr uint32_t ins_mul(uint32_t lane) { return lane == 0u ? 4u : 0u; }
+    static constexpr uint32_t ins_add(uint32_t lane) { return lane == 0u ? BITMAP_OFF : 4u * lane; }
+    static constexpr uint32_t ins_addr(uint32_t x, uint32_t lane) { return (x >> 5) * ins_mul(lane) + ins_add(lane); }  // ds_or_b32
+    static constexpr uint32_t ins_data(uint32_t x, uint32_t lane) { return (lane == 0u ? 1u : 0u) << (x & 31u); }
+    static constexpr uint32_t add_addr(uint32_t x, uint32_t lane) { return ((x >> 14) << 9) + 8u * lane; }  // ds_add_u64
+    // 16 * (fields of the lane at or below w & 255), clamped to 0 .. 63: a 64-bit shift takes six bits of its count, so "no field"
+    // is a shift by 63 (the lowest one lands on bit 63) and the AND that follows takes that bit away
+    static constexpr uint32_t add_shift(uint32_t x, uint32_t lane) {
+        const int32_t t = (int32_t)(16u * ((x >> 6) & 255u)) + 16 - 64 * (int32_t)lane;
+        return (uint32_t)(t < 0 ? 0 : (t > 63 ? 63 : t));
+    }
+    static constexpr uint64_t add_data(uint32_t x, uint32_t lane) { return (FIELD_ONES << add_shift(x, lane)) & 0x7fffffffffffffffull; }
+};
+
 // Dense 16-id blocks in POSITION space (k_roc_encode_u2<20> only, lists of 4097 .. 65 536 ids): block b holds the ids at positions
 // 16 b .. 16 b + 15 of the ascending input as 16 u16 slots (id - first id of the block) and the first id in a u32 table.  Blocks are
 // stored in REVERSED order like the bitmap entries (storage index e = 4095 - b = L1 * 64 + L2 of the reversed counters).  The base
