@@ -457,7 +457,8 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
  *   marked (their numbers are read back once, 4 bytes each); only the lists that lose an entry are re-encoded (their numbers and
  *   survivor counts are read back, 8 bytes per touched list); every other list's stream is copied.  The calls synchronise;
  *   vidc_ctx_last_kernel_ms is the sum over the call's kernels.
- * There is no wavelet-tree form (a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks) and no sharded one. */
+ * There is no wavelet-tree form (a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks).  The sharded form is
+ *   vidc_remove_sharded_dev, behind the sharded append. */
 int vidc_packed_remove_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
                            vidc_packed **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
 int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
@@ -578,6 +579,46 @@ int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host);
 int vidc_sharded_append_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
                             int param, uint32_t flags, vidc_shards **out, int64_t *d_labels, uint64_t *d_invalid);
 int vidc_sharded_loads(const vidc_shards *s, uint64_t *loads /* nshards entries: ids per shard */);
+/* Remove from a sharded object: the "remove" section's contract, carried over the shards.  Called on the home context; d_list_nos (NULL:
+ * any-list mode), d_ids, d_removed (uint8[ntotal_old], may be NULL), d_missing and d_invalid (may be NULL; the caller zeroes them) live on
+ * the home device; n_rm < 2^32 - 1.
+ * Immutable.  *out is a NEW sharded object over the same shard contexts and the same home; `s` stays valid and unchanged, and either may be
+ *   destroyed first.
+ * The map does not change.  Owner and local number of every list in *out are those of `s`: a remove never re-balances.
+ *   vidc_sharded_loads of *out shows the drift; vidc_shards_offsets of *out is the surviving lists' offsets.
+ * The batch is that of the "remove" section, with GLOBAL list numbers: a negative list number is skipped and not counted, one >= nlist is
+ *   skipped and counted in *d_invalid, equality is over all 64 bits, every copy inside a list goes.
+ * The result.  With U = the unsharded object of the same lists and (U', mask, missing, invalid) the single-object remove of the same batch
+ *   from U: every request on *out (decode_all, decode_lists, translate_labels_dev, decode_gather, perm) returns what U' returns; d_removed
+ *   (global decode_all order, every byte written) equals the mask; *d_missing and *d_invalid receive exactly U's increments -- in any-list
+ *   mode an id is missing only if NO shard holds it, which is not the sum of the shards' own counts.
+ * Shards.  Shard k of *out is, word for word, what vidc_{packed,ef,roc}_encode builds from the cut of the surviving CSR by the map of `s`.
+ *   A shard that owns no list holds no object afterwards either; a shard whose lists all become empty holds an ordinary object; the
+ *   whole object may become empty.  n_rm == 0, or a batch that matches nothing, returns an equal object and an all-zero mask.
+ * Parameters.  Packed: param is ignored, the width stays.  ROC: param = precision_mode (the mode the object was built with).  Elias-Fano:
+ *   param is ignored.  flags are the codec's own perm flags and become those of *out.
+ * What runs where.  Pairs mode routes as the append does (local_no where a shard owns the list, -1 elsewhere, an owner byte, the invalid
+ *   count); any-list mode routes nothing: every shard that holds an object gets NULL list numbers and the caller's d_ids.  The host waits
+ *   for the home stream; then one host thread per shard that holds an object runs the shard's own remove, which also answers one FOUND
+ *   byte per pair in batch order (1 iff the pair was valid for that shard and its id hit an entry) and the shard's removed mask in its
+ *   own decode_all order.  A shard on the home device reads d_ids and its slice of the route block in place and writes mask and found
+ *   bytes into the home block; a shard on another device gets list numbers and ids through hipMemcpyAsync(hipMemcpyDefault) into a
+ *   staging block of its own cache, and its mask and found bytes back -- a path that CANNOT RUN ON A ONE-GPU MACHINE AND HAS NOT BEEN RUN.
+ *   On the home stream the inverse cut on bytes (the OLD plan's segment and chunk tables, a wavefront per 1024 bytes of a segment, 16-byte
+ *   accesses where source and destination share their alignment mod 16) writes d_removed, and a join kernel adds to *d_missing the valid
+ *   pairs (any-list mode: every pair; pairs mode: those with an owner) whose found byte no shard set.  d_removed == NULL skips the masks
+ *   and the inverse cut, d_missing == NULL the found bytes and the join.  The new object's offsets are the new shard objects' own list
+ *   sizes scattered through the map, as in the append.  The call WAITS.  vidc_ctx_last_kernel_ms of the home context = route + mask
+ *   inverse cut + join.
+ * Status.  NULL home / s / out, NULL d_ids with n_rm > 0, n_rm >= 2^32 - 1 (these three before the object is looked into), or a home that
+ *   is not the object's: VIDC_ERR_INVALID before any device work.  A status from a shard (a bad precision_mode, say) is returned, "shard
+ *   i: " in front of its message.  A shard's own invalid count stays 0; a non-zero one is an internal error, VIDC_ERR_INVALID.  On any
+ *   error *out == NULL, every new shard object already built is destroyed, `s` is untouched and every context stays usable (the
+ *   counters may have been added to).
+ * Residency.  No id payload crosses PCIe: vidc_ctx_d2h_bytes of the home context and of every shard context does not move. */
+int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm, const int64_t *d_list_nos /* NULL: any-list mode */,
+                            const uint64_t *d_ids, int param, uint32_t flags, vidc_shards **out, uint8_t *d_removed, uint64_t *d_missing,
+                            uint64_t *d_invalid);
 
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,

@@ -211,6 +211,16 @@ int req_done(::vidc_ctx *c);
 // low + high stream bits of an Elias-Fano object (ef.hip): vidc_ef_compressed_bytes before its division by 8
 uint64_t ef_stream_bits(const ::vidc_ef *e);
 
+// vidc_{packed,ef,roc}_remove_dev with one more output (not part of the C-ABI: for vidc_remove_sharded_dev's join).  d_pair_found:
+// device uint8[n_rm] in BATCH order, every byte written -- 1 iff pair i was valid for this object and its id hit an entry (a skipped
+// pair and an id wider than the object can hold: 0); NULL: the public call, kernel for kernel.
+int packed_remove(::vidc_ctx *ctx, const ::vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, ::vidc_packed **out,
+                  uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found);
+int ef_remove(::vidc_ctx *ctx, const ::vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags, ::vidc_ef **out,
+              uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found);
+int roc_remove(::vidc_ctx *ctx, const ::vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
+               uint32_t flags, ::vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found);
+
 }  // namespace vidc
 
 // mt19937(1234) words available to the kernels for ANS stack underflow (codec.h:16-18,32-40).

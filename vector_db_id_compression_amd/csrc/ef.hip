@@ -2700,17 +2700,26 @@ int vidc_ef_append_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_add, const in
 
 // Remove (include/vidc.h): decode_all into scratch, the shared mark and compaction (remove.h), the device-offsets encoder on the
 // surviving CSR.  The survivors of an ascending list are ascending: the encoder stays on its sorted path.
-int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags,
-                       vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+// (the body is vidc::ef_remove, which the sharded remove calls with the per-pair found bytes; common.h)
+extern "C++" {
+namespace vidc {
+int ef_remove(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags, vidc_ef **out,
+              uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found) {
     VIDC_TRY(remove_check(ctx, e, out, n_rm, d_ids));
     if (e->rows || e->arena) { set_error("elias-fano remove: graph objects hold no removable lists"); return VIDC_ERR_UNSUPPORTED; }
     VIDC_HIP(hipSetDevice(ctx->device));
     RemoveRebuilt m;
-    VIDC_TRY(remove_rebuild(ctx, e->nlist, e->ntotal, e->d_offsets.p, n_rm, d_list_nos, d_ids, 64u, d_removed, d_missing, d_invalid, m,
+    VIDC_TRY(remove_rebuild(ctx, e->nlist, e->ntotal, e->d_offsets.p, n_rm, d_list_nos, d_ids, 64u, d_removed, d_missing, d_invalid, d_pair_found, m,
                             [&](uint64_t *d) { return vidc_ef_decode_all(ctx, e, d); }));
     VIDC_TRY(vidc_ef_encode_dev(ctx, e->nlist, m.new_off, m.ntotal_new, m.s_out.as<uint64_t>(), flags, out));
     ctx->last_kernel_ms += m.kernel_ms;
     return VIDC_OK;
+}
+}  // namespace vidc
+}
+int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags,
+                       vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+    return ef_remove(ctx, e, n_rm, d_list_nos, d_ids, flags, out, d_removed, d_missing, d_invalid, nullptr);
 }
 
 int vidc_ef_get(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *list_nos, const uint64_t *offs,

@@ -1192,16 +1192,25 @@ int vidc_packed_append_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_add, 
 
 // Remove (include/vidc.h): decode_all into scratch, the shared mark and compaction (remove.h), the device-offsets encoder on the
 // surviving CSR at the object's own width.  An id of `bits` bits is all the object can hold: a wider batch id matches nothing.
-int vidc_packed_remove_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
-                           vidc_packed **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+// (the body is vidc::packed_remove, which the sharded remove calls with the per-pair found bytes; common.h)
+extern "C++" {
+namespace vidc {
+int packed_remove(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, vidc_packed **out,
+                  uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found) {
     VIDC_TRY(remove_check(ctx, p, out, n_rm, d_ids));
     VIDC_HIP(hipSetDevice(ctx->device));
     RemoveRebuilt m;
-    VIDC_TRY(remove_rebuild(ctx, p->nlist, p->ntotal, p->d_offsets.p, n_rm, d_list_nos, d_ids, (uint32_t)p->bits, d_removed, d_missing, d_invalid, m,
-                            [&](uint64_t *d) { return vidc_packed_decode_all(ctx, p, d); }));
+    VIDC_TRY(remove_rebuild(ctx, p->nlist, p->ntotal, p->d_offsets.p, n_rm, d_list_nos, d_ids, (uint32_t)p->bits, d_removed, d_missing, d_invalid,
+                            d_pair_found, m, [&](uint64_t *d) { return vidc_packed_decode_all(ctx, p, d); }));
     VIDC_TRY(vidc_packed_encode_dev(ctx, p->nlist, m.new_off, m.ntotal_new, m.s_out.as<uint64_t>(), p->bits, out));
     ctx->last_kernel_ms += m.kernel_ms;
     return VIDC_OK;
+}
+}  // namespace vidc
+}
+int vidc_packed_remove_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
+                           vidc_packed **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+    return packed_remove(ctx, p, n_rm, d_list_nos, d_ids, out, d_removed, d_missing, d_invalid, nullptr);
 }
 
 int vidc_packed_export(vidc_ctx *ctx, const vidc_packed *p, uint64_t list_no, uint8_t *bytes, size_t cap) {

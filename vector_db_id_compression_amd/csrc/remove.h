@@ -8,7 +8,8 @@
 //   2. bounds (k_app_bounds): run_off[l] .. run_off[l + 1] is list l's run, ascending by id; sid[] holds the sorted ids themselves.
 //   3. mark: a wavefront per chunk of RM_UNIT decoded elements (the chunk tables of app_chunks) -- every element binary-searches its
 //      list's run, writes its `removed` byte and sets hit[] of the first equal run position; the chunk keeps its kill count.
-//   4. missing: run position p is missing iff hit[first position of its value in its run] == 0.
+//   4. missing: run position p is missing iff hit[first position of its value in its run] == 0.  Found bytes (optional, for the
+//      sharded remove's join): the same flag per pair, sent back to batch order through the sorter's pair numbers.
 //   5. compact: the destination of a survivor is (exclusive scan of the chunk kill counts) + (ballot prefix inside the wavefront);
 //      new_off[s] = seg_off[s] - kills in front of segment s.  No atomic decides a position: the output is the same on every run.
 // What crosses PCIe: the survivor count (8 bytes).  Included by several translation units: everything has internal linkage.
@@ -116,6 +117,19 @@ __global__ void __launch_bounds__(256) k_rm_missing(const uint32_t *__restrict__
     }
 }
 
+// found[vals[p]] = 1 iff sorted position p belongs to a run (keys[p] < nl) and some element hit its value: one byte per pair, in batch
+// order, every byte written (vals is a permutation of 0 .. n - 1).  Skipped pairs and too-wide ids carry the key nl: 0.
+__global__ void __launch_bounds__(256) k_rm_pair_found(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n, uint64_t nl,
+                                                       const uint64_t *__restrict__ run_off, const uint64_t *__restrict__ sid,
+                                                       const uint32_t *__restrict__ hit, uint8_t *__restrict__ found) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) {
+        uint32_t f = 0;
+        if ((uint64_t)keys[p] < nl) f = hit[rm_lower_bound(sid, (uint32_t)run_off[keys[p]], (uint32_t)p, sid[p])];
+        found[vals[p]] = f ? 1 : 0;
+    }
+}
+
 // new_off[s] = seg_off[s] - seg_off[0] - (kills in front of segment s), s = 0 .. nseg: item_off is the chunk table's offset array,
 // ks the exclusive scan of chunk_kill
 __global__ void __launch_bounds__(256) k_rm_new_off(const uint64_t *__restrict__ seg_off, uint64_t nseg, const uint64_t *__restrict__ item_off,
@@ -170,7 +184,7 @@ struct RemoveBatch {
     Scratch s_sort, s_hist, s_scan, s_tmp, s_off, s_sid, s_hit, s_zero;
     uint32_t n = 0, any = 0;
     uint64_t nl = 0;
-    const uint32_t *keys = nullptr;
+    const uint32_t *keys = nullptr, *vals = nullptr;  // vals[p]: the pair at sorted position p
     const uint64_t *run_off = nullptr, *sid = nullptr;
     uint32_t *hit = nullptr;
 };
@@ -212,6 +226,7 @@ inline int remove_sort_batch(::vidc_ctx *ctx, uint64_t nlist, uint64_t n_rm, con
     while (lbits < 32u && (b.nl >> lbits)) lbits++;  // keys are 0 .. nl
     VIDC_TRY(app_sort_phase(ctx, s, lbits, b.s_hist, b.s_scan, b.s_tmp, gather(RM_KEY_LIST)));
     b.keys = s.kin;
+    b.vals = s.vin;
     // (k_app_bounds also adds the run bounds to a set of old offsets: zeros here, the sums are not used)
     VIDC_TRY(b.s_zero.get(ctx, (b.nl + 1) * 8));
     VIDC_HIP(hipMemsetAsync(b.s_zero.p, 0, (b.nl + 1) * 8, ctx->stream));
@@ -259,6 +274,14 @@ inline int remove_count_missing(::vidc_ctx *ctx, const RemoveBatch &b, uint64_t 
     VIDC_HIP(hipGetLastError());
     return VIDC_OK;
 }
+// the per-pair found bytes (d_pair_found: n bytes in batch order, NULL: nothing runs): where remove_count_missing runs
+inline int remove_pair_found(::vidc_ctx *ctx, const RemoveBatch &b, uint8_t *d_pair_found) {
+    if (!d_pair_found || !b.n) return VIDC_OK;
+    hipLaunchKernelGGL(k_rm_pair_found, req_grid(ctx, b.n), dim3(256), 0, ctx->stream, b.keys, b.vals, b.n, b.nl, b.run_off, b.sid,
+                       (const uint32_t *)b.hit, d_pair_found);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
 inline int remove_compact(::vidc_ctx *ctx, const RemoveMarked &m, const uint64_t *d_dec, const uint64_t *d_seg_off, const uint8_t *d_removed,
                           const uint64_t *d_dst_off, const uint32_t *d_take, uint64_t *d_out) {
     hipLaunchKernelGGL(k_rm_compact, app_chunk_grid(ctx, m.ch.bound), dim3(256), 0, ctx->stream, d_dec, d_seg_off, d_removed, m.ch.items, m.ch.n_items,
@@ -282,7 +305,7 @@ struct RemoveRebuilt {
 template <typename DecodeAll>
 inline int remove_rebuild(::vidc_ctx *ctx, uint64_t nlist, uint64_t ntotal_old, const uint64_t *d_old_off, uint64_t n_rm,
                           const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t id_bits, uint8_t *d_removed, uint64_t *d_missing,
-                          uint64_t *d_invalid, RemoveRebuilt &m, DecodeAll &&decode_all) {
+                          uint64_t *d_invalid, uint8_t *d_pair_found, RemoveRebuilt &m, DecodeAll &&decode_all) {
     VIDC_TRY(m.h_back.get(ctx, 64));
     EventTimer tm = EventTimer::started(ctx);
     VIDC_TRY(remove_sort_batch(ctx, nlist, n_rm, d_list_nos, d_ids, id_bits, d_missing, d_invalid, m.batch));
@@ -292,6 +315,7 @@ inline int remove_rebuild(::vidc_ctx *ctx, uint64_t nlist, uint64_t ntotal_old, 
         m.new_off = m.s_new.as<uint64_t>();
         VIDC_HIP(hipMemsetAsync(m.new_off, 0, (nlist + 1) * 8, ctx->stream));
         VIDC_TRY(remove_count_missing(ctx, m.batch, d_missing));
+        VIDC_TRY(remove_pair_found(ctx, m.batch, d_pair_found));
         m.kernel_ms = tm.stop();
         VIDC_HIP(vidc_stream_wait(ctx->stream));
         m.ntotal_new = 0;
@@ -310,6 +334,7 @@ inline int remove_rebuild(::vidc_ctx *ctx, uint64_t nlist, uint64_t ntotal_old, 
     (void)tm.start();
     VIDC_TRY(remove_mark(ctx, m.batch, m.s_old.as<uint64_t>(), d_old_off, nullptr, nlist, ntotal_old, removed, nullptr, nullptr, d_missing, m.marked));
     VIDC_TRY(remove_count_missing(ctx, m.batch, d_missing));
+    VIDC_TRY(remove_pair_found(ctx, m.batch, d_pair_found));
     m.new_off = m.marked.new_off;
     VIDC_TRY(remove_compact(ctx, m.marked, m.s_old.as<uint64_t>(), d_old_off, removed, m.new_off, nullptr, m.s_out.as<uint64_t>()));
     (void)tm.mark();

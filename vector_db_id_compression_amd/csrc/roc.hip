@@ -2252,8 +2252,11 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
 // and marked.  The candidates that lost an entry are the touched lists: their staging numbers and survivor counts come back (8 bytes
 // per touched list), their survivors are compacted into a second staging CSR and encode_impl runs on that alone.  The splice is the
 // append's: metadata from the small object or the old one, the scan of the word counts, a segmented copy of every list's words.
-int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
-                        uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+// (the body is vidc::roc_remove, which the sharded remove calls with the per-pair found bytes; common.h)
+extern "C++" {
+namespace vidc {
+int roc_remove(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode, uint32_t flags,
+               vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found) {
     VIDC_TRY(remove_check(ctx, r, out, n_rm, d_ids));
     if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
         set_error("roc remove: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
@@ -2378,6 +2381,7 @@ int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const i
     }
     (void)tm.start();
     VIDC_TRY(remove_count_missing(ctx, b, d_missing));
+    VIDC_TRY(remove_pair_found(ctx, b, d_pair_found));
     kernel_ms += tm.stop();
     tr.mark("candidates marked, touched lists read back");
     std::unique_ptr<vidc_roc> small;
@@ -2462,6 +2466,12 @@ int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const i
     tr.mark("spliced");
     *out = nr.release();
     return VIDC_OK;
+}
+}  // namespace vidc
+}
+int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
+                        uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+    return roc_remove(ctx, r, n_rm, d_list_nos, d_ids, precision_mode, flags, out, d_removed, d_missing, d_invalid, nullptr);
 }
 
 int vidc_roc_decode_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,

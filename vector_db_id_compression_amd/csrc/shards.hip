@@ -1,7 +1,8 @@
 // shards.hip -- vidc_shards (include/vidc.h): one CSR set of lists cut over several contexts of one process.  The plan is host code
 // (shard_plan.h); the shards are ordinary vidc_packed / vidc_ef / vidc_roc objects built and served through the public entry points, so a
 // shard IS what the single-object encoder builds from its cut CSR.  What is new on the device: the segmented copy (cut, inverse cut,
-// placement of decode_lists results), the route / join pair of translate_labels and the route / join pair of the append.
+// placement of decode_lists results), the route / join pair of translate_labels, the route / join pair of the append, and the remove's
+// byte inverse cut (the shards' removed masks -> the global mask) and found-byte join (the missing count).
 #include <thread>
 
 #include "common.h"
@@ -40,6 +41,35 @@ __global__ void __launch_bounds__(256) k_shard_copy(const uint64_t *__restrict__
             uint4 *dv = (uint4 *)(d + head);
             for (uint32_t j = lane; j < nv; j += 64u) dv[j] = sv[j];
             for (uint32_t j = head + nv * 2u + lane; j < nc; j += 64u) d[j] = s[j];
+        } else {
+            for (uint32_t j = lane; j < nc; j += 64u) d[j] = s[j];
+        }
+    }
+}
+
+// The inverse cut on bytes (the removed mask of a sharded remove): the same segment and chunk tables, counted in uint8_t elements, so a
+// wavefront moves at most SHARD_COPY_UNIT bytes.  16-byte accesses where the two runs share their alignment mod 16, behind a head of at
+// most 15 bytes and in front of a tail of at most 15; byte accesses otherwise.
+template <bool INV>
+__global__ void __launch_bounds__(256) k_shard_copy_bytes(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const Segment *__restrict__ segs,
+                                                          const CopyChunk *__restrict__ chunks, uint64_t nchunks) {
+    const uint32_t lane = dev::lane_id();
+    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < nchunks; c += (uint64_t)gridDim.x * 4u) {
+        const CopyChunk ch = chunks[c];
+        const Segment sg = segs[ch.seg];
+        const uint64_t left = sg.count - ch.start;
+        const uint32_t nc = (uint32_t)(left < SHARD_COPY_UNIT ? left : SHARD_COPY_UNIT);
+        const uint8_t *s = src + (INV ? sg.dst_start : sg.src_start) + ch.start;
+        uint8_t *d = dst + (INV ? sg.src_start : sg.dst_start) + ch.start;
+        if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0u) {
+            uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
+            head = head < nc ? head : nc;
+            if (lane < head) d[lane] = s[lane];
+            const uint32_t nv = (nc - head) / 16u;
+            const uint4 *sv = (const uint4 *)(s + head);
+            uint4 *dv = (uint4 *)(d + head);
+            for (uint32_t j = lane; j < nv; j += 64u) dv[j] = sv[j];
+            for (uint32_t j = head + nv * 16u + lane; j < nc; j += 64u) d[j] = s[j];
         } else {
             for (uint32_t j = lane; j < nc; j += 64u) d[j] = s[j];
         }
@@ -123,6 +153,22 @@ __global__ void __launch_bounds__(256) k_shard_join_labels(const int64_t *__rest
     }
 }
 
+// Found join of a remove: *missing += the valid pairs (owner == NULL, any-list mode: every pair; else owner[i] != NO_OWNER) that no shard
+// found.  found[s * n + i]: shard s's byte for pair i (a shard that does not own the pair's list saw list -1 and answered 0; a shard
+// without an object left the zeros of the memset).
+__global__ void __launch_bounds__(256) k_shard_join_found(const uint8_t *__restrict__ found, const uint8_t *__restrict__ owner, uint64_t n,
+                                                          uint32_t nshards, unsigned long long *missing) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
+        const uint64_t i = i0 + dev::lane_id();
+        const bool valid = i < n && (!owner || owner[i] != NO_OWNER);
+        uint32_t any = 0;
+        if (valid)
+            for (uint32_t s = 0; s < nshards; s++) any |= found[(uint64_t)s * n + i];
+        req_count_invalid(valid && !any, missing);
+    }
+}
+
 inline dim3 copy_grid(const vidc_ctx *c, uint64_t nchunks) {
     return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nchunks + 3) / 4, (uint64_t)c->num_cu * 16)));
 }
@@ -185,6 +231,14 @@ int codec_append(int kind, vidc_ctx *c, const void *o, uint64_t n, const int64_t
     case VIDC_KIND_PACKED: return vidc_packed_append_dev(c, (const vidc_packed *)o, n, d_list_nos, d_ids, param, (vidc_packed **)out, d_labels, d_invalid);
     case VIDC_KIND_EF: return vidc_ef_append_dev(c, (const vidc_ef *)o, n, d_list_nos, d_ids, flags, (vidc_ef **)out, d_labels, d_invalid);
     default: return vidc_roc_append_dev(c, (const vidc_roc *)o, n, d_list_nos, d_ids, param, flags, (vidc_roc **)out, d_labels, d_invalid);
+    }
+}
+int codec_remove(int kind, vidc_ctx *c, const void *o, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int param, uint32_t flags,
+                 void **out, uint8_t *d_removed, uint64_t *d_invalid, uint8_t *d_pair_found) {
+    switch (kind) {
+    case VIDC_KIND_PACKED: return packed_remove(c, (const vidc_packed *)o, n, d_list_nos, d_ids, (vidc_packed **)out, d_removed, nullptr, d_invalid, d_pair_found);
+    case VIDC_KIND_EF: return ef_remove(c, (const vidc_ef *)o, n, d_list_nos, d_ids, flags, (vidc_ef **)out, d_removed, nullptr, d_invalid, d_pair_found);
+    default: return roc_remove(c, (const vidc_roc *)o, n, d_list_nos, d_ids, param, flags, (vidc_roc **)out, d_removed, nullptr, d_invalid, d_pair_found);
     }
 }
 // the sizes of an object's nl lists, through the codecs' host-side accessors (metadata mirrored on first use)
@@ -873,6 +927,155 @@ int vidc_sharded_append_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_add
     for (uint32_t i = 0; i < ns; i++)
         if (h[i]) {  // every local number a shard sees is valid or negative
             set_error("sharded append: internal error, shard %u counted %llu list numbers outside its lists", i, h[i]);
+            return VIDC_ERR_INVALID;
+        }
+    *out = N.release();
+    return VIDC_OK;
+}
+
+// Remove (include/vidc.h): pairs mode routes as the append does, any-list mode hands every shard the caller's ids; every shard that holds
+// an object runs its own remove (one host thread each, behind a host wait for the route) and answers with its removed mask in its own
+// decode_all order and one found byte per pair.  The byte inverse cut with the OLD plan makes the global mask, the found join the
+// missing count.  The new plan keeps the owner of every list; its offsets are the new shard objects' own list sizes.
+int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int param,
+                            uint32_t flags, vidc_shards **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
+    if (out) *out = nullptr;
+    if (!home || !s || !out || (n_rm && !d_ids)) {
+        set_error("sharded remove: NULL context, object, out or id array");
+        return VIDC_ERR_INVALID;
+    }
+    if (n_rm >= 0xffffffffull) { set_error("sharded remove: a batch holds fewer than 2^32 - 1 pairs"); return VIDC_ERR_INVALID; }
+    VIDC_TRY(check_request(home, s, "sharded remove"));
+    HostTrace tr("sharded remove");
+    const ShardPlan &P = s->plan;
+    const uint32_t ns = (uint32_t)P.nshards;
+    const uint64_t n = n_rm;
+    const bool pairs = n && d_list_nos, want_found = n && d_missing;
+    std::vector<int> involved;
+    for (int sh = 0; sh < P.nshards; sh++)
+        if (s->objs[(size_t)sh]) involved.push_back(sh);
+    std::unique_ptr<vidc_shards> N(new vidc_shards());
+    N->kind = s->kind;
+    N->flags = flags;
+    N->home = home;
+    N->ctxs = s->ctxs;
+    N->objs.assign((size_t)ns, nullptr);
+    N->param = s->kind == VIDC_KIND_ROC ? param : s->param;
+    VIDC_HIP(hipSetDevice(home->device));
+    // home block: shard_invalid[ns] | local[ns * n] (pairs mode) | the shards' masks, each at a multiple of 16 | found[ns * n] | owner[n]
+    std::vector<uint64_t> mask_off((size_t)ns + 1, 0);
+    for (uint32_t i = 0; i < ns; i++) mask_off[i + 1] = mask_off[i] + (d_removed ? (P.load[i] + 15) / 16 * 16 : 0);
+    const size_t b_local = ((size_t)ns * 8 + 15) / 16 * 16, b_mask = b_local + (pairs ? (size_t)ns * n * 8 : 0);
+    const size_t b_found = b_mask + mask_off[ns], b_owner = b_found + (want_found ? (size_t)ns * n : 0);
+    PlanTables tables;
+    Scratch blk;
+    Pinned h_inv;
+    std::vector<Scratch> far((size_t)ns);  // a shard on another device: invalid | list numbers[n] | ids[n] | mask | found[n] in its own cache
+    std::vector<std::vector<uint64_t>> sizes((size_t)ns);
+    ShardStreamsGuard sguard(s);
+    StreamGuard hguard(home, false);
+    VIDC_TRY(blk.get(home, b_owner + (pairs ? n : 0) + 16));
+    VIDC_TRY(h_inv.get(home, (size_t)ns * 8));
+    unsigned long long *sh_inv = blk.as<unsigned long long>();
+    int64_t *local = (int64_t *)(blk.as<uint8_t>() + b_local);
+    uint8_t *masks = blk.as<uint8_t>() + b_mask, *found = blk.as<uint8_t>() + b_found;
+    uint8_t *owner = pairs ? blk.as<uint8_t>() + b_owner : nullptr;
+    hguard.arm();
+    EventTimer timer(home);
+    VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
+    if (want_found) VIDC_HIP(hipMemsetAsync(found, 0, (size_t)ns * n, home->stream));  // (a shard without an object answers nothing)
+    double kernel_ms = 0;
+    if (pairs) {
+        VIDC_HIP(timer.start());
+        hipLaunchKernelGGL(k_shard_route_pairs, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, n, (const uint64_t *)s->d_map.p, P.nlist, ns,
+                           local, owner, (unsigned long long *)d_invalid);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(timer.mark());
+    }
+    // every shard's remove waits anyway: the route (and the caller's batch) is waited for here, once, before the shard threads start
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    if (pairs) kernel_ms = timer.elapsed();
+    hguard.disarm();
+    tr.mark("routed, waited");
+    sguard.which = involved;
+    vidc_shards *Np = N.get();
+    const int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        vidc_ctx *c = s->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        const int64_t *ln = pairs ? local + (uint64_t)i * n : nullptr;
+        const uint64_t *ids = n ? d_ids : nullptr;
+        uint8_t *mask = d_removed ? masks + mask_off[i] : nullptr;
+        uint8_t *fnd = want_found ? found + (uint64_t)i * n : nullptr;
+        uint64_t *inv = (uint64_t *)(sh_inv + i);
+        const bool far_shard = !s->same_device(sh);
+        if (far_shard) {
+            const size_t f_mask = 16 + 2 * (size_t)n * 8, f_found = f_mask + (mask_off[i + 1] - mask_off[i]);
+            VIDC_TRY(far[i].get(c, f_found + n + 16));
+            inv = far[i].as<uint64_t>();
+            VIDC_HIP(hipMemsetAsync(inv, 0, 8, c->stream));
+            if (n) {
+                int64_t *f_ln = (int64_t *)(inv + 2);
+                uint64_t *f_ids = (uint64_t *)(f_ln + n);
+                if (pairs) VIDC_HIP(hipMemcpyAsync(f_ln, ln, n * 8, hipMemcpyDefault, c->stream));
+                VIDC_HIP(hipMemcpyAsync(f_ids, d_ids, n * 8, hipMemcpyDefault, c->stream));
+                if (pairs) ln = f_ln;
+                ids = f_ids;
+            }
+            if (mask) mask = far[i].as<uint8_t>() + f_mask;
+            if (fnd) fnd = far[i].as<uint8_t>() + f_found;
+        }
+        VIDC_TRY(codec_remove(s->kind, c, s->objs[i], n, ln, ids, param, flags, &Np->objs[i], mask, inv, fnd));
+        if (far_shard) {
+            if (mask && P.load[i]) VIDC_HIP(hipMemcpyAsync(masks + mask_off[i], mask, P.load[i], hipMemcpyDefault, c->stream));
+            if (fnd) VIDC_HIP(hipMemcpyAsync(found + (uint64_t)i * n, fnd, n, hipMemcpyDefault, c->stream));
+            VIDC_HIP(hipMemcpyAsync(sh_inv + i, inv, 8, hipMemcpyDefault, c->stream));
+        }
+        VIDC_HIP(vidc_stream_wait(c->stream));
+        HostTrace ts("sharded remove, a shard");
+        const int rc = codec_list_sizes(s->kind, c, Np->objs[i], P.lists[i].size(), sizes[i]);
+        ts.mark("list sizes to the host");
+        return rc;
+    });
+    tr.mark("shards removed, sizes read");
+    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
+    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
+    VIDC_HIP(hipSetDevice(home->device));
+    std::vector<uint64_t> off(P.nlist + 1, 0);
+    for (uint64_t l = 0; l < P.nlist; l++) off[l + 1] = off[l] + sizes[(size_t)P.owner[l]][P.local_no[l]];
+    N->plan = make_plan_for_owner(off.data(), P.nlist, P.nshards, P.owner);
+    tr.mark("plan");
+    VIDC_TRY(create_events(N.get()));
+    hguard.arm();
+    const bool tail = (d_removed && P.ntotal) || want_found;
+    if (tail) VIDC_HIP(timer.start());
+    if (d_removed)  // the OLD plan: the masks are in the old shards' decode_all order
+        for (int sh : involved) {
+            const size_t i = (size_t)sh;
+            if (!s->n_cut_chunks[i]) continue;
+            hipLaunchKernelGGL((k_shard_copy_bytes<true>), copy_grid(home, s->n_cut_chunks[i]), dim3(256), 0, home->stream,
+                               (const uint8_t *)(masks + mask_off[i]), d_removed, (const Segment *)s->d_cut[i].p,
+                               (const CopyChunk *)s->d_cut_chunks[i].p, s->n_cut_chunks[i]);
+            VIDC_HIP(hipGetLastError());
+        }
+    if (want_found) {
+        hipLaunchKernelGGL(k_shard_join_found, req_grid(home, n), dim3(256), 0, home->stream, (const uint8_t *)found, (const uint8_t *)owner, n, ns,
+                           (unsigned long long *)d_missing);
+        VIDC_HIP(hipGetLastError());
+    }
+    if (tail) VIDC_HIP(timer.mark());
+    unsigned long long *h = h_inv.as<unsigned long long>();
+    VIDC_HIP(hipMemcpyAsync(h, sh_inv, (size_t)ns * 8, hipMemcpyDeviceToHost, home->stream));
+    VIDC_TRY(upload_plan(N.get(), tables));
+    tr.mark("mask, join, tables enqueued");
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    hguard.disarm();
+    tr.mark("waited");
+    if (tail) kernel_ms += timer.elapsed();
+    home->last_kernel_ms = kernel_ms;  // (route + mask inverse cut + join)
+    for (uint32_t i = 0; i < ns; i++)
+        if (h[i]) {  // every local number a shard sees is valid or negative
+            set_error("sharded remove: internal error, shard %u counted %llu list numbers outside its lists", i, h[i]);
             return VIDC_ERR_INVALID;
         }
     *out = N.release();

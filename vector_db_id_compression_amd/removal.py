@@ -7,7 +7,8 @@ Objects are immutable: `obj` stays valid and unchanged.  The new object is, word
 surviving lists (order kept).  mask[p] (uint8 CUDA tensor, ntotal_old entries) is 1 where position p of obj.decode_all() was removed:
 a caller that keeps per-entry payload (the vector codes) drops the same rows.  Packed bits and Elias-Fano are rebuilt on the device;
 ROC re-encodes only the lists that lose an entry and copies the streams of the others.  A wavelet tree holds a permutation of
-0 .. ntotal - 1, which a removal breaks: it has no remove.
+0 .. ntotal - 1, which a removal breaks: it has no remove.  A sharding.DeviceShards is forwarded to DeviceShards.remove
+(vidc_remove_sharded_dev): every shard removes from its own lists, the mask and the counters are the unsharded object's.
 """
 import ctypes as C
 
@@ -15,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import VIDC_PREC_REFERENCE, VidcError, check, lib, ptr
+from .sharding import DeviceShards
 from .codecs import EfLists, PackedLists, RocLists, WaveletTreeLists, _dev_array, _is_cuda, _on_torch_stream, _torch
 
 
@@ -25,25 +27,9 @@ def _counter(x, what, device):
     return x
 
 
-def remove(obj, list_nos, ids, *, precision_mode=VIDC_PREC_REFERENCE, want_perm=False, removed=True, missing=None, invalid=None):
-    """-> (NEW object of obj's class, removed mask or None).
-
-    list_nos: int64 CUDA tensor (negative = skipped, >= nlist = skipped and counted in `invalid`), or None for any-list mode; ids:
-    int64 / uint64 CUDA tensor with one entry per pair; numpy arrays are uploaded once.  precision_mode (ROC): the mode the object was
-    built with; want_perm (ROC, Elias-Fano): keep the permutation of the new object.  removed: True (a new uint8 CUDA tensor), False /
-    None (none) or a contiguous uint8 CUDA tensor of obj.ntotal entries to fill.  missing / invalid (optional): 1-element int64 CUDA
-    tensors the number of valid pairs that matched nothing / of list numbers >= nlist is added to.  Runs on torch's current stream;
-    the call synchronises."""
-    if isinstance(obj, WaveletTreeLists):
-        raise VidcError("remove: a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks")
-    if isinstance(obj, RocLists):
-        fn, extra = lib().vidc_roc_remove_dev, (int(precision_mode), _lib.VIDC_ROC_WANT_PERM if want_perm else 0)
-    elif isinstance(obj, EfLists):
-        fn, extra = lib().vidc_ef_remove_dev, (_lib.VIDC_EF_WANT_PERM if want_perm else 0,)
-    elif isinstance(obj, PackedLists):
-        fn, extra = lib().vidc_packed_remove_dev, ()
-    else:
-        raise VidcError(f"remove: {type(obj).__name__} holds no removable lists")
+def _call(fn, obj, extra, list_nos, ids, removed, missing, invalid):
+    """The argument handling every remove shares -> (handle of the new object, mask or None).  fn(ctx, obj, n, list_nos, ids, *extra,
+    &out, removed, missing, invalid); obj has .ctx, .h and .ntotal."""
     torch = _torch()
     if not torch.cuda.is_available():
         raise VidcError("no HIP device: remove needs an MI355X (there is no CPU fallback)")
@@ -80,8 +66,36 @@ def remove(obj, list_nos, ids, *, precision_mode=VIDC_PREC_REFERENCE, want_perm=
     _on_torch_stream(obj.ctx)
     h = C.c_void_p()
     check(fn(obj.ctx.h, obj.h, n, ptr(ln), ptr(di) if n else None, *extra, C.byref(h), ptr(mask), ptr(missing), ptr(invalid)))
+    return h, (None if mask is None else mask[:ntotal])
+
+
+def remove(obj, list_nos, ids, *, precision_mode=VIDC_PREC_REFERENCE, want_perm=False, removed=True, missing=None, invalid=None):
+    """-> (NEW object of obj's class, removed mask or None).
+
+    list_nos: int64 CUDA tensor (negative = skipped, >= nlist = skipped and counted in `invalid`), or None for any-list mode; ids:
+    int64 / uint64 CUDA tensor with one entry per pair; numpy arrays are uploaded once.  precision_mode (ROC): the mode the object was
+    built with; want_perm (ROC, Elias-Fano): keep the permutation of the new object.  removed: True (a new uint8 CUDA tensor), False /
+    None (none) or a contiguous uint8 CUDA tensor of obj.ntotal entries to fill.  missing / invalid (optional): 1-element int64 CUDA
+    tensors the number of valid pairs that matched nothing / of list numbers >= nlist is added to.  Runs on torch's current stream;
+    the call synchronises.  A DeviceShards goes to DeviceShards.remove (global list numbers, arrays on the home device)."""
+    if isinstance(obj, WaveletTreeLists):
+        raise VidcError("remove: a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks")
+    if isinstance(obj, DeviceShards):
+        args = {} if obj.kind == 0 else {"want_perm": want_perm}
+        if obj.kind == 2:
+            args["precision_mode"] = precision_mode
+        return obj.remove(list_nos, ids, removed=removed, missing=missing, invalid=invalid, **args)
+    if isinstance(obj, RocLists):
+        fn, extra = lib().vidc_roc_remove_dev, (int(precision_mode), _lib.VIDC_ROC_WANT_PERM if want_perm else 0)
+    elif isinstance(obj, EfLists):
+        fn, extra = lib().vidc_ef_remove_dev, (_lib.VIDC_EF_WANT_PERM if want_perm else 0,)
+    elif isinstance(obj, PackedLists):
+        fn, extra = lib().vidc_packed_remove_dev, ()
+    else:
+        raise VidcError(f"remove: {type(obj).__name__} holds no removable lists")
+    h, mask = _call(fn, obj, extra, list_nos, ids, removed, missing, invalid)
     if isinstance(obj, RocLists):
         new = type(obj)(h, obj.ctx, None)
     else:
         new = type(obj)(h, obj.ctx, None, obj._nlist if obj._offsets is None else obj._offsets.size - 1, None)
-    return new, (None if mask is None else mask[:ntotal])
+    return new, mask

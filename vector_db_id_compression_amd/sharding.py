@@ -13,7 +13,7 @@ arithmetic and the gathered lists land in request order with one indexed copy pe
 `ShardedInvLists` is the multi-process form (one process per GPU, torch.distributed).  `DeviceShards` is the single-process form
 over the C-ABI's vidc_shards: one process drives every context, the cut / placement / label routing are HIP kernels, and no index
 arithmetic happens in Python.  `DeviceShards.append` adds a batch of (list number, id) pairs without re-encoding the index: the map
-stays, `DeviceShards.loads` shows how the balance drifts.  It has been exercised with several contexts on one device; never run on
+stays, `DeviceShards.loads` shows how the balance drifts; `DeviceShards.remove` takes a batch out the same way.  It has been exercised with several contexts on one device; never run on
 more than one GPU.
 """
 import heapq
@@ -366,6 +366,26 @@ class DeviceShards:
             raise TypeError(f"unknown codec arguments: {sorted(codec_args)}")
         h, lab = codecs._append(_lib.lib().vidc_sharded_append_dev, self, list_nos, ids, (param, flags), labels, invalid)
         return type(self)(h, self.ctx, self.ctxs, self.kind), lab  # (the offsets are fetched from the new object on first use)
+
+    def remove(self, list_nos, ids, removed=True, missing=None, invalid=None, **codec_args):
+        """A batch of (GLOBAL list number, id) pairs, or of ids alone (list_nos None: any-list mode), leaves the lists of this object ->
+        (NEW DeviceShards over the same contexts and the same map, removed mask or None); this object stays valid and unchanged
+        (vidc_remove_sharded_dev).  Every shard runs its own remove; the mask is in this object's decode_all order, `missing` counts the
+        valid pairs no shard matched.  codec_args as in append, minus bits: want_perm (ef, roc), precision_mode (roc: the mode this
+        object was built with).  See removal.remove for list_nos / ids / removed / missing / invalid: the arrays live on the home
+        device.  The call waits."""
+        from . import _lib, removal
+
+        param, flags = 0, 0
+        if self.kind == 1:
+            flags = _lib.VIDC_EF_WANT_PERM if codec_args.pop("want_perm", False) else 0
+        elif self.kind == 2:
+            param = int(codec_args.pop("precision_mode", _lib.VIDC_PREC_REFERENCE))
+            flags = _lib.VIDC_ROC_WANT_PERM if codec_args.pop("want_perm", False) else 0
+        if codec_args:
+            raise TypeError(f"unknown codec arguments: {sorted(codec_args)}")
+        h, mask = removal._call(_lib.lib().vidc_remove_sharded_dev, self, (param, flags), list_nos, ids, removed, missing, invalid)
+        return type(self)(h, self.ctx, self.ctxs, self.kind), mask  # (the offsets are fetched from the new object on first use)
 
     def perm(self):
         from ._lib import check, lib, ptr
