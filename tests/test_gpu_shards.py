@@ -208,6 +208,35 @@ def test_decode_all_with_the_home_context_as_a_shard(ctxs, objects, F, kind):
     assert np.array_equal(decode_all_guarded(S), objects(kind).decode_all().cpu().numpy())
 
 
+E_SIZES = [1, 2, 3, 1023, 1024, 1025, 2049]  # segments that end before, on and behind an edge of the copy's 1024-element chunks
+
+
+def test_the_id_inverse_cut_on_both_alignment_paths(ctxs):
+    """k_shard_copy<uint64_t, true> (decode_all's inverse cut), 3 shards of packed bits: the output at 0 mod 16 and one element further,
+    at 8 mod 16.  A segment takes the 16-byte path iff its start in its shard and its start in the output agree mod 16 -- the plan
+    model says that both kinds exist at either skew, and the shift turns each into the other -- behind a head of one id where the
+    destination is at 8 mod 16."""
+    home, shard_ctxs = ctxs
+    off, ids = csr(E_SIZES, seed=31)
+    U = encode_u("packed", off, ids)
+    S = encode_s("packed", off, ids, home, shard_ctxs[:3])
+    want = U.decode_all().cpu().numpy()
+    assert want.size == sum(E_SIZES)
+    segs = np.concatenate([sg for _, _, sg in plan_model(E_SIZES, 3)[3]])
+    assert segs.shape[0] == len(E_SIZES)
+    agree = (segs[:, 0] - segs[:, 1]) % 2 == 0  # (the shards decode into 16-byte aligned blocks)
+    assert agree.any() and (~agree).any(), "both the 16-byte path and the 8-byte path must run at either skew"
+    assert (agree & (segs[:, 0] % 2 == 1)).any(), "a 16-byte segment behind a head of one id"
+    L = _L()
+    for skew in (0, 1):
+        whole, view = cr.guarded(want.size, np.int64, device="cuda", misalign_elems=skew)
+        assert L.ptr(view) % 16 == 8 * skew
+        _torch().cuda.synchronize()
+        L.check(L.lib().vidc_shards_decode_all(S.ctx.h, S.h, L.ptr(view)))
+        cr.assert_guards_intact(whole, view, f"shards decode_all, skew {skew}")
+        cr.assert_view_equals(view, want, f"shards decode_all, skew {skew}")
+
+
 @pytest.mark.parametrize("ns", NSHARDS)
 @pytest.mark.parametrize("kind", KINDS)
 def test_decode_lists_keeps_request_order_and_repeats(objects, kind, ns):

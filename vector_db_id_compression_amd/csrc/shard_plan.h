@@ -1,5 +1,6 @@
 // shard_plan.h -- the host part of vidc_shards (include/vidc.h): which shard owns which list, the lists' local numbers and offsets, the
-// segment tables of the cut and the routing of requests.  Host code only, no HIP include: tests/shard_plan_test.cpp builds it with g++.
+// segment tables of the cut, the routing of requests and the byte layout of the scratch blocks.  Host code only, no HIP include:
+// tests/shard_plan_test.cpp, shard_plan_owner_test.cpp and shard_blocks_test.cpp build it with g++.
 //
 // Ownership is the longest-processing-time rule on the list lengths, stated so that it equals sharding.lpt_partition bit for bit: lists
 // are taken in descending size, ties by ascending list number; each goes to the shard with the least load so far, ties to the lowest
@@ -167,6 +168,42 @@ inline int route_gather(const ShardPlan &p, uint64_t m, const uint64_t *list_nos
         r.item_index[s].push_back(i);
     }
     return 0;
+}
+
+// The byte offsets of the two scratch blocks of a routed call (translate_labels, append, remove) over n requests.  A section the call
+// does not have is empty.  The 8-byte sections come first, so they are 8-aligned; a mask starts at a multiple of 16 (the byte inverse
+// cut takes its 16-byte path by the alignment of both runs) and has its length rounded up to 16; 16 bytes of slack end a block.
+//   home block:               invalid[ns] | local[ns * n] | answers[ns * n] | the shards' masks | found[ns * n] bytes | owner[n] bytes
+//   a far shard's own block:  invalid, 16 bytes | local[n] | ids[n] | answers[n] | found[n] bytes | its mask
+struct UpdateBlocks {
+    size_t local = 0, answers = 0, found = 0, owner = 0, total = 0, found_bytes = 0;  // home block: shard i's slice of a section is its i-th n
+    size_t f_local = 0, f_ids = 0, f_answers = 0, f_found = 0, f_mask = 0;            // a far shard's block
+    std::vector<size_t> mask, f_total;                                                // per shard: its mask in the home block, its far block's size
+};
+// mask_len: per shard, or NULL for a call without masks
+inline UpdateBlocks update_blocks(uint32_t nshards, uint64_t n, bool has_local, bool has_answers, const uint64_t *mask_len, bool has_found,
+                                  bool has_owner) {
+    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t ns = nshards;
+    UpdateBlocks b;
+    b.local = ns * 8;
+    b.answers = b.local + (has_local ? ns * n * 8 : 0);
+    b.found = up16(b.answers + (has_answers ? ns * n * 8 : 0));
+    b.f_local = 16;
+    b.f_ids = b.f_local + (has_local ? n * 8 : 0);
+    b.f_answers = b.f_ids + n * 8;
+    b.f_found = b.f_answers + (has_answers ? n * 8 : 0);
+    b.f_mask = up16(b.f_found + (has_found ? n : 0));
+    for (size_t i = 0; i < ns; i++) {
+        const size_t len = up16(mask_len ? mask_len[i] : 0);
+        b.mask.push_back(b.found);  // (found follows the last mask)
+        b.found += len;
+        b.f_total.push_back(b.f_mask + len + 16);
+    }
+    b.found_bytes = has_found ? ns * n : 0;
+    b.owner = b.found + b.found_bytes;
+    b.total = b.owner + (has_owner ? n : 0) + 16;
+    return b;
 }
 
 }  // namespace shardplan

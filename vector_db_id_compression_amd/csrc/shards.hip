@@ -1,8 +1,11 @@
 // shards.hip -- vidc_shards (include/vidc.h): one CSR set of lists cut over several contexts of one process.  The plan is host code
 // (shard_plan.h); the shards are ordinary vidc_packed / vidc_ef / vidc_roc objects built and served through the public entry points, so a
-// shard IS what the single-object encoder builds from its cut CSR.  What is new on the device: the segmented copy (cut, inverse cut,
-// placement of decode_lists results), the route / join pair of translate_labels, the route / join pair of the append, and the remove's
-// byte inverse cut (the shards' removed masks -> the global mask) and found-byte join (the missing count).
+// shard IS what the single-object encoder builds from its cut CSR.  What is new on the device: the segmented copy k_shard_copy<T, INV>
+// (ids: cut, inverse cut, placement of decode_lists results; bytes: the shards' removed masks -> the global mask of a remove), the route
+// k_shard_route<LABELS> (labels of translate_labels, pairs of append and remove) and the three joins (translate's ids, the append's
+// labels, the remove's found bytes -> the missing count).  Append and remove are one skeleton (update_impl); the byte offsets of their
+// scratch blocks come from shardplan::update_blocks; a shard on another device is served through one helper (FarStage, and DecodedIds
+// for the decodes; the encoder's cut keeps its own copy), a path that has never executed.
 #include <thread>
 
 #include "common.h"
@@ -17,59 +20,32 @@ using namespace vidc::shardplan;
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------------ kernels
-// Segmented copy, a wavefront per chunk of SHARD_COPY_UNIT elements: dst[seg.dst_start ..] = src[seg.src_start ..] (INV: the segment
-// table read the other way round -- the inverse of the cut).  16-byte accesses where the two runs share their alignment mod 16 (after
-// at most one leading element), 8-byte accesses otherwise.  chunks / segs come from the host plan: chunk.seg < the table's length and
-// chunk.start < seg.count by construction (shardplan::build_copy_chunks).
-template <bool INV>
-__global__ void __launch_bounds__(256) k_shard_copy(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, const Segment *__restrict__ segs,
+// Segmented copy, a wavefront per chunk of SHARD_COPY_UNIT elements of T (uint64_t: ids; uint8_t: the removed mask of a sharded remove):
+// dst[seg.dst_start ..] = src[seg.src_start ..] (INV: the segment table read the other way round -- the inverse of the cut).  16-byte
+// accesses where the two runs share their alignment mod 16, behind a head of less than 16 bytes (at most one id, at most 15 mask
+// bytes) and in front of a tail of less than 16; accesses of one element otherwise.  chunks / segs come from the host plan: chunk.seg <
+// the table's length and chunk.start < seg.count by construction (shardplan::build_copy_chunks).
+template <typename T, bool INV>
+__global__ void __launch_bounds__(256) k_shard_copy(const T *__restrict__ src, T *__restrict__ dst, const Segment *__restrict__ segs,
                                                     const CopyChunk *__restrict__ chunks, uint64_t nchunks) {
+    constexpr uint32_t PER16 = 16u / (uint32_t)sizeof(T);
     const uint32_t lane = dev::lane_id();
     for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < nchunks; c += (uint64_t)gridDim.x * 4u) {
         const CopyChunk ch = chunks[c];
         const Segment sg = segs[ch.seg];
         const uint64_t left = sg.count - ch.start;
         const uint32_t nc = (uint32_t)(left < SHARD_COPY_UNIT ? left : SHARD_COPY_UNIT);
-        const uint64_t *s = src + (INV ? sg.dst_start : sg.src_start) + ch.start;
-        uint64_t *d = dst + (INV ? sg.src_start : sg.dst_start) + ch.start;
+        const T *s = src + (INV ? sg.dst_start : sg.src_start) + ch.start;
+        T *d = dst + (INV ? sg.src_start : sg.dst_start) + ch.start;
         if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0u) {
-            uint32_t head = (uint32_t)(((uintptr_t)d & 15u) ? 1u : 0u);
+            uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u) / (uint32_t)sizeof(T);
             head = head < nc ? head : nc;
             if (lane < head) d[lane] = s[lane];
-            const uint32_t nv = (nc - head) / 2u;
+            const uint32_t nv = (nc - head) / PER16;  // (= (nc - head) * sizeof(T) / 16)
             const uint4 *sv = (const uint4 *)(s + head);
             uint4 *dv = (uint4 *)(d + head);
             for (uint32_t j = lane; j < nv; j += 64u) dv[j] = sv[j];
-            for (uint32_t j = head + nv * 2u + lane; j < nc; j += 64u) d[j] = s[j];
-        } else {
-            for (uint32_t j = lane; j < nc; j += 64u) d[j] = s[j];
-        }
-    }
-}
-
-// The inverse cut on bytes (the removed mask of a sharded remove): the same segment and chunk tables, counted in uint8_t elements, so a
-// wavefront moves at most SHARD_COPY_UNIT bytes.  16-byte accesses where the two runs share their alignment mod 16, behind a head of at
-// most 15 bytes and in front of a tail of at most 15; byte accesses otherwise.
-template <bool INV>
-__global__ void __launch_bounds__(256) k_shard_copy_bytes(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const Segment *__restrict__ segs,
-                                                          const CopyChunk *__restrict__ chunks, uint64_t nchunks) {
-    const uint32_t lane = dev::lane_id();
-    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < nchunks; c += (uint64_t)gridDim.x * 4u) {
-        const CopyChunk ch = chunks[c];
-        const Segment sg = segs[ch.seg];
-        const uint64_t left = sg.count - ch.start;
-        const uint32_t nc = (uint32_t)(left < SHARD_COPY_UNIT ? left : SHARD_COPY_UNIT);
-        const uint8_t *s = src + (INV ? sg.dst_start : sg.src_start) + ch.start;
-        uint8_t *d = dst + (INV ? sg.src_start : sg.dst_start) + ch.start;
-        if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0u) {
-            uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
-            head = head < nc ? head : nc;
-            if (lane < head) d[lane] = s[lane];
-            const uint32_t nv = (nc - head) / 16u;
-            const uint4 *sv = (const uint4 *)(s + head);
-            uint4 *dv = (uint4 *)(d + head);
-            for (uint32_t j = lane; j < nv; j += 64u) dv[j] = sv[j];
-            for (uint32_t j = head + nv * 16u + lane; j < nc; j += 64u) d[j] = s[j];
+            for (uint32_t j = head + nv * PER16 + lane; j < nc; j += 64u) d[j] = s[j];
         } else {
             for (uint32_t j = lane; j < nc; j += 64u) d[j] = s[j];
         }
@@ -78,23 +54,26 @@ __global__ void __launch_bounds__(256) k_shard_copy_bytes(const uint8_t *__restr
 
 constexpr uint32_t NO_OWNER = 0xffu;
 
-// Label route: local[s * n + i] = local_no << 32 | offset if shard s owns label i's list, else -1 (the shards' own translate gives -1 for
-// a negative label and does not count it); owner[i] = the owning shard, NO_OWNER for a negative label or a list >= nlist (the latter
-// counted in *invalid).  The offset is checked by the owner.
-__global__ void __launch_bounds__(256) k_shard_route(const int64_t *__restrict__ labels, uint64_t n, const uint64_t *__restrict__ map, uint64_t nlist,
+// Route.  LABELS (translate_labels): req[i] is a label, local[s * n + i] = local_no << 32 | offset if shard s owns label i's list, else
+// -1 (the shards' own translate gives -1 for a negative label and does not count it); the offset is checked by the owner.  !LABELS (the
+// pairs of an append or a remove): req[i] is a list number, local[s * n + i] = its local number if shard s owns it, else -1 (the shards'
+// own calls skip a negative list number and do not count it).  owner[i] = the owning shard, NO_OWNER for a negative request or a list >=
+// nlist (the latter counted in *invalid).
+template <bool LABELS>
+__global__ void __launch_bounds__(256) k_shard_route(const int64_t *__restrict__ req, uint64_t n, const uint64_t *__restrict__ map, uint64_t nlist,
                                                      uint32_t nshards, int64_t *__restrict__ local, uint8_t *__restrict__ owner,
                                                      unsigned long long *invalid) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
         const uint64_t i = i0 + dev::lane_id();
-        const int64_t lab = i < n ? labels[i] : -1;
-        uint64_t list, off;
-        const bool pos = req_label(lab, list, off);
+        const int64_t r = i < n ? req[i] : -1;
+        uint64_t list = (uint64_t)r, off = 0;
+        const bool pos = LABELS ? req_label(r, list, off) : r >= 0;
         const bool ok = pos && list < nlist;
         const uint64_t e = ok ? map[list] : 0;
         const uint32_t own = ok ? (uint32_t)(e >> 32) : NO_OWNER;
         if (i < n) {
-            const int64_t mine = (int64_t)((e & 0xffffffffull) << 32 | off);
+            const int64_t mine = (int64_t)(LABELS ? (e & 0xffffffffull) << 32 | off : e & 0xffffffffull);
             for (uint32_t s = 0; s < nshards; s++) local[(uint64_t)s * n + i] = s == own ? mine : -1;
             owner[i] = (uint8_t)own;
         }
@@ -115,29 +94,6 @@ __global__ void __launch_bounds__(256) k_shard_join(const int64_t *__restrict__ 
         unsigned long long sum = 0;
         for (uint32_t s = 0; s < nshards; s++) sum += shard_invalid[s];
         if (sum) atomicAdd(invalid, sum);
-    }
-}
-
-// Pair route of an append: local[s * n + i] = the local number of pair i's list if shard s owns it, else -1 (the shards' own appends skip
-// a negative list number and do not count it); owner[i] = the owning shard, NO_OWNER for a negative list number or one >= nlist (the
-// latter counted in *invalid).
-__global__ void __launch_bounds__(256) k_shard_route_pairs(const int64_t *__restrict__ list_nos, uint64_t n, const uint64_t *__restrict__ map,
-                                                           uint64_t nlist, uint32_t nshards, int64_t *__restrict__ local, uint8_t *__restrict__ owner,
-                                                           unsigned long long *invalid) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {  // (i0: wavefront-uniform)
-        const uint64_t i = i0 + dev::lane_id();
-        const int64_t l = i < n ? list_nos[i] : -1;
-        const bool pos = l >= 0;
-        const bool ok = pos && (uint64_t)l < nlist;
-        const uint64_t e = ok ? map[l] : 0;
-        const uint32_t own = ok ? (uint32_t)(e >> 32) : NO_OWNER;
-        if (i < n) {
-            const int64_t mine = (int64_t)(e & 0xffffffffull);
-            for (uint32_t s = 0; s < nshards; s++) local[(uint64_t)s * n + i] = s == own ? mine : -1;
-            owner[i] = (uint8_t)own;
-        }
-        req_count_invalid(pos && !ok, invalid);
     }
 }
 
@@ -334,10 +290,10 @@ struct StagedCopy {
     Scratch s_seg, s_chunk;
     std::vector<CopyChunk> chunks;
 };
-template <bool INV>
-int launch_copy(vidc_ctx *home, const uint64_t *src, uint64_t *dst, const Segment *d_segs, const CopyChunk *d_chunks, uint64_t nchunks) {
+template <bool INV, typename T>
+int launch_copy(vidc_ctx *home, const T *src, T *dst, const Segment *d_segs, const CopyChunk *d_chunks, uint64_t nchunks) {
     if (!nchunks) return VIDC_OK;
-    hipLaunchKernelGGL((k_shard_copy<INV>), copy_grid(home, nchunks), dim3(256), 0, home->stream, src, dst, d_segs, d_chunks, nchunks);
+    hipLaunchKernelGGL((k_shard_copy<T, INV>), copy_grid(home, nchunks), dim3(256), 0, home->stream, src, dst, d_segs, d_chunks, nchunks);
     VIDC_HIP(hipGetLastError());
     return VIDC_OK;
 }
@@ -525,6 +481,188 @@ std::vector<int> shards_with_ids(const vidc_shards *s) {
         if (s->objs[(size_t)i] && s->plan.load[(size_t)i]) v.push_back(i);
     return v;
 }
+std::vector<int> shards_with_objects(const vidc_shards *s) {
+    std::vector<int> v;
+    for (int i = 0; i < s->plan.nshards; i++)
+        if (s->objs[(size_t)i]) v.push_back(i);
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------- a shard on another device
+// Both helpers do nothing for a shard on the home device, which reads and writes the home context's blocks in place.  Their other
+// branches have never executed: every test machine has one GPU.
+
+// One shard's arrays of a routed call (translate_labels, append, remove).  For a shard elsewhere a block of the shard's own cache stands
+// in, at the offsets of an UpdateBlocks: in() copies into it on the shard's stream at once, out() hands out a part of it and flush()
+// enqueues the copies back.  A failed HIP call stays in `st` (and in vidc_last_error) and the later calls do nothing, so the caller
+// looks at `st` once, before it uses the pointers.
+struct FarStage {
+    struct Back { void *home; const void *far; size_t bytes; };
+    vidc_ctx *c = nullptr;
+    Scratch blk;  // empty: the shard is on the home device
+    Back back[4] = {};
+    int nback = 0, st = VIDC_OK;
+    // sets the current device to the shard's
+    int open(const vidc_shards *s, int sh, size_t bytes) {
+        c = s->ctxs[(size_t)sh];
+        VIDC_HIP(hipSetDevice(c->device));
+        if (!s->same_device(sh)) st = blk.get(c, bytes);
+        return st;
+    }
+    int copy(void *dst, const void *src, size_t bytes) {
+        if (bytes) VIDC_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, c->stream));
+        return VIDC_OK;
+    }
+    int zero(void *p, size_t bytes) {
+        VIDC_HIP(hipMemsetAsync(p, 0, bytes, c->stream));
+        return VIDC_OK;
+    }
+    // the pointer the shard's call reads: home (NULL stays NULL), or its copy at `off` of the far block
+    template <typename T>
+    const T *in(const T *home, size_t off, size_t bytes) {
+        if (!blk.p || !home) return home;
+        T *far = (T *)(blk.as<uint8_t>() + off);
+        if (st == VIDC_OK) st = copy(far, home, bytes);
+        return far;
+    }
+    // the pointer the shard's call writes: home (NULL stays NULL), or `off` of the far block, copied back by flush()
+    template <typename T>
+    T *out(T *home, size_t off, size_t bytes) {
+        if (!blk.p || !home) return home;
+        back[nback++] = Back{home, blk.as<uint8_t>() + off, bytes};
+        return (T *)(blk.as<uint8_t>() + off);
+    }
+    // the shard's invalid counter: the home one (the caller zeroed it), or the far block's first word, zeroed here
+    uint64_t *counter(unsigned long long *home) {
+        if (blk.p && st == VIDC_OK) st = zero(blk.p, 8);
+        return out((uint64_t *)home, 0, 8);
+    }
+    int flush() {
+        for (int k = 0; k < nback && st == VIDC_OK; k++) st = copy(back[k].home, back[k].far, back[k].bytes);
+        return st;
+    }
+};
+
+// The ids a shard decodes: `decode(c, dst)` enqueues the shard's decode of n_ids ids into a block of its own cache; a shard elsewhere
+// copies them to a block of the home cache on its stream; the shard's stream is waited for.  ids(): what the home stream reads.
+struct DecodedIds {
+    Scratch shard, home;
+    const uint64_t *ids() const { return (home.p ? home : shard).as<uint64_t>(); }
+    template <typename Decode>
+    int run(const vidc_shards *s, int sh, uint64_t n_ids, Decode &&decode) {
+        vidc_ctx *c = s->ctxs[(size_t)sh];
+        VIDC_HIP(hipSetDevice(c->device));
+        VIDC_TRY(shard.get(c, n_ids * 8));
+        VIDC_TRY(decode(c, shard.as<uint64_t>()));
+        if (!s->same_device(sh)) {
+            VIDC_HIP(hipSetDevice(s->home->device));
+            VIDC_TRY(home.get(s->home, n_ids * 8));
+            VIDC_HIP(hipSetDevice(c->device));
+            VIDC_HIP(hipMemcpyAsync(home.p, shard.p, n_ids * 8, hipMemcpyDefault, c->stream));
+        }
+        VIDC_HIP(vidc_stream_wait(c->stream));
+        return VIDC_OK;
+    }
+};
+
+// ------------------------------------------------------------------------------------------- append and remove: one skeleton
+struct UpdateNames {  // the error prefix and the VIDC_TRACE phases
+    const char *call, *a_shard, *shards_done, *tail_enqueued;
+};
+// The route kernel writes every shard's full-length local list numbers (a remove in any-list mode routes nothing), every shard that
+// holds an object runs its own call on them (one host thread each, behind a host wait for the route), the tail kernels join the shards'
+// answers.  The new plan keeps the owner of every list; its offsets are the new shard objects' own list sizes scattered through the map.
+// new_param, flags: the new object's.  d_list_nos: routed if n != 0 and it is not NULL.  shard_call(i, f, base, inv, &new object): shard
+// i's own call; f is open on the shard, base is the home block (offsets: B), inv the shard's invalid counter.  tail(base) enqueues the
+// tail kernels on the home stream; has_tail: there are any (last_kernel_ms = the route's time + theirs).
+template <typename ShardCall, typename Tail>
+int update_impl(vidc_ctx *home, const vidc_shards *s, const UpdateNames &nm, int new_param, uint32_t flags, uint64_t n, const int64_t *d_list_nos,
+                uint64_t *d_invalid, const UpdateBlocks &B, bool has_tail, ShardCall &&shard_call, Tail &&tail, vidc_shards **out) {
+    HostTrace tr(nm.call);
+    const ShardPlan &P = s->plan;
+    const uint32_t ns = (uint32_t)P.nshards;
+    const bool route = n && d_list_nos;
+    const std::vector<int> involved = shards_with_objects(s);
+    std::unique_ptr<vidc_shards> N(new vidc_shards());
+    N->kind = s->kind;
+    N->flags = flags;
+    N->home = home;
+    N->ctxs = s->ctxs;
+    N->objs.assign((size_t)ns, nullptr);
+    N->param = new_param;
+    VIDC_HIP(hipSetDevice(home->device));
+    PlanTables tables;
+    Scratch blk;
+    Pinned h_inv;
+    std::vector<FarStage> far((size_t)ns);
+    std::vector<std::vector<uint64_t>> sizes((size_t)ns);
+    ShardStreamsGuard sguard(s);
+    StreamGuard hguard(home, false);
+    VIDC_TRY(blk.get(home, B.total));
+    VIDC_TRY(h_inv.get(home, (size_t)ns * 8));
+    uint8_t *base = blk.as<uint8_t>();
+    unsigned long long *sh_inv = blk.as<unsigned long long>();
+    hguard.arm();
+    EventTimer timer(home);
+    VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
+    if (B.found_bytes) VIDC_HIP(hipMemsetAsync(base + B.found, 0, B.found_bytes, home->stream));  // (a shard without an object answers nothing)
+    double kernel_ms = 0;
+    if (route) {
+        VIDC_HIP(timer.start());
+        hipLaunchKernelGGL(k_shard_route<false>, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, n, (const uint64_t *)s->d_map.p, P.nlist,
+                           ns, (int64_t *)(base + B.local), base + B.owner, (unsigned long long *)d_invalid);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(timer.mark());
+    }
+    // every shard's call waits anyway: the route (and the caller's batch) is waited for here, once, before the shard threads start
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    if (route) kernel_ms = timer.elapsed();
+    hguard.disarm();
+    tr.mark("routed, waited");
+    sguard.which = involved;
+    vidc_shards *Np = N.get();
+    const int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int sh) -> int {
+        const size_t i = (size_t)sh;
+        FarStage &f = far[i];
+        VIDC_TRY(f.open(s, sh, B.f_total[i]));
+        VIDC_TRY(shard_call(i, f, base, f.counter(sh_inv + i), &Np->objs[i]));
+        VIDC_TRY(f.flush());
+        VIDC_HIP(vidc_stream_wait(f.c->stream));
+        HostTrace ts(nm.a_shard);
+        const int rc = codec_list_sizes(s->kind, f.c, Np->objs[i], P.lists[i].size(), sizes[i]);
+        ts.mark("list sizes to the host");
+        return rc;
+    });
+    tr.mark(nm.shards_done);
+    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
+    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
+    VIDC_HIP(hipSetDevice(home->device));
+    std::vector<uint64_t> off(P.nlist + 1, 0);
+    for (uint64_t l = 0; l < P.nlist; l++) off[l + 1] = off[l] + sizes[(size_t)P.owner[l]][P.local_no[l]];
+    N->plan = make_plan_for_owner(off.data(), P.nlist, P.nshards, P.owner);
+    tr.mark("plan");
+    VIDC_TRY(create_events(N.get()));
+    hguard.arm();
+    if (has_tail) VIDC_HIP(timer.start());
+    VIDC_TRY(tail(base));
+    if (has_tail) VIDC_HIP(timer.mark());
+    unsigned long long *h = h_inv.as<unsigned long long>();
+    VIDC_HIP(hipMemcpyAsync(h, sh_inv, (size_t)ns * 8, hipMemcpyDeviceToHost, home->stream));
+    VIDC_TRY(upload_plan(N.get(), tables));
+    tr.mark(nm.tail_enqueued);
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    hguard.disarm();
+    tr.mark("waited");
+    if (has_tail) kernel_ms += timer.elapsed();
+    home->last_kernel_ms = kernel_ms;  // (route + tail)
+    for (uint32_t i = 0; i < ns; i++)
+        if (h[i]) {  // every local number a shard sees is valid or negative
+            set_error("%s: internal error, shard %u counted %llu list numbers outside its lists", nm.call, i, h[i]);
+            return VIDC_ERR_INVALID;
+        }
+    *out = N.release();
+    return VIDC_OK;
+}
 
 }  // namespace
 
@@ -584,25 +722,14 @@ int vidc_shards_decode_all(vidc_ctx *home, const vidc_shards *s, uint64_t *d_out
     if (!P.ntotal) return VIDC_OK;
     if (!d_out) { set_error("shards decode_all: NULL output"); return VIDC_ERR_INVALID; }
     const std::vector<int> involved = shards_with_ids(s);
-    std::vector<Scratch> st_shard((size_t)P.nshards), st_home((size_t)P.nshards);
+    std::vector<DecodedIds> dec((size_t)P.nshards);
     ShardStreamsGuard sguard(s);
     StreamGuard hguard(home, false);
     sguard.which = involved;
-    // the shards decode concurrently, each into a block of its context's cache (and, from another device, into home staging)
+    // the shards decode concurrently
     VIDC_TRY(fan_out(involved, [&](int sh) -> int {
         const size_t i = (size_t)sh;
-        vidc_ctx *c = s->ctxs[i];
-        VIDC_HIP(hipSetDevice(c->device));
-        VIDC_TRY(st_shard[i].get(c, P.load[i] * 8));
-        VIDC_TRY(codec_decode_all(s->kind, c, s->objs[i], st_shard[i].as<uint64_t>()));
-        if (!s->same_device(sh)) {
-            VIDC_HIP(hipSetDevice(home->device));
-            VIDC_TRY(st_home[i].get(home, P.load[i] * 8));
-            VIDC_HIP(hipSetDevice(c->device));
-            VIDC_HIP(hipMemcpyAsync(st_home[i].p, st_shard[i].p, P.load[i] * 8, hipMemcpyDefault, c->stream));
-        }
-        VIDC_HIP(vidc_stream_wait(c->stream));
-        return VIDC_OK;
+        return dec[i].run(s, sh, P.load[i], [&](vidc_ctx *c, uint64_t *dst) { return codec_decode_all(s->kind, c, s->objs[i], dst); });
     }));
     VIDC_HIP(hipSetDevice(home->device));
     hguard.arm();
@@ -610,8 +737,7 @@ int vidc_shards_decode_all(vidc_ctx *home, const vidc_shards *s, uint64_t *d_out
     VIDC_HIP(uncut_timer.start());
     for (int sh : involved) {
         const size_t i = (size_t)sh;
-        const uint64_t *src = (s->same_device(sh) ? st_shard[i] : st_home[i]).as<uint64_t>();
-        VIDC_TRY(launch_copy<true>(home, src, d_out, s->d_cut[i].p, s->d_cut_chunks[i].p, s->n_cut_chunks[i]));
+        VIDC_TRY(launch_copy<true>(home, dec[i].ids(), d_out, s->d_cut[i].p, s->d_cut_chunks[i].p, s->n_cut_chunks[i]));
     }
     VIDC_TRY(uncut_timer.finish());  // (the call's wait; last_kernel_ms = the inverse cut)
     hguard.disarm();
@@ -639,34 +765,21 @@ int vidc_shards_decode_lists(vidc_ctx *home, const vidc_shards *s, uint64_t m, c
     std::vector<int> involved;
     for (int sh = 0; sh < P.nshards; sh++)
         if (R.staged[(size_t)sh]) involved.push_back(sh);
-    std::vector<Scratch> st_shard((size_t)P.nshards), st_home((size_t)P.nshards);
+    std::vector<DecodedIds> dec((size_t)P.nshards);
     std::vector<StagedCopy> copies((size_t)P.nshards);
     ShardStreamsGuard sguard(s);
     StreamGuard hguard(home, false);
     sguard.which = involved;
     VIDC_TRY(fan_out(involved, [&](int sh) -> int {
         const size_t i = (size_t)sh;
-        vidc_ctx *c = s->ctxs[i];
-        VIDC_HIP(hipSetDevice(c->device));
-        VIDC_TRY(st_shard[i].get(c, R.staged[i] * 8));
         std::vector<uint64_t> off(R.local_lists[i].size() + 1);
-        VIDC_TRY(codec_decode_lists(s->kind, c, s->objs[i], R.local_lists[i].size(), R.local_lists[i].data(), st_shard[i].as<uint64_t>(), off.data()));
-        if (!s->same_device(sh)) {
-            VIDC_HIP(hipSetDevice(home->device));
-            VIDC_TRY(st_home[i].get(home, R.staged[i] * 8));
-            VIDC_HIP(hipSetDevice(c->device));
-            VIDC_HIP(hipMemcpyAsync(st_home[i].p, st_shard[i].p, R.staged[i] * 8, hipMemcpyDefault, c->stream));
-        }
-        VIDC_HIP(vidc_stream_wait(c->stream));
-        return VIDC_OK;
+        return dec[i].run(s, sh, R.staged[i], [&](vidc_ctx *c, uint64_t *dst) {
+            return codec_decode_lists(s->kind, c, s->objs[i], R.local_lists[i].size(), R.local_lists[i].data(), dst, off.data());
+        });
     }));
     VIDC_HIP(hipSetDevice(home->device));
     hguard.arm();
-    for (int sh : involved) {
-        const size_t i = (size_t)sh;
-        const uint64_t *src = (s->same_device(sh) ? st_shard[i] : st_home[i]).as<uint64_t>();
-        VIDC_TRY(staged_copy(home, src, d_out, R.place[i], copies[i]));
-    }
+    for (int sh : involved) VIDC_TRY(staged_copy(home, dec[(size_t)sh].ids(), d_out, R.place[(size_t)sh], copies[(size_t)sh]));
     VIDC_HIP(vidc_stream_wait(home->stream));
     hguard.disarm();
     return VIDC_OK;
@@ -680,47 +793,33 @@ int vidc_shards_translate_labels_dev(vidc_ctx *home, const vidc_shards *s, uint6
     if (n >= (1ull << 32)) { set_error("shards translate_labels: n must be below 2^32"); return VIDC_ERR_INVALID; }
     const ShardPlan &P = s->plan;
     const uint32_t ns = (uint32_t)P.nshards;
-    std::vector<int> involved;
-    for (int sh = 0; sh < P.nshards; sh++)
-        if (s->objs[(size_t)sh]) involved.push_back(sh);
+    const std::vector<int> involved = shards_with_objects(s);
     VIDC_HIP(hipSetDevice(home->device));
-    // home block: shard_invalid[ns] | local[ns * n] | answers[ns * n] | owner[n]
+    const UpdateBlocks B = update_blocks(ns, n, true, true, nullptr, false, true);
     Scratch blk;
-    std::vector<Scratch> far((size_t)P.nshards);  // a shard on another device: invalid | labels[n] | answers[n] in its own cache
+    std::vector<FarStage> far((size_t)ns);
     ShardStreamsGuard sguard(s);
     StreamGuard hguard(home, false);
-    VIDC_TRY(blk.get(home, (size_t)ns * 8 + 2 * (size_t)ns * n * 8 + n));
+    VIDC_TRY(blk.get(home, B.total));
     unsigned long long *sh_inv = blk.as<unsigned long long>();
-    int64_t *local = (int64_t *)(sh_inv + ns), *answers = local + (uint64_t)ns * n;
-    uint8_t *owner = (uint8_t *)(answers + (uint64_t)ns * n);
+    int64_t *local = (int64_t *)(blk.as<uint8_t>() + B.local), *answers = (int64_t *)(blk.as<uint8_t>() + B.answers);
+    uint8_t *owner = blk.as<uint8_t>() + B.owner;
     hguard.arm();
     VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
-    hipLaunchKernelGGL(k_shard_route, req_grid(home, n), dim3(256), 0, home->stream, d_labels, n, (const uint64_t *)s->d_map.p, P.nlist, ns, local,
-                       owner, (unsigned long long *)d_invalid);
+    hipLaunchKernelGGL(k_shard_route<true>, req_grid(home, n), dim3(256), 0, home->stream, d_labels, n, (const uint64_t *)s->d_map.p, P.nlist, ns,
+                       local, owner, (unsigned long long *)d_invalid);
     VIDC_HIP(hipGetLastError());
     sguard.which = involved;
     auto shard_call = [&](int sh) -> int {
         const size_t i = (size_t)sh;
-        vidc_ctx *c = s->ctxs[i];
-        VIDC_HIP(hipSetDevice(c->device));
-        const int64_t *lab = local + (uint64_t)i * n;
-        int64_t *ans = answers + (uint64_t)i * n;
-        uint64_t *inv = (uint64_t *)(sh_inv + i);
-        if (!s->same_device(sh)) {
-            VIDC_TRY(far[i].get(c, 16 + 2 * n * 8));
-            inv = far[i].as<uint64_t>();
-            int64_t *f_lab = (int64_t *)(inv + 2);
-            VIDC_HIP(hipMemsetAsync(inv, 0, 8, c->stream));
-            VIDC_HIP(hipMemcpyAsync(f_lab, lab, n * 8, hipMemcpyDefault, c->stream));
-            lab = f_lab;
-            ans = f_lab + n;
-        }
-        VIDC_TRY(codec_translate(s->kind, c, s->objs[i], n, lab, ans, inv));
-        if (!s->same_device(sh)) {
-            VIDC_HIP(hipMemcpyAsync(answers + (uint64_t)i * n, ans, n * 8, hipMemcpyDefault, c->stream));
-            VIDC_HIP(hipMemcpyAsync(sh_inv + i, inv, 8, hipMemcpyDefault, c->stream));
-        }
-        return VIDC_OK;
+        FarStage &f = far[i];
+        VIDC_TRY(f.open(s, sh, B.f_total[i]));
+        const int64_t *lab = f.in((const int64_t *)local + i * n, B.f_local, n * 8);
+        int64_t *ans = f.out(answers + i * n, B.f_answers, n * 8);
+        uint64_t *inv = f.counter(sh_inv + i);
+        VIDC_TRY(f.st);
+        VIDC_TRY(codec_translate(s->kind, f.c, s->objs[i], n, lab, ans, inv));
+        return f.flush();
     };
     if (s->kind == VIDC_KIND_ROC) {
         // ROC's translate plans on the host and waits: one thread per shard, behind a host wait for the route
@@ -806,9 +905,8 @@ int vidc_sharded_loads(const vidc_shards *s, uint64_t *loads) {
     return VIDC_OK;
 }
 
-// Append (include/vidc.h): the route kernel writes every shard's full-length local list numbers, every shard that holds an object runs
-// its own append on them (one host thread each, behind a host wait for the route), the join kernel turns the owners' labels into global
-// ones.  The new plan keeps the owner of every list; its offsets are the new shard objects' own list sizes scattered through the map.
+// Append (include/vidc.h), through update_impl: every shard appends the pairs whose lists it owns, the join kernel turns the owners'
+// labels into global ones.
 int vidc_sharded_append_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, int param,
                             uint32_t flags, vidc_shards **out, int64_t *d_labels, uint64_t *d_invalid) {
     if (out) *out = nullptr;
@@ -818,125 +916,34 @@ int vidc_sharded_append_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_add
     }
     if (n_add >= 0xffffffffull) { set_error("sharded append: a batch holds fewer than 2^32 - 1 pairs"); return VIDC_ERR_INVALID; }
     VIDC_TRY(check_request(home, s, "sharded append"));
-    HostTrace tr("sharded append");
-    const ShardPlan &P = s->plan;
-    const uint32_t ns = (uint32_t)P.nshards;
     const uint64_t n = n_add;
-    std::vector<int> involved;
-    for (int sh = 0; sh < P.nshards; sh++)
-        if (s->objs[(size_t)sh]) involved.push_back(sh);
-    std::unique_ptr<vidc_shards> N(new vidc_shards());
-    N->kind = s->kind;
-    N->flags = flags;
-    N->home = home;
-    N->ctxs = s->ctxs;
-    N->objs.assign((size_t)ns, nullptr);
-    N->param = s->kind == VIDC_KIND_EF || (s->kind == VIDC_KIND_PACKED && param == 0) ? s->param : param;
-    VIDC_HIP(hipSetDevice(home->device));
-    // home block: shard_invalid[ns] | local[ns * n] | shard labels[ns * n] | owner[n]
-    PlanTables tables;
-    Scratch blk;
-    Pinned h_inv;
-    std::vector<Scratch> far((size_t)ns);  // a shard on another device: invalid | list numbers[n] | ids[n] | labels[n] in its own cache
-    std::vector<std::vector<uint64_t>> sizes((size_t)ns);
-    ShardStreamsGuard sguard(s);
-    StreamGuard hguard(home, false);
-    VIDC_TRY(blk.get(home, (size_t)ns * 8 + 2 * (size_t)ns * n * 8 + n + 8));
-    VIDC_TRY(h_inv.get(home, (size_t)ns * 8));
-    unsigned long long *sh_inv = blk.as<unsigned long long>();
-    int64_t *local = (int64_t *)(sh_inv + ns), *sh_lab = local + (uint64_t)ns * n;
-    uint8_t *owner = (uint8_t *)(sh_lab + (uint64_t)ns * n);
-    hguard.arm();
-    EventTimer timer(home);
-    VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
-    double kernel_ms = 0;
-    if (n) {
-        VIDC_HIP(timer.start());
-        hipLaunchKernelGGL(k_shard_route_pairs, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, n, (const uint64_t *)s->d_map.p, P.nlist, ns,
-                           local, owner, (unsigned long long *)d_invalid);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(timer.mark());
-    }
-    // every shard's append waits anyway: the route (and the caller's batch) is waited for here, once, before the shard threads start
-    VIDC_HIP(vidc_stream_wait(home->stream));
-    if (n) kernel_ms = timer.elapsed();
-    hguard.disarm();
-    tr.mark("routed, waited");
-    sguard.which = involved;
-    vidc_shards *Np = N.get();
-    const int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int sh) -> int {
-        const size_t i = (size_t)sh;
-        vidc_ctx *c = s->ctxs[i];
-        VIDC_HIP(hipSetDevice(c->device));
-        const int64_t *ln = n ? local + (uint64_t)i * n : nullptr;
-        const uint64_t *ids = n ? d_ids : nullptr;
-        int64_t *lab = n && d_labels ? sh_lab + (uint64_t)i * n : nullptr;
-        uint64_t *inv = (uint64_t *)(sh_inv + i);
-        const bool far_shard = !s->same_device(sh);
-        if (far_shard) {
-            VIDC_TRY(far[i].get(c, 16 + 3 * n * 8));
-            inv = far[i].as<uint64_t>();
-            VIDC_HIP(hipMemsetAsync(inv, 0, 8, c->stream));
-            if (n) {
-                int64_t *f_ln = (int64_t *)(inv + 2);
-                uint64_t *f_ids = (uint64_t *)(f_ln + n);
-                VIDC_HIP(hipMemcpyAsync(f_ln, ln, n * 8, hipMemcpyDefault, c->stream));
-                VIDC_HIP(hipMemcpyAsync(f_ids, d_ids, n * 8, hipMemcpyDefault, c->stream));
-                ln = f_ln;
-                ids = f_ids;
-                if (lab) lab = (int64_t *)(f_ids + n);
-            }
-        }
-        VIDC_TRY(codec_append(s->kind, c, s->objs[i], n, ln, ids, param, flags, &Np->objs[i], lab, inv));
-        if (far_shard) {
-            if (lab) VIDC_HIP(hipMemcpyAsync(sh_lab + (uint64_t)i * n, lab, n * 8, hipMemcpyDefault, c->stream));
-            VIDC_HIP(hipMemcpyAsync(sh_inv + i, inv, 8, hipMemcpyDefault, c->stream));
-        }
-        VIDC_HIP(vidc_stream_wait(c->stream));
-        HostTrace ts("sharded append, a shard");
-        const int rc = codec_list_sizes(s->kind, c, Np->objs[i], P.lists[i].size(), sizes[i]);
-        ts.mark("list sizes to the host");
-        return rc;
-    });
-    tr.mark("shards appended, sizes read");
-    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
-    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
-    VIDC_HIP(hipSetDevice(home->device));
-    std::vector<uint64_t> off(P.nlist + 1, 0);
-    for (uint64_t l = 0; l < P.nlist; l++) off[l + 1] = off[l] + sizes[(size_t)P.owner[l]][P.local_no[l]];
-    N->plan = make_plan_for_owner(off.data(), P.nlist, P.nshards, P.owner);
-    tr.mark("plan");
-    VIDC_TRY(create_events(N.get()));
-    hguard.arm();
-    if (n && d_labels) {
-        VIDC_HIP(timer.start());
-        hipLaunchKernelGGL(k_shard_join_labels, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, (const int64_t *)sh_lab,
-                           (const uint8_t *)owner, n, ns, d_labels);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(timer.mark());
-    }
-    unsigned long long *h = h_inv.as<unsigned long long>();
-    VIDC_HIP(hipMemcpyAsync(h, sh_inv, (size_t)ns * 8, hipMemcpyDeviceToHost, home->stream));
-    VIDC_TRY(upload_plan(N.get(), tables));
-    tr.mark("join, tables enqueued");
-    VIDC_HIP(vidc_stream_wait(home->stream));
-    hguard.disarm();
-    tr.mark("waited");
-    if (n && d_labels) kernel_ms += timer.elapsed();
-    home->last_kernel_ms = kernel_ms;  // (route + join)
-    for (uint32_t i = 0; i < ns; i++)
-        if (h[i]) {  // every local number a shard sees is valid or negative
-            set_error("sharded append: internal error, shard %u counted %llu list numbers outside its lists", i, h[i]);
-            return VIDC_ERR_INVALID;
-        }
-    *out = N.release();
-    return VIDC_OK;
+    const uint32_t ns = (uint32_t)s->plan.nshards;
+    const bool want_labels = n && d_labels;
+    const UpdateBlocks B = update_blocks(ns, n, true, want_labels, nullptr, false, true);
+    const UpdateNames nm = {"sharded append", "sharded append, a shard", "shards appended, sizes read", "join, tables enqueued"};
+    const int new_param = s->kind == VIDC_KIND_EF || (s->kind == VIDC_KIND_PACKED && param == 0) ? s->param : param;
+    return update_impl(
+        home, s, nm, new_param, flags, n, d_list_nos, d_invalid, B, want_labels,
+        [&](size_t i, FarStage &f, uint8_t *base, uint64_t *inv, void **obj) -> int {
+            const int64_t *ln = f.in(n ? (const int64_t *)(base + B.local) + i * n : nullptr, B.f_local, n * 8);
+            const uint64_t *ids = f.in(n ? d_ids : nullptr, B.f_ids, n * 8);
+            int64_t *lab = f.out(want_labels ? (int64_t *)(base + B.answers) + i * n : nullptr, B.f_answers, n * 8);
+            VIDC_TRY(f.st);
+            return codec_append(s->kind, f.c, s->objs[i], n, ln, ids, param, flags, obj, lab, inv);
+        },
+        [&](uint8_t *base) -> int {
+            if (!want_labels) return VIDC_OK;
+            hipLaunchKernelGGL(k_shard_join_labels, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, (const int64_t *)(base + B.answers),
+                               (const uint8_t *)(base + B.owner), n, ns, d_labels);
+            VIDC_HIP(hipGetLastError());
+            return VIDC_OK;
+        },
+        out);
 }
 
-// Remove (include/vidc.h): pairs mode routes as the append does, any-list mode hands every shard the caller's ids; every shard that holds
-// an object runs its own remove (one host thread each, behind a host wait for the route) and answers with its removed mask in its own
-// decode_all order and one found byte per pair.  The byte inverse cut with the OLD plan makes the global mask, the found join the
-// missing count.  The new plan keeps the owner of every list; its offsets are the new shard objects' own list sizes.
+// Remove (include/vidc.h), through update_impl: pairs mode routes as the append does, any-list mode hands every shard the caller's ids;
+// every shard answers with its removed mask in its own decode_all order and one found byte per pair.  The byte inverse cut with the OLD
+// plan makes the global mask, the found join the missing count.
 int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int param,
                             uint32_t flags, vidc_shards **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     if (out) *out = nullptr;
@@ -946,140 +953,33 @@ int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm,
     }
     if (n_rm >= 0xffffffffull) { set_error("sharded remove: a batch holds fewer than 2^32 - 1 pairs"); return VIDC_ERR_INVALID; }
     VIDC_TRY(check_request(home, s, "sharded remove"));
-    HostTrace tr("sharded remove");
     const ShardPlan &P = s->plan;
-    const uint32_t ns = (uint32_t)P.nshards;
     const uint64_t n = n_rm;
+    const uint32_t ns = (uint32_t)P.nshards;
     const bool pairs = n && d_list_nos, want_found = n && d_missing;
-    std::vector<int> involved;
-    for (int sh = 0; sh < P.nshards; sh++)
-        if (s->objs[(size_t)sh]) involved.push_back(sh);
-    std::unique_ptr<vidc_shards> N(new vidc_shards());
-    N->kind = s->kind;
-    N->flags = flags;
-    N->home = home;
-    N->ctxs = s->ctxs;
-    N->objs.assign((size_t)ns, nullptr);
-    N->param = s->kind == VIDC_KIND_ROC ? param : s->param;
-    VIDC_HIP(hipSetDevice(home->device));
-    // home block: shard_invalid[ns] | local[ns * n] (pairs mode) | the shards' masks, each at a multiple of 16 | found[ns * n] | owner[n]
-    std::vector<uint64_t> mask_off((size_t)ns + 1, 0);
-    for (uint32_t i = 0; i < ns; i++) mask_off[i + 1] = mask_off[i] + (d_removed ? (P.load[i] + 15) / 16 * 16 : 0);
-    const size_t b_local = ((size_t)ns * 8 + 15) / 16 * 16, b_mask = b_local + (pairs ? (size_t)ns * n * 8 : 0);
-    const size_t b_found = b_mask + mask_off[ns], b_owner = b_found + (want_found ? (size_t)ns * n : 0);
-    PlanTables tables;
-    Scratch blk;
-    Pinned h_inv;
-    std::vector<Scratch> far((size_t)ns);  // a shard on another device: invalid | list numbers[n] | ids[n] | mask | found[n] in its own cache
-    std::vector<std::vector<uint64_t>> sizes((size_t)ns);
-    ShardStreamsGuard sguard(s);
-    StreamGuard hguard(home, false);
-    VIDC_TRY(blk.get(home, b_owner + (pairs ? n : 0) + 16));
-    VIDC_TRY(h_inv.get(home, (size_t)ns * 8));
-    unsigned long long *sh_inv = blk.as<unsigned long long>();
-    int64_t *local = (int64_t *)(blk.as<uint8_t>() + b_local);
-    uint8_t *masks = blk.as<uint8_t>() + b_mask, *found = blk.as<uint8_t>() + b_found;
-    uint8_t *owner = pairs ? blk.as<uint8_t>() + b_owner : nullptr;
-    hguard.arm();
-    EventTimer timer(home);
-    VIDC_HIP(hipMemsetAsync(sh_inv, 0, (size_t)ns * 8, home->stream));
-    if (want_found) VIDC_HIP(hipMemsetAsync(found, 0, (size_t)ns * n, home->stream));  // (a shard without an object answers nothing)
-    double kernel_ms = 0;
-    if (pairs) {
-        VIDC_HIP(timer.start());
-        hipLaunchKernelGGL(k_shard_route_pairs, req_grid(home, n), dim3(256), 0, home->stream, d_list_nos, n, (const uint64_t *)s->d_map.p, P.nlist, ns,
-                           local, owner, (unsigned long long *)d_invalid);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(timer.mark());
-    }
-    // every shard's remove waits anyway: the route (and the caller's batch) is waited for here, once, before the shard threads start
-    VIDC_HIP(vidc_stream_wait(home->stream));
-    if (pairs) kernel_ms = timer.elapsed();
-    hguard.disarm();
-    tr.mark("routed, waited");
-    sguard.which = involved;
-    vidc_shards *Np = N.get();
-    const int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int sh) -> int {
-        const size_t i = (size_t)sh;
-        vidc_ctx *c = s->ctxs[i];
-        VIDC_HIP(hipSetDevice(c->device));
-        const int64_t *ln = pairs ? local + (uint64_t)i * n : nullptr;
-        const uint64_t *ids = n ? d_ids : nullptr;
-        uint8_t *mask = d_removed ? masks + mask_off[i] : nullptr;
-        uint8_t *fnd = want_found ? found + (uint64_t)i * n : nullptr;
-        uint64_t *inv = (uint64_t *)(sh_inv + i);
-        const bool far_shard = !s->same_device(sh);
-        if (far_shard) {
-            const size_t f_mask = 16 + 2 * (size_t)n * 8, f_found = f_mask + (mask_off[i + 1] - mask_off[i]);
-            VIDC_TRY(far[i].get(c, f_found + n + 16));
-            inv = far[i].as<uint64_t>();
-            VIDC_HIP(hipMemsetAsync(inv, 0, 8, c->stream));
-            if (n) {
-                int64_t *f_ln = (int64_t *)(inv + 2);
-                uint64_t *f_ids = (uint64_t *)(f_ln + n);
-                if (pairs) VIDC_HIP(hipMemcpyAsync(f_ln, ln, n * 8, hipMemcpyDefault, c->stream));
-                VIDC_HIP(hipMemcpyAsync(f_ids, d_ids, n * 8, hipMemcpyDefault, c->stream));
-                if (pairs) ln = f_ln;
-                ids = f_ids;
-            }
-            if (mask) mask = far[i].as<uint8_t>() + f_mask;
-            if (fnd) fnd = far[i].as<uint8_t>() + f_found;
-        }
-        VIDC_TRY(codec_remove(s->kind, c, s->objs[i], n, ln, ids, param, flags, &Np->objs[i], mask, inv, fnd));
-        if (far_shard) {
-            if (mask && P.load[i]) VIDC_HIP(hipMemcpyAsync(masks + mask_off[i], mask, P.load[i], hipMemcpyDefault, c->stream));
-            if (fnd) VIDC_HIP(hipMemcpyAsync(found + (uint64_t)i * n, fnd, n, hipMemcpyDefault, c->stream));
-            VIDC_HIP(hipMemcpyAsync(sh_inv + i, inv, 8, hipMemcpyDefault, c->stream));
-        }
-        VIDC_HIP(vidc_stream_wait(c->stream));
-        HostTrace ts("sharded remove, a shard");
-        const int rc = codec_list_sizes(s->kind, c, Np->objs[i], P.lists[i].size(), sizes[i]);
-        ts.mark("list sizes to the host");
-        return rc;
-    });
-    tr.mark("shards removed, sizes read");
-    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
-    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
-    VIDC_HIP(hipSetDevice(home->device));
-    std::vector<uint64_t> off(P.nlist + 1, 0);
-    for (uint64_t l = 0; l < P.nlist; l++) off[l + 1] = off[l] + sizes[(size_t)P.owner[l]][P.local_no[l]];
-    N->plan = make_plan_for_owner(off.data(), P.nlist, P.nshards, P.owner);
-    tr.mark("plan");
-    VIDC_TRY(create_events(N.get()));
-    hguard.arm();
-    const bool tail = (d_removed && P.ntotal) || want_found;
-    if (tail) VIDC_HIP(timer.start());
-    if (d_removed)  // the OLD plan: the masks are in the old shards' decode_all order
-        for (int sh : involved) {
-            const size_t i = (size_t)sh;
-            if (!s->n_cut_chunks[i]) continue;
-            hipLaunchKernelGGL((k_shard_copy_bytes<true>), copy_grid(home, s->n_cut_chunks[i]), dim3(256), 0, home->stream,
-                               (const uint8_t *)(masks + mask_off[i]), d_removed, (const Segment *)s->d_cut[i].p,
-                               (const CopyChunk *)s->d_cut_chunks[i].p, s->n_cut_chunks[i]);
+    const UpdateBlocks B = update_blocks(ns, n, pairs, false, d_removed ? P.load.data() : nullptr, want_found, pairs);
+    const UpdateNames nm = {"sharded remove", "sharded remove, a shard", "shards removed, sizes read", "mask, join, tables enqueued"};
+    return update_impl(
+        home, s, nm, s->kind == VIDC_KIND_ROC ? param : s->param, flags, n, d_list_nos, d_invalid, B, (d_removed && P.ntotal) || want_found,
+        [&](size_t i, FarStage &f, uint8_t *base, uint64_t *inv, void **obj) -> int {
+            const int64_t *ln = f.in(pairs ? (const int64_t *)(base + B.local) + i * n : nullptr, B.f_local, n * 8);
+            const uint64_t *ids = f.in(n ? d_ids : nullptr, B.f_ids, n * 8);
+            uint8_t *mask = f.out(d_removed ? base + B.mask[i] : nullptr, B.f_mask, P.load[i]);
+            uint8_t *fnd = f.out(want_found ? base + B.found + i * n : nullptr, B.f_found, n);
+            VIDC_TRY(f.st);
+            return codec_remove(s->kind, f.c, s->objs[i], n, ln, ids, param, flags, obj, mask, inv, fnd);
+        },
+        [&](uint8_t *base) -> int {
+            if (d_removed)  // the OLD plan: the masks are in the old shards' decode_all order (a shard without an object has no chunk)
+                for (size_t i = 0; i < ns; i++)
+                    VIDC_TRY(launch_copy<true>(home, (const uint8_t *)(base + B.mask[i]), d_removed, s->d_cut[i].p, s->d_cut_chunks[i].p, s->n_cut_chunks[i]));
+            if (!want_found) return VIDC_OK;
+            hipLaunchKernelGGL(k_shard_join_found, req_grid(home, n), dim3(256), 0, home->stream, (const uint8_t *)(base + B.found),
+                               (const uint8_t *)(pairs ? base + B.owner : nullptr), n, ns, (unsigned long long *)d_missing);
             VIDC_HIP(hipGetLastError());
-        }
-    if (want_found) {
-        hipLaunchKernelGGL(k_shard_join_found, req_grid(home, n), dim3(256), 0, home->stream, (const uint8_t *)found, (const uint8_t *)owner, n, ns,
-                           (unsigned long long *)d_missing);
-        VIDC_HIP(hipGetLastError());
-    }
-    if (tail) VIDC_HIP(timer.mark());
-    unsigned long long *h = h_inv.as<unsigned long long>();
-    VIDC_HIP(hipMemcpyAsync(h, sh_inv, (size_t)ns * 8, hipMemcpyDeviceToHost, home->stream));
-    VIDC_TRY(upload_plan(N.get(), tables));
-    tr.mark("mask, join, tables enqueued");
-    VIDC_HIP(vidc_stream_wait(home->stream));
-    hguard.disarm();
-    tr.mark("waited");
-    if (tail) kernel_ms += timer.elapsed();
-    home->last_kernel_ms = kernel_ms;  // (route + mask inverse cut + join)
-    for (uint32_t i = 0; i < ns; i++)
-        if (h[i]) {  // every local number a shard sees is valid or negative
-            set_error("sharded remove: internal error, shard %u counted %llu list numbers outside its lists", i, h[i]);
-            return VIDC_ERR_INVALID;
-        }
-    *out = N.release();
-    return VIDC_OK;
+            return VIDC_OK;
+        },
+        out);
 }
 
 int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host) {
