@@ -137,6 +137,26 @@ const uint32_t *vidc_roc_perm_dev(const vidc_roc *r);
 int vidc_roc_import(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets, const uint32_t *precisions,
                     const uint64_t *heads, const uint32_t *nwords, const uint32_t *mt_draws,
                     const uint32_t *words_concat, vidc_roc **out);
+/* Regroup: a new IVF object made of whole lists of other objects, without encoding.  *out holds m lists on ctx; list j of it is list
+ * list_no[j] of srcs[src_no[j]] (src_no, list_no: host arrays of m).  Size, precision, head, nwords, mt_draws and every stack word are
+ * carried over bit for bit, so the list decodes exactly as it did in its source; no ANS step runs.  A list may be named more than
+ * once; empty lists and lists with nwords == 0 are ordinary.  1 <= nsrc <= VIDC_SHARDS_MAX (declared with the sharded lists below: 8);
+ * every source lives on ctx's device; an entry of srcs may be NULL as long as no src_no names it.  m == 0 is what vidc_roc_import makes
+ * of nlist == 0: VIDC_OK and an object without lists (src_no and list_no may then be NULL).
+ * flags: with VIDC_ROC_WANT_PERM *out carries the IDENTITY permutation in every list -- the convention of the append and the remove: a
+ *   permutation of a derived object is over the positions of what the old lists decode to.  The sources need no permutation.
+ * Like an imported object *out carries no planner hints (the decode planner mirrors the metadata on first use).
+ * Status.  A NULL ctx / srcs / out, a NULL table with m > 0, nsrc outside its range, m >= 2^32 - 1, a src_no >= nsrc or one that names a
+ *   NULL source (these before any source is looked into), a source on another device, a list_no >= its source's nlist:
+ *   VIDC_ERR_INVALID before any device work.  A graph-row source: VIDC_ERR_UNSUPPORTED.  On any error *out == NULL.
+ * What runs, all on the context's stream: the (src_no, list_no) table is uploaded (12 bytes per list); one kernel gathers the five
+ *   per-list arrays from the sources, whose descriptors it takes by value; one scan turns sizes and word counts into the offsets and
+ *   the word offsets; the word total is read back (8 bytes, the call's only read-back); a wavefront per 1024-word chunk copies the
+ *   streams (16-byte accesses where source and destination agree mod 16, behind a head of at most three words -- the copy loop of
+ *   the append's and the remove's splice).  No atomic decides a position and nothing spins.  The call synchronises;
+ *   vidc_ctx_last_kernel_ms covers these launches. */
+int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint64_t m, const uint32_t *src_no /* host, m */,
+                     const uint64_t *list_no /* host, m */, uint32_t flags, vidc_roc **out);
 
 /* Decode every list into d_out (device uint64[ntotal], CSR order, each list in sampling order
  * = the order get_ids returns, codec.cpp:150). */
@@ -546,9 +566,9 @@ int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host);
  * d_labels (may be NULL) and d_invalid (may be NULL; the caller zeroes it) live on the home device; n_add < 2^32 - 1.
  * Immutable.  *out is a NEW sharded object over the same shard contexts and the same home; `s` stays valid and unchanged, and either may be
  *   destroyed first.
- * The map does not change.  Owner and local number of every list in *out are those of `s`: an append never re-balances, so the balance
+ * The map does not change.  Owner and local number of every list in *out are those of `s`: an append keeps the map, so the balance
  *   drifts with the batches.  vidc_sharded_loads (ids per shard = the sum of the owned lists' sizes; a host accessor, no device work) lets a
- *   caller watch the drift and decide when a full re-encode (decode_all + vidc_shards_encode_dev) is worth it.
+ *   caller watch the drift and decide when vidc_rebalance_sharded (below) is worth it.
  * The batch is that of the "append" section: pair i = (d_list_nos[i], d_ids[i]) with GLOBAL list numbers, M_l stable in i, a negative list
  *   number skipped and not counted, one >= nlist skipped and counted in *d_invalid.
  * The result.  Shard k of *out is what vidc_*_append_dev returns for shard k of `s` and the pairs routed to it -- word for word what
@@ -584,8 +604,9 @@ int vidc_sharded_loads(const vidc_shards *s, uint64_t *loads /* nshards entries:
  * the home device; n_rm < 2^32 - 1.
  * Immutable.  *out is a NEW sharded object over the same shard contexts and the same home; `s` stays valid and unchanged, and either may be
  *   destroyed first.
- * The map does not change.  Owner and local number of every list in *out are those of `s`: a remove never re-balances.
- *   vidc_sharded_loads of *out shows the drift; vidc_shards_offsets of *out is the surviving lists' offsets.
+ * The map does not change.  Owner and local number of every list in *out are those of `s`: a remove keeps the map as an append does.
+ *   vidc_sharded_loads of *out shows the drift (vidc_rebalance_sharded undoes it); vidc_shards_offsets of *out is the surviving lists'
+ *   offsets.
  * The batch is that of the "remove" section, with GLOBAL list numbers: a negative list number is skipped and not counted, one >= nlist is
  *   skipped and counted in *d_invalid, equality is over all 64 bits, every copy inside a list goes.
  * The result.  With U = the unsharded object of the same lists and (U', mask, missing, invalid) the single-object remove of the same batch
@@ -619,6 +640,35 @@ int vidc_sharded_loads(const vidc_shards *s, uint64_t *loads /* nshards entries:
 int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm, const int64_t *d_list_nos /* NULL: any-list mode */,
                             const uint64_t *d_ids, int param, uint32_t flags, vidc_shards **out, uint8_t *d_removed, uint64_t *d_missing,
                             uint64_t *d_invalid);
+/* Re-balance a sharded object: the lists of `s` under the map vidc_shards_encode_dev would choose for what `s` decodes to -- the
+ * longest-processing-time rule on vidc_shards_offsets(s).  Called on the home context.
+ * Immutable.  *out is a NEW sharded object over the same shard contexts and the same home; `s` stays valid and unchanged, and either may be
+ *   destroyed first.  One shard, or a map that does not change, returns an equal object.
+ * The result.  decode_all, decode_lists, translate_labels_dev and decode_gather answer on *out exactly as on `s` (ROC's sampling order
+ *   included); vidc_shards_offsets, ntotal and compressed_bytes are those of `s`; vidc_shards_map and vidc_sharded_loads are the new
+ *   map's.  flags are the codec's own perm flags and become those of *out: with the perm flag vidc_shards_perm of *out is the identity
+ *   inside every list (a permutation of a derived object is over the positions of what the old lists decode to).
+ *   *moved_ids (host, may be NULL) = the number of ids whose owner changed, host arithmetic on the two maps.
+ * Shards.  A shard that owns no list under the new map holds no object.  Packed bits (the object's width is kept), Elias-Fano: shard k of
+ *   *out is, word for word, what vidc_{packed,ef}_encode builds from the new map's cut of decode_all(s).  ROC: for every global list the
+ *   new owner's list equals the old owner's list in size, precision, head, nwords, mt_draws and every word.  For the lists the encoder
+ *   reproduces -- distinct ids, at most 65 536 of them, no power-of-two maximum under VIDC_PREC_REFERENCE -- that is also, word for word,
+ *   what vidc_roc_encode builds from the new cut with the object's param; any other list keeps its old stream, as an untouched list does
+ *   in an append.
+ * What runs where.  Packed bits and Elias-Fano are REBUILT: vidc_shards_decode_all into a block of the home cache, then the body of
+ *   vidc_shards_encode_dev on the object's own offsets; no id reaches the host.  ROC lists MOVE AS STREAMS: the host makes, per new shard,
+ *   one (old shard, old local number) row per local list; one host thread per new shard that owns lists calls vidc_roc_regroup on its
+ *   context with the old shard objects as sources -- no ANS chain runs, and a shard that already has its final content still gets a
+ *   regrouped object of its own.  An old shard on another device than its destination first regroups the lists bound there into a
+ *   temporary object on its own context; the destination copies that object's arrays into its own cache with
+ *   hipMemcpyAsync(hipMemcpyDefault) and regroups from the copy -- a path that CANNOT RUN ON A ONE-GPU MACHINE AND HAS NOT BEEN RUN.  The
+ *   call WAITS.
+ * Status.  NULL home / s / out, or a home that is not the object's: VIDC_ERR_INVALID before any device work.  A status from a shard is
+ *   returned, "shard i: " in front of its message.  On any error *out == NULL, every new shard object already built is destroyed, `s`
+ *   is untouched and every context stays usable.
+ * Residency.  No id payload crosses PCIe: vidc_ctx_d2h_bytes of no context moves (ROC reads back one 8-byte word total per regroup,
+ *   metadata, which that counter does not count). */
+int vidc_rebalance_sharded(vidc_ctx *home, const vidc_shards *s, uint32_t flags, vidc_shards **out, uint64_t *moved_ids /* host, may be NULL */);
 
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,
@@ -633,6 +683,7 @@ double vidc_ctx_last_kernel_ms(const vidc_ctx *ctx);
 #define VIDC_PHASE_IMPORT_H2D 5 /* vidc_wt_import / vidc_compact_import: the host -> device copies of the image.  The kernels that rebuild
                                  * and check are vidc_ctx_last_kernel_ms: for wt_type 1 the sum of the intervals in front of and behind the
                                  * read-back of the levels' width totals, without the wait between them */
+#define VIDC_PHASE_ROC_REGROUP_COPY 6 /* vidc_roc_regroup: the segmented word copy alone (0 for an object without words) */
 #define VIDC_PHASE_COUNT 8
 double vidc_ctx_phase_ms(const vidc_ctx *ctx, int phase);
 /* What the chain launch of the last ROC encode (which = 0) / decode (1) on this context processed: ids, lists, longest list and

@@ -72,6 +72,7 @@ def _declare(lib):
     f("vidc_roc_perm", C.c_int, _vp, _vp, _vp)
     f("vidc_roc_perm_dev", _vp, _vp)
     f("vidc_roc_import", C.c_int, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _P(_vp))
+    f("vidc_roc_regroup", C.c_int, _vp, C.c_int, _vp, _u64, _vp, _vp, _u32, _P(_vp))
     f("vidc_roc_decode_all", C.c_int, _vp, _vp, _vp)
     f("vidc_roc_decode_lists", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
     f("vidc_roc_decode_gather", C.c_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp)
@@ -172,6 +173,7 @@ def _declare(lib):
     f("vidc_sharded_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp)
     f("vidc_sharded_loads", C.c_int, _vp, _vp)
     f("vidc_remove_sharded_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp, _vp)
+    f("vidc_rebalance_sharded", C.c_int, _vp, _vp, _u32, _P(_vp), _vp)
 
 
 #: every symbol include/vidc.h declares (checked by the CPU test-suite against the built library)
@@ -202,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "vidc_shards_ntotal", "vidc_shards_compressed_bytes", "vidc_shards_map", "vidc_shards_offsets", "vidc_shards_shard",
     "vidc_shards_shard_ctx", "vidc_shards_decode_all", "vidc_shards_decode_lists", "vidc_shards_translate_labels_dev",
     "vidc_shards_decode_gather", "vidc_shards_perm", "vidc_sharded_append_dev", "vidc_sharded_loads", "vidc_remove_sharded_dev",
+    "vidc_roc_regroup", "vidc_rebalance_sharded",
 ]
 
 

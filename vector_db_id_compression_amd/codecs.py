@@ -428,6 +428,26 @@ class RocLists(_ListCodec):
         return int(lib().vidc_roc_last_decode_handed_back(self.h))
 
 
+def roc_regroup(sources, src_no, list_no, want_perm=False, ctx=None):
+    """A NEW RocLists made of whole lists of other objects, without encoding (vidc_roc_regroup): list j is list list_no[j] of
+    sources[src_no[j]], stream and metadata bit for bit.  sources: up to 8 RocLists on one device, None allowed where no src_no names
+    it; lists may repeat.  want_perm: the identity permutation in every list.  ctx: the context the new object is built through
+    (default: the first source's).  A function of the module, like removal.remove: the method set of the list classes is pinned
+    (tests/test_gpu_call_contract.py)."""
+    sources = list(sources)
+    if ctx is None:
+        ctx = next((s.ctx for s in sources if s is not None), None)
+        ctx = _lib.default_context() if ctx is None else ctx
+    sn = np.ascontiguousarray(src_no, dtype=np.uint32)
+    ln = np.ascontiguousarray(list_no, dtype=np.uint64)
+    assert sn.size == ln.size
+    arr = (C.c_void_p * max(len(sources), 1))(*[None if s is None else s.h for s in sources])
+    h = C.c_void_p()
+    check(lib().vidc_roc_regroup(ctx.h, len(sources), arr, sn.size, ptr(sn) if sn.size else None, ptr(ln) if ln.size else None,
+                                 _lib.VIDC_ROC_WANT_PERM if want_perm else 0, C.byref(h)))
+    return RocLists(h, ctx, None)
+
+
 class PackedLists(_ListCodec):
     """Fixed-width packed ids (vidc_packed): ceil(log2(ntotal+1)) bits per id, LSB-first."""
 

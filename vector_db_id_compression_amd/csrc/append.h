@@ -169,6 +169,28 @@ __global__ void __launch_bounds__(256) k_app_copy(const T *__restrict__ src, con
     }
 }
 
+// One chunk of a segmented copy, by one wavefront: d[0 .. nc) = s[0 .. nc), nc <= APP_COPY_UNIT.  16-byte accesses where the two runs
+// share their alignment mod 16, behind a head of less than 16 bytes and in front of a tail of less than 16; accesses of one element
+// otherwise.  k_app_copy's chunk body as a function, for the kernels that choose a segment's source differently (the ROC regroup's word
+// copy, roc.hip).  k_app_copy keeps its own text: moving it here re-allocates the registers of its 8-byte instantiation, and the code
+// objects of the append and the remove stay what they were, instruction for instruction.
+template <typename T>
+__device__ __forceinline__ void app_copy_chunk(const T *__restrict__ s, T *__restrict__ d, uint32_t nc, uint32_t lane) {
+    constexpr uint32_t VEC = 16u / sizeof(T);
+    if ((((uintptr_t)s ^ (uintptr_t)d) & 15u) == 0u) {
+        uint32_t head = (uint32_t)(((16u - ((uintptr_t)d & 15u)) & 15u) / sizeof(T));
+        head = head < nc ? head : nc;
+        if (lane < head) d[lane] = s[lane];
+        const uint32_t nv = (nc - head) / VEC;
+        const uint4 *sv = (const uint4 *)(s + head);
+        uint4 *dv = (uint4 *)(d + head);
+        for (uint32_t j = lane; j < nv; j += 64u) dv[j] = sv[j];
+        for (uint32_t j = head + nv * VEC + lane; j < nc; j += 64u) d[j] = s[j];
+    } else {
+        for (uint32_t j = lane; j < nc; j += 64u) d[j] = s[j];
+    }
+}
+
 // Labels of the containers that re-order a list (Elias-Fano: ascending, ROC: sampling order) from the permutation of the new
 // object: segment s holds the merged list seg_list[s] (NULL: list s) at perm + seg_off[s]; perm value j >= |old_l| is batch entry
 // j - |old_l| of that list, pair vals[add_off[l] + j - |old_l|] of the batch.  A wavefront per chunk; untouched lists are skipped.

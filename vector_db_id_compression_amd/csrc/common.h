@@ -221,6 +221,11 @@ int ef_remove(::vidc_ctx *ctx, const ::vidc_ef *e, uint64_t n_rm, const int64_t 
 int roc_remove(::vidc_ctx *ctx, const ::vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
                uint32_t flags, ::vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found);
 
+// A copy of an IVF ROC object in blocks of dst_ctx's cache, on dst_ctx's device (not part of the C-ABI: for vidc_rebalance_sharded, whose
+// vidc_roc_regroup wants every source on the destination's device).  The arrays travel through hipMemcpyAsync(hipMemcpyDefault) on
+// dst_ctx's stream; the call waits.  *out == NULL on an error.
+int roc_clone_to(::vidc_ctx *dst_ctx, const ::vidc_roc *r, ::vidc_roc **out);
+
 }  // namespace vidc
 
 // mt19937(1234) words available to the kernels for ANS stack underflow (codec.h:16-18,32-40).

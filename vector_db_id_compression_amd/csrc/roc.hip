@@ -1695,6 +1695,46 @@ __global__ void __launch_bounds__(256) k_rm_roc_sizes(const uint32_t *__restrict
         sizes[l] = (uint32_t)(lflag[l] ? small_off[ltpos[l] + 1] - small_off[ltpos[l]] : old_off[l + 1] - old_off[l]);
 }
 
+// ---- regroup (vidc_roc_regroup): list j of the new object is list list_no[j] of source src_no[j], stream and metadata unchanged.
+// A source: RocMeta plus where its words and its lists start.  Up to VIDC_SHARDS_MAX of them reach the kernels by value; the host
+// checked src_no[j] < nsrc, the source non-NULL and list_no[j] < its nlist before anything was uploaded.
+struct RocSrc : RocMeta {
+    const uint32_t *words;
+    const uint64_t *word_off, *offsets;
+};
+struct RocSrcs {
+    RocSrc s[VIDC_SHARDS_MAX];
+};
+// the five per-list arrays of the new object (sizes: what the scan turns into its offsets)
+__global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs srcs, const uint32_t *__restrict__ src_no, const uint64_t *__restrict__ list_no,
+                                                          uint64_t m, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
+                                                          uint32_t *__restrict__ nwords, uint32_t *__restrict__ draws, uint32_t *__restrict__ sizes) {
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (uint64_t)gridDim.x * blockDim.x) {
+        const RocSrc &s = srcs.s[src_no[j]];
+        const uint64_t k = list_no[j];
+        heads[j] = s.heads[k];
+        prec[j] = s.prec[k];
+        nwords[j] = s.nwords[k];
+        draws[j] = s.draws[k];
+        sizes[j] = (uint32_t)(s.offsets[k + 1] - s.offsets[k]);
+    }
+}
+// the words: k_app_copy<uint32_t, true> with the source of a list chosen among the sources' word arrays.  A wavefront per chunk of the
+// new lists' streams (items: app_chunks on dst_off).
+__global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs srcs, const uint32_t *__restrict__ src_no, const uint64_t *__restrict__ list_no,
+                                                          const uint64_t *__restrict__ dst_off, uint32_t *__restrict__ dst,
+                                                          const Chunk *__restrict__ items, const uint64_t *__restrict__ n_items) {
+    const uint64_t total = *n_items;
+    const uint32_t lane = lane_id();
+    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < total; c += (uint64_t)gridDim.x * 4u) {
+        const Chunk ch = items[c];
+        const uint64_t base = dst_off[ch.list], n = dst_off[ch.list + 1] - base;
+        const uint32_t nc = (uint32_t)(n - ch.start < APP_COPY_UNIT ? n - ch.start : APP_COPY_UNIT);
+        const RocSrc &s = srcs.s[src_no[ch.list]];
+        app_copy_chunk(s.words + s.word_off[list_no[ch.list]] + ch.start, dst + base + ch.start, nc, lane);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2467,11 +2507,187 @@ int roc_remove(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d
     *out = nr.release();
     return VIDC_OK;
 }
+
+// A copy of an IVF object on another context (common.h): the device arrays through hipMemcpyAsync(hipMemcpyDefault) on dst's stream,
+// into blocks of dst's cache; the host offsets with them, no planner hints.  Waits.  Its only caller is the sharded re-balance, for a
+// source shard on another device than its destination: NEVER EXECUTED, every test machine has one GPU.
+int roc_clone_to(vidc_ctx *dst, const vidc_roc *r, vidc_roc **out) {
+    if (out) *out = nullptr;
+    if (!dst || !r || !out) { set_error("roc clone: NULL context, object or out"); return VIDC_ERR_INVALID; }
+    if (r->rows) { set_error("roc clone: graph objects are not cloned"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_TRY(ensure_offsets(r));
+    VIDC_HIP(hipSetDevice(dst->device));
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = dst->device;
+    nr->nlist = r->nlist;
+    nr->ntotal = r->ntotal;
+    nr->total_words = r->total_words;
+    nr->compressed_bytes = r->compressed_bytes;
+    nr->offsets = r->offsets;
+    nr->offsets_host = true;
+    StreamGuard guard(dst);
+    auto copy = [&](auto &to, const auto &from, size_t count, size_t alloc_count) -> int {
+        VIDC_TRY(to.alloc(alloc_count, dst->dpool));
+        if (count) VIDC_HIP(hipMemcpyAsync(to.p, from.p, count * sizeof(*to.p), hipMemcpyDefault, dst->stream));
+        return VIDC_OK;
+    };
+    const size_t nl = r->nlist;
+    VIDC_TRY(copy(nr->d_offsets, r->d_offsets, nl + 1, nl + 1));
+    VIDC_TRY(copy(nr->d_word_off, r->d_word_off, nl + 1, nl + 1));
+    VIDC_TRY(copy(nr->d_heads, r->d_heads, nl, nl));
+    VIDC_TRY(copy(nr->d_prec, r->d_prec, nl, nl));
+    VIDC_TRY(copy(nr->d_nwords, r->d_nwords, nl, nl));
+    VIDC_TRY(copy(nr->d_draws, r->d_draws, nl, nl));
+    VIDC_TRY(copy(nr->d_words, r->d_words, r->total_words, r->total_words + 16));  // + padding: see finish_complete
+    if (r->d_perm.p) VIDC_TRY(copy(nr->d_perm, r->d_perm, r->ntotal, r->ntotal ? r->ntotal : 1));
+    VIDC_HIP(vidc::vidc_stream_wait(dst->stream));
+    guard.disarm();
+    *out = nr.release();
+    return VIDC_OK;
+}
 }  // namespace vidc
 }
 int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
                         uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return roc_remove(ctx, r, n_rm, d_list_nos, d_ids, precision_mode, flags, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+// Regroup (include/vidc.h): the splice of the append and the remove as a call of its own, over up to VIDC_SHARDS_MAX sources instead
+// of two.  The (source, list) table is checked on the host and uploaded (12 bytes per list); one kernel gathers the per-list metadata
+// and the sizes, one scan launch set turns sizes and word counts into the two offset arrays, the word total comes back (8 bytes), and
+// a wavefront per 1024-word chunk copies the streams.  No ANS step runs; like an imported object the result carries no planner hints.
+int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint64_t m, const uint32_t *src_no, const uint64_t *list_no,
+                     uint32_t flags, vidc_roc **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !srcs || !out || (m && (!src_no || !list_no))) {
+        set_error("roc regroup: NULL context, sources, out or table");
+        return VIDC_ERR_INVALID;
+    }
+    if (nsrc < 1 || nsrc > VIDC_SHARDS_MAX) {
+        set_error("roc regroup: nsrc %d outside 1 .. %d", nsrc, VIDC_SHARDS_MAX);
+        return VIDC_ERR_INVALID;
+    }
+    if (m >= 0xffffffffull) { set_error("roc regroup: too many lists"); return VIDC_ERR_INVALID; }
+    bool used[VIDC_SHARDS_MAX] = {};
+    for (uint64_t j = 0; j < m; j++) {
+        if (src_no[j] >= (uint32_t)nsrc) {
+            set_error("roc regroup: list %llu names source %u of %d", (unsigned long long)j, src_no[j], nsrc);
+            return VIDC_ERR_INVALID;
+        }
+        if (!srcs[src_no[j]]) {
+            set_error("roc regroup: list %llu names source %u, which is NULL", (unsigned long long)j, src_no[j]);
+            return VIDC_ERR_INVALID;
+        }
+        used[src_no[j]] = true;
+    }
+    // (from here on the sources are looked into)
+    for (int k = 0; k < nsrc; k++)
+        if (srcs[k] && srcs[k]->device != ctx->device) {
+            set_error("roc regroup: source %d lives on device %d, the context on device %d", k, srcs[k]->device, ctx->device);
+            return VIDC_ERR_INVALID;
+        }
+    for (uint64_t j = 0; j < m; j++)
+        if (list_no[j] >= srcs[src_no[j]]->nlist) {
+            set_error("roc regroup: list %llu names list %llu of source %u, which holds %llu", (unsigned long long)j,
+                      (unsigned long long)list_no[j], src_no[j], (unsigned long long)srcs[src_no[j]]->nlist);
+            return VIDC_ERR_INVALID;
+        }
+    for (int k = 0; k < nsrc; k++)
+        if (srcs[k] && srcs[k]->rows) { set_error("roc regroup: source %d is a graph object", k); return VIDC_ERR_UNSUPPORTED; }
+    for (int k = 0; k < nsrc; k++)
+        if (used[k]) VIDC_TRY(ensure_offsets(srcs[k]));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc regroup");
+    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = ctx->device;
+    nr->nlist = m;
+    nr->offsets = vec_pool<uint64_t>().take(m + 1);
+    nr->offsets.assign(m + 1, 0);
+    uint64_t nonempty = 0;
+    for (uint64_t j = 0; j < m; j++) {
+        const std::vector<uint64_t> &so = srcs[src_no[j]]->offsets;
+        const uint64_t n = so[list_no[j] + 1] - so[list_no[j]];
+        nr->offsets[j + 1] = nr->offsets[j] + n;
+        nonempty += n != 0;
+    }
+    nr->ntotal = nr->offsets[m];
+    nr->offsets_host = true;
+    Scratch s_tab, s_sizes, s_slot, s_t0;
+    Pinned h_tab;
+    AppChunks ch_w, ch_p;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
+    VIDC_TRY(h_tab.get(ctx, 16 + m * 12));
+    VIDC_TRY(s_tab.get(ctx, 16 + m * 12));
+    VIDC_TRY(s_sizes.get(ctx, (m + 1) * 4));
+    uint64_t *h_cnt = h_tab.as<uint64_t>();  // word total | list_no[m] | src_no[m]
+    h_cnt[0] = 0;
+    const uint64_t *d_list_no = s_tab.as<uint64_t>() + 2;
+    const uint32_t *d_src_no = (const uint32_t *)(d_list_no + m);
+    if (m) {
+        std::memcpy(h_cnt + 2, list_no, m * 8);
+        std::memcpy(h_cnt + 2 + m, src_no, m * 4);
+        VIDC_HIP(hipMemcpyAsync(s_tab.as<uint64_t>() + 2, h_cnt + 2, m * 12, hipMemcpyHostToDevice, ctx->stream));
+    }
+    VIDC_TRY(nr->d_offsets.alloc(m + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(m, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(m, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(m, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(m, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(m + 1, ctx->dpool));
+    RocSrcs S{};
+    for (int k = 0; k < nsrc; k++)
+        if (used[k]) {
+            const vidc_roc *r = srcs[k];
+            S.s[k] = RocSrc{{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p}, r->d_words.p, r->d_word_off.p, r->d_offsets.p};
+        }
+    EventTimer tm = EventTimer::started(ctx);
+    if (m) {
+        hipLaunchKernelGGL(k_roc_regroup_meta, req_grid(ctx, m), dim3(256), 0, ctx->stream, S, d_src_no, d_list_no, m, nr->d_heads.p, nr->d_prec.p,
+                           nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+        Scan4 sc{};
+        sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)m, s_t0));
+        VIDC_HIP(hipMemcpyAsync(h_cnt, nr->d_word_off.p + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_cnt[0];
+    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
+    tr.mark("metadata gathered, word total read back");
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    VidcPhaseTimer copy_timer(ctx);  // (the word copy alone: VIDC_PHASE_ROC_REGROUP_COPY)
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, m, nr->total_words, ch_w));
+        copy_timer.begin();
+        hipLaunchKernelGGL(k_roc_regroup_copy, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S, d_src_no, d_list_no,
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
+        copy_timer.end();
+        VIDC_HIP(hipGetLastError());
+    }
+    if (want_perm) {
+        // the convention of the append and the remove: a permutation of a derived object is over the positions of what the old
+        // lists decode to -- the identity (k_app_roc_perm with every list's slot 0)
+        VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
+        if (nr->ntotal) {
+            VIDC_TRY(s_slot.get(ctx, m * 4));
+            VIDC_HIP(hipMemsetAsync(s_slot.p, 0, m * 4, ctx->stream));
+            VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, m, nr->ntotal, ch_p));
+            hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
+                               (const uint32_t *)s_slot.as<uint32_t>(), (const uint32_t *)nullptr, (const uint64_t *)nullptr, ch_p.items,
+                               ch_p.n_items, nr->d_perm.p);
+            VIDC_HIP(hipGetLastError());
+        }
+    }
+    const double kernel_ms = tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    guard.disarm();
+    ctx->last_kernel_ms = kernel_ms;
+    ctx->phase_ms[VIDC_PHASE_ROC_REGROUP_COPY] = copy_timer.collect();
+    tr.mark("streams copied");
+    *out = nr.release();
+    return VIDC_OK;
 }
 
 int vidc_roc_decode_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, uint32_t K, int32_t *d_out,

@@ -92,6 +92,33 @@ inline ShardPlan make_plan(const uint64_t *offsets, uint64_t nlist, int nshards)
     return make_plan_for_owner(offsets, nlist, nshards, lpt_partition(sizes, nshards));
 }
 
+// vidc_rebalance_sharded: the lists of one object under two maps.  Per NEW shard one row per local list, in local order: the list is
+// local list list_no[j] of OLD shard src_no[j] -- the table vidc_roc_regroup takes, with the old shard objects as its sources.
+struct RegroupRows {
+    std::vector<uint32_t> src_no;
+    std::vector<uint64_t> list_no;
+};
+// old_p, new_p: plans of the same offsets over the same number of shards (the caller made new_p from old_p.offsets)
+inline std::vector<RegroupRows> regroup_plan(const ShardPlan &old_p, const ShardPlan &new_p) {
+    std::vector<RegroupRows> rows((size_t)new_p.nshards);
+    for (size_t d = 0; d < rows.size(); d++) {
+        rows[d].src_no.reserve(new_p.lists[d].size());
+        rows[d].list_no.reserve(new_p.lists[d].size());
+        for (uint64_t l : new_p.lists[d]) {
+            rows[d].src_no.push_back((uint32_t)old_p.owner[l]);
+            rows[d].list_no.push_back(old_p.local_no[l]);
+        }
+    }
+    return rows;
+}
+// the ids whose owner changes between the two maps
+inline uint64_t moved_ids(const ShardPlan &old_p, const ShardPlan &new_p) {
+    uint64_t moved = 0;
+    for (uint64_t l = 0; l < old_p.nlist; l++)
+        if (old_p.owner[l] != new_p.owner[l]) moved += old_p.size_of(l);
+    return moved;
+}
+
 // the chunk table of a segment table: every segment cut into pieces of SHARD_COPY_UNIT elements (lists are Zipf: one wavefront per
 // list would leave a 52 k-id list to one wavefront next to hundreds that copy one id)
 inline std::vector<CopyChunk> build_copy_chunks(const std::vector<Segment> &segs) {

@@ -5,7 +5,8 @@
 // k_shard_route<LABELS> (labels of translate_labels, pairs of append and remove) and the three joins (translate's ids, the append's
 // labels, the remove's found bytes -> the missing count).  Append and remove are one skeleton (update_impl); the byte offsets of their
 // scratch blocks come from shardplan::update_blocks; a shard on another device is served through one helper (FarStage, and DecodedIds
-// for the decodes; the encoder's cut keeps its own copy), a path that has never executed.
+// for the decodes; the encoder's cut keeps its own copy), a path that has never executed.  The re-balance (vidc_rebalance_sharded) adds no
+// kernel here: packed bits and Elias-Fano go through decode_all and encode_impl, ROC through vidc_roc_regroup per new shard (roc.hip).
 #include <thread>
 
 #include "common.h"
@@ -980,6 +981,142 @@ int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm,
             return VIDC_OK;
         },
         out);
+}
+
+}  // extern "C"
+
+namespace {
+
+struct RocDelete {
+    void operator()(vidc_roc *r) const { vidc_roc_destroy(r); }
+};
+using RocPtr = std::unique_ptr<vidc_roc, RocDelete>;
+
+// The ROC re-balance: every list's stream moves to its new owner unchanged.  One host thread per new shard that owns lists runs
+// vidc_roc_regroup on its context with the old shard objects as sources.  An old shard on another device than the destination is not
+// a source as it is: it first regroups the lists bound for that destination into a temporary object on its own context (one host
+// thread per such old shard, before the destinations start: a context serves one call at a time), the destination clones the
+// temporary object into its own cache (roc_clone_to) and names the clone's lists 0, 1, ... in its table.  That branch has never
+// executed: every test machine has one GPU.
+int rebalance_roc(vidc_ctx *home, const vidc_shards *s, uint32_t flags, vidc_shards **out) {
+    HostTrace tr("sharded rebalance (roc)");
+    const ShardPlan &P = s->plan;
+    const int ns = P.nshards;
+    std::unique_ptr<vidc_shards> N(new vidc_shards());
+    N->kind = s->kind;
+    N->flags = flags;
+    N->home = home;
+    N->ctxs = s->ctxs;
+    N->objs.assign((size_t)ns, nullptr);
+    N->param = s->param;
+    N->plan = make_plan(P.offsets.data(), P.nlist, ns);
+    const ShardPlan &NP = N->plan;
+    std::vector<RegroupRows> rows = regroup_plan(P, NP);
+    VIDC_TRY(create_events(N.get()));
+    std::vector<int> involved, far_sources;
+    for (int d = 0; d < ns; d++)
+        if (!NP.lists[(size_t)d].empty()) involved.push_back(d);
+    auto near = [&](int k, int d) { return s->ctxs[(size_t)k]->device == s->ctxs[(size_t)d]->device; };
+    // far[k][d]: old shard k's lists bound for new shard d, in d's local order (empty: none, or the two share a device)
+    std::vector<std::vector<std::vector<uint64_t>>> far((size_t)ns, std::vector<std::vector<uint64_t>>((size_t)ns));
+    std::vector<std::vector<RocPtr>> temp((size_t)ns);
+    for (int k = 0; k < ns; k++) temp[(size_t)k].resize((size_t)ns);
+    for (int d : involved) {
+        RegroupRows &R = rows[(size_t)d];
+        for (size_t j = 0; j < R.src_no.size(); j++) {
+            const int k = (int)R.src_no[j];
+            if (near(k, d)) continue;
+            std::vector<uint64_t> &f = far[(size_t)k][(size_t)d];
+            f.push_back(R.list_no[j]);
+            R.list_no[j] = f.size() - 1;  // (its number in the temporary object)
+        }
+    }
+    for (int k = 0; k < ns; k++)
+        for (int d = 0; d < ns; d++)
+            if (!far[(size_t)k][(size_t)d].empty() && (far_sources.empty() || far_sources.back() != k)) far_sources.push_back(k);
+    ShardStreamsGuard sguard(s);
+    if (!far_sources.empty()) {
+        sguard.which = far_sources;
+        VIDC_TRY(fan_out(far_sources, [&](int k) -> int {
+            const size_t i = (size_t)k;
+            vidc_ctx *c = s->ctxs[i];
+            VIDC_HIP(hipSetDevice(c->device));
+            const vidc_roc *src = (const vidc_roc *)s->objs[i];
+            for (int d = 0; d < ns; d++) {
+                const std::vector<uint64_t> &f = far[i][(size_t)d];
+                if (f.empty()) continue;
+                const std::vector<uint32_t> zeros(f.size(), 0u);
+                vidc_roc *t = nullptr;
+                VIDC_TRY(vidc_roc_regroup(c, 1, &src, f.size(), zeros.data(), f.data(), 0u, &t));
+                temp[i][(size_t)d].reset(t);
+            }
+            return VIDC_OK;
+        }));
+        tr.mark("far sources regrouped");
+    }
+    sguard.which = involved;
+    vidc_shards *Np = N.get();
+    const int st = involved.empty() ? VIDC_OK : fan_out(involved, [&](int d) -> int {
+        const size_t i = (size_t)d;
+        vidc_ctx *c = Np->ctxs[i];
+        VIDC_HIP(hipSetDevice(c->device));
+        const vidc_roc *srcs[VIDC_SHARDS_MAX] = {};
+        RocPtr clones[VIDC_SHARDS_MAX];
+        for (int k = 0; k < ns; k++) {
+            if (near(k, d)) {
+                srcs[k] = (const vidc_roc *)s->objs[(size_t)k];  // (NULL for a shard without lists: no row names it)
+            } else if (temp[(size_t)k][i]) {
+                vidc_roc *cl = nullptr;
+                VIDC_TRY(roc_clone_to(c, temp[(size_t)k][i].get(), &cl));
+                clones[k].reset(cl);
+                srcs[k] = cl;
+            }
+        }
+        const RegroupRows &R = rows[i];
+        return vidc_roc_regroup(c, ns, srcs, R.src_no.size(), R.src_no.data(), R.list_no.data(), flags & VIDC_ROC_WANT_PERM,
+                                (vidc_roc **)&Np->objs[i]);
+    });
+    tr.mark("shards regrouped");
+    // (the guard waits for the shard streams -- a failing shard's siblings have finished -- and goes back to the home device)
+    if (st != VIDC_OK) return st;  // ~vidc_shards destroys what was built
+    VIDC_HIP(hipSetDevice(home->device));
+    PlanTables tables;
+    StreamGuard hguard(home);
+    VIDC_TRY(upload_plan(N.get(), tables));
+    VIDC_HIP(vidc_stream_wait(home->stream));
+    hguard.disarm();
+    // no kernel runs on the home stream; a home context that is also a shard context keeps its regroup's time
+    if (std::find(s->ctxs.begin(), s->ctxs.end(), home) == s->ctxs.end()) home->last_kernel_ms = 0;
+    *out = N.release();
+    return VIDC_OK;
+}
+
+// Packed bits and Elias-Fano: decode_all into a block of the home cache, then the encoder's body on the object's own offsets -- the new
+// map is the one make_plan chooses there, and a shard is what the single-object encoder builds from its cut.
+int rebalance_rebuild(vidc_ctx *home, const vidc_shards *s, uint32_t flags, vidc_shards **out) {
+    const ShardPlan &P = s->plan;
+    VIDC_HIP(hipSetDevice(home->device));
+    Scratch ids;
+    VIDC_TRY(ids.get(home, (P.ntotal ? P.ntotal : 2) * 8));
+    VIDC_TRY(vidc_shards_decode_all(home, s, ids.as<uint64_t>()));  // (waits)
+    return encode_impl(home, P.nshards, s->ctxs.data(), s->kind, s->param, flags, P.nlist, P.offsets.data(), ids.as<uint64_t>(), out);
+}
+
+}  // namespace
+
+extern "C" {
+
+// Re-balance (include/vidc.h): the new map is make_plan's on the object's own offsets; moved_ids is host arithmetic on the two maps.
+int vidc_rebalance_sharded(vidc_ctx *home, const vidc_shards *s, uint32_t flags, vidc_shards **out, uint64_t *moved_ids) {
+    if (out) *out = nullptr;
+    if (!home || !s || !out) {
+        set_error("sharded rebalance: NULL context, object or out");
+        return VIDC_ERR_INVALID;
+    }
+    VIDC_TRY(check_request(home, s, "sharded rebalance"));
+    VIDC_TRY(s->kind == VIDC_KIND_ROC ? rebalance_roc(home, s, flags, out) : rebalance_rebuild(home, s, flags, out));
+    if (moved_ids) *moved_ids = shardplan::moved_ids(s->plan, (*out)->plan);
+    return VIDC_OK;
 }
 
 int vidc_shards_perm(vidc_ctx *home, const vidc_shards *s, uint32_t *perm_host) {

@@ -13,7 +13,8 @@ arithmetic and the gathered lists land in request order with one indexed copy pe
 `ShardedInvLists` is the multi-process form (one process per GPU, torch.distributed).  `DeviceShards` is the single-process form
 over the C-ABI's vidc_shards: one process drives every context, the cut / placement / label routing are HIP kernels, and no index
 arithmetic happens in Python.  `DeviceShards.append` adds a batch of (list number, id) pairs without re-encoding the index: the map
-stays, `DeviceShards.loads` shows how the balance drifts; `DeviceShards.remove` takes a batch out the same way.  It has been exercised with several contexts on one device; never run on
+stays, `DeviceShards.loads` shows how the balance drifts; `DeviceShards.remove` takes a batch out the same way, and
+`DeviceShards.rebalance` moves the lists to the map a fresh encode would choose (ROC lists as streams, without encoding).  It has been exercised with several contexts on one device; never run on
 more than one GPU.
 """
 import heapq
@@ -339,7 +340,7 @@ class DeviceShards:
     @property
     def loads(self):
         """uint64[nshards]: ids per shard (the sum of its lists' sizes).  Appends keep the map, so the balance drifts: compare with
-        ntotal / nshards to decide when a full re-encode is worth it."""
+        ntotal / nshards to decide when `rebalance` is worth it."""
         from ._lib import check, lib, ptr
 
         loads = np.zeros(self.nshards, np.uint64)
@@ -386,6 +387,28 @@ class DeviceShards:
             raise TypeError(f"unknown codec arguments: {sorted(codec_args)}")
         h, mask = removal._call(_lib.lib().vidc_remove_sharded_dev, self, (param, flags), list_nos, ids, removed, missing, invalid)
         return type(self)(h, self.ctx, self.ctxs, self.kind), mask  # (the offsets are fetched from the new object on first use)
+
+    def rebalance(self, want_perm=False):
+        """The lists of this object under the map `encode` would choose for what it decodes to -> (NEW DeviceShards over the same
+        contexts, moved_ids); this object stays valid and unchanged (vidc_rebalance_sharded).  Every request answers on the new object
+        as on this one; `owner`, `local_no` and `loads` are the new map's; moved_ids counts the ids whose owner changed.  Packed bits
+        and Elias-Fano are rebuilt from decode_all on the device; ROC lists move as streams, no list is encoded again.  want_perm
+        (ef, roc): the new object's permutation, the identity inside every list.  The call waits."""
+        import ctypes as C
+
+        from . import _lib, codecs
+
+        flags = 0
+        if want_perm:
+            if self.kind == 0:
+                raise TypeError("packed lists keep no permutation")
+            flags = _lib.VIDC_EF_WANT_PERM if self.kind == 1 else _lib.VIDC_ROC_WANT_PERM
+        h, moved = C.c_void_p(), C.c_uint64(0)
+        codecs._on_torch_stream(self.ctx)
+        _lib.check(_lib.lib().vidc_rebalance_sharded(self.ctx.h, self.h, flags, C.byref(h), C.byref(moved)))
+        new = type(self)(h, self.ctx, self.ctxs, self.kind)
+        new._offsets = self._offsets
+        return new, int(moved.value)
 
     def perm(self):
         from ._lib import check, lib, ptr
