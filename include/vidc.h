@@ -486,6 +486,51 @@ int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int
 int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int precision_mode, uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
 
+/* ---------------------------------------------------- update rows (graph objects, device-resident) */
+/* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
+ * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its
+ * memory; the old one stays valid and unchanged, and either may be destroyed first.
+ *
+ * The batch.  d_nodes: device int64[m]; d_rows: device int32[m * K], K the object's K, rows -1 terminated; m < 2^32 - 1.  The updated
+ *   matrix R' has N_new >= N_old rows of K entries: row v is batch row i for the LARGEST i with d_nodes[i] == v (the last mention wins:
+ *   the result is the same on every run); otherwise old row v (what the object's decode_rows returns) for v < N_old; otherwise the
+ *   empty row (-1 in column 0).  A negative node is skipped and not counted; a node >= N_new is skipped and counted in *d_invalid (a
+ *   device uint64 the caller zeroes; may be NULL).  Arrays are read in order on the context's stream.
+ * The result is the object vidc_compact_rows_encode / vidc_ef_encode_rows / vidc_roc_encode_rows(precision_mode) builds from
+ *   (N_new, K, R'), in everything that can be exported or decoded -- compact: bits, stride, size_in_bytes and every byte of export_all
+ *   (the sentinel is N_new in EVERY row, and the fields re-pack when the width steps); Elias-Fano: list_info, stream_words,
+ *   compressed_bytes, every word of export_all, and the arena geometry of a fresh object, sized for max(N_new - 1, the largest id of R');
+ *   ROC: list_info (sizes, precisions, heads, nwords, draws), total_words, compressed_bytes, every word of export_all_words.  A ROC
+ *   stream depends only on the row's multiset and precision, so an untouched row keeps its stream bit for bit (the caller passes the
+ *   precision_mode the object was built with; the call cannot check it).
+ * Status.  NULL context, object or out, a NULL array with m > 0, m >= 2^32 - 1, N_new < N_old, N_new >= 2^32 - 1, a bad precision_mode:
+ *   VIDC_ERR_INVALID before any device work.  An IVF object (not built by *_encode_rows): VIDC_ERR_UNSUPPORTED.  A wide Elias-Fano or
+ *   ROC object (K > 64: these are CSR objects that only carry their K): VIDC_ERR_UNSUPPORTED -- out of scope here; compact rows take
+ *   every K their encoder takes (1 .. 4096).  Ids in batch rows follow the encoders: compact, an id outside [0, N_new); Elias-Fano, a
+ *   negative id before the terminator; ROC, an id >= 2^31 (a negative int32): VIDC_ERR_DOMAIN.  Compact and Elias-Fano judge the batch
+ *   rows that reach R' (a skipped row, or one that loses to a later mention, is not read for content); ROC encodes and therefore judges
+ *   every batch row.  On any error *out == NULL, the old object is untouched and the context stays usable.  m == 0 with N_new == N_old
+ *   returns an object equal to the old one.
+ * What runs.  The slot table (slot[v] = 1 + the largest batch index naming v, one atomicMax per batch entry over a zeroed
+ *   uint32[N_new]; the invalid nodes are counted in the same pass), then
+ *   compact: ONE re-pack kernel writes every row -- the batch row packed from int32, or the old record's fields re-emitted at the new
+ *     width with the sentinel replaced, or the sentinel alone; a 4-byte domain flag comes back;
+ *   Elias-Fano: a pass over the rows of R' finds its largest id and checks its domain (8 bytes come back and fix the geometry); the tile
+ *     encoder codes the m batch rows into a scratch arena at that geometry; one kernel writes the new arena record by record from
+ *     {scratch, old arena, zero}, re-striding old records when (low words, high words) changed; one writes the per-row meta and sums
+ *     the totals (1 KiB comes back);
+ *   ROC: the m batch rows are encoded by the rows path into a temporary object, and the splice of vidc_roc_regroup runs over {old,
+ *     temporary} with the slot table in the place of its host table: metadata gather, one scan launch set, the totals (24 bytes come
+ *     back), the chunked 16-byte word copy.  The result carries no planner hints, like an imported object.
+ *   No row payload crosses PCIe (vidc_ctx_d2h_bytes does not move), no kernel waits for another workgroup, and every position comes
+ *   from a scan or a multiplication.  The calls synchronise; vidc_ctx_last_kernel_ms covers their launches. */
+int vidc_compact_update_rows_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows,
+                                 uint64_t N_new, vidc_compact **out, uint64_t *d_invalid);
+int vidc_ef_update_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows, uint64_t N_new,
+                            vidc_ef **out, uint64_t *d_invalid);
+int vidc_roc_update_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows, uint64_t N_new,
+                             int precision_mode, vidc_roc **out, uint64_t *d_invalid);
+
 /* ---------------------------------------------- sharded lists (several contexts, one process) */
 /* One CSR set of lists cut into shards, one codec object per shard, each built and served through its own context: the container of a
  * process that drives all of its GPUs itself (a Faiss process and its OpenMP loops, custom_invlists_impl.cpp:147,508-525), where

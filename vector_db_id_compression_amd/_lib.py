@@ -152,6 +152,10 @@ def _declare(lib):
     f("vidc_packed_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp, _vp)
     f("vidc_ef_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp, _vp)
     f("vidc_roc_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp, _vp)
+    # update rows (graph objects, device-resident)
+    f("vidc_compact_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
+    f("vidc_ef_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
+    f("vidc_roc_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, C.c_int, _P(_vp), _vp)
     # sharded lists (several contexts, one process)
     f("vidc_shards_encode", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _u32, _u64, _vp, _vp, _P(_vp))
     f("vidc_shards_encode_dev", C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _u32, _u64, _vp, _u64, _vp, _P(_vp))
@@ -205,6 +209,7 @@ EXPORTED_SYMBOLS = [
     "vidc_shards_shard_ctx", "vidc_shards_decode_all", "vidc_shards_decode_lists", "vidc_shards_translate_labels_dev",
     "vidc_shards_decode_gather", "vidc_shards_perm", "vidc_sharded_append_dev", "vidc_sharded_loads", "vidc_remove_sharded_dev",
     "vidc_roc_regroup", "vidc_rebalance_sharded",
+    "vidc_compact_update_rows_dev", "vidc_ef_update_rows_dev", "vidc_roc_update_rows_dev",
 ]
 
 

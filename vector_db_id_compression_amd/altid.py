@@ -6,7 +6,7 @@ Each class is built from the final NSG graph (an int32 [N, K] array, -1 padded) 
 """
 import numpy as np
 
-from .codecs import CompactRows, EfLists, RocLists
+from .codecs import CompactRows, EfLists, RocLists, update_rows
 
 
 def _graph_rows(graph):
@@ -41,6 +41,18 @@ class _GraphBase:
             return self._c.decode_rows(nodes, self.K, want_counts=False)[0]
         return self._c.decode_rows(np.asarray(nodes, dtype=np.uint64), self.K, want_counts=False)[0]
 
+    def update_rows(self, nodes, rows, n_new=None):
+        """What an insert does to the adjacency: batch row i replaces the row of nodes[i] (the last mention of a node wins, a negative
+        node is skipped), and the graph grows to n_new nodes (None: as many as now; new nodes without a batch row have no edges) -> a
+        NEW graph object of the same class; this one stays valid.  nodes: [m] integers, rows: [m, K] int32, -1 terminated; numpy arrays
+        or CUDA tensors.  Nothing is re-encoded but the batch rows (codecs.update_rows)."""
+        g = object.__new__(type(self))
+        g._c = update_rows(self._c, nodes, rows, n_new=n_new)
+        g.N, g.K = int(self.N if n_new is None else n_new), self.K
+        g.data, g._rows = None, None
+        g._derive()
+        return g
+
 
 class CompactBitNSGGraph(_GraphBase):
     """altid_impl.cpp:20-51: ceil(log2(N+1)) bits per edge, fixed stride, sentinel N."""
@@ -48,10 +60,13 @@ class CompactBitNSGGraph(_GraphBase):
     def __init__(self, graph):
         super().__init__(graph)
         self._c = CompactRows.encode_rows(self._rows)
+        self._derive()
+        self._rows = None
+
+    def _derive(self):
         self.bits = self._c.bits
         self.stride = self._c.stride
         self.compressed_ids_size_in_bytes = self._c.size_in_bytes  # compressed_data.size() = N * stride
-        self._rows = None
 
 
 class EliasFanoNSGGraph(_GraphBase):
@@ -60,12 +75,15 @@ class EliasFanoNSGGraph(_GraphBase):
     def __init__(self, graph):
         super().__init__(graph)
         self._c = EfLists.encode_rows(self._rows)
+        self._derive()
+        self._rows = None
+
+    def _derive(self):
         self.compressed_ids_size_in_bytes = self._c.compressed_bytes  # :86,88
         # :55-57: size of each friend list + its max id, ceil(log2 N) bits each
         # (a size_t incremented twice by a double: the value truncates after EACH addition)
         x = self.N * np.ceil(np.log2(self.N)) / 8.0 if self.N > 1 else 0.0
         self.overhead_in_bytes = int(int(x) + x)
-        self._rows = None
 
 
 class ROCNSGGraph(_GraphBase):
@@ -74,13 +92,16 @@ class ROCNSGGraph(_GraphBase):
     def __init__(self, graph):
         super().__init__(graph)
         self._c = RocLists.encode_rows(self._rows)
+        self._derive()
+        self._rows = None
+
+    def _derive(self):
         info = self._c.info()
         self.id_symbol_precision = info["precision"].astype(np.uint64)
         self.num_outgoing_edges = info["sizes"].astype(np.uint32)  # altid_impl.h:61
         # :148 adds ans_states[list_no].size() for EVERY node (8 bytes even for an empty state)
         self.compressed_ids_size_in_bytes = int(8 * self.N + 4 * int(info["nwords"].sum()))
         self.overhead_in_bytes = int(self.N * np.ceil(np.log2(self.N)) / 8.0) if self.N > 1 else 0  # :105
-        self._rows = None
 
 
 AVAILABLE_COMPRESSED_GRAPHS = {  # graph_dynamic_bench_invlists.py:21-26

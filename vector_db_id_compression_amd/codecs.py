@@ -160,6 +160,38 @@ def _append(fn, obj, list_nos, ids, extra, labels, invalid):
     return h, (None if lab is None else lab[:n])
 
 
+def _update_rows(fn, obj, K, n_old, nodes, rows, n_new, extra, invalid):
+    """vidc_*_update_rows_dev: rows of a graph object replaced, and nodes added -> (handle of the NEW object, its node count).  nodes:
+    integer CUDA tensor [m] (negative = skipped; the LAST mention of a node wins), rows: int32 CUDA tensor [m, K], -1 terminated; numpy
+    arrays are uploaded.  n_new: node count of the new object (None: the old one); new nodes without a batch row are empty.  invalid
+    (optional): 1-element int64 CUDA tensor the number of nodes >= n_new is added to.  Runs on torch's current stream; the call
+    synchronises."""
+    torch = _torch()
+    if not torch.cuda.is_available():
+        raise _lib.VidcError("no HIP device: update_rows needs an MI355X (there is no CPU fallback)")
+    if isinstance(nodes, (np.ndarray, list, tuple)):
+        nodes = torch.from_numpy(np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)).cuda()
+    if isinstance(rows, np.ndarray):
+        rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).cuda()
+    if not _is_cuda(nodes) or nodes.dtype.is_floating_point or nodes.dtype == torch.bool:
+        raise TypeError("nodes must be an integer CUDA tensor")
+    if not _is_cuda(rows) or rows.dtype != torch.int32:
+        raise TypeError("rows must be an int32 CUDA tensor")
+    nd = _dev_array(nodes.reshape(-1).long(), obj.ctx, "nodes")
+    m = nd.numel()
+    if rows.numel() != m * K or (m and rows.dim() == 2 and rows.shape[1] != K):
+        raise ValueError(f"rows must hold one row of K = {K} entries per node")
+    rw = _dev_array(rows.reshape(-1), obj.ctx, "rows")
+    if invalid is not None and (not _is_cuda(invalid) or invalid.dtype != torch.int64 or invalid.numel() != 1
+                                or not invalid.is_contiguous() or invalid.device != nd.device):
+        raise ValueError("invalid must be a 1-element int64 CUDA tensor on the batch's device")
+    n_new = int(n_old if n_new is None else n_new)
+    _on_torch_stream(obj.ctx)
+    h = C.c_void_p()
+    check(fn(obj.ctx.h, obj.h, m, ptr(nd) if m else None, ptr(rw) if m else None, n_new, *extra, C.byref(h), ptr(invalid)))
+    return h, n_new
+
+
 def _decode_rows_dev(fn, obj, nodes, K, want_counts, pass_K=True):
     """vidc_*_decode_rows_dev / vidc_compact_rows_decode_dev: rows of a CUDA tensor of nodes (-1 rows for negative nodes and nodes
     >= N) -> (int32 [m, K] CUDA tensor, int32 CUDA counts or None)."""
@@ -335,12 +367,15 @@ class RocLists(_ListCodec):
         nw = info["nwords"]
         words = self.all_words()
         np.savez(path, offsets=self.offsets, precision=info["precision"], heads=info["heads"], nwords=nw,
-                 mt_draws=info["mt_draws"], words=words)
+                 mt_draws=info["mt_draws"], words=words, K=np.int64(getattr(self, "K", 0)))
 
     @classmethod
     def load(cls, path, ctx=None):
         z = np.load(path)
-        return cls.from_streams(z["offsets"], z["precision"], z["heads"], z["nwords"], z["words"], z["mt_draws"], ctx=ctx)
+        obj = cls.from_streams(z["offsets"], z["precision"], z["heads"], z["nwords"], z["words"], z["mt_draws"], ctx=ctx)
+        if "K" in z.files and int(z["K"]):  # a graph object: the row width its decode_rows defaults to
+            obj.K = int(z["K"])
+        return obj
 
     # -- properties
     @property
@@ -703,6 +738,10 @@ class CompactRows:
         check(lib().vidc_compact_rows_encode(ctx.h, N, K, ptr(rows) if N else None, C.byref(h)))
         return cls(h, ctx, N, K)
 
+    def update_rows(self, nodes, rows, n_new=None, invalid=None):
+        """Rows replaced and nodes added -> a NEW CompactRows; this object stays valid and unchanged: update_rows(self, ...) below."""
+        return update_rows(self, nodes, rows, n_new=n_new, invalid=invalid)
+
     @property
     def bits(self):
         return int(lib().vidc_compact_bits(self.h))
@@ -735,6 +774,31 @@ class CompactRows:
         buf = np.zeros(self.stride, np.uint8)
         check(lib().vidc_compact_export_row(self.ctx.h, self.h, node, ptr(buf), self.stride))
         return buf
+
+
+def update_rows(obj, nodes, rows, n_new=None, invalid=None, precision_mode=VIDC_PREC_REFERENCE):
+    """Rows of a graph object replaced and nodes added -> a NEW object of obj's class; obj stays valid and unchanged
+    (vidc_{compact,ef,roc}_update_rows_dev).  obj: what CompactRows / EfLists / RocLists.encode_rows built (Elias-Fano and ROC: K <= 64).
+    CompactRows re-packs every row (the sentinel is the node count) at the width of the new count; EfLists encodes the batch rows into
+    scratch and rewrites its arena at the geometry a fresh object of the updated rows would have; RocLists encodes only the batch rows
+    and copies every other row's stream (precision_mode: the mode obj was built with; ignored by the other two).  See _update_rows for
+    the arguments.  (A function, as removal.remove is: the list classes keep the methods they had.)"""
+    if isinstance(obj, CompactRows):
+        h, n = _update_rows(lib().vidc_compact_update_rows_dev, obj, obj.K, obj.N, nodes, rows, n_new, (), invalid)
+        return type(obj)(h, obj.ctx, n, obj.K)
+    K = getattr(obj, "K", 0)
+    if isinstance(obj, EfLists):
+        n_old = obj._nlist if obj._offsets is None else obj._offsets.size - 1
+        h, n = _update_rows(lib().vidc_ef_update_rows_dev, obj, K, n_old, nodes, rows, n_new, (), invalid)
+        new = type(obj)(h, obj.ctx, None)
+        new._nlist = n
+    elif isinstance(obj, RocLists):
+        h, _ = _update_rows(lib().vidc_roc_update_rows_dev, obj, K, obj.nlist, nodes, rows, n_new, (int(precision_mode),), invalid)
+        new = type(obj)(h, obj.ctx, None)
+    else:
+        raise _lib.VidcError(f"update_rows: {type(obj).__name__} holds no graph rows")
+    new.K = K
+    return new
 
 
 class WaveletTreeLists(_ListCodec):

@@ -24,6 +24,7 @@
 #include "rows_csr.h"
 #include "requests.h"
 #include "rows_tile.h"
+#include "rows_update.h"
 #include "wave.h"
 
 using namespace vidc;
@@ -2565,6 +2566,24 @@ int vidc_ef_decode_rows(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint6
     return ef_decode_some(ctx, e, m, nodes, nullptr, nullptr, d_out, K, nullptr);
 }
 
+// the tile encoder on N rows (K <= 64) into an arena of (LW, HW) records and its per-row meta; d_tot / d_fl zeroed by the caller
+static int ef_rows_encode_launch(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, bool vec, uint32_t LW, uint32_t HW, uint32_t ubound,
+                                 uint64_t *d_arena, uint2 *d_meta, EfRowsTot *d_tot, EfRowsFlags *d_fl) {
+    const dim3 grid((uint32_t)((N + 63) / 64));
+    const uint32_t S = LW + HW;
+#define VIDC_EF_ROWS_ENC(KP, FULL)                                                                                                     \
+    hipLaunchKernelGGL((k_ef_rows_encode_tile<KP, FULL>), grid, dim3(64),                                                                   \
+                       4u * std::max<size_t>((FULL && vec) ? RowsTile<KP>::DWORDS_PF : RowsTile<KP>::DWORDS, 64u * (2u * S + 1u) + 64u), ctx->stream, \
+                       d_rows, N, K, tile_magic(K), vec ? 1u : 0u, LW, HW, tile_magic(S), ubound, d_arena, d_meta, d_tot, d_fl)
+    if (K == 32) VIDC_EF_ROWS_ENC(32, true);
+    else if (K < 32) VIDC_EF_ROWS_ENC(32, false);
+    else if (K == 64) VIDC_EF_ROWS_ENC(64, true);
+    else VIDC_EF_ROWS_ENC(64, false);
+#undef VIDC_EF_ROWS_ENC
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
 int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, vidc_ef **out) {
     if (!ctx || !out || (N && !d_rows)) return VIDC_ERR_INVALID;
     *out = nullptr;
@@ -2609,20 +2628,9 @@ int vidc_ef_encode_rows(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_
         VIDC_HIP(hipMemsetAsync(s_tot.p, 0, tot_bytes, ctx->stream));
         VIDC_HIP(tm.start());
         if (N) {
-            const dim3 grid((uint32_t)((N + 63) / 64));
             EfRowsTot *d_tot = s_tot.as<EfRowsTot>();
-            EfRowsFlags *d_fl = (EfRowsFlags *)(d_tot + 64);
-#define VIDC_EF_ROWS_ENC(KP, FULL)                                                                                                     \
-    hipLaunchKernelGGL((k_ef_rows_encode_tile<KP, FULL>), grid, dim3(64),                                                                   \
-                       4u * std::max<size_t>((FULL && vec) ? RowsTile<KP>::DWORDS_PF : RowsTile<KP>::DWORDS, 64u * (2u * S + 1u) + 64u), ctx->stream, \
-                       d_rows, N, K, tile_magic(K), vec ? 1u : 0u, e->a_lw, \
-                       e->a_hw, tile_magic(S), ubound, e->d_arena.p, e->d_rmeta.p, d_tot, d_fl)
-            if (K == 32) VIDC_EF_ROWS_ENC(32, true);
-            else if (K < 32) VIDC_EF_ROWS_ENC(32, false);
-            else if (K == 64) VIDC_EF_ROWS_ENC(64, true);
-            else VIDC_EF_ROWS_ENC(64, false);
-#undef VIDC_EF_ROWS_ENC
-            VIDC_HIP(hipGetLastError());
+            VIDC_TRY(ef_rows_encode_launch(ctx, N, K, d_rows, vec, e->a_lw, e->a_hw, ubound, e->d_arena.p, e->d_rmeta.p, d_tot,
+                                           (EfRowsFlags *)(d_tot + 64)));
         }
         VIDC_HIP(tm.mark());
         VIDC_HIP(hipMemcpyAsync(tail.p, s_tot.p, tot_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -2671,6 +2679,192 @@ int vidc_ef_decode_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const i
                                             [&](const uint64_t *nd, uint32_t *cnt) { return ef_rows_arena_launch(ctx, e, m, nd, K, d_out, cnt); });
     return req_rows_via_host(ctx, e->nlist, m, d_nodes, K, d_out, d_counts, d_invalid,
                              [&](const uint64_t *hn, uint32_t *hc) { return vidc_ef_decode_rows(ctx, e, m, hn, K, d_out, hc); });
+}
+
+// ---- update rows (include/vidc.h; the slot table: rows_update.h)
+extern "C++" {
+namespace {
+struct EfUpdPre {
+    uint32_t maxid, bad;
+};
+// The largest id of the updated matrix and its domain check, over the rows that reach it: a thread per row of the new object reads the
+// batch row its slot names (ids in front of the first -1) or the old row's universe.  Rows of the batch that are skipped or lose to a
+// later mention are not looked at.
+__global__ void __launch_bounds__(256) k_ef_rows_upd_pre(const uint32_t *__restrict__ slot, uint64_t N_new, uint64_t N_old, const uint2 *__restrict__ old_meta,
+                                                         const int32_t *__restrict__ rows, uint32_t K, EfUpdPre *res) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t mx = 0;
+    bool bad = false;
+    for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < N_new; v += stride) {
+        const uint32_t sl = slot[v];
+        if (sl) {
+            const int32_t *row = rows + (uint64_t)(sl - 1u) * K;
+            for (uint32_t j = 0; j < K; j++) {
+                const int32_t e = row[j];
+                if (e == -1) break;
+                bad |= e < 0;
+                mx = e >= 0 && (uint32_t)e > mx ? (uint32_t)e : mx;
+            }
+        } else if (v < N_old) {
+            const uint2 mt = old_meta[v];
+            mx = (mt.y & 0xffu) && mt.x > mx ? mt.x : mx;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t w = (uint32_t)__shfl_xor((int)mx, o, 64);
+        mx = mx > w ? mx : w;
+    }
+    const uint64_t wbad = ballot(bad);
+    if (lane_id() == 0) {
+        if (mx) atomicMax(&res->maxid, mx);
+        if (wbad) atomicOr(&res->bad, 1u);
+    }
+}
+// The new arena, a thread per word: the record of row v comes from the scratch arena (the batch rows, encoded at the new geometry) by
+// slot[v] - 1, or from the old arena, re-strided when its (LW, HW) differ (rows_upd_restride), or is zero.
+__global__ void __launch_bounds__(256) k_ef_rows_upd_arena(const uint32_t *__restrict__ slot, uint64_t N_new, uint64_t N_old, const uint64_t *__restrict__ old,
+                                                           uint32_t LWo, uint32_t HWo, const uint64_t *__restrict__ batch, uint32_t LW, uint32_t HW,
+                                                           uint32_t smagic, uint64_t *__restrict__ out) {
+    const uint32_t S = LW + HW, So = LWo + HWo, lane = lane_id();
+    const uint64_t ntiles = (N_new + 63u) / 64u;  // a wavefront per tile of 64 records: one contiguous block of the new arena
+    for (uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); tile < ntiles; tile += (uint64_t)gridDim.x * 4u) {
+        const uint64_t row0 = tile * 64u;
+        const uint32_t nrows = (uint32_t)(N_new - row0 < 64u ? N_new - row0 : 64u), total = nrows * S;
+        const uint32_t my_sl = lane < nrows ? slot[row0 + lane] : 0u;  // lane t: the slot of row t of the tile
+        // eight loads in flight per lane before the first store (a load-store loop would wait for every load in turn)
+        for (uint32_t f0 = 0; f0 < total; f0 += 512u) {
+            uint64_t x[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const uint32_t f = f0 + (uint32_t)i * 64u + lane;
+                const uint32_t r = tile_div(f < total ? f : 0u, S, smagic), w = (f < total ? f : 0u) - r * S;
+                const uint32_t sl = (uint32_t)__shfl((int)my_sl, (int)r, 64);
+                const uint64_t v = row0 + r;
+                const uint32_t wo = rows_upd_restride(w, LW, LWo, HWo);
+                x[i] = 0;
+                if (f < total && sl) x[i] = batch[(uint64_t)(sl - 1u) * S + w];
+                else if (f < total && v < N_old && wo != ~0u) x[i] = old[v * So + wo];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const uint32_t f = f0 + (uint32_t)i * 64u + lane;
+                if (f < total) out[row0 * S + f] = x[i];
+            }
+        }
+    }
+}
+// the per-row {universe, n | l << 8} of the new object, and its totals (the tile encoder's sums, over the rows that reach it)
+__global__ void __launch_bounds__(256) k_ef_rows_upd_meta(const uint32_t *__restrict__ slot, uint64_t N_new, uint64_t N_old, const uint2 *__restrict__ old_meta,
+                                                          const uint2 *__restrict__ batch_meta, uint2 *__restrict__ meta, EfRowsTot *tot) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long bits = 0, edges = 0;
+    for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < N_new; v += stride) {
+        const uint32_t sl = slot[v];
+        const uint2 mt = sl ? batch_meta[sl - 1u] : (v < N_old ? old_meta[v] : make_uint2(0u, 0u));
+        meta[v] = mt;
+        const uint32_t n = mt.y & 0xffu, l = mt.y >> 8;
+        bits += n ? (unsigned long long)n * l + (n + 1u) + (mt.x >> l) + 1u : 0ull;  // elias_fano.hpp:28-29, as k_ef_rows_encode_tile sums them
+        edges += n;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        bits += __shfl_xor(bits, o, 64);
+        edges += __shfl_xor(edges, o, 64);
+    }
+    if (lane_id() == 0 && edges) {
+        const uint32_t s = (blockIdx.x * 4u + (threadIdx.x >> 6)) & 63u;
+        atomicAdd(&tot[s].bits, bits);
+        atomicAdd(&tot[s].edges, edges);
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+// Update rows of an arena object.  (1) slot table; the largest id of the updated matrix comes back (8 bytes, with the domain flag) and
+// fixes the new geometry exactly as vidc_ef_encode_rows would find it: ef_rows_geometry(K, max(N_new - 1, largest id)).  (2) the batch
+// rows go through the tile encoder into a scratch arena at that geometry; (3) one kernel writes the new arena from {scratch, old,
+// zero}, one the per-row meta and the totals, which come back (1 KiB).  No row payload leaves the device.
+int vidc_ef_update_rows_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows, uint64_t N_new,
+                            vidc_ef **out, uint64_t *d_invalid) {
+    if (out) *out = nullptr;
+    VIDC_TRY(rows_upd_check("elias-fano", ctx, e, out, m, d_nodes, d_rows, e ? e->nlist : 0, N_new));
+    if (!e->arena) {
+        if (e->K > 64) set_error("elias-fano update_rows: wide rows (K = %u > 64) are CSR objects: not supported", e->K);
+        else set_error("elias-fano update_rows: not a graph object (build it with vidc_ef_encode_rows)");
+        return VIDC_ERR_UNSUPPORTED;
+    }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const uint64_t N_old = e->nlist;
+    const uint32_t K = e->K;
+    std::unique_ptr<vidc_ef> ne(new vidc_ef());
+    ne->device = ctx->device;
+    ne->nlist = N_new;
+    ne->rows = true;
+    ne->arena = true;
+    ne->csr_ready = false;
+    ne->K = K;
+    ne->narrow = true;
+    ne->max_list = K;
+    Scratch s_slot, s_res, s_arena, s_meta;
+    Pinned tail;
+    StreamGuard guard(ctx);
+    const size_t tot_bytes = 64 * sizeof(EfRowsTot) + sizeof(EfRowsFlags);
+    const size_t res_bytes = sizeof(EfUpdPre) + tot_bytes;  // pre | totals | encoder flags
+    VIDC_TRY(tail.get(ctx, res_bytes));
+    VIDC_TRY(s_res.get(ctx, res_bytes));
+    VIDC_TRY(ne->d_rmeta.alloc(N_new ? N_new : 1, ctx->dpool));
+    EfUpdPre *d_pre = s_res.as<EfUpdPre>();
+    EfRowsTot *d_tot = (EfRowsTot *)(d_pre + 1);
+    EfRowsFlags *d_fl = (EfRowsFlags *)(d_tot + 64);
+    VIDC_HIP(hipMemsetAsync(s_res.p, 0, res_bytes, ctx->stream));
+    EventTimer tm(ctx);
+    VIDC_HIP(tm.start());
+    VIDC_TRY(rows_upd_slots(ctx, m, d_nodes, N_new, s_slot, d_invalid));
+    if (N_new) {
+        hipLaunchKernelGGL(k_ef_rows_upd_pre, req_grid(ctx, N_new), dim3(256), 0, ctx->stream, s_slot.as<uint32_t>(), N_new, N_old, e->d_rmeta.p, d_rows,
+                           K, d_pre);
+        VIDC_HIP(hipGetLastError());
+    }
+    VIDC_HIP(tm.mark());
+    VIDC_HIP(hipMemcpyAsync(tail.p, d_pre, sizeof(EfUpdPre), hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    double kernel_ms = tm.elapsed();
+    const EfUpdPre pre = *tail.as<EfUpdPre>();
+    if (pre.bad) { set_error("elias-fano update_rows: negative neighbour id before the -1 terminator"); return VIDC_ERR_DOMAIN; }
+    uint32_t ubound = N_new ? (uint32_t)std::min<uint64_t>(N_new - 1, 0x7fffffffull) : 0u;
+    if (pre.maxid > ubound) ubound = pre.maxid;
+    ef_rows_geometry(K, ubound, &ne->a_lw, &ne->a_hw);
+    const uint32_t S = ne->a_lw + ne->a_hw;
+    if (2u * S + 1u > (K <= 32 ? 33u : 65u)) { set_error("EF rows: record of %u words does not fit the tile", S); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_TRY(ne->d_arena.alloc(N_new * S + 2, ctx->dpool));  // (+2: the decoder reads 16-byte pieces)
+    VIDC_HIP(tm.start());
+    if (m) {
+        VIDC_TRY(s_arena.get(ctx, (m * S + 2) * 8));
+        VIDC_TRY(s_meta.get(ctx, m * sizeof(uint2)));
+        // (the encoder's own flags are not looked at: a skipped or losing row may hold anything; it is encoded as an empty record)
+        VIDC_TRY(ef_rows_encode_launch(ctx, m, K, d_rows, ((uintptr_t)d_rows & 15u) == 0, ne->a_lw, ne->a_hw, ubound, s_arena.as<uint64_t>(),
+                                       s_meta.as<uint2>(), d_tot, d_fl));
+    }
+    if (N_new) {
+        hipLaunchKernelGGL(k_ef_rows_upd_arena, req_grid(ctx, N_new, 256), dim3(256), 0, ctx->stream, s_slot.as<uint32_t>(), N_new, N_old, e->d_arena.p,
+                           e->a_lw, e->a_hw, s_arena.as<uint64_t>(), ne->a_lw, ne->a_hw, tile_magic(S), ne->d_arena.p);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemsetAsync(d_tot, 0, 64 * sizeof(EfRowsTot), ctx->stream));  // (the encoder summed every batch row: start over)
+        hipLaunchKernelGGL(k_ef_rows_upd_meta, req_grid(ctx, N_new), dim3(256), 0, ctx->stream, s_slot.as<uint32_t>(), N_new, N_old, e->d_rmeta.p,
+                           s_meta.as<uint2>(), ne->d_rmeta.p, d_tot);
+        VIDC_HIP(hipGetLastError());
+    }
+    VIDC_HIP(tm.mark());
+    VIDC_HIP(hipMemcpyAsync(tail.p, d_tot, 64 * sizeof(EfRowsTot), hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    guard.disarm();
+    ctx->last_kernel_ms = kernel_ms + tm.elapsed();
+    const EfRowsTot *t = tail.as<EfRowsTot>();
+    ne->ntotal = 0; ne->total_bits = 0;
+    for (int i = 0; i < 64; i++) { ne->ntotal += t[i].edges; ne->total_bits += t[i].bits; }
+    *out = ne.release();
+    return VIDC_OK;
 }
 
 // Append (include/vidc.h): decode_all into scratch, the shared merge (append.h), the device-offsets encoder on the merged CSR.  A

@@ -19,6 +19,7 @@
 #include "host_call.h"
 #include "requests.h"
 #include "rows_tile.h"
+#include "rows_update.h"
 #include "scan.h"
 
 using namespace vidc;
@@ -673,6 +674,179 @@ __global__ void __launch_bounds__(256) k_compact_check_rows(const uint8_t *__res
     }
 }
 
+// vidc_compact_update_rows_dev: row `row` of the new object is batch row slot[row] - 1 packed from int32, or the old record with its
+// fields re-emitted at the new width (the first field equal to N_old, the old sentinel, becomes N_new; the fields behind it stay
+// zero), or -- a new node without a batch row -- the sentinel alone.  A wavefront per row, 64 fields at a time as the wide encoder
+// walks them; an old field (<= 32 bits) is read from the two aligned dwords around its first byte (the old buffer ends with 8
+// padding bytes).  Every byte of every row is written.  Only the rows that reach the new object are read and checked.
+__global__ void __launch_bounds__(64) k_compact_rows_update(const uint8_t *__restrict__ old, uint64_t N_old, uint32_t bits_old, uint32_t stride_old,
+                                                            const int32_t *__restrict__ rows, const uint32_t *__restrict__ slot, uint64_t N_new,
+                                                            uint32_t K, uint32_t bits, uint32_t stride, uint8_t *__restrict__ out, uint32_t *err) {
+    extern __shared__ uint32_t uimg[];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t nw = stride / 4u + 2u;
+    const uint64_t mask_old = (1ull << bits_old) - 1ull;
+    bool bad = false;
+    for (uint64_t row = blockIdx.x; row < N_new; row += gridDim.x) {
+        for (uint32_t t = lane; t < nw; t += 64) uimg[t] = 0;
+        __syncthreads();
+        const uint32_t sl = slot[row];
+        const bool from_old = sl == 0u && row < N_old;
+        const int32_t *src = sl ? rows + (uint64_t)(sl - 1u) * K : nullptr;
+        const uint8_t *rec = old + row * stride_old;  // (only dereferenced when from_old)
+        for (uint32_t j0 = 0; j0 < K; j0 += 64) {
+            const uint32_t j = j0 + lane;
+            uint64_t v = 0;
+            bool end, outside = false;
+            if (from_old) {
+                if (j < K) {
+                    const uint64_t pos = (uint64_t)j * bits_old;
+                    const uintptr_t a = (uintptr_t)(rec + (pos >> 3));
+                    const uint32_t *w = (const uint32_t *)(a & ~(uintptr_t)3);
+                    const uint32_t sh = (uint32_t)(a & 3u) * 8u + (uint32_t)(pos & 7u);
+                    v = ((((uint64_t)w[1] << 32) | w[0]) >> sh) & mask_old;
+                }
+                end = j < K && v == N_old;
+            } else {
+                const int32_t e = (src && j < K) ? src[j] : -1;  // (no batch row: the empty row)
+                end = j < K && e == -1;
+                v = (uint64_t)(uint32_t)e;
+                outside = e < 0 || (uint64_t)e >= N_new;
+            }
+            const uint64_t endm = __ballot(end);
+            const uint32_t first = endm ? j0 + (uint32_t)__builtin_ctzll(endm) : K;  // the sentinel's field, if it lies in this group
+            bad |= j < K && j < first && outside;  // (ids are checked in front of the first -1 only, as the encoder checks them)
+            if (j < K && j <= first) {
+                const uint64_t f = j == first ? N_new : v;
+                const uint64_t pos = (uint64_t)j * bits;
+                const uint64_t sh = f << (pos & 31);
+                atomicOr(&uimg[pos >> 5], (uint32_t)sh);
+                if ((pos & 31) + bits > 32) atomicOr(&uimg[(pos >> 5) + 1], (uint32_t)(sh >> 32));
+            }
+            if (endm) break;
+        }
+        if (__ballot(bad) && lane == 0) *(volatile uint32_t *)err = 1u;  // (every writer stores the same value)
+        __syncthreads();
+        if ((stride & 3u) == 0u) {
+            uint32_t *o = (uint32_t *)(out + row * stride);
+            for (uint32_t t = lane; t < stride / 4u; t += 64) o[t] = uimg[t];
+        } else {
+            const uint8_t *b = (const uint8_t *)uimg;
+            for (uint32_t t = lane; t < stride; t += 64) out[row * stride + t] = b[t];
+        }
+        __syncthreads();
+    }
+}
+
+// The same for K <= 64 when both strides are whole dwords (every K = 32 / 64 graph), 64 consecutive rows per wavefront in the tile
+// layout of the encoder (rows_tile.h): the 64 old records come in as one coalesced block into LDS records of an odd stride; lane t
+// re-emits row t field by field -- the bit position of field e is the same for every lane, so the two dwords around it are a
+// conflict-free LDS read, and the new record is built 32 bits at a time as k_compact_rows_encode_tile builds it (a lane without an
+// old row emits the sentinel alone).  Then the rows of the tile that the batch replaces are packed one after the other by the whole
+// wavefront (lane = field, as k_compact_rows_encode), over the record the first pass left; the 64 records leave as one block.
+__global__ void __launch_bounds__(64) k_compact_rows_update_tile(const uint32_t *__restrict__ old, uint64_t N_old, uint32_t bits_old, uint32_t SDo,
+                                                                 uint32_t sdomagic, const int32_t *__restrict__ rows, const uint32_t *__restrict__ slot,
+                                                                 uint64_t N_new, uint32_t K, uint32_t bits, uint32_t SD, uint32_t sdmagic,
+                                                                 uint32_t *__restrict__ out, uint32_t *err) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // 64 old records (+ 1 spill dword), 64 new records (+ 2)
+    const uint32_t lane = lane_id();
+    const uint32_t SD1o = SDo | 1u, SD1 = SD | 1u;
+    uint32_t *recs_o = lds, *recs_n = lds + 64u * SD1o + 1u;
+    const uint64_t row0 = (uint64_t)blockIdx.x * 64u;
+    const uint32_t nrows = (uint32_t)(N_new - row0 < 64u ? N_new - row0 : 64u);
+    const uint32_t nold = row0 < N_old ? (uint32_t)(N_old - row0 < 64u ? N_old - row0 : 64u) : 0u;
+    {
+        const uint32_t *src = old + row0 * SDo;
+        const uint32_t total = nold * SDo;
+        // sixteen loads in flight per lane before the first one is consumed (a load-store loop would wait for every load in turn)
+        for (uint32_t f0 = 0; f0 < total; f0 += 1024u) {
+            uint32_t v[16];
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const uint32_t f = f0 + (uint32_t)i * 64u + lane;
+                v[i] = f < total ? src[f] : 0u;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const uint32_t f = f0 + (uint32_t)i * 64u + lane;
+                const uint32_t r = tile_div(f, SDo, sdomagic);
+                if (f < total) recs_o[r * SD1o + (f - r * SDo)] = v[i];
+            }
+        }
+    }
+    const uint32_t sl = lane < nrows ? slot[row0 + lane] : 0u;
+    wave_lds_sync();
+    const uint32_t n_old32 = (uint32_t)N_old, n_new32 = (uint32_t)N_new;
+    {
+        const bool from_old = lane < nold && sl == 0u;
+        const uint32_t mask_o = bits_old >= 32u ? 0xffffffffu : (1u << bits_old) - 1u;
+        const uint32_t *ro = recs_o + lane * SD1o;
+        uint32_t *rec = recs_n + lane * SD1;
+        bool alive = true;
+        uint32_t lo = 0, fill = 0, wofs = 0, pos_o = 0;
+#pragma unroll 4
+        for (uint32_t e = 0; e < K; e++) {
+            const uint32_t dw = pos_o >> 5, sh = pos_o & 31u;
+            // (a lane without an old row reads the old sentinel at once: it emits the new sentinel and then zeros)
+            const uint32_t x = from_old ? __builtin_amdgcn_alignbit(ro[dw + 1u], ro[dw], sh) & mask_o : n_old32;
+            const bool was = alive;
+            alive = alive && x != n_old32;
+            const uint32_t v = alive ? x : (was ? n_new32 : 0u);
+            const uint64_t t = ((uint64_t)v << fill) | lo;
+            rec[wofs] = (uint32_t)t;
+            fill += bits;
+            const bool full = fill >= 32u;
+            lo = full ? (uint32_t)(t >> 32) : (uint32_t)t;
+            wofs += full ? 1u : 0u;
+            fill -= full ? 32u : 0u;
+            pos_o += bits_old;
+        }
+        if (fill) rec[wofs] = lo;
+    }
+    wave_lds_sync();
+    bool bad = false;
+    for (uint64_t todo = ballot(sl != 0u); todo; todo &= todo - 1ull) {
+        const uint32_t r = ff1(todo);
+        const uint32_t s = (uint32_t)__shfl((int)sl, (int)r, 64);
+        const int32_t e = lane < K ? rows[(uint64_t)(s - 1u) * K + lane] : -1;
+        const uint64_t endm = ballot(e == -1);
+        const uint32_t n = endm ? ff1(endm) : 64u;  // edges before the first -1 (lanes >= K hold -1: n <= K)
+        bad |= lane < n && (e < 0 || (uint64_t)e >= N_new);
+        uint32_t *rec = recs_n + r * SD1;
+        for (uint32_t w = lane; w < SD1; w += 64u) rec[w] = 0u;
+        wave_lds_sync();
+        if (lane <= n && lane < K) {
+            const uint64_t v = lane == n ? (uint64_t)n_new32 : (uint64_t)(uint32_t)e;
+            const uint32_t pos = lane * bits;
+            const uint64_t shv = v << (pos & 31u);
+            atomicOr(&rec[pos >> 5], (uint32_t)shv);
+            if ((pos & 31u) + bits > 32u) atomicOr(&rec[(pos >> 5) + 1u], (uint32_t)(shv >> 32));
+        }
+    }
+    wave_lds_sync();
+    if (ballot(bad) && lane == 0) *(volatile uint32_t *)err = 1u;  // (every writer stores the same value)
+    uint32_t *dst = out + row0 * SD;
+    if ((SD & 3u) == 0u) {  // 16-byte pieces never straddle two rows; SD <= 64: at most 16 pieces per lane
+        const uint32_t CPR = SD >> 2, total = nrows * CPR;
+        const uint32_t cmagic = tile_magic(CPR);
+        const uint32_t step_rows = tile_div(64u, CPR, cmagic), step_w = 64u - step_rows * CPR;
+        TileCursor c = tile_cursor(CPR, cmagic);
+        for (uint32_t f = lane; f < total; f += 64u) {
+            const uint32_t *q = recs_n + c.row * SD1 + 4u * c.w;
+            ((uint4 *)dst)[f] = make_uint4(q[0], q[1], q[2], q[3]);
+            tile_advance(c, CPR, step_rows, step_w);
+        }
+    } else {
+        const uint32_t total = nrows * SD;
+        const uint32_t step_rows = tile_div(64u, SD, sdmagic), step_w = 64u - step_rows * SD;
+        TileCursor c = tile_cursor(SD, sdmagic);
+        for (uint32_t f = lane; f < total; f += 64u) {
+            dst[f] = recs_n[c.row * SD1 + c.w];
+            tile_advance(c, SD, step_rows, step_w);
+        }
+    }
+}
+
 }  // namespace
 
 struct vidc_compact {
@@ -805,6 +979,52 @@ int vidc_compact_rows_decode_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t 
     const bool tile = compact_tile(c);  // (the other two decoders always write counts)
     return req_rows_on_device<uint64_t>(ctx, c->N, m, d_nodes, c->K, d_out, d_counts, d_invalid, !tile,
                                         [&](const uint64_t *nd, uint32_t *cnt) { return compact_rows_launch(ctx, c, m, nd, d_out, cnt); });
+}
+
+// Update rows (include/vidc.h): the slot table (rows_update.h), then ONE re-pack kernel writes every row of the new object -- the
+// sentinel changes with N in every row, so no row can be copied.  One 4-byte read-back (the domain flag).
+int vidc_compact_update_rows_dev(vidc_ctx *ctx, const vidc_compact *c, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows,
+                                 uint64_t N_new, vidc_compact **out, uint64_t *d_invalid) {
+    if (out) *out = nullptr;
+    VIDC_TRY(rows_upd_check("compact", ctx, c, out, m, d_nodes, d_rows, c ? c->N : 0, N_new));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<vidc_compact> nc(new vidc_compact());
+    nc->device = ctx->device;
+    nc->N = N_new;
+    nc->K = c->K;
+    nc->bits = (uint32_t)vidc_packed_bits_for(N_new);  // (N_new < 2^32 - 1: at most 32 bits, two dwords per field)
+    nc->stride = (c->K * nc->bits + 7) / 8;
+    VIDC_TRY(nc->d_data.alloc(N_new * nc->stride + 8, ctx->dpool));
+    Scratch s_err, s_slot;
+    StreamGuard guard(ctx);
+    VIDC_TRY(s_err.get(ctx, 4));
+    VIDC_HIP(hipMemsetAsync(s_err.p, 0, 4, ctx->stream));
+    VIDC_HIP(hipMemsetAsync(nc->d_data.p + N_new * nc->stride, 0, 8, ctx->stream));
+    EventTimer t(ctx);
+    VIDC_HIP(t.start());
+    VIDC_TRY(rows_upd_slots(ctx, m, d_nodes, N_new, s_slot, d_invalid));
+    if (N_new && c->K <= 64 && (nc->stride & 3u) == 0u && (c->stride & 3u) == 0u) {  // (the old stride is 0 for an object without rows)
+        const uint32_t SDo = c->stride / 4u, SD = nc->stride / 4u;
+        const size_t dyn = ((size_t)64 * (SDo | 1u) + 1u + (size_t)64 * (SD | 1u) + 2u) * 4u;
+        hipLaunchKernelGGL(k_compact_rows_update_tile, dim3((uint32_t)((N_new + 63) / 64)), dim3(64), dyn, ctx->stream, (const uint32_t *)c->d_data.p,
+                           c->N, c->bits, SDo, dev::tile_magic(SDo), d_rows, s_slot.as<uint32_t>(), N_new, c->K, nc->bits, SD, dev::tile_magic(SD),
+                           (uint32_t *)nc->d_data.p, s_err.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+    } else if (N_new) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(N_new, (uint64_t)ctx->num_cu * 64);
+        hipLaunchKernelGGL(k_compact_rows_update, dim3(grid), dim3(64), (nc->stride / 4u + 2u) * 4u, ctx->stream, c->d_data.p, c->N, c->bits,
+                           c->stride, d_rows, s_slot.as<uint32_t>(), N_new, c->K, nc->bits, nc->stride, nc->d_data.p, s_err.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+    }
+    VIDC_HIP(t.mark());
+    uint32_t err = 0;
+    VIDC_HIP(hipMemcpyAsync(&err, s_err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    guard.disarm();
+    ctx->last_kernel_ms = t.elapsed();
+    if (err) { set_error("compact update_rows: neighbour id outside [0, N_new)"); return VIDC_ERR_DOMAIN; }
+    *out = nc.release();
+    return VIDC_OK;
 }
 
 int vidc_compact_export_row(vidc_ctx *ctx, const vidc_compact *c, uint64_t node, uint8_t *bytes, size_t cap) {

@@ -22,6 +22,7 @@
 #include "roc_lane.h"
 #include "roc_grp.h"
 #include "requests.h"
+#include "rows_update.h"
 #include "scan.h"
 
 using namespace vidc;
@@ -1705,24 +1706,66 @@ struct RocSrc : RocMeta {
 struct RocSrcs {
     RocSrc s[VIDC_SHARDS_MAX];
 };
-// the five per-list arrays of the new object (sizes: what the scan turns into its offsets)
-__global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs srcs, const uint32_t *__restrict__ src_no, const uint64_t *__restrict__ list_no,
-                                                          uint64_t m, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
-                                                          uint32_t *__restrict__ nwords, uint32_t *__restrict__ draws, uint32_t *__restrict__ sizes) {
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (uint64_t)gridDim.x * blockDim.x) {
-        const RocSrc &s = srcs.s[src_no[j]];
-        const uint64_t k = list_no[j];
-        heads[j] = s.heads[k];
-        prec[j] = s.prec[k];
-        nwords[j] = s.nwords[k];
-        draws[j] = s.draws[k];
-        sizes[j] = (uint32_t)(s.offsets[k + 1] - s.offsets[k]);
+// Where list j of the new object comes from: get(j, source, list) -> false for a list that has no source (an empty list).
+// The regroup's table, uploaded by the host ...
+struct RocRegroupTable {
+    const uint32_t *src_no;
+    const uint64_t *list_no;
+    __device__ __forceinline__ bool get(uint64_t j, uint32_t &s, uint64_t &k) const {
+        s = src_no[j];
+        k = list_no[j];
+        return true;
+    }
+};
+// ... and the slot table of vidc_roc_update_rows_dev (rows_update.h), built on the device: source 1 holds the encoded batch rows,
+// source 0 is the old object, a new node without a batch row is the empty row.
+struct RocUpdateSlots {
+    const uint32_t *slot;
+    uint64_t N_old;
+    __device__ __forceinline__ bool get(uint64_t j, uint32_t &s, uint64_t &k) const {
+        const uint32_t sl = slot[j];
+        s = sl ? 1u : 0u;
+        k = sl ? (uint64_t)(sl - 1u) : j;
+        return sl != 0u || j < N_old;
+    }
+};
+// the five per-list arrays of the new object (sizes: what the scan turns into its offsets); *nonempty (may be NULL) += lists with ids
+template <typename Lookup>
+__global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs srcs, Lookup look, uint64_t m, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
+                                                          uint32_t *__restrict__ nwords, uint32_t *__restrict__ draws, uint32_t *__restrict__ sizes,
+                                                          unsigned long long *nonempty) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); j0 < m; j0 += stride) {  // (j0: wavefront-uniform)
+        const uint64_t j = j0 + lane_id();
+        uint32_t size = 0;
+        if (j < m) {
+            uint32_t sn;
+            uint64_t k;
+            if (look.get(j, sn, k)) {
+                const RocSrc &s = srcs.s[sn];
+                heads[j] = s.heads[k];
+                prec[j] = s.prec[k];
+                nwords[j] = s.nwords[k];
+                draws[j] = s.draws[k];
+                size = (uint32_t)(s.offsets[k + 1] - s.offsets[k]);
+            } else {  // what the encoders leave for an empty list (k_roc_encode_tiny)
+                heads[j] = VIDC_RANS_L;
+                prec[j] = 0u;
+                nwords[j] = 0u;
+                draws[j] = 0u;
+            }
+            sizes[j] = size;
+        }
+        if (nonempty) {
+            const uint64_t b = ballot(size != 0u);
+            if (b && lane_id() == 0) atomicAdd(nonempty, (unsigned long long)popc64(b));
+        }
     }
 }
 // the words: k_app_copy<uint32_t, true> with the source of a list chosen among the sources' word arrays.  A wavefront per chunk of the
-// new lists' streams (items: app_chunks on dst_off).
-__global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs srcs, const uint32_t *__restrict__ src_no, const uint64_t *__restrict__ list_no,
-                                                          const uint64_t *__restrict__ dst_off, uint32_t *__restrict__ dst,
+// new lists' streams (items: app_chunks on dst_off; a list without a source has no words, hence no chunk).
+template <typename Lookup>
+__global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs srcs, Lookup look, const uint64_t *__restrict__ dst_off, uint32_t *__restrict__ dst,
                                                           const Chunk *__restrict__ items, const uint64_t *__restrict__ n_items) {
     const uint64_t total = *n_items;
     const uint32_t lane = lane_id();
@@ -1730,8 +1773,11 @@ __global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs srcs, const ui
         const Chunk ch = items[c];
         const uint64_t base = dst_off[ch.list], n = dst_off[ch.list + 1] - base;
         const uint32_t nc = (uint32_t)(n - ch.start < APP_COPY_UNIT ? n - ch.start : APP_COPY_UNIT);
-        const RocSrc &s = srcs.s[src_no[ch.list]];
-        app_copy_chunk(s.words + s.word_off[list_no[ch.list]] + ch.start, dst + base + ch.start, nc, lane);
+        uint32_t sn;
+        uint64_t k;
+        if (!look.get(ch.list, sn, k)) continue;
+        const RocSrc &s = srcs.s[sn];
+        app_copy_chunk(s.words + s.word_off[k] + ch.start, dst + base + ch.start, nc, lane);
     }
 }
 
@@ -2641,8 +2687,8 @@ int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint6
         }
     EventTimer tm = EventTimer::started(ctx);
     if (m) {
-        hipLaunchKernelGGL(k_roc_regroup_meta, req_grid(ctx, m), dim3(256), 0, ctx->stream, S, d_src_no, d_list_no, m, nr->d_heads.p, nr->d_prec.p,
-                           nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>());
+        hipLaunchKernelGGL(k_roc_regroup_meta<RocRegroupTable>, req_grid(ctx, m), dim3(256), 0, ctx->stream, S, RocRegroupTable{d_src_no, d_list_no}, m,
+                           nr->d_heads.p, nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>(), (unsigned long long *)nullptr);
         VIDC_HIP(hipGetLastError());
         Scan4 sc{};
         sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
@@ -2661,8 +2707,8 @@ int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint6
     if (nr->total_words) {
         VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, m, nr->total_words, ch_w));
         copy_timer.begin();
-        hipLaunchKernelGGL(k_roc_regroup_copy, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S, d_src_no, d_list_no,
-                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
+        hipLaunchKernelGGL(k_roc_regroup_copy<RocRegroupTable>, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S,
+                           RocRegroupTable{d_src_no, d_list_no}, (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
         copy_timer.end();
         VIDC_HIP(hipGetLastError());
     }
@@ -2685,6 +2731,96 @@ int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint6
     guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
     ctx->phase_ms[VIDC_PHASE_ROC_REGROUP_COPY] = copy_timer.collect();
+    tr.mark("streams copied");
+    *out = nr.release();
+    return VIDC_OK;
+}
+
+// Update rows (include/vidc.h): the regroup's splice over {old object, the encoded batch rows}, with the slot table of rows_update.h on
+// the device where the regroup has its host table.  The m batch rows are encoded by the rows path into a temporary object (every one
+// of them, so every one is checked); one kernel gathers the per-row metadata, one scan launch set gives the offsets and the word
+// offsets, the totals come back (24 bytes: words, edges, non-empty rows), the chunked copy moves the streams.  A row's stream depends on
+// its multiset and precision alone: an untouched row keeps its words.  Like an imported object the result carries no planner hints.
+int vidc_roc_update_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows, uint64_t N_new,
+                             int precision_mode, vidc_roc **out, uint64_t *d_invalid) {
+    if (out) *out = nullptr;
+    VIDC_TRY(rows_upd_check("roc", ctx, r, out, m, d_nodes, d_rows, r ? r->nlist : 0, N_new));
+    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
+        set_error("roc update_rows: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
+        return VIDC_ERR_INVALID;
+    }
+    if (!r->rows) {
+        if (r->K > TINY_MAX) set_error("roc update_rows: wide rows (K = %u > 64) are CSR objects: not supported", r->K);
+        else set_error("roc update_rows: not a graph object (build it with vidc_roc_encode_rows)");
+        return VIDC_ERR_UNSUPPORTED;
+    }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc update_rows");
+    const uint64_t N_old = r->nlist;
+    double kernel_ms = 0;
+    std::unique_ptr<vidc_roc> tmp;
+    if (m) {
+        vidc_roc *t = nullptr;
+        VIDC_TRY(vidc_roc_encode_rows(ctx, m, r->K, d_rows, precision_mode, 0, &t));
+        tmp.reset(t);
+        kernel_ms += ctx->last_kernel_ms;
+    }
+    tr.mark("batch rows encoded");
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = ctx->device;
+    nr->rows = true;
+    nr->K = r->K;
+    nr->nlist = N_new;
+    Scratch s_slot, s_sizes, s_cnt, s_t0;
+    Pinned h_tot;
+    AppChunks ch_w;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
+    VIDC_TRY(h_tot.get(ctx, 24));
+    VIDC_TRY(s_cnt.get(ctx, 8));
+    VIDC_TRY(s_sizes.get(ctx, (N_new + 1) * 4));
+    uint64_t *h_cnt = h_tot.as<uint64_t>();  // word total | edges | non-empty rows
+    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
+    VIDC_TRY(nr->d_offsets.alloc(N_new + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(N_new, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(N_new, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(N_new, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(N_new, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(N_new + 1, ctx->dpool));
+    RocSrcs S{};
+    S.s[0] = RocSrc{{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p}, r->d_words.p, r->d_word_off.p, r->d_offsets.p};
+    if (tmp) S.s[1] = RocSrc{{tmp->d_heads.p, tmp->d_prec.p, tmp->d_nwords.p, tmp->d_draws.p}, tmp->d_words.p, tmp->d_word_off.p, tmp->d_offsets.p};
+    EventTimer tm = EventTimer::started(ctx);
+    VIDC_TRY(rows_upd_slots(ctx, m, d_nodes, N_new, s_slot, d_invalid));
+    const RocUpdateSlots look{s_slot.as<uint32_t>(), N_old};
+    if (N_new) {
+        VIDC_HIP(hipMemsetAsync(s_cnt.p, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_roc_regroup_meta<RocUpdateSlots>, req_grid(ctx, N_new), dim3(256), 0, ctx->stream, S, look, N_new, nr->d_heads.p,
+                           nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>(), s_cnt.as<unsigned long long>());
+        VIDC_HIP(hipGetLastError());
+        Scan4 sc{};
+        sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)N_new, s_t0));
+        VIDC_HIP(hipMemcpyAsync(h_cnt, nr->d_word_off.p + N_new, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, nr->d_offsets.p + N_new, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, s_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_cnt[0];
+    nr->ntotal = h_cnt[1];
+    nr->compressed_bytes = 8ull * h_cnt[2] + 4ull * nr->total_words;
+    tr.mark("metadata gathered, totals read back");
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, N_new, nr->total_words, ch_w));
+        hipLaunchKernelGGL(k_roc_regroup_copy<RocUpdateSlots>, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S, look,
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
+        VIDC_HIP(hipGetLastError());
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    guard.disarm();
+    ctx->last_kernel_ms = kernel_ms;
     tr.mark("streams copied");
     *out = nr.release();
     return VIDC_OK;
