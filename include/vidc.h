@@ -715,6 +715,69 @@ int vidc_remove_sharded_dev(vidc_ctx *home, const vidc_shards *s, uint64_t n_rm,
  *   metadata, which that counter does not count). */
 int vidc_rebalance_sharded(vidc_ctx *home, const vidc_shards *s, uint32_t flags, vidc_shards **out, uint64_t *moved_ids /* host, may be NULL */);
 
+/* ------------------------------------------------ segmented ROC lists (parallel chains inside a list) */
+/* A ROC list is one chain of dependent ANS steps; a list of 50 000 ids is a chain of 50 000.  A set of ids cut BY VALUE RANGE into
+ * segments costs the same number of bits up to a constant per segment, and every segment is an independent chain over a smaller
+ * universe.  vidc_rocseg is the opt-in container built on that: like VIDC_PREC_EXACT it is NOT reference-identical (the reference has one
+ * stream per list); nothing about vidc_roc changes.
+ *
+ * Parameters.  seg_ids = T, a power of two in [16, 65 536] (0: VIDC_ROCSEG_DEFAULT_IDS): the target number of ids per segment.
+ *   universe_bits = B in 1 .. 31 (0: max(1, bit_width(largest id of the call)), found by a reduction on the device).  An id >= 2^B is
+ *   VIDC_ERR_DOMAIN.  The per-list domain is that of vidc_roc_encode.
+ * Segments.  List l with n_l ids has S_l = 2^k_l segments, k_l = 0 for n_l <= T and min(B, ceil_log2(ceil(n_l / T))) otherwise, and
+ *   shift_l = B - k_l: id x sits in segment x >> shift_l and is stored as x & (2^shift_l - 1) (k_l = 0: one segment, the id unchanged).
+ *   S_l > VIDC_ROCSEG_MAX_SEGS is VIDC_ERR_DOMAIN.  A segment keeps its ids in the input order of its list: the partition is stable,
+ *   and no atomic decides a position.
+ * The inner object is an ordinary vidc_roc over the sum of S_l lists in (list, segment) order, encoded with VIDC_PREC_EXACT (rebasing
+ *   makes power-of-two maxima all the time, which the reference precision loses): every segment is, word for word, what vidc_roc_encode
+ *   builds from its rebased ids at bit_width(max); empty segments are empty lists.  Segments of a list are consecutive, so the inner CSR
+ *   addresses the same positions as the outer one and decode_all decodes straight into the caller's buffer.
+ * Order.  A list decodes as its segments in order, each in its own sampling order.  vidc_rocseg_perm maps output position to input
+ *   position within the list, as vidc_roc_perm does (objects encoded with VIDC_ROC_WANT_PERM; VIDC_ERR_INVALID otherwise).
+ * Size.  compressed_bytes = the inner object's + 4 bytes for every segment of a list with S_l > 1.
+ * Requests answer as the vidc_roc calls of the same name do: decode_lists expands the outer list numbers into inner ranges on the host
+ *   and collapses out_offsets back to m + 1; translate_labels_dev rewrites the labels on the device (a binary search over the list's
+ *   inner offsets; a negative label stays negative, an invalid one is counted once), runs vidc_roc_translate_labels_dev on them -- only
+ *   the TOUCHED SEGMENTS decode -- and adds the segment bases to the results >= 0; d_ids == d_labels is allowed.  Behind every decode a
+ *   wavefront per 1024-id chunk ORs segment << shift into the decoded ids in place.  The calls wait; vidc_ctx_last_kernel_ms is the sum
+ *   of the inner call's kernels and the container's own, and vidc_ctx_phase_ms(VIDC_PHASE_ROCSEG_PARTITION) the encode's own kernels.
+ * vidc_rocseg_inner is borrowed: the vidc_roc list_info / export calls on it serve parity checks and saving.  vidc_rocseg_seg_info copies
+ *   the map: seg_first[l] = the first inner list of list l (nlist + 1 entries), shift[l] (nlist entries); either may be NULL.
+ * vidc_rocseg_wrap builds a segmented object from an imported inner object (vidc_roc_import) and an UNTRUSTED map; on success it takes
+ *   ownership of `inner`.  Checked before any device work: seg_first monotone from 0 to the inner object's list count, every segment count
+ *   a power of two <= VIDC_ROCSEG_MAX_SEGS that equals 2^(universe_bits - shift), every inner precision <= its list's shift (a decoded id
+ *   then stays below its segment's width), seg_ids and universe_bits in range (no 0 defaults here).  Anything else: VIDC_ERR_INVALID,
+ *   *out == NULL, and `inner` stays the caller's.  A wrapped object carries no permutation.
+ * Status.  NULL arguments, a seg_ids that is not a power of two in range, universe_bits > 31: VIDC_ERR_INVALID before any device work.  On
+ *   any error *out == NULL and the context stays usable.
+ * Out of scope: append, remove, regroup, sharding and graph rows on segmented objects (re-encode, or use vidc_roc). */
+typedef struct vidc_rocseg vidc_rocseg;
+#define VIDC_ROCSEG_MAX_SEGS 1024u
+#define VIDC_ROCSEG_DEFAULT_IDS 1024u /* the fastest of 1024 .. 8192 on S1 and on 16.8 M ids / 65 536 Zipf lists: DESIGN 9c, profiles/r33_roc_segmented.json */
+int vidc_rocseg_encode(vidc_ctx *ctx, uint64_t nlist, const uint64_t *offsets /* host */, const uint64_t *d_ids, uint32_t seg_ids,
+                       uint32_t universe_bits, uint32_t flags /* VIDC_ROC_WANT_PERM */, vidc_rocseg **out);
+/* d_offsets: device uint64[nlist + 1]; the plan is made on the host, so the offsets cross PCIe once (as vidc_roc_encode_dev) */
+int vidc_rocseg_encode_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint64_t *d_ids, uint32_t seg_ids,
+                           uint32_t universe_bits, uint32_t flags, vidc_rocseg **out);
+void vidc_rocseg_destroy(vidc_rocseg *s);
+uint64_t vidc_rocseg_nlist(const vidc_rocseg *s);
+uint64_t vidc_rocseg_ntotal(const vidc_rocseg *s);
+uint64_t vidc_rocseg_compressed_bytes(const vidc_rocseg *s);
+uint32_t vidc_rocseg_seg_ids(const vidc_rocseg *s);
+uint32_t vidc_rocseg_universe_bits(const vidc_rocseg *s);
+const vidc_roc *vidc_rocseg_inner(const vidc_rocseg *s);
+int vidc_rocseg_seg_info(const vidc_rocseg *s, uint64_t *seg_first /* nlist + 1 */, uint8_t *shift /* nlist */);
+int vidc_rocseg_wrap(vidc_ctx *ctx, vidc_roc *inner, uint64_t nlist, const uint64_t *seg_first, const uint8_t *shift, uint32_t seg_ids,
+                     uint32_t universe_bits, vidc_rocseg **out);
+int vidc_rocseg_decode_all(vidc_ctx *ctx, const vidc_rocseg *s, uint64_t *d_out);
+int vidc_rocseg_decode_lists(vidc_ctx *ctx, const vidc_rocseg *s, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,
+                             uint64_t *out_offsets);
+int vidc_rocseg_translate_labels_dev(vidc_ctx *ctx, const vidc_rocseg *s, uint64_t n, const int64_t *d_labels, int64_t *d_ids,
+                                     uint64_t *d_invalid);
+int vidc_rocseg_perm(vidc_ctx *ctx, const vidc_rocseg *s, uint32_t *perm_host);
+/* vidc_roc_last_decode_handed_back of the inner object */
+uint64_t vidc_rocseg_last_decode_handed_back(const vidc_rocseg *s);
+
 /* ------------------------------------------------------ introspection / timing */
 /* Milliseconds spent inside the kernels of the most recent encode / decode call on this context,
  * measured with hipEvents on the context's stream (used by bench.py for the roofline figure). */
@@ -729,6 +792,8 @@ double vidc_ctx_last_kernel_ms(const vidc_ctx *ctx);
                                  * and check are vidc_ctx_last_kernel_ms: for wt_type 1 the sum of the intervals in front of and behind the
                                  * read-back of the levels' width totals, without the wait between them */
 #define VIDC_PHASE_ROC_REGROUP_COPY 6 /* vidc_roc_regroup: the segmented word copy alone (0 for an object without words) */
+#define VIDC_PHASE_ROCSEG_PARTITION 7 /* vidc_rocseg_encode*: the universe reduction, the multisplit, its scan, the inner offsets and the
+                                       * permutation compose -- everything but the inner vidc_roc_encode_dev */
 #define VIDC_PHASE_COUNT 8
 double vidc_ctx_phase_ms(const vidc_ctx *ctx, int phase);
 /* What the chain launch of the last ROC encode (which = 0) / decode (1) on this context processed: ids, lists, longest list and

@@ -1,0 +1,344 @@
+"""Segmented ROC lists on the GPU (include/vidc.h, "segmented ROC lists"; codecs.RocSegLists) against the numpy model
+(tests/roc_seg_ref.py, pinned by tests/test_roc_seg_ref_cpu.py) and the CPU oracle.
+
+Every comparison is between integers and exact: the map, the inner object's metadata and every exported word against the oracle's encode
+of the model's segments; decode_all against the oracle's sampling order plus base; the permutation, decode_lists, translate_labels (every
+position, negative and invalid labels, in place), decode_gather, compressed_bytes, save / load / wrap.  Shapes are small on purpose:
+T = 16 and 64, B = 10 .. 20, list sizes around T, 2 T and the 1024-id seam of the multisplit's chunks, and one list of 20 000 ids at
+T = 1024.  The main cases also run under VIDC_FORCE_GENERAL=1 and VIDC_NO_LANE=1 (the inner object's other kernel families).
+"""
+import numpy as np
+import pytest
+
+import roc_seg_ref as sr
+
+pytestmark = pytest.mark.gpu
+
+KEYS = ("sizes", "precision", "heads", "nwords", "mt_draws")
+HOOKS = ("VIDC_FORCE_GENERAL", "VIDC_NO_LANE")
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+def _cls():
+    from vector_db_id_compression_amd.codecs import RocSegLists
+
+    return RocSegLists
+
+
+def dev(a):
+    return _torch().from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
+
+
+def csr(lists):
+    off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.uint64)
+    return off, np.concatenate([np.asarray(l, np.uint64) for l in lists] + [np.zeros(0, np.uint64)])
+
+
+def distinct(rng, n, B, shuffled, must=()):
+    """n distinct ids below 2^B holding `must`"""
+    pool = np.setdiff1d(np.arange(1 << B, dtype=np.uint64), np.asarray(must, np.uint64))
+    li = np.concatenate([np.asarray(must, np.uint64), rng.choice(pool, n - len(must), replace=False)]) if n else np.zeros(0, np.uint64)
+    return rng.permutation(li) if shuffled else np.sort(li)
+
+
+def family(name):
+    """-> (T, B, lists)"""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    if name.startswith("sizes"):  # sizes16-asc, sizes16-shuf, sizes64-asc, sizes64-shuf: 0, 1, T, T + 1, 2T, 2T + 1, 100 mixed
+        T, shuffled = int(name[5:7]), name.endswith("shuf")
+        B = 10 if T == 16 else 12
+        sizes = [0, 1, T, T + 1, 0, 2 * T, 2 * T + 1, 100, 3]
+        lists = [distinct(rng, n, B, shuffled) for n in sizes]
+        lists[7] = distinct(rng, 100, B, shuffled, must=[0, (1 << B) - 1])  # ids holding 0 and 2^B - 1
+        return T, B, lists
+    if name.startswith("seam"):  # 1023 / 1024 / 1025 / 2049 cross the seam of the multisplit's 1024-id chunks
+        shuffled = name.endswith("shuf")
+        return 64, 14, [distinct(rng, n, 14, shuffled) for n in (1023, 0, 1024, 1025, 5, 2049)]
+    if name == "skew":  # T = 16, B = 12; 100 ids -> k = 3, shift = 9 (hand-built segments: test_a_rebased_power_of_two_maximum_...)
+        inside = (np.uint64(3 << 9) + rng.choice(512, 100, replace=False).astype(np.uint64))  # one segment holds all, seven are empty
+        low = rng.choice(1024, 46, replace=False).astype(np.uint64)  # 46 ids -> k = 2, all of them in segment 0
+        return 16, 12, [inside, low, np.zeros(0, np.uint64), np.array([4095], np.uint64)]
+    if name.startswith("bits"):  # B = 10 .. 20 at T = 16, the ends of the universe present
+        B = int(name[4:])
+        return 16, B, [distinct(rng, 40, B, True, must=[0, (1 << B) - 1]), np.zeros(0, np.uint64), distinct(rng, 17, B, False),
+                       distinct(rng, 300, B, True)]
+    if name == "large":  # one list of 20 000 ids at T = 1024, B = 20: 32 segments, 20 chunks
+        return 1024, 20, [distinct(rng, 20000, 20, True), distinct(rng, 700, 20, False)]
+    raise KeyError(name)
+
+
+_REF = {}
+
+
+def reference(name, oracle):
+    """model and oracle encode of a family, computed once and shared"""
+    if name not in _REF:
+        T, B, lists = family(name)
+        off, ids = csr(lists)
+        model = sr.split(off, ids, T, B)
+        encs = sr.encode_segments(model, oracle)
+        _REF[name] = dict(T=T, B=B, off=off, ids=ids, model=model, encs=encs, dec=sr.decode_order(model, encs),
+                          perm=sr.compose_perm(model, sr.inner_perm(model, encs)))
+    return _REF[name]
+
+
+def check_inner(inner, encs):
+    """sizes, precisions, heads, word counts, draws and every exported word equal the oracle's encode of the model's segments"""
+    info = inner.info()
+    assert inner.nlist == len(encs)
+    want_words = np.concatenate([e["words"] for e in encs if e is not None] + [np.zeros(0, np.uint32)])
+    for i, e in enumerate(encs):
+        if e is None:
+            assert info["sizes"][i] == 0 and info["nwords"][i] == 0, i
+            continue
+        got = tuple(int(info[k][i]) for k in KEYS)
+        assert got == (e["n"], e["precision"], e["head"], e["words"].size, e["mt_draws"]), (i, got)
+    assert np.array_equal(inner.all_words(), want_words), "stack words"
+    return info
+
+
+def export(obj):
+    inner = obj.inner
+    info = inner.info()
+    sf, sh = obj.seg_info()
+    return [info[k] for k in KEYS] + [inner.all_words(), sf, sh, np.array([obj.seg_ids, obj.universe_bits, obj.nlist, obj.ntotal, obj.compressed_bytes])]
+
+
+def check_object(obj, ref, perm=True):
+    model, encs, off, ids = ref["model"], ref["encs"], ref["off"], ref["ids"]
+    torch = _torch()
+    nlist = off.size - 1
+    assert (obj.nlist, obj.ntotal, obj.seg_ids, obj.universe_bits) == (nlist, ids.size, ref["T"], ref["B"])
+    sf, sh = obj.seg_info()
+    assert np.array_equal(sf, model["seg_first"]) and np.array_equal(sh, model["shift"]), "the map"
+    check_inner(obj.inner, encs)
+    assert obj.compressed_bytes == sr.compressed_bytes(model, encs) == obj.inner.compressed_bytes + 4 * sum(
+        int(sf[l + 1] - sf[l]) for l in range(nlist) if sf[l + 1] - sf[l] > 1)
+    assert np.array_equal(obj.offsets, off)
+    dec = obj.decode_all().cpu().numpy().view(np.uint64)
+    assert np.array_equal(dec, ref["dec"]), "decode_all: per segment the oracle's sampling order plus base"
+    if perm:
+        p = obj.perm()
+        assert np.array_equal(p, ref["perm"])
+        start = np.repeat(off[:-1].astype(np.int64), np.diff(off.astype(np.int64)))
+        assert np.array_equal(ids[start + p], dec), "ids_in[perm] == decode_all"
+    # decode_lists: subsets with repeated lists, empty lists among them
+    rng = np.random.default_rng(nlist)
+    for req in ([], list(range(nlist)), list(rng.integers(0, nlist, 7)) + [nlist - 1, 0, 0]):
+        got, ro = obj.decode_lists(np.asarray(req, np.uint64))
+        want = [ref["dec"][int(off[l]): int(off[l + 1])] for l in req]
+        assert np.array_equal(got.cpu().numpy().view(np.uint64), np.concatenate(want + [np.zeros(0, np.uint64)])), req
+        assert np.array_equal(ro, np.concatenate([[0], np.cumsum([w.size for w in want])]).astype(np.uint64))
+    # translate_labels: every position of every list, negative labels, invalid ones (list >= nlist, offset >= size), in place
+    lists_of = np.repeat(np.arange(nlist, dtype=np.int64), np.diff(off.astype(np.int64)))
+    offs_of = np.arange(ids.size, dtype=np.int64) - off[:-1].astype(np.int64)[lists_of]
+    good = lists_of << 32 | offs_of
+    bad = np.array([nlist << 32, (nlist + 5) << 32 | 3] + [l << 32 | int(off[l + 1] - off[l]) for l in range(nlist)] + [2 ** 62], np.int64)
+    neg = np.array([-1, -7, -(2 ** 40)], np.int64)
+    labels = np.concatenate([neg[:1], good, bad, neg[1:], good[::3]])
+    order = rng.permutation(labels.size)
+    want = np.concatenate([[-1], ref["dec"].view(np.int64), np.full(bad.size, -1), [-1, -1], ref["dec"].view(np.int64)[::3]])
+    d_lab = torch.from_numpy(labels[order]).cuda()
+    invalid = torch.zeros(1, dtype=torch.int64, device="cuda")
+    out = obj.translate_labels(d_lab, invalid=invalid)
+    assert np.array_equal(out.cpu().numpy(), want[order]) and int(invalid.item()) == bad.size
+    assert np.array_equal(d_lab.cpu().numpy(), labels[order]), "the labels are left alone"
+    same = obj.translate_labels(d_lab, out=d_lab, invalid=invalid)
+    assert same is d_lab and np.array_equal(d_lab.cpu().numpy(), want[order]) and int(invalid.item()) == 2 * bad.size, "in place"
+    # decode_gather: labels built on the device
+    if ids.size:
+        uniq = np.unique(lists_of)
+        pick = rng.integers(0, ids.size, 50)
+        slot = np.searchsorted(uniq, lists_of[pick])
+        assert np.array_equal(obj.decode_gather(uniq, slot, offs_of[pick]), ref["dec"].view(np.int64)[pick])
+    return dec
+
+
+MAIN = ["sizes16-asc", "sizes16-shuf", "sizes64-asc", "sizes64-shuf", "seam-asc", "seam-shuf", "skew"]
+
+
+def test_the_families_are_what_the_cases_count_on(oracle):
+    r = reference("skew", oracle)
+    m, encs = r["model"], r["encs"]
+    assert m["k"].tolist() == [3, 2, 0, 0]
+    assert [e is None for e in encs[:8]] == [True, True, True, False, True, True, True, True], "the skew case: other segments empty"
+    sm = reference("seam-shuf", oracle)["model"]
+    assert sm["k"].tolist() == [4, 0, 4, 5, 0, 6]
+    lg = reference("large", oracle)["model"]
+    assert int(lg["k"][0]) == 5 and len(sr.chunk_table(lg["offsets"], 1024, 20)[0]) == 21
+    b = reference("bits10", oracle)
+    assert int(b["ids"].max()) == 1023 and int(b["ids"][:40].min()) == 0
+
+
+def test_a_rebased_power_of_two_maximum_and_a_lone_zero(oracle):
+    """T = 16, B = 12, 100 ids whose segments are built by hand: k = 3, shift 9"""
+    rng = np.random.default_rng(5)
+    seg = lambda s, vals: np.uint64(s << 9) + np.asarray(vals, np.uint64)
+    li = np.concatenate([seg(0, rng.choice(512, 30, replace=False)), seg(2, [1, 3, 64]), seg(5, [0]), seg(6, rng.choice(512, 64, replace=False)),
+                         seg(7, [256, 511])])
+    assert li.size == 100
+    off, ids = csr([rng.permutation(li)])
+    model = sr.split(off, ids, 16, 12)
+    encs = sr.encode_segments(model, oracle)
+    assert encs[2]["precision"] == 7 and int(sr.segment(model, 2).max()) == 64, "a power-of-two maximum: VIDC_PREC_REFERENCE would lose it"
+    assert encs[5]["precision"] == 0 and encs[5]["n"] == 1 and encs[1] is None and encs[3] is None
+    obj = _cls().encode(off, dev(ids), seg_ids=16, universe_bits=12, want_perm=True)
+    ref = dict(T=16, B=12, off=off, ids=ids, model=model, encs=encs, dec=sr.decode_order(model, encs),
+               perm=sr.compose_perm(model, sr.inner_perm(model, encs)))
+    dec = check_object(obj, ref)
+    assert np.array_equal(np.sort(dec), np.sort(ids)), "lossless"
+
+
+@pytest.mark.parametrize("hook", [None, *HOOKS])
+@pytest.mark.parametrize("name", MAIN)
+def test_encode_and_every_request(oracle, monkeypatch, name, hook):
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+    ref = reference(name, oracle)
+    if hook:
+        monkeypatch.setenv(hook, "1")
+    obj = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=ref["T"], universe_bits=ref["B"], want_perm=True)
+    check_object(obj, ref)
+
+
+@pytest.mark.parametrize("B", range(10, 21))
+def test_universe_bits_10_to_20(oracle, B):
+    ref = reference(f"bits{B}", oracle)
+    # universe_bits = None: found on the device -- the family holds 2^B - 1, so it is B
+    obj = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=16, want_perm=True)
+    check_object(obj, ref)
+
+
+@pytest.mark.parametrize("hook", [None, *HOOKS])
+def test_one_list_of_20000_ids(oracle, monkeypatch, hook):
+    for h in HOOKS:
+        monkeypatch.delenv(h, raising=False)
+    ref = reference("large", oracle)
+    if hook:
+        monkeypatch.setenv(hook, "1")
+    obj = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=1024, universe_bits=20, want_perm=True)
+    sf, _ = obj.seg_info()
+    assert sf.tolist() == [0, 32, 33]
+    check_object(obj, ref)
+
+
+def test_device_offsets_no_perm_and_the_default_seg_ids(oracle):
+    from vector_db_id_compression_amd import _lib
+
+    ref = reference("seam-shuf", oracle)
+    d_off = _torch().from_numpy(ref["off"].view(np.int64)).cuda()
+    obj = _cls().encode(d_off, dev(ref["ids"]), seg_ids=64, universe_bits=14)
+    check_object(obj, ref, perm=False)
+    with pytest.raises(_lib.VidcError):
+        obj.perm()
+    host = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=64, universe_bits=14, want_perm=True)
+    for a, b in zip(export(obj), export(host)):
+        assert np.array_equal(a, b)
+    # seg_ids = None: VIDC_ROCSEG_DEFAULT_IDS
+    dflt = _cls().encode(ref["off"], dev(ref["ids"]))
+    assert dflt.seg_ids == _lib.VIDC_ROCSEG_DEFAULT_IDS == sr.DEFAULT_IDS and dflt.universe_bits == 14
+    want_k = [sr.seg_k(int(n), dflt.seg_ids, 14) for n in np.diff(ref["off"].astype(np.int64))]
+    assert np.diff(dflt.seg_info()[0].astype(np.int64)).tolist() == [1 << k for k in want_k]
+    assert np.array_equal(np.sort(dflt.decode_all().cpu().numpy().view(np.uint64)), np.sort(ref["ids"]))
+    empty = _cls().encode(np.array([0, 0, 0], np.uint64), None, seg_ids=16, want_perm=True)
+    assert (empty.nlist, empty.ntotal, empty.compressed_bytes, empty.universe_bits) == (2, 0, 0, 1) and empty.decode_all().numel() == 0
+
+
+def test_save_load_and_wrap(oracle, tmp_path):
+    from vector_db_id_compression_amd import _lib, persist
+    from vector_db_id_compression_amd.codecs import RocLists
+
+    ref = reference("sizes16-shuf", oracle)
+    obj = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=16, universe_bits=10, want_perm=True)
+    want = export(obj)
+    path = persist.save(obj, str(tmp_path / "seg"))
+    back = persist.load(path)
+    assert isinstance(back, _cls())
+    for a, b in zip(export(back), want):
+        assert np.array_equal(a, b)
+    check_object(back, ref, perm=False)
+    back2 = _cls().load(path)
+    assert np.array_equal(back2.decode_all().cpu().numpy().view(np.uint64), ref["dec"])
+    # wrap: damaged maps are refused and leave the inner object usable
+    inner, info = obj.inner, obj.inner.info()
+    sf, sh = obj.seg_info()
+    imp = RocLists.from_streams(inner.offsets, info["precision"], info["heads"], info["nwords"], inner.all_words(), info["mt_draws"])
+    split = int(np.flatnonzero(np.diff(sf.astype(np.int64)) > 1)[0])
+    damaged = []
+    d = sf.copy(); d[-1] += 1; damaged.append((d, sh))
+    d = sf.copy(); d[split + 1:] += 1; damaged.append((d, sh))             # a segment count that is no power of two
+    d = sh.copy(); d[split] -= 1; damaged.append((sf, d))                   # the shift says twice as many segments
+    d = sh.copy(); d[split] += 1; damaged.append((sf, d))
+    d = sf.copy(); d[1] = d[0]; damaged.append((d, sh))
+    for bad_sf, bad_sh in damaged:
+        with pytest.raises(_lib.VidcError, match="status -1"):
+            _cls().wrap(imp, bad_sf, bad_sh, 16, 10)
+        assert imp.h is not None
+    # an inner precision above its shift: a universe of 9 bits with every shift one less keeps the counts consistent
+    with pytest.raises(_lib.VidcError, match="status -1"):
+        _cls().wrap(imp, sf, (sh - 1).astype(np.uint8), 16, 9)
+    assert np.array_equal(imp.decode_all().cpu().numpy().view(np.uint64), np.concatenate([e["order"] for e in ref["encs"] if e is not None])), \
+        "the inner object still decodes after the refusals"
+    wrapped = _cls().wrap(imp, sf, sh, 16, 10)
+    assert imp.h is None, "ownership moved"
+    for a, b in zip(export(wrapped), want):
+        assert np.array_equal(a, b)
+    assert np.array_equal(wrapped.decode_all().cpu().numpy().view(np.uint64), ref["dec"])
+
+
+def test_encode_refusals():
+    from vector_db_id_compression_amd import _lib
+
+    off, ids = csr([np.array([5, 1024, 7], np.uint64)])
+    with pytest.raises(_lib.VidcError, match="status -4"):
+        _cls().encode(off, dev(ids), seg_ids=16, universe_bits=10)  # an id >= 2^B, list not split
+    li = np.arange(40, dtype=np.uint64)
+    li[33] = 1 << 12
+    with pytest.raises(_lib.VidcError, match="status -4"):
+        _cls().encode(np.array([0, 40], np.uint64), dev(li), seg_ids=16, universe_bits=12)  # ... and in a split list
+    n = 16 * 1024 + 1
+    with pytest.raises(_lib.VidcError, match="status -4"):
+        _cls().encode(np.array([0, n], np.uint64), dev(np.arange(n, dtype=np.uint64)), seg_ids=16, universe_bits=20)
+    with pytest.raises(_lib.VidcError, match="status -4"):
+        _cls().encode(np.array([0, 2], np.uint64), dev(np.array([1, 1 << 31], np.uint64)), seg_ids=16)  # universe_bits from the ids: > 31
+    # the context stays usable
+    ok = _cls().encode(np.array([0, 40], np.uint64), dev(np.arange(40, dtype=np.uint64)), seg_ids=16, universe_bits=12)
+    assert np.array_equal(np.sort(ok.decode_all().cpu().numpy()), np.arange(40))
+
+
+def test_through_the_ivf_harness():
+    """a small IVFIndex whose lists (about 500 vectors each) split at T = 64: the segmented container returns the (D, I) of the
+    FenwickTree container from search_defer_id_decoding, on both of its paths"""
+    from vector_db_id_compression_amd import custom_invlists as ci
+    from vector_db_id_compression_amd.ivf import IVFIndex
+
+    rng = np.random.default_rng(9)
+    xb = rng.standard_normal((4000, 8)).astype(np.float32)
+    xq = rng.standard_normal((20, 8)).astype(np.float32)
+    index = IVFIndex(8, 8, "Flat")
+    index.train(xb)
+    index.add(xb)
+    index.nprobe = 3
+    index.parallel_mode = 3
+    plain = index.invlists
+    fen = ci.CompressedIDInvertedListsFenwickTree(plain)
+    seg = ci.CompressedIDInvertedListsROCSegmented(plain, seg_ids=64)
+    sf, _ = seg._c.seg_info()
+    assert int(np.diff(sf.astype(np.int64)).max()) >= 4, "a list long enough to split"
+    assert seg.compressed_ids_size_in_bytes == seg._c.compressed_bytes and seg.ntotal == 4000
+    for l in (0, 5):
+        assert np.array_equal(np.sort(seg.get_ids(l)), np.sort(fen.get_ids(l)))
+    out = {}
+    for name, il in (("fenwick", fen), ("segmented", seg)):
+        index.replace_invlists(il, False)
+        out[name] = [index.search_defer_id_decoding(xq, 10, decode_1by1=one) for one in (False, True)]
+    for (Df, If), (Ds, Is) in zip(out["fenwick"], out["segmented"]):
+        np.testing.assert_array_equal(Is, If)
+        np.testing.assert_array_equal(Ds, Df)
+    with pytest.raises(RuntimeError, match="no append"):
+        index.add(xb[:2])

@@ -20,6 +20,9 @@ VIDC_EF_WANT_PERM = 1
 VIDC_ROC_MAX_LIST = 262144
 VIDC_KIND_PACKED, VIDC_KIND_EF, VIDC_KIND_ROC, VIDC_KIND_WT = 0, 1, 2, 3
 VIDC_SHARDS_MAX = 8
+VIDC_ROCSEG_MAX_SEGS = 1024
+VIDC_ROCSEG_DEFAULT_IDS = 1024
+VIDC_PHASE_ROCSEG_PARTITION = 7
 
 _lib = None
 
@@ -178,6 +181,23 @@ def _declare(lib):
     f("vidc_sharded_loads", C.c_int, _vp, _vp)
     f("vidc_remove_sharded_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp, _vp)
     f("vidc_rebalance_sharded", C.c_int, _vp, _vp, _u32, _P(_vp), _vp)
+    # segmented ROC lists (parallel chains inside a list)
+    f("vidc_rocseg_encode", C.c_int, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _P(_vp))
+    f("vidc_rocseg_encode_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _P(_vp))
+    f("vidc_rocseg_destroy", None, _vp)
+    f("vidc_rocseg_nlist", _u64, _vp)
+    f("vidc_rocseg_ntotal", _u64, _vp)
+    f("vidc_rocseg_compressed_bytes", _u64, _vp)
+    f("vidc_rocseg_seg_ids", _u32, _vp)
+    f("vidc_rocseg_universe_bits", _u32, _vp)
+    f("vidc_rocseg_inner", _vp, _vp)
+    f("vidc_rocseg_seg_info", C.c_int, _vp, _vp, _vp)
+    f("vidc_rocseg_wrap", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _u32, _P(_vp))
+    f("vidc_rocseg_decode_all", C.c_int, _vp, _vp, _vp)
+    f("vidc_rocseg_decode_lists", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_rocseg_translate_labels_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp)
+    f("vidc_rocseg_perm", C.c_int, _vp, _vp, _vp)
+    f("vidc_rocseg_last_decode_handed_back", _u64, _vp)
 
 
 #: every symbol include/vidc.h declares (checked by the CPU test-suite against the built library)
@@ -210,6 +230,10 @@ EXPORTED_SYMBOLS = [
     "vidc_shards_decode_gather", "vidc_shards_perm", "vidc_sharded_append_dev", "vidc_sharded_loads", "vidc_remove_sharded_dev",
     "vidc_roc_regroup", "vidc_rebalance_sharded",
     "vidc_compact_update_rows_dev", "vidc_ef_update_rows_dev", "vidc_roc_update_rows_dev",
+    "vidc_rocseg_encode", "vidc_rocseg_encode_dev", "vidc_rocseg_destroy", "vidc_rocseg_nlist", "vidc_rocseg_ntotal",
+    "vidc_rocseg_compressed_bytes", "vidc_rocseg_seg_ids", "vidc_rocseg_universe_bits", "vidc_rocseg_inner", "vidc_rocseg_seg_info",
+    "vidc_rocseg_wrap", "vidc_rocseg_decode_all", "vidc_rocseg_decode_lists", "vidc_rocseg_translate_labels_dev", "vidc_rocseg_perm",
+    "vidc_rocseg_last_decode_handed_back",
 ]
 
 

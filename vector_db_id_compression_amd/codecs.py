@@ -857,3 +857,169 @@ class WaveletTreeLists(_ListCodec):
 
     def select(self, list_nos, offs):
         return self._get("select", list_nos, offs)
+
+
+class _BorrowedRoc(RocLists):
+    """The inner object of a RocSegLists: a RocLists view of a handle its owner destroys (the owner is kept alive meanwhile)."""
+
+    def __init__(self, handle, ctx, owner):
+        super().__init__(handle, ctx, None)
+        self._owner = owner
+
+    def __del__(self):
+        self.h = None
+
+
+def _check_seg_params(seg_ids, universe_bits):
+    """seg_ids: None (the library's default) or a power of two in [16, 65536]; universe_bits: None (from the ids) or 1 .. 31 -> the
+    C call's two integers (0 = the default).  Real exceptions: a bad value must not reach the library as a 0."""
+    T = 0 if seg_ids is None else int(seg_ids)
+    B = 0 if universe_bits is None else int(universe_bits)
+    if seg_ids is not None and (T < 16 or T > 65536 or T & (T - 1)):
+        raise ValueError(f"seg_ids must be a power of two in [16, 65536], not {seg_ids}")
+    if universe_bits is not None and not 1 <= B <= 31:
+        raise ValueError(f"universe_bits must be in 1 .. 31, not {universe_bits}")
+    return T, B
+
+
+class RocSegLists(_ListCodec):
+    """Segmented ROC lists (vidc_rocseg): every list longer than seg_ids is cut by value range into 2^k segments, each an independent
+    ANS chain of the inner RocLists (`inner`, encoded with VIDC_PREC_EXACT).  Opt-in and not reference-identical; append, remove,
+    regroup and sharding are out of scope."""
+
+    _prefix = "vidc_rocseg"
+
+    @property
+    def offsets(self):
+        """CSR offsets of the decoded output: the inner object's offsets at the first segment of every list"""
+        if self._offsets is None:
+            seg_first, _ = self.seg_info()
+            self._offsets = np.ascontiguousarray(self.inner.offsets[seg_first.astype(np.int64)], dtype=np.uint64)
+        return self._offsets
+
+    @classmethod
+    def encode(cls, offsets, ids, seg_ids=None, universe_bits=None, want_perm=False, ctx=None):
+        """offsets: host (numpy / list) or an int64 / uint64 CUDA tensor; ids: int64 / uint64 CUDA tensor (numpy arrays are uploaded)"""
+        T, B = _check_seg_params(seg_ids, universe_bits)
+        ctx = _lib.default_context() if ctx is None else ctx
+        flags = _lib.VIDC_ROC_WANT_PERM if want_perm else 0
+        h = C.c_void_p()
+        d_off = _cuda_offsets(offsets, ctx)
+        if d_off is not None:
+            d_ids = _dev_ids_dev(ids, d_off)
+            check(lib().vidc_rocseg_encode_dev(ctx.h, d_off.numel() - 1, ptr(d_off), d_ids.numel(), ptr(d_ids) if d_ids.numel() else None,
+                                               T, B, flags, C.byref(h)))
+            return cls(h, ctx, None)
+        off = _as_offsets(offsets)
+        if off[0] != 0:
+            raise ValueError("offsets must start at 0")
+        d_ids = _dev_ids(ids, int(off[-1])) if off[-1] else None
+        check(lib().vidc_rocseg_encode(ctx.h, off.size - 1, ptr(off), ptr(d_ids), T, B, flags, C.byref(h)))
+        return cls(h, ctx, off)
+
+    @classmethod
+    def wrap(cls, inner, seg_first, shift, seg_ids, universe_bits):
+        """vidc_rocseg_wrap: a segmented object over an imported RocLists and an untrusted map.  On success `inner` is consumed (its
+        handle moves into the new object); on a VidcError it stays usable."""
+        T, B = _check_seg_params(seg_ids, universe_bits)
+        sf = np.ascontiguousarray(seg_first, dtype=np.uint64)
+        sh = np.ascontiguousarray(shift, dtype=np.uint8)
+        if sf.ndim != 1 or sf.size != sh.size + 1:
+            raise ValueError("seg_first needs one entry more than shift")
+        h = C.c_void_p()
+        check(lib().vidc_rocseg_wrap(inner.ctx.h, inner.h, sh.size, ptr(sf), ptr(sh) if sh.size else None, T, B, C.byref(h)))
+        inner.h = None  # (owned by the new object now)
+        return cls(h, inner.ctx, None)
+
+    # -- flat image: the inner object's ROC export plus the map
+    def save(self, path):
+        inner = self.inner
+        info = inner.info()
+        seg_first, shift = self.seg_info()
+        np.savez(path, kind=np.array("rocseg"), offsets=inner.offsets, precision=info["precision"], heads=info["heads"], nwords=info["nwords"],
+                 mt_draws=info["mt_draws"], words=inner.all_words(), seg_first=seg_first, shift=shift, seg_ids=np.int64(self.seg_ids),
+                 universe_bits=np.int64(self.universe_bits))
+
+    @classmethod
+    def load(cls, path, ctx=None):
+        with np.load(path) as z:
+            inner = RocLists.from_streams(z["offsets"], z["precision"], z["heads"], z["nwords"], z["words"], z["mt_draws"], ctx=ctx)
+            return cls.wrap(inner, z["seg_first"], z["shift"], int(z["seg_ids"]), int(z["universe_bits"]))
+
+    # -- properties
+    @property
+    def nlist(self):
+        return int(lib().vidc_rocseg_nlist(self.h))
+
+    @property
+    def ntotal(self):
+        return int(lib().vidc_rocseg_ntotal(self.h))
+
+    @property
+    def compressed_bytes(self):
+        """the inner object's bytes + 4 per segment of every list that is split"""
+        return int(lib().vidc_rocseg_compressed_bytes(self.h))
+
+    @property
+    def seg_ids(self):
+        return int(lib().vidc_rocseg_seg_ids(self.h))
+
+    @property
+    def universe_bits(self):
+        return int(lib().vidc_rocseg_universe_bits(self.h))
+
+    @property
+    def inner(self):
+        """the inner RocLists (borrowed): info, words, all_words serve parity checks and saving"""
+        return _BorrowedRoc(C.c_void_p(lib().vidc_rocseg_inner(self.h)), self.ctx, self)
+
+    def seg_info(self):
+        """-> (seg_first uint64[nlist + 1], shift uint8[nlist]): the first inner list of every list and its shift"""
+        n = self.nlist
+        seg_first = np.zeros(n + 1, np.uint64)
+        shift = np.zeros(max(n, 1), np.uint8)
+        check(lib().vidc_rocseg_seg_info(self.h, ptr(seg_first), ptr(shift)))
+        return seg_first, shift[:n]
+
+    def info(self):
+        """the map, the parameters and the inner object's per-segment metadata"""
+        seg_first, shift = self.seg_info()
+        return dict(seg_first=seg_first, shift=shift, seg_ids=self.seg_ids, universe_bits=self.universe_bits, inner=self.inner.info())
+
+    def perm(self):
+        """output position -> input position within the list (objects encoded with want_perm)"""
+        p = np.zeros(max(self.ntotal, 1), np.uint32)
+        check(lib().vidc_rocseg_perm(self.ctx.h, self.h, ptr(p)))
+        return p[: self.ntotal]
+
+    # -- decode (decode_all, decode_lists: _ListCodec)
+    def translate_labels(self, labels, out=None, invalid=None):
+        """Faiss labels (int64 CUDA tensor, list_no << 32 | offset) -> ids, on the device (vidc_rocseg_translate_labels_dev): only the
+        touched SEGMENTS decode.  Negative labels and labels outside the object give -1; the latter are added to `invalid`.  `out` may
+        be `labels`."""
+        return _translate_labels(lib().vidc_rocseg_translate_labels_dev, self, labels, out, invalid)
+
+    def decode_gather(self, list_nos, item_slot, item_off):
+        """ids[i] = list_nos[item_slot[i]][item_off[i]] -> numpy int64: the labels are built on the device and go through
+        translate_labels; 8 bytes per result come back.  An item outside its list is a VidcError, as in the other containers."""
+        torch = _torch()
+        ln = np.ascontiguousarray(list_nos, dtype=np.int64)
+        sl = np.ascontiguousarray(item_slot, dtype=np.int64)
+        of = np.ascontiguousarray(item_off, dtype=np.int64)
+        if sl.size != of.size:
+            raise ValueError("item_slot and item_off must have one entry per item")
+        if not sl.size:
+            return np.zeros(0, np.int64)
+        if ln.size == 0 or int(sl.min()) < 0 or int(sl.max()) >= ln.size or int(of.min()) < 0 or int(of.max()) >= 1 << 32:
+            raise _lib.VidcError("decode_gather: an item names no list of the request")
+        d_ln = torch.from_numpy(ln).cuda()
+        labels = (d_ln[torch.from_numpy(sl).cuda()] << 32) | torch.from_numpy(of).cuda()
+        invalid = torch.zeros(1, dtype=torch.int64, device=labels.device)
+        ids = self.translate_labels(labels, out=labels, invalid=invalid)
+        if int(invalid.item()):
+            raise _lib.VidcError(f"decode_gather: {int(invalid.item())} items are outside their list")
+        return ids.cpu().numpy()
+
+    @property
+    def last_decode_handed_back(self):
+        return int(lib().vidc_rocseg_last_decode_handed_back(self.h))

@@ -13,7 +13,7 @@ custom_invlists_impl.cpp:508-525) and `get_single_ids(list_nos, offsets)` (:466-
 import numpy as np
 
 from . import _lib
-from .codecs import EfLists, PackedLists, RocLists, WaveletTreeLists
+from .codecs import EfLists, PackedLists, RocLists, RocSegLists, WaveletTreeLists
 from .invlists import to_csr
 
 
@@ -337,6 +337,45 @@ class CompressedIDInvertedListsWaveletTree(InvertedListsArrayCodes):
 
     def get_single_ids(self, list_nos, offsets):
         return self._c.select(list_nos, offsets)
+
+
+class CompressedIDInvertedListsROCSegmented(InvertedListsArrayCodes):
+    """ROC with parallel chains inside a list (vidc_rocseg, include/vidc.h): the surface of the FenwickTree container over a RocSegLists.
+    Long lists are cut by value range into segments of about `seg_ids` ids (None: the library's default), so a deferred search decodes
+    only the segments its labels touch.  Not a reference container (it is not in AVAILABLE_COMPRESSED_IVFS): the streams are not the
+    reference's, and add_batch / remove_batch are out of scope."""
+
+    def __init__(self, il, seg_ids=None):
+        super().__init__(il)
+        self.seg_ids = seg_ids
+        self._c = RocSegLists.encode(self._offsets, self._ids_host, seg_ids=seg_ids, want_perm=self.code_size > 0)
+        self.overhead_in_bytes = 0
+        self._store_codes(self._c.perm() if self.code_size else None)  # codes follow the decode order, as in the FenwickTree container
+        self._refresh_sizes()
+        self._ids_host = None
+
+    def _refresh_sizes(self):
+        self.id_symbol_precision = self._c.inner.info()["precision"].astype(np.uint64)  # per SEGMENT
+        self.compressed_ids_size_in_bytes = self._c.compressed_bytes  # the inner object's + 4 bytes per segment of a split list
+        nonempty = int(np.count_nonzero(self._offsets[1:] > self._offsets[:-1]))
+        self.codes_size_in_bytes = nonempty * self.ntotal * self.code_size
+
+    def add_batch(self, list_nos, ids, codes=None):
+        raise RuntimeError("not implemented: segmented ROC lists have no append (re-encode, or use the FenwickTree container)")
+
+    def remove_batch(self, list_nos, ids):
+        raise RuntimeError("not implemented: segmented ROC lists have no remove (re-encode, or use the FenwickTree container)")
+
+    def get_ids_all(self):
+        return self._c.decode_all()
+
+    def decode_lists(self, list_nos):
+        return self._c.decode_lists(np.asarray(list_nos, dtype=np.uint64))
+
+    def get_single_ids(self, list_nos, offsets):
+        ln = np.asarray(list_nos, dtype=np.uint64)
+        uniq, inv = np.unique(ln, return_inverse=True)
+        return self._c.decode_gather(uniq, inv, offsets)
 
 
 AVAILABLE_COMPRESSED_IVFS = {  # bench_invlists.py:19-25

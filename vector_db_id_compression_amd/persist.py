@@ -3,7 +3,8 @@
 A wavelet tree (both wt_types) and compact graph rows are stored as the arrays of vidc_wt_export_all / vidc_compact_export_all plus
 their geometry and a `kind` entry; the derived tables of a tree (rank directory, samples, node ranks) are not stored: vidc_wt_import
 rebuilds them on the GPU and checks the image before any query kernel walks it (include/vidc.h).  RocLists, EfLists and PackedLists
-keep their own save / load and file layout; `load` recognises their files by their keys.
+keep their own save / load and file layout; `load` recognises their files by their keys.  RocSegLists writes kind "rocseg": its inner
+object's ROC export plus the segment map, loaded through vidc_rocseg_wrap, which checks the map.
 """
 import ctypes as C
 
@@ -11,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .codecs import CompactRows, EfLists, PackedLists, RocLists, WaveletTreeLists, _as_offsets
+from .codecs import CompactRows, EfLists, PackedLists, RocLists, RocSegLists, WaveletTreeLists, _as_offsets
 
 
 def _npz_path(path):
@@ -73,7 +74,7 @@ def save(obj, path):
                  offs=im["offs"], off_bits=im["off_bits"])
     elif isinstance(obj, CompactRows):
         np.savez(path, kind=np.array("compact"), N=np.int64(obj.N), K=np.int64(obj.K), data=compact_image(obj))
-    elif isinstance(obj, (RocLists, EfLists, PackedLists)):
+    elif isinstance(obj, (RocLists, RocSegLists, EfLists, PackedLists)):
         obj.save(path)
     else:
         raise TypeError(f"persist.save: {type(obj).__name__} has no image")
@@ -90,6 +91,8 @@ def load(path, ctx=None):
                 return wt_from_image(z["offsets"], int(z["wt_type"]), z["wt_bits"], z["cls"], z["offs"], z["off_bits"], ctx)
             if kind == "compact":
                 return compact_from_image(int(z["N"]), int(z["K"]), z["data"], ctx)
+            if kind == "rocseg":
+                return RocSegLists.load(path, ctx)
             raise ValueError(f"{path}: unknown image kind {kind!r}")
     if "heads" in keys:
         return RocLists.load(path, ctx)
