@@ -2,6 +2,8 @@
 // k_roc_encode_u2 with dense 16-id blocks: identical head / words / order, ns per step of each (hipEvents, five repeats: min and
 // max); then the stream through k_roc_decode_u (round 1), k_roc_decode_u2 and, for ub 20, k_roc_decode_u2 on word-granular rows
 // (U2DecWord), five repeats each as well.  With -DU2_PROF the decode section table is the LAST decode arm's.
+// -DU2_DEC_STEP=0..3 selects the form of the k_roc_decode_u2 step (roc_u2.h: bit 0 rank at the bit's lane, bit 1 one-branch pops;
+// 0 is the step before both): one binary per value, run in one session, is how a candidate is measured against the step without it.
 // usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: section tables of the LAST encode arm run and of the k_roc_decode_u2 step;
 // -DU2_PROF2: generic steps, entries into the asm loop and bits in the bitmap of the last k_roc_decode_u2 launch)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I vector_db_id_compression_amd/csrc tools/chain_u2.hip -o /tmp/chain_u2
@@ -129,7 +131,8 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
         dsame = dd == n && dst[0] == 0 && dst[1] == 0 && dend[0] == dend[1];
         printf("                         DECODE old %.1f ns/step, new %.1f ns/step; status %u/%u end state %u/%u first diff old/new at %zu, new/encoder order at %zu -> %s\n",
                dms[0] * 1e6 / n, dms[1] * 1e6 / n, dst[0], dst[1], dend[0], dend[1], dd, od, dsame ? "IDENTICAL" : "MISMATCH");
-        printf("    five repeats, ns/step min..max: old %.1f..%.1f, u2 %.1f..%.1f\n", dms[0] * 1e6 / n, dms_max[0] * 1e6 / n, dms[1] * 1e6 / n, dms_max[1] * 1e6 / n);
+        printf("    five repeats, ns/step min..max: old %.1f..%.1f, u2 %.1f..%.1f   (U2_DEC_STEP=%d: rank at the bit's lane %s, one-branch pops %s)\n", dms[0] * 1e6 / n,
+               dms_max[0] * 1e6 / n, dms[1] * 1e6 / n, dms_max[1] * 1e6 / n, U2_DEC_STEP, (U2_DEC_STEP & 1) ? "on" : "off", (U2_DEC_STEP & 2) ? "on" : "off");
         if (ndarm == 3) {
             size_t wd = 0; while (wd < n && outv[0][wd] == outv[2][wd]) wd++;
             const bool wsame = wd == n && dst[2] == 0 && dend[2] == dend[0];
@@ -141,9 +144,9 @@ int run(uint32_t n, uint32_t seed, uint32_t P) {
 #ifdef U2_PROF
         {   // the decode step's sections (the last launch of k_roc_decode_u2 left them in the slots array)
             uint32_t dp[14]; CK(hipMemcpy(dp, d_slots, 56, hipMemcpyDeviceToHost));
-            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", "TOP: two slices, refill tests, pack (9)", "IDX: entry, 2 addresses, 2 ds_read, [g,] dword (7 / 6)",
-                "MID: L1, L2, bfm, m0 (4)", "MID: 2 readlanes, row address, data (2 / 4), ring write (6 / 8)", "MID: renormalise H (4)", "MID: H * nmax, m0 (5)",
-                "(unused)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7)", "RANK: addc E1, readlane (2)", "RANK: address, bit, ring write, ds_or, ds_add (5)", "(unused)",
+            const char *sn[14] = {"branch -> top (+ first probe)", "EMPTY (probe cost)", (U2_DEC_STEP & 2) ? "TOP: head test, two slices, shift, refill, pack (10)" : "TOP: two slices, refill tests, pack (9)", "IDX: entry, 2 addresses, 2 ds_read, [g,] dword (7 / 6)",
+                "MID: L1, L2, [bfm,] m0 (4 / 3)", "MID: 2 readlanes, row address, data (2 / 4), ring write (6 / 8)", "MID: renormalise H (4)", "MID: [lane of the carried word,] H * nmax, m0 (5 / 6)",
+                "(unused)", "RANK: waitcnt, valu incl. L1 cmp (12 / 7 / 5)", "RANK: addc E1, readlane (2)", "RANK: [carried word,] address, bit, ring write, ds_or, ds_add (5 / 6)", "(unused)",
                 "BOT: counters, head', refill test (6) [+ cmp, branch]"};
             double tot = 0, pc = (double)dp[1] / n;
             int np = 0;  // probes the step has (a slot the step does not use stays 0)

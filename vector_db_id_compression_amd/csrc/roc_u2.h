@@ -1112,6 +1112,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //   s61 lo  s62 lq  s64 rank (bucket kernels: below)  s65 tmp  s66:67 mask below b  s68 tmp  s69 t  s70 t_end  s71 limit  s72 tmp
 //   s73 2^p1 - 1  s74 2^p0 - 1  s75 nmax  s76 p0  s77 p1  s85 N0  s86 steps left at lane 0  s87 output index of lane 0
 //   s88:89 output pointer  s94:95 divisor table  s96:97 saved exec  s98 s99 tmp
+//   (k_roc_decode_u2 only, U2_DEC_TOP_P: s41 carried stack word  s42 its lane  s56 31 + p1  s57 s_bfe operand of x_lo  s63 p1 + p0)
 #ifdef U2_PROF  // the decode arm's probes (the encoder's U2P with registers the loop of k_roc_decode_u2 leaves alone: s78..s81; the
                 // bucket kernels, which share some of the probed macros, use those registers: k_roc_decode_b2 refuses a probed build)
 #define U2PD(i) "s_memtime s[78:79]\n s_waitcnt lgkmcnt(0)\n s_sub_u32 s81, s78, s80\n s_mov_b32 s80, s78\n v_add_u32 v" #i ", s81, v" #i "\n"
@@ -1175,7 +1176,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_ashrrev_i32 v58, 31, v58\n" \
     "v_sub_u32 v4, v4, v58\n"                          /* E1 += 1 in lanes below L1 */ U2PD(142)
 // ---- the step of k_roc_decode_u2 (the bucket kernels have their own index / middle / rank macros further down and share
-// U2_DEC_TOP_L, U2_DEC_AFTER_RANK, U2_DEC_BOT_CORE*, U2_DEC_SIDE and U2_DEC_OUTER).  Ordered by the rule the encoder's dense step was
+// U2_DEC_AFTER_RANK, U2_DEC_BOT_CORE*, U2_DEC_OUTER and, for their pops, U2_DEC_TOP_L / U2_DEC_SIDE; the pops of this kernel are
+// U2_DEC_TOP_P below).  Ordered by the rule the encoder's dense step was
 // built on: a scalar instruction issued within ~16 cycles of a vector instruction that wrote an SGPR or VCC (v_readlane, v_cmp,
 // v_addc) waits the window out, so each read-out whose result the scalar unit needs is followed by four vector / LDS instructions
 // (profiles/r21_roc_decode_step.txt and profiles/r27_roc_decode_rows_lds.txt have the section tables and what each change bought).
@@ -1190,7 +1192,11 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //    and 0 elsewhere: no exec write, no VCC, no write-back) behind the ds_or, and the next step's read sees it by the same in-order
 //    argument.  No s_set_gpr_idx bracket and no v_readlane of the row is left in the step.
 //  * rank: E1[L1] rides in on the addend of a v_bcnt and the row element on a v_add3 (a VGPR operand now), so the read-out is the
-//    whole rank and head' is one 64-bit add.
+//    whole rank and head' is one 64-bit add.  The one-word steps (one word per entry, and the word-granular rows below) take the
+//    rank at the bit's lane instead: the word is a broadcast, so v_mbcnt_lo / v_mbcnt_hi (E1[L1] as the addend of the first) leave
+//    the rank of x in lane x & 63 and v_readlane at x reads it: no s_bfm_b64, no v_and (U2_DEC_RANK_1W; three instructions less).
+//  * pops: one test of the head, one shift, a branch-free refill from a carried stack word (U2_DEC_TOP_P: ten instructions and two
+//    for the carried word against nine, but no taken branch in seven steps of eight; profiles/r34_roc_decode_pops_rank.txt).
 //  * counters: the E1 update is v_cmp_lt (L1 < lane) + v_addc_co (+ 0 + carry) inside the rank's vector block, where vector work
 //    follows both; the v_addc takes the wait state in front of the read-out.  Row address and the 0 / 1 data of the ds_add write no
 //    SGPR and fill the window of the two read-outs of U2_DEC_MID_U together with the ring write.
@@ -1198,13 +1204,72 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //    L2 (s_lshl_b64 -2, L2) + v_cndmask with the insertion's address in the freed slot of the window, is 1.2 ns longer with four
 //    words per entry and 2 ns longer with one (profiles/r28_roc_chain_rows_order.txt; with reversed entries the four-word body had
 //    preferred it by 0.4 .. 0.8 ns, profiles/r27_roc_decode_rows_lds.txt).
-//  * 62 instructions per step with four words per entry, 56 with one.  The 20-bit launch runs the one-word step on word-granular
+//  * 65 instructions per step with four words per entry, 56 with one.  The 20-bit launch runs the one-word step on word-granular
 //    rows by default (U2_DEC_*_W below, 58 instructions); the four-word step stays as k_roc_decode_u2<20, false>.
+// ---- build-time forms of the k_roc_decode_u2 step (tools/chain_u2.hip builds one binary per value; the library builds the default):
+//   bit 0  rank at the bit's lane (U2_DEC_RANK_W, U2_DEC_RANK_U_G1): the word was read as a broadcast, so v_mbcnt_lo / v_mbcnt_hi of it
+//          give lane L the number of its bits below L, and lane b = x & 63 holds the wanted rank: no mask of the bits below b
+//          (s_bfm_b64), no v_and of the two halves; E1[L1] rides on the addend of the first v_mbcnt, the read-out is v_readlane at x
+//          (the instruction takes six bits of its lane select).  0: the masked v_bcnt pair and v_readfirstlane.
+//   bit 1  one-branch slice pops (U2_DEC_TOP_P).  0: U2_DEC_TOP_L, the two pops with a refill test and a side path each.
+#ifndef U2_DEC_STEP
+#define U2_DEC_STEP 3
+#endif
+// ---- the two slice pops of the k_roc_decode_u2 step as ONE classified shift (csrc/u2_pops_ref.h is the same in plain C++ and
+// tests/u2_pops_test.cpp checks it against the two-pop sequence of codec.cpp:78-90).  With p1 = clamp(P - 16, 0, 16), p0 = min(P, 16)
+// and head' >= 2^31 (every way into the loop and the exit test of every step see to that):
+//   * a step refills at most once: after a refill the head is at least 2^(63 - p1) and the pops left take at most p0 <= 16 bits;
+//   * which pop refills is a function of head' alone: head' < 2^(31 + p1) slice 1, else head' < 2^(31 + p1 + p0) slice 0, else none.
+// So the common path tests head' once, takes x_hi and x_lo out of the low dword of head' (p1 + p0 <= 32 for every precision),
+// shifts once by p1 + p0 and refills with two s_cselect and the word w that the previous step left in s41: no v_readlane and no
+// branch on the refill.  s_addc_u32 sp, sp, -1 subtracts one exactly when SCC = 0 (refilled).  The slice-1 class leaves for a side
+// path behind the loop, where both pops are unconditional: it refills behind the first and never behind the second.
+//   s41 w = ring word (sp - 1) & 63, loaded behind the index push of the previous step (U2_DEC_W_IDX / U2_DEC_W_LOAD) and by
+//   U2_DEC_ENTRY_U / the re-entry of U2_DEC_OUTER_U (so also behind a generic step, a ring spill or a ring refill of the C++ glue,
+//   which all come back through the entry): nothing else is carried across an exit.   s42 its lane
+//   s56 31 + p1   s57 s_bfe operand of x_lo (p0 << 16 | p1)   s63 p1 + p0
+#define U2_DEC_TOP_P(LA, LB) \
+    U2PD(130) U2PD(131) \
+    "s_lshr_b64 s[98:99], s[58:59], s56\n"            /* SCC = head' >= 2^(31 + p1): slice 1 does not refill */ \
+    "s_cbranch_scc0 " LA "f\n" \
+    "s_and_b32 s46, s58, s73\n"                        /* x_hi */ \
+    "s_bfe_u32 s40, s58, s57\n"                        /* x_lo */ \
+    "s_lshr_b64 s[58:59], s[58:59], s63\n"             /* both pops */ \
+    "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* SCC = head >= 2^31: no refill */ \
+    "s_cselect_b32 s59, s59, s58\n"                    /* refill: head = (head << 32) | w */ \
+    "s_cselect_b32 s58, s58, s41\n" \
+    "s_addc_u32 s60, s60, -1\n"                        /* sp -= 1 if it refilled */ \
+    LB ":\n" \
+    "s_pack_ll_b32_b16 s40, s40, s46\n"                /* x = x_hi : x_lo */ U2PD(132)
+#define U2_DEC_SIDE_P(LA, LB) \
+    LA ":\n"                                           /* head' < 2^(31 + p1): slice 1 refills, slice 0 cannot */ \
+    "s_and_b32 s46, s58, s73\n" \
+    "s_lshr_b64 s[58:59], s[58:59], s77\n" \
+    "s_sub_u32 s60, s60, 1\n" \
+    "s_mov_b32 s59, s58\n" \
+    "s_mov_b32 s58, s41\n" \
+    "s_and_b32 s40, s58, s74\n" \
+    "s_lshr_b64 s[58:59], s[58:59], s76\n" \
+    "s_branch " LB "b\n"
+#if U2_DEC_STEP & 2
+#define U2_DEC_W_IDX "s_sub_u32 s42, s60, 1\n"         /* lane of the word the next pop returns (the read takes six bits of it) */
+#define U2_DEC_W_LOAD "v_readlane_b32 s41, v5, s42\n"
+#else
+#define U2_DEC_W_IDX ""
+#define U2_DEC_W_LOAD ""
+#endif
+#if U2_DEC_STEP & 1
+#define U2_DEC_BFM ""
+#else
+#define U2_DEC_BFM "s_bfm_b64 s[66:67], s40, 0\n"      /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */
+#endif
 #define U2_DEC_INS_ADDR "v_mad_u32_u24 v26, s65, v8, v9\n" /* insertion address: lane 0 the bitmap dword, lane j its strip dword */
-#define U2_DEC_MID_U \
+#define U2_DEC_MID_U U2_DEC_MID_U_T("s_bfm_b64 s[66:67], s40, 0\n")  /* bits below b = x mod 64 (six bits of the width operand are read) */
+#define U2_DEC_MID_U1 U2_DEC_MID_U_T(U2_DEC_BFM)       /* one word per entry */
+#define U2_DEC_MID_U_T(BFM) \
     "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
-    "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 (the instruction reads six bits of its width operand) */ \
+    BFM \
     "s_and_b32 m0, s60, 63\n" U2PD(134) \
     "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
@@ -1216,12 +1281,14 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_cselect_b32 s50, s59, s58\n" \
     "s_cselect_b32 s51, 0, s59\n" \
     "s_addc_u32 s60, s60, 0\n" U2PD(136) \
+    U2_DEC_W_IDX \
     "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
     "s_mul_hi_u32 s53, s50, s75\n" \
     "s_mul_i32 s68, s51, s75\n" \
     "s_add_u32 s53, s53, s68\n" \
     "s_mov_b32 m0, s69\n" U2PD(137)
 #define U2_DEC_RANK_TAIL_U \
+    U2_DEC_W_LOAD                                      /* w of the next step's pops: behind the ring write and the s_addc of U2_DEC_MID_U */ \
     U2_DEC_INS_ADDR \
     "v_lshlrev_b32_e64 v27, s40, 1\n" \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
@@ -1243,21 +1310,32 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes above L1 */ \
     "v_readlane_b32 s64, v37, s47\n" U2PD(140) \
     U2_DEC_RANK_TAIL_U
-#define U2_DEC_RANK_U_G1 \
+#if U2_DEC_STEP & 1
+#define U2_DEC_RANK_1W(T) \
     "s_waitcnt lgkmcnt(0)\n" \
-    "v_and_b32 v33, s66, v30\n" \
-    "v_and_b32 v34, s67, v31\n" \
-    "v_bcnt_u32_b32 v33, v33, s49\n" \
-    "v_bcnt_u32_b32 v33, v34, v33\n" \
+    "v_mbcnt_lo_u32_b32 v" T ", v30, s49\n"            /* lane L: E1[L1] + the word's bits below L ... */ \
+    "v_mbcnt_hi_u32_b32 v" T ", v31, v" T "\n" \
     "v_cmp_lt_u32 vcc, s43, v2\n" \
-    "v_add_u32 v37, v29, v33\n" U2PD(139) \
-    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n" \
-    "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
-    U2_DEC_RANK_TAIL_U
+    "v_add_u32 v37, v29, v" T "\n"                     /* ... + the row element: lane b holds the rank of x */ U2PD(139) \
+    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes above L1 */ \
+    "v_readlane_b32 s64, v37, s40\n"                  /* lane x & 63 */ U2PD(140)
+#else
+#define U2_DEC_RANK_1W(T) \
+    "s_waitcnt lgkmcnt(0)\n" \
+    "v_and_b32 v32, s66, v30\n" \
+    "v_and_b32 v33, s67, v31\n" \
+    "v_bcnt_u32_b32 v32, v32, s49\n"                   /* E1[L1] + ... */ \
+    "v_bcnt_u32_b32 v32, v33, v32\n"                   /* ... the bits below b */ \
+    "v_cmp_lt_u32 vcc, s43, v2\n" \
+    "v_add_u32 v37, v29, v32\n"                        /* + the row element: the rank of x, in every lane */ U2PD(139) \
+    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes above L1 */ \
+    "v_readfirstlane_b32 s64, v37\n" U2PD(140)
+#endif
+#define U2_DEC_RANK_U_G1 U2_DEC_RANK_1W("33") U2_DEC_RANK_TAIL_U
 // ---- the 20-bit step on word-granular rows (U2DecWord, k_roc_decode_u2<20, true>): the one-word step above with w = x >> 6 in the
 // place of the entry.  u16 row[64][256] sits at LDS byte 0 and the bitmap at byte 32 768, which the bitmap read takes as its offset
-// field; the row element is a broadcast ds_read_u16 of byte 2 w.  L1 = w >> 8, and the rank is E1[L1] + row[w] + the masked popcount
-// of the one word, read out with v_readfirstlane: no g, no whole-word popcounts, no prefix over four lanes.
+// field; the row element is a broadcast ds_read_u16 of byte 2 w.  L1 = w >> 8, and the rank is E1[L1] + row[w] + the bits of the one
+// word below b (U2_DEC_RANK_1W): no g, no whole-word popcounts, no prefix over four lanes.
 //  * row update: ONE ds_add_u64 by all lanes.  Lane j owns u64 j of row L1 (the fields of words 4 j .. 4 j + 3) and adds 1 to the
 //    fields above w & 255: FIELD_ONES << 16 z with z = the lane's fields at or below w & 255.  16 z = 16 (w & 255) + 16 - 64 j clamped
 //    to 0 .. 64 (v3 = 16 - 64 j: one v_lshl_add, one v_med3).  A 64-bit shift takes six bits of its count, so the clamp stops at 63:
@@ -1268,7 +1346,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //    elsewhere: the other lanes OR nothing into the rows.  Lane 0's dword lies in the bitmap, so no two lanes meet.
 //  * every address is formed from x < 2^20 alone: row element below 32 768, word and dword inside the bitmap, u64 (x >> 14, lane) inside
 //    the rows (U2DecWord's functions are these formulas; tests/roc_u2_decword_geom_test.cpp walks all of them).
-//  * 58 instructions per step (the four-word step: 62).
+//  * 58 instructions per step (the four-word step: 65).
 //   v3 16 - 64 * lane   v11 8 * lane   v12 lane == 0   v29 address, then value of row[w]   v32 v33 masked word, popcounts
 //   v[34:35] data of the row update   v38 its address   v39 shift count   s43 L1   s44 w & 255   s45 w   s[54:55] FIELD_ONES
 // The other four-instruction form of the data was measured 0.6 ns per step longer: both halves by v_med3_i32 (y, 0, 0x10001) with
@@ -1284,7 +1362,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 #define U2_DEC_MID_W \
     "s_lshr_b32 s43, s45, 8\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 255\n"                        /* word inside the block */ \
-    "s_bfm_b64 s[66:67], s40, 0\n"                     /* bits below b = x mod 64 */ \
+    U2_DEC_BFM \
     "s_and_b32 m0, s60, 63\n" U2PD(134) \
     "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
@@ -1298,21 +1376,15 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_cselect_b32 s50, s59, s58\n" \
     "s_cselect_b32 s51, 0, s59\n" \
     "s_addc_u32 s60, s60, 0\n" U2PD(136) \
+    U2_DEC_W_IDX \
     "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
     "s_mul_hi_u32 s53, s50, s75\n" \
     "s_mul_i32 s68, s51, s75\n" \
     "s_add_u32 s53, s53, s68\n" \
     "s_mov_b32 m0, s69\n" U2PD(137)
 #define U2_DEC_RANK_W \
-    "s_waitcnt lgkmcnt(0)\n" \
-    "v_and_b32 v32, s66, v30\n" \
-    "v_and_b32 v33, s67, v31\n" \
-    "v_bcnt_u32_b32 v32, v32, s49\n"                   /* E1[L1] + ... */ \
-    "v_bcnt_u32_b32 v32, v33, v32\n"                   /* ... the bits below b */ \
-    "v_cmp_lt_u32 vcc, s43, v2\n" \
-    "v_add_u32 v37, v29, v32\n"                        /* + row[w]: the rank of x, in every lane */ U2PD(139) \
-    "v_addc_co_u32 v4, vcc, 0, v4, vcc\n"              /* E1 += 1 in lanes above L1 */ \
-    "v_readfirstlane_b32 s64, v37\n" U2PD(140) \
+    U2_DEC_RANK_1W("32") \
+    U2_DEC_W_LOAD                                      /* w of the next step's pops: behind the ring write and the s_addc of U2_DEC_MID_W */ \
     U2_DEC_INS_ADDR \
     "v_lshlrev_b32 v27, s40, v12\n"                    /* the bit in lane 0, 0 elsewhere */ \
     "v_writelane_b32 v6, s40, m0\n"                    /* output ring */ \
@@ -1338,16 +1410,27 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
     "s_cselect_b32 s71, s70, 0\n" U2PD(143) \
     "s_cmp_lt_u32 s69, s71\n"
-#define U2_DEC_STEP_U(IDX, MID, RANK, LA, LB, LC, LD) U2_DEC_TOP_L(LA, LB, LC, LD) IDX MID RANK U2_DEC_BOT_NR_U "s_cbranch_scc0 2f\n"
+#if U2_DEC_STEP & 2
+#define U2_DEC_TOP_U(LA, LB, LC, LD) U2_DEC_TOP_P(LA, LB)
+#define U2_DEC_SIDE_U(LA, LB, LC, LD) U2_DEC_SIDE_P(LA, LB)
+#define U2_DEC_ENTRY_U U2_DEC_ENTRY U2_DEC_W_IDX U2_DEC_W_LOAD
+#define U2_DEC_OUTER_U(RLO, RSPAN) U2_DEC_OUTER_TR(RLO, RSPAN, U2_DEC_W_IDX U2_DEC_W_LOAD)
+#else
+#define U2_DEC_TOP_U(LA, LB, LC, LD) U2_DEC_TOP_L(LA, LB, LC, LD)
+#define U2_DEC_SIDE_U(LA, LB, LC, LD) U2_DEC_SIDE(LA, LB, LC, LD)
+#define U2_DEC_ENTRY_U U2_DEC_ENTRY
+#define U2_DEC_OUTER_U(RLO, RSPAN) U2_DEC_OUTER_T(RLO, RSPAN)
+#endif
+#define U2_DEC_STEP_U(IDX, MID, RANK, LA, LB, LC, LD) U2_DEC_TOP_U(LA, LB, LC, LD) IDX MID RANK U2_DEC_BOT_NR_U "s_cbranch_scc0 2f\n"
 #define U2_DEC_LOOP8_U(IDX, MID, RANK) \
     "1:\n" U2_DEC_STEP_U(IDX, MID, RANK, "20", "21", "22", "23") U2_DEC_STEP_U(IDX, MID, RANK, "30", "31", "32", "33") \
     U2_DEC_STEP_U(IDX, MID, RANK, "40", "41", "42", "43") U2_DEC_STEP_U(IDX, MID, RANK, "50", "51", "52", "53") \
     U2_DEC_STEP_U(IDX, MID, RANK, "60", "61", "62", "63") U2_DEC_STEP_U(IDX, MID, RANK, "70", "71", "72", "73") \
     U2_DEC_STEP_U(IDX, MID, RANK, "80", "81", "82", "83") \
-    U2_DEC_TOP_L("90", "91", "92", "93") IDX MID RANK U2_DEC_BOT_T_U("-18", "35") "s_cbranch_scc1 1b\n s_branch 2f\n" \
-    U2_DEC_SIDE("20", "21", "22", "23") U2_DEC_SIDE("30", "31", "32", "33") U2_DEC_SIDE("40", "41", "42", "43") \
-    U2_DEC_SIDE("50", "51", "52", "53") U2_DEC_SIDE("60", "61", "62", "63") U2_DEC_SIDE("70", "71", "72", "73") \
-    U2_DEC_SIDE("80", "81", "82", "83") U2_DEC_SIDE("90", "91", "92", "93") "2:\n"
+    U2_DEC_TOP_U("90", "91", "92", "93") IDX MID RANK U2_DEC_BOT_T_U("-18", "35") "s_cbranch_scc1 1b\n s_branch 2f\n" \
+    U2_DEC_SIDE_U("20", "21", "22", "23") U2_DEC_SIDE_U("30", "31", "32", "33") U2_DEC_SIDE_U("40", "41", "42", "43") \
+    U2_DEC_SIDE_U("50", "51", "52", "53") U2_DEC_SIDE_U("60", "61", "62", "63") U2_DEC_SIDE_U("70", "71", "72", "73") \
+    U2_DEC_SIDE_U("80", "81", "82", "83") U2_DEC_SIDE_U("90", "91", "92", "93") "2:\n"
 #define U2_DEC_BOT U2_DEC_BOT_CORE "s_cbranch_scc1 1b\n s_branch 2f\n" U2_DEC_SIDE("20", "21", "22", "23") "2:\n"
 #define U2_DEC_BOT_CORE U2_DEC_BOT_CORE_T("-2", "59")
 #define U2_DEC_BOT_CORE_T(RLO, RSPAN)                  /* the next step may run while RLO <= words in the ring <= RLO + RSPAN */ \
@@ -1375,7 +1458,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_cmp_lt_u32 s69, s71\n"
 // Ring of the eight-copy loop: a step pops at most two words and pushes at most one, so eight steps are safe while the ring
 // holds U2_DEC_RING_LO .. U2_DEC_RING_HI words when the first copy starts (18 - 16 = 2 words left for the last pops, 53 + 8 = 61
-// before the last push); only the last copy, U2_DEC_OUTER and the C++ glue test it.
+// before the last push); only the last copy, U2_DEC_OUTER and the C++ glue test it.  (A k_roc_decode_u2 step pops at most one word,
+// U2_DEC_TOP_P: the bound is only more conservative for it.)
 #define U2_DEC_RING_LO 18u
 #define U2_DEC_RING_HI 53u
 #define U2_DEC_SIDE(LA, LB, LC, LD) \
@@ -1429,7 +1513,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_mov_b64 exec, s[96:97]\n" \
     "s_sub_u32 s87, s87, s72\n"
 #define U2_DEC_OUTER U2_DEC_OUTER_T("-2", "59")
-#define U2_DEC_OUTER_T(RLO, RSPAN) \
+#define U2_DEC_OUTER_T(RLO, RSPAN) U2_DEC_OUTER_TR(RLO, RSPAN, "")
+#define U2_DEC_OUTER_TR(RLO, RSPAN, RELOAD)            /* RELOAD: what a kernel carries from step to step, loaded again before it goes on */ \
     "s_lshr_b64 s[98:99], s[58:59], 31\n" \
     "s_cselect_b32 s99, 0, 1\n"                        /* head < 2^31 */ \
     "s_sub_u32 s68, s60, s61\n" \
@@ -1449,6 +1534,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "5:\n" \
     "s_cmp_ge_u32 s69, s70\n" \
     "s_cbranch_scc1 9f\n" \
+    RELOAD \
     "s_cmp_eq_u32 s99, 0\n" \
     "s_cbranch_scc1 1b\n" \
     "9:\n" \
@@ -1534,6 +1620,7 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
     const uint32_t ins_bit = lane == 0u ? 1u : 0u;
     const uint64_t field_ones = rfl64(U2DecWord::FIELD_ONES);
     const uint32_t M1 = (1u << p1) - 1u, M0 = (1u << p0) - 1u;
+    const uint32_t pop_thr = 31u + p1, pop_bfe = (p0 << 16) | p1, pop_sh = p1 + p0;  // U2_DEC_TOP_P: s56, s57, s63
     uint64_t *out = a.out + ooff;
     wave_sync();
 #ifdef U2_PROF
@@ -1576,14 +1663,15 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
               "+{s[58:59]}"(s_h), "+{s60}"(st.sp), "+{s69}"(s_t), "+{s85}"(s_N0), "+{s86}"(s_left), "+{s87}"(s_oidx)        \
               U2P_OPERANDS                                                                                                 \
             : __VA_ARGS__ "{v2}"(lane), "{v3}"(l3off), "{v8}"(ins_mul), "{v9}"(ins_add), "{v11}"(row_lane), "{s61}"(st.lo), \
-              "{s73}"(M1), "{s74}"(M0), "{s76}"(p0), "{s77}"(p1), "{s[88:89]}"(out), "{s[94:95]}"(dtab)                     \
+              "{s73}"(M1), "{s74}"(M0), "{s76}"(p0), "{s77}"(p1), "{s[88:89]}"(out), "{s[94:95]}"(dtab),                    \
+              "{s56}"(pop_thr), "{s57}"(pop_bfe), "{s63}"(pop_sh)                                                            \
             : "memory", "vcc", "scc", "v10", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36",     \
-              "v37", "v38", "v39", "v54", "v55", "v56", "v57", "v58", "s40", "s43", "s44", "s45", "s46", "s47", "s49", "s50", \
-              "s51", "s52", "s53", "s62", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", "s97",       \
-              "s98", "s99" U2PD_CLOBBERS)
-        if constexpr (WORD) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_W, U2_DEC_MID_W, U2_DEC_RANK_W) U2_DEC_OUTER_T("-18", "35"), U2_DEC_IN_W);
-        else if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U, U2_DEC_RANK_U_G4) U2_DEC_OUTER_T("-18", "35"));
-        else U2_DEC_ASM(U2_DEC_ENTRY U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_MID_U, U2_DEC_RANK_U_G1) U2_DEC_OUTER_T("-18", "35"));
+              "v37", "v38", "v39", "v54", "v55", "v56", "v57", "v58", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", \
+              "s49", "s50", "s51", "s52", "s53", "s62", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s75", "s96", \
+              "s97", "s98", "s99" U2PD_CLOBBERS)
+        if constexpr (WORD) U2_DEC_ASM(U2_DEC_ENTRY_U U2_DEC_LOOP8_U(U2_DEC_IDX_W, U2_DEC_MID_W, U2_DEC_RANK_W) U2_DEC_OUTER_U("-18", "35"), U2_DEC_IN_W);
+        else if (U::G == 4u) U2_DEC_ASM(U2_DEC_ENTRY_U U2_DEC_LOOP8_U(U2_DEC_IDX_G4, U2_DEC_MID_U, U2_DEC_RANK_U_G4) U2_DEC_OUTER_U("-18", "35"));
+        else U2_DEC_ASM(U2_DEC_ENTRY_U U2_DEC_LOOP8_U(U2_DEC_IDX_G1, U2_DEC_MID_U1, U2_DEC_RANK_U_G1) U2_DEC_OUTER_U("-18", "35"));
 #undef U2_DEC_ASM
 #undef U2_DEC_IN_W
         // clang-format on
