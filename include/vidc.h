@@ -486,6 +486,46 @@ int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int
 int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int precision_mode, uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
 
+/* ---------------------------------------------------- locate (batches of pairs, device-resident) */
+/* The inverse of translate_labels -- Faiss's direct map (DirectMap, reconstruct, update_vectors): at which (list, offset) does an id
+ * sit?  The object is read-only and unchanged.
+ *
+ * The batch is the remove's.  Pair i is (d_list_nos[i], d_ids[i]); n < 2^32 - 1.  d_list_nos chooses the mode:
+ *   Pairs mode (d_list_nos != NULL): the id is looked for in list d_list_nos[i] only.  A negative list number is skipped and not
+ *     counted; a list number >= nlist is skipped and counted in *d_invalid.
+ *   Any-list mode (d_list_nos == NULL): the id is looked for in every list.
+ *   Equality is over all 64 bits of what the object decodes to.  An id the object cannot hold matches nothing: >= 2^32 for ROC,
+ *   >= 2^bits for packed bits, >= ntotal for the wavelet tree.
+ * The result.  d_labels (device int64[n]): every element is written and nothing outside is.  d_labels[i] = list_no << 32 | offset of
+ *   an entry equal to d_ids[i], the offset in the object's own order (what vidc_*_decode_lists and translate_labels use: sampling
+ *   order for ROC, ascending for Elias-Fano and the wavelet tree, input order for packed bits).  If several entries match, the label
+ *   is the smallest one: lowest list, then lowest offset -- the same on every run.  No match, a skipped or an invalid pair: -1.
+ *   *d_missing += the valid pairs that got -1 (in pairs mode that includes an id that sits in another list); repeated pairs each count
+ *   and each get the same label.  d_missing and d_invalid are device uint64 the caller zeroes; either may be NULL.  Wherever
+ *   d_labels[i] >= 0, vidc_*_translate_labels_dev on the same object maps it back to d_ids[i].  d_labels must not overlap the inputs.
+ * Arrays are device arrays on the context's device, read and written in order on the context's stream.
+ * Status.  NULL context or object, NULL d_ids or d_labels with n > 0, n >= 2^32 - 1: VIDC_ERR_INVALID before any device work.  A graph
+ *   object (rows, Elias-Fano arena): VIDC_ERR_UNSUPPORTED.  n == 0: VIDC_OK, nothing is launched.  The context stays usable after any
+ *   error.
+ * Residency.  No id payload crosses PCIe (vidc_ctx_d2h_bytes does not move).  Packed bits, Elias-Fano, ROC: the batch is sorted by
+ *   (list, id) as a remove sorts it, the object is decoded into scratch (decode_all; ROC: the candidates of a remove -- the non-empty
+ *   lists a valid pair names, in any-list mode EVERY non-empty list, which decodes the whole object), every decoded entry
+ *   binary-searches its list's run and a 64-bit atomic minimum keeps the smallest label per batch value: a minimum does not depend on
+ *   the order of its operands, nothing timing-dependent decides a result.  Packed bits and Elias-Fano read nothing back; ROC reads
+ *   back the candidate list numbers once (4 bytes each).  These calls wait for their last kernel; vidc_ctx_last_kernel_ms is the sum
+ *   over the call's kernels.  The wavelet tree walks every id down its levels (the bit at the position, the rank inside the node): a
+ *   thread per pair, no sort, no decode, enqueue only like vidc_wt_translate_labels_dev (vidc_ctx_last_kernel_ms is left alone).
+ * Out of scope: segmented ROC objects, sharded objects and graph objects; a search inside compressed Elias-Fano lists; a persistent
+ *   direct map kept beside the object. */
+int vidc_packed_locate_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
+                           int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
+int vidc_ef_locate_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
+                       int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
+int vidc_wt_locate_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
+                       int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
+int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
+                        int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

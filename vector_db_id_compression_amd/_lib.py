@@ -155,6 +155,9 @@ def _declare(lib):
     f("vidc_packed_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp, _vp)
     f("vidc_ef_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp, _vp)
     f("vidc_roc_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp, _vp)
+    # locate (batches of pairs, device-resident): ctx, obj, n, list_nos, ids, labels, missing, invalid
+    for name in ("vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev"):
+        f(name, C.c_int, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
     # update rows (graph objects, device-resident)
     f("vidc_compact_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
     f("vidc_ef_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
@@ -223,6 +226,7 @@ EXPORTED_SYMBOLS = [
     "vidc_compact_rows_decode_dev", "vidc_ef_decode_rows_dev", "vidc_roc_decode_rows_dev",
     "vidc_packed_append_dev", "vidc_ef_append_dev", "vidc_wt_append_dev", "vidc_roc_append_dev",
     "vidc_packed_remove_dev", "vidc_ef_remove_dev", "vidc_roc_remove_dev",
+    "vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
     "vidc_shards_encode", "vidc_shards_encode_dev", "vidc_shards_destroy", "vidc_shards_count", "vidc_shards_kind", "vidc_shards_nlist",
     "vidc_shards_ntotal", "vidc_shards_compressed_bytes", "vidc_shards_map", "vidc_shards_offsets", "vidc_shards_shard",

@@ -16,6 +16,7 @@
 #include "chunks.h"
 #include "append.h"
 #include "remove.h"
+#include "locate.h"
 #include "common.h"
 #include "dev_offsets.h"
 #include "ef_plan.h"
@@ -2914,6 +2915,18 @@ int ef_remove(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_l
 int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags,
                        vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return ef_remove(ctx, e, n_rm, d_list_nos, d_ids, flags, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+// Locate (include/vidc.h): decode_all into scratch, the mark and the labels of locate.h.  The offsets are positions in the ascending
+// list, the order decode_lists and translate_labels use.
+int vidc_ef_locate_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_labels,
+                       uint64_t *d_missing, uint64_t *d_invalid) {
+    VIDC_TRY(locate_check(ctx, e, n, d_ids, d_labels));
+    if (e->rows || e->arena) { set_error("elias-fano locate: graph objects hold no lists to locate in"); return VIDC_ERR_UNSUPPORTED; }
+    if (!n) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    return locate_decoded(ctx, e->nlist, e->ntotal, e->d_offsets.p, n, d_list_nos, d_ids, 64u, d_labels, d_missing, d_invalid,
+                          [&](uint64_t *d) { return vidc_ef_decode_all(ctx, e, d); });
 }
 
 int vidc_ef_get(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *list_nos, const uint64_t *offs,

@@ -14,6 +14,7 @@
 #include "chunks.h"
 #include "append.h"
 #include "remove.h"
+#include "locate.h"
 #include "common.h"
 #include "dev_offsets.h"
 #include "host_call.h"
@@ -1431,6 +1432,17 @@ int packed_remove(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int6
 int vidc_packed_remove_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
                            vidc_packed **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return packed_remove(ctx, p, n_rm, d_list_nos, d_ids, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+// Locate (include/vidc.h): decode_all into scratch, the mark and the labels of locate.h.  An id of `bits` bits is all the object can
+// hold: a wider batch id matches nothing.
+int vidc_packed_locate_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_labels,
+                           uint64_t *d_missing, uint64_t *d_invalid) {
+    VIDC_TRY(locate_check(ctx, p, n, d_ids, d_labels));
+    if (!n) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    return locate_decoded(ctx, p->nlist, p->ntotal, p->d_offsets.p, n, d_list_nos, d_ids, (uint32_t)p->bits, d_labels, d_missing, d_invalid,
+                          [&](uint64_t *d) { return vidc_packed_decode_all(ctx, p, d); });
 }
 
 int vidc_packed_export(vidc_ctx *ctx, const vidc_packed *p, uint64_t list_no, uint8_t *bytes, size_t cap) {

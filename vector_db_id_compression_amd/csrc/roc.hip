@@ -11,6 +11,7 @@
 
 #include "append.h"
 #include "remove.h"
+#include "locate.h"
 #include "common.h"
 #include "host_call.h"
 #include "roc_dec_plan.h"
@@ -2596,6 +2597,89 @@ int roc_clone_to(vidc_ctx *dst, const vidc_roc *r, vidc_roc **out) {
 int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
                         uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return roc_remove(ctx, r, n_rm, d_list_nos, d_ids, precision_mode, flags, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+// Locate (include/vidc.h).  The batch is sorted as a remove sorts it and the same candidates -- the non-empty lists a valid pair names,
+// or every non-empty list in any-list mode -- are compacted on the device; their numbers come back once (4 bytes per candidate,
+// metadata), the host sizes a staging CSR, the candidates are decoded into it (plan_decode / decode_impl on the subset) in ascending
+// list order and marked (locate.h).  The offsets are positions in sampling order, the order decode_lists and translate_labels use.
+int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_labels,
+                        uint64_t *d_missing, uint64_t *d_invalid) {
+    VIDC_TRY(locate_check(ctx, r, n, d_ids, d_labels));
+    if (r->rows) { set_error("roc locate: graph objects hold no lists to locate in"); return VIDC_ERR_UNSUPPORTED; }
+    if (!n) return VIDC_OK;
+    VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc locate");
+    const uint64_t nlist = r->nlist;
+    double kernel_ms = 0;
+    LocateBatch b;
+    AppChunks ch;
+    Scratch s_mark, s_off, s_cand, s_t0, s_stage, s_seg;
+    Pinned h_back, h_seg;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
+    EventTimer tm = EventTimer::started(ctx);
+    VIDC_TRY(locate_sort_batch(ctx, nlist, n, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
+    // the candidates
+    VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
+    VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
+    VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
+    uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
+    uint64_t *stage_off = s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
+    uint32_t *d_cand = s_cand.as<uint32_t>();
+    VIDC_TRY(h_back.get(ctx, 8 + (nlist + 1) * 4));
+    uint64_t *h_cnt = h_back.as<uint64_t>();
+    uint32_t *h_cand = (uint32_t *)(h_cnt + 1);
+    *h_cnt = 0;
+    if (nlist) {
+        hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p,
+                           b.batch.any ? (const uint64_t *)nullptr : b.batch.run_off, nlist, mark, flag);
+        Scan4 sc{};
+        sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
+        hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    const uint64_t cnt = *h_cnt;
+    std::vector<uint32_t> cand(cnt);
+    VIDC_TRY(h_seg.get(ctx, (cnt + 1) * 8));
+    uint64_t *seg_off = h_seg.as<uint64_t>();
+    seg_off[0] = 0;
+    if (cnt) {
+        VIDC_HIP(hipMemcpyAsync(h_cand, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        for (uint64_t k = 0; k < cnt; k++) {
+            cand[k] = h_cand[k];
+            seg_off[k + 1] = seg_off[k] + (r->offsets[cand[k] + 1] - r->offsets[cand[k]]);
+        }
+    }
+    const uint64_t total = seg_off[cnt];
+    tr.mark("batch sorted, candidates read back");
+    if (cnt) {
+        VIDC_TRY(s_stage.get(ctx, total * 8));
+        VIDC_TRY(s_seg.get(ctx, (cnt + 1) * 8));
+        VIDC_HIP(hipMemcpyAsync(s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        {
+            PooledDecPlan p;
+            plan_decode(r, cand, false, p, ctx->wide);
+            std::vector<uint64_t> out_off(cnt);
+            for (size_t k = 0; k < cnt; k++) out_off[k] = seg_off[p.item[k]];  // work item k -> its place in the staging
+            VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+            kernel_ms += ctx->last_kernel_ms;
+        }
+        tr.mark("candidates decoded");
+    }
+    (void)tm.start();
+    if (cnt) VIDC_TRY(locate_mark(ctx, b, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), d_cand, cnt, total, ch));
+    VIDC_TRY(locate_labels(ctx, b, d_labels, d_missing));
+    ctx->last_kernel_ms = kernel_ms + tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    guard.disarm();
+    tr.mark("candidates marked, labels written");
+    return VIDC_OK;
 }
 
 // Regroup (include/vidc.h): the splice of the append and the remove as a call of its own, over up to VIDC_SHARDS_MAX sources instead

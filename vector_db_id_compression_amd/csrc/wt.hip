@@ -884,6 +884,49 @@ __global__ void k_wt_select(View vw, const uint64_t *C, const uint32_t *__restri
     }
 }
 
+// Locate (vidc_wt_locate_dev), one thread per pair: wt_select_walk the other way.  Id i is position i of the root; at every level the
+// bit at the position names the child and the rank inside the node (the level's rank minus the ones before the node start, nrank) is
+// the position in that child.  The leaf is the list, the last position the offset.  No sort and no decode: a tree holds every id
+// 0 .. ntotal - 1 exactly once, so the label is unique.  list_nos == NULL: any-list mode; else the leaf has to equal list_nos[q]
+// (negative: skipped; >= nlist: skipped and counted in *invalid).  -1 and one more in *missing for a valid pair that finds nothing.
+template <class View>
+__global__ void k_wt_locate(View vw, const uint64_t *C, const uint32_t *__restrict__ nrank, uint32_t nlist, uint32_t L, uint64_t ntotal, uint64_t n,
+                            const int64_t *__restrict__ list_nos, const uint64_t *__restrict__ ids, int64_t *__restrict__ labels,
+                            unsigned long long *missing, unsigned long long *invalid) {
+    __shared__ uint64_t s_binom[View::kRrrView ? 64 * 64 : 1];
+    __shared__ uint8_t s_ow[64];
+    wt_stage_tables(vw, s_binom, s_ow);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); q0 < n; q0 += stride) {  // (q0: wavefront-uniform)
+        const uint64_t q = q0 + (threadIdx.x & 63u);
+        const bool in = q < n;
+        const int64_t l = in ? (list_nos ? list_nos[q] : 0) : -1;
+        const bool ok = in && (!list_nos || (l >= 0 && (uint64_t)l < nlist));
+        const uint64_t id = in ? ids[q] : 0;
+        int64_t lab = -1;
+        if (ok && id < ntotal) {
+            uint64_t pos = id;
+            uint32_t p = 0;
+            for (uint32_t level = 0; level < L; level++) {
+                const uint32_t sh = L - level;
+                uint64_t s_lo = sh >= 32 ? 0 : ((uint64_t)p << sh);
+                if (s_lo > nlist) s_lo = nlist;
+                const uint64_t ns = C[s_lo];
+                auto bv = vw.level(level);
+                wt_use_tables(bv, s_binom, s_ow);
+                bool bit;
+                const uint64_t ones = bv.rank_1_bit(ns + pos, bit) - nrank[wt_nrank_base(level) + p];
+                pos = bit ? ones : pos - ones;
+                p = 2u * p + (bit ? 1u : 0u);
+            }
+            if (!list_nos || (int64_t)p == l) lab = (int64_t)(((uint64_t)p << 32) | pos);
+        }
+        if (in) labels[q] = lab;
+        req_count_invalid(in && l >= 0 && !ok, invalid);
+        req_count_invalid(ok && lab < 0, missing);
+    }
+}
+
 // get_ids of the requested lists (custom_invlists_impl.cpp:381-392 loops get_single_id): one thread per output slot,
 // its request item found in the m + 1 output offsets
 template <class View>
@@ -1634,6 +1677,29 @@ int vidc_wt_translate_labels_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, co
     else
         hipLaunchKernelGGL((k_wt_select<WtPlainView, true>), sgrid, dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p,
                            (uint32_t)w->nlist, w->L, n, lab, (const uint64_t *)nullptr, d_ids, inv);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
+}
+
+// Locate (include/vidc.h): one walk from the root per pair (k_wt_locate), over the tables the select calls use.  Enqueue only, like
+// vidc_wt_translate_labels_dev: no scratch, no wait, vidc_ctx_last_kernel_ms is left alone.
+int vidc_wt_locate_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_labels,
+                       uint64_t *d_missing, uint64_t *d_invalid) {
+    if (!ctx || !w || (n && (!d_ids || !d_labels))) {
+        set_error("wt locate: NULL context, object, id or label array");
+        return VIDC_ERR_INVALID;
+    }
+    if (n >= 0xffffffffull) { set_error("wt locate: a batch holds fewer than 2^32 - 1 pairs"); return VIDC_ERR_INVALID; }
+    if (!n) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const dim3 sgrid((uint32_t)std::min<uint64_t>((n + 127) / 128, 1u << 16));
+    unsigned long long *mis = (unsigned long long *)d_missing, *inv = (unsigned long long *)d_invalid;
+    if (w->wt_type == 1)
+        hipLaunchKernelGGL(k_wt_locate<WtRrrView>, sgrid, dim3(128), 0, ctx->stream, rrr_view(w), w->d_C.p, w->d_nrank.p, (uint32_t)w->nlist, w->L,
+                           w->ntotal, n, d_list_nos, d_ids, d_labels, mis, inv);
+    else
+        hipLaunchKernelGGL(k_wt_locate<WtPlainView>, sgrid, dim3(128), 0, ctx->stream, plain_view(w), w->d_C.p, w->d_nrank.p, (uint32_t)w->nlist,
+                           w->L, w->ntotal, n, d_list_nos, d_ids, d_labels, mis, inv);
     VIDC_HIP(hipGetLastError());
     return VIDC_OK;
 }

@@ -197,6 +197,14 @@ class InvertedListsArrayCodes:
         the loop of custom_invlists_impl.cpp:508-525 for a caller whose labels come from a GPU top-k (codec translate_labels)."""
         return self._c.translate_labels(labels, out=out, invalid=invalid)
 
+    def locate_batch(self, list_nos, ids):
+        """The inverse of translate_labels, Faiss's direct map (locate.locate on the codec): labels (int64 CUDA tensor, list_no << 32 |
+        offset, -1 = not found) of the ids; list_nos=None looks in every list, else id i is looked for in list list_nos[i] only.  The
+        offsets are positions in the container's own order: row offsets[list_no] + offset of codes_all is the id's code."""
+        from . import locate
+
+        return locate.locate(self._c, list_nos, ids)
+
 
 class CompressedIDInvertedListsPackedBits(InvertedListsArrayCodes):
     """custom_invlists_impl.cpp:64-118."""
@@ -365,6 +373,9 @@ class CompressedIDInvertedListsROCSegmented(InvertedListsArrayCodes):
 
     def remove_batch(self, list_nos, ids):
         raise RuntimeError("not implemented: segmented ROC lists have no remove (re-encode, or use the FenwickTree container)")
+
+    def locate_batch(self, list_nos, ids):
+        raise RuntimeError("not implemented: segmented ROC lists have no locate (use the FenwickTree container)")
 
     def get_ids_all(self):
         return self._c.decode_all()

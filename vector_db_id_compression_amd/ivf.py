@@ -47,6 +47,20 @@ def _kmeans(x, k, iters=10, seed=123):
     return c
 
 
+def _host_rows(il, ids):
+    """The direct map of uncompressed lists on the host: row of to_csr(il)'s codes for every id (of equal ids the first in list
+    order, the smallest label); raises on an id that is not in the lists."""
+    want = np.asarray(ids, dtype=np.int64).reshape(-1)
+    all_ids = to_csr(il)[1].view(np.int64)
+    order = np.argsort(all_ids, kind="stable")
+    at = np.searchsorted(all_ids[order], want)
+    ok = at < order.size
+    ok[ok] = all_ids[order[at[ok]]] == want[ok]
+    if not ok.all():
+        raise RuntimeError(f"reconstruct_batch: {int((~ok).sum())} ids are not in the index")
+    return order[at]
+
+
 class IVFIndex:
     def __init__(self, d, nlist, code="Flat"):
         self.d, self.nlist = int(d), int(nlist)
@@ -130,6 +144,27 @@ class IVFIndex:
         self.ntotal -= n
         self._dev = None
         return n
+
+    def reconstruct_batch(self, ids):
+        """IndexIVF::reconstruct_batch through the direct map: the stored vectors of `ids` -> float32 CUDA tensor [n, d].  A compressed
+        container locates the ids on the device (locate_batch, any-list mode); ArrayInvertedLists is searched on the host.  Raises
+        on an id that is not in the index."""
+        torch = _torch()
+        il = self.invlists
+        off, codes = self._device_lists()
+        if hasattr(il, "locate_batch"):
+            if not hasattr(ids, "is_cuda"):
+                ids = torch.from_numpy(np.asarray(ids, dtype=np.int64))
+            labels = il.locate_batch(None, ids.to(torch.int64).cuda().reshape(-1))
+            absent = int((labels < 0).sum().item())
+            if absent:
+                raise RuntimeError(f"reconstruct_batch: {absent} ids are not in the index")
+            rows = torch.from_numpy(off).to(labels.device)[labels >> 32] + (labels & 0xFFFFFFFF)
+        elif isinstance(il, ArrayInvertedLists):
+            rows = torch.from_numpy(_host_rows(il, np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids, dtype=np.int64))).cuda()
+        else:
+            raise RuntimeError("reconstruct_batch: the inverted lists have no direct map")
+        return self._decode_codes(codes[rows])
 
     def replace_invlists(self, il, own=False):
         self.invlists = il
