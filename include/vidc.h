@@ -26,8 +26,9 @@
  * Environment (test hooks, read per call): VIDC_NO_LANE=1 / VIDC_FORCE_LANE=1 never / always use the
  * lane-per-list ROC kernels (default: only for calls with thousands of short lists), VIDC_FORCE_GENERAL=1 routes
  * every list through the general wave-per-list kernels, VIDC_HOST_THREADS=n caps the host threads used to plan calls
- * with >= 131072 lists (default 8), VIDC_TRACE=1 prints host-side phase times.  The bit streams do not depend on
- * any of them.
+ * with >= 131072 lists (default 8), VIDC_TRACE=1 prints host-side phase times.  Read when a context is created:
+ * VIDC_WIDE_STREAMS=1 (behave as if GPU_MAX_HW_QUEUES >= 8), VIDC_NUM_CU=n (size grids as if the device had n < its own
+ * count of compute units, see vidc_ctx_num_cu), VIDC_POOL_POISON=1.  The bit streams do not depend on any of them.
  */
 #ifndef VIDC_H
 #define VIDC_H
@@ -79,6 +80,12 @@ int vidc_ctx_debug_pool_poison(vidc_ctx *ctx, int on);
  * the Python / C++ program that loads Faiss, not after `import faiss`), otherwise 4.  The published S2 numbers are the 8-stream
  * mode; the 4-stream mode is ~10 % slower on calls of ~10^6 lists and identical on small calls.  Returns 0 for NULL. */
 int vidc_ctx_class_streams(const vidc_ctx *ctx);
+/* Compute units the context sizes its grids by: the device's multiProcessorCount, unless VIDC_NUM_CU=n was in the environment when
+ * the context was created (test hook).  The hook can only LOWER the count: it applies for 1 <= n < the device's own count and is
+ * ignored otherwise (0, not a number, at or above the device's count), so a grid never exceeds what the device holds -- the graph
+ * compaction kernel relies on every wavefront of its launch being resident.  With a small n the grid-stride loops of the kernels take
+ * several trips at sizes where they would otherwise take one; the output does not depend on it.  Returns 0 for NULL. */
+uint32_t vidc_ctx_num_cu(const vidc_ctx *ctx);
 /* Device memory helpers for hosts without their own allocator (Python uses torch tensors instead). */
 int vidc_dev_alloc(vidc_ctx *ctx, size_t bytes, void **dev_ptr);
 int vidc_dev_free(vidc_ctx *ctx, void *dev_ptr);

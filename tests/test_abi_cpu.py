@@ -40,6 +40,9 @@ def test_pure_host_entry_points(libpath):
     for name in ("vidc_roc_last_decode_nonclean", "vidc_roc_last_decode_handed_back"):
         fn = getattr(L, name)
         assert fn.restype is ctypes.c_uint64 and fn(None) == 0, name
+    # the compute-unit count a context sizes its grids by (VIDC_NUM_CU test hook): u32, 0 without a context
+    assert "vidc_ctx_num_cu" in _lib.EXPORTED_SYMBOLS and hasattr(_lib.Context, "num_cu")
+    assert L.vidc_ctx_num_cu.restype is ctypes.c_uint32 and L.vidc_ctx_num_cu(None) == 0
 
 
 def test_no_gpu_fails_loudly(libpath):

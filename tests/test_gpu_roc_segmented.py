@@ -46,6 +46,21 @@ def distinct(rng, n, B, shuffled, must=()):
     return rng.permutation(li) if shuffled else np.sort(li)
 
 
+def many_segments(rng, k, B, T=16):
+    """one shuffled list that splits into 2^k segments at T ids a segment: the fewest ids that do (k = 7: T * 2^6 + 1) or the most a
+    list may hold (k = 10 = MAX_SEGS: T * 2^10, one more is refused); ids 0 and 2^B - 1 present, segment 2^k / 3 empty, the one behind
+    it holding a single id"""
+    S, W = 1 << k, 1 << (B - k)
+    n = T * (S // 2) + 1 if k < 10 else T * S
+    assert sr.seg_k(n, T, B) == k and sr.seg_k(n - (1 if k < 10 else 0), T, B) == (k - 1 if k < 10 else k)
+    empty, single = S // 3, S // 3 + 1
+    must = np.array([0, (1 << B) - 1, single * W + W // 2], np.uint64)
+    pool = np.arange(1 << B, dtype=np.uint64)
+    pool = pool[((pool >> np.uint64(B - k)) != empty) & ((pool >> np.uint64(B - k)) != single)]
+    pool = np.setdiff1d(pool, must)
+    return rng.permutation(np.concatenate([must, rng.choice(pool, n - must.size, replace=False)]))
+
+
 def family(name):
     """-> (T, B, lists)"""
     rng = np.random.default_rng(sum(map(ord, name)))
@@ -67,6 +82,10 @@ def family(name):
         B = int(name[4:])
         return 16, B, [distinct(rng, 40, B, True, must=[0, (1 << B) - 1]), np.zeros(0, np.uint64), distinct(rng, 17, B, False),
                        distinct(rng, 300, B, True)]
+    if name in ("segs7", "segs10"):  # more than 64 segments in a list: T = 16, 2^7 and 2^10 (MAX_SEGS) segments
+        k = int(name[4:])
+        B = 14 if k == 7 else 16
+        return 16, B, [many_segments(rng, k, B), distinct(rng, 9, B, True), np.zeros(0, np.uint64)]
     if name == "large":  # one list of 20 000 ids at T = 1024, B = 20: 32 segments, 20 chunks
         return 1024, 20, [distinct(rng, 20000, 20, True), distinct(rng, 700, 20, False)]
     raise KeyError(name)
@@ -173,6 +192,16 @@ def test_the_families_are_what_the_cases_count_on(oracle):
     assert int(lg["k"][0]) == 5 and len(sr.chunk_table(lg["offsets"], 1024, 20)[0]) == 21
     b = reference("bits10", oracle)
     assert int(b["ids"].max()) == 1023 and int(b["ids"][:40].min()) == 0
+    for name, k, B in (("segs7", 7, 14), ("segs10", 10, 16)):
+        r = reference(name, oracle)
+        m, li = r["model"], r["ids"][: int(r["off"][1])]
+        assert m["k"].tolist() == [k, 0, 0] and int(li.min()) == 0 and int(li.max()) == (1 << B) - 1
+        assert not np.array_equal(li, np.sort(li)), "shuffled"
+        seg_sizes = np.diff(m["inner_offsets"].astype(np.int64))[: 1 << k]
+        assert seg_sizes[(1 << k) // 3] == 0 and seg_sizes[(1 << k) // 3 + 1] == 1 and int(seg_sizes.sum()) == li.size
+        table_len = int(sr.chunk_table(r["off"], 16, B)[1][-1])
+        assert (table_len > 8192) == (k == 10), "2^10 segments: the count table takes the three-launch scan"
+    assert sr.seg_k(16 * 1024, 16, 16) == 10 and sr.seg_k(16 * 1024 + 1, 16, 16) == 11, "segs10 is the longest list T = 16 accepts"
 
 
 def test_a_rebased_power_of_two_maximum_and_a_lone_zero(oracle):
@@ -204,6 +233,40 @@ def test_encode_and_every_request(oracle, monkeypatch, name, hook):
         monkeypatch.setenv(hook, "1")
     obj = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=ref["T"], universe_bits=ref["B"], want_perm=True)
     check_object(obj, ref)
+
+
+@pytest.fixture(scope="module")
+def one_cu():
+    """a context whose grids are sized for one compute unit (VIDC_NUM_CU, include/vidc.h), on torch's stream like the default one"""
+    from vector_db_id_compression_amd import _lib
+
+    mp = pytest.MonkeyPatch()
+    mp.setenv("VIDC_NUM_CU", "1")
+    ctx = _lib.Context(0)
+    mp.undo()
+    assert ctx.num_cu() == 1
+    ctx.set_pool_poison(True)
+    ctx.set_stream(_torch().cuda.current_stream().cuda_stream)
+    yield ctx
+    _torch().cuda.synchronize()
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", ["segs7", "segs10"])
+def test_more_than_64_segments_in_a_list(oracle, one_cu, name):
+    """2^7 and 2^10 segments: the `s += 64` loops of both multisplit passes beyond their first 64 entries, the ballot ranking over 7 and
+    10 key bits, and (2^10) a count table of more than 8192 entries; on the default context and on a one-CU context"""
+    ref = reference(name, oracle)
+    got = []
+    for ctx in (None, one_cu):
+        obj = _cls().encode(ref["off"], dev(ref["ids"]), seg_ids=16, universe_bits=ref["B"], want_perm=True, ctx=ctx)
+        assert np.diff(obj.seg_info()[0].astype(np.int64)).tolist() == [1 << int(name[4:]), 1, 1]
+        dec = check_object(obj, ref)
+        off = ref["off"].astype(np.int64)
+        assert all(np.array_equal(np.sort(dec[off[l]:off[l + 1]]), np.sort(ref["ids"][off[l]:off[l + 1]])) for l in range(3)), "lossless"
+        got.append(export(obj))
+    for a, b in zip(*got):
+        assert np.array_equal(a, b), "the one-CU context builds the default context's object"
 
 
 @pytest.mark.parametrize("B", range(10, 21))

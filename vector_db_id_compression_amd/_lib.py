@@ -52,6 +52,7 @@ def _declare(lib):
     f("vidc_ctx_trim", C.c_int, _vp, C.POINTER(C.c_uint64))
     f("vidc_ctx_debug_pool_poison", C.c_int, _vp, C.c_int)
     f("vidc_ctx_class_streams", C.c_int, _vp)
+    f("vidc_ctx_num_cu", _u32, _vp)
     f("vidc_dev_alloc", C.c_int, _vp, C.c_size_t, _P(_vp))
     f("vidc_dev_free", C.c_int, _vp, _vp)
     f("vidc_copy_h2d", C.c_int, _vp, _vp, _vp, C.c_size_t)
@@ -206,7 +207,7 @@ def _declare(lib):
 #: every symbol include/vidc.h declares (checked by the CPU test-suite against the built library)
 EXPORTED_SYMBOLS = [
     "vidc_last_error", "vidc_version", "vidc_ctx_create", "vidc_ctx_destroy", "vidc_ctx_set_stream", "vidc_ctx_reset_stream",
-    "vidc_ctx_synchronize", "vidc_ctx_trim", "vidc_ctx_debug_pool_poison", "vidc_ctx_class_streams", "vidc_dev_alloc", "vidc_dev_free", "vidc_copy_h2d", "vidc_copy_d2h", "vidc_ctx_d2h_bytes",
+    "vidc_ctx_synchronize", "vidc_ctx_trim", "vidc_ctx_debug_pool_poison", "vidc_ctx_class_streams", "vidc_ctx_num_cu", "vidc_dev_alloc", "vidc_dev_free", "vidc_copy_h2d", "vidc_copy_d2h", "vidc_ctx_d2h_bytes",
     "vidc_ctx_last_kernel_ms", "vidc_ctx_phase_ms", "vidc_ctx_chain_info",
     "vidc_roc_encode", "vidc_roc_encode_rows", "vidc_roc_destroy", "vidc_roc_nlist", "vidc_roc_ntotal",
     "vidc_roc_compressed_bytes", "vidc_roc_total_words", "vidc_roc_list_info", "vidc_roc_export_words", "vidc_roc_export_all_words",
@@ -313,6 +314,11 @@ class Context:
     def class_streams(self):
         """Streams the kernel classes of a large ROC call are spread over: 8 if the process started with GPU_MAX_HW_QUEUES >= 8, else 4."""
         return int(lib().vidc_ctx_class_streams(self.h))
+
+    def num_cu(self):
+        """Compute units the context sizes its grids by: the device's own count, or the smaller VIDC_NUM_CU=n that was in the
+        environment when the context was created (test hook, can only lower it: vidc_ctx_num_cu)."""
+        return int(lib().vidc_ctx_num_cu(self.h))
 
     def d2h_bytes(self):
         """Id payload this context has copied device -> host so far (vidc_ctx_d2h_bytes)."""

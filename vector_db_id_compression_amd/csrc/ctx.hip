@@ -203,6 +203,7 @@ extern "C" {
 const char *vidc_last_error(void) { return vidc::g_last_error.c_str(); }
 int vidc_version(void) { return VIDC_VERSION; }
 int vidc_ctx_class_streams(const vidc_ctx *ctx) { return ctx ? ctx->naux() + 1 : 0; }
+uint32_t vidc_ctx_num_cu(const vidc_ctx *ctx) { return ctx ? (uint32_t)ctx->num_cu : 0u; }
 
 int vidc_ctx_create(int device, vidc_ctx **out) {
     if (!out) return VIDC_ERR_INVALID;
@@ -231,6 +232,13 @@ int vidc_ctx_create(int device, vidc_ctx **out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cu = prop.multiProcessorCount;
     if (const char *e = std::getenv("GPU_MAX_HW_QUEUES")) c->wide = std::atoi(e) >= 8;
     if (const char *e = std::getenv("VIDC_WIDE_STREAMS")) c->wide = e[0] == '1';  // test hook
+    if (const char *e = std::getenv("VIDC_NUM_CU")) {
+        // test hook: size every grid as if the device had n compute units.  It only LOWERS the count (1 <= n < the device's own):
+        // k_roc_rows_compact needs every wavefront of its launch resident, which a grid sized for more CUs than there are would break.
+        char *end = nullptr;
+        const long n = std::strtol(e, &end, 10);
+        if (end != e && *end == '\0' && n >= 1 && n < (long)c->num_cu) c->num_cu = (int)n;
+    }
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
         [&] { for (auto &st : c->aux) if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return true; return false; }() ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
