@@ -449,6 +449,54 @@ int vidc_wt_append_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n_add, const in
 int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int precision_mode, uint32_t flags, vidc_roc **out, int64_t *d_labels, uint64_t *d_invalid);
 
+/* ---------------------------------------------------- merge (two objects over the same lists, device-resident) */
+/* Faiss's InvertedLists::merge_from(other, add_id): an index built in pieces, or sharded by id range, becomes one without leaving
+ * the compressed form.  Objects stay immutable: a merge returns a NEW object in *out, `a` and `b` stay valid and unchanged, any of the
+ * three may be destroyed first (the new object owns all of its memory), and a == b is allowed.
+ *
+ * The merged input.  With a_l and b_l = list l of each object in the object's own order (what vidc_*_decode_lists returns), the merged
+ *   input of list l is
+ *       M_l = a_l ++ [x + add_id for x in b_l]
+ * The result is the object the existing encoder builds from the CSR form of M, word for word (streams, per-list metadata, sizes,
+ *   compressed_bytes, and the permutation when the flag asks for it): vidc_packed_encode with `bits` (0 keeps a's width; a larger width
+ *   re-packs every list; an id that does not fit gives VIDC_ERR_DOMAIN), vidc_ef_encode with `flags`, vidc_wt_build with a's wt_type (M
+ *   must be what vidc_wt_build demands -- a permutation of 0 .. ntotal_new - 1, ascending inside each list; the usual add_id =
+ *   ntotal(a) makes it so -- otherwise the build's status is returned), vidc_roc_encode with `precision_mode` and `flags` (the caller
+ *   passes the mode the objects were built with; the call cannot check it).  A permutation is over positions in M_l: j < |a_l| is a's
+ *   entry at offset j, j >= |a_l| is b's entry at offset j - |a_l|.
+ * ROC.  A list with b_l empty keeps a's stream; a list with a_l empty and add_id == 0 keeps b's stream; both get the identity
+ *   permutation.  That is the from-scratch result whenever the list decodes to its own distinct ids (not for the reference's lossy
+ *   cases -- duplicates, a power-of-two maximum under VIDC_PREC_REFERENCE, more than 65 536 ids -- nor for a `b` built with another
+ *   precision mode, which the call cannot check): the caveat the append states for the lists a batch does not touch.  Every other
+ *   non-empty list is decoded on both sides and re-encoded.
+ * d_src (device int64[ntotal_new], may be NULL): every element is written and nothing outside is.  For position q of the new object's
+ *   decode_all order it holds p >= 0 if the entry is position p of a's decode_all order, and ~p (negative) if it is position p of
+ *   b's: a caller that keeps per-entry payload builds the new payload with one gather.  With a == b the two halves are told apart by
+ *   the sign in the same way.
+ * Status.  NULL ctx / a / b / out, nlist(a) != nlist(b), either object on another device than ctx, ntotal(a) + ntotal(b) >= 2^32 - 1,
+ *   a bad precision_mode or width: VIDC_ERR_INVALID before any device work.  A graph object (rows, Elias-Fano arena) on either side:
+ *   VIDC_ERR_UNSUPPORTED.  A merged ROC list above VIDC_ROC_MAX_LIST, a shifted id >= 2^31 (ROC), a shifted id that does not fit
+ *   `bits` (packed bits) or 64 bits: VIDC_ERR_DOMAIN.  On any error *out == NULL, both sources are untouched and the context stays
+ *   usable.  Two empty objects, or an empty b, give an object equal to a (the wavelet tree is built from ntotal alone: there the result
+ *   equals the build).
+ * Residency.  No id payload crosses PCIe (vidc_ctx_d2h_bytes does not move), and nothing is sorted: both sides are grouped by list
+ *   already.  The new offsets are the sum of the two offset arrays; every list of b goes behind the same list of a as one segmented
+ *   copy, a wavefront per 1024-id chunk, add_id added on the way.  Packed bits, Elias-Fano and the wavelet tree are REBUILT:
+ *   decode_all of both objects into scratch (once when a == b), the placement, the device-offsets encoder; one 8-byte read-back (the
+ *   largest id of b, for the domain checks), no O(nlist) array on the host.  ROC is SPLICED: the lists are classified on the device,
+ *   the numbers and merged sizes of the re-encoded ones are read back once (8 bytes per such list), only those are decoded and
+ *   encoded, every other list's stream is copied from whichever object holds it.  d_src is arithmetic on the three offset arrays
+ *   (packed bits, wavelet tree) or read off the new object's permutation (Elias-Fano, ROC).  The only atomic is the maximum of the
+ *   domain check, which does not depend on the order of its operands: no atomic decides a position, nothing spins, the result is the
+ *   same on every run.  The calls synchronise; vidc_ctx_last_kernel_ms is the sum over the call's kernels.
+ * Out of scope: segmented ROC objects, sharded objects and graph objects; emptying `b` as Faiss does; copy_subset_to. */
+int vidc_packed_merge_dev(vidc_ctx *ctx, const vidc_packed *a, const vidc_packed *b, uint64_t add_id, int bits, vidc_packed **out,
+                          int64_t *d_src);
+int vidc_ef_merge_dev(vidc_ctx *ctx, const vidc_ef *a, const vidc_ef *b, uint64_t add_id, uint32_t flags, vidc_ef **out, int64_t *d_src);
+int vidc_wt_merge_dev(vidc_ctx *ctx, const vidc_wt *a, const vidc_wt *b, uint64_t add_id, vidc_wt **out, int64_t *d_src);
+int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint64_t add_id, int precision_mode, uint32_t flags,
+                       vidc_roc **out, int64_t *d_src);
+
 /* ---------------------------------------------------- remove (batches of pairs, device-resident) */
 /* Objects stay immutable: a remove returns a NEW object in *out, the old one stays valid and unchanged, and either may be destroyed
  * first (the new object owns all of its memory).

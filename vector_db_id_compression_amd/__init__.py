@@ -9,5 +9,6 @@ from ._lib import VIDC_PREC_EXACT, VIDC_PREC_REFERENCE, VidcError  # noqa: F401
 from . import persist  # noqa: F401,E402  (save / load of every container: flat .npz images)
 from . import removal  # noqa: F401,E402  (removal of (list, id) batches from the list containers)
 from . import locate  # noqa: F401,E402  (id -> label: the inverse of translate_labels for the list containers)
+from . import merge  # noqa: F401,E402  (two objects over the same lists -> one: Faiss's merge_from)
 
-__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal", "locate"]
+__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal", "locate", "merge"]

@@ -152,6 +152,11 @@ def _declare(lib):
     f("vidc_ef_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp)
     f("vidc_wt_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp)
     f("vidc_roc_append_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp)
+    # merge (two objects over the same lists, device-resident): ctx, a, b, add_id, codec arguments, out, src
+    f("vidc_packed_merge_dev", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _P(_vp), _vp)
+    f("vidc_ef_merge_dev", C.c_int, _vp, _vp, _vp, _u64, _u32, _P(_vp), _vp)
+    f("vidc_wt_merge_dev", C.c_int, _vp, _vp, _vp, _u64, _P(_vp), _vp)
+    f("vidc_roc_merge_dev", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _u32, _P(_vp), _vp)
     # remove (batches of pairs, device-resident)
     f("vidc_packed_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp, _vp)
     f("vidc_ef_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp, _vp)
@@ -226,6 +231,7 @@ EXPORTED_SYMBOLS = [
     "vidc_packed_translate_labels_dev", "vidc_ef_translate_labels_dev", "vidc_wt_translate_labels_dev", "vidc_roc_translate_labels_dev",
     "vidc_compact_rows_decode_dev", "vidc_ef_decode_rows_dev", "vidc_roc_decode_rows_dev",
     "vidc_packed_append_dev", "vidc_ef_append_dev", "vidc_wt_append_dev", "vidc_roc_append_dev",
+    "vidc_packed_merge_dev", "vidc_ef_merge_dev", "vidc_wt_merge_dev", "vidc_roc_merge_dev",
     "vidc_packed_remove_dev", "vidc_ef_remove_dev", "vidc_roc_remove_dev",
     "vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",

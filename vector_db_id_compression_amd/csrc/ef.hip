@@ -15,6 +15,7 @@
 #include "bits.h"
 #include "chunks.h"
 #include "append.h"
+#include "merge.h"
 #include "remove.h"
 #include "locate.h"
 #include "common.h"
@@ -2889,6 +2890,37 @@ int vidc_ef_append_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_add, const in
         if (st != VIDC_OK) { delete ne; return st; }
         if (!(flags & VIDC_EF_WANT_PERM)) { ne->d_perm.release(); ne->has_perm = false; }
     }
+    *out = ne;
+    return VIDC_OK;
+}
+
+// Merge (include/vidc.h): decode_all of both objects into scratch, the placement of merge.h, the device-offsets encoder on the merged
+// CSR.  An entry's place is its position in the stable ascending order of the merged list: d_src is read off the new object's sort
+// permutation (kept only when the caller asked for it).
+int vidc_ef_merge_dev(vidc_ctx *ctx, const vidc_ef *a, const vidc_ef *b, uint64_t add_id, uint32_t flags, vidc_ef **out, int64_t *d_src) {
+    VIDC_TRY(merge_check(ctx, a, b, out));
+    if (a->rows || a->arena || b->rows || b->arena) { set_error("elias-fano merge: graph objects hold no lists to merge"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    MergeRebuilt m;
+    VIDC_TRY(merge_rebuild(ctx, a->nlist, a->ntotal, b->ntotal, a->d_offsets.p, b->d_offsets.p, add_id, a == b, m,
+                           [&](uint64_t *d) { return vidc_ef_decode_all(ctx, a, d); }, [&](uint64_t *d) { return vidc_ef_decode_all(ctx, b, d); }));
+    if (b->ntotal && merge_shift_overflows(m.max_b, add_id, 64u)) {
+        set_error("elias-fano merge: id %llu + add_id %llu does not fit 64 bits", (unsigned long long)m.max_b, (unsigned long long)add_id);
+        return VIDC_ERR_DOMAIN;
+    }
+    const bool need_perm = d_src && m.ntotal_new;
+    vidc_ef *ne = nullptr;
+    VIDC_TRY(vidc_ef_encode_dev(ctx, a->nlist, m.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), need_perm ? flags | VIDC_EF_WANT_PERM : flags,
+                                &ne));
+    double kernel_ms = m.kernel_ms + ctx->last_kernel_ms;
+    if (need_perm) {
+        if (!ne->has_perm) { delete ne; set_error("elias-fano merge: the encoder kept no permutation"); return VIDC_ERR_INVALID; }
+        const int st = merge_write_src(ctx, a->nlist, m.ntotal_new, a->d_offsets.p, b->d_offsets.p, ne->d_offsets.p, ne->d_perm.p, ne->d_offsets.p,
+                                       nullptr, d_src, kernel_ms);
+        if (st != VIDC_OK) { delete ne; return st; }
+        if (!(flags & VIDC_EF_WANT_PERM)) { ne->d_perm.release(); ne->has_perm = false; }
+    }
+    ctx->last_kernel_ms = kernel_ms;
     *out = ne;
     return VIDC_OK;
 }

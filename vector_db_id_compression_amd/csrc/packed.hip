@@ -13,6 +13,7 @@
 #include "bits.h"
 #include "chunks.h"
 #include "append.h"
+#include "merge.h"
 #include "remove.h"
 #include "locate.h"
 #include "common.h"
@@ -1409,6 +1410,30 @@ int vidc_packed_append_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_add, 
     VIDC_TRY(append_merge(ctx, p->nlist, p->ntotal, p->d_offsets.p, n_add, d_list_nos, d_ids, d_labels, d_invalid, true, m,
                           [&](uint64_t *d) { return vidc_packed_decode_all(ctx, p, d); }));
     return vidc_packed_encode_dev(ctx, p->nlist, m.batch.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), bits ? bits : p->bits, out);
+}
+
+// Merge (include/vidc.h): decode_all of both objects into scratch, the placement of merge.h, the device-offsets encoder on the merged
+// CSR.  d_src of this input-order container is arithmetic on the three offset arrays.
+int vidc_packed_merge_dev(vidc_ctx *ctx, const vidc_packed *a, const vidc_packed *b, uint64_t add_id, int bits, vidc_packed **out,
+                          int64_t *d_src) {
+    VIDC_TRY(merge_check(ctx, a, b, out));
+    if (bits < 0 || bits > 64) { set_error("packed merge: bits must be 0 (keep) .. 64"); return VIDC_ERR_INVALID; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    const int nbits = bits ? bits : a->bits;
+    MergeRebuilt m;
+    VIDC_TRY(merge_rebuild(ctx, a->nlist, a->ntotal, b->ntotal, a->d_offsets.p, b->d_offsets.p, add_id, a == b, m,
+                           [&](uint64_t *d) { return vidc_packed_decode_all(ctx, a, d); },
+                           [&](uint64_t *d) { return vidc_packed_decode_all(ctx, b, d); }));
+    if (b->ntotal && merge_shift_overflows(m.max_b, add_id, (uint32_t)nbits)) return packed_id_does_not_fit(nbits);
+    vidc_packed *np = nullptr;
+    VIDC_TRY(vidc_packed_encode_dev(ctx, a->nlist, m.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), nbits, &np));
+    double kernel_ms = m.kernel_ms + ctx->last_kernel_ms;
+    const int st = merge_write_src(ctx, a->nlist, m.ntotal_new, a->d_offsets.p, b->d_offsets.p, np->d_offsets.p, nullptr, nullptr, nullptr, d_src,
+                                   kernel_ms);
+    if (st != VIDC_OK) { delete np; return st; }
+    ctx->last_kernel_ms = kernel_ms;
+    *out = np;
+    return VIDC_OK;
 }
 
 // Remove (include/vidc.h): decode_all into scratch, the shared mark and compaction (remove.h), the device-offsets encoder on the

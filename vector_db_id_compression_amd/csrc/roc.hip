@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "append.h"
+#include "merge.h"
 #include "remove.h"
 #include "locate.h"
 #include "common.h"
@@ -1730,6 +1731,17 @@ struct RocUpdateSlots {
         return sl != 0u || j < N_old;
     }
 };
+// ... and the class table of vidc_roc_merge_dev (merge.h), built on the device: source cls[j] = 0 is `a`, 1 is `b` -- list j of
+// either --, 2 is the fresh encode of the lists that hold ids of both sides, list tpos[j] of it.
+struct RocMergeSlots {
+    const uint32_t *cls;
+    const uint64_t *tpos;
+    __device__ __forceinline__ bool get(uint64_t j, uint32_t &s, uint64_t &k) const {
+        s = cls[j];
+        k = s == MRG_ENCODE ? tpos[j] : j;
+        return true;
+    }
+};
 // the five per-list arrays of the new object (sizes: what the scan turns into its offsets); *nonempty (may be NULL) += lists with ids
 template <typename Lookup>
 __global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs srcs, Lookup look, uint64_t m, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
@@ -2327,6 +2339,195 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
     }
     kernel_ms += tm.stop();
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    ctx->last_kernel_ms = kernel_ms;
+    tr.mark("spliced");
+    *out = nr.release();
+    return VIDC_OK;
+}
+
+// Merge (include/vidc.h).  The lists are classified on the device (merge.h): a list without ids of `b` keeps a's stream, a list
+// without ids of `a` keeps b's when nothing is shifted, every other list is re-encoded.  The numbers and merged sizes of the
+// re-encoded lists come back once (8 bytes each, metadata); the host sizes a staging CSR of them, a's ids are decoded into it
+// (plan_decode / decode_impl on the subset), b's into a staging of their own and from there behind a's with add_id added
+// (k_mrg_copy_add, which also reduces the largest id for the domain check), and encode_impl runs on the staging CSR alone.  The new
+// object is spliced as vidc_roc_update_rows_dev splices: metadata gathered from {a, b, the small object} through the class table, one
+// scan launch set for the offsets and the word offsets, a chunked copy of every list's words from whichever object holds them.  Like
+// an imported object the result carries no planner hints.
+int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint64_t add_id, int precision_mode, uint32_t flags, vidc_roc **out,
+                       int64_t *d_src) {
+    VIDC_TRY(merge_check(ctx, a, b, out));
+    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
+        set_error("roc merge: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
+        return VIDC_ERR_INVALID;
+    }
+    if (a->rows || b->rows) { set_error("roc merge: graph objects hold no lists to merge"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_TRY(a->prec.size() == a->nlist ? ensure_offsets(a) : ensure_meta(a));
+    if (b != a) VIDC_TRY(b->prec.size() == b->nlist ? ensure_offsets(b) : ensure_meta(b));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc merge");
+    const uint64_t nlist = a->nlist;
+    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0, need_perm = want_perm || d_src;
+    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    double kernel_ms = 0;
+    std::unique_ptr<vidc_roc> small, nr;
+    Scratch s_cls, s_off, s_touched, s_t0, s_t1, s_stage, s_bstage, s_sizes, s_cnt;
+    Pinned h_back;
+    AppChunks ch_b, ch_w, ch_p;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
+    VIDC_TRY(s_cls.get(ctx, 5 * (nlist + 1) * 4));      // cls | flag | mark | bmark | slot
+    VIDC_TRY(s_off.get(ctx, 4 * (nlist + 1) * 8));      // stage_off | tpos | bstage_off | dst_start
+    VIDC_TRY(s_touched.get(ctx, 2 * (nlist + 1) * 4));  // touched | msize
+    VIDC_TRY(s_sizes.get(ctx, (nlist + 1) * 4));
+    VIDC_TRY(s_cnt.get(ctx, 16));                       // non-empty lists | largest id of b's re-encoded lists
+    VIDC_TRY(h_back.get(ctx, 32 + (nlist + 1) * 8));
+    uint32_t *cls = s_cls.as<uint32_t>(), *flag = cls + nlist + 1, *mark = flag + nlist + 1, *bmark = mark + nlist + 1, *slot = bmark + nlist + 1;
+    uint64_t *stage_off = s_off.as<uint64_t>(), *tpos = stage_off + nlist + 1, *bstage_off = tpos + nlist + 1, *dst_start = bstage_off + nlist + 1;
+    uint32_t *d_touched = s_touched.as<uint32_t>(), *d_msize = d_touched + nlist + 1;
+    uint64_t *h_cnt = h_back.as<uint64_t>();  // re-encoded lists | largest id | word total | non-empty lists
+    uint32_t *h_touched = (uint32_t *)(h_cnt + 4), *h_msize = h_touched + nlist + 1;
+    h_cnt[0] = h_cnt[1] = h_cnt[2] = h_cnt[3] = 0;
+    const uint64_t *a_off = a->d_offsets.p, *b_off = b->d_offsets.p;
+    EventTimer tm = EventTimer::started(ctx);
+    if (nlist) {
+        hipLaunchKernelGGL(k_mrg_roc_classify, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, a_off, b_off, nlist, add_id != 0, cls, flag, mark, bmark);
+        Scan4 sc{};
+        sc.in[0] = mark; sc.in[1] = flag; sc.in[2] = bmark; sc.out[0] = stage_off; sc.out[1] = tpos; sc.out[2] = bstage_off;
+        VIDC_TRY(device_exscan4(ctx, sc, 3, (uint32_t)nlist, s_t0));
+        hipLaunchKernelGGL(k_mrg_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)flag, (const uint64_t *)tpos,
+                           (const uint32_t *)mark, (const uint64_t *)stage_off, a_off, nlist, d_touched, d_msize, slot, dst_start);
+        VIDC_HIP(hipGetLastError());
+        (void)tm.mark();
+        VIDC_HIP(hipMemcpyAsync(h_cnt, tpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        (void)tm.mark();
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    kernel_ms += tm.elapsed();
+    const uint64_t cnt = h_cnt[0];
+    if (cnt) {
+        VIDC_HIP(hipMemcpyAsync(h_touched, d_touched, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_msize, d_msize, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    }
+    // staging CSRs of the re-encoded lists: the merged lists, and b's decoded part of them
+    std::vector<uint64_t> st_off(cnt + 1, 0), bst_off(cnt + 1, 0);
+    std::vector<uint32_t> dec_a, dec_a_slot, dec_b;  // re-encoded lists that hold ids of a (and their number among the re-encoded); of b: all
+    for (uint64_t k = 0; k < cnt; k++) {
+        const uint64_t l = h_touched[k], a_n = a->offsets[l + 1] - a->offsets[l], b_n = b->offsets[l + 1] - b->offsets[l], n = h_msize[k];
+        if (n != a_n + b_n) { set_error("roc merge: list %llu: the device and the host disagree about its size", (unsigned long long)l); return VIDC_ERR_INVALID; }
+        if (n > VIDC_ROC_MAX_LIST) {
+            set_error("roc merge: list %llu would hold %llu ids (limit %u)", (unsigned long long)l, (unsigned long long)n, VIDC_ROC_MAX_LIST);
+            return VIDC_ERR_DOMAIN;
+        }
+        st_off[k + 1] = st_off[k] + n;
+        bst_off[k + 1] = bst_off[k] + b_n;
+        if (a_n) { dec_a.push_back((uint32_t)l); dec_a_slot.push_back((uint32_t)k); }
+        dec_b.push_back((uint32_t)l);
+    }
+    const uint64_t total = st_off[cnt], btotal = bst_off[cnt];
+    tr.mark("lists classified, re-encoded lists read back");
+    if (cnt) {
+        VIDC_TRY(s_stage.get(ctx, total * 8));
+        VIDC_TRY(s_bstage.get(ctx, btotal * 8));
+        if (!dec_a.empty()) {
+            PooledDecPlan p;
+            plan_decode(a, dec_a, false, p, ctx->wide);
+            std::vector<uint64_t> out_off(dec_a.size());
+            for (size_t k = 0; k < dec_a.size(); k++) out_off[k] = st_off[dec_a_slot[p.item[k]]];  // work item k -> its place in the staging
+            VIDC_TRY(decode_impl(ctx, a, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+            kernel_ms += ctx->last_kernel_ms;
+        }
+        {
+            PooledDecPlan p;
+            plan_decode(b, dec_b, false, p, ctx->wide);
+            std::vector<uint64_t> out_off(cnt);
+            for (size_t k = 0; k < cnt; k++) out_off[k] = bst_off[p.item[k]];
+            VIDC_TRY(decode_impl(ctx, b, p, out_off.data(), s_bstage.as<uint64_t>(), nullptr, 0));
+            kernel_ms += ctx->last_kernel_ms;
+        }
+        tr.mark("re-encoded lists decoded on both sides");
+        (void)tm.start();
+        VIDC_HIP(hipMemsetAsync(s_cnt.as<uint64_t>() + 1, 0, 8, ctx->stream));
+        VIDC_TRY(app_chunks(ctx, bstage_off, nlist, btotal, ch_b));
+        hipLaunchKernelGGL(k_mrg_copy_add, app_chunk_grid(ctx, ch_b.bound), dim3(256), 0, ctx->stream, (const uint64_t *)s_bstage.as<uint64_t>(),
+                           (const uint64_t *)bstage_off, (const uint64_t *)dst_start, s_stage.as<uint64_t>(), add_id, ch_b.items, ch_b.n_items,
+                           s_cnt.as<unsigned long long>() + 1);
+        VIDC_HIP(hipGetLastError());
+        (void)tm.mark();
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, s_cnt.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        kernel_ms += tm.elapsed();
+        if (merge_shift_overflows(h_cnt[1], add_id, 31u)) {
+            set_error("roc merge: id %llu + add_id %llu is outside [0, 2^31)", (unsigned long long)h_cnt[1], (unsigned long long)add_id);
+            return VIDC_ERR_DOMAIN;
+        }
+        vidc_roc *sp = nullptr;
+        VIDC_TRY(encode_impl(ctx, cnt, st_off.data(), s_stage.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
+                             need_perm ? VIDC_ROC_WANT_PERM : 0u, &sp));
+        small.reset(sp);
+        kernel_ms += ctx->last_kernel_ms;
+        tr.mark("re-encoded lists encoded");
+    }
+    // splice
+    nr.reset(new vidc_roc());
+    nr->device = ctx->device;
+    nr->nlist = nlist;
+    nr->ntotal = a->ntotal + b->ntotal;
+    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
+    nr->offsets.resize(nlist + 1);
+    for (uint64_t l = 0; l <= nlist; l++) nr->offsets[l] = a->offsets[l] + b->offsets[l];
+    nr->offsets_host = true;
+    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
+    RocSrcs S{};
+    S.s[MRG_KEEP_A] = RocSrc{{a->d_heads.p, a->d_prec.p, a->d_nwords.p, a->d_draws.p}, a->d_words.p, a->d_word_off.p, a->d_offsets.p};
+    S.s[MRG_KEEP_B] = RocSrc{{b->d_heads.p, b->d_prec.p, b->d_nwords.p, b->d_draws.p}, b->d_words.p, b->d_word_off.p, b->d_offsets.p};
+    if (small)
+        S.s[MRG_ENCODE] = RocSrc{{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p}, small->d_words.p, small->d_word_off.p,
+                                 small->d_offsets.p};
+    const RocMergeSlots look{cls, tpos};
+    (void)tm.start();
+    if (nlist) {
+        VIDC_HIP(hipMemsetAsync(s_cnt.p, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(k_roc_regroup_meta<RocMergeSlots>, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, S, look, nlist, nr->d_heads.p,
+                           nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>(), s_cnt.as<unsigned long long>());
+        VIDC_HIP(hipGetLastError());
+        Scan4 sc{};
+        sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t1));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 3, s_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_cnt[2];
+    nr->compressed_bytes = 8ull * h_cnt[3] + 4ull * nr->total_words;
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, ch_w));
+        hipLaunchKernelGGL(k_roc_regroup_copy<RocMergeSlots>, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S, look,
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
+        VIDC_HIP(hipGetLastError());
+    }
+    if (want_perm && nr->ntotal) {
+        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, ch_p));
+        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
+                           (const uint32_t *)slot, small ? (const uint32_t *)small->d_perm.p : nullptr,
+                           small ? (const uint64_t *)small->d_offsets.p : nullptr, ch_p.items, ch_p.n_items, nr->d_perm.p);
+        VIDC_HIP(hipGetLastError());
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    // where every entry came from: the small object's permutation names the input position of a re-encoded list's entries, the kept
+    // lists decode in their source's order
+    VIDC_TRY(merge_write_src(ctx, nlist, nr->ntotal, a_off, b_off, nr->d_offsets.p, small ? (const uint32_t *)small->d_perm.p : nullptr,
+                             small ? (const uint64_t *)small->d_offsets.p : nullptr, slot, d_src, kernel_ms));
+    guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
     tr.mark("spliced");
     *out = nr.release();

@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "append.h"
+#include "merge.h"
 #include "bits.h"
 #include "common.h"
 #include "dev_offsets.h"
@@ -1714,6 +1715,25 @@ int vidc_wt_append_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n_add, const in
     VIDC_TRY(append_merge(ctx, w->nlist, w->ntotal, w->d_C.p, n_add, d_list_nos, d_ids, d_labels, d_invalid, true, m,
                           [&](uint64_t *d) { return vidc_wt_decode_all(ctx, w, d); }));
     return vidc_wt_build_dev(ctx, w->nlist, m.batch.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), w->wt_type, out);
+}
+
+// Merge (include/vidc.h): decode_all of both objects into scratch, the placement of merge.h, vidc_wt_build_dev on the merged CSR with
+// a's wt_type -- which checks what the reference asserts of it (add_id = ntotal(a) makes it so).  d_src of this container (ascending
+// lists, and M_l must be ascending) is arithmetic on the three offset arrays.
+int vidc_wt_merge_dev(vidc_ctx *ctx, const vidc_wt *a, const vidc_wt *b, uint64_t add_id, vidc_wt **out, int64_t *d_src) {
+    VIDC_TRY(merge_check(ctx, a, b, out));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    MergeRebuilt m;
+    VIDC_TRY(merge_rebuild(ctx, a->nlist, a->ntotal, b->ntotal, a->d_C.p, b->d_C.p, add_id, a == b, m,
+                           [&](uint64_t *d) { return vidc_wt_decode_all(ctx, a, d); }, [&](uint64_t *d) { return vidc_wt_decode_all(ctx, b, d); }));
+    vidc_wt *nw = nullptr;
+    VIDC_TRY(vidc_wt_build_dev(ctx, a->nlist, m.new_off, m.ntotal_new, m.s_merged.as<uint64_t>(), a->wt_type, &nw));
+    double kernel_ms = m.kernel_ms + ctx->last_kernel_ms;
+    const int st = merge_write_src(ctx, a->nlist, m.ntotal_new, a->d_C.p, b->d_C.p, nw->d_C.p, nullptr, nullptr, nullptr, d_src, kernel_ms);
+    if (st != VIDC_OK) { delete nw; return st; }
+    ctx->last_kernel_ms = kernel_ms;
+    *out = nw;
+    return VIDC_OK;
 }
 
 int vidc_wt_decode_lists(vidc_ctx *ctx, const vidc_wt *w, uint64_t m, const uint64_t *list_nos, uint64_t *d_out,

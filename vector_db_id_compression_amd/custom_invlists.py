@@ -172,6 +172,37 @@ class InvertedListsArrayCodes:
         """whether a fresh constructor keeps the codec's permutation (the new object then does as well)"""
         return False
 
+    # -- union: two containers over the same lists become one.  The compressed ids go through the codec's merge (vidc_*_merge_dev).
+    def _merge_args(self, other):
+        """the codec arguments of merge.merge for this container"""
+        return {}
+
+    def merge_from(self, other, add_id=0):
+        """Faiss's InvertedLists::merge_from(other, add_id): every list of `other` goes behind the same list of this container, add_id
+        added to its ids.  `other` is a container of the same class, list count and code size (it may be this one).  A new codec
+        object replaces `self._c` (merge.merge), codes_all is rebuilt with one gather through the merge's `src`, and offsets, ntotal
+        and the size attributes become what a fresh container over the merged lists reports.  `other` is left unchanged -- Faiss
+        empties it; a caller that wants that drops its reference."""
+        from . import merge
+
+        if type(other) is not type(self):
+            raise TypeError(f"merge_from: {type(other).__name__} is not a {type(self).__name__}")
+        if other.nlist != self.nlist or other.code_size != self.code_size:
+            raise ValueError(f"merge_from: nlist / code_size differ ({other.nlist} / {other.code_size} against {self.nlist} / {self.code_size})")
+        torch = _torch()
+        n_a, n_b = self.ntotal, other.ntotal
+        src = torch.empty(n_a + n_b, dtype=torch.int64, device="cuda")
+        new_c = merge.merge(self._c, other._c, int(add_id), src=src, **self._merge_args(other))
+        if self.code_size:
+            rows = torch.where(src >= 0, src, n_a + ~src)
+            self.codes_all = torch.cat([self.codes_all, other.codes_all])[rows]
+        self._c = new_c
+        self._offsets = (self._offsets.astype(np.uint64) + other._offsets.astype(np.uint64)).astype(np.uint64)
+        self.ntotal = n_a + n_b
+        # (vectors ever added = those of both sides, also when other is this container: what _merge_args sized the width by)
+        self._n_removed = getattr(self, "_n_removed", 0) + getattr(other, "_n_removed", 0)
+        self._refresh_sizes()
+
     # -- batched helpers shared by the subclasses
     def get_single_id(self, list_no, offset):
         return int(self.get_single_ids([list_no], [offset])[0])
@@ -230,6 +261,10 @@ class CompressedIDInvertedListsPackedBits(InvertedListsArrayCodes):
         new_c, labels = self._c.append(list_nos, ids, bits=PackedLists.bits_for(ntotal_new), invalid=invalid)
         return new_c, labels, None
 
+    def _merge_args(self, other):
+        # the width a fresh container takes for the merged index (:68-70), over the vectors ever added on both sides (see _append_ids)
+        return dict(bits=PackedLists.bits_for(self.ntotal + other.ntotal + getattr(self, "_n_removed", 0) + getattr(other, "_n_removed", 0)))
+
     def get_ids_all(self):
         return self._c.decode_all()
 
@@ -266,6 +301,9 @@ class CompressedIDInvertedListsFenwickTree(InvertedListsArrayCodes):
         want = self.code_size > 0
         new_c, labels = self._c.append(list_nos, ids, want_perm=want, invalid=invalid)  # (the constructor's precision mode)
         return new_c, labels, (new_c.perm() if want else None)
+
+    def _merge_args(self, other):
+        return dict(want_perm=self.code_size > 0)  # (the constructor's precision mode)
 
     def get_ids_all(self):
         return self._c.decode_all()
@@ -305,6 +343,9 @@ class CompressedIDInvertedListsEliasFano(InvertedListsArrayCodes):
         new_c, labels = self._c.append(list_nos, ids, want_perm=want, invalid=invalid)
         return new_c, labels, (new_c.perm() if want else None)
 
+    def _merge_args(self, other):
+        return dict(want_perm=self.code_size > 0)
+
     def get_ids_all(self):
         return self._c.decode_all()
 
@@ -336,6 +377,11 @@ class CompressedIDInvertedListsWaveletTree(InvertedListsArrayCodes):
 
     def remove_batch(self, list_nos, ids):
         raise RuntimeError("not implemented: a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks")
+
+    def _merge_args(self, other):
+        if other.wt_type != self.wt_type:
+            raise ValueError(f"merge_from: wt_type differs ({other.wt_type} against {self.wt_type})")
+        return {}
 
     def get_ids_all(self):
         return self._c.decode_all()
@@ -376,6 +422,9 @@ class CompressedIDInvertedListsROCSegmented(InvertedListsArrayCodes):
 
     def locate_batch(self, list_nos, ids):
         raise RuntimeError("not implemented: segmented ROC lists have no locate (use the FenwickTree container)")
+
+    def merge_from(self, other, add_id=0):
+        raise RuntimeError("not implemented: segmented ROC lists have no merge (re-encode, or use the FenwickTree container)")
 
     def get_ids_all(self):
         return self._c.decode_all()

@@ -145,6 +145,35 @@ class IVFIndex:
         self._dev = None
         return n
 
+    def merge_from(self, other, add_id=None):
+        """IndexIVF::merge_from: every list of `other` goes behind the same list of this index, add_id added to its ids (None: the
+        number of vectors ever added here, so ids stay distinct).  Both indexes must share d, nlist, code, centroids (and PQ
+        codebooks) and the class of their inverted lists.  A compressed container merges on the device (its merge_from);
+        ArrayInvertedLists is merged on the host.  `other` is left unchanged (Faiss empties it)."""
+        if not isinstance(other, IVFIndex):
+            raise TypeError("merge_from: other must be an IVFIndex")
+        if (other.d, other.nlist, other.code) != (self.d, self.nlist, self.code):
+            raise ValueError("merge_from: d, nlist or code differ")
+        for mine, theirs, what in ((self.centroids, other.centroids, "centroids"), (self.pq, other.pq, "PQ codebooks")):
+            if (mine is None) != (theirs is None) or (mine is not None and not _torch().equal(mine, theirs)):
+                raise ValueError(f"merge_from: the {what} differ")
+        il, ol = self.invlists, other.invlists
+        if type(il) is not type(ol):
+            raise TypeError(f"merge_from: the inverted lists are a {type(il).__name__} and a {type(ol).__name__}")
+        add_id = self._next_id if add_id is None else int(add_id)
+        if isinstance(il, ArrayInvertedLists):
+            for l in range(il.nlist):
+                ids, codes = ol._ids[l] + add_id, ol._codes[l]  # (read before the append: other may be this index)
+                if ids.size:
+                    il.add_entries(l, ids, codes)
+        elif hasattr(il, "merge_from"):
+            il.merge_from(ol, add_id)
+        else:
+            raise RuntimeError("merge_from: the inverted lists are read-only")
+        self.ntotal += other.ntotal
+        self._next_id = max(self._next_id, add_id + other._next_id)
+        self._dev = None
+
     def reconstruct_batch(self, ids):
         """IndexIVF::reconstruct_batch through the direct map: the stored vectors of `ids` -> float32 CUDA tensor [n, d].  A compressed
         container locates the ids on the device (locate_batch, any-list mode); ArrayInvertedLists is searched on the host.  Raises
