@@ -489,7 +489,8 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
  *   (packed bits, wavelet tree) or read off the new object's permutation (Elias-Fano, ROC).  The only atomic is the maximum of the
  *   domain check, which does not depend on the order of its operands: no atomic decides a position, nothing spins, the result is the
  *   same on every run.  The calls synchronise; vidc_ctx_last_kernel_ms is the sum over the call's kernels.
- * Out of scope: segmented ROC objects, sharded objects and graph objects; emptying `b` as Faiss does; copy_subset_to. */
+ * Out of scope: segmented ROC objects, sharded objects and graph objects; emptying `b` as Faiss does.  (The inverse, Faiss's
+ *   copy_subset_to, is the "subset" section behind the remove.) */
 int vidc_packed_merge_dev(vidc_ctx *ctx, const vidc_packed *a, const vidc_packed *b, uint64_t add_id, int bits, vidc_packed **out,
                           int64_t *d_src);
 int vidc_ef_merge_dev(vidc_ctx *ctx, const vidc_ef *a, const vidc_ef *b, uint64_t add_id, uint32_t flags, vidc_ef **out, int64_t *d_src);
@@ -540,6 +541,62 @@ int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int
                        uint32_t flags, vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
 int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int precision_mode, uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid);
+
+/* ---------------------------------------------------- subset (a part of every list, chosen by rule, device-resident) */
+/* Faiss's InvertedLists::copy_subset_to(other, subset_type, a1, a2), the inverse of the merge: an index is split into shards by id
+ * range, id residue, list range or list fraction, and vidc_*_merge_dev puts the shards back together.  Objects stay immutable: a subset
+ * returns a NEW object over the same nlist lists in *out, the source stays valid and unchanged, and either may be destroyed first (the
+ * new object owns all of its memory).
+ *
+ * Notation.  old_l = list l of the object in the object's own order (what vidc_*_decode_lists returns), n = |old_l|, off[] = the
+ *   object's offsets, T = ntotal.  Ids and all arithmetic are unsigned 64-bit.
+ * Which entries are taken.  Entry i of list l, holding `id`, is taken iff
+ *     VIDC_SUBSET_ID_RANGE (0)          a1 <= id < a2
+ *     VIDC_SUBSET_ID_MOD (1)            id % a1 == a2                                        (needs a1 >= 1, a2 < a1)
+ *     VIDC_SUBSET_ELEMENT_RANGE (2)     i1 <= i < i2 with i1 = floor(off[l + 1] * a1 / T) - floor(off[l] * a1 / T) and i2 the same
+ *                                       with a2                                              (needs a1 <= a2 <= T)
+ *     VIDC_SUBSET_INVLIST_FRACTION (3)  floor(n * a2 / a1) <= i < floor(n * (a2 + 1) / a1)   (needs 1 <= a1 < 2^32, a2 < a1)
+ *     VIDC_SUBSET_INVLIST (4)           a1 <= l < a2                  (bounds above nlist are clamped; a1 >= a2 takes nothing)
+ *   Type 2: the bounds are local offsets computed from running totals, so i1 may exceed i2, and then nothing is taken from that list
+ *   (offsets 0, 3, 4, 10 with a1 = 3, a2 = 4 give list 1 i1 = 1, i2 = 0); i2 <= n always holds under the stated condition; all
+ *   products fit 64 bits because T < 2^32.  T == 0 returns an empty object for every type.
+ * The result.  With S_l = the taken entries of old_l, order kept, the new object is the one the existing encoder builds from the CSR
+ *   form of S, word for word (streams, per-list metadata, sizes, compressed_bytes, and the permutation when the flag asks for it, which
+ *   is over positions in S_l): vidc_packed_encode with the object's own width, vidc_ef_encode with `flags`, vidc_roc_encode with
+ *   `precision_mode` and `flags` (the caller passes the mode the object was built with; the call cannot check it).  A ROC list that
+ *   keeps every entry keeps its stream and gets the identity permutation: that is the from-scratch result whenever the list decodes
+ *   to its own distinct ids (not for the reference's lossy cases -- duplicates, a power-of-two maximum under VIDC_PREC_REFERENCE, more
+ *   than 65 536 ids), the caveat the remove states.  A list that keeps nothing becomes empty without any decode.
+ * d_taken (device uint8[T], may be NULL): every byte is written -- 1 where the entry at that position of the source's decode_all order
+ *   is in the subset, 0 elsewhere; nothing outside the T bytes is written.  A caller that keeps per-entry payload (the vector codes)
+ *   takes the same rows.  *n_taken (host, may be NULL) = the size of the subset.
+ * Status.  NULL ctx / object / out, a subset_type outside 0 .. 4, an argument condition above violated, a bad precision_mode:
+ *   VIDC_ERR_INVALID before any device work.  A graph object (rows, Elias-Fano arena): VIDC_ERR_UNSUPPORTED.  On any error
+ *   *out == NULL, the source is untouched and the context stays usable.
+ * Residency.  No id payload crosses PCIe (vidc_ctx_d2h_bytes, which counts id payload, does not move: what comes back are counts and
+ *   list numbers).  Types 0 and 1 evaluate the predicate on the decoded ids, a wavefront per 1024-id chunk, and place the taken entries
+ *   by a scan of per-chunk counts as a remove places its survivors; for ID_MOD a power-of-two a1 is a mask and a1 < 2^32 reduces the
+ *   high half of the id first.  Types 2 .. 4 need no mark: one thread per list computes [i1, i2) from the offsets alone, a scan gives
+ *   the new offsets and a segmented copy takes old_l[i1:i2] to its place.  Packed bits and Elias-Fano are REBUILT: decode_all into
+ *   scratch, the mark and the compaction or the slice, the device-offsets encoder; one 8-byte read-back (the size of the subset).  ROC is
+ *   SPLICED: type 4 decodes nothing -- every kept list's stream is copied, the other lists are empty; types 2 and 3 decode, slice and
+ *   re-encode only the lists that keep a part (the host finds them on its mirror of the offsets); types 0 and 1 take every non-empty
+ *   list as a candidate, as the remove's any-list mode does -- lists that keep everything keep their stream, the others are re-encoded
+ *   (their numbers and sizes are read back, 8 bytes per such list).  No atomic decides a position, nothing spins, the result is the
+ *   same on every run.  The calls synchronise; vidc_ctx_last_kernel_ms is the sum over the call's kernels.
+ * There is no wavelet-tree form (a wavelet tree holds a permutation of 0 .. ntotal - 1, which a subset breaks).  Segmented ROC objects
+ *   and sharded objects are out of scope. */
+#define VIDC_SUBSET_ID_RANGE 0
+#define VIDC_SUBSET_ID_MOD 1
+#define VIDC_SUBSET_ELEMENT_RANGE 2
+#define VIDC_SUBSET_INVLIST_FRACTION 3
+#define VIDC_SUBSET_INVLIST 4
+int vidc_packed_subset_dev(vidc_ctx *ctx, const vidc_packed *p, int subset_type, uint64_t a1, uint64_t a2, vidc_packed **out,
+                           uint8_t *d_taken, uint64_t *n_taken);
+int vidc_ef_subset_dev(vidc_ctx *ctx, const vidc_ef *e, int subset_type, uint64_t a1, uint64_t a2, uint32_t flags, vidc_ef **out,
+                       uint8_t *d_taken, uint64_t *n_taken);
+int vidc_roc_subset_dev(vidc_ctx *ctx, const vidc_roc *r, int subset_type, uint64_t a1, uint64_t a2, int precision_mode, uint32_t flags,
+                        vidc_roc **out, uint8_t *d_taken, uint64_t *n_taken);
 
 /* ---------------------------------------------------- locate (batches of pairs, device-resident) */
 /* The inverse of translate_labels -- Faiss's direct map (DirectMap, reconstruct, update_vectors): at which (list, offset) does an id

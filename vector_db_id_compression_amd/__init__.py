@@ -10,5 +10,6 @@ from . import persist  # noqa: F401,E402  (save / load of every container: flat 
 from . import removal  # noqa: F401,E402  (removal of (list, id) batches from the list containers)
 from . import locate  # noqa: F401,E402  (id -> label: the inverse of translate_labels for the list containers)
 from . import merge  # noqa: F401,E402  (two objects over the same lists -> one: Faiss's merge_from)
+from . import subset  # noqa: F401,E402  (a part of every list, chosen by rule -> a new object: Faiss's copy_subset_to)
 
-__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal", "locate", "merge"]
+__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal", "locate", "merge", "subset"]

@@ -161,6 +161,10 @@ def _declare(lib):
     f("vidc_packed_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _P(_vp), _vp, _vp, _vp)
     f("vidc_ef_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u32, _P(_vp), _vp, _vp, _vp)
     f("vidc_roc_remove_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, C.c_int, _u32, _P(_vp), _vp, _vp, _vp)
+    # subset (Faiss's copy_subset_to): a subset type and two arguments -> a NEW object, the taken mask, the size of the subset
+    f("vidc_packed_subset_dev", C.c_int, _vp, _vp, C.c_int, _u64, _u64, _P(_vp), _vp, _P(_u64))
+    f("vidc_ef_subset_dev", C.c_int, _vp, _vp, C.c_int, _u64, _u64, _u32, _P(_vp), _vp, _P(_u64))
+    f("vidc_roc_subset_dev", C.c_int, _vp, _vp, C.c_int, _u64, _u64, C.c_int, _u32, _P(_vp), _vp, _P(_u64))
     # locate (batches of pairs, device-resident): ctx, obj, n, list_nos, ids, labels, missing, invalid
     for name in ("vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev"):
         f(name, C.c_int, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
@@ -233,6 +237,7 @@ EXPORTED_SYMBOLS = [
     "vidc_packed_append_dev", "vidc_ef_append_dev", "vidc_wt_append_dev", "vidc_roc_append_dev",
     "vidc_packed_merge_dev", "vidc_ef_merge_dev", "vidc_wt_merge_dev", "vidc_roc_merge_dev",
     "vidc_packed_remove_dev", "vidc_ef_remove_dev", "vidc_roc_remove_dev",
+    "vidc_packed_subset_dev", "vidc_ef_subset_dev", "vidc_roc_subset_dev",
     "vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
     "vidc_shards_encode", "vidc_shards_encode_dev", "vidc_shards_destroy", "vidc_shards_count", "vidc_shards_kind", "vidc_shards_nlist",

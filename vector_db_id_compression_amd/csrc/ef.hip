@@ -17,6 +17,7 @@
 #include "append.h"
 #include "merge.h"
 #include "remove.h"
+#include "subset.h"
 #include "locate.h"
 #include "common.h"
 #include "dev_offsets.h"
@@ -2947,6 +2948,22 @@ int ef_remove(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_l
 int vidc_ef_remove_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, uint32_t flags,
                        vidc_ef **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return ef_remove(ctx, e, n_rm, d_list_nos, d_ids, flags, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+// Subset (include/vidc.h): decode_all into scratch, the predicate mark and the compaction or the slice (subset.h), the device-offsets
+// encoder on the subset's CSR.  A subset of an ascending list is ascending: the encoder stays on its sorted path.
+int vidc_ef_subset_dev(vidc_ctx *ctx, const vidc_ef *e, int subset_type, uint64_t a1, uint64_t a2, uint32_t flags, vidc_ef **out,
+                       uint8_t *d_taken, uint64_t *n_taken) {
+    VIDC_TRY(subset_check("elias-fano", ctx, e, out, subset_type, a1, a2));
+    if (e->rows || e->arena) { set_error("elias-fano subset: graph objects hold no lists to take a subset of"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_HIP(hipSetDevice(ctx->device));
+    SubsetRebuilt m;
+    VIDC_TRY(subset_rebuild(ctx, e->nlist, e->ntotal, e->d_offsets.p, subset_type, a1, a2, d_taken, m,
+                            [&](uint64_t *d) { return vidc_ef_decode_all(ctx, e, d); }));
+    VIDC_TRY(vidc_ef_encode_dev(ctx, e->nlist, m.new_off, m.ntotal_new, m.s_out.as<uint64_t>(), flags, out));
+    ctx->last_kernel_ms += m.kernel_ms;
+    if (n_taken) *n_taken = m.ntotal_new;
+    return VIDC_OK;
 }
 
 // Locate (include/vidc.h): decode_all into scratch, the mark and the labels of locate.h.  The offsets are positions in the ascending

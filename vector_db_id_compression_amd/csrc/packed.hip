@@ -15,6 +15,7 @@
 #include "append.h"
 #include "merge.h"
 #include "remove.h"
+#include "subset.h"
 #include "locate.h"
 #include "common.h"
 #include "dev_offsets.h"
@@ -1457,6 +1458,21 @@ int packed_remove(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int6
 int vidc_packed_remove_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids,
                            vidc_packed **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return packed_remove(ctx, p, n_rm, d_list_nos, d_ids, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+// Subset (include/vidc.h): decode_all into scratch, the predicate mark and the compaction or the slice (subset.h), the device-offsets
+// encoder on the subset's CSR at the object's own width.
+int vidc_packed_subset_dev(vidc_ctx *ctx, const vidc_packed *p, int subset_type, uint64_t a1, uint64_t a2, vidc_packed **out, uint8_t *d_taken,
+                           uint64_t *n_taken) {
+    VIDC_TRY(subset_check("packed", ctx, p, out, subset_type, a1, a2));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    SubsetRebuilt m;
+    VIDC_TRY(subset_rebuild(ctx, p->nlist, p->ntotal, p->d_offsets.p, subset_type, a1, a2, d_taken, m,
+                            [&](uint64_t *d) { return vidc_packed_decode_all(ctx, p, d); }));
+    VIDC_TRY(vidc_packed_encode_dev(ctx, p->nlist, m.new_off, m.ntotal_new, m.s_out.as<uint64_t>(), p->bits, out));
+    ctx->last_kernel_ms += m.kernel_ms;
+    if (n_taken) *n_taken = m.ntotal_new;
+    return VIDC_OK;
 }
 
 // Locate (include/vidc.h): decode_all into scratch, the mark and the labels of locate.h.  An id of `bits` bits is all the object can

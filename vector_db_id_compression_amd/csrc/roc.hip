@@ -12,6 +12,7 @@
 #include "append.h"
 #include "merge.h"
 #include "remove.h"
+#include "subset.h"
 #include "locate.h"
 #include "common.h"
 #include "host_call.h"
@@ -2543,6 +2544,70 @@ int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint
 // (the body is vidc::roc_remove, which the sharded remove calls with the per-pair found bytes; common.h)
 extern "C++" {
 namespace vidc {
+// The splice of the remove and of the subset: nr (nlist, ntotal and the host offsets filled in; `nonempty` of its lists hold ids) takes
+// list l from list ltpos[l] of `small` where lflag[l] != 0 and from the old object r otherwise -- metadata, the scan of the word
+// counts, a segmented copy of every list's words, the permutation (small's, or the identity).  small == NULL: no list is flagged.
+// The scratch blocks and the pinned word total (h_words) are the caller's, declared in front of its StreamGuard; tm is restarted
+// here and stopped into kernel_ms.  Ends enqueued: the caller waits.
+struct RocSpliceScratch {
+    Scratch s_slot, s_sizes, s_t1, s_t2;
+    AppChunks ch_w, ch_p;
+};
+static int roc_splice_small(vidc_ctx *ctx, const vidc_roc *r, vidc_roc *nr, uint64_t nonempty, const uint32_t *lflag, const uint64_t *ltpos,
+                            const vidc_roc *small, bool want_perm, uint64_t *h_words, RocSpliceScratch &S, EventTimer &tm, double &kernel_ms) {
+    const uint64_t nlist = r->nlist;
+    nr->offsets_host = true;
+    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
+    VIDC_TRY(S.s_slot.get(ctx, (nlist + 1) * 4));
+    VIDC_TRY(S.s_sizes.get(ctx, (nlist + 1) * 4));
+    (void)tm.start();
+    if (nlist) {
+        if (small) {
+            hipLaunchKernelGGL(k_rm_roc_sizes, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos,
+                               (const uint64_t *)r->d_offsets.p, (const uint64_t *)small->d_offsets.p, nlist, S.s_sizes.as<uint32_t>());
+            VIDC_TRY(device_exscan(ctx, S.s_sizes.as<uint32_t>(), (uint32_t)nlist, nr->d_offsets.p, S.s_t2));
+        } else {
+            VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, r->d_offsets.p, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};
+        const RocMeta m_small = small ? RocMeta{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p} : m_old;
+        hipLaunchKernelGGL(k_app_roc_meta, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos, nlist,
+                           m_old, m_small, nr->d_heads.p, nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, S.s_slot.as<uint32_t>());
+        VIDC_HIP(hipGetLastError());
+        VIDC_TRY(device_exscan(ctx, nr->d_nwords.p, (uint32_t)nlist, nr->d_word_off.p, S.s_t1));
+        VIDC_HIP(hipMemcpyAsync(h_words, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+        h_words[0] = 0;
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_words[0];
+    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, S.ch_w));
+        hipLaunchKernelGGL((k_app_copy<uint32_t, true>), app_chunk_grid(ctx, S.ch_w.bound), dim3(256), 0, ctx->stream, (const uint32_t *)r->d_words.p,
+                           (const uint64_t *)r->d_word_off.p, small ? (const uint32_t *)small->d_words.p : nullptr,
+                           small ? (const uint64_t *)small->d_word_off.p : nullptr, (const uint32_t *)S.s_slot.as<uint32_t>(),
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, S.ch_w.items, S.ch_w.n_items);
+        VIDC_HIP(hipGetLastError());
+    }
+    if (want_perm && nr->ntotal) {
+        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, S.ch_p));
+        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, S.ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
+                           (const uint32_t *)S.s_slot.as<uint32_t>(), small ? (const uint32_t *)small->d_perm.p : nullptr,
+                           small ? (const uint64_t *)small->d_offsets.p : nullptr, S.ch_p.items, S.ch_p.n_items, nr->d_perm.p);
+        VIDC_HIP(hipGetLastError());
+    }
+    kernel_ms += tm.stop();
+    return VIDC_OK;
+}
+
 int roc_remove(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode, uint32_t flags,
                vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found) {
     VIDC_TRY(remove_check(ctx, r, out, n_rm, d_ids));
@@ -2560,8 +2625,9 @@ int roc_remove(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d
     double kernel_ms = 0;
     RemoveBatch b;
     RemoveMarked mk;
-    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_t2, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids, s_slot, s_sizes;
+    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids;
     Pinned h_back, h_seg;
+    RocSpliceScratch sp_scratch;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
     EventTimer tm = EventTimer::started(ctx);
     VIDC_TRY(remove_sort_batch(ctx, nlist, n_rm, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
@@ -2698,60 +2764,275 @@ int roc_remove(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d
         }
         nr->offsets[nlist] = r->offsets[nlist] - gone;
     }
-    nr->offsets_host = true;
-    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(s_slot.get(ctx, (nlist + 1) * 4));
-    VIDC_TRY(s_sizes.get(ctx, (nlist + 1) * 4));
-    (void)tm.start();
-    if (nlist) {
-        if (small) {
-            hipLaunchKernelGGL(k_rm_roc_sizes, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos,
-                               (const uint64_t *)r->d_offsets.p, (const uint64_t *)small->d_offsets.p, nlist, s_sizes.as<uint32_t>());
-            VIDC_TRY(device_exscan(ctx, s_sizes.as<uint32_t>(), (uint32_t)nlist, nr->d_offsets.p, s_t2));
-        } else {
-            VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, r->d_offsets.p, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};
-        const RocMeta m_small = small ? RocMeta{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p} : m_old;
-        hipLaunchKernelGGL(k_app_roc_meta, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos, nlist,
-                           m_old, m_small, nr->d_heads.p, nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_slot.as<uint32_t>());
-        VIDC_HIP(hipGetLastError());
-        VIDC_TRY(device_exscan(ctx, nr->d_nwords.p, (uint32_t)nlist, nr->d_word_off.p, s_t1));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 3, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
-        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
-        h_cnt[3] = 0;
-    }
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    nr->total_words = h_cnt[3];
-    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
-    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
-    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
-    AppChunks ch_w, ch_p;
-    if (nr->total_words) {
-        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, ch_w));
-        hipLaunchKernelGGL((k_app_copy<uint32_t, true>), app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, (const uint32_t *)r->d_words.p,
-                           (const uint64_t *)r->d_word_off.p, small ? (const uint32_t *)small->d_words.p : nullptr,
-                           small ? (const uint64_t *)small->d_word_off.p : nullptr, (const uint32_t *)s_slot.as<uint32_t>(),
-                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
-        VIDC_HIP(hipGetLastError());
-    }
-    if (want_perm && nr->ntotal) {
-        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, ch_p));
-        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
-                           (const uint32_t *)s_slot.as<uint32_t>(), small ? (const uint32_t *)small->d_perm.p : nullptr,
-                           small ? (const uint64_t *)small->d_offsets.p : nullptr, ch_p.items, ch_p.n_items, nr->d_perm.p);
-        VIDC_HIP(hipGetLastError());
-    }
-    kernel_ms += tm.stop();
+    VIDC_TRY(roc_splice_small(ctx, r, nr.get(), nonempty, lflag, ltpos, small.get(), want_perm, h_cnt + 3, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
     guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
     tr.mark("spliced");
+    *out = nr.release();
+    return VIDC_OK;
+}
+
+// ---- subset (vidc_roc_subset_dev).  lflag / ltpos of the splice from the classes of k_sub_bounds: a partial list takes list ppos[l]
+// of the small object (ppos = exclusive scan of pflag), a list that keeps nothing takes the small object's trailing empty list
+// (number ppos[nlist], the count of partial lists), a kept list stays with the source.
+namespace {
+__global__ void __launch_bounds__(256) k_sub_roc_slots(const uint32_t *__restrict__ cls, const uint64_t *__restrict__ ppos, uint64_t nlist,
+                                                       uint32_t *__restrict__ lflag, uint64_t *__restrict__ ltpos) {
+    const uint64_t np = ppos[nlist];
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t c = cls[l];
+        lflag[l] = c != SUBC_KEEP ? 1u : 0u;
+        ltpos[l] = c == SUBC_PARTIAL ? ppos[l] : np;
+    }
+}
+}  // namespace
+
+// Subset (include/vidc.h).  Types 0 and 1 are a remove in any-list mode with the predicate mark of subset.h in place of the batch:
+// every non-empty list is a candidate, decoded into a staging CSR and marked; the candidates that lose an entry are compacted into a
+// second staging CSR and encode_impl runs on that alone.  Types 2 .. 4 need no id: k_sub_bounds classifies every list from the
+// offsets, the host runs the same functions (subset_plan.h) on its mirror of the offsets and so knows the partial lists and every new
+// size without a read-back; only the partial lists are decoded, sliced in staging and encoded.  The lists that keep nothing take the
+// encoder's own empty list, one trailing list of the small object.  The splice is the remove's (roc_splice_small).
+static int roc_subset(vidc_ctx *ctx, const vidc_roc *r, int type, uint64_t a1, uint64_t a2, int precision_mode, uint32_t flags, vidc_roc **out,
+                      uint8_t *d_taken, uint64_t *n_taken) {
+    VIDC_TRY(subset_check("roc", ctx, r, out, type, a1, a2));
+    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
+        set_error("roc subset: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
+        return VIDC_ERR_INVALID;
+    }
+    if (r->rows) { set_error("roc subset: graph objects hold no lists to take a subset of"); return VIDC_ERR_UNSUPPORTED; }
+    VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
+    VIDC_HIP(hipSetDevice(ctx->device));
+    HostTrace tr("roc subset");
+    const uint64_t nlist = r->nlist, ntotal_old = r->ntotal;
+    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0, by_id = subset_by_id(type);
+    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    double kernel_ms = 0;
+    RemoveMarked mk;
+    AppChunks ch_s, ch_t;
+    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids, s_lo, s_dst;
+    Pinned h_back, h_seg, h_dst;
+    RocSpliceScratch sp_scratch;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
+    EventTimer tm = EventTimer::started(ctx);
+    VIDC_TRY(h_back.get(ctx, 32 + (nlist + 1) * 8));
+    uint64_t *h_cnt = h_back.as<uint64_t>();
+    uint32_t *h_a = (uint32_t *)(h_cnt + 4), *h_b = h_a + nlist + 1;
+    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
+    VIDC_TRY(s_lf.get(ctx, (nlist + 1) * 4));
+    VIDC_TRY(s_lt.get(ctx, (nlist + 1) * 8));
+    uint32_t *lflag = s_lf.as<uint32_t>();
+    uint64_t *ltpos = s_lt.as<uint64_t>();
+    VIDC_HIP(hipMemsetAsync(lflag, 0, (nlist + 1) * 4, ctx->stream));
+    // the new object's host offsets are filled in by either path
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = ctx->device;
+    nr->nlist = nlist;
+    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
+    nr->offsets.resize(nlist + 1);
+    uint64_t nonempty = 0, nsmall = 0, small_total = 0;
+    std::vector<uint64_t> ts_off(1, 0);  // the small object's offsets
+    if (by_id) {
+        // the candidates: every non-empty list
+        VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
+        VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
+        VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
+        uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
+        uint64_t *stage_off = s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
+        uint32_t *d_cand = s_cand.as<uint32_t>();
+        if (nlist && ntotal_old) {
+            hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p,
+                               (const uint64_t *)nullptr, nlist, mark, flag);
+            Scan4 sc{};
+            sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
+            VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
+            hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
+            VIDC_HIP(hipGetLastError());
+            VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        kernel_ms += tm.stop();
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        const uint64_t cnt = h_cnt[0];
+        std::vector<uint32_t> cand(cnt);
+        VIDC_TRY(h_seg.get(ctx, (cnt + 1) * 8));
+        uint64_t *seg_off = h_seg.as<uint64_t>();
+        seg_off[0] = 0;
+        if (cnt) {
+            VIDC_HIP(hipMemcpyAsync(h_a, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+            for (uint64_t k = 0; k < cnt; k++) {
+                cand[k] = h_a[k];
+                seg_off[k + 1] = seg_off[k] + (r->offsets[cand[k] + 1] - r->offsets[cand[k]]);
+            }
+        }
+        const uint64_t total = seg_off[cnt];
+        tr.mark("candidates read back");
+        uint64_t T = 0, killed = 0;
+        std::vector<uint32_t> t_list;  // list numbers of the touched lists, ascending
+        if (cnt) {
+            VIDC_TRY(s_stage.get(ctx, total * 8));
+            VIDC_TRY(s_rm.get(ctx, total));
+            VIDC_TRY(s_seg.get(ctx, (cnt + 1) * 8));
+            VIDC_HIP(hipMemcpyAsync(s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+            {
+                PooledDecPlan p;
+                plan_decode(r, cand, false, p, ctx->wide);
+                std::vector<uint64_t> out_off(cnt);
+                for (size_t k = 0; k < cnt; k++) out_off[k] = seg_off[p.item[k]];  // work item k -> its place in the staging
+                VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+                kernel_ms += ctx->last_kernel_ms;
+            }
+            tr.mark("candidates decoded");
+            (void)tm.start();
+            VIDC_TRY(subset_mark(ctx, type, a1, a2, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), d_cand, cnt, total, s_rm.as<uint8_t>(), d_taken,
+                                 (const uint64_t *)r->d_offsets.p, mk));
+            VIDC_TRY(s_tf.get(ctx, 2 * (cnt + 1) * 4));  // tflag | tmark
+            VIDC_TRY(s_tp.get(ctx, 2 * (cnt + 1) * 8));  // tpos | tdst
+            VIDC_TRY(s_tl.get(ctx, 2 * (cnt + 1) * 4));  // t_cand | t_left
+            uint32_t *tflag = s_tf.as<uint32_t>(), *tmark = tflag + cnt + 1;
+            uint64_t *tpos = s_tp.as<uint64_t>(), *tdst = tpos + cnt + 1;
+            uint32_t *t_cand = s_tl.as<uint32_t>(), *t_left = t_cand + cnt + 1;
+            hipLaunchKernelGGL(k_rm_roc_kills, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint64_t *)s_seg.as<uint64_t>(),
+                               (const uint64_t *)mk.new_off, cnt, tflag, tmark);
+            Scan4 sc{};
+            sc.in[0] = tflag; sc.in[1] = tmark; sc.out[0] = tpos; sc.out[1] = tdst;
+            VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)cnt, s_t1));
+            hipLaunchKernelGGL(k_rm_roc_touched, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint32_t *)tflag, (const uint32_t *)tmark,
+                               (const uint64_t *)tpos, (const uint32_t *)d_cand, cnt, t_cand, t_left, lflag, ltpos);
+            VIDC_HIP(hipGetLastError());
+            VIDC_HIP(hipMemcpyAsync(h_cnt + 1, tpos + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+            VIDC_HIP(hipMemcpyAsync(h_cnt + 2, mk.new_off + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+            kernel_ms += tm.stop();
+            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+            T = h_cnt[1];
+            killed = total - h_cnt[2];
+            if (T) {
+                VIDC_HIP(hipMemcpyAsync(h_a, t_cand, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+                VIDC_HIP(hipMemcpyAsync(h_b, t_left, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+                VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+                ts_off.resize(T + 1);
+                t_list.resize(T);
+                for (uint64_t t = 0; t < T; t++) {
+                    t_list[t] = cand[h_a[t]];
+                    ts_off[t + 1] = ts_off[t] + h_b[t];
+                }
+                small_total = ts_off[T];
+                VIDC_TRY(s_small_ids.get(ctx, (small_total ? small_total : 1) * 8));
+                (void)tm.start();
+                VIDC_TRY(remove_compact(ctx, mk, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), s_rm.as<uint8_t>(), tdst, tflag, s_small_ids.as<uint64_t>()));
+                kernel_ms += tm.stop();
+            }
+        }
+        tr.mark("candidates marked, touched lists read back");
+        nsmall = T;
+        nr->ntotal = ntotal_old - killed;
+        uint64_t gone = 0, t = 0;
+        for (uint64_t l = 0; l < nlist; l++) {
+            nr->offsets[l] = r->offsets[l] - gone;
+            if (t < T && t_list[t] == l) { gone += (r->offsets[l + 1] - r->offsets[l]) - (ts_off[t + 1] - ts_off[t]); t++; }
+            nonempty += r->offsets[l + 1] - gone != nr->offsets[l];
+        }
+        nr->offsets[nlist] = r->offsets[nlist] - gone;
+    } else {
+        // the host's half: the same bounds on the mirror of the offsets
+        std::vector<uint32_t> part;  // the partial lists, ascending
+        std::vector<uint64_t> seg(1, 0);
+        bool any_empty = false;
+        nr->offsets[0] = 0;
+        for (uint64_t l = 0; l < nlist; l++) {
+            const uint64_t n = r->offsets[l + 1] - r->offsets[l];
+            uint64_t i1 = 0, i2 = 0;
+            if (ntotal_old) subset_bounds(type, a1, a2, ntotal_old, l, r->offsets[l], r->offsets[l + 1], i1, i2);
+            const uint32_t c = subset_roc_class(n, i2 - i1);
+            if (c == SUBC_PARTIAL) {
+                part.push_back((uint32_t)l);
+                seg.push_back(seg.back() + n);
+                ts_off.push_back(ts_off.back() + (i2 - i1));
+            }
+            any_empty |= c == SUBC_EMPTY;
+            nonempty += i2 != i1;
+            nr->offsets[l + 1] = nr->offsets[l] + (i2 - i1);
+        }
+        nr->ntotal = nr->offsets[nlist];
+        const uint64_t np = part.size(), total = seg[np];
+        small_total = ts_off[np];
+        if (any_empty) ts_off.push_back(small_total);  // the trailing empty list
+        nsmall = ts_off.size() - 1;
+        if (nlist && ntotal_old) {
+            VIDC_TRY(s_lo.get(ctx, 4 * (nlist + 1) * 4));  // lo | sizes | cls | pflag
+            VIDC_TRY(s_off.get(ctx, (nlist + 1) * 8));     // ppos
+            VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
+            uint32_t *lo = s_lo.as<uint32_t>(), *sizes = lo + nlist + 1, *cls = sizes + nlist + 1, *pflag = cls + nlist + 1;
+            uint64_t *ppos = s_off.as<uint64_t>();
+            uint32_t *d_part = s_cand.as<uint32_t>();
+            hipLaunchKernelGGL(k_sub_bounds, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p, nlist, type, a1, a2, lo,
+                               sizes, cls, pflag);
+            VIDC_HIP(hipGetLastError());
+            VIDC_TRY(device_exscan(ctx, pflag, (uint32_t)nlist, ppos, s_t0));
+            hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)pflag, (const uint64_t *)ppos, nlist,
+                               d_part);
+            hipLaunchKernelGGL(k_sub_roc_slots, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)cls, (const uint64_t *)ppos, nlist,
+                               lflag, ltpos);
+            VIDC_HIP(hipGetLastError());
+            if (d_taken) {
+                VIDC_TRY(app_chunks(ctx, r->d_offsets.p, nlist, ntotal_old, ch_t));
+                hipLaunchKernelGGL(k_sub_slice, app_chunk_grid(ctx, ch_t.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nullptr,
+                                   (const uint64_t *)r->d_offsets.p, (const uint32_t *)nullptr, (const uint32_t *)lo, (const uint32_t *)sizes, ch_t.items,
+                                   ch_t.n_items, (const uint64_t *)nullptr, (uint64_t *)nullptr, d_taken, (const uint64_t *)r->d_offsets.p);
+                VIDC_HIP(hipGetLastError());
+            }
+            kernel_ms += tm.stop();
+            if (np) {
+                VIDC_TRY(s_stage.get(ctx, total * 8));
+                VIDC_TRY(s_seg.get(ctx, (np + 1) * 8));
+                VIDC_TRY(s_dst.get(ctx, (np + 1) * 8));
+                VIDC_TRY(h_seg.get(ctx, (np + 1) * 8));
+                VIDC_TRY(h_dst.get(ctx, (np + 1) * 8));
+                std::memcpy(h_seg.p, seg.data(), (np + 1) * 8);
+                std::memcpy(h_dst.p, ts_off.data(), (np + 1) * 8);
+                VIDC_HIP(hipMemcpyAsync(s_seg.p, h_seg.p, (np + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+                VIDC_HIP(hipMemcpyAsync(s_dst.p, h_dst.p, (np + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+                {
+                    PooledDecPlan p;
+                    plan_decode(r, part, false, p, ctx->wide);
+                    std::vector<uint64_t> out_off(np);
+                    for (size_t k = 0; k < np; k++) out_off[k] = seg[p.item[k]];  // work item k -> its place in the staging
+                    VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
+                    kernel_ms += ctx->last_kernel_ms;
+                }
+                tr.mark("partial lists decoded");
+                VIDC_TRY(s_small_ids.get(ctx, (small_total ? small_total : 1) * 8));
+                (void)tm.start();
+                VIDC_TRY(app_chunks(ctx, s_seg.as<uint64_t>(), np, total, ch_s));
+                hipLaunchKernelGGL(k_sub_slice, app_chunk_grid(ctx, ch_s.bound), dim3(256), 0, ctx->stream, (const uint64_t *)s_stage.as<uint64_t>(),
+                                   (const uint64_t *)s_seg.as<uint64_t>(), (const uint32_t *)d_part, (const uint32_t *)lo, (const uint32_t *)sizes,
+                                   ch_s.items, ch_s.n_items, (const uint64_t *)s_dst.as<uint64_t>(), s_small_ids.as<uint64_t>(), (uint8_t *)nullptr,
+                                   (const uint64_t *)nullptr);
+                VIDC_HIP(hipGetLastError());
+                kernel_ms += tm.stop();
+            }
+        } else {
+            kernel_ms += tm.stop();
+        }
+        if (nsmall && !s_small_ids.p) VIDC_TRY(s_small_ids.get(ctx, 8));
+        tr.mark("bounds, partial lists sliced");
+    }
+    std::unique_ptr<vidc_roc> small;
+    if (nsmall) {
+        vidc_roc *sp = nullptr;
+        VIDC_TRY(encode_impl(ctx, nsmall, ts_off.data(), s_small_ids.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
+                             want_perm ? VIDC_ROC_WANT_PERM : 0u, &sp));
+        small.reset(sp);
+        kernel_ms += ctx->last_kernel_ms;
+    }
+    tr.mark("re-encoded lists encoded");
+    VIDC_TRY(roc_splice_small(ctx, r, nr.get(), nonempty, lflag, ltpos, small.get(), want_perm, h_cnt + 3, sp_scratch, tm, kernel_ms));
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    guard.disarm();
+    ctx->last_kernel_ms = kernel_ms;
+    tr.mark("spliced");
+    if (n_taken) *n_taken = nr->ntotal;
     *out = nr.release();
     return VIDC_OK;
 }
@@ -2798,6 +3079,11 @@ int roc_clone_to(vidc_ctx *dst, const vidc_roc *r, vidc_roc **out) {
 int vidc_roc_remove_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
                         uint32_t flags, vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid) {
     return roc_remove(ctx, r, n_rm, d_list_nos, d_ids, precision_mode, flags, out, d_removed, d_missing, d_invalid, nullptr);
+}
+
+int vidc_roc_subset_dev(vidc_ctx *ctx, const vidc_roc *r, int subset_type, uint64_t a1, uint64_t a2, int precision_mode, uint32_t flags,
+                        vidc_roc **out, uint8_t *d_taken, uint64_t *n_taken) {
+    return vidc::roc_subset(ctx, r, subset_type, a1, a2, precision_mode, flags, out, d_taken, n_taken);
 }
 
 // Locate (include/vidc.h).  The batch is sorted as a remove sorts it and the same candidates -- the non-empty lists a valid pair names,

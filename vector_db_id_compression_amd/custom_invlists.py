@@ -203,6 +203,45 @@ class InvertedListsArrayCodes:
         self._n_removed = getattr(self, "_n_removed", 0) + getattr(other, "_n_removed", 0)
         self._refresh_sizes()
 
+    # -- split: the inverse of merge_from.  The compressed ids go through the codec's subset (vidc_*_subset_dev).
+    def copy_subset_to(self, other, subset_type, a1, a2):
+        """Faiss's InvertedLists::copy_subset_to(other, subset_type, a1, a2): the entries of every list that the rule takes
+        (subset.ID_RANGE .. subset.INVLIST, see subset.subset) go behind the same list of `other`, ids unchanged -> the number added.
+        `other` is a container of the same class, list count and code size.  The subset is built as a codec object of its own
+        (subset.subset), its codes are the rows of codes_all the mask names (following the new permutation where the container
+        re-orders, as remove_batch does), and both are merged into `other` with other.merge_from(<the subset as a container>, 0).
+        This container is left unchanged.  The positions of ELEMENT_RANGE and INVLIST_FRACTION are those of the container's own
+        order (ROC: sampling order; Elias-Fano: ascending), which need not be the order the entries were added in."""
+        from . import subset
+
+        if type(other) is not type(self):
+            raise TypeError(f"copy_subset_to: {type(other).__name__} is not a {type(self).__name__}")
+        if other.nlist != self.nlist or other.code_size != self.code_size:
+            raise ValueError(f"copy_subset_to: nlist / code_size differ ({other.nlist} / {other.code_size} against {self.nlist} / {self.code_size})")
+        torch = _torch()
+        want = self._reorders and self.code_size > 0
+        sub_c, mask = subset.subset(self._c, subset_type, a1, a2, want_perm=want or self._keeps_perm())
+        part = type(self).__new__(type(self))  # the subset as a container over the same lists: what merge_from reads
+        part.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_c", "codes_all", "_offsets", "ntotal", "_n_removed")})
+        taken = torch.cat([mask.new_zeros(1, dtype=torch.int64), torch.cumsum(mask.to(torch.int64), 0)])
+        old_off = torch.from_numpy(self._offsets.astype(np.int64)).to(mask.device)
+        new_off = taken[old_off]
+        n_taken = int(new_off[-1].item())
+        codes = None
+        if self.code_size:
+            codes = self.codes_all[mask == 1]
+            if want:  # position q of list l holds taken entry perm[q] of that list
+                sizes = new_off[1:] - new_off[:-1]
+                base = torch.repeat_interleave(new_off[:-1], sizes)
+                codes = codes[base + torch.from_numpy(sub_c.perm().astype(np.int64)).to(mask.device)]
+        part._c, part.codes_all = sub_c, codes
+        part._offsets = new_off.cpu().numpy().astype(np.uint64)
+        part.ntotal = n_taken
+        # (the ids of the part were handed out among the vectors ever added here: the width of a merged packed-bits container covers them)
+        part._n_removed = self.ntotal + getattr(self, "_n_removed", 0) - n_taken
+        other.merge_from(part, 0)
+        return n_taken
+
     # -- batched helpers shared by the subclasses
     def get_single_id(self, list_no, offset):
         return int(self.get_single_ids([list_no], [offset])[0])
@@ -378,6 +417,9 @@ class CompressedIDInvertedListsWaveletTree(InvertedListsArrayCodes):
     def remove_batch(self, list_nos, ids):
         raise RuntimeError("not implemented: a wavelet tree holds a permutation of 0 .. ntotal - 1, which a removal breaks")
 
+    def copy_subset_to(self, other, subset_type, a1, a2):
+        raise RuntimeError("not implemented: a wavelet tree holds a permutation of 0 .. ntotal - 1, which a subset breaks: no copy_subset_to")
+
     def _merge_args(self, other):
         if other.wt_type != self.wt_type:
             raise ValueError(f"merge_from: wt_type differs ({other.wt_type} against {self.wt_type})")
@@ -425,6 +467,9 @@ class CompressedIDInvertedListsROCSegmented(InvertedListsArrayCodes):
 
     def merge_from(self, other, add_id=0):
         raise RuntimeError("not implemented: segmented ROC lists have no merge (re-encode, or use the FenwickTree container)")
+
+    def copy_subset_to(self, other, subset_type, a1, a2):
+        raise RuntimeError("not implemented: segmented ROC lists have no copy_subset_to (re-encode, or use the FenwickTree container)")
 
     def get_ids_all(self):
         return self._c.decode_all()

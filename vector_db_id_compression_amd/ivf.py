@@ -61,6 +61,37 @@ def _host_rows(il, ids):
     return order[at]
 
 
+def _host_subset(il, subset_type, a1, a2):
+    """the five rules of subset.subset on an ArrayInvertedLists -> one boolean keep array per list (unsigned 64-bit arithmetic)"""
+    sizes = [int(x.size) for x in il._ids]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    T = int(off[-1])
+    ok = {0: True, 1: a1 >= 1 and a2 < a1, 2: a1 <= a2 <= T, 3: 1 <= a1 < 2 ** 32 and a2 < a1, 4: True}.get(subset_type)
+    if ok is None or min(a1, a2) < 0 or max(a1, a2) >> 64:
+        raise ValueError(f"copy_subset_to: subset_type {subset_type} is not one of 0 .. 4, or an argument is outside [0, 2^64)")
+    if not ok:
+        raise ValueError(f"copy_subset_to: subset_type {subset_type} does not take a1 = {a1}, a2 = {a2}")
+    keeps = []
+    for l, n in enumerate(sizes):
+        ids = il._ids[l].view(np.uint64)
+        if subset_type == 0:
+            keep = (ids >= np.uint64(a1)) & (ids < np.uint64(a2))
+        elif subset_type == 1:
+            keep = np.array([int(x) % a1 == a2 for x in ids], bool) if n else np.zeros(0, bool)
+        else:
+            if subset_type == 2:
+                o0, o1 = int(off[l]), int(off[l + 1])
+                i1, i2 = (o1 * a1 // T - o0 * a1 // T, o1 * a2 // T - o0 * a2 // T) if T else (0, 0)
+            elif subset_type == 3:
+                i1, i2 = n * a2 // a1, n * (a2 + 1) // a1
+            else:
+                i1, i2 = (0, n) if a1 <= l < a2 else (0, 0)
+            pos = np.arange(n)
+            keep = (pos >= i1) & (pos < i2)
+        keeps.append(keep)
+    return keeps
+
+
 class IVFIndex:
     def __init__(self, d, nlist, code="Flat"):
         self.d, self.nlist = int(d), int(nlist)
@@ -150,16 +181,8 @@ class IVFIndex:
         number of vectors ever added here, so ids stay distinct).  Both indexes must share d, nlist, code, centroids (and PQ
         codebooks) and the class of their inverted lists.  A compressed container merges on the device (its merge_from);
         ArrayInvertedLists is merged on the host.  `other` is left unchanged (Faiss empties it)."""
-        if not isinstance(other, IVFIndex):
-            raise TypeError("merge_from: other must be an IVFIndex")
-        if (other.d, other.nlist, other.code) != (self.d, self.nlist, self.code):
-            raise ValueError("merge_from: d, nlist or code differ")
-        for mine, theirs, what in ((self.centroids, other.centroids, "centroids"), (self.pq, other.pq, "PQ codebooks")):
-            if (mine is None) != (theirs is None) or (mine is not None and not _torch().equal(mine, theirs)):
-                raise ValueError(f"merge_from: the {what} differ")
+        self._check_same_index(other, "merge_from")
         il, ol = self.invlists, other.invlists
-        if type(il) is not type(ol):
-            raise TypeError(f"merge_from: the inverted lists are a {type(il).__name__} and a {type(ol).__name__}")
         add_id = self._next_id if add_id is None else int(add_id)
         if isinstance(il, ArrayInvertedLists):
             for l in range(il.nlist):
@@ -173,6 +196,39 @@ class IVFIndex:
         self.ntotal += other.ntotal
         self._next_id = max(self._next_id, add_id + other._next_id)
         self._dev = None
+
+    def _check_same_index(self, other, what):
+        if not isinstance(other, IVFIndex):
+            raise TypeError(f"{what}: other must be an IVFIndex")
+        if (other.d, other.nlist, other.code) != (self.d, self.nlist, self.code):
+            raise ValueError(f"{what}: d, nlist or code differ")
+        for mine, theirs, name in ((self.centroids, other.centroids, "centroids"), (self.pq, other.pq, "PQ codebooks")):
+            if (mine is None) != (theirs is None) or (mine is not None and not _torch().equal(mine, theirs)):
+                raise ValueError(f"{what}: the {name} differ")
+        if type(self.invlists) is not type(other.invlists):
+            raise TypeError(f"{what}: the inverted lists are a {type(self.invlists).__name__} and a {type(other.invlists).__name__}")
+
+    def copy_subset_to(self, other, subset_type, a1, a2):
+        """IndexIVF::copy_subset_to: the entries the rule takes (subset.ID_RANGE .. subset.INVLIST, see subset.subset) go behind the
+        same lists of `other`, ids unchanged -> the number copied.  The compatibility checks are merge_from's.  A compressed container
+        takes the subset on the device (its copy_subset_to); ArrayInvertedLists is filtered on the host by the same five rules.  This
+        index is left unchanged."""
+        self._check_same_index(other, "copy_subset_to")
+        il, ol = self.invlists, other.invlists
+        if isinstance(il, ArrayInvertedLists):
+            n = 0
+            for l, keep in enumerate(_host_subset(il, int(subset_type), int(a1), int(a2))):
+                if keep.any():
+                    ol.add_entries(l, il._ids[l][keep], il._codes[l][keep])
+                    n += int(keep.sum())
+        elif hasattr(il, "copy_subset_to"):
+            n = il.copy_subset_to(ol, subset_type, a1, a2)
+        else:
+            raise RuntimeError("copy_subset_to: the inverted lists are read-only")
+        other.ntotal += n
+        other._next_id = max(other._next_id, self._next_id)
+        other._dev = None
+        return n
 
     def reconstruct_batch(self, ids):
         """IndexIVF::reconstruct_batch through the direct map: the stored vectors of `ids` -> float32 CUDA tensor [n, d].  A compressed
