@@ -628,7 +628,7 @@ int vidc_roc_subset_dev(vidc_ctx *ctx, const vidc_roc *r, int subset_type, uint6
  *   over the call's kernels.  The wavelet tree walks every id down its levels (the bit at the position, the rank inside the node): a
  *   thread per pair, no sort, no decode, enqueue only like vidc_wt_translate_labels_dev (vidc_ctx_last_kernel_ms is left alone).
  * Out of scope: segmented ROC objects, sharded objects and graph objects; a search inside compressed Elias-Fano lists; a persistent
- *   direct map kept beside the object. */
+ *   direct map kept beside the object.  (The search inside compressed Elias-Fano lists is vidc_ef_rank_dev, below.) */
 int vidc_packed_locate_dev(vidc_ctx *ctx, const vidc_packed *p, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
                            int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
 int vidc_ef_locate_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
@@ -637,6 +637,31 @@ int vidc_wt_locate_dev(vidc_ctx *ctx, const vidc_wt *w, uint64_t n, const int64_
                        int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
 int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids,
                         int64_t *d_labels, uint64_t *d_missing, uint64_t *d_invalid);
+
+/* ---------------------------------------------------- rank inside Elias-Fano lists and rows (device-resident) */
+/* How many entries of list d_list_nos[i] are smaller than d_ids[i]?  Answered inside the compressed streams: nothing is decoded.  From
+ * the rank follow membership, the successor (next_geq), a count of ids in a range, and for graph rows has_edge(u, v).
+ *
+ * Inputs.  All arrays are device arrays on the context's device, read and written in order on the context's stream.  Pair i asks
+ *   about list d_list_nos[i] (graph objects: the node).  Pairs mode only: d_list_nos is required.  A negative list number is skipped
+ *   and not counted; a list number >= nlist is skipped and counted in *d_invalid (device uint64 the caller zeroes, may be NULL).
+ * The result.  d_ranks[i] = r, the number of entries of that list < d_ids[i], compared over all 64 bits, unsigned: 0 <= r <= size.  r
+ *   is the offset of the first entry >= the id in the object's own (ascending) order: where r < size, list << 32 | r is a label that
+ *   vidc_ef_translate_labels_dev maps to the successor; of equal entries r is the first (vidc_ef_locate_dev's smallest label).  An id
+ *   above the list's largest gives r = size (ids >= 2^32, 2^63 and 2^64 - 1 are legal queries); an empty list gives 0; skipped and
+ *   invalid pairs get -1.  Every element of d_ranks is written and nothing outside it.  d_found (device uint8[n], may be NULL):
+ *   d_found[i] = 1 iff r < size and entry r equals the id, else 0 (also for skipped pairs); every element is written.  The outputs
+ *   must not overlap the inputs.
+ * Status.  NULL context or object, NULL d_list_nos, d_ids or d_ranks with n > 0, n >= 2^32 - 1: VIDC_ERR_INVALID before any device
+ *   work.  n == 0: VIDC_OK, nothing is launched.  The context stays usable after any error.
+ * Residency.  Enqueue only, like vidc_wt_locate_dev: no wait, no read-back; vidc_ctx_d2h_bytes does not move and
+ *   vidc_ctx_last_kernel_ms is left alone.  No allocation at all, so none that grows with ntotal.  The object is not changed.
+ * Objects.  Every Elias-Fano object: lists (per-list streams and the select directory: 16 lanes per pair binary-search the directory
+ *   for the batch of 64 high words that holds a zero of the unary high stream, scan that batch's popcounts, and binary-search the
+ *   bucket's low fields), graph rows of more than 64 edges (the same, list = node), and graph rows of up to 64 edges, read in place
+ *   from the fixed-stride arena by one lane per pair (the per-list streams are NOT built for this call). */
+int vidc_ef_rank_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_ranks,
+                     uint8_t *d_found, uint64_t *d_invalid);
 
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a

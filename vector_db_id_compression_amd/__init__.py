@@ -11,5 +11,6 @@ from . import removal  # noqa: F401,E402  (removal of (list, id) batches from th
 from . import locate  # noqa: F401,E402  (id -> label: the inverse of translate_labels for the list containers)
 from . import merge  # noqa: F401,E402  (two objects over the same lists -> one: Faiss's merge_from)
 from . import subset  # noqa: F401,E402  (a part of every list, chosen by rule -> a new object: Faiss's copy_subset_to)
+from . import rank  # noqa: F401,E402  (rank, membership and range counts inside compressed Elias-Fano lists and graph rows)
 
-__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal", "locate", "merge", "subset"]
+__all__ = ["VidcError", "VIDC_PREC_REFERENCE", "VIDC_PREC_EXACT", "persist", "removal", "locate", "merge", "subset", "rank"]

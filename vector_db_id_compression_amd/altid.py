@@ -85,6 +85,22 @@ class EliasFanoNSGGraph(_GraphBase):
         x = self.N * np.ceil(np.log2(self.N)) / 8.0 if self.N > 1 else 0.0
         self.overhead_in_bytes = int(int(x) + x)
 
+    def has_edges(self, u, v):
+        """-> bool CUDA tensor: is v[i] a neighbour of u[i]?  Searched inside the compressed rows (rank.contains), no row is decoded.  u, v:
+        integer arrays or CUDA tensors with one entry per pair; a node u[i] outside 0 .. N-1 gives False, and so does a v[i] that is no
+        node id (negative: as an unsigned number it is above every id a row holds)."""
+        from . import rank
+        from .codecs import _is_cuda, _torch
+
+        torch = _torch()
+
+        def dev(a):
+            if _is_cuda(a):
+                return a.reshape(-1).to(torch.int64)
+            return np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int64)
+
+        return rank.contains(self._c, dev(u), dev(v))
+
 
 class ROCNSGGraph(_GraphBase):
     """altid_impl.cpp:103-165."""

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "dev_offsets.h"
 #include "ef_plan.h"
+#include "ef_rank_ref.h"
 #include "host_call.h"
 #include "scan.h"
 #include "rows_csr.h"
@@ -1657,6 +1658,137 @@ __global__ void __launch_bounds__(256) k_ef_translate_g16(const uint64_t *__rest
     }
 }
 
+// ---- rank (vidc_ef_rank_dev; the arithmetic and its bounds argument: ef_rank_ref.h)
+// select0(jz) of one list by a 16-lane group, k_ef_translate_g16's scan with the words inverted: the directory search (every lane of
+// the group runs the same one), lane j takes words 4j .. 4j + 3 of the batch, the group scans its 16 popcount sums, the lane whose
+// words hold the zero finds it and the group reads the position from that lane.  Called by whole wavefronts: groups with nothing to
+// search pass ok = false and keep shuffling.  A zero the list's words do not hold answers nhw * 64.
+__device__ __forceinline__ uint64_t ef_g16_select0(bool ok, const uint64_t *hw, uint64_t nhw, const uint32_t *hr, uint64_t nb, uint64_t jz,
+                                                   uint32_t g, uint32_t j) {
+    uint64_t z[4] = {0ull, 0ull, 0ull, 0ull};
+    uint64_t w0 = 0, need = 0;
+    uint32_t c = 0;
+    if (ok) {
+        const uint64_t k = efr::batch_of_zero(hr, nb, jz);
+        need = jz - efr::zeros_before_batch(k, hr[k]);
+        w0 = k * 64 + 4u * j;
+#pragma unroll
+        for (int i = 0; i < 4; i++) z[i] = efr::zero_word(hw, nhw, w0 + i);
+        c = popc64(z[0]) + popc64(z[1]) + popc64(z[2]) + popc64(z[3]);
+    }
+    uint32_t incl = c;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, o, 16);
+        if (j >= (uint32_t)o) incl += v;
+    }
+    const uint32_t hit = (uint32_t)(ballot(ok && (uint64_t)incl > need) >> (16u * g)) & 0xffffu;
+    const uint32_t src = hit ? ff1(hit) : 0u;
+    uint64_t pos = 0;
+    if (hit && j == src) {
+        uint32_t k = (uint32_t)need - (incl - c);
+        // (no dynamic index into z[]: it would live in scratch)
+        uint64_t zz = z[0];
+        uint32_t ws = 0;
+        const uint32_t c0 = popc64(z[0]);
+        if (k >= c0) {
+            k -= c0; zz = z[1]; ws = 1;
+            const uint32_t c1 = popc64(z[1]);
+            if (k >= c1) {
+                k -= c1; zz = z[2]; ws = 2;
+                const uint32_t c2 = popc64(z[2]);
+                if (k >= c2) { k -= c2; zz = z[3]; ws = 3; }
+            }
+        }
+        pos = (w0 + ws) * 64 + efr::select_in_word(zz, k);
+    }
+    const uint32_t plo = (uint32_t)__shfl((int)(uint32_t)pos, (int)src, 16), phi = (uint32_t)__shfl((int)(uint32_t)(pos >> 32), (int)src, 16);
+    return hit ? ((uint64_t)phi << 32) | plo : nhw * 64;
+}
+
+// CSR form: 16 lanes per (list, id) pair, four pairs per wavefront (every list, whatever its batch count: the batches only deepen the
+// directory search, which is per lane).  Both selects run with wavefront-uniform control flow; lane 0 of the group then searches the
+// bucket's low fields and writes the pair's outputs.
+__global__ void __launch_bounds__(256) k_ef_rank_g16(const uint64_t *__restrict__ low, const uint64_t *__restrict__ high,
+                                                     const uint64_t *__restrict__ low_off, const uint64_t *__restrict__ high_off,
+                                                     const uint32_t *__restrict__ lbits, const uint64_t *__restrict__ universe,
+                                                     const uint64_t *__restrict__ batch_off, const uint32_t *__restrict__ hrank,
+                                                     const uint64_t *__restrict__ offsets, uint64_t nlist, uint64_t n,
+                                                     const int64_t *__restrict__ list_nos, const uint64_t *__restrict__ ids,
+                                                     int64_t *__restrict__ ranks, uint8_t *__restrict__ found, unsigned long long *invalid) {
+    const uint32_t lane = lane_id(), g = lane >> 4, j = lane & 15u;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t q0 = wave * 4u; q0 < n; q0 += nwaves * 4u) {  // (q0: wavefront-uniform)
+        const uint64_t q = q0 + g;
+        const int64_t ln = q < n ? list_nos[q] : -1;
+        const bool valid = ln >= 0 && (uint64_t)ln < nlist;
+        req_count_invalid(j == 0 && ln >= 0 && !valid, invalid);
+        uint64_t x = 0, m = 0, u = 0, nhw = 0, nb = 0;
+        uint32_t b = 0;
+        const uint64_t *hw = high;
+        const uint32_t *hr = hrank;
+        if (valid) {
+            x = ids[q];
+            m = offsets[ln + 1] - offsets[ln];
+            b = lbits[ln];
+            u = universe[ln];
+            hw = high + high_off[ln];
+            nhw = high_off[ln + 1] - high_off[ln];
+            hr = hrank + batch_off[ln];
+            nb = batch_off[ln + 1] - batch_off[ln];
+        }
+        const bool srch = valid && m && x <= u && nhw && nb;  // (a list with ids has high words and a batch)
+        const uint64_t h = srch ? x >> b : 0;
+        const uint64_t s0 = ef_g16_select0(srch && h, hw, nhw, hr, nb, h - 1, g, j);
+        const uint64_t p1 = ef_g16_select0(srch, hw, nhw, hr, nb, h, g, j);
+        if (j == 0 && q < n) {
+            int64_t r = -1;
+            uint32_t f = 0;
+            if (srch) {
+                const efr::RankResult rr = efr::rank_in_bucket(low + low_off[ln], low_off[ln + 1] - low_off[ln], b, m, x, h ? s0 + 1 : 0, p1);
+                r = (int64_t)rr.rank;
+                f = rr.found;
+            } else if (valid) {
+                r = (int64_t)m;  // an empty list: 0; an id above the largest: m
+            }
+            ranks[q] = r;
+            if (found) found[q] = (uint8_t)f;
+        }
+    }
+}
+
+// Arena form (graph rows of up to 64 edges): a lane per pair.  The row's record is read in place; its high stream is at most 3 n + 1
+// bits, so the lane walks the row's own high words (no directory) and searches its low fields, all through the record pointer.
+__global__ void __launch_bounds__(256) k_ef_rank_arena(const uint64_t *__restrict__ arena, const uint2 *__restrict__ meta, uint64_t N, uint32_t LW,
+                                                       uint32_t HW, uint64_t n, const int64_t *__restrict__ list_nos,
+                                                       const uint64_t *__restrict__ ids, int64_t *__restrict__ ranks, uint8_t *__restrict__ found,
+                                                       unsigned long long *invalid) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); q0 < n; q0 += stride) {  // (q0: wavefront-uniform)
+        const uint64_t q = q0 + lane_id();
+        const int64_t ln = q < n ? list_nos[q] : -1;
+        const bool valid = ln >= 0 && (uint64_t)ln < N;
+        req_count_invalid(ln >= 0 && !valid, invalid);
+        int64_t r = -1;
+        uint32_t f = 0;
+        if (valid) {
+            const uint2 mt = meta[ln];
+            const uint32_t m = mt.y & 0xffu, l = (mt.y >> 8) & 0x1fu;
+            const uint64_t *rec = arena + (uint64_t)ln * (LW + HW);
+            uint64_t hw = m ? ef_high_words(m, mt.x, l) : 0;
+            hw = hw < HW ? hw : HW;
+            const efr::RankResult rr = efr::rank_serial(rec, LW, rec + LW, hw, nullptr, 0, m, l, mt.x, ids[q]);
+            r = (int64_t)rr.rank;
+            f = rr.found;
+        }
+        if (q < n) {
+            ranks[q] = r;
+            if (found) found[q] = (uint8_t)f;
+        }
+    }
+}
+
 
 // ---- per-list geometry and work-item tables, built on the device
 // elias_fano.hpp:28-29 per list; word counts of the two streams and of the select directory
@@ -2976,6 +3108,28 @@ int vidc_ef_locate_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_
     VIDC_HIP(hipSetDevice(ctx->device));
     return locate_decoded(ctx, e->nlist, e->ntotal, e->d_offsets.p, n, d_list_nos, d_ids, 64u, d_labels, d_missing, d_invalid,
                           [&](uint64_t *d) { return vidc_ef_decode_all(ctx, e, d); });
+}
+
+// Rank (include/vidc.h): the lower bound of every id inside its own list, searched in the compressed streams (ef_rank_ref.h).  Nothing
+// is decoded and nothing allocated; an arena object is read in place (no ef_ensure_csr).  Enqueue only.
+int vidc_ef_rank_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_ranks,
+                     uint8_t *d_found, uint64_t *d_invalid) {
+    if (!ctx || !e || (n && (!d_list_nos || !d_ids || !d_ranks))) {
+        set_error("ef rank: NULL context, object, list number, id or rank array");
+        return VIDC_ERR_INVALID;
+    }
+    if (n >= 0xffffffffull) { set_error("ef rank: a batch holds fewer than 2^32 - 1 pairs"); return VIDC_ERR_INVALID; }
+    if (!n) return VIDC_OK;
+    VIDC_HIP(hipSetDevice(ctx->device));
+    if (e->arena)
+        hipLaunchKernelGGL(k_ef_rank_arena, req_grid(ctx, n), dim3(256), 0, ctx->stream, e->d_arena.p, e->d_rmeta.p, e->nlist, e->a_lw, e->a_hw, n,
+                           d_list_nos, d_ids, d_ranks, d_found, (unsigned long long *)d_invalid);
+    else
+        hipLaunchKernelGGL(k_ef_rank_g16, req_grid(ctx, n, 16), dim3(256), 0, ctx->stream, e->d_low.p, e->d_high.p, e->d_low_off.p,
+                           e->d_high_off.p, e->d_lbits.p, e->d_universe.p, e->d_batch_off.p, e->d_hrank.p, e->d_offsets.p, e->nlist, n,
+                           d_list_nos, d_ids, d_ranks, d_found, (unsigned long long *)d_invalid);
+    VIDC_HIP(hipGetLastError());
+    return VIDC_OK;
 }
 
 int vidc_ef_get(vidc_ctx *ctx, const vidc_ef *e, uint64_t m, const uint64_t *list_nos, const uint64_t *offs,

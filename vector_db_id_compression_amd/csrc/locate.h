@@ -17,6 +17,7 @@
 // remove is touched.  Out of scope: segmented ROC objects, sharded containers and graph objects; a search inside the compressed
 // Elias-Fano lists without decoding them (decode_all runs at memory rate); the Faiss adapter header; a direct map kept beside the
 // object.  Included by several translation units: everything has internal linkage.
+// (That search now exists beside this file: vidc_ef_rank_dev, ef_rank_ref.h and the rank kernels of ef.hip; locate does not use it.)
 #pragma once
 #include "remove.h"
 

@@ -394,6 +394,20 @@ class CompressedIDInvertedListsEliasFano(InvertedListsArrayCodes):
     def get_single_ids(self, list_nos, offsets):
         return self._c.get(list_nos, offsets)
 
+    def rank_batch(self, list_nos, ids):
+        """How many ids of list list_nos[i] are smaller than ids[i] (rank.rank on the codec: searched in the compressed lists, nothing is
+        decoded): int64 CUDA tensor, -1 for a negative or too large list number.  The rank is the offset of the first id >= ids[i] in the
+        container's own order: row offsets[list_no] + rank of codes_all is the successor's code."""
+        from . import rank
+
+        return rank.rank(self._c, list_nos, ids)
+
+    def contains_batch(self, list_nos, ids):
+        """Is ids[i] in list list_nos[i]? -> bool CUDA tensor (rank.contains on the codec)."""
+        from . import rank
+
+        return rank.contains(self._c, list_nos, ids)
+
 
 class CompressedIDInvertedListsWaveletTree(InvertedListsArrayCodes):
     """custom_invlists_impl.cpp:346-397; wt_type 0 = bit_vector levels, 1 = rrr_vector<63> levels."""

@@ -9,6 +9,7 @@ translate_labels use), or -1.  Of several matching entries the smallest label wi
 labels[i] >= 0, obj.translate_labels(labels)[i] == ids[i].  The object is not changed.  Packed bits, Elias-Fano and ROC sort the
 batch and search it from the decoded lists (ROC decodes only the lists the batch names; any-list mode decodes the whole object); a
 wavelet tree walks every id down its levels.  Segmented ROC lists, sharded containers and graph objects are out of scope.
+The search inside compressed Elias-Fano lists and graph rows, which decodes nothing, is rank.rank (vidc_ef_rank_dev).
 """
 import numpy as np
 
