@@ -663,6 +663,46 @@ int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int6
 int vidc_ef_rank_dev(vidc_ctx *ctx, const vidc_ef *e, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_ranks,
                      uint8_t *d_found, uint64_t *d_invalid);
 
+/* ---------------------------------------------------- search graph rows (device-resident, one launch) */
+/* Best-first search over a neighbour graph (NSG search_on_graph) for a batch of queries as ONE kernel launch: every query gets a
+ * wavefront of its own, which decodes the compressed rows it expands inside the kernel; the pool, the frontier and the visited set
+ * never leave the device.  vidc_rows_search_dev takes raw rows (int32 [N, K], the uncompressed baseline), the other two the objects
+ * of vidc_compact_rows_encode and vidc_ef_encode_rows.
+ *
+ * Semantics (per query, independently; graph_search.search of the Python package is the statement).  The pool holds at most L entries
+ *   (distance, node, expanded) ordered by (distance, node) ascending and starts as the entry node alone.  A step takes the first
+ *   unexpanded entry, marks it expanded and reads its row; every neighbour not yet visited is marked visited, gets its distance and
+ *   is inserted; the best L stay.  The search ends when no unexpanded entry is left or after max_rounds steps (0: no cap).  Visited
+ *   is permanent (a node dropped from the pool stays visited); a neighbour that a row holds twice counts once.  Distances are
+ *   squared L2 in float32.  Ties in distance are decided by the node id, so the result does not depend on the order of a row.
+ * Arrays.  All device arrays on the context's device.  d_x: float32 [N, d] row-major; d_xq: float32 [nq, d]; d_D float32 / d_I int64:
+ *   [nq, k], the first k pool entries of every query, padded with +inf / -1: every element is written and nothing outside them.
+ *   d_stats (may be NULL): uint32 [nq, 2] = {steps taken, distances computed (the entry's included)}.
+ * Rows.  A raw row ends at its first negative entry, a compact row at its first sentinel, an Elias-Fano row is its n ids.  A decoded
+ *   id >= N is skipped: it is never used as an index into d_x or the visited set, so a damaged image gives a wrong result, not an
+ *   access outside the call's arrays.
+ * Status.  VIDC_ERR_INVALID before any device work: NULL context or object, NULL arrays with nq > 0, anything outside
+ *   1 <= k <= L <= 256, 1 <= d <= 2048, entry < N, N < 2^31, nq < 2^32 - 1 (raw rows: K >= 1).  nq == 0: VIDC_OK, nothing is
+ *   launched.  VIDC_ERR_UNSUPPORTED: an Elias-Fano object that holds lists and not graph rows; a graph object of rows wider than 64
+ *   edges (it has no fixed-stride arena); compact rows outside the K limits of vidc_compact_rows_encode.
+ * Scratch.  The visited set is exact: a bitset of N bits per RESIDENT WAVEFRONT (slot), not per query, taken from the context's
+ *   block cache: slots * ceil(N / 64) * 8 bytes with slots = min(nq, 32 * compute units, 1024) -- at most 128 MB at N = 10^6.  A slot
+ *   is cleared by its wavefront in front of every query (a wide memset inside the kernel, measured at 12-14 % of the kernel's time at most on a
+ *   10^6-node graph; replaying a log of the visited nodes instead was not built).
+ * Residency.  Enqueued on the context's stream; the call waits for its kernel, because the scratch goes back to the cache.
+ *   vidc_ctx_d2h_bytes does not move; vidc_ctx_last_kernel_ms is the kernel's time.  The objects are not changed; the Elias-Fano
+ *   arena is read in place (the per-list streams are not built for this call).
+ * Not here.  There is no ROC form: a ROC row is one serial ANS chain, which a single lane of the query's wavefront would have to
+ *   run -- the batched search over vidc_roc_decode_rows_dev (graph_search.search_batched) stays the ROC path.  Inner product,
+ *   per-query entry nodes and sharded graphs are out of scope as well. */
+int vidc_rows_search_dev(vidc_ctx *ctx, uint64_t N, uint32_t K, const int32_t *d_rows, const float *d_x, uint32_t d, uint64_t nq,
+                         const float *d_xq, uint32_t k, uint32_t L, uint32_t entry, uint32_t max_rounds, float *d_D, int64_t *d_I,
+                         uint32_t *d_stats);
+int vidc_compact_search_dev(vidc_ctx *ctx, const vidc_compact *c, const float *d_x, uint32_t d, uint64_t nq, const float *d_xq,
+                            uint32_t k, uint32_t L, uint32_t entry, uint32_t max_rounds, float *d_D, int64_t *d_I, uint32_t *d_stats);
+int vidc_ef_search_dev(vidc_ctx *ctx, const vidc_ef *e, const float *d_x, uint32_t d, uint64_t nq, const float *d_xq, uint32_t k,
+                       uint32_t L, uint32_t entry, uint32_t max_rounds, float *d_D, int64_t *d_I, uint32_t *d_stats);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

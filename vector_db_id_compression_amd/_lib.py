@@ -170,6 +170,11 @@ def _declare(lib):
         f(name, C.c_int, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
     # rank inside Elias-Fano lists and rows: ctx, obj, n, list_nos, ids, ranks, found, invalid
     f("vidc_ef_rank_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
+    # search graph rows in one launch: ..., x, d, nq, xq, k, L, entry, max_rounds, D, I, stats
+    _tail = (_vp, _u32, _u64, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp)
+    f("vidc_rows_search_dev", C.c_int, _vp, _u64, _u32, _vp, *_tail)
+    f("vidc_compact_search_dev", C.c_int, _vp, _vp, *_tail)
+    f("vidc_ef_search_dev", C.c_int, _vp, _vp, *_tail)
     # update rows (graph objects, device-resident)
     f("vidc_compact_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
     f("vidc_ef_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
@@ -241,6 +246,7 @@ EXPORTED_SYMBOLS = [
     "vidc_packed_remove_dev", "vidc_ef_remove_dev", "vidc_roc_remove_dev",
     "vidc_packed_subset_dev", "vidc_ef_subset_dev", "vidc_roc_subset_dev",
     "vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev", "vidc_ef_rank_dev",
+    "vidc_rows_search_dev", "vidc_compact_search_dev", "vidc_ef_search_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
     "vidc_shards_encode", "vidc_shards_encode_dev", "vidc_shards_destroy", "vidc_shards_count", "vidc_shards_kind", "vidc_shards_nlist",
     "vidc_shards_ntotal", "vidc_shards_compressed_bytes", "vidc_shards_map", "vidc_shards_offsets", "vidc_shards_shard",

@@ -23,6 +23,7 @@
 #include "dev_offsets.h"
 #include "ef_plan.h"
 #include "ef_rank_ref.h"
+#include "graph_search_views.h"
 #include "host_call.h"
 #include "scan.h"
 #include "rows_csr.h"
@@ -2459,6 +2460,10 @@ uint64_t vidc_ef_compressed_bytes(const vidc_ef *e) { return e ? e->total_bits /
 extern "C++" {
 namespace vidc {
 uint64_t ef_stream_bits(const vidc_ef *e) { return e ? e->total_bits : 0; }
+// graph_search.hip reads the arena of a graph object in place (graph_search_views.h)
+void ef_rows_view(const vidc_ef *e, EfRowsView *out) {
+    *out = EfRowsView{e->rows, e->arena, e->d_arena.p, e->d_rmeta.p, e->nlist, e->K, e->a_lw, e->a_hw};
+}
 }  // namespace vidc
 }
 

@@ -19,6 +19,7 @@
 #include "locate.h"
 #include "common.h"
 #include "dev_offsets.h"
+#include "graph_search_views.h"
 #include "host_call.h"
 #include "requests.h"
 #include "rows_tile.h"
@@ -858,6 +859,9 @@ struct vidc_compact {
     uint32_t K = 0, bits = 0, stride = 0;
     DevBuf<uint8_t> d_data;
 };
+
+// graph_search.hip reads the row bytes in place (graph_search_views.h)
+void vidc::compact_rows_view(const vidc_compact *c, CompactRowsView *out) { *out = CompactRowsView{c->d_data.p, c->N, c->K, c->bits, c->stride}; }
 
 // the rows_tile.h kernels serve the object (they write every byte of every row, and need no counts array to decode)
 static bool compact_tile(const vidc_compact *c) { return c->K <= 64 && (c->stride & 3u) == 0u; }

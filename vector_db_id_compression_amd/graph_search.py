@@ -82,6 +82,80 @@ def search(graph, x, xq, k, L=32, entry=0):
     return D, I
 
 
+def _device_rows(graph):
+    """-> ("rows" | "compact" | "ef", the object the C call takes, N, K) of a graph `search_device` can walk; VidcError by class name
+    for everything else (decided before the device is looked at)."""
+    from . import altid, codecs
+    from ._lib import VidcError
+
+    if isinstance(graph, RawGraph):
+        return "rows", graph, graph.N, graph.K
+    if isinstance(graph, (altid.CompactBitNSGGraph, altid.EliasFanoNSGGraph)):
+        graph = graph._c
+    if isinstance(graph, codecs.CompactRows):
+        return "compact", graph, getattr(graph, "N", None), getattr(graph, "K", 0)
+    if isinstance(graph, codecs.EfLists):
+        n = getattr(graph, "_nlist", None) if getattr(graph, "_offsets", None) is None else graph._offsets.size - 1
+        return "ef", graph, n, getattr(graph, "K", 0)
+    raise VidcError(f"search_device: {type(graph).__name__} rows cannot be decoded inside the search kernel (raw, compact and "
+                    "Elias-Fano rows can; a ROC row is a serial ANS chain): use graph_search.search_batched")
+
+
+def search_device(graph, x, xq, k, L=64, entry=0, max_rounds=None, stats=False):
+    """The best-first search of `search` for a whole batch as ONE kernel launch (vidc_{rows,compact,ef}_search_dev): a wavefront per query
+    decodes the rows it expands inside the kernel; pools, frontier and visited sets stay on the device.
+
+    graph: RawGraph, CompactBitNSGGraph, EliasFanoNSGGraph, or the CompactRows / EfLists graph objects behind them (Elias-Fano: rows of
+    at most 64 edges).  ROCNSGGraph and every other class: VidcError naming the class (search_batched is their path).  x: float32 [N, d]
+    (a CUDA tensor stays where it is, anything else is uploaded once); xq: [nq, d]; 1 <= k <= L <= 256; max_rounds None / 0: no cap.
+    -> (D float32 [nq, k], I int64 [nq, k]) CUDA tensors, +inf / -1 padded, and with stats=True a third, int32 [nq, 2] = (steps taken,
+    distances computed) per query.  Runs on torch's current stream; the call waits for its kernel."""
+    from . import _lib
+    from ._lib import VidcError, check, lib, ptr
+
+    kind, obj, N, K = _device_rows(graph)
+    import torch
+
+    if not torch.cuda.is_available():
+        raise VidcError("no HIP device: search_device needs an MI355X (there is no CPU fallback)")
+
+    def f32(a):
+        if not (isinstance(a, torch.Tensor) and a.is_cuda):
+            a = torch.from_numpy(np.array(a, dtype=np.float32, order="C")).cuda()  # (a copy: torch wants a writable array)
+        return a.to(torch.float32).contiguous()
+
+    xt, qt = f32(x), f32(xq)
+    if xt.dim() != 2 or qt.dim() != 2 or qt.shape[1] != xt.shape[1]:
+        raise ValueError("x must be [N, d] and xq [nq, d]")
+    if N is not None and xt.shape[0] != N:
+        raise ValueError(f"x holds {xt.shape[0]} vectors, the graph {N} nodes")
+    nq, d = int(qt.shape[0]), int(xt.shape[1])
+    k, L, entry, rounds = int(k), int(L), int(entry), int(max_rounds or 0)
+    if min(k, L, entry, rounds) < 0 or max(k, L, entry, rounds) >= 2 ** 32:
+        raise ValueError("k, L, entry and max_rounds are unsigned 32-bit numbers")
+    D = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=xt.device)
+    I = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=xt.device)
+    S = torch.empty((nq, 2), dtype=torch.int32, device=xt.device) if stats else None
+    tail = (ptr(xt) if xt.numel() else None, d, nq, ptr(qt) if nq else None, k, L, entry, rounds, ptr(D) if D.numel() else None,
+            ptr(I) if I.numel() else None, ptr(S) if stats and nq else None)
+    if kind == "rows":
+        if getattr(graph, "_dev", None) is None:
+            graph._dev = torch.from_numpy(graph.rows).cuda()
+        ctx = _lib.default_context()
+        st = lib().vidc_rows_search_dev(ctx.h, xt.shape[0], K, ptr(graph._dev) if graph._dev.numel() else None, *tail)
+    else:
+        from .codecs import _on_torch_stream
+
+        _on_torch_stream(obj.ctx)
+        fn = lib().vidc_compact_search_dev if kind == "compact" else lib().vidc_ef_search_dev
+        st = fn(obj.ctx.h, obj.h, *tail)
+    try:
+        check(st)
+    except VidcError as e:
+        raise VidcError(f"search_device: {type(graph).__name__}: {e}") from None
+    return (D, I, S) if stats else (D, I)
+
+
 def search_batched(graph, x, xq, k, L=64, entry=0, max_rounds=None):
     """The same best-first search for a whole batch of queries in lock step on the GPU: every round expands the best
     unexpanded candidate of every query with ONE `get_neighbors_device` call (one decode launch for the whole
