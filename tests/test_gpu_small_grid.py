@@ -41,7 +41,8 @@ CAPACITY = {
     # inner_offsets / max; ef.hip k_iota_perm has the same geometry
     "req": (32 * 256, 64),
     # roc_seg.hip chunk_grid (k_rocseg_count / scatter / fix), append.h app_chunk_grid (k_app_copy, k_app_labels_perm, k_rm_mark,
-    # k_rm_compact, k_loc_mark), shards.hip copy_grid: 16 workgroups x 4 wavefronts, a chunk of <= 1024 elements of one list each
+    # k_rm_compact, k_loc_mark; the ROC splice's k_roc_regroup_copy / perm), shards.hip copy_grid: 16 workgroups x 4 wavefronts, a chunk
+    # of <= 1024 elements of one list each
     "chunk1024": (16 * 4, 4),
     # append.h app_sort_phase (k_app_hist, k_app_scatter): 32 workgroups of one wavefront, a tile of 1024 pairs each
     "sort_tile": (32, 1),

@@ -136,10 +136,9 @@ __global__ void k_app_count_chunks(const uint64_t *len_off, uint32_t nseg, uint3
         cnt[s] = (uint32_t)((len_off[s + 1] - len_off[s] + APP_COPY_UNIT - 1) / APP_COPY_UNIT);
 }
 
-// Segmented copy, a wavefront per chunk: segment s (length src_off[s + 1] - src_off[s], or dst_off[s + 1] - dst_off[s] when LEN_DST) goes
-// to dst + dst_off[s].  Its source is src + src_off[s], or -- when slot[s] != 0 -- alt + alt_off[slot[s] - 1] (the splice of a ROC
-// stream: a list's words come from whichever object holds them).
-template <typename T, bool LEN_DST>
+// Segmented copy, a wavefront per chunk: segment s (length src_off[s + 1] - src_off[s]) goes to dst + dst_off[s].  Its source is
+// src + src_off[s], or -- when slot[s] != 0 -- alt + alt_off[slot[s] - 1].
+template <typename T>
 __global__ void __launch_bounds__(256) k_app_copy(const T *__restrict__ src, const uint64_t *__restrict__ src_off, const T *__restrict__ alt,
                                                   const uint64_t *__restrict__ alt_off, const uint32_t *__restrict__ slot,
                                                   const uint64_t *__restrict__ dst_off, T *__restrict__ dst, const Chunk *__restrict__ items,
@@ -149,7 +148,7 @@ __global__ void __launch_bounds__(256) k_app_copy(const T *__restrict__ src, con
     const uint32_t lane = dev::lane_id();
     for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < total; c += (uint64_t)gridDim.x * 4u) {
         const Chunk ch = items[c];
-        const uint64_t n = LEN_DST ? dst_off[ch.list + 1] - dst_off[ch.list] : src_off[ch.list + 1] - src_off[ch.list];
+        const uint64_t n = src_off[ch.list + 1] - src_off[ch.list];
         const uint32_t nc = (uint32_t)(n - ch.start < APP_COPY_UNIT ? n - ch.start : APP_COPY_UNIT);
         const uint32_t sl = slot ? slot[ch.list] : 0u;
         const T *s = (sl ? alt + alt_off[sl - 1u] : src + src_off[ch.list]) + ch.start;
@@ -171,7 +170,7 @@ __global__ void __launch_bounds__(256) k_app_copy(const T *__restrict__ src, con
 
 // One chunk of a segmented copy, by one wavefront: d[0 .. nc) = s[0 .. nc), nc <= APP_COPY_UNIT.  16-byte accesses where the two runs
 // share their alignment mod 16, behind a head of less than 16 bytes and in front of a tail of less than 16; accesses of one element
-// otherwise.  k_app_copy's chunk body as a function, for the kernels that choose a segment's source differently (the ROC regroup's word
+// otherwise.  k_app_copy's chunk body as a function, for the kernels that choose a segment's source differently (the ROC splice's word
 // copy, roc.hip).  k_app_copy keeps its own text: moving it here re-allocates the registers of its 8-byte instantiation, and the code
 // objects of the append and the remove stay what they were, instruction for instruction.
 template <typename T>
@@ -356,7 +355,7 @@ inline int append_merge(::vidc_ctx *ctx, uint64_t nlist, uint64_t ntotal_old, co
         VIDC_TRY(decode_all(m.s_old.as<uint64_t>()));
         AppChunks ch;
         VIDC_TRY(app_chunks(ctx, d_old_off, nlist, ntotal_old, ch));
-        hipLaunchKernelGGL((k_app_copy<uint64_t, false>), app_chunk_grid(ctx, ch.bound), dim3(256), 0, ctx->stream, m.s_old.as<uint64_t>(), d_old_off,
+        hipLaunchKernelGGL(k_app_copy<uint64_t>, app_chunk_grid(ctx, ch.bound), dim3(256), 0, ctx->stream, m.s_old.as<uint64_t>(), d_old_off,
                            (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, m.batch.new_off,
                            m.s_merged.as<uint64_t>(), ch.items, ch.n_items);
         VIDC_HIP(hipGetLastError());

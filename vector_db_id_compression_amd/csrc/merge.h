@@ -237,7 +237,7 @@ inline int merge_rebuild(::vidc_ctx *ctx, uint64_t nlist, uint64_t na, uint64_t 
     VIDC_HIP(hipGetLastError());
     if (na) {
         VIDC_TRY(app_chunks(ctx, d_a_off, nlist, na, ch_a));
-        hipLaunchKernelGGL((k_app_copy<uint64_t, false>), app_chunk_grid(ctx, ch_a.bound), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(k_app_copy<uint64_t>, app_chunk_grid(ctx, ch_a.bound), dim3(256), 0, ctx->stream,
                            (const uint64_t *)m.s_a.as<uint64_t>(), d_a_off, (const uint64_t *)nullptr, (const uint64_t *)nullptr,
                            (const uint32_t *)nullptr, (const uint64_t *)new_off, m.s_merged.as<uint64_t>(), ch_a.items, ch_a.n_items);
         VIDC_HIP(hipGetLastError());

@@ -1619,42 +1619,6 @@ __global__ void __launch_bounds__(256) k_app_roc_touched(const uint32_t *__restr
             added[tpos[l]] = (uint32_t)(add_off[l + 1] - add_off[l]);
         }
 }
-// per-list metadata of the spliced object: from the small object (list tpos[l] of it) for a touched list, from the old one otherwise;
-// slot[l] = tpos[l] + 1 or 0, what the word and permutation copies select their source by
-struct RocMeta {
-    const uint64_t *heads;
-    const uint32_t *prec, *nwords, *draws;
-};
-__global__ void __launch_bounds__(256) k_app_roc_meta(const uint32_t *__restrict__ flag, const uint64_t *__restrict__ tpos, uint64_t nlist, RocMeta old,
-                                                      RocMeta small, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
-                                                      uint32_t *__restrict__ nwords, uint32_t *__restrict__ draws, uint32_t *__restrict__ slot) {
-    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x) {
-        const bool t = flag[l] != 0u;
-        const uint64_t k = t ? tpos[l] : l;
-        const RocMeta &m = t ? small : old;
-        heads[l] = m.heads[k];
-        prec[l] = m.prec[k];
-        nwords[l] = m.nwords[k];
-        draws[l] = m.draws[k];
-        slot[l] = t ? (uint32_t)k + 1u : 0u;
-    }
-}
-// sampling permutation of the spliced object: the small object's for a touched list, the identity otherwise (a decoded list of
-// distinct ids re-encodes to the identity).  A wavefront per chunk of the new lists.
-__global__ void __launch_bounds__(256) k_app_roc_perm(const uint64_t *__restrict__ new_off, const uint32_t *__restrict__ slot,
-                                                      const uint32_t *__restrict__ sperm, const uint64_t *__restrict__ soff,
-                                                      const Chunk *__restrict__ items, const uint64_t *__restrict__ n_items, uint32_t *__restrict__ perm) {
-    const uint64_t total = *n_items;
-    const uint32_t lane = lane_id();
-    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < total; c += (uint64_t)gridDim.x * 4u) {
-        const Chunk ch = items[c];
-        const uint64_t base = new_off[ch.list], n = new_off[ch.list + 1] - base;
-        const uint32_t nc = (uint32_t)(n - ch.start < APP_COPY_UNIT ? n - ch.start : APP_COPY_UNIT);
-        const uint32_t sl = slot[ch.list];
-        const uint32_t *src = sl ? sperm + soff[sl - 1u] + ch.start : nullptr;
-        for (uint32_t j = lane; j < nc; j += 64u) perm[base + ch.start + j] = sl ? src[j] : ch.start + j;
-    }
-}
 
 // ---- remove (vidc_roc_remove_dev): the candidates are decoded and marked, the lists that lose an entry are re-encoded, the rest is
 // spliced.  flag[l] = list l is a candidate -- non-empty and (run_off != NULL) named by a pair of the batch; mark[l] = its ids.
@@ -1691,23 +1655,20 @@ __global__ void __launch_bounds__(256) k_rm_roc_touched(const uint32_t *__restri
             ltpos[cand[k]] = tpos[k];
         }
 }
-// sizes of the spliced object's lists: the small object's for a touched list, the old one's otherwise
-__global__ void __launch_bounds__(256) k_rm_roc_sizes(const uint32_t *__restrict__ lflag, const uint64_t *__restrict__ ltpos,
-                                                      const uint64_t *__restrict__ old_off, const uint64_t *__restrict__ small_off, uint64_t nlist,
-                                                      uint32_t *__restrict__ sizes) {
-    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < nlist; l += (uint64_t)gridDim.x * blockDim.x)
-        sizes[l] = (uint32_t)(lflag[l] ? small_off[ltpos[l] + 1] - small_off[ltpos[l]] : old_off[l + 1] - old_off[l]);
-}
 
-// ---- regroup (vidc_roc_regroup): list j of the new object is list list_no[j] of source src_no[j], stream and metadata unchanged.
-// A source: RocMeta plus where its words and its lists start.  Up to VIDC_SHARDS_MAX of them reach the kernels by value; the host
-// checked src_no[j] < nsrc, the source non-NULL and list_no[j] < its nlist before anything was uploaded.
-struct RocSrc : RocMeta {
+// ---- the splice (roc_splice, below): list j of the new object is list k of source s, stream and metadata unchanged.  Every
+// operation that derives one object from others ends in it -- append, remove, subset, merge, regroup, update_rows.
+// A source: its per-list metadata, and where its words and its lists start.  The N sources of an operation (2, 3, or up to
+// VIDC_SHARDS_MAX for the regroup) reach the kernels by value; the regroup's host checked src_no[j] < nsrc, the source non-NULL and list_no[j] < its nlist before anything was uploaded.
+struct RocSrc {
+    const uint64_t *heads;
+    const uint32_t *prec, *nwords, *draws;
     const uint32_t *words;
     const uint64_t *word_off, *offsets;
 };
+template <int N>
 struct RocSrcs {
-    RocSrc s[VIDC_SHARDS_MAX];
+    RocSrc s[N];
 };
 // Where list j of the new object comes from: get(j, source, list) -> false for a list that has no source (an empty list).
 // The regroup's table, uploaded by the host ...
@@ -1743,9 +1704,21 @@ struct RocMergeSlots {
         return true;
     }
 };
-// the five per-list arrays of the new object (sizes: what the scan turns into its offsets); *nonempty (may be NULL) += lists with ids
-template <typename Lookup>
-__global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs srcs, Lookup look, uint64_t m, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
+// ... and the flags of the append, the remove and the subset, built on the device: source 1 is the small object of the re-encoded
+// lists, list ltpos[j] of it where lflag[j] != 0; source 0 is the old object, list j.
+struct RocSmallSlots {
+    const uint32_t *lflag;
+    const uint64_t *ltpos;
+    __device__ __forceinline__ bool get(uint64_t j, uint32_t &s, uint64_t &k) const {
+        const bool t = lflag[j] != 0u;
+        s = t ? 1u : 0u;
+        k = t ? ltpos[j] : j;
+        return true;
+    }
+};
+// the five per-list arrays of the new object (sizes: what the scan turns into its offsets); *nonempty += lists with ids
+template <int N, typename Lookup>
+__global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs<N> srcs, Lookup look, uint64_t m, uint64_t *__restrict__ heads, uint32_t *__restrict__ prec,
                                                           uint32_t *__restrict__ nwords, uint32_t *__restrict__ draws, uint32_t *__restrict__ sizes,
                                                           unsigned long long *nonempty) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -1770,16 +1743,14 @@ __global__ void __launch_bounds__(256) k_roc_regroup_meta(RocSrcs srcs, Lookup l
             }
             sizes[j] = size;
         }
-        if (nonempty) {
-            const uint64_t b = ballot(size != 0u);
-            if (b && lane_id() == 0) atomicAdd(nonempty, (unsigned long long)popc64(b));
-        }
+        const uint64_t b = ballot(size != 0u);
+        if (b && lane_id() == 0) atomicAdd(nonempty, (unsigned long long)popc64(b));
     }
 }
-// the words: k_app_copy<uint32_t, true> with the source of a list chosen among the sources' word arrays.  A wavefront per chunk of the
-// new lists' streams (items: app_chunks on dst_off; a list without a source has no words, hence no chunk).
-template <typename Lookup>
-__global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs srcs, Lookup look, const uint64_t *__restrict__ dst_off, uint32_t *__restrict__ dst,
+// the words: a list's stream from the word array of whichever source holds it.  A wavefront per chunk of the new lists' streams
+// (items: app_chunks on dst_off; a list without a source has no words, hence no chunk).
+template <int N, typename Lookup>
+__global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs<N> srcs, Lookup look, const uint64_t *__restrict__ dst_off, uint32_t *__restrict__ dst,
                                                           const Chunk *__restrict__ items, const uint64_t *__restrict__ n_items) {
     const uint64_t total = *n_items;
     const uint32_t lane = lane_id();
@@ -1793,6 +1764,284 @@ __global__ void __launch_bounds__(256) k_roc_regroup_copy(RocSrcs srcs, Lookup l
         const RocSrc &s = srcs.s[sn];
         app_copy_chunk(s.words + s.word_off[k] + ch.start, dst + base + ch.start, nc, lane);
     }
+}
+// sampling permutation of the new object: source perm_src's (sperm, over its lists at soff) for a list taken from it -- the small
+// object of freshly encoded lists --, the identity for every other list (a decoded list of distinct ids re-encodes to the identity).
+// sperm == NULL: the identity everywhere.  A wavefront per chunk of the new lists (items: app_chunks on new_off).
+template <typename Lookup>
+__global__ void __launch_bounds__(256) k_roc_regroup_perm(Lookup look, uint32_t perm_src, const uint32_t *__restrict__ sperm,
+                                                          const uint64_t *__restrict__ soff, const uint64_t *__restrict__ new_off,
+                                                          const Chunk *__restrict__ items, const uint64_t *__restrict__ n_items,
+                                                          uint32_t *__restrict__ perm) {
+    const uint64_t total = *n_items;
+    const uint32_t lane = lane_id();
+    for (uint64_t c = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); c < total; c += (uint64_t)gridDim.x * 4u) {
+        const Chunk ch = items[c];
+        const uint64_t base = new_off[ch.list], n = new_off[ch.list + 1] - base;
+        const uint32_t nc = (uint32_t)(n - ch.start < APP_COPY_UNIT ? n - ch.start : APP_COPY_UNIT);
+        uint32_t sn = 0;
+        uint64_t k = 0;
+        const bool fresh = sperm && look.get(ch.list, sn, k) && sn == perm_src;
+        const uint32_t *src = fresh ? sperm + soff[k] + ch.start : nullptr;
+        for (uint32_t j = lane; j < nc; j += 64u) perm[base + ch.start + j] = fresh ? src[j] : ch.start + j;
+    }
+}
+
+// ---- host side of the operations that derive an object from others: what they share
+// what: the prefix of the caller's message ("roc merge: ")
+bool roc_precision_ok(const char *what, int precision_mode) {
+    if (precision_mode >= VIDC_PREC_EXACT && precision_mode <= 32) return true;
+    set_error("%sprecision_mode %d unsupported (fixed precision must be 0..32)", what, precision_mode);
+    return false;
+}
+void clear_chain_info(vidc_ctx *ctx) {
+    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+}
+RocSrc roc_src(const vidc_roc *r) {
+    return RocSrc{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p, r->d_words.p, r->d_word_off.p, r->d_offsets.p};
+}
+// a new object of nlist lists on the context's device; host_offsets: with a host mirror of nlist + 1 offsets (from the process-wide
+// vector cache) that the caller fills in
+std::unique_ptr<vidc_roc> roc_derived(vidc_ctx *ctx, uint64_t nlist, bool host_offsets = true) {
+    std::unique_ptr<vidc_roc> nr(new vidc_roc());
+    nr->device = ctx->device;
+    nr->nlist = nlist;
+    if (host_offsets) {
+        nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
+        nr->offsets.resize(nlist + 1);
+        nr->offsets_host = true;
+    }
+    return nr;
+}
+
+// The lists `lists` of r, decoded into the staging CSR d_stage: lists[i] goes to d_stage + place(i).  (plan_decode orders the work
+// items by class: work item k is lists[p.item[k]].)
+template <class Place>
+int decode_into_staging(vidc_ctx *ctx, const vidc_roc *r, const std::vector<uint32_t> &lists, Place &&place, uint64_t *d_stage, double &kernel_ms) {
+    if (lists.empty()) return VIDC_OK;
+    PooledDecPlan p;
+    plan_decode(r, lists, false, p, ctx->wide);
+    std::vector<uint64_t> out_off(lists.size());
+    for (size_t k = 0; k < lists.size(); k++) out_off[k] = place(p.item[k]);  // work item k -> its place in the staging
+    VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), d_stage, nullptr, 0));
+    kernel_ms += ctx->last_kernel_ms;
+    return VIDC_OK;
+}
+
+// The splice.  List j of nr (device, nlist, rows / K set; offsets / ntotal too where the caller has a host mirror) takes its
+// metadata and its words from the list of S that `look` names, or is the encoders' empty list where it names none:
+//   the six per-list arrays; k_roc_regroup_meta (sizes, metadata, the non-empty count); one scan launch set for d_offsets and
+//   d_word_off; the totals back (24 bytes: words, ids, non-empty lists); the words with their padding; k_roc_regroup_copy;
+//   the permutation (want_perm): sperm over the lists of source perm_src where `look` names that source, the identity elsewhere.
+// An untouched list costs a copy of its words, not an ANS chain; like an imported object the result carries no planner hints (prec /
+// umax / order_desc are empty: the planners mirror the metadata on first use).  The blocks are the caller's, declared in front of
+// its StreamGuard; tm was started by the caller and is stopped into kernel_ms; copy_timer (optional) brackets the word copy alone.
+// Ends enqueued: the caller waits.
+struct RocSpliceScratch {
+    Scratch s_sizes, s_cnt, s_scan;
+    Pinned h_tot;  // word total | id total | non-empty lists
+    AppChunks ch_w, ch_p;
+};
+template <int N, class Lookup>
+int roc_splice(vidc_ctx *ctx, const RocSrcs<N> &S, const Lookup &look, vidc_roc *nr, bool want_perm, uint32_t perm_src, const uint32_t *sperm,
+               VidcPhaseTimer *copy_timer, RocSpliceScratch &sc, EventTimer &tm, double &kernel_ms) {
+    const uint64_t m = nr->nlist;
+    VIDC_TRY(nr->d_offsets.alloc(m + 1, ctx->dpool));
+    VIDC_TRY(nr->d_heads.alloc(m, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(m, ctx->dpool));
+    VIDC_TRY(nr->d_nwords.alloc(m, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(m, ctx->dpool));
+    VIDC_TRY(nr->d_word_off.alloc(m + 1, ctx->dpool));
+    VIDC_TRY(sc.s_sizes.get(ctx, (m + 1) * 4));
+    VIDC_TRY(sc.s_cnt.get(ctx, 8));
+    VIDC_TRY(sc.h_tot.get(ctx, 24));
+    uint64_t *h_tot = sc.h_tot.as<uint64_t>();
+    h_tot[0] = h_tot[1] = h_tot[2] = 0;
+    if (m) {
+        VIDC_HIP(hipMemsetAsync(sc.s_cnt.p, 0, 8, ctx->stream));
+        hipLaunchKernelGGL((k_roc_regroup_meta<N, Lookup>), req_grid(ctx, m), dim3(256), 0, ctx->stream, S, look, m, nr->d_heads.p, nr->d_prec.p,
+                           nr->d_nwords.p, nr->d_draws.p, sc.s_sizes.as<uint32_t>(), sc.s_cnt.as<unsigned long long>());
+        VIDC_HIP(hipGetLastError());
+        Scan4 scan{};
+        scan.in[0] = sc.s_sizes.as<uint32_t>(); scan.in[1] = nr->d_nwords.p; scan.out[0] = nr->d_offsets.p; scan.out[1] = nr->d_word_off.p;
+        VIDC_TRY(device_exscan4(ctx, scan, 2, (uint32_t)m, sc.s_scan));
+        VIDC_HIP(hipMemcpyAsync(h_tot, nr->d_word_off.p + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_tot + 1, nr->d_offsets.p + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_tot + 2, sc.s_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
+    }
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    nr->total_words = h_tot[0];
+    if (!nr->offsets_host) nr->ntotal = h_tot[1];  // (a caller with a host mirror of the offsets has set it)
+    nr->compressed_bytes = 8ull * h_tot[2] + 4ull * nr->total_words;
+    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
+    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
+    if (nr->total_words) {
+        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, m, nr->total_words, sc.ch_w));
+        if (copy_timer) copy_timer->begin();
+        hipLaunchKernelGGL((k_roc_regroup_copy<N, Lookup>), app_chunk_grid(ctx, sc.ch_w.bound), dim3(256), 0, ctx->stream, S, look,
+                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, sc.ch_w.items, sc.ch_w.n_items);
+        if (copy_timer) copy_timer->end();
+        VIDC_HIP(hipGetLastError());
+    }
+    if (want_perm && nr->ntotal) {
+        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, m, nr->ntotal, sc.ch_p));
+        hipLaunchKernelGGL(k_roc_regroup_perm<Lookup>, app_chunk_grid(ctx, sc.ch_p.bound), dim3(256), 0, ctx->stream, look, perm_src, sperm,
+                           sperm ? S.s[perm_src].offsets : (const uint64_t *)nullptr, (const uint64_t *)nr->d_offsets.p, sc.ch_p.items,
+                           sc.ch_p.n_items, nr->d_perm.p);
+        VIDC_HIP(hipGetLastError());
+    }
+    kernel_ms += tm.stop();
+    return VIDC_OK;
+}
+// the splice over {the old object, the small object of its re-encoded lists (may be NULL: no list is flagged)}: append, remove, subset
+int roc_splice(vidc_ctx *ctx, const vidc_roc *r, const vidc_roc *small, const RocSmallSlots &look, vidc_roc *nr, bool want_perm,
+                     RocSpliceScratch &sc, EventTimer &tm, double &kernel_ms) {
+    RocSrcs<2> S{};
+    S.s[0] = roc_src(r);
+    if (small) S.s[1] = roc_src(small);
+    return roc_splice(ctx, S, look, nr, want_perm, 1u, small ? (const uint32_t *)small->d_perm.p : nullptr, nullptr, sc, tm, kernel_ms);
+}
+
+// The candidate pass of the remove and of the subset by id; the locate runs its first half.
+// roc_decode_candidates: the candidates -- the non-empty lists of r that run_off names (NULL: every one; `any_work` false: none) -- are
+// compacted on the device and their numbers come back once (4 bytes per candidate, metadata); the host sizes a staging CSR (h_seg,
+// s_seg) and the candidates are decoded into it (s_stage), in ascending list order.
+// roc_candidate_pass: then mark(d_stage, d_seg, d_cand, cnt, total, d_rm, mk) marks the entries that go.  The candidates that lost an
+// entry are the touched lists: their staging numbers and survivor counts come back (8 bytes per touched list) and their survivors are
+// compacted into s_small_ids, the CSR (T lists, ts_off) that the caller encodes.  Leaves lflag / ltpos for the splice
+// (RocSmallSlots), t_list, killed, and in nr its id total and host offsets.
+// tm was started by the caller: what it enqueued since counts with the candidate kernels.  The blocks live in front of the caller's
+// StreamGuard.
+struct RocCandPass {
+    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids;
+    Pinned h_back, h_seg;
+    RemoveMarked mk;
+    uint64_t cnt = 0, total = 0;      // candidates, their ids
+    std::vector<uint32_t> cand;       // their list numbers, ascending
+    uint64_t T = 0, killed = 0;
+    std::vector<uint64_t> ts_off{0};  // the small object's offsets
+    std::vector<uint32_t> t_list;     // list numbers of the touched lists, ascending
+    RocSmallSlots look() const { return RocSmallSlots{s_lf.as<uint32_t>(), s_lt.as<uint64_t>()}; }
+};
+// the lflag / ltpos of a pass, or of a caller that fills them itself: allocated, no list flagged
+int roc_small_slots_clear(vidc_ctx *ctx, uint64_t nlist, RocCandPass &cp) {
+    VIDC_TRY(cp.s_lf.get(ctx, (nlist + 1) * 4));
+    VIDC_TRY(cp.s_lt.get(ctx, (nlist + 1) * 8));
+    VIDC_HIP(hipMemsetAsync(cp.s_lf.p, 0, (nlist + 1) * 4, ctx->stream));
+    return VIDC_OK;
+}
+int roc_decode_candidates(vidc_ctx *ctx, const vidc_roc *r, bool any_work, const uint64_t *run_off, RocCandPass &cp, HostTrace &tr, EventTimer &tm,
+                          double &kernel_ms) {
+    const uint64_t nlist = r->nlist;
+    VIDC_TRY(cp.s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
+    VIDC_TRY(cp.s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
+    VIDC_TRY(cp.s_cand.get(ctx, (nlist + 1) * 4));
+    uint32_t *mark_sz = cp.s_mark.as<uint32_t>(), *flag = mark_sz + nlist + 1;
+    uint64_t *stage_off = cp.s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
+    uint32_t *d_cand = cp.s_cand.as<uint32_t>();
+    VIDC_TRY(cp.h_back.get(ctx, 32 + (nlist + 1) * 8));
+    uint64_t *h_cnt = cp.h_back.as<uint64_t>();  // candidates | touched lists | survivors
+    uint32_t *h_a = (uint32_t *)(h_cnt + 4);
+    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
+    if (nlist && any_work) {
+        hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p, run_off, nlist, mark_sz,
+                           flag);
+        Scan4 sc{};
+        sc.in[0] = mark_sz; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, cp.s_t0));
+        hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    kernel_ms += tm.stop();
+    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+    const uint64_t cnt = cp.cnt = h_cnt[0];
+    cp.cand.resize(cnt);
+    VIDC_TRY(cp.h_seg.get(ctx, (cnt + 1) * 8));
+    uint64_t *seg_off = cp.h_seg.as<uint64_t>();
+    seg_off[0] = 0;
+    if (cnt) {
+        VIDC_HIP(hipMemcpyAsync(h_a, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        for (uint64_t k = 0; k < cnt; k++) {
+            cp.cand[k] = h_a[k];
+            seg_off[k + 1] = seg_off[k] + (r->offsets[h_a[k] + 1] - r->offsets[h_a[k]]);
+        }
+    }
+    cp.total = seg_off[cnt];
+    tr.mark("candidates read back");
+    if (cnt) {
+        VIDC_TRY(cp.s_stage.get(ctx, cp.total * 8));
+        VIDC_TRY(cp.s_seg.get(ctx, (cnt + 1) * 8));
+        VIDC_HIP(hipMemcpyAsync(cp.s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        VIDC_TRY(decode_into_staging(ctx, r, cp.cand, [&](uint32_t i) { return seg_off[i]; }, cp.s_stage.as<uint64_t>(), kernel_ms));
+        tr.mark("candidates decoded");
+    }
+    return VIDC_OK;
+}
+template <class Mark>
+int roc_candidate_pass(vidc_ctx *ctx, const vidc_roc *r, bool any_work, const uint64_t *run_off, Mark &&mark, vidc_roc *nr, RocCandPass &cp,
+                       HostTrace &tr, EventTimer &tm, double &kernel_ms) {
+    const uint64_t nlist = r->nlist;
+    VIDC_TRY(roc_decode_candidates(ctx, r, any_work, run_off, cp, tr, tm, kernel_ms));
+    VIDC_TRY(roc_small_slots_clear(ctx, nlist, cp));
+    if (const uint64_t cnt = cp.cnt) {
+        const uint64_t total = cp.total;
+        uint64_t *h_cnt = cp.h_back.as<uint64_t>();
+        uint32_t *h_a = (uint32_t *)(h_cnt + 4), *h_b = h_a + nlist + 1;
+        uint64_t *d_stage = cp.s_stage.as<uint64_t>(), *d_seg = cp.s_seg.as<uint64_t>();
+        uint32_t *d_cand = cp.s_cand.as<uint32_t>();
+        VIDC_TRY(cp.s_rm.get(ctx, total));
+        (void)tm.start();
+        VIDC_TRY(mark(d_stage, d_seg, d_cand, cnt, total, cp.s_rm.as<uint8_t>(), cp.mk));
+        VIDC_TRY(cp.s_tf.get(ctx, 2 * (cnt + 1) * 4));  // tflag | tmark
+        VIDC_TRY(cp.s_tp.get(ctx, 2 * (cnt + 1) * 8));  // tpos | tdst
+        VIDC_TRY(cp.s_tl.get(ctx, 2 * (cnt + 1) * 4));  // t_cand | t_left
+        uint32_t *tflag = cp.s_tf.as<uint32_t>(), *tmark = tflag + cnt + 1;
+        uint64_t *tpos = cp.s_tp.as<uint64_t>(), *tdst = tpos + cnt + 1;
+        uint32_t *t_cand = cp.s_tl.as<uint32_t>(), *t_left = t_cand + cnt + 1;
+        hipLaunchKernelGGL(k_rm_roc_kills, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint64_t *)d_seg, (const uint64_t *)cp.mk.new_off, cnt,
+                           tflag, tmark);
+        Scan4 sc{};
+        sc.in[0] = tflag; sc.in[1] = tmark; sc.out[0] = tpos; sc.out[1] = tdst;
+        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)cnt, cp.s_t1));
+        hipLaunchKernelGGL(k_rm_roc_touched, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint32_t *)tflag, (const uint32_t *)tmark,
+                           (const uint64_t *)tpos, (const uint32_t *)d_cand, cnt, t_cand, t_left, cp.s_lf.as<uint32_t>(), cp.s_lt.as<uint64_t>());
+        VIDC_HIP(hipGetLastError());
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, tpos + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, cp.mk.new_off + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        kernel_ms += tm.stop();
+        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+        cp.T = h_cnt[1];
+        cp.killed = total - h_cnt[2];
+        if (cp.T) {
+            VIDC_HIP(hipMemcpyAsync(h_a, t_cand, cp.T * 4, hipMemcpyDeviceToHost, ctx->stream));
+            VIDC_HIP(hipMemcpyAsync(h_b, t_left, cp.T * 4, hipMemcpyDeviceToHost, ctx->stream));
+            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
+            cp.ts_off.resize(cp.T + 1);
+            cp.t_list.resize(cp.T);
+            for (uint64_t t = 0; t < cp.T; t++) {
+                cp.t_list[t] = cp.cand[h_a[t]];
+                cp.ts_off[t + 1] = cp.ts_off[t] + h_b[t];
+            }
+            const uint64_t ttotal = cp.ts_off[cp.T];
+            VIDC_TRY(cp.s_small_ids.get(ctx, (ttotal ? ttotal : 1) * 8));
+            (void)tm.start();
+            VIDC_TRY(remove_compact(ctx, cp.mk, d_stage, d_seg, cp.s_rm.as<uint8_t>(), tdst, tflag, cp.s_small_ids.as<uint64_t>()));
+            kernel_ms += tm.stop();
+        }
+    }
+    tr.mark("candidates marked, touched lists read back");
+    // the new object's host offsets: every list moves down by what the touched lists in front of it lost
+    nr->ntotal = r->ntotal - cp.killed;
+    uint64_t gone = 0, t = 0;
+    for (uint64_t l = 0; l < nlist; l++) {
+        nr->offsets[l] = r->offsets[l] - gone;
+        if (t < cp.T && cp.t_list[t] == l) { gone += (r->offsets[l + 1] - r->offsets[l]) - (cp.ts_off[t + 1] - cp.ts_off[t]); t++; }
+    }
+    nr->offsets[nlist] = r->offsets[nlist] - gone;
+    return VIDC_OK;
 }
 
 }  // namespace
@@ -2181,41 +2430,38 @@ int vidc_roc_translate_labels_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, 
 
 // Append (include/vidc.h).  The batch is sorted by list on the device (append.h); the touched lists are marked and compacted there, and
 // their numbers and add counts come back once (8 bytes per touched list, metadata).  The host sizes a staging CSR of the merged touched
-// lists, the old ids are decoded into it (plan_decode / decode_impl on the subset), the batch ids are placed behind them, and
-// encode_impl runs on the staging CSR alone: a small object of the touched lists.  The new object is spliced on the device -- metadata
-// from the small object or the old one, the scan of the word counts, a segmented copy of every list's words from whichever object
-// holds them -- so an untouched list costs a copy of its words, not an ANS chain.  Like an imported object it carries no planner
-// hints (prec / umax / order_desc are empty: the planners mirror the metadata on first use).
+// lists, the old ids are decoded into it, the batch ids are placed behind them, and encode_impl runs on the staging CSR alone: the
+// small object of the touched lists, which the splice joins with the old one (flag / tpos are its RocSmallSlots).
 int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode,
                         uint32_t flags, vidc_roc **out, int64_t *d_labels, uint64_t *d_invalid) {
     VIDC_TRY(append_check(ctx, r, out, n_add, d_list_nos, d_ids));
     if (r->rows) { set_error("roc append: graph objects are not appendable"); return VIDC_ERR_UNSUPPORTED; }
-    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
-        set_error("precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
-        return VIDC_ERR_INVALID;
-    }
+    if (!roc_precision_ok("", precision_mode)) return VIDC_ERR_INVALID;
     VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
     VIDC_HIP(hipSetDevice(ctx->device));
     HostTrace tr("roc append");
     const uint64_t nlist = r->nlist;
     const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
-    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    clear_chain_info(ctx);
     double kernel_ms = 0;
     AppendBatch b;
+    std::unique_ptr<vidc_roc> small, nr;
+    Scratch s_mark, s_off, s_touched, s_t0, s_stage;
+    Pinned h_back;
+    AppChunks ch_l;
+    RocSpliceScratch sp_scratch;
+    StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
     VIDC_TRY(append_sort_batch(ctx, nlist, r->d_offsets.p, n_add, d_list_nos, d_invalid, b));
     tr.mark("batch sorted by list");
     // the touched lists
-    Scratch s_mark, s_off, s_touched, s_t0, s_stage, s_slot;
-    Pinned h_back;
     VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));   // mark | flag
     VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));    // stage_off | tpos
     VIDC_TRY(s_touched.get(ctx, 2 * (nlist + 1) * 4));  // touched | added
-    VIDC_TRY(s_slot.get(ctx, (nlist + 1) * 4));
     uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
     uint64_t *stage_off = s_off.as<uint64_t>(), *tpos = stage_off + nlist + 1;
-    VIDC_TRY(h_back.get(ctx, 16 + (nlist + 1) * 8));
+    VIDC_TRY(h_back.get(ctx, 8 + (nlist + 1) * 8));
     uint64_t *h_cnt = h_back.as<uint64_t>();
-    uint32_t *h_touched = (uint32_t *)(h_cnt + 2), *h_added = h_touched + nlist + 1;
+    uint32_t *h_touched = (uint32_t *)(h_cnt + 1), *h_added = h_touched + nlist + 1;
     uint32_t *d_touched = s_touched.as<uint32_t>(), *d_added = d_touched + nlist + 1;
     h_cnt[0] = 0;
     if (nlist) {
@@ -2248,40 +2494,25 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
         if (old_n) { dec_lists.push_back((uint32_t)l); dec_slot.push_back((uint32_t)k); }
     }
     const uint64_t total = st_off[cnt];
-    std::unique_ptr<vidc_roc> nr(new vidc_roc());
-    nr->device = ctx->device;
-    nr->nlist = nlist;
+    nr = roc_derived(ctx, nlist);
     nr->ntotal = r->ntotal + b.n_valid;
-    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
-    nr->offsets.resize(nlist + 1);
-    uint64_t nonempty = 0;
     {
         uint64_t shift = 0, k = 0;
         for (uint64_t l = 0; l < nlist; l++) {
             nr->offsets[l] = r->offsets[l] + shift;
             if (k < cnt && h_touched[k] == l) shift += h_added[k++];
-            nonempty += r->offsets[l + 1] + shift != nr->offsets[l];
         }
         nr->offsets[nlist] = r->offsets[nlist] + shift;
     }
-    nr->offsets_host = true;
     tr.mark("touched lists read back, staging sized");
     VIDC_TRY(s_stage.get(ctx, (total ? total : 1) * 8));
-    if (!dec_lists.empty()) {
-        PooledDecPlan p;
-        plan_decode(r, dec_lists, false, p, ctx->wide);
-        std::vector<uint64_t> out_off(dec_lists.size());
-        for (size_t k = 0; k < dec_lists.size(); k++) out_off[k] = st_off[dec_slot[p.item[k]]];  // work item k -> its place in the staging
-        VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
-        kernel_ms += ctx->last_kernel_ms;
-    }
+    VIDC_TRY(decode_into_staging(ctx, r, dec_lists, [&](uint32_t i) { return st_off[dec_slot[i]]; }, s_stage.as<uint64_t>(), kernel_ms));
     tr.mark("touched lists decoded");
     if (n_add) {
         hipLaunchKernelGGL(k_app_place, req_grid(ctx, n_add), dim3(256), 0, ctx->stream, b.keys, b.vals, (uint32_t)n_add, nlist, r->d_offsets.p,
                            (const uint64_t *)b.add_off, (const uint64_t *)stage_off, d_ids, s_stage.as<uint64_t>(), d_labels, false);
         VIDC_HIP(hipGetLastError());
     }
-    std::unique_ptr<vidc_roc> small;
     if (cnt) {
         vidc_roc *sp = nullptr;
         VIDC_TRY(encode_impl(ctx, cnt, st_off.data(), s_stage.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
@@ -2290,47 +2521,7 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
         kernel_ms += ctx->last_kernel_ms;
     }
     tr.mark("touched lists encoded");
-    // splice
-    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, b.new_off, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
     EventTimer tm = EventTimer::started(ctx);
-    Scratch s_t1;
-    if (nlist) {
-        const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};
-        const RocMeta m_small = small ? RocMeta{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p} : m_old;
-        hipLaunchKernelGGL(k_app_roc_meta, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, tpos, nlist, m_old, m_small, nr->d_heads.p,
-                           nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_slot.as<uint32_t>());
-        VIDC_HIP(hipGetLastError());
-        VIDC_TRY(device_exscan(ctx, nr->d_nwords.p, (uint32_t)nlist, nr->d_word_off.p, s_t1));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
-        h_cnt[1] = 0;
-    }
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    nr->total_words = h_cnt[1];
-    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
-    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
-    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
-    AppChunks ch_w, ch_p, ch_l;
-    if (nr->total_words) {
-        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, ch_w));
-        hipLaunchKernelGGL((k_app_copy<uint32_t, true>), app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, (const uint32_t *)r->d_words.p,
-                           (const uint64_t *)r->d_word_off.p, small ? (const uint32_t *)small->d_words.p : nullptr,
-                           small ? (const uint64_t *)small->d_word_off.p : nullptr, (const uint32_t *)s_slot.as<uint32_t>(),
-                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
-        VIDC_HIP(hipGetLastError());
-    }
-    if (want_perm && nr->ntotal) {
-        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, ch_p));
-        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
-                           (const uint32_t *)s_slot.as<uint32_t>(), small ? (const uint32_t *)small->d_perm.p : nullptr,
-                           small ? (const uint64_t *)small->d_offsets.p : nullptr, ch_p.items, ch_p.n_items, nr->d_perm.p);
-        VIDC_HIP(hipGetLastError());
-    }
     if (d_labels && small) {  // a batch entry's offset: where the small object's permutation names it (sampling order)
         VIDC_TRY(app_chunks(ctx, small->d_offsets.p, cnt, total, ch_l));
         hipLaunchKernelGGL(k_app_labels_perm, app_chunk_grid(ctx, ch_l.bound), dim3(256), 0, ctx->stream, (const uint32_t *)small->d_perm.p,
@@ -2338,8 +2529,9 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
                            (const uint64_t *)b.add_off, b.vals, ch_l.items, ch_l.n_items, d_labels);
         VIDC_HIP(hipGetLastError());
     }
-    kernel_ms += tm.stop();
+    VIDC_TRY(roc_splice(ctx, r, small.get(), RocSmallSlots{flag, tpos}, nr.get(), want_perm, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
+    guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
     tr.mark("spliced");
     *out = nr.release();
@@ -2348,19 +2540,14 @@ int vidc_roc_append_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_add, const 
 
 // Merge (include/vidc.h).  The lists are classified on the device (merge.h): a list without ids of `b` keeps a's stream, a list
 // without ids of `a` keeps b's when nothing is shifted, every other list is re-encoded.  The numbers and merged sizes of the
-// re-encoded lists come back once (8 bytes each, metadata); the host sizes a staging CSR of them, a's ids are decoded into it
-// (plan_decode / decode_impl on the subset), b's into a staging of their own and from there behind a's with add_id added
-// (k_mrg_copy_add, which also reduces the largest id for the domain check), and encode_impl runs on the staging CSR alone.  The new
-// object is spliced as vidc_roc_update_rows_dev splices: metadata gathered from {a, b, the small object} through the class table, one
-// scan launch set for the offsets and the word offsets, a chunked copy of every list's words from whichever object holds them.  Like
-// an imported object the result carries no planner hints.
+// re-encoded lists come back once (8 bytes each, metadata); the host sizes a staging CSR of them, a's ids are decoded into it, b's
+// into a staging of their own and from there behind a's with add_id added (k_mrg_copy_add, which also reduces the largest id for the
+// domain check), and encode_impl runs on the staging CSR alone.  The splice is over {a, b, the small object} through the class table
+// (RocMergeSlots).
 int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint64_t add_id, int precision_mode, uint32_t flags, vidc_roc **out,
                        int64_t *d_src) {
     VIDC_TRY(merge_check(ctx, a, b, out));
-    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
-        set_error("roc merge: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
-        return VIDC_ERR_INVALID;
-    }
+    if (!roc_precision_ok("roc merge: ", precision_mode)) return VIDC_ERR_INVALID;
     if (a->rows || b->rows) { set_error("roc merge: graph objects hold no lists to merge"); return VIDC_ERR_UNSUPPORTED; }
     VIDC_TRY(a->prec.size() == a->nlist ? ensure_offsets(a) : ensure_meta(a));
     if (b != a) VIDC_TRY(b->prec.size() == b->nlist ? ensure_offsets(b) : ensure_meta(b));
@@ -2368,25 +2555,25 @@ int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint
     HostTrace tr("roc merge");
     const uint64_t nlist = a->nlist;
     const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0, need_perm = want_perm || d_src;
-    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    clear_chain_info(ctx);
     double kernel_ms = 0;
     std::unique_ptr<vidc_roc> small, nr;
-    Scratch s_cls, s_off, s_touched, s_t0, s_t1, s_stage, s_bstage, s_sizes, s_cnt;
+    Scratch s_cls, s_off, s_touched, s_t0, s_stage, s_bstage, s_max;
     Pinned h_back;
-    AppChunks ch_b, ch_w, ch_p;
+    AppChunks ch_b;
+    RocSpliceScratch sp_scratch;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
     VIDC_TRY(s_cls.get(ctx, 5 * (nlist + 1) * 4));      // cls | flag | mark | bmark | slot
     VIDC_TRY(s_off.get(ctx, 4 * (nlist + 1) * 8));      // stage_off | tpos | bstage_off | dst_start
     VIDC_TRY(s_touched.get(ctx, 2 * (nlist + 1) * 4));  // touched | msize
-    VIDC_TRY(s_sizes.get(ctx, (nlist + 1) * 4));
-    VIDC_TRY(s_cnt.get(ctx, 16));                       // non-empty lists | largest id of b's re-encoded lists
-    VIDC_TRY(h_back.get(ctx, 32 + (nlist + 1) * 8));
+    VIDC_TRY(s_max.get(ctx, 8));                        // largest id of b's re-encoded lists
+    VIDC_TRY(h_back.get(ctx, 16 + (nlist + 1) * 8));
     uint32_t *cls = s_cls.as<uint32_t>(), *flag = cls + nlist + 1, *mark = flag + nlist + 1, *bmark = mark + nlist + 1, *slot = bmark + nlist + 1;
     uint64_t *stage_off = s_off.as<uint64_t>(), *tpos = stage_off + nlist + 1, *bstage_off = tpos + nlist + 1, *dst_start = bstage_off + nlist + 1;
     uint32_t *d_touched = s_touched.as<uint32_t>(), *d_msize = d_touched + nlist + 1;
-    uint64_t *h_cnt = h_back.as<uint64_t>();  // re-encoded lists | largest id | word total | non-empty lists
-    uint32_t *h_touched = (uint32_t *)(h_cnt + 4), *h_msize = h_touched + nlist + 1;
-    h_cnt[0] = h_cnt[1] = h_cnt[2] = h_cnt[3] = 0;
+    uint64_t *h_cnt = h_back.as<uint64_t>();  // re-encoded lists | largest id
+    uint32_t *h_touched = (uint32_t *)(h_cnt + 2), *h_msize = h_touched + nlist + 1;
+    h_cnt[0] = h_cnt[1] = 0;
     const uint64_t *a_off = a->d_offsets.p, *b_off = b->d_offsets.p;
     EventTimer tm = EventTimer::started(ctx);
     if (nlist) {
@@ -2430,32 +2617,18 @@ int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint
     if (cnt) {
         VIDC_TRY(s_stage.get(ctx, total * 8));
         VIDC_TRY(s_bstage.get(ctx, btotal * 8));
-        if (!dec_a.empty()) {
-            PooledDecPlan p;
-            plan_decode(a, dec_a, false, p, ctx->wide);
-            std::vector<uint64_t> out_off(dec_a.size());
-            for (size_t k = 0; k < dec_a.size(); k++) out_off[k] = st_off[dec_a_slot[p.item[k]]];  // work item k -> its place in the staging
-            VIDC_TRY(decode_impl(ctx, a, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
-            kernel_ms += ctx->last_kernel_ms;
-        }
-        {
-            PooledDecPlan p;
-            plan_decode(b, dec_b, false, p, ctx->wide);
-            std::vector<uint64_t> out_off(cnt);
-            for (size_t k = 0; k < cnt; k++) out_off[k] = bst_off[p.item[k]];
-            VIDC_TRY(decode_impl(ctx, b, p, out_off.data(), s_bstage.as<uint64_t>(), nullptr, 0));
-            kernel_ms += ctx->last_kernel_ms;
-        }
+        VIDC_TRY(decode_into_staging(ctx, a, dec_a, [&](uint32_t i) { return st_off[dec_a_slot[i]]; }, s_stage.as<uint64_t>(), kernel_ms));
+        VIDC_TRY(decode_into_staging(ctx, b, dec_b, [&](uint32_t i) { return bst_off[i]; }, s_bstage.as<uint64_t>(), kernel_ms));
         tr.mark("re-encoded lists decoded on both sides");
         (void)tm.start();
-        VIDC_HIP(hipMemsetAsync(s_cnt.as<uint64_t>() + 1, 0, 8, ctx->stream));
+        VIDC_HIP(hipMemsetAsync(s_max.p, 0, 8, ctx->stream));
         VIDC_TRY(app_chunks(ctx, bstage_off, nlist, btotal, ch_b));
         hipLaunchKernelGGL(k_mrg_copy_add, app_chunk_grid(ctx, ch_b.bound), dim3(256), 0, ctx->stream, (const uint64_t *)s_bstage.as<uint64_t>(),
                            (const uint64_t *)bstage_off, (const uint64_t *)dst_start, s_stage.as<uint64_t>(), add_id, ch_b.items, ch_b.n_items,
-                           s_cnt.as<unsigned long long>() + 1);
+                           s_max.as<unsigned long long>());
         VIDC_HIP(hipGetLastError());
         (void)tm.mark();
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, s_cnt.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, s_max.p, 8, hipMemcpyDeviceToHost, ctx->stream));
         VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
         kernel_ms += tm.elapsed();
         if (merge_shift_overflows(h_cnt[1], add_id, 31u)) {
@@ -2470,59 +2643,16 @@ int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint
         tr.mark("re-encoded lists encoded");
     }
     // splice
-    nr.reset(new vidc_roc());
-    nr->device = ctx->device;
-    nr->nlist = nlist;
+    nr = roc_derived(ctx, nlist);
     nr->ntotal = a->ntotal + b->ntotal;
-    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
-    nr->offsets.resize(nlist + 1);
     for (uint64_t l = 0; l <= nlist; l++) nr->offsets[l] = a->offsets[l] + b->offsets[l];
-    nr->offsets_host = true;
-    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
-    RocSrcs S{};
-    S.s[MRG_KEEP_A] = RocSrc{{a->d_heads.p, a->d_prec.p, a->d_nwords.p, a->d_draws.p}, a->d_words.p, a->d_word_off.p, a->d_offsets.p};
-    S.s[MRG_KEEP_B] = RocSrc{{b->d_heads.p, b->d_prec.p, b->d_nwords.p, b->d_draws.p}, b->d_words.p, b->d_word_off.p, b->d_offsets.p};
-    if (small)
-        S.s[MRG_ENCODE] = RocSrc{{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p}, small->d_words.p, small->d_word_off.p,
-                                 small->d_offsets.p};
-    const RocMergeSlots look{cls, tpos};
+    RocSrcs<3> S{};
+    S.s[MRG_KEEP_A] = roc_src(a);
+    S.s[MRG_KEEP_B] = roc_src(b);
+    if (small) S.s[MRG_ENCODE] = roc_src(small.get());
     (void)tm.start();
-    if (nlist) {
-        VIDC_HIP(hipMemsetAsync(s_cnt.p, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_roc_regroup_meta<RocMergeSlots>, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, S, look, nlist, nr->d_heads.p,
-                           nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>(), s_cnt.as<unsigned long long>());
-        VIDC_HIP(hipGetLastError());
-        Scan4 sc{};
-        sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
-        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t1));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 3, s_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
-        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
-    }
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    nr->total_words = h_cnt[2];
-    nr->compressed_bytes = 8ull * h_cnt[3] + 4ull * nr->total_words;
-    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
-    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
-    if (nr->total_words) {
-        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, ch_w));
-        hipLaunchKernelGGL(k_roc_regroup_copy<RocMergeSlots>, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S, look,
-                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
-        VIDC_HIP(hipGetLastError());
-    }
-    if (want_perm && nr->ntotal) {
-        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, ch_p));
-        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
-                           (const uint32_t *)slot, small ? (const uint32_t *)small->d_perm.p : nullptr,
-                           small ? (const uint64_t *)small->d_offsets.p : nullptr, ch_p.items, ch_p.n_items, nr->d_perm.p);
-        VIDC_HIP(hipGetLastError());
-    }
-    kernel_ms += tm.stop();
+    VIDC_TRY(roc_splice(ctx, S, RocMergeSlots{cls, tpos}, nr.get(), want_perm, MRG_ENCODE, small ? (const uint32_t *)small->d_perm.p : nullptr,
+                        nullptr, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
     // where every entry came from: the small object's permutation names the input position of a re-encoded list's entries, the kept
     // lists decode in their source's order
@@ -2535,236 +2665,52 @@ int vidc_roc_merge_dev(vidc_ctx *ctx, const vidc_roc *a, const vidc_roc *b, uint
     return VIDC_OK;
 }
 
-// Remove (include/vidc.h).  The batch is sorted by (list, id) on the device (remove.h).  The candidates -- the non-empty lists a valid
-// pair names, or every non-empty list in any-list mode -- are compacted there and their numbers come back once (4 bytes per
-// candidate, metadata); the host sizes a staging CSR, the candidates are decoded into it (plan_decode / decode_impl on the subset)
-// and marked.  The candidates that lost an entry are the touched lists: their staging numbers and survivor counts come back (8 bytes
-// per touched list), their survivors are compacted into a second staging CSR and encode_impl runs on that alone.  The splice is the
-// append's: metadata from the small object or the old one, the scan of the word counts, a segmented copy of every list's words.
+// Remove (include/vidc.h).  The batch is sorted by (list, id) on the device (remove.h); the candidates are the non-empty lists a
+// valid pair names, or every non-empty list in any-list mode (roc_candidate_pass with the batch's mark); encode_impl runs on the
+// compacted survivors of the touched lists alone, and the splice joins that small object with the old one.
 // (the body is vidc::roc_remove, which the sharded remove calls with the per-pair found bytes; common.h)
 extern "C++" {
 namespace vidc {
-// The splice of the remove and of the subset: nr (nlist, ntotal and the host offsets filled in; `nonempty` of its lists hold ids) takes
-// list l from list ltpos[l] of `small` where lflag[l] != 0 and from the old object r otherwise -- metadata, the scan of the word
-// counts, a segmented copy of every list's words, the permutation (small's, or the identity).  small == NULL: no list is flagged.
-// The scratch blocks and the pinned word total (h_words) are the caller's, declared in front of its StreamGuard; tm is restarted
-// here and stopped into kernel_ms.  Ends enqueued: the caller waits.
-struct RocSpliceScratch {
-    Scratch s_slot, s_sizes, s_t1, s_t2;
-    AppChunks ch_w, ch_p;
-};
-static int roc_splice_small(vidc_ctx *ctx, const vidc_roc *r, vidc_roc *nr, uint64_t nonempty, const uint32_t *lflag, const uint64_t *ltpos,
-                            const vidc_roc *small, bool want_perm, uint64_t *h_words, RocSpliceScratch &S, EventTimer &tm, double &kernel_ms) {
-    const uint64_t nlist = r->nlist;
-    nr->offsets_host = true;
-    VIDC_TRY(nr->d_offsets.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(nr->d_heads.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_nwords.alloc(nlist, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(nlist, ctx->dpool));
-    VIDC_TRY(nr->d_word_off.alloc(nlist + 1, ctx->dpool));
-    VIDC_TRY(S.s_slot.get(ctx, (nlist + 1) * 4));
-    VIDC_TRY(S.s_sizes.get(ctx, (nlist + 1) * 4));
-    (void)tm.start();
-    if (nlist) {
-        if (small) {
-            hipLaunchKernelGGL(k_rm_roc_sizes, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos,
-                               (const uint64_t *)r->d_offsets.p, (const uint64_t *)small->d_offsets.p, nlist, S.s_sizes.as<uint32_t>());
-            VIDC_TRY(device_exscan(ctx, S.s_sizes.as<uint32_t>(), (uint32_t)nlist, nr->d_offsets.p, S.s_t2));
-        } else {
-            VIDC_HIP(hipMemcpyAsync(nr->d_offsets.p, r->d_offsets.p, (nlist + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        const RocMeta m_old{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p};
-        const RocMeta m_small = small ? RocMeta{small->d_heads.p, small->d_prec.p, small->d_nwords.p, small->d_draws.p} : m_old;
-        hipLaunchKernelGGL(k_app_roc_meta, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint32_t *)lflag, (const uint64_t *)ltpos, nlist,
-                           m_old, m_small, nr->d_heads.p, nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, S.s_slot.as<uint32_t>());
-        VIDC_HIP(hipGetLastError());
-        VIDC_TRY(device_exscan(ctx, nr->d_nwords.p, (uint32_t)nlist, nr->d_word_off.p, S.s_t1));
-        VIDC_HIP(hipMemcpyAsync(h_words, nr->d_word_off.p + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
-        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
-        h_words[0] = 0;
-    }
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    nr->total_words = h_words[0];
-    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
-    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
-    if (want_perm) VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
-    if (nr->total_words) {
-        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, nlist, nr->total_words, S.ch_w));
-        hipLaunchKernelGGL((k_app_copy<uint32_t, true>), app_chunk_grid(ctx, S.ch_w.bound), dim3(256), 0, ctx->stream, (const uint32_t *)r->d_words.p,
-                           (const uint64_t *)r->d_word_off.p, small ? (const uint32_t *)small->d_words.p : nullptr,
-                           small ? (const uint64_t *)small->d_word_off.p : nullptr, (const uint32_t *)S.s_slot.as<uint32_t>(),
-                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, S.ch_w.items, S.ch_w.n_items);
-        VIDC_HIP(hipGetLastError());
-    }
-    if (want_perm && nr->ntotal) {
-        VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, nlist, nr->ntotal, S.ch_p));
-        hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, S.ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
-                           (const uint32_t *)S.s_slot.as<uint32_t>(), small ? (const uint32_t *)small->d_perm.p : nullptr,
-                           small ? (const uint64_t *)small->d_offsets.p : nullptr, S.ch_p.items, S.ch_p.n_items, nr->d_perm.p);
-        VIDC_HIP(hipGetLastError());
-    }
-    kernel_ms += tm.stop();
-    return VIDC_OK;
-}
-
 int roc_remove(vidc_ctx *ctx, const vidc_roc *r, uint64_t n_rm, const int64_t *d_list_nos, const uint64_t *d_ids, int precision_mode, uint32_t flags,
                vidc_roc **out, uint8_t *d_removed, uint64_t *d_missing, uint64_t *d_invalid, uint8_t *d_pair_found) {
     VIDC_TRY(remove_check(ctx, r, out, n_rm, d_ids));
-    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
-        set_error("roc remove: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
-        return VIDC_ERR_INVALID;
-    }
+    if (!roc_precision_ok("roc remove: ", precision_mode)) return VIDC_ERR_INVALID;
     if (r->rows) { set_error("roc remove: graph objects hold no removable lists"); return VIDC_ERR_UNSUPPORTED; }
     VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
     VIDC_HIP(hipSetDevice(ctx->device));
     HostTrace tr("roc remove");
-    const uint64_t nlist = r->nlist;
     const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
-    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    clear_chain_info(ctx);
     double kernel_ms = 0;
     RemoveBatch b;
-    RemoveMarked mk;
-    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids;
-    Pinned h_back, h_seg;
+    std::unique_ptr<vidc_roc> small, nr = roc_derived(ctx, r->nlist);
+    RocCandPass cp;
     RocSpliceScratch sp_scratch;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
     EventTimer tm = EventTimer::started(ctx);
-    VIDC_TRY(remove_sort_batch(ctx, nlist, n_rm, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
+    VIDC_TRY(remove_sort_batch(ctx, r->nlist, n_rm, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
     if (d_removed && r->ntotal) VIDC_HIP(hipMemsetAsync(d_removed, 0, r->ntotal, ctx->stream));
-    // the candidates
-    VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
-    VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
-    VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
-    uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
-    uint64_t *stage_off = s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
-    uint32_t *d_cand = s_cand.as<uint32_t>();
-    VIDC_TRY(h_back.get(ctx, 32 + (nlist + 1) * 8));
-    uint64_t *h_cnt = h_back.as<uint64_t>();
-    uint32_t *h_a = (uint32_t *)(h_cnt + 4), *h_b = h_a + nlist + 1;
-    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
-    if (nlist && n_rm) {  // (an empty batch has no candidate, in either mode)
-        hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p,
-                           b.any ? (const uint64_t *)nullptr : b.run_off, nlist, mark, flag);
-        Scan4 sc{};
-        sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
-        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
-        hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    kernel_ms += tm.stop();
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    const uint64_t cnt = h_cnt[0];
-    std::vector<uint32_t> cand(cnt);
-    VIDC_TRY(h_seg.get(ctx, (cnt + 1) * 8));
-    uint64_t *seg_off = h_seg.as<uint64_t>();
-    seg_off[0] = 0;
-    if (cnt) {
-        VIDC_HIP(hipMemcpyAsync(h_a, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        for (uint64_t k = 0; k < cnt; k++) {
-            cand[k] = h_a[k];
-            seg_off[k + 1] = seg_off[k] + (r->offsets[cand[k] + 1] - r->offsets[cand[k]]);
-        }
-    }
-    const uint64_t total = seg_off[cnt];
-    tr.mark("batch sorted, candidates read back");
-    // decode and mark the candidates; the touched ones
-    uint64_t T = 0, ttotal = 0, killed = 0;
-    std::vector<uint64_t> ts_off(1, 0);
-    std::vector<uint32_t> t_list;  // list numbers of the touched lists, ascending
-    VIDC_TRY(s_lf.get(ctx, (nlist + 1) * 4));
-    VIDC_TRY(s_lt.get(ctx, (nlist + 1) * 8));
-    uint32_t *lflag = s_lf.as<uint32_t>();
-    uint64_t *ltpos = s_lt.as<uint64_t>();
-    VIDC_HIP(hipMemsetAsync(lflag, 0, (nlist + 1) * 4, ctx->stream));
-    if (cnt) {
-        VIDC_TRY(s_stage.get(ctx, total * 8));
-        VIDC_TRY(s_rm.get(ctx, total));
-        VIDC_TRY(s_seg.get(ctx, (cnt + 1) * 8));
-        VIDC_HIP(hipMemcpyAsync(s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        {
-            PooledDecPlan p;
-            plan_decode(r, cand, false, p, ctx->wide);
-            std::vector<uint64_t> out_off(cnt);
-            for (size_t k = 0; k < cnt; k++) out_off[k] = seg_off[p.item[k]];  // work item k -> its place in the staging
-            VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
-            kernel_ms += ctx->last_kernel_ms;
-        }
-        tr.mark("candidates decoded");
-        (void)tm.start();
-        VIDC_TRY(remove_mark(ctx, b, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), d_cand, cnt, total, s_rm.as<uint8_t>(), d_removed,
-                             (const uint64_t *)r->d_offsets.p, d_missing, mk));
-        VIDC_TRY(s_tf.get(ctx, 2 * (cnt + 1) * 4));  // tflag | tmark
-        VIDC_TRY(s_tp.get(ctx, 2 * (cnt + 1) * 8));  // tpos | tdst
-        VIDC_TRY(s_tl.get(ctx, 2 * (cnt + 1) * 4));  // t_cand | t_left
-        uint32_t *tflag = s_tf.as<uint32_t>(), *tmark = tflag + cnt + 1;
-        uint64_t *tpos = s_tp.as<uint64_t>(), *tdst = tpos + cnt + 1;
-        uint32_t *t_cand = s_tl.as<uint32_t>(), *t_left = t_cand + cnt + 1;
-        hipLaunchKernelGGL(k_rm_roc_kills, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint64_t *)s_seg.as<uint64_t>(),
-                           (const uint64_t *)mk.new_off, cnt, tflag, tmark);
-        Scan4 sc{};
-        sc.in[0] = tflag; sc.in[1] = tmark; sc.out[0] = tpos; sc.out[1] = tdst;
-        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)cnt, s_t1));
-        hipLaunchKernelGGL(k_rm_roc_touched, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint32_t *)tflag, (const uint32_t *)tmark,
-                           (const uint64_t *)tpos, (const uint32_t *)d_cand, cnt, t_cand, t_left, lflag, ltpos);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, tpos + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, mk.new_off + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-        kernel_ms += tm.stop();
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        T = h_cnt[1];
-        killed = total - h_cnt[2];
-        if (T) {
-            VIDC_HIP(hipMemcpyAsync(h_a, t_cand, T * 4, hipMemcpyDeviceToHost, ctx->stream));
-            VIDC_HIP(hipMemcpyAsync(h_b, t_left, T * 4, hipMemcpyDeviceToHost, ctx->stream));
-            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-            ts_off.resize(T + 1);
-            t_list.resize(T);
-            for (uint64_t t = 0; t < T; t++) {
-                t_list[t] = cand[h_a[t]];
-                ts_off[t + 1] = ts_off[t] + h_b[t];
-            }
-            ttotal = ts_off[T];
-            VIDC_TRY(s_small_ids.get(ctx, (ttotal ? ttotal : 1) * 8));
-            (void)tm.start();
-            VIDC_TRY(remove_compact(ctx, mk, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), s_rm.as<uint8_t>(), tdst, tflag, s_small_ids.as<uint64_t>()));
-            kernel_ms += tm.stop();
-        }
-    }
+    // (an empty batch has no candidate, in either mode)
+    VIDC_TRY(roc_candidate_pass(ctx, r, n_rm != 0, b.any ? (const uint64_t *)nullptr : b.run_off,
+                                [&](auto *d_stage, auto *d_seg, auto *d_cand, uint64_t cnt, uint64_t total, uint8_t *d_rm, RemoveMarked &mk) {
+                                    return remove_mark(ctx, b, d_stage, d_seg, d_cand, cnt, total, d_rm, d_removed, (const uint64_t *)r->d_offsets.p,
+                                                       d_missing, mk);
+                                },
+                                nr.get(), cp, tr, tm, kernel_ms));
     (void)tm.start();
     VIDC_TRY(remove_count_missing(ctx, b, d_missing));
     VIDC_TRY(remove_pair_found(ctx, b, d_pair_found));
     kernel_ms += tm.stop();
-    tr.mark("candidates marked, touched lists read back");
-    std::unique_ptr<vidc_roc> small;
-    if (T) {
+    if (cp.T) {
         vidc_roc *sp = nullptr;
-        VIDC_TRY(encode_impl(ctx, T, ts_off.data(), s_small_ids.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
+        VIDC_TRY(encode_impl(ctx, cp.T, cp.ts_off.data(), cp.s_small_ids.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
                              want_perm ? VIDC_ROC_WANT_PERM : 0u, &sp));
         small.reset(sp);
         kernel_ms += ctx->last_kernel_ms;
     }
     tr.mark("touched lists encoded");
-    // the new object: host offsets, then the append's splice
-    std::unique_ptr<vidc_roc> nr(new vidc_roc());
-    nr->device = ctx->device;
-    nr->nlist = nlist;
-    nr->ntotal = r->ntotal - killed;
-    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
-    nr->offsets.resize(nlist + 1);
-    uint64_t nonempty = 0;
-    {
-        uint64_t gone = 0, t = 0;
-        for (uint64_t l = 0; l < nlist; l++) {
-            nr->offsets[l] = r->offsets[l] - gone;
-            if (t < T && t_list[t] == l) { gone += (r->offsets[l + 1] - r->offsets[l]) - (ts_off[t + 1] - ts_off[t]); t++; }
-            nonempty += r->offsets[l + 1] - gone != nr->offsets[l];
-        }
-        nr->offsets[nlist] = r->offsets[nlist] - gone;
-    }
-    VIDC_TRY(roc_splice_small(ctx, r, nr.get(), nonempty, lflag, ltpos, small.get(), want_perm, h_cnt + 3, sp_scratch, tm, kernel_ms));
+    (void)tm.start();
+    VIDC_TRY(roc_splice(ctx, r, small.get(), cp.look(), nr.get(), want_perm, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
     guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
@@ -2788,153 +2734,46 @@ __global__ void __launch_bounds__(256) k_sub_roc_slots(const uint32_t *__restric
 }
 }  // namespace
 
-// Subset (include/vidc.h).  Types 0 and 1 are a remove in any-list mode with the predicate mark of subset.h in place of the batch:
-// every non-empty list is a candidate, decoded into a staging CSR and marked; the candidates that lose an entry are compacted into a
-// second staging CSR and encode_impl runs on that alone.  Types 2 .. 4 need no id: k_sub_bounds classifies every list from the
-// offsets, the host runs the same functions (subset_plan.h) on its mirror of the offsets and so knows the partial lists and every new
-// size without a read-back; only the partial lists are decoded, sliced in staging and encoded.  The lists that keep nothing take the
-// encoder's own empty list, one trailing list of the small object.  The splice is the remove's (roc_splice_small).
+// Subset (include/vidc.h).  Types 0 and 1 are a remove in any-list mode with the predicate mark of subset.h in place of the batch
+// (roc_candidate_pass over every non-empty list).  Types 2 .. 4 need no id: k_sub_bounds classifies every list from the offsets, the
+// host runs the same functions (subset_plan.h) on its mirror of the offsets and so knows the partial lists and every new size without
+// a read-back; only the partial lists are decoded, sliced in staging and encoded.  The lists that keep nothing take the encoder's own
+// empty list, one trailing list of the small object.
 static int roc_subset(vidc_ctx *ctx, const vidc_roc *r, int type, uint64_t a1, uint64_t a2, int precision_mode, uint32_t flags, vidc_roc **out,
                       uint8_t *d_taken, uint64_t *n_taken) {
     VIDC_TRY(subset_check("roc", ctx, r, out, type, a1, a2));
-    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
-        set_error("roc subset: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
-        return VIDC_ERR_INVALID;
-    }
+    if (!roc_precision_ok("roc subset: ", precision_mode)) return VIDC_ERR_INVALID;
     if (r->rows) { set_error("roc subset: graph objects hold no lists to take a subset of"); return VIDC_ERR_UNSUPPORTED; }
     VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
     VIDC_HIP(hipSetDevice(ctx->device));
     HostTrace tr("roc subset");
     const uint64_t nlist = r->nlist, ntotal_old = r->ntotal;
-    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0, by_id = subset_by_id(type);
-    for (int w = 0; w < 2; w++) ctx->chain_info[w][0] = ctx->chain_info[w][1] = ctx->chain_info[w][2] = ctx->chain_info[w][3] = 0;
+    const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
+    clear_chain_info(ctx);
     double kernel_ms = 0;
-    RemoveMarked mk;
+    std::unique_ptr<vidc_roc> small, nr = roc_derived(ctx, nlist);  // (the host offsets are filled in by either path)
     AppChunks ch_s, ch_t;
-    Scratch s_mark, s_off, s_cand, s_t0, s_t1, s_stage, s_seg, s_rm, s_tf, s_tp, s_tl, s_lf, s_lt, s_small_ids, s_lo, s_dst;
-    Pinned h_back, h_seg, h_dst;
+    RocCandPass cp;  // (the positional types leave ts_off, lflag / ltpos and s_small_ids in it as the pass does)
+    Scratch s_lo, s_dst, s_off, s_cand, s_t0, s_stage, s_seg;
+    Pinned h_seg, h_dst;
     RocSpliceScratch sp_scratch;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
     EventTimer tm = EventTimer::started(ctx);
-    VIDC_TRY(h_back.get(ctx, 32 + (nlist + 1) * 8));
-    uint64_t *h_cnt = h_back.as<uint64_t>();
-    uint32_t *h_a = (uint32_t *)(h_cnt + 4), *h_b = h_a + nlist + 1;
-    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
-    VIDC_TRY(s_lf.get(ctx, (nlist + 1) * 4));
-    VIDC_TRY(s_lt.get(ctx, (nlist + 1) * 8));
-    uint32_t *lflag = s_lf.as<uint32_t>();
-    uint64_t *ltpos = s_lt.as<uint64_t>();
-    VIDC_HIP(hipMemsetAsync(lflag, 0, (nlist + 1) * 4, ctx->stream));
-    // the new object's host offsets are filled in by either path
-    std::unique_ptr<vidc_roc> nr(new vidc_roc());
-    nr->device = ctx->device;
-    nr->nlist = nlist;
-    nr->offsets = vec_pool<uint64_t>().take(nlist + 1);
-    nr->offsets.resize(nlist + 1);
-    uint64_t nonempty = 0, nsmall = 0, small_total = 0;
-    std::vector<uint64_t> ts_off(1, 0);  // the small object's offsets
-    if (by_id) {
-        // the candidates: every non-empty list
-        VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
-        VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
-        VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
-        uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
-        uint64_t *stage_off = s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
-        uint32_t *d_cand = s_cand.as<uint32_t>();
-        if (nlist && ntotal_old) {
-            hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p,
-                               (const uint64_t *)nullptr, nlist, mark, flag);
-            Scan4 sc{};
-            sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
-            VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
-            hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
-            VIDC_HIP(hipGetLastError());
-            VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        kernel_ms += tm.stop();
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        const uint64_t cnt = h_cnt[0];
-        std::vector<uint32_t> cand(cnt);
-        VIDC_TRY(h_seg.get(ctx, (cnt + 1) * 8));
-        uint64_t *seg_off = h_seg.as<uint64_t>();
-        seg_off[0] = 0;
-        if (cnt) {
-            VIDC_HIP(hipMemcpyAsync(h_a, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-            for (uint64_t k = 0; k < cnt; k++) {
-                cand[k] = h_a[k];
-                seg_off[k + 1] = seg_off[k] + (r->offsets[cand[k] + 1] - r->offsets[cand[k]]);
-            }
-        }
-        const uint64_t total = seg_off[cnt];
-        tr.mark("candidates read back");
-        uint64_t T = 0, killed = 0;
-        std::vector<uint32_t> t_list;  // list numbers of the touched lists, ascending
-        if (cnt) {
-            VIDC_TRY(s_stage.get(ctx, total * 8));
-            VIDC_TRY(s_rm.get(ctx, total));
-            VIDC_TRY(s_seg.get(ctx, (cnt + 1) * 8));
-            VIDC_HIP(hipMemcpyAsync(s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-            {
-                PooledDecPlan p;
-                plan_decode(r, cand, false, p, ctx->wide);
-                std::vector<uint64_t> out_off(cnt);
-                for (size_t k = 0; k < cnt; k++) out_off[k] = seg_off[p.item[k]];  // work item k -> its place in the staging
-                VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
-                kernel_ms += ctx->last_kernel_ms;
-            }
-            tr.mark("candidates decoded");
-            (void)tm.start();
-            VIDC_TRY(subset_mark(ctx, type, a1, a2, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), d_cand, cnt, total, s_rm.as<uint8_t>(), d_taken,
-                                 (const uint64_t *)r->d_offsets.p, mk));
-            VIDC_TRY(s_tf.get(ctx, 2 * (cnt + 1) * 4));  // tflag | tmark
-            VIDC_TRY(s_tp.get(ctx, 2 * (cnt + 1) * 8));  // tpos | tdst
-            VIDC_TRY(s_tl.get(ctx, 2 * (cnt + 1) * 4));  // t_cand | t_left
-            uint32_t *tflag = s_tf.as<uint32_t>(), *tmark = tflag + cnt + 1;
-            uint64_t *tpos = s_tp.as<uint64_t>(), *tdst = tpos + cnt + 1;
-            uint32_t *t_cand = s_tl.as<uint32_t>(), *t_left = t_cand + cnt + 1;
-            hipLaunchKernelGGL(k_rm_roc_kills, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint64_t *)s_seg.as<uint64_t>(),
-                               (const uint64_t *)mk.new_off, cnt, tflag, tmark);
-            Scan4 sc{};
-            sc.in[0] = tflag; sc.in[1] = tmark; sc.out[0] = tpos; sc.out[1] = tdst;
-            VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)cnt, s_t1));
-            hipLaunchKernelGGL(k_rm_roc_touched, req_grid(ctx, cnt), dim3(256), 0, ctx->stream, (const uint32_t *)tflag, (const uint32_t *)tmark,
-                               (const uint64_t *)tpos, (const uint32_t *)d_cand, cnt, t_cand, t_left, lflag, ltpos);
-            VIDC_HIP(hipGetLastError());
-            VIDC_HIP(hipMemcpyAsync(h_cnt + 1, tpos + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-            VIDC_HIP(hipMemcpyAsync(h_cnt + 2, mk.new_off + cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-            kernel_ms += tm.stop();
-            VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-            T = h_cnt[1];
-            killed = total - h_cnt[2];
-            if (T) {
-                VIDC_HIP(hipMemcpyAsync(h_a, t_cand, T * 4, hipMemcpyDeviceToHost, ctx->stream));
-                VIDC_HIP(hipMemcpyAsync(h_b, t_left, T * 4, hipMemcpyDeviceToHost, ctx->stream));
-                VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-                ts_off.resize(T + 1);
-                t_list.resize(T);
-                for (uint64_t t = 0; t < T; t++) {
-                    t_list[t] = cand[h_a[t]];
-                    ts_off[t + 1] = ts_off[t] + h_b[t];
-                }
-                small_total = ts_off[T];
-                VIDC_TRY(s_small_ids.get(ctx, (small_total ? small_total : 1) * 8));
-                (void)tm.start();
-                VIDC_TRY(remove_compact(ctx, mk, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), s_rm.as<uint8_t>(), tdst, tflag, s_small_ids.as<uint64_t>()));
-                kernel_ms += tm.stop();
-            }
-        }
-        tr.mark("candidates marked, touched lists read back");
-        nsmall = T;
-        nr->ntotal = ntotal_old - killed;
-        uint64_t gone = 0, t = 0;
-        for (uint64_t l = 0; l < nlist; l++) {
-            nr->offsets[l] = r->offsets[l] - gone;
-            if (t < T && t_list[t] == l) { gone += (r->offsets[l + 1] - r->offsets[l]) - (ts_off[t + 1] - ts_off[t]); t++; }
-            nonempty += r->offsets[l + 1] - gone != nr->offsets[l];
-        }
-        nr->offsets[nlist] = r->offsets[nlist] - gone;
+    uint64_t nsmall = 0;
+    std::vector<uint64_t> &ts_off = cp.ts_off;
+    if (subset_by_id(type)) {
+        VIDC_TRY(roc_candidate_pass(ctx, r, ntotal_old != 0, nullptr,
+                                    [&](auto *d_stage, auto *d_seg, auto *d_cand, uint64_t cnt, uint64_t total, uint8_t *d_rm, RemoveMarked &mk) {
+                                        return subset_mark(ctx, type, a1, a2, d_stage, d_seg, d_cand, cnt, total, d_rm, d_taken,
+                                                           (const uint64_t *)r->d_offsets.p, mk);
+                                    },
+                                    nr.get(), cp, tr, tm, kernel_ms));
+        nsmall = cp.T;
     } else {
+        Scratch &s_small_ids = cp.s_small_ids;
+        VIDC_TRY(roc_small_slots_clear(ctx, nlist, cp));
+        uint32_t *lflag = cp.s_lf.as<uint32_t>();
+        uint64_t *ltpos = cp.s_lt.as<uint64_t>();
         // the host's half: the same bounds on the mirror of the offsets
         std::vector<uint32_t> part;  // the partial lists, ascending
         std::vector<uint64_t> seg(1, 0);
@@ -2951,12 +2790,10 @@ static int roc_subset(vidc_ctx *ctx, const vidc_roc *r, int type, uint64_t a1, u
                 ts_off.push_back(ts_off.back() + (i2 - i1));
             }
             any_empty |= c == SUBC_EMPTY;
-            nonempty += i2 != i1;
             nr->offsets[l + 1] = nr->offsets[l] + (i2 - i1);
         }
         nr->ntotal = nr->offsets[nlist];
-        const uint64_t np = part.size(), total = seg[np];
-        small_total = ts_off[np];
+        const uint64_t np = part.size(), total = seg[np], small_total = ts_off[np];
         if (any_empty) ts_off.push_back(small_total);  // the trailing empty list
         nsmall = ts_off.size() - 1;
         if (nlist && ntotal_old) {
@@ -2993,14 +2830,7 @@ static int roc_subset(vidc_ctx *ctx, const vidc_roc *r, int type, uint64_t a1, u
                 std::memcpy(h_dst.p, ts_off.data(), (np + 1) * 8);
                 VIDC_HIP(hipMemcpyAsync(s_seg.p, h_seg.p, (np + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
                 VIDC_HIP(hipMemcpyAsync(s_dst.p, h_dst.p, (np + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-                {
-                    PooledDecPlan p;
-                    plan_decode(r, part, false, p, ctx->wide);
-                    std::vector<uint64_t> out_off(np);
-                    for (size_t k = 0; k < np; k++) out_off[k] = seg[p.item[k]];  // work item k -> its place in the staging
-                    VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
-                    kernel_ms += ctx->last_kernel_ms;
-                }
+                VIDC_TRY(decode_into_staging(ctx, r, part, [&](uint32_t i) { return seg[i]; }, s_stage.as<uint64_t>(), kernel_ms));
                 tr.mark("partial lists decoded");
                 VIDC_TRY(s_small_ids.get(ctx, (small_total ? small_total : 1) * 8));
                 (void)tm.start();
@@ -3018,16 +2848,16 @@ static int roc_subset(vidc_ctx *ctx, const vidc_roc *r, int type, uint64_t a1, u
         if (nsmall && !s_small_ids.p) VIDC_TRY(s_small_ids.get(ctx, 8));
         tr.mark("bounds, partial lists sliced");
     }
-    std::unique_ptr<vidc_roc> small;
     if (nsmall) {
         vidc_roc *sp = nullptr;
-        VIDC_TRY(encode_impl(ctx, nsmall, ts_off.data(), s_small_ids.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
+        VIDC_TRY(encode_impl(ctx, nsmall, ts_off.data(), cp.s_small_ids.as<uint64_t>(), false, 0, 0, nullptr, precision_mode,
                              want_perm ? VIDC_ROC_WANT_PERM : 0u, &sp));
         small.reset(sp);
         kernel_ms += ctx->last_kernel_ms;
     }
     tr.mark("re-encoded lists encoded");
-    VIDC_TRY(roc_splice_small(ctx, r, nr.get(), nonempty, lflag, ltpos, small.get(), want_perm, h_cnt + 3, sp_scratch, tm, kernel_ms));
+    (void)tm.start();
+    VIDC_TRY(roc_splice(ctx, r, small.get(), cp.look(), nr.get(), want_perm, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
     guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
@@ -3086,10 +2916,9 @@ int vidc_roc_subset_dev(vidc_ctx *ctx, const vidc_roc *r, int subset_type, uint6
     return vidc::roc_subset(ctx, r, subset_type, a1, a2, precision_mode, flags, out, d_taken, n_taken);
 }
 
-// Locate (include/vidc.h).  The batch is sorted as a remove sorts it and the same candidates -- the non-empty lists a valid pair names,
-// or every non-empty list in any-list mode -- are compacted on the device; their numbers come back once (4 bytes per candidate,
-// metadata), the host sizes a staging CSR, the candidates are decoded into it (plan_decode / decode_impl on the subset) in ascending
-// list order and marked (locate.h).  The offsets are positions in sampling order, the order decode_lists and translate_labels use.
+// Locate (include/vidc.h).  The batch is sorted as a remove sorts it and the same candidates are decoded (roc_decode_candidates), in
+// ascending list order, and marked (locate.h).  The offsets are positions in sampling order, the order decode_lists and
+// translate_labels use.
 int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int64_t *d_list_nos, const uint64_t *d_ids, int64_t *d_labels,
                         uint64_t *d_missing, uint64_t *d_invalid) {
     VIDC_TRY(locate_check(ctx, r, n, d_ids, d_labels));
@@ -3098,69 +2927,16 @@ int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int6
     VIDC_TRY(r->prec.size() == r->nlist ? ensure_offsets(r) : ensure_meta(r));
     VIDC_HIP(hipSetDevice(ctx->device));
     HostTrace tr("roc locate");
-    const uint64_t nlist = r->nlist;
     double kernel_ms = 0;
     LocateBatch b;
     AppChunks ch;
-    Scratch s_mark, s_off, s_cand, s_t0, s_stage, s_seg;
-    Pinned h_back, h_seg;
+    RocCandPass cp;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
     EventTimer tm = EventTimer::started(ctx);
-    VIDC_TRY(locate_sort_batch(ctx, nlist, n, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
-    // the candidates
-    VIDC_TRY(s_mark.get(ctx, 2 * (nlist + 1) * 4));  // mark | flag
-    VIDC_TRY(s_off.get(ctx, 2 * (nlist + 1) * 8));   // stage_off | cpos
-    VIDC_TRY(s_cand.get(ctx, (nlist + 1) * 4));
-    uint32_t *mark = s_mark.as<uint32_t>(), *flag = mark + nlist + 1;
-    uint64_t *stage_off = s_off.as<uint64_t>(), *cpos = stage_off + nlist + 1;
-    uint32_t *d_cand = s_cand.as<uint32_t>();
-    VIDC_TRY(h_back.get(ctx, 8 + (nlist + 1) * 4));
-    uint64_t *h_cnt = h_back.as<uint64_t>();
-    uint32_t *h_cand = (uint32_t *)(h_cnt + 1);
-    *h_cnt = 0;
-    if (nlist) {
-        hipLaunchKernelGGL(k_rm_roc_cand, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, (const uint64_t *)r->d_offsets.p,
-                           b.batch.any ? (const uint64_t *)nullptr : b.batch.run_off, nlist, mark, flag);
-        Scan4 sc{};
-        sc.in[0] = mark; sc.in[1] = flag; sc.out[0] = stage_off; sc.out[1] = cpos;
-        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)nlist, s_t0));
-        hipLaunchKernelGGL(k_req_roc_touched, req_grid(ctx, nlist), dim3(256), 0, ctx->stream, flag, cpos, nlist, d_cand);
-        VIDC_HIP(hipGetLastError());
-        VIDC_HIP(hipMemcpyAsync(h_cnt, cpos + nlist, 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    kernel_ms += tm.stop();
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    const uint64_t cnt = *h_cnt;
-    std::vector<uint32_t> cand(cnt);
-    VIDC_TRY(h_seg.get(ctx, (cnt + 1) * 8));
-    uint64_t *seg_off = h_seg.as<uint64_t>();
-    seg_off[0] = 0;
-    if (cnt) {
-        VIDC_HIP(hipMemcpyAsync(h_cand, d_cand, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-        for (uint64_t k = 0; k < cnt; k++) {
-            cand[k] = h_cand[k];
-            seg_off[k + 1] = seg_off[k] + (r->offsets[cand[k] + 1] - r->offsets[cand[k]]);
-        }
-    }
-    const uint64_t total = seg_off[cnt];
-    tr.mark("batch sorted, candidates read back");
-    if (cnt) {
-        VIDC_TRY(s_stage.get(ctx, total * 8));
-        VIDC_TRY(s_seg.get(ctx, (cnt + 1) * 8));
-        VIDC_HIP(hipMemcpyAsync(s_seg.p, seg_off, (cnt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        {
-            PooledDecPlan p;
-            plan_decode(r, cand, false, p, ctx->wide);
-            std::vector<uint64_t> out_off(cnt);
-            for (size_t k = 0; k < cnt; k++) out_off[k] = seg_off[p.item[k]];  // work item k -> its place in the staging
-            VIDC_TRY(decode_impl(ctx, r, p, out_off.data(), s_stage.as<uint64_t>(), nullptr, 0));
-            kernel_ms += ctx->last_kernel_ms;
-        }
-        tr.mark("candidates decoded");
-    }
+    VIDC_TRY(locate_sort_batch(ctx, r->nlist, n, d_list_nos, d_ids, 32u, d_missing, d_invalid, b));
+    VIDC_TRY(roc_decode_candidates(ctx, r, true, b.batch.any ? (const uint64_t *)nullptr : b.batch.run_off, cp, tr, tm, kernel_ms));
     (void)tm.start();
-    if (cnt) VIDC_TRY(locate_mark(ctx, b, s_stage.as<uint64_t>(), s_seg.as<uint64_t>(), d_cand, cnt, total, ch));
+    if (cp.cnt) VIDC_TRY(locate_mark(ctx, b, cp.s_stage.as<uint64_t>(), cp.s_seg.as<uint64_t>(), cp.s_cand.as<uint32_t>(), cp.cnt, cp.total, ch));
     VIDC_TRY(locate_labels(ctx, b, d_labels, d_missing));
     ctx->last_kernel_ms = kernel_ms + tm.stop();
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
@@ -3169,10 +2945,8 @@ int vidc_roc_locate_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t n, const int6
     return VIDC_OK;
 }
 
-// Regroup (include/vidc.h): the splice of the append and the remove as a call of its own, over up to VIDC_SHARDS_MAX sources instead
-// of two.  The (source, list) table is checked on the host and uploaded (12 bytes per list); one kernel gathers the per-list metadata
-// and the sizes, one scan launch set turns sizes and word counts into the two offset arrays, the word total comes back (8 bytes), and
-// a wavefront per 1024-word chunk copies the streams.  No ANS step runs; like an imported object the result carries no planner hints.
+// Regroup (include/vidc.h): the splice as a call of its own, over up to VIDC_SHARDS_MAX sources.  The (source, list) table is checked
+// on the host and uploaded (12 bytes per list; RocRegroupTable).  No ANS step runs.
 int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint64_t m, const uint32_t *src_no, const uint64_t *list_no,
                      uint32_t flags, vidc_roc **out) {
     if (out) *out = nullptr;
@@ -3216,88 +2990,36 @@ int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint6
     VIDC_HIP(hipSetDevice(ctx->device));
     HostTrace tr("roc regroup");
     const bool want_perm = (flags & VIDC_ROC_WANT_PERM) != 0;
-    std::unique_ptr<vidc_roc> nr(new vidc_roc());
-    nr->device = ctx->device;
-    nr->nlist = m;
-    nr->offsets = vec_pool<uint64_t>().take(m + 1);
-    nr->offsets.assign(m + 1, 0);
-    uint64_t nonempty = 0;
+    std::unique_ptr<vidc_roc> nr = roc_derived(ctx, m);
+    nr->offsets[0] = 0;
     for (uint64_t j = 0; j < m; j++) {
         const std::vector<uint64_t> &so = srcs[src_no[j]]->offsets;
-        const uint64_t n = so[list_no[j] + 1] - so[list_no[j]];
-        nr->offsets[j + 1] = nr->offsets[j] + n;
-        nonempty += n != 0;
+        nr->offsets[j + 1] = nr->offsets[j] + (so[list_no[j] + 1] - so[list_no[j]]);
     }
     nr->ntotal = nr->offsets[m];
-    nr->offsets_host = true;
-    Scratch s_tab, s_sizes, s_slot, s_t0;
+    Scratch s_tab;
     Pinned h_tab;
-    AppChunks ch_w, ch_p;
+    RocSpliceScratch sp_scratch;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
-    VIDC_TRY(h_tab.get(ctx, 16 + m * 12));
-    VIDC_TRY(s_tab.get(ctx, 16 + m * 12));
-    VIDC_TRY(s_sizes.get(ctx, (m + 1) * 4));
-    uint64_t *h_cnt = h_tab.as<uint64_t>();  // word total | list_no[m] | src_no[m]
-    h_cnt[0] = 0;
-    const uint64_t *d_list_no = s_tab.as<uint64_t>() + 2;
+    VIDC_TRY(h_tab.get(ctx, m * 12 + 8));
+    VIDC_TRY(s_tab.get(ctx, m * 12 + 8));
+    uint64_t *h_list_no = h_tab.as<uint64_t>();  // list_no[m] | src_no[m]
+    const uint64_t *d_list_no = s_tab.as<uint64_t>();
     const uint32_t *d_src_no = (const uint32_t *)(d_list_no + m);
     if (m) {
-        std::memcpy(h_cnt + 2, list_no, m * 8);
-        std::memcpy(h_cnt + 2 + m, src_no, m * 4);
-        VIDC_HIP(hipMemcpyAsync(s_tab.as<uint64_t>() + 2, h_cnt + 2, m * 12, hipMemcpyHostToDevice, ctx->stream));
+        std::memcpy(h_list_no, list_no, m * 8);
+        std::memcpy(h_list_no + m, src_no, m * 4);
+        VIDC_HIP(hipMemcpyAsync(s_tab.p, h_list_no, m * 12, hipMemcpyHostToDevice, ctx->stream));
     }
-    VIDC_TRY(nr->d_offsets.alloc(m + 1, ctx->dpool));
-    VIDC_TRY(nr->d_heads.alloc(m, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(m, ctx->dpool));
-    VIDC_TRY(nr->d_nwords.alloc(m, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(m, ctx->dpool));
-    VIDC_TRY(nr->d_word_off.alloc(m + 1, ctx->dpool));
-    RocSrcs S{};
+    RocSrcs<VIDC_SHARDS_MAX> S{};
     for (int k = 0; k < nsrc; k++)
-        if (used[k]) {
-            const vidc_roc *r = srcs[k];
-            S.s[k] = RocSrc{{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p}, r->d_words.p, r->d_word_off.p, r->d_offsets.p};
-        }
+        if (used[k]) S.s[k] = roc_src(srcs[k]);
+    double kernel_ms = 0;
     EventTimer tm = EventTimer::started(ctx);
-    if (m) {
-        hipLaunchKernelGGL(k_roc_regroup_meta<RocRegroupTable>, req_grid(ctx, m), dim3(256), 0, ctx->stream, S, RocRegroupTable{d_src_no, d_list_no}, m,
-                           nr->d_heads.p, nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>(), (unsigned long long *)nullptr);
-        VIDC_HIP(hipGetLastError());
-        Scan4 sc{};
-        sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
-        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)m, s_t0));
-        VIDC_HIP(hipMemcpyAsync(h_cnt, nr->d_word_off.p + m, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
-        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
-    }
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    nr->total_words = h_cnt[0];
-    nr->compressed_bytes = 8ull * nonempty + 4ull * nr->total_words;
-    tr.mark("metadata gathered, word total read back");
-    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
     VidcPhaseTimer copy_timer(ctx);  // (the word copy alone: VIDC_PHASE_ROC_REGROUP_COPY)
-    if (nr->total_words) {
-        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, m, nr->total_words, ch_w));
-        copy_timer.begin();
-        hipLaunchKernelGGL(k_roc_regroup_copy<RocRegroupTable>, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S,
-                           RocRegroupTable{d_src_no, d_list_no}, (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
-        copy_timer.end();
-        VIDC_HIP(hipGetLastError());
-    }
-    if (want_perm) {
-        // the convention of the append and the remove: a permutation of a derived object is over the positions of what the old
-        // lists decode to -- the identity (k_app_roc_perm with every list's slot 0)
-        VIDC_TRY(nr->d_perm.alloc(nr->ntotal ? nr->ntotal : 1, ctx->dpool));
-        if (nr->ntotal) {
-            VIDC_TRY(s_slot.get(ctx, m * 4));
-            VIDC_HIP(hipMemsetAsync(s_slot.p, 0, m * 4, ctx->stream));
-            VIDC_TRY(app_chunks(ctx, nr->d_offsets.p, m, nr->ntotal, ch_p));
-            hipLaunchKernelGGL(k_app_roc_perm, app_chunk_grid(ctx, ch_p.bound), dim3(256), 0, ctx->stream, (const uint64_t *)nr->d_offsets.p,
-                               (const uint32_t *)s_slot.as<uint32_t>(), (const uint32_t *)nullptr, (const uint64_t *)nullptr, ch_p.items,
-                               ch_p.n_items, nr->d_perm.p);
-            VIDC_HIP(hipGetLastError());
-        }
-    }
-    const double kernel_ms = tm.stop();
+    // the convention of the append and the remove: a permutation of a derived object is over the positions of what the old lists
+    // decode to -- the identity
+    VIDC_TRY(roc_splice(ctx, S, RocRegroupTable{d_src_no, d_list_no}, nr.get(), want_perm, 0u, nullptr, &copy_timer, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
     guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
@@ -3307,19 +3029,15 @@ int vidc_roc_regroup(vidc_ctx *ctx, int nsrc, const vidc_roc *const *srcs, uint6
     return VIDC_OK;
 }
 
-// Update rows (include/vidc.h): the regroup's splice over {old object, the encoded batch rows}, with the slot table of rows_update.h on
-// the device where the regroup has its host table.  The m batch rows are encoded by the rows path into a temporary object (every one
-// of them, so every one is checked); one kernel gathers the per-row metadata, one scan launch set gives the offsets and the word
-// offsets, the totals come back (24 bytes: words, edges, non-empty rows), the chunked copy moves the streams.  A row's stream depends on
-// its multiset and precision alone: an untouched row keeps its words.  Like an imported object the result carries no planner hints.
+// Update rows (include/vidc.h): the splice over {old object, the encoded batch rows}, with the slot table of rows_update.h built on the
+// device (RocUpdateSlots).  The m batch rows are encoded by the rows path into a temporary object (every one of them, so every one is
+// checked).  The object has no host mirror of its offsets: the edge total comes back with the splice's totals.  A row's stream depends
+// on its multiset and precision alone: an untouched row keeps its words.
 int vidc_roc_update_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const int64_t *d_nodes, const int32_t *d_rows, uint64_t N_new,
                              int precision_mode, vidc_roc **out, uint64_t *d_invalid) {
     if (out) *out = nullptr;
     VIDC_TRY(rows_upd_check("roc", ctx, r, out, m, d_nodes, d_rows, r ? r->nlist : 0, N_new));
-    if (precision_mode < VIDC_PREC_EXACT || precision_mode > 32) {
-        set_error("roc update_rows: precision_mode %d unsupported (fixed precision must be 0..32)", precision_mode);
-        return VIDC_ERR_INVALID;
-    }
+    if (!roc_precision_ok("roc update_rows: ", precision_mode)) return VIDC_ERR_INVALID;
     if (!r->rows) {
         if (r->K > TINY_MAX) set_error("roc update_rows: wide rows (K = %u > 64) are CSR objects: not supported", r->K);
         else set_error("roc update_rows: not a graph object (build it with vidc_roc_encode_rows)");
@@ -3337,58 +3055,18 @@ int vidc_roc_update_rows_dev(vidc_ctx *ctx, const vidc_roc *r, uint64_t m, const
         kernel_ms += ctx->last_kernel_ms;
     }
     tr.mark("batch rows encoded");
-    std::unique_ptr<vidc_roc> nr(new vidc_roc());
-    nr->device = ctx->device;
+    std::unique_ptr<vidc_roc> nr = roc_derived(ctx, N_new, /*host_offsets=*/false);
     nr->rows = true;
     nr->K = r->K;
-    nr->nlist = N_new;
-    Scratch s_slot, s_sizes, s_cnt, s_t0;
-    Pinned h_tot;
-    AppChunks ch_w;
+    Scratch s_slot;
+    RocSpliceScratch sp_scratch;
     StreamGuard guard(ctx);  // (an early return waits for what is in flight before the blocks above go back)
-    VIDC_TRY(h_tot.get(ctx, 24));
-    VIDC_TRY(s_cnt.get(ctx, 8));
-    VIDC_TRY(s_sizes.get(ctx, (N_new + 1) * 4));
-    uint64_t *h_cnt = h_tot.as<uint64_t>();  // word total | edges | non-empty rows
-    h_cnt[0] = h_cnt[1] = h_cnt[2] = 0;
-    VIDC_TRY(nr->d_offsets.alloc(N_new + 1, ctx->dpool));
-    VIDC_TRY(nr->d_heads.alloc(N_new, ctx->dpool)); VIDC_TRY(nr->d_prec.alloc(N_new, ctx->dpool));
-    VIDC_TRY(nr->d_nwords.alloc(N_new, ctx->dpool)); VIDC_TRY(nr->d_draws.alloc(N_new, ctx->dpool));
-    VIDC_TRY(nr->d_word_off.alloc(N_new + 1, ctx->dpool));
-    RocSrcs S{};
-    S.s[0] = RocSrc{{r->d_heads.p, r->d_prec.p, r->d_nwords.p, r->d_draws.p}, r->d_words.p, r->d_word_off.p, r->d_offsets.p};
-    if (tmp) S.s[1] = RocSrc{{tmp->d_heads.p, tmp->d_prec.p, tmp->d_nwords.p, tmp->d_draws.p}, tmp->d_words.p, tmp->d_word_off.p, tmp->d_offsets.p};
+    RocSrcs<2> S{};
+    S.s[0] = roc_src(r);
+    if (tmp) S.s[1] = roc_src(tmp.get());
     EventTimer tm = EventTimer::started(ctx);
     VIDC_TRY(rows_upd_slots(ctx, m, d_nodes, N_new, s_slot, d_invalid));
-    const RocUpdateSlots look{s_slot.as<uint32_t>(), N_old};
-    if (N_new) {
-        VIDC_HIP(hipMemsetAsync(s_cnt.p, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_roc_regroup_meta<RocUpdateSlots>, req_grid(ctx, N_new), dim3(256), 0, ctx->stream, S, look, N_new, nr->d_heads.p,
-                           nr->d_prec.p, nr->d_nwords.p, nr->d_draws.p, s_sizes.as<uint32_t>(), s_cnt.as<unsigned long long>());
-        VIDC_HIP(hipGetLastError());
-        Scan4 sc{};
-        sc.in[0] = s_sizes.as<uint32_t>(); sc.in[1] = nr->d_nwords.p; sc.out[0] = nr->d_offsets.p; sc.out[1] = nr->d_word_off.p;
-        VIDC_TRY(device_exscan4(ctx, sc, 2, (uint32_t)N_new, s_t0));
-        VIDC_HIP(hipMemcpyAsync(h_cnt, nr->d_word_off.p + N_new, 8, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 1, nr->d_offsets.p + N_new, 8, hipMemcpyDeviceToHost, ctx->stream));
-        VIDC_HIP(hipMemcpyAsync(h_cnt + 2, s_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        VIDC_HIP(hipMemsetAsync(nr->d_offsets.p, 0, 8, ctx->stream));
-        VIDC_HIP(hipMemsetAsync(nr->d_word_off.p, 0, 8, ctx->stream));
-    }
-    VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));
-    nr->total_words = h_cnt[0];
-    nr->ntotal = h_cnt[1];
-    nr->compressed_bytes = 8ull * h_cnt[2] + 4ull * nr->total_words;
-    tr.mark("metadata gathered, totals read back");
-    VIDC_TRY(nr->d_words.alloc(nr->total_words + 16, ctx->dpool));  // + padding: see finish_complete
-    if (nr->total_words) {
-        VIDC_TRY(app_chunks(ctx, nr->d_word_off.p, N_new, nr->total_words, ch_w));
-        hipLaunchKernelGGL(k_roc_regroup_copy<RocUpdateSlots>, app_chunk_grid(ctx, ch_w.bound), dim3(256), 0, ctx->stream, S, look,
-                           (const uint64_t *)nr->d_word_off.p, nr->d_words.p, ch_w.items, ch_w.n_items);
-        VIDC_HIP(hipGetLastError());
-    }
-    kernel_ms += tm.stop();
+    VIDC_TRY(roc_splice(ctx, S, RocUpdateSlots{s_slot.as<uint32_t>(), N_old}, nr.get(), false, 0u, nullptr, nullptr, sp_scratch, tm, kernel_ms));
     VIDC_HIP(vidc::vidc_stream_wait(ctx->stream));  // (the scratch blocks go back to the context's cache)
     guard.disarm();
     ctx->last_kernel_ms = kernel_ms;
