@@ -703,6 +703,42 @@ int vidc_compact_search_dev(vidc_ctx *ctx, const vidc_compact *c, const float *d
 int vidc_ef_search_dev(vidc_ctx *ctx, const vidc_ef *e, const float *d_x, uint32_t d, uint64_t nq, const float *d_xq, uint32_t k,
                        uint32_t L, uint32_t entry, uint32_t max_rounds, float *d_D, int64_t *d_I, uint32_t *d_stats);
 
+/* ---------------------------------------------------- scan IVF lists (device-resident, deferred id decoding) */
+/* The scan of the IVF search with deferred id decoding (custom_invlists_impl.cpp:407-526) for a batch of queries on the device: every
+ * probed list of a query is scanned and the k best (distance, list_no << 32 | offset) labels stay.  D and the labels are device
+ * arrays: vidc_*_translate_labels_dev turns the labels into ids without a host trip.
+ *
+ * Semantics (per query, independently; tests/ivf_scan_ref.py is the statement).  The candidates are all entries of the DISTINCT VALID
+ *   lists the query's probe row names: a probe that is negative or >= nlist is skipped (Faiss writes -1 for "no list"), a list named
+ *   twice in a row is scanned once.  The distance is squared L2 in float32: VIDC_IVF_FLAT, query minus stored vector; VIDC_IVF_PQ8, the
+ *   sum over the M sub-quantisers of || xq_m - codebook[m][code_m] ||^2 (asymmetric distance from a per-query table; the value of
+ *   decoding the code and taking L2).  The result is the first k candidates in ascending (distance, label) order, label =
+ *   list_no << 32 | offset, padded with +inf / -1.  Ties are decided by the label, so the result does not depend on how the work was cut.
+ * Arrays.  All device arrays on the context's device.  d_offsets: uint64 [nlist + 1]; d_codes: uint8 [ntotal, code_size] in the
+ *   container's order (code_size = 4 * d, or M); d_codebooks (PQ8): float32 [M, 256, d / M]; d_xq: float32 [nq, d]; d_probes: int64
+ *   [nq, nprobe]; d_D float32 / d_labels int64: [nq, k] -- every element is written and nothing outside them.  d_stats (may be NULL):
+ *   uint32 [nq, 2] = {lists scanned, codes scanned}.  The inputs are not changed.
+ * Bounds.  A list's range is clamped to a <= b <= ntotal before it indexes d_codes, and a PQ code byte indexes a 256-entry table:
+ *   damaged offsets give a wrong result, never a read outside the call's arrays.
+ * Status.  VIDC_ERR_INVALID before any device work, nothing written: NULL context; NULL arrays with nq > 0; k outside 1 .. 256; nprobe
+ *   outside 1 .. 1024; d outside 1 .. 2048; ntotal >= 2^32 (a key packs a position in 32 bits); nlist >= 2^31; an unknown code_kind;
+ *   PQ8 with M outside 1 .. 64, with d % M != 0, or with NULL codebooks.  nq == 0: VIDC_OK, nothing is launched.
+ * What runs.  A wavefront per (query, piece): small batches still fill the device because a probe row is cut into S of 1, 2, 4, 8, 16
+ *   contiguous pieces -- the smallest S with nq * S >= the resident wavefronts, S <= nprobe; the row is de-duplicated before the cut.
+ *   With S > 1 a second kernel merges the pieces' sorted runs, a wavefront per query.
+ * Scratch.  None with S == 1.  Otherwise nq * S * (k + 1) * 8 bytes from the context's block cache (the pieces' keys [nq, S, k] and
+ *   their counters): at most 16 * 257 * 8 bytes per query, and S > 1 only while nq is below the resident wavefronts (<= 8192).
+ * Residency.  Enqueued on the context's stream; the call waits for its kernels.  vidc_ctx_d2h_bytes does not move;
+ *   vidc_ctx_last_kernel_ms is the kernels' time.
+ * Not here.  Inner product, residual PQ, sub-quantisers of other than 8 bits, returning the codes (return_codes), the coarse
+ *   quantiser (the caller brings the probes), sharded and segmented containers.  The Faiss adapter does not call this: Faiss's own
+ *   scanner stays its path. */
+#define VIDC_IVF_FLAT 0 /* code = d float32, code_size = 4 * d */
+#define VIDC_IVF_PQ8 1  /* code = M bytes, codebooks float32 [M, 256, d / M] */
+int vidc_ivf_scan_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes, int code_kind,
+                      uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, uint32_t nprobe,
+                      const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

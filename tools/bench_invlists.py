@@ -5,7 +5,10 @@ Same flow and CSV columns (bench_invlists.py:120-137): build the index, construc
 lists, time `search_defer_id_decoding` for nprobe in {1, 4, 16}, k = 20.  Datasets are synthetic (sift1M / deep1M
 are not available offline): index 0 = small smoke set, 1 = 1M x 128 ("sift1M shape"), 2 = 1M x 96 ("deep1M shape").
 
-    python tools/bench_invlists.py 1 IVF1024,PQ16 [num_runs] [nq]
+    python tools/bench_invlists.py 1 IVF1024,PQ16 [num_runs] [nq] [--device-scan]
+
+--device-scan times IVFIndex.search_device (vidc_ivf_scan_dev + translate_labels, everything on the device) in place of the per-query
+torch loop of search_defer_id_decoding; off by default.  The distances are then compared bit for bit between the containers.
 """
 import sys
 import time
@@ -44,7 +47,7 @@ def same_up_to_ties(D, I, Dr, Ir, k, what):
         print(f"   note: {len(set(qs))} queries have tied distances resolved in a different order", flush=True)
 
 
-def run(dataset_idx, index_str, num_runs, nq):
+def run(dataset_idx, index_str, num_runs, nq, device_scan=False):
     data = ClusteredVectors(nq=nq, **SHAPES[dataset_idx])
     index = parse_index(data.d, index_str)
     index.train(data.get_train())
@@ -55,6 +58,8 @@ def run(dataset_idx, index_str, num_runs, nq):
     containers = {None: index.invlists, **{m: AVAILABLE_COMPRESSED_IVFS[m](index.invlists) for m in methods}}
     print(f"built {len(methods)} compressed invlists in {time.time() - t0:.2f} s", flush=True)
     table = ResultTable("gpurun_out/results-online-ivf", "ivf-results-{now}-" + f"{index_str}-{dataset_idx}".replace(",", "_"))
+    if device_scan:
+        table.columns += ("device_scan",)
     queries = data.get_queries()
     reference = {}
     for method, il in containers.items():
@@ -64,19 +69,26 @@ def run(dataset_idx, index_str, num_runs, nq):
             index.nprobe = nprobe
             for run_id in range(num_runs):
                 t0 = time.time()
-                D, I = index.search_defer_id_decoding(queries, k=K, decode_1by1=method in SELECT_PER_RESULT)
+                if device_scan:
+                    D, I = (t.cpu().numpy() for t in index.search_device(queries, K))
+                else:
+                    D, I = index.search_defer_id_decoding(queries, k=K, decode_1by1=method in SELECT_PER_RESULT)
                 dt = time.time() - t0
                 if method is None:
                     reference[nprobe] = (D, I)
+                elif device_scan:  # (every container scans the same codes in its own order: the distances are the same bits)
+                    assert np.array_equal(D, reference[nprobe][0]), (method, nprobe)
                 else:
                     same_up_to_ties(D, I, *reference[nprobe], K, (method, nprobe))
                 row = table.add(dt_search=dt, nprobe=nprobe, run_id=run_id, index_str=index_str, k=K, nq=queries.shape[0],
                                 comp_method=method or "ref", dataset=f"Synthetic{dataset_idx}", ids_size=ids_size,
-                                overhead_size=overhead, nb=data.nb, nt=data.nt)
+                                overhead_size=overhead, nb=data.nb, nt=data.nt, device_scan=int(device_scan))
             print(row, flush=True)
     df = table.save()
     print(df.groupby(["comp_method", "nprobe"]).agg(dt=("dt_search", "median"), ids_size=("ids_size", "first")), flush=True)
 
 
 if __name__ == "__main__":
-    run(int(sys.argv[1]), str(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 3, int(sys.argv[4]) if len(sys.argv) > 4 else 200)
+    argv = [v for v in sys.argv[1:] if v != "--device-scan"]
+    run(int(argv[0]), str(argv[1]), int(argv[2]) if len(argv) > 2 else 3, int(argv[3]) if len(argv) > 3 else 200,
+        device_scan="--device-scan" in sys.argv)

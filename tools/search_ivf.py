@@ -34,6 +34,8 @@ if __name__ == "__main__":
     ap.add_argument("--id_decoding_1by1", default=False, action="store_true")
     ap.add_argument("--redo_search", default=1, type=int, help="number of times to redo the search (to stabilize timings)")
     ap.add_argument("--nprobe", default=[1, 4, 16, 64], nargs="+", type=int)
+    ap.add_argument("--device-scan", dest="device_scan", default=False, action="store_true",
+                    help="search with IVFIndex.search_device (the scan and the id decoding on the device) instead of the torch loop")
     args = ap.parse_args()
 
     g = torch.Generator(device="cuda")
@@ -60,7 +62,9 @@ if __name__ == "__main__":
         for _ in range(args.redo_search):
             torch.cuda.synchronize()
             t0 = time.time()
-            if args.defer_id_decoding:
+            if args.device_scan:
+                D, I = (t.cpu().numpy() for t in index.search_device(xq, args.k))
+            elif args.defer_id_decoding:
                 D, I = index.search_defer_id_decoding(xq, args.k, decode_1by1=args.id_decoding_1by1)
             else:
                 D, I = index.search(xq, args.k)

@@ -303,6 +303,76 @@ class IVFIndex:
             L[q, :kk] = labs[top.indices].cpu().numpy()
         return D, L
 
+    # -- the scan on the device (vidc_ivf_scan_dev): _scan above stays the baseline
+    def _device_offsets(self):
+        """(offsets as a uint64-valued int64 CUDA tensor, the ids of plain lists in list order or None): uploaded once and kept for as
+        long as the _device_lists view they belong to"""
+        torch = _torch()
+        off, codes = self._device_lists()
+        held = getattr(self, "_dev_off", None)
+        if held is None or held[0] is not self._dev:
+            ids = None
+            if getattr(self.invlists, "codes_all", None) is None:
+                ids = torch.from_numpy(to_csr(self.invlists)[1].view(np.int64).copy()).to(codes.device)
+            held = self._dev_off = (self._dev, torch.from_numpy(off.astype(np.int64)).to(codes.device), ids)
+        return held[1], held[2]
+
+    def scan_device(self, xq, k, probes=None):
+        """The scan of _scan as one library call (vidc_ivf_scan_dev): -> (D float32 [nq, k], labels int64 [nq, k] = list_no << 32 |
+        offset) as CUDA tensors, +inf / -1 padded, ascending in (distance, label).  probes: an int64 [nq, nprobe] CUDA tensor of list
+        numbers, used as it is (-1 = no list); None picks them on the device with the cdist + topk of _scan.  Works over the codes of
+        a compressed container and of ArrayInvertedLists, for "Flat" and ("PQ", M).  Runs on torch's current stream."""
+        from . import _lib
+
+        torch = _torch()
+        if not torch.cuda.is_available():
+            raise _lib.VidcError("no HIP device: scan_device needs an MI355X (there is no CPU fallback)")
+        if not (isinstance(xq, torch.Tensor) and xq.is_cuda):
+            xq = torch.from_numpy(np.array(xq, dtype=np.float32, order="C")).cuda()
+        xq = xq.to(torch.float32).contiguous()
+        if xq.dim() != 2 or xq.shape[1] != self.d:
+            raise ValueError(f"xq must be [nq, {self.d}]")
+        if probes is None:
+            probes = torch.cdist(xq, self.centroids).topk(min(self.nprobe, self.nlist), largest=False).indices
+        if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.int64 and probes.dim() == 2
+                and probes.shape[0] == xq.shape[0]):
+            raise ValueError("probes must be an int64 CUDA tensor [nq, nprobe]")
+        probes = probes.contiguous()
+        _, codes = self._device_lists()
+        off, _ = self._device_offsets()
+        nq, k = int(xq.shape[0]), int(k)
+        if not 0 <= k < 2 ** 32:
+            raise ValueError("k is an unsigned 32-bit number")
+        D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
+        labels = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+        ptr = _lib.ptr
+        pq = self.pq.to(torch.float32).contiguous() if self.M else None
+        ctx = _lib.default_context()
+        _lib.check(_lib.lib().vidc_ivf_scan_dev(
+            ctx.h, self.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None,
+            _lib.VIDC_IVF_PQ8 if self.M else _lib.VIDC_IVF_FLAT, self.d, self.M, ptr(pq) if self.M else None, nq, ptr(xq) if nq else None,
+            int(probes.shape[1]), ptr(probes) if probes.numel() else None, k, ptr(D) if D.numel() else None,
+            ptr(labels) if labels.numel() else None, None))
+        return D, labels
+
+    def search_device(self, xq, k):
+        """search_defer_id_decoding with nothing on the host: scan_device, then the labels -> ids on the device (translate_labels of
+        a compressed container; one gather of the ids of plain lists).  -> (D, I) CUDA tensors, I = -1 where D = +inf."""
+        torch = _torch()
+        D, labels = self.scan_device(xq, k)
+        il = self.invlists
+        if hasattr(il, "translate_labels"):
+            return D, il.translate_labels(labels)
+        off, ids = self._device_offsets()
+        if ids is None:
+            raise RuntimeError("search_device: the inverted lists cannot translate labels")
+        valid = labels >= 0
+        safe = torch.where(valid, labels, torch.zeros_like(labels))
+        rows = off[safe >> 32] + (safe & 0xFFFFFFFF)
+        if ids.numel() == 0:
+            return D, torch.full_like(labels, -1)
+        return D, torch.where(valid, ids[rows.clamp(max=ids.numel() - 1)], torch.full_like(labels, -1))
+
     # -- searches
     def search(self, xq, k):
         """Non-deferred path: every probed list is fully decoded (get_ids) like IndexIVF::search_preassigned."""
