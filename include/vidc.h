@@ -739,6 +739,52 @@ int vidc_ivf_scan_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, 
                       uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, uint32_t nprobe,
                       const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
 
+/* ---------------------------------------------------- range search over IVF lists (device-resident, deferred id decoding) */
+/* IndexIVF::range_search's scan for a batch of queries on the device: every entry of a query's probed lists whose distance is below
+ * a radius, as (distance, list_no << 32 | offset).  The result has a variable length, so there are two calls and the caller allocates
+ * between them: count -> the limits of every slot and the total; fill -> D and the labels.  vidc_*_translate_labels_dev turns the
+ * labels into ids: only what passed the radius is decoded.  A top-k scan at k = 256 is no substitute: it truncates.
+ *
+ * Semantics (tests/ivf_range_ref.py is the statement).  The arguments up to d_probes are vidc_ivf_scan_dev's, with its arrays.
+ *   Slot s = q * nprobe + j is entry j of query q's probe row.  Its candidates are the entries of the list it names, in ascending
+ *   offset order, if the entry is a valid list number and the FIRST mention of that list in the row (the probe rules of the scan: a
+ *   probe that is negative or >= nlist is skipped, a repeated list counts once); every other slot has no candidates.  A candidate is a
+ *   hit iff distance < radius, compared strictly in float32 as Faiss's L2 range search does; the distances are the scan's, bit for bit
+ *   (VIDC_IVF_FLAT and VIDC_IVF_PQ8).  A NaN, zero or negative radius gives no hit, +inf gives every candidate.
+ * Count.  d_slot_lims: device uint64 [nq * nprobe + 1], the exclusive prefix sum of the hits per slot in slot order, every element
+ *   written; d_slot_lims[nq * nprobe] is the total, copied to *total (HOST) unless total is NULL.  Query q's results are
+ *   [d_slot_lims[q * nprobe], d_slot_lims[(q + 1) * nprobe]): Faiss's lims is the strided view d_slot_lims[::nprobe].
+ * Fill.  The r-th hit of slot s goes to position d_slot_lims[s] + r of d_D (float32) / d_labels (int64), device arrays of `capacity`
+ *   entries, label = list_no << 32 | offset.  The order is probe-row order, then offset: it does not depend on how the work was cut,
+ *   and no atomic operation decides a position.  With the d_slot_lims of a count over the same arguments and capacity >= the total,
+ *   every position below the total is written.
+ * Bounds.  The fill writes position p of slot s only if p < d_slot_lims[s + 1] and p < capacity; list ranges are clamped as in the
+ *   scan.  A d_slot_lims that came from another radius, a capacity below the total or damaged offsets give a wrong or partial
+ *   result, never a write outside [0, capacity) of the two output arrays nor a read outside the call's arrays.  Positions of a slot
+ *   beyond the hits the fill finds are left untouched.
+ * Status.  VIDC_ERR_INVALID before any device work, nothing written: every refusal of vidc_ivf_scan_dev but k's (there is no k);
+ *   nq * nprobe >= 2^32 - 1; NULL d_slot_lims with nq > 0; NULL d_D or d_labels with capacity > 0.  nq == 0: VIDC_OK; the count writes
+ *   d_slot_lims[0] = 0 if the array is given and *total = 0 if total is given, the fill launches nothing.  capacity == 0: VIDC_OK,
+ *   nothing written.
+ * What runs.  One kernel per call, a wavefront per (query, piece) with the cut of the scan; the pieces of a query own disjoint slots,
+ *   so there is no merge.  Count: the hit ballots are summed per slot, then one device scan of the counts.  Fill: the distance pass
+ *   again (the function and the plan of the count, hence the same bits), every hit stored at its place.
+ * Scratch.  nq * nprobe uint32 hit counts from the context's block cache, and the tile sums of the device scan beyond 8192 slots.
+ *   Nothing grows with the number of results.
+ * Residency.  Enqueued on the context's stream; both calls wait for their kernels.  The count with total != NULL reads back exactly 8
+ *   bytes (vidc_ctx_d2h_bytes moves by 8), with total == NULL nothing; the fill never moves it.  vidc_ctx_last_kernel_ms is the
+ *   call's kernels' time.
+ * Not here.  Per-query radii; inner product, residual PQ, sub-quantisers of other than 8 bits; the coarse quantiser (the caller
+ *   brings the probes); sharded containers; a one-pass form that buffers hits; the Faiss adapter (Faiss's own scanner stays its
+ *   path). */
+int vidc_ivf_range_count_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes,
+                             int code_kind, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq,
+                             uint32_t nprobe, const int64_t *d_probes, float radius, uint64_t *d_slot_lims, uint64_t *total);
+int vidc_ivf_range_fill_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes,
+                            int code_kind, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq,
+                            uint32_t nprobe, const int64_t *d_probes, float radius, const uint64_t *d_slot_lims, uint64_t capacity,
+                            float *d_D, int64_t *d_labels);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

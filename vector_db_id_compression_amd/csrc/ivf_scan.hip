@@ -9,10 +9,9 @@
 //   * the query vector and the probe row sit in LDS.  The row is mapped to list numbers (-1: no list) and de-duplicated in place over
 //     the WHOLE row, 64 entries a pass: lane j compares its entry with every entry in front of it (uniform trip count); the piece
 //     [piece_begin(s), piece_begin(s + 1)) is cut afterwards.
-//   * a trip takes 64 codes of a list, whose range was clamped to a <= b <= ntotal.  FLAT: G lanes share one vector (16-byte loads
-//     when d % 4 == 0 and both bases are aligned: gs::group), partial sums meet in a G-lane butterfly; which lanes sum which
-//     components depends on (d, G) only.  PQ8: the wavefront builds the query's M x 256 table in LDS once per item; a lane takes one
-//     code, its M bytes with loads of W bytes, and adds M table reads in m order (a byte indexes 256 entries: always inside).
+//   * a trip takes 64 codes of a list, whose range was clamped to a <= b <= ntotal, and gives one distance per lane
+//     (csrc/ivf_dist.h, shared with ivf_range.hip: the FLAT G-lane butterfly, the PQ8 table walk).  PQ8: the wavefront builds the
+//     query's M x 256 table in LDS once per item.
 //   * a candidate whose key is not below the pool's last key is dropped by a ballot; the survivors are ranked among themselves by
 //     lane reads, against the pool by binary search, and every element is stored at its place in the other pool array.  No private
 //     arrays.
@@ -21,6 +20,7 @@
 // Every loop that holds a cross-lane operation has a wavefront-uniform trip count.  Nothing spins and no wavefront waits for another.
 #include "common.h"
 #include "host_call.h"
+#include "ivf_dist.h"
 #include "ivf_scan_plan.h"
 #include "ivf_scan_ref.h"
 #include "requests.h"
@@ -51,34 +51,6 @@ struct IvScan {
     uint32_t *stats;
 };
 
-// one PQ code -> its distance: M bytes, W at a load, the table entries added in m order
-template <int W>
-__device__ __forceinline__ float pq_distance(const uint8_t *code, const float *table, uint32_t M) {
-    float s = 0.f;
-    for (uint32_t m0 = 0; m0 < M; m0 += W) {
-        uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-        if (W == 16) {
-            const uint4 v = *(const uint4 *)(code + m0);
-            w0 = v.x; w1 = v.y; w2 = v.z; w3 = v.w;
-        } else if (W == 8) {
-            const uint2 v = *(const uint2 *)(code + m0);
-            w0 = v.x; w1 = v.y;
-        } else if (W == 4) {
-            w0 = *(const uint32_t *)(code + m0);
-        } else if (W == 2) {
-            w0 = *(const uint16_t *)(code + m0);
-        } else {
-            w0 = code[m0];
-        }
-#pragma unroll
-        for (int b = 0; b < W; b++) {
-            const uint32_t w = b < 4 ? w0 : (b < 8 ? w1 : (b < 12 ? w2 : w3));
-            s += table[(m0 + b) * 256u + ((w >> ((b & 3) * 8)) & 255u)];
-        }
-    }
-    return s;
-}
-
 // KIND FLAT: V components per load (4 or 1).  KIND PQ8: V is W, the bytes of a code load.
 template <int KIND, int V>
 __global__ void __launch_bounds__(64) k_ivf_scan(IvScan a) {
@@ -90,7 +62,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan(IvScan a) {
     float *behind = (float *)((uint8_t *)lds + a.head_bytes + a.row_bytes);
     float *qv = KIND == ivs::PQ8 ? (float *)lds : behind;
     const float *table = behind;  // (PQ8)
-    const uint32_t logG = a.logG, G = a.G, per = 64u >> logG, g = lane & (G - 1u);
+    const uint32_t logG = a.logG, G = a.G;
     const uint64_t items = a.nq * a.S;
 
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
@@ -130,37 +102,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan(IvScan a) {
             ncodes += rb - ra;
             for (uint64_t p0 = ra; p0 < rb; p0 += ivs::TRIP) {
                 const uint32_t n = rb - p0 < ivs::TRIP ? (uint32_t)(rb - p0) : ivs::TRIP;
-                float dist = 0.f;
-                if (KIND == ivs::PQ8) {
-                    if (lane < n) dist = pq_distance<V>(a.codes + (p0 + lane) * a.M, table, a.M);
-                } else {
-                    for (uint32_t c0 = 0; c0 < n; c0 += per) {
-                        const uint32_t idx = c0 + (lane >> logG);
-                        float sum = 0.f;
-                        if (idx < n) {
-                            const float *vec = (const float *)(a.codes + (p0 + idx) * ((uint64_t)d * 4u));
-                            if (V == 4) {
-                                for (uint32_t i = g * 4u; i < d; i += G * 4u) {
-                                    const float4 x = *(const float4 *)(vec + i), y = *(const float4 *)(qv + i);
-                                    const float t0 = y.x - x.x, t1 = y.y - x.y, t2 = y.z - x.z, t3 = y.w - x.w;
-                                    sum += t0 * t0;
-                                    sum += t1 * t1;
-                                    sum += t2 * t2;
-                                    sum += t3 * t3;
-                                }
-                            } else {
-                                for (uint32_t i = g; i < d; i += G) {
-                                    const float t = qv[i] - vec[i];
-                                    sum += t * t;
-                                }
-                            }
-                        }
-                        for (uint32_t o = G >> 1; o; o >>= 1) sum += __shfl_xor(sum, (int)o, 64);
-                        if (idx < n && g == 0) cdist[idx] = sum;
-                    }
-                    __syncthreads();
-                    if (lane < n) dist = cdist[lane];
-                }
+                const float dist = ivf_trip_distance<KIND, V>(a.codes, p0, n, lane, d, a.M, qv, table, cdist, G, logG);
                 const uint64_t key = lane < n ? ivs::key_make(dist, (uint32_t)(p0 + lane)) : ivs::EMPTY;
                 const bool keep = lane < n && !ivs::key_dropped(key, pool[k - 1u]);
                 const uint64_t keepm = __ballot(keep);
