@@ -732,7 +732,7 @@ int vidc_ef_search_dev(vidc_ctx *ctx, const vidc_ef *e, const float *d_x, uint32
  *   vidc_ctx_last_kernel_ms is the kernels' time.
  * Not here.  Inner product, residual PQ, sub-quantisers of other than 8 bits, returning the codes (return_codes), the coarse
  *   quantiser (the caller brings the probes), sharded and segmented containers.  The Faiss adapter does not call this: Faiss's own
- *   scanner stays its path. */
+ *   scanner stays its path.  (Residual PQ has entry points of its own: see the residual section behind the range search.) */
 #define VIDC_IVF_FLAT 0 /* code = d float32, code_size = 4 * d */
 #define VIDC_IVF_PQ8 1  /* code = M bytes, codebooks float32 [M, 256, d / M] */
 int vidc_ivf_scan_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes, int code_kind,
@@ -776,7 +776,7 @@ int vidc_ivf_scan_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, 
  *   call's kernels' time.
  * Not here.  Per-query radii; inner product, residual PQ, sub-quantisers of other than 8 bits; the coarse quantiser (the caller
  *   brings the probes); sharded containers; a one-pass form that buffers hits; the Faiss adapter (Faiss's own scanner stays its
- *   path). */
+ *   path).  (Residual PQ has entry points of its own: see the residual section below.) */
 int vidc_ivf_range_count_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes,
                              int code_kind, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq,
                              uint32_t nprobe, const int64_t *d_probes, float radius, uint64_t *d_slot_lims, uint64_t *total);
@@ -784,6 +784,57 @@ int vidc_ivf_range_fill_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_off
                             int code_kind, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq,
                             uint32_t nprobe, const int64_t *d_probes, float radius, const uint64_t *d_slot_lims, uint64_t capacity,
                             float *d_D, int64_t *d_labels);
+
+/* ---------------------------------------------------- residual PQ in the IVF scan and range search (by_residual, device-resident) */
+/* vidc_ivf_scan_dev and the two range calls for the index faiss.index_factory(d, "IVF<n>,PQ<M>") builds: an IndexIVFPQ with
+ * by_residual = true, where the code of a vector is the 8-bit PQ code of (vector - its list's centroid).  There is no code_kind
+ * argument: codes are M bytes each.  d_centroids: device float32 [nlist, d]; every other argument is the one of the same name in
+ * vidc_ivf_scan_dev / vidc_ivf_range_count_dev / vidc_ivf_range_fill_dev, with its array.
+ *
+ * Semantics (tests/ivf_residual_ref.py is the statement, csrc/ivf_residual_ref.h the serial form).  For a query xq, a valid list l
+ *   and a code of M bytes in that list, with dsub = d / M:
+ *     r           = xq - centroids[l]                                   one float32 subtraction per component
+ *     entry(m, c) = sum_i (r[m * dsub + i] - codebooks[m][c][i])^2      float32, components in order
+ *     distance    = sum_m entry(m, code[m])                             float32, in m order
+ *   the form Faiss uses without a precomputed table: a distance table per (query, list).  Everything else is unchanged from the
+ *   calls above: invalid probes are skipped and a repeated list counts once; a list's range is clamped; the key is
+ *   (distance bits << 32 | position); the scan's result is the first k in ascending (distance, label) order, padded with +inf / -1;
+ *   d_stats = {lists scanned, codes scanned}, an empty list still a list; a range hit is distance < radius, strictly; the slot
+ *   limits, the order of range results and the bounds on what the fill writes.  The distances of the two range calls are the
+ *   scan's, bit for bit: one function builds the table and one runs the trip, for all three.
+ * Bounds.  A centroid row is read only for a list number the probe rule accepted (0 <= l < nlist); a list's range is clamped to
+ *   a <= b <= ntotal before it indexes d_codes; a code byte indexes a 256-entry table.  Damaged offsets give a wrong result, never
+ *   an access outside the call's arrays.
+ * Status.  VIDC_ERR_INVALID before any device work, nothing written: the refusals of the call above it for VIDC_IVF_PQ8 (NULL
+ *   context; NULL arrays with nq > 0; k outside 1 .. 256; nprobe outside 1 .. 1024; d outside 1 .. 2048; ntotal >= 2^32; nlist >=
+ *   2^31; M outside 1 .. 64; d % M != 0; NULL codebooks; for the range calls nq * nprobe >= 2^32 - 1, NULL d_slot_lims with nq > 0,
+ *   NULL d_D or d_labels with capacity > 0), and NULL d_centroids with nq > 0.  nq == 0 and capacity == 0 behave as they do there.
+ * What runs.  The kernels of the calls above with one step more: a wavefront per (query, piece), the same cut S, pools, insert by
+ *   rank and merge kernel, count / device scan / fill.  In front of every probed list whose clamped range is not empty the wavefront
+ *   writes r to LDS and builds that list's M x 256 table from the codebooks (256 * d * 4 bytes read per (query, list)); an empty list
+ *   builds nothing.  Tables belong to lists, so cutting a row into S pieces builds no table twice.
+ * LDS.  Per wavefront: the scan's pools (2 * k * 8 + 768 bytes; the range calls have none), the probe row round16(4 * nprobe), the
+ *   query vector and the residual 2 * round16(4 * d), the table 1024 * M.  Scan at d = 128, M = 16, k = 20, nprobe = 16: 18560 bytes,
+ *   eight wavefronts per compute unit; at the limits (d = 2048, M = 64, nprobe = 1024, k = 256) 90880 bytes, one.
+ * Scratch.  That of the calls above: none for an uncut scan, nq * S * (k + 1) * 8 bytes for a cut one; nq * nprobe uint32 hit counts
+ *   and the tile sums of the device scan for a count; none for a fill.
+ * Residency.  Enqueued on the context's stream; every call waits for its kernels.  vidc_ctx_d2h_bytes does not move, except by the 8
+ *   bytes of a count with total != NULL.  vidc_ctx_last_kernel_ms is the call's kernels' time.
+ * Not here.  Inner product; precomputed tables (Faiss's use_precomputed_table: its float32 bits would differ); sub-quantisers of
+ *   other than 8 bits; per-query radii; the coarse quantiser (the caller brings the probes); sharded containers; the Faiss adapter
+ *   (Faiss's own scanner stays its path). */
+int vidc_ivf_scan_residual_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes,
+                               uint32_t d, uint32_t M, const float *d_codebooks, const float *d_centroids, uint64_t nq,
+                               const float *d_xq, uint32_t nprobe, const int64_t *d_probes, uint32_t k, float *d_D,
+                               int64_t *d_labels, uint32_t *d_stats);
+int vidc_ivf_range_count_residual_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes,
+                                      uint32_t d, uint32_t M, const float *d_codebooks, const float *d_centroids, uint64_t nq,
+                                      const float *d_xq, uint32_t nprobe, const int64_t *d_probes, float radius,
+                                      uint64_t *d_slot_lims, uint64_t *total);
+int vidc_ivf_range_fill_residual_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes,
+                                     uint32_t d, uint32_t M, const float *d_codebooks, const float *d_centroids, uint64_t nq,
+                                     const float *d_xq, uint32_t nprobe, const int64_t *d_probes, float radius,
+                                     const uint64_t *d_slot_lims, uint64_t capacity, float *d_D, int64_t *d_labels);
 
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a

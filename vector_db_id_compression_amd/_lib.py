@@ -183,6 +183,11 @@ def _declare(lib):
     _head = (_vp, _u64, _vp, _u64, _vp, C.c_int, _u32, _u32, _vp, _u64, _vp, _u32, _vp, C.c_float)
     f("vidc_ivf_range_count_dev", C.c_int, *_head, _vp, _P(_u64))
     f("vidc_ivf_range_fill_dev", C.c_int, *_head, _vp, _u64, _vp, _vp)
+    # residual PQ: no code_kind, the centroids behind the codebooks; the tails are the three calls' above
+    _rhead = (_vp, _u64, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _u32, _vp)
+    f("vidc_ivf_scan_residual_dev", C.c_int, *_rhead, _u32, _vp, _vp, _vp)
+    f("vidc_ivf_range_count_residual_dev", C.c_int, *_rhead, C.c_float, _vp, _P(_u64))
+    f("vidc_ivf_range_fill_residual_dev", C.c_int, *_rhead, C.c_float, _vp, _u64, _vp, _vp)
     # update rows (graph objects, device-resident)
     f("vidc_compact_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
     f("vidc_ef_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
@@ -256,6 +261,7 @@ EXPORTED_SYMBOLS = [
     "vidc_packed_locate_dev", "vidc_ef_locate_dev", "vidc_wt_locate_dev", "vidc_roc_locate_dev", "vidc_ef_rank_dev",
     "vidc_rows_search_dev", "vidc_compact_search_dev", "vidc_ef_search_dev", "vidc_ivf_scan_dev",
     "vidc_ivf_range_count_dev", "vidc_ivf_range_fill_dev",
+    "vidc_ivf_scan_residual_dev", "vidc_ivf_range_count_residual_dev", "vidc_ivf_range_fill_residual_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
     "vidc_shards_encode", "vidc_shards_encode_dev", "vidc_shards_destroy", "vidc_shards_count", "vidc_shards_kind", "vidc_shards_nlist",
     "vidc_shards_ntotal", "vidc_shards_compressed_bytes", "vidc_shards_map", "vidc_shards_offsets", "vidc_shards_shard",

@@ -5,6 +5,7 @@
 //     G-lane butterfly; which lanes sum which components depends on (d, G) only.  cdist: 64 floats of LDS.
 //   PQ8: a lane takes one code, its M bytes with loads of W = V bytes, and adds M table reads in m order (a byte indexes 256 entries:
 //     always inside).  table: the query's M x 256 entries in LDS.
+//   Residual PQ: the PQ8 trip over a table that residual_table built for (query, list).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,6 +41,53 @@ __device__ __forceinline__ float pq_distance(const uint8_t *code, const float *t
         }
     }
     return s;
+}
+
+// Residual PQ (ivf_residual.hip: scan, count and fill call this one function in front of every probed list that is not empty): the
+// residual r = qv - centroid, one float32 subtraction per component, goes to LDS and the wavefront builds the list's M x 256 table
+// from it; ivf_trip_distance<PQ8, W> then walks that table.  An entry is ivs::pq_entry(r, codebooks, dsub, m, c): the same
+// subtractions, squares and additions in the same order, with four entries of a lane in flight (lane e, e + 64, e + 128, e + 192 of
+// sub-quantiser m: M * 256 is a multiple of 256, so no entry is out of range) -- a lane that walked one entry at a time waited for
+// every load in turn.  vec4: the codebooks are read 16 bytes at a load (dsub % 4 == 0 and a 16-byte aligned base:
+// ivx::codebook_vec4), else a float at a load; the value does not depend on it.  A load of the wavefront covers 64 neighbouring
+// codebook rows.  qv, r: d floats of LDS each, 16-byte aligned; centroid: the list's row of the centroid array.  Holds three barriers
+// (lanes may still read the previous list's table; r is complete; the table is complete): every lane of the wavefront calls it.
+__device__ __forceinline__ void residual_table(const float *qv, const float *__restrict__ centroid, const float *__restrict__ codebooks,
+                                               uint32_t d, uint32_t M, bool vec4, uint32_t lane, float *r, float *table) {
+    __syncthreads();
+    for (uint32_t i = lane; i < d; i += 64) r[i] = qv[i] - centroid[i];
+    __syncthreads();
+    const uint32_t dsub = d / M;
+    for (uint32_t m = 0; m < M; m++) {
+        const float *rm = r + m * dsub;
+        const float *row = codebooks + ((uint64_t)m * 256u + lane) * dsub;  // entry (m, lane); entry (m, lane + 64 u) is 64 u rows on
+        const uint64_t step = (uint64_t)64 * dsub;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        if (vec4) {
+            for (uint32_t i = 0; i < dsub; i += 4) {
+                const float4 y = *(const float4 *)(rm + i);
+                const float4 x0 = *(const float4 *)(row + i), x1 = *(const float4 *)(row + step + i);
+                const float4 x2 = *(const float4 *)(row + 2 * step + i), x3 = *(const float4 *)(row + 3 * step + i);
+                float t;
+                t = y.x - x0.x; s0 += t * t; t = y.y - x0.y; s0 += t * t; t = y.z - x0.z; s0 += t * t; t = y.w - x0.w; s0 += t * t;
+                t = y.x - x1.x; s1 += t * t; t = y.y - x1.y; s1 += t * t; t = y.z - x1.z; s1 += t * t; t = y.w - x1.w; s1 += t * t;
+                t = y.x - x2.x; s2 += t * t; t = y.y - x2.y; s2 += t * t; t = y.z - x2.z; s2 += t * t; t = y.w - x2.w; s2 += t * t;
+                t = y.x - x3.x; s3 += t * t; t = y.y - x3.y; s3 += t * t; t = y.z - x3.z; s3 += t * t; t = y.w - x3.w; s3 += t * t;
+            }
+        } else {
+            for (uint32_t i = 0; i < dsub; i++) {
+                const float y = rm[i], x0 = row[i], x1 = row[step + i], x2 = row[2 * step + i], x3 = row[3 * step + i];
+                float t;
+                t = y - x0; s0 += t * t;
+                t = y - x1; s1 += t * t;
+                t = y - x2; s2 += t * t;
+                t = y - x3; s3 += t * t;
+            }
+        }
+        float *tm = table + m * 256u + lane;
+        tm[0] = s0; tm[64] = s1; tm[128] = s2; tm[192] = s3;
+    }
+    __syncthreads();
 }
 
 // The trip: codes p0 .. p0 + n of the code array (n <= 64, wavefront-uniform) -> lane c holds the distance of code p0 + c, lanes

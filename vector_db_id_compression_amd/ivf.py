@@ -7,7 +7,8 @@ It reproduces the call pattern the reference exercises through Faiss (SURVEY.md 
                                      by one (`get_single_id`, custom_invlists_impl.cpp:466-475) or per touched list
                                      (`get_ids`, :477-525) -- here as ONE batched device decode
 The vector side (k-means, flat / PQ codes, distance scan) is plain torch: it is harness plumbing, not the
-product.  Codes: "Flat" (float32 bytes) or ("PQ", M) with 8-bit sub-quantizers (PQ4np / PQ16 style).
+product.  Codes: "Flat" (float32 bytes) or ("PQ", M) with 8-bit sub-quantizers (PQ4np / PQ16 style); by_residual=True makes the PQ
+code that of (vector - its list's centroid), as faiss.index_factory(d, "IVF<n>,PQ<M>") does.
 """
 import numpy as np
 
@@ -93,9 +94,12 @@ def _host_subset(il, subset_type, a1, a2):
 
 
 class IVFIndex:
-    def __init__(self, d, nlist, code="Flat"):
+    def __init__(self, d, nlist, code="Flat", by_residual=False):
         self.d, self.nlist = int(d), int(nlist)
         self.code = code
+        self.by_residual = bool(by_residual)
+        if self.by_residual and not isinstance(code, tuple):
+            raise ValueError("by_residual needs (\"PQ\", M) codes")
         self.nprobe = 1
         self.parallel_mode = 0
         self.centroids = None
@@ -119,19 +123,23 @@ class IVFIndex:
         if self.M:
             dsub = self.d // self.M
             assert dsub * self.M == self.d
+            if self.by_residual:
+                xt = xt - self.centroids[_assign(xt, self.centroids)]
             self.pq = torch.stack([_kmeans(xt[:, m * dsub:(m + 1) * dsub], 256, seed=7 + m) for m in range(self.M)])
 
-    def _encode_dev(self, x):
-        """codes of x as a uint8 CUDA tensor [n, code_size]"""
+    def _encode_dev(self, x, assign=None):
+        """codes of x as a uint8 CUDA tensor [n, code_size]; assign: the list of every row (by_residual encodes x - centroids[assign])"""
         torch = _torch()
         if not self.M:
             return x.contiguous().view(torch.uint8).reshape(x.shape[0], 4 * self.d)
+        if self.by_residual:
+            x = x - self.centroids[assign]
         dsub = self.d // self.M
         codes = torch.stack([_assign(x[:, m * dsub:(m + 1) * dsub].contiguous(), self.pq[m]) for m in range(self.M)], 1)
         return codes.to(torch.uint8)
 
-    def _encode(self, x):
-        return self._encode_dev(x).cpu().numpy()
+    def _encode(self, x, assign=None):
+        return self._encode_dev(x, assign).cpu().numpy()
 
     def add(self, xb):
         torch = _torch()
@@ -139,13 +147,15 @@ class IVFIndex:
         if hasattr(self.invlists, "add_batch"):  # a compressed container: assignments, ids and codes stay on the device
             n = xb.shape[0]
             ids = torch.arange(self._next_id, self._next_id + n, dtype=torch.int64, device=xb.device)
-            self.invlists.add_batch(_assign(xb, self.centroids), ids, self._encode_dev(xb))
+            assign = _assign(xb, self.centroids)
+            self.invlists.add_batch(assign, ids, self._encode_dev(xb, assign))
             self.ntotal += n
             self._next_id += n
             self._dev = None
             return
-        assign = _assign(xb, self.centroids).cpu().numpy()
-        codes = self._encode(xb)
+        assign = _assign(xb, self.centroids)
+        codes = self._encode(xb, assign)
+        assign = assign.cpu().numpy()
         ids = np.arange(self._next_id, self._next_id + xb.shape[0], dtype=np.int64)
         order = np.argsort(assign, kind="stable")
         bounds = np.searchsorted(assign[order], np.arange(self.nlist + 1))
@@ -202,6 +212,8 @@ class IVFIndex:
             raise TypeError(f"{what}: other must be an IVFIndex")
         if (other.d, other.nlist, other.code) != (self.d, self.nlist, self.code):
             raise ValueError(f"{what}: d, nlist or code differ")
+        if other.by_residual != self.by_residual:
+            raise ValueError(f"{what}: by_residual differs")
         for mine, theirs, name in ((self.centroids, other.centroids, "centroids"), (self.pq, other.pq, "PQ codebooks")):
             if (mine is None) != (theirs is None) or (mine is not None and not _torch().equal(mine, theirs)):
                 raise ValueError(f"{what}: the {name} differ")
@@ -249,7 +261,16 @@ class IVFIndex:
             rows = torch.from_numpy(_host_rows(il, np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids, dtype=np.int64))).cuda()
         else:
             raise RuntimeError("reconstruct_batch: the inverted lists have no direct map")
-        return self._decode_codes(codes[rows])
+        vecs = self._decode_codes(codes[rows])
+        if self.by_residual:
+            vecs = vecs + self.centroids[self._rows_lists(rows)]
+        return vecs
+
+    def _rows_lists(self, rows):
+        """the list every row of the code array lies in, as an int64 CUDA tensor (the last l with offsets[l] <= row)"""
+        torch = _torch()
+        off, _ = self._device_lists()
+        return torch.searchsorted(torch.from_numpy(off[1:].copy()).to(rows.device), rows, right=True)
 
     def replace_invlists(self, il, own=False):
         self.invlists = il
@@ -296,6 +317,8 @@ class IVFIndex:
                 continue
             rows, labs = torch.cat(rows), torch.cat(labs)
             vecs = self._decode_codes(codes[rows])
+            if self.by_residual:
+                vecs = vecs + self.centroids[labs >> 32]
             dist = ((vecs - xq[q][None, :]) ** 2).sum(1)
             kk = min(k, dist.numel())
             top = torch.topk(dist, kk, largest=False, sorted=True)
@@ -321,7 +344,8 @@ class IVFIndex:
         """The scan of _scan as one library call (vidc_ivf_scan_dev): -> (D float32 [nq, k], labels int64 [nq, k] = list_no << 32 |
         offset) as CUDA tensors, +inf / -1 padded, ascending in (distance, label).  probes: an int64 [nq, nprobe] CUDA tensor of list
         numbers, used as it is (-1 = no list); None picks them on the device with the cdist + topk of _scan.  Works over the codes of
-        a compressed container and of ArrayInvertedLists, for "Flat" and ("PQ", M).  Runs on torch's current stream."""
+        a compressed container and of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the latter through
+        vidc_ivf_scan_residual_dev).  Runs on torch's current stream."""
         from . import _lib
 
         torch = _torch()
@@ -348,6 +372,13 @@ class IVFIndex:
         ptr = _lib.ptr
         pq = self.pq.to(torch.float32).contiguous() if self.M else None
         ctx = _lib.default_context()
+        if self.by_residual:
+            cent = self.centroids.to(torch.float32).contiguous()
+            _lib.check(_lib.lib().vidc_ivf_scan_residual_dev(
+                ctx.h, self.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None, self.d, self.M, ptr(pq), ptr(cent),
+                nq, ptr(xq) if nq else None, int(probes.shape[1]), ptr(probes) if probes.numel() else None, k,
+                ptr(D) if D.numel() else None, ptr(labels) if labels.numel() else None, None))
+            return D, labels
         _lib.check(_lib.lib().vidc_ivf_scan_dev(
             ctx.h, self.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None,
             _lib.VIDC_IVF_PQ8 if self.M else _lib.VIDC_IVF_FLAT, self.d, self.M, ptr(pq) if self.M else None, nq, ptr(xq) if nq else None,

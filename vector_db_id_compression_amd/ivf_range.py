@@ -6,8 +6,9 @@ deferred id decoding -- every stored vector of the probed lists closer than a ra
 
 Query q's results are D[lims[q]:lims[q + 1]], in probe-row order and then offset order (not sorted by distance, as in Faiss).  A
 result is a candidate whose squared L2 distance is strictly below the radius.  Works over the codes of a compressed container and
-of ArrayInvertedLists, for "Flat" and ("PQ", M).  The only host traffic is the total (8 bytes) between the two passes: the output is
-allocated from it.  Per-query radii, inner product and sharded containers are out of scope.
+of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the two *_residual_dev calls).  The only host traffic is the
+total (8 bytes) between the two passes: the output is allocated from it.  Per-query radii, inner product and sharded containers are
+out of scope.
 """
 import ctypes as C
 
@@ -48,13 +49,18 @@ def range_scan_device(index, xq, radius, probes=None):
     head = (ctx.h, index.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None,
             VIDC_IVF_PQ8 if index.M else VIDC_IVF_FLAT, index.d, index.M, ptr(pq) if index.M else None, nq, ptr(xq) if nq else None,
             nprobe, ptr(probes) if probes.numel() else None, radius)
+    count, fill = lib().vidc_ivf_range_count_dev, lib().vidc_ivf_range_fill_dev
+    if getattr(index, "by_residual", False):  # residual PQ: no code kind, the centroids behind the codebooks
+        cent = index.centroids.to(torch.float32).contiguous()
+        head = head[:5] + (index.d, index.M, ptr(pq), ptr(cent)) + head[9:]
+        count, fill = lib().vidc_ivf_range_count_residual_dev, lib().vidc_ivf_range_fill_residual_dev
     slot_lims = torch.empty(nq * nprobe + 1, dtype=torch.int64, device=xq.device)
     total = C.c_uint64(0)
-    check(lib().vidc_ivf_range_count_dev(*head, ptr(slot_lims), C.byref(total)))
+    check(count(*head, ptr(slot_lims), C.byref(total)))
     n = int(total.value)
     D = torch.empty(n, dtype=torch.float32, device=xq.device)
     labels = torch.empty(n, dtype=torch.int64, device=xq.device)
-    check(lib().vidc_ivf_range_fill_dev(*head, ptr(slot_lims), n, ptr(D) if n else None, ptr(labels) if n else None))
+    check(fill(*head, ptr(slot_lims), n, ptr(D) if n else None, ptr(labels) if n else None))
     return slot_lims[::nprobe].contiguous(), D, labels
 
 
