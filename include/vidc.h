@@ -836,6 +836,38 @@ int vidc_ivf_range_fill_residual_dev(vidc_ctx *ctx, uint64_t nlist, const uint64
                                      const float *d_xq, uint32_t nprobe, const int64_t *d_probes, float radius,
                                      const uint64_t *d_slot_lims, uint64_t capacity, float *d_D, int64_t *d_labels);
 
+/* ---------------------------------------------------- the probe rows of the IVF calls on the device (nearest centroids, float32 MFMA) */
+/* The step the sections above leave to the caller: the nprobe nearest centroids of every query.  d_centroids: device float32
+ * [nlist, d]; d_xq: device float32 [nq, d]; d_probes: device int64 [nq, nprobe]; d_cdist: device float32 [nq, nprobe], or NULL.  A
+ * row of d_probes is directly the d_probes row of vidc_ivf_scan_dev, the two range calls and the three residual calls.
+ *
+ * Semantics, per query and independently.  The candidates are the lists 0 .. nlist - 1; the key of list l is (squared L2 distance
+ *   between the query and centroid l, l); the result is the first nprobe lists in ascending (distance, list number) order.  With
+ *   nprobe > nlist the tail is -1 in d_probes and +inf in d_cdist.  Every element of both arrays is written and nothing outside them.
+ * Distance.  float32, max(0, |q|^2 + |c|^2 - 2 q.c).  Where every partial sum is an integer below 2^24 that is the exact distance;
+ *   on float data it lies within (d + 4) * 2^-24 * (|q| + |c|)^2 of it (a d-term float32 dot product in any order, and three scalar
+ *   operations).  The clamp keeps the value non-negative, so float bits << 32 | l orders like (distance, l).  The value of a pair
+ *   (q, c) does not depend on how the work was cut nor on where q or c falls in a tile: the component loop has one length and one
+ *   order, zero padding adds nothing, both norms are summed in one fixed order.  Results are bit-equal on every context.  Non-finite
+ *   inputs give some order, never a list number outside [-1, nlist).
+ * Status.  VIDC_ERR_INVALID before any device work, nothing written: NULL context; NULL d_centroids, d_xq or d_probes with nq > 0;
+ *   nprobe outside 1 .. 256 (the pool limit of the scan); d outside 1 .. 2048; nlist outside 1 .. 2^31 - 1; nq >= 2^32.  nq == 0
+ *   returns VIDC_OK and launches nothing.
+ * What runs.  k_ivf_probe: a workgroup of four wavefronts per (tile of TQ queries, piece of the centroid range), TQ = 32 up to
+ *   nprobe = 64 and 16 above.  Centroids are streamed in tiles of 128, 32 components at a time, through two staging buffers in LDS;
+ *   the products are v_mfma_f32_16x16x4_f32 (no fp16, bf16 or xf32 pass); a tile's distances go through the scan's drop-by-ballot /
+ *   insert-by-rank step into two pools of nprobe keys per query.  The centroid range is cut into S pieces, S the smallest power of
+ *   two <= 256 that fills the resident workgroups; with S > 1 k_ivf_probe_merge, a wavefront per query, merges the S runs.
+ * LDS.  16 * TQ * nprobe (pools) + 2048 + 288 * (TQ + 128) (staging) + 528 * TQ + 4 * (TQ + 128): 73856 bytes at nprobe = 16,
+ *   118080 at nprobe = 256.
+ * Scratch.  None for S == 1; nq * S * nprobe * 8 bytes from the context's block cache otherwise.
+ * Residency.  Enqueued on the context's stream; the call waits for its kernels.  vidc_ctx_d2h_bytes does not move.
+ *   vidc_ctx_last_kernel_ms is the kernels' time.
+ * Not here.  fp16 / bf16 distance passes with a float32 re-rank; inner product; nprobe > 256; fusing this step into the scan
+ *   kernel; HNSW coarse quantisers; the Faiss adapter. */
+int vidc_ivf_probe_dev(vidc_ctx *ctx, uint64_t nlist, const float *d_centroids, uint32_t d, uint64_t nq, const float *d_xq,
+                       uint32_t nprobe, int64_t *d_probes, float *d_cdist);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

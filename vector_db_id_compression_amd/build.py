@@ -22,6 +22,9 @@ HASH = LIB + ".srchash"
 LOCK = LIB + ".lock"
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
+# flags of single translation units.  ivf_probe.hip is the one float32 kernel: its arithmetic stays on the unpacked instructions
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"ivf_probe.hip": NO_PACKED_FP32}
 
 
 def sources():
@@ -33,7 +36,7 @@ def _deps():
 
 
 def source_hash():
-    h = hashlib.sha256(" ".join(FLAGS).encode())
+    h = hashlib.sha256(" ".join(FLAGS + [f"{u}: {' '.join(f)}" for u, f in sorted(UNIT_FLAGS.items())]).encode())
     for d in _deps():
         h.update(os.path.basename(d).encode() + b"\0")
         with open(d, "rb") as f:
@@ -83,7 +86,7 @@ def build(force=False, verbose=False):
                 # one compiler process per translation unit (they are independent), then one link
                 def compile_one(src):
                     obj = os.path.join(objdir, os.path.basename(src) + ".o")
-                    cmd = [hipcc] + [f for f in FLAGS if f != "-shared"] + ["-c", src, "-o", obj]
+                    cmd = [hipcc] + [f for f in FLAGS if f != "-shared"] + UNIT_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
                     if verbose:
                         print(" ".join(cmd), file=sys.stderr)
                     subprocess.check_call(cmd)

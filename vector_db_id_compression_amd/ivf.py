@@ -110,6 +110,8 @@ class IVFIndex:
         self.ntotal = 0
         self._next_id = 0  # vectors ever added: ids handed out by add never repeat, also after remove_ids
         self._dev = None
+        # True: probe rows (nprobe <= 256) and add's list assignment come from vidc_ivf_probe_dev (ivf_probe.py), not torch
+        self.coarse_device = False
 
     # -- build
     def train(self, xt):
@@ -141,19 +143,35 @@ class IVFIndex:
     def _encode(self, x, assign=None):
         return self._encode_dev(x, assign).cpu().numpy()
 
+    def _assign_lists(self, xb):
+        if self.coarse_device:
+            from . import ivf_probe
+
+            return ivf_probe.assign_device(self, xb)
+        return _assign(xb, self.centroids)
+
+    def _probe_rows(self, xq):
+        nprobe = min(self.nprobe, self.nlist)
+        if self.coarse_device:
+            from . import ivf_probe
+
+            if nprobe <= ivf_probe.MAX_NPROBE:
+                return ivf_probe.probe_device(self, xq, nprobe)[0]
+        return _torch().cdist(xq, self.centroids).topk(nprobe, largest=False).indices
+
     def add(self, xb):
         torch = _torch()
         xb = torch.as_tensor(np.asarray(xb, dtype=np.float32)).cuda()
         if hasattr(self.invlists, "add_batch"):  # a compressed container: assignments, ids and codes stay on the device
             n = xb.shape[0]
             ids = torch.arange(self._next_id, self._next_id + n, dtype=torch.int64, device=xb.device)
-            assign = _assign(xb, self.centroids)
+            assign = self._assign_lists(xb)
             self.invlists.add_batch(assign, ids, self._encode_dev(xb, assign))
             self.ntotal += n
             self._next_id += n
             self._dev = None
             return
-        assign = _assign(xb, self.centroids)
+        assign = self._assign_lists(xb)
         codes = self._encode(xb, assign)
         assign = assign.cpu().numpy()
         ids = np.arange(self._next_id, self._next_id + xb.shape[0], dtype=np.int64)
@@ -357,7 +375,7 @@ class IVFIndex:
         if xq.dim() != 2 or xq.shape[1] != self.d:
             raise ValueError(f"xq must be [nq, {self.d}]")
         if probes is None:
-            probes = torch.cdist(xq, self.centroids).topk(min(self.nprobe, self.nlist), largest=False).indices
+            probes = self._probe_rows(xq)
         if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.int64 and probes.dim() == 2
                 and probes.shape[0] == xq.shape[0]):
             raise ValueError("probes must be an int64 CUDA tensor [nq, nprobe]")

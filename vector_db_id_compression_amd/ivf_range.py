@@ -36,7 +36,7 @@ def range_scan_device(index, xq, radius, probes=None):
     if xq.dim() != 2 or xq.shape[1] != index.d:
         raise ValueError(f"xq must be [nq, {index.d}]")
     if probes is None:
-        probes = torch.cdist(xq, index.centroids).topk(min(index.nprobe, index.nlist), largest=False).indices
+        probes = index._probe_rows(xq)
     if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.int64 and probes.dim() == 2
             and probes.shape[0] == xq.shape[0]):
         raise ValueError("probes must be an int64 CUDA tensor [nq, nprobe]")
