@@ -868,6 +868,33 @@ int vidc_ivf_range_fill_residual_dev(vidc_ctx *ctx, uint64_t nlist, const uint64
 int vidc_ivf_probe_dev(vidc_ctx *ctx, uint64_t nlist, const float *d_centroids, uint32_t d, uint64_t nq, const float *d_xq,
                        uint32_t nprobe, int64_t *d_probes, float *d_cdist);
 
+/* ---------------------------------------------------- the PQ codes of a vector batch on the device (8-bit sub-quantisers, float32 MFMA) */
+/* The last step of an add that the sections above leave to the caller: the codes the PQ8 scan and range calls read.  d_x: device
+ * float32 [n, d]; d_pq: device float32 [M, 256, d / M], the d_codebooks of the scan calls; d_codes: device uint8 [n, M], row-major and
+ * tight.  d_centroids == NULL is raw PQ: nlist and d_assign are ignored.  With d_centroids (device float32 [nlist, d]) and d_assign
+ * (device int64 [n]) the code is that of r = x[i] - centroids[assign[i]], one float32 subtraction per component: the code
+ * vidc_ivf_scan_residual_dev reads.  A row whose assign[i] is outside [0, nlist) gets M zero bytes.
+ *
+ * The code.  code[i][m] is the smallest j that minimises the computed score s(i, m, j) = |c_j|^2 - 2 r.c_j over the 256 codewords of
+ *   sub-quantiser m (|r|^2 is the same for every j and is not computed).  |c_j|^2 is summed with fmaf in component order, r.c_j is a
+ *   float32 dot product in an order that depends on d / M alone, the score is fmaf(-2, r.c_j, |c_j|^2).  Where every partial sum is an
+ *   integer below 2^24 the result is the float64 argmin with first-index ties; on float data the chosen codeword's distance is within
+ *   2 (d / M + 4) 2^-24 (|r| + max |c|)^2 of the smallest.  A code is the same bit pattern however the batch was tiled or cut and
+ *   whichever context ran it.  Every byte of d_codes is written and nothing outside it.
+ * Status.  VIDC_ERR_INVALID before any device work, nothing written: NULL context; NULL d_x, d_pq or d_codes with n > 0; centroids
+ *   without d_assign, or with nlist == 0 or nlist >= 2^31; d outside 1 .. 2048; M == 0 or d % M != 0; d / M > 128 (the codebook of one
+ *   sub-quantiser is held in LDS); n >= 2^32.  n == 0 returns VIDC_OK and launches nothing.
+ * What runs.  k_ivf_pq_encode: a workgroup of four wavefronts per (sub-quantiser, piece of the vector range), S pieces so that M * S
+ *   covers the resident workgroups.  The codebook is staged once per item as [256][round_up(d / M, 4) + 4] floats; vectors go from
+ *   global memory straight into MFMA operands, 32 rows a wavefront; v_mfma_f32_16x16x4_f32 against all 256 codewords; the argmin is
+ *   taken in registers (a lane's 16 column blocks, then a four-step butterfly) and one lane per row stores the byte.
+ * LDS.  1024 * (round_up(d / M, 4) + 5) bytes: 13312 at d / M = 8, 136192 at 128.  No scratch, no context scratch.
+ * Residency.  Enqueued on the context's stream; the call waits for its kernel.  vidc_ctx_d2h_bytes does not move.
+ *   vidc_ctx_last_kernel_ms is the kernel's time.
+ * Not here.  Sub-quantisers of other than 8 bits; inner product; d / M > 128; k-means; fusing the coarse assignment. */
+int vidc_ivf_pq_encode_dev(vidc_ctx *ctx, uint64_t n, const float *d_x, uint32_t d, uint32_t M, const float *d_pq, uint64_t nlist,
+                           const float *d_centroids, const int64_t *d_assign, uint8_t *d_codes);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

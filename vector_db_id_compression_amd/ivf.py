@@ -112,6 +112,8 @@ class IVFIndex:
         self._dev = None
         # True: probe rows (nprobe <= 256) and add's list assignment come from vidc_ivf_probe_dev (ivf_probe.py), not torch
         self.coarse_device = False
+        # True: PQ codes (d / M <= 128) come from vidc_ivf_pq_encode_dev (ivf_encode.py), not torch
+        self.pq_device = False
 
     # -- build
     def train(self, xt):
@@ -134,6 +136,10 @@ class IVFIndex:
         torch = _torch()
         if not self.M:
             return x.contiguous().view(torch.uint8).reshape(x.shape[0], 4 * self.d)
+        if self.pq_device and self.d // self.M <= 128:
+            from . import ivf_encode
+
+            return ivf_encode.encode_device(self, x, assign)
         if self.by_residual:
             x = x - self.centroids[assign]
         dsub = self.d // self.M
