@@ -4,6 +4,8 @@
 // (U2DecWord), five repeats each as well.  With -DU2_PROF the decode section table is the LAST decode arm's.
 // -DU2_DEC_STEP=0..3 selects the form of the k_roc_decode_u2 step (roc_u2.h: bit 0 rank at the bit's lane, bit 1 one-branch pops;
 // 0 is the step before both): one binary per value, run in one session, is how a candidate is measured against the step without it.
+// -DU2_ENC_PUSH=0 builds the dense encode step with both slices of the id push branch-free in every step (the step before the
+// classified push, roc_u2.h); the default is the library's step.
 // usage: chain_u2 [n] [seed] [ub] [P]     (-DU2_PROF: section tables of the LAST encode arm run and of the k_roc_decode_u2 step;
 // -DU2_PROF2: generic steps, entries into the asm loop and bits in the bitmap of the last k_roc_decode_u2 launch)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I vector_db_id_compression_amd/csrc tools/chain_u2.hip -o /tmp/chain_u2

@@ -379,7 +379,7 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "v_readfirstlane_b32 s67, v31\n" \
     "v_mul_lo_u32 v48, v46, v9\n"
 
-// The output ring (64 words, a step pushes at most two) is checked by the LAST copy of the loop body only, for the up to eight
+// The output ring (64 words; a step pushes at most one, the bound of two is kept) is checked by the LAST copy of the loop body only, for the up to eight
 // steps that follow: U2_RING_ROOM words at most on entry (the C++ glue and U2_ENC_OUTER spill from there on), 48 + 2 * 8 = 64.
 #define U2_RING_ROOM 48
 #define U2_RING_CHECK \
@@ -416,7 +416,7 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* (first instruction of the exit test, SCC = B >= 2^31: m0 settles meanwhile) */ \
     "v_writelane_b32 v6, s40, m0\n"
 
-// ---- the step on dense blocks (U2Dense), 79 instructions: the bitmap step's fix-up and level 1, with k kept in s42 (v_cmp takes
+// ---- the step on dense blocks (U2Dense), 64 instructions (79 in the side body of a push that spills): the bitmap step's fix-up and level 1, with k kept in s42 (v_cmp takes
 // the SGPR operand) and the level-1 mask in s[82:83].  Level 2 compares k itself with E1[L1] + row (one v_add in all lanes instead
 // of a scalar subtraction between two read-outs); the v_readlane of that sum at L2 gives E1[L1] + row[L2], one s_sub the rank inside
 // the block.  Behind level 2 all 64 lanes read u16 slots from the block's first slot on (lane j holds slot j; lanes >= 16 read the
@@ -432,14 +432,36 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
 // read (bytes 2 (L - 1) of it, L <= 15) or lies in the strip: inside U2Dense::LDS_BYTES.  LDS operations of one wavefront execute
 // in order, so the next read of the block sees the shift; slots behind a block's alive count hold stale values and are never
 // selected.  Nothing is pending at a step boundary (the bitmap step clears the previous id's bit at the top of the next one).
-// A scalar instruction issued within ~16 cycles of a v_readlane / v_cmp / carry-writing instruction waits the window out: both
-// slices are renormalised BEFORE level 2 (they depend on q alone); v_mul_hi fills the window of the level-2 compare, the four counter
+// A scalar instruction issued within ~16 cycles of a v_readlane / v_cmp / carry-writing instruction waits the window out: the
+// push (U2_ENC_CLASS_D, in the side body both slices) is done BEFORE level 2 (it depends on q alone); v_mul_hi fills the window of the level-2 compare, the four counter
 // instructions the window of the level-2 read-out, the three v_mad_u64_u32 of the division (U2_DIV) run behind the removal's compare
 // in the shadow of the LDS reads, and v_mul_lo fills the window of x.  (profiles/r24_roc_encode_step.txt: what each change bought.)
 //   v3 = 2 * lane - 2 + SLOT_OFF   v26 base address   v27 E1[L1] + row   v28 slot address - 2   v30 slots   v31 base   v32 base + slots
 //   v59 -1 / 0 of a counter update   v60 lane number in lanes 1..15, else 0   v61 address of the removal's store   v62 STRIP_OFF + 4 * lane
 //   s42 k, then the rank inside the block   s63 E1[L1] + row[L2]   s[82:83] level-1 mask, then the lanes of the shift
-#define U2_ENC_TOP_D \
+// ---- the id push of the dense step (codec_push, codec.cpp:92-105), classified once from q = the head behind the index pop
+// (csrc/u2_push_ref.h is the same in plain C++; tests/u2_push_test.cpp checks it against the two slices).  With p0 = min(P, 16),
+// p1 = clamp(P - 16, 0, 16): a step spills at most once, and which slice spills depends on q alone, never on x:
+//   class A  q >= 2^(63 - p0)            slice 0 spills q's low word          B = (q >> 32) << (p0 + p1)
+//   class B  2^(63 - p0 - p1) <= q < ..  slice 1 spills a word that holds x_lo   B = (q >> (32 - p0)) << p1, x_lo leaves c(x)
+//   class C  q < 2^(63 - p0 - p1)        no spill, no ring write, sp unchanged   B = q << (p0 + p1)
+// The common path (class C, four steps in five of a 20-bit list) is one compare of q's high word with s46 = 2^(31 - p0 - p1), one
+// branch not taken and one s_lshl_b64; classes A and B leave for a side body behind the copies of the loop (one per copy, like
+// U2_DEC_SIDE_P), which runs the two branch-free slices and the REST of the step with the word of the second slice, and comes back at
+// the top of the next copy.
+//   s41 multiplier of x_lo in the next step's fix-up: written ONCE, by U2_ENC_ENTRY_D (2^p1), and by nothing inside the loop.  A
+//       class-B step instead clears the low half of s40 behind its last use (the order ring and the spilled word have x by then; a
+//       dense step leaves nothing pending that needs x), so c(x) = x_hi on every way into the next top and in the C++ glue behind an
+//       exit, which computes c(x) from s40 and s41.
+//   s46 2^(31 - p0 - p1)   s47 p0 + p1   (U2_ENC_ENTRY_D; the dense step leaves both alone)   s48 mask of s40 in the side body
+// Ring slots at or above sp keep whatever they held: the common path writes none.  Nothing reads them: U2_ENC_OUTER and ws_spill32
+// store the 32 slots from lo (sp - lo >= 48 there), ws_flush the slots in [lo, sp), U2_RING_CHECK reads sp and lo only; a later push
+// writes its slot before sp moves over it.  A step pushes at most one word, so U2_RING_ROOM + 8 <= 64 holds as before.
+// -DU2_ENC_PUSH=0 (tools/chain_u2.hip) builds the step before this: both slices branch-free in every step.  The library builds the default.
+#ifndef U2_ENC_PUSH
+#define U2_ENC_PUSH 1
+#endif
+#define U2_ENC_TOP_D_FIX \
     U2P(130) U2P(131) \
     "v_lshrrev_b32_e64 v14, 16, s40\n"                 /* x_hi */ \
     "v_bfe_u32 v15, s40, 0, 16\n"                      /* x_lo */ \
@@ -461,7 +483,8 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_ff1_i32_b64 s43, s[82:83]\n" \
     "s_set_gpr_idx_on s43, gpr_idx(SRC0)\n" \
     "v_mov_b32 v13, v64\n"                             /* row L1 */ \
-    "s_set_gpr_idx_off\n" U2P(134) \
+    "s_set_gpr_idx_off\n" U2P(134)
+#define U2_ENC_SLICES_D(SEL) \
     "s_and_b32 m0, s60, 63\n"                          /* slice 0 (codec.cpp:65-76), branch-free */ \
     "s_cmp_ge_u32 s51, s73\n" \
     "v_writelane_b32 v5, s50, m0\n" \
@@ -471,11 +494,16 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_lshl_b64 s[54:55], s[52:53], s76\n" \
     "s_and_b32 s62, s60, 63\n"                         /* slice 1: B is known before the select has started */ \
     "s_cmp_ge_u32 s55, s74\n" \
-    "s_cselect_b32 s41, 0, s75\n" \
+    SEL \
     "s_cselect_b32 s56, s55, s54\n" \
     "s_cselect_b32 s57, 0, s55\n" \
     "s_addc_u32 s60, s60, 0\n" \
-    "s_lshl_b64 s[58:59], s[56:57], s77\n"             /* B */ U2P(135) \
+    "s_lshl_b64 s[58:59], s[56:57], s77\n"             /* B */ U2P(135)
+#define U2_ENC_CLASS_D(LA) \
+    "s_cmp_ge_u32 s51, s46\n"                          /* q >= 2^(63 - p0 - p1): class A or B */ \
+    "s_cbranch_scc1 " LA "f\n" \
+    "s_lshl_b64 s[58:59], s[50:51], s47\n"             /* class C: B = q << (p0 + p1) */ U2P(135)
+#define U2_ENC_TOP_D_L2 \
     "v_readlane_b32 s49, v4, s43\n" \
     "v_add_u32 v27, s49, v13\n"                        /* E1[L1] + row: level 2 compares k itself, no scalar subtraction in between */ \
     "v_cmp_ge_u32 vcc, s42, v27\n"                     /* level 2 */ \
@@ -500,17 +528,19 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "v_mov_b32 v40, v43\n" \
     "v_mad_u64_u32 v[46:47], s[78:79], s59, v8, v[40:41]\n" \
     "s_waitcnt lgkmcnt(0)\n" U2P(139)
-#define U2_ENC_BOT_D(ORDER, LSHR, RING, TAIL) \
+#define U2_ENC_WORD2_D \
+    "s_mov_b32 m0, s62\n" \
+    "s_and_b32 s68, s40, 0xffff\n" \
+    "s_or_b32 s68, s68, s54\n" \
+    "v_writelane_b32 v5, s68, m0\n"                    /* word of the second slice (kept only if it renormalised) */
+#define U2_ENC_BOT_D(WORD2, ORDER, LSHR, RING, TAIL) \
     "v_add_u32 v32, v30, v31\n"                        /* every lane: the block's first id + its slot */ \
     "v_cndmask_b32_e64 v61, v62, v28, s[82:83]\n"      /* the slot below, or the lane's own dword of the strip */ \
     "v_readlane_b32 s40, v32, s42\n"                   /* x */ \
     "ds_write_b16 v61, v30\n"                          /* removal: the alive slots behind k_rem move one slot down (all lanes store) */ \
     "v_mul_lo_u32 v48, v46, v9\n"                      /* (16 cycles: the window of the read-out) */ \
     "v_sub_u32 v48, s58, v48\n"                        /* r_B in [0, 2d) */ U2P(140) \
-    "s_mov_b32 m0, s62\n" \
-    "s_and_b32 s68, s40, 0xffff\n" \
-    "s_or_b32 s68, s68, s54\n" \
-    "v_writelane_b32 v5, s68, m0\n"                    /* word of the second slice (kept only if it renormalised) */ \
+    WORD2 \
     ORDER U2P(141) \
     "s_set_gpr_idx_on s43, gpr_idx(DST)\n" \
     "v_mov_b32 v64, v13\n" \
@@ -523,6 +553,35 @@ __device__ __forceinline__ uint32_t u2d_slow_step(uint64_t &head, WStack &st, ui
     "s_add_u32 s69, s69, 1\n" U2P(143) \
     "s_cmp_lt_u32 s69, s71\n" \
     TAIL
+#if U2_ENC_PUSH
+#define U2_ENC_ENTRY_D \
+    "s_add_u32 s47, s76, s77\n" \
+    "s_lshr_b32 s46, s73, s77\n" \
+    "s_mov_b32 s41, s75\n"
+// one copy of the loop (LT: the label of its top), and the side body of that copy (LA), which goes on at the top of the next copy (NEXT)
+#define U2_STEP_D(ORDER, LSHR, LT, LA) LT ":\n" U2_ENC_TOP_D_FIX U2_ENC_CLASS_D(LA) U2_ENC_TOP_D_L2 U2_ENC_MID_D U2_ENC_BOT_D("", ORDER, LSHR, "", "s_cbranch_scc0 7f\n")
+#define U2_LAST_D(ORDER, LSHR, LT, LA) LT ":\n" U2_ENC_TOP_D_FIX U2_ENC_CLASS_D(LA) U2_ENC_TOP_D_L2 U2_ENC_MID_D U2_ENC_BOT_D("", ORDER, LSHR, U2_RING_CHECK, "s_cbranch_scc1 1b\n s_branch 7f\n")
+#define U2_ENC_SIDE_T(ORDER, LSHR, LA, RING, TAIL) \
+    LA ":\n" U2_ENC_SLICES_D("s_cselect_b32 s48, 0xffff0000, -1\n") U2_ENC_TOP_D_L2 U2_ENC_MID_D \
+    U2_ENC_BOT_D(U2_ENC_WORD2_D, ORDER, LSHR, "s_and_b32 s40, s40, s48\n" RING, TAIL)
+#define U2_SIDE_D(ORDER, LSHR, LA, NEXT) U2_ENC_SIDE_T(ORDER, LSHR, LA, "", "s_cbranch_scc1 " NEXT "b\n s_branch 7f\n")
+#define U2_SIDE_LAST_D(ORDER, LSHR, LA) U2_ENC_SIDE_T(ORDER, LSHR, LA, U2_RING_CHECK, "s_cbranch_scc1 1b\n s_branch 7f\n")
+#define U2_LOOP8_D(O, L) \
+    U2_STEP_D(O, L, "1", "20") U2_STEP_D(O, L, "21", "30") U2_STEP_D(O, L, "31", "40") U2_STEP_D(O, L, "41", "50") \
+    U2_STEP_D(O, L, "51", "60") U2_STEP_D(O, L, "61", "70") U2_STEP_D(O, L, "71", "80") U2_LAST_D(O, L, "81", "90") \
+    U2_SIDE_D(O, L, "20", "21") U2_SIDE_D(O, L, "30", "31") U2_SIDE_D(O, L, "40", "41") U2_SIDE_D(O, L, "50", "51") \
+    U2_SIDE_D(O, L, "60", "61") U2_SIDE_D(O, L, "70", "71") U2_SIDE_D(O, L, "80", "81") U2_SIDE_LAST_D(O, L, "90") "7:\n"
+#define U2_LOOP4_D(O, L) \
+    U2_STEP_D(O, L, "1", "20") U2_STEP_D(O, L, "21", "30") U2_STEP_D(O, L, "31", "40") U2_LAST_D(O, L, "41", "50") \
+    U2_SIDE_D(O, L, "20", "21") U2_SIDE_D(O, L, "30", "31") U2_SIDE_D(O, L, "40", "41") U2_SIDE_LAST_D(O, L, "50") "7:\n"
+#else
+#define U2_ENC_ENTRY_D ""
+#define U2_ENC_TOP_D U2_ENC_TOP_D_FIX U2_ENC_SLICES_D("s_cselect_b32 s41, 0, s75\n") U2_ENC_TOP_D_L2
+#define U2_STEP_D(ORDER, LSHR) U2_ENC_TOP_D U2_ENC_MID_D U2_ENC_BOT_D(U2_ENC_WORD2_D, ORDER, LSHR, "", "s_cbranch_scc0 7f\n")
+#define U2_LAST_D(ORDER, LSHR) U2_ENC_TOP_D U2_ENC_MID_D U2_ENC_BOT_D(U2_ENC_WORD2_D, ORDER, LSHR, U2_RING_CHECK, "s_cbranch_scc1 1b\n")
+#define U2_LOOP8_D(O, L) "1:\n" U2_STEP_D(O, L) U2_STEP_D(O, L) U2_STEP_D(O, L) U2_STEP_D(O, L) U2_STEP_D(O, L) U2_STEP_D(O, L) U2_STEP_D(O, L) U2_LAST_D(O, L) "7:\n"
+#define U2_LOOP4_D(O, L) "1:\n" U2_STEP_D(O, L) U2_STEP_D(O, L) U2_STEP_D(O, L) U2_LAST_D(O, L) "7:\n"
+#endif
 
 // store order-ring lanes [0, s72) at order[s87 ...]; s87 += s72
 #define U2_ORDER_FLUSH \
@@ -739,14 +798,8 @@ __global__ void __launch_bounds__(64) k_roc_encode_u2(RocEncArgs a, const U2Div 
               "s97", "s98", "s99")
         if (dense) {
             // (eight / four copies and the ring test in the last one, like the bitmap bodies)
-#define U2_STEP_D(ORDER, LSHR) U2_ENC_TOP_D U2_ENC_MID_D U2_ENC_BOT_D(ORDER, LSHR, "", "s_cbranch_scc0 7f\n")
-#define U2_LAST_D(ORDER, LSHR) U2_ENC_TOP_D U2_ENC_MID_D U2_ENC_BOT_D(ORDER, LSHR, U2_RING_CHECK, "s_cbranch_scc1 1b\n")
-            if (WANT_ORDER) U2_ENC_ASM(U2_ENC_ENTRY "1:\n" U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "") U2_STEP_D(U2_ENC_ORDER, "")
-                                       U2_LAST_D(U2_ENC_ORDER, "") "7:\n" U2_ENC_OUTER(U2_ORDER_FLUSH));
-            else U2_ENC_ASM(U2_ENC_ENTRY "1:\n" U2_STEP_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") U2_STEP_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") U2_STEP_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n")
-                            U2_LAST_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") "7:\n" U2_ENC_OUTER(""));
-#undef U2_STEP_D
-#undef U2_LAST_D
+            if (WANT_ORDER) U2_ENC_ASM(U2_ENC_ENTRY U2_ENC_ENTRY_D U2_LOOP8_D(U2_ENC_ORDER, "") U2_ENC_OUTER(U2_ORDER_FLUSH));
+            else U2_ENC_ASM(U2_ENC_ENTRY U2_ENC_ENTRY_D U2_LOOP4_D("", "s_lshr_b64 s[98:99], s[58:59], 31\n") U2_ENC_OUTER(""));
         } else if (U::G == 4u) {
             // four steps per loop iteration: the taken branch at the end of a step costs ~6 cycles of instruction-buffer refill
 #define U2_STEP_X(ORDER, LSHR) U2_ENC_TOP_NL U2_ENC_MID_G4 U2_ENC_SLICE1_G4 U2_ENC_L3_G4 U2_ENC_BOT_T(ORDER, LSHR, "", "s_cbranch_scc0 7f\n")
