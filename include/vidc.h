@@ -891,9 +891,51 @@ int vidc_ivf_probe_dev(vidc_ctx *ctx, uint64_t nlist, const float *d_centroids, 
  * LDS.  1024 * (round_up(d / M, 4) + 5) bytes: 13312 at d / M = 8, 136192 at 128.  No scratch, no context scratch.
  * Residency.  Enqueued on the context's stream; the call waits for its kernel.  vidc_ctx_d2h_bytes does not move.
  *   vidc_ctx_last_kernel_ms is the kernel's time.
- * Not here.  Sub-quantisers of other than 8 bits; inner product; d / M > 128; k-means; fusing the coarse assignment. */
+ * Not here.  Sub-quantisers of other than 8 bits; inner product; d / M > 128; fusing the coarse assignment. */
 int vidc_ivf_pq_encode_dev(vidc_ctx *ctx, uint64_t n, const float *d_x, uint32_t d, uint32_t M, const float *d_pq, uint64_t nlist,
                            const float *d_centroids, const int64_t *d_assign, uint8_t *d_codes);
+
+/* ---------------------------------------------------- one Lloyd k-means iteration on the device (float32 MFMA, deterministic) */
+/* What trains the centroids and the codebooks the sections above read: one assignment and one update, batched over G independent
+ * groups of columns.  d_x: device float32 [n, ld]; group g (0 <= g < G) clusters the columns [g * dsub, (g + 1) * dsub) of every row:
+ * the coarse quantiser is G = 1, dsub = ld = d, the PQ codebooks are G = M, dsub = d / M, ld = d.  d_c_in, d_c_out: device float32
+ * [G, k, dsub] (for k = 256 the d_pq of the encoder and the d_codebooks of the scans); d_c_out must not alias d_c_in.  d_assign:
+ * device int32 [G, n], may be NULL; d_counts: device uint32 [G, k], may be NULL.  Every element of each given output is written and
+ * nothing outside it; inputs are not changed.
+ *
+ * Assignment.  assign[g][i] is the smallest j that minimises the computed score s = fmaf(-2, x_g[i].c[g][j], |c[g][j]|^2): the score
+ *   and the tie rule of vidc_ivf_pq_encode_dev.  |c|^2 is summed with fmaf in component order, the dot product is float32 in an order
+ *   that depends on dsub alone.  Where every partial sum is an integer below 2^24 the result is the float64 argmin with first-index
+ *   ties; on float data the chosen centroid's squared distance is within 2 (dsub + 4) 2^-24 (|x| + max |c|)^2 of the smallest.  (A
+ *   row none of whose scores is finite is assigned 0.)
+ * Update.  The members of (g, j) are the points with assign[g][i] == j in ascending i, cut by rank into chunks of 256 consecutive
+ *   members.  A chunk's partial is the sequential float32 sum (from +0) of its rows in member order, the cluster sum the sequential
+ *   float32 sum (from +0) of the partials in chunk order, c_out[g][j] = sum / (float)count, IEEE-rounded; count == 0 copies
+ *   c_in[g][j] bit for bit.  No float atomic and no atomic-decided position enters a value: the same inputs give the same bits on
+ *   every cut and every context.
+ * Status.  VIDC_ERR_INVALID before any device work, nothing written: NULL context; NULL d_x, d_c_in or d_c_out with n > 0; G == 0;
+ *   k == 0; dsub outside 1 .. 2048; G * dsub > ld; G * k > 2^24; n >= 2^32; d_c_out == d_c_in.  n == 0: c_out = c_in, counts zero,
+ *   VIDC_OK.
+ * What runs.  k_kmeans_norms (|c|^2).  k_kmeans_assign: a workgroup of four wavefronts per (group, piece of the point range), blocks
+ *   of 128 points, 32 rows a wavefront; points go from global memory straight into v_mfma_f32_16x16x4_f32 operands; the centroids of
+ *   a group are held whole in LDS where k * (round_up(dsub, 4) + 4) * 4 <= 65536 and stream through two staging buffers in tiles of
+ *   128 centroids x 32 components otherwise; accumulators stay in registers across the chunks of a tile; a lane keeps a running
+ *   (score, j) best across all tiles and one four-step butterfly per row ends it.  Members: keys g * k + j, the stable 8-bit LSD
+ *   radix sort of the append calls, bounds by binary search.  k_kmeans_partial: lanes over components (a lane owns 4 with 16-byte
+ *   loads where dsub % 4 == 0, ld % 4 == 0 and d_x is 16-byte aligned, else 1; up to 32 such slots a wavefront serves
+ *   64 / bit_ceil(slots) chunks side by side, beyond that one chunk in ceil(slots / 64) passes), rows added strictly in member order.
+ *   k_kmeans_finish: per (g, j), partials in chunk order, the division, the counts.
+ * LDS.  k * (round_up(dsub, 4) + 4) * 4 bytes held whole (12288 at k = 256, dsub = 8; 36864 at dsub = 32), 36864 streamed.
+ * Scratch.  From the context's block cache.  4 G k (norms) + 4 G n (only where d_assign is NULL), and for a batch of gb groups
+ *   (gb = G unless G * n > 2^26; P = gb * n, L = gb * k): 16 P (keys, pair numbers and their double buffers) + 3072 ceil(P / 1024) + 8
+ *   (digit histograms) + 16 (L + 1) (bounds, chunk counts, chunk offsets) + 8 (P / 256 + L + 1) (chunk table) +
+ *   4 dsub (P / 256 + L) (partials) bytes.
+ * Residency.  Enqueued on the context's stream; the call waits for its kernels.  vidc_ctx_d2h_bytes does not move.
+ *   vidc_ctx_last_kernel_ms is the kernels' time.
+ * Not here.  An objective value; Faiss's splitting of empty clusters; k-means++ initialisation; inner product; fp16 passes; fusing
+ *   assignment and update; the Faiss adapter. */
+int vidc_ivf_kmeans_step_dev(vidc_ctx *ctx, uint64_t n, const float *d_x, uint32_t ld, uint32_t G, uint32_t dsub, uint32_t k,
+                             const float *d_c_in, float *d_c_out, int32_t *d_assign, uint32_t *d_counts);
 
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a

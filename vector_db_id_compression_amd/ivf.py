@@ -114,6 +114,8 @@ class IVFIndex:
         self.coarse_device = False
         # True: PQ codes (d / M <= 128) come from vidc_ivf_pq_encode_dev (ivf_encode.py), not torch
         self.pq_device = False
+        # True: train takes centroids and codebooks from vidc_ivf_kmeans_step_dev (ivf_train.py), not torch
+        self.train_device = False
 
     # -- build
     def train(self, xt):
@@ -123,13 +125,21 @@ class IVFIndex:
             g = torch.Generator(device="cpu")
             g.manual_seed(99)
             xt = xt[torch.randperm(xt.shape[0], generator=g)[:200_000].to(xt.device)]
-        self.centroids = _kmeans(xt, self.nlist)
+        if self.train_device:
+            from . import ivf_train
+
+            self.centroids = ivf_train.kmeans_device(xt, self.nlist)
+        else:
+            self.centroids = _kmeans(xt, self.nlist)
         if self.M:
             dsub = self.d // self.M
             assert dsub * self.M == self.d
             if self.by_residual:
                 xt = xt - self.centroids[_assign(xt, self.centroids)]
-            self.pq = torch.stack([_kmeans(xt[:, m * dsub:(m + 1) * dsub], 256, seed=7 + m) for m in range(self.M)])
+            if self.train_device:
+                self.pq = ivf_train.pq_train_device(xt, self.M)
+                return
+            self.pq =torch.stack([_kmeans(xt[:, m * dsub:(m + 1) * dsub], 256, seed=7 + m) for m in range(self.M)])
 
     def _encode_dev(self, x, assign=None):
         """codes of x as a uint8 CUDA tensor [n, code_size]; assign: the list of every row (by_residual encodes x - centroids[assign])"""

@@ -6,7 +6,8 @@ kernel -- the step IVFIndex._encode_dev does otherwise with M calls of torch.cdi
     codes = ivf_encode.encode_device(index, x, assign)               # over an IVFIndex (raw or by_residual)
 
 IVFIndex.pq_device = True makes add (and everything else that goes through _encode_dev) take its codes from here while
-d / M <= 128; above it Python stays with torch.  Sub-quantisers of other than 8 bits, inner product and k-means are out of scope.
+d / M <= 128; above it Python stays with torch.  Sub-quantisers of other than 8 bits and inner product are out of scope; the
+codebooks themselves come from ivf_train.py.
 """
 import numpy as np
 
