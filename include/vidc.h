@@ -937,6 +937,57 @@ int vidc_ivf_pq_encode_dev(vidc_ctx *ctx, uint64_t n, const float *d_x, uint32_t
 int vidc_ivf_kmeans_step_dev(vidc_ctx *ctx, uint64_t n, const float *d_x, uint32_t ld, uint32_t G, uint32_t dsub, uint32_t k,
                              const float *d_c_in, float *d_c_out, int32_t *d_assign, uint32_t *d_counts);
 
+/* ---------------------------------------------------- PQ sub-quantisers of 1 to 12 bits: packed codes in the encoder and the scan */
+/* IVF<n>,PQ<M>x<nbits> (PQ8x10: eight sub-quantisers of 10 bits, an 80-bit code in 10 bytes), raw and by_residual.  The 8-bit calls
+ * above keep their signatures and their refusals; these two take nbits.
+ *
+ * The layout.  ksub = 2^nbits, code_size = ceil(M * nbits / 8).  A code row is one little-endian bit string: sub-quantiser m occupies
+ *   the bits [m * nbits, (m + 1) * nbits), least significant bit first; bit i of the row is bit i % 8 of byte i / 8; the pad bits of
+ *   the last byte are 0.  Codebooks are float32 [M, ksub, d / M].  At nbits == 8 this is the M bytes of the calls above.  This is the
+ *   layout of Faiss's generic PQ encoder and decoder AS WRITTEN FROM MEMORY OF THE FAISS SOURCE: Faiss was not at hand to check
+ *   against, so the layout is pinned by the numpy model tests/ivf_pqbits_ref.py (pack / unpack) and a known row (M = 3, nbits = 10,
+ *   fields 1, 2, 3 -> bytes 01 08 30 00).
+ *
+ * vidc_ivf_pq_encode_bits_dev.  d_x: device float32 [n, d]; d_pq: device float32 [M, ksub, d / M]; d_codes: device uint8
+ *   [n, code_size], tight.  d_centroids == NULL is raw PQ (nlist and d_assign are ignored); otherwise the code is that of
+ *   r = x[i] - centroids[assign[i]].  Field m of row i is the smallest j that minimises fmaf(-2, r.c_j, |c_j|^2) over the ksub
+ *   codewords: the score, the tie rule and the float32 MFMA products of vidc_ivf_pq_encode_dev, with its accuracy statement.  A row
+ *   whose assign is outside [0, nlist) gets code_size zero bytes.  Exactly n * code_size bytes are written.  The result depends on the
+ *   inputs alone, not on the context or on how the batch was cut.
+ *   What runs.  k_pqbits_norms; k_ivf_pqbits_argmin, the form of k_kmeans_assign (the codebook of m held whole in LDS where
+ *   ksub * (round_up(d / M, 4) + 4) * 4 <= 65536, else streamed through two staging buffers in tiles of 128 codewords; vectors
+ *   straight into v_mfma_f32_16x16x4_f32 operands; a running (score, j) per lane, one 16-lane butterfly per row), which writes the
+ *   winning index as uint16 [n, M] to context scratch; k_pqbits_pack, a thread per output byte (sub-quantisers share bytes wherever
+ *   nbits % 8 != 0, so no (m, piece) item stores code bytes; no atomics).  Scratch: 4 M ksub + 2 n M bytes of the context's cache.
+ *   Status.  The refusals of vidc_ivf_pq_encode_dev (d / M <= 128 among them), and nbits outside 1 .. 12.
+ *
+ * vidc_ivf_scan_pqbits_dev.  The top-k scan of vidc_ivf_scan_dev / vidc_ivf_scan_residual_dev over such codes: d_codes device uint8
+ *   [ntotal, code_size], d_codebooks as d_pq.  d_centroids == NULL: raw PQ, one table per query.  Otherwise residual PQ: a table per
+ *   (query, probed list that is not empty) from r = xq - centroids[l].  entry(m, c) = sum over the d / M components, in order, of
+ *   (v_i - codebook[m][c]_i)^2 in float32 (the PQ8 entry over ksub codewords); distance = the sum of entry(m, field_m) in m order.
+ *   Probe rules, duplicate rule, clamp of a list range, key, order by (distance, label), padding, d_stats, the cut S and the merge are
+ *   those of the 8-bit calls, unchanged.
+ *   What runs.  k_ivf_scan_pqbits, a wavefront per (query, piece).  The 64 code rows of a trip are one span of 64 * code_size bytes on
+ *   no particular boundary: the wavefront copies the aligned 16-byte chunks that cover it into LDS (the first and last chunk of the
+ *   array are put together from aligned words and guarded bytes: nothing outside [d_codes, d_codes + ntotal * code_size) is read) and
+ *   each lane takes its M fields through a 64-bit window.  The table build keeps four entries of a lane in flight from ksub = 256 on;
+ *   an entry's value does not depend on the build.  k_ivf_merge behind a cut call.
+ *   LDS.  16 k + 768 (pools) + round16(4 nprobe) + round16(4 d) (twice with centroids) + round16(64 code_size + 32) + 4 M ksub bytes:
+ *   35616 at PQ8x10 residual, d = 128, k = 20, nprobe = 16 (four wavefronts a compute unit).
+ *   Status.  The refusals of the 8-bit scans; nbits outside 1 .. 12; d % M != 0; an LDS size above 163840 bytes (160 KB: the error
+ *   text names the limit; M = 64 at 10 bits is refused, M * ksub = 32768 passes).  VIDC_ERR_INVALID before any device work, nothing
+ *   written.
+ * Residency.  Enqueued on the context's stream; the calls wait for their kernels.  vidc_ctx_d2h_bytes does not move.
+ *   vidc_ctx_last_kernel_ms is the kernels' time.
+ * Not here.  Range search over these codes: the six range calls take no nbits and read one byte a sub-quantiser, so they cannot tell
+ *   and must not be given a packed array (the Python layer refuses such an index); nbits above 12; inner product; precomputed
+ *   tables; the Faiss adapter; sharded containers; any change to the 8-bit kernels. */
+int vidc_ivf_pq_encode_bits_dev(vidc_ctx *ctx, uint64_t n, const float *d_x, uint32_t d, uint32_t M, uint32_t nbits, const float *d_pq,
+                                uint64_t nlist, const float *d_centroids, const int64_t *d_assign, uint8_t *d_codes);
+int vidc_ivf_scan_pqbits_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes, uint32_t d,
+                             uint32_t M, uint32_t nbits, const float *d_codebooks, const float *d_centroids, uint64_t nq, const float *d_xq,
+                             uint32_t nprobe, const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

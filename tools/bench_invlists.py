@@ -33,6 +33,9 @@ def parse_index(d, index_str):
     if code == "Flat":
         return IVFIndex(d, nlist, "Flat")
     assert code.startswith("PQ")
+    if "x" in code:  # PQ8x10: M sub-quantisers of nbits bits, packed (the encoder is the device's)
+        M, nbits = code[2:].split("x")
+        return IVFIndex(d, nlist, ("PQ", int(M), int(nbits)))
     return IVFIndex(d, nlist, ("PQ", int(code[2:].replace("np", ""))))
 
 

@@ -7,8 +7,9 @@ It reproduces the call pattern the reference exercises through Faiss (SURVEY.md 
                                      by one (`get_single_id`, custom_invlists_impl.cpp:466-475) or per touched list
                                      (`get_ids`, :477-525) -- here as ONE batched device decode
 The vector side (k-means, flat / PQ codes, distance scan) is plain torch: it is harness plumbing, not the
-product.  Codes: "Flat" (float32 bytes) or ("PQ", M) with 8-bit sub-quantizers (PQ4np / PQ16 style); by_residual=True makes the PQ
-code that of (vector - its list's centroid), as faiss.index_factory(d, "IVF<n>,PQ<M>") does.
+product.  Codes: "Flat" (float32 bytes), ("PQ", M) with 8-bit sub-quantizers (PQ4np / PQ16 style) or ("PQ", M, nbits) with packed
+sub-quantizers of 1 .. 12 bits (PQ8x10 style: encoder and scan_device are the device's, include/vidc.h); by_residual=True makes the
+PQ code that of (vector - its list's centroid), as faiss.index_factory(d, "IVF<n>,PQ<M>") does.
 """
 import numpy as np
 
@@ -103,9 +104,13 @@ class IVFIndex:
         self.nprobe = 1
         self.parallel_mode = 0
         self.centroids = None
-        self.pq = None  # [M, 256, dsub]
+        self.pq = None  # [M, 2^nbits, dsub]
         self.M = code[1] if isinstance(code, tuple) else 0
-        self.code_size = 4 * self.d if code == "Flat" else self.M
+        self.packed = isinstance(code, tuple) and len(code) == 3  # ("PQ", M, nbits): one bit string a row, ceil(M * nbits / 8) bytes
+        self.nbits = int(code[2]) if self.packed else 8
+        if not 1 <= self.nbits <= 12:
+            raise ValueError("(\"PQ\", M, nbits) needs 1 <= nbits <= 12")
+        self.code_size = 4 * self.d if code == "Flat" else ((self.M * self.nbits + 7) // 8 if self.packed else self.M)
         self.invlists = ArrayInvertedLists(self.nlist, self.code_size)
         self.ntotal = 0
         self._next_id = 0  # vectors ever added: ids handed out by add never repeat, also after remove_ids
@@ -137,16 +142,16 @@ class IVFIndex:
             if self.by_residual:
                 xt = xt - self.centroids[_assign(xt, self.centroids)]
             if self.train_device:
-                self.pq = ivf_train.pq_train_device(xt, self.M)
+                self.pq = ivf_train.pq_train_device(xt, self.M, ksub=1 << self.nbits)
                 return
-            self.pq =torch.stack([_kmeans(xt[:, m * dsub:(m + 1) * dsub], 256, seed=7 + m) for m in range(self.M)])
+            self.pq =torch.stack([_kmeans(xt[:, m * dsub:(m + 1) * dsub], 1 << self.nbits, seed=7 + m) for m in range(self.M)])
 
     def _encode_dev(self, x, assign=None):
         """codes of x as a uint8 CUDA tensor [n, code_size]; assign: the list of every row (by_residual encodes x - centroids[assign])"""
         torch = _torch()
         if not self.M:
             return x.contiguous().view(torch.uint8).reshape(x.shape[0], 4 * self.d)
-        if self.pq_device and self.d // self.M <= 128:
+        if self.packed or (self.pq_device and self.d // self.M <= 128):  # (packed codes have no torch encoder)
             from . import ivf_encode
 
             return ivf_encode.encode_device(self, x, assign)
@@ -328,6 +333,12 @@ class IVFIndex:
         if not self.M:
             return codes.contiguous().view(torch.float32).reshape(-1, self.d)
         dsub = self.d // self.M
+        if self.packed:  # field m: the bits [m * nbits, (m + 1) * nbits) of the row's little-endian bit string
+            wide = torch.nn.functional.pad(codes, (0, 2)).to(torch.int32)
+            at = [m * self.nbits for m in range(self.M)]
+            win = [wide[:, b >> 3] | (wide[:, (b >> 3) + 1] << 8) | (wide[:, (b >> 3) + 2] << 16) for b in at]
+            fields = [(w >> (b & 7)) & ((1 << self.nbits) - 1) for w, b in zip(win, at)]
+            return torch.cat([self.pq[m][fields[m].long()] for m in range(self.M)], 1).reshape(-1, dsub * self.M)
         parts = [self.pq[m][codes[:, m].long()] for m in range(self.M)]
         return torch.cat(parts, 1).reshape(-1, dsub * self.M)
 
@@ -379,7 +390,7 @@ class IVFIndex:
         offset) as CUDA tensors, +inf / -1 padded, ascending in (distance, label).  probes: an int64 [nq, nprobe] CUDA tensor of list
         numbers, used as it is (-1 = no list); None picks them on the device with the cdist + topk of _scan.  Works over the codes of
         a compressed container and of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the latter through
-        vidc_ivf_scan_residual_dev).  Runs on torch's current stream."""
+        vidc_ivf_scan_residual_dev), and for ("PQ", M, nbits) through vidc_ivf_scan_pqbits_dev.  Runs on torch's current stream."""
         from . import _lib
 
         torch = _torch()
@@ -406,6 +417,13 @@ class IVFIndex:
         ptr = _lib.ptr
         pq = self.pq.to(torch.float32).contiguous() if self.M else None
         ctx = _lib.default_context()
+        if self.packed:
+            cent = self.centroids.to(torch.float32).contiguous() if self.by_residual else None
+            _lib.check(_lib.lib().vidc_ivf_scan_pqbits_dev(
+                ctx.h, self.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None, self.d, self.M, self.nbits, ptr(pq),
+                ptr(cent) if self.by_residual else None, nq, ptr(xq) if nq else None, int(probes.shape[1]),
+                ptr(probes) if probes.numel() else None, k, ptr(D) if D.numel() else None, ptr(labels) if labels.numel() else None, None))
+            return D, labels
         if self.by_residual:
             cent = self.centroids.to(torch.float32).contiguous()
             _lib.check(_lib.lib().vidc_ivf_scan_residual_dev(

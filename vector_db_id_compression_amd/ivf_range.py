@@ -7,8 +7,9 @@ deferred id decoding -- every stored vector of the probed lists closer than a ra
 Query q's results are D[lims[q]:lims[q + 1]], in probe-row order and then offset order (not sorted by distance, as in Faiss).  A
 result is a candidate whose squared L2 distance is strictly below the radius.  Works over the codes of a compressed container and
 of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the two *_residual_dev calls).  The only host traffic is the
-total (8 bytes) between the two passes: the output is allocated from it.  Per-query radii, inner product and sharded containers are
-out of scope.
+total (8 bytes) between the two passes: the output is allocated from it.  Per-query radii, inner product, sharded containers and the
+packed codes of ("PQ", M, nbits) are out of scope: the range calls take no nbits and read one byte a sub-quantiser, so such an index
+is refused here, before any device call.
 """
 import ctypes as C
 
@@ -28,6 +29,8 @@ def range_scan_device(index, xq, radius, probes=None):
     of list numbers, used as it is (-1 = no list, a repeated list counts once); None picks them on the device with the cdist + topk
     of IVFIndex.scan_device.  Runs count, one 8-byte read-back of the total, the allocation, fill, on torch's current stream."""
     torch = _torch()
+    if getattr(index, "packed", False):  # (the range kernels would walk ceil(M * nbits / 8)-byte rows as M bytes: refused up here)
+        raise ValueError("range search over (\"PQ\", M, nbits) codes is not supported: the range calls read 8-bit codes only")
     if not torch.cuda.is_available():
         raise VidcError("no HIP device: range_scan_device needs an MI355X (there is no CPU fallback)")
     if not (isinstance(xq, torch.Tensor) and xq.is_cuda):

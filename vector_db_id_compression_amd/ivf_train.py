@@ -3,7 +3,7 @@ groups of columns, with a deterministic result -- the step IVFIndex.train does o
 
     c_new, assign, counts = ivf_train.kmeans_step_device(x, c, groups=1)   # c [G, k, dsub] (or [k, d] for one group)
     centroids = ivf_train.kmeans_device(x, k, iters=10, seed=123)          # [k, d]; the initial rows of ivf._kmeans
-    pq = ivf_train.pq_train_device(x, M, iters=10)                         # [M, 256, d / M]; all sub-quantisers advance together
+    pq = ivf_train.pq_train_device(x, M, iters=10, ksub=256)               # [M, ksub, d / M]; all sub-quantisers advance together
 
 IVFIndex.train_device = True makes train take its centroids and its codebooks from here.  An objective value, splitting of empty
 clusters, k-means++ and inner product are out of scope.
@@ -74,8 +74,8 @@ def kmeans_device(x, k, iters=10, seed=123):
     return c
 
 
-def pq_train_device(x, M, iters=10):
-    """x [n, d], d a multiple of M -> codebooks [M, 256, d / M]: sub-quantiser m starts from seed 7 + m, one step call per iteration
+def pq_train_device(x, M, iters=10, ksub=256):
+    """x [n, d], d a multiple of M -> codebooks [M, ksub, d / M]: sub-quantiser m starts from seed 7 + m, one step call per iteration
     advances all M"""
     torch = _torch()
     x = _f32(x)
@@ -83,7 +83,7 @@ def pq_train_device(x, M, iters=10):
     if M < 1 or d % M:
         raise ValueError("d must be a multiple of M")
     dsub = d // M
-    pq = torch.stack([_initial_rows(x[:, m * dsub:(m + 1) * dsub], 256, 7 + m) for m in range(M)]).contiguous()
+    pq = torch.stack([_initial_rows(x[:, m * dsub:(m + 1) * dsub], ksub, 7 + m) for m in range(M)]).contiguous()
     for _ in range(iters):
         pq = kmeans_step_device(x, pq, groups=M)[0]
     return pq
