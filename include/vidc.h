@@ -988,6 +988,53 @@ int vidc_ivf_scan_pqbits_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_of
                              uint32_t M, uint32_t nbits, const float *d_codebooks, const float *d_centroids, uint64_t nq, const float *d_xq,
                              uint32_t nprobe, const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
 
+/* ---------------------------------------------------- additive-quantiser codes (RQ<M>x8_Nfloat) in the IVF scan */
+/* IVF<n>,RQ<M>x8_Nfloat (RQ8x8_Nfloat: eight residual-quantiser stages of 8 bits and a float32 norm, 12 bytes), raw and by_residual.
+ *
+ * The layout.  code_size = M + 4.  Bytes 0 .. M - 1 of a row are the stage indices c_0 .. c_{M-1}; bytes M .. M + 3 are the
+ *   little-endian float32 norm n = |y|^2 of the stored vector y (the sum of the M codewords, plus the list's centroid where the
+ *   index is by_residual).  Codebooks are float32 [M, 256, d]: every codeword spans all d components, so there is no d % M
+ *   condition.  This is the layout of Faiss's additive quantisers with Search_type_t ST_norm_float AS WRITTEN FROM MEMORY OF THE
+ *   FAISS SOURCE: Faiss was not at hand to check against, so the layout is pinned by the numpy model tests/ivf_aq_ref.py (pack /
+ *   unpack) and a known row (M = 2, indices 1, 2, norm 1.0 -> bytes 01 02 00 00 80 3f).
+ *
+ * vidc_ivf_aq_lut_dev.  d_codebooks: device float32 [M, 256, d]; d_xq: device float32 [nq, d]; d_lut: device float32 [nq, M, 256],
+ *   tight.  lut[q][m][j] = <xq[q], codebooks[m][j]> in float32: the products are accumulated over the components in ascending
+ *   order, four an instruction (v_mfma_f32_16x16x4_f32), on one accumulator chain.  An entry's bits depend on the two vectors alone:
+ *   not on nq, on the query's place in the batch, on the context or on a tile.  No array needs an alignment.
+ *   What runs.  k_ivf_aq_lut, one GEMM of nq x (M * 256) x d: a workgroup of four wavefronts per tile of 64 queries x 128 entries,
+ *   32 components of both operands staged in LDS per pass (27648 bytes), eight accumulator quads a wavefront.
+ *   Status.  NULL codebooks, a NULL query or table array with nq > 0, d outside 1 .. 2048, M outside 1 .. 64, nq >= 2^32:
+ *   VIDC_ERR_INVALID before any device work, nothing written; the error text starts with "ivf aq lut:".
+ *
+ * vidc_ivf_scan_aq_dev.  The top-k scan of vidc_ivf_scan_dev over such codes: d_codes device uint8 [ntotal, code_size], on any byte
+ *   boundary.  The distance of the entry with indices c_0 .. c_{M-1} and stored norm n in list l:
+ *     t = lut[0][c_0] + ... + lut[M-1][c_{M-1}]     (float32, in m order, lut as above)
+ *     ip = cq + t, cq = <xq, centroids[l]>;  with d_centroids == NULL (codes of the raw vector) ip = t
+ *     v = fmaf(-2, ip, qn + n), qn = |xq|^2;  dist = v > 0 ? v : +0.0f
+ *   The last rule is a compare: a key is the raw bits of the distance, so a negative value, -0.0f or a NaN becomes +0.  qn and cq
+ *   come from one fixed reduction that depends on d alone, so every piece, chunk and context gets the same bits.  The stored norm
+ *   is read, never recomputed.  Probe rules, duplicate rule, clamp of a list range, key, order by (distance, label), padding,
+ *   d_stats, the cut S and the merge are those of vidc_ivf_scan_dev, unchanged.
+ *   What runs.  The queries go in chunks of max(16, floor(64 MiB / (1024 M)) rounded down to 16): per chunk k_ivf_aq_lut into
+ *   context scratch, then k_ivf_scan_aq, a wavefront per (query, piece), which copies its query's table into LDS (16-byte loads),
+ *   stages the 64 rows of a trip as the aligned 16-byte chunks that cover them (the first and last chunk of the array are put
+ *   together from aligned words and guarded bytes: nothing outside [d_codes, d_codes + ntotal * code_size) is read), walks a lane's
+ *   M index bytes through the table and takes its norm from LDS; k_ivf_merge behind a cut.  Results do not depend on the chunking.
+ *   LDS.  16 k + 768 (pools) + round16(4 nprobe) + round16(4 d) + round16(64 code_size + 32) + 1024 M bytes: 10656 at RQ8, d = 128,
+ *   k = 20, nprobe = 16 (fifteen wavefronts a compute unit); 87072 at the limits.
+ *   Scratch.  From the context's block cache: at most 64 MiB of tables, and the runs of a cut call.
+ *   Status.  The refusals of vidc_ivf_scan_dev (k, nprobe, d, ntotal, nlist, NULL arrays); M outside 1 .. 64; NULL codebooks;
+ *   nq >= 2^32.  VIDC_ERR_INVALID before any device work, nothing written; the error text starts with "ivf aq scan:".
+ * Residency.  Enqueued on the context's stream; the calls wait for their kernels.  vidc_ctx_d2h_bytes does not move.
+ *   vidc_ctx_last_kernel_ms is the kernels' time.
+ * Not here.  Range search over these codes (the Python layer refuses such an index); other norm encodings; stage widths other than
+ *   8 bits; inner product; beam-search encoding; k above 256; sharded containers; the Faiss adapter. */
+int vidc_ivf_aq_lut_dev(vidc_ctx *ctx, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, float *d_lut);
+int vidc_ivf_scan_aq_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes, uint32_t d,
+                         uint32_t M, const float *d_codebooks, const float *d_centroids, uint64_t nq, const float *d_xq, uint32_t nprobe,
+                         const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

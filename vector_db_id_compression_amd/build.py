@@ -22,11 +22,11 @@ HASH = LIB + ".srchash"
 LOCK = LIB + ".lock"
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
-# flags of single translation units.  ivf_probe.hip, ivf_pq_encode.hip, ivf_kmeans.hip and the two ivf_pqbits units are the float32
-# kernels: their arithmetic stays on the unpacked instructions
+# flags of single translation units.  ivf_probe.hip, ivf_pq_encode.hip, ivf_kmeans.hip, the two ivf_pqbits units and ivf_aq.hip are
+# the float32 kernels: their arithmetic stays on the unpacked instructions
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"ivf_probe.hip": NO_PACKED_FP32, "ivf_pq_encode.hip": NO_PACKED_FP32, "ivf_kmeans.hip": NO_PACKED_FP32,
-              "ivf_pqbits.hip": NO_PACKED_FP32, "ivf_pqbits_encode.hip": NO_PACKED_FP32}
+              "ivf_pqbits.hip": NO_PACKED_FP32, "ivf_pqbits_encode.hip": NO_PACKED_FP32, "ivf_aq.hip": NO_PACKED_FP32}
 
 
 def sources():

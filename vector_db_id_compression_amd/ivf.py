@@ -9,7 +9,8 @@ It reproduces the call pattern the reference exercises through Faiss (SURVEY.md 
 The vector side (k-means, flat / PQ codes, distance scan) is plain torch: it is harness plumbing, not the
 product.  Codes: "Flat" (float32 bytes), ("PQ", M) with 8-bit sub-quantizers (PQ4np / PQ16 style) or ("PQ", M, nbits) with packed
 sub-quantizers of 1 .. 12 bits (PQ8x10 style: encoder and scan_device are the device's, include/vidc.h); by_residual=True makes the
-PQ code that of (vector - its list's centroid), as faiss.index_factory(d, "IVF<n>,PQ<M>") does.
+PQ code that of (vector - its list's centroid), as faiss.index_factory(d, "IVF<n>,PQ<M>") does.  ("RQ", M) is the additive code
+RQ<M>x8_Nfloat (ivf_aq.py): M stage indices over codebooks [M, 256, d] and the float32 norm of the stored vector.
 """
 import numpy as np
 
@@ -107,10 +108,13 @@ class IVFIndex:
         self.pq = None  # [M, 2^nbits, dsub]
         self.M = code[1] if isinstance(code, tuple) else 0
         self.packed = isinstance(code, tuple) and len(code) == 3  # ("PQ", M, nbits): one bit string a row, ceil(M * nbits / 8) bytes
+        self.aq = isinstance(code, tuple) and code[0] == "RQ"  # ("RQ", M): M index bytes and a float32 norm a row (ivf_aq.py)
+        if self.aq and len(code) != 2:
+            raise ValueError("(\"RQ\", M) takes no third entry: the stages are 8 bits wide")
         self.nbits = int(code[2]) if self.packed else 8
         if not 1 <= self.nbits <= 12:
             raise ValueError("(\"PQ\", M, nbits) needs 1 <= nbits <= 12")
-        self.code_size = 4 * self.d if code == "Flat" else ((self.M * self.nbits + 7) // 8 if self.packed else self.M)
+        self.code_size = 4 * self.d if code == "Flat" else ((self.M * self.nbits + 7) // 8 if self.packed else self.M + 4 * self.aq)
         self.invlists = ArrayInvertedLists(self.nlist, self.code_size)
         self.ntotal = 0
         self._next_id = 0  # vectors ever added: ids handed out by add never repeat, also after remove_ids
@@ -136,7 +140,11 @@ class IVFIndex:
             self.centroids = ivf_train.kmeans_device(xt, self.nlist)
         else:
             self.centroids = _kmeans(xt, self.nlist)
-        if self.M:
+        if self.aq:
+            from . import ivf_aq
+
+            self.pq = ivf_aq.train(self, xt - self.centroids[_assign(xt, self.centroids)] if self.by_residual else xt)
+        elif self.M:
             dsub = self.d // self.M
             assert dsub * self.M == self.d
             if self.by_residual:
@@ -151,6 +159,10 @@ class IVFIndex:
         torch = _torch()
         if not self.M:
             return x.contiguous().view(torch.uint8).reshape(x.shape[0], 4 * self.d)
+        if self.aq:
+            from . import ivf_aq
+
+            return ivf_aq.encode(self, x, assign)
         if self.packed or (self.pq_device and self.d // self.M <= 128):  # (packed codes have no torch encoder)
             from . import ivf_encode
 
@@ -332,6 +344,10 @@ class IVFIndex:
         torch = _torch()
         if not self.M:
             return codes.contiguous().view(torch.float32).reshape(-1, self.d)
+        if self.aq:
+            from . import ivf_aq
+
+            return ivf_aq.decode(self, codes)
         dsub = self.d // self.M
         if self.packed:  # field m: the bits [m * nbits, (m + 1) * nbits) of the row's little-endian bit string
             wide = torch.nn.functional.pad(codes, (0, 2)).to(torch.int32)
@@ -390,7 +406,8 @@ class IVFIndex:
         offset) as CUDA tensors, +inf / -1 padded, ascending in (distance, label).  probes: an int64 [nq, nprobe] CUDA tensor of list
         numbers, used as it is (-1 = no list); None picks them on the device with the cdist + topk of _scan.  Works over the codes of
         a compressed container and of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the latter through
-        vidc_ivf_scan_residual_dev), and for ("PQ", M, nbits) through vidc_ivf_scan_pqbits_dev.  Runs on torch's current stream."""
+        vidc_ivf_scan_residual_dev), for ("PQ", M, nbits) through vidc_ivf_scan_pqbits_dev and for ("RQ", M) through
+        vidc_ivf_scan_aq_dev.  Runs on torch's current stream."""
         from . import _lib
 
         torch = _torch()
@@ -412,6 +429,10 @@ class IVFIndex:
         nq, k = int(xq.shape[0]), int(k)
         if not 0 <= k < 2 ** 32:
             raise ValueError("k is an unsigned 32-bit number")
+        if self.aq:
+            from . import ivf_aq
+
+            return ivf_aq.scan_device(self, xq, probes, k, off, codes)
         D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
         labels = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
         ptr = _lib.ptr

@@ -9,7 +9,7 @@ result is a candidate whose squared L2 distance is strictly below the radius.  W
 of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the two *_residual_dev calls).  The only host traffic is the
 total (8 bytes) between the two passes: the output is allocated from it.  Per-query radii, inner product, sharded containers and the
 packed codes of ("PQ", M, nbits) are out of scope: the range calls take no nbits and read one byte a sub-quantiser, so such an index
-is refused here, before any device call.
+is refused here, before any device call; so is an index of additive ("RQ", M) codes, whose rows carry a norm.
 """
 import ctypes as C
 
@@ -31,6 +31,8 @@ def range_scan_device(index, xq, radius, probes=None):
     torch = _torch()
     if getattr(index, "packed", False):  # (the range kernels would walk ceil(M * nbits / 8)-byte rows as M bytes: refused up here)
         raise ValueError("range search over (\"PQ\", M, nbits) codes is not supported: the range calls read 8-bit codes only")
+    if getattr(index, "aq", False):
+        raise ValueError("range search over (\"RQ\", M) codes is not supported: the range calls read PQ codes only")
     if not torch.cuda.is_available():
         raise VidcError("no HIP device: range_scan_device needs an MI355X (there is no CPU fallback)")
     if not (isinstance(xq, torch.Tensor) and xq.is_cuda):
