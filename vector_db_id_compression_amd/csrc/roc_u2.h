@@ -1160,12 +1160,14 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //   v38 address / v39 data of the row update  v54:57 table entry of the next block  v58 tmp
 //   (the bucket kernels, which keep their level-2 rows in registers: v3 4 * lane (+ the rows' start), v13 row, v58 v59 tmp,
 //   v64..v127 level-2 rows, s63 row[L2])
-//   s40 x  s43 L1  s44 L2  s45 entry  s46 x_hi  s47 g  s49 E1[L1]  s50:51 H  s52:53 H * nmax  s58:59 head  s60 sp
+//   s40 x  s43 L1  s44 L2  s45 entry  s46 x_hi  s47 g  s49 E1[L1]  s50:51 H (the bucket kernels and k_roc_decode_u2 built with
+//   U2_DEC_STEP bit 2 clear; with the bit set H stays in s58:59)  s52:53 H * nmax  s58:59 head  s60 sp
 //   (word-granular rows, U2_DEC_*_W: v3 16 - 64 * lane, v11 8 * lane, v12 lane == 0, v[34:35] row data, s44 w & 255, s[54:55] field ones)
 //   s61 lo  s62 lq  s64 rank (bucket kernels: below)  s65 tmp  s66:67 mask below b  s68 tmp  s69 t  s70 t_end  s71 limit  s72 tmp
 //   s73 2^p1 - 1  s74 2^p0 - 1  s75 nmax  s76 p0  s77 p1  s85 N0  s86 steps left at lane 0  s87 output index of lane 0
 //   s88:89 output pointer  s94:95 divisor table  s96:97 saved exec  s98 s99 tmp
-//   (k_roc_decode_u2 only, U2_DEC_TOP_P: s41 carried stack word  s42 its lane  s56 31 + p1  s57 s_bfe operand of x_lo  s63 p1 + p0)
+//   (k_roc_decode_u2 only, U2_DEC_TOP_P: s41 carried stack word  s42 its lane  s56 31 + p1  s57 s_bfe operand of x_lo  s63 p1 + p0;
+//    U2_DEC_TOP_Q: s62 is the lq of the step that starts next, H stays in s[58:59], s50 s51 unused)
 #ifdef U2_PROF  // the decode arm's probes (the encoder's U2P with registers the loop of k_roc_decode_u2 leaves alone: s78..s81; the
                 // bucket kernels, which share some of the probed macros, use those registers: k_roc_decode_b2 refuses a probed build)
 #define U2PD(i) "s_memtime s[78:79]\n s_waitcnt lgkmcnt(0)\n s_sub_u32 s81, s78, s80\n s_mov_b32 s80, s78\n v_add_u32 v" #i ", s81, v" #i "\n"
@@ -1259,14 +1261,22 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 //    preferred it by 0.4 .. 0.8 ns, profiles/r27_roc_decode_rows_lds.txt).
 //  * 65 instructions per step with four words per entry, 56 with one.  The 20-bit launch runs the one-word step on word-granular
 //    rows by default (U2_DEC_*_W below, 58 instructions); the four-word step stays as k_roc_decode_u2<20, false>.
+//  * ring traffic: the refill of the pops, the ring write and renormalisation of the index push and the read of the carried word
+//    run only in the steps that change the ring (U2_DEC_TOP_Q / U2_DEC_SIDE_Q below: seven instructions less on the quiet path,
+//    four steps in five of a 20-bit list; 58 -> 51, 65 -> 58, 56 -> 49; profiles/r51_roc_decode_ring_class.txt).
 // ---- build-time forms of the k_roc_decode_u2 step (tools/chain_u2.hip builds one binary per value; the library builds the default):
 //   bit 0  rank at the bit's lane (U2_DEC_RANK_W, U2_DEC_RANK_U_G1): the word was read as a broadcast, so v_mbcnt_lo / v_mbcnt_hi of it
 //          give lane L the number of its bits below L, and lane b = x & 63 holds the wanted rank: no mask of the bits below b
 //          (s_bfm_b64), no v_and of the two halves; E1[L1] rides on the addend of the first v_mbcnt, the read-out is v_readlane at x
 //          (the instruction takes six bits of its lane select).  0: the masked v_bcnt pair and v_readfirstlane.
 //   bit 1  one-branch slice pops (U2_DEC_TOP_P).  0: U2_DEC_TOP_L, the two pops with a refill test and a side path each.
+//   bit 2  ring traffic classified once (U2_DEC_TOP_Q, needs bit 1): a step whose refill and index push leave the ring as it was
+//          runs neither.  0: refill, ring write, renormalisation and carried-word read in every step.
 #ifndef U2_DEC_STEP
-#define U2_DEC_STEP 3
+#define U2_DEC_STEP 7
+#endif
+#if (U2_DEC_STEP & 4) && !(U2_DEC_STEP & 2)
+#error "U2_DEC_STEP bit 2 (classified ring traffic) is built on the one-branch pops of bit 1"
 #endif
 // ---- the two slice pops of the k_roc_decode_u2 step as ONE classified shift (csrc/u2_pops_ref.h is the same in plain C++ and
 // tests/u2_pops_test.cpp checks it against the two-pop sequence of codec.cpp:78-90).  With p1 = clamp(P - 16, 0, 16), p0 = min(P, 16)
@@ -1304,7 +1314,100 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_and_b32 s40, s58, s74\n" \
     "s_lshr_b64 s[58:59], s[58:59], s76\n" \
     "s_branch " LB "b\n"
-#if U2_DEC_STEP & 2
+// ---- the ring traffic of a step, classified once (U2_DEC_STEP bit 2; csrc/u2_dec_ring_ref.h is the same in plain C++ and
+// tests/u2_dec_ring_test.cpp checks it against the sequence above followed by the index push of codec.cpp:44-63).
+// With h = head' >> (p1 + p0) on the common path and lq = 2^31 / nmax of this step, the refill of U2_DEC_TOP_P and the index push of
+// U2_DEC_MID_* together do one of four things:
+//   h < lq                refill, no spill:   H = (h << 32) | w, sp - 1, w is the word below          LOUD
+//   lq <= h < 2^31        refill and spill:   the spill puts w back into the slot it came from: H = h, sp and w unchanged   QUIET
+//   2^31 <= h < lq 2^32   neither:            H = h, sp and w unchanged (the parent writes h_lo to slot sp, above the top)  QUIET
+//   h >= lq 2^32          spill, no refill:   H = h_hi, h_lo goes to slot sp, sp + 1, w = h_lo       LOUD
+// so a step is quiet iff lq <= h < lq 2^32, tested as "no borrow from h - lq" and "h_hi < lq": exact for every head' >= 2^31, every
+// w and every lq of nmax = 1 .. 65 536 (lq >= 2^15 > 0; h < 2^63 as p1 + p0 >= 1).  The test is two-sided on purpose: the fourth
+// class is empty while nmax <= 2^P (h_hi < 2^(31 - P) <= lq), but the loop also runs on multiset and imported streams, where a list
+// is longer than its universe and nothing bounds nmax by 2^P.
+// A quiet step runs no refill, no ring write, no renormalisation and no read of the carried word: H is h, in s[58:59], and the
+// multiply reads it there.  The loud classes and the slice-1 class leave for a side body behind the copies of the loop (one per
+// copy), which runs the parent's branch-free refill, index push and carried-word read and comes back in front of s_pack.
+//   s62 lq of the step that starts next: read in the previous step's vector block (lane t + 1 of v10; s69 is incremented in front of
+//       it), and by U2_DEC_ENTRY_U / the re-entry of U2_DEC_OUTER_U like s41, so every way into the loop has both.  The read of lane
+//       64 behind the last step of a block wraps to lane 0 of the old table: the block change reloads it from the new one.
+// Ring slots at or above sp keep whatever they held, since the quiet "neither" step no longer writes slot sp.  Nothing reads them:
+// ws_spill32 stores the 32 slots from lo and runs only while sp - lo > 56; ws_refill32 writes the slots of [lo - 32, lo), which are
+// free while sp - lo < 22; ws_pop / the generic steps and the exit's second half of the index push read slot sp - 1 and write slot
+// sp before sp moves over it; U2_DEC_FLUSH stores the OUTPUT ring v6, not the stack ring; the end test reads sp alone.
+#define U2_DEC_TOP_Q(LA, LB, LC) \
+    U2PD(130) U2PD(131) \
+    "s_lshr_b64 s[98:99], s[58:59], s56\n"            /* SCC = head' >= 2^(31 + p1): slice 1 does not refill */ \
+    "s_cbranch_scc0 " LA "f\n" \
+    "s_and_b32 s46, s58, s73\n"                        /* x_hi */ \
+    "s_bfe_u32 s40, s58, s57\n"                        /* x_lo */ \
+    "s_lshr_b64 s[58:59], s[58:59], s63\n"             /* both pops: h */ \
+    U2_DEC_QTEST(LC) \
+    LB ":\n" \
+    "s_pack_ll_b32_b16 s40, s40, s46\n"                /* x = x_hi : x_lo */ U2PD(132)
+#define U2_DEC_QTEST(LC)                               /* one branch; the form with a branch behind each compare was 2.6 .. 7.8 ns per step longer */ \
+    "s_sub_u32 s98, s58, s62\n" \
+    "s_subb_u32 s98, s59, 0\n"                         /* SCC = borrow of h - lq: h < lq */ \
+    "s_cselect_b32 s98, -1, s59\n" \
+    "s_cmp_ge_u32 s98, s62\n"                          /* ... or h_hi >= lq (lq <= 2^31 < 2^32 - 1) */ \
+    "s_cbranch_scc1 " LC "f\n"
+#define U2_DEC_SIDE_Q(LA, LB, LC, LD) \
+    LC ":\n"                                           /* common path, loud: the refill of U2_DEC_TOP_P ... */ \
+    "s_lshr_b64 s[98:99], s[58:59], 31\n" \
+    "s_cselect_b32 s59, s59, s58\n" \
+    "s_cselect_b32 s58, s58, s41\n" \
+    "s_addc_u32 s60, s60, -1\n" \
+    "s_branch " LD "f\n" \
+    LA ":\n"                                           /* head' < 2^(31 + p1): slice 1 refills, slice 0 cannot (U2_DEC_SIDE_P) */ \
+    "s_and_b32 s46, s58, s73\n" \
+    "s_lshr_b64 s[58:59], s[58:59], s77\n" \
+    "s_sub_u32 s60, s60, 1\n" \
+    "s_mov_b32 s59, s58\n" \
+    "s_mov_b32 s58, s41\n" \
+    "s_and_b32 s40, s58, s74\n" \
+    "s_lshr_b64 s[58:59], s[58:59], s76\n" \
+    LD ":\n"                                           /* ... and the index push (codec.cpp:44-63), H left in s[58:59] */ \
+    "s_and_b32 m0, s60, 63\n" \
+    "s_cmp_ge_u32 s59, s62\n" \
+    "v_writelane_b32 v5, s58, m0\n"                    /* the word, kept if H renormalises */ \
+    "s_cselect_b32 s58, s59, s58\n" \
+    "s_cselect_b32 s59, 0, s59\n" \
+    "s_addc_u32 s60, s60, 0\n" \
+    "s_sub_u32 s42, s60, 1\n" \
+    "v_readlane_b32 s41, v5, s42\n"                    /* the carried word of the next step */ \
+    "s_branch " LB "b\n"
+// the pieces of U2_DEC_MID_* / U2_DEC_RANK_* / U2_DEC_BOT_*_U that bit 2 takes out, moves or renames (bit 2 clear: the parent's text)
+#if U2_DEC_STEP & 4
+#define U2_DEC_M0_SP "s_mov_b32 m0, s69\n s_add_u32 s69, s69, 1\n"  /* m0 = t for the output ring; s69 = t + 1 from here on */
+#define U2_DEC_LQ_MID "v_readlane_b32 s62, v10, s69\n"              /* lq of the NEXT step (the read takes six bits of the lane) */
+#define U2_DEC_RING_WR ""
+#define U2_DEC_RENORM ""
+#define U2_DEC_HLO "s58"
+#define U2_DEC_HHI "s59"
+#define U2_DEC_M0_T ""
+#define U2_DEC_T_INC ""
+#else
+#define U2_DEC_M0_SP "s_and_b32 m0, s60, 63\n"
+#define U2_DEC_LQ_MID "v_readlane_b32 s62, v10, s69\n"              /* lq of this step */
+#define U2_DEC_RING_WR "v_writelane_b32 v5, s58, m0\n"              /* index push, first half (codec.cpp:44-63): the word, kept if H renormalises */
+#define U2_DEC_RENORM \
+    "s_cmp_ge_u32 s59, s62\n" \
+    "s_cselect_b32 s50, s59, s58\n" \
+    "s_cselect_b32 s51, 0, s59\n" \
+    "s_addc_u32 s60, s60, 0\n" U2PD(136)
+#define U2_DEC_HLO "s50"
+#define U2_DEC_HHI "s51"
+#define U2_DEC_M0_T "s_mov_b32 m0, s69\n"
+#define U2_DEC_T_INC "s_add_u32 s69, s69, 1\n"
+#endif
+#define U2_DEC_H_MUL \
+    "s_mul_i32 s52, " U2_DEC_HLO ", s75\n"             /* H * nmax */ \
+    "s_mul_hi_u32 s53, " U2_DEC_HLO ", s75\n" \
+    "s_mul_i32 s68, " U2_DEC_HHI ", s75\n" \
+    "s_add_u32 s53, s53, s68\n" \
+    U2_DEC_M0_T U2PD(137)
+#if (U2_DEC_STEP & 2) && !(U2_DEC_STEP & 4)
 #define U2_DEC_W_IDX "s_sub_u32 s42, s60, 1\n"         /* lane of the word the next pop returns (the read takes six bits of it) */
 #define U2_DEC_W_LOAD "v_readlane_b32 s41, v5, s42\n"
 #else
@@ -1323,23 +1426,16 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_lshr_b32 s43, s45, 6\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 63\n"                         /* L2 */ \
     BFM \
-    "s_and_b32 m0, s60, 63\n" U2PD(134) \
-    "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
+    U2_DEC_M0_SP U2PD(134) \
+    U2_DEC_LQ_MID \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
     "v_lshl_add_u32 v38, s43, 8, v11\n"                /* lane j: dword j of row L1 */ \
     "v_sub_u32 v39, s44, v2\n" \
     "v_lshrrev_b32 v39, 31, v39\n"                     /* 1 in lanes above L2, 0 elsewhere */ \
-    "v_writelane_b32 v5, s58, m0\n"                    /* index push, first half (codec.cpp:44-63): the word, kept if H renormalises */ U2PD(135) \
-    "s_cmp_ge_u32 s59, s62\n" \
-    "s_cselect_b32 s50, s59, s58\n" \
-    "s_cselect_b32 s51, 0, s59\n" \
-    "s_addc_u32 s60, s60, 0\n" U2PD(136) \
+    U2_DEC_RING_WR U2PD(135) \
+    U2_DEC_RENORM \
     U2_DEC_W_IDX \
-    "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
-    "s_mul_hi_u32 s53, s50, s75\n" \
-    "s_mul_i32 s68, s51, s75\n" \
-    "s_add_u32 s53, s53, s68\n" \
-    "s_mov_b32 m0, s69\n" U2PD(137)
+    U2_DEC_H_MUL
 #define U2_DEC_RANK_TAIL_U \
     U2_DEC_W_LOAD                                      /* w of the next step's pops: behind the ring write and the s_addc of U2_DEC_MID_U */ \
     U2_DEC_INS_ADDR \
@@ -1416,25 +1512,18 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_lshr_b32 s43, s45, 8\n"                         /* L1 */ \
     "s_and_b32 s44, s45, 255\n"                        /* word inside the block */ \
     U2_DEC_BFM \
-    "s_and_b32 m0, s60, 63\n" U2PD(134) \
-    "v_readlane_b32 s62, v10, s69\n"                   /* lq of this step */ \
+    U2_DEC_M0_SP U2PD(134) \
+    U2_DEC_LQ_MID \
     "v_readlane_b32 s49, v4, s43\n"                    /* E1[L1] */ \
     "v_lshl_add_u32 v38, s43, 9, v11\n"                /* lane j: u64 j of row L1 */ \
     "v_lshl_add_u32 v39, s44, 4, v3\n"                 /* 16 * (fields of the lane at or below the word), unclamped */ \
     "v_med3_i32 v39, v39, 0, 63\n" \
-    "v_writelane_b32 v5, s58, m0\n"                    /* index push, first half */ \
+    U2_DEC_RING_WR \
     "v_lshlrev_b64 v[34:35], v39, s[54:55]\n"          /* 1 in the fields above the word */ \
     "v_and_b32 v35, 0x7fffffff, v35\n"                 /* (the shift by 63 of a lane with no such field) */ U2PD(135) \
-    "s_cmp_ge_u32 s59, s62\n" \
-    "s_cselect_b32 s50, s59, s58\n" \
-    "s_cselect_b32 s51, 0, s59\n" \
-    "s_addc_u32 s60, s60, 0\n" U2PD(136) \
+    U2_DEC_RENORM \
     U2_DEC_W_IDX \
-    "s_mul_i32 s52, s50, s75\n"                        /* H * nmax */ \
-    "s_mul_hi_u32 s53, s50, s75\n" \
-    "s_mul_i32 s68, s51, s75\n" \
-    "s_add_u32 s53, s53, s68\n" \
-    "s_mov_b32 m0, s69\n" U2PD(137)
+    U2_DEC_H_MUL
 #define U2_DEC_RANK_W \
     U2_DEC_RANK_1W("32") \
     U2_DEC_W_LOAD                                      /* w of the next step's pops: behind the ring write and the s_addc of U2_DEC_MID_W */ \
@@ -1446,7 +1535,7 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 #define U2_DEC_BOT_T_U(RLO, RSPAN)                     /* (U2_DEC_BOT_CORE_T with the rank in one register) */ \
     "s_sub_u32 s68, s60, s61\n"                        /* ring: two pops and one push must fit the next step */ \
     "s_add_u32 s68, s68, " RLO "\n" \
-    "s_add_u32 s69, s69, 1\n" \
+    U2_DEC_T_INC \
     "s_add_u32 s75, s75, 1\n" \
     "s_add_u32 s58, s52, s64\n"                        /* head' = H * nmax + rank */ \
     "s_addc_u32 s59, s53, 0\n" \
@@ -1456,14 +1545,20 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
     "s_cselect_b32 s71, s71, 0\n" U2PD(143) \
     "s_cmp_lt_u32 s69, s71\n"
 #define U2_DEC_BOT_NR_U \
-    "s_add_u32 s69, s69, 1\n" \
+    U2_DEC_T_INC \
     "s_add_u32 s75, s75, 1\n" \
     "s_add_u32 s58, s52, s64\n"                        /* head' = H * nmax + rank */ \
     "s_addc_u32 s59, s53, 0\n" \
     "s_lshr_b64 s[98:99], s[58:59], 31\n"             /* head' < 2^31: the push refills (generic code) */ \
     "s_cselect_b32 s71, s70, 0\n" U2PD(143) \
     "s_cmp_lt_u32 s69, s71\n"
-#if U2_DEC_STEP & 2
+#if U2_DEC_STEP & 4
+#define U2_DEC_TOP_U(LA, LB, LC, LD) U2_DEC_TOP_Q(LA, LB, LC)
+#define U2_DEC_SIDE_U(LA, LB, LC, LD) U2_DEC_SIDE_Q(LA, LB, LC, LD)
+#define U2_DEC_RELOAD_Q "s_sub_u32 s42, s60, 1\n v_readlane_b32 s41, v5, s42\n v_readlane_b32 s62, v10, s69\n"  /* w and lq of the step that runs next */
+#define U2_DEC_ENTRY_U U2_DEC_ENTRY U2_DEC_RELOAD_Q
+#define U2_DEC_OUTER_U(RLO, RSPAN) U2_DEC_OUTER_TR(RLO, RSPAN, U2_DEC_RELOAD_Q)
+#elif U2_DEC_STEP & 2
 #define U2_DEC_TOP_U(LA, LB, LC, LD) U2_DEC_TOP_P(LA, LB)
 #define U2_DEC_SIDE_U(LA, LB, LC, LD) U2_DEC_SIDE_P(LA, LB)
 #define U2_DEC_ENTRY_U U2_DEC_ENTRY U2_DEC_W_IDX U2_DEC_W_LOAD
@@ -1512,7 +1607,9 @@ __global__ void __launch_bounds__(64) k_roc_encode_r2(RocEncArgs a, const U2Div 
 // Ring of the eight-copy loop: a step pops at most two words and pushes at most one, so eight steps are safe while the ring
 // holds U2_DEC_RING_LO .. U2_DEC_RING_HI words when the first copy starts (18 - 16 = 2 words left for the last pops, 53 + 8 = 61
 // before the last push); only the last copy, U2_DEC_OUTER and the C++ glue test it.  (A k_roc_decode_u2 step pops at most one word,
-// U2_DEC_TOP_P: the bound is only more conservative for it.)
+// U2_DEC_TOP_P: the bound is only more conservative for it.  With U2_DEC_STEP bit 2 a quiet step moves sp by 0 where the parent went
+// down one and up one: the extremes over eight steps are the same or closer, so the ring test of the last copy and the exit on
+// head' < 2^31 mean what they meant, only more conservatively.)
 #define U2_DEC_RING_LO 18u
 #define U2_DEC_RING_HI 53u
 #define U2_DEC_SIDE(LA, LB, LC, LD) \
@@ -1709,6 +1806,8 @@ __global__ void __launch_bounds__(64) k_roc_decode_u2(RocDecArgs a, const U2Div 
         st.sp = rfl(st.sp);
         st.lo = rfl(st.lo);
         // clang-format off
+        // (clobbers: s50 and s51 are written only with U2_DEC_STEP bit 2 clear -- U2_DEC_RENORM -- and stay listed so that every value
+        // of U2_DEC_STEP shares one list; the default build leaves them alone)
 #define U2_DEC_IN_W "{v12}"(ins_bit), "{s[54:55]}"(field_ones),  /* (the word-row body's own inputs) */
 #define U2_DEC_ASM(BODY, ...)                                                                                             \
         asm volatile(BODY                                                                                                 \
