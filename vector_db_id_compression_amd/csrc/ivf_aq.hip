@@ -16,9 +16,9 @@
 //     4 t .. 4 t + 3: an entry is accumulated over the components in ascending order, four an instruction, on one accumulator.
 //   * rows are KC + 4 floats apart: 16-byte aligned, and the 16 rows of a fragment read start in distinct bank groups.
 //   * a zero pad adds +0 to the chain, so an entry's bits depend on the query and the codeword alone.
-// k_ivf_scan_aq.  The organisation is k_ivf_scan's: one workgroup = one wavefront = one slot, slots take items (query, piece) in a
-// grid-stride loop, the probe row is de-duplicated as a whole before the cut, a trip takes 64 rows, survivors are inserted by rank, a
-// cut call is merged by k_ivf_merge.  Per item the wavefront copies the query's table (1024 M bytes) from scratch into LDS, 16 bytes
+// k_ivf_scan_aq.  One workgroup = one wavefront = one slot, slots take items (query, piece) in a grid-stride loop; the kernel calls
+// ivf_item_head, ivf_insert_trip and ivf_write_item (csrc/ivf_scan_steps.h), a trip takes 64 rows, and a cut call is merged by
+// k_ivf_merge.  Per item the wavefront copies the query's table (1024 M bytes) from scratch into LDS, 16 bytes
 // a lane and pass, and reduces qn = |xq|^2; per probed list that is not empty it reduces cq = <xq, centroid> (wave_dot: a lane's
 // components lane, lane + 64, ... with fmaf, then a six-step butterfly -- the order depends on d alone).  The trip's rows go
 // through LDS as the aligned 16-byte chunks that cover them (stage_span, ivf_stage.h); a lane walks its M index bytes through the
@@ -30,6 +30,7 @@
 #include "ivf_aq_plan.h"
 #include "ivf_merge.h"
 #include "ivf_scan_ref.h"
+#include "ivf_scan_steps.h"
 #include "ivf_stage.h"
 #include "requests.h"
 #include "wave.h"
@@ -165,19 +166,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_aq(IvAq a) {
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint64_t q = item / a.S;
         const uint32_t s = (uint32_t)(item % a.S);
-        // the head of an item (k_ivf_scan's): the query vector and the probe row to LDS, the row mapped and de-duplicated as a whole
-        for (uint32_t i = lane; i < d; i += 64) qv[i] = a.xq[q * d + i];
-        for (uint32_t j = lane; j < nprobe; j += 64) row[j] = ivs::probe_list(a.probes[q * nprobe + j], a.nlist);
-        __syncthreads();
-        for (uint32_t j0 = 0; j0 < nprobe; j0 += 64) {
-            const uint32_t j = j0 + lane, end = j0 + 64u < nprobe ? j0 + 64u : nprobe;
-            const int32_t mine = j < nprobe ? row[j] : -1;
-            bool dup = false;
-            for (uint32_t i = 0; i < end; i++) dup = dup || (i < j && row[i] == mine);
-            __syncthreads();
-            if (dup && mine >= 0) row[j] = -1;
-            __syncthreads();
-        }
+        ivf_item_head(a.xq, a.probes, a.nlist, q, d, nprobe, lane, qv, row);
         {  // the query's table: built once per query by k_ivf_aq_lut, copied here
             const uint4 *src = (const uint4 *)(a.lut + q * (uint64_t)a.M * iaq::KSUB);
             for (uint32_t e = lane; e < tvec; e += 64) ((uint4 *)table)[e] = src[e];
@@ -204,30 +193,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_aq(IvAq a) {
                 __syncthreads();
                 const float dist = lane < n ? aq_distance(stage, head + lane * a.cs, table, a.M, cq, qn, res) : 0.f;
                 const uint64_t key = lane < n ? ivs::key_make(dist, (uint32_t)(p0 + lane)) : ivs::EMPTY;
-                const bool keep = lane < n && !ivs::key_dropped(key, pool[k - 1u]);
-                const uint64_t keepm = __ballot(keep);
-                const uint32_t C = popc64(keepm);
-                if (C == 0) continue;
-
-                // insert by rank (k_ivf_scan): the survivors among themselves, against the pool, everything into the other array
-                const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-                uint32_t below = 0;
-                for (uint64_t m = keepm; m; m &= m - 1ull) below += ivs::key_less(rl64(klo, khi, ff1(m)), key) ? 1u : 0u;
-                uint32_t pb = 0;
-                if (keep) {
-                    ckey[below] = key;  // the survivors in ascending order
-                    pb = ivs::lower_bound(pool, k, key);
-                }
-                __syncthreads();
-                for (uint32_t t = 0; t < k; t += 64) {
-                    const uint32_t i = t + lane;
-                    if (i < k) {
-                        const uint64_t pk = pool[i];
-                        const uint32_t place = i + ivs::lower_bound(ckey, C, pk);
-                        if (ivs::place_kept(place, k)) other[place] = pk;
-                    }
-                }
-                if (keep && ivs::place_kept(pb + below, k)) other[pb + below] = key;
+                if (!ivf_insert_trip(key, lane < n, pool, other, ckey, k, lane)) continue;
                 uint64_t *t = pool;
                 pool = other;
                 other = t;
@@ -235,23 +201,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_aq(IvAq a) {
             }
         }
 
-        if (a.S == 1) {
-            for (uint32_t i = lane; i < k; i += 64) {
-                const uint64_t ki = pool[i];
-                a.D[q * k + i] = ki == ivs::EMPTY ? __builtin_inff() : ivs::key_dist(ki);
-                a.labels[q * k + i] = ki == ivs::EMPTY ? -1 : ivs::key_label(a.off, a.nlist, ki);
-            }
-            if (a.stats && lane == 0) {
-                a.stats[q * 2] = nlists;
-                a.stats[q * 2 + 1] = ncodes;
-            }
-        } else {
-            for (uint32_t i = lane; i < k; i += 64) a.runs[item * k + i] = pool[i];
-            if (lane == 0) {
-                a.run_stats[item * 2] = nlists;
-                a.run_stats[item * 2 + 1] = ncodes;
-            }
-        }
+        ivf_write_item(pool, k, lane, q, item, a.S, a.off, a.nlist, nlists, ncodes, a.D, a.labels, a.stats, a.runs, a.run_stats);
         __syncthreads();  // (the next item rewrites the pool, the row, the query vector and the table)
     }
 }
@@ -319,8 +269,7 @@ extern "C" int vidc_ivf_scan_aq_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_
     a.lut = s_lut.as<float>(); a.cent = d_centroids; a.nprobe = nprobe; a.k = k;
     a.pool_bytes = (uint32_t)ivx::pool_bytes(k); a.row_bytes = (uint32_t)ivx::row_bytes(nprobe); a.vec_bytes = (uint32_t)ivx::vec_bytes(d);
     a.stage_bytes = (uint32_t)iaq::stage_bytes(M);
-    if (pf.lds > 64u * 1024u)  // (M = 64 with a long probe row or query: above the default cap of a launch)
-        VIDC_HIP(hipFuncSetAttribute((const void *)k_ivf_scan_aq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pf.lds));
+    VIDC_TRY(ivf_lds_cap(k_ivf_scan_aq, pf.lds));  // (M = 64 with a long probe row or query)
     EventTimer t(ctx);
     VIDC_HIP(t.start());
     for (uint64_t c = 0; c < iaq::chunks(nq, M); c++) {
@@ -328,16 +277,9 @@ extern "C" int vidc_ivf_scan_aq_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_
         const iaq::Plan &p = n == first ? pf : pt;
         VIDC_TRY(launch_lut(ctx, d, M, d_codebooks, n, d_xq + q0 * d, s_lut.as<float>()));
         a.nq = n; a.xq = d_xq + q0 * d; a.probes = d_probes + q0 * nprobe; a.S = p.S;
-        a.runs = p.S > 1 ? s_runs.as<uint64_t>() : nullptr;
-        a.run_stats = p.S > 1 ? (uint32_t *)(s_runs.as<uint64_t>() + ivs::scratch_keys(n, p.S, k)) : nullptr;
+        ivf_carve_runs(a, s_runs, n, p.S, k);
         a.D = d_D + q0 * k; a.labels = d_labels + q0 * k; a.stats = d_stats ? d_stats + q0 * 2 : nullptr;
-        hipLaunchKernelGGL(k_ivf_scan_aq, dim3(p.nslots), dim3(64), p.lds, ctx->stream, a);
-        VIDC_HIP(hipGetLastError());
-        if (p.S > 1) {
-            hipLaunchKernelGGL(k_ivf_merge, req_grid(ctx, n, 1), dim3(64), p.merge_lds, ctx->stream, (const uint64_t *)a.runs,
-                               (const uint32_t *)a.run_stats, n, p.S, k, d_offsets, nlist, a.D, a.labels, a.stats);
-            VIDC_HIP(hipGetLastError());
-        }
+        VIDC_TRY(ivf_launch_scan(ctx, k_ivf_scan_aq, p, a));
     }
     VIDC_TRY(t.finish());  // the call's one wait: the tables and the runs go back to the context's cache
     guard.disarm();

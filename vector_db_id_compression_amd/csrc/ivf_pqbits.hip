@@ -2,9 +2,9 @@
 // row is one little-endian bit string of ceil(M * nbits / 8) bytes (PQ8x10: 10 bytes), raw or of (vector - centroids[l]).
 //
 // The rules are the 8-bit scan's (csrc/ivf_scan_ref.h, ivf_merge.h) and are called, not restated; what the host decides, the layout
-// and the table entry are csrc/ivf_pqbits_plan.h.  The organisation is k_ivf_scan's: one workgroup = one wavefront = one slot, slots
-// take items (query, piece) in a grid-stride loop, the probe row is de-duplicated as a whole before the cut, a trip takes 64 codes,
-// survivors are inserted by rank, a cut call is merged by k_ivf_merge.  What is new:
+// and the table entry are csrc/ivf_pqbits_plan.h.  One workgroup = one wavefront = one slot, slots take items (query, piece) in a
+// grid-stride loop; the kernel calls ivf_item_head, ivf_insert_trip and ivf_write_item (csrc/ivf_scan_steps.h), and a cut call is
+// merged by k_ivf_merge.  What is this unit's own:
 //   * the trip's codes go through LDS.  64 consecutive rows are one span of 64 * code_size bytes that starts on no particular
 //     boundary; the wavefront copies the aligned 16-byte chunks that cover it (stage_span), one chunk a lane and pass.  A chunk that
 //     is not wholly inside [d_codes, d_codes + ntotal * code_size) -- only the first and the last of the array can be -- is put
@@ -25,6 +25,7 @@
 #include "ivf_merge.h"
 #include "ivf_pqbits_plan.h"
 #include "ivf_scan_ref.h"
+#include "ivf_scan_steps.h"
 #include "ivf_stage.h"
 #include "requests.h"
 #include "wave.h"
@@ -149,19 +150,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_pqbits(IvBits a) {
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint64_t q = item / a.S;
         const uint32_t s = (uint32_t)(item % a.S);
-        // the head of an item (k_ivf_scan's): the query vector and the probe row to LDS, the row mapped and de-duplicated as a whole
-        for (uint32_t i = lane; i < d; i += 64) qv[i] = a.xq[q * d + i];
-        for (uint32_t j = lane; j < nprobe; j += 64) row[j] = ivs::probe_list(a.probes[q * nprobe + j], a.nlist);
-        __syncthreads();
-        for (uint32_t j0 = 0; j0 < nprobe; j0 += 64) {
-            const uint32_t j = j0 + lane, end = j0 + 64u < nprobe ? j0 + 64u : nprobe;
-            const int32_t mine = j < nprobe ? row[j] : -1;
-            bool dup = false;
-            for (uint32_t i = 0; i < end; i++) dup = dup || (i < j && row[i] == mine);
-            __syncthreads();
-            if (dup && mine >= 0) row[j] = -1;
-            __syncthreads();
-        }
+        ivf_item_head(a.xq, a.probes, a.nlist, q, d, nprobe, lane, qv, row);
         if (!RES) build_table<false>(qv, nullptr, a.cb, d, a.M, a.nbits, a.vec4 != 0, lane, nullptr, table);
         for (uint32_t i = lane; i < k; i += 64) pool[i] = ivs::EMPTY;
         __syncthreads();
@@ -183,30 +172,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_pqbits(IvBits a) {
                 __syncthreads();
                 const float dist = lane < n ? bits_distance(stage, head + lane * a.cs, table, a.M, a.nbits) : 0.f;
                 const uint64_t key = lane < n ? ivs::key_make(dist, (uint32_t)(p0 + lane)) : ivs::EMPTY;
-                const bool keep = lane < n && !ivs::key_dropped(key, pool[k - 1u]);
-                const uint64_t keepm = __ballot(keep);
-                const uint32_t C = popc64(keepm);
-                if (C == 0) continue;
-
-                // insert by rank (k_ivf_scan): the survivors among themselves, against the pool, everything into the other array
-                const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-                uint32_t below = 0;
-                for (uint64_t m = keepm; m; m &= m - 1ull) below += ivs::key_less(rl64(klo, khi, ff1(m)), key) ? 1u : 0u;
-                uint32_t pb = 0;
-                if (keep) {
-                    ckey[below] = key;  // the survivors in ascending order
-                    pb = ivs::lower_bound(pool, k, key);
-                }
-                __syncthreads();
-                for (uint32_t t = 0; t < k; t += 64) {
-                    const uint32_t i = t + lane;
-                    if (i < k) {
-                        const uint64_t pk = pool[i];
-                        const uint32_t place = i + ivs::lower_bound(ckey, C, pk);
-                        if (ivs::place_kept(place, k)) other[place] = pk;
-                    }
-                }
-                if (keep && ivs::place_kept(pb + below, k)) other[pb + below] = key;
+                if (!ivf_insert_trip(key, lane < n, pool, other, ckey, k, lane)) continue;
                 uint64_t *t = pool;
                 pool = other;
                 other = t;
@@ -214,23 +180,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_pqbits(IvBits a) {
             }
         }
 
-        if (a.S == 1) {
-            for (uint32_t i = lane; i < k; i += 64) {
-                const uint64_t ki = pool[i];
-                a.D[q * k + i] = ki == ivs::EMPTY ? __builtin_inff() : ivs::key_dist(ki);
-                a.labels[q * k + i] = ki == ivs::EMPTY ? -1 : ivs::key_label(a.off, a.nlist, ki);
-            }
-            if (a.stats && lane == 0) {
-                a.stats[q * 2] = nlists;
-                a.stats[q * 2 + 1] = ncodes;
-            }
-        } else {
-            for (uint32_t i = lane; i < k; i += 64) a.runs[item * k + i] = pool[i];
-            if (lane == 0) {
-                a.run_stats[item * 2] = nlists;
-                a.run_stats[item * 2 + 1] = ncodes;
-            }
-        }
+        ivf_write_item(pool, k, lane, q, item, a.S, a.off, a.nlist, nlists, ncodes, a.D, a.labels, a.stats, a.runs, a.run_stats);
         __syncthreads();  // (the next item rewrites the pool, the row, the query vector and the table)
     }
 }
@@ -263,21 +213,13 @@ extern "C" int vidc_ivf_scan_pqbits_dev(vidc_ctx *ctx, uint64_t nlist, const uin
     a.probes = d_probes; a.S = p.S; a.vec4 = p.vec4 ? 1u : 0u; a.k = k;
     a.pool_bytes = (uint32_t)ivx::pool_bytes(k); a.row_bytes = (uint32_t)ivx::row_bytes(nprobe); a.vec_bytes = (uint32_t)ivx::vec_bytes(d);
     a.stage_bytes = (uint32_t)ipb::stage_bytes(M, nbits);
-    a.runs = p.S > 1 ? s_runs.as<uint64_t>() : nullptr;
-    a.run_stats = p.S > 1 ? (uint32_t *)(s_runs.as<uint64_t>() + ivs::scratch_keys(nq, p.S, k)) : nullptr;
+    ivf_carve_runs(a, s_runs, nq, p.S, k);
     a.D = d_D; a.labels = d_labels; a.stats = d_stats;
     void (*fn)(IvBits) = res ? k_ivf_scan_pqbits<true> : k_ivf_scan_pqbits<false>;
-    if (p.lds > 64u * 1024u)  // (a table of more than about 15000 entries: above the default cap of a launch)
-        VIDC_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    VIDC_TRY(ivf_lds_cap(fn, p.lds));  // (a table of more than about 15000 entries)
     EventTimer t(ctx);
     VIDC_HIP(t.start());
-    hipLaunchKernelGGL(fn, dim3(p.nslots), dim3(64), p.lds, ctx->stream, a);
-    VIDC_HIP(hipGetLastError());
-    if (p.S > 1) {
-        hipLaunchKernelGGL(k_ivf_merge, req_grid(ctx, nq, 1), dim3(64), p.merge_lds, ctx->stream, (const uint64_t *)a.runs,
-                           (const uint32_t *)a.run_stats, nq, p.S, k, d_offsets, nlist, d_D, d_labels, d_stats);
-        VIDC_HIP(hipGetLastError());
-    }
+    VIDC_TRY(ivf_launch_scan(ctx, fn, p, a));
     VIDC_TRY(t.finish());  // the call's one wait: the runs go back to the context's cache
     guard.disarm();
     return VIDC_OK;

@@ -1,6 +1,7 @@
 // ivf_probe_select.h -- one trip of the selection of vidc_ivf_probe_dev: up to 64 keys, one per lane, into a sorted pool of k keys in
-// LDS.  The step is k_ivf_scan's (drop by ballot, insert by rank) and the rules are those of csrc/ivf_scan_ref.h: key_dropped,
-// lower_bound, place_kept.  k_ivf_probe runs it over the distance tile of a query, k_ivf_probe_merge over the S runs of one.
+// LDS.  The step is that of the scan kernels (drop by ballot, insert by rank), whose workgroup-barrier form is ivf_insert_trip
+// (csrc/ivf_scan_steps.h), and the rules are those of csrc/ivf_scan_ref.h: key_dropped, lower_bound, place_kept.  k_ivf_probe runs
+// it over the distance tile of a query, k_ivf_probe_merge over the S runs of one.
 // Device only.  The caller's wavefront owns pool, other and ckey; nothing here meets another wavefront, so the LDS is ordered by
 // wave_lds_sync and the function may be called where the wavefronts of a workgroup have diverged.
 #pragma once

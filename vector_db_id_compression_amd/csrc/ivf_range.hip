@@ -9,8 +9,8 @@
 //
 // k_ivf_range<KIND, V, FILL>.  One workgroup = one wavefront; wavefronts take items (query, piece) = item / S, item % S in a
 // grid-stride loop, the cut of the scan: a small batch still fills the device, and a PQ table is built once per item.
-//   * the query vector, the de-duplicated probe row and the PQ table sit in LDS (the row is de-duplicated over the WHOLE row before
-//     the piece is cut, as in k_ivf_scan).  No pools.
+//   * the query vector, the de-duplicated probe row and the PQ table sit in LDS (ivf_item_head, csrc/ivf_scan_steps.h, which the scan
+//     kernels call too: the row is de-duplicated over the WHOLE row before the piece is cut).  No pools.
 //   * a slot is entry j of the row; the pieces of a query own disjoint slots, so there is nothing to merge and no run scratch.
 //   * a trip takes 64 codes of the slot's list; the hits are a ballot of dist < radius.
 //     count: the popcount goes to the slot's counter; lane 0 stores the uint32 count when the slot is done, 0 for a slot without
@@ -23,6 +23,7 @@
 #include "ivf_dist.h"
 #include "ivf_range_plan.h"
 #include "ivf_range_ref.h"
+#include "ivf_scan_steps.h"
 #include "scan.h"
 #include "wave.h"
 
@@ -67,19 +68,7 @@ __global__ void __launch_bounds__(64) k_ivf_range(IvRange a) {
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint64_t q = item / a.S;
         const uint32_t s = (uint32_t)(item % a.S);
-        for (uint32_t i = lane; i < d; i += 64) qv[i] = a.xq[q * d + i];
-        for (uint32_t j = lane; j < nprobe; j += 64) row[j] = ivs::probe_list(a.probes[q * nprobe + j], a.nlist);
-        __syncthreads();
-        // the duplicate rule over the whole row, in place (k_ivf_scan's passes)
-        for (uint32_t j0 = 0; j0 < nprobe; j0 += 64) {
-            const uint32_t j = j0 + lane, end = j0 + 64u < nprobe ? j0 + 64u : nprobe;
-            const int32_t mine = j < nprobe ? row[j] : -1;
-            bool dup = false;
-            for (uint32_t i = 0; i < end; i++) dup = dup || (i < j && row[i] == mine);
-            __syncthreads();
-            if (dup && mine >= 0) row[j] = -1;
-            __syncthreads();
-        }
+        ivf_item_head(a.xq, a.probes, a.nlist, q, d, nprobe, lane, qv, row);
         if (KIND == ivs::PQ8) {
             const uint32_t dsub = d / a.M;
             for (uint32_t e = lane; e < a.M * 256u; e += 64) behind[e] = ivs::pq_entry(qv, a.cb, dsub, e >> 8, e & 255u);

@@ -4,10 +4,10 @@
 //
 // The rules are csrc/ivf_residual_ref.h (and through it ivf_scan_ref.h / ivf_range_ref.h), which these kernels call and
 // tests/ivf_residual_test.cpp runs serially; what the host decides is csrc/ivf_residual_plan.h; tests/ivf_residual_ref.py is the
-// statement of the result.  The organisation is k_ivf_scan's and k_ivf_range's (ivf_scan.hip, ivf_range.hip): one workgroup = one
-// wavefront = one slot, slots take items (query, piece) in a grid-stride loop, the probe row is de-duplicated as a whole before the
-// cut, a trip takes 64 codes, survivors are inserted by rank, a cut call is merged by k_ivf_merge (ivf_merge.h), the range search
-// counts, scans the counts on the device and fills.  What is new sits in front of each probed list:
+// statement of the result.  One workgroup = one wavefront = one slot, slots take items (query, piece) in a grid-stride loop.  Both
+// kernels call ivf_item_head; k_ivf_scan_residual calls ivf_insert_trip and ivf_write_item as well (csrc/ivf_scan_steps.h), and its
+// cut call is merged by k_ivf_merge (ivf_merge.h); the range search counts, scans the counts on the device and fills, as
+// k_ivf_range does (ivf_range.hip).  What is this unit's own sits in front of each probed list:
 //   * the query vector stays in LDS for the whole item (it shares no bytes with the pools);
 //   * for a valid list whose clamped range is not empty the wavefront writes r = q - centroids[l] to LDS and builds the list's
 //     M x 256 table from it (residual_table, csrc/ivf_dist.h: the one function scan, count and fill call); an empty list builds nothing;
@@ -20,6 +20,7 @@
 #include "ivf_merge.h"
 #include "ivf_residual_plan.h"
 #include "ivf_residual_ref.h"
+#include "ivf_scan_steps.h"
 #include "requests.h"
 #include "scan.h"
 #include "wave.h"
@@ -56,24 +57,6 @@ struct IvRes {
     int64_t *labels;
 };
 
-// the head of an item, shared: the query vector and the probe row go to LDS, the row is mapped to list numbers (-1: no list) and
-// de-duplicated in place over the WHOLE row (k_ivf_scan's passes).  Ends behind a barrier.
-__device__ __forceinline__ void load_item(const IvRes &a, uint64_t q, uint32_t lane, float *qv, int32_t *row) {
-    const uint32_t d = a.d, nprobe = a.nprobe;
-    for (uint32_t i = lane; i < d; i += 64) qv[i] = a.xq[q * d + i];
-    for (uint32_t j = lane; j < nprobe; j += 64) row[j] = ivs::probe_list(a.probes[q * nprobe + j], a.nlist);
-    __syncthreads();
-    for (uint32_t j0 = 0; j0 < nprobe; j0 += 64) {
-        const uint32_t j = j0 + lane, end = j0 + 64u < nprobe ? j0 + 64u : nprobe;
-        const int32_t mine = j < nprobe ? row[j] : -1;
-        bool dup = false;
-        for (uint32_t i = 0; i < end; i++) dup = dup || (i < j && row[i] == mine);
-        __syncthreads();
-        if (dup && mine >= 0) row[j] = -1;
-        __syncthreads();
-    }
-}
-
 template <int W>
 __global__ void __launch_bounds__(64) k_ivf_scan_residual(IvRes a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];  // the layout of ivx::scan_lds_bytes
@@ -88,7 +71,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_residual(IvRes a) {
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint64_t q = item / a.S;
         const uint32_t s = (uint32_t)(item % a.S);
-        load_item(a, q, lane, qv, row);
+        ivf_item_head(a.xq, a.probes, a.nlist, q, d, nprobe, lane, qv, row);
         for (uint32_t i = lane; i < k; i += 64) pool[i] = ivs::EMPTY;
         __syncthreads();
 
@@ -106,30 +89,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_residual(IvRes a) {
                 const uint32_t n = rb - p0 < ivs::TRIP ? (uint32_t)(rb - p0) : ivs::TRIP;
                 const float dist = ivf_trip_distance<ivs::PQ8, W>(a.codes, p0, n, lane, d, a.M, qv, table, nullptr, 1u, 0u);
                 const uint64_t key = lane < n ? ivs::key_make(dist, (uint32_t)(p0 + lane)) : ivs::EMPTY;
-                const bool keep = lane < n && !ivs::key_dropped(key, pool[k - 1u]);
-                const uint64_t keepm = __ballot(keep);
-                const uint32_t C = popc64(keepm);
-                if (C == 0) continue;
-
-                // insert by rank (k_ivf_scan): the survivors among themselves, against the pool, everything into the other array
-                const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-                uint32_t below = 0;
-                for (uint64_t m = keepm; m; m &= m - 1ull) below += ivs::key_less(rl64(klo, khi, ff1(m)), key) ? 1u : 0u;
-                uint32_t pb = 0;
-                if (keep) {
-                    ckey[below] = key;  // the survivors in ascending order
-                    pb = ivs::lower_bound(pool, k, key);
-                }
-                __syncthreads();
-                for (uint32_t t = 0; t < k; t += 64) {
-                    const uint32_t i = t + lane;
-                    if (i < k) {
-                        const uint64_t pk = pool[i];
-                        const uint32_t place = i + ivs::lower_bound(ckey, C, pk);
-                        if (ivs::place_kept(place, k)) other[place] = pk;
-                    }
-                }
-                if (keep && ivs::place_kept(pb + below, k)) other[pb + below] = key;
+                if (!ivf_insert_trip(key, lane < n, pool, other, ckey, k, lane)) continue;
                 uint64_t *t = pool;
                 pool = other;
                 other = t;
@@ -137,23 +97,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan_residual(IvRes a) {
             }
         }
 
-        if (a.S == 1) {
-            for (uint32_t i = lane; i < k; i += 64) {
-                const uint64_t ki = pool[i];
-                a.D[q * k + i] = ki == ivs::EMPTY ? __builtin_inff() : ivs::key_dist(ki);
-                a.labels[q * k + i] = ki == ivs::EMPTY ? -1 : ivs::key_label(a.off, a.nlist, ki);
-            }
-            if (a.stats && lane == 0) {
-                a.stats[q * 2] = nlists;
-                a.stats[q * 2 + 1] = ncodes;
-            }
-        } else {
-            for (uint32_t i = lane; i < k; i += 64) a.runs[item * k + i] = pool[i];
-            if (lane == 0) {
-                a.run_stats[item * 2] = nlists;
-                a.run_stats[item * 2 + 1] = ncodes;
-            }
-        }
+        ivf_write_item(pool, k, lane, q, item, a.S, a.off, a.nlist, nlists, ncodes, a.D, a.labels, a.stats, a.runs, a.run_stats);
         __syncthreads();  // (the next item rewrites the pool, the row and the query vector)
     }
 }
@@ -171,7 +115,7 @@ __global__ void __launch_bounds__(64) k_ivf_range_residual(IvRes a) {
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint64_t q = item / a.S;
         const uint32_t s = (uint32_t)(item % a.S);
-        load_item(a, q, lane, qv, row);
+        ivf_item_head(a.xq, a.probes, a.nlist, q, d, nprobe, lane, qv, row);
 
         const uint32_t jb = ivs::piece_begin(nprobe, a.S, s), je = ivs::piece_begin(nprobe, a.S, s + 1u);
         for (uint32_t j = jb; j < je; j++) {
@@ -271,17 +215,13 @@ extern "C" int vidc_ivf_scan_residual_dev(vidc_ctx *ctx, uint64_t nlist, const u
     IvRes a = common_args(args, p);
     a.pool_bytes = (uint32_t)ivx::pool_bytes(k);
     a.k = k;
-    a.runs = p.S > 1 ? s_runs.as<uint64_t>() : nullptr;
-    a.run_stats = p.S > 1 ? (uint32_t *)(s_runs.as<uint64_t>() + ivs::scratch_keys(nq, p.S, k)) : nullptr;
+    ivf_carve_runs(a, s_runs, nq, p.S, k);
     a.D = d_D; a.labels = d_labels; a.stats = d_stats;
+    const ResKernel fn = scan_kernel(p.W);
     EventTimer t(ctx);
     VIDC_HIP(t.start());
-    VIDC_TRY(launch(ctx, scan_kernel(p.W), p, a));
-    if (p.S > 1) {
-        hipLaunchKernelGGL(k_ivf_merge, req_grid(ctx, nq, 1), dim3(64), p.merge_lds, ctx->stream, (const uint64_t *)a.runs,
-                           (const uint32_t *)a.run_stats, nq, p.S, k, d_offsets, nlist, d_D, d_labels, d_stats);
-        VIDC_HIP(hipGetLastError());
-    }
+    VIDC_TRY(ivf_lds_cap(fn, p.lds));  // (a table of about 48 sub-quantisers and more)
+    VIDC_TRY(ivf_launch_scan(ctx, fn, p, a));
     VIDC_TRY(t.finish());  // the call's one wait: the runs go back to the context's cache
     guard.disarm();
     return VIDC_OK;

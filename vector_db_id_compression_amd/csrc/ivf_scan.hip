@@ -6,17 +6,18 @@
 // cut S, scratch, LDS, lane grouping, load width) is csrc/ivf_scan_plan.h.  tests/ivf_scan_ref.py is the statement of the result.
 //
 // k_ivf_scan.  One workgroup = one wavefront = one SLOT; slots take items (query, piece) = item / S, item % S in a grid-stride loop.
-//   * the query vector and the probe row sit in LDS.  The row is mapped to list numbers (-1: no list) and de-duplicated in place over
-//     the WHOLE row, 64 entries a pass: lane j compares its entry with every entry in front of it (uniform trip count); the piece
-//     [piece_begin(s), piece_begin(s + 1)) is cut afterwards.
+// The three steps every scan kernel takes are csrc/ivf_scan_steps.h, called here and by the kernels of ivf_residual.hip,
+// ivf_pqbits.hip and ivf_aq.hip:
+//   * ivf_item_head: the query vector and the probe row sit in LDS.  The row is mapped to list numbers (-1: no list) and
+//     de-duplicated in place over the WHOLE row; the piece [piece_begin(s), piece_begin(s + 1)) is cut afterwards.
 //   * a trip takes 64 codes of a list, whose range was clamped to a <= b <= ntotal, and gives one distance per lane
 //     (csrc/ivf_dist.h, shared with ivf_range.hip: the FLAT G-lane butterfly, the PQ8 table walk).  PQ8: the wavefront builds the
 //     query's M x 256 table in LDS once per item.
-//   * a candidate whose key is not below the pool's last key is dropped by a ballot; the survivors are ranked among themselves by
-//     lane reads, against the pool by binary search, and every element is stored at its place in the other pool array.  No private
-//     arrays.
-//   * S == 1: the wavefront writes D and the labels itself.  S > 1: it writes its k keys and two counters to context scratch, and
-//     k_ivf_merge, a wavefront per query, merges the S sorted runs by rank.
+//   * ivf_insert_trip: a candidate whose key is not below the pool's last key is dropped by a ballot; the survivors are inserted by
+//     rank into the other pool array.  No private arrays.
+//   * ivf_write_item.  S == 1: the wavefront writes D and the labels itself.  S > 1: it writes its k keys and two counters to
+//     context scratch, and k_ivf_merge, a wavefront per query, merges the S sorted runs by rank (csrc/ivf_merge.h, with the host
+//     tail of the four scan entry points).
 // Every loop that holds a cross-lane operation has a wavefront-uniform trip count.  Nothing spins and no wavefront waits for another.
 #include "common.h"
 #include "host_call.h"
@@ -24,6 +25,7 @@
 #include "ivf_merge.h"
 #include "ivf_scan_plan.h"
 #include "ivf_scan_ref.h"
+#include "ivf_scan_steps.h"
 #include "requests.h"
 #include "wave.h"
 
@@ -69,20 +71,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan(IvScan a) {
     for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const uint64_t q = item / a.S;
         const uint32_t s = (uint32_t)(item % a.S);
-        for (uint32_t i = lane; i < d; i += 64) qv[i] = a.xq[q * d + i];
-        for (uint32_t j = lane; j < nprobe; j += 64) row[j] = ivs::probe_list(a.probes[q * nprobe + j], a.nlist);
-        __syncthreads();
-        // the duplicate rule over the whole row, in place: a pass clears the later mentions among its 64 entries, so every pass
-        // behind it still finds the first one
-        for (uint32_t j0 = 0; j0 < nprobe; j0 += 64) {
-            const uint32_t j = j0 + lane, end = j0 + 64u < nprobe ? j0 + 64u : nprobe;
-            const int32_t mine = j < nprobe ? row[j] : -1;
-            bool dup = false;
-            for (uint32_t i = 0; i < end; i++) dup = dup || (i < j && row[i] == mine);
-            __syncthreads();
-            if (dup && mine >= 0) row[j] = -1;
-            __syncthreads();
-        }
+        ivf_item_head(a.xq, a.probes, a.nlist, q, d, nprobe, lane, qv, row);
         if (KIND == ivs::PQ8) {
             float *tw = behind;
             const uint32_t dsub = d / a.M;
@@ -105,30 +94,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan(IvScan a) {
                 const uint32_t n = rb - p0 < ivs::TRIP ? (uint32_t)(rb - p0) : ivs::TRIP;
                 const float dist = ivf_trip_distance<KIND, V>(a.codes, p0, n, lane, d, a.M, qv, table, cdist, G, logG);
                 const uint64_t key = lane < n ? ivs::key_make(dist, (uint32_t)(p0 + lane)) : ivs::EMPTY;
-                const bool keep = lane < n && !ivs::key_dropped(key, pool[k - 1u]);
-                const uint64_t keepm = __ballot(keep);
-                const uint32_t C = popc64(keepm);
-                if (C == 0) continue;
-
-                // insert by rank: the survivors among themselves, against the pool, everything into the other array
-                const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-                uint32_t below = 0;
-                for (uint64_t m = keepm; m; m &= m - 1ull) below += ivs::key_less(rl64(klo, khi, ff1(m)), key) ? 1u : 0u;
-                uint32_t pb = 0;
-                if (keep) {
-                    ckey[below] = key;  // the survivors in ascending order
-                    pb = ivs::lower_bound(pool, k, key);
-                }
-                __syncthreads();
-                for (uint32_t t = 0; t < k; t += 64) {
-                    const uint32_t i = t + lane;
-                    if (i < k) {
-                        const uint64_t pk = pool[i];
-                        const uint32_t place = i + ivs::lower_bound(ckey, C, pk);
-                        if (ivs::place_kept(place, k)) other[place] = pk;
-                    }
-                }
-                if (keep && ivs::place_kept(pb + below, k)) other[pb + below] = key;
+                if (!ivf_insert_trip(key, lane < n, pool, other, ckey, k, lane)) continue;
                 uint64_t *t = pool;
                 pool = other;
                 other = t;
@@ -136,23 +102,7 @@ __global__ void __launch_bounds__(64) k_ivf_scan(IvScan a) {
             }
         }
 
-        if (a.S == 1) {
-            for (uint32_t i = lane; i < k; i += 64) {
-                const uint64_t ki = pool[i];
-                a.D[q * k + i] = ki == ivs::EMPTY ? __builtin_inff() : ivs::key_dist(ki);
-                a.labels[q * k + i] = ki == ivs::EMPTY ? -1 : ivs::key_label(a.off, a.nlist, ki);
-            }
-            if (a.stats && lane == 0) {
-                a.stats[q * 2] = nlists;
-                a.stats[q * 2 + 1] = ncodes;
-            }
-        } else {
-            for (uint32_t i = lane; i < k; i += 64) a.runs[item * k + i] = pool[i];
-            if (lane == 0) {
-                a.run_stats[item * 2] = nlists;
-                a.run_stats[item * 2 + 1] = ncodes;
-            }
-        }
+        ivf_write_item(pool, k, lane, q, item, a.S, a.off, a.nlist, nlists, ncodes, a.D, a.labels, a.stats, a.runs, a.run_stats);
         __syncthreads();  // (the next item rewrites the pool, the row and the query vector)
     }
 }
@@ -198,21 +148,13 @@ extern "C" int vidc_ivf_scan_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *
     const size_t pools = (size_t)2 * k * 8 + (size_t)ivs::TRIP * 12, qbytes = ivs::round16((size_t)d * 4);
     a.head_bytes = (uint32_t)(code_kind == ivs::PQ8 && qbytes > pools ? qbytes : pools);
     a.row_bytes = (uint32_t)ivs::round16((size_t)nprobe * 4);
-    a.runs = p.S > 1 ? s_runs.as<uint64_t>() : nullptr;
-    a.run_stats = p.S > 1 ? (uint32_t *)(s_runs.as<uint64_t>() + ivs::scratch_keys(nq, p.S, k)) : nullptr;
+    ivf_carve_runs(a, s_runs, nq, p.S, k);
     a.D = d_D; a.labels = d_labels; a.stats = d_stats;
     const ScanKernel fn = scan_kernel(code_kind, p);
-    if (p.lds > 64u * 1024u)  // (a PQ table of more than 48 sub-quantisers: above the default cap of a launch)
-        VIDC_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    VIDC_TRY(ivf_lds_cap(fn, p.lds));  // (a PQ table of more than 48 sub-quantisers)
     EventTimer t(ctx);
     VIDC_HIP(t.start());
-    hipLaunchKernelGGL(fn, dim3(p.nslots), dim3(64), p.lds, ctx->stream, a);
-    VIDC_HIP(hipGetLastError());
-    if (p.S > 1) {
-        hipLaunchKernelGGL(k_ivf_merge, req_grid(ctx, nq, 1), dim3(64), p.merge_lds, ctx->stream, (const uint64_t *)a.runs,
-                           (const uint32_t *)a.run_stats, nq, p.S, k, d_offsets, nlist, d_D, d_labels, d_stats);
-        VIDC_HIP(hipGetLastError());
-    }
+    VIDC_TRY(ivf_launch_scan(ctx, fn, p, a));
     VIDC_TRY(t.finish());  // the call's one wait: the runs go back to the context's cache
     guard.disarm();
     return VIDC_OK;
