@@ -1035,6 +1035,36 @@ int vidc_ivf_scan_aq_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offset
                          uint32_t M, const float *d_codebooks, const float *d_centroids, uint64_t nq, const float *d_xq, uint32_t nprobe,
                          const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
 
+/* ---------------------------------------------------- short lists of up to 2048 results: the wide IVF scan */
+/* The top-k scans above for 1 <= k <= 2048 (a re-ranker's short list: nshort = 10 .. 1000 in search_ivf_qinco.py; Faiss's GPU scanners
+ * go to 2048).  The calls above stop at k = 256 and keep doing so: their pool is rewritten on every trip that keeps a candidate.
+ *
+ * vidc_ivf_scan_wide_dev takes the arguments of the 8-bit top-k call (code_kind VIDC_IVF_FLAT or VIDC_IVF_PQ8),
+ * vidc_ivf_scan_aq_wide_dev those of vidc_ivf_scan_aq_dev, with the same arrays, semantics, bounds, d_stats and residency.  The result
+ *   is the same bytes as the narrow call's wherever both accept k: the distances come from the same per-trip code, keys of a query are
+ *   distinct, and the first k keys ascending are one set in one order, whatever the cut, the context or the interleaving of wavefronts.
+ * Status.  Every refusal of the narrow call except k's, which is 1 <= k <= 2048; VIDC_ERR_INVALID before any device work, nothing
+ *   written, the error text names the "wide scan".  nq == 0: VIDC_OK, no array is touched.
+ * What runs.  k_ivf_scan_wide: a workgroup of 256 threads (four wavefronts) per (query, piece).  A list is walked in rounds of 256
+ *   codes, a trip of 64 per wavefront.  A candidate that is not below the pool's k-th key (read at the start of the round) is dropped;
+ *   the others go unsorted into the wavefront's own quarter of an LDS buffer (ballot and prefix rank, no atomics).  When a quarter
+ *   could not take 64 more keys, and at the end of the item, the workgroup sorts the buffer with a bitonic network and merges it into
+ *   the sorted pool: new[i] = min(pool[i], buffer[K2 - 1 - i]), then log2(K2) half-cleaner steps.  K2 is the power of two >= k, at
+ *   least 512; the buffer holds max(1024, K2) keys.  The cut S is the narrow rule over this kernel's residency, compute units x
+ *   min(8, 160 KiB / LDS); with S > 1 k_ivf_merge_wide, a workgroup per query, merges run after run into run 0 with the same merge
+ *   step, two runs in LDS at a time.  The additive-quantiser call keeps its table chunks (one k_ivf_aq_lut launch per chunk).
+ * LDS.  8 (K2 + buffer) + 64 + round16(4 nprobe) + round16(4 d), and FLAT: 1024; PQ8: 1024 M; additive: 4 round16(64 code_size + 32)
+ *   + 1024 M bytes.  12 KiB of pool and buffer at k = 257, 32 KiB at k = 2048; 128192 bytes at the additive limits.
+ * Scratch.  None with S == 1, else nq * S * (k + 1) * 8 bytes from the context's block cache; the additive call's tables as above.
+ * Not here.  Wide forms of the residual-PQ8 and packed-bit scans, range search, return_codes, re-ranking, k above 2048, inner
+ *   product, the Faiss adapter. */
+int vidc_ivf_scan_wide_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes, int code_kind,
+                           uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, uint32_t nprobe,
+                           const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
+int vidc_ivf_scan_aq_wide_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_t *d_offsets, uint64_t ntotal, const uint8_t *d_codes, uint32_t d,
+                              uint32_t M, const float *d_codebooks, const float *d_centroids, uint64_t nq, const float *d_xq,
+                              uint32_t nprobe, const int64_t *d_probes, uint32_t k, float *d_D, int64_t *d_labels, uint32_t *d_stats);
+
 /* ---------------------------------------------------- update rows (graph objects, device-resident) */
 /* What an NSG / HNSW-style insert does to its adjacency -- rows for the new nodes, rewritten rows for the neighbours that gained a
  * back-edge -- without re-encoding the graph.  Objects stay immutable: the call returns a NEW object in *out that owns all of its

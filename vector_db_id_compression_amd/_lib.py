@@ -202,6 +202,9 @@ def _declare(lib):
     # ctx, nlist, offsets, ntotal, codes, d, M, codebooks, centroids (None: raw), nq, xq, nprobe, probes, k, D, labels, stats
     f("vidc_ivf_aq_lut_dev", C.c_int, _vp, _u32, _u32, _vp, _u64, _vp, _vp)
     f("vidc_ivf_scan_aq_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _vp)
+    # the wide scans (1 <= k <= 2048): the arguments of vidc_ivf_scan_dev and of vidc_ivf_scan_aq_dev
+    f("vidc_ivf_scan_wide_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, C.c_int, _u32, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _vp)
+    f("vidc_ivf_scan_aq_wide_dev", C.c_int, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _vp)
     # update rows (graph objects, device-resident)
     f("vidc_compact_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
     f("vidc_ef_update_rows_dev", C.c_int, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _vp)
@@ -277,7 +280,7 @@ EXPORTED_SYMBOLS = [
     "vidc_ivf_range_count_dev", "vidc_ivf_range_fill_dev",
     "vidc_ivf_scan_residual_dev", "vidc_ivf_range_count_residual_dev", "vidc_ivf_range_fill_residual_dev", "vidc_ivf_probe_dev",
     "vidc_ivf_pq_encode_dev", "vidc_ivf_kmeans_step_dev", "vidc_ivf_pq_encode_bits_dev", "vidc_ivf_scan_pqbits_dev",
-    "vidc_ivf_aq_lut_dev", "vidc_ivf_scan_aq_dev",
+    "vidc_ivf_aq_lut_dev", "vidc_ivf_scan_aq_dev", "vidc_ivf_scan_wide_dev", "vidc_ivf_scan_aq_wide_dev",
     "vidc_wt_type", "vidc_wt_image_words", "vidc_wt_export_all", "vidc_wt_import", "vidc_compact_export_all", "vidc_compact_import",
     "vidc_shards_encode", "vidc_shards_encode_dev", "vidc_shards_destroy", "vidc_shards_count", "vidc_shards_kind", "vidc_shards_nlist",
     "vidc_shards_ntotal", "vidc_shards_compressed_bytes", "vidc_shards_map", "vidc_shards_offsets", "vidc_shards_shard",

@@ -27,6 +27,7 @@
 // workgroup waits for another.
 #include "common.h"
 #include "host_call.h"
+#include "ivf_aq_dist.h"
 #include "ivf_aq_plan.h"
 #include "ivf_merge.h"
 #include "ivf_scan_ref.h"
@@ -131,25 +132,7 @@ struct IvAq {
     uint32_t *stats;
 };
 
-// <x, y> over d components, the same bits in every lane: lane l sums the components l, l + 64, ... in order with fmaf, then the
-// lanes meet in a butterfly (a + b == b + a, so both sides of a step hold the same sum).  The order depends on d alone.
-__device__ __forceinline__ float wave_dot(const float *x, const float *y, uint32_t d, uint32_t lane) {
-    float s = 0.f;
-    for (uint32_t i = lane; i < d; i += 64) s = __builtin_fmaf(x[i], y[i], s);
-#pragma unroll
-    for (uint32_t o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
-}
-
-// the distance of the code row that starts at stage byte rs (iaq::distance): the M table entries added in m order, the norm from the
-// four bytes behind the indices through two aligned words
-__device__ __forceinline__ float aq_distance(const uint32_t *stage, uint32_t rs, const float *table, uint32_t M, float cq, float qn, bool res) {
-    const float t = iaq::table_sum((const uint8_t *)stage + rs, M, table);
-    const uint32_t o = rs + M, wi = o >> 2, sh = (o & 3u) * 8u;
-    const uint64_t win = (uint64_t)stage[wi] | ((uint64_t)stage[wi + 1u] << 32);
-    const float n = ivs::bits_f32((uint32_t)(win >> sh));
-    return iaq::finish(t, n, cq, qn, res);
-}
+// wave_dot and aq_distance: csrc/ivf_aq_dist.h (the wide scan of ivf_wide.hip calls them too)
 
 __global__ void __launch_bounds__(64) k_ivf_scan_aq(IvAq a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];  // the layout of iaq::lds_bytes
@@ -206,8 +189,10 @@ __global__ void __launch_bounds__(64) k_ivf_scan_aq(IvAq a) {
     }
 }
 
+}  // namespace
+
 // the tables of nq queries into lut, on the context's stream
-int launch_lut(vidc_ctx *ctx, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, float *lut) {
+int vidc::ivf_aq_launch_lut(vidc_ctx *ctx, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, float *lut) {
     AqLut a = {};
     a.cb = d_codebooks; a.xq = d_xq; a.lut = lut; a.nq = nq; a.d = d; a.M = M;
     a.ctiles = (uint32_t)iaq::lut_col_tiles(M);
@@ -216,8 +201,6 @@ int launch_lut(vidc_ctx *ctx, uint32_t d, uint32_t M, const float *d_codebooks, 
     VIDC_HIP(hipGetLastError());
     return VIDC_OK;
 }
-
-}  // namespace
 
 extern "C" int vidc_ivf_aq_lut_dev(vidc_ctx *ctx, uint32_t d, uint32_t M, const float *d_codebooks, uint64_t nq, const float *d_xq, float *d_lut) {
     if (!ctx) {
@@ -234,7 +217,7 @@ extern "C" int vidc_ivf_aq_lut_dev(vidc_ctx *ctx, uint32_t d, uint32_t M, const 
     StreamGuard guard(ctx);
     EventTimer t(ctx);
     VIDC_HIP(t.start());
-    VIDC_TRY(launch_lut(ctx, d, M, d_codebooks, nq, d_xq, d_lut));
+    VIDC_TRY(ivf_aq_launch_lut(ctx, d, M, d_codebooks, nq, d_xq, d_lut));
     VIDC_TRY(t.finish());  // the call's one wait
     guard.disarm();
     return VIDC_OK;
@@ -275,7 +258,7 @@ extern "C" int vidc_ivf_scan_aq_dev(vidc_ctx *ctx, uint64_t nlist, const uint64_
     for (uint64_t c = 0; c < iaq::chunks(nq, M); c++) {
         const uint64_t q0 = c * chunk, n = nq - q0 < chunk ? nq - q0 : chunk;
         const iaq::Plan &p = n == first ? pf : pt;
-        VIDC_TRY(launch_lut(ctx, d, M, d_codebooks, n, d_xq + q0 * d, s_lut.as<float>()));
+        VIDC_TRY(ivf_aq_launch_lut(ctx, d, M, d_codebooks, n, d_xq + q0 * d, s_lut.as<float>()));
         a.nq = n; a.xq = d_xq + q0 * d; a.probes = d_probes + q0 * nprobe; a.S = p.S;
         ivf_carve_runs(a, s_runs, n, p.S, k);
         a.D = d_D + q0 * k; a.labels = d_labels + q0 * k; a.stats = d_stats ? d_stats + q0 * 2 : nullptr;

@@ -17,6 +17,9 @@ import numpy as np
 from .invlists import ArrayInvertedLists, to_csr
 
 
+NARROW_K = 256  # the largest k of the narrow scan kernels (ivs::MAX_K); above it "Flat", raw ("PQ", M) and ("RQ", M) scan wide
+
+
 def _torch():
     import torch
 
@@ -407,7 +410,8 @@ class IVFIndex:
         numbers, used as it is (-1 = no list); None picks them on the device with the cdist + topk of _scan.  Works over the codes of
         a compressed container and of ArrayInvertedLists, for "Flat" and ("PQ", M), raw or by_residual (the latter through
         vidc_ivf_scan_residual_dev), for ("PQ", M, nbits) through vidc_ivf_scan_pqbits_dev and for ("RQ", M) through
-        vidc_ivf_scan_aq_dev.  Runs on torch's current stream."""
+        vidc_ivf_scan_aq_dev.  k > 256 (to 2048) goes to the wide calls vidc_ivf_scan_wide_dev / vidc_ivf_scan_aq_wide_dev for "Flat", raw
+        ("PQ", M) and ("RQ", M); the other forms refuse it.  Runs on torch's current stream."""
         from . import _lib
 
         torch = _torch()
@@ -452,7 +456,9 @@ class IVFIndex:
                 nq, ptr(xq) if nq else None, int(probes.shape[1]), ptr(probes) if probes.numel() else None, k,
                 ptr(D) if D.numel() else None, ptr(labels) if labels.numel() else None, None))
             return D, labels
-        _lib.check(_lib.lib().vidc_ivf_scan_dev(
+        # a short list of more than NARROW_K results goes to the wide kernels (vidc_ivf_scan_wide_dev: 1 <= k <= 2048)
+        call = _lib.lib().vidc_ivf_scan_wide_dev if k > NARROW_K else _lib.lib().vidc_ivf_scan_dev
+        _lib.check(call(
             ctx.h, self.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None,
             _lib.VIDC_IVF_PQ8 if self.M else _lib.VIDC_IVF_FLAT, self.d, self.M, ptr(pq) if self.M else None, nq, ptr(xq) if nq else None,
             int(probes.shape[1]), ptr(probes) if probes.numel() else None, k, ptr(D) if D.numel() else None,

@@ -88,7 +88,10 @@ def scan_device(index, xq, probes, k, off, codes):
     labels = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
     cb = index.pq.to(torch.float32).contiguous()
     cent = index.centroids.to(torch.float32).contiguous() if index.by_residual else None
-    check(lib().vidc_ivf_scan_aq_dev(
+    from .ivf import NARROW_K
+
+    call = lib().vidc_ivf_scan_aq_wide_dev if k > NARROW_K else lib().vidc_ivf_scan_aq_dev  # (wide: 1 <= k <= 2048)
+    check(call(
         default_context().h, index.nlist, ptr(off), int(codes.shape[0]), ptr(codes) if codes.numel() else None, index.d, index.M, ptr(cb),
         ptr(cent) if index.by_residual else None, nq, ptr(xq) if nq else None, int(probes.shape[1]),
         ptr(probes) if probes.numel() else None, k, ptr(D) if D.numel() else None, ptr(labels) if labels.numel() else None, None))
